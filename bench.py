@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Msamples/s (pixels x spp / s) of the per-pixel render loop on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2] [--spp S]
+    python bench.py --gpus N --steps K --warmup W [--config C2] [--spp S] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch: `spp` samples per pixel of the configured frame (default
 BASELINE.json configs[1]: Cornell box, 1280x720, 8 bounces, 256 spp), i.e. 256 RenderFrame() calls as one trace_kernel +
@@ -89,7 +89,13 @@ def parse_args(argv=None):
     ap.add_argument("--wall-limit", type=float, default=540.0, help="N > 1, self-launched: the parent ends the ranks after this many seconds")
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="N > 1: rendezvous + barrier only, no GPU work - exercises the launcher's failure handling (tests)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the headline render returns to its caller (the float accumulator - at "
+                         "N > 1 the image gathered on rank 0 - and, at N = 1, the 8-bit frame) as DIR/<name>.npy, float32, <= 64 MB")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 T_START = time.time()
@@ -253,6 +259,26 @@ def cpu_baseline(scene, name: str, budget_s: float = 8.0):
         out["reference_recipe_sha256"] = modes["reference"]["recipe_sha256"]
     out["reference_missing"] = "reference" not in modes
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write each [H, W, C] array as out_dir/<name>.npy in float32.  Should they exceed DUMP_LIMIT_BYTES together, the same
+    fixed, seeded sample of pixels is taken from every array ([k, C]) and its flat pixel indices go to pixel_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        first = next(iter(arrays.values()))
+        pixels = first.shape[0] * first.shape[1]
+        k = min(pixels, DUMP_LIMIT_BYTES // (total // pixels + 8))          # (+ 8 bytes per pixel for its float64 index)
+        idx = np.sort(np.random.default_rng(12345).choice(pixels, size=k, replace=False))
+        arrays = {n: a.reshape(pixels, -1)[idx] for n, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def parity_check(pt, ctx, scene, W, H, D, spp, seed, levels):
@@ -488,6 +514,15 @@ def measure(name: str, args, rank: int, world: int, local_rank: int, steps: int,
                   f"exchange mode {exchange.mode}, {timed_exchanges} exchanges in the timed region", file=sys.stderr)
             if not ok:
                 sys.exit(5)
+    # ---- what the timed steps returned, before anything else renders into the accumulator (rank 0) -------------------
+    if headline and args.dump_outputs and rank == 0:
+        if world > 1:
+            got = exchange.result()
+            got = got.cpu().numpy() if hasattr(got, "cpu") else np.asarray(got)
+            outputs = {"accum": got.reshape(H, W, 3)}
+        else:
+            outputs = {"accum": ctx.read_accum(), "rgb8": ctx.resolve_rgb8()}
+        dump_outputs(args.dump_outputs, outputs)
 
     # ---- the contracted build of the trace kernels on the same steps (every rank; value stays the exact build's) ----
     contracted = None

@@ -87,6 +87,9 @@ struct ptk_ctx {
     std::atomic<uint32_t> render_gen{ 1 };       // generation of the newest render: Exit() names it and thereby every render still in flight (kernels stand down
                                                  // when the named generation >= their own); renders issued afterwards are not affected
     uint32_t* d_exit = nullptr;
+    uint32_t* h_exit = nullptr;                  // page-locked source of the copy that writes d_exit (ptk_request_exit)
+    hipStream_t exit_stream = nullptr;           // high priority, nothing else on it: the copy of the Exit() word never waits behind a render
+    std::mutex exit_mu;                          // (Exit() may come from several threads: the source word never goes back)
     unsigned long long* d_stats = nullptr;
     unsigned* d_queues = nullptr;                // item queues of trace_kernel's persistent waves
     // live-quadrant list (which 8x8 quadrants of the owned tiles have pixels to trace) and what it was built for
@@ -557,12 +560,14 @@ int ptk_create(ptk_ctx** out, int device_ordinal)
         if (cus > 0) c->num_cus = cus;
     }
     if (hipMalloc(&c->d_exit, sizeof(uint32_t)) != hipSuccess || hipMemset(c->d_exit, 0, sizeof(uint32_t)) != hipSuccess ||
+        hipHostMalloc((void**)&c->h_exit, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
         hipMalloc(&c->d_stats, 16 * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc(&c->d_queues, PTK_QUEUE_BLOCK_BYTES) != hipSuccess)
     {
         ptk_destroy(c);
         return PTK_ERR_HIP;
     }
+    *c->h_exit = 0;
     for (int i = 0; i < ptk_ctx::kMaxTimedPasses; i++)
         for (int k = 0; k < 3; k++)
             if (hipEventCreate(&c->ev[i][k]) != hipSuccess) { ptk_destroy(c); return PTK_ERR_HIP; }
@@ -577,6 +582,7 @@ int ptk_create(ptk_ctx** out, int device_ordinal)
         int lo = 0, hi = 0;                      // (numerically lowest = greatest priority)
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         if (hipStreamCreateWithPriority(&c->xstream, hipStreamNonBlocking, hi) != hipSuccess ||
+            hipStreamCreateWithPriority(&c->exit_stream, hipStreamNonBlocking, hi) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_rendered, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_packed, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_gathered, hipEventDisableTiming) != hipSuccess)
@@ -611,6 +617,8 @@ void ptk_destroy(ptk_ctx* c)
     if (c->ev_packed) (void)hipEventDestroy(c->ev_packed);
     if (c->ev_gathered) (void)hipEventDestroy(c->ev_gathered);
     dfree(c->d_packed); dfree(c->d_gathered);
+    if (c->exit_stream) { (void)hipStreamSynchronize(c->exit_stream); (void)hipStreamDestroy(c->exit_stream); }
+    if (c->h_exit) (void)hipHostFree(c->h_exit);
     dfree(c->d_exit); dfree(c->d_stats); dfree(c->d_queues); dfree(c->d_samples);
     dfree(c->d_live_mask); dfree(c->d_live_list);
     for (int i = 0; i < ptk_ctx::kMaxTimedPasses; i++)
@@ -1202,12 +1210,16 @@ int ptk_samples(ptk_ctx* c) { return c ? c->samples.load() : 0; }
 int ptk_request_exit(ptk_ctx* c)
 {
     if (!c) return PTK_ERR_BAD_ARG;
-    // blocks that have not started yet read the flag and return (kernel prologue); written with a
-    // blocking copy outside the render stream so it lands while a render is in flight
+    // blocks that have not started yet read the flag and return (kernel prologue).  Written by an asynchronous copy on a
+    // stream of its own, so it lands while renders are in flight: a blocking hipMemcpy may be held back by the runtime until
+    // the queued renders have run to their end (it then cut nothing).  Generations only grow, so a copy that reads a later
+    // store of the source word still names every render it was meant to cut.
+    std::lock_guard<std::mutex> lk(c->exit_mu);
     uint32_t gen = c->render_gen.load();
     c->out_full_next = true;                     // a cut render may have skipped a full write of the bound hand-off buffer
+    if (gen > __atomic_load_n(c->h_exit, __ATOMIC_RELAXED)) __atomic_store_n(c->h_exit, gen, __ATOMIC_RELAXED);
     (void)hipSetDevice(c->device);
-    (void)hipMemcpy(c->d_exit, &gen, sizeof(gen), hipMemcpyHostToDevice);
+    (void)hipMemcpyAsync(c->d_exit, c->h_exit, sizeof(uint32_t), hipMemcpyHostToDevice, c->exit_stream);
     return PTK_OK;
 }
 
