@@ -35,7 +35,7 @@
 //     tested first (its record comes with the light sample), then any hit the closest-hit rule accepts is nearer and
 //     ends the walk (Walk::occl_tri).
 //   * Pinhole cameras without opacity textures: the camera ray's hit is cached per pixel, pixels whose camera ray
-//     misses are never traced, and a new path starts directly in the SHADE block (PTK_FUSED_START).
+//     misses are never traced, and a new path starts directly in the SHADE block.
 //   * RNG: PCG-RXS-M-XS-32 per path, keyed on (seed, pixel, sample) - never on lane/block/GPU.
 //
 // Float arithmetic is written operation by operation in the reference's order and this file is
@@ -64,9 +64,7 @@ namespace fma {
 #define PTK_FLT_EPSILON 1.1920928955078125e-7f
 #define PTK_PI_D 3.14159265358979323846
 #define PTK_BLOCK 256
-#ifndef PTK_TRACE_BLOCK
 #define PTK_TRACE_BLOCK 64          // trace_kernel: one wave per workgroup -> finest-grained dispatch
-#endif
 #ifndef PTK_TRACE_WAVES
 #define PTK_TRACE_WAVES 5           // waves per SIMD the register allocator must allow, FLAT variant: 96 VGPRs (4 spilled) since the parameters
                                     // are read through the constant address space; C2 +3.4-4.5 %, C1 +4 % over four waves (six: 80 VGPRs, 37 spilled, -6 %)
@@ -75,9 +73,9 @@ namespace fma {
 #define PTK_TRACE_WAVES_BVH 4       // ... BVH variant
 #endif
 #define PTK_NOHIT 0x7fffffff
-#ifndef PTK_GEN_CACHED_FAST
-#define PTK_GEN_CACHED_FAST 1        // cached camera hits: the camera-ray block only loads the pixel's direction and hit
-#endif
+// rows of the per-lane LDS traversal stack: the most entries the tree may defer, plus one row of slack that walk_step's
+// branchless pushes write into (every link is stored at the running top, also one that does not stay)
+#define PTK_STACK_ROWS (PTK_MAX_BVH_DEPTH + 1)
 
 struct v3 { float x, y, z; };
 
@@ -99,19 +97,14 @@ __device__ __forceinline__ v3 cross(v3 x, v3 y)
 // 13 issue cycles instead of the 43 of the compiler's v_div_scale / v_div_fmas / v_div_fixup expansion (which exists for the
 // denormal ranges).  The range cannot be left by a triangle's determinant or a vector's length while scene coordinates stay
 // below 2^61 in magnitude, which ptk_upload_scene enforces.
-#ifndef PTK_SHORT_RCP
-#define PTK_SHORT_RCP 1
-#endif
 __device__ __forceinline__ float rcp_ieee(float a)
 {
 #if PTK_CONTRACT >= 2
     return __builtin_amdgcn_rcpf(a);
-#elif PTK_SHORT_RCP
+#else
     const float y = __builtin_amdgcn_rcpf(a);
     const float e = __builtin_fmaf(-a, y, 1.0f);
     return __builtin_fmaf(y, e, y);
-#else
-    return 1.0f / a;
 #endif
 }
 // ... plus IEEE results for zeros, infinities and NaNs (one v_div_fixup_f32): where a zero length can occur
@@ -119,10 +112,8 @@ __device__ __forceinline__ float rcp_ieee_any(float a)
 {
 #if PTK_CONTRACT >= 2
     return __builtin_amdgcn_rcpf(a);
-#elif PTK_SHORT_RCP
-    return __builtin_amdgcn_div_fixupf(rcp_ieee(a), a, 1.0f);
 #else
-    return 1.0f / a;
+    return __builtin_amdgcn_div_fixupf(rcp_ieee(a), a, 1.0f);
 #endif
 }
 // sqrtf(x), BIT FOR BIT the correctly rounded IEEE-754 root: v_sqrt_f32 (1 ulp) and the exact residuals (fma) of its two
@@ -131,46 +122,17 @@ __device__ __forceinline__ float rcp_ieee_any(float a)
 // exact_math.json): identical to sqrtf for +0, +inf and every x >= 2^-104 (the largest input that differs is 0x0b6e9372,
 // where the residuals underflow); anything below - a positive length under 2^-52, which no scene produces, and negative
 // or NaN arguments - takes the compiler's expansion behind a branch that is practically never taken.
-#ifndef PTK_NODE_PREFETCH
-#define PTK_NODE_PREFETCH 1
-#endif
-#ifndef PTK_FLAT_SHARED_ORIGIN
-#define PTK_FLAT_SHARED_ORIGIN 1    // FLAT pass: the origin-only part of Moeller-Trumbore once per lane, not once per ray
-#endif
-#ifndef PTK_FLAT_EXEC_UPDATE
-#define PTK_FLAT_EXEC_UPDATE 1     // FLAT pass: the closest hit is updated with exec-masked moves behind a branch, not four selects per ray (C2 +1 %; the same in the BVH walk's tri_test: +-0)
-#endif
-#ifndef PTK_HIT_CLAMP
-#define PTK_HIT_CLAMP 1            // node arm: max(entry, 0) <= min(exit, closest hit) - one compare per child (round 4: C4 +1.5 %)
-#endif
-#ifndef PTK_PUSH_BRANCHLESS
-#define PTK_PUSH_BRANCHLESS 1      // node arm: unconditional stack writes, conditional pointer bumps (round 4: C4 +2 %; with the above: 28 -> 11 scalar instructions per node)
-#endif
-#ifndef PTK_TRI_PER_EXEC
-#define PTK_TRI_PER_EXEC 2          // triangles one execution of walk_step's (voted) triangle arm tests per lane
-#endif
-#ifndef PTK_FUSED_START
-#define PTK_FUSED_START 1
-#endif
-#ifndef PTK_ROBUST_BOXES
-#define PTK_ROBUST_BOXES 1
-#endif
-#ifndef PTK_SHORT_SQRT
-#define PTK_SHORT_SQRT 1
-#endif
 __device__ __forceinline__ float sqrt_ieee(float x)
 {
 #if PTK_CONTRACT >= 2
     return __builtin_amdgcn_sqrtf(x);
-#elif PTK_SHORT_SQRT
+#else
     if (__builtin_expect(!(x >= 0x1p-104f), 0)) return sqrtf(x);          // (zero too: correct either way, and as rare)
     float s = __builtin_amdgcn_sqrtf(x);
     const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
     const float rm = __builtin_fmaf(-sm, s, x), rp = __builtin_fmaf(-sp, s, x);
     s = rm <= 0.0f ? sm : s;
     return rp > 0.0f ? sp : s;
-#else
-    return sqrtf(x);
 #endif
 }
 __device__ __forceinline__ v3 normalize(v3 a)
@@ -309,7 +271,6 @@ struct Walk {
         // 228 153 node visits for one ray of the 1 M-triangle scene, a 0.5 s tail per launch)
         inv = V(__builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.x), -1e18f, 1e18f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.y), -1e18f, 1e18f),
                 __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.z), -1e18f, 1e18f));
-#if PTK_ROBUST_BOXES
         // The slab arithmetic of walk_step, t = fma(q, A, B) with A = scale * inv and B = (origin - ro) * inv, is off by at most
         // 2^-21 (|B| + 256 |A|) (see there).  Every node origin lies inside the scene's padded bounds and a node's 255 grid
         // steps span at most the scene, so per axis that is at most 2^-21 (max |ro| + 3.1 scene_bound) |inv| - a property of the RAY,
@@ -323,9 +284,6 @@ struct Walk {
         // which the bound above was derived with - |origin - ro| <= |origin| + |ro| - so it is covered)
         cn = V(__builtin_fmaf(-o.x, inv.x, -slack.x), __builtin_fmaf(-o.y, inv.y, -slack.y), __builtin_fmaf(-o.z, inv.z, -slack.z));
         cf = V(__builtin_fmaf(-o.x, inv.x, slack.x), __builtin_fmaf(-o.y, inv.y, slack.y), __builtin_fmaf(-o.z, inv.z, slack.z));
-#else
-        cn = V(-(o.x * inv.x), -(o.y * inv.y), -(o.z * inv.z)); cf = cn;
-#endif
         sgnx = (uint32_t)(__float_as_int(inv.x) >> 31); sgny = (uint32_t)(__float_as_int(inv.y) >> 31); sgnz = (uint32_t)(__float_as_int(inv.z) >> 31);
         node = num_nodes > 0 ? 0 : NODE_EXIT;
         top = stack;
@@ -400,6 +358,7 @@ __device__ __forceinline__ bool tri_test(const PT& P, Walk& W, float4 t0, float4
 // nearly halves the instructions of the hottest loop of the Cornell configs.  No early returns: all quantities are
 // computed and the reference's tests AND-ed in their negated form, exactly as tri_test does.  Returns true when the
 // shadow ray has been decided by an occluder.
+// (ox, oy, oz are not read - both rays leave W.ro, see tri_test_pair - but dropping them reorders a few moves of the kernels)
 struct RayPair { f2 ox, oy, oz, dx, dy, dz; };
 
 template <bool STATS, class PT>
@@ -412,7 +371,6 @@ __device__ __forceinline__ bool tri_test_pair(const PT& P, Walk& W, Walk& WS, co
     const f2 hx = R.dy * e2z - R.dz * e2y, hy = R.dz * e2x - R.dx * e2z, hz = R.dx * e2y - R.dy * e2x;
     const f2 a = hx * e1x + hy * e1y + hz * e1z;                 // dot(edge1, h)
     const f2 f = { rcp_ieee(a.x), rcp_ieee(a.y) };
-#if PTK_FLAT_SHARED_ORIGIN
     // The two rays of a lane leave the SAME point (shade_interaction starts both at p), so everything of Moeller-Trumbore that
     // depends on the origin alone - s = ro - v0, q = cross(s, edge1), dot(edge2, q) - is the same number for both: computed once
     // in scalar f32 (full rate) instead of twice in packed f32 (half rate), 17 of the ~60 operations per ray and triangle.  The
@@ -422,14 +380,6 @@ __device__ __forceinline__ bool tri_test_pair(const PT& P, Walk& W, Walk& WS, co
     const float qx = sy * e1z - sz * e1y, qy = sz * e1x - sx * e1z, qz = sx * e1y - sy * e1x;      // q = cross(s, edge1)
     const f2 v = f * (R.dx * qx + R.dy * qy + R.dz * qz);
     const f2 t = f * (qx * e2x + qy * e2y + qz * e2z);
-#else
-    const f2 sx = R.ox - v0x, sy = R.oy - v0y, sz = R.oz - v0z;  // s = ro - v0
-    const f2 u = f * (sx * hx + sy * hy + sz * hz);
-    // q = cross(s, edge1)
-    const f2 qx = sy * e1z - sz * e1y, qy = sz * e1x - sx * e1z, qz = sx * e1y - sy * e1x;
-    const f2 v = f * (R.dx * qx + R.dy * qy + R.dz * qz);
-    const f2 t = f * (qx * e2x + qy * e2y + qz * e2z);
-#endif
     const f2 uv = u + v;
     const int tri = __float_as_int(t2.y);
     const int otex = __float_as_int(t2.z);
@@ -459,14 +409,10 @@ __device__ __forceinline__ bool tri_test_pair(const PT& P, Walk& W, Walk& WS, co
             oks = rng.opacity(ray_shadow, (uint32_t)tri) < op;
         }
     }
-#if PTK_FLAT_EXEC_UPDATE
-    // (exec-masked moves - full rate - instead of four half-rate selects per ray; skipped outright when no lane accepts)
+    // (exec-masked moves - full rate - instead of four half-rate selects per ray; skipped outright when no lane accepts.
+    // C2 +1 %; the same in the BVH walk's tri_test measured +-0, so that one keeps its selects)
     if (okb) { W.best.tri = tri; W.best.t = t.x; W.best.u = u.x; W.best.v = v.x; asm volatile("" : "+v"(W.best.t), "+v"(W.best.u), "+v"(W.best.v)); }
     if (oks) { WS.best.tri = tri; WS.best.t = t.y; WS.best.u = u.y; WS.best.v = v.y; asm volatile("" : "+v"(WS.best.t), "+v"(WS.best.u), "+v"(WS.best.v)); }
-#else
-    W.best.tri = okb ? tri : W.best.tri; W.best.t = okb ? t.x : W.best.t; W.best.u = okb ? u.x : W.best.u; W.best.v = okb ? v.x : W.best.v;
-    WS.best.tri = oks ? tri : WS.best.tri; WS.best.t = oks ? t.y : WS.best.t; WS.best.u = oks ? u.y : WS.best.u; WS.best.v = oks ? v.y : WS.best.v;
-#endif
     return oks & (tri != WS.occl_tri);
 }
 
@@ -501,11 +447,10 @@ __device__ __forceinline__ WalkParams walk_params(const PT& P)
     return w;
 }
 
-// One BVH step of a lane: up to TWO units of work - one triangle of the pending leaf (arm A) AND one
-// interior node (arm B).  A leaf reached by arm B is parked in the lane's one-entry triangle queue and the
-// descent continues with the next node from the stack, so the two arms overlap instead of alternating
-// (the wave executes both arms every iteration anyway).  The price is slightly later t-max tightening;
-// the result is unaffected (closest hit is order-independent).
+// One BVH step of a lane: up to two triangles of the pending leaf (arm A) AND one interior node (arm B).  A leaf
+// reached by arm B is parked in the lane's one-entry triangle queue and the descent continues with the next node
+// from the stack, so the two arms overlap instead of alternating (the wave executes both arms every iteration anyway).
+// The price is slightly later t-max tightening; the result is unaffected (closest hit is order-independent).
 struct NodeRec { float4 q0, q1, q2, q3; };      // one 64-byte node record in flight / in registers
 // the record of the node a lane will test next (a lane without a node reads the root - every such lane the same 64 bytes - which
 // costs less than a branch around the loads and zeroing sixteen registers for the lanes that skip them)
@@ -520,20 +465,18 @@ __device__ __forceinline__ void request_node(const PT& P, const Walk& W, NodeRec
 // loop or at the end of the lane's previous step, and the record of the node this step ends on is requested before the step
 // returns, so its round trip also covers the loop's wave-uniform bookkeeping (ballots, debts, ~30 dependent scalar instructions)
 // instead of starting behind it.
-template <bool STATS, int STRIDE, bool PIPELINED = false, int TRI_PER_EXEC = PTK_TRI_PER_EXEC, class PT>
+template <bool STATS, int STRIDE, bool PIPELINED = false, class PT>
 __device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, uint32_t ray, int* stack, Counters& cnt,
                                           const bool run_tri_arm = true, NodeRec* rec = nullptr)
 {
-#if PTK_NODE_PREFETCH
     // the node record of arm B is requested BEFORE arm A runs, so that its round trip overlaps arm A's loads and arithmetic
     // (one memory latency per iteration instead of two; the compiler would otherwise issue it after arm A's join)
     NodeRec here;
     if (PIPELINED) here = *rec; else request_node(P, W, here);
     const float4 q0 = here.q0, q1 = here.q1, q2 = here.q2, q3 = here.q3;
     asm volatile("" ::: "memory");
-#endif
     const bool node_was = W.node >= 0;
-    if (TRI_PER_EXEC == 2 && run_tri_arm && W.tri_left > 0)       // ---- arm A: up to TWO triangles
+    if (run_tri_arm && W.tri_left > 0)                    // ---- arm A: up to TWO triangles
     {
         // The second triangle: the pending leaf's next one, or - the pending leaf has only this one left and the lane is BLOCKED
         // on a second leaf (W.node holds it: the one-leaf queue was busy) - the first triangle of that leaf, whose remainder then
@@ -562,22 +505,8 @@ __device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, 
         W.tri_left = stop ? 0 : W.tri_left;
         W.node = stop ? NODE_EXIT : W.node;
     }
-    if (TRI_PER_EXEC != 2 && run_tri_arm && W.tri_left > 0)       // ---- arm A: one triangle
-    {
-        const float4* tp = (const float4*)((const char*)P.tris + (uint32_t)W.tri_next * (uint32_t)(TRI_F4 * 16));
-        float4 t0 = ldg4(tp), t1 = ldg4(tp + 1), t2 = ldg4(tp + 2);
-        W.tri_next++; W.tri_left--;
-        const bool stop = tri_test<STATS>(P, W, t0, t1, t2, rng, ray, cnt);
-        W.top = stop ? stack : W.top;                     // an occluder decides a shadow ray: drop everything
-        W.tri_left = stop ? 0 : W.tri_left;
-        W.node = stop ? NODE_EXIT : W.node;
-    }
     if (node_was && W.node >= 0)                          // ---- arm B: one 4-wide interior node (its record is `here`; a node popped by arm A waits a step)
     {
-#if !PTK_NODE_PREFETCH
-        const float4* np = P.nodes + (size_t)W.node * NODE_F4;
-        const float4 q0 = ldg4(np), q1 = ldg4(np + 1), q2 = ldg4(np + 2), q3 = ldg4(np + 3);
-#endif
         if (STATS) { cnt.nodes++; cnt.cur_nodes++; }
         // child planes live on the node's 8-bit grid: plane = origin + q * scale, so along the ray
         //   t = (plane - ro) * inv = q * (scale * inv) + (origin - ro) * inv = fma(q, A, B)
@@ -603,14 +532,10 @@ __device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, 
         const uint32_t ny = (hiy & my) | (loy & ~my), fy = (loy & my) | (hiy & ~my);
         const uint32_t nz = (hiz & mz) | (loz & ~mz), fz = (loz & mz) | (hiz & ~mz);
         const int link0 = __float_as_int(q1.z), link1 = __float_as_int(q1.w), link2 = __float_as_int(q2.x), link3 = __float_as_int(q2.y);
-#if PTK_ROBUST_BOXES
         // ... and a node is only culled against the closest hit so far when it lies beyond it by more than Moeller-Trumbore's
         // own error in t (relative ~1e-7 / cos of the incidence angle: which of two triangles 1e-6 apart is "closest" is
         // decided by that arithmetic, not by geometry - the second half of the same soak finding)
         const float tmax = W.best.t * 1.0000153f;
-#else
-        const float tmax = W.best.t;
-#endif
         int key[4];
         bool hit[4];
 #pragma unroll
@@ -621,15 +546,9 @@ __device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, 
             const float tnz = __builtin_fmaf((float)((nz >> (8 * k)) & 255u), Az, Bnz), tfz = __builtin_fmaf((float)((fz >> (8 * k)) & 255u), Az, Bfz);
             // NaNs (0 * inf for axis-parallel rays) drop out of min3 / max3: that axis then does not constrain - conservative
             const float tn = fmaxf(fmaxf(tnx, tny), tnz), tf = fminf(fminf(tfx, tfy), tfz);
-#if PTK_HIT_CLAMP
             // entry no earlier than the ray's start, exit no later than the closest hit: ONE compare instead of three (and no
-            // scalar ands of three lane masks per child)
+            // scalar ands of three lane masks per child; round 4: C4 +1.5 %)
             hit[k] = fmaxf(tn, 0.0f) <= fminf(tf, tmax);
-#elif PTK_ROBUST_BOXES
-            hit[k] = (tn <= tf) & (tf >= 0.0f) & (tn <= tmax);
-#else
-            hit[k] = (tn <= tf * 1.000001f) & (tf >= 0.0f) & (tn <= tmax);
-#endif
             // order key: the entry distance with the slot in its low bits (negative distances - origin inside - sort first)
             key[k] = hit[k] ? ((__float_as_int(tn) & ~3) | k) : 0x7fffffff;
         }
@@ -638,19 +557,13 @@ __device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, 
         // four compares decide which of the others wait on the stack (two hits: exactly far-after-near; more: slot order)
         const bool o0 = key[0] != kmin, o1 = key[1] != kmin, o2 = key[2] != kmin;
         int next = !o0 ? link0 : (!o1 ? link1 : (!o2 ? link2 : link3));
-#if PTK_PUSH_BRANCHLESS
         // every link is written at the running top and the top moves on only behind a link that stays: no exec-mask juggling around
-        // four conditional stores (the stack has one row of slack above the tree's own need: lds_stack is PTK_MAX_BVH_DEPTH + 1 rows)
+        // four conditional stores (round 4: C4 +2 %; with the clamped compare above: 28 -> 11 scalar instructions per node).  A link
+        // that does not stay is still stored, one row above a stack that may be full: hence the slack row of PTK_STACK_ROWS
         *W.top = link0; W.top += (hit[0] & o0) ? STRIDE : 0;
         *W.top = link1; W.top += (hit[1] & o1) ? STRIDE : 0;
         *W.top = link2; W.top += (hit[2] & o2) ? STRIDE : 0;
         *W.top = link3; W.top += (hit[3] & (key[3] != kmin)) ? STRIDE : 0;
-#else
-        if (hit[0] & o0) { *W.top = link0; W.top += STRIDE; }
-        if (hit[1] & o1) { *W.top = link1; W.top += STRIDE; }
-        if (hit[2] & o2) { *W.top = link2; W.top += STRIDE; }
-        if (hit[3] & (key[3] != kmin)) { *W.top = link3; W.top += STRIDE; }
-#endif
         if (kmin == 0x7fffffff) next = W.template pop<STRIDE>(stack);
         W.node = next;
     }
@@ -1039,7 +952,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRAC
     // used instead of being preloaded whole into SGPRs (ptk_device.h: 30 / 42 SGPR spills -> 0)
     typedef const __attribute__((address_space(4))) RenderParams ConstParams;
     ConstParams& P = *(ConstParams*)(uintptr_t)Pp;
-    __shared__ int lds_stack[FLAT ? 1 : (PTK_MAX_BVH_DEPTH + PTK_PUSH_BRANCHLESS) * PTK_TRACE_BLOCK];
+    __shared__ int lds_stack[FLAT ? 1 : PTK_STACK_ROWS * PTK_TRACE_BLOCK];
     if (P.exit_flag && __hip_atomic_load(P.exit_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= P.exit_gen) return;     // an Exit() named this render or a later one
 
     const int tid = threadIdx.x;
@@ -1159,15 +1072,11 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRAC
                     pix = (lds_item[IT_Y0] + (q >> 3)) * (uint32_t)P.width + lds_item[IT_X0] + (q & 7u);
                     sample_abs = lds_item[IT_SBEGIN] + s_in_chunk;
                     out_idx = lds_item[IT_OUTBASE] + s_in_chunk * 64u + q;
-#if PTK_FUSED_START
                     // cached camera rays (pinhole, no stochastic opacity): the path starts at its first surface
                     // interaction, so the lane queues for the SHADE block directly and sets its path up there (depth < 0
                     // marks it) - one voted block less to wait for per path, and bigger shading batches
                     st = P.primary_hit ? ST_SHADE : ST_GEN;
                     depth = -1;
-#else
-                    st = ST_GEN;
-#endif
                 }
                 next_unit = min(total_units, next_unit + (uint32_t)__popcll(m_need));
                 m_need = __ballot(st == ST_NEED);
@@ -1287,10 +1196,14 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRAC
             if (STATS) { const uint32_t nsx = (uint32_t)__popcll(__ballot(st == ST_SHADE)); if (lane == 0) { cnt.shade_execs++; cnt.shade_lanes += nsx; } }
             if (st == ST_SHADE)
             {
-#if PTK_FUSED_START
                 if (depth < 0)
                 {
-                    // a path dealt since the last shade block (see the camera-ray block below for the reasoning)
+                    // a path dealt since the last shade block.  Pinhole camera, no stochastic opacity: every sample of this
+                    // pixel shoots the same camera ray, so its direction and closest hit were computed once (primary_hits_kernel)
+                    // and the path starts at its first surface interaction (pixels whose camera ray misses are never dealt).
+                    // The stream is set up as in the camera-ray block below, and the two SampleCircle draws a pinhole frame
+                    // still consumes (pathtracer.cpp:787, always two) only advance it - two LCG steps in one:
+                    //   s2 = (s * a + inc) * a + inc = s * a^2 + inc * (a + 1)      (mod 2^32: the identical state)
                     const uint2 pr = P.pixel_rng[pix];
                     const float4 c = P.primary_hit[pix], r = P.primary_rd[pix];
                     rng.inc = pr.y;
@@ -1305,7 +1218,6 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRAC
                     W.best.tri = __float_as_int(c.x); W.best.t = c.y; W.best.u = c.z; W.best.v = c.w;
                     W.node = NODE_EXIT; W.top = stack; W.tri_left = 0;
                 }
-#endif
                 // ---- one surface interaction of PathTracer::Trace, pathtracer.cpp:551-727 ----
                 const bool ended = shade_interaction<STATS, FLAT>(P, W, WS, stack, rng, L, T, Tdi, nextDir, depth, iter, inside, ray, cnt);
                 if (ended) PTK_FINISH_PATH();
@@ -1318,6 +1230,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRAC
             if (st == ST_GEN)
             {
                 // ---- camera ray with thin-lens DOF, pathtracer.cpp:785-791 + SampleCircle :734-739 ----
+                // (uncached cameras only: a cached camera ray's path starts in the shade block)
                 // the pixel's RNG stream constants (pixel_key, increment) come from a per-frame table: they depend on
                 // (seed, pixel) only, and four of the five hashes of a path's start went into them
                 const uint2 pr = P.pixel_rng[pix];
@@ -1329,50 +1242,24 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRAC
                 depth = 0; iter = 0; inside = false; ray = 0;
                 W.occl_tri = -1;
                 if (STATS) cnt.started++;
-                if (!PTK_FUSED_START && PTK_GEN_CACHED_FAST && P.primary_hit)      // (fused start: such lanes never come here)
+                // per-pixel constants are re-read here (L1/L2 hits) instead of living in registers
+                const float4 d0 = P.primary[pix];
+                const v3 dir0 = V(d0.x, d0.y, d0.z);
+                v3 focalPoint = add(camPos0, muls(dir0, P.focal_dist));
+                float r1 = rng.next(), r2 = rng.next();          // always two draws, even with a pinhole
+                v3 ro = camPos0;
+                if (P.aperture != 0.0f)
                 {
-                    // Pinhole camera, no stochastic opacity: every sample of this pixel shoots the same camera ray, so its
-                    // direction and closest hit were computed once (primary_hits_kernel) and the path starts at its first
-                    // surface interaction.  The two SampleCircle draws a pinhole frame still consumes (pathtracer.cpp:787,
-                    // always two) only advance the stream - two LCG steps in one:
-                    //   s2 = (s * a + inc) * a + inc = s * a^2 + inc * (a + 1)      (mod 2^32: the identical state)
-                    rng.state = rng.state * (747796405u * 747796405u) + rng.inc * (747796405u + 1u);
-                    const float4 c = P.primary_hit[pix], r = P.primary_rd[pix];
-                    W.ro = camPos0; W.rd = V(r.x, r.y, r.z);
-                    W.best.tri = __float_as_int(c.x); W.best.t = c.y; W.best.u = c.z; W.best.v = c.w;
-                    W.node = NODE_EXIT; W.top = stack; W.tri_left = 0;
-                    ray = 1;
-                    st = ST_SHADE;              // (pixels whose camera ray misses never get here)
+                    float angle = (float)((double)r1 * 2. * PTK_PI_D);
+                    float radius = sqrt_ieee(r2);
+                    float sn, cs;
+                    sincos_2pi(angle, sn, cs);
+                    float offx = (cs * radius) * P.aperture, offy = (sn * radius) * P.aperture;
+                    ro = add(camPos0, add(muls(camRight, offx), muls(camUp, offy)));
                 }
-                else
-                {
-                    // per-pixel constants are re-read here (L1/L2 hits) instead of living in registers
-                    const float4 d0 = P.primary[pix];
-                    const v3 dir0 = V(d0.x, d0.y, d0.z);
-                    v3 focalPoint = add(camPos0, muls(dir0, P.focal_dist));
-                    float r1 = rng.next(), r2 = rng.next();          // always two draws, even with a pinhole
-                    v3 ro = camPos0;
-                    if (P.aperture != 0.0f)
-                    {
-                        float angle = (float)((double)r1 * 2. * PTK_PI_D);
-                        float radius = sqrt_ieee(r2);
-                        float sn, cs;
-                        sincos_2pi(angle, sn, cs);
-                        float offx = (cs * radius) * P.aperture, offy = (sn * radius) * P.aperture;
-                        ro = add(camPos0, add(muls(camRight, offx), muls(camUp, offy)));
-                    }
-                    v3 rd = normalize(sub(focalPoint, ro));
-                    W.begin(ro, rd, P.num_nodes, stack, P.scene_bound);
-                    st = ST_TRAV;
-                    if (!PTK_FUSED_START && P.primary_hit)
-                    {
-                        const float4 c = P.primary_hit[pix];
-                        W.best.tri = __float_as_int(c.x); W.best.t = c.y; W.best.u = c.z; W.best.v = c.w;
-                        W.node = NODE_EXIT;
-                        ray = 1;
-                        st = ST_SHADE;
-                    }
-                }
+                v3 rd = normalize(sub(focalPoint, ro));
+                W.begin(ro, rd, P.num_nodes, stack, P.scene_bound);
+                st = ST_TRAV;
             }
         }
     }
@@ -1514,7 +1401,7 @@ __global__ void primary_dirs_kernel(const PrimaryParams P)
 // so its closest hit is found once per camera / scene change instead of once per sample.
 __global__ __launch_bounds__(PTK_BLOCK) void primary_hits_kernel(const RenderParams P, float4* out, float4* out_rd)
 {
-    __shared__ int lds_stack[(PTK_MAX_BVH_DEPTH + PTK_PUSH_BRANCHLESS) * PTK_BLOCK];
+    __shared__ int lds_stack[PTK_STACK_ROWS * PTK_BLOCK];
     const int i = blockIdx.x * PTK_BLOCK + threadIdx.x;
     if (i >= P.width * P.height) return;
     Rng rng; rng.inc = 1u; rng.state = 0u; rng.key = 0u;            // no opacity draws can occur here
@@ -1534,7 +1421,7 @@ __global__ __launch_bounds__(PTK_BLOCK) void primary_hits_kernel(const RenderPar
 // Parity probe: closest hit for a list of rays (no opacity draws differ: key 0, ray 0).
 __global__ __launch_bounds__(PTK_BLOCK) void probe_hits_kernel(const ProbeParams P)
 {
-    __shared__ int lds_stack[(PTK_MAX_BVH_DEPTH + PTK_PUSH_BRANCHLESS) * PTK_BLOCK];
+    __shared__ int lds_stack[PTK_STACK_ROWS * PTK_BLOCK];
     int i = blockIdx.x * PTK_BLOCK + threadIdx.x;
     if (i >= P.n) return;
     Rng rng; rng.inc = (hash32(0u ^ 0x9E3779B9u) << 1) | 1u; rng.state = hash32(0u); rng.key = rng.state;
@@ -1555,7 +1442,7 @@ __global__ __launch_bounds__(PTK_BLOCK) void probe_hits_kernel(const ProbeParams
 __global__ __launch_bounds__(PTK_BLOCK) void probe_direct_kernel(const ProbeParams P, const float* __restrict__ pts, const float* __restrict__ nrm,
                                                                  const float* __restrict__ dif, const float* __restrict__ tape, float* __restrict__ out)
 {
-    __shared__ int lds_stack[(PTK_MAX_BVH_DEPTH + PTK_PUSH_BRANCHLESS) * PTK_BLOCK];
+    __shared__ int lds_stack[PTK_STACK_ROWS * PTK_BLOCK];
     const int i = blockIdx.x * PTK_BLOCK + threadIdx.x;
     if (i >= P.n) return;
     Rng rng; rng.inc = (hash32(0u ^ 0x9E3779B9u) << 1) | 1u; rng.state = hash32(0u); rng.key = rng.state;
