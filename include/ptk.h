@@ -75,21 +75,34 @@ typedef struct ptk_scene_desc {
 } ptk_scene_desc;
 
 /* traversal statistics from the counters-enabled (untimed) kernel variant; feeds the
- * algorithmic-bytes roofline of SURVEY.md §8(d4) */
+ * algorithmic-bytes roofline of SURVEY.md §8(d4).  Definitions (tests/test_gpu_stats_counters.py checks each against the CPU
+ * oracle's own counts, oracle/pt_oracle.h orc_render_counted; DESIGN.md §5 lists which are exact and which bounded): */
 typedef struct ptk_stats {
-    uint64_t samples;            /* pixel*spp processed */
-    uint64_t rays;               /* closest-hit traversals (bounce + shadow rays) */
-    uint64_t shadow_rays;
-    uint64_t node_visits;        /* 64-byte BVH node records fetched (4 child boxes each) */
-    uint64_t tri_tests;          /* 48-byte triangle records fetched */
-    uint64_t hits_shaded;        /* surface interactions shaded */
-    uint64_t tex_fetches;        /* 4-byte texel fetches */
+    uint64_t samples;            /* pixel*spp of the owned pixels, traced or not */
+    uint64_t rays;               /* closest-hit traversals the trace kernel made: camera rays (not those the pinhole primary-hit
+                                    cache resolved in primary_hits_kernel, nor those of pixels left out as sure misses), bounce
+                                    rays and shadow rays */
+    uint64_t shadow_rays;        /* DirectIllumimation visibility rays (one per diffuse bounce whose light sample faces the surface) */
+    uint64_t node_visits;        /* BVH4 interior nodes a ray's walk tested (one 64-byte record each, 4 child boxes); 0 in FLAT */
+    uint64_t tri_tests;          /* ray-triangle tests (Moeller-Trumbore, one per ray and candidate): BVH - the leaf triangles the
+                                    walk tested plus, per shadow ray, the test of its light triangle before the walk; FLAT - every
+                                    triangle for every ray (rays x triangles; the pass loads each triangle once per WAVE, with scalar
+                                    loads shared by both rays of a lane, so these are not 48-byte record fetches) */
+    uint64_t hits_shaded;        /* surface interactions shaded (every closest hit of a camera or bounce ray, the last one included) */
+    uint64_t tex_fetches;        /* texture lookups, one 4-byte RGBA8 texel each: at shading time the normal map of every hit and,
+                                    below the depth limit, the diffuse / emissive / roughness / metallic maps; plus one per opacity test
+                                    (a candidate with an opacity map that Moeller-Trumbore accepts and that is nearer than the best hit
+                                    so far, or as near with a smaller index) - which depends on the order candidates are tested in:
+                                    ascending index in FLAT, the walk's order in a BVH */
     /* SIMD utilisation of the wave state machine: lanes that took part / (64 * wave-level executions) */
-    uint64_t walk_wave_iters, walk_lane_iters;     /* BVH-walk loop iterations per wave, and lanes active in them */
-    uint64_t shade_wave_execs, shade_lanes;        /* shading block executions per wave, lanes shaded */
-    uint64_t gen_wave_execs, gen_lanes;            /* camera-ray block executions per wave, lanes generated */
-    uint64_t tri_wave_execs, tri_lanes;            /* triangle-arm executions of the BVH walk per wave, lanes testing */
-    uint64_t max_walk_nodes;                       /* most node records a single ray fetched (tail diagnostic) */
+    uint64_t walk_wave_iters, walk_lane_iters;     /* BVH-walk loop iterations per wave, and lanes in the walk state in them
+                                                      (FLAT: triangle passes, and lanes passing - one per bounce or camera ray) */
+    uint64_t shade_wave_execs, shade_lanes;        /* shading block executions per wave, lanes shaded (= hits_shaded) */
+    uint64_t gen_wave_execs, gen_lanes;            /* camera-ray block executions per wave, lanes generated (= paths_started, or 0
+                                                      under the primary-hit cache, whose paths start in the shading block) */
+    uint64_t tri_wave_execs, tri_lanes;            /* triangle-arm executions of the BVH walk per wave, lanes testing (1 or 2
+                                                      triangles each: tri_lanes <= tri_tests - shadow_rays <= 2 tri_lanes) */
+    uint64_t max_walk_nodes;                       /* most node_visits of a single ray (tail diagnostic) */
     uint64_t paths_started;                        /* samples actually traced (the others: camera ray known to miss) */
 } ptk_stats;
 

@@ -27,6 +27,15 @@ assert TEXTURE_DTYPE.itemsize == 16
 
 _f = C.POINTER(C.c_float)
 
+# per-pixel counters of Oracle.render_counted (oracle/pt_oracle.h ORC_CNT_*)
+COUNT_NAMES = ("paths", "camera_rays", "bounce_rays", "shadow_rays", "shaded", "tex_shade", "tex_opacity", "ray_numbers")
+RAY_CAMERA, RAY_BOUNCE, RAY_SHADOW = 0, 1, 2
+# one closest-hit traversal of Oracle.render_counted(dump=True) (orc_ray_rec)
+RAY_DTYPE = np.dtype([("pixel", np.uint32), ("sample", np.uint32), ("ray", np.uint32), ("kind", np.int32),
+                      ("ro", np.float32, 3), ("rd", np.float32, 3), ("t", np.float32), ("tri", np.int32),
+                      ("light", np.int32), ("occluded", np.int32)])
+assert RAY_DTYPE.itemsize == 56
+
 
 class SceneDescC(C.Structure):
     _fields_ = [
@@ -129,6 +138,9 @@ class Oracle:
         L.orc_sample_circle.argtypes = [C.c_float, C.c_float, _f]
         L.orc_bvh_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.orc_direct_illumination_tape.argtypes = [C.c_void_p, _f, _f, _f, _f, _f]
+        L.orc_render_counted.restype = C.c_int
+        L.orc_render_counted.argtypes = [C.c_void_p, C.POINTER(CameraC), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
         self.arrays = normalise_arrays(arrays)
         self.desc = fill_desc(SceneDescC(), self.arrays)
         self.h = L.orc_create(C.byref(self.desc))
@@ -157,6 +169,30 @@ class Oracle:
         self.lib.orc_render(self.h, C.byref(cam), width, height, depth, first_sample, spp, seed, rank, world,
                             total.ctypes.data, rgb.ctypes.data if rgb is not None else None, threads)
         return total, rgb
+
+    def render_counted(self, cam: CameraC, width, height, depth, first_sample, spp, seed, rank=0, world=1, threads=0,
+                       dump=False, total=None):
+        """orc_render that also counts, per pixel, what the trace kernels' STATS build counts.  Returns dict(counts [H, W, 8] int64
+        (rows top-down; columns COUNT_NAMES), total [H, W, 3] float32 (rows bottom-up, as render), rays: RAY_DTYPE records of every
+        closest-hit traversal, pixel by pixel in the order they are cast, or None without dump)."""
+        if total is None:
+            total = np.zeros((height, width, 3), dtype=np.float32)
+        assert total.dtype == np.float32 and total.flags.c_contiguous
+        counts = np.zeros((height, width, len(COUNT_NAMES)), np.int64)
+        args = (self.h, C.byref(cam), width, height, depth, first_sample, spp, seed, rank, world)
+        rays = None
+        if dump:
+            # the records' places come from the counts of a first, image-less pass
+            assert self.lib.orc_render_counted(*args, None, counts.ctypes.data, None, None, 0, threads) == 0
+            per_px = counts[..., 1:4].sum(axis=2).reshape(-1)
+            offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum(per_px)[:-1]]), np.int64)
+            rays = np.zeros(int(per_px.sum()), RAY_DTYPE)
+            rc = self.lib.orc_render_counted(*args, total.ctypes.data, counts.ctypes.data, rays.ctypes.data, offsets.ctypes.data,
+                                             len(rays), threads)
+        else:
+            rc = self.lib.orc_render_counted(*args, total.ctypes.data, counts.ctypes.data, None, None, 0, threads)
+        assert rc == 0, "ray records overflowed"
+        return dict(counts=counts, total=total, rays=rays)
 
     def render_tape(self, cam: CameraC, width, height, depth, tape):
         """One RenderFrame with the reference's draws on tape (its single-thread pixel order); returns (total, draws consumed)."""
@@ -221,4 +257,16 @@ def lib():
     L.orc_primary_dirs.argtypes = [C.POINTER(CameraC), C.c_int, C.c_int, C.c_void_p]
     L.orc_aabb_intersect.argtypes = [_f] * 4
     L.orc_aabb_build.argtypes = [_f, C.c_int, _f]
+    L.orc_intersect_many.argtypes = [C.c_int64, _f, _f, _f, _f]
     return L
+
+
+def intersect_many(ro, rd, tri9) -> np.ndarray:
+    """orc_intersect_triangle (the kernels' Moeller-Trumbore, bit for bit) on n (ray, triangle) pairs: ro, rd [n, 3], tri9 [n, 9]
+    (v1 v2 v3) float32 -> [n, 3] (t, u, v), all zero where the triangle is missed."""
+    L = lib()
+    a = [np.ascontiguousarray(x, np.float32) for x in (ro, rd, tri9)]
+    n = len(a[0])
+    out = np.zeros((n, 3), np.float32)
+    L.orc_intersect_many(n, *[x.ctypes.data_as(_f) for x in a], out.ctypes.data_as(_f))
+    return out

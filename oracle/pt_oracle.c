@@ -325,23 +325,26 @@ void orc_bvh_info(const orc_scene* s, int32_t* nodes, int32_t* depth) { *nodes =
 typedef struct { int32_t tri; float t, u, v; } hit_t;
 
 /* candidate test of one triangle: Hit leaf branch, pathtracer.cpp:463-489 */
-static inline void test_triangle(const orc_scene* s, int tri, v3 ro, v3 rd, rng_t* rng, uint32_t ray, hit_t* best)
+/* returns 1 when it looked up an opacity texel (the candidate hits and is nearer than the best so far), for the counting
+ * render below; the others ignore it */
+static inline int test_triangle(const orc_scene* s, int tri, v3 ro, v3 rd, rng_t* rng, uint32_t ray, hit_t* best)
 {
     const float* p = s->verts + (size_t)tri * 9;
     float t, u, v;
-    if (!intersect_triangle(ro, rd, ld3(p), ld3(p + 3), ld3(p + 6), &t, &u, &v)) return;
+    if (!intersect_triangle(ro, rd, ld3(p), ld3(p + 3), ld3(p + 6), &t, &u, &v)) return 0;
     /* (an infinite t - an overflowed determinant of a ray far outside every scene - is no hit: with best->t starting at
        infinity the tie rule would otherwise accept it; the kernels test the same) */
-    if (!(t < INFINITY) || !(t < best->t || (t == best->t && tri < best->tri))) return;
+    if (!(t < INFINITY) || !(t < best->t || (t == best->t && tri < best->tri))) return 0;
     int otex = s->mats[s->material[tri]].tex[5];
     if (otex >= 0)
     {
         float ux, uy, c[4];
         get_uv(s, tri, u, v, &ux, &uy);
         tex2d(s, otex, ux, uy, c);
-        if (!(rnd_opacity(rng, ray, (uint32_t)tri) < c[0])) return;
+        if (!(rnd_opacity(rng, ray, (uint32_t)tri) < c[0])) return 1;
     }
     best->tri = tri; best->t = t; best->u = u; best->v = v;
+    return otex >= 0;
 }
 
 static int closest_hit(const orc_scene* s, v3 ro, v3 rd, rng_t* rng, uint32_t ray, hit_t* out)
@@ -395,6 +398,46 @@ int orc_hit_brute(const orc_scene* s, const float* ro, const float* rd, float* t
     *tri = h.tri; tuv[0] = h.t; tuv[1] = h.u; tuv[2] = h.v; return 1;
 }
 
+/* ---- counting (test infrastructure for the trace kernels' counters, include/ptk.h ptk_stats) ----------------------------
+ * orc_render_counted traces exactly what orc_render traces and counts, per pixel, what the kernels' STATS build counts. */
+typedef struct {
+    int64_t* px;          /* this pixel's ORC_CNT_N counters */
+    orc_ray_rec* rec;     /* where this pixel's next ray record goes; NULL: no dump */
+    orc_ray_rec* rec_end;
+    int overflow;
+    uint32_t pixel, sample;
+    int brute;            /* the scene has opacity textures: candidates in ascending index order, the FLAT pass's */
+} count_t;
+
+static int closest_hit_counted(const orc_scene* s, v3 ro, v3 rd, rng_t* rng, uint32_t ray, int kind, int light, count_t* cc,
+                               hit_t* out)
+{
+    int hit;
+    cc->px[ORC_CNT_CAMERA + kind]++;
+    if (cc->brute)
+    {
+        /* closest_hit_brute, counting the opacity texels its candidate order reads (its closest hit is the tree walk's) */
+        hit_t best; best.tri = 0x7fffffff; best.t = INFINITY; best.u = best.v = 0.0f;
+        for (int i = 0; i < s->nt; i++) cc->px[ORC_CNT_TEX_OPACITY] += test_triangle(s, i, ro, rd, rng, ray, &best);
+        hit = best.tri != 0x7fffffff;
+        if (hit) *out = best;
+    }
+    else hit = closest_hit(s, ro, rd, rng, ray, out);
+    if (cc->rec)
+    {
+        if (cc->rec < cc->rec_end)
+        {
+            orc_ray_rec* r = cc->rec++;
+            r->pixel = cc->pixel; r->sample = cc->sample; r->ray = ray; r->kind = kind;
+            r->ro[0] = ro.x; r->ro[1] = ro.y; r->ro[2] = ro.z; r->rd[0] = rd.x; r->rd[1] = rd.y; r->rd[2] = rd.z;
+            r->t = hit ? out->t : INFINITY; r->tri = hit ? out->tri : -1;
+            r->light = light; r->occluded = kind == ORC_RAY_SHADOW && hit && out->tri != light;
+        }
+        else cc->overflow = 1;
+    }
+    return hit;
+}
+
 /* ---- hemisphere / lobe samplers, pathtracer.cpp:606-611 and :618-623 ------------------------------
  * pole: the axis the sample is built around (n or r); basis_from: vector crossed to make u,v
  * (n for the hemisphere form, r for the lobe form); nx_test: |n.x| against thr chooses the helper. */
@@ -411,7 +454,7 @@ static inline v3 sample_about(v3 n_for_test, float thr, v3 basis_from, v3 pole, 
 }
 
 /* PathTracer::SampleTriangle + DirectIllumimation, pathtracer.cpp:494-531 */
-static v3 direct_illumination(const orc_scene* s, v3 p, v3 n, v3 diffuse, rng_t* rng, uint32_t* ray)
+static v3 direct_illumination_c(const orc_scene* s, v3 p, v3 n, v3 diffuse, rng_t* rng, uint32_t* ray, count_t* cc)
 {
     if (s->nl == 0) return V(0.0f, 0.0f, 0.0f);
     int lightId = (int)floorf(rnd(rng) * (float)s->nl);
@@ -427,13 +470,17 @@ static v3 direct_illumination(const orc_scene* s, v3 p, v3 n, v3 diffuse, rng_t*
     if (ndl <= 0.0f) return V(0.0f, 0.0f, 0.0f);
     hit_t h;
     uint32_t r = (*ray)++;
-    if (closest_hit(s, p, l, rng, r, &h))
+    if (cc ? closest_hit_counted(s, p, l, rng, r, ORC_RAY_SHADOW, ltri, cc, &h) : closest_hit(s, p, l, rng, r, &h))
     {
         if (h.tri != ltri) return V(0.0f, 0.0f, 0.0f);
     }
     const orc_material* lm = &s->mats[s->material[ltri]];
     v3 lColor = muls(ld3(lm->emissive), lm->emissive_intensity);
     return muls(mulv(lColor, diffuse), ndl);
+}
+static v3 direct_illumination(const orc_scene* s, v3 p, v3 n, v3 diffuse, rng_t* rng, uint32_t* ray)
+{
+    return direct_illumination_c(s, p, n, diffuse, rng, ray, NULL);
 }
 
 /* One surface interaction of PathTracer::Trace (pathtracer.cpp:551-727): everything between the
@@ -601,6 +648,36 @@ static v3 trace(const orc_scene* s, v3 ro, v3 rd, int D, rng_t* rng)
         T = mulv(T, b.weight);
         ro = b.p; rd = b.dir;
     }
+    return L;
+}
+
+/* trace() with the counters of orc_render_counted: the same calls in the same order, so the same radiance bit for bit */
+static v3 trace_counted(const orc_scene* s, v3 ro, v3 rd, int D, rng_t* rng, count_t* cc)
+{
+    v3 L = V(0.0f, 0.0f, 0.0f), T = V(1.0f, 1.0f, 1.0f);
+    int depth = 0, iter = 0, inside = 0;
+    uint32_t ray = 0;
+    cc->px[ORC_CNT_PATHS]++;
+    for (;;)
+    {
+        hit_t h; bounce_t b;
+        const uint32_t r = ray++;
+        if (!closest_hit_counted(s, ro, rd, rng, r, r == 0 ? ORC_RAY_CAMERA : ORC_RAY_BOUNCE, -1, cc, &h)) break;
+        /* shade() looks up the normal map of every hit, the other four maps only below the depth limit (:571) */
+        const int32_t* tx = s->mats[s->material[h.tri]].tex;
+        cc->px[ORC_CNT_SHADED]++;
+        cc->px[ORC_CNT_TEX_SHADE] += (tx[1] >= 0) + (iter < D ? (tx[0] >= 0) + (tx[2] >= 0) + (tx[3] >= 0) + (tx[4] >= 0) : 0);
+        if (!shade(s, ro, rd, &h, D, &depth, &iter, &inside, rng, &b)) break;
+        L = add(L, mulv(T, b.e));
+        if (b.diffuse_bounce)
+        {
+            v3 di = direct_illumination_c(s, b.p, b.n, b.diffuse, rng, &ray, cc);
+            L = add(L, mulv(T, di));
+        }
+        T = mulv(T, b.weight);
+        ro = b.p; rd = b.dir;
+    }
+    cc->px[ORC_CNT_RAY_NUMBERS] += ray;
     return L;
 }
 
@@ -816,6 +893,65 @@ void orc_render(const orc_scene* s, const orc_camera* cam, int W, int H, int D,
     free(dirs_all);
 }
 
+int orc_render_counted(const orc_scene* s, const orc_camera* cam, int W, int H, int D,
+                       uint32_t first_sample, uint32_t spp, uint64_t seed, int rank, int world,
+                       float* total, int64_t* counts, orc_ray_rec* rec, const int64_t* rec_offsets, int64_t rec_capacity, int threads)
+{
+    frame_t f; frame_setup(cam, W, H, &f);
+    int tiles_x = (W + ORC_TILE - 1) / ORC_TILE, tiles_y = (H + ORC_TILE - 1) / ORC_TILE;
+    if (world < 1) world = 1;
+#ifdef _OPENMP
+    if (threads <= 0) threads = omp_get_max_threads();
+#endif
+    int brute = 0;
+    for (int m = 0; m < s->nm; m++) brute |= s->mats[m].tex[5] >= 0;
+    float* dirs_all = (float*)malloc((size_t)W * H * 3 * sizeof(float));
+    for (int i = 0; i < H; i++) primary_row(&f, W, i, dirs_all + (size_t)i * W * 3);
+    memset(counts, 0, (size_t)W * H * ORC_CNT_N * sizeof(int64_t));
+    int overflow = 0;
+    /* every pixel's counters and records are written by the one thread that traces it: the result does not depend on the
+       thread count */
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads) reduction(| : overflow)
+#endif
+    for (int t = 0; t < tiles_x * tiles_y; t++)
+    {
+        const int ty = t / tiles_x, tx = t % tiles_x;
+        const int tile = ty * tiles_x + (tx + 3 * ty) % tiles_x;
+        if (tile % world != rank) continue;
+        for (int i = ty * ORC_TILE; i < (ty + 1) * ORC_TILE && i < H; i++)
+            for (int j = tx * ORC_TILE; j < (tx + 1) * ORC_TILE && j < W; j++)
+            {
+                const size_t pix = (size_t)i * W + j;
+                count_t cc;
+                cc.px = counts + pix * ORC_CNT_N; cc.brute = brute; cc.overflow = 0; cc.pixel = (uint32_t)pix;
+                cc.rec = rec ? rec + rec_offsets[pix] : NULL;
+                cc.rec_end = rec ? rec + rec_capacity : NULL;
+                uint32_t pkey = pixel_key(seed, (uint32_t)pix);
+                size_t px = ((size_t)(H - 1 - i) * W + j) * 3;
+                v3 acc = total ? ld3(total + px) : V(0.0f, 0.0f, 0.0f);
+                v3 rayDir0 = ld3(dirs_all + pix * 3);
+                for (uint32_t k = 0; k < spp; k++)
+                {
+                    rng_t rng; rng_init(&rng, pkey, first_sample + k);
+                    cc.sample = first_sample + k;
+                    v3 camPos = f.pos;
+                    v3 focalPoint = add(camPos, muls(rayDir0, cam->focal_dist));
+                    float r1 = rnd(&rng), r2 = rnd(&rng), off[2];
+                    orc_sample_circle(r1, r2, off);
+                    off[0] = off[0] * cam->aperture; off[1] = off[1] * cam->aperture;
+                    camPos = add(camPos, add(muls(f.right, off[0]), muls(f.up, off[1])));
+                    v3 rayDir = normalize(sub(focalPoint, camPos));
+                    acc = add(acc, trace_counted(s, camPos, rayDir, D, &rng, &cc));
+                }
+                if (total) { total[px] = acc.x; total[px + 1] = acc.y; total[px + 2] = acc.z; }
+                overflow |= cc.overflow;
+            }
+    }
+    free(dirs_all);
+    return overflow ? -1 : 0;
+}
+
 /* RenderFrame (pathtracer.cpp:741-817) for ONE frame with the draws of the reference's single engine on tape, in the order its
  * loop consumes them when it runs on one thread: rows top to bottom, columns left to right, per pixel the two draws of
  * SampleCircle (:736-737) and then the path's (recursive form, g++'s operand order).  Adds into `total` (rows bottom-up, :796)
@@ -849,3 +985,9 @@ int orc_render_tape(const orc_scene* s, const orc_camera* cam, int W, int H, int
     return r.tape_pos;
 }
 
+
+void orc_intersect_many(int64_t n, const float* ro, const float* rd, const float* tri9, float* out3)
+{
+    for (int64_t i = 0; i < n; i++)
+        orc_intersect_triangle(ro + 3 * i, rd + 3 * i, tri9 + 9 * i, tri9 + 9 * i + 3, tri9 + 9 * i + 6, out3 + 3 * i);
+}

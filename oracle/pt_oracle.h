@@ -91,6 +91,30 @@ void orc_render(const orc_scene* s, const orc_camera* cam, int width, int height
                 uint32_t first_sample, uint32_t spp, uint64_t seed, int rank, int world,
                 float* total, uint8_t* rgb8, int threads);
 
+/* orc_render that also COUNTS, per pixel (counts [H][W][ORC_CNT_N], rows top-down, the kernels' pixel index), what the trace
+ * kernels' STATS build counts (include/ptk.h ptk_stats): paths, closest-hit traversals by kind, surface interactions shaded,
+ * texel lookups at shading time, opacity texels looked up, and the sum over paths of the final ray number.  The opacity count
+ * follows the brute-force ascending-index candidate order (orc_hit_brute), the FLAT kernel's.  rec (may be NULL): one record
+ * per closest-hit traversal; pixel p's records start at rec[rec_offsets[p]] (exclusive prefix sums of a previous call's
+ * camera + bounce + shadow counts), in the order they are cast.  total (may be NULL) is accumulated as orc_render does.
+ * Returns 0, or -1 when rec_capacity was too small.  The result does not depend on the thread count. */
+enum { ORC_CNT_PATHS = 0, ORC_CNT_CAMERA, ORC_CNT_BOUNCE, ORC_CNT_SHADOW, ORC_CNT_SHADED, ORC_CNT_TEX_SHADE, ORC_CNT_TEX_OPACITY,
+       ORC_CNT_RAY_NUMBERS, ORC_CNT_N };
+enum { ORC_RAY_CAMERA = 0, ORC_RAY_BOUNCE = 1, ORC_RAY_SHADOW = 2 };
+typedef struct {
+    uint32_t pixel, sample, ray;   /* ray: the path's ray number (the opacity draws' key) */
+    int32_t kind;                  /* ORC_RAY_* */
+    float ro[3], rd[3];
+    float t; int32_t tri;          /* closest accepted hit; +inf / -1 on a miss */
+    int32_t light;                 /* shadow rays: the sampled light triangle; -1 otherwise */
+    int32_t occluded;              /* shadow rays: the closest hit is not the light triangle */
+} orc_ray_rec;                     /* 56 bytes */
+int orc_render_counted(const orc_scene* s, const orc_camera* cam, int width, int height, int max_depth,
+                       uint32_t first_sample, uint32_t spp, uint64_t seed, int rank, int world,
+                       float* total, int64_t* counts, orc_ray_rec* rec, const int64_t* rec_offsets, int64_t rec_capacity, int threads);
+/* Moeller-Trumbore of orc_intersect_triangle on n (ray, triangle) pairs: ro, rd [n][3], tri9 [n][9] -> out3 [n][3] */
+void orc_intersect_many(int64_t n, const float* ro, const float* rd, const float* tri9, float* out3);
+
 /* Primary ray directions before DOF, row-major top-down [H][W][3]; follows the incremental
  * `pixel += camRight*deltaX` arithmetic of pathtracer.cpp:755-766,782-785,814. */
 void orc_primary_dirs(const orc_camera* cam, int width, int height, float* out);

@@ -1,0 +1,161 @@
+"""The oracle's counting render (Oracle.render_counted, the reference for the trace kernels' counters) and the per-ray bounds
+of tests/stats_bounds.py, on the CPU.  tests/test_gpu_stats_counters.py compares the kernels' ptk_stats with both."""
+import numpy as np
+import pytest
+
+import stats_bounds as SB
+from oracle import oracle_binding as OB
+from test_gpu_random_scenes import random_scene
+
+W, H, D = 40, 28, 6
+
+
+def _oracle(seed, n_tris, tex, aperture=None):
+    arrays, cam = random_scene(seed, n_tris, tex)
+    if aperture is not None:
+        cam["aperture"] = aperture
+    o = OB.Oracle(arrays)
+    ocam = OB.make_camera(cam["pos"], cam["dir"], cam["up"], cam["focal"], cam["fovy"], cam["focal_dist"], cam["aperture"])
+    return o, ocam, arrays
+
+
+@pytest.mark.parametrize("seed,n_tris,tex,aperture", [(12, 16, True, 0.08), (14, 300, True, None), (15, 300, False, 0.0)])
+def test_counted_render_is_the_render(seed, n_tris, tex, aperture):
+    """Counting changes nothing that is traced: the same accumulator bit for bit, and the same counts on 1 and 5 threads."""
+    o, ocam, _ = _oracle(seed, n_tris, tex, aperture)
+    ref, _ = o.render(ocam, W, H, D, 3, 5, seed)
+    a = o.render_counted(ocam, W, H, D, 3, 5, seed, threads=5, dump=True)
+    b = o.render_counted(ocam, W, H, D, 3, 5, seed, threads=1, dump=True)
+    assert np.array_equal(a["total"], ref) and np.array_equal(b["total"], ref)
+    assert np.array_equal(a["counts"], b["counts"])
+    assert np.array_equal(a["rays"], b["rays"])
+    c = a["counts"]
+    assert (c[..., 0] == 5).all()                                     # every pixel, every sample: one path
+    assert (c[..., 1] == 5).all()                                     # ... and one camera ray each
+    assert (c[..., 2] > 0).any() and (c[..., 3] > 0).any() and (c[..., 5] > 0).any() == tex
+    o.close()
+
+
+@pytest.mark.parametrize("seed,n_tris,tex", [(12, 16, True), (14, 300, True)])
+def test_counts_add_over_sample_ranges_and_tiles(seed, n_tris, tex):
+    o, ocam, _ = _oracle(seed, n_tris, tex)
+    whole = o.render_counted(ocam, W, H, D, 0, 8, seed)["counts"]
+    halves = o.render_counted(ocam, W, H, D, 0, 4, seed)["counts"] + o.render_counted(ocam, W, H, D, 4, 4, seed)["counts"]
+    assert np.array_equal(whole, halves)
+    parts = [o.render_counted(ocam, W, H, D, 0, 8, seed, rank=r, world=3)["counts"] for r in range(3)]
+    owned = [p[..., 0] > 0 for p in parts]
+    assert (sum(m.astype(int) for m in owned) == 1).all()               # the ranks' pixels partition the frame
+    assert np.array_equal(sum(parts), whole)
+    o.close()
+
+
+@pytest.mark.parametrize("seed,n_tris,tex,aperture", [(12, 16, True, 0.08), (14, 300, True, None), (17, 6000, False, 0.0)])
+def test_ray_records_are_the_counts(seed, n_tris, tex, aperture):
+    """Every path's rays are numbered 0, 1, ... in the order they are cast, ray 0 is its camera ray, a shadow ray is followed by the
+    bounce it belongs to, and the counters are what the records say: traversals by kind, the final ray numbers, hits shaded."""
+    o, ocam, arrays = _oracle(seed, n_tris, tex, aperture)
+    r = o.render_counted(ocam, W, H, D, 0, 3, seed, dump=True)
+    c, rays = r["counts"].reshape(W * H, -1), r["rays"]
+    key = rays["pixel"].astype(np.int64) * 3 + rays["sample"]
+    assert (np.diff(key) >= 0).all(), "records are pixel by pixel, sample by sample"
+    start = np.r_[True, key[1:] != key[:-1]]
+    idx = np.arange(len(rays)) - np.maximum.accumulate(np.where(start, np.arange(len(rays)), 0))
+    assert np.array_equal(rays["ray"], idx), "ray numbers are 0 .. n-1 in casting order"
+    assert np.array_equal(rays["kind"] == OB.RAY_CAMERA, rays["ray"] == 0)
+    sh = np.nonzero(rays["kind"] == OB.RAY_SHADOW)[0]
+    assert (sh + 1 < len(rays)).all() and (rays["kind"][sh + 1] == OB.RAY_BOUNCE).all() and (key[sh + 1] == key[sh]).all()
+    assert (rays["light"][sh] >= 0).all() and (rays["light"][rays["kind"] != OB.RAY_SHADOW] == -1).all()
+    assert np.array_equal(rays["occluded"][sh] != 0, (rays["tri"][sh] >= 0) & (rays["tri"][sh] != rays["light"][sh]))
+    n_paths = len(np.unique(key))
+    assert n_paths == W * H * 3 and c[:, 0].sum() == n_paths
+    assert c[:, 7].sum() == len(rays)                                  # final ray number of every path = its rays
+    assert np.array_equal(c[:, 1] + c[:, 2] + c[:, 3], c[:, 7])
+    for kind, col in ((OB.RAY_CAMERA, 1), (OB.RAY_BOUNCE, 2), (OB.RAY_SHADOW, 3)):
+        assert np.array_equal(np.bincount(rays["pixel"][rays["kind"] == kind], minlength=W * H), c[:, col])
+    hits = (rays["kind"] != OB.RAY_SHADOW) & (rays["tri"] >= 0)
+    assert np.array_equal(np.bincount(rays["pixel"][hits], minlength=W * H), c[:, 4])
+    # the records hold the oracle's closest hits (opacity draws are keyed on the path: checked on opaque scenes)
+    for i in np.linspace(0, len(rays) - 1, 200).astype(int) if not tex else ():
+        h, tri, tuv = o.hit(rays["ro"][i], rays["rd"][i])
+        assert (tri, tuv[0] if h else np.inf) == (rays["tri"][i], rays["t"][i])
+    o.close()
+
+
+def test_opacity_texels_follow_the_ascending_candidate_order():
+    """A ray through a stack of opacity layers reads one texel per layer nearer than the best accepted so far, in ascending triangle
+    index order: layers listed far to near are each read once until one is accepted."""
+    from pbrpathtracer_amd import ptk
+    z = np.array([-1.0, -0.5, 0.0, 0.5], np.float32)          # ascending index = far to near as seen from +z
+    n = len(z)
+    verts = np.zeros((n, 9), np.float32)
+    for i, zz in enumerate(z):
+        verts[i] = [-50, -50, zz, 150, -50, zz, -50, 150, zz]
+    mats = np.zeros(2, ptk.MATERIAL_DTYPE)
+    mats["tex"] = -1
+    mats[1]["tex"][5] = 0
+    mats["diffuse"] = 0.5
+    textures = np.zeros(1, ptk.TEXTURE_DTYPE); textures[0] = (1, 1, 0)
+    arrays = dict(verts=verts, normals=np.tile(np.array([0, 0, 1], np.float32), (n, 3)), uvs=np.zeros((n, 6), np.float32),
+                  tbn=np.tile(np.array([0, 0, 1, 1, 0, 0, 0, 1, 0], np.float32), (n, 1)), smoothing=np.zeros(n, np.uint8),
+                  material=np.array([1, 1, 1, 1], np.int32), materials=mats, textures=textures,
+                  texels=np.array([255, 0, 0, 255], np.uint8), lights=np.zeros(0, np.int32))
+    o = OB.Oracle(arrays)
+    cam = OB.make_camera([0, 0, 5], [0, 0, -1], [0, 1, 0], 0.05, 20.0, 5.0, 0.0)
+    c = o.render_counted(cam, 8, 8, 1, 0, 1, 1, dump=True)
+    # opacity 1 everywhere: ascending order accepts z=-1, then each nearer layer again - four texels, the nearest one is the hit
+    cam_rays = c["rays"][c["rays"]["kind"] == OB.RAY_CAMERA]
+    assert (cam_rays["tri"] == 3).all()
+    bounce = c["rays"][c["rays"]["kind"] == OB.RAY_BOUNCE]              # (bounces leave the stack upwards: no candidates)
+    assert len(bounce) and (bounce["tri"] == -1).all()
+    assert (c["counts"][..., 6] == 4).all()
+    o.close()
+
+
+def _node(boxes, links):
+    """A BVH4 record (ptk_device.h) with origin 0 and grid step 1/8: boxes [(lo, hi) in grid units] or None for an empty slot."""
+    rec = np.zeros(16, np.float32)
+    u = rec.view(np.uint32)
+    rec[3:6] = 0.125
+    for k in range(4):
+        lo, hi = boxes[k] if k < len(boxes) and boxes[k] is not None else ((255, 255, 255), (0, 0, 0))
+        u[6 + k] = np.uint32(np.int32(links[k] if k < len(links) else 0).view(np.uint32))
+        for a in range(3):
+            u[10 + a] |= np.uint32(lo[a]) << np.uint32(8 * k)
+            u[13 + a] |= np.uint32(hi[a]) << np.uint32(8 * k)
+    return rec
+
+
+def _leaf(first, count):
+    return ~((first << 3) | (count - 1))
+
+
+def _wall(x):
+    return [x, 0.5, 0.5, x, 3.5, 0.5, x, 0.5, 3.5]
+
+
+def test_bounds_on_a_hand_built_tree():
+    """Root: slot 0 = node 1 over x in [4, 12], slot 1 = a leaf of two walls at x = 21, 23 (box x in [20, 24]); node 1: one wall
+    at x = 5 and one at x = 11 in leaves of their own.  Walls span y, z in [0.5, 3.5]; rays run along x at y = z = 1."""
+    g = lambda x0, x1: ((int(x0 * 8), 0, 0), (int(x1 * 8), 32, 32))
+    nodes = np.stack([_node([g(4, 12), g(20, 24)], [1, _leaf(0, 2)]),
+                      _node([g(4, 6), g(10, 12)], [_leaf(2, 1), _leaf(3, 1)])])
+    verts = np.array([_wall(11), _wall(21), _wall(5), _wall(23)], np.float32)       # scene triangles 0..3
+    order = np.array([1, 3, 2, 0], np.int32)                                         # leaf records -> scene triangles
+    rays = np.zeros(4, OB.RAY_DTYPE)
+    rays["light"] = -1
+    # 0: bounce ray from x = 0 along +x, closest hit the wall at x = 5 (t = 5)
+    rays[0] = (0, 0, 1, OB.RAY_BOUNCE, (0, 1, 1), (1, 0, 0), 5.0, 2, -1, 0)
+    # 1: camera ray along -x: every box lies behind it
+    rays[1] = (0, 0, 0, OB.RAY_CAMERA, (0, 1, 1), (-1, 0, 0), np.inf, -1, -1, 0)
+    # 2: shadow ray from x = 7 to its light, the wall at x = 11 (t = 4), not occluded
+    rays[2] = (0, 0, 2, OB.RAY_SHADOW, (7, 1, 1), (1, 0, 0), 4.0, 0, 0, 0)
+    # 3: shadow ray from x = 0 to the wall at x = 21, occluded by the wall at x = 5
+    rays[3] = (0, 0, 2, OB.RAY_SHADOW, (0, 1, 1), (1, 0, 0), 5.0, 2, 1, 1)
+    opaque = np.array([True, True, False, False])                                   # walls x = 11 and x = 21 have opacity maps
+    b = SB.ray_bounds(nodes, order, verts, rays, opaque, OB.intersect_many)
+    assert b["node_lo"].tolist() == [2, 1, 2, 1]
+    assert b["node_hi"].tolist() == [2, 1, 2, 2]
+    assert b["tri_lo"].tolist() == [1, 0, 2, 1]            # shadow rays: + the light pre-test
+    assert b["tri_hi"].tolist() == [4, 0, 4, 5]
+    assert b["opa_lo"].tolist() == [0, 0, 1, 1]
+    assert b["opa_hi"].tolist() == [2, 0, 3, 3]
