@@ -115,7 +115,8 @@ void ptk_destroy(ptk_ctx* ctx);
 /* replaces BuildBVH (pathtracer.cpp:260-274, mesh.cpp:169-211): stages the scene, builds the BVH (own builders; closest
  * hit is tree-independent) and leaves everything resident in HBM.  Scenes of >= 4096 triangles are built ON THE GPU - binned
  * SAH level by level, collapse to the 4-wide quantised nodes, record packing (csrc/bvh_device.hip); smaller ones, and any
- * scene whose device-built tree would not fit the traversal stack, by the host builder (option "device_build" = 0 forces it).
+ * scene whose device-built tree would not fit the traversal stack or the device builder's node store, by the host builder
+ * (option "device_build" = 0 forces it).
  * Limits (PTK_ERR_LIMIT): at most 89 478 485 triangles (the walk addresses its 48-byte records with 32-bit byte offsets),
  * |coordinate| < 2^61, a tree that defers at most PTK_MAX_BVH_DEPTH entries (the host builder always meets that). */
 int ptk_upload_scene(ptk_ctx* ctx, const ptk_scene_desc* scene);
@@ -270,7 +271,8 @@ int ptk_probe_unpack(ptk_ctx* ctx, int world, const float* host_packed /* all ra
  * a pass whose sample buffer cannot be allocated is halved and tried again - more passes, the same image;
  * "bvh_leaf_max" (1..8), "bvh_trav_cost" (SAH cost of a node visit in triangle tests), "bvh_verbose" = builder tuning, process-wide,
  * effective at the next ptk_upload_scene (0 = the builders' own choices: 4 / 1.0 / quiet): they shape the tree, and closest hits do
- * not depend on the tree.
+ * not depend on the tree (tests/test_gpu_bvh_limits.py holds both builders to the brute-force closest hit at every leaf_max
+ * 1..8, at a full traversal stack and out to the largest accepted coordinate).
  * ONE option changes results, within the stated tolerance: "contract" = 0 (default: every kernel bit-identical to the CPU oracle),
  * 1 = the trace kernels built with -ffp-contract=fast (a * b + c fuses), 2 = ... and 1-ulp hardware reciprocal / square root / rsq:
  * per-channel RMSE of the mean image against the exact kernels <= 1e-3 (measured ~1e-5 .. 9e-5, tests/test_gpu_contract.py).

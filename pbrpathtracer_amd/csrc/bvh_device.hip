@@ -235,7 +235,7 @@ __device__ __forceinline__ void box_grow(BinBox& b, const uint32_t* w)
 
 // One thread per node of the level: sweep its histograms, close it as a leaf or split it (bvh_build.cpp Builder::build).
 __global__ __launch_bounds__(kThreads) void level_split_kernel(BNode* __restrict__ nodes, const uint32_t* __restrict__ hist, uint32_t* counters, int lvl_start, int lvl_end,
-                                                               int level /* 1-based */, int max_depth, int leaf_max, float trav_cost)
+                                                               int level /* 1-based */, int max_depth, int leaf_max, float trav_cost, int node_cap)
 {
     const int id = lvl_start + blockIdx.x * kThreads + threadIdx.x;
     if (id >= lvl_end) return;
@@ -301,6 +301,9 @@ __global__ __launch_bounds__(kThreads) void level_split_kernel(BNode* __restrict
         if (best_axis >= 0 && level + need_levels(max(nl, count - nl), leaf_max) > max_depth) { atomicExch(&counters[CNT_FAIL], 1u); close_leaf(); return; }
     }
     const int c0 = (int)atomicAdd(&counters[CNT_NEXT_FREE], 2u);
+    // A parity split may put every triangle on one side (identical triangles: each pair has an even chance to stay together),
+    // so the tree can outgrow 2 n nodes: give up here - the host builder takes over - instead of writing past the store
+    if (c0 + 2 > node_cap) { atomicExch(&counters[CNT_FAIL], 1u); close_leaf(); return; }
     BNode L, R;
     if (best_axis < 0)
     {
@@ -596,7 +599,7 @@ bool build_bvh_device(const float* d_verts, int32_t n, int max_stack, int leaf_m
                                    d_boxes, d_node_of, d_bnodes, d_hist, n, ls, count, level);
             else
                 hipLaunchKernelGGL(level_bin_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, stream, d_boxes, d_node_of, d_bnodes, d_hist, n, ls, level);
-            hipLaunchKernelGGL(level_split_kernel, dim3(blocks_for(count, kThreads)), dim3(kThreads), 0, stream, d_bnodes, d_hist, d_cnt, ls, lvl_end, level, max_stack, leaf_max, trav_cost);
+            hipLaunchKernelGGL(level_split_kernel, dim3(blocks_for(count, kThreads)), dim3(kThreads), 0, stream, d_bnodes, d_hist, d_cnt, ls, lvl_end, level, max_stack, leaf_max, trav_cost, (int)node_cap);
             DCHK(hipGetLastError());
             DCHK(hipMemcpyAsync(h_cnt, d_cnt, CNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             DCHK(hipStreamSynchronize(stream));

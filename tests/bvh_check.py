@@ -66,3 +66,14 @@ def check_bvh(nodes: np.ndarray, order: np.ndarray, verts: np.ndarray, max_stack
     assert (seen_tri == 1).all(), "triangle in %s leaves" % np.unique(seen_tri)
     assert stack_need <= max_stack, (stack_need, max_stack)
     return dict(depth=depth, stack_need=stack_need, children_per_node=children / N, nodes=N)
+
+
+def leaf_sizes(nodes: np.ndarray) -> np.ndarray:
+    """Histogram of leaf sizes of a downloaded BVH4: [9] int, entry c = leaves of c triangles (decoded as the walk decodes a leaf
+    link: ~link = first << 3 | (count - 1))."""
+    raw = np.ascontiguousarray(nodes, np.float32).view(np.uint32)
+    link = raw[:, 6:10].view(np.int32)
+    lo = np.stack([(raw[:, 10 + a][:, None] >> (8 * np.arange(4))) & 255 for a in range(3)], axis=-1)
+    hi = np.stack([(raw[:, 13 + a][:, None] >> (8 * np.arange(4))) & 255 for a in range(3)], axis=-1)
+    leaf = (lo <= hi).all(axis=2) & (link < 0)
+    return np.bincount(((~link[leaf]) & 7) + 1, minlength=9)

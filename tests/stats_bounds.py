@@ -18,6 +18,15 @@ Opacity texels: a candidate reads one when Moeller-Trumbore accepts it and it is
 a smaller index).  Lower bound: the candidates of the lower-bound leaves nearer than the final hit, the final hit itself, and the
 light pre-test.  Upper bound: every candidate of the upper-bound leaves that Moeller-Trumbore accepts, and the light pre-test.
 Moeller-Trumbore is the oracle's (oracle_binding.intersect_many), bit-identical to the kernels' - no margin there.
+
+Deferred entries (stack_lower_bound).  At an interior node walk_step writes every child box the ray enters to the LDS stack
+except the one with the smallest key - the entry distance t_near with the slot in its two low bits - and goes on with that one.
+The kernel's t_near lies between the entry distance of the quantised box inflated by MARGIN and that of the box shrunk by
+MARGIN, so a child is surely pushed when the ray surely enters it before its final t and another child it surely enters has
+a sure entry earlier than this child's earliest possible one - or has the very same quantised box in a lower slot (the same
+bytes give the same t_near, bit for bit, and the slot bits break the tie).  The walk pops nothing while it goes on into interior nodes,
+so along the chain of children that are surely the nearest the pushes add up: their sum is a lower bound on the entries the
+ray's stack holds at once.
 """
 import numpy as np
 
@@ -146,3 +155,55 @@ def ray_bounds(nodes, order, verts, rays, opacity_tris=None, intersect=None):
         np.add.at(hi, r[hit], 1)
     out.update(opa_lo=lo, opa_hi=hi)
     return out
+
+
+def stack_lower_bound(nodes, verts, ro, rd, t):
+    """nodes [N,16] float32, verts [n,9] float32 (for the margin), rays ro, rd [m,3] with no direction component of magnitude in
+    (0, 1e-18) (where the kernel's clamp of 1 / d would make its slab distances smaller than the exact ones), t [m] the final
+    closest-hit distance (inf: a miss).  Returns int64 [m]: entries that are surely on the ray's traversal stack at once."""
+    bmin, bmax, valid, link = decode(nodes)
+    raw = np.ascontiguousarray(nodes, np.float32).view(np.uint32)
+    quant = np.stack([(raw[:, 10 + a][:, None] >> (8 * np.arange(4))) & 255 for a in range(6)], axis=-1)      # [N, 4, 6]
+    ro = np.asarray(ro, np.float64); rd = np.asarray(rd, np.float64); t = np.asarray(t, np.float64)
+    m = len(ro)
+    extent = float(np.abs(verts).max()) if len(verts) else 1.0
+    margin = (MARGIN * (np.abs(ro).max(axis=1) + 2.0 * extent))[:, None]
+    early = 1.0 - 2.0 ** -20          # keys keep all but two low bits of t_near: a sure order needs a few ulps between the two
+    depth = np.zeros(m, np.int64)
+    ray = np.arange(m)
+    node = np.zeros(m, np.int64)
+    while len(ray):
+        sure = np.zeros((len(ray), 4), bool)
+        t_sure = np.full((len(ray), 4), np.inf)         # latest possible entry (shrunk box)
+        t_soon = np.full((len(ray), 4), np.inf)         # earliest possible entry (inflated box), inf: surely not entered
+        for k in range(4):
+            v = valid[node, k]
+            lo_s, hi_s = bmin[node, k] + margin[ray], bmax[node, k] - margin[ray]
+            tn, tf = _slabs(lo_s, hi_s, ro[ray], rd[ray], False)
+            sure[:, k] = v & (lo_s <= hi_s).all(axis=1) & (np.maximum(tn, 0.0) <= tf) & (tn < t[ray])
+            t_sure[:, k] = np.where(sure[:, k], tn, np.inf)
+            tn, tf = _slabs(bmin[node, k] - margin[ray], bmax[node, k] + margin[ray], ro[ray], rd[ray], False)
+            t_soon[:, k] = np.where(v & (np.maximum(tn, 0.0) <= tf), tn, np.inf)
+        q = quant[node]                                  # [r, 4, 6] box bytes: equal rows give bit-identical t_near
+        pushed = np.zeros(len(ray), np.int64)
+        nearest = np.full(len(ray), -1)
+        for k in range(4):
+            others = [j for j in range(4) if j != k]
+            # surely pushed: another child surely entered, surely earlier
+            before = np.zeros(len(ray), bool)
+            for j in others:
+                same = (q[:, j] == q[:, k]).all(axis=1)
+                before |= sure[:, j] & (((t_sure[:, j] < t_soon[:, k] * early) & (t_soon[:, k] > 0.0)) | (same & (j < k)))
+            pushed += sure[:, k] & before
+            # surely the nearest: entered, and every other child either surely not entered or surely entered later
+            first = sure[:, k].copy()
+            for j in others:
+                same = (q[:, j] == q[:, k]).all(axis=1)
+                first &= (t_soon[:, j] == np.inf) | ((t_sure[:, k] < t_soon[:, j] * early) & (t_soon[:, j] > 0.0)) | (same & (k < j))
+            nearest = np.where(first, k, nearest)
+        depth[ray] += pushed
+        has = nearest >= 0
+        nxt = link[node[has], nearest[has]]
+        inner = nxt >= 0
+        ray, node = ray[has][inner], nxt[inner].astype(np.int64)
+    return depth

@@ -159,3 +159,24 @@ def test_bounds_on_a_hand_built_tree():
     assert b["tri_hi"].tolist() == [4, 0, 4, 5]
     assert b["opa_lo"].tolist() == [0, 0, 1, 1]
     assert b["opa_hi"].tolist() == [2, 0, 3, 3]
+
+
+def test_stack_lower_bound_on_a_hand_built_tree():
+    """Root: node 1 over x in [2, 8] and leaves over [10, 12], [20, 24], [30, 31]; node 1: node 2 over [2, 4], a leaf with the very
+    same box, a leaf over [5, 8]; node 2: leaves over [2, 3] and [3.5, 4].  Boxes span y, z in [0, 4], the walls y, z in [0.5, 3.5]."""
+    g = lambda x0, x1: ((int(x0 * 8), 0, 0), (int(x1 * 8), 32, 32))
+    nodes = np.stack([_node([g(2, 8), g(10, 12), g(20, 24), g(30, 31)], [1, _leaf(0, 1), _leaf(1, 1), _leaf(2, 1)]),
+                      _node([g(2, 4), g(2, 4), g(5, 8)], [2, _leaf(3, 1), _leaf(4, 1)]),
+                      _node([g(2, 3), g(3.5, 4)], [_leaf(5, 1), _leaf(6, 1)])])
+    verts = np.array([_wall(11), _wall(21), _wall(30.5), _wall(3), _wall(6), _wall(2.5), _wall(3.75)], np.float32)
+    ro = np.array([(0, 0.25, 0.25), (0, 1, 1), (40, 0.25, 0.25), (2.5, 0.25, 0.25), (0, 0.25, 0.25), (0, 0.25, 0.25)], np.float32)
+    rd = np.array([(1, 0, 0), (1, 0, 0), (-1, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0)], np.float32)
+    t = np.array([np.inf, 11.0, np.inf, np.inf, np.inf, np.inf])
+    b = SB.stack_lower_bound(nodes, verts, ro, rd, t)
+    # 0: misses every wall, enters every box: 3 at the root, 2 in node 1 (the twin box in the higher slot, [5, 8]), 1 in node 2
+    # 1: closest hit at t = 11: only [10, 12] of the root's other children is surely entered before it
+    # 2: from x = 40 backwards: the root's nearest child is the leaf [30, 31], the walk stops going down - the 3 others stay
+    # 3: from inside node 2's box: same as 0 (entry distances below zero are the nearest)
+    # 4: from x = 0 backwards: every box lies behind the ray
+    # 5: along +y through x = 0: outside every box
+    assert b.tolist() == [6, 4, 3, 6, 0, 0]
