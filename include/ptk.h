@@ -275,7 +275,8 @@ int ptk_probe_unpack(ptk_ctx* ctx, int world, const float* host_packed /* all ra
  * 1..8, at a full traversal stack and out to the largest accepted coordinate).
  * ONE option changes results, within the stated tolerance: "contract" = 0 (default: every kernel bit-identical to the CPU oracle),
  * 1 = the trace kernels built with -ffp-contract=fast (a * b + c fuses), 2 = ... and 1-ulp hardware reciprocal / square root / rsq:
- * per-channel RMSE of the mean image against the exact kernels <= 1e-3 (measured ~1e-5 .. 9e-5, tests/test_gpu_contract.py).
+ * per-channel RMSE of the mean image against the exact kernels <= 1e-3 (measured ~1e-5 .. 9e-5, tests/test_gpu_contract.py);
+ * sample by sample and reproducibility bit for bit: tests/test_gpu_contract_samples.py.
  * No environment variable reaches the library. */
 int ptk_set_option(ptk_ctx* ctx, const char* name, double value);
 
@@ -309,9 +310,11 @@ int ptk_probe_primary_dirs(ptk_ctx* ctx, float* host_out /* [H][W][3] top-down *
  * on tape: light sample, n.l test, shadow walk and visibility rule exactly as the trace kernel applies them; out3 = the value
  * the reference's function returns (zero when unlit).  Inputs / output [n][3]. */
 int ptk_probe_direct(ptk_ctx* ctx, int n, const float* points, const float* normals, const float* diffuse, const float* tape3, float* out3);
-/* the kernels' exact-arithmetic helpers on an array: op 0 = the short reciprocal (valid for 2^-126 <= |a| <= 2^126), 1 = the
- * reciprocal with IEEE special cases, 2 = the short square root, 3 = 1 / sqrt(x) as the normalisations compute it.  Each must
- * return the bits of the IEEE-754 operation the reference's CPU code performs (1.0f / a, sqrtf(x)). */
+/* the kernels' arithmetic helpers on an array, as the build the "contract" option selects compiles them: op 0 = the short
+ * reciprocal (valid for 2^-126 <= |a| <= 2^126), 1 = the reciprocal with IEEE special cases, 2 = the short square root,
+ * 3 = the factor normalize() multiplies by (1 / sqrt(x); contract 2: the hardware's rsq), 4 / 5 = sin / cos of the fixed
+ * polynomial for angles in [0, 2 pi].  In the exact build ops 0-3 return the bits of the IEEE-754 operation the reference's
+ * CPU code performs (1.0f / a, sqrtf(x)) and ops 4 / 5 those of the CPU oracle's polynomial. */
 int ptk_probe_math(ptk_ctx* ctx, int op, int n, const float* in, float* out);
 
 #ifdef __cplusplus

@@ -251,6 +251,7 @@ def lib():
     L.orc_intersect_triangle.argtypes = [_f] * 6
     L.orc_triangle_init.argtypes = [_f, _f]
     L.orc_sincos.argtypes = [C.c_float, _f, _f]
+    L.orc_sincos_n.argtypes = [_f, C.c_int, _f, _f]
     L.orc_rand_u01.restype = C.c_float
     L.orc_rand_u01.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int]
     L.orc_sample_circle.argtypes = [C.c_float, C.c_float, _f]
@@ -270,3 +271,12 @@ def intersect_many(ro, rd, tri9) -> np.ndarray:
     out = np.zeros((n, 3), np.float32)
     L.orc_intersect_many(n, *[x.ctypes.data_as(_f) for x in a], out.ctypes.data_as(_f))
     return out
+
+
+def sincos_many(a) -> tuple:
+    """orc_sincos (the kernels' sin / cos polynomial, bit for bit) on an array of angles -> (sin, cos) float32."""
+    L = lib()
+    a = np.ascontiguousarray(a, np.float32).reshape(-1)
+    s = np.empty_like(a); c = np.empty_like(a)
+    L.orc_sincos_n(a.ctypes.data_as(_f), a.size, s.ctypes.data_as(_f), c.ctypes.data_as(_f))
+    return s, c

@@ -73,6 +73,12 @@ void orc_sincos(float a, float* s, float* c)
 }
 #endif
 
+/* orc_sincos on n angles (the exhaustive tests pass 2^24 of them) */
+void orc_sincos_n(const float* a, int n, float* s, float* c)
+{
+    for (int i = 0; i < n; ++i) orc_sincos(a[i], &s[i], &c[i]);
+}
+
 /* ---- RNG -------------------------------------------------------------------------------------
  * Replaces PathTracer::Rand (pathtracer.cpp:367-371; one std::mt19937 raced by all workers) by a
  * counter-based PCG-RXS-M-XS-32 stream per (seed, pixel, sample).  Tape mode replays recorded

@@ -137,6 +137,7 @@ int  orc_hit_brute(const orc_scene* s, const float* ro, const float* rd, float* 
 void orc_tex2d(const orc_scene* s, int tex, float u, float v, float* out4);
 void orc_triangle_init(const float* in15, float* out9);
 void orc_sincos(float a, float* s, float* c);
+void orc_sincos_n(const float* a, int n, float* s, float* c);                                   /* orc_sincos on an array */
 float orc_rand_u01(uint64_t seed, uint32_t pixel, uint32_t sample, int n);  /* n-th draw of a path */
 void orc_sample_circle(float r1, float r2, float* out2);
 int  orc_aabb_intersect(const float* bmin, const float* bmax, const float* ro, const float* rd);   /* AABB::Intersect */

@@ -1843,7 +1843,7 @@ int ptk_probe_direct(ptk_ctx* c, int n, const float* pts, const float* normals, 
 
 int ptk_probe_math(ptk_ctx* c, int op, int n, const float* in, float* out)
 {
-    if (!c || op < 0 || op > 3 || n < 0 || (n > 0 && (!in || !out))) return PTK_ERR_BAD_ARG;
+    if (!c || op < 0 || op > 5 || n < 0 || (n > 0 && (!in || !out))) return PTK_ERR_BAD_ARG;
     if (n == 0) return PTK_OK;
     HIPCHK(c, hipSetDevice(c->device));
     float *d_in = nullptr, *d_out = nullptr;
@@ -1851,7 +1851,14 @@ int ptk_probe_math(ptk_ctx* c, int op, int n, const float* in, float* out)
     hipError_t e = hipMalloc(&d_in, bytes);
     if (e == hipSuccess) e = hipMalloc(&d_out, bytes);
     if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) { launch_probe_math(op, d_in, d_out, n, c->stream); e = hipGetLastError(); }
+    if (e == hipSuccess)
+    {
+        // the build the "contract" option selects for the trace kernels
+        if (c->opt_contract == 1) fma::launch_probe_math(op, d_in, d_out, n, c->stream);
+        else if (c->opt_contract == 2) fast::launch_probe_math(op, d_in, d_out, n, c->stream);
+        else launch_probe_math(op, d_in, d_out, n, c->stream);
+        e = hipGetLastError();
+    }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d_in); (void)hipFree(d_out);

@@ -134,8 +134,14 @@ inline const RenderParams* queue_block_params(const unsigned* block) { return (c
 void launch_trace(const RenderParams& p, int num_subtiles, int resident_waves, hipStream_t stream, bool stats);
 // the same trace kernels from the second and third builds of ptk_kernels.hip (-ffp-contract=fast; `fast` also with the
 // hardware's 1-ulp reciprocal / square root): the "contract" option, results within tolerance instead of bit-exact
-namespace fma { void launch_trace(const RenderParams& p, int num_subtiles, int resident_waves, hipStream_t stream, bool stats); }
-namespace fast { void launch_trace(const RenderParams& p, int num_subtiles, int resident_waves, hipStream_t stream, bool stats); }
+namespace fma {
+void launch_trace(const RenderParams& p, int num_subtiles, int resident_waves, hipStream_t stream, bool stats);
+void launch_probe_math(int op, const float* d_in, float* d_out, int n, hipStream_t stream);
+}
+namespace fast {
+void launch_trace(const RenderParams& p, int num_subtiles, int resident_waves, hipStream_t stream, bool stats);
+void launch_probe_math(int op, const float* d_in, float* d_out, int n, hipStream_t stream);
+}
 void launch_pixel_rng(uint32_t seed_lo, uint32_t seed_hi, int n, uint2* out, hipStream_t stream);
 void launch_live_list(const RenderParams& p, int num_subtiles, unsigned long long* mask, unsigned* list, unsigned* count, hipStream_t stream);
 void launch_accumulate(const RenderParams& p, int owned_tiles, hipStream_t stream);
@@ -145,6 +151,7 @@ void launch_primary(const PrimaryParams& p, hipStream_t stream);
 void launch_primary_hits(const RenderParams& p, float4* out, float4* out_rd, hipStream_t stream);
 void launch_probe(const ProbeParams& p, hipStream_t stream);
 void launch_probe_direct(const ProbeParams& p, const float* pts, const float* nrm, const float* dif, const float* tape, float* out, hipStream_t stream);
+// the arithmetic helpers of the exact build on an array (ptk_probe_math); fma:: / fast:: above: those of the contracted builds
 void launch_probe_math(int op, const float* d_in, float* d_out, int n, hipStream_t stream);
 
 }  // namespace ptk

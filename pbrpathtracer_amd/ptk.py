@@ -406,7 +406,8 @@ class Context:
         return out
 
     def probe_math(self, op: int, x: np.ndarray) -> np.ndarray:
-        """The kernels' exact-arithmetic helpers on an array (op 0 rcp, 1 rcp with special cases, 2 sqrt, 3 1/sqrt)."""
+        """The kernels' arithmetic helpers on an array, from the build the "contract" option selects (op 0 rcp, 1 rcp with
+        special cases, 2 sqrt, 3 normalize()'s factor 1/sqrt, 4 sin and 5 cos of the polynomial on [0, 2 pi])."""
         x = np.ascontiguousarray(x, np.float32)
         out = np.empty_like(x)
         self._chk(self.L.ptk_probe_math(self.h, op, x.size, x.ctypes.data, out.ctypes.data), "ptk_probe_math")

@@ -57,7 +57,8 @@ def test_few_triangles(ctx, oracle_mod, n):
     assert np.array_equal(ref, got) and np.array_equal(ref8, got8)
 
 
-def test_no_lights_and_degenerate_triangles(ctx, oracle_mod):
+def no_lights_degenerate_scene():
+    """tier_s_glass without lights or emission and with two zero-area triangles: (arrays, camera)"""
     z = load_golden("tier_s_glass.npz")
     a = scene_from_golden(z)
     a["lights"] = np.zeros(0, np.int32)                       # DirectIllumimation returns 0 (pathtracer.cpp:506-507)
@@ -65,7 +66,12 @@ def test_no_lights_and_degenerate_triangles(ctx, oracle_mod):
     a["verts"] = a["verts"].copy()
     a["verts"][3, 3:6] = a["verts"][3, 0:3]                   # zero-area triangle: |a| < EPS cull (pathtracer.cpp:387)
     a["verts"][5, 6:9] = a["verts"][5, 3:6]
-    ref, ref8, got, got8 = _both(ctx, oracle_mod, a, _cam(z), 48, 32, 6, 3)
+    return a, _cam(z)
+
+
+def test_no_lights_and_degenerate_triangles(ctx, oracle_mod):
+    a, cam = no_lights_degenerate_scene()
+    ref, ref8, got, got8 = _both(ctx, oracle_mod, a, cam, 48, 32, 6, 3)
     assert np.array_equal(ref, got) and not got.any()          # nothing emits -> black, but every branch ran
 
 
