@@ -23,6 +23,7 @@ typedef unsigned char GLubyte;   // the only thing the reference takes from <GL/
 
 struct ptk_ctx;
 struct ptk_scene_desc;
+struct ptk_adaptive_result;
 
 const float EPS = 0.00001f;      // mesh.h:12
 const float INF = (float)0xFFFF; // mesh.h:13
@@ -174,6 +175,13 @@ public:
     // `count` RenderFrame() calls in one kernel launch (identical image; the accumulator stays in
     // registers between samples).  The RGB8 host copy happens once at the end.
     void RenderFrames(int count);
+    // Adaptive render (include/ptk.h ptk_render_adaptive): ResetImage(), then rounds of `step` samples; a pixel stops once its
+    // noise meets `threshold` (from min_spp on) or at max_spp.  Each pixel then holds exactly what a plain render of its own
+    // sample count puts there; RenderFrame() refuses to add to it until ResetImage().
+    // The result (rounds, max_count, pixel_samples, active_pixels) goes to *out when it is not NULL.
+    bool RenderAdaptive(float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, ptk_adaptive_result* out = nullptr);
+    // samples per pixel (W*H, rows bottom-up, 0 = not owned)
+    bool ReadSampleCounts(uint32_t* out);
     // mTotalImg (float RGB, rows bottom-up), W*H*3 floats
     bool ReadAccumulation(float* out);
     // last error text of the device layer ("" when none); the reference API itself stays silent

@@ -192,6 +192,36 @@ void  ptk_host_free(void* p);
 int ptk_read_accum(ptk_ctx* ctx, float* host_out);
 int ptk_write_accum(ptk_ctx* ctx, const float* host_in, int samples);   /* resume from a saved accumulator */
 
+/* ---- adaptive render (no counterpart in the reference): stop tracing a pixel once its noise meets a target ------------------
+ * Rounds of `step` samples.  Each owned pixel p keeps S1 (the accumulator), S2 (per-channel sums of squared samples, folded in
+ * sample order as S2 = S2 + v*v) and n_p (samples received).  After every round whose count n >= min_spp, in float32 and this
+ * order (c over R, G, B):
+ *   nf = (float)n;  m_c = S1_c / nf;  v_c = S2_c / nf - m_c * m_c, 0 if negative (NaN stays NaN);
+ *   err2 = ((v_r + v_g) + v_b) / (3 * (nf - 1));  lum = ((m_r + m_g) + m_b) / 3;  tol = threshold * (lum + 1/256);
+ *   done(p) = err2 < tol * tol          (strict: threshold 0 never converges, NaN never converges)
+ * A pixel stays active for the next round if it is active now and some active pixel q with !done(q) lies in its 3x3
+ * neighbourhood clipped to its 16x16 tile and to the image (so the result does not depend on ptk_set_tile).  The active set only
+ * shrinks; the render ends after the round that leaves no pixel active, or at max_spp.  Pixels a plain render never traces (cached
+ * camera-ray misses, lens-culled pixels) start active and are counted, but are never traced.
+ * Invariant: for every owned pixel, S1, S2 and the 8-bit resolve (S1 / n_p) equal those of a plain render of samples [0, n_p).
+ * ptk_render_adaptive resets the accumulator itself and is synchronous; ptk_request_exit cuts it (an aborted pass adds and counts
+ * nothing, the invariant holds).  Afterwards ptk_samples = max_count, and ptk_render fails with PTK_ERR_BAD_ARG until ptk_reset,
+ * ptk_write_accum or ptk_set_frame with another resolution: the accumulator no longer has one sample count.  Argument checks
+ * (PTK_ERR_BAD_ARG): step >= 2, step divides min_spp and max_spp, min_spp <= max_spp, threshold finite and >= 0.
+ * Tile-split renders: each rank renders its own tiles adaptively; ptk_gather_accum gathers S1 only (combining the counts across
+ * ranks is up to the caller).  Memory: 16 B per pixel and 20 B per 8x8 quadrant, allocated by the first adaptive render. */
+typedef struct ptk_adaptive_result {
+    uint32_t rounds, max_count;          /* rounds run; largest per-pixel count (= ptk_samples afterwards) */
+    uint64_t pixel_samples;              /* sum of n_p over owned pixels */
+    uint64_t active_pixels;              /* still active when it stopped: 0 = every pixel converged */
+} ptk_adaptive_result;
+int ptk_render_adaptive(ptk_ctx* ctx, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp,
+                        uint64_t seed, ptk_adaptive_result* out /* may be NULL */);
+/* n_p: W*H, rows bottom-up; 0 = not owned (after a plain render: ptk_samples for every owned pixel) */
+int ptk_read_sample_counts(ptk_ctx* ctx, uint32_t* host_out);
+/* S2 of the last adaptive render: W*H*3 sums of squares, rows bottom-up */
+int ptk_read_moments(ptk_ctx* ctx, float* host_out);
+
 int ptk_samples(ptk_ctx* ctx);         /* GetSamples (pathtracer.cpp:362-365); thread-safe */
 /* Exit (pathtracer.cpp:819-822); thread-safe.  Cuts EVERY render in flight - ptk_render is asynchronous while no output
  * image is bound, so several may be queued: all of them, not only the newest - : passes whose kernels have not started are

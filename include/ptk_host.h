@@ -51,6 +51,9 @@ void pth_set_seed(pth_tracer* t, uint64_t seed);
 void pth_set_tile(pth_tracer* t, int rank, int world);
 void pth_render_frames(pth_tracer* t, int count);
 int  pth_read_accum(pth_tracer* t, float* out);           /* 1 on success */
+/* RenderAdaptive: 1 on success (the result may be NULL); ReadSampleCounts: W*H counts, rows bottom-up, 1 on success */
+int  pth_render_adaptive(pth_tracer* t, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, ptk_adaptive_result* out);
+int  pth_read_sample_counts(pth_tracer* t, uint32_t* out);
 const char* pth_last_error(pth_tracer* t);
 ptk_ctx* pth_context(pth_tracer* t);
 const ptk_scene_desc* pth_staged_scene(pth_tracer* t);    /* flat arrays of the staged scene (host only) */

@@ -646,13 +646,10 @@ const int PathTracer::GetSamples() const { return m->ctx ? ptk_samples(m->ctx) :
 
 void PathTracer::RenderFrame() { RenderFrames(1); }                    // :741-817
 
-void PathTracer::RenderFrames(int count)
+// What a render call brings up to date before it renders (render_mu held): material / texture edits, camera, resolution, the
+// hand-off binding and a pending ResetImage().  false: the render must not run (the error is noted).
+static bool prepare_render(PathTracer::Impl* m, GLubyte*& out_img, unsigned& out_gl, void*& out_dev)
 {
-    if (count <= 0) return;
-    if (!m->scene_uploaded && m->built_once && !m->triangles.empty())
-        m->error = "geometry changed after BuildBVH(): call BuildBVH() again before RenderFrame()";   // (the reference would chase dangling pointers)
-    if (!m->scene_uploaded || !m->have_resolution || !m->ensure_ctx()) return;
-    std::lock_guard<std::mutex> render_guard(m->render_mu);
     int rc;
     if (m->materials_dirty || m->textures_dirty)
     {
@@ -667,7 +664,7 @@ void PathTracer::RenderFrames(int count)
         }
         else rc = ptk_update_materials(m->ctx, (int32_t)fs.materials.size(), fs.materials.data());
         m->note(rc);
-        if (rc != PTK_OK) return;
+        if (rc != PTK_OK) return false;
         m->materials_dirty = m->textures_dirty = false;
     }
     if (m->camera_dirty)
@@ -680,12 +677,12 @@ void PathTracer::RenderFrames(int count)
     {
         rc = ptk_set_frame(m->ctx, m->resolution.x, m->resolution.y, m->max_depth);
         m->note(rc);
-        if (rc != PTK_OK) return;
+        if (rc != PTK_OK) return false;
         m->frame_dirty = false;
         std::lock_guard<std::mutex> g(m->bind_mu);
         m->bind_dirty = true;                                           // (a new resolution unbinds the hand-off buffer: say again what is bound)
     }
-    GLubyte* out_img; unsigned out_gl; void* out_dev; bool rebind;
+    bool rebind;
     {
         // one snapshot of the hand-off target per call (the setters may run on another thread)
         std::lock_guard<std::mutex> g(m->bind_mu);
@@ -707,12 +704,52 @@ void PathTracer::RenderFrames(int count)
         m->need_reset = false;
         m->samples = 0;
     }
+    return true;
+}
+
+void PathTracer::RenderFrames(int count)
+{
+    if (count <= 0) return;
+    if (!m->scene_uploaded && m->built_once && !m->triangles.empty())
+        m->error = "geometry changed after BuildBVH(): call BuildBVH() again before RenderFrame()";   // (the reference would chase dangling pointers)
+    if (!m->scene_uploaded || !m->have_resolution || !m->ensure_ctx()) return;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    GLubyte* out_img; unsigned out_gl; void* out_dev;
+    if (!prepare_render(m, out_img, out_gl, out_dev)) return;
+    int rc;
     uint32_t first = (uint32_t)ptk_samples(m->ctx);
     rc = ptk_render(m->ctx, first, (uint32_t)count, m->seed);         // mSamples += count (:753)
     m->note(rc);
     m->samples = ptk_samples(m->ctx);
     if (rc == PTK_OK && out_img) m->note(ptk_resolve_rgb8(m->ctx, out_img));   // :802-812 into the caller's buffer
     else if (rc == PTK_OK && (out_gl || out_dev)) m->note(ptk_synchronize(m->ctx));   // RenderFrame() returns with the frame in the OpenGL / device buffer
+}
+
+// Adaptive render (ptk_render_adaptive): ResetImage() and rounds of `step` samples until every pixel meets `threshold` or
+// holds max_spp; the 8-bit image goes to the hand-off target as RenderFrame()'s does.  RenderFrame() refuses to add to it until
+// the next ResetImage().
+bool PathTracer::RenderAdaptive(float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, ptk_adaptive_result* out)
+{
+    ptk_adaptive_result res = {};
+    if (out) *out = res;
+    if (!m->scene_uploaded || !m->have_resolution || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    GLubyte* out_img; unsigned out_gl; void* out_dev;
+    if (!prepare_render(m, out_img, out_gl, out_dev)) return false;
+    int rc = ptk_render_adaptive(m->ctx, threshold, min_spp, step, max_spp, m->seed, &res);
+    m->note(rc);
+    m->samples = ptk_samples(m->ctx);
+    if (out) *out = res;
+    if (rc == PTK_OK && out_img) { rc = ptk_resolve_rgb8(m->ctx, out_img); m->note(rc); }
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ReadSampleCounts(uint32_t* out)
+{
+    if (!m->ctx || !out) return false;
+    const int rc = ptk_read_sample_counts(m->ctx, out);
+    m->note(rc);
+    return rc == PTK_OK;
 }
 
 void PathTracer::Exit() { if (m->ctx) ptk_request_exit(m->ctx); }      // :819-822

@@ -23,6 +23,7 @@
 #include "bvh_build.h"
 #include "bvh_device.h"
 #include "ptk_device.h"
+#include "ptk_adaptive.h"
 
 using namespace ptk;
 
@@ -99,6 +100,17 @@ struct ptk_ctx {
     unsigned long long hit_generation = 0;       // bumped whenever the primary-hit cache is recomputed
     struct LiveKey { int width, height, rank, world, cached; unsigned long long generation; } live_key = { 0, 0, -1, 0, -1, 0 };
     int resident_waves = 4096;                   // one-wave workgroups the device holds at once (CUs x 16)
+
+    // adaptive render (ptk_render_adaptive): allocated by the first one, freed by ptk_set_frame with another resolution
+    uint32_t* d_counts = nullptr;                // [H][W] samples per pixel, rows bottom-up
+    float* d_moments = nullptr;                  // [H][W][3] sums of squared samples (S2)
+    unsigned long long* d_adapt_active = nullptr, * d_adapt_traced = nullptr;     // per quadrant of the frame: active set, active & live
+    unsigned* d_adapt_list = nullptr;            // [adapt_capacity] entries + 1 word: the count (the traced mask's quadrants)
+    unsigned long long* d_adapt_stats = nullptr; // [0] pixel samples, [1] largest count, [2] low word: active pixels after the last test
+    int adapt_capacity = 0;                      // quadrants the buffers hold (every quadrant of the frame: any tile split fits)
+    unsigned* h_adapt_count = nullptr;           // page-locked [2]: the active count of rounds r and r + 1, read one round behind
+    hipEvent_t ev_adapt[2] = { nullptr, nullptr };
+    bool adaptive_accum = false;                 // the accumulator holds an adaptive render: per-pixel counts, no single sample count
 
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
@@ -321,6 +333,14 @@ struct GlMapping
     ~GlMapping() { if (mapped) { (void)hipGraphicsUnmapResources(1, &c->gl_res, c->stream); (void)hipGetLastError(); } }
 };
 
+void free_adaptive(ptk_ctx* c)
+{
+    dfree(c->d_counts); dfree(c->d_moments); dfree(c->d_adapt_active); dfree(c->d_adapt_traced); dfree(c->d_adapt_list);
+    dfree(c->d_adapt_stats);
+    c->adapt_capacity = 0;
+    c->adaptive_accum = false;
+}
+
 int owned_tiles(const RenderParams& p)
 {
     // tiles t with t % world == rank
@@ -328,11 +348,21 @@ int owned_tiles(const RenderParams& p)
     return (p.num_tiles - p.rank + p.world - 1) / p.world;
 }
 
+// One round of an adaptive render (ptk_render_adaptive): the trace kernels are fed the round's traced mask and list, the adaptive
+// accumulate kernel folds S1 / S2 and counts for the active set.  init: before the first round, converge_kernel sets the active
+// set to every owned pixel and derives the traced mask from the live mask of a plain render (which run_passes brings up to date).
+struct AdaptiveRound
+{
+    AdaptiveParams a;
+    ConvergeParams cp;
+    bool init;
+};
+
 // One pass = trace_kernel over (owned tiles x 4 quadrants x chunks) + accumulate_kernel.  The pass
 // size is bounded by the sample-buffer budget; chunk boundaries never change results (the RNG is
 // keyed on the absolute sample index and the accumulate kernel adds in sample order).
 int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool stats, float* accum, uint8_t* rgb8,
-               const uint32_t* exit_flag, bool timed)
+               const uint32_t* exit_flag, bool timed, const AdaptiveRound* ad = nullptr)
 {
     RenderParams p;
     fill_params(c, p, first, spp, seed);
@@ -407,6 +437,21 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
             c->inputs_dirty = true;
         }
         p.live_mask = c->d_live_mask; p.live_list = c->d_live_list; p.live_count = c->d_live_list + c->live_capacity;
+        if (ad)
+        {
+            // (kept apart from the cached list above: a plain render after this one finds it as it was)
+            unsigned* count = c->d_adapt_list + c->adapt_capacity;
+            if (ad->init)
+            {
+                ConvergeParams cp = ad->cp;
+                cp.base = c->d_live_mask; cp.init = 1; cp.test = 0;
+                launch_converge(p, cp, tiles, c->stream);
+                HIPCHK(c, hipGetLastError());
+                launch_mask_compact(c->d_adapt_traced, subtiles, c->d_adapt_list, count, c->stream);
+                HIPCHK(c, hipGetLastError());
+            }
+            p.live_mask = c->d_adapt_traced; p.live_list = c->d_adapt_list; p.live_count = count;
+        }
     }
     const size_t per_sample = (size_t)tiles * 4 * 64 * sizeof(float4);
     // Samples per work item.  The waves are persistent and lanes take units from item after item, so short items
@@ -418,7 +463,8 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
         chunk_opt = (double)spp * (double)tiles * 4.0 / 8.0 >= 49152.0 ? 8 : 4;
     // (a bound hand-off buffer means the caller waits for every frame: nothing to overlap, and one stream is two event
     // hops per frame less)
-    const bool overlap = c->opt_overlap != 0 && c->trace_stream[0] != nullptr && !handoff;
+    // (nor in an adaptive render: each round depends on the one before)
+    const bool overlap = c->opt_overlap != 0 && c->trace_stream[0] != nullptr && !handoff && !ad;
     // The pass size: what the sample-buffer budget allows - and what the device can actually give.  When an allocation of that
     // size fails (memory shared with the caller's framework, a huge scene, a 144-megapixel frame) the pass is halved and tried
     // again instead of failing the render: more passes, the same image (chunk boundaries never change a bit).
@@ -520,7 +566,8 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
             HIPCHK(c, hipEventRecord(c->ev_trace_done[b], tstream));
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_trace_done[b], 0));
         }
-        launch_accumulate(p, tiles, c->stream);
+        if (ad) launch_accumulate_adaptive(p, ad->a, tiles, c->stream);
+        else launch_accumulate(p, tiles, c->stream);
         HIPCHK(c, hipGetLastError());
         if (timed && pi >= 0) HIPCHK(c, hipEventRecord(c->ev[pi][2], c->stream));
         if (overlap)
@@ -621,6 +668,10 @@ void ptk_destroy(ptk_ctx* c)
     if (c->h_exit) (void)hipHostFree(c->h_exit);
     dfree(c->d_exit); dfree(c->d_stats); dfree(c->d_queues); dfree(c->d_samples);
     dfree(c->d_live_mask); dfree(c->d_live_list);
+    free_adaptive(c);
+    for (int b = 0; b < 2; b++)
+        if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
+    if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);
     for (int i = 0; i < ptk_ctx::kMaxTimedPasses; i++)
         for (int k = 0; k < 3; k++)
             if (c->ev[i][k]) (void)hipEventDestroy(c->ev[i][k]);
@@ -952,6 +1003,7 @@ int ptk_set_frame(ptk_ctx* c, int width, int height, int max_depth)
         HIPCHK(c, hipMalloc(&c->d_pixel_rng, px * sizeof(uint2)));
         HIPCHK(c, hipMalloc(&c->d_accum, px * 3 * sizeof(float)));
         HIPCHK(c, hipMalloc(&c->d_rgb8, px * 3));
+        free_adaptive(c);
         c->width = width; c->height = height;
         c->d_accum_bound = nullptr;
         unbind_out_image(c, true);               // another resolution: the caller's buffer has another size (main.cpp:3425-3446)
@@ -980,6 +1032,7 @@ int ptk_reset(ptk_ctx* c)
     HIPCHK(c, hipMemsetAsync(accum_ptr(c), 0, px * 3 * sizeof(float), c->stream));     // pathtracer.cpp:745-751
     HIPCHK(c, hipMemsetAsync(c->d_rgb8, 0, px * 3, c->stream));
     c->samples = 0;
+    c->adaptive_accum = false;
     if (c->out_host_dev)
     {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -996,6 +1049,8 @@ int ptk_render(ptk_ctx* c, uint32_t first_sample, uint32_t spp_count, uint64_t s
     if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
     if (!accum_ptr(c) || !c->d_primary) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
     if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
+    if (c->adaptive_accum)
+        return fail(c, PTK_ERR_BAD_ARG, "the accumulator holds an adaptive render (per-pixel sample counts): ptk_reset, ptk_write_accum or a new resolution first");
     HIPCHK(c, hipSetDevice(c->device));
     c->last_launches = 0;
     c->timed = false;
@@ -1011,6 +1066,170 @@ int ptk_render(ptk_ctx* c, uint32_t first_sample, uint32_t spp_count, uint64_t s
     if (rc != PTK_OK) return rc;
     c->timed = true;
     c->samples = (int)(first_sample + spp_count);
+    return PTK_OK;
+}
+
+// Adaptive render: rounds of `step` samples; after each, converge_kernel decides which pixels go on (include/ptk.h).  Every
+// round is queued on the context's stream (trace + adaptive accumulate per pass, converge_kernel, live_compact_kernel, a copy
+// of the active count to page-locked memory, an event); the host learns that a round left no pixel active ONE ROUND LATE, by
+// polling that round's event while the next round is already queued - so the stream never drains between rounds, and at most
+// one round is issued that finds the active set empty (it traces, adds and counts nothing).
+int ptk_render_adaptive(ptk_ctx* c, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, uint64_t seed,
+                        ptk_adaptive_result* out)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (!accum_ptr(c) || !c->d_primary) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
+    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
+    if (step < 2 || min_spp % step != 0 || max_spp % step != 0 || min_spp > max_spp)
+        return fail(c, PTK_ERR_BAD_ARG, "ptk_render_adaptive: need step >= 2 dividing min_spp and max_spp, min_spp <= max_spp");
+    if (!std::isfinite(threshold) || threshold < 0.0f) return fail(c, PTK_ERR_BAD_ARG, "ptk_render_adaptive: threshold must be finite and >= 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->last_launches = 0;
+    c->timed = false;
+    const size_t px = (size_t)c->width * c->height;
+    const int tiles_x = (c->width + PTK_TILE - 1) / PTK_TILE;
+    const int capacity = tiles_x * ((c->height + PTK_TILE - 1) / PTK_TILE) * 4;
+    if (c->adapt_capacity != capacity || !c->d_counts)
+    {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        free_adaptive(c);
+        HIPCHK(c, hipMalloc(&c->d_counts, px * sizeof(uint32_t)));
+        HIPCHK(c, hipMalloc(&c->d_moments, px * 3 * sizeof(float)));
+        HIPCHK(c, hipMalloc(&c->d_adapt_active, (size_t)capacity * sizeof(unsigned long long)));
+        HIPCHK(c, hipMalloc(&c->d_adapt_traced, (size_t)capacity * sizeof(unsigned long long)));
+        HIPCHK(c, hipMalloc(&c->d_adapt_list, ((size_t)capacity + 1) * sizeof(unsigned)));
+        HIPCHK(c, hipMalloc(&c->d_adapt_stats, 4 * sizeof(unsigned long long)));
+        c->adapt_capacity = capacity;
+    }
+    if (!c->h_adapt_count)
+    {
+        HIPCHK(c, hipHostMalloc((void**)&c->h_adapt_count, 2 * sizeof(unsigned), hipHostMallocDefault));
+        for (int b = 0; b < 2; b++) HIPCHK(c, hipEventCreateWithFlags(&c->ev_adapt[b], hipEventDisableTiming));
+    }
+    // the accumulator starts from zero: ResetImage, plus the counts, S2 and the counters of this render
+    int rc = ptk_reset(c);
+    if (rc != PTK_OK) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_counts, 0, px * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_moments, 0, px * 3 * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_adapt_stats, 0, 4 * sizeof(unsigned long long), c->stream));
+    c->adaptive_accum = true;
+    c->inputs_dirty = true;
+    if (max_spp == 0) return ptk_synchronize(c);
+    c->render_gen.fetch_add(1);                  // (one generation for all rounds: an Exit() cuts the whole render)
+    const uint32_t gen = c->render_gen.load();
+    rc = ensure_primary(c);
+    if (rc != PTK_OK) return rc;
+
+    AdaptiveRound ad;
+    ad.a.active = c->d_adapt_active; ad.a.counts = c->d_counts; ad.a.moments = c->d_moments; ad.a.stats = c->d_adapt_stats;
+    std::memset(&ad.cp, 0, sizeof(ad.cp));
+    ad.cp.active = c->d_adapt_active; ad.cp.traced = c->d_adapt_traced; ad.cp.base = c->d_live_mask;
+    ad.cp.accum = accum_ptr(c); ad.cp.moments = c->d_moments; ad.cp.counts = c->d_counts;
+    ad.cp.active_count = (unsigned*)(c->d_adapt_stats + 2);
+    ad.cp.threshold = threshold;
+    const uint32_t rounds_max = max_spp / step;
+    uint32_t rounds = 0, issued = 0;
+    bool converged = false;
+    for (uint32_t r = 0; r < rounds_max; r++)
+    {
+        ad.init = r == 0;
+        rc = run_passes(c, r * step, step, seed, false, accum_ptr(c), c->d_rgb8, c->d_exit, false, &ad);
+        if (rc != PTK_OK) return rc;
+        if (c->last_passes == 0) break;          // (no owned pixel)
+        RenderParams p;
+        fill_params(c, p, r * step, step, seed);
+        p.exit_flag = c->d_exit; p.exit_gen = gen;
+        ConvergeParams cp = ad.cp;
+        cp.base = c->d_live_mask;
+        cp.test = (r + 1) * step >= min_spp ? 1 : 0;
+        const int tiles = owned_tiles(p);
+        HIPCHK(c, hipMemsetAsync(cp.active_count, 0, sizeof(unsigned), c->stream));
+        launch_converge(p, cp, tiles, c->stream);
+        HIPCHK(c, hipGetLastError());
+        launch_mask_compact(c->d_adapt_traced, tiles * 4, c->d_adapt_list, c->d_adapt_list + c->adapt_capacity, c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->h_adapt_count + (r & 1), cp.active_count, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_adapt[r & 1], c->stream));
+        c->last_launches += 2;
+        issued = r + 1;
+        rounds = issued;
+        if (r >= 1)
+        {
+            // round r is queued: now wait for round r - 1's count (polled for a while, then the runtime's blocking wait)
+            const auto t0 = std::chrono::steady_clock::now();
+            hipError_t q;
+            while ((q = hipEventQuery(c->ev_adapt[(r - 1) & 1])) == hipErrorNotReady &&
+                   std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(2)) {}
+            if (q == hipErrorNotReady) q = hipEventSynchronize(c->ev_adapt[(r - 1) & 1]);
+            if (q != hipSuccess) return fail(c, PTK_ERR_HIP, std::string("hipEventSynchronize: ") + hipGetErrorString(q));
+            if (c->h_adapt_count[(r - 1) & 1] == 0u) { converged = true; rounds = r; break; }     // round r found nothing to do
+        }
+        if (__atomic_load_n(c->h_exit, __ATOMIC_RELAXED) >= gen) break;                        // Exit(): the rest stands down anyway
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    unsigned long long st[3] = { 0, 0, 0 };
+    HIPCHK(c, hipMemcpyAsync(st, c->d_adapt_stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint64_t active = 0;
+    const bool cut = __atomic_load_n(c->h_exit, __ATOMIC_RELAXED) >= gen;
+    if (cut)
+    {
+        // the kernels that stood down left the active set as it was: count it
+        const int tiles = (int)((capacity / 4 <= c->rank) ? 0 : (capacity / 4 - c->rank + c->world - 1) / c->world);
+        std::vector<unsigned long long> m((size_t)tiles * 4);
+        if (!m.empty())
+        {
+            HIPCHK(c, hipMemcpyAsync(m.data(), c->d_adapt_active, m.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        for (unsigned long long w : m) active += (uint64_t)__builtin_popcountll(w);
+    }
+    else if (!converged && issued > 0) active = c->h_adapt_count[(issued - 1) & 1];
+    c->samples = (int)st[1];
+    if (out)
+    {
+        out->rounds = rounds; out->max_count = (uint32_t)st[1];
+        out->pixel_samples = st[0]; out->active_pixels = active;
+    }
+    return PTK_OK;
+}
+
+int ptk_read_sample_counts(ptk_ctx* c, uint32_t* host_out)
+{
+    if (!c || !host_out) return PTK_ERR_BAD_ARG;
+    if (!c->d_primary) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)c->width * c->height;
+    if (!c->d_counts || !c->adaptive_accum)
+    {
+        // no adaptive render in the accumulator: every owned pixel holds ptk_samples samples
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        std::memset(host_out, 0, px * sizeof(uint32_t));
+        const int tiles_x = (c->width + PTK_TILE - 1) / PTK_TILE, tiles_y = (c->height + PTK_TILE - 1) / PTK_TILE;
+        const uint32_t n = (uint32_t)c->samples.load();
+        for (int tile = c->rank; tile < tiles_x * tiles_y; tile += c->world)
+        {
+            const int ty = tile / tiles_x, tx = (tile % tiles_x + tiles_x - (3 * ty) % tiles_x) % tiles_x;
+            for (int y = ty * PTK_TILE; y < std::min(c->height, (ty + 1) * PTK_TILE); y++)
+                for (int x = tx * PTK_TILE; x < std::min(c->width, (tx + 1) * PTK_TILE); x++)
+                    host_out[(size_t)(c->height - 1 - y) * c->width + x] = n;
+        }
+        return PTK_OK;
+    }
+    HIPCHK(c, hipMemcpyAsync(host_out, c->d_counts, px * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PTK_OK;
+}
+
+int ptk_read_moments(ptk_ctx* c, float* host_out)
+{
+    if (!c || !host_out) return PTK_ERR_BAD_ARG;
+    if (!c->d_moments || !c->adaptive_accum) return fail(c, PTK_ERR_BAD_ARG, "ptk_read_moments: the accumulator holds no adaptive render");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(host_out, c->d_moments, (size_t)c->width * c->height * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return PTK_OK;
 }
 
@@ -1201,6 +1420,7 @@ int ptk_write_accum(ptk_ctx* c, const float* host_in, int samples)
     HIPCHK(c, hipMemcpyAsync(accum_ptr(c), host_in, (size_t)c->width * c->height * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->samples = samples;
+    c->adaptive_accum = false;
     c->out_full_next = true;
     return PTK_OK;
 }

@@ -99,6 +99,11 @@ void pth_set_seed(pth_tracer* t, uint64_t seed) { t->pt.SetSeed(seed); }
 void pth_set_tile(pth_tracer* t, int rank, int world) { t->pt.SetTile(rank, world); }
 void pth_render_frames(pth_tracer* t, int count) { t->pt.RenderFrames(count); }
 int pth_read_accum(pth_tracer* t, float* out) { return t->pt.ReadAccumulation(out) ? 1 : 0; }
+int pth_render_adaptive(pth_tracer* t, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, ptk_adaptive_result* out)
+{
+    return t->pt.RenderAdaptive(threshold, min_spp, step, max_spp, out) ? 1 : 0;
+}
+int pth_read_sample_counts(pth_tracer* t, uint32_t* out) { return t->pt.ReadSampleCounts(out) ? 1 : 0; }
 const char* pth_last_error(pth_tracer* t)
 {
     std::string e = t->pt.LastError();

@@ -34,7 +34,7 @@ HOST_SYMBOLS = [
     "pth_render_frame", "pth_exit", "pth_set_seed", "pth_set_tile", "pth_render_frames", "pth_read_accum",
     "pth_last_error", "pth_context", "pth_staged_scene", "pth_load_scene_file", "pth_pts_roundtrip",
     "pth_trs_matrix", "pth_euler_camera", "pth_triangle_init", "pth_image_load", "pth_image_data", "pth_image_tex2d",
-    "pth_export_png",
+    "pth_export_png", "pth_render_adaptive", "pth_read_sample_counts",
 ]
 
 _bound = False
@@ -79,6 +79,9 @@ def _bind_locked(L) -> C.CDLL:
     L.pth_set_tile.restype = None; L.pth_set_tile.argtypes = [vp, i32, i32]
     L.pth_render_frames.restype = None; L.pth_render_frames.argtypes = [vp, i32]
     L.pth_read_accum.restype = i32; L.pth_read_accum.argtypes = [vp, vp]
+    L.pth_render_adaptive.restype = i32
+    L.pth_render_adaptive.argtypes = [vp, f32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_ptk.AdaptiveResult)]
+    L.pth_read_sample_counts.restype = i32; L.pth_read_sample_counts.argtypes = [vp, vp]
     L.pth_last_error.restype = C.c_char_p; L.pth_last_error.argtypes = [vp]
     L.pth_context.restype = vp; L.pth_context.argtypes = [vp]
     L.pth_staged_scene.restype = C.POINTER(_ptk.SceneDesc); L.pth_staged_scene.argtypes = [vp]
@@ -226,6 +229,22 @@ class PathTracer:
     def SetSeed(self, seed: int): self.L.pth_set_seed(self.h, seed)
     def SetTile(self, rank: int, world: int): self.L.pth_set_tile(self.h, rank, world)
     def RenderFrames(self, count: int): self.L.pth_render_frames(self.h, count)
+
+    def RenderAdaptive(self, threshold: float, min_spp: int, step: int, max_spp: int) -> dict:
+        """ResetImage() + adaptive render (include/ptk.h ptk_render_adaptive) with this tracer's seed; the 8-bit image goes to
+        the hand-off target.  Returns rounds, max_count, pixel_samples, active_pixels."""
+        r = _ptk.AdaptiveResult()
+        if not self.L.pth_render_adaptive(self.h, float(threshold), int(min_spp), int(step), int(max_spp), C.byref(r)):
+            raise _ptk.PtkError("RenderAdaptive failed: " + self.LastError())
+        return r.as_dict()
+
+    def ReadSampleCounts(self) -> np.ndarray:
+        """[H][W] uint32 samples per pixel, rows bottom-up like ReadAccumulation(); 0 = not owned."""
+        w, h = self.GetResolution()
+        out = np.empty((h, w), np.uint32)
+        if not self.L.pth_read_sample_counts(self.h, out.ctypes.data):
+            raise _ptk.PtkError("ReadSampleCounts failed: " + self.LastError())
+        return out
 
     def ReadAccumulation(self) -> np.ndarray:
         w, h = self.GetResolution()

@@ -54,6 +54,13 @@ class Stats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class AdaptiveResult(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("max_count", C.c_uint32), ("pixel_samples", C.c_uint64), ("active_pixels", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class PtkError(RuntimeError):
     pass
 
@@ -71,7 +78,7 @@ SYMBOLS = [
     "ptk_packed_floats", "ptk_packed_layout", "ptk_comm_unique_id", "ptk_comm_init", "ptk_comm_destroy",
     "ptk_gather_wait", "ptk_read_gathered", "ptk_gathered_device_ptr", "ptk_probe_pack", "ptk_probe_unpack",
     "ptk_bind_out_image", "ptk_bind_out_device", "ptk_bind_gl_buffer", "ptk_comm_info", "ptk_kernel_log", "ptk_kernel_log_read",
-    "ptk_debug_stall_exchange",
+    "ptk_debug_stall_exchange", "ptk_render_adaptive", "ptk_read_sample_counts", "ptk_read_moments",
 ]
 
 
@@ -138,6 +145,9 @@ def _load_locked() -> C.CDLL:
     L.ptk_last_kernel_ms.argtypes = [vp, fp, fp]
     L.ptk_set_option.argtypes = [vp, C.c_char_p, C.c_double]
     L.ptk_collect_stats.argtypes = [vp, u32, u32, u64, C.POINTER(Stats)]
+    L.ptk_render_adaptive.argtypes = [vp, f32, u32, u32, u32, u64, C.POINTER(AdaptiveResult)]
+    L.ptk_read_sample_counts.argtypes = [vp, vp]
+    L.ptk_read_moments.argtypes = [vp, vp]
     try:
         L.ptk_kernel_log.argtypes = [vp, i32]
         L.ptk_kernel_log_read.argtypes = [vp, C.POINTER(C.c_float), i32, C.POINTER(C.c_int)]
@@ -241,6 +251,26 @@ class Context:
     # ---- render ----------------------------------------------------------------------------
     def render(self, first_sample: int, spp: int, seed: int):
         self._chk(self.L.ptk_render(self.h, first_sample, spp, seed), "ptk_render")
+
+    def render_adaptive(self, threshold: float, min_spp: int, step: int, max_spp: int, seed: int) -> dict:
+        """Adaptive render (include/ptk.h ptk_render_adaptive): resets the accumulator, renders rounds of `step` samples until
+        every pixel meets `threshold` or has max_spp; synchronous.  Returns rounds, max_count, pixel_samples, active_pixels."""
+        r = AdaptiveResult()
+        self._chk(self.L.ptk_render_adaptive(self.h, float(threshold), int(min_spp), int(step), int(max_spp), int(seed),
+                                             C.byref(r)), "ptk_render_adaptive")
+        return r.as_dict()
+
+    def read_sample_counts(self) -> np.ndarray:
+        """[H][W] uint32 samples per pixel, rows bottom-up like read_accum; 0 = not owned."""
+        out = np.empty((self.height, self.width), dtype=np.uint32)
+        self._chk(self.L.ptk_read_sample_counts(self.h, out.ctypes.data), "ptk_read_sample_counts")
+        return out
+
+    def read_moments(self) -> np.ndarray:
+        """[H][W][3] float32 sums of squared samples of the last adaptive render, rows bottom-up."""
+        out = np.empty((self.height, self.width, 3), dtype=np.float32)
+        self._chk(self.L.ptk_read_moments(self.h, out.ctypes.data), "ptk_read_moments")
+        return out
 
     def synchronize(self):
         self._chk(self.L.ptk_synchronize(self.h), "ptk_synchronize")

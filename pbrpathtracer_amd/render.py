@@ -1,6 +1,10 @@
 """Headless driver: render a reference `.pts` scene file on the GPU and export a PNG.
 
     python -m pbrpathtracer_amd.render scene.pts --spp 256 --out image.png [--seed S] [--device D]
+    python -m pbrpathtracer_amd.render scene.pts --noise-threshold 0.02 [--min-spp 16] [--step 8] --spp 1024
+
+With --noise-threshold the render is adaptive (include/ptk.h ptk_render_adaptive): --spp becomes the most samples a pixel
+gets, and pixels stop once their noise meets the threshold.
 
 The headless equivalent of the reference's Start button + Export (main.cpp:3563-3618, :760-771):
 LoadScene -> SendObjectsToPathTracer -> RenderFrame() x spp -> PNG (flipped to top-down)."""
@@ -13,15 +17,23 @@ import time
 import numpy as np
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__)
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene")
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--out", default="render.png")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--pinhole", action="store_true", help="SetCameraAperture(0) after loading")
-    a = ap.parse_args(argv)
+    ap.add_argument("--noise-threshold", type=float, default=None,
+                    help="adaptive render: relative noise target per pixel (--spp is then the maximum)")
+    ap.add_argument("--min-spp", type=int, default=None, help="adaptive: samples before the first test (default: 2 x step)")
+    ap.add_argument("--step", type=int, default=8, help="adaptive: samples per round (default 8)")
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     from .pathtracer import PathTracer, export_png
     pt = PathTracer(a.device)
     t0 = time.time()
@@ -33,14 +45,28 @@ def main(argv=None):
     pt.SetOutImage(out)
     pt.SetSeed(a.seed)
     t1 = time.time()
-    pt.RenderFrames(a.spp)
+    res = None
+    if a.noise_threshold is None:
+        pt.RenderFrames(a.spp)
+    else:
+        min_spp = a.min_spp if a.min_spp is not None else min(2 * a.step, a.spp)
+        try:
+            res = pt.RenderAdaptive(a.noise_threshold, min_spp, a.step, a.spp)
+        except RuntimeError as e:
+            print("error:", e, file=sys.stderr)
+            return 1
     t2 = time.time()
     if pt.LastError():
         print("error:", pt.LastError(), file=sys.stderr)
         return 1
     export_png(a.out, out)
+    done = res["pixel_samples"] if res is not None else w * h * a.spp
     print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {w}x{h}, {a.spp} spp: load {t1 - t0:.2f} s, "
-          f"render {t2 - t1:.3f} s ({w * h * a.spp / (t2 - t1) / 1e6:.0f} Msamples/s) -> {a.out}")
+          f"render {t2 - t1:.3f} s ({done / (t2 - t1) / 1e6:.0f} Msamples/s) -> {a.out}")
+    if res is not None:
+        print(f"adaptive (threshold {a.noise_threshold}): {res['pixel_samples']} pixel samples of {w * h * a.spp} "
+              f"({res['pixel_samples'] / (w * h * a.spp):.3f}), {res['rounds']} rounds, "
+              f"{res['active_pixels']} pixels still active")
     return 0
 
 
