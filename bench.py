@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Msamples/s (pixels x spp / s) of the per-pixel render loop on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2] [--spp S] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config C2] [--spp S] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch: `spp` samples per pixel of the configured frame (default
 BASELINE.json configs[1]: Cornell box, 1280x720, 8 bounces, 256 spp), i.e. 256 RenderFrame() calls as one trace_kernel +
@@ -16,7 +16,10 @@ packed RCCL gather (ptk_gather_accum: pack kernel -> grouped ncclSend/ncclRecv -
 `--exchange-every` steps (default 8) and once more after the last step, inside the timed region, overlapping the next
 step's trace kernel.
 
-Prints ONE JSON line on rank 0 (see the driver contract) including
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run does only what its headline figure needs: it sets
+up, warms up, times the steps, writes --dump-outputs and prints metric, value, unit, higher_is_better, dtype,
+ms_per_step and the configuration.  With --full (off by default) it goes on to measure and check what follows; the
+--no-* options leave single parts of it out.
   roofline       the roof that bounds trace_kernel, chosen from the data: "valu" when the PMC-measured traffic that left
                  the L2 (profiles/traffic_<config>.json - used only while the kernel sources still hash to what was
                  profiled, else `traffic` is null and says so) is under 10 % of the HBM peak, else "l2_miss_fabric"
@@ -33,9 +36,10 @@ Prints ONE JSON line on rank 0 (see the driver contract) including
                  workload (N = 1 only): the reference's own OpenMP path as shipped (oracle/_ref, built from
                  /root/reference by __graft_entry__.build()) and the oracle port with a per-path RNG on all cores, timed
                  at 1 and at 16 samples per call; `value` is the FASTEST (the >= 10x target is judged against it).
-  other_configs  N = 1, default run: the BVH-walk configs C3, C4 (3 steps each) and C5 (2 steps) after the timed headline,
-                 numbers and short keys only.  N > 1 with --with-c5 (implied by --gpus 8): BASELINE config 5 as stated -
-                 C5 tile-split over the ranks, the exchange inside the timed region, gathered-image checksum.
+  other_configs  N = 1: the BVH-walk configs C3, C4 (4 steps each) and C5 (3 steps) after the timed headline, numbers
+                 and short keys only.  N > 1 with --with-c5 (implied by --gpus 8): BASELINE config 5 as stated - C5
+                 tile-split over the ranks, the exchange inside the timed region, gathered-image checksum.
+  config.gathered_checksum  N > 1: the image gathered on rank 0 against the sum of what the ranks hold (exit 5 if not).
 """
 from __future__ import annotations
 
@@ -69,8 +73,10 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="C2", choices=sorted(WORKLOADS))
     ap.add_argument("--spp", type=int, default=0, help="samples per pixel per step (default: the config's spp)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the C3 / C4 / C5 block after the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline and counters, parity, contracted build, interactive loop, CPU baseline, other configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the C3 / C4 / C5 block after the headline")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--exchange-every", type=int, default=8,
                     help="N > 1: gather the accumulator to rank 0 every K steps (and always after the last timed step)")
@@ -80,10 +86,10 @@ def parse_args(argv=None):
                     help="gloo = REHEARSAL of the N>1 control flow where ranks must share one GPU (RCCL refuses that): the exchange "
                          "then goes through host copies in the library's packing order; the numbers mean nothing")
     ap.add_argument("--share-of", type=int, default=0, help="rehearsal: render only rank 0's tiles of an N-rank split on this one GPU")
-    ap.add_argument("--with-c5", action="store_true", help="N > 1: append BASELINE config 5 (C5 tile-split over the ranks, 1 step) as other_configs.C5; implied by --gpus 8")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle spot check beside the number")
-    ap.add_argument("--no-contracted", action="store_true", help="skip the contracted-build measurement")
-    ap.add_argument("--no-interactive", action="store_true", help="skip the RenderFrame()-per-iteration measurement")
+    ap.add_argument("--with-c5", action="store_true", help="--full, N > 1: append BASELINE config 5 (C5 tile-split over the ranks, 1 step) as other_configs.C5; implied by --gpus 8")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle spot check beside the number")
+    ap.add_argument("--no-contracted", action="store_true", help="--full: skip the contracted-build measurement")
+    ap.add_argument("--no-interactive", action="store_true", help="--full: skip the RenderFrame()-per-iteration measurement")
     ap.add_argument("--rank-timeout", type=float, default=150.0,
                     help="N > 1: bound in seconds of every wait on another rank (rendezvous, RCCL communicator, exchange, barriers)")
     ap.add_argument("--wall-limit", type=float, default=540.0, help="N > 1, self-launched: the parent ends the ranks after this many seconds")
@@ -95,6 +101,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.with_c5 and not args.full:
+        ap.error("--with-c5 belongs to --full")
     return args
 
 
@@ -136,8 +144,10 @@ def self_launch(args) -> int:
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", str(max(1, (os.cpu_count() or 8) // max(1, args.gpus))))
     # what the run should take: start-up (the first `import torch` of a fresh box pages the image in: up to 2 min), the headline
-    # steps, the contracted build's steps, per-launch timing, counters, the oracle's parity tiles, and - at 8 ranks - C5
-    est = 45.0 + 2.0 * (args.steps + args.warmup) * 0.008 / max(1, args.gpus) + 25.0 + (40.0 if args.gpus == 8 or args.with_c5 else 0.0)
+    # steps and, with --full, the contracted build's steps, per-launch timing, counters, the oracle's parity tiles and - at 8 ranks - C5
+    est = 45.0 + 2.0 * (args.steps + args.warmup) * 0.008 / max(1, args.gpus)
+    if args.full:
+        est += 25.0 + (40.0 if args.gpus == 8 or args.with_c5 else 0.0)
     print(f"bench.py: starting {args.gpus} ranks on 127.0.0.1:{port}; expected wall time about {est:.0f} s (up to {est + 120:.0f} s on a "
           f"freshly booted box), every wait on another rank bounded by {args.rank_timeout:.0f} s, hard limit {args.wall_limit:.0f} s", file=sys.stderr, flush=True)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
@@ -383,6 +393,7 @@ def measure(name: str, args, rank: int, world: int, local_rank: int, steps: int,
     from pbrpathtracer_amd.distributed import NativeExchange, HostPackedExchange, owned_tile_count
 
     rehearsal = args.backend == "gloo"
+    full = args.full                            # everything after the timed steps and the dump is --full's
     # ---- scene: synthesised through the reference's own formats (.obj + .pts) ---------------------
     tmp = tempfile.mkdtemp(prefix=f"bench_{name}_r{rank}_")
     t0 = time.time()
@@ -493,12 +504,12 @@ def measure(name: str, args, rank: int, world: int, local_rank: int, steps: int,
             el = float(t.item())
         return el
 
-    elapsed = timed(warmup, steps, log_key="exact")
+    elapsed = timed(warmup, steps, log_key="exact")     # (the launch log stays on in a plain run: the same timed steps either way)
     timed_exchanges = exchanges[0]
     if world > 1:
         progress(f"{name}: {steps} timed steps done, {elapsed / steps * 1e3:.3f} ms per step, {timed_exchanges} exchanges")
     checksum = None
-    if world > 1 and exchange is not None:
+    if full and world > 1 and exchange is not None:
         # property check of the exchange: the gathered image holds exactly what the ranks hold together
         mine = ctx.read_accum()
         part = torch.tensor([float(mine.astype(np.float64).sum())], dtype=torch.float64)
@@ -526,12 +537,40 @@ def measure(name: str, args, rank: int, world: int, local_rank: int, steps: int,
 
     # ---- the contracted build of the trace kernels on the same steps (every rank; value stays the exact build's) ----
     contracted = None
-    if not args.no_contracted and "contract=" not in args.opts:
+    if full and not args.no_contracted and "contract=" not in args.opts:
         ctx.set_option("contract", 2)
         n_c = max(1, min(steps, 100))
         el_c = timed(min(warmup, 2), n_c)
         ctx.set_option("contract", 0)
         contracted = {"level": 2, "steps": n_c, "elapsed": el_c}
+
+    total_samples = float(W) * H * spp * steps
+    value = total_samples / elapsed / 1e6
+    ms_per_step = elapsed / steps * 1e3
+    out = None
+    if rank == 0:
+        nodes, depth, ntri = ctx.bvh_info()
+        out = {
+            "metric": "Msamples/s (pixels*spp/s)", "value": round(value, 2), "unit": "Msamples/s",
+            "n_gpus": world, "steps": steps, "warmup": warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": WORKLOADS[name], "name": name, "width": W, "height": H, "max_depth": D, "spp_per_step": spp,
+                       "triangles": ntri, "bvh_nodes": nodes, "bvh_depth": depth,
+                       "parallelism": f"tile-split x{world}" if world > 1 else "single GPU",
+                       "rccl_ranks": comm["rccl_ranks"], "devices": comm["devices"],
+                       "exchange": ((("native packed RCCL gather (ptk_gather_accum: each rank's owned tiles, 1/N of the float accumulator, "
+                                      "ncclSend/ncclRecv to rank 0)" if not rehearsal else "REHEARSAL: packed gather over gloo through host copies")
+                                     + f", every {every} steps and after the last, overlapped with the next step's trace kernel")
+                                    if exchange is not None else "none"),
+                       "exchange_every": every if exchange is not None else None,
+                       "exchanges_in_timed_region": timed_exchanges if exchange is not None else 0,
+                       "gathered_checksum": checksum},
+            "host": {"scene_gen_s": round(t_gen, 3), "scene_load_bvh_upload_s": round(t_load, 3)},
+        }
+    if not full:
+        pt.close()
+        return out, scene
 
     # kernel time per launch, measured live with HIP events recorded on the kernels' own stream around each launch
     # (trace_kernel and accumulate_kernel separately), launch by launch, un-overlapped: in the timed loop above the
@@ -550,15 +589,11 @@ def measure(name: str, args, rank: int, world: int, local_rank: int, steps: int,
             ctx.set_option("overlap", float(kv.split("=")[1]))
     fence()
 
-    total_samples = float(W) * H * spp * steps
-    value = total_samples / elapsed / 1e6
-    ms_per_step = elapsed / steps * 1e3
     if rank != 0:
         pt.close()
         return None, scene
 
     # ---- traversal counts of the kernel's own counters-enabled (untimed) variant ---------------------
-    ntri = ctx.bvh_info()[2]
     chunk = 8 if spp * owned_tile_count(W, H, rank, world) * 4.0 / 8.0 >= 49152.0 else 4   # ptk's automatic work-item size
     chunk = min(chunk, spp)
     ctx.set_tile(0, 1)
@@ -571,7 +606,6 @@ def measure(name: str, args, rank: int, world: int, local_rank: int, steps: int,
     per = {k: stats[k] / s for k in ("rays", "shadow_rays", "node_visits", "tri_tests", "hits_shaded", "tex_fetches")}
     per["max_nodes_one_ray"] = stats["max_walk_nodes"]
     live_fraction = stats["paths_started"] / s                         # paths actually traced (camera ray not a cached miss)
-    nodes, depth, _ = ctx.bvh_info()
     node_boxes = ctx.node_width() if hasattr(ctx, "node_width") else 2
     # SURVEY.md §8(d4), its own record sizes and flop counts; a visited node here holds `node_boxes` child boxes =
     # that many of the survey's 32-B node records / 30-flop box tests
@@ -667,28 +701,11 @@ def measure(name: str, args, rank: int, world: int, local_rank: int, steps: int,
         # chip sustains for 64-byte records at this occupancy (tools/microbench/gather_bench.hip)
         rec = (per["node_visits"] + per["tri_tests"] * 0.75) * step_samples / step_s / world / 256.0 / 1e9
         roofline["gather"] = {"records64_per_s_per_cu_G": round(rec, 4), "ceiling_source": "profiles/r02/gather_ceiling.json"}
-    out = {
-        "metric": "Msamples/s (pixels*spp/s)", "value": round(value, 2), "unit": "Msamples/s",
-        "n_gpus": world, "steps": steps, "warmup": warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        # what compares across rounds and configs: the samples that are actually traced (value counts every pixel of the frame;
-        # live_fraction = pixels whose camera rays can hit anything - the exact culls skip the rest)
-        "traced_samples_per_s": round(value * live_fraction, 2), "live_fraction": round(live_fraction, 4),
-        "config": {"workload": WORKLOADS[name], "name": name, "width": W, "height": H, "max_depth": D, "spp_per_step": spp,
-                   "triangles": ntri, "bvh_nodes": nodes, "bvh_depth": depth,
-                   "parallelism": f"tile-split x{world}" if world > 1 else "single GPU",
-                   "rccl_ranks": comm["rccl_ranks"], "devices": comm["devices"],
-                   "exchange": ((("native packed RCCL gather (ptk_gather_accum: each rank's owned tiles, 1/N of the float accumulator, "
-                                  "ncclSend/ncclRecv to rank 0)" if not rehearsal else "REHEARSAL: packed gather over gloo through host copies")
-                                 + f", every {every} steps and after the last, overlapped with the next step's trace kernel")
-                                if exchange is not None else "none"),
-                   "exchange_every": every if exchange is not None else None,
-                   "exchanges_in_timed_region": timed_exchanges if exchange is not None else 0,
-                   "gathered_checksum": checksum},
-        "roofline": roofline,
-        "host": {"scene_gen_s": round(t_gen, 3), "scene_load_bvh_upload_s": round(t_load, 3)},
-    }
+    # what compares across rounds and configs: the samples that are actually traced (value counts every pixel of the frame;
+    # live_fraction = pixels whose camera rays can hit anything - the exact culls skip the rest)
+    out["traced_samples_per_s"] = round(value * live_fraction, 2)
+    out["live_fraction"] = round(live_fraction, 4)
+    out["roofline"] = roofline
     if contracted is not None:
         v_c = float(W) * H * spp * contracted["steps"] / contracted["elapsed"] / 1e6
         out["value_contracted"] = {"value": round(v_c, 2), "unit": "Msamples/s", "ms_per_step": round(contracted["elapsed"] / contracted["steps"] * 1e3, 4),
@@ -792,7 +809,7 @@ def main():
         progress("process group up")
 
     out, scene = measure(args.config, args, rank, world, local_rank, args.steps, args.warmup, headline=True)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             base = cpu_baseline(scene, args.config)
             out["cpu_baseline"] = base
@@ -800,7 +817,7 @@ def main():
         except Exception as e:  # the baseline is reported, never required
             out["cpu_baseline"] = {"value": None, "unit": "Msamples/s", "cores": 0, "kind": "port", "sample": f"failed: {type(e).__name__}: {e}"}
     others = {}
-    if world == 1 and not args.no_other_configs and args.config == "C2" and not args.opts:
+    if args.full and world == 1 and not args.no_other_configs and args.config == "C2" and not args.opts:
         # the BVH-walk configs at their full BASELINE size, through the identical code path (numbers + short keys only)
         for name, k in (("C3", 4), ("C4", 4), ("C5", 3)):
             try:
@@ -808,7 +825,7 @@ def main():
                 others[name] = short(o)
             except Exception as e:
                 others[name] = {"value": None, "error": f"{type(e).__name__}: {e}"}
-    elif world > 1 and (args.with_c5 or world == 8) and args.config != "C5":
+    elif args.full and world > 1 and (args.with_c5 or world == 8) and args.config != "C5":
         # BASELINE config 5 as stated: the 1 M-triangle frame tile-split over the ranks, 1024 spp per step, the exchange
         # inside the timed region (after the last step), gathered-image checksum - every rank runs it
         try:

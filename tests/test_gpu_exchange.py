@@ -83,10 +83,10 @@ def test_native_gather_one_rank_communicator_and_overlap():
 
 
 def test_bench_exchange_on_one_gpu():
-    """bench.py --force-exchange: the N > 1 code path (communicator, exchange every K steps and after the last, checksum)
-    with one rank."""
+    """bench.py --force-exchange --full: the N > 1 code path (communicator, exchange every K steps and after the last,
+    checksum) with one rank."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C1", "--steps", "5", "--warmup", "1",
-                        "--force-exchange", "--exchange-every", "2", "--no-cpu-baseline", "--no-other-configs"],
+                        "--full", "--force-exchange", "--exchange-every", "2", "--no-cpu-baseline", "--no-other-configs"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -99,13 +99,13 @@ def test_bench_exchange_on_one_gpu():
 
 
 def test_bench_two_ranks_rehearsal_self_launched():
-    """`python bench.py --gpus 2` as the driver runs it - NOT under torchrun: bench.py starts its two ranks itself (child
+    """`python bench.py --gpus 2 --full` as the driver runs it - NOT under torchrun: bench.py starts its two ranks itself (child
     process, before it touches the GPU) and relays rank 0's line.  Two ranks must share this box's one GPU, which RCCL
     refuses, so the rehearsal backend (gloo, exchange through host copies in the library's packing order) stands in; the
     gathered image must hold exactly what the two ranks hold together."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--config", "C1", "--backend", "gloo", "--exchange-every", "2", "--no-cpu-baseline", "--with-c5"],
+                        "--config", "C1", "--backend", "gloo", "--exchange-every", "2", "--full", "--no-cpu-baseline", "--with-c5"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "C1 gathered-image checksum OK" in r.stderr and "C5 gathered-image checksum OK" in r.stderr, r.stderr[-3000:]

@@ -112,7 +112,7 @@ if len(rows) > 8:
     # steady state: the timed loop's launches (the first ones still share the chip with the warm-up; the last three are
     # bench.py's isolated launches, overlap = 0, which start after their predecessor has ended)
     steady = [p for p in pairs[len(pairs) // 4:] if p["overlap_ms"] > 0.0 and p["launch_ms"] < 1.5 * med]
-    ov = {"command": "rocprofv3 --kernel-trace -- python3 bench.py --config C2 --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity --no-contracted --no-interactive   (overlap option at its default, 1)",
+    ov = {"command": "rocprofv3 --kernel-trace -- python3 bench.py --config C2 --steps 40 --warmup 5 --full --no-cpu-baseline --no-other-configs --no-parity --no-contracted --no-interactive   (overlap option at its default, 1)",
           "kernel": "trace_kernel<false, true>", "full_launches": len(full),
           "mean_launch_ms": round(sum(p["launch_ms"] for p in steady) / len(steady), 4),
           "mean_start_to_start_ms": round(sum(p["next_start_after_this_start_ms"] for p in steady) / len(steady), 4),
@@ -147,7 +147,7 @@ for c in ("C2", "C3", "C4", "C5"):
                                             "TCC_REQ": mean_of(ds["tcc"], "TCC_REQ_sum"), "TCC_READ": mean_of(ds["tcc"], "TCC_READ_sum"),
                                             "note": "L2 (TCC) requests of one launch, summed over the 8 XCDs; what misses goes to the Infinity Cache / HBM (FETCH_SIZE)"},
         "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum (three separate passes) on "
-                  "`python3 bench.py --config %s --no-cpu-baseline --no-other-configs --opts overlap=0`; FETCH_SIZE x2 per MI355X_MICROARCH.md "
+                  "`python3 bench.py --config %s --full --no-cpu-baseline --no-other-configs --opts overlap=0`; FETCH_SIZE x2 per MI355X_MICROARCH.md "
                   "(gfx950 counts 128-B requests as 64 B), WRITE_SIZE as read" % c,
         "accumulate_kernel": {"FETCH_SIZE_KiB": mean_of(acc["fetch"], "FETCH_SIZE"), "WRITE_SIZE_KiB": mean_of(acc["write"], "WRITE_SIZE"),
                               "ms": mean_of(acc["fetch"], "ms")},

@@ -15,20 +15,20 @@ WHAT=${@:-bench ktrace traffic sq class}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 has() { [[ " $WHAT " == *" $1 "* ]]; }
-B="--no-cpu-baseline --no-other-configs --no-parity --no-contracted --no-interactive --opts overlap=0"
+B="--full --no-cpu-baseline --no-other-configs --no-parity --no-contracted --no-interactive --opts overlap=0"
 steps_of() { case $1 in C5) echo "--steps 1 --warmup 0";; C3|C4) echo "--steps 2 --warmup 1";; *) echo "--steps 3 --warmup 1";; esac; }
 
 if has bench; then
-  python3 $ROOT/bench.py --steps 100 --warmup 5 > $OUT/bench_C2.json 2> $OUT/bench_C2.err
-  python3 $ROOT/bench.py --config C1 --steps 200 --warmup 10 --no-cpu-baseline --no-other-configs > $OUT/bench_C1.json 2> $OUT/bench_C1.err
-  python3 $ROOT/bench.py --config C3 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_C3.json 2> $OUT/bench_C3.err
-  python3 $ROOT/bench.py --config C4 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_C4.json 2> $OUT/bench_C4.err
-  python3 $ROOT/bench.py --config C5 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_C5.json 2> $OUT/bench_C5.err
+  python3 $ROOT/bench.py --steps 100 --warmup 5 --full > $OUT/bench_C2.json 2> $OUT/bench_C2.err
+  python3 $ROOT/bench.py --config C1 --steps 200 --warmup 10 --full --no-cpu-baseline --no-other-configs > $OUT/bench_C1.json 2> $OUT/bench_C1.err
+  python3 $ROOT/bench.py --config C3 --steps 5 --warmup 1 --full --no-cpu-baseline > $OUT/bench_C3.json 2> $OUT/bench_C3.err
+  python3 $ROOT/bench.py --config C4 --steps 5 --warmup 1 --full --no-cpu-baseline > $OUT/bench_C4.json 2> $OUT/bench_C4.err
+  python3 $ROOT/bench.py --config C5 --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/bench_C5.json 2> $OUT/bench_C5.err
 fi
 python3 -c "import sys; sys.path.insert(0, '$ROOT'); import bench; print(bench.kernel_source_sha256())" > $OUT/kernel_source_sha256.txt
 if has ktrace; then
   # the DEFAULT run (overlap = 1): consecutive launches on two streams, for profiles/<round>/overlap_trace_C2.json
-  timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d $OUT/ktrace_overlap_C2 -- python3 $ROOT/bench.py --config C2 --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity --no-contracted --no-interactive > $OUT/ktrace_overlap_C2.log 2>&1
+  timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d $OUT/ktrace_overlap_C2 -- python3 $ROOT/bench.py --config C2 --steps 40 --warmup 5 --full --no-cpu-baseline --no-other-configs --no-parity --no-contracted --no-interactive > $OUT/ktrace_overlap_C2.log 2>&1
   for cfg in C2 C4; do
     timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ktrace_$cfg -- python3 $ROOT/bench.py --config $cfg $(steps_of $cfg) $B > $OUT/ktrace_$cfg.log 2>&1
   done
