@@ -237,6 +237,8 @@ int ptk_accum_device_ptr(ptk_ctx* ctx, void** dev_ptr, size_t* bytes);
 int ptk_rgb8_device_ptr(ptk_ctx* ctx, void** dev_ptr, size_t* bytes);
 /* render into a caller-owned device accumulator (W*H*3 floats) instead of the internal one */
 int ptk_bind_accum(ptk_ctx* ctx, void* dev_ptr);
+/* render on the caller's stream from now on (it stays the caller's: ptk_destroy leaves it alone).  Switching from one caller
+ * stream to another needs no host wait: the new stream is ordered behind everything queued on the old one. */
 int ptk_set_stream(ptk_ctx* ctx, void* hip_stream);
 
 /* ---- multi-GPU exchange step (no counterpart in the reference, which renders on one CPU: SURVEY.md 8e) -------------
@@ -269,6 +271,9 @@ int ptk_gather_accum(ptk_ctx* ctx, void* rccl_comm, int root);
 int ptk_gather_wait(ptk_ctx* ctx);                                    /* host waits for the last exchange */
 int ptk_read_gathered(ptk_ctx* ctx, float* host_out);                 /* root: W*H*3 floats, rows bottom-up; waits */
 int ptk_gathered_device_ptr(ptk_ctx* ctx, void** dev_ptr, size_t* bytes);
+/* A failed exchange (ptk_gather_wait, or the wait inside ptk_read_gathered, returns an error: a timeout, an aborted
+ * communicator, an asynchronous RCCL or HIP error) leaves no gathered image: ptk_read_gathered and ptk_gathered_device_ptr
+ * refuse with PTK_ERR_BAD_ARG until the next ptk_gather_accum succeeds. */
 /* test hook: keeps the exchange stream busy for `milliseconds` (0 .. 10 000) ahead of whatever is queued on it next, so that the
  * bound of ptk_gather_wait ("comm_timeout_s") can be exercised on one GPU; the kernel behind it always ends by itself */
 int ptk_debug_stall_exchange(ptk_ctx* ctx, int milliseconds);

@@ -690,7 +690,16 @@ const char* ptk_last_error(ptk_ctx* c)
 int ptk_set_stream(ptk_ctx* c, void* s)
 {
     if (!c) return PTK_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
     if (c->own_stream && c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
+    else if ((hipStream_t)s != c->stream)
+    {
+        // from one caller stream to another, with no host wait: the new stream goes on behind everything queued on the old one
+        // (accumulate kernels of the renders in flight, whose trace kernels run on the internal streams), so that the next
+        // accumulate kernel adds to a finished accumulator and the caller's work on the new stream sees every batch, in order
+        HIPCHK(c, hipEventRecord(c->ev_inputs, c->stream));
+        HIPCHK(c, hipStreamWaitEvent((hipStream_t)s, c->ev_inputs, 0));
+    }
     c->stream = (hipStream_t)s;
     c->own_stream = false;
     c->inputs_dirty = true;                      // re-anchor the trace streams behind the new stream
@@ -1665,7 +1674,8 @@ int ptk_gather_accum(ptk_ctx* c, void* rccl_comm, int root)
 // Bounded: polls the exchange's last event; when it has not fired within comm_timeout_s (a rank never entered its
 // ptk_gather_accum, or died in it) the communicator is aborted - which releases the transfer kernel stuck on the exchange
 // stream - and the caller gets PTK_ERR_RCCL with rank, step and the bytes that were expected.  An asynchronous RCCL error
-// (a peer's process gone) ends the wait at once.
+// (a peer's process gone) ends the wait at once.  A failed exchange leaves no gathered image: d_gathered may hold part of this
+// step's or the last step's image, so ptk_read_gathered and ptk_gathered_device_ptr refuse until a ptk_gather_accum succeeds.
 int ptk_gather_wait(ptk_ctx* c)
 {
     if (!c) return PTK_ERR_BAD_ARG;
@@ -1677,7 +1687,11 @@ int ptk_gather_wait(ptk_ctx* c)
     {
         const hipError_t q = hipEventQuery(c->ev_gathered);
         if (q == hipSuccess) break;
-        if (q != hipErrorNotReady) { c->gather_pending = false; return fail(c, PTK_ERR_HIP, std::string("hipEventQuery (exchange): ") + hipGetErrorString(q)); }
+        if (q != hipErrorNotReady)
+        {
+            c->gather_pending = false; c->gathered_w = c->gathered_h = 0;
+            return fail(c, PTK_ERR_HIP, std::string("hipEventQuery (exchange): ") + hipGetErrorString(q));
+        }
         (void)hipGetLastError();
         const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         ncclResult_t async = ncclSuccess;
@@ -1704,7 +1718,7 @@ int ptk_gather_wait(ptk_ctx* c)
                 while (!done->load() && std::chrono::duration<double>(std::chrono::steady_clock::now() - a0).count() < grace)
                     std::this_thread::sleep_for(std::chrono::milliseconds(1));
             }
-            c->gather_pending = false;
+            c->gather_pending = false; c->gathered_w = c->gathered_h = 0;
             return fail(c, PTK_ERR_RCCL, msg);
         }
         if (waited > 0.002) std::this_thread::sleep_for(std::chrono::microseconds(200));

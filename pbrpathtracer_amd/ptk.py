@@ -358,6 +358,11 @@ class Context:
         self._chk(self.L.ptk_accum_device_ptr(self.h, C.byref(p), C.byref(b)), "ptk_accum_device_ptr")
         return p.value, b.value
 
+    def rgb8_device_ptr(self):
+        p = C.c_void_p(); b = C.c_size_t()
+        self._chk(self.L.ptk_rgb8_device_ptr(self.h, C.byref(p), C.byref(b)), "ptk_rgb8_device_ptr")
+        return p.value, b.value
+
     def bind_accum(self, dev_ptr: int):
         self._chk(self.L.ptk_bind_accum(self.h, dev_ptr), "ptk_bind_accum")
 
@@ -407,6 +412,11 @@ class Context:
         out = np.empty((self.height, self.width, 3), dtype=np.float32)
         self._chk(self.L.ptk_read_gathered(self.h, out.ctypes.data), "ptk_read_gathered")
         return out
+
+    def gathered_device_ptr(self):
+        p = C.c_void_p(); b = C.c_size_t()
+        self._chk(self.L.ptk_gathered_device_ptr(self.h, C.byref(p), C.byref(b)), "ptk_gathered_device_ptr")
+        return p.value, b.value
 
     def probe_pack(self, rank: int, world: int) -> np.ndarray:
         out = np.zeros(packed_floats(self.width, self.height, rank, world), np.float32)

@@ -169,8 +169,9 @@ def test_native_gather_wait_is_bounded():
 def test_native_gather_wait_times_out_on_a_step_that_does_not_complete():
     """The bound INSIDE ptk_gather_wait, on one GPU: the exchange stream is kept busy for 3 s (ptk_debug_stall_exchange) ahead of an
     exchange step, and comm_timeout_s is 0.3 s - the wait must come back with PTK_ERR_RCCL naming step, rank, root and the bytes
-    outstanding well before the stream drains, the communicator is gone afterwards (aborted), and a fresh one gathers the right
-    image again.  In a child process under a time limit: a wait that is not bounded would otherwise hang the suite."""
+    outstanding well before the stream drains, the communicator is gone afterwards (aborted), no gathered image is left to read
+    (ptk_read_gathered and ptk_gathered_device_ptr refuse rather than hand out a partial or stale one), and a fresh one gathers the
+    right image again.  In a child process under a time limit: a wait that is not bounded would otherwise hang the suite."""
     code = (
         "import sys, time; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
         "import numpy as np\n"
@@ -187,6 +188,11 @@ def test_native_gather_wait_times_out_on_a_step_that_does_not_complete():
         "    c.gather_wait(); print('WAITED %%.2f s' %% (time.time() - t0))\n"
         "except ptk.PtkError as e:\n"
         "    print('REFUSED in %%.2f s: %%s' %% (time.time() - t0, e))\n"
+        "for name in ('read_gathered', 'gathered_device_ptr'):\n"      # a failed exchange leaves no gathered image to read
+        "    try:\n"
+        "        getattr(c, name)(); print('STALE IMAGE FROM %%s' %% name)\n"
+        "    except ptk.PtkError as e:\n"
+        "        print('NO IMAGE FROM %%s: %%s' %% (name, e))\n"
         "try:\n"
         "    c.gather_accum(0); print('GATHERED WITHOUT A COMMUNICATOR')\n"
         "except ptk.PtkError as e:\n"
@@ -196,6 +202,7 @@ def test_native_gather_wait_times_out_on_a_step_that_does_not_complete():
         "c.comm_init(ptk.comm_unique_id(), 0, 1)\n"
         "c.gather_accum(0); g = c.read_gathered()\n"
         "print('RECOVERED' if np.array_equal(g, c.read_accum()) else 'WRONG IMAGE AFTER RECOVERY')\n"
+        "print('DEVICE VIEW %%d bytes' %% c.gathered_device_ptr()[1])\n"
         "sys.stdout.flush()\n"
         "import os; os._exit(0)\n") % (ROOT, os.path.join(ROOT, "tests"))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT)
@@ -204,7 +211,10 @@ def test_native_gather_wait_times_out_on_a_step_that_does_not_complete():
     waited = float(out.split("REFUSED in ")[1].split(" s")[0])
     assert 0.3 <= waited < 1.5, out
     assert "AFTERWARDS:" in out and "communicator" in out.split("AFTERWARDS:")[1].splitlines()[0], out
+    for name in ("read_gathered", "gathered_device_ptr"):
+        assert f"NO IMAGE FROM {name}:" in out and "no gathered image" in out.split(f"NO IMAGE FROM {name}:")[1].splitlines()[0], (out, r.stderr[-2000:])
     assert "RECOVERED" in out, (out, r.stderr[-2000:])
+    assert f"DEVICE VIEW {W * H * 12} bytes" in out, out
 
 
 def test_native_gather_between_two_gpus(tmp_path):
