@@ -312,6 +312,10 @@ int ptk_probe_unpack(ptk_ctx* ctx, int world, const float* host_packed /* all ra
  * 1 = the trace kernels built with -ffp-contract=fast (a * b + c fuses), 2 = ... and 1-ulp hardware reciprocal / square root / rsq:
  * per-channel RMSE of the mean image against the exact kernels <= 1e-3 (measured ~1e-5 .. 9e-5, tests/test_gpu_contract.py);
  * sample by sample and reproducibility bit for bit: tests/test_gpu_contract_samples.py.
+ * "plain_kernel" = 0/1 (default 1): a PLAIN scene is traced by a variant of the FLAT kernel with everything such a scene cannot
+ * reach compiled out; 0 launches the generic FLAT kernel for it as well.  Bit-identical either way (tests/test_gpu_plain_kernel.py).
+ * A scene is plain when ptk_scene_is_plain holds for its tables AND the primary-hit cache is active (aperture 0, "primary_cache"
+ * and "flat" on); decided anew for every render, so material edits, a new scene or an opened aperture take effect at once.
  * No environment variable reaches the library. */
 int ptk_set_option(ptk_ctx* ctx, const char* name, double value);
 
@@ -326,6 +330,17 @@ int ptk_last_kernel_ms(ptk_ctx* ctx, float* trace_ms, float* accumulate_ms);
  * ptk_kernel_log_read waits for the streams and returns the durations in launch order (bench.py: the per-launch times INSIDE
  * its timed region, beside ms_per_step). */
 int ptk_kernel_log(ptk_ctx* ctx, int capacity);
+/* which trace kernel the newest launch of this context ran (renders and ptk_collect_stats alike; the counters-enabled kernels
+ * have no PLAIN variant) */
+#define PTK_TRACE_NONE 0         /* nothing launched yet */
+#define PTK_TRACE_BVH 1          /* the BVH walk */
+#define PTK_TRACE_FLAT 2         /* <= 16 triangles: the generic FLAT kernel */
+#define PTK_TRACE_FLAT_PLAIN 3   /* ... its PLAIN variant */
+int ptk_trace_variant(ptk_ctx* ctx, int* variant);
+/* the scene-table half of the PLAIN predicate, no device needed: 1 when the scene has 1..16 triangles, every material is OPAQUE
+ * (type 0) with none of its five shading textures (tex[0..4] < 0), and no triangle is smoothed or has a material with an opacity
+ * texture (tex[5] >= 0); 0 otherwise */
+int ptk_scene_is_plain(const ptk_scene_desc* scene);
 int ptk_kernel_log_read(ptk_ctx* ctx, float* trace_ms, int max_entries, int* num_entries);
 int ptk_collect_stats(ptk_ctx* ctx, uint32_t first_sample, uint32_t spp_count, uint64_t seed, ptk_stats* out);
 int ptk_bvh_info(ptk_ctx* ctx, int32_t* num_nodes, int32_t* depth /* wide nodes on the longest chain */, int32_t* num_leaf_tris);

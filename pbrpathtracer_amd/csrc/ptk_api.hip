@@ -50,6 +50,12 @@ struct ptk_ctx {
     std::vector<ptk_material> h_materials;
     std::vector<int32_t> h_texmap, h_light_material;
     std::vector<float> h_lights;
+    // FLAT scenes: each triangle's smoothing flag and material, for re-deciding scene_plain when the materials are edited
+    std::vector<uint8_t> h_flat_smoothing;
+    std::vector<int32_t> h_flat_material;
+    bool scene_plain = false;           // plain_tables() of the staged scene: kept current by ptk_upload_scene and ptk_update_materials
+    int opt_plain_kernel = 1;           // 0: plain scenes launch the generic FLAT kernel too (tests, A/B runs)
+    int last_trace_variant = PTK_TRACE_NONE;     // of the newest trace launch (ptk_trace_variant)
 
     // camera (host copies, already normalised / clamped like the reference setters)
     float cam_pos[3] = { 0, 0, 0 }, cam_dir[3] = { 0, 0, 1 }, cam_up[3] = { 0, 1, 0 };
@@ -271,6 +277,26 @@ int ensure_primary(ptk_ctx* c)
     return PTK_OK;
 }
 
+// The scene-table half of "plain" (ptk.h ptk_scene_is_plain): few enough triangles for the FLAT kernel, every material opaque and
+// without a texture in its five shading slots, no triangle smoothed or of a material with an opacity texture.  Such a scene cannot
+// reach anything the PLAIN variant of the FLAT trace kernel leaves out, whatever its materials' other fields hold.
+bool plain_tables(int32_t n, const uint8_t* smoothing, const int32_t* material, int32_t num_materials, const ptk_material* mats)
+{
+    if (n <= 0 || n > 16 || !smoothing || !material || !mats) return false;
+    for (int32_t i = 0; i < num_materials; i++)
+    {
+        if (mats[i].type != 0) return false;
+        for (int k = 0; k < 5; k++)
+            if (mats[i].tex[k] >= 0) return false;
+    }
+    for (int32_t i = 0; i < n; i++)
+    {
+        if (smoothing[i]) return false;
+        if (material[i] < 0 || material[i] >= num_materials || mats[material[i]].tex[5] >= 0) return false;
+    }
+    return true;
+}
+
 bool primary_cacheable(const ptk_ctx* c)
 {
     return c->opt_primary_cache && c->aperture == 0.0f && !c->scene_has_opacity && c->have_scene && c->d_primary_hit;
@@ -380,6 +406,8 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
         }
         p.primary_hit = c->d_primary_hit; p.primary_rd = c->d_primary_rd;
     }
+    // decided per render from the staged state: a material edit, a new scene or an opened aperture since the last one is seen here
+    p.plain = (c->opt_plain_kernel && c->scene_plain && p.flat_count > 0 && p.primary_hit != nullptr) ? 1 : 0;
     if (!c->pixel_rng_valid || c->pixel_rng_seed != seed)
     {
         launch_pixel_rng((uint32_t)seed, (uint32_t)(seed >> 32), c->width * c->height, c->d_pixel_rng, c->stream);
@@ -559,6 +587,7 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
         else if (c->opt_contract == 2 && !stats) fast::launch_trace(p, tiles * 4, c->resident_waves, tstream, false);
         else launch_trace(p, tiles * 4, c->resident_waves, tstream, stats);
         HIPCHK(c, hipGetLastError());
+        c->last_trace_variant = p.flat_count <= 0 ? PTK_TRACE_BVH : ((p.plain && !stats) ? PTK_TRACE_FLAT_PLAIN : PTK_TRACE_FLAT);
         if (timed && pi >= 0) HIPCHK(c, hipEventRecord(c->ev[pi][1], tstream));
         if (kl >= 0) { HIPCHK(c, hipEventRecord(c->klog_ev[2 * kl + 1], tstream)); c->klog_n = kl + 1; }
         if (overlap)
@@ -933,6 +962,9 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
     c->h_materials.assign(s->materials, s->materials + s->num_materials);
     c->h_texmap = texmap;
     c->h_lights = lights;
+    c->h_flat_smoothing.clear(); c->h_flat_material.clear();
+    if (n > 0 && n <= 16) { c->h_flat_smoothing.assign(s->smoothing, s->smoothing + n); c->h_flat_material.assign(s->material, s->material + n); }
+    c->scene_plain = plain_tables(n, s->smoothing, s->material, s->num_materials, s->materials);
     c->h_light_material.resize(s->num_lights);
     for (int32_t k = 0; k < s->num_lights; k++) c->h_light_material[k] = s->material[s->lights[k]];
     c->primary_hit_dirty = true;
@@ -968,7 +1000,21 @@ int ptk_update_materials(ptk_ctx* c, int32_t num_materials, const ptk_material* 
     if (!c->h_lights.empty()) HIPCHK(c, hipMemcpyAsync(c->d_lights, c->h_lights.data(), c->h_lights.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // the host vectors above go out of scope
     c->h_materials.assign(materials, materials + num_materials);
+    c->scene_plain = plain_tables((int32_t)c->h_flat_material.size(), c->h_flat_smoothing.data(), c->h_flat_material.data(), num_materials, materials);
     c->inputs_dirty = true;
+    return PTK_OK;
+}
+
+int ptk_scene_is_plain(const ptk_scene_desc* s)
+{
+    if (!s) return 0;
+    return plain_tables(s->num_triangles, s->smoothing, s->material, s->num_materials, s->materials) ? 1 : 0;
+}
+
+int ptk_trace_variant(ptk_ctx* c, int* variant)
+{
+    if (!c || !variant) return PTK_ERR_BAD_ARG;
+    *variant = c->last_trace_variant;
     return PTK_OK;
 }
 
@@ -1952,6 +1998,11 @@ int ptk_set_option(ptk_ctx* c, const char* name, double value)
     if (!std::strcmp(name, "flat"))
     {
         c->opt_flat = value != 0.0;
+        return PTK_OK;
+    }
+    if (!std::strcmp(name, "plain_kernel"))
+    {
+        c->opt_plain_kernel = value != 0.0;
         return PTK_OK;
     }
     if (!std::strcmp(name, "device_build"))

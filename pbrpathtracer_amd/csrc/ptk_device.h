@@ -98,6 +98,9 @@ struct RenderParams {
     float cam_pos[3], cam_right[3], cam_up[3];
     float focal_dist, aperture;
     float resolve_samples;      // (float)(first_sample + spp) = (float)mSamples
+    int plain;                  // 1: launch_trace takes the PLAIN variant of the FLAT kernel - a host-side promise (ptk_api.hip plain_scene +
+                                // primary-hit cache) that every material is opaque and untextured, no triangle is smoothed or has an
+                                // opacity texture and primary_hit is set; no kernel reads it (last field: the others keep their offsets)
 };
 
 struct PrimaryParams {

@@ -72,6 +72,10 @@ namespace fma {
 #define PTK_TRACE_WAVES 5           // waves per SIMD the register allocator must allow, FLAT variant: 96 VGPRs (4 spilled) since the parameters
                                     // are read through the constant address space; C2 +3.4-4.5 %, C1 +4 % over four waves (six: 80 VGPRs, 37 spilled, -6 %)
 #endif
+#ifndef PTK_TRACE_WAVES_PLAIN
+#define PTK_TRACE_WAVES_PLAIN 5     // ... its PLAIN variant: 72 VGPRs and nothing spilled at five, six and seven alike.  Seven make an isolated C2 launch
+                                    // 3 % shorter and leave ms_per_step where it is (consecutive launches share the chip either way): five stay
+#endif
 #ifndef PTK_TRACE_WAVES_BVH
 #define PTK_TRACE_WAVES_BVH 4       // ... BVH variant
 #endif
@@ -368,7 +372,8 @@ __device__ __forceinline__ bool tri_test(const PT& P, Walk& W, float4 t0, float4
 // (ox, oy, oz are not read - both rays leave W.ro, see tri_test_pair - but dropping them reorders a few moves of the kernels)
 struct RayPair { f2 ox, oy, oz, dx, dy, dz; };
 
-template <bool STATS, class PT>
+// PLAIN (trace_kernel): no triangle of the scene has an opacity texture, so the opacity branch is dead code.
+template <bool STATS, bool PLAIN, class PT>
 __device__ __forceinline__ bool tri_test_pair(const PT& P, Walk& W, Walk& WS, const RayPair& R, const bool shadow_live, float4 t0, float4 t1,
                                               float4 t2, const Rng& rng, uint32_t ray_bounce, uint32_t ray_shadow, Counters& cnt)
 {
@@ -396,7 +401,7 @@ __device__ __forceinline__ bool tri_test_pair(const PT& P, Walk& W, Walk& WS, co
     // later record: nearer-than-best is the whole rule
     okb = okb & (t.x < W.best.t);
     oks = oks & shadow_live & (t.y < WS.best.t);
-    if ((okb | oks) && otex >= 0)
+    if (!PLAIN && (okb | oks) && otex >= 0)
     {
         // stochastic opacity, pathtracer.cpp:469-476 (GetUV :533-536); rare: skipped with s_cbranch_execz
         const float4* sp4 = P.shade + (size_t)tri * SHADE_F4;
@@ -642,7 +647,10 @@ __device__ __forceinline__ bool sample_direct_light(const PT& P, v3 p, v3 n, v3 
 // ends here; otherwise W holds the next ray to walk (BVH kernels: the shadow ray towards the sampled light - W.occl_tri >= 0,
 // W.best = its light triangle's own hit, Tdi its contribution, nextDir the bounce direction that follows - or the bounce
 // ray itself; FLAT kernel: W the bounce ray and WS the shadow ray, tested in one pass).  Shared by every trace kernel.
-template <bool STATS, bool FLAT, class PT>
+// PLAIN (trace_kernel): every material is opaque and untextured and no triangle is smoothed, so the texture lookups, the UVs,
+// the smoothed and normal-mapped normals and the glass branch are dead code; what remains is the mtype == 0 route, operation
+// for operation and draw for draw.
+template <bool STATS, bool FLAT, bool PLAIN, class PT>
 __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS, int* stack, Rng& rng, v3& L, v3& T, v3& Tdi, v3& nextDir,
                                                   int& depth, int& iter, bool& inside, const uint32_t ray, Counters& cnt)
 {
@@ -652,20 +660,21 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
     const float4* sp4 = P.shade + (size_t)h.tri * SHADE_F4;
     float4 s0 = ldg4(sp4);
     int mbits = __float_as_int(s0.w);
-    int matid = mbits & 0x7fffffff;
-    bool smoothing = mbits < 0;
+    int matid = PLAIN ? mbits : mbits & 0x7fffffff;
+    bool smoothing = !PLAIN && mbits < 0;
     const float4* mp = P.mats + (size_t)matid * MAT_F4;
     // the whole 96-byte material in one batch (two of its words are only needed further down: asked for there,
     // they cost the block another memory round trip), and the vertex normals of a smoothed triangle with it
     float4 m0 = ldg4(mp), m1 = ldg4(mp + 1), m2 = ldg4(mp + 2), m3 = ldg4(mp + 3);
-    float4 m4f = ldg4(mp + 4), m5f = ldg4(mp + 5);
+    const float4 notex = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), __int_as_float(-1));
+    float4 m4f = PLAIN ? notex : ldg4(mp + 4), m5f = PLAIN ? notex : ldg4(mp + 5);
     float4 sn2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), sn3 = sn2, sn4 = sn2;
     if (smoothing) { sn2 = ldg4(sp4 + 2); sn3 = ldg4(sp4 + 3); sn4 = ldg4(sp4 + 4); }
     asm volatile("" ::: "memory");
     int tex_diffuse = __float_as_int(m4f.x), tex_normal = __float_as_int(m4f.y);
     int tex_emiss = __float_as_int(m4f.z), tex_rough = __float_as_int(m4f.w);
     int tex_metal = __float_as_int(m5f.x);
-    bool any_tex = __float_as_int(m5f.z) != 0;
+    bool any_tex = !PLAIN && __float_as_int(m5f.z) != 0;
 
     v3 p = add(ro, muls(rd, h.t));                  // :553
     float uvx = 0.0f, uvy = 0.0f;
@@ -714,7 +723,7 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
         if (tex_rough >= 0) { roughness = tex2d_r(P, tex_rough, uvx, uvy); if (STATS) cnt.tex++; }
         float reflectiveness = m3.x;
         if (tex_metal >= 0) { reflectiveness = tex2d_r(P, tex_metal, uvx, uvy); if (STATS) cnt.tex++; }
-        const int mtype = __float_as_int(m0.w);
+        const int mtype = PLAIN ? 0 : __float_as_int(m0.w);
         const v3 specular = V(m1.x, m1.y, m1.z);
         const float emissI = m1.w;
 
@@ -952,13 +961,18 @@ enum : int { ST_NEED = 0, ST_GEN = 1, ST_TRAV = 2, ST_SHADE = 3, ST_DONE = 4 };
 // lane tests every triangle, the records are fetched with SCALAR loads (one s_load per triangle per
 // wave, operands broadcast from SGPRs, no vector memory traffic and no LDS stack), and the whole walk
 // is one block of the state machine, so lanes re-synchronise by themselves.
-template <bool STATS, bool FLAT>
-__global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRACE_WAVES_BVH)) void trace_kernel(const RenderParams* __restrict__ Pp)
+// PLAIN = a FLAT scene that is also opaque, untextured, flat-shaded, without opacity textures and seen through a cached pinhole
+// camera (ptk_api.hip decides, see RenderParams::plain): the same text with everything such a scene cannot reach compiled out -
+// textures, UVs, smoothed / mapped normals, stochastic opacity and its two keys per pass, the glass branch, the camera-ray block.
+// The route it does take is untouched, so its samples are bit-identical to the generic kernel's.
+template <bool STATS, bool FLAT, bool PLAIN>
+__global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : FLAT ? PTK_TRACE_WAVES : PTK_TRACE_WAVES_BVH)) void trace_kernel(const RenderParams* __restrict__ Pp)
 {
     // the parameters live in the launch's queue block, in the constant address space: fields are s_load-ed where they are
     // used instead of being preloaded whole into SGPRs (ptk_device.h: 30 / 42 SGPR spills -> 0)
     typedef const __attribute__((address_space(4))) RenderParams ConstParams;
     ConstParams& P = *(ConstParams*)(uintptr_t)Pp;
+    static_assert(FLAT || !PLAIN, "PLAIN is a variant of the FLAT kernel");
     __shared__ int lds_stack[FLAT ? 1 : PTK_STACK_ROWS * PTK_TRACE_BLOCK];
     if (P.exit_flag && __hip_atomic_load(P.exit_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= P.exit_gen) return;     // an Exit() named this render or a later one
 
@@ -1082,7 +1096,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRAC
                     // cached camera rays (pinhole, no stochastic opacity): the path starts at its first surface
                     // interaction, so the lane queues for the SHADE block directly and sets its path up there (depth < 0
                     // marks it) - one voted block less to wait for per path, and bigger shading batches
-                    st = P.primary_hit ? ST_SHADE : ST_GEN;
+                    st = (PLAIN || P.primary_hit) ? ST_SHADE : ST_GEN;
                     depth = -1;
                 }
                 next_unit = min(total_units, next_unit + (uint32_t)__popcll(m_need));
@@ -1091,7 +1105,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRAC
         }
         const unsigned long long m_trav = __ballot(st == ST_TRAV);
         const unsigned long long m_shade = __ballot(st == ST_SHADE);
-        const unsigned long long m_gen = __ballot(st == ST_GEN);
+        const unsigned long long m_gen = PLAIN ? 0ull : __ballot(st == ST_GEN);      // (PLAIN: no lane is ever in GEN)
         const int n_trav = __popcll(m_trav), n_shade = __popcll(m_shade), n_gen = __popcll(m_gen);
         const int n_live = n_trav + n_shade + n_gen;
         if (n_live == 0) break;
@@ -1130,7 +1144,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRAC
                         const f4v a0 = ct[k * TRI_F4], a1 = ct[k * TRI_F4 + 1], a2 = ct[k * TRI_F4 + 2];
                         const float4 t0 = make_float4(a0.x, a0.y, a0.z, a0.w), t1 = make_float4(a1.x, a1.y, a1.z, a1.w),
                                      t2 = make_float4(a2.x, a2.y, a2.z, a2.w);
-                        (void)tri_test_pair<STATS>(P, W, WS, R, shadow, t0, t1, t2, rng, bounce_ray, ray, cnt);
+                        (void)tri_test_pair<STATS, PLAIN>(P, W, WS, R, shadow, t0, t1, t2, rng, bounce_ray, ray, cnt);
                     }
                     if (shadow)
                     {
@@ -1226,12 +1240,12 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (FLAT ? PTK_TRACE_WAVES : PTK_TRAC
                     W.node = NODE_EXIT; W.top = stack; W.tri_left = 0;
                 }
                 // ---- one surface interaction of PathTracer::Trace, pathtracer.cpp:551-727 ----
-                const bool ended = shade_interaction<STATS, FLAT>(P, W, WS, stack, rng, L, T, Tdi, nextDir, depth, iter, inside, ray, cnt);
+                const bool ended = shade_interaction<STATS, FLAT, PLAIN>(P, W, WS, stack, rng, L, T, Tdi, nextDir, depth, iter, inside, ray, cnt);
                 if (ended) PTK_FINISH_PATH();
                 else st = ST_TRAV;
             }
         }
-        else
+        else if (!PLAIN)
         {
             if (STATS) { const uint32_t ngx = (uint32_t)__popcll(__ballot(st == ST_GEN)); if (lane == 0) { cnt.gen_execs++; cnt.gen_lanes += ngx; } }
             if (st == ST_GEN)
@@ -1655,7 +1669,7 @@ void launch_trace(const RenderParams& p0, int num_subtiles, int resident_waves, 
     // big launches: persistent waves, as many one-wave workgroups as the chip holds at once, each pulling items until
     // none is left; small ones: a wave per (possible) item, the dispatcher balances those better
     if (!(p.flat_count > 0) && PTK_TRACE_WAVES_BVH != 4) resident_waves = resident_waves / 16 * 4 * PTK_TRACE_WAVES_BVH;
-    if (p.flat_count > 0 && PTK_TRACE_WAVES != 4) resident_waves = resident_waves / 16 * 4 * PTK_TRACE_WAVES;
+    if (p.flat_count > 0 && PTK_TRACE_WAVES != 4) resident_waves = resident_waves / 16 * 4 * ((p.plain && !stats) ? PTK_TRACE_WAVES_PLAIN : PTK_TRACE_WAVES);
     if (p.persistent < 0) p.persistent = padded > 4 * resident_waves ? 1 : 0;
     const int generations = p.persistent ? std::max(1, std::min(p.generations, padded / resident_waves)) : 1;
     const int blocks = p.persistent ? resident_waves * generations : padded;
@@ -1664,12 +1678,13 @@ void launch_trace(const RenderParams& p0, int num_subtiles, int resident_waves, 
     const RenderParams* dp = queue_block_params(p.queues);
     const bool flat = p.flat_count > 0;
 #if !PTK_CONTRACT
-    if (stats && flat) hipLaunchKernelGGL((trace_kernel<true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
-    else if (stats) hipLaunchKernelGGL((trace_kernel<true, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    if (stats && flat) hipLaunchKernelGGL((trace_kernel<true, true, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    else if (stats) hipLaunchKernelGGL((trace_kernel<true, false, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else
 #endif
-    if (flat) hipLaunchKernelGGL((trace_kernel<false, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
-    else hipLaunchKernelGGL((trace_kernel<false, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    if (flat && p.plain) hipLaunchKernelGGL((trace_kernel<false, true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    else if (flat) hipLaunchKernelGGL((trace_kernel<false, true, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    else hipLaunchKernelGGL((trace_kernel<false, false, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
 }
 
 #if !PTK_CONTRACT

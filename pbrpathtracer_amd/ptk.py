@@ -79,6 +79,7 @@ SYMBOLS = [
     "ptk_gather_wait", "ptk_read_gathered", "ptk_gathered_device_ptr", "ptk_probe_pack", "ptk_probe_unpack",
     "ptk_bind_out_image", "ptk_bind_out_device", "ptk_bind_gl_buffer", "ptk_comm_info", "ptk_kernel_log", "ptk_kernel_log_read",
     "ptk_debug_stall_exchange", "ptk_render_adaptive", "ptk_read_sample_counts", "ptk_read_moments",
+    "ptk_trace_variant", "ptk_scene_is_plain",
 ]
 
 
@@ -152,6 +153,8 @@ def _load_locked() -> C.CDLL:
         L.ptk_kernel_log.argtypes = [vp, i32]
         L.ptk_kernel_log_read.argtypes = [vp, C.POINTER(C.c_float), i32, C.POINTER(C.c_int)]
         L.ptk_debug_stall_exchange.argtypes = [vp, i32]
+        L.ptk_trace_variant.argtypes = [vp, C.POINTER(C.c_int)]
+        L.ptk_scene_is_plain.argtypes = [C.POINTER(SceneDesc)]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -165,6 +168,16 @@ def _load_locked() -> C.CDLL:
     L.ptk_probe_primary_dirs.argtypes = [vp, vp]
     _lib = L
     return L
+
+
+TRACE_NONE, TRACE_BVH, TRACE_FLAT, TRACE_FLAT_PLAIN = 0, 1, 2, 3      # ptk_trace_variant
+
+
+def scene_is_plain(arrays: dict) -> bool:
+    """ptk_scene_is_plain on a scene's arrays: the table half of the PLAIN-kernel predicate (no device needed)."""
+    a = normalise_arrays(arrays)
+    d = scene_desc(a)
+    return bool(load().ptk_scene_is_plain(C.byref(d)))
 
 
 def normalise_arrays(a: dict) -> dict:
@@ -318,6 +331,12 @@ class Context:
         buf = (C.c_float * cap)(); n = C.c_int(0)
         self._chk(self.L.ptk_kernel_log_read(self.h, buf, cap, C.byref(n)), "ptk_kernel_log_read")
         return [float(buf[i]) for i in range(n.value)]
+
+    def trace_variant(self) -> int:
+        """Which trace kernel the newest launch ran: TRACE_NONE / TRACE_BVH / TRACE_FLAT / TRACE_FLAT_PLAIN."""
+        v = C.c_int(0)
+        self._chk(self.L.ptk_trace_variant(self.h, C.byref(v)), "ptk_trace_variant")
+        return v.value
 
     def set_option(self, name: str, value: float):
         self._chk(self.L.ptk_set_option(self.h, name.encode(), float(value)), "ptk_set_option")
