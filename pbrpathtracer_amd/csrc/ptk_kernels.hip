@@ -1052,7 +1052,13 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
     } while (0)
 
     // a finished walk: shadow rays resolve DirectIllumimation's visibility and roll into the sampled
-    // bounce; bounce rays end the path on a miss or queue for shading
+    // bounce; bounce rays end the path on a miss or queue for shading.
+    // FLAT: a hit whose interaction would be the terminal one (pathtracer.cpp:571, `iter` does not change between
+    // shade_interaction and here) ends the path like a miss: that interaction sets `ended` before any draw, any
+    // emission, any write to L, and the pass has folded the shadow ray into L already.  Parked in SHADE instead,
+    // the lane took a slot of a shade block for nothing, was dealt its next unit after that block and sat out
+    // the whole following pass.  (The STATS kernels keep the parked route: their shade_lanes counts executed
+    // interactions and equals hits_shaded, which includes the terminal one.)
 #define PTK_WALK_DONE()                                                                           \
     do {                                                                                          \
         if (STATS) { cnt.rays++; cnt.max_nodes = max(cnt.max_nodes, cnt.cur_nodes); cnt.cur_nodes = 0; }     \
@@ -1066,7 +1072,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
             W.occl_tri = -1;                                                                      \
             W.begin(W.ro, nextDir, num_nodes_u, stack, scene_bound_u);                                   \
         }                                                                                         \
-        else if (!hit_) PTK_FINISH_PATH();              /* :550 miss -> black */                  \
+        else if (!hit_ || (FLAT && !STATS && !(iter < P.max_depth))) PTK_FINISH_PATH();     /* :550 miss -> black */  \
         else st = ST_SHADE;                                                                       \
     } while (0)
 
@@ -1074,6 +1080,24 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
     for (;;)
     {
         // deal the next work units to the lanes that need one (wave-uniform code)
+        // FLAT: deal lazily.  The kernel runs in lock-step - shade (all lanes), pass (all but the few whose path just ended),
+        // shade ... - and a lane dealt after the shade block only waits in SHADE / GEN for the block after the pass, in front
+        // of which the lanes that missed are dealt anyway.  So the deal is skipped while it cannot change the vote below:
+        // the pass wins even if every NEED lane is counted for its strongest rival.  A dealt lane lands in SHADE, GEN or DONE,
+        // so with the deal the pass would have run with the same lanes; only which lane picks up which unit differs.
+        // Termination: a skipped iteration has n_trav > 0 and runs the pass (weights are >= 1: the skip test implies the vote),
+        // after which no lane of it is in TRAV, so two skips never follow each other and no skip reaches the `break` below
+        // (n_live >= n_trav > 0).  With n_trav == 0 the deal always runs, and it leaves no lane in NEED (each gets a unit
+        // or, when every queue is empty, DONE): n_live == 0 is only ever seen right after such a deal, with nothing undealt.
+        // One-item-per-wave launches and the quota of a multi-GPU share live in acquire_item and see the same calls.
+        bool deal = true;
+        if (FLAT)
+        {
+            const int n_need = __popcll(__ballot(st == ST_NEED)), nt = __popcll(__ballot(st == ST_TRAV));
+            const int ns = __popcll(__ballot(st == ST_SHADE)), ng = PLAIN ? 0 : __popcll(__ballot(st == ST_GEN));
+            deal = nt == 0 || nt * 8 < (ns + n_need) * P.flat_shade_w || (!PLAIN && nt * 8 < (ng + n_need) * P.flat_gen_w);
+        }
+        if (!FLAT || deal)
         {
             unsigned long long m_need = __ballot(st == ST_NEED);
             while (m_need)
