@@ -182,6 +182,15 @@ public:
     bool RenderAdaptive(float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, ptk_adaptive_result* out = nullptr);
     // samples per pixel (W*H, rows bottom-up, 0 = not owned)
     bool ReadSampleCounts(uint32_t* out);
+    // First-hit feature planes (include/ptk.h ptk_render_features: depth, ids, normals, albedo ... of what each pixel's camera ray
+    // sees with the lens closed): computes the planes of `mask` (bit k = PTK_FEAT_k) for sample `sample` of the class's seed.
+    // Pending material / camera / resolution edits apply as for RenderFrame(); the image and the sample count are not touched.
+    bool RenderFeatures(uint32_t mask, uint32_t sample = 0);
+    // one plane of the last RenderFeatures(): W*H*channels elements of 4 bytes (ptk_feature_info), rows bottom-up
+    bool ReadFeature(int feature, void* out);
+    // The (object, element) under pixel (x, y), y counted from the top row: one ray (ptk_pick), pending edits applied first.
+    // A pixel that sees nothing gives -1 / -1 (and triangle -1) and true; false: no scene / resolution yet, or (x, y) outside the frame.
+    bool Pick(int x, int y, int* objId, int* elementId, int* triangle = nullptr);
     // mTotalImg (float RGB, rows bottom-up), W*H*3 floats
     bool ReadAccumulation(float* out);
     // last error text of the device layer ("" when none); the reference API itself stays silent

@@ -222,6 +222,58 @@ int ptk_read_sample_counts(ptk_ctx* ctx, uint32_t* host_out);
 /* S2 of the last adaptive render: W*H*3 sums of squares, rows bottom-up */
 int ptk_read_moments(ptk_ctx* ctx, float* host_out);
 
+/* ---- first-hit feature planes and picking (no counterpart in the reference's tracer; its viewer picks through OpenGL) ---------
+ * What each pixel sees, for denoiser guides, compositing and picking.  For the current scene, camera, frame and tile split and a
+ * caller-given (seed, sample):
+ * The FEATURE RAY of pixel i (top-down index, the kernels' pixel index) is its camera ray with the lens closed, computed exactly as
+ * the camera-ray block does at zero lens offset: ro = cam_pos, rd = normalize((cam_pos + primary[i] * focal_dist) - cam_pos).  The
+ * camera's aperture is ignored.
+ * Its HIT is the closest accepted hit under the product's rule: the minimum over accepted triangles, ties broken by smaller t,
+ * then smaller index; a candidate with an opacity map is tested with the path's own draw, hash(path key of (seed, pixel, sample),
+ * ray 0, triangle).  It is therefore precisely the first hit of sample `sample` of a plain render with aperture 0: deterministic,
+ * independent of the tree and the same under any tile split.
+ * One plane per feature, W*H*channels elements of 4 bytes, rows BOTTOM-UP like the accumulator; a miss gives the value in brackets:
+ *   id name         type   value
+ *    0 DEPTH        f32    t of the hit [+inf]
+ *    1 TRIANGLE     i32    scene triangle index [-1]
+ *    2 MATERIAL     i32    material[tri], the staged element's material index [-1]
+ *    3 BARY         f32x2  u, v of the hit [0]
+ *    4 POSITION     f32x3  ro + rd * t (pathtracer.cpp:553), before the epsilon offset of :569 [0]
+ *    5 NORMAL_GEOM  f32x3  the staged face normal tbn[tri][0:3], not flipped [0]
+ *    6 NORMAL       f32x3  the shading normal of that interaction: smoothed when the triangle's smoothing bit is set, then
+ *                          normal-mapped, then flipped against rd (pathtracer.cpp:556-568) [0]
+ *    7 ALBEDO       f32x3  the material's diffuse colour, or the diffuse texel where a diffuse map is bound (it replaces the colour) [0]
+ *    8 EMISSION     f32x3  (emissive colour, or its texel) * emissive_intensity [0]
+ *    9 GLOSS        f32x2  roughness, reflectiveness after their textures [0]
+ * Every float is the result of the same IEEE operations in the same order as in the exact trace kernel and the CPU oracle
+ * (tests/test_gpu_features.py: array_equal).
+ * ptk_render_features is asynchronous on the context's stream (the caller's after ptk_set_stream) and needs a scene, a camera and
+ * a frame (else PTK_ERR_BAD_ARG).  It applies a pending camera change as a render does and touches neither the accumulator, the
+ * sample count, the 8-bit image, the adaptive state nor a bound hand-off buffer.  Only the planes in `mask` (bit k = feature k)
+ * are computed; planes are allocated on first use.  Under a tile split only owned pixels are written, the others hold the miss
+ * values.  Edits made with ptk_update_materials are seen by the next call.
+ * The planes are a SNAPSHOT: later scene, camera or material edits do not invalidate them.  ptk_read_feature (waits for the
+ * stream) and ptk_feature_device_ptr fail with PTK_ERR_BAD_ARG when the plane was not in the mask of the last
+ * ptk_render_features, when the frame's resolution has changed since, or when `feature` is unknown.
+ * ptk_pick traces the feature ray of ONE pixel (sample 0 of `seed`) and waits for it: the triangle, its material index and t;
+ * a miss gives -1, -1, +inf and PTK_OK; coordinates outside the frame PTK_ERR_BAD_ARG.  Any output pointer may be NULL. */
+#define PTK_FEAT_DEPTH 0
+#define PTK_FEAT_TRIANGLE 1
+#define PTK_FEAT_MATERIAL 2
+#define PTK_FEAT_BARY 3
+#define PTK_FEAT_POSITION 4
+#define PTK_FEAT_NORMAL_GEOM 5
+#define PTK_FEAT_NORMAL 6
+#define PTK_FEAT_ALBEDO 7
+#define PTK_FEAT_EMISSION 8
+#define PTK_FEAT_GLOSS 9
+#define PTK_FEAT_COUNT 10
+int ptk_feature_info(int feature, int* channels, int* is_int);      /* host-only, no device needed */
+int ptk_render_features(ptk_ctx* ctx, uint32_t sample, uint64_t seed, uint32_t mask);
+int ptk_read_feature(ptk_ctx* ctx, int feature, void* host_out);
+int ptk_feature_device_ptr(ptk_ctx* ctx, int feature, void** dev_ptr, size_t* bytes);
+int ptk_pick(ptk_ctx* ctx, int x, int y_top_down, uint64_t seed, int32_t* tri, int32_t* material, float* t);
+
 int ptk_samples(ptk_ctx* ctx);         /* GetSamples (pathtracer.cpp:362-365); thread-safe */
 /* Exit (pathtracer.cpp:819-822); thread-safe.  Cuts EVERY render in flight - ptk_render is asynchronous while no output
  * image is bound, so several may be queued: all of them, not only the newest - : passes whose kernels have not started are

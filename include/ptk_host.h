@@ -54,6 +54,11 @@ int  pth_read_accum(pth_tracer* t, float* out);           /* 1 on success */
 /* RenderAdaptive: 1 on success (the result may be NULL); ReadSampleCounts: W*H counts, rows bottom-up, 1 on success */
 int  pth_render_adaptive(pth_tracer* t, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, ptk_adaptive_result* out);
 int  pth_read_sample_counts(pth_tracer* t, uint32_t* out);
+/* RenderFeatures / ReadFeature / Pick (first-hit feature planes, include/ptk.h): 1 on success; pth_pick: y from the top row,
+ * obj = elem = tri = -1 where the pixel sees nothing (outputs may be NULL) */
+int  pth_render_features(pth_tracer* t, uint32_t mask, uint32_t sample);
+int  pth_read_feature(pth_tracer* t, int feature, void* out);
+int  pth_pick(pth_tracer* t, int x, int y, int* obj, int* elem, int* tri);
 const char* pth_last_error(pth_tracer* t);
 ptk_ctx* pth_context(pth_tracer* t);
 const ptk_scene_desc* pth_staged_scene(pth_tracer* t);    /* flat arrays of the staged scene (host only) */

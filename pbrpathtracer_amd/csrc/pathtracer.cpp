@@ -752,6 +752,55 @@ bool PathTracer::ReadSampleCounts(uint32_t* out)
     return rc == PTK_OK;
 }
 
+// First-hit feature planes (ptk_render_features) of the scene as the next RenderFrame() would see it
+bool PathTracer::RenderFeatures(uint32_t mask, uint32_t sample)
+{
+    if (!m->scene_uploaded || !m->have_resolution || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    GLubyte* out_img; unsigned out_gl; void* out_dev;
+    if (!prepare_render(m, out_img, out_gl, out_dev)) return false;
+    const int rc = ptk_render_features(m->ctx, sample, m->seed, mask);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ReadFeature(int feature, void* out)
+{
+    if (!m->ctx || !out) return false;
+    const int rc = ptk_read_feature(m->ctx, feature, out);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::Pick(int x, int y, int* objId, int* elementId, int* triangle)
+{
+    if (objId) *objId = -1;
+    if (elementId) *elementId = -1;
+    if (triangle) *triangle = -1;
+    if (!m->scene_uploaded || !m->have_resolution || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    GLubyte* out_img; unsigned out_gl; void* out_dev;
+    if (!prepare_render(m, out_img, out_gl, out_dev)) return false;
+    int32_t tri = -1, mat = -1;
+    const int rc = ptk_pick(m->ctx, x, y, m->seed, &tri, &mat, nullptr);
+    m->note(rc);
+    if (rc != PTK_OK) return false;
+    if (triangle) *triangle = tri;
+    // flatten_scene numbers the materials object by object, element by element
+    for (size_t o = 0; mat >= 0 && o < m->objects.size(); o++)
+    {
+        const int ne = (int)m->objects[o].elements.size();
+        if (mat < ne)
+        {
+            if (objId) *objId = (int)o;
+            if (elementId) *elementId = mat;
+            break;
+        }
+        mat -= ne;
+    }
+    return true;
+}
+
 void PathTracer::Exit() { if (m->ctx) ptk_request_exit(m->ctx); }      // :819-822
 
 // ---- extensions -----------------------------------------------------------------------------------------

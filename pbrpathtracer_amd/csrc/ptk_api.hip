@@ -24,6 +24,7 @@
 #include "bvh_device.h"
 #include "ptk_device.h"
 #include "ptk_adaptive.h"
+#include "ptk_features.h"
 
 using namespace ptk;
 
@@ -117,6 +118,11 @@ struct ptk_ctx {
     unsigned* h_adapt_count = nullptr;           // page-locked [2]: the active count of rounds r and r + 1, read one round behind
     hipEvent_t ev_adapt[2] = { nullptr, nullptr };
     bool adaptive_accum = false;                 // the accumulator holds an adaptive render: per-pixel counts, no single sample count
+
+    // first-hit feature planes (ptk_render_features): allocated on first use, each for the frame feat_w x feat_h
+    void* d_feat[NUM_FEATURES] = {};
+    int feat_w = 0, feat_h = 0;                  // the frame the planes were allocated for and last rendered at
+    uint32_t feat_mask = 0;                      // planes the last ptk_render_features wrote
 
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
@@ -358,6 +364,28 @@ struct GlMapping
     ptk_ctx* c; bool mapped = false;
     ~GlMapping() { if (mapped) { (void)hipGraphicsUnmapResources(1, &c->gl_res, c->stream); (void)hipGetLastError(); } }
 };
+
+// channels and element type of the feature planes (ptk.h PTK_FEAT_*)
+const int kFeatChannels[NUM_FEATURES] = { 1, 1, 1, 2, 3, 3, 3, 3, 3, 2 };
+const int kFeatIsInt[NUM_FEATURES] = { 0, 1, 1, 0, 0, 0, 0, 0, 0, 0 };
+
+void free_features(ptk_ctx* c)
+{
+    for (int k = 0; k < NUM_FEATURES; k++) dfree(c->d_feat[k]);
+    c->feat_w = c->feat_h = 0; c->feat_mask = 0;
+}
+
+// the plane `feature` of the last ptk_render_features, or null with the reason in the context's error text
+void* feature_plane(ptk_ctx* c, int feature, size_t* bytes)
+{
+    if (feature < 0 || feature >= NUM_FEATURES) { fail(c, PTK_ERR_BAD_ARG, "unknown feature id"); return nullptr; }
+    if (c->feat_w != c->width || c->feat_h != c->height || c->feat_w == 0)
+    { fail(c, PTK_ERR_BAD_ARG, "no feature planes for the current resolution: ptk_render_features first"); return nullptr; }
+    if (!((c->feat_mask >> feature) & 1u) || !c->d_feat[feature])
+    { fail(c, PTK_ERR_BAD_ARG, "this feature was not in the mask of the last ptk_render_features"); return nullptr; }
+    *bytes = (size_t)c->feat_w * c->feat_h * kFeatChannels[feature] * 4;
+    return c->d_feat[feature];
+}
 
 void free_adaptive(ptk_ctx* c)
 {
@@ -698,6 +726,7 @@ void ptk_destroy(ptk_ctx* c)
     dfree(c->d_exit); dfree(c->d_stats); dfree(c->d_queues); dfree(c->d_samples);
     dfree(c->d_live_mask); dfree(c->d_live_list);
     free_adaptive(c);
+    free_features(c);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
     if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);
@@ -1059,6 +1088,7 @@ int ptk_set_frame(ptk_ctx* c, int width, int height, int max_depth)
         HIPCHK(c, hipMalloc(&c->d_accum, px * 3 * sizeof(float)));
         HIPCHK(c, hipMalloc(&c->d_rgb8, px * 3));
         free_adaptive(c);
+        free_features(c);
         c->width = width; c->height = height;
         c->d_accum_bound = nullptr;
         unbind_out_image(c, true);               // another resolution: the caller's buffer has another size (main.cpp:3425-3446)
@@ -1248,6 +1278,118 @@ int ptk_render_adaptive(ptk_ctx* c, float threshold, uint32_t min_spp, uint32_t 
         out->rounds = rounds; out->max_count = (uint32_t)st[1];
         out->pixel_samples = st[0]; out->active_pixels = active;
     }
+    return PTK_OK;
+}
+
+// ---- first-hit feature planes (ptk.h) ------------------------------------------------------------------------------------
+int ptk_feature_info(int feature, int* channels, int* is_int)
+{
+    if (feature < 0 || feature >= NUM_FEATURES) return PTK_ERR_BAD_ARG;
+    if (channels) *channels = kFeatChannels[feature];
+    if (is_int) *is_int = kFeatIsInt[feature];
+    return PTK_OK;
+}
+
+int ptk_render_features(ptk_ctx* c, uint32_t sample, uint64_t seed, uint32_t mask)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (!c->d_primary) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
+    if (mask >> NUM_FEATURES) return fail(c, PTK_ERR_BAD_ARG, "unknown feature bit in the mask");
+    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensure_primary(c);
+    if (rc != PTK_OK) return rc;
+    RenderParams p;
+    fill_params(c, p, sample, 1, seed);
+    // the cache is brought up to date exactly as a render does it (run_passes), and taken in place of the walk where it is valid
+    if (primary_cacheable(c))
+    {
+        if (c->primary_hit_dirty)
+        {
+            launch_primary_hits(p, c->d_primary_hit, c->d_primary_rd, c->stream);
+            HIPCHK(c, hipGetLastError());
+            c->primary_hit_dirty = false;
+            c->hit_generation++;
+            c->out_full_next = true;
+            c->inputs_dirty = true;
+        }
+        p.primary_hit = c->d_primary_hit; p.primary_rd = c->d_primary_rd;
+    }
+    const size_t px = (size_t)c->width * c->height;
+    c->feat_mask = 0;
+    for (int k = 0; k < NUM_FEATURES; k++)
+        if (((mask >> k) & 1u) && !c->d_feat[k]) HIPCHK(c, hipMalloc(&c->d_feat[k], px * kFeatChannels[k] * 4));
+    c->feat_w = c->width; c->feat_h = c->height;
+    FeatureParams f = {};
+    void** slot[NUM_FEATURES] = { (void**)&f.depth, (void**)&f.triangle, (void**)&f.material, (void**)&f.bary, (void**)&f.position,
+                                  (void**)&f.normal_geom, (void**)&f.normal, (void**)&f.albedo, (void**)&f.emission, (void**)&f.gloss };
+    for (int k = 0; k < NUM_FEATURES; k++)
+    {
+        if (!((mask >> k) & 1u)) continue;
+        *slot[k] = c->d_feat[k];
+        // a tile split writes the owned pixels only: the others hold the miss values (+inf, -1, 0)
+        if (c->world > 1)
+            HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_feat[k], k == 0 ? 0x7f800000 : (kFeatIsInt[k] ? -1 : 0), px * kFeatChannels[k], c->stream));
+    }
+    f.sample = sample; f.seed_lo = (uint32_t)seed; f.seed_hi = (uint32_t)(seed >> 32);
+    if (mask) launch_features(p, f, owned_tiles(p), c->stream);
+    HIPCHK(c, hipGetLastError());
+    c->feat_mask = mask;
+    return PTK_OK;
+}
+
+int ptk_read_feature(ptk_ctx* c, int feature, void* host_out)
+{
+    if (!c || !host_out) return PTK_ERR_BAD_ARG;
+    size_t bytes = 0;
+    void* d = feature_plane(c, feature, &bytes);
+    if (!d) return PTK_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(host_out, d, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PTK_OK;
+}
+
+int ptk_feature_device_ptr(ptk_ctx* c, int feature, void** dev_ptr, size_t* bytes)
+{
+    if (!c || !dev_ptr) return PTK_ERR_BAD_ARG;
+    size_t b = 0;
+    void* d = feature_plane(c, feature, &b);
+    if (!d) return PTK_ERR_BAD_ARG;
+    *dev_ptr = d;
+    if (bytes) *bytes = b;
+    return PTK_OK;
+}
+
+int ptk_pick(ptk_ctx* c, int x, int y_top_down, uint64_t seed, int32_t* tri, int32_t* material, float* t)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (!c->d_primary) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
+    if (x < 0 || y_top_down < 0 || x >= c->width || y_top_down >= c->height) return fail(c, PTK_ERR_BAD_ARG, "ptk_pick: pixel outside the frame");
+    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensure_primary(c);
+    if (rc != PTK_OK) return rc;
+    // one ray: [0] the triangle, [1] its material index, [2] the bits of t
+    int32_t* d_out = nullptr;
+    HIPCHK(c, hipMalloc(&d_out, 3 * sizeof(int32_t)));
+    RenderParams p;
+    fill_params(c, p, 0, 1, seed);
+    FeatureParams f = {};
+    f.sample = 0; f.seed_lo = (uint32_t)seed; f.seed_hi = (uint32_t)(seed >> 32);
+    launch_pick(p, f, y_top_down * c->width + x, d_out, c->stream);
+    int32_t out[3] = { -1, -1, 0 };
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(c, PTK_ERR_HIP, hipGetErrorString(e));
+    float th; std::memcpy(&th, &out[2], 4);
+    if (tri) *tri = out[0];
+    if (material) *material = out[1];
+    if (t) *t = th;
     return PTK_OK;
 }
 

@@ -1,0 +1,189 @@
+// HIP kernels for gfx950 of the first-hit feature planes and of picking (include/ptk.h ptk_render_features, ptk_pick).
+// They are built from the trace kernels' own device functions - the exact normalize, tex2d, Walk, tri_test, walk_step, the RNG
+// keys - which live in ptk_kernels.hip, not in a header.  That file stays byte for byte as it is (the committed counter files are
+// tied to its hash, and its kernels keep their machine code): this translation unit includes it in the form that holds the shared
+// device functions and the trace kernels only (PTK_CONTRACT 1: the sections of the exact build are left out) under a namespace of
+// its own, and is compiled with -ffp-contract=off like the exact build.  At PTK_CONTRACT 1 the arithmetic helpers are the exact
+// ones (only level 2 swaps in the hardware's reciprocal and root), so every operation below is the IEEE operation of the exact
+// trace kernel.  The price is a private copy of the trace kernels in this object, which nothing launches.
+#include "ptk_features.h"
+
+#define PTK_CONTRACT 1
+#define fma features_tu          // the namespace ptk_kernels.hip opens at PTK_CONTRACT 1; ptk::fma itself belongs to the contracted build
+#include "ptk_kernels.hip"
+#undef fma
+
+namespace ptk {
+namespace features_tu {
+
+// the feature ray of pixel `pix` (top-down index): the camera-ray block at zero lens offset
+template <class PT>
+__device__ __forceinline__ v3 feature_ray(const PT& P, v3 ro, size_t pix)
+{
+    const float4 d = P.primary[pix];
+    return normalize(sub(add(ro, muls(V(d.x, d.y, d.z), P.focal_dist)), ro));
+}
+
+// ... and its closest accepted hit: a walk whose opacity draws are keyed as the trace kernel keys ray 0 of (seed, pixel, sample)
+template <class PT>
+__device__ __forceinline__ Hit feature_walk(const PT& P, const FeatureParams& F, v3 ro, v3 rd, size_t pix, int* stack)
+{
+    Rng rng; rng.inc = 1u; rng.state = 0u;                                 // (no draws from the stream: only the key counts)
+    rng.key = hash32(F.sample + pixel_key(F.seed_lo, F.seed_hi, (uint32_t)pix));
+    Counters cnt = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    Walk W;
+    W.occl_tri = -1;
+    W.begin(ro, rd, P.num_nodes, stack, P.scene_bound);
+    while (!W.done()) walk_step<false, PTK_BLOCK>(P, W, rng, 0u, stack, cnt);
+    return W.best;
+}
+
+// First-hit feature planes (include/ptk.h ptk_render_features): per owned pixel the closest accepted hit of its camera ray with the
+// lens closed, and the surface quantities shade_interaction computes at that interaction - the same IEEE operations in the same
+// order, on the records of the accepted hit only.  One workgroup per owned 16x16 tile, one wave per 8x8 quadrant
+// (accumulate_kernel's pixel mapping: a wave's 64 rays are one coherent bundle).  The hit comes from the primary-hit cache where
+// that is valid (the same walk of the same ray, done once), otherwise from a walk whose opacity draws are keyed as the trace
+// kernel keys ray 0 of (seed, pixel, sample).  Only planes with a non-null pointer are computed and stored (kernel arguments:
+// uniform branches); a pixel's element is 4, 8 or 12 bytes, stored by its own lane.
+__global__ __launch_bounds__(PTK_BLOCK) void features_kernel(const RenderParams P, const FeatureParams F)
+{
+    __shared__ int lds_stack[PTK_STACK_ROWS * PTK_BLOCK];
+    const int tid = threadIdx.x, lane = tid & 63, quad = tid >> 6;
+    const int tile = blockIdx.x * P.world + P.rank;
+    if (tile >= P.num_tiles) return;
+    const int ty = tile / P.tiles_x, tx = (tile % P.tiles_x + P.tiles_x - (3 * ty) % P.tiles_x) % P.tiles_x;
+    const int px = tx * PTK_TILE + (quad & 1) * 8 + (lane & 7);
+    const int py = ty * PTK_TILE + (quad >> 1) * 8 + (lane >> 3);
+    if (px >= P.width || py >= P.height) return;
+    const size_t pix = (size_t)py * P.width + px;                          // top-down: primary, primary_hit, the RNG's pixel
+    const size_t o = (size_t)(P.height - 1 - py) * P.width + px;           // bottom-up, like the accumulator
+    const v3 ro = V(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]);
+    v3 rd;
+    Hit h;
+    if (P.primary_hit)
+    {
+        const float4 c = P.primary_hit[pix], r = P.primary_rd[pix];
+        rd = V(r.x, r.y, r.z);
+        h.tri = __float_as_int(c.x); h.t = c.y; h.u = c.z; h.v = c.w;
+    }
+    else
+    {
+        rd = feature_ray(P, ro, pix);
+        h = feature_walk(P, F, ro, rd, pix, lds_stack + tid);
+    }
+    const bool hit = h.tri != PTK_NOHIT;
+    if (F.depth) F.depth[o] = hit ? h.t : __builtin_inff();
+    if (F.triangle) F.triangle[o] = hit ? h.tri : -1;
+    if (F.bary) *(float2*)(F.bary + o * 2) = hit ? make_float2(h.u, h.v) : make_float2(0.0f, 0.0f);
+    if (F.position)
+    {
+        const v3 p = hit ? add(ro, muls(rd, h.t)) : V(0.0f, 0.0f, 0.0f);   // :553, before the offset of :569
+        F.position[o * 3] = p.x; F.position[o * 3 + 1] = p.y; F.position[o * 3 + 2] = p.z;
+    }
+    if (!(F.material || F.normal_geom || F.normal || F.albedo || F.emission || F.gloss)) return;
+    int matid = -1;
+    v3 ng = V(0.0f, 0.0f, 0.0f), n = ng, albedo = ng, emission = ng;
+    float roughness = 0.0f, reflectiveness = 0.0f;
+    if (hit)
+    {
+        const float4* sp4 = P.shade + (size_t)h.tri * SHADE_F4;
+        const float4 s0 = ldg4(sp4);
+        const int mbits = __float_as_int(s0.w);
+        matid = mbits & 0x7fffffff;
+        ng = V(s0.x, s0.y, s0.z);
+        if (F.normal || F.albedo || F.emission || F.gloss)
+        {
+            const float4* mp = P.mats + (size_t)matid * MAT_F4;
+            const float4 m4f = ldg4(mp + 4), m5f = ldg4(mp + 5);
+            const int tex_diffuse = __float_as_int(m4f.x), tex_normal = __float_as_int(m4f.y);
+            const int tex_emiss = __float_as_int(m4f.z), tex_rough = __float_as_int(m4f.w);
+            const int tex_metal = __float_as_int(m5f.x);
+            float uvx = 0.0f, uvy = 0.0f;
+            if (__float_as_int(m5f.z) != 0)             // some map is bound
+            {
+                const float4 s1 = ldg4(sp4 + 1), s2 = ldg4(sp4 + 2);
+                const float w = 1.0f - h.u - h.v;       // GetUV :533-536
+                uvx = w * s1.x + h.u * s1.z + h.v * s2.x;
+                uvy = w * s1.y + h.u * s1.w + h.v * s2.y;
+            }
+            if (F.normal)
+            {
+                n = ng;
+                if (mbits < 0)                          // :556, GetSmoothNormal :538-543
+                {
+                    const float4 s2 = ldg4(sp4 + 2), s3 = ldg4(sp4 + 3), s4 = ldg4(sp4 + 4);
+                    const float w = 1.0f - h.u - h.v;
+                    const v3 n1 = V(s2.z, s2.w, s3.x), n2 = V(s3.y, s3.z, s3.w), n3 = V(s4.x, s4.y, s4.z);
+                    n = normalize(add(add(muls(n1, w), muls(n2, h.u)), muls(n3, h.v)));
+                }
+                if (tex_normal >= 0)                    // :558-566
+                {
+                    const float4 s4 = ldg4(sp4 + 4), s5 = ldg4(sp4 + 5), s6 = ldg4(sp4 + 6);
+                    const float4 c = tex2d(P, tex_normal, uvx, uvy);
+                    v3 nt = V(c.x * 2.0f - 1.0f, c.y * 2.0f - 1.0f, c.z * 2.0f - 1.0f);
+                    if (nt.z <= 0.0f) nt = V(nt.x, nt.y, PTK_EPS);
+                    nt = normalize(nt);
+                    const v3 tg = V(s4.w, s5.x, s5.y), bt = V(s5.z, s5.w, s6.x);
+                    const v3 m = V(tg.x * nt.x + bt.x * nt.y + n.x * nt.z,
+                                   tg.y * nt.x + bt.y * nt.y + n.y * nt.z,
+                                   tg.z * nt.x + bt.z * nt.y + n.z * nt.z);
+                    n = normalize(m);
+                }
+                if (dot(n, rd) > 0.0f) n = neg(n);      // :567-568
+            }
+            if (F.albedo)
+            {
+                const float4 m0 = ldg4(mp);
+                albedo = V(m0.x, m0.y, m0.z);
+                if (tex_diffuse >= 0) { const float4 c = tex2d(P, tex_diffuse, uvx, uvy); albedo = V(c.x, c.y, c.z); }
+            }
+            if (F.emission)
+            {
+                const float4 m1 = ldg4(mp + 1), m2 = ldg4(mp + 2);
+                v3 emiss = V(m2.x, m2.y, m2.z);
+                if (tex_emiss >= 0) { const float4 c = tex2d(P, tex_emiss, uvx, uvy); emiss = V(c.x, c.y, c.z); }
+                emission = muls(emiss, m1.w);
+            }
+            if (F.gloss)
+            {
+                roughness = ldg4(mp + 2).w;
+                if (tex_rough >= 0) roughness = tex2d_r(P, tex_rough, uvx, uvy);
+                reflectiveness = ldg4(mp + 3).x;
+                if (tex_metal >= 0) reflectiveness = tex2d_r(P, tex_metal, uvx, uvy);
+            }
+        }
+    }
+    if (F.material) F.material[o] = matid;
+    if (F.normal_geom) { F.normal_geom[o * 3] = ng.x; F.normal_geom[o * 3 + 1] = ng.y; F.normal_geom[o * 3 + 2] = ng.z; }
+    if (F.normal) { F.normal[o * 3] = n.x; F.normal[o * 3 + 1] = n.y; F.normal[o * 3 + 2] = n.z; }
+    if (F.albedo) { F.albedo[o * 3] = albedo.x; F.albedo[o * 3 + 1] = albedo.y; F.albedo[o * 3 + 2] = albedo.z; }
+    if (F.emission) { F.emission[o * 3] = emission.x; F.emission[o * 3 + 1] = emission.y; F.emission[o * 3 + 2] = emission.z; }
+    if (F.gloss) *(float2*)(F.gloss + o * 2) = make_float2(roughness, reflectiveness);
+}
+
+// ptk_pick: the feature ray of ONE pixel - one lane of one workgroup (the stack layout is that of a whole workgroup)
+__global__ __launch_bounds__(PTK_BLOCK) void pick_kernel(const RenderParams P, const FeatureParams F, int pixel, int32_t* out3)
+{
+    __shared__ int lds_stack[PTK_STACK_ROWS * PTK_BLOCK];
+    if (threadIdx.x != 0) return;
+    const v3 ro = V(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]);
+    const v3 rd = feature_ray(P, ro, (size_t)pixel);
+    const Hit h = feature_walk(P, F, ro, rd, (size_t)pixel, lds_stack);
+    const bool hit = h.tri != PTK_NOHIT;
+    out3[0] = hit ? h.tri : -1;
+    out3[1] = hit ? (__float_as_int(ldg4(P.shade + (size_t)h.tri * SHADE_F4).w) & 0x7fffffff) : -1;
+    out3[2] = __float_as_int(hit ? h.t : __builtin_inff());
+}
+
+}  // namespace features_tu
+
+void launch_features(const RenderParams& p, const FeatureParams& f, int owned_tiles, hipStream_t stream)
+{
+    if (owned_tiles > 0) hipLaunchKernelGGL(features_tu::features_kernel, dim3(owned_tiles), dim3(PTK_BLOCK), 0, stream, p, f);
+}
+void launch_pick(const RenderParams& p, const FeatureParams& f, int pixel, int32_t* out3, hipStream_t stream)
+{
+    hipLaunchKernelGGL(features_tu::pick_kernel, dim3(1), dim3(PTK_BLOCK), 0, stream, p, f, pixel, out3);
+}
+
+}  // namespace ptk

@@ -104,6 +104,9 @@ int pth_render_adaptive(pth_tracer* t, float threshold, uint32_t min_spp, uint32
     return t->pt.RenderAdaptive(threshold, min_spp, step, max_spp, out) ? 1 : 0;
 }
 int pth_read_sample_counts(pth_tracer* t, uint32_t* out) { return t->pt.ReadSampleCounts(out) ? 1 : 0; }
+int pth_render_features(pth_tracer* t, uint32_t mask, uint32_t sample) { return t->pt.RenderFeatures(mask, sample) ? 1 : 0; }
+int pth_read_feature(pth_tracer* t, int feature, void* out) { return t->pt.ReadFeature(feature, out) ? 1 : 0; }
+int pth_pick(pth_tracer* t, int x, int y, int* obj, int* elem, int* tri) { return t->pt.Pick(x, y, obj, elem, tri) ? 1 : 0; }
 const char* pth_last_error(pth_tracer* t)
 {
     std::string e = t->pt.LastError();

@@ -35,6 +35,7 @@ HOST_SYMBOLS = [
     "pth_last_error", "pth_context", "pth_staged_scene", "pth_load_scene_file", "pth_pts_roundtrip",
     "pth_trs_matrix", "pth_euler_camera", "pth_triangle_init", "pth_image_load", "pth_image_data", "pth_image_tex2d",
     "pth_export_png", "pth_render_adaptive", "pth_read_sample_counts",
+    "pth_render_features", "pth_read_feature", "pth_pick",
 ]
 
 _bound = False
@@ -82,6 +83,9 @@ def _bind_locked(L) -> C.CDLL:
     L.pth_render_adaptive.restype = i32
     L.pth_render_adaptive.argtypes = [vp, f32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_ptk.AdaptiveResult)]
     L.pth_read_sample_counts.restype = i32; L.pth_read_sample_counts.argtypes = [vp, vp]
+    L.pth_render_features.restype = i32; L.pth_render_features.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.pth_read_feature.restype = i32; L.pth_read_feature.argtypes = [vp, i32, vp]
+    L.pth_pick.restype = i32; L.pth_pick.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.pth_last_error.restype = C.c_char_p; L.pth_last_error.argtypes = [vp]
     L.pth_context.restype = vp; L.pth_context.argtypes = [vp]
     L.pth_staged_scene.restype = C.POINTER(_ptk.SceneDesc); L.pth_staged_scene.argtypes = [vp]
@@ -245,6 +249,27 @@ class PathTracer:
         if not self.L.pth_read_sample_counts(self.h, out.ctypes.data):
             raise _ptk.PtkError("ReadSampleCounts failed: " + self.LastError())
         return out
+
+    def RenderFeatures(self, mask: int, sample: int = 0):
+        """First-hit feature planes (include/ptk.h ptk_render_features) of the planes in `mask` (bit k = ptk.FEAT_*), for sample
+        `sample` of this tracer's seed; pending edits apply as for RenderFrame(), the image is not touched."""
+        if not self.L.pth_render_features(self.h, int(mask), int(sample)):
+            raise _ptk.PtkError("RenderFeatures failed: " + self.LastError())
+
+    def ReadFeature(self, feature: int) -> np.ndarray:
+        """One plane of the last RenderFeatures(): [H, W] or [H, W, c], float32 or int32, rows bottom-up."""
+        w, h = self.GetResolution()
+        out = _ptk.feature_array(feature, w, h)
+        if not self.L.pth_read_feature(self.h, int(feature), out.ctypes.data):
+            raise _ptk.PtkError("ReadFeature failed: " + self.LastError())
+        return out
+
+    def Pick(self, x: int, y: int):
+        """(object, element, triangle) under pixel (x, y), y from the top row; (-1, -1, -1) where the pixel sees nothing."""
+        o, e, t = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        if not self.L.pth_pick(self.h, int(x), int(y), C.byref(o), C.byref(e), C.byref(t)):
+            raise _ptk.PtkError("Pick failed: " + self.LastError())
+        return o.value, e.value, t.value
 
     def ReadAccumulation(self) -> np.ndarray:
         w, h = self.GetResolution()

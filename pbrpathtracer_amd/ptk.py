@@ -80,6 +80,7 @@ SYMBOLS = [
     "ptk_bind_out_image", "ptk_bind_out_device", "ptk_bind_gl_buffer", "ptk_comm_info", "ptk_kernel_log", "ptk_kernel_log_read",
     "ptk_debug_stall_exchange", "ptk_render_adaptive", "ptk_read_sample_counts", "ptk_read_moments",
     "ptk_trace_variant", "ptk_scene_is_plain",
+    "ptk_feature_info", "ptk_render_features", "ptk_read_feature", "ptk_feature_device_ptr", "ptk_pick",
 ]
 
 
@@ -158,6 +159,11 @@ def _load_locked() -> C.CDLL:
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
+    L.ptk_feature_info.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
+    L.ptk_render_features.argtypes = [vp, u32, u64, u32]
+    L.ptk_read_feature.argtypes = [vp, i32, vp]
+    L.ptk_feature_device_ptr.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ptk_pick.argtypes = [vp, i32, i32, u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
     L.ptk_bvh_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.ptk_bvh_layout.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.ptk_download_bvh.argtypes = [vp, vp, vp]
@@ -171,6 +177,27 @@ def _load_locked() -> C.CDLL:
 
 
 TRACE_NONE, TRACE_BVH, TRACE_FLAT, TRACE_FLAT_PLAIN = 0, 1, 2, 3      # ptk_trace_variant
+
+
+# first-hit feature planes (ptk_render_features): ids, and their names in id order
+(FEAT_DEPTH, FEAT_TRIANGLE, FEAT_MATERIAL, FEAT_BARY, FEAT_POSITION, FEAT_NORMAL_GEOM, FEAT_NORMAL, FEAT_ALBEDO, FEAT_EMISSION,
+ FEAT_GLOSS) = range(10)
+FEAT_NAMES = ("depth", "triangle", "material", "bary", "position", "normal_geom", "normal", "albedo", "emission", "gloss")
+FEAT_ALL = (1 << len(FEAT_NAMES)) - 1
+
+
+def feature_info(feature: int):
+    """(channels, is_int) of a feature plane (ptk_feature_info; no device needed); raises for an unknown id."""
+    ch = C.c_int(0); isint = C.c_int(0)
+    if load().ptk_feature_info(int(feature), C.byref(ch), C.byref(isint)) != PTK_OK:
+        raise PtkError(f"ptk_feature_info: unknown feature {feature}")
+    return ch.value, bool(isint.value)
+
+
+def feature_array(feature: int, width: int, height: int) -> np.ndarray:
+    """An empty host array of a feature plane's shape and type: [H, W] or [H, W, c], float32 or int32."""
+    ch, isint = feature_info(feature)
+    return np.empty((height, width) if ch == 1 else (height, width, ch), np.int32 if isint else np.float32)
 
 
 def scene_is_plain(arrays: dict) -> bool:
@@ -272,6 +299,27 @@ class Context:
         self._chk(self.L.ptk_render_adaptive(self.h, float(threshold), int(min_spp), int(step), int(max_spp), int(seed),
                                              C.byref(r)), "ptk_render_adaptive")
         return r.as_dict()
+
+    def render_features(self, mask: int, sample: int = 0, seed: int = 0):
+        """ptk_render_features: the first-hit planes of `mask` (bit k = FEAT_*) for sample `sample` of `seed`; asynchronous."""
+        self._chk(self.L.ptk_render_features(self.h, int(sample), int(seed), int(mask)), "ptk_render_features")
+
+    def read_feature(self, feature: int) -> np.ndarray:
+        """One plane of the last render_features: [H, W] or [H, W, c], float32 or int32, rows bottom-up like read_accum."""
+        out = feature_array(feature, self.width, self.height)
+        self._chk(self.L.ptk_read_feature(self.h, int(feature), out.ctypes.data), "ptk_read_feature")
+        return out
+
+    def feature_device_ptr(self, feature: int):
+        p = C.c_void_p(); b = C.c_size_t()
+        self._chk(self.L.ptk_feature_device_ptr(self.h, int(feature), C.byref(p), C.byref(b)), "ptk_feature_device_ptr")
+        return p.value, b.value
+
+    def pick(self, x: int, y: int, seed: int = 0):
+        """ptk_pick: (triangle, material, t) of what pixel (x, y) sees, y from the top row; (-1, -1, inf) for nothing."""
+        tri = C.c_int32(-1); mat = C.c_int32(-1); t = C.c_float(0)
+        self._chk(self.L.ptk_pick(self.h, int(x), int(y), int(seed), C.byref(tri), C.byref(mat), C.byref(t)), "ptk_pick")
+        return tri.value, mat.value, t.value
 
     def read_sample_counts(self) -> np.ndarray:
         """[H][W] uint32 samples per pixel, rows bottom-up like read_accum; 0 = not owned."""

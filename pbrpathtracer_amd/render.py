@@ -2,6 +2,7 @@
 
     python -m pbrpathtracer_amd.render scene.pts --spp 256 --out image.png [--seed S] [--device D]
     python -m pbrpathtracer_amd.render scene.pts --noise-threshold 0.02 [--min-spp 16] [--step 8] --spp 1024
+    python -m pbrpathtracer_amd.render scene.pts --features planes.npz
 
 With --noise-threshold the render is adaptive (include/ptk.h ptk_render_adaptive): --spp becomes the most samples a pixel
 gets, and pixels stop once their noise meets the threshold.
@@ -29,6 +30,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="adaptive render: relative noise target per pixel (--spp is then the maximum)")
     ap.add_argument("--min-spp", type=int, default=None, help="adaptive: samples before the first test (default: 2 x step)")
     ap.add_argument("--step", type=int, default=8, help="adaptive: samples per round (default 8)")
+    ap.add_argument("--features", metavar="FILE.npz", default=None,
+                    help="also write the first-hit feature planes (depth, triangle, material, bary, position, normal_geom, normal, "
+                         "albedo, emission, gloss; sample 0) to this .npz, rows top-down like the PNG")
     return ap
 
 
@@ -60,6 +64,10 @@ def main(argv=None):
         print("error:", pt.LastError(), file=sys.stderr)
         return 1
     export_png(a.out, out)
+    if a.features:
+        from . import ptk
+        pt.RenderFeatures(ptk.FEAT_ALL)
+        np.savez(a.features, **{name: pt.ReadFeature(k)[::-1].copy() for k, name in enumerate(ptk.FEAT_NAMES)})
     done = res["pixel_samples"] if res is not None else w * h * a.spp
     print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {w}x{h}, {a.spp} spp: load {t1 - t0:.2f} s, "
           f"render {t2 - t1:.3f} s ({done / (t2 - t1) / 1e6:.0f} Msamples/s) -> {a.out}")
