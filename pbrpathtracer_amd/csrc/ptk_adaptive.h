@@ -1,4 +1,5 @@
-// Adaptive render (include/ptk.h ptk_render_adaptive): parameter blocks and launchers of the kernels in ptk_adaptive.hip.
+// Adaptive render (include/ptk.h ptk_render_adaptive): parameter blocks and launchers of the kernels in ptk_adaptive.hip, and of
+// the list compaction it shares with the plain render (ptk_frame.hip).
 // The trace kernels are unchanged: they are fed the round's traced mask and list in RenderParams::live_mask / live_list.
 #pragma once
 
@@ -31,7 +32,7 @@ struct ConvergeParams {
 
 void launch_accumulate_adaptive(const RenderParams& p, const AdaptiveParams& a, int owned_tiles, hipStream_t stream);
 void launch_converge(const RenderParams& p, const ConvergeParams& cp, int owned_tiles, hipStream_t stream);
-// ordered list of the quadrants whose mask is not zero, and their number (live_compact_kernel's contract)
-void launch_mask_compact(const unsigned long long* mask, int num_subtiles, unsigned* list, unsigned* count, hipStream_t stream);
+// ordered list of the quadrants whose mask is not zero, and their number: launch_live_list's second half (live_compact_kernel)
+void launch_compact_list(const unsigned long long* mask, int num_subtiles, unsigned* list, unsigned* count, hipStream_t stream);
 
 }  // namespace ptk

@@ -1,22 +1,20 @@
 // HIP kernels for gfx950 of the adaptive render (include/ptk.h ptk_render_adaptive): rounds of `step` samples, after each of
 // which converge_kernel decides which pixels need more.  The trace kernels of ptk_kernels.hip run unchanged, fed the round's
-// traced mask and list; this file holds what differs from a plain render:
-//   * accumulate_adaptive_kernel - accumulate_kernel (ptk_kernels.hip) for the round's active set: S1 and S2 folded in sample
-//     order, a per-pixel sample count, the 8-bit resolve by that count;
+// traced mask and list (the list by launch_compact_list, ptk_frame.hip); this file holds what differs from a plain render:
+//   * accumulate_adaptive_kernel - accumulate_kernel (ptk_frame.hip) for the round's active set: S1 and S2 folded in sample
+//     order, a per-pixel sample count, the 8-bit resolve by that count (the pixel mapping and the resolve are the shared ones of
+//     ptk_device_fn.h);
 //   * converge_kernel - the test, the 3x3 dilation within the 16x16 tile, the next round's active and traced masks and the
-//     active count that tells the host when to stop;
-//   * mask_compact_kernel - the ordered list of quadrants of the traced mask (live_compact_kernel's contract).
-// Separate from ptk_kernels.hip so that the plain render's kernels stay exactly as they are.  Compiled with -ffp-contract=off
-// like the exact build: S2 = S2 + v * v is a multiply and an add, and the test is float32 in the documented order - the
-// tests recompute both in numpy.
+//     active count that tells the host when to stop.
+// Compiled with -ffp-contract=off like the exact build: S2 = S2 + v * v is a multiply and an add, and the test is float32 in
+// the documented order - the tests recompute both in numpy.
+#include "ptk_device_fn.h"
 #include "ptk_adaptive.h"
 
 namespace ptk {
 
-#define PTK_ABLOCK 256
-
 // One workgroup per owned 16x16 tile, one wave per 8x8 quadrant, one thread per pixel (accumulate_kernel's layout).
-__global__ __launch_bounds__(PTK_ABLOCK) void accumulate_adaptive_kernel(const RenderParams P, const AdaptiveParams A)
+__global__ __launch_bounds__(PTK_BLOCK) void accumulate_adaptive_kernel(const RenderParams P, const AdaptiveParams A)
 {
     // an aborted pass adds and counts nothing (the trace waves that saw the exit flag stored nothing)
     if (P.exit_flag && __hip_atomic_load(P.exit_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= P.exit_gen) return;
@@ -25,9 +23,8 @@ __global__ __launch_bounds__(PTK_ABLOCK) void accumulate_adaptive_kernel(const R
     const int owned = blockIdx.x;
     const int tile = owned * P.world + P.rank;
     if (tile >= P.num_tiles) return;
-    const int ty = tile / P.tiles_x, tx = (tile % P.tiles_x + P.tiles_x - (3 * ty) % P.tiles_x) % P.tiles_x;
-    const int px = tx * PTK_TILE + (quad & 1) * 8 + (lane & 7);
-    const int py = ty * PTK_TILE + (quad >> 1) * 8 + (lane >> 3);
+    int tx, ty, px, py; tile_origin(tile, P.tiles_x, tx, ty);
+    quadrant_pixel(tx, ty, quad, lane, px, py);
     if (px >= P.width || py >= P.height) return;
     const size_t pix = (size_t)(P.height - 1 - py) * P.width + px;      // bottom-up, like the accumulator
     const size_t accidx = pix * 3;
@@ -70,10 +67,7 @@ __global__ __launch_bounds__(PTK_ABLOCK) void accumulate_adaptive_kernel(const R
 #pragma unroll
     for (int k = 0; k < 3; k++)
     {
-        float x = c3[k];
-        x = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x);
-        if (!(x == x)) x = 0.0f;
-        b3[k] = (uint8_t)(x * 255);
+        b3[k] = resolve8(c3[k]);
         if (active) P.rgb8[accidx + k] = b3[k];
     }
     if (P.rgb8_host)
@@ -105,7 +99,7 @@ __global__ __launch_bounds__(PTK_ABLOCK) void accumulate_adaptive_kernel(const R
 // neighbourhood clipped to the tile (pixels off the image are never active, which clips to the image).  Writes the new active
 // mask in place (each workgroup reads and writes only its own tile's four words), the traced mask base & active, and adds the
 // active pixels to the count the host reads.
-__global__ __launch_bounds__(PTK_ABLOCK) void converge_kernel(const RenderParams P, const ConvergeParams C)
+__global__ __launch_bounds__(PTK_BLOCK) void converge_kernel(const RenderParams P, const ConvergeParams C)
 {
     __shared__ unsigned long long need[4];
     __shared__ int stand_down;
@@ -116,9 +110,9 @@ __global__ __launch_bounds__(PTK_ABLOCK) void converge_kernel(const RenderParams
     if (stand_down) return;
     const int owned = blockIdx.x, tile = owned * P.world + P.rank;
     if (tile >= P.num_tiles) return;                 // (uniform over the workgroup)
-    const int ty = tile / P.tiles_x, tx = (tile % P.tiles_x + P.tiles_x - (3 * ty) % P.tiles_x) % P.tiles_x;
-    const int lx = (quad & 1) * 8 + (lane & 7), ly = (quad >> 1) * 8 + (lane >> 3);
-    const int px = tx * PTK_TILE + lx, py = ty * PTK_TILE + ly;
+    int tx, ty, px, py; tile_origin(tile, P.tiles_x, tx, ty);
+    quadrant_pixel(tx, ty, quad, lane, px, py);
+    const int lx = px - tx * PTK_TILE, ly = py - ty * PTK_TILE;      // the pixel within its tile
     const size_t subtile = (size_t)owned * 4 + quad;
     const bool act = px < P.width && py < P.height && (C.init || ((C.active[subtile] >> lane) & 1ull) != 0ull);
     bool open = act;
@@ -163,42 +157,13 @@ __global__ __launch_bounds__(PTK_ABLOCK) void converge_kernel(const RenderParams
     }
 }
 
-// Ordered list of the quadrants with a non-zero mask, and their number (one workgroup: a few hundred thousand quadrants at most)
-__global__ __launch_bounds__(1024) void mask_compact_kernel(const unsigned long long* mask, int num_subtiles, unsigned* list, unsigned* count)
-{
-    __shared__ unsigned wave_total[16];
-    __shared__ unsigned base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) base = 0;
-    __syncthreads();
-    for (int s0 = 0; s0 < num_subtiles; s0 += 1024)
-    {
-        const int sidx = s0 + t;
-        const bool live = sidx < num_subtiles && mask[sidx] != 0ull;
-        const unsigned long long b = __ballot(live);
-        if (lane == 0) wave_total[wave] = (unsigned)__popcll(b);
-        __syncthreads();
-        unsigned before = base;
-        for (int w = 0; w < wave; w++) before += wave_total[w];
-        if (live) list[before + (unsigned)__popcll(b & ((1ull << lane) - 1ull))] = (unsigned)sidx;
-        __syncthreads();
-        if (t == 0) { unsigned sum = 0; for (int w = 0; w < 16; w++) sum += wave_total[w]; base += sum; }
-        __syncthreads();
-    }
-    if (t == 0) *count = base;
-}
-
 void launch_accumulate_adaptive(const RenderParams& p, const AdaptiveParams& a, int owned_tiles, hipStream_t stream)
 {
-    if (owned_tiles > 0) hipLaunchKernelGGL(accumulate_adaptive_kernel, dim3(owned_tiles), dim3(PTK_ABLOCK), 0, stream, p, a);
+    if (owned_tiles > 0) hipLaunchKernelGGL(accumulate_adaptive_kernel, dim3(owned_tiles), dim3(PTK_BLOCK), 0, stream, p, a);
 }
 void launch_converge(const RenderParams& p, const ConvergeParams& cp, int owned_tiles, hipStream_t stream)
 {
-    if (owned_tiles > 0) hipLaunchKernelGGL(converge_kernel, dim3(owned_tiles), dim3(PTK_ABLOCK), 0, stream, p, cp);
-}
-void launch_mask_compact(const unsigned long long* mask, int num_subtiles, unsigned* list, unsigned* count, hipStream_t stream)
-{
-    if (num_subtiles > 0) hipLaunchKernelGGL(mask_compact_kernel, dim3(1), dim3(1024), 0, stream, mask, num_subtiles, list, count);
+    if (owned_tiles > 0) hipLaunchKernelGGL(converge_kernel, dim3(owned_tiles), dim3(PTK_BLOCK), 0, stream, p, cp);
 }
 
 }  // namespace ptk

@@ -22,7 +22,7 @@
 
 #include "bvh_build.h"
 #include "bvh_device.h"
-#include "ptk_device.h"
+#include "ptk_device_fn.h"
 #include "ptk_adaptive.h"
 #include "ptk_features.h"
 
@@ -261,7 +261,7 @@ unsigned long long owned_pixels(const ptk_ctx* c)
     unsigned long long n = 0;
     for (int tile = c->rank; tile < tiles_x * tiles_y; tile += c->world)
     {
-        const int ty = tile / tiles_x, tx = (tile % tiles_x + tiles_x - (3 * ty) % tiles_x) % tiles_x;
+        int tx, ty; tile_origin(tile, tiles_x, tx, ty);
         const int w = std::min(PTK_TILE, c->width - tx * PTK_TILE), h = std::min(PTK_TILE, c->height - ty * PTK_TILE);
         n += (unsigned long long)w * h;
     }
@@ -503,7 +503,7 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
                 cp.base = c->d_live_mask; cp.init = 1; cp.test = 0;
                 launch_converge(p, cp, tiles, c->stream);
                 HIPCHK(c, hipGetLastError());
-                launch_mask_compact(c->d_adapt_traced, subtiles, c->d_adapt_list, count, c->stream);
+                launch_compact_list(c->d_adapt_traced, subtiles, c->d_adapt_list, count, c->stream);
                 HIPCHK(c, hipGetLastError());
             }
             p.live_mask = c->d_adapt_traced; p.live_list = c->d_adapt_list; p.live_count = count;
@@ -772,7 +772,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
         return fail(c, PTK_ERR_BAD_ARG, "negative count in scene description");
     if (n > 0 && (!s->verts || !s->normals || !s->uvs || !s->tbn || !s->smoothing || !s->material || !s->materials))
         return fail(c, PTK_ERR_BAD_ARG, "null triangle/material array");
-    // (the walk addresses triangle and node records with 32-bit BYTE offsets from wave-uniform bases - ptk_kernels.hip
+    // (the walk addresses triangle and node records with 32-bit BYTE offsets from wave-uniform bases - ptk_device_fn.h
     // request_node / walk_step - so a record array ends below 4 GiB: 89 478 485 triangles of 48 bytes; checked before anything
     // reads the arrays.  The node array of such a scene, ~0.4 nodes of 64 bytes per triangle, stays below that by itself and is
     // checked once it exists)
@@ -787,7 +787,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
             return fail(c, PTK_ERR_BAD_ARG, "triangle material index out of range");
     for (int32_t i = 0; i < s->num_lights; i++)
         if (s->lights[i] < 0 || s->lights[i] >= n) return fail(c, PTK_ERR_BAD_ARG, "light triangle index out of range");
-    // the kernels' exact short reciprocal (ptk_kernels.hip rcp_ieee) covers determinants and lengths up to 2^126: coordinates
+    // the kernels' exact short reciprocal (ptk_device_fn.h rcp_ieee) covers determinants and lengths up to 2^126: coordinates
     // must stay below 2^61 in magnitude (the reference's own float arithmetic is long meaningless out there)
     float vmax = 0.0f;
     float vlo[3] = { INFINITY, INFINITY, INFINITY }, vhi[3] = { -INFINITY, -INFINITY, -INFINITY };
@@ -1233,7 +1233,7 @@ int ptk_render_adaptive(ptk_ctx* c, float threshold, uint32_t min_spp, uint32_t 
         HIPCHK(c, hipMemsetAsync(cp.active_count, 0, sizeof(unsigned), c->stream));
         launch_converge(p, cp, tiles, c->stream);
         HIPCHK(c, hipGetLastError());
-        launch_mask_compact(c->d_adapt_traced, tiles * 4, c->d_adapt_list, c->d_adapt_list + c->adapt_capacity, c->stream);
+        launch_compact_list(c->d_adapt_traced, tiles * 4, c->d_adapt_list, c->d_adapt_list + c->adapt_capacity, c->stream);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(c->h_adapt_count + (r & 1), cp.active_count, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipEventRecord(c->ev_adapt[r & 1], c->stream));
@@ -1408,7 +1408,7 @@ int ptk_read_sample_counts(ptk_ctx* c, uint32_t* host_out)
         const uint32_t n = (uint32_t)c->samples.load();
         for (int tile = c->rank; tile < tiles_x * tiles_y; tile += c->world)
         {
-            const int ty = tile / tiles_x, tx = (tile % tiles_x + tiles_x - (3 * ty) % tiles_x) % tiles_x;
+            int tx, ty; tile_origin(tile, tiles_x, tx, ty);
             for (int y = ty * PTK_TILE; y < std::min(c->height, (ty + 1) * PTK_TILE); y++)
                 for (int x = tx * PTK_TILE; x < std::min(c->width, (tx + 1) * PTK_TILE); x++)
                     host_out[(size_t)(c->height - 1 - y) * c->width + x] = n;
@@ -1695,7 +1695,7 @@ int ptk_packed_layout(int width, int height, int rank, int world, int64_t* src_i
     int64_t k = 0;
     for (int tile = rank; tile < num_tiles; tile += world)
     {
-        const int ty = tile / tiles_x, tx = (tile % tiles_x + tiles_x - (3 * ty) % tiles_x) % tiles_x;
+        int tx, ty; tile_origin(tile, tiles_x, tx, ty);
         for (int p = 0; p < PTK_TILE * PTK_TILE; p++)
         {
             const int px = tx * PTK_TILE + (p & 15), py = ty * PTK_TILE + (p >> 4);

@@ -1,0 +1,550 @@
+// Device functions shared by every kernel file of libptk.so, all __forceinline__: the v3 arithmetic in the reference's order, the
+// exact 1 / x and sqrt (rcp_ieee, sqrt_ieee), the RNG and its keys, tex2d, the re-entrant BVH walk (Walk, tri_test, walk_step), the
+// light sampler, the owned-tile / quadrant pixel mapping and the 8-bit resolve.  PTK_CONTRACT selects namespace and arithmetic:
+// 0 (the default: what a file that does not define it gets) namespace ptk, every operation the IEEE operation of the CPU oracle;
+// 1 ptk::fma, the same text for -ffp-contract=fast; 2 ptk::fast, 1 / x, sqrt and 1 / sqrt straight from the hardware as well.
+// Only ptk_kernels.hip is built at levels 1 and 2 (see there).  The committed counter files are tied to this file's sha256
+// (kernel_header_sha256, profiles/README.md) beside that of ptk_kernels.hip + ptk_device.h: the trace kernels' walk is here.
+#pragma once
+
+#include "ptk_device.h"
+
+#ifndef PTK_CONTRACT
+#define PTK_CONTRACT 0
+#endif
+
+namespace ptk {
+#if PTK_CONTRACT >= 2
+namespace fast {
+#elif PTK_CONTRACT
+namespace fma {
+#endif
+
+#define PTK_EPS 0.00001f                        // mesh.h:12
+#define PTK_FLT_EPSILON 1.1920928955078125e-7f
+#define PTK_PI_D 3.14159265358979323846
+#define PTK_BLOCK 256
+#define PTK_NOHIT 0x7fffffff
+// rows of the per-lane LDS traversal stack: the most entries the tree may defer, plus one row of slack that walk_step's
+// branchless pushes write into (every link is stored at the running top, also one that does not stay)
+#define PTK_STACK_ROWS (PTK_MAX_BVH_DEPTH + 1)
+
+struct v3 { float x, y, z; };
+
+__device__ __forceinline__ v3 V(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
+__device__ __forceinline__ v3 add(v3 a, v3 b) { return V(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ __forceinline__ v3 sub(v3 a, v3 b) { return V(a.x - b.x, a.y - b.y, a.z - b.z); }
+__device__ __forceinline__ v3 mulv(v3 a, v3 b) { return V(a.x * b.x, a.y * b.y, a.z * b.z); }
+__device__ __forceinline__ v3 muls(v3 a, float s) { return V(a.x * s, a.y * s, a.z * s); }
+__device__ __forceinline__ v3 neg(v3 a) { return V(-a.x, -a.y, -a.z); }
+// glm 0.9.3.1 dot / cross / normalize / reflect (include/glm/core/func_geometric.inl:161-283)
+__device__ __forceinline__ float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ v3 cross(v3 x, v3 y)
+{
+    return V(x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y);
+}
+// 1.0f / a, BIT FOR BIT the IEEE-754 round-to-nearest quotient the oracle and the reference compute, for every float with
+// 2^-126 <= |a| <= 2^126: v_rcp_f32 (1 ulp) and one Newton step with an exact residual.  Proven by enumeration - all 2^32
+// bit patterns on this GPU, tools/microbench/exact_math.hip, profiles/r02/exact_math.json: 0 mismatches in that range - and
+// 13 issue cycles instead of the 43 of the compiler's v_div_scale / v_div_fmas / v_div_fixup expansion (which exists for the
+// denormal ranges).  The range cannot be left by a triangle's determinant or a vector's length while scene coordinates stay
+// below 2^61 in magnitude, which ptk_upload_scene enforces.
+__device__ __forceinline__ float rcp_ieee(float a)
+{
+#if PTK_CONTRACT >= 2
+    return __builtin_amdgcn_rcpf(a);
+#else
+    const float y = __builtin_amdgcn_rcpf(a);
+    const float e = __builtin_fmaf(-a, y, 1.0f);
+    return __builtin_fmaf(y, e, y);
+#endif
+}
+// ... plus IEEE results for zeros, infinities and NaNs (one v_div_fixup_f32): where a zero length can occur
+__device__ __forceinline__ float rcp_ieee_any(float a)
+{
+#if PTK_CONTRACT >= 2
+    return __builtin_amdgcn_rcpf(a);
+#else
+    return __builtin_amdgcn_div_fixupf(rcp_ieee(a), a, 1.0f);
+#endif
+}
+// sqrtf(x), BIT FOR BIT the correctly rounded IEEE-754 root: v_sqrt_f32 (1 ulp) and the exact residuals (fma) of its two
+// neighbours - the core of the compiler's own expansion without its range scaling (x < 2^-96 is multiplied by 2^32 first)
+// and special-case selects.  Enumerated over all 2^32 bit patterns (tools/microbench/exact_math.hip, profiles/r02/
+// exact_math.json): identical to sqrtf for +0, +inf and every x >= 2^-104 (the largest input that differs is 0x0b6e9372,
+// where the residuals underflow); anything below - a positive length under 2^-52, which no scene produces, and negative
+// or NaN arguments - takes the compiler's expansion behind a branch that is practically never taken.
+__device__ __forceinline__ float sqrt_ieee(float x)
+{
+#if PTK_CONTRACT >= 2
+    return __builtin_amdgcn_sqrtf(x);
+#else
+    if (__builtin_expect(!(x >= 0x1p-104f), 0)) return sqrtf(x);          // (zero too: correct either way, and as rare)
+    float s = __builtin_amdgcn_sqrtf(x);
+    const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
+    const float rm = __builtin_fmaf(-sm, s, x), rp = __builtin_fmaf(-sp, s, x);
+    s = rm <= 0.0f ? sm : s;
+    return rp > 0.0f ? sp : s;
+#endif
+}
+// the factor normalize() multiplies by: glm's inversesqrt = 1 / sqrt(x), two IEEE roundings (level 2: v_rsq_f32)
+__device__ __forceinline__ float inv_length(float sqr)
+{
+#if PTK_CONTRACT >= 2
+    return __builtin_amdgcn_rsqf(sqr);
+#else
+    return rcp_ieee_any(sqrt_ieee(sqr));
+#endif
+}
+__device__ __forceinline__ v3 normalize(v3 a)
+{
+    float sqr = a.x * a.x + a.y * a.y + a.z * a.z;
+    return muls(a, inv_length(sqr));
+}
+__device__ __forceinline__ v3 reflect(v3 I, v3 N)
+{
+    float d = dot(N, I);
+    return sub(I, muls(muls(N, d), 2.0f));
+}
+
+// sin/cos on [0, 2*pi]: fixed polynomial shared (by construction, not by source) with the oracle
+__device__ __forceinline__ void sincos_2pi(float a, float& s, float& c)
+{
+    int k = (int)(a * 0.636619772367581343f + 0.5f);
+    float r = (float)((double)a - (double)k * 1.57079632679489661923);
+    float z = r * r;
+    float sp = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
+    float cp = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z
+               - 0.5f * z + 1.0f;
+    int q = k & 3;
+    float ss = (q & 1) ? cp : sp;
+    float cc = (q & 1) ? sp : cp;
+    s = (q & 2) ? -ss : ss;
+    c = (q == 1 || q == 2) ? -cc : cc;
+}
+
+// ---- RNG (replaces PathTracer::Rand, pathtracer.cpp:367-371) -----------------------------------
+__device__ __forceinline__ uint32_t pcg_out(uint32_t st)
+{
+    uint32_t w = ((st >> ((st >> 28u) + 4u)) ^ st) * 277803737u;
+    return (w >> 22u) ^ w;
+}
+__device__ __forceinline__ uint32_t hash32(uint32_t x) { return pcg_out(x * 747796405u + 2891336453u); }
+__device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-8f; }
+
+struct Rng {
+    uint32_t state, inc, key;
+    __device__ __forceinline__ float next()
+    {
+        uint32_t old = state;
+        state = old * 747796405u + inc;
+        return u01(pcg_out(old));
+    }
+    __device__ __forceinline__ float opacity(uint32_t ray, uint32_t tri) const
+    {
+        return u01(hash32(tri + hash32(ray + key)));
+    }
+};
+
+__device__ __forceinline__ float4 ldg4(const float4* p) { return *p; }
+typedef float f2 __attribute__((ext_vector_type(2)));
+// (float)byte / 255.0f, exactly: the double product rounds to the same float for all 256 bytes
+// (checked exhaustively in tests/test_host_cpu.py); saves the IEEE division sequence
+__device__ __forceinline__ float unorm8(uint32_t b) { return (float)((double)b * (1.0 / 255.0)); }
+
+// ---- Image::tex2D (image.cpp:63-86), nearest + repeat, RGBA8 atlas -----------------------------------
+template <class PT>
+__device__ __forceinline__ float4 tex2d(const PT& P, int tex, float uvx, float uvy)
+{
+    int4 ti = P.texinfo[tex];
+    float u = uvx - truncf(uvx);              // == fmodf(uvx, 1.0f), exact
+    float v = uvy - truncf(uvy);
+    if (u < 0.0f) u += 1.0f;
+    if (v < 0.0f) v += 1.0f;
+    int cx = (int)((float)ti.x * u);
+    int cy = (int)((float)ti.y * v);
+    cx = min(cx, ti.x - 1); cy = min(cy, ti.y - 1);
+    cx = max(cx, 0); cy = max(cy, 0);
+    uint32_t w = P.texels[(size_t)ti.z + (size_t)cy * (size_t)ti.x + (size_t)cx];
+    float4 r;
+    r.x = unorm8(w & 255u);
+    r.y = unorm8((w >> 8) & 255u);
+    r.z = unorm8((w >> 16) & 255u);
+    r.w = unorm8(w >> 24);
+    return r;
+}
+template <class PT>
+__device__ __forceinline__ float tex2d_r(const PT& P, int tex, float uvx, float uvy)
+{
+    int4 ti = P.texinfo[tex];
+    float u = uvx - truncf(uvx);
+    float v = uvy - truncf(uvy);
+    if (u < 0.0f) u += 1.0f;
+    if (v < 0.0f) v += 1.0f;
+    int cx = (int)((float)ti.x * u);
+    int cy = (int)((float)ti.y * v);
+    cx = min(cx, ti.x - 1); cy = min(cy, ti.y - 1);
+    cx = max(cx, 0); cy = max(cy, 0);
+    uint32_t w = P.texels[(size_t)ti.z + (size_t)cy * (size_t)ti.x + (size_t)cx];
+    return unorm8(w & 255u);
+}
+
+struct Hit { int tri; float t, u, v; };
+
+struct Counters { uint32_t rays, shadow, nodes, tris, shaded, tex, walk_iters, walk_lanes, shade_execs, shade_lanes, gen_execs, gen_lanes, tri_execs, tri_lanes, cur_nodes, max_nodes, started; };
+
+// ---- closest hit (replaces the recursive PathTracer::Hit, pathtracer.cpp:411-492) ---------------------
+// The walk is re-entrant: all of its state lives in this struct so a wave can interleave BVH steps
+// with shading of other lanes.  stack: this thread's column of the block's LDS stack, element k at
+// stack[k * PTK_BLOCK].
+struct Walk {
+    v3 ro, rd, inv;
+    v3 cn, cf;                   // per axis: -(ro * inv + slack) and slack - ro * inv, the constant terms of a node's near / far slab
+                                 // distances for this ray; slack = what the slab arithmetic can be off by for any node (walk_step)
+    uint32_t sgnx, sgny, sgnz;   // per axis: all ones when the ray travels towards -axis (selects the near / far plane bytes with one v_bfi each)
+    int node;
+    int* top;                    // this lane's stack top in LDS (== its column's base when empty); unused by the FLAT kernel
+    int tri_next, tri_left;      // pending leaf: records [tri_next, tri_next + tri_left) still to test
+    Hit best;
+    // occl_tri >= 0 marks a shadow ray towards light triangle occl_tri.  DirectIllumimation's test (pathtracer.cpp:522-526) is
+    // "the closest hit along the ray is the light triangle (or nothing)".  The light triangle is tested FIRST, before the walk
+    // (its record comes with the light sample), so `best` already holds its hit - if the ray hits it at all - and any other
+    // triangle the walk then accepts is, by the closest-hit rule, nearer: it decides the test and ends the walk.  Order
+    // independent by construction.  (Round 1 ended the walk on any hit nearer than 0.9999 x the distance to the light SAMPLE:
+    // wrong when Moeller-Trumbore places a grazing hit on the light triangle itself nearer than that - found by
+    // tools/soak_random_scenes.py, one pixel-sample in 19 of 3000 random scenes.)
+    int occl_tri;
+
+    // node: >= 0 interior node to test next; NODE_EXIT nothing left on the node side; any other negative
+    // value = a leaf waiting for the triangle queue (tri_next, tri_left) to drain
+    __device__ __forceinline__ void begin(v3 o, v3 d, int num_nodes, int* stack, float scene_bound)
+    {
+        ro = o; rd = d;
+        // acceleration only: 1-ulp reciprocals are fine for conservative slab tests.  Clamped to +-1e18 so that a ray
+        // parallel to an axis (a zero component: a hemisphere sample with w == 0 about an axis-aligned normal, one path in
+        // 2^24) keeps FINITE slab distances of the right sign - with +-inf the quantised form q * (scale * inv) + (origin -
+        // ro) * inv turns into NaNs on that axis, the axis stops culling and such a ray walks the whole tree (measured:
+        // 228 153 node visits for one ray of the 1 M-triangle scene, a 0.5 s tail per launch)
+        inv = V(__builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.x), -1e18f, 1e18f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.y), -1e18f, 1e18f),
+                __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.z), -1e18f, 1e18f));
+        // The slab arithmetic of walk_step, t = fma(q, A, B) with A = scale * inv and B = (origin - ro) * inv, is off by at most
+        // 2^-21 (|B| + 256 |A|) (see there).  Every node origin lies inside the scene's padded bounds and a node's 255 grid
+        // steps span at most the scene, so per axis that is at most 2^-21 (max |ro| + 3.1 scene_bound) |inv| - a property of the RAY,
+        // computed here once instead of twelve instructions per node visited.  (In position units 5e-7 x the scene's size:
+        // nothing next to a node's own extent until rays come from ~10^5 scene sizes away, where it is exactly what is needed.)
+        const float r21 = (fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)) + scene_bound) * 0x1p-21f;      // (one bound for the three axes)
+        const v3 slack = V(r21 * fabsf(inv.x), r21 * fabsf(inv.y), r21 * fabsf(inv.z));
+        // ... and folded, with the ray's own share of B, into the constant of ONE fma per plane family and axis:
+        //   B -+ slack = origin * inv - ro * inv -+ slack = fma(origin, inv, cn | cf),   cn = fma(-ro, inv, -slack), cf = fma(-ro, inv, slack)
+        // (origin * inv - ro * inv instead of (origin - ro) * inv: the cancellation costs 2^-24 (|origin| + |ro|) |inv| at most,
+        // which the bound above was derived with - |origin - ro| <= |origin| + |ro| - so it is covered)
+        cn = V(__builtin_fmaf(-o.x, inv.x, -slack.x), __builtin_fmaf(-o.y, inv.y, -slack.y), __builtin_fmaf(-o.z, inv.z, -slack.z));
+        cf = V(__builtin_fmaf(-o.x, inv.x, slack.x), __builtin_fmaf(-o.y, inv.y, slack.y), __builtin_fmaf(-o.z, inv.z, slack.z));
+        sgnx = (uint32_t)(__float_as_int(inv.x) >> 31); sgny = (uint32_t)(__float_as_int(inv.y) >> 31); sgnz = (uint32_t)(__float_as_int(inv.z) >> 31);
+        node = num_nodes > 0 ? 0 : NODE_EXIT;
+        top = stack;
+        tri_next = 0; tri_left = 0;
+        best.tri = PTK_NOHIT; best.t = __builtin_inff(); best.u = 0.0f; best.v = 0.0f;
+    }
+    __device__ __forceinline__ bool done() const { return node == NODE_EXIT && tri_left == 0; }
+    template <int STRIDE>
+    __device__ __forceinline__ int pop(const int* stack)
+    {
+        if (top == stack) return NODE_EXIT;
+        top -= STRIDE;
+        return *top;
+    }
+};
+
+// Candidate test of one triangle record: Hit's leaf branch (pathtracer.cpp:463-489) = Moeller-Trumbore
+// + order-independent closest rule + stochastic opacity.  Returns true when the walk can stop (an
+// occluder decided a shadow ray).
+template <bool STATS, class PT>
+__device__ __forceinline__ bool tri_test(const PT& P, Walk& W, float4 t0, float4 t1, float4 t2, const Rng& rng,
+                                         uint32_t ray, Counters& cnt)
+{
+    const v3 ro = W.ro, rd = W.rd;
+    if (STATS) cnt.tris++;
+    // Moeller-Trumbore, PathTracer::IntersectTriangle pathtracer.cpp:373-409.  The reference returns
+    // early after each rejection test; here every quantity is computed and the SAME tests (in their
+    // negated form, so NaNs fall through exactly as they do there) are AND-ed: identical results for
+    // every accepted hit, no divergent branches in the hot loop.
+    v3 v0 = V(t0.x, t0.y, t0.z);
+    v3 edge1 = V(t0.w, t1.x, t1.y);
+    v3 edge2 = V(t1.z, t1.w, t2.x);
+    v3 h = cross(rd, edge2);
+    float a = dot(edge1, h);
+    float f = rcp_ieee(a);                      // (|a| < EPS, a NaN or infinite: rejected below whatever f is)
+    v3 s = sub(ro, v0);
+    float u = f * dot(s, h);
+    v3 q = cross(s, edge1);
+    float v = f * dot(rd, q);
+    float t = f * dot(edge2, q);
+    int tri = __float_as_int(t2.y);
+    // (the reference also returns on u > 1, pathtracer.cpp:393: implied here - v >= 0 makes fl(u + v) >= u, rounding being
+    // monotone, so u > 1 fails the u + v test, and a NaN u passes both forms alike)
+    bool ok = !(fabsf(a) < PTK_EPS) & !(u < 0.0f) & !(v < 0.0f) & !(u + v > 1.0f) & (t > PTK_EPS);
+    // (t < inf: with a ray origin ~1e30 away q overflows, v is NaN, t +inf - the reference rejects that on u > 1 or on a NaN
+    // of its own; without the test the tie rule below would take t == best.t == inf for a hit.  ptk_set_camera bounds the
+    // camera position, so only a path that has already left every float range could get here)
+    ok = ok & (t < __builtin_inff()) & ((t < W.best.t) | ((t == W.best.t) & (tri < W.best.tri)));
+    int otex = __float_as_int(t2.z);
+    if (ok && otex >= 0)
+    {
+        // stochastic opacity, pathtracer.cpp:469-476 (GetUV :533-536); rare: skipped with s_cbranch_execz
+        const float4* sp4 = P.shade + (size_t)tri * SHADE_F4;
+        float4 s1 = ldg4(sp4 + 1), s2 = ldg4(sp4 + 2);
+        float w = 1.0f - u - v;
+        float ux = w * s1.x + u * s1.z + v * s2.x;
+        float uy = w * s1.y + u * s1.w + v * s2.y;
+        float op = tex2d_r(P, otex, ux, uy);
+        if (STATS) cnt.tex++;
+        ok = rng.opacity(ray, (uint32_t)tri) < op;
+    }
+    W.best.tri = ok ? tri : W.best.tri;
+    W.best.t = ok ? t : W.best.t;
+    W.best.u = ok ? u : W.best.u;
+    W.best.v = ok ? v : W.best.v;
+    return ok & (W.occl_tri >= 0) & (tri != W.occl_tri);
+}
+
+// What the walk loop reads of the launch parameters, held in SGPRs for the length of the loop.  The parameters themselves
+// live in the constant address space (trace_kernel), where a field is an s_load at its point of use - right for the hundreds of
+// fields-times-places outside the hot loop, wrong inside it: the compiler re-issued the loads of the node and triangle pointers
+// in EVERY walk iteration and waited for them before the node record could even be requested.  readfirstlane makes the
+// values opaque (not re-materialisable as loads).
+// (The pointers keep the GLOBAL address space through the integer round trip: a generic pointer would turn every record fetch
+// into a flat_load, which is slower and counts against the LDS counter as well.)
+#define PTK_GLOBAL __attribute__((address_space(1)))
+struct WalkParams {
+    const float4* nodes; const float4* tris; const float4* shade;
+    const int4* texinfo; const uint32_t* texels;
+    int tri_thr, shade_thr, gen_thr;
+};
+template <class T>
+__device__ __forceinline__ T* uniform_ptr(T* p)
+{
+    const uint64_t v = (uint64_t)(uintptr_t)p;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return (T*)(PTK_GLOBAL T*)(uintptr_t)(((uint64_t)hi << 32) | lo);        // integer -> GLOBAL pointer -> generic: the loads stay global_load
+}
+template <class PT>
+__device__ __forceinline__ WalkParams walk_params(const PT& P)
+{
+    WalkParams w;
+    w.nodes = uniform_ptr(P.nodes); w.tris = uniform_ptr(P.tris); w.shade = uniform_ptr(P.shade);
+    w.texinfo = uniform_ptr(P.texinfo); w.texels = uniform_ptr(P.texels);
+    w.tri_thr = __builtin_amdgcn_readfirstlane(P.tri_thr); w.shade_thr = __builtin_amdgcn_readfirstlane(P.shade_thr);
+    w.gen_thr = __builtin_amdgcn_readfirstlane(P.gen_thr);
+    return w;
+}
+
+// One BVH step of a lane: up to two triangles of the pending leaf (arm A) AND one interior node (arm B).  A leaf
+// reached by arm B is parked in the lane's one-entry triangle queue and the descent continues with the next node
+// from the stack, so the two arms overlap instead of alternating (the wave executes both arms every iteration anyway).
+// The price is slightly later t-max tightening; the result is unaffected (closest hit is order-independent).
+struct NodeRec { float4 q0, q1, q2, q3; };      // one 64-byte node record in flight / in registers
+// the record of the node a lane will test next (a lane without a node reads the root - every such lane the same 64 bytes - which
+// costs less than a branch around the loads and zeroing sixteen registers for the lanes that skip them)
+template <class PT>
+__device__ __forceinline__ void request_node(const PT& P, const Walk& W, NodeRec& r)
+{
+    // (a 32-bit byte offset from the wave-uniform base: the load takes its base from an SGPR pair, no 64-bit address arithmetic)
+    const float4* np = (const float4*)((const char*)P.nodes + (uint32_t)max(W.node, 0) * (uint32_t)(NODE_F4 * 16));
+    r.q0 = ldg4(np); r.q1 = ldg4(np + 1); r.q2 = ldg4(np + 2); r.q3 = ldg4(np + 3);
+}
+// PIPELINED: the caller's loop keeps a node record in flight ACROSS iterations - `rec` was requested (request_node) before the
+// loop or at the end of the lane's previous step, and the record of the node this step ends on is requested before the step
+// returns, so its round trip also covers the loop's wave-uniform bookkeeping (ballots, debts, ~30 dependent scalar instructions)
+// instead of starting behind it.
+template <bool STATS, int STRIDE, bool PIPELINED = false, class PT>
+__device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, uint32_t ray, int* stack, Counters& cnt,
+                                          const bool run_tri_arm = true, NodeRec* rec = nullptr)
+{
+    // the node record of arm B is requested BEFORE arm A runs, so that its round trip overlaps arm A's loads and arithmetic
+    // (one memory latency per iteration instead of two; the compiler would otherwise issue it after arm A's join)
+    NodeRec here;
+    if (PIPELINED) here = *rec; else request_node(P, W, here);
+    const float4 q0 = here.q0, q1 = here.q1, q2 = here.q2, q3 = here.q3;
+    asm volatile("" ::: "memory");
+    const bool node_was = W.node >= 0;
+    if (run_tri_arm && W.tri_left > 0)                    // ---- arm A: up to TWO triangles
+    {
+        // The second triangle: the pending leaf's next one, or - the pending leaf has only this one left and the lane is BLOCKED
+        // on a second leaf (W.node holds it: the one-leaf queue was busy) - the first triangle of that leaf, whose remainder then
+        // becomes the pending leaf while the lane pops its next node.  Both records are requested together and tested one after
+        // the other: the same tri_test calls in the same order as one per execution, so results cannot differ.  Leaves hold
+        // 1.1-1.5 triangles on average, so what this buys is mostly the blocked leaf - its lane walks on an iteration earlier -
+        // and a triangle arm that is voted 44 % less often (round 4: C4 +2 %, C5 +4 %, C3 +4 %; three or four per execution,
+        // and the pair in packed f32, measured slower: DESIGN 12).
+        const bool two = W.tri_left >= 2;
+        const bool blocked = !two & (W.node < 0) & (W.node != NODE_EXIT);
+        const int code = ~W.node;
+        const int iA = W.tri_next, iB = two ? iA + 1 : (blocked ? (code >> 3) : iA);
+        const float4* tpa = (const float4*)((const char*)P.tris + (uint32_t)iA * (uint32_t)(TRI_F4 * 16));
+        const float4* tpb = (const float4*)((const char*)P.tris + (uint32_t)iB * (uint32_t)(TRI_F4 * 16));
+        float4 a0 = ldg4(tpa), a1 = ldg4(tpa + 1), a2 = ldg4(tpa + 2);
+        float4 b0 = ldg4(tpb), b1 = ldg4(tpb + 1), b2 = ldg4(tpb + 2);
+        bool stop = tri_test<STATS>(P, W, a0, a1, a2, rng, ray, cnt);
+        if ((two | blocked) && !stop) stop = tri_test<STATS>(P, W, b0, b1, b2, rng, ray, cnt);
+        if (blocked)
+        {
+            W.tri_next = (code >> 3) + 1; W.tri_left = code & 7;
+            W.node = W.template pop<STRIDE>(stack);
+        }
+        else { W.tri_next = iA + (two ? 2 : 1); W.tri_left -= two ? 2 : 1; }
+        W.top = stop ? stack : W.top;                     // an occluder decides a shadow ray: drop everything
+        W.tri_left = stop ? 0 : W.tri_left;
+        W.node = stop ? NODE_EXIT : W.node;
+    }
+    if (node_was && W.node >= 0)                          // ---- arm B: one 4-wide interior node (its record is `here`; a node popped by arm A waits a step)
+    {
+        if (STATS) { cnt.nodes++; cnt.cur_nodes++; }
+        // child planes live on the node's 8-bit grid: plane = origin + q * scale, so along the ray
+        //   t = (plane - ro) * inv = q * (scale * inv) + (origin - ro) * inv = fma(q, A, B)
+        // (box tests are acceleration only - any conservative test gives the same closest hit - so fused
+        // multiply-adds and approximate reciprocals are fine here; the grid boxes enclose the padded boxes)
+        const float Ax = q0.w * W.inv.x, Ay = q1.x * W.inv.y, Az = q1.y * W.inv.z;
+        // CONSERVATIVE for every ray, however far its origin: t = fma(q, A, B) is the sum of two possibly large terms, so its
+        // error is absolute - at most 2^-22 (|B| + 255 |A|) from the roundings of the products, the 1-ulp reciprocal and the
+        // fmas - i.e. a position error of ~6e-8 x the distance between the ray's origin and the node, which exceeds an 8-bit
+        // grid step once that distance is > 65 000 node extents (and Moeller-Trumbore's own decisions carry the same
+        // uncertainty, so no padding of the tree can stand in for it).  Near planes are taken that much (x 2) too early and far
+        // planes too late; found by tools/soak_bvh.py: two clusters of 1e-3 at +-1e3 gave tree-dependent hits.  The bound is
+        // taken per RAY (Walk::begin: |B| <= (|ro| + scene bound) |inv|, 256 |A| <= 2.01 scene bound |inv|) and folded into the
+        // ray's constants: six fused multiply-adds per node here (round 2: fifteen instructions).
+        const float Bnx = __builtin_fmaf(q0.x, W.inv.x, W.cn.x), Bny = __builtin_fmaf(q0.y, W.inv.y, W.cn.y), Bnz = __builtin_fmaf(q0.z, W.inv.z, W.cn.z);
+        const float Bfx = __builtin_fmaf(q0.x, W.inv.x, W.cf.x), Bfy = __builtin_fmaf(q0.y, W.inv.y, W.cf.y), Bfz = __builtin_fmaf(q0.z, W.inv.z, W.cf.z);
+        // the ray enters a slab through the low plane when it travels in +axis, through the high plane otherwise:
+        // pick the near / far plane bytes of all four children at once by the sign of the direction
+        const uint32_t mx = W.sgnx, my = W.sgny, mz = W.sgnz;
+        const uint32_t lox = __float_as_uint(q2.z), loy = __float_as_uint(q2.w), loz = __float_as_uint(q3.x);
+        const uint32_t hix = __float_as_uint(q3.y), hiy = __float_as_uint(q3.z), hiz = __float_as_uint(q3.w);
+        const uint32_t nx = (hix & mx) | (lox & ~mx), fx = (lox & mx) | (hix & ~mx);
+        const uint32_t ny = (hiy & my) | (loy & ~my), fy = (loy & my) | (hiy & ~my);
+        const uint32_t nz = (hiz & mz) | (loz & ~mz), fz = (loz & mz) | (hiz & ~mz);
+        const int link0 = __float_as_int(q1.z), link1 = __float_as_int(q1.w), link2 = __float_as_int(q2.x), link3 = __float_as_int(q2.y);
+        // ... and a node is only culled against the closest hit so far when it lies beyond it by more than Moeller-Trumbore's
+        // own error in t (relative ~1e-7 / cos of the incidence angle: which of two triangles 1e-6 apart is "closest" is
+        // decided by that arithmetic, not by geometry - the second half of the same soak finding)
+        const float tmax = W.best.t * 1.0000153f;
+        int key[4];
+        bool hit[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+        {
+            const float tnx = __builtin_fmaf((float)((nx >> (8 * k)) & 255u), Ax, Bnx), tfx = __builtin_fmaf((float)((fx >> (8 * k)) & 255u), Ax, Bfx);
+            const float tny = __builtin_fmaf((float)((ny >> (8 * k)) & 255u), Ay, Bny), tfy = __builtin_fmaf((float)((fy >> (8 * k)) & 255u), Ay, Bfy);
+            const float tnz = __builtin_fmaf((float)((nz >> (8 * k)) & 255u), Az, Bnz), tfz = __builtin_fmaf((float)((fz >> (8 * k)) & 255u), Az, Bfz);
+            // NaNs (0 * inf for axis-parallel rays) drop out of min3 / max3: that axis then does not constrain - conservative
+            const float tn = fmaxf(fmaxf(tnx, tny), tnz), tf = fminf(fminf(tfx, tfy), tfz);
+            // entry no earlier than the ray's start, exit no later than the closest hit: ONE compare instead of three (and no
+            // scalar ands of three lane masks per child; round 4: C4 +1.5 %)
+            hit[k] = fmaxf(tn, 0.0f) <= fminf(tf, tmax);
+            // order key: the entry distance with the slot in its low bits (negative distances - origin inside - sort first)
+            key[k] = hit[k] ? ((__float_as_int(tn) & ~3) | k) : 0x7fffffff;
+        }
+        const int kmin = min(min(key[0], key[1]), min(key[2], key[3]));
+        // the nearest child is the one whose key is the minimum (keys of hit children differ in their slot bits); the same
+        // four compares decide which of the others wait on the stack (two hits: exactly far-after-near; more: slot order)
+        const bool o0 = key[0] != kmin, o1 = key[1] != kmin, o2 = key[2] != kmin;
+        int next = !o0 ? link0 : (!o1 ? link1 : (!o2 ? link2 : link3));
+        // every link is written at the running top and the top moves on only behind a link that stays: no exec-mask juggling around
+        // four conditional stores (round 4: C4 +2 %; with the clamped compare above: 28 -> 11 scalar instructions per node).  A link
+        // that does not stay is still stored, one row above a stack that may be full: hence the slack row of PTK_STACK_ROWS
+        *W.top = link0; W.top += (hit[0] & o0) ? STRIDE : 0;
+        *W.top = link1; W.top += (hit[1] & o1) ? STRIDE : 0;
+        *W.top = link2; W.top += (hit[2] & o2) ? STRIDE : 0;
+        *W.top = link3; W.top += (hit[3] & (key[3] != kmin)) ? STRIDE : 0;
+        if (kmin == 0x7fffffff) next = W.template pop<STRIDE>(stack);
+        W.node = next;
+    }
+    if (W.node < 0 && W.node != NODE_EXIT && W.tri_left == 0)   // a leaf and the triangle queue is free
+    {
+        const int code = ~W.node;
+        W.tri_next = code >> 3;
+        W.tri_left = (code & 7) + 1;
+        W.node = W.template pop<STRIDE>(stack);
+    }
+    if (PIPELINED) request_node(P, W, *rec);                    // for this lane's next step (a finished walk asks for the root: where its next ray starts)
+}
+
+// hemisphere / lobe sampler, pathtracer.cpp:606-611 (:618-623 lobe form): see oracle sample_about()
+__device__ __forceinline__ v3 sample_about(v3 n_for_test, float thr, v3 basis_from, v3 pole, float w, float theta)
+{
+    v3 u = fabsf(n_for_test.x) < thr ? cross(V(1.0f, 0.0f, 0.0f), basis_from) : cross(V(1.0f, 1.0f, 1.0f), basis_from);
+    u = normalize(u);
+    v3 v = normalize(cross(u, basis_from));
+    float ang = (float)(2.0f * PTK_PI_D * theta);
+    float sn, cs;
+    sincos_2pi(ang, sn, cs);
+    v3 d = add(add(muls(u, w * cs), muls(v, w * sn)), muls(pole, sqrt_ieee(1.0f - w * w)));
+    return normalize(d);
+}
+
+__device__ __forceinline__ uint32_t pixel_key(uint32_t seed_lo, uint32_t seed_hi, uint32_t pixel)
+{
+    uint32_t a = hash32(seed_hi);
+    uint32_t b = hash32(seed_lo + a);
+    return hash32(pixel + b);
+}
+
+// DirectIllumimation's sampling half (pathtracer.cpp:494-521, 527-530; SampleTriangle :494-503): picks a light triangle and a
+// point on it from three draws, in the reference's order, and returns false when the surface faces away (:518-520).  Its
+// visibility half (:522-526, closest hit along l is the light) is the shadow walk the caller starts: towards `l`, with
+// occl_tri = light_tri, after testing the light triangle itself (lt0..lt2, its record) first.  di is the value DirectIllumimation returns when that walk finds the
+// light (:530).
+template <class PT>
+__device__ __forceinline__ bool sample_direct_light(const PT& P, v3 p, v3 n, v3 diffuse, float u_light, float u_su, float u_sv,
+                                                    v3& l, v3& di, int& light_tri, float4& lt0, float4& lt1, float4& lt2)
+{
+    int lightId = (int)floorf(u_light * (float)P.num_lights);
+    if (lightId == P.num_lights && lightId > 0) lightId--;
+    const float4* lp = P.lights + (size_t)lightId * LIGHT_F4;
+    float4 l0 = ldg4(lp), l1 = ldg4(lp + 1), l2 = ldg4(lp + 2), l3 = ldg4(lp + 3);
+    float su = sqrt_ieee(u_su);
+    float sv = u_sv;
+    float w0 = 1.0f - su, w1 = su * (1.0f - sv), w2 = su * sv;
+    v3 vLight = add(add(muls(V(l0.x, l0.y, l0.z), w0), muls(V(l1.x, l1.y, l1.z), w1)),
+                    muls(V(l2.x, l2.y, l2.z), w2));
+    const v3 dl = sub(vLight, p);
+    l = normalize(dl);
+    float ndl = dot(neg(n), neg(l));
+    light_tri = __float_as_int(l0.w);
+    // the light triangle's own record, as the walk would fetch it: v0, e1 = v2 - v1, e2 = v3 - v1 (the same subtractions the
+    // record packers perform), its index and opacity texture
+    lt0 = make_float4(l0.x, l0.y, l0.z, l1.x - l0.x);
+    lt1 = make_float4(l1.y - l0.y, l1.z - l0.z, l2.x - l0.x, l2.y - l0.y);
+    lt2 = make_float4(l2.z - l0.z, l0.w, l3.y, 0.0f);
+    if (ndl <= 0.0f) return false;              // (:519 in its own form: a NaN normal - a normal map on a mesh without uvs - goes ON, as there)
+    v3 lColor = V(l1.w, l2.w, l3.x);
+    di = muls(mulv(lColor, diffuse), ndl);      // :530
+    return true;
+}
+
+// ---- owned tiles -> pixels ------------------------------------------------------------------------------------------------
+// Tile column and row of tile index `tile` (rank r of `world` owns tiles r, r + world, ...): rows are rotated by 3 tiles each so
+// that a rank's tiles form diagonals, not columns (load balance).  Also what the host's loops over owned tiles use (ptk_api.hip).
+__host__ __device__ __forceinline__ void tile_origin(int tile, int tiles_x, int& tx, int& ty)
+{
+    ty = tile / tiles_x; tx = (tile % tiles_x + tiles_x - (3 * ty) % tiles_x) % tiles_x;
+}
+// the pixel of `lane` of the wave that holds 8x8 quadrant `quad` of tile (tx, ty): one wave per quadrant, rows of eight lanes
+__device__ __forceinline__ void quadrant_pixel(int tx, int ty, int quad, int lane, int& px, int& py)
+{
+    px = tx * PTK_TILE + (quad & 1) * 8 + (lane & 7);
+    py = ty * PTK_TILE + (quad >> 1) * 8 + (lane >> 3);
+}
+
+// one channel of the 8-bit resolve (pathtracer.cpp:802-812): clamped to [0, 1], NaN to 0, x * 255 truncated
+__device__ __forceinline__ uint8_t resolve8(float x)
+{
+    x = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x);
+    if (!(x == x)) x = 0.0f;
+    return (uint8_t)(x * 255);
+}
+
+#if PTK_CONTRACT
+}  // namespace fma / fast
+#endif
+}  // namespace ptk

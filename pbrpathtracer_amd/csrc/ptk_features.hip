@@ -1,20 +1,11 @@
 // HIP kernels for gfx950 of the first-hit feature planes and of picking (include/ptk.h ptk_render_features, ptk_pick).
-// They are built from the trace kernels' own device functions - the exact normalize, tex2d, Walk, tri_test, walk_step, the RNG
-// keys - which live in ptk_kernels.hip, not in a header.  That file stays byte for byte as it is (the committed counter files are
-// tied to its hash, and its kernels keep their machine code): this translation unit includes it in the form that holds the shared
-// device functions and the trace kernels only (PTK_CONTRACT 1: the sections of the exact build are left out) under a namespace of
-// its own, and is compiled with -ffp-contract=off like the exact build.  At PTK_CONTRACT 1 the arithmetic helpers are the exact
-// ones (only level 2 swaps in the hardware's reciprocal and root), so every operation below is the IEEE operation of the exact
-// trace kernel.  The price is a private copy of the trace kernels in this object, which nothing launches.
+// They are built from the trace kernels' own device functions (ptk_device_fn.h: the exact normalize, tex2d, Walk, tri_test,
+// walk_step, the RNG keys) and compiled once, with -ffp-contract=off like the exact build, so every operation below is the IEEE
+// operation of the exact trace kernel.
+#include "ptk_device_fn.h"
 #include "ptk_features.h"
 
-#define PTK_CONTRACT 1
-#define fma features_tu          // the namespace ptk_kernels.hip opens at PTK_CONTRACT 1; ptk::fma itself belongs to the contracted build
-#include "ptk_kernels.hip"
-#undef fma
-
 namespace ptk {
-namespace features_tu {
 
 // the feature ray of pixel `pix` (top-down index): the camera-ray block at zero lens offset
 template <class PT>
@@ -51,9 +42,8 @@ __global__ __launch_bounds__(PTK_BLOCK) void features_kernel(const RenderParams 
     const int tid = threadIdx.x, lane = tid & 63, quad = tid >> 6;
     const int tile = blockIdx.x * P.world + P.rank;
     if (tile >= P.num_tiles) return;
-    const int ty = tile / P.tiles_x, tx = (tile % P.tiles_x + P.tiles_x - (3 * ty) % P.tiles_x) % P.tiles_x;
-    const int px = tx * PTK_TILE + (quad & 1) * 8 + (lane & 7);
-    const int py = ty * PTK_TILE + (quad >> 1) * 8 + (lane >> 3);
+    int tx, ty, px, py; tile_origin(tile, P.tiles_x, tx, ty);
+    quadrant_pixel(tx, ty, quad, lane, px, py);
     if (px >= P.width || py >= P.height) return;
     const size_t pix = (size_t)py * P.width + px;                          // top-down: primary, primary_hit, the RNG's pixel
     const size_t o = (size_t)(P.height - 1 - py) * P.width + px;           // bottom-up, like the accumulator
@@ -175,15 +165,13 @@ __global__ __launch_bounds__(PTK_BLOCK) void pick_kernel(const RenderParams P, c
     out3[2] = __float_as_int(hit ? h.t : __builtin_inff());
 }
 
-}  // namespace features_tu
-
 void launch_features(const RenderParams& p, const FeatureParams& f, int owned_tiles, hipStream_t stream)
 {
-    if (owned_tiles > 0) hipLaunchKernelGGL(features_tu::features_kernel, dim3(owned_tiles), dim3(PTK_BLOCK), 0, stream, p, f);
+    if (owned_tiles > 0) hipLaunchKernelGGL(features_kernel, dim3(owned_tiles), dim3(PTK_BLOCK), 0, stream, p, f);
 }
 void launch_pick(const RenderParams& p, const FeatureParams& f, int pixel, int32_t* out3, hipStream_t stream)
 {
-    hipLaunchKernelGGL(features_tu::pick_kernel, dim3(1), dim3(PTK_BLOCK), 0, stream, p, f, pixel, out3);
+    hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(PTK_BLOCK), 0, stream, p, f, pixel, out3);
 }
 
 }  // namespace ptk

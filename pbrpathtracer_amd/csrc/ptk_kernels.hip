@@ -2,7 +2,9 @@
 //   PathTracer::RenderFrame -> Trace -> Hit -> {IntersectTriangle, Image::tex2D, DirectIllumimation}
 //   (reference PathTracing/src/pathtracer.cpp:367-822, mesh.cpp:48-59, image.cpp:63-86)
 // as a path-tracing kernel of persistent waves (trace_kernel: one path per lane) followed by a streaming
-// accumulate_kernel.
+// accumulate_kernel.  This file holds what is compiled once per arithmetic level (below): the trace kernels, what only they use,
+// the queue set-up, probe_math_kernel.  The shared device functions (v3, the exact arithmetic, the RNG, tex2d, the walk) are in
+// ptk_device_fn.h; accumulate_kernel and the other kernels that exist once are in ptk_frame.hip.
 //
 // Design (not a translation of the reference's recursion):
 //   * Trace is iterative: L += T*e; L += T*direct; T *= weight, with the reference's two counters
@@ -40,9 +42,7 @@
 //
 // Float arithmetic is written operation by operation in the reference's order and this file is
 // compiled with -ffp-contract=off: results are reproducible against the CPU oracle bit for bit.
-
-#include "ptk_device.h"
-
+//
 // This file is compiled THREE times into libptk.so.  PTK_CONTRACT 0 (default): -ffp-contract=off, the bit-exact product kernels
 // in namespace ptk.  PTK_CONTRACT 1: the same trace kernels in namespace ptk::fma, built with -ffp-contract=fast (the compiler
 // fuses a * b + c into v_fma_f32 wherever it appears: Moeller-Trumbore, dot products, normalisations, shading) for the
@@ -51,10 +51,9 @@
 // bit-identical to the oracle, but held to it sample by sample (tests/test_gpu_contract_samples.py: nearly every sample within
 // 1e-4 relative of the exact kernels' and no bias among those; the rest took another branch or texel) and to the mean image's
 // tolerance (tests/test_gpu_contract.py); and still reproducible bit for bit, whatever the work distribution, passes or tiles.
-// Each build has its own probe_math_kernel (ptk_probe_math follows the option).
-#ifndef PTK_CONTRACT
-#define PTK_CONTRACT 0
-#endif
+// Each build has its own probe_math_kernel (ptk_probe_math follows the option).  (The header defaults PTK_CONTRACT to 0.)
+
+#include "ptk_device_fn.h"
 
 namespace ptk {
 #if PTK_CONTRACT >= 2
@@ -63,10 +62,6 @@ namespace fast {
 namespace fma {
 #endif
 
-#define PTK_EPS 0.00001f                        // mesh.h:12
-#define PTK_FLT_EPSILON 1.1920928955078125e-7f
-#define PTK_PI_D 3.14159265358979323846
-#define PTK_BLOCK 256
 #define PTK_TRACE_BLOCK 64          // trace_kernel: one wave per workgroup -> finest-grained dispatch
 #ifndef PTK_TRACE_WAVES
 #define PTK_TRACE_WAVES 5           // waves per SIMD the register allocator must allow, FLAT variant: 96 VGPRs (4 spilled) since the parameters
@@ -79,289 +74,6 @@ namespace fma {
 #ifndef PTK_TRACE_WAVES_BVH
 #define PTK_TRACE_WAVES_BVH 4       // ... BVH variant
 #endif
-#define PTK_NOHIT 0x7fffffff
-// rows of the per-lane LDS traversal stack: the most entries the tree may defer, plus one row of slack that walk_step's
-// branchless pushes write into (every link is stored at the running top, also one that does not stay)
-#define PTK_STACK_ROWS (PTK_MAX_BVH_DEPTH + 1)
-
-struct v3 { float x, y, z; };
-
-__device__ __forceinline__ v3 V(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
-__device__ __forceinline__ v3 add(v3 a, v3 b) { return V(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ v3 sub(v3 a, v3 b) { return V(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ v3 mulv(v3 a, v3 b) { return V(a.x * b.x, a.y * b.y, a.z * b.z); }
-__device__ __forceinline__ v3 muls(v3 a, float s) { return V(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ v3 neg(v3 a) { return V(-a.x, -a.y, -a.z); }
-// glm 0.9.3.1 dot / cross / normalize / reflect (include/glm/core/func_geometric.inl:161-283)
-__device__ __forceinline__ float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ v3 cross(v3 x, v3 y)
-{
-    return V(x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y);
-}
-// 1.0f / a, BIT FOR BIT the IEEE-754 round-to-nearest quotient the oracle and the reference compute, for every float with
-// 2^-126 <= |a| <= 2^126: v_rcp_f32 (1 ulp) and one Newton step with an exact residual.  Proven by enumeration - all 2^32
-// bit patterns on this GPU, tools/microbench/exact_math.hip, profiles/r02/exact_math.json: 0 mismatches in that range - and
-// 13 issue cycles instead of the 43 of the compiler's v_div_scale / v_div_fmas / v_div_fixup expansion (which exists for the
-// denormal ranges).  The range cannot be left by a triangle's determinant or a vector's length while scene coordinates stay
-// below 2^61 in magnitude, which ptk_upload_scene enforces.
-__device__ __forceinline__ float rcp_ieee(float a)
-{
-#if PTK_CONTRACT >= 2
-    return __builtin_amdgcn_rcpf(a);
-#else
-    const float y = __builtin_amdgcn_rcpf(a);
-    const float e = __builtin_fmaf(-a, y, 1.0f);
-    return __builtin_fmaf(y, e, y);
-#endif
-}
-// ... plus IEEE results for zeros, infinities and NaNs (one v_div_fixup_f32): where a zero length can occur
-__device__ __forceinline__ float rcp_ieee_any(float a)
-{
-#if PTK_CONTRACT >= 2
-    return __builtin_amdgcn_rcpf(a);
-#else
-    return __builtin_amdgcn_div_fixupf(rcp_ieee(a), a, 1.0f);
-#endif
-}
-// sqrtf(x), BIT FOR BIT the correctly rounded IEEE-754 root: v_sqrt_f32 (1 ulp) and the exact residuals (fma) of its two
-// neighbours - the core of the compiler's own expansion without its range scaling (x < 2^-96 is multiplied by 2^32 first)
-// and special-case selects.  Enumerated over all 2^32 bit patterns (tools/microbench/exact_math.hip, profiles/r02/
-// exact_math.json): identical to sqrtf for +0, +inf and every x >= 2^-104 (the largest input that differs is 0x0b6e9372,
-// where the residuals underflow); anything below - a positive length under 2^-52, which no scene produces, and negative
-// or NaN arguments - takes the compiler's expansion behind a branch that is practically never taken.
-__device__ __forceinline__ float sqrt_ieee(float x)
-{
-#if PTK_CONTRACT >= 2
-    return __builtin_amdgcn_sqrtf(x);
-#else
-    if (__builtin_expect(!(x >= 0x1p-104f), 0)) return sqrtf(x);          // (zero too: correct either way, and as rare)
-    float s = __builtin_amdgcn_sqrtf(x);
-    const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
-    const float rm = __builtin_fmaf(-sm, s, x), rp = __builtin_fmaf(-sp, s, x);
-    s = rm <= 0.0f ? sm : s;
-    return rp > 0.0f ? sp : s;
-#endif
-}
-// the factor normalize() multiplies by: glm's inversesqrt = 1 / sqrt(x), two IEEE roundings (level 2: v_rsq_f32)
-__device__ __forceinline__ float inv_length(float sqr)
-{
-#if PTK_CONTRACT >= 2
-    return __builtin_amdgcn_rsqf(sqr);
-#else
-    return rcp_ieee_any(sqrt_ieee(sqr));
-#endif
-}
-__device__ __forceinline__ v3 normalize(v3 a)
-{
-    float sqr = a.x * a.x + a.y * a.y + a.z * a.z;
-    return muls(a, inv_length(sqr));
-}
-__device__ __forceinline__ v3 reflect(v3 I, v3 N)
-{
-    float d = dot(N, I);
-    return sub(I, muls(muls(N, d), 2.0f));
-}
-
-// sin/cos on [0, 2*pi]: fixed polynomial shared (by construction, not by source) with the oracle
-__device__ __forceinline__ void sincos_2pi(float a, float& s, float& c)
-{
-    int k = (int)(a * 0.636619772367581343f + 0.5f);
-    float r = (float)((double)a - (double)k * 1.57079632679489661923);
-    float z = r * r;
-    float sp = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
-    float cp = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z
-               - 0.5f * z + 1.0f;
-    int q = k & 3;
-    float ss = (q & 1) ? cp : sp;
-    float cc = (q & 1) ? sp : cp;
-    s = (q & 2) ? -ss : ss;
-    c = (q == 1 || q == 2) ? -cc : cc;
-}
-
-// ---- RNG (replaces PathTracer::Rand, pathtracer.cpp:367-371) -----------------------------------
-__device__ __forceinline__ uint32_t pcg_out(uint32_t st)
-{
-    uint32_t w = ((st >> ((st >> 28u) + 4u)) ^ st) * 277803737u;
-    return (w >> 22u) ^ w;
-}
-__device__ __forceinline__ uint32_t hash32(uint32_t x) { return pcg_out(x * 747796405u + 2891336453u); }
-__device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-8f; }
-
-struct Rng {
-    uint32_t state, inc, key;
-    __device__ __forceinline__ float next()
-    {
-        uint32_t old = state;
-        state = old * 747796405u + inc;
-        return u01(pcg_out(old));
-    }
-    __device__ __forceinline__ float opacity(uint32_t ray, uint32_t tri) const
-    {
-        return u01(hash32(tri + hash32(ray + key)));
-    }
-};
-
-__device__ __forceinline__ float4 ldg4(const float4* p) { return *p; }
-typedef float f2 __attribute__((ext_vector_type(2)));
-// (float)byte / 255.0f, exactly: the double product rounds to the same float for all 256 bytes
-// (checked exhaustively in tests/test_host_cpu.py); saves the IEEE division sequence
-__device__ __forceinline__ float unorm8(uint32_t b) { return (float)((double)b * (1.0 / 255.0)); }
-
-// ---- Image::tex2D (image.cpp:63-86), nearest + repeat, RGBA8 atlas -----------------------------------
-template <class PT>
-__device__ __forceinline__ float4 tex2d(const PT& P, int tex, float uvx, float uvy)
-{
-    int4 ti = P.texinfo[tex];
-    float u = uvx - truncf(uvx);              // == fmodf(uvx, 1.0f), exact
-    float v = uvy - truncf(uvy);
-    if (u < 0.0f) u += 1.0f;
-    if (v < 0.0f) v += 1.0f;
-    int cx = (int)((float)ti.x * u);
-    int cy = (int)((float)ti.y * v);
-    cx = min(cx, ti.x - 1); cy = min(cy, ti.y - 1);
-    cx = max(cx, 0); cy = max(cy, 0);
-    uint32_t w = P.texels[(size_t)ti.z + (size_t)cy * (size_t)ti.x + (size_t)cx];
-    float4 r;
-    r.x = unorm8(w & 255u);
-    r.y = unorm8((w >> 8) & 255u);
-    r.z = unorm8((w >> 16) & 255u);
-    r.w = unorm8(w >> 24);
-    return r;
-}
-template <class PT>
-__device__ __forceinline__ float tex2d_r(const PT& P, int tex, float uvx, float uvy)
-{
-    int4 ti = P.texinfo[tex];
-    float u = uvx - truncf(uvx);
-    float v = uvy - truncf(uvy);
-    if (u < 0.0f) u += 1.0f;
-    if (v < 0.0f) v += 1.0f;
-    int cx = (int)((float)ti.x * u);
-    int cy = (int)((float)ti.y * v);
-    cx = min(cx, ti.x - 1); cy = min(cy, ti.y - 1);
-    cx = max(cx, 0); cy = max(cy, 0);
-    uint32_t w = P.texels[(size_t)ti.z + (size_t)cy * (size_t)ti.x + (size_t)cx];
-    return unorm8(w & 255u);
-}
-
-struct Hit { int tri; float t, u, v; };
-
-struct Counters { uint32_t rays, shadow, nodes, tris, shaded, tex, walk_iters, walk_lanes, shade_execs, shade_lanes, gen_execs, gen_lanes, tri_execs, tri_lanes, cur_nodes, max_nodes, started; };
-
-// ---- closest hit (replaces the recursive PathTracer::Hit, pathtracer.cpp:411-492) ---------------------
-// The walk is re-entrant: all of its state lives in this struct so a wave can interleave BVH steps
-// with shading of other lanes.  stack: this thread's column of the block's LDS stack, element k at
-// stack[k * PTK_BLOCK].
-struct Walk {
-    v3 ro, rd, inv;
-    v3 cn, cf;                   // per axis: -(ro * inv + slack) and slack - ro * inv, the constant terms of a node's near / far slab
-                                 // distances for this ray; slack = what the slab arithmetic can be off by for any node (walk_step)
-    uint32_t sgnx, sgny, sgnz;   // per axis: all ones when the ray travels towards -axis (selects the near / far plane bytes with one v_bfi each)
-    int node;
-    int* top;                    // this lane's stack top in LDS (== its column's base when empty); unused by the FLAT kernel
-    int tri_next, tri_left;      // pending leaf: records [tri_next, tri_next + tri_left) still to test
-    Hit best;
-    // occl_tri >= 0 marks a shadow ray towards light triangle occl_tri.  DirectIllumimation's test (pathtracer.cpp:522-526) is
-    // "the closest hit along the ray is the light triangle (or nothing)".  The light triangle is tested FIRST, before the walk
-    // (its record comes with the light sample), so `best` already holds its hit - if the ray hits it at all - and any other
-    // triangle the walk then accepts is, by the closest-hit rule, nearer: it decides the test and ends the walk.  Order
-    // independent by construction.  (Round 1 ended the walk on any hit nearer than 0.9999 x the distance to the light SAMPLE:
-    // wrong when Moeller-Trumbore places a grazing hit on the light triangle itself nearer than that - found by
-    // tools/soak_random_scenes.py, one pixel-sample in 19 of 3000 random scenes.)
-    int occl_tri;
-
-    // node: >= 0 interior node to test next; NODE_EXIT nothing left on the node side; any other negative
-    // value = a leaf waiting for the triangle queue (tri_next, tri_left) to drain
-    __device__ __forceinline__ void begin(v3 o, v3 d, int num_nodes, int* stack, float scene_bound)
-    {
-        ro = o; rd = d;
-        // acceleration only: 1-ulp reciprocals are fine for conservative slab tests.  Clamped to +-1e18 so that a ray
-        // parallel to an axis (a zero component: a hemisphere sample with w == 0 about an axis-aligned normal, one path in
-        // 2^24) keeps FINITE slab distances of the right sign - with +-inf the quantised form q * (scale * inv) + (origin -
-        // ro) * inv turns into NaNs on that axis, the axis stops culling and such a ray walks the whole tree (measured:
-        // 228 153 node visits for one ray of the 1 M-triangle scene, a 0.5 s tail per launch)
-        inv = V(__builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.x), -1e18f, 1e18f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.y), -1e18f, 1e18f),
-                __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.z), -1e18f, 1e18f));
-        // The slab arithmetic of walk_step, t = fma(q, A, B) with A = scale * inv and B = (origin - ro) * inv, is off by at most
-        // 2^-21 (|B| + 256 |A|) (see there).  Every node origin lies inside the scene's padded bounds and a node's 255 grid
-        // steps span at most the scene, so per axis that is at most 2^-21 (max |ro| + 3.1 scene_bound) |inv| - a property of the RAY,
-        // computed here once instead of twelve instructions per node visited.  (In position units 5e-7 x the scene's size:
-        // nothing next to a node's own extent until rays come from ~10^5 scene sizes away, where it is exactly what is needed.)
-        const float r21 = (fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)) + scene_bound) * 0x1p-21f;      // (one bound for the three axes)
-        const v3 slack = V(r21 * fabsf(inv.x), r21 * fabsf(inv.y), r21 * fabsf(inv.z));
-        // ... and folded, with the ray's own share of B, into the constant of ONE fma per plane family and axis:
-        //   B -+ slack = origin * inv - ro * inv -+ slack = fma(origin, inv, cn | cf),   cn = fma(-ro, inv, -slack), cf = fma(-ro, inv, slack)
-        // (origin * inv - ro * inv instead of (origin - ro) * inv: the cancellation costs 2^-24 (|origin| + |ro|) |inv| at most,
-        // which the bound above was derived with - |origin - ro| <= |origin| + |ro| - so it is covered)
-        cn = V(__builtin_fmaf(-o.x, inv.x, -slack.x), __builtin_fmaf(-o.y, inv.y, -slack.y), __builtin_fmaf(-o.z, inv.z, -slack.z));
-        cf = V(__builtin_fmaf(-o.x, inv.x, slack.x), __builtin_fmaf(-o.y, inv.y, slack.y), __builtin_fmaf(-o.z, inv.z, slack.z));
-        sgnx = (uint32_t)(__float_as_int(inv.x) >> 31); sgny = (uint32_t)(__float_as_int(inv.y) >> 31); sgnz = (uint32_t)(__float_as_int(inv.z) >> 31);
-        node = num_nodes > 0 ? 0 : NODE_EXIT;
-        top = stack;
-        tri_next = 0; tri_left = 0;
-        best.tri = PTK_NOHIT; best.t = __builtin_inff(); best.u = 0.0f; best.v = 0.0f;
-    }
-    __device__ __forceinline__ bool done() const { return node == NODE_EXIT && tri_left == 0; }
-    template <int STRIDE>
-    __device__ __forceinline__ int pop(const int* stack)
-    {
-        if (top == stack) return NODE_EXIT;
-        top -= STRIDE;
-        return *top;
-    }
-};
-
-// Candidate test of one triangle record: Hit's leaf branch (pathtracer.cpp:463-489) = Moeller-Trumbore
-// + order-independent closest rule + stochastic opacity.  Returns true when the walk can stop (an
-// occluder decided a shadow ray).
-template <bool STATS, class PT>
-__device__ __forceinline__ bool tri_test(const PT& P, Walk& W, float4 t0, float4 t1, float4 t2, const Rng& rng,
-                                         uint32_t ray, Counters& cnt)
-{
-    const v3 ro = W.ro, rd = W.rd;
-    if (STATS) cnt.tris++;
-    // Moeller-Trumbore, PathTracer::IntersectTriangle pathtracer.cpp:373-409.  The reference returns
-    // early after each rejection test; here every quantity is computed and the SAME tests (in their
-    // negated form, so NaNs fall through exactly as they do there) are AND-ed: identical results for
-    // every accepted hit, no divergent branches in the hot loop.
-    v3 v0 = V(t0.x, t0.y, t0.z);
-    v3 edge1 = V(t0.w, t1.x, t1.y);
-    v3 edge2 = V(t1.z, t1.w, t2.x);
-    v3 h = cross(rd, edge2);
-    float a = dot(edge1, h);
-    float f = rcp_ieee(a);                      // (|a| < EPS, a NaN or infinite: rejected below whatever f is)
-    v3 s = sub(ro, v0);
-    float u = f * dot(s, h);
-    v3 q = cross(s, edge1);
-    float v = f * dot(rd, q);
-    float t = f * dot(edge2, q);
-    int tri = __float_as_int(t2.y);
-    // (the reference also returns on u > 1, pathtracer.cpp:393: implied here - v >= 0 makes fl(u + v) >= u, rounding being
-    // monotone, so u > 1 fails the u + v test, and a NaN u passes both forms alike)
-    bool ok = !(fabsf(a) < PTK_EPS) & !(u < 0.0f) & !(v < 0.0f) & !(u + v > 1.0f) & (t > PTK_EPS);
-    // (t < inf: with a ray origin ~1e30 away q overflows, v is NaN, t +inf - the reference rejects that on u > 1 or on a NaN
-    // of its own; without the test the tie rule below would take t == best.t == inf for a hit.  ptk_set_camera bounds the
-    // camera position, so only a path that has already left every float range could get here)
-    ok = ok & (t < __builtin_inff()) & ((t < W.best.t) | ((t == W.best.t) & (tri < W.best.tri)));
-    int otex = __float_as_int(t2.z);
-    if (ok && otex >= 0)
-    {
-        // stochastic opacity, pathtracer.cpp:469-476 (GetUV :533-536); rare: skipped with s_cbranch_execz
-        const float4* sp4 = P.shade + (size_t)tri * SHADE_F4;
-        float4 s1 = ldg4(sp4 + 1), s2 = ldg4(sp4 + 2);
-        float w = 1.0f - u - v;
-        float ux = w * s1.x + u * s1.z + v * s2.x;
-        float uy = w * s1.y + u * s1.w + v * s2.y;
-        float op = tex2d_r(P, otex, ux, uy);
-        if (STATS) cnt.tex++;
-        ok = rng.opacity(ray, (uint32_t)tri) < op;
-    }
-    W.best.tri = ok ? tri : W.best.tri;
-    W.best.t = ok ? t : W.best.t;
-    W.best.u = ok ? u : W.best.u;
-    W.best.v = ok ? v : W.best.v;
-    return ok & (W.occl_tri >= 0) & (tri != W.occl_tri);
-}
 
 // FLAT pass, both rays of a lane against one triangle in PACKED f32: x = the bounce ray (W), y = the shadow ray (WS).
 // Every Moeller-Trumbore operation is the same IEEE mul / add / sub as in tri_test, on two values at once
@@ -426,220 +138,6 @@ __device__ __forceinline__ bool tri_test_pair(const PT& P, Walk& W, Walk& WS, co
     if (okb) { W.best.tri = tri; W.best.t = t.x; W.best.u = u.x; W.best.v = v.x; asm volatile("" : "+v"(W.best.t), "+v"(W.best.u), "+v"(W.best.v)); }
     if (oks) { WS.best.tri = tri; WS.best.t = t.y; WS.best.u = u.y; WS.best.v = v.y; asm volatile("" : "+v"(WS.best.t), "+v"(WS.best.u), "+v"(WS.best.v)); }
     return oks & (tri != WS.occl_tri);
-}
-
-// What the walk loop reads of the launch parameters, held in SGPRs for the length of the loop.  The parameters themselves
-// live in the constant address space (trace_kernel), where a field is an s_load at its point of use - right for the hundreds of
-// fields-times-places outside the hot loop, wrong inside it: the compiler re-issued the loads of the node and triangle pointers
-// in EVERY walk iteration and waited for them before the node record could even be requested.  readfirstlane makes the
-// values opaque (not re-materialisable as loads).
-// (The pointers keep the GLOBAL address space through the integer round trip: a generic pointer would turn every record fetch
-// into a flat_load, which is slower and counts against the LDS counter as well.)
-#define PTK_GLOBAL __attribute__((address_space(1)))
-struct WalkParams {
-    const float4* nodes; const float4* tris; const float4* shade;
-    const int4* texinfo; const uint32_t* texels;
-    int tri_thr, shade_thr, gen_thr;
-};
-template <class T>
-__device__ __forceinline__ T* uniform_ptr(T* p)
-{
-    const uint64_t v = (uint64_t)(uintptr_t)p;
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-    return (T*)(PTK_GLOBAL T*)(uintptr_t)(((uint64_t)hi << 32) | lo);        // integer -> GLOBAL pointer -> generic: the loads stay global_load
-}
-template <class PT>
-__device__ __forceinline__ WalkParams walk_params(const PT& P)
-{
-    WalkParams w;
-    w.nodes = uniform_ptr(P.nodes); w.tris = uniform_ptr(P.tris); w.shade = uniform_ptr(P.shade);
-    w.texinfo = uniform_ptr(P.texinfo); w.texels = uniform_ptr(P.texels);
-    w.tri_thr = __builtin_amdgcn_readfirstlane(P.tri_thr); w.shade_thr = __builtin_amdgcn_readfirstlane(P.shade_thr);
-    w.gen_thr = __builtin_amdgcn_readfirstlane(P.gen_thr);
-    return w;
-}
-
-// One BVH step of a lane: up to two triangles of the pending leaf (arm A) AND one interior node (arm B).  A leaf
-// reached by arm B is parked in the lane's one-entry triangle queue and the descent continues with the next node
-// from the stack, so the two arms overlap instead of alternating (the wave executes both arms every iteration anyway).
-// The price is slightly later t-max tightening; the result is unaffected (closest hit is order-independent).
-struct NodeRec { float4 q0, q1, q2, q3; };      // one 64-byte node record in flight / in registers
-// the record of the node a lane will test next (a lane without a node reads the root - every such lane the same 64 bytes - which
-// costs less than a branch around the loads and zeroing sixteen registers for the lanes that skip them)
-template <class PT>
-__device__ __forceinline__ void request_node(const PT& P, const Walk& W, NodeRec& r)
-{
-    // (a 32-bit byte offset from the wave-uniform base: the load takes its base from an SGPR pair, no 64-bit address arithmetic)
-    const float4* np = (const float4*)((const char*)P.nodes + (uint32_t)max(W.node, 0) * (uint32_t)(NODE_F4 * 16));
-    r.q0 = ldg4(np); r.q1 = ldg4(np + 1); r.q2 = ldg4(np + 2); r.q3 = ldg4(np + 3);
-}
-// PIPELINED: the caller's loop keeps a node record in flight ACROSS iterations - `rec` was requested (request_node) before the
-// loop or at the end of the lane's previous step, and the record of the node this step ends on is requested before the step
-// returns, so its round trip also covers the loop's wave-uniform bookkeeping (ballots, debts, ~30 dependent scalar instructions)
-// instead of starting behind it.
-template <bool STATS, int STRIDE, bool PIPELINED = false, class PT>
-__device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, uint32_t ray, int* stack, Counters& cnt,
-                                          const bool run_tri_arm = true, NodeRec* rec = nullptr)
-{
-    // the node record of arm B is requested BEFORE arm A runs, so that its round trip overlaps arm A's loads and arithmetic
-    // (one memory latency per iteration instead of two; the compiler would otherwise issue it after arm A's join)
-    NodeRec here;
-    if (PIPELINED) here = *rec; else request_node(P, W, here);
-    const float4 q0 = here.q0, q1 = here.q1, q2 = here.q2, q3 = here.q3;
-    asm volatile("" ::: "memory");
-    const bool node_was = W.node >= 0;
-    if (run_tri_arm && W.tri_left > 0)                    // ---- arm A: up to TWO triangles
-    {
-        // The second triangle: the pending leaf's next one, or - the pending leaf has only this one left and the lane is BLOCKED
-        // on a second leaf (W.node holds it: the one-leaf queue was busy) - the first triangle of that leaf, whose remainder then
-        // becomes the pending leaf while the lane pops its next node.  Both records are requested together and tested one after
-        // the other: the same tri_test calls in the same order as one per execution, so results cannot differ.  Leaves hold
-        // 1.1-1.5 triangles on average, so what this buys is mostly the blocked leaf - its lane walks on an iteration earlier -
-        // and a triangle arm that is voted 44 % less often (round 4: C4 +2 %, C5 +4 %, C3 +4 %; three or four per execution,
-        // and the pair in packed f32, measured slower: DESIGN 12).
-        const bool two = W.tri_left >= 2;
-        const bool blocked = !two & (W.node < 0) & (W.node != NODE_EXIT);
-        const int code = ~W.node;
-        const int iA = W.tri_next, iB = two ? iA + 1 : (blocked ? (code >> 3) : iA);
-        const float4* tpa = (const float4*)((const char*)P.tris + (uint32_t)iA * (uint32_t)(TRI_F4 * 16));
-        const float4* tpb = (const float4*)((const char*)P.tris + (uint32_t)iB * (uint32_t)(TRI_F4 * 16));
-        float4 a0 = ldg4(tpa), a1 = ldg4(tpa + 1), a2 = ldg4(tpa + 2);
-        float4 b0 = ldg4(tpb), b1 = ldg4(tpb + 1), b2 = ldg4(tpb + 2);
-        bool stop = tri_test<STATS>(P, W, a0, a1, a2, rng, ray, cnt);
-        if ((two | blocked) && !stop) stop = tri_test<STATS>(P, W, b0, b1, b2, rng, ray, cnt);
-        if (blocked)
-        {
-            W.tri_next = (code >> 3) + 1; W.tri_left = code & 7;
-            W.node = W.template pop<STRIDE>(stack);
-        }
-        else { W.tri_next = iA + (two ? 2 : 1); W.tri_left -= two ? 2 : 1; }
-        W.top = stop ? stack : W.top;                     // an occluder decides a shadow ray: drop everything
-        W.tri_left = stop ? 0 : W.tri_left;
-        W.node = stop ? NODE_EXIT : W.node;
-    }
-    if (node_was && W.node >= 0)                          // ---- arm B: one 4-wide interior node (its record is `here`; a node popped by arm A waits a step)
-    {
-        if (STATS) { cnt.nodes++; cnt.cur_nodes++; }
-        // child planes live on the node's 8-bit grid: plane = origin + q * scale, so along the ray
-        //   t = (plane - ro) * inv = q * (scale * inv) + (origin - ro) * inv = fma(q, A, B)
-        // (box tests are acceleration only - any conservative test gives the same closest hit - so fused
-        // multiply-adds and approximate reciprocals are fine here; the grid boxes enclose the padded boxes)
-        const float Ax = q0.w * W.inv.x, Ay = q1.x * W.inv.y, Az = q1.y * W.inv.z;
-        // CONSERVATIVE for every ray, however far its origin: t = fma(q, A, B) is the sum of two possibly large terms, so its
-        // error is absolute - at most 2^-22 (|B| + 255 |A|) from the roundings of the products, the 1-ulp reciprocal and the
-        // fmas - i.e. a position error of ~6e-8 x the distance between the ray's origin and the node, which exceeds an 8-bit
-        // grid step once that distance is > 65 000 node extents (and Moeller-Trumbore's own decisions carry the same
-        // uncertainty, so no padding of the tree can stand in for it).  Near planes are taken that much (x 2) too early and far
-        // planes too late; found by tools/soak_bvh.py: two clusters of 1e-3 at +-1e3 gave tree-dependent hits.  The bound is
-        // taken per RAY (Walk::begin: |B| <= (|ro| + scene bound) |inv|, 256 |A| <= 2.01 scene bound |inv|) and folded into the
-        // ray's constants: six fused multiply-adds per node here (round 2: fifteen instructions).
-        const float Bnx = __builtin_fmaf(q0.x, W.inv.x, W.cn.x), Bny = __builtin_fmaf(q0.y, W.inv.y, W.cn.y), Bnz = __builtin_fmaf(q0.z, W.inv.z, W.cn.z);
-        const float Bfx = __builtin_fmaf(q0.x, W.inv.x, W.cf.x), Bfy = __builtin_fmaf(q0.y, W.inv.y, W.cf.y), Bfz = __builtin_fmaf(q0.z, W.inv.z, W.cf.z);
-        // the ray enters a slab through the low plane when it travels in +axis, through the high plane otherwise:
-        // pick the near / far plane bytes of all four children at once by the sign of the direction
-        const uint32_t mx = W.sgnx, my = W.sgny, mz = W.sgnz;
-        const uint32_t lox = __float_as_uint(q2.z), loy = __float_as_uint(q2.w), loz = __float_as_uint(q3.x);
-        const uint32_t hix = __float_as_uint(q3.y), hiy = __float_as_uint(q3.z), hiz = __float_as_uint(q3.w);
-        const uint32_t nx = (hix & mx) | (lox & ~mx), fx = (lox & mx) | (hix & ~mx);
-        const uint32_t ny = (hiy & my) | (loy & ~my), fy = (loy & my) | (hiy & ~my);
-        const uint32_t nz = (hiz & mz) | (loz & ~mz), fz = (loz & mz) | (hiz & ~mz);
-        const int link0 = __float_as_int(q1.z), link1 = __float_as_int(q1.w), link2 = __float_as_int(q2.x), link3 = __float_as_int(q2.y);
-        // ... and a node is only culled against the closest hit so far when it lies beyond it by more than Moeller-Trumbore's
-        // own error in t (relative ~1e-7 / cos of the incidence angle: which of two triangles 1e-6 apart is "closest" is
-        // decided by that arithmetic, not by geometry - the second half of the same soak finding)
-        const float tmax = W.best.t * 1.0000153f;
-        int key[4];
-        bool hit[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-        {
-            const float tnx = __builtin_fmaf((float)((nx >> (8 * k)) & 255u), Ax, Bnx), tfx = __builtin_fmaf((float)((fx >> (8 * k)) & 255u), Ax, Bfx);
-            const float tny = __builtin_fmaf((float)((ny >> (8 * k)) & 255u), Ay, Bny), tfy = __builtin_fmaf((float)((fy >> (8 * k)) & 255u), Ay, Bfy);
-            const float tnz = __builtin_fmaf((float)((nz >> (8 * k)) & 255u), Az, Bnz), tfz = __builtin_fmaf((float)((fz >> (8 * k)) & 255u), Az, Bfz);
-            // NaNs (0 * inf for axis-parallel rays) drop out of min3 / max3: that axis then does not constrain - conservative
-            const float tn = fmaxf(fmaxf(tnx, tny), tnz), tf = fminf(fminf(tfx, tfy), tfz);
-            // entry no earlier than the ray's start, exit no later than the closest hit: ONE compare instead of three (and no
-            // scalar ands of three lane masks per child; round 4: C4 +1.5 %)
-            hit[k] = fmaxf(tn, 0.0f) <= fminf(tf, tmax);
-            // order key: the entry distance with the slot in its low bits (negative distances - origin inside - sort first)
-            key[k] = hit[k] ? ((__float_as_int(tn) & ~3) | k) : 0x7fffffff;
-        }
-        const int kmin = min(min(key[0], key[1]), min(key[2], key[3]));
-        // the nearest child is the one whose key is the minimum (keys of hit children differ in their slot bits); the same
-        // four compares decide which of the others wait on the stack (two hits: exactly far-after-near; more: slot order)
-        const bool o0 = key[0] != kmin, o1 = key[1] != kmin, o2 = key[2] != kmin;
-        int next = !o0 ? link0 : (!o1 ? link1 : (!o2 ? link2 : link3));
-        // every link is written at the running top and the top moves on only behind a link that stays: no exec-mask juggling around
-        // four conditional stores (round 4: C4 +2 %; with the clamped compare above: 28 -> 11 scalar instructions per node).  A link
-        // that does not stay is still stored, one row above a stack that may be full: hence the slack row of PTK_STACK_ROWS
-        *W.top = link0; W.top += (hit[0] & o0) ? STRIDE : 0;
-        *W.top = link1; W.top += (hit[1] & o1) ? STRIDE : 0;
-        *W.top = link2; W.top += (hit[2] & o2) ? STRIDE : 0;
-        *W.top = link3; W.top += (hit[3] & (key[3] != kmin)) ? STRIDE : 0;
-        if (kmin == 0x7fffffff) next = W.template pop<STRIDE>(stack);
-        W.node = next;
-    }
-    if (W.node < 0 && W.node != NODE_EXIT && W.tri_left == 0)   // a leaf and the triangle queue is free
-    {
-        const int code = ~W.node;
-        W.tri_next = code >> 3;
-        W.tri_left = (code & 7) + 1;
-        W.node = W.template pop<STRIDE>(stack);
-    }
-    if (PIPELINED) request_node(P, W, *rec);                    // for this lane's next step (a finished walk asks for the root: where its next ray starts)
-}
-
-// hemisphere / lobe sampler, pathtracer.cpp:606-611 (:618-623 lobe form): see oracle sample_about()
-__device__ __forceinline__ v3 sample_about(v3 n_for_test, float thr, v3 basis_from, v3 pole, float w, float theta)
-{
-    v3 u = fabsf(n_for_test.x) < thr ? cross(V(1.0f, 0.0f, 0.0f), basis_from) : cross(V(1.0f, 1.0f, 1.0f), basis_from);
-    u = normalize(u);
-    v3 v = normalize(cross(u, basis_from));
-    float ang = (float)(2.0f * PTK_PI_D * theta);
-    float sn, cs;
-    sincos_2pi(ang, sn, cs);
-    v3 d = add(add(muls(u, w * cs), muls(v, w * sn)), muls(pole, sqrt_ieee(1.0f - w * w)));
-    return normalize(d);
-}
-
-__device__ __forceinline__ uint32_t pixel_key(uint32_t seed_lo, uint32_t seed_hi, uint32_t pixel)
-{
-    uint32_t a = hash32(seed_hi);
-    uint32_t b = hash32(seed_lo + a);
-    return hash32(pixel + b);
-}
-
-// DirectIllumimation's sampling half (pathtracer.cpp:494-521, 527-530; SampleTriangle :494-503): picks a light triangle and a
-// point on it from three draws, in the reference's order, and returns false when the surface faces away (:518-520).  Its
-// visibility half (:522-526, closest hit along l is the light) is the shadow walk the caller starts: towards `l`, with
-// occl_tri = light_tri, after testing the light triangle itself (lt0..lt2, its record) first.  di is the value DirectIllumimation returns when that walk finds the
-// light (:530).
-template <class PT>
-__device__ __forceinline__ bool sample_direct_light(const PT& P, v3 p, v3 n, v3 diffuse, float u_light, float u_su, float u_sv,
-                                                    v3& l, v3& di, int& light_tri, float4& lt0, float4& lt1, float4& lt2)
-{
-    int lightId = (int)floorf(u_light * (float)P.num_lights);
-    if (lightId == P.num_lights && lightId > 0) lightId--;
-    const float4* lp = P.lights + (size_t)lightId * LIGHT_F4;
-    float4 l0 = ldg4(lp), l1 = ldg4(lp + 1), l2 = ldg4(lp + 2), l3 = ldg4(lp + 3);
-    float su = sqrt_ieee(u_su);
-    float sv = u_sv;
-    float w0 = 1.0f - su, w1 = su * (1.0f - sv), w2 = su * sv;
-    v3 vLight = add(add(muls(V(l0.x, l0.y, l0.z), w0), muls(V(l1.x, l1.y, l1.z), w1)),
-                    muls(V(l2.x, l2.y, l2.z), w2));
-    const v3 dl = sub(vLight, p);
-    l = normalize(dl);
-    float ndl = dot(neg(n), neg(l));
-    light_tri = __float_as_int(l0.w);
-    // the light triangle's own record, as the walk would fetch it: v0, e1 = v2 - v1, e2 = v3 - v1 (the same subtractions the
-    // record packers perform), its index and opacity texture
-    lt0 = make_float4(l0.x, l0.y, l0.z, l1.x - l0.x);
-    lt1 = make_float4(l1.y - l0.y, l1.z - l0.z, l2.x - l0.x, l2.y - l0.y);
-    lt2 = make_float4(l2.z - l0.z, l0.w, l3.y, 0.0f);
-    if (ndl <= 0.0f) return false;              // (:519 in its own form: a NaN normal - a normal map on a mesh without uvs - goes ON, as there)
-    v3 lColor = V(l1.w, l2.w, l3.x);
-    di = muls(mulv(lColor, diffuse), ndl);      // :530
-    return true;
 }
 
 // One surface interaction of PathTracer::Trace (pathtracer.cpp:551-727) for the hit W.best of the ray (W.ro, W.rd): emission,
@@ -930,8 +428,7 @@ __device__ __forceinline__ uint32_t acquire_work_item(const PT& P, uint32_t* lds
         const int item = subtile * num_chunks + chunk_id;
         const int owned = subtile >> 2, quad = subtile & 3;
         const int tile = owned * world + rank;
-        // rows are rotated by 3 tiles each so that a rank's tiles form diagonals, not columns (load balance)
-        const int ty = tile / tiles_x, tx = (tile % tiles_x + tiles_x - (3 * ty) % tiles_x) % tiles_x;
+        int tx, ty; tile_origin(tile, tiles_x, tx, ty);
         const int x0 = tx * PTK_TILE + (quad & 1) * 8, y0 = ty * PTK_TILE + (quad >> 1) * 8;
         const uint32_t s_begin = (uint32_t)chunk_id * (uint32_t)chunk;
         const uint32_t s_count = min((uint32_t)chunk, spp - s_begin);      // host guarantees s_begin < spp
@@ -1334,187 +831,6 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
     }
 }
 
-#if !PTK_CONTRACT      // ---- everything but the trace kernels exists once, in the exact build
-// Streaming fold of the sample buffer into the float accumulator, strictly in sample order
-// (`mTotalImg[px] += color` once per RenderFrame(), pathtracer.cpp:798-800), plus the 8-bit resolve
-// (pathtracer.cpp:802-812).  One thread per pixel; each sample read is a coalesced 1 KiB per wave.
-__global__ __launch_bounds__(PTK_BLOCK) void accumulate_kernel(const RenderParams P)
-{
-    // an aborted pass adds nothing: trace waves that saw the exit flag returned without writing their samples, so the
-    // sample buffer may hold another pass's values (the reference adds nothing for the rows it skips, pathtracer.cpp:779-780)
-    if (P.exit_flag && __hip_atomic_load(P.exit_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= P.exit_gen) return;     // an Exit() named this render or a later one
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, quad = tid >> 6;
-    const int owned = blockIdx.x;
-    const int tile = owned * P.world + P.rank;
-    if (tile >= P.num_tiles) return;
-    // rows are rotated by 3 tiles each so that a rank's tiles form diagonals, not columns (load balance)
-    const int ty = tile / P.tiles_x, tx = (tile % P.tiles_x + P.tiles_x - (3 * ty) % P.tiles_x) % P.tiles_x;
-    const int px = tx * PTK_TILE + (quad & 1) * 8 + (lane & 7);
-    const int py = ty * PTK_TILE + (quad >> 1) * 8 + (lane >> 3);
-    if (px >= P.width || py >= P.height) return;
-    const size_t accidx = ((size_t)(P.height - 1 - py) * P.width + px) * 3;   // bottom-up (pathtracer.cpp:796)
-    v3 acc = V(P.accum[accidx], P.accum[accidx + 1], P.accum[accidx + 2]);
-    const size_t subtile = (size_t)owned * 4 + quad;
-    // (a pixel that is not in its quadrant's live mask - cached camera ray misses, or no lens ray reaches the scene - was not
-    // traced: nothing was stored for it and it receives nothing)
-    const bool black = ((P.live_mask[subtile] >> lane) & 1ull) == 0ull;
-    if (!black)
-    {
-        // the samples of one pixel are a strided array (chunk after chunk of its quadrant's items): sample s sits at
-        // in[s * 64].  Eight loads in flight per lane, added strictly in sample order.
-        const float4* in = P.samples + (subtile * P.num_chunks * P.chunk) * 64 + lane;
-        uint32_t s = 0;
-        for (; s + 8 <= P.spp; s += 8)
-        {
-            float4 v[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) v[k] = in[(size_t)(s + k) * 64];
-#pragma unroll
-            for (int k = 0; k < 8; k++) acc = add(acc, V(v[k].x, v[k].y, v[k].z));
-        }
-        for (; s < P.spp; s++)
-        {
-            const float4 col = in[(size_t)s * 64];
-            acc = add(acc, V(col.x, col.y, col.z));
-        }
-    }
-    P.accum[accidx] = acc.x; P.accum[accidx + 1] = acc.y; P.accum[accidx + 2] = acc.z;
-    float c3[3] = { acc.x / P.resolve_samples, acc.y / P.resolve_samples, acc.z / P.resolve_samples };
-    uint8_t b3[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-    {
-        float x = c3[k];
-        x = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x);
-        if (!(x == x)) x = 0.0f;
-        b3[k] = (uint8_t)(x * 255);
-        P.rgb8[accidx + k] = b3[k];
-    }
-    if (P.rgb8_host)
-    {
-        // The hand-off: straight into the caller's page-locked buffer, over PCIe.  A pixel that receives nothing AND holds
-        // nothing resolves to 0 whatever the sample count - it was written when the buffer was bound / reset and is
-        // skipped (four fifths of the C2 frame); one that holds light from before a camera move keeps dimming and is
-        // written.  Byte stores of single pixels crawl over the link (measured: 0.5 MB in 70 us), so a row of the quadrant
-        // - 8 pixels, 24 contiguous bytes - is gathered with lane shuffles and leaves as six dwords.
-        const bool skip_host = black && acc.x == 0.0f && acc.y == 0.0f && acc.z == 0.0f && !P.rgb8_host_full;
-        const uint32_t mine = (uint32_t)b3[0] | ((uint32_t)b3[1] << 8) | ((uint32_t)b3[2] << 16);
-        const unsigned long long row_live = (__ballot(!skip_host) >> (lane & ~7)) & 0xffull;     // this row's pixels that must be written
-        // dword d (0..5) of the row holds bytes 4d..4d+3 = pixels (4d)/3 .. (4d+3)/3; lanes 0..5 of each row write one each
-        const int d = lane & 7;
-        const int p0 = (4 * d) / 3, p1 = min(7, (4 * d + 3) / 3), sh = (4 * d) % 3;          // first pixel, last pixel, byte offset in the first
-        const uint32_t w0 = (uint32_t)__shfl((int)mine, (lane & ~7) + min(p0, 7)), w1 = (uint32_t)__shfl((int)mine, (lane & ~7) + p1);
-        // bytes of pixel p0 from offset sh, then pixel p0 + 1 (= p1 unless the dword lies within one pixel... it never does: 4 > 3)
-        const uint32_t word = (w0 >> (8 * sh)) | (w1 << (8 * (3 - sh)));
-        const bool aligned = (((size_t)P.width * 3) & 3) == 0 && (((uintptr_t)P.rgb8_host) & 3) == 0;
-        const int row_px = min(8, P.width - (px - (lane & 7)));                                // pixels of this row on the image (>= 1 here)
-        if (aligned && row_px == 8)
-        {
-            if (d < 6 && row_live != 0ull) *(uint32_t*)(P.rgb8_host + accidx - (size_t)(lane & 7) * 3 + d * 4) = word;
-        }
-        else if (!skip_host)
-        {
-            P.rgb8_host[accidx] = b3[0]; P.rgb8_host[accidx + 1] = b3[1]; P.rgb8_host[accidx + 2] = b3[2];
-        }
-    }
-}
-
-// Primary ray directions before DOF: one thread per image row walks the row with the reference's
-// incremental `pixel += camRight * deltaX` (pathtracer.cpp:782-785, :814), so every direction is
-// the value the reference computes.  Runs once per camera / resolution change.
-__global__ void primary_dirs_kernel(const PrimaryParams P)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P.height) return;
-    v3 up = V(P.cam_up[0], P.cam_up[1], P.cam_up[2]);
-    v3 right = V(P.cam_right[0], P.cam_right[1], P.cam_right[2]);
-    v3 pos = V(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]);
-    v3 pixel = sub(V(P.top_left[0], P.top_left[1], P.top_left[2]), muls(up, (float)i * P.delta_y));
-    v3 step = muls(right, P.delta_x);
-    float4* row = P.primary + (size_t)i * P.width;
-    for (int j = 0; j < P.width; j++)
-    {
-        v3 d = normalize(sub(pixel, pos));
-        row[j] = make_float4(d.x, d.y, d.z, 0.0f);
-        pixel = add(pixel, step);
-    }
-}
-
-// Primary-visibility cache for pinhole cameras (aperture == 0) in scenes without opacity textures: the
-// camera ray of a pixel is the same for every sample (pathtracer.cpp:785-791 with a zero lens offset),
-// so its closest hit is found once per camera / scene change instead of once per sample.
-__global__ __launch_bounds__(PTK_BLOCK) void primary_hits_kernel(const RenderParams P, float4* out, float4* out_rd)
-{
-    __shared__ int lds_stack[PTK_STACK_ROWS * PTK_BLOCK];
-    const int i = blockIdx.x * PTK_BLOCK + threadIdx.x;
-    if (i >= P.width * P.height) return;
-    Rng rng; rng.inc = 1u; rng.state = 0u; rng.key = 0u;            // no opacity draws can occur here
-    Counters cnt = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-    float4 d = P.primary[i];
-    const v3 camPos0 = V(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]);
-    v3 focalPoint = add(camPos0, muls(V(d.x, d.y, d.z), P.focal_dist));
-    v3 rd = normalize(sub(focalPoint, camPos0));
-    Walk W;
-    W.occl_tri = -1;
-    W.begin(camPos0, rd, P.num_nodes, lds_stack + threadIdx.x, P.scene_bound);
-    while (!W.done()) walk_step<false, PTK_BLOCK>(P, W, rng, 0u, lds_stack + threadIdx.x, cnt);
-    out[i] = make_float4(__int_as_float(W.best.tri), W.best.t, W.best.u, W.best.v);
-    out_rd[i] = make_float4(rd.x, rd.y, rd.z, 0.0f);           // the very floats the camera-ray block computes for a zero lens offset
-}
-
-// Parity probe: closest hit for a list of rays (no opacity draws differ: key 0, ray 0).
-__global__ __launch_bounds__(PTK_BLOCK) void probe_hits_kernel(const ProbeParams P)
-{
-    __shared__ int lds_stack[PTK_STACK_ROWS * PTK_BLOCK];
-    int i = blockIdx.x * PTK_BLOCK + threadIdx.x;
-    if (i >= P.n) return;
-    Rng rng; rng.inc = (hash32(0u ^ 0x9E3779B9u) << 1) | 1u; rng.state = hash32(0u); rng.key = rng.state;
-    Counters cnt = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-    v3 ro = V(P.ro[i * 3], P.ro[i * 3 + 1], P.ro[i * 3 + 2]);
-    v3 rd = V(P.rd[i * 3], P.rd[i * 3 + 1], P.rd[i * 3 + 2]);
-    Walk W;
-    W.occl_tri = -1;
-    W.begin(ro, rd, P.num_nodes, lds_stack + threadIdx.x, P.scene_bound);
-    while (!W.done()) walk_step<false, PTK_BLOCK>(P, W, rng, 0u, lds_stack + threadIdx.x, cnt);
-    bool hit = W.best.tri != PTK_NOHIT;
-    P.tri[i] = hit ? W.best.tri : -1;
-    P.tuv[i * 3] = hit ? W.best.t : 0.0f; P.tuv[i * 3 + 1] = hit ? W.best.u : 0.0f; P.tuv[i * 3 + 2] = hit ? W.best.v : 0.0f;
-}
-
-// Parity probe of DirectIllumimation (pathtracer.cpp:505-531) with its three draws on tape: the sampling half above, then the
-// shadow walk and the visibility rule exactly as trace_kernel applies them (PTK_WALK_DONE).
-__global__ __launch_bounds__(PTK_BLOCK) void probe_direct_kernel(const ProbeParams P, const float* __restrict__ pts, const float* __restrict__ nrm,
-                                                                 const float* __restrict__ dif, const float* __restrict__ tape, float* __restrict__ out)
-{
-    __shared__ int lds_stack[PTK_STACK_ROWS * PTK_BLOCK];
-    const int i = blockIdx.x * PTK_BLOCK + threadIdx.x;
-    if (i >= P.n) return;
-    Rng rng; rng.inc = (hash32(0u ^ 0x9E3779B9u) << 1) | 1u; rng.state = hash32(0u); rng.key = rng.state;
-    Counters cnt = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-    const v3 p = V(pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]), n = V(nrm[i * 3], nrm[i * 3 + 1], nrm[i * 3 + 2]);
-    const v3 diffuse = V(dif[i * 3], dif[i * 3 + 1], dif[i * 3 + 2]);
-    v3 l, di, res = V(0.0f, 0.0f, 0.0f);
-    int light_tri;
-    float4 lt0, lt1, lt2;
-    if (P.num_lights > 0 && sample_direct_light(P, p, n, diffuse, tape[i * 3], tape[i * 3 + 1], tape[i * 3 + 2], l, di, light_tri, lt0, lt1, lt2))
-    {
-        Walk W;
-        W.begin(p, l, P.num_nodes, lds_stack + threadIdx.x, P.scene_bound);
-        W.occl_tri = light_tri;
-        (void)tri_test<false>(P, W, lt0, lt1, lt2, rng, 0u, cnt);
-        while (!W.done()) walk_step<false, PTK_BLOCK>(P, W, rng, 0u, lds_stack + threadIdx.x, cnt);
-        if (!(W.best.tri != PTK_NOHIT && W.best.tri != W.occl_tri)) res = di;        // :522-526: lit unless something else is closest
-    }
-    out[i * 3] = res.x; out[i * 3 + 1] = res.y; out[i * 3 + 2] = res.z;
-}
-void launch_probe_direct(const ProbeParams& p, const float* pts, const float* nrm, const float* dif, const float* tape, float* out, hipStream_t stream)
-{
-    if (p.n > 0) hipLaunchKernelGGL(probe_direct_kernel, dim3((p.n + PTK_BLOCK - 1) / PTK_BLOCK), dim3(PTK_BLOCK), 0, stream, p, pts, nrm, dif, tape, out);
-}
-
-#endif  // !PTK_CONTRACT
-
 // Probe of the arithmetic helpers as THIS build compiles them (op 0: rcp_ieee, 1: rcp_ieee_any, 2: sqrt_ieee, 3: inv_length,
 // the normalisation's factor, 4 / 5: sin / cos of sincos_2pi): the tests hold the exact build against the host's IEEE results
 // and the oracle, the contracted builds against float64 within their documented error.
@@ -1564,117 +880,6 @@ __global__ void queue_init_kernel(unsigned* block, const QueueGeometry geo, cons
     if (t < QG_WORDS) ((int*)(block + 8 * PTK_QUEUE_STRIDE))[t] = w;
 }
 
-#if !PTK_CONTRACT
-// Uncached cameras (thin lens; pinhole with opacity textures): can ANY camera ray of this pixel reach the scene?  Every lens ray
-// of a pixel starts inside the aperture square around the camera position and passes through the pixel's focal point
-// (pathtracer.cpp:785-791; the camera-ray block of trace_kernel): origin o = cam + x right + y up with |x|, |y| <= aperture,
-// direction parallel to F - o.  Per axis that is o_k in [cam_k - h_k, cam_k + h_k], d_k in [F_k - cam_k - h_k, F_k - cam_k + h_k]
-// with h_k = aperture (|right_k| + |up_k|); taking the two intervals as independent (a superset of the bundle), the ray
-// parameters t >= 0 at which SOME such ray is inside the scene's bounding box on axis k form an interval given by two linear
-// inequalities; the pixel is dead - black for every sample, never traced, nothing stored - when the three intervals have no
-// common point.  Conservative by construction and by margin: the box is padded by 1e-4 of the scene's size and of the camera's
-// distance (Moeller-Trumbore accepts nothing measurably outside a triangle, and every triangle lies in the box), the intervals by
-// the float rounding of o, F and the normalised direction; evaluated in double, once per camera / frame / scene change.
-// Exact: bit-identical images with the cull on and off (tests/test_gpu_host_api.py::test_lens_cull_is_exact).
-__device__ bool lens_rays_may_reach_scene(const RenderParams& P, const float4 d0)
-{
-    double ext = 0.0, far_ = 0.0;
-    for (int k = 0; k < 3; k++)
-    {
-        ext = fmax(ext, (double)P.scene_hi[k] - (double)P.scene_lo[k]);
-        far_ = fmax(far_, fmax(fabs((double)P.scene_lo[k] - (double)P.cam_pos[k]), fabs((double)P.scene_hi[k] - (double)P.cam_pos[k])));
-    }
-    const double pad = 1e-4 * (ext + far_) + 1e-5;
-    const double ap = fabs((double)P.aperture) * 1.0001;
-    const float dir0[3] = { d0.x, d0.y, d0.z };
-    double tlo = 0.0, thi = 1e300;
-    bool feasible = true;
-    for (int k = 0; k < 3; k++)
-    {
-        const float Ff = P.cam_pos[k] + dir0[k] * P.focal_dist;            // the focal point as the camera-ray block computes it
-        const double oc = (double)P.cam_pos[k], F = (double)Ff;
-        const double h = ap * (fabs((double)P.cam_right[k]) + fabs((double)P.cam_up[k])) + 1e-6 * fabs(oc);
-        const double dc = F - oc, hd = h + 1e-6 * (fabs(F) + fabs(oc) + fabs(dc));
-        const double lo = (double)P.scene_lo[k] - pad, hi = (double)P.scene_hi[k] + pad;
-        // the smallest coordinate any ray of the bundle has at parameter t must not exceed hi, the largest not fall short of lo
-        const double a1 = (oc - h) - hi, b1 = dc - hd;                     // a1 + t b1 <= 0
-        const double a2 = lo - (oc + h), b2 = -(dc + hd);                  // a2 + t b2 <= 0
-        if (b1 > 0.0) thi = fmin(thi, -a1 / b1); else if (b1 < 0.0) tlo = fmax(tlo, -a1 / b1); else if (a1 > 0.0) feasible = false;
-        if (b2 > 0.0) thi = fmin(thi, -a2 / b2); else if (b2 < 0.0) tlo = fmax(tlo, -a2 / b2); else if (a2 > 0.0) feasible = false;
-    }
-    return feasible && tlo <= thi * (1.0 + 1e-9) + 1e-12;
-}
-
-// Which pixels of every owned 8x8 quadrant need tracing: on the image, and - when the camera ray's closest hit is
-// cached - not a miss (pathtracer.cpp:550: such a pixel is black for every sample); uncached cameras: not a pixel whose
-// lens rays all miss the scene's bounds (above).  One wave per quadrant.
-__global__ __launch_bounds__(PTK_BLOCK) void live_mask_kernel(const RenderParams P, unsigned long long* mask, int num_subtiles)
-{
-    const int subtile = blockIdx.x * (PTK_BLOCK / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (subtile >= num_subtiles) return;
-    const int owned = subtile >> 2, quad = subtile & 3;
-    const int tile = owned * P.world + P.rank;
-    bool live = false;
-    if (tile < P.num_tiles)
-    {
-        const int ty = tile / P.tiles_x, tx = (tile % P.tiles_x + P.tiles_x - (3 * ty) % P.tiles_x) % P.tiles_x;
-        const int px = tx * PTK_TILE + (quad & 1) * 8 + (lane & 7), py = ty * PTK_TILE + (quad >> 1) * 8 + (lane >> 3);
-        live = px < P.width && py < P.height;
-        if (live && P.primary_hit) live = __float_as_int(P.primary_hit[(size_t)py * P.width + px].x) != PTK_NOHIT;
-        else if (live && P.lens_cull) live = lens_rays_may_reach_scene(P, P.primary[(size_t)py * P.width + px]);
-    }
-    const unsigned long long m = __ballot(live);
-    if (lane == 0) mask[subtile] = m;
-}
-
-// Ordered list of the quadrants that have live pixels (single workgroup: a few hundred thousand quadrants at most).
-__global__ __launch_bounds__(1024) void live_compact_kernel(const unsigned long long* mask, int num_subtiles, unsigned* list, unsigned* count)
-{
-    __shared__ unsigned wave_total[16];
-    __shared__ unsigned base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) base = 0;
-    __syncthreads();
-    for (int s0 = 0; s0 < num_subtiles; s0 += 1024)
-    {
-        const int sidx = s0 + t;
-        const bool live = sidx < num_subtiles && mask[sidx] != 0ull;
-        const unsigned long long b = __ballot(live);
-        if (lane == 0) wave_total[wave] = (unsigned)__popcll(b);
-        __syncthreads();
-        unsigned before = base;
-        for (int w = 0; w < wave; w++) before += wave_total[w];
-        if (live) list[before + (unsigned)__popcll(b & ((1ull << lane) - 1ull))] = (unsigned)sidx;
-        __syncthreads();
-        if (t == 0) { unsigned sum = 0; for (int w = 0; w < 16; w++) sum += wave_total[w]; base += sum; }
-        __syncthreads();
-    }
-    if (t == 0) *count = base;
-}
-
-__global__ __launch_bounds__(PTK_BLOCK) void pixel_rng_kernel(uint32_t seed_lo, uint32_t seed_hi, int n, uint2* out)
-{
-    const int i = blockIdx.x * PTK_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t pkey = pixel_key(seed_lo, seed_hi, (uint32_t)i);
-    out[i] = make_uint2(pkey, (hash32(pkey ^ 0x9E3779B9u) << 1) | 1u);
-}
-void launch_pixel_rng(uint32_t seed_lo, uint32_t seed_hi, int n, uint2* out, hipStream_t stream)
-{
-    if (n > 0) hipLaunchKernelGGL(pixel_rng_kernel, dim3((n + PTK_BLOCK - 1) / PTK_BLOCK), dim3(PTK_BLOCK), 0, stream, seed_lo, seed_hi, n, out);
-}
-
-void launch_live_list(const RenderParams& p, int num_subtiles, unsigned long long* mask, unsigned* list, unsigned* count, hipStream_t stream)
-{
-    if (num_subtiles <= 0) return;
-    const int per_block = PTK_BLOCK / 64;
-    hipLaunchKernelGGL(live_mask_kernel, dim3((num_subtiles + per_block - 1) / per_block), dim3(PTK_BLOCK), 0, stream, p, mask, num_subtiles);
-    hipLaunchKernelGGL(live_compact_kernel, dim3(1), dim3(1024), 0, stream, (const unsigned long long*)mask, num_subtiles, list, count);
-}
-
-#endif  // !PTK_CONTRACT
-
 void launch_trace(const RenderParams& p0, int num_subtiles, int resident_waves, hipStream_t stream, bool stats)
 {
     if (num_subtiles <= 0) return;
@@ -1710,82 +915,6 @@ void launch_trace(const RenderParams& p0, int num_subtiles, int resident_waves, 
     else if (flat) hipLaunchKernelGGL((trace_kernel<false, true, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else hipLaunchKernelGGL((trace_kernel<false, false, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
 }
-
-#if !PTK_CONTRACT
-// ---- multi-GPU exchange step: packed form of the float accumulator ---------------------------------
-// Packed layout of rank r of `world` (include/ptk.h ptk_packed_layout): its owned tiles in ascending tile order, 768
-// floats each = the tile's 16 x 16 pixels row-major from the tile's top-left, RGB; pixels off the image hold 0.
-// pack: accumulator -> packed (one workgroup per owned tile, 768 B contiguous per wave-store);
-// unpack: the packed buffers of ALL ranks (rank r's starts at float offset base[r]) -> full image, one workgroup per tile.
-struct ExchangeBases { long long base[PTK_MAX_RANKS]; };
-
-__global__ __launch_bounds__(PTK_BLOCK) void pack_owned_kernel(const float* __restrict__ accum, float* __restrict__ packed, int width, int height,
-                                                               int tiles_x, int num_tiles, int rank, int world)
-{
-    const int owned = blockIdx.x, tile = owned * world + rank;
-    if (tile >= num_tiles) return;
-    const int ty = tile / tiles_x, tx = (tile % tiles_x + tiles_x - (3 * ty) % tiles_x) % tiles_x;
-    const int p = threadIdx.x, px = tx * PTK_TILE + (p & 15), py = ty * PTK_TILE + (p >> 4);
-    float r = 0.0f, g = 0.0f, b = 0.0f;
-    if (px < width && py < height)
-    {
-        const size_t a = ((size_t)(height - 1 - py) * width + px) * 3;
-        r = accum[a]; g = accum[a + 1]; b = accum[a + 2];
-    }
-    float* o = packed + (size_t)owned * (PTK_BLOCK * 3) + p * 3;
-    o[0] = r; o[1] = g; o[2] = b;
-}
-
-__global__ __launch_bounds__(PTK_BLOCK) void unpack_all_kernel(const float* __restrict__ packed, const ExchangeBases bases, float* __restrict__ image,
-                                                               int width, int height, int tiles_x, int num_tiles, int world)
-{
-    const int tile = blockIdx.x;
-    if (tile >= num_tiles) return;
-    const int rank = tile % world, owned = tile / world;
-    const int ty = tile / tiles_x, tx = (tile % tiles_x + tiles_x - (3 * ty) % tiles_x) % tiles_x;
-    const int p = threadIdx.x, px = tx * PTK_TILE + (p & 15), py = ty * PTK_TILE + (p >> 4);
-    if (px >= width || py >= height) return;
-    const float* in = packed + bases.base[rank] + (size_t)owned * (PTK_BLOCK * 3) + p * 3;
-    const size_t a = ((size_t)(height - 1 - py) * width + px) * 3;
-    image[a] = in[0]; image[a + 1] = in[1]; image[a + 2] = in[2];
-}
-
-void launch_pack_owned(const float* accum, float* packed, int width, int height, int rank, int world, hipStream_t stream)
-{
-    const int tiles_x = (width + PTK_TILE - 1) / PTK_TILE, num_tiles = tiles_x * ((height + PTK_TILE - 1) / PTK_TILE);
-    const int owned = num_tiles <= rank ? 0 : (num_tiles - rank + world - 1) / world;
-    if (owned > 0) hipLaunchKernelGGL(pack_owned_kernel, dim3(owned), dim3(PTK_BLOCK), 0, stream, accum, packed, width, height, tiles_x, num_tiles, rank, world);
-}
-void launch_unpack_all(const float* packed, const long long* bases, float* image, int width, int height, int world, hipStream_t stream)
-{
-    const int tiles_x = (width + PTK_TILE - 1) / PTK_TILE, num_tiles = tiles_x * ((height + PTK_TILE - 1) / PTK_TILE);
-    ExchangeBases b = {};
-    for (int r = 0; r < world && r < PTK_MAX_RANKS; r++) b.base[r] = bases[r];
-    hipLaunchKernelGGL(unpack_all_kernel, dim3(num_tiles), dim3(PTK_BLOCK), 0, stream, packed, b, image, width, height, tiles_x, num_tiles, world);
-}
-
-void launch_accumulate(const RenderParams& p, int owned_tiles, hipStream_t stream)
-{
-    if (owned_tiles <= 0) return;
-    hipLaunchKernelGGL(accumulate_kernel, dim3(owned_tiles), dim3(PTK_BLOCK), 0, stream, p);
-}
-void launch_primary_hits(const RenderParams& p, float4* out, float4* out_rd, hipStream_t stream)
-{
-    int n = p.width * p.height;
-    hipLaunchKernelGGL(primary_hits_kernel, dim3((n + PTK_BLOCK - 1) / PTK_BLOCK), dim3(PTK_BLOCK), 0, stream, p, out, out_rd);
-}
-void launch_primary(const PrimaryParams& p, hipStream_t stream)
-{
-    int threads = 64;
-    hipLaunchKernelGGL(primary_dirs_kernel, dim3((p.height + threads - 1) / threads), dim3(threads), 0, stream, p);
-}
-void launch_probe(const ProbeParams& p, hipStream_t stream)
-{
-    if (p.n <= 0) return;
-    hipLaunchKernelGGL(probe_hits_kernel, dim3((p.n + PTK_BLOCK - 1) / PTK_BLOCK), dim3(PTK_BLOCK), 0, stream, p);
-}
-
-#endif  // !PTK_CONTRACT
 
 #if PTK_CONTRACT
 }  // namespace fma / fast

@@ -459,15 +459,20 @@ def test_dropin_header_compiles_and_links_natively(tmp_path):
 def test_committed_counter_files_belong_to_the_kernels_as_built():
     """profiles/traffic_C*.json (what bench.py's roofline.traffic is read from) and profiles/r04/pmc_sq_*.json carry the sha256
     of the kernel sources they were collected for; bench.py ignores them once the sources change.  This keeps the committed
-    set honest: whoever edits csrc/ptk_kernels.hip or csrc/ptk_device.h re-runs tools/profile_round.sh (or sees this fail)."""
+    set honest: whoever edits csrc/ptk_kernels.hip or csrc/ptk_device.h re-runs tools/profile_round.sh (or sees this fail).  The
+    shared device functions the trace kernels are built from live in csrc/ptk_device_fn.h, which that hash does not cover: the
+    files carry its sha256 as kernel_header_sha256, held to the file in the tree in the same way."""
     import glob
     import importlib.util
     import json
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
     sha = bench.kernel_source_sha256()
+    import hashlib
+    header_sha = hashlib.sha256(open(os.path.join(ROOT, "pbrpathtracer_amd", "csrc", "ptk_device_fn.h"), "rb").read()).hexdigest()
     files = sorted(glob.glob(os.path.join(ROOT, "profiles", "traffic_C*.json")) + glob.glob(os.path.join(ROOT, "profiles", "r04", "pmc_sq_trace_kernel_C*.json")) +
                    glob.glob(os.path.join(ROOT, "profiles", "r04", "overlap_trace_C2.json")))
     assert len(files) >= 8
     for f in files:
         assert json.load(open(f)).get("kernel_source_sha256") == sha, f + " was collected for other kernel sources"
+        assert json.load(open(f)).get("kernel_header_sha256") == header_sha, f + " was collected for another csrc/ptk_device_fn.h"

@@ -37,7 +37,16 @@ def kernel_source_sha256():
     return h.hexdigest()
 
 
+def kernel_header_sha256():
+    """... and to the shared device functions the trace kernels are built from (csrc/ptk_device_fn.h), which bench.py's hash does not cover"""
+    f = os.path.join(src, "kernel_header_sha256.txt")
+    if os.path.exists(f):
+        return open(f).read().strip()
+    return hashlib.sha256(open(os.path.join(ROOT, "pbrpathtracer_amd", "csrc", "ptk_device_fn.h"), "rb").read()).hexdigest()
+
+
 SHA = kernel_source_sha256()
+HSHA = kernel_header_sha256()
 TRACE = "trace_kernel<false"
 
 
@@ -91,7 +100,7 @@ for c in ("C2", "C4"):
                        "all_trace_kernel_dispatches_ms": [[k.split("(")[0], round(d, 4)] for k, d in ds],
                        "full_size_launches_ms": full, "full_size_mean_ms": round(sum(full) / max(1, len(full)), 4),
                        "note": "under the profiler a launch runs a few per cent longer than bench.py's own HIP-event timing of the same launch (roofline.kernel_ms_isolated)",
-                       "kernel_source_sha256": SHA}, open(os.path.join(dst, f"kernel_trace_launches_{c}.json"), "w"), indent=1)
+                       "kernel_source_sha256": SHA, "kernel_header_sha256": HSHA}, open(os.path.join(dst, f"kernel_trace_launches_{c}.json"), "w"), indent=1)
 
 # the DEFAULT (overlap = 1) C2 run: start / end of consecutive trace_kernel launches - how much of a launch's tail the next
 # launch covers, i.e. why ms_per_step < the isolated kernel time
@@ -118,7 +127,7 @@ if len(rows) > 8:
           "mean_start_to_start_ms": round(sum(p["next_start_after_this_start_ms"] for p in steady) / len(steady), 4),
           "mean_overlap_ms": round(sum(p["overlap_ms"] for p in steady) / len(steady), 4),
           "note": "consecutive launches alternate between two streams; launch k+1 starts while launch k's last waves (its longest paths) are still running: "
-                  "start-to-start (= ms_per_step) is shorter than a launch by the mean overlap", "kernel_source_sha256": SHA, "pairs_head": pairs[:12]}
+                  "start-to-start (= ms_per_step) is shorter than a launch by the mean overlap", "kernel_source_sha256": SHA, "kernel_header_sha256": HSHA, "pairs_head": pairs[:12]}
     json.dump(ov, open(os.path.join(dst, "overlap_trace_C2.json"), "w"), indent=1)
     print("overlap C2:", {k: v for k, v in ov.items() if k.startswith("mean") or k == "full_launches"})
 for name in ("valu_calibration.json", "gather_ceiling.json", "exact_math.json"):
@@ -138,7 +147,7 @@ for c in ("C2", "C3", "C4", "C5"):
     hit, miss = mean_of(ds["tcc"], "TCC_HIT_sum"), mean_of(ds["tcc"], "TCC_MISS_sum")
     acc = {n: full_launches(dispatches(os.path.join(base, p), "accumulate_kernel")) for n, p in (("fetch", "p1"), ("write", "p2"))}
     out = {
-        "config": c, "spp": SPP[c], "n_gpus": 1, "kernel": ds["fetch"][0]["kernel"], "kernel_source_sha256": SHA,
+        "config": c, "spp": SPP[c], "n_gpus": 1, "kernel": ds["fetch"][0]["kernel"], "kernel_source_sha256": SHA, "kernel_header_sha256": HSHA,
         "hbm_bytes_per_launch": int((2 * fetch + write) * 1024),
         "fetch_size_kib": fetch, "write_size_kib": write,
         "launches_averaged": len(ds["fetch"]), "kernel_ms_under_profiler": mean_of(ds["fetch"], "ms"),
@@ -210,6 +219,7 @@ for c in ("C2", "C4", "C5"):
                                     "min/max, conversions, integer multiplies, f64) at the measured half rate.  The truth lies between; the "
                                     "kernels' compares / selects / conversions put it near the high figure.")
     m["kernel_source_sha256"] = SHA
+    m["kernel_header_sha256"] = HSHA
     m["units"] = "SQ_*_CYCLES / SQ_WAIT_* / SQ_ACTIVE_* are in quad-cycles summed over waves; ms is the kernel time under the profiler"
     json.dump(m, open(os.path.join(dst, f"pmc_sq_trace_kernel_{c}.json"), "w"), indent=1)
     print(c, {k: (round(v, 3) if isinstance(v, float) else v) for k, v in m.items() if k[0].islower() and k not in ("classes", "valu_pipe_busy_note", "units", "kernel")})

@@ -3,7 +3,7 @@
 #   1. on the GPU box, from the repo root:   gpurun --timeout 1200 -- 'bash tools/profile_round.sh r04 [what ...]'
 #        what = bench ktrace traffic sq class mem   (default: bench ktrace traffic sq class); raw output -> gpurun_out/prof_r04/
 #   2. here:                                  python tools/profile_collect.py gpurun_out/prof_r04 profiles/r04
-#        summaries (bench lines, kernel-stats CSVs, traffic / SQ / class counters), each tied to the kernel sources by sha256
+#        summaries (bench lines, kernel-stats CSVs, traffic / SQ / class counters), each tied to the kernel sources and to ptk_device_fn.h by sha256
 # then `python tools/design_table.py profiles/r04` prints DESIGN.md 7's tables (incl. registers / LDS / spills read from libptk.so).
 # Every rocprofv3 call profiles `python3 bench.py` directly (no shell / env hop after `--`), counters in passes of their
 # own (--pmc only, no trace flags), each pass into its own directory.
@@ -26,6 +26,7 @@ if has bench; then
   python3 $ROOT/bench.py --config C5 --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/bench_C5.json 2> $OUT/bench_C5.err
 fi
 python3 -c "import sys; sys.path.insert(0, '$ROOT'); import bench; print(bench.kernel_source_sha256())" > $OUT/kernel_source_sha256.txt
+sha256sum $ROOT/pbrpathtracer_amd/csrc/ptk_device_fn.h | cut -d' ' -f1 > $OUT/kernel_header_sha256.txt     # the shared device functions: not in bench.py's hash
 if has ktrace; then
   # the DEFAULT run (overlap = 1): consecutive launches on two streams, for profiles/<round>/overlap_trace_C2.json
   timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d $OUT/ktrace_overlap_C2 -- python3 $ROOT/bench.py --config C2 --steps 40 --warmup 5 --full --no-cpu-baseline --no-other-configs --no-parity --no-contracted --no-interactive > $OUT/ktrace_overlap_C2.log 2>&1
