@@ -161,6 +161,12 @@ public:
     // The reference seeds one std::mt19937 from std::random_device (pathtracer.cpp:11); here the RNG
     // is counter-based and keyed on (seed, pixel, sample index), default seed 0.
     void SetSeed(uint64_t seed);
+    // Moves a loaded object: its triangles are staged again under `model` from the object-space data kept at LoadObject, bit for
+    // bit what LoadObject(file, model) stages.  Before BuildBVH() this changes what will be built.  After BuildBVH() the next
+    // RenderFrame() / RenderFeatures() / Pick() / RenderAdaptive() sends the object's triangle range to the device
+    // (ptk_update_geometry, include/ptk.h): records are rewritten and the BVH refitted in place, no rebuild.  The image is not
+    // reset (ResetImage() stays the caller's) and the light list stays BuildBVH's.  A bad id is ignored.
+    void SetObjectTransform(int objId, const glm::mat4& model);
     // EXPERIMENTAL (never executed: headless build boxes).  SetOutImage for a display path that stays on the GPU: the 8-bit image
     // (the layout of texData) is written into this OpenGL buffer object - the viewer's GL_PIXEL_UNPACK_BUFFER - instead of a host
     // buffer.  Call it on the thread whose OpenGL context is current (the viewer's GUI thread): the buffer is registered HERE

@@ -126,6 +126,44 @@ int ptk_upload_scene(ptk_ctx* ctx, const ptk_scene_desc* scene);
  * it.  Rewrites the material table and the lights' colours in place; counts and texture bindings must be the uploaded ones. */
 int ptk_update_materials(ptk_ctx* ctx, int32_t num_materials, const ptk_material* materials);
 
+/* Geometry edits after BuildBVH (no counterpart in the reference, whose triangles are frozen by BuildBVH): replaces the world-space
+ * vertices, vertex normals and (normal, tangent, bitangent) frames of triangles [first_tri, first_tri + num_tris) of the uploaded
+ * scene - [num_tris][9] floats each, the layouts of ptk_scene_desc - and REFITS the resident BVH: the tree keeps its links, leaf
+ * order and traversal-stack need, every child box is recomputed bottom-up from the moved vertices with the builders' own padding
+ * and quantiser.  Closest hits do not depend on the tree, so the next render is bit for bit that of a fresh ptk_upload_scene of the
+ * moved arrays; only its speed depends on how far the triangles strayed from the boxes the builder chose (ptk_geometry_info).
+ * Unchanged: the triangle count, materials, uvs, smoothing bits, textures and the light LIST (lights inside the range move with
+ * their triangles).  normals and tbn may both be NULL to move vertices only; one of them alone is PTK_ERR_BAD_ARG, as are a call
+ * before ptk_upload_scene, a range outside the scene and a null verts with num_tris > 0; num_tris == 0 is PTK_OK and does nothing.
+ * A coordinate that is not finite or reaches 2^61 gives PTK_ERR_LIMIT and leaves the resident scene exactly as it was.
+ * Afterwards the triangle, shading and light records, the scene bound and extent are what ptk_upload_scene of the moved arrays
+ * would have put there.  Like a material edit, an update resets neither the accumulator, the sample count, the adaptive state nor
+ * the feature planes: that stays the caller's ptk_reset.
+ * Ordering: the update takes effect behind every render already queued and ahead of every later one.  The call stages the
+ * arrays and reduces the new bounds on an internal stream and waits for THAT (about 32 bytes come back); renders queued since
+ * the previous update are not waited for.  The arrays are the caller's again when the call returns.
+ *   ptk_update_geometry:        host arrays.
+ *   ptk_update_geometry_device: memory of this context's GPU (a torch tensor, hipMalloc); its contents must be complete when
+ *                               the call is made (they are read on an internal stream, not the caller's).
+ * Memory: ptk_upload_scene keeps the world-space vertices resident for this, 36 B per triangle beside the 160 B of records (a
+ * refit needs the exact second and third vertex, which the intersection records hold only as edges); the first update adds
+ * 4 B per triangle and 36 B per node of tables, and the staging buffer of the largest update so far (36 or 108 B per triangle).
+ * The first update after an upload also downloads the node links once (and waits for the stream) to schedule the levels. */
+int ptk_update_geometry(ptk_ctx* ctx, int32_t first_tri, int32_t num_tris, const float* verts, const float* normals, const float* tbn);
+int ptk_update_geometry_device(ptk_ctx* ctx, int32_t first_tri, int32_t num_tris, const float* d_verts, const float* d_normals, const float* d_tbn);
+/* updates since the last ptk_upload_scene; whether the resident tree is a refitted one; the SAH cost of the tree as built and as
+ * it is now: the sum over nodes of child half-area / root half-area of the padded float boxes, the builders' units.  Nothing acts on
+ * the ratio: it is what a caller needs to decide when to call ptk_upload_scene again.  Asking for a cost waits for the stream.
+ * "As built" is taken by the refit's own pass over the uploaded vertices, writing no node: the cost of the tree a refit of the
+ * unmoved scene gives.  That is the builder's tree, box for box, except below a parity split of the device builder - triangles with
+ * identical centroids -, whose leaves keep their parent's bounds where the refit's are the triangles' own: there sah_built is a
+ * little below the cost of the boxes the walk tests until the first update tightens them.
+ * Any output pointer may be NULL. */
+int ptk_geometry_info(ptk_ctx* ctx, uint32_t* updates, int* refitted, double* sah_built, double* sah_now);
+/* measurement hook (tools/refit_timing.py), not part of the feature: HIP-event times of the last update,
+ * ms3 = { staging copies + bounds reduction, record repack, refit }; waits for the update */
+int ptk_geometry_timing(ptk_ctx* ctx, float* ms3);
+
 /* SetCamera + SetProjection + SetCameraFocalDist + SetCameraAperture (pathtracer.cpp:333-360).
  * dir/up are normalised and focal/fovy clamped exactly as the reference setters do. */
 int ptk_set_camera(ptk_ctx* ctx, const float pos[3], const float dir[3], const float up[3],

@@ -22,6 +22,8 @@ void pth_destroy(pth_tracer* t);
 
 /* PathTracer API */
 void pth_load_object(pth_tracer* t, const char* file, const float model_colmajor[16]);
+/* SetObjectTransform (extension): stage object `obj` again under another matrix; after BuildBVH the next render call refits */
+void pth_set_object_transform(pth_tracer* t, int obj, const float model_colmajor[16]);
 void pth_set_material(pth_tracer* t, int obj, int elem, const float m15[15]);  /* type, diffuse3, specular3, emissive3, I, roughness, reflectiveness, translucency, ior */
 void pth_set_texture(pth_tracer* t, int obj, int elem, int slot, const char* file); /* slot 0..5: diffuse normal emissive roughness metallic opacity */
 void pth_build_bvh(pth_tracer* t);

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ptk_device.h"
+#include "bvh_quantise.h"
 
 namespace ptk {
 namespace {
@@ -479,7 +480,7 @@ __global__ __launch_bounds__(kThreads) void collapse_kernel(const BNode* __restr
     }
     atomicMax(&counters[CNT_STACK], (uint32_t)(it.used + max(nc, 1) - 1));
     // padded child boxes (the host pads every triangle box by `pad` before building; min / max commute with that)
-    float cmn[4][3], cmx[4][3], umn[3] = { INFINITY, INFINITY, INFINITY }, umx[3] = { -INFINITY, -INFINITY, -INFINITY };
+    float cmn[4][3], cmx[4][3], umn[3], umx[3];
     int32_t link[4];
     // the interior children of one node get CONSECUTIVE numbers (one counter bump per node, not per child): a ray that enters
     // two of them finds the second record in the 128-byte line the first brought in (or in its neighbour)
@@ -491,11 +492,7 @@ __global__ __launch_bounds__(kThreads) void collapse_kernel(const BNode* __restr
         link[k] = NODE_EXIT;
         if (k >= nc) continue;
         const BNode& c = nodes[child[k]];
-        for (int a = 0; a < 3; a++)
-        {
-            cmn[k][a] = c.mn[a] - pad; cmx[k][a] = c.mx[a] + pad;
-            umn[a] = fminf(umn[a], cmn[k][a]); umx[a] = fmaxf(umx[a], cmx[k][a]);
-        }
+        for (int a = 0; a < 3; a++) { cmn[k][a] = c.mn[a] - pad; cmx[k][a] = c.mx[a] + pad; }
         if (c.left < 0) link[k] = ~((c.first << 3) | (c.count - 1));
         else
         {
@@ -505,31 +502,7 @@ __global__ __launch_bounds__(kThreads) void collapse_kernel(const BNode* __restr
             pos++;
         }
     }
-    float scale[3];
-    uint32_t lo[3] = { 0, 0, 0 }, hi[3] = { 0, 0, 0 };
-    for (int a = 0; a < 3; a++)
-    {
-        const double ext = (double)umx[a] - (double)umn[a];
-        float s = (float)(ext / 255.0 * (1.0 + 1e-6));
-        if (!(s > 1e-30f)) s = 1e-30f;
-        while ((double)umn[a] + 255.0 * (double)s < (double)umx[a]) s = nextafterf(s, INFINITY);
-        scale[a] = s;
-        for (int k = 0; k < 4; k++)
-        {
-            if (k >= nc) { lo[a] |= 255u << (8 * k); continue; }          // empty slot: inverted box
-            const double o = umn[a], sd = s;
-            int ql = (int)floor(((double)cmn[k][a] - o) / sd), qh = (int)ceil(((double)cmx[k][a] - o) / sd);
-            ql = min(max(ql, 0), 255); qh = min(max(qh, 0), 255);
-            while (ql > 0 && o + ql * sd > (double)cmn[k][a]) ql--;
-            while (qh < 255 && o + qh * sd < (double)cmx[k][a]) qh++;
-            lo[a] |= (uint32_t)ql << (8 * k); hi[a] |= (uint32_t)qh << (8 * k);
-        }
-    }
-    float4* o4 = out_nodes + (size_t)(wide_start + q) * NODE_F4;
-    o4[0] = make_float4(umn[0], umn[1], umn[2], scale[0]);
-    o4[1] = make_float4(scale[1], scale[2], __int_as_float(link[0]), __int_as_float(link[1]));
-    o4[2] = make_float4(__int_as_float(link[2]), __int_as_float(link[3]), __uint_as_float(lo[0]), __uint_as_float(lo[1]));
-    o4[3] = make_float4(__uint_as_float(lo[2]), __uint_as_float(hi[0]), __uint_as_float(hi[1]), __uint_as_float(hi[2]));
+    emit_wide_node(cmn, cmx, nc, link, out_nodes + (size_t)(wide_start + q) * NODE_F4, umn, umx);        // bvh_quantise.h
 }
 
 inline unsigned blocks_for(long long n, int per) { return (unsigned)std::max<long long>(1, (n + per - 1) / per); }

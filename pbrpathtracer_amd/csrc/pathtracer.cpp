@@ -429,6 +429,15 @@ struct PathTracer::Impl {
     // edits after BuildBVH: the reference's triangles point into the loaded materials, so they take effect at the next
     // RenderFrame() without a rebuild (pathtracer.cpp:250-258); the light list stays as BuildBVH collected it (:267-273)
     bool materials_dirty = false, textures_dirty = false, built_once = false;
+    // SetObjectTransform: the object-space data of every loaded object and where its triangles were staged; after BuildBVH the
+    // moved objects wait here for the next render call, which sends their ranges to ptk_update_geometry
+    struct ObjectSource
+    {
+        ObjData obj; size_t first = 0, count = 0;
+        glm::mat4 model, resident;                  // the matrix the triangles are staged under; the one the device last accepted
+    };
+    std::vector<ObjectSource> sources;
+    std::vector<uint8_t> geometry_dirty;            // per object
     std::vector<int32_t> built_lights;
     bool camera_dirty = true, frame_dirty = true;
 
@@ -478,33 +487,22 @@ PathTracer::~PathTracer()
     delete m;
 }
 
-// pathtracer.cpp:41-145
-void PathTracer::LoadObject(const std::string& file, const glm::mat4& model)
+// The staging of LoadObject (pathtracer.cpp:64-141): every triangle of every shape of `obj` under `model`, appended to `out` in
+// file order.  Which faces are dropped (a corner that names a vertex the file does not have) does not depend on the matrix, so
+// staging the same data again under another matrix gives the same count in the same order (SetObjectTransform).
+static void stage_object(const ObjData& obj, const glm::mat4& model, int objectId, std::vector<StagedTriangle>& out)
 {
-    ObjData obj;
-    if (!load_obj(file, obj)) return;                      // parse failure is silently ignored (:47)
-
-    int nameStartIndex = (int)file.find_last_of('/') + 1;
-    if (nameStartIndex > (int)file.size() - 1) nameStartIndex = 0;
-    size_t nameEnd = file.find_last_of(".");
-    int nameEndIndex = nameEnd == std::string::npos ? (int)file.size() - 1 : (int)nameEnd;
-    // (a dot that lies BEFORE the file name - "./mesh", "dir.v2/mesh" - makes the count negative: as a size_t it takes the rest, :56)
-    std::string objName = file.substr((size_t)nameStartIndex, (size_t)(nameEndIndex - nameStartIndex));
-    PathTracerLoader::Object object(objName);
-
     const bool has_normals = !obj.normals.empty();
     const bool has_uvs = !obj.texcoords.empty();
     const int nv = (int)obj.positions.size() / 3, nn = (int)obj.normals.size() / 3, nt = (int)obj.texcoords.size() / 2;
     for (size_t i = 0; i < obj.shapes.size(); i++)
     {
-        object.elements.push_back(PathTracerLoader::Element(obj.shapes[i].name));
         const ObjShape& sh = obj.shapes[i];
         const size_t ntri = std::min(sh.indices.size() / 3, sh.smoothing.size());
-        const size_t first = m->triangles.size();
-        m->triangles.resize(first + ntri);
+        const size_t first = out.size();
+        out.resize(first + ntri);
         std::vector<uint8_t> okv(ntri, 1);
-        const int objectId = (int)m->objects.size();
-        StagedTriangle* dst = m->triangles.data() + first;
+        StagedTriangle* dst = out.data() + first;
         // every triangle is staged independently (x-negation, model transform, v-flip, Triangle::Init): all cores
         parallel_for(ntri, [&](size_t tj) {
             const size_t j = tj * 3;
@@ -539,8 +537,33 @@ void PathTracer::LoadObject(const std::string& file, const glm::mat4& model)
         size_t kept = 0;
         for (size_t tj = 0; tj < ntri; tj++)
             if (okv[tj]) { if (kept != tj) dst[kept] = dst[tj]; kept++; }
-        m->triangles.resize(first + kept);
+        out.resize(first + kept);
     }
+}
+
+// pathtracer.cpp:41-145
+void PathTracer::LoadObject(const std::string& file, const glm::mat4& model)
+{
+    ObjData obj;
+    if (!load_obj(file, obj)) return;                      // parse failure is silently ignored (:47)
+
+    int nameStartIndex = (int)file.find_last_of('/') + 1;
+    if (nameStartIndex > (int)file.size() - 1) nameStartIndex = 0;
+    size_t nameEnd = file.find_last_of(".");
+    int nameEndIndex = nameEnd == std::string::npos ? (int)file.size() - 1 : (int)nameEnd;
+    // (a dot that lies BEFORE the file name - "./mesh", "dir.v2/mesh" - makes the count negative: as a size_t it takes the rest, :56)
+    std::string objName = file.substr((size_t)nameStartIndex, (size_t)(nameEndIndex - nameStartIndex));
+    PathTracerLoader::Object object(objName);
+
+    for (size_t i = 0; i < obj.shapes.size(); i++) object.elements.push_back(PathTracerLoader::Element(obj.shapes[i].name));
+    Impl::ObjectSource src;
+    src.first = m->triangles.size();
+    stage_object(obj, model, (int)m->objects.size(), m->triangles);
+    src.count = m->triangles.size() - src.first;
+    src.obj = std::move(obj);
+    src.model = src.resident = model;
+    m->sources.push_back(std::move(src));
+    m->geometry_dirty.push_back(0);
     m->objects.push_back(object);
     m->scene_uploaded = false;
 }
@@ -582,6 +605,8 @@ void PathTracer::BuildBVH()
     m->built_lights = fs.lights;
     m->built_once = m->built_once || rc == PTK_OK;
     m->materials_dirty = m->textures_dirty = false;
+    std::fill(m->geometry_dirty.begin(), m->geometry_dirty.end(), (uint8_t)0);
+    if (rc == PTK_OK) for (auto& src : m->sources) src.resident = src.model;
 }
 
 void PathTracer::ResetImage() { m->need_reset = true; }                // :276-279
@@ -590,6 +615,7 @@ void PathTracer::ClearScene()                                           // :281-
 {
     m->triangles.clear();
     m->objects.clear();
+    m->sources.clear(); m->geometry_dirty.clear();
     for (auto t : m->textures) delete t;
     m->textures.clear();
     m->scene_uploaded = false;
@@ -651,6 +677,40 @@ void PathTracer::RenderFrame() { RenderFrames(1); }                    // :741-8
 static bool prepare_render(PathTracer::Impl* m, GLubyte*& out_img, unsigned& out_gl, void*& out_dev)
 {
     int rc;
+    if (std::find(m->geometry_dirty.begin(), m->geometry_dirty.end(), (uint8_t)1) != m->geometry_dirty.end())
+    {
+        // SetObjectTransform after BuildBVH: one ptk_update_geometry per contiguous run of moved objects' triangles.  An update
+        // the device layer refuses (a coordinate out of bounds) leaves the resident scene unmoved and its text in LastError();
+        // the run's objects are then staged again under the matrices the device last accepted, so that StagedScene() and any
+        // later re-upload (a texture edit) hold what is rendered.  (Ahead of the material / texture edits for that reason.)
+        const size_t no = m->sources.size();
+        for (size_t o = 0; o < no;)
+        {
+            if (!m->geometry_dirty[o]) { o++; continue; }
+            const size_t first = m->sources[o].first, o0 = o;
+            size_t end = first;
+            while (o < no && m->geometry_dirty[o] && m->sources[o].first == end) { end += m->sources[o].count; m->geometry_dirty[o++] = 0; }
+            const size_t n = end - first;
+            std::vector<float> v(n * 9), nn(n * 9), tb(n * 9);
+            for (size_t i = 0; i < n; i++)
+            {
+                const StagedTriangle& t = m->triangles[first + i];
+                for (int k = 0; k < 3; k++) for (int a = 0; a < 3; a++) { v[i * 9 + k * 3 + a] = t.v[k][a]; nn[i * 9 + k * 3 + a] = t.n[k][a]; }
+                for (int a = 0; a < 3; a++) { tb[i * 9 + a] = t.normal[a]; tb[i * 9 + 3 + a] = t.tangent[a]; tb[i * 9 + 6 + a] = t.bitangent[a]; }
+            }
+            rc = ptk_update_geometry(m->ctx, (int32_t)first, (int32_t)n, v.data(), nn.data(), tb.data());
+            m->note(rc);
+            for (size_t k = o0; k < o; k++)
+            {
+                PathTracer::Impl::ObjectSource& src = m->sources[k];
+                if (rc == PTK_OK) { src.resident = src.model; continue; }
+                std::vector<StagedTriangle> staged;
+                stage_object(src.obj, src.resident, (int)k, staged);
+                if (staged.size() == src.count) std::copy(staged.begin(), staged.end(), m->triangles.begin() + (ptrdiff_t)src.first);
+                src.model = src.resident;
+            }
+        }
+    }
     if (m->materials_dirty || m->textures_dirty)
     {
         // SetMaterial / Set...TextureForElement after BuildBVH: seen by this frame, as in the reference
@@ -805,6 +865,22 @@ void PathTracer::Exit() { if (m->ctx) ptk_request_exit(m->ctx); }      // :819-8
 
 // ---- extensions -----------------------------------------------------------------------------------------
 void PathTracer::SetSeed(uint64_t seed) { m->seed = seed; }
+// Stages the object's triangles again from the object-space data LoadObject kept, exactly as LoadObject(file, model) would have.
+// Before BuildBVH() that only changes what will be built; after it, the next render call moves the triangles on the device
+// (ptk_update_geometry: the BVH is refitted, not rebuilt).  The light list stays BuildBVH's.  A bad id is ignored.
+void PathTracer::SetObjectTransform(int objId, const glm::mat4& model)
+{
+    if (objId < 0 || objId >= (int)m->sources.size()) return;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const Impl::ObjectSource& src = m->sources[objId];
+    std::vector<StagedTriangle> staged;
+    stage_object(src.obj, model, objId, staged);
+    if (staged.size() != src.count || src.first + src.count > m->triangles.size()) return;
+    std::copy(staged.begin(), staged.end(), m->triangles.begin() + (ptrdiff_t)src.first);
+    m->sources[objId].model = model;
+    if (m->scene_uploaded) m->geometry_dirty[objId] = 1;
+    else m->sources[objId].resident = model;
+}
 // EXPERIMENTAL (built, its refusal tested, never executed: the GPU boxes are headless).  Registration talks to the OpenGL driver
 // through the CALLING thread's current context, so it happens here, in the setter the viewer's GUI thread calls - not inside
 // RenderFrame(), which the viewer runs on a thread without a context (PathTracerLoop, main.cpp:3665-3678).  The setter waits for a

@@ -25,6 +25,7 @@
 #include "ptk_device_fn.h"
 #include "ptk_adaptive.h"
 #include "ptk_features.h"
+#include "ptk_refit.h"
 
 using namespace ptk;
 
@@ -54,6 +55,25 @@ struct ptk_ctx {
     // FLAT scenes: each triangle's smoothing flag and material, for re-deciding scene_plain when the materials are edited
     std::vector<uint8_t> h_flat_smoothing;
     std::vector<int32_t> h_flat_material;
+    // geometry updates (ptk_update_geometry): the world-space vertices stay resident beside the records (a refit needs the exact
+    // v2, v3: fl(v1 + fl(v2 - v1)) is not v2); everything else is made by the first update and lives until the next upload
+    float* d_verts_res = nullptr;                // [num_tris][9]
+    int32_t* d_tri_pos = nullptr;                // triangle -> position of its record in the leaf order
+    int32_t* d_level_nodes = nullptr;            // node indices sorted by level, the root's level first
+    std::vector<int> level_start;                // [levels + 1] offsets into d_level_nodes
+    double* d_refit_partial = nullptr;           // one partial SAH sum per 256 nodes
+    float4* d_refit_side = nullptr;              // per node: union box + summed child half-area (ptk_refit.h)
+    float* d_geo_stage = nullptr; size_t geo_stage_floats = 0;     // staged verts | normals | tbn of the update in progress
+    uint32_t* d_geo_red = nullptr;               // GEO_RED_WORDS of the bounds reduction, then one double: the SAH cost
+    uint32_t* h_geo_red = nullptr;               // page-locked target of its read-back
+    hipStream_t geo_stream = nullptr;            // staging copies and the bounds reduction: the one host wait of an update is for this stream alone
+    // events of the newest update: [0] [1] around staging + bounds on geo_stream; [2] before the repack, [3] behind it, [4] behind
+    // the refit on the context's stream ([4] also orders the next update's staging behind this one's kernels)
+    hipEvent_t ev_geo_t[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    bool geo_done_recorded = false, lights_stale = false;          // lights_stale: h_lights lacks the vertices an update moved
+    uint32_t geo_updates = 0;
+    double sah_built = 0.0, sah_now = 0.0; bool sah_now_pending = false;
+    float bvh_pad = 0.0f;                        // the builders' box padding for the current scene extent
     bool scene_plain = false;           // plain_tables() of the staged scene: kept current by ptk_upload_scene and ptk_update_materials
     int opt_plain_kernel = 1;           // 0: plain scenes launch the generic FLAT kernel too (tests, A/B runs)
     int last_trace_variant = PTK_TRACE_NONE;     // of the newest trace launch (ptk_trace_variant)
@@ -387,6 +407,14 @@ void* feature_plane(ptk_ctx* c, int feature, size_t* bytes)
     return c->d_feat[feature];
 }
 
+// what the first geometry update derives from a tree's topology; dropped with the tree
+void free_geometry_cache(ptk_ctx* c)
+{
+    dfree(c->d_tri_pos); dfree(c->d_level_nodes); dfree(c->d_refit_side); dfree(c->d_refit_partial);
+    c->level_start.clear();
+    c->geo_updates = 0; c->sah_built = c->sah_now = 0.0; c->sah_now_pending = false;
+}
+
 void free_adaptive(ptk_ctx* c)
 {
     dfree(c->d_counts); dfree(c->d_moments); dfree(c->d_adapt_active); dfree(c->d_adapt_traced); dfree(c->d_adapt_list);
@@ -682,6 +710,12 @@ int ptk_create(ptk_ctx** out, int device_ordinal)
             hipMalloc(&c->d_queues2[b], PTK_QUEUE_BLOCK_BYTES) != hipSuccess)
         { ptk_destroy(c); return PTK_ERR_HIP; }
     if (hipEventCreateWithFlags(&c->ev_inputs, hipEventDisableTiming) != hipSuccess) { ptk_destroy(c); return PTK_ERR_HIP; }
+    if (hipStreamCreateWithFlags(&c->geo_stream, hipStreamNonBlocking) != hipSuccess ||
+        hipMalloc(&c->d_geo_red, GEO_RED_WORDS * sizeof(uint32_t) + sizeof(double)) != hipSuccess ||
+        hipHostMalloc((void**)&c->h_geo_red, GEO_RED_WORDS * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+    { ptk_destroy(c); return PTK_ERR_HIP; }
+    for (hipEvent_t& e : c->ev_geo_t)
+        if (hipEventCreate(&e) != hipSuccess) { ptk_destroy(c); return PTK_ERR_HIP; }
     {
         int lo = 0, hi = 0;                      // (numerically lowest = greatest priority)
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
@@ -704,6 +738,10 @@ void ptk_destroy(ptk_ctx* c)
     unbind_out_image(c);
     dfree(c->d_nodes); dfree(c->d_tris); dfree(c->d_shade); dfree(c->d_mats); dfree(c->d_lights);
     dfree(c->d_flat_tris);
+    free_geometry_cache(c); dfree(c->d_verts_res); dfree(c->d_geo_stage); dfree(c->d_geo_red);
+    if (c->h_geo_red) (void)hipHostFree(c->h_geo_red);
+    if (c->geo_stream) { (void)hipStreamSynchronize(c->geo_stream); (void)hipStreamDestroy(c->geo_stream); }
+    for (hipEvent_t e : c->ev_geo_t) if (e) (void)hipEventDestroy(e);
     dfree(c->d_texinfo); dfree(c->d_texels); dfree(c->d_primary); dfree(c->d_primary_hit); dfree(c->d_primary_rd); dfree(c->d_accum); dfree(c->d_rgb8);
     dfree(c->d_pixel_rng);
     for (int b = 0; b < 2; b++)
@@ -924,6 +962,8 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
     const auto t_copy = std::chrono::steady_clock::now();
     dfree(c->d_nodes); dfree(c->d_tris); dfree(c->d_shade); dfree(c->d_mats); dfree(c->d_lights);
     dfree(c->d_texinfo); dfree(c->d_texels);
+    dfree(c->d_verts_res); free_geometry_cache(c);
+    c->lights_stale = false;
     c->have_scene = false;
     auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
         size_t alloc = bytes ? bytes : 64;      // (never null: the walk reads node 0 unconditionally)
@@ -958,6 +998,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->d_nodes = dbvh.d_nodes; dguard.armed = false;
+        c->d_verts_res = d_verts; tmp.p[0] = nullptr;              // the builder's input stays resident (ptk_update_geometry)
         (void)hipFree(dbvh.d_order); dbvh.d_order = nullptr;
         bvh.num_nodes = dbvh.num_nodes; bvh.depth = dbvh.depth; bvh.stack_need = dbvh.stack_need;
     }
@@ -974,6 +1015,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
             HIPCHK(c, up((void**)&c->d_flat_tris, flat.data(), flat.size() * 4));
         }
         HIPCHK(c, up((void**)&c->d_shade, shade.data(), shade.size() * 4));
+        HIPCHK(c, up((void**)&c->d_verts_res, s->verts, (size_t)n * 9 * sizeof(float)));
     }
     c->built_on_device = on_device;
     HIPCHK(c, up((void**)&c->d_mats, mats.data(), mats.size() * 4));
@@ -982,6 +1024,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
     HIPCHK(c, up((void**)&c->d_texels, texels.data(), texels.size() * 4));
     c->num_nodes = bvh.num_nodes; c->num_tris = n; c->num_lights = s->num_lights; c->bvh_depth = bvh.depth; c->bvh_stack = bvh.stack_need;
     c->scene_bound = scene_bound;
+    c->bvh_pad = 1e-5f * std::max(vmax, 1.0f);                     // bvh_build.cpp / bvh_device.hip: 1e-5 x max(1, largest |coordinate|)
     for (int a = 0; a < 3; a++) { c->scene_lo[a] = n > 0 ? vlo[a] : 0.0f; c->scene_hi[a] = n > 0 ? vhi[a] : 0.0f; }
     c->view_generation++;
     c->scene_has_opacity = false;
@@ -1016,6 +1059,13 @@ int ptk_update_materials(ptk_ctx* c, int32_t num_materials, const ptk_material* 
             if (materials[i].tex[k] != c->h_materials[i].tex[k])
                 return fail(c, PTK_ERR_BAD_ARG, "texture bindings changed: upload the scene again");
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->lights_stale && !c->h_lights.empty())
+    {
+        // a geometry update moved light triangles on the device: take their vertices back before the records are rewritten whole
+        HIPCHK(c, hipMemcpyAsync(c->h_lights.data(), c->d_lights, c->h_lights.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    c->lights_stale = false;
     std::vector<float> mats((size_t)num_materials * MAT_F4 * 4, 0.0f);
     for (int32_t i = 0; i < num_materials; i++) pack_material(materials[i], c->h_texmap, mats.data() + (size_t)i * MAT_F4 * 4);
     for (size_t k = 0; k < c->h_light_material.size(); k++)
@@ -1031,6 +1081,212 @@ int ptk_update_materials(ptk_ctx* c, int32_t num_materials, const ptk_material* 
     c->h_materials.assign(materials, materials + num_materials);
     c->scene_plain = plain_tables((int32_t)c->h_flat_material.size(), c->h_flat_smoothing.data(), c->h_flat_material.data(), num_materials, materials);
     c->inputs_dirty = true;
+    return PTK_OK;
+}
+
+// ---- geometry updates after ptk_upload_scene (ptk.h) ----------------------------------------------------------
+namespace {
+
+static double* geo_cost_ptr(ptk_ctx* c) { return reinterpret_cast<double*>(c->d_geo_red + GEO_RED_WORDS); }
+
+// the refit, deepest level first, then the SAH sum; each level is one launch and stream order is the barrier between them
+static void queue_refit(ptk_ctx* c, float pad, int write_nodes, hipStream_t stream)
+{
+    for (int l = (int)c->level_start.size() - 2; l >= 0; l--)
+        launch_refit_level(c->d_level_nodes + c->level_start[l], c->level_start[l + 1] - c->level_start[l], c->d_nodes, c->d_tris, c->d_verts_res,
+                           c->d_refit_side, pad, write_nodes, stream);
+    launch_refit_cost(c->d_refit_side, c->num_nodes, c->d_refit_partial, geo_cost_ptr(c), stream);
+}
+
+// Once per topology: each node's level and the per-level node lists (from a one-off download of the links: both builders number
+// children after their parents, so one ascending sweep assigns every level), the inverse of the leaf order (on the device) and
+// the SAH cost of the tree as built (a refit pass over the uploaded vertices that writes no node).
+static int ensure_refit_topology(ptk_ctx* c)
+{
+    if (c->d_level_nodes) return PTK_OK;
+    const int nn = c->num_nodes, nt = c->num_tris;
+    if (nn <= 0 || nt <= 0 || !c->d_verts_res) return fail(c, PTK_ERR_BAD_ARG, "the uploaded scene has no triangles");
+    std::vector<float> nodes((size_t)nn * NODE_F4 * 4);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(nodes.data(), c->d_nodes, nodes.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<int32_t> level((size_t)nn, -1);
+    level[0] = 0;
+    int levels = 1;
+    for (int id = 0; id < nn; id++)
+    {
+        if (level[id] < 0) return fail(c, PTK_ERR_LIMIT, "refit: a node no parent links to");
+        int32_t link[4];
+        std::memcpy(link, &nodes[(size_t)id * 16 + 6], sizeof(link));
+        bool open = true;
+        for (int k = 0; k < 4; k++)
+        {
+            const int32_t l = link[k];
+            if (l == NODE_EXIT) { open = false; continue; }
+            if (!open) return fail(c, PTK_ERR_LIMIT, "refit: child slots not filled from the first");
+            if (l >= 0)
+            {
+                if (l <= id || l >= nn || level[l] >= 0) return fail(c, PTK_ERR_LIMIT, "refit: a link that does not point forward to a node of its own");
+                level[l] = level[id] + 1;
+                levels = std::max(levels, level[l] + 1);
+            }
+            else if ((int64_t)((~l) >> 3) + ((~l) & 7) + 1 > (int64_t)nt) return fail(c, PTK_ERR_LIMIT, "refit: a leaf outside the triangle records");
+        }
+    }
+    std::vector<int> start((size_t)levels + 1, 0);
+    for (int id = 0; id < nn; id++) start[(size_t)level[id] + 1]++;
+    for (int l = 0; l < levels; l++) start[(size_t)l + 1] += start[l];
+    std::vector<int32_t> list((size_t)nn);
+    {
+        std::vector<int> fill(start.begin(), start.end() - 1);
+        for (int id = 0; id < nn; id++) list[(size_t)fill[level[id]]++] = id;
+    }
+    int32_t* d_list = nullptr; int32_t* d_pos = nullptr; float4* d_side = nullptr; double* d_partial = nullptr;
+    hipError_t e = hipMalloc(&d_list, (size_t)nn * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&d_partial, ((size_t)nn + 255) / 256 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&d_pos, (size_t)nt * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&d_side, (size_t)nn * 2 * sizeof(float4));
+    if (e == hipSuccess) e = hipMemcpy(d_list, list.data(), (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(d_pos, 0, (size_t)nt * sizeof(int32_t), c->stream);
+    if (e != hipSuccess)
+    {
+        (void)hipFree(d_list); (void)hipFree(d_pos); (void)hipFree(d_side); (void)hipFree(d_partial);
+        return fail(c, PTK_ERR_HIP, std::string("refit tables: ") + hipGetErrorString(e));
+    }
+    c->d_level_nodes = d_list; c->d_tri_pos = d_pos; c->d_refit_side = d_side; c->d_refit_partial = d_partial;
+    c->level_start = start;
+    launch_inverse_order(c->d_tris, c->d_tri_pos, nt, c->stream);
+    queue_refit(c, c->bvh_pad, 0, c->stream);
+    HIPCHK(c, hipGetLastError());
+    double cost = 0.0;
+    HIPCHK(c, hipMemcpyAsync(&cost, geo_cost_ptr(c), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->sah_built = c->sah_now = cost;
+    c->sah_now_pending = false;
+    return PTK_OK;
+}
+
+static inline float geo_dec(uint32_t e) { const uint32_t u = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e; float f; std::memcpy(&f, &u, 4); return f; }
+
+static int update_geometry(ptk_ctx* c, int32_t first, int32_t count, const float* verts, const float* normals, const float* tbn, bool on_device)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (first < 0 || count < 0 || (int64_t)first + (int64_t)count > (int64_t)c->num_tris)
+        return fail(c, PTK_ERR_BAD_ARG, "triangle range outside the uploaded scene");
+    if ((normals == nullptr) != (tbn == nullptr)) return fail(c, PTK_ERR_BAD_ARG, "normals and tbn go together: both, or neither to move vertices only");
+    if (count == 0) return PTK_OK;
+    if (!verts) return fail(c, PTK_ERR_BAD_ARG, "null vertex array");
+    const char* limit_msg = "vertex coordinate is not finite or exceeds 2^61: the scene is unchanged";
+    const size_t per = (size_t)count * 9;
+    if (!on_device)
+        for (size_t i = 0; i < per; i++)
+            if (!(std::fabs(verts[i]) < 2.305843e18f)) return fail(c, PTK_ERR_LIMIT, limit_msg);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensure_refit_topology(c);
+    if (rc != PTK_OK) return rc;
+
+    // 1. stage the arrays and find the bounds the scene WOULD have, on a stream of their own: nothing resident is written yet
+    const size_t floats = per * (normals ? 3 : 1);
+    if (floats > c->geo_stage_floats)
+    {
+        if (c->geo_done_recorded) HIPCHK(c, hipEventSynchronize(c->ev_geo_t[4]));       // (the previous update's repack reads the old buffer)
+        dfree(c->d_geo_stage); c->geo_stage_floats = 0;
+        HIPCHK(c, hipMalloc(&c->d_geo_stage, floats * sizeof(float)));
+        c->geo_stage_floats = floats;
+    }
+    float* sv = c->d_geo_stage; float* sn = normals ? sv + per : nullptr; float* st = normals ? sv + 2 * per : nullptr;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (c->geo_done_recorded) HIPCHK(c, hipStreamWaitEvent(c->geo_stream, c->ev_geo_t[4], 0));
+    HIPCHK(c, hipEventRecord(c->ev_geo_t[0], c->geo_stream));
+    HIPCHK(c, hipMemcpyAsync(sv, verts, per * sizeof(float), kind, c->geo_stream));
+    if (normals)
+    {
+        HIPCHK(c, hipMemcpyAsync(sn, normals, per * sizeof(float), kind, c->geo_stream));
+        HIPCHK(c, hipMemcpyAsync(st, tbn, per * sizeof(float), kind, c->geo_stream));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_geo_red, 0, GEO_RED_WORDS * sizeof(uint32_t), c->geo_stream));
+    launch_geometry_bounds(c->d_verts_res, sv, first, count, c->num_tris, c->d_geo_red, c->geo_stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->h_geo_red, c->d_geo_red, GEO_RED_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->geo_stream));
+    HIPCHK(c, hipEventRecord(c->ev_geo_t[1], c->geo_stream));
+    // the one host wait of an update: for the staging stream, which stands behind the PREVIOUS update only - renders queued
+    // since then are not waited for; the caller's arrays are free again from here on
+    HIPCHK(c, hipStreamSynchronize(c->geo_stream));
+    const uint32_t* red = c->h_geo_red;
+    if (red[7]) return fail(c, PTK_ERR_LIMIT, limit_msg);
+    float vmax; std::memcpy(&vmax, &red[6], 4);
+
+    // 2. rewrite on the context's stream: behind every render already queued - their accumulate kernels are on this stream,
+    // each behind its trace kernel on the internal streams, so no trace still reads the old records - and ahead of every
+    // later one (inputs_dirty re-anchors the trace streams behind these kernels)
+    HIPCHK(c, hipEventRecord(c->ev_geo_t[2], c->stream));
+    launch_repack_geometry(sv, sn, st, first, count, c->d_verts_res, c->d_tri_pos, c->d_tris, c->d_flat_tris, c->d_shade, c->stream);
+    launch_repack_lights(c->d_verts_res, first, count, c->d_lights, c->num_lights, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_geo_t[3], c->stream));
+    c->bvh_pad = 1e-5f * std::max(vmax, 1.0f);
+    queue_refit(c, c->bvh_pad, 1, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_geo_t[4], c->stream));
+    c->geo_done_recorded = true;
+
+    c->scene_bound = 3.1f * (1.01f * vmax + 1e-3f);
+    for (int a = 0; a < 3; a++) { c->scene_lo[a] = geo_dec(~red[a]); c->scene_hi[a] = geo_dec(red[3 + a]); }
+    if (c->num_lights > 0) c->lights_stale = true;
+    c->geo_updates++;
+    c->sah_now_pending = true;
+    c->view_generation++;
+    c->primary_hit_dirty = true;
+    c->out_full_next = true;
+    c->inputs_dirty = true;
+    return PTK_OK;
+}
+
+}  // namespace
+
+int ptk_update_geometry(ptk_ctx* c, int32_t first_tri, int32_t num_tris, const float* verts, const float* normals, const float* tbn)
+{
+    return update_geometry(c, first_tri, num_tris, verts, normals, tbn, false);
+}
+
+int ptk_update_geometry_device(ptk_ctx* c, int32_t first_tri, int32_t num_tris, const float* d_verts, const float* d_normals, const float* d_tbn)
+{
+    return update_geometry(c, first_tri, num_tris, d_verts, d_normals, d_tbn, true);
+}
+
+int ptk_geometry_info(ptk_ctx* c, uint32_t* updates, int* refitted, double* sah_built, double* sah_now)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((sah_built || sah_now) && c->num_tris > 0)
+    {
+        const int rc = ensure_refit_topology(c);
+        if (rc != PTK_OK) return rc;
+        if (c->sah_now_pending)
+        {
+            double cost = 0.0;
+            HIPCHK(c, hipMemcpyAsync(&cost, geo_cost_ptr(c), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            c->sah_now = cost; c->sah_now_pending = false;
+        }
+    }
+    if (updates) *updates = c->geo_updates;
+    if (refitted) *refitted = c->geo_updates > 0 ? 1 : 0;
+    if (sah_built) *sah_built = c->sah_built;
+    if (sah_now) *sah_now = c->sah_now;
+    return PTK_OK;
+}
+
+int ptk_geometry_timing(ptk_ctx* c, float* ms3)
+{
+    if (!c || !ms3) return PTK_ERR_BAD_ARG;
+    if (!c->geo_done_recorded) return fail(c, PTK_ERR_BAD_ARG, "no geometry update yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(c->ev_geo_t[4]));
+    HIPCHK(c, hipEventElapsedTime(&ms3[0], c->ev_geo_t[0], c->ev_geo_t[1]));
+    HIPCHK(c, hipEventElapsedTime(&ms3[1], c->ev_geo_t[2], c->ev_geo_t[3]));
+    HIPCHK(c, hipEventElapsedTime(&ms3[2], c->ev_geo_t[3], c->ev_geo_t[4]));
     return PTK_OK;
 }
 

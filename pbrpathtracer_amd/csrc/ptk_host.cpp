@@ -33,6 +33,12 @@ void pth_load_object(pth_tracer* t, const char* file, const float* mm)
     for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) M[c][r] = mm[c * 4 + r];
     t->pt.LoadObject(file, M);
 }
+void pth_set_object_transform(pth_tracer* t, int obj, const float* mm)
+{
+    glm::mat4 M(1.0f);
+    for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) M[c][r] = mm[c * 4 + r];
+    t->pt.SetObjectTransform(obj, M);
+}
 void pth_set_material(pth_tracer* t, int obj, int elem, const float* m)
 {
     Material mat;

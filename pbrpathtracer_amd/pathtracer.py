@@ -35,7 +35,7 @@ HOST_SYMBOLS = [
     "pth_last_error", "pth_context", "pth_staged_scene", "pth_load_scene_file", "pth_pts_roundtrip",
     "pth_trs_matrix", "pth_euler_camera", "pth_triangle_init", "pth_image_load", "pth_image_data", "pth_image_tex2d",
     "pth_export_png", "pth_render_adaptive", "pth_read_sample_counts",
-    "pth_render_features", "pth_read_feature", "pth_pick",
+    "pth_render_features", "pth_read_feature", "pth_pick", "pth_set_object_transform",
 ]
 
 _bound = False
@@ -58,6 +58,7 @@ def _bind_locked(L) -> C.CDLL:
     L.pth_create.restype = vp; L.pth_create.argtypes = [i32]
     L.pth_destroy.restype = None; L.pth_destroy.argtypes = [vp]
     L.pth_load_object.restype = None; L.pth_load_object.argtypes = [vp, C.c_char_p, _f]
+    L.pth_set_object_transform.restype = None; L.pth_set_object_transform.argtypes = [vp, i32, _f]
     L.pth_set_material.restype = None; L.pth_set_material.argtypes = [vp, i32, i32, _f]
     L.pth_set_texture.restype = None; L.pth_set_texture.argtypes = [vp, i32, i32, i32, C.c_char_p]
     for n in ("pth_build_bvh", "pth_reset_image", "pth_clear_scene", "pth_render_frame", "pth_exit"):
@@ -232,6 +233,12 @@ class PathTracer:
     # ---- extensions ----------------------------------------------------------------------------
     def SetSeed(self, seed: int): self.L.pth_set_seed(self.h, seed)
     def SetTile(self, rank: int, world: int): self.L.pth_set_tile(self.h, rank, world)
+
+    def SetObjectTransform(self, objId: int, model):
+        """Extension: stage object `objId` again under the 4x4 `model` ([column][row], as LoadObject takes it).  After BuildBVH()
+        the next render call moves its triangles on the device and refits the BVH (include/ptk.h ptk_update_geometry)."""
+        M = np.ascontiguousarray(model, dtype=np.float32)
+        self.L.pth_set_object_transform(self.h, int(objId), _fp(M.reshape(16)))
     def RenderFrames(self, count: int): self.L.pth_render_frames(self.h, count)
 
     def RenderAdaptive(self, threshold: float, min_spp: int, step: int, max_spp: int) -> dict:

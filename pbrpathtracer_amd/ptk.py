@@ -81,6 +81,7 @@ SYMBOLS = [
     "ptk_debug_stall_exchange", "ptk_render_adaptive", "ptk_read_sample_counts", "ptk_read_moments",
     "ptk_trace_variant", "ptk_scene_is_plain",
     "ptk_feature_info", "ptk_render_features", "ptk_read_feature", "ptk_feature_device_ptr", "ptk_pick",
+    "ptk_update_geometry", "ptk_update_geometry_device", "ptk_geometry_info", "ptk_geometry_timing",
 ]
 
 
@@ -164,6 +165,10 @@ def _load_locked() -> C.CDLL:
     L.ptk_read_feature.argtypes = [vp, i32, vp]
     L.ptk_feature_device_ptr.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ptk_pick.argtypes = [vp, i32, i32, u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+    L.ptk_update_geometry.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp]
+    L.ptk_update_geometry_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp]
+    L.ptk_geometry_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.ptk_geometry_timing.argtypes = [vp, C.POINTER(C.c_float)]
     L.ptk_bvh_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.ptk_bvh_layout.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.ptk_download_bvh.argtypes = [vp, vp, vp]
@@ -272,6 +277,52 @@ class Context:
     def update_materials(self, materials: np.ndarray):
         m = np.ascontiguousarray(materials, dtype=MATERIAL_DTYPE)
         self._chk(self.L.ptk_update_materials(self.h, len(m), m.ctypes.data), "ptk_update_materials")
+
+    def update_geometry(self, first: int, verts, normals=None, tbn=None, num_tris: Optional[int] = None):
+        """ptk_update_geometry: move triangles [first, first + n) of the uploaded scene and refit the BVH.  verts / normals / tbn
+        are [n, 9] float32: numpy arrays (host call), or - for ptk_update_geometry_device - torch tensors on the context's GPU
+        or integer device addresses (then num_tris says how many triangles).  normals and tbn go together or are both None."""
+        def dev_ptr(a):
+            if a is None:
+                return None
+            if isinstance(a, int):
+                return C.c_void_p(a)
+            assert a.is_cuda and a.is_contiguous() and str(a.dtype) == "torch.float32", "float32 contiguous device tensor"
+            return C.c_void_p(a.data_ptr())
+        if isinstance(verts, int) or hasattr(verts, "data_ptr"):
+            n = int(num_tris) if num_tris is not None else verts.numel() // 9
+            dev = self.device_ordinal()
+            for t in (verts, normals, tbn):                   # tensors: on THIS context's GPU, and n x 9 floats each
+                if t is not None and not isinstance(t, int):
+                    assert t.device.index == dev, f"tensor on cuda:{t.device.index}, context on device {dev}"
+                    assert t.numel() == n * 9, f"{t.numel()} elements where {n} triangles need {n * 9}"
+            self._chk(self.L.ptk_update_geometry_device(self.h, int(first), n, dev_ptr(verts), dev_ptr(normals), dev_ptr(tbn)),
+                      "ptk_update_geometry_device")
+            return
+        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 9)
+        nn = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(len(v), 9)
+        tb = None if tbn is None else np.ascontiguousarray(tbn, dtype=np.float32).reshape(len(v), 9)
+        self._chk(self.L.ptk_update_geometry(self.h, int(first), len(v), v.ctypes.data if len(v) else None,
+                                             None if nn is None else nn.ctypes.data, None if tb is None else tb.ctypes.data),
+                  "ptk_update_geometry")
+
+    def device_ordinal(self) -> int:
+        """the HIP ordinal of this context's GPU"""
+        d = C.c_int32(-1)
+        self.L.ptk_comm_info(self.h, None, None, None, C.byref(d))       # (the ordinal is written even where there is no communicator)
+        return d.value
+
+    def geometry_info(self) -> dict:
+        """ptk_geometry_info: updates since the upload, whether the tree is a refitted one, its SAH cost as built and now."""
+        u = C.c_uint32(0); r = C.c_int(0); b = C.c_double(0); n = C.c_double(0)
+        self._chk(self.L.ptk_geometry_info(self.h, C.byref(u), C.byref(r), C.byref(b), C.byref(n)), "ptk_geometry_info")
+        return {"updates": u.value, "refitted": bool(r.value), "sah_built": b.value, "sah_now": n.value}
+
+    def geometry_timing(self) -> dict:
+        """HIP-event times (ms) of the last update_geometry: staging copies + bounds, record repack, refit."""
+        t = (C.c_float * 3)()
+        self._chk(self.L.ptk_geometry_timing(self.h, t), "ptk_geometry_timing")
+        return {"copy_ms": t[0], "repack_ms": t[1], "refit_ms": t[2]}
 
     def set_camera(self, pos, dir, up, focal, fovy, focal_dist, aperture):
         f3 = C.c_float * 3

@@ -87,7 +87,7 @@ def kernel_resources(lib):
     rows = []
     for k in out:
         name = subprocess.run(["c++filt", k["name"]], capture_output=True, text=True).stdout.strip() or k["name"]
-        name = re.sub(r"\(.*\)$", "", name)
+        name = re.sub(r"\(.*\)$", "", name.replace("(anonymous namespace)::", ""))
         rows.append((name, int(k.get("vgpr_count", 0)), int(k.get("sgpr_count", 0)), int(k.get("vgpr_spill_count", 0)), int(k.get("sgpr_spill_count", 0)),
                      int(k.get("group_segment_fixed_size", 0)), int(k.get("private_segment_fixed_size", 0))))
     return rows
@@ -103,7 +103,7 @@ if os.path.exists(lib):
         print("| kernel | VGPRs | SGPRs | VGPR spills | SGPR spills | LDS bytes / workgroup | scratch bytes / lane | waves / SIMD by registers |")
         print("|---|---|---|---|---|---|---|---|")
         for r in sorted(rows):
-            if "trace" in r[0] or "accumulate" in r[0] or "level_bin" in r[0] or "collapse" in r[0]:
+            if "trace" in r[0] or "accumulate" in r[0] or "level_bin" in r[0] or "collapse" in r[0] or "refit" in r[0] or "repack" in r[0] or "geometry_bounds" in r[0]:
                 alloc = (r[1] + 7) // 8 * 8
                 print("| `%s` | %d | %d | %d | %d | %d | %d | %d |" % (r[0], r[1], r[2], r[3], r[4], r[5], r[6], min(8, 512 // max(8, alloc))))
     except Exception as e:          # (no llvm tools: the measurement table above still stands)
