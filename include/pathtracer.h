@@ -197,6 +197,15 @@ public:
     // The (object, element) under pixel (x, y), y counted from the top row: one ray (ptk_pick), pending edits applied first.
     // A pixel that sees nothing gives -1 / -1 (and triangle -1) and true; false: no scene / resolution yet, or (x, y) outside the frame.
     bool Pick(int x, int y, int* objId, int* elementId, int* triangle = nullptr);
+    // Radiance along caller-supplied rays (include/ptk.h ptk_trace_rays, host arrays, synchronous): out[i] = the float32 in-order
+    // sum over samples [first_sample, first_sample + spp) of what Trace returns for the ray (origins[i], dirs[i]) - unit
+    // directions - at the class's trace depth, on the streams of (the class's seed, RNG pixel key_base + i, sample);
+    // flags = PTK_RAYS_ACCUMULATE | PTK_RAYS_LENS_DRAWS.  Valid after BuildBVH(): needs neither a resolution nor a camera; pending
+    // material and geometry edits apply as for RenderFrame(); the image and the sample count are not touched.
+    bool TraceRays(int num_rays, const float* origins, const float* dirs, uint32_t first_sample, uint32_t spp, uint32_t key_base,
+                   uint32_t flags, float* out);
+    // the camera as SetCamera last received it (position, direction, up; not normalised), 3 floats each
+    void GetCamera(float* pos, float* dir, float* up) const;
     // mTotalImg (float RGB, rows bottom-up), W*H*3 floats
     bool ReadAccumulation(float* out);
     // last error text of the device layer ("" when none); the reference API itself stays silent

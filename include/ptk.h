@@ -312,6 +312,49 @@ int ptk_read_feature(ptk_ctx* ctx, int feature, void* host_out);
 int ptk_feature_device_ptr(ptk_ctx* ctx, int feature, void** dev_ptr, size_t* bytes);
 int ptk_pick(ptk_ctx* ctx, int x, int y_top_down, uint64_t seed, int32_t* tri, int32_t* material, float* t);
 
+/* ---- radiance along caller-supplied rays (no counterpart in the reference, whose every path starts at its one camera) -------
+ * For other camera models (orthographic, fisheye, panoramas, stereo pairs), light baking (lightmap texels, irradiance probes) and
+ * radiance probes.  For the uploaded scene, num_rays rays (origins[i], dirs[i]) and the sample range [first_sample, first_sample + spp):
+ *   out[i] = (((base_i + L(i, first_sample)) + L(i, first_sample + 1)) + ... )
+ * summed in float32 per channel, strictly in sample order; base_i = 0, or the value already in out[i] under PTK_RAYS_ACCUMULATE.
+ * L(i, s) is the radiance PathTracer::Trace (pathtracer.cpp:551-727) returns for the ray (origins[i], dirs[i]) with depth limit
+ * max_depth, in the iterative form the trace kernels compute.  Its random stream is that of (seed, RNG pixel key_base + i, sample
+ * s) - key_base + i taken mod 2^32 - with no draw consumed before Trace, and the caller's ray is ray number 0 of the path (the key
+ * of its stochastic-opacity draws): bit for bit the CPU oracle's orc_trace_counter(scene, ro, rd, max_depth, seed, key_base + i, s,
+ * mode 0).  PTK_RAYS_LENS_DRAWS starts every stream behind the two SampleCircle draws a camera ray always consumes
+ * (pathtracer.cpp:787): then rays equal to a camera's own, with key_base + i = the pixel's top-down index, reproduce
+ * ptk_render's accumulator bit for bit.
+ * Hence the result does not depend on how the samples are batched into calls (later calls with PTK_RAYS_ACCUMULATE), on how a ray
+ * set is cut into calls (each call's key_base = the global index of its first ray), on the builder that made the tree, on the
+ * "flat" option (the call always walks the BVH) or on ptk_set_tile, which it ignores (tests/test_gpu_rays.py: array_equal).
+ * Directions are used as given: the reference's Trace assumes unit length, normalising is the caller's business.  Rays must be
+ * finite; a non-finite component makes THAT ray's output unspecified and affects neither another ray nor whether the call ends
+ * (every loop of the walk is bounded by the tree).
+ * The call needs a scene only - no camera, no frame - and reads it as ptk_update_materials / ptk_update_geometry left it.  It
+ * touches neither the accumulator, the sample count, the 8-bit image, the adaptive state, the feature planes nor a bound hand-off
+ * buffer, and stays legal after ptk_render_adaptive.  The "contract" option does not reach it (its kernel exists once, in the exact
+ * arithmetic), and ptk_request_exit does NOT cut it: a ray query always runs to its end.
+ *   ptk_trace_rays:        host arrays, synchronous; with PTK_RAYS_ACCUMULATE it reads out first.
+ *   ptk_trace_rays_device: memory of this context's GPU (a torch tensor, hipMalloc), asynchronous on the context's stream (the
+ *                          caller's after ptk_set_stream): the inputs are read and out is written on that stream, so tensors
+ *                          produced on it need no host wait.  The arrays must stay allocated until the stream has passed the call.
+ * PTK_ERR_BAD_ARG: a null context, a null array with num_rays > 0, num_rays < 0, unknown flag bits, a call before ptk_upload_scene.
+ * (max_depth: every value ptk_set_frame takes - all of them; a limit <= 0 ends each path at its first interaction.)  num_rays == 0
+ * is PTK_OK and does nothing; spp == 0 is PTK_OK and zeroes out unless PTK_RAYS_ACCUMULATE is set.
+ * Memory: a sample buffer of the call's own, 16 B per ray and sample of a pass, grown to the largest pass so far and freed by
+ * ptk_destroy; a call is cut into passes over the sample range (and, past that, into blocks of rays) so that no pass needs more
+ * than "pass_bytes" or half of the free device memory; later passes fold onto earlier ones, the same bits.  The host entry also
+ * stages 36 B per ray for the length of the call. */
+#define PTK_RAYS_ACCUMULATE 1u
+#define PTK_RAYS_LENS_DRAWS 2u
+int ptk_trace_rays(ptk_ctx* ctx, int32_t num_rays, const float* origins /*[n][3]*/, const float* dirs /*[n][3]*/, int max_depth,
+                   uint32_t first_sample, uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* out /*[n][3]*/);
+int ptk_trace_rays_device(ptk_ctx* ctx, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth,
+                          uint32_t first_sample, uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out);
+/* measurement hook (tools/rays_timing.py), not part of the feature: HIP-event times of the last ray query's kernels, summed over
+ * its passes (the first 64 of them) - rays_kernel with its one-wave set-up launch, rays_fold_kernel; waits for the call */
+int ptk_last_rays_ms(ptk_ctx* ctx, float* trace_ms, float* fold_ms);
+
 int ptk_samples(ptk_ctx* ctx);         /* GetSamples (pathtracer.cpp:362-365); thread-safe */
 /* Exit (pathtracer.cpp:819-822); thread-safe.  Cuts EVERY render in flight - ptk_render is asynchronous while no output
  * image is bound, so several may be queued: all of them, not only the newest - : passes whose kernels have not started are

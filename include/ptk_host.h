@@ -61,6 +61,10 @@ int  pth_read_sample_counts(pth_tracer* t, uint32_t* out);
 int  pth_render_features(pth_tracer* t, uint32_t mask, uint32_t sample);
 int  pth_read_feature(pth_tracer* t, int feature, void* out);
 int  pth_pick(pth_tracer* t, int x, int y, int* obj, int* elem, int* tri);
+/* TraceRays (radiance along caller-supplied rays, include/ptk.h ptk_trace_rays with the tracer's seed and trace depth): 1 on success */
+int  pth_trace_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, uint32_t first_sample, uint32_t spp,
+                    uint32_t key_base, uint32_t flags, float* out);
+void pth_get_camera(pth_tracer* t, float pos[3], float dir[3], float up[3]);   /* GetCamera (extension): what SetCamera last received */
 const char* pth_last_error(pth_tracer* t);
 ptk_ctx* pth_context(pth_tracer* t);
 const ptk_scene_desc* pth_staged_scene(pth_tracer* t);    /* flat arrays of the staged scene (host only) */

@@ -672,9 +672,9 @@ const int PathTracer::GetSamples() const { return m->ctx ? ptk_samples(m->ctx) :
 
 void PathTracer::RenderFrame() { RenderFrames(1); }                    // :741-817
 
-// What a render call brings up to date before it renders (render_mu held): material / texture edits, camera, resolution, the
-// hand-off binding and a pending ResetImage().  false: the render must not run (the error is noted).
-static bool prepare_render(PathTracer::Impl* m, GLubyte*& out_img, unsigned& out_gl, void*& out_dev)
+// The scene half of what a render call brings up to date (render_mu held): geometry, material and texture edits made after
+// BuildBVH().  false: the call must not run (the error is noted).
+static bool apply_scene_edits(PathTracer::Impl* m)
 {
     int rc;
     if (std::find(m->geometry_dirty.begin(), m->geometry_dirty.end(), (uint8_t)1) != m->geometry_dirty.end())
@@ -727,6 +727,15 @@ static bool prepare_render(PathTracer::Impl* m, GLubyte*& out_img, unsigned& out
         if (rc != PTK_OK) return false;
         m->materials_dirty = m->textures_dirty = false;
     }
+    return true;
+}
+
+// What a render call brings up to date before it renders (render_mu held): the scene edits above, camera, resolution, the
+// hand-off binding and a pending ResetImage().  false: the render must not run (the error is noted).
+static bool prepare_render(PathTracer::Impl* m, GLubyte*& out_img, unsigned& out_gl, void*& out_dev)
+{
+    int rc;
+    if (!apply_scene_edits(m)) return false;
     if (m->camera_dirty)
     {
         rc = ptk_set_camera(m->ctx, m->cam_pos, m->cam_dir, m->cam_up, m->focal, m->fovy, m->focal_dist, m->aperture);
@@ -861,6 +870,18 @@ bool PathTracer::Pick(int x, int y, int* objId, int* elementId, int* triangle)
     return true;
 }
 
+// Radiance along caller-supplied rays (ptk_trace_rays) in the scene as the next RenderFrame() would see it
+bool PathTracer::TraceRays(int num_rays, const float* origins, const float* dirs, uint32_t first_sample, uint32_t spp, uint32_t key_base,
+                           uint32_t flags, float* out)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_trace_rays(m->ctx, num_rays, origins, dirs, m->max_depth, first_sample, spp, m->seed, key_base, flags, out);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 void PathTracer::Exit() { if (m->ctx) ptk_request_exit(m->ctx); }      // :819-822
 
 // ---- extensions -----------------------------------------------------------------------------------------
@@ -912,6 +933,10 @@ void PathTracer::SetTile(int rank, int world)
 {
     m->rank = rank; m->world = world;
     if (m->ctx) m->note(ptk_set_tile(m->ctx, rank, world));
+}
+void PathTracer::GetCamera(float* pos, float* dir, float* up) const
+{
+    for (int a = 0; a < 3; a++) { pos[a] = m->cam_pos[a]; dir[a] = m->cam_dir[a]; up[a] = m->cam_up[a]; }
 }
 bool PathTracer::ReadAccumulation(float* out)
 {

@@ -25,6 +25,7 @@
 #include "ptk_device_fn.h"
 #include "ptk_adaptive.h"
 #include "ptk_features.h"
+#include "ptk_rays.h"
 #include "ptk_refit.h"
 
 using namespace ptk;
@@ -143,6 +144,14 @@ struct ptk_ctx {
     void* d_feat[NUM_FEATURES] = {};
     int feat_w = 0, feat_h = 0;                  // the frame the planes were allocated for and last rendered at
     uint32_t feat_mask = 0;                      // planes the last ptk_render_features wrote
+
+    // radiance along caller-supplied rays (ptk_trace_rays): its own sample buffer between rays_kernel and rays_fold_kernel - renders
+    // may still be in flight on the internal streams with theirs -, grown to the largest pass so far; the item counter and
+    // parameter block of a launch; three events per pass of the last call: before rays_kernel, behind it, behind the fold
+    float4* d_rays_samples = nullptr; size_t rays_samples_bytes = 0;
+    RaysBlock* d_rays_block = nullptr;
+    std::vector<hipEvent_t> ev_rays;
+    int rays_passes = 0;                         // timed passes of the last call (at most kMaxTimedPasses)
 
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
@@ -765,6 +774,8 @@ void ptk_destroy(ptk_ctx* c)
     dfree(c->d_live_mask); dfree(c->d_live_list);
     free_adaptive(c);
     free_features(c);
+    dfree(c->d_rays_samples); dfree(c->d_rays_block);
+    for (hipEvent_t e : c->ev_rays) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
     if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);
@@ -1646,6 +1657,162 @@ int ptk_pick(ptk_ctx* c, int x, int y_top_down, uint64_t seed, int32_t* tri, int
     if (tri) *tri = out[0];
     if (material) *material = out[1];
     if (t) *t = th;
+    return PTK_OK;
+}
+
+// ---- radiance along caller-supplied rays (ptk.h) ---------------------------------------------------------------------------
+// The argument checks both entries share; PTK_OK with *nothing = true: the call is legal and has nothing to do.
+static int check_rays_args(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, uint32_t flags, const float* out, bool* nothing)
+{
+    *nothing = false;
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (flags & ~(PTK_RAYS_ACCUMULATE | PTK_RAYS_LENS_DRAWS)) return fail(c, PTK_ERR_BAD_ARG, "ptk_trace_rays: unknown flag bits");
+    if (num_rays < 0) return fail(c, PTK_ERR_BAD_ARG, "ptk_trace_rays: negative ray count");
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (num_rays > 0 && (!origins || !dirs || !out)) return fail(c, PTK_ERR_BAD_ARG, "ptk_trace_rays: null array");
+    // (max_depth: ptk_set_frame takes every value - a limit <= 0 ends each path at its first interaction -, and so does this call)
+    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
+    *nothing = num_rays == 0;
+    return PTK_OK;
+}
+
+// The call proper, on the context's stream, every pointer into this GPU's memory.  Cut into passes over the sample range - and,
+// where even one sample of every ray exceeds the budget, into blocks of rays - so that no pass's sample buffer exceeds
+// "pass_bytes" or half of the free device memory; a later pass folds onto what the earlier ones left in out.
+static int trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,
+                                uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out)
+{
+    c->rays_passes = 0;
+    // (a scene without triangles has no tree to walk: every path is black)
+    if (spp == 0 || c->num_nodes == 0)
+    {
+        if (!(flags & PTK_RAYS_ACCUMULATE)) HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)num_rays * 3 * sizeof(float), c->stream));
+        return PTK_OK;
+    }
+    if (!c->d_rays_block) HIPCHK(c, hipMalloc(&c->d_rays_block, sizeof(RaysBlock)));
+    RenderParams p;
+    fill_params(c, p, first_sample, spp, seed);
+    p.max_depth = max_depth;
+    p.exit_flag = nullptr;                       // ptk_request_exit does not cut a ray query
+    const size_t groups = ((size_t)num_rays + 63) / 64, group_bytes = 64 * sizeof(float4);      // one sample of one group of rays
+    // samples per work item, by trace_kernel's rule (run_passes)
+    const uint32_t chunk_opt = c->opt_chunk > 0 ? (uint32_t)c->opt_chunk : ((double)spp * (double)groups / 8.0 >= 49152.0 ? 8u : 4u);
+    // (sample slots are 32-bit indices: 2^31 float4 at most)
+    size_t budget = std::min<size_t>(std::max<size_t>(c->opt_pass_bytes, group_bytes), (size_t)1 << 35);
+    {
+        const size_t want = std::min(budget, groups * group_bytes * ((size_t)spp + chunk_opt));
+        size_t free_b = 0, total_b = 0;
+        if (want > c->rays_samples_bytes)        // (only a call that has to allocate asks the driver)
+        {
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, std::max(std::max(free_b / 2, c->rays_samples_bytes), group_bytes));
+            else (void)hipGetLastError();
+        }
+    }
+    // The largest pass is the first one: the buffer is brought to its size here, the budget halved while the device refuses.
+    size_t block_groups; uint32_t max_pass;
+    for (;;)
+    {
+        block_groups = std::min(groups, budget / group_bytes);
+        max_pass = (uint32_t)std::min<size_t>(0x40000000u, budget / (block_groups * group_bytes));
+        if (max_pass > chunk_opt) max_pass -= max_pass % chunk_opt;             // whole chunks
+        // (the first pass's sample slots: its chunks, the last of which may be partly used)
+        const uint32_t n0 = std::min(spp, max_pass), slots = n0 <= chunk_opt ? n0 : (n0 + chunk_opt - 1) / chunk_opt * chunk_opt;
+        const size_t need = block_groups * group_bytes * slots;
+        if (need <= c->rays_samples_bytes) break;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        dfree(c->d_rays_samples); c->rays_samples_bytes = 0;
+        if (hipMalloc(&c->d_rays_samples, need) == hipSuccess) { c->rays_samples_bytes = need; break; }
+        (void)hipGetLastError(); c->d_rays_samples = nullptr;
+        if (budget <= group_bytes) return fail(c, PTK_ERR_HIP, "hipMalloc: no memory for the sample buffer of even one sample of 64 rays");
+        budget = std::max(group_bytes, budget / 2);
+    }
+    RaysParams r = {};
+    r.lens_draws = (flags & PTK_RAYS_LENS_DRAWS) ? 1 : 0;
+    p.samples = c->d_rays_samples;
+    for (size_t g0 = 0; g0 < groups; g0 += block_groups)
+    {
+        const size_t ray0 = g0 * 64, nr = std::min((size_t)num_rays - ray0, block_groups * 64), nb = (nr + 63) / 64;
+        r.origins = d_origins + ray0 * 3; r.dirs = d_dirs + ray0 * 3;
+        r.num_rays = (int)nr; r.key_base = key_base + (uint32_t)ray0;
+        for (uint32_t done = 0; done < spp;)
+        {
+            const uint32_t n = std::min(spp - done, max_pass);
+            p.first_sample = first_sample + done; p.spp = n;
+            p.chunk = (int)std::min(n, chunk_opt); p.num_chunks = (int)((n + p.chunk - 1) / p.chunk);
+            p.num_items = (int)(nb * (size_t)p.num_chunks);
+            const int pi = c->rays_passes < ptk_ctx::kMaxTimedPasses ? c->rays_passes : -1;
+            if (pi >= 0)
+                while (c->ev_rays.size() < (size_t)(pi + 1) * 3)
+                {
+                    hipEvent_t e = nullptr;
+                    HIPCHK(c, hipEventCreate(&e));
+                    c->ev_rays.push_back(e);
+                }
+            if (pi >= 0) HIPCHK(c, hipEventRecord(c->ev_rays[pi * 3], c->stream));
+            launch_rays(p, r, c->d_rays_block, c->resident_waves, c->stream);
+            HIPCHK(c, hipGetLastError());
+            if (pi >= 0) HIPCHK(c, hipEventRecord(c->ev_rays[pi * 3 + 1], c->stream));
+            launch_rays_fold(c->d_rays_samples, d_out + ray0 * 3, (int)nr, p.chunk, p.num_chunks, n, ((flags & PTK_RAYS_ACCUMULATE) || done > 0) ? 1 : 0, c->stream);
+            HIPCHK(c, hipGetLastError());
+            if (pi >= 0) { HIPCHK(c, hipEventRecord(c->ev_rays[pi * 3 + 2], c->stream)); c->rays_passes = pi + 1; }
+            done += n;
+        }
+    }
+    return PTK_OK;
+}
+
+int ptk_trace_rays_device(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample, uint32_t spp,
+                          uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out)
+{
+    bool nothing;
+    const int rc = check_rays_args(c, num_rays, d_origins, d_dirs, flags, d_out, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return trace_rays_on_stream(c, num_rays, d_origins, d_dirs, max_depth, first_sample, spp, seed, key_base, flags, d_out);
+}
+
+int ptk_trace_rays(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, int max_depth, uint32_t first_sample, uint32_t spp,
+                   uint64_t seed, uint32_t key_base, uint32_t flags, float* out)
+{
+    bool nothing;
+    int rc = check_rays_args(c, num_rays, origins, dirs, flags, out, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // origins | dirs | out, staged for the length of the call
+    const size_t n3 = (size_t)num_rays * 3, bytes = n3 * sizeof(float);
+    float* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, 3 * bytes));
+    hipError_t e = hipMemcpyAsync(d, origins, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + n3, dirs, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && (flags & PTK_RAYS_ACCUMULATE)) e = hipMemcpyAsync(d + 2 * n3, out, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+    {
+        rc = trace_rays_on_stream(c, num_rays, d, d + n3, max_depth, first_sample, spp, seed, key_base, flags, d + 2 * n3);
+        if (rc == PTK_OK) e = hipMemcpyAsync(out, d + 2 * n3, bytes, hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also on the way out of a failure: the staging buffer may be in use)
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    if (rc != PTK_OK) return rc;
+    if (e != hipSuccess) return fail(c, PTK_ERR_HIP, hipGetErrorString(e));
+    return PTK_OK;
+}
+
+int ptk_last_rays_ms(ptk_ctx* c, float* trace_ms, float* fold_ms)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    float t = 0.0f, f = 0.0f;
+    for (int i = 0; i < c->rays_passes; i++)
+    {
+        float a = 0.0f, b = 0.0f;
+        HIPCHK(c, hipEventSynchronize(c->ev_rays[i * 3 + 2]));
+        HIPCHK(c, hipEventElapsedTime(&a, c->ev_rays[i * 3], c->ev_rays[i * 3 + 1]));
+        HIPCHK(c, hipEventElapsedTime(&b, c->ev_rays[i * 3 + 1], c->ev_rays[i * 3 + 2]));
+        t += a; f += b;
+    }
+    if (trace_ms) *trace_ms = t;
+    if (fold_ms) *fold_ms = f;
     return PTK_OK;
 }
 

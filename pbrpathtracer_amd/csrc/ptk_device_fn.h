@@ -1,6 +1,6 @@
 // Device functions shared by every kernel file of libptk.so, all __forceinline__: the v3 arithmetic in the reference's order, the
 // exact 1 / x and sqrt (rcp_ieee, sqrt_ieee), the RNG and its keys, tex2d, the re-entrant BVH walk (Walk, tri_test, walk_step), the
-// light sampler, the owned-tile / quadrant pixel mapping and the 8-bit resolve.  PTK_CONTRACT selects namespace and arithmetic:
+// light sampler, one surface interaction of Trace (shade_interaction), the owned-tile / quadrant pixel mapping and the 8-bit resolve.  PTK_CONTRACT selects namespace and arithmetic:
 // 0 (the default: what a file that does not define it gets) namespace ptk, every operation the IEEE operation of the CPU oracle;
 // 1 ptk::fma, the same text for -ffp-contract=fast; 2 ptk::fast, 1 / x, sqrt and 1 / sqrt straight from the hardware as well.
 // Only ptk_kernels.hip is built at levels 1 and 2 (see there).  The committed counter files are tied to this file's sha256
@@ -520,6 +520,214 @@ __device__ __forceinline__ bool sample_direct_light(const PT& P, v3 p, v3 n, v3 
     v3 lColor = V(l1.w, l2.w, l3.x);
     di = muls(mulv(lColor, diffuse), ndl);      // :530
     return true;
+}
+
+// One surface interaction of PathTracer::Trace (pathtracer.cpp:551-727) for the hit W.best of the ray (W.ro, W.rd): emission,
+// Russian roulette, material branch, direction sampling, the light sample of DirectIllumimation.  Returns true when the path
+// ends here; otherwise W holds the next ray to walk (BVH kernels: the shadow ray towards the sampled light - W.occl_tri >= 0,
+// W.best = its light triangle's own hit, Tdi its contribution, nextDir the bounce direction that follows - or the bounce
+// ray itself; FLAT kernel: W the bounce ray and WS the shadow ray, tested in one pass).  Shared by every trace kernel.
+// PLAIN (trace_kernel): every material is opaque and untextured and no triangle is smoothed, so the texture lookups, the UVs,
+// the smoothed and normal-mapped normals and the glass branch are dead code; what remains is the mtype == 0 route, operation
+// for operation and draw for draw.
+template <bool STATS, bool FLAT, bool PLAIN, class PT>
+__device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS, int* stack, Rng& rng, v3& L, v3& T, v3& Tdi, v3& nextDir,
+                                                  int& depth, int& iter, bool& inside, const uint32_t ray, Counters& cnt)
+{
+    const Hit h = W.best;
+    const v3 ro = W.ro, rd = W.rd;
+    if (STATS) cnt.shaded++;
+    const float4* sp4 = P.shade + (size_t)h.tri * SHADE_F4;
+    float4 s0 = ldg4(sp4);
+    int mbits = __float_as_int(s0.w);
+    int matid = PLAIN ? mbits : mbits & 0x7fffffff;
+    bool smoothing = !PLAIN && mbits < 0;
+    const float4* mp = P.mats + (size_t)matid * MAT_F4;
+    // the whole 96-byte material in one batch (two of its words are only needed further down: asked for there,
+    // they cost the block another memory round trip), and the vertex normals of a smoothed triangle with it
+    float4 m0 = ldg4(mp), m1 = ldg4(mp + 1), m2 = ldg4(mp + 2), m3 = ldg4(mp + 3);
+    const float4 notex = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), __int_as_float(-1));
+    float4 m4f = PLAIN ? notex : ldg4(mp + 4), m5f = PLAIN ? notex : ldg4(mp + 5);
+    float4 sn2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), sn3 = sn2, sn4 = sn2;
+    if (smoothing) { sn2 = ldg4(sp4 + 2); sn3 = ldg4(sp4 + 3); sn4 = ldg4(sp4 + 4); }
+    asm volatile("" ::: "memory");
+    int tex_diffuse = __float_as_int(m4f.x), tex_normal = __float_as_int(m4f.y);
+    int tex_emiss = __float_as_int(m4f.z), tex_rough = __float_as_int(m4f.w);
+    int tex_metal = __float_as_int(m5f.x);
+    bool any_tex = !PLAIN && __float_as_int(m5f.z) != 0;
+
+    v3 p = add(ro, muls(rd, h.t));                  // :553
+    float uvx = 0.0f, uvy = 0.0f;
+    if (any_tex)
+    {
+        float4 s1 = ldg4(sp4 + 1), s2 = ldg4(sp4 + 2);
+        float w = 1.0f - h.u - h.v;                 // GetUV :533-536
+        uvx = w * s1.x + h.u * s1.z + h.v * s2.x;
+        uvy = w * s1.y + h.u * s1.w + h.v * s2.y;
+    }
+    v3 n = V(s0.x, s0.y, s0.z);
+    if (smoothing)                                  // :556, GetSmoothNormal :538-543
+    {
+        const float4 s2 = sn2, s3 = sn3, s4 = sn4;
+        float w = 1.0f - h.u - h.v;
+        v3 n1 = V(s2.z, s2.w, s3.x), n2 = V(s3.y, s3.z, s3.w), n3 = V(s4.x, s4.y, s4.z);
+        v3 sn = add(add(muls(n1, w), muls(n2, h.u)), muls(n3, h.v));
+        n = normalize(sn);
+    }
+    if (tex_normal >= 0)                            // :558-566
+    {
+        float4 s4 = ldg4(sp4 + 4), s5 = ldg4(sp4 + 5), s6 = ldg4(sp4 + 6);
+        float4 c = tex2d(P, tex_normal, uvx, uvy);
+        if (STATS) cnt.tex++;
+        v3 nt = V(c.x * 2.0f - 1.0f, c.y * 2.0f - 1.0f, c.z * 2.0f - 1.0f);
+        if (nt.z <= 0.0f) nt = V(nt.x, nt.y, PTK_EPS);
+        nt = normalize(nt);
+        v3 tg = V(s4.w, s5.x, s5.y), bt = V(s5.z, s5.w, s6.x);
+        v3 m = V(tg.x * nt.x + bt.x * nt.y + n.x * nt.z,
+                 tg.y * nt.x + bt.y * nt.y + n.y * nt.z,
+                 tg.z * nt.x + bt.z * nt.y + n.z * nt.z);
+        n = normalize(m);
+    }
+    if (dot(n, rd) > 0.0f) n = neg(n);              // :567-568
+    p = add(p, muls(n, PTK_EPS));                   // :569
+
+    bool ended = false;
+    if (!(iter < P.max_depth)) ended = true;        // :571 terminal bounce: no emission
+    else
+    {
+        v3 diffuse = V(m0.x, m0.y, m0.z);
+        if (tex_diffuse >= 0) { float4 c = tex2d(P, tex_diffuse, uvx, uvy); diffuse = V(c.x, c.y, c.z); if (STATS) cnt.tex++; }
+        v3 emiss = V(m2.x, m2.y, m2.z);
+        if (tex_emiss >= 0) { float4 c = tex2d(P, tex_emiss, uvx, uvy); emiss = V(c.x, c.y, c.z); if (STATS) cnt.tex++; }
+        float roughness = m2.w;
+        if (tex_rough >= 0) { roughness = tex2d_r(P, tex_rough, uvx, uvy); if (STATS) cnt.tex++; }
+        float reflectiveness = m3.x;
+        if (tex_metal >= 0) { reflectiveness = tex2d_r(P, tex_metal, uvx, uvy); if (STATS) cnt.tex++; }
+        const int mtype = PLAIN ? 0 : __float_as_int(m0.w);
+        const v3 specular = V(m1.x, m1.y, m1.z);
+        const float emissI = m1.w;
+
+        depth++; iter++;                            // :586-587
+        const float prob = m3.w;                    // min(0.95, max(diffuse)) of the constant colour
+        if (depth >= P.max_depth)
+        {
+            if (fabsf(rng.next()) > prob) ended = true;     // :590-594, no 1/prob compensation
+        }
+        if (!ended)
+        {
+            v3 r = reflect(rd, n);                  // :596
+            v3 dir;
+            v3 weight;
+            bool diffuse_bounce = false;
+            // the reference spells the same three-way roughness sampler out three times
+            // (:603-624, :679-700) and the hemisphere sampler twice more (:631-636, :717-722);
+            // here the branch only picks the sampler's arguments and ONE call does the work
+            int sampler = 0;                        // 0: mirror direction r, 1: hemisphere about n, 2: lobe about r
+            if (mtype == 0)
+            {
+                if (rng.next() < reflectiveness)    // :601
+                {
+                    sampler = roughness == 1.0f ? 1 : (roughness == 0.0f ? 0 : 2);
+                    iter--;
+                    weight = specular;              // :626
+                }
+                else
+                {
+                    sampler = 1;                    // :631-636
+                    diffuse_bounce = true;
+                    weight = diffuse;               // :638
+                }
+            }
+            else
+            {
+                bool refract = false;
+                v3 refractN = n;
+                if (roughness != 0.0f)              // :645-654
+                {
+                    float w = rng.next() * roughness, th = rng.next();
+                    refractN = sample_about(n, 1.0f - PTK_FLT_EPSILON, r, n, w, th);
+                }
+                float nc = 1.0f, ng = m3.z;
+                float eta = inside ? ng / nc : nc / ng;     // :658
+                float r0 = (nc - ng) / (nc + ng);
+                r0 = r0 * r0;
+                float c = fabsf(dot(rd, refractN));
+                float k = 1.0f - eta * eta * (1.0f - c * c);
+                if (k < 0.0f) refract = false;
+                else
+                {
+                    float re = r0 + (1.0f - r0) * (1.0f - c) * (1.0f - c);    // :668
+                    if (fabsf(rng.next()) < re) refract = false;
+                    else if (rng.next() < reflectiveness) refract = false;
+                    else refract = true;
+                }
+                if (!refract)
+                {
+                    sampler = roughness == 1.0f ? 1 : (roughness == 0.0f ? 0 : 2);
+                    iter--;
+                    weight = specular;              // :702
+                }
+                else if (rng.next() < m3.y)         // :706 translucency
+                {
+                    float a = eta * dot(n, rd) + sqrt_ieee(k);
+                    dir = normalize(sub(muls(rd, eta), muls(refractN, a)));   // :708
+                    p = sub(p, muls(muls(n, PTK_EPS), 2.0f));                  // :709
+                    inside = !inside;
+                    iter--;
+                    weight = diffuse;               // :712
+                    sampler = 3;                    // direction already set
+                }
+                else
+                {
+                    sampler = 1;                    // :717-722
+                    diffuse_bounce = true;
+                    weight = diffuse;               // :724
+                }
+            }
+            if (sampler == 0) dir = r;
+            else if (sampler != 3)
+            {
+                const bool lobe = sampler == 2;
+                float w = rng.next();
+                if (lobe) w = w * roughness;
+                float th = rng.next();
+                dir = sample_about(n, lobe ? 1.0f - PTK_FLT_EPSILON : 1.0f - PTK_EPS, lobe ? r : n, lobe ? r : n, w, th);
+            }
+
+            L = add(L, mulv(T, muls(emiss, emissI)));      // emiss * emissiveIntensity term
+            v3 next_ro = p, next_rd = dir;
+            float4 lt0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), lt1 = lt0, lt2 = lt0;
+            if (diffuse_bounce && P.num_lights > 0)
+            {
+                // DirectIllumimation + SampleTriangle, pathtracer.cpp:494-531
+                const float u_light = rng.next(), u_su = rng.next(), u_sv = rng.next();
+                v3 l, di;
+                int light_tri;
+                if (sample_direct_light(P, p, n, diffuse, u_light, u_su, u_sv, l, di, light_tri, lt0, lt1, lt2))
+                {
+                    Tdi = mulv(T, di);
+                    if (FLAT)
+                    {
+                        // the shadow ray rides along with the bounce ray in the next flat pass, which finds its
+                        // closest hit over ALL triangles (no early end: the pass runs for the bounce ray anyway)
+                        WS.begin(p, l, P.num_nodes, stack, P.scene_bound);
+                        WS.occl_tri = light_tri;
+                    }
+                    else
+                    {
+                        W.occl_tri = light_tri;
+                        nextDir = dir;
+                        next_rd = l;
+                    }
+                }
+            }
+            T = mulv(T, weight);
+            W.begin(next_ro, next_rd, P.num_nodes, stack, P.scene_bound);
+            // a shadow ray meets its light triangle before anything else (see Walk::occl_tri)
+            if (!FLAT && W.occl_tri >= 0) (void)tri_test<STATS>(P, W, lt0, lt1, lt2, rng, ray, cnt);
+        }
+    }
+    return ended;
 }
 
 // ---- owned tiles -> pixels ------------------------------------------------------------------------------------------------

@@ -113,6 +113,12 @@ int pth_read_sample_counts(pth_tracer* t, uint32_t* out) { return t->pt.ReadSamp
 int pth_render_features(pth_tracer* t, uint32_t mask, uint32_t sample) { return t->pt.RenderFeatures(mask, sample) ? 1 : 0; }
 int pth_read_feature(pth_tracer* t, int feature, void* out) { return t->pt.ReadFeature(feature, out) ? 1 : 0; }
 int pth_pick(pth_tracer* t, int x, int y, int* obj, int* elem, int* tri) { return t->pt.Pick(x, y, obj, elem, tri) ? 1 : 0; }
+int pth_trace_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, uint32_t first_sample, uint32_t spp,
+                   uint32_t key_base, uint32_t flags, float* out)
+{
+    return t->pt.TraceRays(num_rays, origins, dirs, first_sample, spp, key_base, flags, out) ? 1 : 0;
+}
+void pth_get_camera(pth_tracer* t, float* pos, float* dir, float* up) { t->pt.GetCamera(pos, dir, up); }
 const char* pth_last_error(pth_tracer* t)
 {
     std::string e = t->pt.LastError();

@@ -35,7 +35,7 @@ HOST_SYMBOLS = [
     "pth_last_error", "pth_context", "pth_staged_scene", "pth_load_scene_file", "pth_pts_roundtrip",
     "pth_trs_matrix", "pth_euler_camera", "pth_triangle_init", "pth_image_load", "pth_image_data", "pth_image_tex2d",
     "pth_export_png", "pth_render_adaptive", "pth_read_sample_counts",
-    "pth_render_features", "pth_read_feature", "pth_pick", "pth_set_object_transform",
+    "pth_render_features", "pth_read_feature", "pth_pick", "pth_set_object_transform", "pth_trace_rays", "pth_get_camera",
 ]
 
 _bound = False
@@ -87,6 +87,13 @@ def _bind_locked(L) -> C.CDLL:
     L.pth_render_features.restype = i32; L.pth_render_features.argtypes = [vp, C.c_uint32, C.c_uint32]
     L.pth_read_feature.restype = i32; L.pth_read_feature.argtypes = [vp, i32, vp]
     L.pth_pick.restype = i32; L.pth_pick.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    try:
+        L.pth_get_camera.restype = None; L.pth_get_camera.argtypes = [vp, _f, _f, _f]
+        L.pth_trace_rays.restype = i32
+        L.pth_trace_rays.argtypes = [vp, i32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    except AttributeError:
+        if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
+            raise
     L.pth_last_error.restype = C.c_char_p; L.pth_last_error.argtypes = [vp]
     L.pth_context.restype = vp; L.pth_context.argtypes = [vp]
     L.pth_staged_scene.restype = C.POINTER(_ptk.SceneDesc); L.pth_staged_scene.argtypes = [vp]
@@ -277,6 +284,28 @@ class PathTracer:
         if not self.L.pth_pick(self.h, int(x), int(y), C.byref(o), C.byref(e), C.byref(t)):
             raise _ptk.PtkError("Pick failed: " + self.LastError())
         return o.value, e.value, t.value
+
+    def GetCamera(self):
+        """Extension: (pos, dir, up) as SetCamera last received them (not normalised), float32 [3] each."""
+        p, d, u = (np.zeros(3, np.float32) for _ in range(3))
+        self.L.pth_get_camera(self.h, _fp(p), _fp(d), _fp(u))
+        return p, d, u
+
+    def TraceRays(self, origins, dirs, first_sample: int, spp: int, key_base: int = 0, out=None, lens_draws: bool = False) -> np.ndarray:
+        """Extension: radiance along caller-supplied rays (include/ptk.h ptk_trace_rays) at this tracer's seed and trace depth;
+        [n, 3] float32 numpy arrays in, the float32 in-order sums over samples [first_sample, first_sample + spp) out.  Valid
+        after BuildBVH(); pending material / geometry edits apply as for RenderFrame().  out: sums of earlier samples to add to."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        assert len(d) == len(o), "as many directions as origins"
+        flags = (_ptk.RAYS_ACCUMULATE if out is not None else 0) | (_ptk.RAYS_LENS_DRAWS if lens_draws else 0)
+        if out is None:
+            out = np.empty((len(o), 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == o.size
+        ptr = (lambda a: a.ctypes.data if len(o) else None)
+        if not self.L.pth_trace_rays(self.h, len(o), ptr(o), ptr(d), int(first_sample), int(spp), int(key_base) & 0xffffffff, flags, ptr(out)):
+            raise _ptk.PtkError("TraceRays failed: " + self.LastError())
+        return out
 
     def ReadAccumulation(self) -> np.ndarray:
         w, h = self.GetResolution()

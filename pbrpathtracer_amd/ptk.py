@@ -82,6 +82,7 @@ SYMBOLS = [
     "ptk_trace_variant", "ptk_scene_is_plain",
     "ptk_feature_info", "ptk_render_features", "ptk_read_feature", "ptk_feature_device_ptr", "ptk_pick",
     "ptk_update_geometry", "ptk_update_geometry_device", "ptk_geometry_info", "ptk_geometry_timing",
+    "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
 ]
 
 
@@ -157,6 +158,9 @@ def _load_locked() -> C.CDLL:
         L.ptk_debug_stall_exchange.argtypes = [vp, i32]
         L.ptk_trace_variant.argtypes = [vp, C.POINTER(C.c_int)]
         L.ptk_scene_is_plain.argtypes = [C.POINTER(SceneDesc)]
+        for fn in (L.ptk_trace_rays, L.ptk_trace_rays_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, i32, u32, u32, u64, u32, u32, vp]
+        L.ptk_last_rays_ms.argtypes = [vp, fp, fp]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -182,6 +186,7 @@ def _load_locked() -> C.CDLL:
 
 
 TRACE_NONE, TRACE_BVH, TRACE_FLAT, TRACE_FLAT_PLAIN = 0, 1, 2, 3      # ptk_trace_variant
+RAYS_ACCUMULATE, RAYS_LENS_DRAWS = 1, 2                               # ptk_trace_rays flags
 
 
 # first-hit feature planes (ptk_render_features): ids, and their names in id order
@@ -371,6 +376,47 @@ class Context:
         tri = C.c_int32(-1); mat = C.c_int32(-1); t = C.c_float(0)
         self._chk(self.L.ptk_pick(self.h, int(x), int(y), int(seed), C.byref(tri), C.byref(mat), C.byref(t)), "ptk_pick")
         return tri.value, mat.value, t.value
+
+    def trace_rays(self, origins, dirs, max_depth: int, first_sample: int, spp: int, seed: int, key_base: int = 0, out=None,
+                   lens_draws: bool = False):
+        """ptk_trace_rays: radiance along the rays (origins[i], dirs[i]) - [n, 3] float32, unit directions - summed in float32 over
+        samples [first_sample, first_sample + spp) in sample order, on the streams of (seed, RNG pixel key_base + i, sample).
+        numpy arrays go through the host entry (synchronous) and give a numpy [n, 3] float32 array.  torch tensors on the context's
+        GPU go through ptk_trace_rays_device with no host copy and give a torch tensor, written on the context's stream: after
+        set_stream(the tensors' stream) everything is ordered on that stream, otherwise synchronise around the call.
+        out: an array / tensor of the same kind that already holds sums of earlier samples; the new ones are added to it in place
+        (PTK_RAYS_ACCUMULATE) and it is returned.  lens_draws: PTK_RAYS_LENS_DRAWS (include/ptk.h)."""
+        flags = (RAYS_ACCUMULATE if out is not None else 0) | (RAYS_LENS_DRAWS if lens_draws else 0)
+        args = (int(max_depth), int(first_sample), int(spp), int(seed), int(key_base) & 0xffffffff, flags)
+        if hasattr(origins, "data_ptr"):
+            import torch
+            dev = self.device_ordinal()
+            n = origins.numel() // 3
+            if out is None:
+                out = torch.empty((n, 3), dtype=torch.float32, device=origins.device)
+            for t in (origins, dirs, out):
+                assert t.is_cuda and t.device.index == dev, f"tensor on {t.device}, context on device {dev}"
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n * 3, "[n, 3] float32 contiguous tensors"
+            ptr = (lambda t: C.c_void_p(t.data_ptr()) if n else None)
+            self._chk(self.L.ptk_trace_rays_device(self.h, n, ptr(origins), ptr(dirs), *args, ptr(out)), "ptk_trace_rays_device")
+            return out
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n, "as many directions as origins"
+        if out is None:
+            out = np.empty((n, 3), np.float32)
+        assert isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.size == n * 3, \
+            "out: a C-contiguous float32 array of n x 3"
+        ptr = (lambda a: a.ctypes.data if n else None)
+        self._chk(self.L.ptk_trace_rays(self.h, n, ptr(o), ptr(d), *args, ptr(out)), "ptk_trace_rays")
+        return out
+
+    def last_rays_ms(self):
+        """(trace_ms, fold_ms): HIP-event times of the last trace_rays call's kernels, summed over its passes; waits for it."""
+        t = C.c_float(0); f = C.c_float(0)
+        self._chk(self.L.ptk_last_rays_ms(self.h, C.byref(t), C.byref(f)), "ptk_last_rays_ms")
+        return t.value, f.value
 
     def read_sample_counts(self) -> np.ndarray:
         """[H][W] uint32 samples per pixel, rows bottom-up like read_accum; 0 = not owned."""

@@ -3,9 +3,13 @@
     python -m pbrpathtracer_amd.render scene.pts --spp 256 --out image.png [--seed S] [--device D]
     python -m pbrpathtracer_amd.render scene.pts --noise-threshold 0.02 [--min-spp 16] [--step 8] --spp 1024
     python -m pbrpathtracer_amd.render scene.pts --features planes.npz
+    python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
 
 With --noise-threshold the render is adaptive (include/ptk.h ptk_render_adaptive): --spp becomes the most samples a pixel
 gets, and pixels stop once their noise meets the threshold.
+
+With --equirect WIDTH the image is a WIDTH x WIDTH/2 latitude-longitude panorama from the scene's camera position, traced through
+PathTracer.TraceRays (include/ptk.h ptk_trace_rays; rays.equirect_rays) instead of the perspective camera.
 
 The headless equivalent of the reference's Start button + Export (main.cpp:3563-3618, :760-771):
 LoadScene -> SendObjectsToPathTracer -> RenderFrame() x spp -> PNG (flipped to top-down)."""
@@ -22,7 +26,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene")
     ap.add_argument("--spp", type=int, default=64)
-    ap.add_argument("--out", default="render.png")
+    ap.add_argument("-o", "--out", default="render.png")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--pinhole", action="store_true", help="SetCameraAperture(0) after loading")
@@ -33,7 +37,36 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--features", metavar="FILE.npz", default=None,
                     help="also write the first-hit feature planes (depth, triangle, material, bary, position, normal_geom, normal, "
                          "albedo, emission, gloss; sample 0) to this .npz, rows top-down like the PNG")
+    ap.add_argument("--equirect", type=int, metavar="WIDTH", default=None,
+                    help="render a WIDTH x WIDTH/2 latitude-longitude panorama about the scene's camera instead of its perspective view")
+    ap.add_argument("--npy", metavar="FILE.npy", default=None,
+                    help="--equirect: also write the float32 sums over the samples, [H, W, 3], rows top-down (mean = sum / spp)")
     return ap
+
+
+def render_equirect(pt, a) -> int:
+    """The panorama: one TraceRays call over the pixel centres' rays, mean = sum / spp resolved to 8 bits by the frame's own rule
+    (pathtracer.cpp:802-812: clamped to [0, 1], NaN to 0, x * 255 truncated)."""
+    from .pathtracer import export_png
+    from .rays import equirect_rays
+    w, h = a.equirect, a.equirect // 2
+    if h < 1 or a.spp < 1:
+        print("error: --equirect needs a width of at least 2 and --spp of at least 1", file=sys.stderr)
+        return 1
+    origins, dirs = equirect_rays(*pt.GetCamera(), w, h)
+    t1 = time.time()
+    total = pt.TraceRays(origins, dirs, 0, a.spp).reshape(h, w, 3)
+    t2 = time.time()
+    with np.errstate(all="ignore"):
+        x = total / np.float32(a.spp)
+    x = np.where(x < 0, np.float32(0), np.where(x > 1, np.float32(1), x))
+    x = np.where(np.isnan(x), np.float32(0), x).astype(np.float32)
+    export_png(a.out, (x * np.float32(255)).astype(np.uint8)[::-1].copy())
+    if a.npy:
+        np.save(a.npy, total)
+    print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {w}x{h} panorama, {a.spp} spp, depth {pt.GetTraceDepth()}: "
+          f"{t2 - t1:.3f} s ({w * h * a.spp / (t2 - t1) / 1e6:.0f} Msamples/s) -> {a.out}")
+    return 0
 
 
 def main(argv=None):
@@ -44,10 +77,16 @@ def main(argv=None):
     pt.LoadSceneFile(a.scene)
     if a.pinhole:
         pt.SetCameraAperture(0.0)
+    pt.SetSeed(a.seed)
+    if a.equirect is not None:
+        try:
+            return render_equirect(pt, a)
+        except RuntimeError as e:
+            print("error:", e, file=sys.stderr)
+            return 1
     w, h = pt.GetResolution()
     out = np.zeros((h, w, 3), np.uint8)
     pt.SetOutImage(out)
-    pt.SetSeed(a.seed)
     t1 = time.time()
     res = None
     if a.noise_threshold is None:
