@@ -1020,12 +1020,17 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
         dfree(c->d_flat_tris);
         if (n > 0 && n <= 16)
         {
-            std::vector<float> flat((size_t)n * TRI_F4 * 4);
+            std::vector<float> flat((size_t)(FLAT_FRAMES_AT + n * FLAT_FRAME_F4) * 4);     // records, room up to FLAT_MAX_TRIS, frame table
             for (int32_t k = 0; k < n; k++)             // record of leaf position k holds triangle bvh.order[k]
                 std::memcpy(flat.data() + (size_t)bvh.order[k] * TRI_F4 * 4, tris.data() + (size_t)k * TRI_F4 * 4, TRI_F4 * 16);
             HIPCHK(c, up((void**)&c->d_flat_tris, flat.data(), flat.size() * 4));
         }
         HIPCHK(c, up((void**)&c->d_shade, shade.data(), shade.size() * 4));
+        if (c->d_flat_tris)                             // the frame table behind the flat records, from the normals just written
+        {
+            launch_flat_frames(c->d_shade, c->d_flat_tris, 0, n, c->stream);
+            HIPCHK(c, hipGetLastError());
+        }
         HIPCHK(c, up((void**)&c->d_verts_res, s->verts, (size_t)n * 9 * sizeof(float)));
     }
     c->built_on_device = on_device;
@@ -1233,6 +1238,7 @@ static int update_geometry(ptk_ctx* c, int32_t first, int32_t count, const float
     HIPCHK(c, hipEventRecord(c->ev_geo_t[2], c->stream));
     launch_repack_geometry(sv, sn, st, first, count, c->d_verts_res, c->d_tri_pos, c->d_tris, c->d_flat_tris, c->d_shade, c->stream);
     launch_repack_lights(c->d_verts_res, first, count, c->d_lights, c->num_lights, c->stream);
+    if (c->d_flat_tris && sn) launch_flat_frames(c->d_shade, c->d_flat_tris, first, count, c->stream);     // (vertices only: the normals stay)
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_geo_t[3], c->stream));
     c->bvh_pad = 1e-5f * std::max(vmax, 1.0f);

@@ -25,6 +25,15 @@ constexpr int32_t NODE_EXIT = INT32_MIN;
 //   t0 = (v0.xyz, e1.x)  t1 = (e1.yz, e2.xy)  t2 = (e2.z, bits tri_index, bits opacity_tex, 0)
 constexpr int TRI_F4 = 3;
 
+// FLAT scenes (<= FLAT_MAX_TRIS triangles): flat_tris holds the same records in ascending triangle index and, behind room for
+// FLAT_MAX_TRIS of them, the frame table [triangle][side][2] = (u.xyz, 0), (v.xyz, 0): the hemisphere sampler's tangent frame
+// (sample_basis) about the stored shading normal s0.xyz (side 0) and about its negation (side 1), which the exact PLAIN kernel
+// reads instead of computing it.  (One allocation at a fixed distance, not a pointer of its own in RenderParams: that struct
+// is embedded by value in other kernels' arguments, whose fields behind it would move.)
+constexpr int FLAT_MAX_TRIS = 16;
+constexpr int FLAT_FRAMES_AT = FLAT_MAX_TRIS * TRI_F4;      // in float4s from flat_tris
+constexpr int FLAT_FRAME_F4 = 4;                            // per triangle
+
 // Shading record, 112 B, indexed by the scene's triangle index (fetched only for the accepted hit):
 //   s0 = (normal.xyz, bits (material | smoothing << 31))
 //   s1 = (uv1.xy, uv2.xy)  s2 = (uv3.xy, n1.xy)  s3 = (n1.z, n2.xyz)  s4 = (n3.xyz, tangent.x)
@@ -150,6 +159,8 @@ void launch_live_list(const RenderParams& p, int num_subtiles, unsigned long lon
 void launch_accumulate(const RenderParams& p, int owned_tiles, hipStream_t stream);
 void launch_pack_owned(const float* accum, float* packed, int width, int height, int rank, int world, hipStream_t stream);
 void launch_unpack_all(const float* packed, const long long* bases, float* image, int width, int height, int world, hipStream_t stream);
+// the frame table behind d_flat_tris for triangles [first, first + count), from their shading records' normals (sample_basis, the exact build's)
+void launch_flat_frames(const float4* d_shade, float4* d_flat_tris, int first, int count, hipStream_t stream);
 void launch_primary(const PrimaryParams& p, hipStream_t stream);
 void launch_primary_hits(const RenderParams& p, float4* out, float4* out_rd, hipStream_t stream);
 void launch_probe(const ProbeParams& p, hipStream_t stream);

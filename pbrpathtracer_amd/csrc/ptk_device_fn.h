@@ -470,16 +470,28 @@ __device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, 
 }
 
 // hemisphere / lobe sampler, pathtracer.cpp:606-611 (:618-623 lobe form): see oracle sample_about()
-__device__ __forceinline__ v3 sample_about(v3 n_for_test, float thr, v3 basis_from, v3 pole, float w, float theta)
+// its tangent frame: depends on the axis the sampler turns about only, not on the draws (for the hemisphere about an unsmoothed,
+// unmapped triangle's normal: one of two values per triangle - fill_flat_frames_kernel tabulates them for the PLAIN kernel)
+__device__ __forceinline__ void sample_basis(v3 n_for_test, float thr, v3 basis_from, v3& u, v3& v)
 {
-    v3 u = fabsf(n_for_test.x) < thr ? cross(V(1.0f, 0.0f, 0.0f), basis_from) : cross(V(1.0f, 1.0f, 1.0f), basis_from);
+    u = fabsf(n_for_test.x) < thr ? cross(V(1.0f, 0.0f, 0.0f), basis_from) : cross(V(1.0f, 1.0f, 1.0f), basis_from);
     u = normalize(u);
-    v3 v = normalize(cross(u, basis_from));
+    v = normalize(cross(u, basis_from));
+}
+// ... and the direction drawn in that frame
+__device__ __forceinline__ v3 sample_in_basis(v3 u, v3 v, v3 pole, float w, float theta)
+{
     float ang = (float)(2.0f * PTK_PI_D * theta);
     float sn, cs;
     sincos_2pi(ang, sn, cs);
     v3 d = add(add(muls(u, w * cs), muls(v, w * sn)), muls(pole, sqrt_ieee(1.0f - w * w)));
     return normalize(d);
+}
+__device__ __forceinline__ v3 sample_about(v3 n_for_test, float thr, v3 basis_from, v3 pole, float w, float theta)
+{
+    v3 u, v;
+    sample_basis(n_for_test, thr, basis_from, u, v);
+    return sample_in_basis(u, v, pole, w, theta);
 }
 
 __device__ __forceinline__ uint32_t pixel_key(uint32_t seed_lo, uint32_t seed_hi, uint32_t pixel)
@@ -522,6 +534,10 @@ __device__ __forceinline__ bool sample_direct_light(const PT& P, v3 p, v3 n, v3 
     return true;
 }
 
+// a triangle's entry of the frame table (see FLAT_FRAMES_AT): both sides; nothing in the kernels that compute the frame
+template <bool ON> struct FlatFrames { float4 u0, v0, u1, v1; };
+template <> struct FlatFrames<false> {};
+
 // One surface interaction of PathTracer::Trace (pathtracer.cpp:551-727) for the hit W.best of the ray (W.ro, W.rd): emission,
 // Russian roulette, material branch, direction sampling, the light sample of DirectIllumimation.  Returns true when the path
 // ends here; otherwise W holds the next ray to walk (BVH kernels: the shadow ray towards the sampled light - W.occl_tri >= 0,
@@ -550,6 +566,15 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
     float4 m4f = PLAIN ? notex : ldg4(mp + 4), m5f = PLAIN ? notex : ldg4(mp + 5);
     float4 sn2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), sn3 = sn2, sn4 = sn2;
     if (smoothing) { sn2 = ldg4(sp4 + 2); sn3 = ldg4(sp4 + 3); sn4 = ldg4(sp4 + 4); }
+    // PLAIN, exact build: the hemisphere sampler's frames about the triangle's two possible normals ride in the same batch (the
+    // table fill_flat_frames_kernel computed with the same operations); asked for by index after the flip test instead - two
+    // loads, not four - they cost the block a memory round trip of its own and half of the gain
+    FlatFrames<PLAIN && !PTK_CONTRACT> frames;
+    if constexpr (PLAIN && !PTK_CONTRACT)
+    {
+        const float4* fp = P.flat_tris + FLAT_FRAMES_AT + h.tri * FLAT_FRAME_F4;
+        frames.u0 = ldg4(fp); frames.v0 = ldg4(fp + 1); frames.u1 = ldg4(fp + 2); frames.v1 = ldg4(fp + 3);
+    }
     asm volatile("" ::: "memory");
     int tex_diffuse = __float_as_int(m4f.x), tex_normal = __float_as_int(m4f.y);
     int tex_emiss = __float_as_int(m4f.z), tex_rough = __float_as_int(m4f.w);
@@ -587,6 +612,13 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
                  tg.y * nt.x + bt.y * nt.y + n.y * nt.z,
                  tg.z * nt.x + bt.z * nt.y + n.z * nt.z);
         n = normalize(m);
+    }
+    v3 frame_u = V(0.0f, 0.0f, 0.0f), frame_v = frame_u;
+    if constexpr (PLAIN && !PTK_CONTRACT)           // n becomes one of the triangle's two possible normals: its frame
+    {
+        const bool flip = dot(n, rd) > 0.0f;
+        frame_u = V(flip ? frames.u1.x : frames.u0.x, flip ? frames.u1.y : frames.u0.y, flip ? frames.u1.z : frames.u0.z);
+        frame_v = V(flip ? frames.v1.x : frames.v0.x, flip ? frames.v1.y : frames.v0.y, flip ? frames.v1.z : frames.v0.z);
     }
     if (dot(n, rd) > 0.0f) n = neg(n);              // :567-568
     p = add(p, muls(n, PTK_EPS));                   // :569
@@ -691,7 +723,14 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
                 float w = rng.next();
                 if (lobe) w = w * roughness;
                 float th = rng.next();
-                dir = sample_about(n, lobe ? 1.0f - PTK_FLT_EPSILON : 1.0f - PTK_EPS, lobe ? r : n, lobe ? r : n, w, th);
+                if constexpr (PLAIN && !PTK_CONTRACT)
+                {
+                    v3 u = frame_u, v = frame_v;
+                    if (lobe) sample_basis(n, 1.0f - PTK_FLT_EPSILON, r, u, v);
+                    dir = sample_in_basis(u, v, lobe ? r : n, w, th);
+                }
+                else
+                    dir = sample_about(n, lobe ? 1.0f - PTK_FLT_EPSILON : 1.0f - PTK_EPS, lobe ? r : n, lobe ? r : n, w, th);
             }
 
             L = add(L, mulv(T, muls(emiss, emissI)));      // emiss * emissiveIntensity term

@@ -7,6 +7,30 @@
 
 namespace ptk {
 
+// The hemisphere sampler's tangent frame (sample_basis) about an unsmoothed, unmapped triangle's shading normal takes two values:
+// one for the stored normal, one for its negation (shade_interaction's flip test).  They are tabulated here for the FLAT scenes'
+// triangles, by the device function and with the arguments the shade block would use - the negated normal's frame is computed from
+// the negated normal, not by negating the other (the signs of zeros differ) - so the PLAIN kernel reads the bits it used to compute.
+// One thread per (triangle, side); a degenerate triangle's NaN normal gives the NaN frame it always gave.
+__global__ __launch_bounds__(64) void fill_flat_frames_kernel(const float4* __restrict__ shade, float4* __restrict__ flat_tris, int first, int count)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= count * 2) return;
+    const int tri = first + (j >> 1), side = j & 1;
+    const float4 s0 = shade[(size_t)tri * SHADE_F4];
+    v3 n = V(s0.x, s0.y, s0.z);
+    if (side) n = neg(n);
+    v3 u, v;
+    sample_basis(n, 1.0f - PTK_EPS, n, u, v);
+    float4* f = flat_tris + FLAT_FRAMES_AT + tri * FLAT_FRAME_F4 + side * 2;
+    f[0] = make_float4(u.x, u.y, u.z, 0.0f);
+    f[1] = make_float4(v.x, v.y, v.z, 0.0f);
+}
+void launch_flat_frames(const float4* d_shade, float4* d_flat_tris, int first, int count, hipStream_t stream)
+{
+    if (count > 0) hipLaunchKernelGGL(fill_flat_frames_kernel, dim3((count * 2 + 63) / 64), dim3(64), 0, stream, d_shade, d_flat_tris, first, count);
+}
+
 // Streaming fold of the sample buffer into the float accumulator, strictly in sample order
 // (`mTotalImg[px] += color` once per RenderFrame(), pathtracer.cpp:798-800), plus the 8-bit resolve
 // (pathtracer.cpp:802-812).  One thread per pixel; each sample read is a coalesced 1 KiB per wave.
