@@ -204,6 +204,15 @@ public:
     // material and geometry edits apply as for RenderFrame(); the image and the sample count are not touched.
     bool TraceRays(int num_rays, const float* origins, const float* dirs, uint32_t first_sample, uint32_t spp, uint32_t key_base,
                    uint32_t flags, float* out);
+    // Extensions: lightmap baking (include/ptk.h ptk_bake_lightmap / ptk_bake_coverage / ptk_lightmap_dilate, host arrays,
+    // synchronous) at the class's seed and trace depth.  uvs: [triangles][6] chart corners, or null for the scene's own uvs;
+    // out: width*height*3 floats, rows bottom-up; owner (may be null): width*height triangle indices, -1 uncovered;
+    // flags = PTK_BAKE_ACCUMULATE | PTK_BAKE_BACK.  Valid after BuildBVH() with no resolution set; pending material and geometry
+    // edits apply as for TraceRays; the image and the sample count are not touched.
+    bool BakeLightmap(int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp, uint32_t key_base,
+                      uint32_t flags, float* out, int32_t* owner = nullptr);
+    bool BakeCoverage(int width, int height, const float* uvs, int32_t* owner, float* bary = nullptr, float* pos = nullptr);
+    bool DilateLightmap(int width, int height, int passes, float* image, int32_t* owner);
     // the camera as SetCamera last received it (position, direction, up; not normalised), 3 floats each
     void GetCamera(float* pos, float* dir, float* up) const;
     // mTotalImg (float RGB, rows bottom-up), W*H*3 floats

@@ -355,6 +355,66 @@ int ptk_trace_rays_device(ptk_ctx* ctx, int32_t num_rays, const float* d_origins
  * its passes (the first 64 of them) - rays_kernel with its one-wave set-up launch, rays_fold_kernel; waits for the call */
 int ptk_last_rays_ms(ptk_ctx* ctx, float* trace_ms, float* fold_ms);
 
+/* ---- lightmap baking: the radiance leaving the scene's surfaces, per texel of a uv chart layout (no counterpart in the reference) --
+ * The surface half of light baking in front of and behind ptk_trace_rays' kernel: a uv rasteriser, a ray generator, a scatter and
+ * a chart-padding pass, all on the GPU from what ptk_upload_scene left resident.  Inputs: the uploaded scene, a lightmap of
+ * width x height texels (each in 1..16384) and a uv table uvs[num_triangles][6] in the layout of ptk_scene_desc.uvs; NULL: the
+ * scene's own uvs as they lie in the shading records.
+ * Coverage.  In texel space, with W = (float)width, H = (float)height: triangle k has a = (u1 * W, v1 * H), b and c likewise; the
+ * centre of texel (x, y) is p = ((float)x + 0.5f, (float)y + 0.5f); rows are bottom-up (v grows with y) like the accumulator, and
+ * there is no wrap: texels exist only for 0 <= x < width, 0 <= y < height.  Every product and difference rounded on its own in float32:
+ *   area = (bx-ax)*(cy-ay) - (by-ay)*(cx-ax)        w1 = (cx-bx)*(py-by) - (cy-by)*(px-bx)
+ *   w2   = (px-ax)*(cy-ay) - (py-ay)*(cx-ax)        w3 = (bx-ax)*(py-ay) - (by-ay)*(px-ax)
+ * Triangle k covers the texel when area is finite and non-zero and w1, w2, w3 are all >= 0 (area > 0) or all <= 0 (area < 0); a
+ * NaN anywhere: not covered.  The texel's OWNER is the smallest covering triangle index; a texel without one is uncovered.  This
+ * rule, not the rasteriser's traversal, decides (its boxes are conservative: one texel wider than floor / ceil of the corners).
+ * Surface point.  b2 = w2 / area, b3 = w3 / area (IEEE division), b1 = (1.0f - b2) - b3, P = ((v1*b1) + (v2*b2)) + (v3*b3) per
+ * component from the resident world-space vertices - the bake sees ptk_update_geometry -; n = the staged face normal (tbn[k][0:3]),
+ * negated under PTK_BAKE_BACK.
+ * Ray.  origin = P + n*offset (the product rounded, then the sum), dir = -n.  The texel's value is the radiance Trace returns along
+ * that ray: what a camera looking straight down at the texel from `offset` away sees - exactly the view-independent outgoing
+ * radiance of the reference's Lambertian surfaces; for glossy or translucent surfaces it is the outgoing radiance ALONG THE NORMAL.
+ * offset must be finite and > 0 and is the caller's choice, typically 1e-3 of the scene extent: the triangle test rejects hits at
+ * t <= 1e-5, so an offset at or below that bakes whatever lies BEHIND the surface.  Whatever the ray hits is the result by
+ * definition - a nearer occluder, or a neighbouring triangle at a chart edge.
+ * Radiance.  For a covered texel of index t = y * width + x:  out[t] = ((base + L(t, first_sample)) + L(t, first_sample + 1)) + ...
+ * in float32, in sample order; base = 0, or out[t] under PTK_BAKE_ACCUMULATE; L(t, s) bit for bit the CPU oracle's
+ * orc_trace_counter(scene, origin, dir, max_depth, seed, (key_base + t) mod 2^32, s, mode 0).  The RNG pixel is the TEXEL INDEX, not
+ * the position in the compacted ray list: editing one chart does not re-key the others, and progressive bakes with
+ * PTK_BAKE_ACCUMULATE equal one long bake.  Uncovered texels are written 0 (left alone under PTK_BAKE_ACCUMULATE).  owner (may be
+ * NULL) receives the owner per texel, -1 where uncovered.
+ * Like ptk_trace_rays the call needs a scene only - no camera, no frame -, touches no frame state, is not cut by ptk_request_exit
+ * and ignores ptk_set_tile, "flat" and "contract"; it is cut into passes by "pass_bytes" as a ray query is, the same bits.
+ *   ptk_bake_coverage:        host arrays, synchronous, no tracing: owner[H][W] and, optionally (NULL: not wanted),
+ *                             bary[H][W][2] = (b2, b3) and pos[H][W][3] = P; both 0 where uncovered.
+ *   ptk_bake_lightmap:        host arrays, synchronous; stages uvs, out (read first under PTK_BAKE_ACCUMULATE) and owner.
+ *   ptk_bake_lightmap_device: every pointer in this GPU's memory, asynchronous on the context's stream (the caller's after
+ *                             ptk_set_stream) - but for ONE small host wait inside the call: the covered count comes back to size
+ *                             the compacted arrays and the trace.
+ *   ptk_lightmap_dilate, ptk_lightmap_dilate_device: chart padding, in place, `passes` times.  In each pass every texel with
+ *                             owner == -1 that has at least one 8-neighbour with owner != -1 in the state BEFORE the pass is filled
+ *                             with the float32 sum of those neighbours' values - added in the order dy = -1, 0, 1 outer,
+ *                             dx = -1, 0, 1 inner - divided by their count as a float; its owner becomes -2: filled, treated as
+ *                             covered by later passes.  Needs no scene.
+ * PTK_ERR_BAD_ARG: a null context, a call before ptk_upload_scene (the bake entries), width or height outside 1..16384, unknown
+ * flag bits, an offset that is not finite or <= 0, null out (dilate: a null array), negative passes.  spp == 0 is PTK_OK: it zeroes
+ * out unless accumulating and still writes owner.  PTK_ERR_LIMIT as for ptk_trace_rays.
+ * Memory, owned by the context, grown to the largest bake so far and freed by ptk_destroy: 4 B per texel (the owner plane, plus a
+ * count per 256 texels), 44 B per COVERED texel (origin, direction, sum, key, texel index), ptk_trace_rays' sample buffer, and
+ * 16 B per texel for ptk_lightmap_dilate.  The host entries also stage their arrays for the length of the call. */
+#define PTK_BAKE_ACCUMULATE 1u
+#define PTK_BAKE_BACK 2u
+int ptk_bake_coverage(ptk_ctx* ctx, int width, int height, const float* uvs, int32_t* owner, float* bary, float* pos);
+int ptk_bake_lightmap(ptk_ctx* ctx, int width, int height, const float* uvs, float offset, int max_depth, uint32_t first_sample,
+                      uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* out /*[H][W][3]*/, int32_t* owner /*[H][W]*/);
+int ptk_bake_lightmap_device(ptk_ctx* ctx, int width, int height, const float* d_uvs, float offset, int max_depth, uint32_t first_sample,
+                             uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, int32_t* d_owner);
+int ptk_lightmap_dilate(ptk_ctx* ctx, int width, int height, int passes, float* image /*[H][W][3]*/, int32_t* owner /*[H][W]*/);
+int ptk_lightmap_dilate_device(ptk_ctx* ctx, int width, int height, int passes, float* d_image, int32_t* d_owner);
+/* measurement hook (tools/bake_timing.py), not part of the feature: HIP-event times of the last bake's kernels - coverage (plane
+ * fill, bake_cover_kernel, the count and its scan), ray generation, the trace (ptk_last_rays_ms splits it), zero fill + scatter */
+int ptk_last_bake_ms(ptk_ctx* ctx, float* coverage_ms, float* raygen_ms, float* trace_ms, float* scatter_ms);
+
 int ptk_samples(ptk_ctx* ctx);         /* GetSamples (pathtracer.cpp:362-365); thread-safe */
 /* Exit (pathtracer.cpp:819-822); thread-safe.  Cuts EVERY render in flight - ptk_render is asynchronous while no output
  * image is bound, so several may be queued: all of them, not only the newest - : passes whose kernels have not started are

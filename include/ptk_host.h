@@ -64,6 +64,12 @@ int  pth_pick(pth_tracer* t, int x, int y, int* obj, int* elem, int* tri);
 /* TraceRays (radiance along caller-supplied rays, include/ptk.h ptk_trace_rays with the tracer's seed and trace depth): 1 on success */
 int  pth_trace_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, uint32_t first_sample, uint32_t spp,
                     uint32_t key_base, uint32_t flags, float* out);
+/* BakeLightmap / BakeCoverage / DilateLightmap (lightmap baking, include/ptk.h ptk_bake_lightmap with the tracer's seed and trace
+ * depth): 1 on success */
+int  pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,
+                       uint32_t key_base, uint32_t flags, float* out, int32_t* owner);
+int  pth_bake_coverage(pth_tracer* t, int width, int height, const float* uvs, int32_t* owner, float* bary, float* pos);
+int  pth_lightmap_dilate(pth_tracer* t, int width, int height, int passes, float* image, int32_t* owner);
 void pth_get_camera(pth_tracer* t, float pos[3], float dir[3], float up[3]);   /* GetCamera (extension): what SetCamera last received */
 const char* pth_last_error(pth_tracer* t);
 ptk_ctx* pth_context(pth_tracer* t);

@@ -882,6 +882,37 @@ bool PathTracer::TraceRays(int num_rays, const float* origins, const float* dirs
     return rc == PTK_OK;
 }
 
+// Lightmap baking (ptk_bake_lightmap, ptk_bake_coverage, ptk_lightmap_dilate) of the scene as the next RenderFrame() would see it
+bool PathTracer::BakeLightmap(int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp, uint32_t key_base,
+                              uint32_t flags, float* out, int32_t* owner)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_bake_lightmap(m->ctx, width, height, uvs, offset, m->max_depth, first_sample, spp, m->seed, key_base, flags, out, owner);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::BakeCoverage(int width, int height, const float* uvs, int32_t* owner, float* bary, float* pos)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_bake_coverage(m->ctx, width, height, uvs, owner, bary, pos);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::DilateLightmap(int width, int height, int passes, float* image, int32_t* owner)
+{
+    if (!m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const int rc = ptk_lightmap_dilate(m->ctx, width, height, passes, image, owner);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 void PathTracer::Exit() { if (m->ctx) ptk_request_exit(m->ctx); }      // :819-822
 
 // ---- extensions -----------------------------------------------------------------------------------------

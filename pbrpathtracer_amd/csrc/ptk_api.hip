@@ -26,6 +26,7 @@
 #include "ptk_adaptive.h"
 #include "ptk_features.h"
 #include "ptk_rays.h"
+#include "ptk_bake.h"
 #include "ptk_refit.h"
 
 using namespace ptk;
@@ -152,6 +153,18 @@ struct ptk_ctx {
     RaysBlock* d_rays_block = nullptr;
     std::vector<hipEvent_t> ev_rays;
     int rays_passes = 0;                         // timed passes of the last call (at most kMaxTimedPasses)
+
+    // lightmap baking (ptk_bake_lightmap), each grown to the largest bake so far: the owner plane (4 B per texel) with the covered
+    // count per block of 256 texels behind it; the compacted rays of the covered texels (origins | dirs | sums | keys | texel
+    // index, 44 B each); the second image + owner plane of ptk_lightmap_dilate (16 B per texel); the covered count's page-locked
+    // read-back word; six events of the last bake: start, behind coverage + count, before and behind the ray generator, behind the
+    // trace, behind the scatter
+    int* d_bake_plane = nullptr; size_t bake_plane_texels = 0;
+    float* d_bake_compact = nullptr; size_t bake_compact_rays = 0;
+    float* d_bake_dilate = nullptr; size_t bake_dilate_texels = 0;
+    uint32_t* h_bake_total = nullptr;
+    hipEvent_t ev_bake[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    bool bake_timed = false, bake_traced = false;
 
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
@@ -775,6 +788,9 @@ void ptk_destroy(ptk_ctx* c)
     free_adaptive(c);
     free_features(c);
     dfree(c->d_rays_samples); dfree(c->d_rays_block);
+    dfree(c->d_bake_plane); dfree(c->d_bake_compact); dfree(c->d_bake_dilate);
+    if (c->h_bake_total) (void)hipHostFree(c->h_bake_total);
+    for (hipEvent_t e : c->ev_bake) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_rays) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
@@ -1686,7 +1702,7 @@ static int check_rays_args(ptk_ctx* c, int32_t num_rays, const float* origins, c
 // where even one sample of every ray exceeds the budget, into blocks of rays - so that no pass's sample buffer exceeds
 // "pass_bytes" or half of the free device memory; a later pass folds onto what the earlier ones left in out.
 static int trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,
-                                uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out)
+                                uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, const uint32_t* d_keys = nullptr)
 {
     c->rays_passes = 0;
     // (a scene without triangles has no tree to walk: every path is black)
@@ -1740,6 +1756,7 @@ static int trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_ori
         const size_t ray0 = g0 * 64, nr = std::min((size_t)num_rays - ray0, block_groups * 64), nb = (nr + 63) / 64;
         r.origins = d_origins + ray0 * 3; r.dirs = d_dirs + ray0 * 3;
         r.num_rays = (int)nr; r.key_base = key_base + (uint32_t)ray0;
+        r.keys = d_keys ? d_keys + ray0 : nullptr;      // (a key per ray: ptk_bake_lightmap)
         for (uint32_t done = 0; done < spp;)
         {
             const uint32_t n = std::min(spp - done, max_pass);
@@ -1819,6 +1836,246 @@ int ptk_last_rays_ms(ptk_ctx* c, float* trace_ms, float* fold_ms)
     }
     if (trace_ms) *trace_ms = t;
     if (fold_ms) *fold_ms = f;
+    return PTK_OK;
+}
+
+// ---- lightmap baking (ptk.h) -------------------------------------------------------------------------------------------------
+static int check_bake_map(ptk_ctx* c, const char* who, int width, int height)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (width < 1 || height < 1 || width > 16384 || height > 16384)
+        return fail(c, PTK_ERR_BAD_ARG, (std::string(who) + ": width and height must be in 1..16384").c_str());
+    return PTK_OK;
+}
+
+static int check_lightmap_args(ptk_ctx* c, int width, int height, float offset, uint32_t flags, const float* out)
+{
+    const int rc = check_bake_map(c, "ptk_bake_lightmap", width, height);
+    if (rc != PTK_OK) return rc;
+    if (flags & ~(PTK_BAKE_ACCUMULATE | PTK_BAKE_BACK)) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_lightmap: unknown flag bits");
+    if (!std::isfinite(offset) || !(offset > 0.0f)) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_lightmap: offset must be finite and > 0");
+    if (!out) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_lightmap: null out");
+    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
+    return PTK_OK;
+}
+
+// Coverage - and, with d_out, the bake - on the context's stream, every pointer into this GPU's memory.
+static int bake_on_stream(ptk_ctx* c, int width, int height, const float* d_uvs, float offset, int max_depth, uint32_t first_sample, uint32_t spp,
+                          uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, int32_t* d_owner, float* d_bary, float* d_pos)
+{
+    const size_t texels = (size_t)width * height, blocks = (texels + 255) / 256;
+    c->bake_timed = false; c->bake_traced = false;
+    for (hipEvent_t& e : c->ev_bake)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    if (texels > c->bake_plane_texels)
+    {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        dfree(c->d_bake_plane); c->d_bake_plane = nullptr; c->bake_plane_texels = 0;
+        // the plane, then one count per block of 256 texels
+        HIPCHK(c, hipMalloc(&c->d_bake_plane, (texels + blocks + 1) * sizeof(int)));
+        c->bake_plane_texels = texels;
+    }
+    BakeParams b = {};
+    b.uvs = d_uvs; b.shade = c->d_shade; b.verts = c->d_verts_res; b.num_tris = c->d_verts_res ? c->num_tris : 0;
+    b.width = width; b.height = height; b.offset = offset; b.back = (flags & PTK_BAKE_BACK) ? 1 : 0; b.key_base = key_base;
+    b.plane = c->d_bake_plane; b.block_counts = (uint32_t*)(c->d_bake_plane + c->bake_plane_texels);
+    b.owner = d_owner; b.bary = d_bary; b.pos = d_pos;
+    HIPCHK(c, hipEventRecord(c->ev_bake[0], c->stream));
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.plane, PTK_BAKE_UNOWNED, texels, c->stream));
+    launch_bake_cover(b, c->stream);
+    HIPCHK(c, hipGetLastError());
+    uint32_t covered = 0;
+    if (d_out)
+    {
+        // the covered count sizes the compacted arrays and the trace: the one host wait of a bake
+        if (!c->h_bake_total) HIPCHK(c, hipHostMalloc((void**)&c->h_bake_total, sizeof(uint32_t), hipHostMallocDefault));
+        uint32_t* d_total = b.block_counts + blocks;
+        launch_bake_count(b, d_total, c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev_bake[1], c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_bake_total, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        covered = *c->h_bake_total;
+        if (covered > texels) return fail(c, PTK_ERR_HIP, "ptk_bake_lightmap: covered count exceeds the map");
+        if (covered > c->bake_compact_rays)
+        {
+            dfree(c->d_bake_compact); c->d_bake_compact = nullptr; c->bake_compact_rays = 0;
+            HIPCHK(c, hipMalloc(&c->d_bake_compact, (size_t)covered * 11 * sizeof(float)));
+            c->bake_compact_rays = covered;
+        }
+        if (covered)
+        {
+            const size_t cap = c->bake_compact_rays;
+            b.origins = c->d_bake_compact; b.dirs = b.origins + cap * 3; b.sums = b.dirs + cap * 3;
+            b.keys = (uint32_t*)(b.sums + cap * 3); b.texel = b.keys + cap;
+            b.out = (flags & PTK_BAKE_ACCUMULATE) ? d_out : nullptr;
+        }
+    }
+    else HIPCHK(c, hipEventRecord(c->ev_bake[1], c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_bake[2], c->stream));
+    launch_bake_rays(b, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_bake[3], c->stream));
+    if (d_out)
+    {
+        if (covered)
+        {
+            const int rc = trace_rays_on_stream(c, (int32_t)covered, b.origins, b.dirs, max_depth, first_sample, spp, seed, 0u,
+                                                (flags & PTK_BAKE_ACCUMULATE) ? PTK_RAYS_ACCUMULATE : 0u, b.sums, b.keys);
+            if (rc != PTK_OK) return rc;
+        }
+        HIPCHK(c, hipEventRecord(c->ev_bake[4], c->stream));
+        if (!(flags & PTK_BAKE_ACCUMULATE)) HIPCHK(c, hipMemsetAsync(d_out, 0, texels * 3 * sizeof(float), c->stream));     // uncovered texels
+        launch_bake_scatter(b.sums, b.texel, covered, d_out, c->stream);
+        HIPCHK(c, hipGetLastError());
+        c->bake_traced = true;
+    }
+    else HIPCHK(c, hipEventRecord(c->ev_bake[4], c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_bake[5], c->stream));
+    c->bake_timed = true;
+    return PTK_OK;
+}
+
+// Host entries: uvs | out | owner | bary | pos staged in one device buffer for the length of the call.
+static int bake_staged(ptk_ctx* c, int width, int height, const float* uvs, float offset, int max_depth, uint32_t first_sample, uint32_t spp,
+                       uint64_t seed, uint32_t key_base, uint32_t flags, float* out, int32_t* owner, float* bary, float* pos)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t texels = (size_t)width * height, n_uv = uvs ? (size_t)c->num_tris * 6 : 0;
+    const size_t words = n_uv + (out ? texels * 3 : 0) + (owner ? texels : 0) + (bary ? texels * 2 : 0) + (pos ? texels * 3 : 0);
+    float* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, std::max<size_t>(words, 1) * sizeof(float)));
+    float* q = d;
+    const float* d_uvs = n_uv ? q : nullptr; q += n_uv;
+    float* d_out = out ? q : nullptr; q += out ? texels * 3 : 0;
+    int32_t* d_owner = owner ? (int32_t*)q : nullptr; q += owner ? texels : 0;
+    float* d_bary = bary ? q : nullptr; q += bary ? texels * 2 : 0;
+    float* d_pos = pos ? q : nullptr;
+    hipError_t e = hipSuccess;
+    int rc = PTK_OK;
+    if (n_uv) e = hipMemcpyAsync(d, uvs, n_uv * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && out && (flags & PTK_BAKE_ACCUMULATE)) e = hipMemcpyAsync(d_out, out, texels * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+    {
+        rc = bake_on_stream(c, width, height, d_uvs, offset, max_depth, first_sample, spp, seed, key_base, flags, d_out, d_owner, d_bary, d_pos);
+        if (rc == PTK_OK && out) e = hipMemcpyAsync(out, d_out, texels * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess && owner) e = hipMemcpyAsync(owner, d_owner, texels * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess && bary) e = hipMemcpyAsync(bary, d_bary, texels * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess && pos) e = hipMemcpyAsync(pos, d_pos, texels * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also on the way out of a failure: the staging buffer may be in use)
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    if (rc != PTK_OK) return rc;
+    if (e != hipSuccess) return fail(c, PTK_ERR_HIP, hipGetErrorString(e));
+    return PTK_OK;
+}
+
+int ptk_bake_coverage(ptk_ctx* c, int width, int height, const float* uvs, int32_t* owner, float* bary, float* pos)
+{
+    const int rc = check_bake_map(c, "ptk_bake_coverage", width, height);
+    if (rc != PTK_OK) return rc;
+    return bake_staged(c, width, height, uvs, 0.0f, 0, 0, 0, 0, 0, 0, nullptr, owner, bary, pos);
+}
+
+int ptk_bake_lightmap(ptk_ctx* c, int width, int height, const float* uvs, float offset, int max_depth, uint32_t first_sample, uint32_t spp,
+                      uint64_t seed, uint32_t key_base, uint32_t flags, float* out, int32_t* owner)
+{
+    const int rc = check_lightmap_args(c, width, height, offset, flags, out);
+    if (rc != PTK_OK) return rc;
+    return bake_staged(c, width, height, uvs, offset, max_depth, first_sample, spp, seed, key_base, flags, out, owner, nullptr, nullptr);
+}
+
+int ptk_bake_lightmap_device(ptk_ctx* c, int width, int height, const float* d_uvs, float offset, int max_depth, uint32_t first_sample, uint32_t spp,
+                             uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, int32_t* d_owner)
+{
+    const int rc = check_lightmap_args(c, width, height, offset, flags, d_out);
+    if (rc != PTK_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return bake_on_stream(c, width, height, d_uvs, offset, max_depth, first_sample, spp, seed, key_base, flags, d_out, d_owner, nullptr, nullptr);
+}
+
+static int check_dilate_args(ptk_ctx* c, int width, int height, int passes, const float* image, const int32_t* owner)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(c, PTK_ERR_BAD_ARG, "ptk_lightmap_dilate: width and height must be in 1..16384");
+    if (passes < 0) return fail(c, PTK_ERR_BAD_ARG, "ptk_lightmap_dilate: negative passes");
+    if (!image || !owner) return fail(c, PTK_ERR_BAD_ARG, "ptk_lightmap_dilate: null array");
+    return PTK_OK;
+}
+
+int ptk_lightmap_dilate_device(ptk_ctx* c, int width, int height, int passes, float* d_image, int32_t* d_owner)
+{
+    const int rc = check_dilate_args(c, width, height, passes, d_image, d_owner);
+    if (rc != PTK_OK || passes == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t texels = (size_t)width * height;
+    if (texels > c->bake_dilate_texels)
+    {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        dfree(c->d_bake_dilate); c->d_bake_dilate = nullptr; c->bake_dilate_texels = 0;
+        HIPCHK(c, hipMalloc(&c->d_bake_dilate, texels * 4 * sizeof(float)));
+        c->bake_dilate_texels = texels;
+    }
+    // ping-pong between the caller's arrays and the context's; an odd number of passes ends in the latter and is copied back
+    float* img[2] = { d_image, c->d_bake_dilate };
+    int32_t* own[2] = { d_owner, (int32_t*)(c->d_bake_dilate + texels * 3) };
+    for (int i = 0; i < passes; i++)
+    {
+        launch_dilate(img[i & 1], own[i & 1], img[(i + 1) & 1], own[(i + 1) & 1], width, height, c->stream);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (passes & 1)
+    {
+        HIPCHK(c, hipMemcpyAsync(d_image, img[1], texels * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_owner, own[1], texels * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    }
+    return PTK_OK;
+}
+
+int ptk_lightmap_dilate(ptk_ctx* c, int width, int height, int passes, float* image, int32_t* owner)
+{
+    int rc = check_dilate_args(c, width, height, passes, image, owner);
+    if (rc != PTK_OK || passes == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t texels = (size_t)width * height;
+    float* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, texels * 4 * sizeof(float)));
+    int32_t* d_owner = (int32_t*)(d + texels * 3);
+    hipError_t e = hipMemcpyAsync(d, image, texels * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_owner, owner, texels * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+    {
+        rc = ptk_lightmap_dilate_device(c, width, height, passes, d, d_owner);
+        if (rc == PTK_OK) e = hipMemcpyAsync(image, d, texels * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess) e = hipMemcpyAsync(owner, d_owner, texels * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    if (rc != PTK_OK) return rc;
+    if (e != hipSuccess) return fail(c, PTK_ERR_HIP, hipGetErrorString(e));
+    return PTK_OK;
+}
+
+int ptk_last_bake_ms(ptk_ctx* c, float* coverage_ms, float* raygen_ms, float* trace_ms, float* scatter_ms)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    float t[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    if (c->bake_timed)
+    {
+        HIPCHK(c, hipEventSynchronize(c->ev_bake[5]));
+        HIPCHK(c, hipEventElapsedTime(&t[0], c->ev_bake[0], c->ev_bake[1]));
+        HIPCHK(c, hipEventElapsedTime(&t[1], c->ev_bake[2], c->ev_bake[3]));
+        HIPCHK(c, hipEventElapsedTime(&t[2], c->ev_bake[3], c->ev_bake[4]));
+        HIPCHK(c, hipEventElapsedTime(&t[3], c->ev_bake[4], c->ev_bake[5]));
+    }
+    if (coverage_ms) *coverage_ms = t[0];
+    if (raygen_ms) *raygen_ms = t[1];
+    if (trace_ms) *trace_ms = t[2];
+    if (scatter_ms) *scatter_ms = t[3];
     return PTK_OK;
 }
 

@@ -118,6 +118,19 @@ int pth_trace_rays(pth_tracer* t, int num_rays, const float* origins, const floa
 {
     return t->pt.TraceRays(num_rays, origins, dirs, first_sample, spp, key_base, flags, out) ? 1 : 0;
 }
+int pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,
+                      uint32_t key_base, uint32_t flags, float* out, int32_t* owner)
+{
+    return t->pt.BakeLightmap(width, height, uvs, offset, first_sample, spp, key_base, flags, out, owner) ? 1 : 0;
+}
+int pth_bake_coverage(pth_tracer* t, int width, int height, const float* uvs, int32_t* owner, float* bary, float* pos)
+{
+    return t->pt.BakeCoverage(width, height, uvs, owner, bary, pos) ? 1 : 0;
+}
+int pth_lightmap_dilate(pth_tracer* t, int width, int height, int passes, float* image, int32_t* owner)
+{
+    return t->pt.DilateLightmap(width, height, passes, image, owner) ? 1 : 0;
+}
 void pth_get_camera(pth_tracer* t, float* pos, float* dir, float* up) { t->pt.GetCamera(pos, dir, up); }
 const char* pth_last_error(pth_tracer* t)
 {

@@ -14,6 +14,7 @@ struct RaysParams {
     int num_rays;
     uint32_t key_base;          // ray i draws from the streams of RNG pixel key_base + i (mod 2^32)
     int lens_draws;             // 1: every stream starts behind the two SampleCircle draws of a camera ray
+    const uint32_t* keys;       // [num_rays] or null; not null: ray i draws from the streams of RNG pixel keys[i] (rays_keyed_kernel)
 };
 
 // One launch's device block: the item counter on a 128-B line of its own, then the parameters, which the kernel reads through the

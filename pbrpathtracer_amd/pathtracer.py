@@ -36,6 +36,7 @@ HOST_SYMBOLS = [
     "pth_trs_matrix", "pth_euler_camera", "pth_triangle_init", "pth_image_load", "pth_image_data", "pth_image_tex2d",
     "pth_export_png", "pth_render_adaptive", "pth_read_sample_counts",
     "pth_render_features", "pth_read_feature", "pth_pick", "pth_set_object_transform", "pth_trace_rays", "pth_get_camera",
+    "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate",
 ]
 
 _bound = False
@@ -91,6 +92,10 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_get_camera.restype = None; L.pth_get_camera.argtypes = [vp, _f, _f, _f]
         L.pth_trace_rays.restype = i32
         L.pth_trace_rays.argtypes = [vp, i32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.pth_bake_lightmap.restype = i32
+        L.pth_bake_lightmap.argtypes = [vp, i32, i32, vp, f32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+        L.pth_bake_coverage.restype = i32; L.pth_bake_coverage.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+        L.pth_lightmap_dilate.restype = i32; L.pth_lightmap_dilate.argtypes = [vp, i32, i32, i32, vp, vp]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -306,6 +311,47 @@ class PathTracer:
         if not self.L.pth_trace_rays(self.h, len(o), ptr(o), ptr(d), int(first_sample), int(spp), int(key_base) & 0xffffffff, flags, ptr(out)):
             raise _ptk.PtkError("TraceRays failed: " + self.LastError())
         return out
+
+    def _chart_uvs(self, uvs):
+        if uvs is None:
+            return None, None
+        u = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 6)
+        assert len(u) == self.GetTriangleCount(), "one chart (6 floats) per triangle"
+        return u, u.ctypes.data
+
+    def BakeLightmap(self, width: int, height: int, offset: float, first_sample: int, spp: int, uvs=None, key_base: int = 0, out=None,
+                     back: bool = False):
+        """Extension: bake a width x height lightmap (include/ptk.h ptk_bake_lightmap) at this tracer's seed and trace depth.
+        uvs: [triangles, 6] chart corners (lightmap.grid_atlas), None for the scene's own.  Returns (sums [H, W, 3] float32, rows
+        bottom-up; owner [H, W] int32, -1 uncovered).  out: sums of earlier samples to add to (PTK_BAKE_ACCUMULATE)."""
+        u, up = self._chart_uvs(uvs)
+        flags = (_ptk.BAKE_ACCUMULATE if out is not None else 0) | (_ptk.BAKE_BACK if back else 0)
+        if out is None:
+            out = np.empty((height, width, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == width * height * 3
+        owner = np.empty((height, width), np.int32)
+        if not self.L.pth_bake_lightmap(self.h, int(width), int(height), up, float(offset), int(first_sample), int(spp),
+                                        int(key_base) & 0xffffffff, flags, out.ctypes.data, owner.ctypes.data):
+            raise _ptk.PtkError("BakeLightmap failed: " + self.LastError())
+        return out, owner
+
+    def BakeCoverage(self, width: int, height: int, uvs=None):
+        """Extension: (owner [H, W] int32, bary [H, W, 2], pos [H, W, 3]) of a lightmap's texels (ptk_bake_coverage); no tracing."""
+        u, up = self._chart_uvs(uvs)
+        owner = np.empty((height, width), np.int32)
+        bary = np.empty((height, width, 2), np.float32); pos = np.empty((height, width, 3), np.float32)
+        if not self.L.pth_bake_coverage(self.h, int(width), int(height), up, owner.ctypes.data, bary.ctypes.data, pos.ctypes.data):
+            raise _ptk.PtkError("BakeCoverage failed: " + self.LastError())
+        return owner, bary, pos
+
+    def DilateLightmap(self, image: np.ndarray, owner: np.ndarray, passes: int):
+        """Extension: chart padding in place (ptk_lightmap_dilate); returns (image, owner)."""
+        h, w = owner.shape
+        assert image.dtype == np.float32 and image.flags.c_contiguous and image.size == w * h * 3
+        assert owner.dtype == np.int32 and owner.flags.c_contiguous
+        if not self.L.pth_lightmap_dilate(self.h, w, h, int(passes), image.ctypes.data, owner.ctypes.data):
+            raise _ptk.PtkError("DilateLightmap failed: " + self.LastError())
+        return image, owner
 
     def ReadAccumulation(self) -> np.ndarray:
         w, h = self.GetResolution()

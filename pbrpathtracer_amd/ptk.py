@@ -83,6 +83,8 @@ SYMBOLS = [
     "ptk_feature_info", "ptk_render_features", "ptk_read_feature", "ptk_feature_device_ptr", "ptk_pick",
     "ptk_update_geometry", "ptk_update_geometry_device", "ptk_geometry_info", "ptk_geometry_timing",
     "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
+    "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
+    "ptk_last_bake_ms",
 ]
 
 
@@ -161,6 +163,12 @@ def _load_locked() -> C.CDLL:
         for fn in (L.ptk_trace_rays, L.ptk_trace_rays_device):
             fn.argtypes = [vp, C.c_int32, vp, vp, i32, u32, u32, u64, u32, u32, vp]
         L.ptk_last_rays_ms.argtypes = [vp, fp, fp]
+        L.ptk_bake_coverage.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+        for fn in (L.ptk_bake_lightmap, L.ptk_bake_lightmap_device):
+            fn.argtypes = [vp, i32, i32, vp, f32, i32, u32, u32, u64, u32, u32, vp, vp]
+        for fn in (L.ptk_lightmap_dilate, L.ptk_lightmap_dilate_device):
+            fn.argtypes = [vp, i32, i32, i32, vp, vp]
+        L.ptk_last_bake_ms.argtypes = [vp, fp, fp, fp, fp]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -187,6 +195,7 @@ def _load_locked() -> C.CDLL:
 
 TRACE_NONE, TRACE_BVH, TRACE_FLAT, TRACE_FLAT_PLAIN = 0, 1, 2, 3      # ptk_trace_variant
 RAYS_ACCUMULATE, RAYS_LENS_DRAWS = 1, 2                               # ptk_trace_rays flags
+BAKE_ACCUMULATE, BAKE_BACK = 1, 2                                     # ptk_bake_lightmap flags
 
 
 # first-hit feature planes (ptk_render_features): ids, and their names in id order
@@ -417,6 +426,80 @@ class Context:
         t = C.c_float(0); f = C.c_float(0)
         self._chk(self.L.ptk_last_rays_ms(self.h, C.byref(t), C.byref(f)), "ptk_last_rays_ms")
         return t.value, f.value
+
+    # ---- lightmap baking -------------------------------------------------------------------
+    def _bake_uvs(self, uvs, torch_side: bool):
+        if uvs is None:
+            return None, None
+        if torch_side:
+            assert hasattr(uvs, "data_ptr") and uvs.is_cuda and uvs.is_contiguous() and str(uvs.dtype) == "torch.float32", \
+                "uvs: a float32 contiguous tensor on the context's GPU, like out"
+            return uvs, C.c_void_p(uvs.data_ptr())
+        u = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 6)
+        return u, u.ctypes.data
+
+    def bake_coverage(self, width: int, height: int, uvs=None):
+        """ptk_bake_coverage: (owner [H, W] int32, -1 uncovered; bary [H, W, 2] = (b2, b3); pos [H, W, 3]) of a width x height
+        lightmap over the chart corners uvs [triangles, 6] (None: the scene's own uvs); rows bottom-up; no tracing."""
+        u, up = self._bake_uvs(uvs, False)
+        owner = np.empty((height, width), np.int32)
+        bary = np.empty((height, width, 2), np.float32); pos = np.empty((height, width, 3), np.float32)
+        self._chk(self.L.ptk_bake_coverage(self.h, int(width), int(height), up, owner.ctypes.data, bary.ctypes.data, pos.ctypes.data),
+                  "ptk_bake_coverage")
+        return owner, bary, pos
+
+    def bake_lightmap(self, width: int, height: int, offset: float, max_depth: int, first_sample: int, spp: int, seed: int, uvs=None,
+                      key_base: int = 0, out=None, back: bool = False, device: bool = False):
+        """ptk_bake_lightmap: (sums [H, W, 3] float32, owner [H, W] int32) of a width x height lightmap - the float32 in-order sums
+        over samples [first_sample, first_sample + spp) of the radiance along each covered texel's ray (origin = P + n * offset,
+        direction -n), on the streams of (seed, RNG pixel key_base + texel index, sample); rows bottom-up.
+        numpy arrays (or nothing) go through the host entry (synchronous).  With a torch tensor for uvs or out - or device=True -
+        the call is ptk_bake_lightmap_device with no host copy: tensors on the context's GPU in and out, written on the context's
+        stream.  out: sums of earlier samples, added to in place (PTK_BAKE_ACCUMULATE).  back: PTK_BAKE_BACK."""
+        flags = (BAKE_ACCUMULATE if out is not None else 0) | (BAKE_BACK if back else 0)
+        args = (float(offset), int(max_depth), int(first_sample), int(spp), int(seed), int(key_base) & 0xffffffff, flags)
+        if device or hasattr(uvs, "data_ptr") or hasattr(out, "data_ptr"):
+            import torch
+            dev = torch.device("cuda", self.device_ordinal())
+            u, up = self._bake_uvs(uvs, True)
+            if out is None:
+                out = torch.empty((height, width, 3), dtype=torch.float32, device=dev)
+            owner = torch.empty((height, width), dtype=torch.int32, device=dev)
+            assert out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() \
+                and out.numel() == width * height * 3, "out: a [H, W, 3] float32 contiguous tensor on the context's GPU"
+            self._chk(self.L.ptk_bake_lightmap_device(self.h, int(width), int(height), up, *args, C.c_void_p(out.data_ptr()),
+                                                      C.c_void_p(owner.data_ptr())), "ptk_bake_lightmap_device")
+            return out, owner
+        u, up = self._bake_uvs(uvs, False)
+        if out is None:
+            out = np.empty((height, width, 3), np.float32)
+        assert isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.size == width * height * 3, \
+            "out: a C-contiguous float32 array of H x W x 3"
+        owner = np.empty((height, width), np.int32)
+        self._chk(self.L.ptk_bake_lightmap(self.h, int(width), int(height), up, *args, out.ctypes.data, owner.ctypes.data), "ptk_bake_lightmap")
+        return out, owner
+
+    def dilate_lightmap(self, image, owner, passes: int):
+        """ptk_lightmap_dilate: chart padding in place, `passes` times; numpy arrays (host entry) or torch tensors on the context's
+        GPU (device entry, on the context's stream).  image [H, W, 3] float32, owner [H, W] int32; returns (image, owner)."""
+        h, w = owner.shape
+        if hasattr(image, "data_ptr"):
+            import torch
+            assert image.is_cuda and owner.is_cuda and image.is_contiguous() and owner.is_contiguous()
+            assert image.dtype == torch.float32 and owner.dtype == torch.int32 and image.numel() == w * h * 3
+            self._chk(self.L.ptk_lightmap_dilate_device(self.h, w, h, int(passes), C.c_void_p(image.data_ptr()), C.c_void_p(owner.data_ptr())),
+                      "ptk_lightmap_dilate_device")
+            return image, owner
+        assert image.dtype == np.float32 and image.flags["C_CONTIGUOUS"] and image.size == w * h * 3
+        assert owner.dtype == np.int32 and owner.flags["C_CONTIGUOUS"]
+        self._chk(self.L.ptk_lightmap_dilate(self.h, w, h, int(passes), image.ctypes.data, owner.ctypes.data), "ptk_lightmap_dilate")
+        return image, owner
+
+    def last_bake_ms(self) -> dict:
+        """HIP-event times (ms) of the last bake's kernels: coverage, ray generation, trace, scatter; waits for it."""
+        t = [C.c_float(0) for _ in range(4)]
+        self._chk(self.L.ptk_last_bake_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_bake_ms")
+        return dict(zip(("coverage_ms", "raygen_ms", "trace_ms", "scatter_ms"), (x.value for x in t)))
 
     def read_sample_counts(self) -> np.ndarray:
         """[H][W] uint32 samples per pixel, rows bottom-up like read_accum; 0 = not owned."""

@@ -4,12 +4,18 @@
     python -m pbrpathtracer_amd.render scene.pts --noise-threshold 0.02 [--min-spp 16] [--step 8] --spp 1024
     python -m pbrpathtracer_amd.render scene.pts --features planes.npz
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
+    python -m pbrpathtracer_amd.render scene.pts --bake-lightmap 1024 --spp 64 [--bake-atlas] [--bake-offset F] [--bake-back]
+                                                 [--dilate K] -o map.png [--npy map.npy]
 
 With --noise-threshold the render is adaptive (include/ptk.h ptk_render_adaptive): --spp becomes the most samples a pixel
 gets, and pixels stop once their noise meets the threshold.
 
 With --equirect WIDTH the image is a WIDTH x WIDTH/2 latitude-longitude panorama from the scene's camera position, traced through
 PathTracer.TraceRays (include/ptk.h ptk_trace_rays; rays.equirect_rays) instead of the perspective camera.
+
+With --bake-lightmap SIZE the image is a SIZE x SIZE lightmap (include/ptk.h ptk_bake_lightmap): per texel of the scene's own uv
+layout - or, with --bake-atlas, of lightmap.grid_atlas, one chart per triangle - the radiance leaving the surface along its normal,
+baked by PathTracer.BakeLightmap and padded by --dilate K passes of ptk_lightmap_dilate.
 
 The headless equivalent of the reference's Start button + Export (main.cpp:3563-3618, :760-771):
 LoadScene -> SendObjectsToPathTracer -> RenderFrame() x spp -> PNG (flipped to top-down)."""
@@ -41,7 +47,54 @@ def build_parser() -> argparse.ArgumentParser:
                     help="render a WIDTH x WIDTH/2 latitude-longitude panorama about the scene's camera instead of its perspective view")
     ap.add_argument("--npy", metavar="FILE.npy", default=None,
                     help="--equirect: also write the float32 sums over the samples, [H, W, 3], rows top-down (mean = sum / spp)")
+    ap.add_argument("--bake-lightmap", type=int, metavar="SIZE", default=None,
+                    help="bake a SIZE x SIZE lightmap over the scene's uvs instead of rendering a view; the PNG holds the mean "
+                         "(sum / spp) resolved like a frame, rows top-down; --npy the float32 sums [SIZE, SIZE, 3], rows bottom-up as baked")
+    ap.add_argument("--bake-atlas", action="store_true", help="--bake-lightmap: lay the triangles out with lightmap.grid_atlas")
+    ap.add_argument("--bake-offset", type=float, default=None,
+                    help="--bake-lightmap: distance of the ray origins from the surface (default: 1e-3 of the scene extent)")
+    ap.add_argument("--bake-back", action="store_true", help="--bake-lightmap: bake the back side (PTK_BAKE_BACK)")
+    ap.add_argument("--dilate", type=int, default=0, metavar="K", help="--bake-lightmap: chart padding passes")
     return ap
+
+
+def resolve_mean(total, spp):
+    """mean = sum / spp resolved to 8 bits by the frame's own rule (pathtracer.cpp:802-812: clamped to [0, 1], NaN to 0, x * 255
+    truncated)"""
+    with np.errstate(all="ignore"):
+        x = total / np.float32(spp)
+    x = np.where(x < 0, np.float32(0), np.where(x > 1, np.float32(1), x))
+    x = np.where(np.isnan(x), np.float32(0), x).astype(np.float32)
+    return (x * np.float32(255)).astype(np.uint8)
+
+
+def bake_offset(pt) -> float:
+    """the default --bake-offset: 1e-3 of the largest side of the staged scene's bounding box"""
+    v = np.asarray(pt.StagedScene()["verts"], np.float64).reshape(-1, 3)
+    return float(np.float32(1e-3 * (v.max(axis=0) - v.min(axis=0)).max())) if len(v) else 1e-3
+
+
+def render_lightmap(pt, a) -> int:
+    from .lightmap import grid_atlas
+    from .pathtracer import export_png
+    size = a.bake_lightmap
+    if size < 1 or size > 16384 or a.spp < 1 or a.dilate < 0:
+        print("error: --bake-lightmap needs a size in 1..16384, --spp of at least 1 and --dilate of at least 0", file=sys.stderr)
+        return 1
+    uvs = grid_atlas(pt.GetTriangleCount(), size, size) if a.bake_atlas else None
+    offset = a.bake_offset if a.bake_offset is not None else bake_offset(pt)
+    t1 = time.time()
+    total, owner = pt.BakeLightmap(size, size, offset, 0, a.spp, uvs=uvs, back=a.bake_back)
+    covered = int((owner >= 0).sum())
+    if a.dilate:
+        pt.DilateLightmap(total, owner, a.dilate)
+    t2 = time.time()
+    export_png(a.out, resolve_mean(total, a.spp))       # (the bake's rows are bottom-up, as export_png takes them: top-down in the file)
+    if a.npy:
+        np.save(a.npy, total)
+    print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {size}x{size} lightmap, {covered} texels covered, {a.spp} spp, "
+          f"depth {pt.GetTraceDepth()}, offset {offset:g}: {t2 - t1:.3f} s ({covered * a.spp / (t2 - t1) / 1e6:.0f} Msamples/s) -> {a.out}")
+    return 0
 
 
 def render_equirect(pt, a) -> int:
@@ -78,6 +131,12 @@ def main(argv=None):
     if a.pinhole:
         pt.SetCameraAperture(0.0)
     pt.SetSeed(a.seed)
+    if a.bake_lightmap is not None:
+        try:
+            return render_lightmap(pt, a)
+        except (RuntimeError, ValueError) as e:
+            print("error:", e, file=sys.stderr)
+            return 1
     if a.equirect is not None:
         try:
             return render_equirect(pt, a)
