@@ -213,6 +213,16 @@ public:
                       uint32_t flags, float* out, int32_t* owner = nullptr);
     bool BakeCoverage(int width, int height, const float* uvs, int32_t* owner, float* bary = nullptr, float* pos = nullptr);
     bool DilateLightmap(int width, int height, int passes, float* image, int32_t* owner);
+    // Extensions: irradiance probe baking (include/ptk.h ptk_bake_probes / ptk_probes_irradiance, host arrays, synchronous) at the
+    // class's seed and trace depth.  positions: num_probes*3 floats; dirs: num_dirs*3 floats, used as given; radiance (may be null
+    // unless flags has PTK_PROBES_ACCUMULATE): num_probes*num_dirs*3 sums; coefs: num_probes*27 floats.  Valid after BuildBVH() with
+    // no resolution set; pending material and geometry edits apply as for TraceRays; the image and the sample count are not touched.
+    bool BakeProbes(int num_probes, const float* positions, int num_dirs, const float* dirs, uint32_t first_sample, uint32_t spp,
+                    uint32_t key_base, uint32_t flags, float weight, float* radiance, float* coefs);
+    // out[i] = the irradiance the probe grid (dims, origin, spacing; coefs as BakeProbes wrote them for its probes in x-fastest
+    // order) gives at (points[i], normals[i]); needs no scene
+    bool SampleProbes(const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs, int num_points,
+                      const float* points, const float* normals, float* out);
     // the camera as SetCamera last received it (position, direction, up; not normalised), 3 floats each
     void GetCamera(float* pos, float* dir, float* up) const;
     // mTotalImg (float RGB, rows bottom-up), W*H*3 floats

@@ -415,6 +415,64 @@ int ptk_lightmap_dilate_device(ptk_ctx* ctx, int width, int height, int passes, 
  * fill, bake_cover_kernel, the count and its scan), ray generation, the trace (ptk_last_rays_ms splits it), zero fill + scatter */
 int ptk_last_bake_ms(ptk_ctx* ctx, float* coverage_ms, float* raygen_ms, float* trace_ms, float* scatter_ms);
 
+/* ---- irradiance probe baking: radiance gathered at points in space, stored as 9 spherical-harmonic coefficients per probe and
+ * channel, looked up by position and normal (no counterpart in the reference) --
+ * The volume half of light baking - what lights anything that moves -, in front of and behind ptk_trace_rays' kernel: a ray
+ * generator, a projection and a sampler on the GPU.  Every float below is an individual IEEE float32 operation in the order written.
+ * Rays.  Ray r = p * num_dirs + j starts at positions[p] along dirs[j]; the direction is used as given (normalising is the
+ * caller's business, as for ptk_trace_rays); its RNG pixel is (key_base + r) mod 2^32; no lens draws are consumed.
+ * Radiance table.  S[p][j] = ((base + L(r, first_sample)) + L(r, first_sample + 1)) + ... in sample order; base = 0, or
+ * radiance[p][j] under PTK_PROBES_ACCUMULATE (which needs radiance != NULL); L(r, s) bit for bit the CPU oracle's
+ * orc_trace_counter(scene, positions[p], dirs[j], max_depth, seed, (key_base + r) mod 2^32, s, mode 0) - exactly what
+ * ptk_trace_rays returns for the expanded ray list.  With radiance == NULL the table lives in a buffer of the context's.
+ * Basis.  With (x, y, z) = dirs[j] and these float32 literals:
+ *   Y0 = 0.282095f               Y1 = 0.488603f*y             Y2 = 0.488603f*z             Y3 = 0.488603f*x
+ *   Y4 = 1.092548f*(x*y)         Y5 = 1.092548f*(y*z)         Y6 = 0.315392f*((3.0f*(z*z)) - 1.0f)
+ *   Y7 = 1.092548f*(x*z)         Y8 = 0.546274f*((x*x) - (y*y))
+ * Projection, always from the FULL table S, so that progressive bakes under PTK_PROBES_ACCUMULATE equal one long bake:
+ *   acc = 0; for j = 0 .. num_dirs-1 ascending: acc = acc + (S[p][j][ch] * Yk(j));  coefs[p][k][ch] = acc * weight.
+ * weight is the caller's and must be finite; for a uniform direction set it is 4 pi / (num_dirs * total samples).
+ * Irradiance.  A grid of dims = (nx, ny, nz) probes, probe (ix, iy, iz) at origin + i * spacing with index (iz*ny + iy)*nx + ix.
+ * Per axis a with n = dims[a], for the query point q:
+ *   g = (q_a - origin_a) / spacing_a;  g = g > 0 ? g : 0 (NaN gives 0);  top = (float)(n-1);  g = g < top ? g : top;
+ *   i0 = (int)g;  if (i0 > n-2) i0 = max(n-2, 0);  f = g - (float)i0;  i1 = min(i0+1, n-1).
+ * With lerp(a, b, f) = a + ((b - a) * f), per coefficient k and channel: along x for the four (y, z) corner pairs, then along y -
+ * c0 = lerp(c(y0,z0), c(y1,z0), fy), c1 = lerp(c(y0,z1), c(y1,z1), fy) -, then c = lerp(c0, c1, fz).  With A = 3.141593f (k = 0),
+ * 2.094395f (k = 1..3), 0.785398f (k = 4..8) and Yk taken at the query normal:
+ *   E = (A*c[0])*Y0;  for k = 1..8: E = E + ((A*c[k]) * Yk).
+ * Points outside the grid take the boundary's value.  There is NO visibility weighting: a probe behind a wall leaks into the room
+ * in front of it; leak handling is out of scope.
+ * Like ptk_trace_rays the bake entries need a scene only - no camera, no frame -, read the scene as material and geometry edits
+ * left it, touch no frame, adaptive or feature state, are not cut by ptk_request_exit and ignore ptk_set_tile, "flat" and
+ * "contract".  A bake is cut into blocks of whole probes of at most max(num_dirs, "pass_bytes" / 256) rays, each a ray query of its
+ * own (and cut into passes as one): the same bits.  ptk_probes_irradiance needs no scene.
+ *   ptk_bake_probes, ptk_probes_irradiance:                host arrays, synchronous; staged for the length of the call.
+ *   ptk_bake_probes_device, ptk_probes_irradiance_device:  every array in this GPU's memory (dims, origin, spacing stay host
+ *                             arrays), asynchronous on the context's stream (the caller's after ptk_set_stream).
+ * PTK_ERR_BAD_ARG: a null context, a bake before ptk_upload_scene, a negative count, num_dirs outside 1..65536 when num_probes > 0,
+ * num_probes * num_dirs >= 2^31, a null array with a non-zero count (radiance may be NULL), PTK_PROBES_ACCUMULATE with NULL radiance,
+ * unknown flag bits, a weight that is not finite; a dims entry < 1 (or 2^31 probes or more), a spacing that is not finite or <= 0,
+ * an origin that is not finite.  Zero probes or zero points: PTK_OK, nothing is done.  spp == 0 is PTK_OK: S becomes 0 - or stays
+ * what it was under PTK_PROBES_ACCUMULATE - and coefs is still written.  PTK_ERR_LIMIT as for ptk_trace_rays.
+ * Memory, owned by the context, grown to the largest call so far and freed by ptk_destroy: 36 B per direction (the basis table),
+ * 24 B per ray of ONE block, 12 B per ray for S while the caller passes no radiance table, and ptk_trace_rays' sample buffer. */
+#define PTK_PROBES_ACCUMULATE 1u
+int ptk_bake_probes(ptk_ctx* ctx, int32_t num_probes, const float* positions /*[P][3]*/, int32_t num_dirs, const float* dirs /*[D][3]*/,
+                    int max_depth, uint32_t first_sample, uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float weight,
+                    float* radiance /*[P][D][3], may be NULL without ACCUMULATE*/, float* coefs /*[P][9][3]*/);
+int ptk_bake_probes_device(ptk_ctx* ctx, int32_t num_probes, const float* d_positions, int32_t num_dirs, const float* d_dirs, int max_depth,
+                           uint32_t first_sample, uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float weight,
+                           float* d_radiance, float* d_coefs);
+int ptk_probes_irradiance(ptk_ctx* ctx, const int32_t dims[3], const float origin[3], const float spacing[3],
+                          const float* coefs /*[nz][ny][nx][9][3]*/, int32_t num_points, const float* points /*[n][3]*/,
+                          const float* normals /*[n][3]*/, float* out /*[n][3]*/);
+int ptk_probes_irradiance_device(ptk_ctx* ctx, const int32_t dims[3], const float origin[3], const float spacing[3], const float* d_coefs,
+                                 int32_t num_points, const float* d_points, const float* d_normals, float* d_out);
+/* measurement hook (tools/probes_timing.py), not part of the feature: HIP-event times of the last probe bake's kernels - ray
+ * generation (the basis table and probe_rays_kernel), the trace (rays_kernel and its fold), the projection - summed over its blocks
+ * of probes (the first 64 of them); waits for the call */
+int ptk_last_probes_ms(ptk_ctx* ctx, float* raygen_ms, float* trace_ms, float* project_ms);
+
 int ptk_samples(ptk_ctx* ctx);         /* GetSamples (pathtracer.cpp:362-365); thread-safe */
 /* Exit (pathtracer.cpp:819-822); thread-safe.  Cuts EVERY render in flight - ptk_render is asynchronous while no output
  * image is bound, so several may be queued: all of them, not only the newest - : passes whose kernels have not started are

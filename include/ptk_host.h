@@ -70,6 +70,12 @@ int  pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, f
                        uint32_t key_base, uint32_t flags, float* out, int32_t* owner);
 int  pth_bake_coverage(pth_tracer* t, int width, int height, const float* uvs, int32_t* owner, float* bary, float* pos);
 int  pth_lightmap_dilate(pth_tracer* t, int width, int height, int passes, float* image, int32_t* owner);
+/* BakeProbes / SampleProbes (irradiance probes, include/ptk.h ptk_bake_probes / ptk_probes_irradiance with the tracer's seed and
+ * trace depth): 1 on success */
+int  pth_bake_probes(pth_tracer* t, int num_probes, const float* positions, int num_dirs, const float* dirs, uint32_t first_sample,
+                     uint32_t spp, uint32_t key_base, uint32_t flags, float weight, float* radiance, float* coefs);
+int  pth_sample_probes(pth_tracer* t, const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs,
+                       int num_points, const float* points, const float* normals, float* out);
 void pth_get_camera(pth_tracer* t, float pos[3], float dir[3], float up[3]);   /* GetCamera (extension): what SetCamera last received */
 const char* pth_last_error(pth_tracer* t);
 ptk_ctx* pth_context(pth_tracer* t);

@@ -913,6 +913,29 @@ bool PathTracer::DilateLightmap(int width, int height, int passes, float* image,
     return rc == PTK_OK;
 }
 
+// Irradiance probes (ptk_bake_probes, ptk_probes_irradiance) of the scene as the next RenderFrame() would see it
+bool PathTracer::BakeProbes(int num_probes, const float* positions, int num_dirs, const float* dirs, uint32_t first_sample, uint32_t spp,
+                            uint32_t key_base, uint32_t flags, float weight, float* radiance, float* coefs)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_bake_probes(m->ctx, num_probes, positions, num_dirs, dirs, m->max_depth, first_sample, spp, m->seed, key_base, flags, weight,
+                                   radiance, coefs);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::SampleProbes(const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs, int num_points,
+                              const float* points, const float* normals, float* out)
+{
+    if (!m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const int rc = ptk_probes_irradiance(m->ctx, dims, origin, spacing, coefs, num_points, points, normals, out);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 void PathTracer::Exit() { if (m->ctx) ptk_request_exit(m->ctx); }      // :819-822
 
 // ---- extensions -----------------------------------------------------------------------------------------

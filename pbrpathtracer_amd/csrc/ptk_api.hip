@@ -27,6 +27,7 @@
 #include "ptk_features.h"
 #include "ptk_rays.h"
 #include "ptk_bake.h"
+#include "ptk_probes.h"
 #include "ptk_refit.h"
 
 using namespace ptk;
@@ -165,6 +166,18 @@ struct ptk_ctx {
     uint32_t* h_bake_total = nullptr;
     hipEvent_t ev_bake[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
     bool bake_timed = false, bake_traced = false;
+
+    // irradiance probe baking (ptk_bake_probes), each grown to the largest call so far: the basis table (36 B per direction), one
+    // block of rays (origins | dirs, 24 B each) and, while the caller passes no table, the radiance table (12 B per ray); four
+    // events of the last bake - around the basis table, around the projection - and three per block of probes (the first
+    // kMaxTimedPasses of them): before the ray generator, behind it, behind the trace
+    float* d_probe_basis = nullptr; size_t probe_basis_dirs = 0;
+    float* d_probe_rays = nullptr; size_t probe_rays_cap = 0;
+    float* d_probe_table = nullptr; size_t probe_table_rays = 0;
+    hipEvent_t ev_probes[4] = { nullptr, nullptr, nullptr, nullptr };
+    std::vector<hipEvent_t> ev_probe_blocks;
+    int probe_blocks_timed = 0;
+    bool probes_timed = false;
 
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
@@ -791,6 +804,9 @@ void ptk_destroy(ptk_ctx* c)
     dfree(c->d_bake_plane); dfree(c->d_bake_compact); dfree(c->d_bake_dilate);
     if (c->h_bake_total) (void)hipHostFree(c->h_bake_total);
     for (hipEvent_t e : c->ev_bake) if (e) (void)hipEventDestroy(e);
+    dfree(c->d_probe_basis); dfree(c->d_probe_rays); dfree(c->d_probe_table);
+    for (hipEvent_t e : c->ev_probes) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_probe_blocks) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_rays) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
@@ -2076,6 +2092,217 @@ int ptk_last_bake_ms(ptk_ctx* c, float* coverage_ms, float* raygen_ms, float* tr
     if (raygen_ms) *raygen_ms = t[1];
     if (trace_ms) *trace_ms = t[2];
     if (scatter_ms) *scatter_ms = t[3];
+    return PTK_OK;
+}
+
+// ---- irradiance probe baking (ptk.h) -----------------------------------------------------------------------------------------
+static int check_probes_args(ptk_ctx* c, int32_t num_probes, const float* positions, int32_t num_dirs, const float* dirs, uint32_t flags, float weight,
+                             const float* radiance, const float* coefs, bool* nothing)
+{
+    *nothing = false;
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (flags & ~PTK_PROBES_ACCUMULATE) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_probes: unknown flag bits");
+    if (num_probes < 0 || num_dirs < 0) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_probes: negative count");
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (!std::isfinite(weight)) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_probes: weight must be finite");
+    if ((flags & PTK_PROBES_ACCUMULATE) && !radiance) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_probes: PTK_PROBES_ACCUMULATE needs a radiance table");
+    if (num_probes > 0)
+    {
+        if (num_dirs < 1 || num_dirs > 65536) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_probes: num_dirs must be in 1..65536");
+        if ((uint64_t)num_probes * (uint64_t)num_dirs >= (1ull << 31)) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_probes: 2^31 rays or more");
+        if (!positions || !dirs || !coefs) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_probes: null array");
+    }
+    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
+    *nothing = num_probes == 0;
+    return PTK_OK;
+}
+
+// brings a context-owned buffer of `floats_per` floats per element to at least `want` elements
+static int grow_probe_buffer(ptk_ctx* c, float*& buf, size_t& have, size_t want, size_t floats_per)
+{
+    if (want <= have) return PTK_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    dfree(buf); have = 0;
+    HIPCHK(c, hipMalloc(&buf, want * floats_per * sizeof(float)));
+    have = want;
+    return PTK_OK;
+}
+
+// The bake proper, on the context's stream, every pointer into this GPU's memory: the basis table, then block by block of whole
+// probes the rays and their trace into the block's slice of the radiance table, then the projection of the whole table.
+static int probes_on_stream(ptk_ctx* c, int32_t num_probes, const float* d_positions, int32_t num_dirs, const float* d_dirs, int max_depth,
+                            uint32_t first_sample, uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float weight, float* d_radiance,
+                            float* d_coefs)
+{
+    c->probes_timed = false; c->probe_blocks_timed = 0;
+    for (hipEvent_t& e : c->ev_probes)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    const size_t D = (size_t)num_dirs, rays = (size_t)num_probes * D;
+    // a block holds at most max(D, pass_bytes / 256) rays, in whole probes: the rays are never all materialised
+    const size_t block_probes = std::min<size_t>((size_t)num_probes, std::max<size_t>(1, c->opt_pass_bytes / 256 / D));
+    int rc = grow_probe_buffer(c, c->d_probe_basis, c->probe_basis_dirs, D, PTK_PROBE_COEFS);
+    if (rc == PTK_OK) rc = grow_probe_buffer(c, c->d_probe_rays, c->probe_rays_cap, block_probes * D, 6);
+    if (rc == PTK_OK && !d_radiance) rc = grow_probe_buffer(c, c->d_probe_table, c->probe_table_rays, rays, 3);
+    if (rc != PTK_OK) return rc;
+    float* const table = d_radiance ? d_radiance : c->d_probe_table;
+    float* const origins = c->d_probe_rays, * const ray_dirs = origins + c->probe_rays_cap * 3;
+    HIPCHK(c, hipEventRecord(c->ev_probes[0], c->stream));
+    launch_probe_basis(d_dirs, num_dirs, c->d_probe_basis, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_probes[1], c->stream));
+    for (size_t p0 = 0; p0 < (size_t)num_probes; p0 += block_probes)
+    {
+        const size_t np = std::min(block_probes, (size_t)num_probes - p0), ray0 = p0 * D;
+        const int bi = c->probe_blocks_timed < ptk_ctx::kMaxTimedPasses ? c->probe_blocks_timed : -1;
+        if (bi >= 0)
+            while (c->ev_probe_blocks.size() < (size_t)(bi + 1) * 3)
+            {
+                hipEvent_t e = nullptr;
+                HIPCHK(c, hipEventCreate(&e));
+                c->ev_probe_blocks.push_back(e);
+            }
+        if (bi >= 0) HIPCHK(c, hipEventRecord(c->ev_probe_blocks[bi * 3], c->stream));
+        launch_probe_rays(d_positions + p0 * 3, d_dirs, (int)np, num_dirs, origins, ray_dirs, c->stream);
+        HIPCHK(c, hipGetLastError());
+        if (bi >= 0) HIPCHK(c, hipEventRecord(c->ev_probe_blocks[bi * 3 + 1], c->stream));
+        // (contiguous keys: plain rays_kernel)
+        rc = trace_rays_on_stream(c, (int32_t)(np * D), origins, ray_dirs, max_depth, first_sample, spp, seed, key_base + (uint32_t)ray0,
+                                  (flags & PTK_PROBES_ACCUMULATE) ? PTK_RAYS_ACCUMULATE : 0u, table + ray0 * 3);
+        if (rc != PTK_OK) return rc;
+        if (bi >= 0) { HIPCHK(c, hipEventRecord(c->ev_probe_blocks[bi * 3 + 2], c->stream)); c->probe_blocks_timed = bi + 1; }
+    }
+    HIPCHK(c, hipEventRecord(c->ev_probes[2], c->stream));
+    launch_probe_project(table, c->d_probe_basis, num_probes, num_dirs, weight, d_coefs, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_probes[3], c->stream));
+    c->probes_timed = true;
+    return PTK_OK;
+}
+
+int ptk_bake_probes_device(ptk_ctx* c, int32_t num_probes, const float* d_positions, int32_t num_dirs, const float* d_dirs, int max_depth,
+                           uint32_t first_sample, uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float weight, float* d_radiance,
+                           float* d_coefs)
+{
+    bool nothing;
+    const int rc = check_probes_args(c, num_probes, d_positions, num_dirs, d_dirs, flags, weight, d_radiance, d_coefs, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return probes_on_stream(c, num_probes, d_positions, num_dirs, d_dirs, max_depth, first_sample, spp, seed, key_base, flags, weight, d_radiance, d_coefs);
+}
+
+int ptk_bake_probes(ptk_ctx* c, int32_t num_probes, const float* positions, int32_t num_dirs, const float* dirs, int max_depth, uint32_t first_sample,
+                    uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float weight, float* radiance, float* coefs)
+{
+    bool nothing;
+    int rc = check_probes_args(c, num_probes, positions, num_dirs, dirs, flags, weight, radiance, coefs, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // positions | dirs | coefs | radiance (where the caller wants it), staged for the length of the call
+    const size_t n_pos = (size_t)num_probes * 3, n_dir = (size_t)num_dirs * 3, n_coef = (size_t)num_probes * PTK_PROBE_COEFS * 3;
+    const size_t n_rad = radiance ? (size_t)num_probes * (size_t)num_dirs * 3 : 0;
+    float* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, (n_pos + n_dir + n_coef + n_rad) * sizeof(float)));
+    float* d_dirs = d + n_pos, * d_coefs = d_dirs + n_dir, * d_rad = radiance ? d_coefs + n_coef : nullptr;
+    hipError_t e = hipMemcpyAsync(d, positions, n_pos * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_dirs, dirs, n_dir * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && (flags & PTK_PROBES_ACCUMULATE)) e = hipMemcpyAsync(d_rad, radiance, n_rad * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+    {
+        rc = probes_on_stream(c, num_probes, d, num_dirs, d_dirs, max_depth, first_sample, spp, seed, key_base, flags, weight, d_rad, d_coefs);
+        if (rc == PTK_OK) e = hipMemcpyAsync(coefs, d_coefs, n_coef * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess && radiance) e = hipMemcpyAsync(radiance, d_rad, n_rad * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also on the way out of a failure: the staging buffer may be in use)
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    if (rc != PTK_OK) return rc;
+    if (e != hipSuccess) return fail(c, PTK_ERR_HIP, hipGetErrorString(e));
+    return PTK_OK;
+}
+
+static int check_irradiance_args(ptk_ctx* c, const int32_t* dims, const float* origin, const float* spacing, const float* coefs, int32_t num_points,
+                                 const float* points, const float* normals, const float* out, ProbeGrid* grid, bool* nothing)
+{
+    *nothing = false;
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!dims || !origin || !spacing) return fail(c, PTK_ERR_BAD_ARG, "ptk_probes_irradiance: null dims, origin or spacing");
+    if (num_points < 0) return fail(c, PTK_ERR_BAD_ARG, "ptk_probes_irradiance: negative point count");
+    uint64_t probes = 1;
+    for (int a = 0; a < 3; a++)
+    {
+        if (dims[a] < 1) return fail(c, PTK_ERR_BAD_ARG, "ptk_probes_irradiance: dims must be at least 1");
+        if (!std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) return fail(c, PTK_ERR_BAD_ARG, "ptk_probes_irradiance: spacing must be finite and > 0");
+        if (!std::isfinite(origin[a])) return fail(c, PTK_ERR_BAD_ARG, "ptk_probes_irradiance: origin must be finite");
+        probes *= (uint64_t)dims[a];
+        if (probes >= (1ull << 31)) return fail(c, PTK_ERR_BAD_ARG, "ptk_probes_irradiance: 2^31 probes or more");
+        grid->dims[a] = dims[a]; grid->origin[a] = origin[a]; grid->spacing[a] = spacing[a];
+    }
+    if (num_points > 0 && (!coefs || !points || !normals || !out)) return fail(c, PTK_ERR_BAD_ARG, "ptk_probes_irradiance: null array");
+    *nothing = num_points == 0;
+    return PTK_OK;
+}
+
+int ptk_probes_irradiance_device(ptk_ctx* c, const int32_t dims[3], const float origin[3], const float spacing[3], const float* d_coefs,
+                                 int32_t num_points, const float* d_points, const float* d_normals, float* d_out)
+{
+    ProbeGrid g; bool nothing;
+    const int rc = check_irradiance_args(c, dims, origin, spacing, d_coefs, num_points, d_points, d_normals, d_out, &g, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_probe_irradiance(g, d_coefs, num_points, d_points, d_normals, d_out, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return PTK_OK;
+}
+
+int ptk_probes_irradiance(ptk_ctx* c, const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs, int32_t num_points,
+                          const float* points, const float* normals, float* out)
+{
+    ProbeGrid g; bool nothing;
+    int rc = check_irradiance_args(c, dims, origin, spacing, coefs, num_points, points, normals, out, &g, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // coefs | points | normals | out, staged for the length of the call
+    const size_t n_coef = (size_t)dims[0] * dims[1] * dims[2] * PTK_PROBE_COEFS * 3, n3 = (size_t)num_points * 3;
+    float* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, (n_coef + 3 * n3) * sizeof(float)));
+    float* d_points = d + n_coef, * d_normals = d_points + n3, * d_out = d_normals + n3;
+    hipError_t e = hipMemcpyAsync(d, coefs, n_coef * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_points, points, n3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_normals, normals, n3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+    {
+        launch_probe_irradiance(g, d, num_points, d_points, d_normals, d_out, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(c, PTK_ERR_HIP, hipGetErrorString(e));
+    return PTK_OK;
+}
+
+int ptk_last_probes_ms(ptk_ctx* c, float* raygen_ms, float* trace_ms, float* project_ms)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    float gen = 0.0f, trace = 0.0f, project = 0.0f;
+    if (c->probes_timed)
+    {
+        HIPCHK(c, hipEventSynchronize(c->ev_probes[3]));
+        HIPCHK(c, hipEventElapsedTime(&gen, c->ev_probes[0], c->ev_probes[1]));         // (the basis table counts as ray generation)
+        HIPCHK(c, hipEventElapsedTime(&project, c->ev_probes[2], c->ev_probes[3]));
+        for (int i = 0; i < c->probe_blocks_timed; i++)
+        {
+            float a = 0.0f, b = 0.0f;
+            HIPCHK(c, hipEventElapsedTime(&a, c->ev_probe_blocks[i * 3], c->ev_probe_blocks[i * 3 + 1]));
+            HIPCHK(c, hipEventElapsedTime(&b, c->ev_probe_blocks[i * 3 + 1], c->ev_probe_blocks[i * 3 + 2]));
+            gen += a; trace += b;
+        }
+    }
+    if (raygen_ms) *raygen_ms = gen;
+    if (trace_ms) *trace_ms = trace;
+    if (project_ms) *project_ms = project;
     return PTK_OK;
 }
 

@@ -131,6 +131,16 @@ int pth_lightmap_dilate(pth_tracer* t, int width, int height, int passes, float*
 {
     return t->pt.DilateLightmap(width, height, passes, image, owner) ? 1 : 0;
 }
+int pth_bake_probes(pth_tracer* t, int num_probes, const float* positions, int num_dirs, const float* dirs, uint32_t first_sample, uint32_t spp,
+                    uint32_t key_base, uint32_t flags, float weight, float* radiance, float* coefs)
+{
+    return t->pt.BakeProbes(num_probes, positions, num_dirs, dirs, first_sample, spp, key_base, flags, weight, radiance, coefs) ? 1 : 0;
+}
+int pth_sample_probes(pth_tracer* t, const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs, int num_points,
+                      const float* points, const float* normals, float* out)
+{
+    return t->pt.SampleProbes(dims, origin, spacing, coefs, num_points, points, normals, out) ? 1 : 0;
+}
 void pth_get_camera(pth_tracer* t, float* pos, float* dir, float* up) { t->pt.GetCamera(pos, dir, up); }
 const char* pth_last_error(pth_tracer* t)
 {

@@ -36,7 +36,7 @@ HOST_SYMBOLS = [
     "pth_trs_matrix", "pth_euler_camera", "pth_triangle_init", "pth_image_load", "pth_image_data", "pth_image_tex2d",
     "pth_export_png", "pth_render_adaptive", "pth_read_sample_counts",
     "pth_render_features", "pth_read_feature", "pth_pick", "pth_set_object_transform", "pth_trace_rays", "pth_get_camera",
-    "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate",
+    "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
 ]
 
 _bound = False
@@ -96,6 +96,9 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_bake_lightmap.argtypes = [vp, i32, i32, vp, f32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
         L.pth_bake_coverage.restype = i32; L.pth_bake_coverage.argtypes = [vp, i32, i32, vp, vp, vp, vp]
         L.pth_lightmap_dilate.restype = i32; L.pth_lightmap_dilate.argtypes = [vp, i32, i32, i32, vp, vp]
+        L.pth_bake_probes.restype = i32
+        L.pth_bake_probes.argtypes = [vp, i32, vp, i32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32, vp, vp]
+        L.pth_sample_probes.restype = i32; L.pth_sample_probes.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -352,6 +355,39 @@ class PathTracer:
         if not self.L.pth_lightmap_dilate(self.h, w, h, int(passes), image.ctypes.data, owner.ctypes.data):
             raise _ptk.PtkError("DilateLightmap failed: " + self.LastError())
         return image, owner
+
+    def BakeProbes(self, positions, dirs, first_sample: int, spp: int, weight: float, key_base: int = 0, radiance=None):
+        """Extension: bake irradiance probes (include/ptk.h ptk_bake_probes) at this tracer's seed and trace depth.  positions
+        [P, 3], dirs [D, 3] (probes.grid_positions, probes.fibonacci_dirs); returns (radiance [P, D, 3], coefs [P, 9, 3]) float32.
+        radiance: the table of earlier samples' sums, added to in place (PTK_PROBES_ACCUMULATE)."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        flags = _ptk.PROBES_ACCUMULATE if radiance is not None else 0
+        if radiance is None:
+            radiance = np.empty((len(pos), len(d), 3), np.float32)
+        assert radiance.dtype == np.float32 and radiance.flags.c_contiguous and radiance.size == len(pos) * len(d) * 3
+        coefs = np.empty((len(pos), 9, 3), np.float32)
+        ptr = (lambda a: a.ctypes.data if a.size else None)
+        if not self.L.pth_bake_probes(self.h, len(pos), ptr(pos), len(d), ptr(d), int(first_sample), int(spp), int(key_base) & 0xffffffff,
+                                      flags, float(weight), ptr(radiance), ptr(coefs)):
+            raise _ptk.PtkError("BakeProbes failed: " + self.LastError())
+        return radiance, coefs
+
+    def SampleProbes(self, dims, origin, spacing, coefs, points, normals) -> np.ndarray:
+        """Extension: [n, 3] float32 irradiance at (points, normals) from a probe grid (ptk_probes_irradiance); coefs
+        [nz, ny, nx, 9, 3] as BakeProbes gave them for probes.grid_positions(dims, origin, spacing)."""
+        g_dims = (C.c_int32 * 3)(*(int(n) for n in dims))
+        g_origin = (C.c_float * 3)(*(float(x) for x in origin))
+        g_spacing = (C.c_float * 3)(*(float(x) for x in spacing))
+        c = np.ascontiguousarray(coefs, dtype=np.float32)
+        q = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        assert c.size == int(g_dims[0]) * int(g_dims[1]) * int(g_dims[2]) * 27 and len(nrm) == len(q)
+        out = np.empty((len(q), 3), np.float32)
+        ptr = (lambda a: a.ctypes.data if a.size else None)
+        if not self.L.pth_sample_probes(self.h, g_dims, g_origin, g_spacing, ptr(c), len(q), ptr(q), ptr(nrm), ptr(out)):
+            raise _ptk.PtkError("SampleProbes failed: " + self.LastError())
+        return out
 
     def ReadAccumulation(self) -> np.ndarray:
         w, h = self.GetResolution()

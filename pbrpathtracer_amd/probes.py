@@ -1,0 +1,58 @@
+"""Irradiance probe helpers for Context.bake_probes / PathTracer.BakeProbes (include/ptk.h ptk_bake_probes): a direction set, the
+positions of a regular grid and the projection weight that goes with a uniform direction set - the worked use that keeps the Python
+path honest, as rays.equirect_rays and lightmap.grid_atlas are for theirs."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+
+def fibonacci_dirs(num_dirs: int) -> np.ndarray:
+    """[num_dirs, 3] float32 unit directions of the spherical Fibonacci lattice: z_i = 1 - (2 i + 1) / D, azimuth i times the
+    golden angle; computed and normalised in float64, then cast.  The lattice is a near-uniform quadrature rule of weight
+    4 pi / D per direction (sh_weight)."""
+    if num_dirs < 1:
+        raise ValueError("fibonacci_dirs: at least one direction")
+    i = np.arange(num_dirs, dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / num_dirs
+    r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    phi = i * (math.pi * (3.0 - math.sqrt(5.0)))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return np.ascontiguousarray(d, np.float32)
+
+
+def grid_positions(dims, origin, spacing) -> np.ndarray:
+    """[nz * ny * nx, 3] float32 positions of a probe grid in the order ptk_probes_irradiance indexes it ((iz * ny + iy) * nx + ix):
+    origin + (float)i * spacing per axis, in float32"""
+    nx, ny, nz = (int(n) for n in dims)
+    if min(nx, ny, nz) < 1:
+        raise ValueError("grid_positions: dims must be at least 1")
+    o = np.asarray(origin, np.float32).reshape(3)
+    s = np.asarray(spacing, np.float32).reshape(3)
+    ax = [o[a] + np.arange(n, dtype=np.float32) * s[a] for a, n in enumerate((nx, ny, nz))]
+    pos = np.empty((nz, ny, nx, 3), np.float32)
+    pos[..., 0] = ax[0][None, None, :]
+    pos[..., 1] = ax[1][None, :, None]
+    pos[..., 2] = ax[2][:, None, None]
+    return pos.reshape(-1, 3)
+
+
+def sh_weight(num_dirs: int, samples: int) -> float:
+    """the projection weight of a uniform direction set: 4 pi / (num_dirs * samples), rounded to float32"""
+    return float(np.float32(4.0 * math.pi / (float(num_dirs) * float(samples))))
+
+
+def grid_over_bounds(lo, hi, dims):
+    """(origin, spacing) float32 [3] each of a grid of dims probes that spans the box lo..hi: the outermost probes lie on the box;
+    an axis of one probe puts it in the middle (spacing 1 there, as for an axis without extent)"""
+    lo = np.asarray(lo, np.float64).reshape(3)
+    hi = np.asarray(hi, np.float64).reshape(3)
+    origin, spacing = np.empty(3, np.float32), np.empty(3, np.float32)
+    for a, n in enumerate(dims):
+        if n > 1 and hi[a] > lo[a]:
+            origin[a], spacing[a] = lo[a], (hi[a] - lo[a]) / (n - 1)
+        else:
+            origin[a], spacing[a] = (0.5 * (lo[a] + hi[a]) if n == 1 else lo[a]), 1.0
+    return origin, spacing

@@ -85,6 +85,7 @@ SYMBOLS = [
     "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
     "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
     "ptk_last_bake_ms",
+    "ptk_bake_probes", "ptk_bake_probes_device", "ptk_probes_irradiance", "ptk_probes_irradiance_device", "ptk_last_probes_ms",
 ]
 
 
@@ -169,6 +170,11 @@ def _load_locked() -> C.CDLL:
         for fn in (L.ptk_lightmap_dilate, L.ptk_lightmap_dilate_device):
             fn.argtypes = [vp, i32, i32, i32, vp, vp]
         L.ptk_last_bake_ms.argtypes = [vp, fp, fp, fp, fp]
+        for fn in (L.ptk_bake_probes, L.ptk_bake_probes_device):
+            fn.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, i32, u32, u32, u64, u32, u32, f32, vp, vp]
+        for fn in (L.ptk_probes_irradiance, L.ptk_probes_irradiance_device):
+            fn.argtypes = [vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp]
+        L.ptk_last_probes_ms.argtypes = [vp, fp, fp, fp]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -196,6 +202,7 @@ def _load_locked() -> C.CDLL:
 TRACE_NONE, TRACE_BVH, TRACE_FLAT, TRACE_FLAT_PLAIN = 0, 1, 2, 3      # ptk_trace_variant
 RAYS_ACCUMULATE, RAYS_LENS_DRAWS = 1, 2                               # ptk_trace_rays flags
 BAKE_ACCUMULATE, BAKE_BACK = 1, 2                                     # ptk_bake_lightmap flags
+PROBES_ACCUMULATE = 1                                                 # ptk_bake_probes flags
 
 
 # first-hit feature planes (ptk_render_features): ids, and their names in id order
@@ -500,6 +507,85 @@ class Context:
         t = [C.c_float(0) for _ in range(4)]
         self._chk(self.L.ptk_last_bake_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_bake_ms")
         return dict(zip(("coverage_ms", "raygen_ms", "trace_ms", "scatter_ms"), (x.value for x in t)))
+
+    # ---- irradiance probes -----------------------------------------------------------------
+    def bake_probes(self, positions, dirs, max_depth: int, first_sample: int, spp: int, seed: int, weight: float, key_base: int = 0,
+                    radiance=None, want_radiance: bool = True):
+        """ptk_bake_probes: (radiance [P, D, 3], coefs [P, 9, 3]) float32 of the probes at positions [P, 3] over the directions
+        dirs [D, 3] (used as given): radiance[p, j] = the float32 in-order sum over samples [first_sample, first_sample + spp) of
+        the radiance along (positions[p], dirs[j]) on the streams of (seed, RNG pixel key_base + p * D + j, sample); coefs = its
+        projection onto 9 real spherical harmonics times weight (probes.sh_weight for a uniform direction set).
+        numpy arrays go through the host entry (synchronous); torch tensors on the context's GPU through ptk_bake_probes_device with
+        no host copy, written on the context's stream.  radiance: the table of earlier samples' sums, added to in place
+        (PTK_PROBES_ACCUMULATE); coefs always comes from the whole table.  want_radiance=False (without a table): the table stays in
+        the context's own buffer and None is returned for it."""
+        flags = PROBES_ACCUMULATE if radiance is not None else 0
+        args = (int(max_depth), int(first_sample), int(spp), int(seed), int(key_base) & 0xffffffff, flags, float(weight))
+        if hasattr(positions, "data_ptr"):
+            import torch
+            dev = self.device_ordinal()
+            P, D = positions.numel() // 3, dirs.numel() // 3
+            if radiance is None and want_radiance:
+                radiance = torch.empty((P, D, 3), dtype=torch.float32, device=positions.device)
+            coefs = torch.empty((P, 9, 3), dtype=torch.float32, device=positions.device)
+            for t, n in ((positions, P * 3), (dirs, D * 3), (radiance, P * D * 3), (coefs, P * 27)):
+                if t is None:
+                    continue
+                assert t.is_cuda and t.device.index == dev, f"tensor on {t.device}, context on device {dev}"
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, "float32 contiguous tensors of [P, 3], [D, 3], [P, D, 3]"
+            ptr = (lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None)
+            self._chk(self.L.ptk_bake_probes_device(self.h, P, ptr(positions), D, ptr(dirs), *args, ptr(radiance), ptr(coefs)),
+                      "ptk_bake_probes_device")
+            return radiance, coefs
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        P, D = len(pos), len(d)
+        if radiance is None and want_radiance:
+            radiance = np.empty((P, D, 3), np.float32)
+        assert radiance is None or (isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.flags["C_CONTIGUOUS"]
+                                    and radiance.size == P * D * 3), "radiance: a C-contiguous float32 array of P x D x 3"
+        coefs = np.empty((P, 9, 3), np.float32)
+        ptr = (lambda a: a.ctypes.data if a is not None and a.size else None)
+        self._chk(self.L.ptk_bake_probes(self.h, P, ptr(pos), D, ptr(d), *args, ptr(radiance), ptr(coefs)), "ptk_bake_probes")
+        return radiance, coefs
+
+    def probes_irradiance(self, dims, origin, spacing, coefs, points, normals):
+        """ptk_probes_irradiance: [n, 3] float32 Lambertian irradiance at (points[i], normals[i]) from the probe grid of dims =
+        (nx, ny, nz) probes at origin + i * spacing whose coefficients coefs [nz, ny, nx, 9, 3] (bake_probes over
+        probes.grid_positions) are interpolated trilinearly; no visibility weighting.  numpy arrays: the host entry; torch tensors
+        (coefs, points, normals) on the context's GPU: the device entry, on the context's stream."""
+        g_dims = (C.c_int32 * 3)(*(int(n) for n in dims))
+        g_origin = (C.c_float * 3)(*(float(x) for x in origin))
+        g_spacing = (C.c_float * 3)(*(float(x) for x in spacing))
+        count = int(g_dims[0]) * int(g_dims[1]) * int(g_dims[2]) * 27
+        if hasattr(points, "data_ptr"):
+            import torch
+            dev = self.device_ordinal()
+            n = points.numel() // 3
+            out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+            for t, m in ((coefs, count), (points, n * 3), (normals, n * 3)):
+                assert t.is_cuda and t.device.index == dev, f"tensor on {t.device}, context on device {dev}"
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == m, "float32 contiguous tensors of [nz, ny, nx, 9, 3], [n, 3]"
+            ptr = (lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None)
+            self._chk(self.L.ptk_probes_irradiance_device(self.h, g_dims, g_origin, g_spacing, ptr(coefs), n, ptr(points), ptr(normals), ptr(out)),
+                      "ptk_probes_irradiance_device")
+            return out
+        c = np.ascontiguousarray(coefs, dtype=np.float32)
+        q = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        assert c.size == count, "coefs: dims[0] * dims[1] * dims[2] probes of 9 x 3 floats"
+        assert len(nrm) == len(q), "as many normals as points"
+        out = np.empty((len(q), 3), np.float32)
+        ptr = (lambda a: a.ctypes.data if a.size else None)
+        self._chk(self.L.ptk_probes_irradiance(self.h, g_dims, g_origin, g_spacing, ptr(c), len(q), ptr(q), ptr(nrm), ptr(out)),
+                  "ptk_probes_irradiance")
+        return out
+
+    def last_probes_ms(self) -> dict:
+        """HIP-event times (ms) of the last probe bake's kernels: ray generation, trace, projection; waits for it."""
+        t = [C.c_float(0) for _ in range(3)]
+        self._chk(self.L.ptk_last_probes_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_probes_ms")
+        return dict(zip(("raygen_ms", "trace_ms", "project_ms"), (x.value for x in t)))
 
     def read_sample_counts(self) -> np.ndarray:
         """[H][W] uint32 samples per pixel, rows bottom-up like read_accum; 0 = not owned."""

@@ -6,6 +6,7 @@
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
     python -m pbrpathtracer_amd.render scene.pts --bake-lightmap 1024 --spp 64 [--bake-atlas] [--bake-offset F] [--bake-back]
                                                  [--dilate K] -o map.png [--npy map.npy]
+    python -m pbrpathtracer_amd.render scene.pts --bake-probes NX NY NZ [--probe-dirs D] --spp N -o probes.npz
 
 With --noise-threshold the render is adaptive (include/ptk.h ptk_render_adaptive): --spp becomes the most samples a pixel
 gets, and pixels stop once their noise meets the threshold.
@@ -16,6 +17,10 @@ PathTracer.TraceRays (include/ptk.h ptk_trace_rays; rays.equirect_rays) instead 
 With --bake-lightmap SIZE the image is a SIZE x SIZE lightmap (include/ptk.h ptk_bake_lightmap): per texel of the scene's own uv
 layout - or, with --bake-atlas, of lightmap.grid_atlas, one chart per triangle - the radiance leaving the surface along its normal,
 baked by PathTracer.BakeLightmap and padded by --dilate K passes of ptk_lightmap_dilate.
+
+With --bake-probes NX NY NZ the output is an .npz of irradiance probes (include/ptk.h ptk_bake_probes): a grid of NX x NY x NZ probes
+that spans the scene's vertex bounds, --probe-dirs directions of probes.fibonacci_dirs each, baked by PathTracer.BakeProbes; it holds
+coefs [NZ, NY, NX, 9, 3], dims, origin and spacing - the arguments of ptk_probes_irradiance / PathTracer.SampleProbes.
 
 The headless equivalent of the reference's Start button + Export (main.cpp:3563-3618, :760-771):
 LoadScene -> SendObjectsToPathTracer -> RenderFrame() x spp -> PNG (flipped to top-down)."""
@@ -55,6 +60,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--bake-lightmap: distance of the ray origins from the surface (default: 1e-3 of the scene extent)")
     ap.add_argument("--bake-back", action="store_true", help="--bake-lightmap: bake the back side (PTK_BAKE_BACK)")
     ap.add_argument("--dilate", type=int, default=0, metavar="K", help="--bake-lightmap: chart padding passes")
+    ap.add_argument("--bake-probes", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
+                    help="bake a grid of NX x NY x NZ irradiance probes over the scene's vertex bounds instead of rendering a view; "
+                         "-o names an .npz with coefs [NZ, NY, NX, 9, 3], dims, origin, spacing")
+    ap.add_argument("--probe-dirs", type=int, default=256, metavar="D", help="--bake-probes: directions per probe (default 256)")
     return ap
 
 
@@ -97,6 +106,29 @@ def render_lightmap(pt, a) -> int:
     return 0
 
 
+def render_probes(pt, a) -> int:
+    from .probes import fibonacci_dirs, grid_over_bounds, grid_positions, sh_weight
+    dims = tuple(a.bake_probes)
+    if min(dims) < 1 or not 1 <= a.probe_dirs <= 65536 or a.spp < 1:
+        print("error: --bake-probes needs dims of at least 1, --probe-dirs in 1..65536 and --spp of at least 1", file=sys.stderr)
+        return 1
+    v = np.asarray(pt.StagedScene()["verts"], np.float64).reshape(-1, 3)
+    if not len(v):
+        print("error: --bake-probes: the scene has no triangles", file=sys.stderr)
+        return 1
+    origin, spacing = grid_over_bounds(v.min(axis=0), v.max(axis=0), dims)
+    pos = grid_positions(dims, origin, spacing)
+    t1 = time.time()
+    _, coefs = pt.BakeProbes(pos, fibonacci_dirs(a.probe_dirs), 0, a.spp, sh_weight(a.probe_dirs, a.spp))
+    t2 = time.time()
+    with open(a.out, "wb") as f:                # (np.savez would append .npz to another suffix)
+        np.savez(f, coefs=coefs.reshape(dims[2], dims[1], dims[0], 9, 3), dims=np.array(dims, np.int32), origin=origin, spacing=spacing)
+    rays = len(pos) * a.probe_dirs
+    print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {dims[0]}x{dims[1]}x{dims[2]} probes x {a.probe_dirs} directions, {a.spp} spp, "
+          f"depth {pt.GetTraceDepth()}: {t2 - t1:.3f} s ({rays * a.spp / (t2 - t1) / 1e6:.0f} Msamples/s) -> {a.out}")
+    return 0
+
+
 def render_equirect(pt, a) -> int:
     """The panorama: one TraceRays call over the pixel centres' rays, mean = sum / spp resolved to 8 bits by the frame's own rule
     (pathtracer.cpp:802-812: clamped to [0, 1], NaN to 0, x * 255 truncated)."""
@@ -134,6 +166,12 @@ def main(argv=None):
     if a.bake_lightmap is not None:
         try:
             return render_lightmap(pt, a)
+        except (RuntimeError, ValueError) as e:
+            print("error:", e, file=sys.stderr)
+            return 1
+    if a.bake_probes is not None:
+        try:
+            return render_probes(pt, a)
         except (RuntimeError, ValueError) as e:
             print("error:", e, file=sys.stderr)
             return 1
