@@ -24,6 +24,7 @@ typedef unsigned char GLubyte;   // the only thing the reference takes from <GL/
 struct ptk_ctx;
 struct ptk_scene_desc;
 struct ptk_adaptive_result;
+struct ptk_rays_adaptive_result;
 
 const float EPS = 0.00001f;      // mesh.h:12
 const float INF = (float)0xFFFF; // mesh.h:13
@@ -211,6 +212,15 @@ public:
     // edits apply as for TraceRays; the image and the sample count are not touched.
     bool BakeLightmap(int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp, uint32_t key_base,
                       uint32_t flags, float* out, int32_t* owner = nullptr);
+    // Extensions: the adaptive forms (include/ptk.h ptk_trace_rays_adaptive / ptk_bake_lightmap_adaptive, host arrays, synchronous)
+    // at the class's seed and trace depth: rounds of `step` samples until a ray's / texel's noise meets `threshold`, or max_spp.
+    // sum / out: the float32 sums, counts: the samples each ray / texel received (mean = sum / count); sumsq, owner, res may be
+    // null.  flags = PTK_RAYS_LENS_DRAWS / PTK_BAKE_BACK.  Pending edits apply as for TraceRays; the image is not touched.
+    bool TraceRaysAdaptive(int num_rays, const float* origins, const float* dirs, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp,
+                           uint32_t key_base, uint32_t flags, float* sum, float* sumsq, uint32_t* counts, ptk_rays_adaptive_result* res = nullptr);
+    bool BakeLightmapAdaptive(int width, int height, const float* uvs, float offset, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp,
+                              uint32_t key_base, uint32_t flags, float* out, uint32_t* counts, int32_t* owner = nullptr,
+                              ptk_rays_adaptive_result* res = nullptr);
     bool BakeCoverage(int width, int height, const float* uvs, int32_t* owner, float* bary = nullptr, float* pos = nullptr);
     bool DilateLightmap(int width, int height, int passes, float* image, int32_t* owner);
     // Extensions: irradiance probe baking (include/ptk.h ptk_bake_probes / ptk_probes_irradiance, host arrays, synchronous) at the

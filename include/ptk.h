@@ -415,6 +415,71 @@ int ptk_lightmap_dilate_device(ptk_ctx* ctx, int width, int height, int passes, 
  * fill, bake_cover_kernel, the count and its scan), ray generation, the trace (ptk_last_rays_ms splits it), zero fill + scatter */
 int ptk_last_bake_ms(ptk_ctx* ctx, float* coverage_ms, float* raygen_ms, float* trace_ms, float* scatter_ms);
 
+/* ---- adaptive ray queries and lightmap bakes: stop a ray once its noise meets a target (no counterpart in the reference) -------
+ * What ptk_render_adaptive is to ptk_render, for caller-supplied rays and for lightmap texels: most rays of a bake need few samples
+ * (an evenly lit texel, a ray that leaves the scene), a few carry nearly all the noise (a penumbra, glass).
+ * Ray query.  Work proceeds in rounds of `step` samples.  Every ray i starts active with n_i = 0, S1_i = S2_i = 0.  A round adds the
+ * samples [n, n + step) to every active ray, per channel and strictly in sample order in float32:
+ *   S1 = S1 + L;  S2 = S2 + L*L (the product rounded first);  then n += step.
+ * L(i, s) is exactly ptk_trace_rays' L: the stream of (seed, RNG pixel (key_base + i) mod 2^32, sample s), PTK_RAYS_LENS_DRAWS with
+ * the meaning it has there.  After every round with n >= min_spp the rule of ptk_render_adaptive is applied per active ray,
+ * operation for operation in float32 (c over R, G, B):
+ *   nf = (float)n;  m_c = S1_c / nf;  v_c = S2_c / nf - m_c * m_c, 0 if negative (NaN stays NaN);
+ *   err2 = ((v_r + v_g) + v_b) / (3 * (nf - 1));  lum = ((m_r + m_g) + m_b) / 3;  tol = threshold * (lum + 1/256);
+ *   done(i) = err2 < tol * tol          (strict: threshold 0 never converges, NaN never converges)
+ * An active ray with done(i) leaves the active set - rays have no neighbours, there is no neighbourhood term.  The call ends after
+ * the round that leaves no ray active, or at max_spp.  (The rounds before min_spp, which test nothing, are traced as one launch;
+ * they count as min_spp / step rounds.)
+ * Invariant: for every ray, sum[i] is bit for bit what ptk_trace_rays(first_sample 0, spp counts[i]) gives for that ray alone at its
+ * RNG pixel, and sumsq[i] (may be NULL: not wanted) is the in-order sum of the squares of the same samples.  Hence the result does
+ * not depend on how a round is cut into passes ("pass_bytes"), on the order in which the active list is compacted, on the builder, on
+ * "flat" or on ptk_set_tile (tests/test_gpu_rays_adaptive.py: array_equal against tests/rays_adaptive_rule.py).
+ * Result (may be NULL): rounds run, the largest count, the sum of the counts, and the rays still active when the call stopped (0:
+ * every ray converged).
+ * Lightmap.  Coverage, surface point, ray and RNG pixel (the texel index) are exactly those of ptk_bake_lightmap; the adaptive state
+ * lives per COVERED texel.  A covered texel stays active for the next round if it is active now and some active, not-done, covered
+ * texel lies in its 3x3 neighbourhood clipped to the map (no tiles here; uncovered texels take no part).  out receives S1 per
+ * texel, counts n per texel; uncovered texels get out = 0 and count = 0; owner (may be NULL) as ptk_bake_lightmap writes it.  The
+ * invariant holds per texel against ptk_bake_lightmap(first_sample 0, spp counts[t]).  Flags: PTK_BAKE_BACK only.
+ * Both the host entries (host arrays, staged for the length of the call) and the _device entries (every array in this GPU's memory,
+ * work queued on the context's stream, the caller's after ptk_set_stream) are SYNCHRONOUS: one 4-byte active count comes back to
+ * the host per round, as in ptk_render_adaptive - it sizes the next round's launch -, and the call returns with the stream drained.
+ * Like ptk_trace_rays the calls need a scene only, read it as ptk_update_materials / ptk_update_geometry left it, touch no frame,
+ * adaptive-render or feature state, are not cut by ptk_request_exit, and "contract" does not reach them.
+ * PTK_ERR_BAD_ARG: whatever the plain calls refuse; step < 2; step not dividing min_spp or max_spp; min_spp == 0; min_spp > max_spp;
+ * a threshold that is not finite or < 0; PTK_RAYS_ACCUMULATE / PTK_BAKE_ACCUMULATE (an adaptive call always starts at sample 0); null
+ * sum / out or null counts with a non-zero size.  A refused call leaves its outputs alone.  num_rays == 0 is PTK_OK.  A scene
+ * without triangles gives zeros and counts = min_spp: black converges at the first test (unless threshold is so small that
+ * tol * tol is not above 0 - threshold 0 for one -, when every count is max_spp as the rule says).
+ * Memory, owned by the context, grown to the largest call so far and freed by ptk_destroy: 56 B per ray (per covered texel) - the
+ * round's compacted origin, direction, key and source index (32 B), the next active list and the keep flags (4 B each), S2 and the
+ * count (16 B) - with 4 B per 256 rays, 1 B per texel of a lightmap (the need plane), ptk_bake_lightmap's buffers and
+ * ptk_trace_rays' sample buffer, which holds one ROUND of the active rays at most.  The host ray entry also stages 52 B per ray,
+ * the host lightmap entry the uvs and 20 B per texel. */
+typedef struct ptk_rays_adaptive_result {
+    uint32_t rounds, max_count;          /* rounds run; largest per-ray count */
+    uint64_t ray_samples;                /* sum of counts */
+    uint64_t active_rays;                /* still active when it stopped: 0 = every ray converged */
+} ptk_rays_adaptive_result;
+int ptk_trace_rays_adaptive(ptk_ctx* ctx, int32_t num_rays, const float* origins /*[n][3]*/, const float* dirs /*[n][3]*/, int max_depth,
+                            float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t key_base, uint32_t flags,
+                            float* sum /*[n][3]*/, float* sumsq /*[n][3], may be NULL*/, uint32_t* counts /*[n]*/,
+                            ptk_rays_adaptive_result* res /*may be NULL*/);
+int ptk_trace_rays_adaptive_device(ptk_ctx* ctx, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth,
+                                   float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t key_base,
+                                   uint32_t flags, float* d_sum, float* d_sumsq, uint32_t* d_counts, ptk_rays_adaptive_result* res);
+int ptk_bake_lightmap_adaptive(ptk_ctx* ctx, int width, int height, const float* uvs, float offset, int max_depth, float threshold,
+                               uint32_t min_spp, uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t key_base, uint32_t flags,
+                               float* out /*[H][W][3] sums*/, uint32_t* counts /*[H][W]*/, int32_t* owner /*[H][W], may be NULL*/,
+                               ptk_rays_adaptive_result* res /*may be NULL*/);
+int ptk_bake_lightmap_adaptive_device(ptk_ctx* ctx, int width, int height, const float* d_uvs, float offset, int max_depth, float threshold,
+                                      uint32_t min_spp, uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t key_base, uint32_t flags,
+                                      float* d_out, uint32_t* d_counts, int32_t* d_owner, ptk_rays_adaptive_result* res);
+/* measurement hook (tools/rays_adaptive_timing.py), not part of the feature: of the last adaptive ray query or bake, the host's
+ * wall time for the round loop, the HIP-event time of its rays_keyed_kernel launches, and that of the other kernels of its rounds
+ * (gather, fold, converge, compaction, the count's copy); total - trace - other is what the host spent between rounds */
+int ptk_last_rays_adaptive_ms(ptk_ctx* ctx, float* total_ms, float* trace_ms, float* other_ms);
+
 /* ---- irradiance probe baking: radiance gathered at points in space, stored as 9 spherical-harmonic coefficients per probe and
  * channel, looked up by position and normal (no counterpart in the reference) --
  * The volume half of light baking - what lights anything that moves -, in front of and behind ptk_trace_rays' kernel: a ray

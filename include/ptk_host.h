@@ -68,6 +68,14 @@ int  pth_trace_rays(pth_tracer* t, int num_rays, const float* origins, const flo
  * depth): 1 on success */
 int  pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,
                        uint32_t key_base, uint32_t flags, float* out, int32_t* owner);
+/* TraceRaysAdaptive / BakeLightmapAdaptive (include/ptk.h ptk_trace_rays_adaptive / ptk_bake_lightmap_adaptive with the tracer's seed
+ * and trace depth): 1 on success; sumsq, owner and res may be NULL */
+int  pth_trace_rays_adaptive(pth_tracer* t, int num_rays, const float* origins, const float* dirs, float threshold, uint32_t min_spp,
+                             uint32_t step, uint32_t max_spp, uint32_t key_base, uint32_t flags, float* sum, float* sumsq, uint32_t* counts,
+                             ptk_rays_adaptive_result* res);
+int  pth_bake_lightmap_adaptive(pth_tracer* t, int width, int height, const float* uvs, float offset, float threshold, uint32_t min_spp,
+                                uint32_t step, uint32_t max_spp, uint32_t key_base, uint32_t flags, float* out, uint32_t* counts,
+                                int32_t* owner, ptk_rays_adaptive_result* res);
 int  pth_bake_coverage(pth_tracer* t, int width, int height, const float* uvs, int32_t* owner, float* bary, float* pos);
 int  pth_lightmap_dilate(pth_tracer* t, int width, int height, int passes, float* image, int32_t* owner);
 /* BakeProbes / SampleProbes (irradiance probes, include/ptk.h ptk_bake_probes / ptk_probes_irradiance with the tracer's seed and

@@ -894,6 +894,32 @@ bool PathTracer::BakeLightmap(int width, int height, const float* uvs, float off
     return rc == PTK_OK;
 }
 
+bool PathTracer::TraceRaysAdaptive(int num_rays, const float* origins, const float* dirs, float threshold, uint32_t min_spp, uint32_t step,
+                                   uint32_t max_spp, uint32_t key_base, uint32_t flags, float* sum, float* sumsq, uint32_t* counts,
+                                   ptk_rays_adaptive_result* res)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_trace_rays_adaptive(m->ctx, num_rays, origins, dirs, m->max_depth, threshold, min_spp, step, max_spp, m->seed, key_base, flags,
+                                           sum, sumsq, counts, res);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::BakeLightmapAdaptive(int width, int height, const float* uvs, float offset, float threshold, uint32_t min_spp, uint32_t step,
+                                      uint32_t max_spp, uint32_t key_base, uint32_t flags, float* out, uint32_t* counts, int32_t* owner,
+                                      ptk_rays_adaptive_result* res)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_bake_lightmap_adaptive(m->ctx, width, height, uvs, offset, m->max_depth, threshold, min_spp, step, max_spp, m->seed, key_base,
+                                              flags, out, counts, owner, res);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 bool PathTracer::BakeCoverage(int width, int height, const float* uvs, int32_t* owner, float* bary, float* pos)
 {
     if (!m->scene_uploaded || !m->ensure_ctx()) return false;

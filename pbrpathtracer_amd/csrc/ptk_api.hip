@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <memory>
 #include <string>
@@ -28,6 +29,7 @@
 #include "ptk_rays.h"
 #include "ptk_bake.h"
 #include "ptk_probes.h"
+#include "ptk_rays_adaptive.h"
 #include "ptk_refit.h"
 
 using namespace ptk;
@@ -166,6 +168,17 @@ struct ptk_ctx {
     uint32_t* h_bake_total = nullptr;
     hipEvent_t ev_bake[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
     bool bake_timed = false, bake_traced = false;
+
+    // adaptive ray queries and lightmap bakes (ptk_trace_rays_adaptive, ptk_bake_lightmap_adaptive), each grown to the largest call
+    // so far: per ray 56 B - the round's compacted origins | dirs (24 B), keys, source indices, the next active list and the keep
+    // flags (4 B each), S2 and the counts where the caller's arrays do not hold them (12 + 4 B) - with a count per 256 rays and the
+    // total behind them; a lightmap's need plane (1 B per texel); the total's page-locked read-back word; two events around the
+    // GPU work of a round; the last call's times (ptk_last_rays_adaptive_ms)
+    float* d_radapt = nullptr; size_t radapt_rays = 0;
+    uint8_t* d_radapt_need = nullptr; size_t radapt_need_texels = 0;
+    uint32_t* h_radapt_total = nullptr;
+    hipEvent_t ev_radapt[2] = { nullptr, nullptr };
+    float radapt_ms[3] = { 0.0f, 0.0f, 0.0f };   // host wall time of the round loop; rays_keyed_kernel; the other kernels of the rounds
 
     // irradiance probe baking (ptk_bake_probes), each grown to the largest call so far: the basis table (36 B per direction), one
     // block of rays (origins | dirs, 24 B each) and, while the caller passes no table, the radiance table (12 B per ray); four
@@ -803,6 +816,9 @@ void ptk_destroy(ptk_ctx* c)
     dfree(c->d_rays_samples); dfree(c->d_rays_block);
     dfree(c->d_bake_plane); dfree(c->d_bake_compact); dfree(c->d_bake_dilate);
     if (c->h_bake_total) (void)hipHostFree(c->h_bake_total);
+    dfree(c->d_radapt); dfree(c->d_radapt_need);
+    if (c->h_radapt_total) (void)hipHostFree(c->h_radapt_total);
+    for (hipEvent_t e : c->ev_radapt) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_bake) if (e) (void)hipEventDestroy(e);
     dfree(c->d_probe_basis); dfree(c->d_probe_rays); dfree(c->d_probe_table);
     for (hipEvent_t e : c->ev_probes) if (e) (void)hipEventDestroy(e);
@@ -1717,16 +1733,14 @@ static int check_rays_args(ptk_ctx* c, int32_t num_rays, const float* origins, c
 // The call proper, on the context's stream, every pointer into this GPU's memory.  Cut into passes over the sample range - and,
 // where even one sample of every ray exceeds the budget, into blocks of rays - so that no pass's sample buffer exceeds
 // "pass_bytes" or half of the free device memory; a later pass folds onto what the earlier ones left in out.
-static int trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,
-                                uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, const uint32_t* d_keys = nullptr)
+// fold(ray0, rays, chunk, num_chunks, samples of the pass, samples of the earlier passes) queues what takes the pass's samples
+// out of c->d_rays_samples: rays_fold_kernel for a plain query, rays_fold_moments_kernel for an adaptive round.  spp > 0, and the
+// scene has a tree.
+using RaysFold = std::function<void(size_t ray0, int rays, int chunk, int num_chunks, uint32_t samples, uint32_t samples_before)>;
+static int trace_rays_passes(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,
+                             uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, const uint32_t* d_keys, const RaysFold& fold)
 {
     c->rays_passes = 0;
-    // (a scene without triangles has no tree to walk: every path is black)
-    if (spp == 0 || c->num_nodes == 0)
-    {
-        if (!(flags & PTK_RAYS_ACCUMULATE)) HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)num_rays * 3 * sizeof(float), c->stream));
-        return PTK_OK;
-    }
     if (!c->d_rays_block) HIPCHK(c, hipMalloc(&c->d_rays_block, sizeof(RaysBlock)));
     RenderParams p;
     fill_params(c, p, first_sample, spp, seed);
@@ -1791,13 +1805,30 @@ static int trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_ori
             launch_rays(p, r, c->d_rays_block, c->resident_waves, c->stream);
             HIPCHK(c, hipGetLastError());
             if (pi >= 0) HIPCHK(c, hipEventRecord(c->ev_rays[pi * 3 + 1], c->stream));
-            launch_rays_fold(c->d_rays_samples, d_out + ray0 * 3, (int)nr, p.chunk, p.num_chunks, n, ((flags & PTK_RAYS_ACCUMULATE) || done > 0) ? 1 : 0, c->stream);
+            fold(ray0, (int)nr, p.chunk, p.num_chunks, n, done);
             HIPCHK(c, hipGetLastError());
             if (pi >= 0) { HIPCHK(c, hipEventRecord(c->ev_rays[pi * 3 + 2], c->stream)); c->rays_passes = pi + 1; }
             done += n;
         }
     }
     return PTK_OK;
+}
+
+static int trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,
+                                uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, const uint32_t* d_keys = nullptr)
+{
+    c->rays_passes = 0;
+    // (a scene without triangles has no tree to walk: every path is black)
+    if (spp == 0 || c->num_nodes == 0)
+    {
+        if (!(flags & PTK_RAYS_ACCUMULATE)) HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)num_rays * 3 * sizeof(float), c->stream));
+        return PTK_OK;
+    }
+    return trace_rays_passes(c, num_rays, d_origins, d_dirs, max_depth, first_sample, spp, seed, key_base, flags, d_keys,
+                             [&](size_t ray0, int nr, int chunk, int num_chunks, uint32_t n, uint32_t done) {
+                                 launch_rays_fold(c->d_rays_samples, d_out + ray0 * 3, nr, chunk, num_chunks, n,
+                                                  ((flags & PTK_RAYS_ACCUMULATE) || done > 0) ? 1 : 0, c->stream);
+                             });
 }
 
 int ptk_trace_rays_device(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample, uint32_t spp,
@@ -1876,9 +1907,10 @@ static int check_lightmap_args(ptk_ctx* c, int width, int height, float offset, 
     return PTK_OK;
 }
 
-// Coverage - and, with d_out, the bake - on the context's stream, every pointer into this GPU's memory.
-static int bake_on_stream(ptk_ctx* c, int width, int height, const float* d_uvs, float offset, int max_depth, uint32_t first_sample, uint32_t spp,
-                          uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, int32_t* d_owner, float* d_bary, float* d_pos)
+// The front half of a bake on the context's stream: coverage and - with want_rays - the covered count (the one host wait) and the
+// compacted rays of the covered texels in b (their sums loaded from acc_out where that is not null: PTK_BAKE_ACCUMULATE).
+static int bake_rays_on_stream(ptk_ctx* c, int width, int height, const float* d_uvs, float offset, uint32_t key_base, uint32_t flags, bool want_rays,
+                               const float* acc_out, int32_t* d_owner, float* d_bary, float* d_pos, BakeParams& b, uint32_t& covered)
 {
     const size_t texels = (size_t)width * height, blocks = (texels + 255) / 256;
     c->bake_timed = false; c->bake_traced = false;
@@ -1892,7 +1924,7 @@ static int bake_on_stream(ptk_ctx* c, int width, int height, const float* d_uvs,
         HIPCHK(c, hipMalloc(&c->d_bake_plane, (texels + blocks + 1) * sizeof(int)));
         c->bake_plane_texels = texels;
     }
-    BakeParams b = {};
+    b = BakeParams{};
     b.uvs = d_uvs; b.shade = c->d_shade; b.verts = c->d_verts_res; b.num_tris = c->d_verts_res ? c->num_tris : 0;
     b.width = width; b.height = height; b.offset = offset; b.back = (flags & PTK_BAKE_BACK) ? 1 : 0; b.key_base = key_base;
     b.plane = c->d_bake_plane; b.block_counts = (uint32_t*)(c->d_bake_plane + c->bake_plane_texels);
@@ -1901,8 +1933,8 @@ static int bake_on_stream(ptk_ctx* c, int width, int height, const float* d_uvs,
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.plane, PTK_BAKE_UNOWNED, texels, c->stream));
     launch_bake_cover(b, c->stream);
     HIPCHK(c, hipGetLastError());
-    uint32_t covered = 0;
-    if (d_out)
+    covered = 0;
+    if (want_rays)
     {
         // the covered count sizes the compacted arrays and the trace: the one host wait of a bake
         if (!c->h_bake_total) HIPCHK(c, hipHostMalloc((void**)&c->h_bake_total, sizeof(uint32_t), hipHostMallocDefault));
@@ -1925,7 +1957,7 @@ static int bake_on_stream(ptk_ctx* c, int width, int height, const float* d_uvs,
             const size_t cap = c->bake_compact_rays;
             b.origins = c->d_bake_compact; b.dirs = b.origins + cap * 3; b.sums = b.dirs + cap * 3;
             b.keys = (uint32_t*)(b.sums + cap * 3); b.texel = b.keys + cap;
-            b.out = (flags & PTK_BAKE_ACCUMULATE) ? d_out : nullptr;
+            b.out = acc_out;
         }
     }
     else HIPCHK(c, hipEventRecord(c->ev_bake[1], c->stream));
@@ -1933,11 +1965,24 @@ static int bake_on_stream(ptk_ctx* c, int width, int height, const float* d_uvs,
     launch_bake_rays(b, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_bake[3], c->stream));
+    return PTK_OK;
+}
+
+// Coverage - and, with d_out, the bake - on the context's stream, every pointer into this GPU's memory.
+static int bake_on_stream(ptk_ctx* c, int width, int height, const float* d_uvs, float offset, int max_depth, uint32_t first_sample, uint32_t spp,
+                          uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, int32_t* d_owner, float* d_bary, float* d_pos)
+{
+    const size_t texels = (size_t)width * height;
+    BakeParams b;
+    uint32_t covered = 0;
+    int rc = bake_rays_on_stream(c, width, height, d_uvs, offset, key_base, flags, d_out != nullptr, (flags & PTK_BAKE_ACCUMULATE) ? d_out : nullptr,
+                                 d_owner, d_bary, d_pos, b, covered);
+    if (rc != PTK_OK) return rc;
     if (d_out)
     {
         if (covered)
         {
-            const int rc = trace_rays_on_stream(c, (int32_t)covered, b.origins, b.dirs, max_depth, first_sample, spp, seed, 0u,
+            rc = trace_rays_on_stream(c, (int32_t)covered, b.origins, b.dirs, max_depth, first_sample, spp, seed, 0u,
                                                 (flags & PTK_BAKE_ACCUMULATE) ? PTK_RAYS_ACCUMULATE : 0u, b.sums, b.keys);
             if (rc != PTK_OK) return rc;
         }
@@ -2010,6 +2055,278 @@ int ptk_bake_lightmap_device(ptk_ctx* c, int width, int height, const float* d_u
     if (rc != PTK_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     return bake_on_stream(c, width, height, d_uvs, offset, max_depth, first_sample, spp, seed, key_base, flags, d_out, d_owner, nullptr, nullptr);
+}
+
+// ---- adaptive ray queries and lightmap bakes (ptk.h) -------------------------------------------------------------------------
+static int check_adaptive_args(ptk_ctx* c, const char* who, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp)
+{
+    if (step < 2 || min_spp == 0 || min_spp % step != 0 || max_spp % step != 0 || min_spp > max_spp)
+        return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": need step >= 2 dividing min_spp and max_spp, 0 < min_spp <= max_spp");
+    if (!std::isfinite(threshold) || threshold < 0.0f) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": threshold must be finite and >= 0");
+    return PTK_OK;
+}
+
+// the context's adaptive buffer, cut up for its capacity
+struct RaysAdaptiveBuffers {
+    float *origins, *dirs, *s2;
+    uint32_t *keys, *src, *list, *keep, *counts, *block_counts, *total;
+};
+static RaysAdaptiveBuffers radapt_buffers(ptk_ctx* c)
+{
+    const size_t cap = c->radapt_rays;
+    RaysAdaptiveBuffers a;
+    a.origins = c->d_radapt; a.dirs = a.origins + cap * 3; a.s2 = a.dirs + cap * 3;
+    a.keys = (uint32_t*)(a.s2 + cap * 3); a.src = a.keys + cap; a.list = a.src + cap; a.keep = a.list + cap; a.counts = a.keep + cap;
+    a.block_counts = a.counts + cap; a.total = a.block_counts + (cap + 255) / 256;
+    return a;
+}
+
+// The round loop on the context's stream, every pointer into this GPU's memory; n > 0.  s2 / counts null: the context's own.
+// texel not null: a lightmap's covered texels (keys = their RNG pixels; the 3x3 rule over the width x height map).  Synchronous:
+// every round ends with the host reading the next round's ray count.
+static int rays_adaptive_on_stream(ptk_ctx* c, uint32_t n, const float* d_origins, const float* d_dirs, const uint32_t* d_keys, uint32_t key_base,
+                                   int max_depth, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t rays_flags,
+                                   float* s1, float* s2, uint32_t* counts, const uint32_t* texel, int width, int height, ptk_rays_adaptive_result* res)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    c->radapt_ms[0] = c->radapt_ms[1] = c->radapt_ms[2] = 0.0f;
+    if (n > c->radapt_rays)
+    {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        dfree(c->d_radapt); c->d_radapt = nullptr; c->radapt_rays = 0;
+        HIPCHK(c, hipMalloc(&c->d_radapt, ((size_t)n * 14 + ((size_t)n + 255) / 256 + 1) * sizeof(float)));
+        c->radapt_rays = n;
+    }
+    if (!c->h_radapt_total)
+    {
+        HIPCHK(c, hipHostMalloc((void**)&c->h_radapt_total, sizeof(uint32_t), hipHostMallocDefault));
+        for (hipEvent_t& e : c->ev_radapt) HIPCHK(c, hipEventCreate(&e));
+    }
+    const RaysAdaptiveBuffers a = radapt_buffers(c);
+    if (!s2) s2 = a.s2;
+    if (!counts) counts = a.counts;
+    uint8_t* need = nullptr;
+    if (texel)
+    {
+        const size_t texels = (size_t)width * height;
+        if (texels > c->radapt_need_texels)
+        {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            dfree(c->d_radapt_need); c->d_radapt_need = nullptr; c->radapt_need_texels = 0;
+            HIPCHK(c, hipMalloc(&c->d_radapt_need, texels));
+            c->radapt_need_texels = texels;
+        }
+        need = c->d_radapt_need;
+        HIPCHK(c, hipMemsetAsync(need, 0, texels, c->stream));
+    }
+    HIPCHK(c, hipMemsetAsync(s1, 0, (size_t)n * 3 * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(s2, 0, (size_t)n * 3 * sizeof(float), c->stream));
+    uint32_t rounds = 0, done = 0, active = n;
+    uint64_t ray_samples = 0;
+    if (c->num_nodes == 0)
+    {
+        // a scene without triangles has no tree to walk: every sample is black, and the rule decides at the first test - for all
+        // rays alike - whether black has converged (it has, unless the tolerance's square is not above 0)
+        const float tol = threshold * (0.0f + 1.0f / 256.0f);
+        const float tol2 = tol * tol;
+        done = 0.0f < tol2 ? min_spp : max_spp;
+        HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)counts, (int)done, n, c->stream));
+        rounds = done / step; ray_samples = (uint64_t)n * done;
+        active = 0.0f < tol2 ? 0u : n;
+    }
+    else
+    {
+        HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)n * sizeof(uint32_t), c->stream));
+        const uint32_t* list = nullptr;              // round 0: every ray, in index order
+        while (active > 0 && done < max_spp)
+        {
+            // no test before min_spp samples: the rounds up to there are traced as one
+            const uint32_t take = done == 0 ? min_spp : step;
+            HIPCHK(c, hipEventRecord(c->ev_radapt[0], c->stream));
+            launch_rays_gather(list, active, d_origins, d_dirs, d_keys, key_base, a.origins, a.dirs, a.keys, a.src, c->stream);
+            HIPCHK(c, hipGetLastError());
+            const int rc = trace_rays_passes(c, (int32_t)active, a.origins, a.dirs, max_depth, done, take, seed, 0u, rays_flags, a.keys,
+                                             [&](size_t ray0, int nr, int chunk, int num_chunks, uint32_t ns, uint32_t before) {
+                                                 // (the last pass of a block of rays counts the round's samples)
+                                                 launch_rays_fold_moments(c->d_rays_samples, a.src + ray0, s1, s2, counts, nr, chunk, num_chunks, ns,
+                                                                          before + ns == take ? take : 0u, c->stream);
+                                             });
+            if (rc != PTK_OK) return rc;
+            done += take; rounds += take / step; ray_samples += (uint64_t)active * take;
+            launch_rays_converge(a.src, active, s1, s2, counts, threshold, a.keep, need, texel, c->stream);
+            if (texel) launch_bake_keep(a.src, active, texel, need, width, height, a.keep, c->stream);
+            launch_rays_compact(a.src, a.keep, active, a.block_counts, a.total, a.list, c->stream);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(c->h_radapt_total, a.total, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipEventRecord(c->ev_radapt[1], c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (*c->h_radapt_total > active) return fail(c, PTK_ERR_HIP, "adaptive rays: the active list grew");
+            float all = 0.0f;
+            HIPCHK(c, hipEventElapsedTime(&all, c->ev_radapt[0], c->ev_radapt[1]));
+            float trace = 0.0f;
+            for (int i = 0; i < c->rays_passes; i++)
+            {
+                float t = 0.0f;
+                HIPCHK(c, hipEventElapsedTime(&t, c->ev_rays[i * 3], c->ev_rays[i * 3 + 1]));
+                trace += t;
+            }
+            c->radapt_ms[1] += trace; c->radapt_ms[2] += all - trace;
+            active = *c->h_radapt_total;
+            list = a.list;
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->radapt_ms[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (res)
+    {
+        res->rounds = rounds; res->max_count = done;
+        res->ray_samples = ray_samples; res->active_rays = active;
+    }
+    return PTK_OK;
+}
+
+static int check_rays_adaptive_args(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, float threshold, uint32_t min_spp, uint32_t step,
+                                    uint32_t max_spp, uint32_t flags, const float* sum, const uint32_t* counts, bool* nothing)
+{
+    *nothing = false;
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (flags & PTK_RAYS_ACCUMULATE) return fail(c, PTK_ERR_BAD_ARG, "ptk_trace_rays_adaptive: an adaptive query starts at sample 0, it cannot accumulate");
+    int rc = check_rays_args(c, num_rays, origins, dirs, flags, sum, nothing);
+    if (rc != PTK_OK) return rc;
+    *nothing = false;
+    if (num_rays > 0 && !counts) return fail(c, PTK_ERR_BAD_ARG, "ptk_trace_rays_adaptive: null counts");
+    rc = check_adaptive_args(c, "ptk_trace_rays_adaptive", threshold, min_spp, step, max_spp);
+    if (rc != PTK_OK) return rc;
+    *nothing = num_rays == 0;
+    return PTK_OK;
+}
+
+int ptk_trace_rays_adaptive_device(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, float threshold,
+                                   uint32_t min_spp, uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_sum,
+                                   float* d_sumsq, uint32_t* d_counts, ptk_rays_adaptive_result* res)
+{
+    bool nothing;
+    const int rc = check_rays_adaptive_args(c, num_rays, d_origins, d_dirs, threshold, min_spp, step, max_spp, flags, d_sum, d_counts, &nothing);
+    if (rc != PTK_OK) return rc;
+    if (res) std::memset(res, 0, sizeof(*res));
+    if (nothing) return PTK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return rays_adaptive_on_stream(c, (uint32_t)num_rays, d_origins, d_dirs, nullptr, key_base, max_depth, threshold, min_spp, step, max_spp, seed, flags,
+                                   d_sum, d_sumsq, d_counts, nullptr, 0, 0, res);
+}
+
+int ptk_trace_rays_adaptive(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, int max_depth, float threshold, uint32_t min_spp,
+                            uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* sum, float* sumsq, uint32_t* counts,
+                            ptk_rays_adaptive_result* res)
+{
+    bool nothing;
+    int rc = check_rays_adaptive_args(c, num_rays, origins, dirs, threshold, min_spp, step, max_spp, flags, sum, counts, &nothing);
+    if (rc != PTK_OK) return rc;
+    if (res) std::memset(res, 0, sizeof(*res));
+    if (nothing) return PTK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    // origins | dirs | sum | sumsq | counts, staged for the length of the call
+    const size_t n3 = (size_t)num_rays * 3, bytes = n3 * sizeof(float);
+    float* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, 4 * bytes + (size_t)num_rays * sizeof(uint32_t)));
+    float *d_sum = d + 2 * n3, *d_sumsq = d + 3 * n3;
+    uint32_t* d_counts = (uint32_t*)(d + 4 * n3);
+    hipError_t e = hipMemcpyAsync(d, origins, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + n3, dirs, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+    {
+        rc = rays_adaptive_on_stream(c, (uint32_t)num_rays, d, d + n3, nullptr, key_base, max_depth, threshold, min_spp, step, max_spp, seed, flags, d_sum,
+                                     d_sumsq, d_counts, nullptr, 0, 0, res);
+        if (rc == PTK_OK) e = hipMemcpyAsync(sum, d_sum, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess && sumsq) e = hipMemcpyAsync(sumsq, d_sumsq, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, (size_t)num_rays * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also on the way out of a failure: the staging buffer may be in use)
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    if (rc != PTK_OK) return rc;
+    if (e != hipSuccess) return fail(c, PTK_ERR_HIP, hipGetErrorString(e));
+    return PTK_OK;
+}
+
+static int check_lightmap_adaptive_args(ptk_ctx* c, int width, int height, float offset, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp,
+                                        uint32_t flags, const float* out, const uint32_t* counts)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (flags & PTK_BAKE_ACCUMULATE) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_lightmap_adaptive: an adaptive bake starts at sample 0, it cannot accumulate");
+    int rc = check_lightmap_args(c, width, height, offset, flags, out);
+    if (rc != PTK_OK) return rc;
+    if (!counts) return fail(c, PTK_ERR_BAD_ARG, "ptk_bake_lightmap_adaptive: null counts");
+    return check_adaptive_args(c, "ptk_bake_lightmap_adaptive", threshold, min_spp, step, max_spp);
+}
+
+int ptk_bake_lightmap_adaptive_device(ptk_ctx* c, int width, int height, const float* d_uvs, float offset, int max_depth, float threshold, uint32_t min_spp,
+                                      uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, uint32_t* d_counts,
+                                      int32_t* d_owner, ptk_rays_adaptive_result* res)
+{
+    int rc = check_lightmap_adaptive_args(c, width, height, offset, threshold, min_spp, step, max_spp, flags, d_out, d_counts);
+    if (rc != PTK_OK) return rc;
+    if (res) std::memset(res, 0, sizeof(*res));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t texels = (size_t)width * height;
+    BakeParams b;
+    uint32_t covered = 0;
+    rc = bake_rays_on_stream(c, width, height, d_uvs, offset, key_base, flags, true, nullptr, d_owner, nullptr, nullptr, b, covered);
+    if (rc != PTK_OK) return rc;
+    HIPCHK(c, hipMemsetAsync(d_out, 0, texels * 3 * sizeof(float), c->stream));                 // uncovered texels
+    HIPCHK(c, hipMemsetAsync(d_counts, 0, texels * sizeof(uint32_t), c->stream));
+    if (covered)
+    {
+        rc = rays_adaptive_on_stream(c, covered, b.origins, b.dirs, b.keys, 0u, max_depth, threshold, min_spp, step, max_spp, seed, 0u, b.sums, nullptr,
+                                     nullptr, b.texel, width, height, res);
+        if (rc != PTK_OK) return rc;
+        launch_bake_scatter(b.sums, b.texel, covered, d_out, c->stream);
+        launch_bake_scatter_counts(radapt_buffers(c).counts, b.texel, covered, d_counts, c->stream);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PTK_OK;
+}
+
+int ptk_bake_lightmap_adaptive(ptk_ctx* c, int width, int height, const float* uvs, float offset, int max_depth, float threshold, uint32_t min_spp,
+                               uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* out, uint32_t* counts, int32_t* owner,
+                               ptk_rays_adaptive_result* res)
+{
+    int rc = check_lightmap_adaptive_args(c, width, height, offset, threshold, min_spp, step, max_spp, flags, out, counts);
+    if (rc != PTK_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // uvs | out | counts | owner, staged for the length of the call
+    const size_t texels = (size_t)width * height, n_uv = uvs ? (size_t)c->num_tris * 6 : 0;
+    float* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, (n_uv + texels * 5) * sizeof(float)));
+    float* d_out = d + n_uv;
+    uint32_t* d_counts = (uint32_t*)(d_out + texels * 3);
+    int32_t* d_owner = owner ? (int32_t*)(d_counts + texels) : nullptr;
+    hipError_t e = hipSuccess;
+    if (n_uv) e = hipMemcpyAsync(d, uvs, n_uv * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+    {
+        rc = ptk_bake_lightmap_adaptive_device(c, width, height, n_uv ? d : nullptr, offset, max_depth, threshold, min_spp, step, max_spp, seed, key_base,
+                                               flags, d_out, d_counts, d_owner, res);
+        if (rc == PTK_OK) e = hipMemcpyAsync(out, d_out, texels * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, texels * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess && owner) e = hipMemcpyAsync(owner, d_owner, texels * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also on the way out of a failure: the staging buffer may be in use)
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    if (rc != PTK_OK) return rc;
+    if (e != hipSuccess) return fail(c, PTK_ERR_HIP, hipGetErrorString(e));
+    return PTK_OK;
+}
+
+int ptk_last_rays_adaptive_ms(ptk_ctx* c, float* total_ms, float* trace_ms, float* other_ms)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (total_ms) *total_ms = c->radapt_ms[0];
+    if (trace_ms) *trace_ms = c->radapt_ms[1];
+    if (other_ms) *other_ms = c->radapt_ms[2];
+    return PTK_OK;
 }
 
 static int check_dilate_args(ptk_ctx* c, int width, int height, int passes, const float* image, const int32_t* owner)

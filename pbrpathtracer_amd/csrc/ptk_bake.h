@@ -32,6 +32,8 @@ struct BakeParams {
 void launch_bake_cover(const BakeParams& p, hipStream_t stream);
 // block_counts <- exclusive prefix of the covered texels per block; *total <- their number
 void launch_bake_count(const BakeParams& p, uint32_t* total, hipStream_t stream);
+// the scan alone: counts[0 .. n) <- their exclusive prefix sums, *total <- their sum (ptk_rays_adaptive.hip compacts with it)
+void launch_bake_scan(uint32_t* counts, uint32_t n, uint32_t* total, hipStream_t stream);
 void launch_bake_rays(const BakeParams& p, hipStream_t stream);
 // out[texel[i]] = sums[i]
 void launch_bake_scatter(const float* sums, const uint32_t* texel, uint32_t count, float* out, hipStream_t stream);

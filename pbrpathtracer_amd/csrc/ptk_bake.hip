@@ -222,7 +222,12 @@ void launch_bake_count(const BakeParams& p, uint32_t* total, hipStream_t stream)
 {
     const size_t texels = (size_t)p.width * p.height;
     hipLaunchKernelGGL(bake_count_kernel, dim3(texel_blocks(texels)), dim3(PTK_BAKE_BLOCK), 0, stream, p.plane, texels, p.block_counts);
-    hipLaunchKernelGGL(bake_scan_kernel, dim3(1), dim3(PTK_BAKE_SCAN), 0, stream, p.block_counts, (uint32_t)texel_blocks(texels), total);
+    launch_bake_scan(p.block_counts, (uint32_t)texel_blocks(texels), total, stream);
+}
+
+void launch_bake_scan(uint32_t* counts, uint32_t n, uint32_t* total, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bake_scan_kernel, dim3(1), dim3(PTK_BAKE_SCAN), 0, stream, counts, n, total);
 }
 
 void launch_bake_rays(const BakeParams& p, hipStream_t stream)

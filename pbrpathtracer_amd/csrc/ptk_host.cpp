@@ -123,6 +123,17 @@ int pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, fl
 {
     return t->pt.BakeLightmap(width, height, uvs, offset, first_sample, spp, key_base, flags, out, owner) ? 1 : 0;
 }
+int pth_trace_rays_adaptive(pth_tracer* t, int num_rays, const float* origins, const float* dirs, float threshold, uint32_t min_spp, uint32_t step,
+                            uint32_t max_spp, uint32_t key_base, uint32_t flags, float* sum, float* sumsq, uint32_t* counts, ptk_rays_adaptive_result* res)
+{
+    return t->pt.TraceRaysAdaptive(num_rays, origins, dirs, threshold, min_spp, step, max_spp, key_base, flags, sum, sumsq, counts, res) ? 1 : 0;
+}
+int pth_bake_lightmap_adaptive(pth_tracer* t, int width, int height, const float* uvs, float offset, float threshold, uint32_t min_spp, uint32_t step,
+                               uint32_t max_spp, uint32_t key_base, uint32_t flags, float* out, uint32_t* counts, int32_t* owner,
+                               ptk_rays_adaptive_result* res)
+{
+    return t->pt.BakeLightmapAdaptive(width, height, uvs, offset, threshold, min_spp, step, max_spp, key_base, flags, out, counts, owner, res) ? 1 : 0;
+}
 int pth_bake_coverage(pth_tracer* t, int width, int height, const float* uvs, int32_t* owner, float* bary, float* pos)
 {
     return t->pt.BakeCoverage(width, height, uvs, owner, bary, pos) ? 1 : 0;

@@ -37,6 +37,7 @@ HOST_SYMBOLS = [
     "pth_export_png", "pth_render_adaptive", "pth_read_sample_counts",
     "pth_render_features", "pth_read_feature", "pth_pick", "pth_set_object_transform", "pth_trace_rays", "pth_get_camera",
     "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
+    "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive",
 ]
 
 _bound = False
@@ -99,6 +100,11 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_bake_probes.restype = i32
         L.pth_bake_probes.argtypes = [vp, i32, vp, i32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32, vp, vp]
         L.pth_sample_probes.restype = i32; L.pth_sample_probes.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
+        u32, res = C.c_uint32, C.POINTER(_ptk.RaysAdaptiveResult)
+        L.pth_trace_rays_adaptive.restype = i32
+        L.pth_trace_rays_adaptive.argtypes = [vp, i32, vp, vp, f32, u32, u32, u32, u32, u32, vp, vp, vp, res]
+        L.pth_bake_lightmap_adaptive.restype = i32
+        L.pth_bake_lightmap_adaptive.argtypes = [vp, i32, i32, vp, f32, f32, u32, u32, u32, u32, u32, vp, vp, vp, res]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -337,6 +343,37 @@ class PathTracer:
                                         int(key_base) & 0xffffffff, flags, out.ctypes.data, owner.ctypes.data):
             raise _ptk.PtkError("BakeLightmap failed: " + self.LastError())
         return out, owner
+
+    def TraceRaysAdaptive(self, origins, dirs, threshold: float, min_spp: int, step: int, max_spp: int, key_base: int = 0,
+                          lens_draws: bool = False):
+        """Extension: adaptive ray query (include/ptk.h ptk_trace_rays_adaptive) at this tracer's seed and trace depth.  Returns
+        (sum [n, 3] float32, sumsq [n, 3] float32, counts [n] uint32, result dict); the mean is sum / counts."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        assert len(d) == len(o), "as many directions as origins"
+        s1 = np.empty((len(o), 3), np.float32); s2 = np.empty((len(o), 3), np.float32); counts = np.empty((len(o),), np.uint32)
+        r = _ptk.RaysAdaptiveResult()
+        ptr = (lambda a: a.ctypes.data if len(o) else None)
+        if not self.L.pth_trace_rays_adaptive(self.h, len(o), ptr(o), ptr(d), float(threshold), int(min_spp), int(step), int(max_spp),
+                                              int(key_base) & 0xffffffff, _ptk.RAYS_LENS_DRAWS if lens_draws else 0, ptr(s1), ptr(s2),
+                                              ptr(counts), C.byref(r)):
+            raise _ptk.PtkError("TraceRaysAdaptive failed: " + self.LastError())
+        return s1, s2, counts, r.as_dict()
+
+    def BakeLightmapAdaptive(self, width: int, height: int, offset: float, threshold: float, min_spp: int, step: int, max_spp: int,
+                             uvs=None, key_base: int = 0, back: bool = False):
+        """Extension: adaptive lightmap bake (include/ptk.h ptk_bake_lightmap_adaptive) at this tracer's seed and trace depth.
+        Returns (sums [H, W, 3] float32, counts [H, W] uint32, owner [H, W] int32, result dict), rows bottom-up."""
+        u, up = self._chart_uvs(uvs)
+        out = np.empty((height, width, 3), np.float32)
+        counts = np.empty((height, width), np.uint32)
+        owner = np.empty((height, width), np.int32)
+        r = _ptk.RaysAdaptiveResult()
+        if not self.L.pth_bake_lightmap_adaptive(self.h, int(width), int(height), up, float(offset), float(threshold), int(min_spp),
+                                                 int(step), int(max_spp), int(key_base) & 0xffffffff, _ptk.BAKE_BACK if back else 0,
+                                                 out.ctypes.data, counts.ctypes.data, owner.ctypes.data, C.byref(r)):
+            raise _ptk.PtkError("BakeLightmapAdaptive failed: " + self.LastError())
+        return out, counts, owner, r.as_dict()
 
     def BakeCoverage(self, width: int, height: int, uvs=None):
         """Extension: (owner [H, W] int32, bary [H, W, 2], pos [H, W, 3]) of a lightmap's texels (ptk_bake_coverage); no tracing."""

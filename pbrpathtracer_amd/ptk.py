@@ -61,6 +61,14 @@ class AdaptiveResult(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class RaysAdaptiveResult(C.Structure):
+    """ptk_rays_adaptive_result"""
+    _fields_ = [("rounds", C.c_uint32), ("max_count", C.c_uint32), ("ray_samples", C.c_uint64), ("active_rays", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class PtkError(RuntimeError):
     pass
 
@@ -85,6 +93,8 @@ SYMBOLS = [
     "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
     "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
     "ptk_last_bake_ms",
+    "ptk_trace_rays_adaptive", "ptk_trace_rays_adaptive_device", "ptk_bake_lightmap_adaptive", "ptk_bake_lightmap_adaptive_device",
+    "ptk_last_rays_adaptive_ms",
     "ptk_bake_probes", "ptk_bake_probes_device", "ptk_probes_irradiance", "ptk_probes_irradiance_device", "ptk_last_probes_ms",
 ]
 
@@ -175,6 +185,11 @@ def _load_locked() -> C.CDLL:
         for fn in (L.ptk_probes_irradiance, L.ptk_probes_irradiance_device):
             fn.argtypes = [vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp]
         L.ptk_last_probes_ms.argtypes = [vp, fp, fp, fp]
+        for fn in (L.ptk_trace_rays_adaptive, L.ptk_trace_rays_adaptive_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, i32, f32, u32, u32, u32, u64, u32, u32, vp, vp, vp, C.POINTER(RaysAdaptiveResult)]
+        for fn in (L.ptk_bake_lightmap_adaptive, L.ptk_bake_lightmap_adaptive_device):
+            fn.argtypes = [vp, i32, i32, vp, f32, i32, f32, u32, u32, u32, u64, u32, u32, vp, vp, vp, C.POINTER(RaysAdaptiveResult)]
+        L.ptk_last_rays_adaptive_ms.argtypes = [vp, fp, fp, fp]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -507,6 +522,81 @@ class Context:
         t = [C.c_float(0) for _ in range(4)]
         self._chk(self.L.ptk_last_bake_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_bake_ms")
         return dict(zip(("coverage_ms", "raygen_ms", "trace_ms", "scatter_ms"), (x.value for x in t)))
+
+    # ---- adaptive ray queries and lightmap bakes ---------------------------------------------
+    def trace_rays_adaptive(self, origins, dirs, max_depth: int, threshold: float, min_spp: int, step: int, max_spp: int, seed: int,
+                            key_base: int = 0, lens_draws: bool = False, want_sumsq: bool = True):
+        """ptk_trace_rays_adaptive: rounds of `step` samples along the rays (origins[i], dirs[i]) until each ray's noise meets
+        `threshold` (the rule of render_adaptive, per ray) or it has max_spp.  Returns (sum [n, 3] float32, sumsq [n, 3] float32 or
+        None, counts [n] uint32, result dict: rounds, max_count, ray_samples, active_rays); sum[i] is bit for bit
+        trace_rays(first_sample 0, spp counts[i]) of ray i, the mean is sum / counts.  numpy arrays go through the host entry and
+        give numpy arrays; torch tensors on the context's GPU go through the device entry with no host copy and give tensors
+        (counts as int32 holding the uint32 bits).  Either way the call is synchronous."""
+        flags = RAYS_LENS_DRAWS if lens_draws else 0
+        args = (int(max_depth), float(threshold), int(min_spp), int(step), int(max_spp), int(seed), int(key_base) & 0xffffffff, flags)
+        r = RaysAdaptiveResult()
+        if hasattr(origins, "data_ptr"):
+            import torch
+            dev = self.device_ordinal()
+            n = origins.numel() // 3
+            for t in (origins, dirs):
+                assert t.is_cuda and t.device.index == dev, f"tensor on {t.device}, context on device {dev}"
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n * 3, "[n, 3] float32 contiguous tensors"
+            s1 = torch.empty((n, 3), dtype=torch.float32, device=origins.device)
+            s2 = torch.empty((n, 3), dtype=torch.float32, device=origins.device) if want_sumsq else None
+            counts = torch.empty((n,), dtype=torch.int32, device=origins.device)
+            ptr = (lambda t: C.c_void_p(t.data_ptr()) if n and t is not None else None)
+            self._chk(self.L.ptk_trace_rays_adaptive_device(self.h, n, ptr(origins), ptr(dirs), *args, ptr(s1), ptr(s2), ptr(counts),
+                                                            C.byref(r)), "ptk_trace_rays_adaptive_device")
+            return s1, s2, counts, r.as_dict()
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n, "as many directions as origins"
+        s1 = np.empty((n, 3), np.float32)
+        s2 = np.empty((n, 3), np.float32) if want_sumsq else None
+        counts = np.empty((n,), np.uint32)
+        ptr = (lambda a: a.ctypes.data if n and a is not None else None)
+        self._chk(self.L.ptk_trace_rays_adaptive(self.h, n, ptr(o), ptr(d), *args, ptr(s1), ptr(s2), ptr(counts), C.byref(r)),
+                  "ptk_trace_rays_adaptive")
+        return s1, s2, counts, r.as_dict()
+
+    def bake_lightmap_adaptive(self, width: int, height: int, offset: float, max_depth: int, threshold: float, min_spp: int, step: int,
+                               max_spp: int, seed: int, uvs=None, key_base: int = 0, back: bool = False, device: bool = False):
+        """ptk_bake_lightmap_adaptive: (sums [H, W, 3] float32, counts [H, W] uint32, owner [H, W] int32, result dict) of a
+        width x height lightmap baked in rounds of `step` samples until each covered texel's 3x3 neighbourhood meets `threshold`,
+        or max_spp; rows bottom-up; uncovered texels hold 0 / 0; the mean is sums / counts.  numpy uvs (or none) go through the host
+        entry; a torch tensor for uvs - or device=True - through the device entry: tensors on the context's GPU (counts as int32
+        holding the uint32 bits).  Either way the call is synchronous.  back: PTK_BAKE_BACK."""
+        flags = BAKE_BACK if back else 0
+        args = (float(offset), int(max_depth), float(threshold), int(min_spp), int(step), int(max_spp), int(seed), int(key_base) & 0xffffffff,
+                flags)
+        r = RaysAdaptiveResult()
+        if device or hasattr(uvs, "data_ptr"):
+            import torch
+            dev = torch.device("cuda", self.device_ordinal())
+            u, up = self._bake_uvs(uvs, True)
+            out = torch.empty((height, width, 3), dtype=torch.float32, device=dev)
+            counts = torch.empty((height, width), dtype=torch.int32, device=dev)
+            owner = torch.empty((height, width), dtype=torch.int32, device=dev)
+            self._chk(self.L.ptk_bake_lightmap_adaptive_device(self.h, int(width), int(height), up, *args, C.c_void_p(out.data_ptr()),
+                                                               C.c_void_p(counts.data_ptr()), C.c_void_p(owner.data_ptr()), C.byref(r)),
+                      "ptk_bake_lightmap_adaptive_device")
+            return out, counts, owner, r.as_dict()
+        u, up = self._bake_uvs(uvs, False)
+        out = np.empty((height, width, 3), np.float32)
+        counts = np.empty((height, width), np.uint32)
+        owner = np.empty((height, width), np.int32)
+        self._chk(self.L.ptk_bake_lightmap_adaptive(self.h, int(width), int(height), up, *args, out.ctypes.data, counts.ctypes.data,
+                                                    owner.ctypes.data, C.byref(r)), "ptk_bake_lightmap_adaptive")
+        return out, counts, owner, r.as_dict()
+
+    def last_rays_adaptive_ms(self) -> dict:
+        """Times (ms) of the last adaptive ray query or bake: the host's wall time for the round loop, the HIP-event time of its
+        rays_keyed_kernel launches, that of the other kernels of its rounds."""
+        t = [C.c_float(0) for _ in range(3)]
+        self._chk(self.L.ptk_last_rays_adaptive_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_rays_adaptive_ms")
+        return dict(zip(("total_ms", "trace_ms", "other_ms"), (x.value for x in t)))
 
     # ---- irradiance probes -----------------------------------------------------------------
     def bake_probes(self, positions, dirs, max_depth: int, first_sample: int, spp: int, seed: int, weight: float, key_base: int = 0,

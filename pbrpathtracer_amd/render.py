@@ -9,7 +9,9 @@
     python -m pbrpathtracer_amd.render scene.pts --bake-probes NX NY NZ [--probe-dirs D] --spp N -o probes.npz
 
 With --noise-threshold the render is adaptive (include/ptk.h ptk_render_adaptive): --spp becomes the most samples a pixel
-gets, and pixels stop once their noise meets the threshold.
+gets, and pixels stop once their noise meets the threshold.  --equirect and --bake-lightmap take it too (ptk_trace_rays_adaptive,
+ptk_bake_lightmap_adaptive): the image is then the mean sum / count per pixel or texel, --npy FILE.npy holds that float32 mean and
+FILE.counts.npy beside it the uint32 sample counts.
 
 With --equirect WIDTH the image is a WIDTH x WIDTH/2 latitude-longitude panorama from the scene's camera position, traced through
 PathTracer.TraceRays (include/ptk.h ptk_trace_rays; rays.equirect_rays) instead of the perspective camera.
@@ -77,6 +79,22 @@ def resolve_mean(total, spp):
     return (x * np.float32(255)).astype(np.uint8)
 
 
+def adaptive_args(a):
+    """(threshold, min_spp, step, max_spp) of an adaptive call: --spp is the maximum, --min-spp defaults to 2 x step"""
+    return a.noise_threshold, a.min_spp if a.min_spp is not None else min(2 * a.step, a.spp), a.step, a.spp
+
+
+def mean_of(total, counts):
+    """sum / count in float32, 0 where the count is 0"""
+    with np.errstate(all="ignore"):
+        m = total / counts.astype(np.float32)[..., None]
+    return np.where(counts[..., None] == 0, np.float32(0), m).astype(np.float32)
+
+
+def counts_path(npy: str) -> str:
+    return (npy[:-4] if npy.endswith(".npy") else npy) + ".counts.npy"
+
+
 def bake_offset(pt) -> float:
     """the default --bake-offset: 1e-3 of the largest side of the staged scene's bounding box"""
     v = np.asarray(pt.StagedScene()["verts"], np.float64).reshape(-1, 3)
@@ -93,6 +111,8 @@ def render_lightmap(pt, a) -> int:
     uvs = grid_atlas(pt.GetTriangleCount(), size, size) if a.bake_atlas else None
     offset = a.bake_offset if a.bake_offset is not None else bake_offset(pt)
     t1 = time.time()
+    if a.noise_threshold is not None:
+        return render_lightmap_adaptive(pt, a, size, uvs, offset)
     total, owner = pt.BakeLightmap(size, size, offset, 0, a.spp, uvs=uvs, back=a.bake_back)
     covered = int((owner >= 0).sum())
     if a.dilate:
@@ -103,6 +123,27 @@ def render_lightmap(pt, a) -> int:
         np.save(a.npy, total)
     print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {size}x{size} lightmap, {covered} texels covered, {a.spp} spp, "
           f"depth {pt.GetTraceDepth()}, offset {offset:g}: {t2 - t1:.3f} s ({covered * a.spp / (t2 - t1) / 1e6:.0f} Msamples/s) -> {a.out}")
+    return 0
+
+
+def render_lightmap_adaptive(pt, a, size, uvs, offset) -> int:
+    """--bake-lightmap with --noise-threshold: the mean per texel, padded like a plain bake"""
+    from .pathtracer import export_png
+    t1 = time.time()
+    total, counts, owner, res = pt.BakeLightmapAdaptive(size, size, offset, *adaptive_args(a), uvs=uvs, back=a.bake_back)
+    covered = int((owner >= 0).sum())
+    mean = mean_of(total, counts)
+    if a.dilate:
+        pt.DilateLightmap(mean, owner, a.dilate)
+    t2 = time.time()
+    export_png(a.out, resolve_mean(mean, 1))
+    if a.npy:
+        np.save(a.npy, mean)
+        np.save(counts_path(a.npy), counts)
+    print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {size}x{size} lightmap, {covered} texels covered, depth {pt.GetTraceDepth()}, "
+          f"offset {offset:g}: {t2 - t1:.3f} s -> {a.out}")
+    print(f"adaptive (threshold {a.noise_threshold}): {res['ray_samples']} texel samples of {covered * a.spp} "
+          f"({res['ray_samples'] / max(covered * a.spp, 1):.3f}), {res['rounds']} rounds, {res['active_rays']} texels still active")
     return 0
 
 
@@ -140,6 +181,18 @@ def render_equirect(pt, a) -> int:
         return 1
     origins, dirs = equirect_rays(*pt.GetCamera(), w, h)
     t1 = time.time()
+    if a.noise_threshold is not None:
+        total, _, counts, res = pt.TraceRaysAdaptive(origins, dirs, *adaptive_args(a))
+        mean = mean_of(total.reshape(h, w, 3), counts.reshape(h, w))
+        t2 = time.time()
+        export_png(a.out, resolve_mean(mean, 1)[::-1].copy())
+        if a.npy:
+            np.save(a.npy, mean)
+            np.save(counts_path(a.npy), counts.reshape(h, w))
+        print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {w}x{h} panorama, depth {pt.GetTraceDepth()}: {t2 - t1:.3f} s -> {a.out}")
+        print(f"adaptive (threshold {a.noise_threshold}): {res['ray_samples']} ray samples of {w * h * a.spp} "
+              f"({res['ray_samples'] / (w * h * a.spp):.3f}), {res['rounds']} rounds, {res['active_rays']} rays still active")
+        return 0
     total = pt.TraceRays(origins, dirs, 0, a.spp).reshape(h, w, 3)
     t2 = time.time()
     with np.errstate(all="ignore"):
