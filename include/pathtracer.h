@@ -205,6 +205,15 @@ public:
     // material and geometry edits apply as for RenderFrame(); the image and the sample count are not touched.
     bool TraceRays(int num_rays, const float* origins, const float* dirs, uint32_t first_sample, uint32_t spp, uint32_t key_base,
                    uint32_t flags, float* out);
+    // Extensions: closest-hit and occlusion queries for caller-supplied rays (include/ptk.h ptk_intersect_rays / ptk_occluded_rays,
+    // host arrays, synchronous) with the opacity draws of sample `sample` at the class's seed and RNG pixel key_base + i.  tri, t,
+    // bary (2 per ray) and material may each be null, not all four; tmax null: +inf; directions are used as given, t in units of
+    // |dir|.  Valid after BuildBVH() with no resolution set; pending material and geometry edits apply as for TraceRays; the image
+    // and the sample count are not touched.
+    bool IntersectRays(int num_rays, const float* origins, const float* dirs, uint32_t sample, uint32_t key_base, int32_t* tri, float* t,
+                       float* bary, int32_t* material);
+    bool OccludedRays(int num_rays, const float* origins, const float* dirs, const float* tmax, uint32_t sample, uint32_t key_base,
+                      uint8_t* occluded);
     // Extensions: lightmap baking (include/ptk.h ptk_bake_lightmap / ptk_bake_coverage / ptk_lightmap_dilate, host arrays,
     // synchronous) at the class's seed and trace depth.  uvs: [triangles][6] chart corners, or null for the scene's own uvs;
     // out: width*height*3 floats, rows bottom-up; owner (may be null): width*height triangle indices, -1 uncovered;

@@ -355,6 +355,51 @@ int ptk_trace_rays_device(ptk_ctx* ctx, int32_t num_rays, const float* d_origins
  * its passes (the first 64 of them) - rays_kernel with its one-wave set-up launch, rays_fold_kernel; waits for the call */
 int ptk_last_rays_ms(ptk_ctx* ctx, float* trace_ms, float* fold_ms);
 
+/* ---- closest-hit and occlusion queries for caller-supplied rays (no counterpart in the reference's interface: its Hit is private) --
+ * "What does this ray hit" and "is anything between these two points": probe visibility, ambient occlusion, validity of baked
+ * texels, line of sight, depth panoramas, collision picking.  For the uploaded scene and num_rays rays (origins[i], dirs[i]):
+ * CANDIDATE RULE, the product's own (tri_test; oracle/pt_oracle.c test_triangle).  Triangle k is ACCEPTED by ray i when
+ * Moeller-Trumbore (pathtracer.cpp:373-409) accepts it with t > 1e-5 and t < inf and - where its material binds an opacity map -
+ *   u01(hash32(k + hash32(0 + key_i))) < tex2d(opacity map, uv(u, v)).r
+ * i.e. the ray is ray number 0 of a path whose key is key_i = hash32(sample + pixel_key(seed, (key_base + i) mod 2^32)): the key
+ * ptk_trace_rays gives sample `sample` of that ray.  No draw is consumed from any stream (so PTK_RAYS_LENS_DRAWS has no counterpart
+ * here), and acceptance is a function of (ray, triangle) alone.
+ *   ptk_intersect_rays: the HIT of ray i is the accepted triangle of smallest t, ties going to the smaller index - bit for bit the
+ *     first interaction of sample `sample` of ptk_trace_rays for that ray, and, for a camera's feature rays with key_base + i = the
+ *     pixel's top-down index, bit for bit the DEPTH / TRIANGLE / BARY / MATERIAL planes of ptk_render_features(sample, seed).
+ *     Outputs, each of which may be NULL but not all four: tri[n] (-1 on a miss), t[n] (+inf on a miss), bary[n][2] = u, v (0 on a
+ *     miss), material[n] (-1 on a miss).
+ *   ptk_occluded_rays: occluded[i] = 1 when some accepted triangle has t < tmax[i], STRICTLY, else 0.  tmax == NULL stands for
+ *     +inf for every ray; a tmax that is NaN, zero or negative gives 0.  This is "closest t < tmax", so it does not depend on the
+ *     order in which a walk meets the triangles, although the walk stops at the first accepted one.
+ * Neither call depends on the builder that made the tree, on "bvh_leaf_max", on "flat" (they always walk the BVH), on ptk_set_tile
+ * or on "contract" (their kernels exist once, in the exact arithmetic), nor on how a ray set is cut into calls (each call's
+ * key_base = the global index of its first ray) (tests/test_gpu_hits.py: array_equal).  Directions are used as given and need
+ * not be unit vectors: t is in units of |dir|, so the segment from a to b is (a, b - a) with tmax = 1.  A non-finite component makes
+ * THAT ray's output unspecified and affects neither another ray nor whether the call ends.
+ * The calls need a scene only - no camera, no frame - and read it as ptk_update_materials / ptk_update_geometry left it.  They
+ * touch no frame, adaptive, feature or bake state, stay legal after ptk_render_adaptive, and ptk_request_exit does not cut them.
+ *   ptk_intersect_rays, ptk_occluded_rays: host arrays, synchronous; 24 B per ray plus the requested outputs (and tmax) are
+ *     staged in device memory for the length of the call.
+ *   ptk_intersect_rays_device, ptk_occluded_rays_device: every array in memory of this context's GPU, asynchronous on the
+ *     context's stream (the caller's after ptk_set_stream).  No host wait and no allocation of device memory inside the call.
+ *     The arrays must stay allocated until the stream has passed the call.
+ * PTK_ERR_BAD_ARG: a null context, a call before ptk_upload_scene, num_rays < 0, a null origins / dirs / occluded with
+ * num_rays > 0, all four hit outputs NULL; a refused call leaves the outputs alone.  num_rays == 0 is PTK_OK and does nothing.  A
+ * scene without triangles gives misses, or 0 for occlusion.  PTK_ERR_LIMIT as for ptk_trace_rays.
+ * Limits: one workgroup per 64 rays, in one launch: every num_rays the signature allows (2^31 - 1 rays are 2^25 workgroups). */
+int ptk_intersect_rays(ptk_ctx* ctx, int32_t num_rays, const float* origins /*[n][3]*/, const float* dirs /*[n][3]*/, uint32_t sample,
+                       uint64_t seed, uint32_t key_base, int32_t* tri /*[n]*/, float* t /*[n]*/, float* bary /*[n][2]*/, int32_t* material /*[n]*/);
+int ptk_intersect_rays_device(ptk_ctx* ctx, int32_t num_rays, const float* d_origins, const float* d_dirs, uint32_t sample, uint64_t seed,
+                              uint32_t key_base, int32_t* d_tri, float* d_t, float* d_bary, int32_t* d_material);
+int ptk_occluded_rays(ptk_ctx* ctx, int32_t num_rays, const float* origins /*[n][3]*/, const float* dirs /*[n][3]*/,
+                      const float* tmax /*[n] or NULL*/, uint32_t sample, uint64_t seed, uint32_t key_base, uint8_t* occluded /*[n]*/);
+int ptk_occluded_rays_device(ptk_ctx* ctx, int32_t num_rays, const float* d_origins, const float* d_dirs, const float* d_tmax,
+                             uint32_t sample, uint64_t seed, uint32_t key_base, uint8_t* d_occluded);
+/* measurement hook (tools/hits_timing.py), not part of the feature: the HIP-event time of the last hit or occlusion query's kernel
+ * (0 where the call launched none); waits for the call */
+int ptk_last_hits_ms(ptk_ctx* ctx, float* ms);
+
 /* ---- lightmap baking: the radiance leaving the scene's surfaces, per texel of a uv chart layout (no counterpart in the reference) --
  * The surface half of light baking in front of and behind ptk_trace_rays' kernel: a uv rasteriser, a ray generator, a scatter and
  * a chart-padding pass, all on the GPU from what ptk_upload_scene left resident.  Inputs: the uploaded scene, a lightmap of

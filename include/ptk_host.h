@@ -64,6 +64,12 @@ int  pth_pick(pth_tracer* t, int x, int y, int* obj, int* elem, int* tri);
 /* TraceRays (radiance along caller-supplied rays, include/ptk.h ptk_trace_rays with the tracer's seed and trace depth): 1 on success */
 int  pth_trace_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, uint32_t first_sample, uint32_t spp,
                     uint32_t key_base, uint32_t flags, float* out);
+/* IntersectRays / OccludedRays (closest hits and occlusion along caller-supplied rays, include/ptk.h ptk_intersect_rays /
+ * ptk_occluded_rays with the tracer's seed): 1 on success; tri, t, bary, material may be NULL but not all four, tmax may be NULL */
+int  pth_intersect_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, uint32_t sample, uint32_t key_base,
+                        int32_t* tri, float* thit, float* bary, int32_t* material);
+int  pth_occluded_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, const float* tmax, uint32_t sample,
+                       uint32_t key_base, uint8_t* occluded);
 /* BakeLightmap / BakeCoverage / DilateLightmap (lightmap baking, include/ptk.h ptk_bake_lightmap with the tracer's seed and trace
  * depth): 1 on success */
 int  pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,

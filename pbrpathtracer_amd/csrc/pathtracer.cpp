@@ -882,6 +882,30 @@ bool PathTracer::TraceRays(int num_rays, const float* origins, const float* dirs
     return rc == PTK_OK;
 }
 
+// Closest hits and occlusion along caller-supplied rays (ptk_intersect_rays, ptk_occluded_rays) in the scene as the next
+// RenderFrame() would see it
+bool PathTracer::IntersectRays(int num_rays, const float* origins, const float* dirs, uint32_t sample, uint32_t key_base, int32_t* tri, float* t,
+                               float* bary, int32_t* material)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_intersect_rays(m->ctx, num_rays, origins, dirs, sample, m->seed, key_base, tri, t, bary, material);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::OccludedRays(int num_rays, const float* origins, const float* dirs, const float* tmax, uint32_t sample, uint32_t key_base,
+                              uint8_t* occluded)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_occluded_rays(m->ctx, num_rays, origins, dirs, tmax, sample, m->seed, key_base, occluded);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 // Lightmap baking (ptk_bake_lightmap, ptk_bake_coverage, ptk_lightmap_dilate) of the scene as the next RenderFrame() would see it
 bool PathTracer::BakeLightmap(int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp, uint32_t key_base,
                               uint32_t flags, float* out, int32_t* owner)

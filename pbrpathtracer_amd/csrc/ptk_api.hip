@@ -30,6 +30,7 @@
 #include "ptk_bake.h"
 #include "ptk_probes.h"
 #include "ptk_rays_adaptive.h"
+#include "ptk_hits.h"
 #include "ptk_refit.h"
 
 using namespace ptk;
@@ -191,6 +192,11 @@ struct ptk_ctx {
     std::vector<hipEvent_t> ev_probe_blocks;
     int probe_blocks_timed = 0;
     bool probes_timed = false;
+
+    // closest-hit and occlusion queries (ptk_intersect_rays, ptk_occluded_rays): two events around the last call's kernel, made
+    // by the first call
+    hipEvent_t ev_hits[2] = { nullptr, nullptr };
+    bool hits_timed = false;
 
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
@@ -824,6 +830,7 @@ void ptk_destroy(ptk_ctx* c)
     for (hipEvent_t e : c->ev_probes) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_probe_blocks) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_rays) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_hits) if (e) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
     if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);
@@ -1883,6 +1890,150 @@ int ptk_last_rays_ms(ptk_ctx* c, float* trace_ms, float* fold_ms)
     }
     if (trace_ms) *trace_ms = t;
     if (fold_ms) *fold_ms = f;
+    return PTK_OK;
+}
+
+// ---- closest-hit and occlusion queries for caller-supplied rays (ptk.h) --------------------------------------------------------
+// The argument checks the entries share; PTK_OK with *nothing = true: the call is legal and has nothing to do.
+static int check_hits_args(ptk_ctx* c, const char* who, int32_t num_rays, const float* origins, const float* dirs, bool have_out, bool* nothing)
+{
+    *nothing = false;
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (num_rays < 0) return fail(c, PTK_ERR_BAD_ARG, (std::string(who) + ": negative ray count").c_str());
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (!have_out) return fail(c, PTK_ERR_BAD_ARG, (std::string(who) + ": no output array").c_str());
+    if (num_rays > 0 && (!origins || !dirs)) return fail(c, PTK_ERR_BAD_ARG, (std::string(who) + ": null array").c_str());
+    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
+    *nothing = num_rays == 0;
+    return PTK_OK;
+}
+
+// The call proper, on the context's stream, every pointer into this GPU's memory: h holds the rays and the outputs, the scene
+// half is filled in here.  One kernel between the two events; a scene without triangles has no tree to walk and gets its misses
+// from fills.
+static int hits_on_stream(ptk_ctx* c, HitsParams& h, uint32_t sample, uint64_t seed, uint32_t key_base, bool occlusion)
+{
+    c->hits_timed = false;
+    const size_t n = (size_t)h.num_rays;
+    if (c->num_nodes == 0)
+    {
+        if (occlusion) HIPCHK(c, hipMemsetAsync(h.occluded, 0, n, c->stream));
+        if (h.tri) HIPCHK(c, hipMemsetAsync(h.tri, 0xff, n * sizeof(int32_t), c->stream));
+        if (h.t) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)h.t, 0x7f800000, n, c->stream));
+        if (h.bary) HIPCHK(c, hipMemsetAsync(h.bary, 0, n * 2 * sizeof(float), c->stream));
+        if (h.material) HIPCHK(c, hipMemsetAsync(h.material, 0xff, n * sizeof(int32_t), c->stream));
+        return PTK_OK;
+    }
+    h.nodes = c->d_nodes; h.tris = c->d_tris; h.shade = c->d_shade; h.texinfo = c->d_texinfo; h.texels = c->d_texels;
+    h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound; h.tri_thr = c->opt_tri_thr;
+    h.seed_lo = (uint32_t)seed; h.seed_hi = (uint32_t)(seed >> 32); h.sample = sample; h.key_base = key_base;
+    for (hipEvent_t& e : c->ev_hits)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    HIPCHK(c, hipEventRecord(c->ev_hits[0], c->stream));
+    if (occlusion) launch_occluded(h, c->stream); else launch_hits(h, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_hits[1], c->stream));
+    c->hits_timed = true;
+    return PTK_OK;
+}
+
+int ptk_intersect_rays_device(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, uint32_t sample, uint64_t seed,
+                              uint32_t key_base, int32_t* d_tri, float* d_t, float* d_bary, int32_t* d_material)
+{
+    bool nothing;
+    const int rc = check_hits_args(c, "ptk_intersect_rays", num_rays, d_origins, d_dirs, d_tri || d_t || d_bary || d_material, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HitsParams h = {};
+    h.origins = d_origins; h.dirs = d_dirs; h.num_rays = num_rays;
+    h.tri = d_tri; h.t = d_t; h.bary = d_bary; h.material = d_material;
+    return hits_on_stream(c, h, sample, seed, key_base, false);
+}
+
+int ptk_occluded_rays_device(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, const float* d_tmax, uint32_t sample,
+                             uint64_t seed, uint32_t key_base, uint8_t* d_occluded)
+{
+    bool nothing;
+    const int rc = check_hits_args(c, "ptk_occluded_rays", num_rays, d_origins, d_dirs, num_rays == 0 || d_occluded, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HitsParams h = {};
+    h.origins = d_origins; h.dirs = d_dirs; h.tmax = d_tmax; h.num_rays = num_rays; h.occluded = d_occluded;
+    return hits_on_stream(c, h, sample, seed, key_base, true);
+}
+
+// The host entries: origins | dirs | tmax | the requested outputs in one staging buffer (every part a multiple of 4 B but the
+// occlusion bytes, which come last)
+static int hits_staged(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, const float* tmax, uint32_t sample, uint64_t seed,
+                       uint32_t key_base, int32_t* tri, float* t, float* bary, int32_t* material, uint8_t* occluded)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)num_rays, w = sizeof(float);
+    const size_t words = 6 * n + (tmax ? n : 0) + (tri ? n : 0) + (t ? n : 0) + (bary ? 2 * n : 0) + (material ? n : 0);
+    float* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, words * w + (occluded ? n : 0)));
+    float* q = d;
+    auto take = [&](size_t k) { float* r = q; q += k; return r; };
+    HitsParams h = {};
+    float* const d_o = take(3 * n), * const d_d = take(3 * n);
+    h.origins = d_o; h.dirs = d_d; h.num_rays = num_rays;
+    float* const d_tmax = tmax ? take(n) : nullptr;
+    h.tmax = d_tmax;
+    if (tri) h.tri = (int32_t*)take(n);
+    if (t) h.t = take(n);
+    if (bary) h.bary = take(2 * n);
+    if (material) h.material = (int32_t*)take(n);
+    if (occluded) h.occluded = (uint8_t*)q;
+    int rc = PTK_OK;
+    hipError_t e = hipMemcpyAsync(d_o, origins, 3 * n * w, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_d, dirs, 3 * n * w, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && tmax) e = hipMemcpyAsync(d_tmax, tmax, n * w, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+    {
+        rc = hits_on_stream(c, h, sample, seed, key_base, occluded != nullptr);
+        if (rc == PTK_OK && tri) e = hipMemcpyAsync(tri, h.tri, n * w, hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess && t) e = hipMemcpyAsync(t, h.t, n * w, hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess && bary) e = hipMemcpyAsync(bary, h.bary, 2 * n * w, hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess && material) e = hipMemcpyAsync(material, h.material, n * w, hipMemcpyDeviceToHost, c->stream);
+        if (rc == PTK_OK && e == hipSuccess && occluded) e = hipMemcpyAsync(occluded, h.occluded, n, hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also on the way out of a failure: the staging buffer may be in use)
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    if (rc != PTK_OK) return rc;
+    if (e != hipSuccess) return fail(c, PTK_ERR_HIP, hipGetErrorString(e));
+    return PTK_OK;
+}
+
+int ptk_intersect_rays(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, uint32_t sample, uint64_t seed, uint32_t key_base,
+                       int32_t* tri, float* t, float* bary, int32_t* material)
+{
+    bool nothing;
+    const int rc = check_hits_args(c, "ptk_intersect_rays", num_rays, origins, dirs, tri || t || bary || material, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    return hits_staged(c, num_rays, origins, dirs, nullptr, sample, seed, key_base, tri, t, bary, material, nullptr);
+}
+
+int ptk_occluded_rays(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, const float* tmax, uint32_t sample, uint64_t seed,
+                      uint32_t key_base, uint8_t* occluded)
+{
+    bool nothing;
+    const int rc = check_hits_args(c, "ptk_occluded_rays", num_rays, origins, dirs, num_rays == 0 || occluded, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    return hits_staged(c, num_rays, origins, dirs, tmax, sample, seed, key_base, nullptr, nullptr, nullptr, nullptr, occluded);
+}
+
+int ptk_last_hits_ms(ptk_ctx* c, float* ms)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    float t = 0.0f;
+    if (c->hits_timed)
+    {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipEventSynchronize(c->ev_hits[1]));
+        HIPCHK(c, hipEventElapsedTime(&t, c->ev_hits[0], c->ev_hits[1]));
+    }
+    if (ms) *ms = t;
     return PTK_OK;
 }
 

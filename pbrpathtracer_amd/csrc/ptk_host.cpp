@@ -118,6 +118,16 @@ int pth_trace_rays(pth_tracer* t, int num_rays, const float* origins, const floa
 {
     return t->pt.TraceRays(num_rays, origins, dirs, first_sample, spp, key_base, flags, out) ? 1 : 0;
 }
+int pth_intersect_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, uint32_t sample, uint32_t key_base, int32_t* tri,
+                       float* thit, float* bary, int32_t* material)
+{
+    return t->pt.IntersectRays(num_rays, origins, dirs, sample, key_base, tri, thit, bary, material) ? 1 : 0;
+}
+int pth_occluded_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, const float* tmax, uint32_t sample, uint32_t key_base,
+                      uint8_t* occluded)
+{
+    return t->pt.OccludedRays(num_rays, origins, dirs, tmax, sample, key_base, occluded) ? 1 : 0;
+}
 int pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,
                       uint32_t key_base, uint32_t flags, float* out, int32_t* owner)
 {

@@ -37,7 +37,7 @@ HOST_SYMBOLS = [
     "pth_export_png", "pth_render_adaptive", "pth_read_sample_counts",
     "pth_render_features", "pth_read_feature", "pth_pick", "pth_set_object_transform", "pth_trace_rays", "pth_get_camera",
     "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
-    "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive",
+    "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays",
 ]
 
 _bound = False
@@ -105,6 +105,8 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_trace_rays_adaptive.argtypes = [vp, i32, vp, vp, f32, u32, u32, u32, u32, u32, vp, vp, vp, res]
         L.pth_bake_lightmap_adaptive.restype = i32
         L.pth_bake_lightmap_adaptive.argtypes = [vp, i32, i32, vp, f32, f32, u32, u32, u32, u32, u32, vp, vp, vp, res]
+        L.pth_intersect_rays.restype = i32; L.pth_intersect_rays.argtypes = [vp, i32, vp, vp, u32, u32, vp, vp, vp, vp]
+        L.pth_occluded_rays.restype = i32; L.pth_occluded_rays.argtypes = [vp, i32, vp, vp, vp, u32, u32, vp]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -319,6 +321,35 @@ class PathTracer:
         ptr = (lambda a: a.ctypes.data if len(o) else None)
         if not self.L.pth_trace_rays(self.h, len(o), ptr(o), ptr(d), int(first_sample), int(spp), int(key_base) & 0xffffffff, flags, ptr(out)):
             raise _ptk.PtkError("TraceRays failed: " + self.LastError())
+        return out
+
+    def IntersectRays(self, origins, dirs, sample: int = 0, key_base: int = 0):
+        """Extension: closest hits along caller-supplied rays (include/ptk.h ptk_intersect_rays) at this tracer's seed; [n, 3]
+        float32 numpy arrays in, (tri [n] int32, t [n] float32, bary [n, 2] float32, material [n] int32) out, -1 / inf / 0 / -1 on
+        a miss.  Valid after BuildBVH(); pending material / geometry edits apply as for RenderFrame()."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n, "as many directions as origins"
+        out = (np.empty(n, np.int32), np.empty(n, np.float32), np.empty((n, 2), np.float32), np.empty(n, np.int32))
+        if n and not self.L.pth_intersect_rays(self.h, n, o.ctypes.data, d.ctypes.data, int(sample), int(key_base) & 0xffffffff,
+                                         *(a.ctypes.data for a in out)):
+            raise _ptk.PtkError("IntersectRays failed: " + self.LastError())
+        return out
+
+    def OccludedRays(self, origins, dirs, tmax=None, sample: int = 0, key_base: int = 0) -> np.ndarray:
+        """Extension: occlusion along caller-supplied rays (include/ptk.h ptk_occluded_rays) at this tracer's seed: [n] uint8, 1
+        where an accepted triangle lies at t < tmax[i] (None: no bound)."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n, "as many directions as origins"
+        tm = None if tmax is None else np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+        assert tm is None or len(tm) == n, "one tmax per ray"
+        out = np.empty(n, np.uint8)
+        if n and not self.L.pth_occluded_rays(self.h, n, o.ctypes.data, d.ctypes.data, tm.ctypes.data if tm is not None else None, int(sample),
+                                        int(key_base) & 0xffffffff, out.ctypes.data):
+            raise _ptk.PtkError("OccludedRays failed: " + self.LastError())
         return out
 
     def _chart_uvs(self, uvs):

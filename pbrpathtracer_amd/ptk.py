@@ -91,6 +91,7 @@ SYMBOLS = [
     "ptk_feature_info", "ptk_render_features", "ptk_read_feature", "ptk_feature_device_ptr", "ptk_pick",
     "ptk_update_geometry", "ptk_update_geometry_device", "ptk_geometry_info", "ptk_geometry_timing",
     "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
+    "ptk_intersect_rays", "ptk_intersect_rays_device", "ptk_occluded_rays", "ptk_occluded_rays_device", "ptk_last_hits_ms",
     "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
     "ptk_last_bake_ms",
     "ptk_trace_rays_adaptive", "ptk_trace_rays_adaptive_device", "ptk_bake_lightmap_adaptive", "ptk_bake_lightmap_adaptive_device",
@@ -190,6 +191,11 @@ def _load_locked() -> C.CDLL:
         for fn in (L.ptk_bake_lightmap_adaptive, L.ptk_bake_lightmap_adaptive_device):
             fn.argtypes = [vp, i32, i32, vp, f32, i32, f32, u32, u32, u32, u64, u32, u32, vp, vp, vp, C.POINTER(RaysAdaptiveResult)]
         L.ptk_last_rays_adaptive_ms.argtypes = [vp, fp, fp, fp]
+        for fn in (L.ptk_intersect_rays, L.ptk_intersect_rays_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, u32, u64, u32, vp, vp, vp, vp]
+        for fn in (L.ptk_occluded_rays, L.ptk_occluded_rays_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, vp, u32, u64, u32, vp]
+        L.ptk_last_hits_ms.argtypes = [vp, fp]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -448,6 +454,78 @@ class Context:
         t = C.c_float(0); f = C.c_float(0)
         self._chk(self.L.ptk_last_rays_ms(self.h, C.byref(t), C.byref(f)), "ptk_last_rays_ms")
         return t.value, f.value
+
+    # ---- closest-hit and occlusion queries --------------------------------------------------
+    def _ray_tensors(self, tensors, n, widths):
+        import torch
+        dev = self.device_ordinal()
+        for t, (dtype, k) in zip(tensors, widths):
+            assert t.is_cuda and t.device.index == dev, f"tensor on {t.device}, context on device {dev}"
+            assert t.dtype == dtype and t.is_contiguous() and t.numel() == n * k, f"contiguous {dtype} tensors of n x {k}"
+
+    def intersect_rays(self, origins, dirs, sample: int = 0, seed: int = 0, key_base: int = 0):
+        """ptk_intersect_rays: the closest accepted hit of the rays (origins[i], dirs[i]) - [n, 3] float32, directions used as
+        given - with the stochastic-opacity draws of sample `sample` of (seed, RNG pixel key_base + i).  Returns (tri [n] int32, -1
+        on a miss; t [n] float32 in units of |dir|, inf on a miss; bary [n, 2] float32 = u, v; material [n] int32, -1 on a miss).
+        numpy arrays go through the host entry (synchronous) and give numpy arrays; torch tensors on the context's GPU go through
+        ptk_intersect_rays_device with no host copy and give torch tensors written on the context's stream (see trace_rays)."""
+        args = (int(sample), int(seed), int(key_base) & 0xffffffff)
+        if hasattr(origins, "data_ptr"):
+            import torch
+            n = origins.numel() // 3
+            mk = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=origins.device)
+            out = (mk((n,), torch.int32), mk((n,), torch.float32), mk((n, 2), torch.float32), mk((n,), torch.int32))
+            self._ray_tensors((origins, dirs), n, ((torch.float32, 3),) * 2)
+            if n:
+                self._chk(self.L.ptk_intersect_rays_device(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(dirs.data_ptr()), *args,
+                                                           *(C.c_void_p(t.data_ptr()) for t in out)), "ptk_intersect_rays_device")
+            return out
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n, "as many directions as origins"
+        out = (np.empty(n, np.int32), np.empty(n, np.float32), np.empty((n, 2), np.float32), np.empty(n, np.int32))
+        if n:
+            self._chk(self.L.ptk_intersect_rays(self.h, n, o.ctypes.data, d.ctypes.data, *args, *(a.ctypes.data for a in out)),
+                      "ptk_intersect_rays")
+        return out
+
+    def occluded_rays(self, origins, dirs, tmax=None, sample: int = 0, seed: int = 0, key_base: int = 0):
+        """ptk_occluded_rays: [n] uint8, 1 where some accepted triangle lies at t < tmax[i] (strictly; t in units of |dir|) along
+        ray i, under the candidate rule of intersect_rays.  tmax: [n] float32 of the rays' kind, or None for no bound.  numpy in,
+        numpy out through the host entry; torch in, torch out through ptk_occluded_rays_device with no host copy."""
+        args = (int(sample), int(seed), int(key_base) & 0xffffffff)
+        if hasattr(origins, "data_ptr"):
+            import torch
+            n = origins.numel() // 3
+            out = torch.empty((n,), dtype=torch.uint8, device=origins.device)
+            self._ray_tensors((origins, dirs), n, ((torch.float32, 3),) * 2)
+            if tmax is not None:
+                self._ray_tensors((tmax,), n, ((torch.float32, 1),))
+            if n:
+                self._chk(self.L.ptk_occluded_rays_device(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(dirs.data_ptr()),
+                                                          C.c_void_p(tmax.data_ptr()) if tmax is not None else None, *args,
+                                                          C.c_void_p(out.data_ptr())), "ptk_occluded_rays_device")
+            return out
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n, "as many directions as origins"
+        tm = None
+        if tmax is not None:
+            tm = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+            assert len(tm) == n, "one tmax per ray"
+        out = np.empty(n, np.uint8)
+        if n:
+            self._chk(self.L.ptk_occluded_rays(self.h, n, o.ctypes.data, d.ctypes.data, tm.ctypes.data if tm is not None else None, *args,
+                                               out.ctypes.data), "ptk_occluded_rays")
+        return out
+
+    def last_hits_ms(self) -> float:
+        """HIP-event time of the last intersect_rays / occluded_rays call's kernel; waits for it."""
+        t = C.c_float(0)
+        self._chk(self.L.ptk_last_hits_ms(self.h, C.byref(t)), "ptk_last_hits_ms")
+        return t.value
 
     # ---- lightmap baking -------------------------------------------------------------------
     def _bake_uvs(self, uvs, torch_side: bool):

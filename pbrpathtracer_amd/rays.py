@@ -1,5 +1,7 @@
 """Ray sets for Context.trace_rays / PathTracer.TraceRays (include/ptk.h ptk_trace_rays): camera models the library's own
-perspective camera does not cover, as plain (origins, directions) arrays.  Host only, no GPU."""
+perspective camera does not cover, as plain (origins, directions) arrays - and for Context.intersect_rays / occluded_rays
+(ptk_intersect_rays, ptk_occluded_rays): segments between point pairs and ambient occlusion.  Host only but for
+ambient_occlusion, which runs its rays through the context it is given."""
 from __future__ import annotations
 
 import numpy as np
@@ -28,3 +30,45 @@ def equirect_rays(pos, dir, up, width: int, height: int):
     dirs = np.ascontiguousarray(d.reshape(-1, 3), np.float32)
     origins = np.ascontiguousarray(np.broadcast_to(np.asarray(pos, np.float64), dirs.shape), np.float32)
     return origins, dirs
+
+
+def segment_rays(a, b):
+    """(origins, dirs, tmax) for the segments from a[i] to b[i], [n, 3] each: origins = a, dirs = b - a in float32 (not
+    normalised) and tmax = 1, so that Context.occluded_rays(origins, dirs, tmax) asks "is anything strictly between the two points"
+    and the visibility between the pairs is 1 - occluded."""
+    a = np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(b, np.float32).reshape(-1, 3)
+    assert len(a) == len(b), "as many end points as start points"
+    return a, np.ascontiguousarray(b - a), np.ones(len(a), np.float32)
+
+
+def ambient_occlusion_rays(points, normals, dirs, offset):
+    """The rays of ambient_occlusion: for point p with normal n the rays (p + n * offset, d_j) over the directions d_j with float32
+    c_j = (n.x * d.x + n.y * d.y) + n.z * d.z > 0, point-major then in direction order - that order is a ray's global index.
+    Returns (origins [m, 3], ray_dirs [m, 3], point [m] int64 - the point each ray belongs to -, cos [m] float32 - its c_j)."""
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    assert len(n) == len(p), "one normal per point"
+    c = (n[:, None, 0] * d[None, :, 0] + n[:, None, 1] * d[None, :, 1]) + n[:, None, 2] * d[None, :, 2]      # [points, dirs], float32
+    pi, di = np.nonzero(c > 0)                                                                                # row-major: point-major
+    origins = np.ascontiguousarray(p[pi] + n[pi] * np.float32(offset))
+    return origins, np.ascontiguousarray(d[di]), pi, np.ascontiguousarray(c[pi, di])
+
+
+def ambient_occlusion_fold(num_points: int, point, cos, occluded):
+    """float32 [num_points] of sum c_j (1 - occluded_j) / sum c_j over each point's rays, summed in float64; 1 where a point has
+    no ray."""
+    w = np.asarray(cos, np.float64)
+    open_ = np.bincount(point, weights=w * (1.0 - np.asarray(occluded, np.float64)), minlength=num_points)
+    total = np.bincount(point, weights=w, minlength=num_points)
+    return np.where(total > 0, open_ / np.where(total > 0, total, 1.0), 1.0).astype(np.float32)
+
+
+def ambient_occlusion(ctx, points, normals, dirs, radius, offset, sample: int = 0, seed: int = 0):
+    """Cosine-weighted openness of the surface points (points[i], normals[i]) over the direction set dirs (probes.fibonacci_dirs for
+    instance): one Context.occluded_rays call over ambient_occlusion_rays with tmax = radius (in units of |d_j|), folded by
+    ambient_occlusion_fold.  1 = nothing within radius, 0 = closed in.  numpy arrays in, float32 [len(points)] out."""
+    origins, ray_dirs, point, cos = ambient_occlusion_rays(points, normals, dirs, offset)
+    occ = ctx.occluded_rays(origins, ray_dirs, np.full(len(origins), radius, np.float32), sample=sample, seed=seed)
+    return ambient_occlusion_fold(len(np.asarray(points).reshape(-1, 3)), point, cos, occ)

@@ -4,6 +4,7 @@
     python -m pbrpathtracer_amd.render scene.pts --noise-threshold 0.02 [--min-spp 16] [--step 8] --spp 1024
     python -m pbrpathtracer_amd.render scene.pts --features planes.npz
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
+    python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz
     python -m pbrpathtracer_amd.render scene.pts --bake-lightmap 1024 --spp 64 [--bake-atlas] [--bake-offset F] [--bake-back]
                                                  [--dilate K] -o map.png [--npy map.npy]
     python -m pbrpathtracer_amd.render scene.pts --bake-probes NX NY NZ [--probe-dirs D] --spp N -o probes.npz
@@ -15,6 +16,10 @@ FILE.counts.npy beside it the uint32 sample counts.
 
 With --equirect WIDTH the image is a WIDTH x WIDTH/2 latitude-longitude panorama from the scene's camera position, traced through
 PathTracer.TraceRays (include/ptk.h ptk_trace_rays; rays.equirect_rays) instead of the perspective camera.
+
+With --equirect WIDTH --hits FILE.npz nothing is traced and no image written: the .npz holds what the panorama's rays hit
+(PathTracer.IntersectRays, include/ptk.h ptk_intersect_rays, sample 0) - depth, triangle, material [H, W] and bary [H, W, 2], rows
+top-down - a depth panorama; --spp is not needed.
 
 With --bake-lightmap SIZE the image is a SIZE x SIZE lightmap (include/ptk.h ptk_bake_lightmap): per texel of the scene's own uv
 layout - or, with --bake-atlas, of lightmap.grid_atlas, one chart per triangle - the radiance leaving the surface along its normal,
@@ -54,6 +59,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="render a WIDTH x WIDTH/2 latitude-longitude panorama about the scene's camera instead of its perspective view")
     ap.add_argument("--npy", metavar="FILE.npy", default=None,
                     help="--equirect: also write the float32 sums over the samples, [H, W, 3], rows top-down (mean = sum / spp)")
+    ap.add_argument("--hits", metavar="FILE.npz", default=None,
+                    help="--equirect: instead of tracing, write what the panorama's rays hit (depth, triangle, material, bary; rows "
+                         "top-down) to this .npz")
     ap.add_argument("--bake-lightmap", type=int, metavar="SIZE", default=None,
                     help="bake a SIZE x SIZE lightmap over the scene's uvs instead of rendering a view; the PNG holds the mean "
                          "(sum / spp) resolved like a frame, rows top-down; --npy the float32 sums [SIZE, SIZE, 3], rows bottom-up as baked")
@@ -181,6 +189,14 @@ def render_equirect(pt, a) -> int:
         return 1
     origins, dirs = equirect_rays(*pt.GetCamera(), w, h)
     t1 = time.time()
+    if a.hits:
+        tri, t, bary, material = pt.IntersectRays(origins, dirs)
+        t2 = time.time()
+        with open(a.hits, "wb") as f:               # (np.savez would append .npz to another suffix)
+            np.savez(f, depth=t.reshape(h, w), triangle=tri.reshape(h, w), material=material.reshape(h, w), bary=bary.reshape(h, w, 2))
+        print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {w}x{h} panorama, {int((tri >= 0).sum())} of {w * h} rays hit: "
+              f"{t2 - t1:.3f} s -> {a.hits}")
+        return 0
     if a.noise_threshold is not None:
         total, _, counts, res = pt.TraceRaysAdaptive(origins, dirs, *adaptive_args(a))
         mean = mean_of(total.reshape(h, w, 3), counts.reshape(h, w))
