@@ -1,0 +1,298 @@
+// The context of the ptk C-ABI (include/ptk.h) and what the host API files ptk_api*.hip share.  Internal: not installed.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "ptk_features.h"
+
+typedef struct ncclComm* ncclComm_t;             // rccl.h's own declaration, repeated so that only ptk_api_exchange.hip includes that header (which checks it)
+namespace ptk { struct RaysBlock; }
+
+struct ptk_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    std::string error;
+    std::mutex err_mu;
+
+    // scene (device)
+    float4* d_flat_tris = nullptr;      // <= 16 triangles: records in ascending triangle index for the FLAT kernel
+    float4 *d_nodes = nullptr, *d_tris = nullptr, *d_shade = nullptr, *d_mats = nullptr, *d_lights = nullptr;
+    int4* d_texinfo = nullptr;
+    uint32_t* d_texels = nullptr;
+    int num_nodes = 0, num_tris = 0, num_lights = 0, bvh_depth = 0, bvh_stack = 0, num_leaf_tris = 0;
+    float scene_bound = 0.0f;           // 3.1 x (1.01 x the largest |vertex coordinate| + 1e-3): RenderParams::scene_bound
+    float scene_lo[3] = { 0, 0, 0 }, scene_hi[3] = { 0, 0, 0 };     // the vertices' bounding box
+    int opt_lens_cull = 1;              // uncached cameras: pixels whose whole bundle of lens rays misses that box are never traced
+    unsigned long long view_generation = 0;      // bumped whenever camera, frame or scene change what an uncached pixel can see
+    bool have_scene = false;
+    double upload_ms[4] = { 0, 0, 0, 0 };       // last ptk_upload_scene: BVH build, record packing, device copies, total
+    // host copies kept for ptk_update_materials: what was uploaded, the texture index map, the light records
+    std::vector<ptk_material> h_materials;
+    std::vector<int32_t> h_texmap, h_light_material;
+    std::vector<float> h_lights;
+    // FLAT scenes: each triangle's smoothing flag and material, for re-deciding scene_plain when the materials are edited
+    std::vector<uint8_t> h_flat_smoothing;
+    std::vector<int32_t> h_flat_material;
+    // geometry updates (ptk_update_geometry): the world-space vertices stay resident beside the records (a refit needs the exact
+    // v2, v3: fl(v1 + fl(v2 - v1)) is not v2); everything else is made by the first update and lives until the next upload
+    float* d_verts_res = nullptr;                // [num_tris][9]
+    int32_t* d_tri_pos = nullptr;                // triangle -> position of its record in the leaf order
+    int32_t* d_level_nodes = nullptr;            // node indices sorted by level, the root's level first
+    std::vector<int> level_start;                // [levels + 1] offsets into d_level_nodes
+    double* d_refit_partial = nullptr;           // one partial SAH sum per 256 nodes
+    float4* d_refit_side = nullptr;              // per node: union box + summed child half-area (ptk_refit.h)
+    float* d_geo_stage = nullptr; size_t geo_stage_floats = 0;     // staged verts | normals | tbn of the update in progress
+    uint32_t* d_geo_red = nullptr;               // GEO_RED_WORDS of the bounds reduction, then one double: the SAH cost
+    uint32_t* h_geo_red = nullptr;               // page-locked target of its read-back
+    hipStream_t geo_stream = nullptr;            // staging copies and the bounds reduction: the one host wait of an update is for this stream alone
+    // events of the newest update: [0] [1] around staging + bounds on geo_stream; [2] before the repack, [3] behind it, [4] behind
+    // the refit on the context's stream ([4] also orders the next update's staging behind this one's kernels)
+    hipEvent_t ev_geo_t[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    bool geo_done_recorded = false, lights_stale = false;          // lights_stale: h_lights lacks the vertices an update moved
+    uint32_t geo_updates = 0;
+    double sah_built = 0.0, sah_now = 0.0; bool sah_now_pending = false;
+    float bvh_pad = 0.0f;                        // the builders' box padding for the current scene extent
+    bool scene_plain = false;           // plain_tables() of the staged scene: kept current by ptk_upload_scene and ptk_update_materials
+    int opt_plain_kernel = 1;           // 0: plain scenes launch the generic FLAT kernel too (tests, A/B runs)
+    int last_trace_variant = PTK_TRACE_NONE;     // of the newest trace launch (ptk_trace_variant)
+
+    // camera (host copies, already normalised / clamped like the reference setters)
+    float cam_pos[3] = { 0, 0, 0 }, cam_dir[3] = { 0, 0, 1 }, cam_up[3] = { 0, 1, 0 };
+    float focal = 0.1f, fovy = 90.0f, focal_dist = 5.0f, aperture = 0.0f;   // pathtracer.cpp:17-22
+    float cam_right[3] = { 1, 0, 0 };
+    bool primary_dirty = true;
+
+    // frame
+    int width = 0, height = 0, max_depth = 3;                                 // pathtracer.cpp:15
+    float4* d_primary = nullptr;
+    float4* d_primary_hit = nullptr;  // primary-visibility cache (pinhole, no opacity textures)
+    float4* d_primary_rd = nullptr;   // ... and the camera ray's direction per pixel
+    uint2* d_pixel_rng = nullptr;     // per pixel: (pixel key, PCG increment) for pixel_rng_seed
+    uint64_t pixel_rng_seed = 0; bool pixel_rng_valid = false;
+    bool primary_hit_dirty = true, scene_has_opacity = false;
+    int opt_primary_cache = 1;
+    int opt_flat_shade_w = 8, opt_flat_gen_w = 64;
+    int opt_flat = 1;                    // scenes of <= PTK_FLAT_MAX triangles: no BVH walk (trace_kernel<.., FLAT>)
+    float* d_accum = nullptr;        // owned accumulator
+    float* d_accum_bound = nullptr;  // caller-owned accumulator (ptk_bind_accum) or null
+    uint8_t* d_rgb8 = nullptr;
+    // hand-off buffer bound by ptk_bind_out_image: the caller's pointer, its device-visible alias, whether this context
+    // page-locked it, and whether the next accumulate kernel must write every pixel (after binding, reset, a camera or
+    // scene change: the set of always-black pixels may have changed)
+    uint8_t* out_host = nullptr; uint8_t* out_host_dev = nullptr;
+    bool out_registered = false;
+    std::atomic<bool> out_full_next{ true };
+    // ... or a DEVICE buffer bound by ptk_bind_out_device, or an OpenGL buffer object registered by ptk_bind_gl_buffer (mapped
+    // for the length of each render: run_passes)
+    uint8_t* out_device = nullptr;
+    hipGraphicsResource_t gl_res = nullptr;
+    unsigned gl_buffer = 0;
+    int rank = 0, world = 1;
+
+    std::atomic<int> samples{ 0 };
+    std::atomic<uint32_t> render_gen{ 1 };       // generation of the newest render: Exit() names it and thereby every render still in flight (kernels stand down
+                                                 // when the named generation >= their own); renders issued afterwards are not affected
+    uint32_t* d_exit = nullptr;
+    uint32_t* h_exit = nullptr;                  // page-locked source of the copy that writes d_exit (ptk_request_exit)
+    hipStream_t exit_stream = nullptr;           // high priority, nothing else on it: the copy of the Exit() word never waits behind a render
+    std::mutex exit_mu;                          // (Exit() may come from several threads: the source word never goes back)
+    unsigned long long* d_stats = nullptr;
+    unsigned* d_queues = nullptr;                // item queues of trace_kernel's persistent waves
+    // live-quadrant list (which 8x8 quadrants of the owned tiles have pixels to trace) and what it was built for
+    unsigned long long* d_live_mask = nullptr;
+    unsigned* d_live_list = nullptr;             // [capacity] entries + 1 word: the count
+    int live_capacity = 0;
+    unsigned long long hit_generation = 0;       // bumped whenever the primary-hit cache is recomputed
+    struct LiveKey { int width, height, rank, world, cached; unsigned long long generation; } live_key = { 0, 0, -1, 0, -1, 0 };
+    int resident_waves = 4096;                   // one-wave workgroups the device holds at once (CUs x 16)
+
+    // adaptive render (ptk_render_adaptive): allocated by the first one, freed by ptk_set_frame with another resolution
+    uint32_t* d_counts = nullptr;                // [H][W] samples per pixel, rows bottom-up
+    float* d_moments = nullptr;                  // [H][W][3] sums of squared samples (S2)
+    unsigned long long* d_adapt_active = nullptr, * d_adapt_traced = nullptr;     // per quadrant of the frame: active set, active & live
+    unsigned* d_adapt_list = nullptr;            // [adapt_capacity] entries + 1 word: the count (the traced mask's quadrants)
+    unsigned long long* d_adapt_stats = nullptr; // [0] pixel samples, [1] largest count, [2] low word: active pixels after the last test
+    int adapt_capacity = 0;                      // quadrants the buffers hold (every quadrant of the frame: any tile split fits)
+    unsigned* h_adapt_count = nullptr;           // page-locked [2]: the active count of rounds r and r + 1, read one round behind
+    hipEvent_t ev_adapt[2] = { nullptr, nullptr };
+    bool adaptive_accum = false;                 // the accumulator holds an adaptive render: per-pixel counts, no single sample count
+
+    // first-hit feature planes (ptk_render_features): allocated on first use, each for the frame feat_w x feat_h
+    void* d_feat[ptk::NUM_FEATURES] = {};
+    int feat_w = 0, feat_h = 0;                  // the frame the planes were allocated for and last rendered at
+    uint32_t feat_mask = 0;                      // planes the last ptk_render_features wrote
+
+    // radiance along caller-supplied rays (ptk_trace_rays): its own sample buffer between rays_kernel and rays_fold_kernel - renders
+    // may still be in flight on the internal streams with theirs -, grown to the largest pass so far; the item counter and
+    // parameter block of a launch; three events per pass of the last call: before rays_kernel, behind it, behind the fold
+    float4* d_rays_samples = nullptr; size_t rays_samples_bytes = 0;
+    ptk::RaysBlock* d_rays_block = nullptr;
+    std::vector<hipEvent_t> ev_rays;
+    int rays_passes = 0;                         // timed passes of the last call (at most kMaxTimedPasses)
+
+    // lightmap baking (ptk_bake_lightmap), each grown to the largest bake so far: the owner plane (4 B per texel) with the covered
+    // count per block of 256 texels behind it; the compacted rays of the covered texels (origins | dirs | sums | keys | texel
+    // index, 44 B each); the second image + owner plane of ptk_lightmap_dilate (16 B per texel); the covered count's page-locked
+    // read-back word; six events of the last bake: start, behind coverage + count, before and behind the ray generator, behind the
+    // trace, behind the scatter
+    int* d_bake_plane = nullptr; size_t bake_plane_texels = 0;
+    float* d_bake_compact = nullptr; size_t bake_compact_rays = 0;
+    float* d_bake_dilate = nullptr; size_t bake_dilate_texels = 0;
+    uint32_t* h_bake_total = nullptr;
+    hipEvent_t ev_bake[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    bool bake_timed = false, bake_traced = false;
+
+    // adaptive ray queries and lightmap bakes (ptk_trace_rays_adaptive, ptk_bake_lightmap_adaptive), each grown to the largest call
+    // so far: per ray 56 B - the round's compacted origins | dirs (24 B), keys, source indices, the next active list and the keep
+    // flags (4 B each), S2 and the counts where the caller's arrays do not hold them (12 + 4 B) - with a count per 256 rays and the
+    // total behind them; a lightmap's need plane (1 B per texel); the total's page-locked read-back word; two events around the
+    // GPU work of a round; the last call's times (ptk_last_rays_adaptive_ms)
+    float* d_radapt = nullptr; size_t radapt_rays = 0;
+    uint8_t* d_radapt_need = nullptr; size_t radapt_need_texels = 0;
+    uint32_t* h_radapt_total = nullptr;
+    hipEvent_t ev_radapt[2] = { nullptr, nullptr };
+    float radapt_ms[3] = { 0.0f, 0.0f, 0.0f };   // host wall time of the round loop; rays_keyed_kernel; the other kernels of the rounds
+
+    // irradiance probe baking (ptk_bake_probes), each grown to the largest call so far: the basis table (36 B per direction), one
+    // block of rays (origins | dirs, 24 B each) and, while the caller passes no table, the radiance table (12 B per ray); four
+    // events of the last bake - around the basis table, around the projection - and three per block of probes (the first
+    // kMaxTimedPasses of them): before the ray generator, behind it, behind the trace
+    float* d_probe_basis = nullptr; size_t probe_basis_dirs = 0;
+    float* d_probe_rays = nullptr; size_t probe_rays_cap = 0;
+    float* d_probe_table = nullptr; size_t probe_table_rays = 0;
+    hipEvent_t ev_probes[4] = { nullptr, nullptr, nullptr, nullptr };
+    std::vector<hipEvent_t> ev_probe_blocks;
+    int probe_blocks_timed = 0;
+    bool probes_timed = false;
+
+    // closest-hit and occlusion queries (ptk_intersect_rays, ptk_occluded_rays): two events around the last call's kernel, made
+    // by the first call
+    hipEvent_t ev_hits[2] = { nullptr, nullptr };
+    bool hits_timed = false;
+
+    // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
+    // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
+    // overlaps the tail of pass k's (a launch ends with the few waves that hold its longest paths - Russian roulette
+    // lets one path in tens of millions live for 60+ bounces, ~0.4 ms with the rest of the chip idle) and pass k's
+    // accumulate kernel.  The accumulate kernels stay on the context's stream, in order, each behind its trace kernel,
+    // so everything the caller orders after ptk_render on that stream still sees the finished batch.
+    float4* d_samples = nullptr;                 // (non-overlapped path)
+    size_t samples_bytes = 0;
+    float4* d_samples2[2] = { nullptr, nullptr };
+    size_t samples_bytes2[2] = { 0, 0 };
+    unsigned* d_queues2[2] = { nullptr, nullptr };
+    hipStream_t trace_stream[2] = { nullptr, nullptr };
+    hipEvent_t ev_trace_done[2] = { nullptr, nullptr }, ev_acc_done[2] = { nullptr, nullptr }, ev_inputs = nullptr;
+    bool acc_pending[2] = { false, false }, inputs_recorded = false;
+    bool inputs_dirty = true;                    // scene / camera tables were (re)written on the context's stream since ev_inputs
+    unsigned pass_counter = 0;
+    int opt_overlap = 1;
+    int opt_register_out = 0;                    // 1: ptk_bind_out_image page-locks a pageable caller buffer in place (round 3's default; the caller must unbind before freeing)
+    int opt_contract = 0;                        // 0: bit-exact kernels; 1: -ffp-contract=fast build; 2: ... with 1-ulp hardware rcp / sqrt
+    int opt_chunk = 0;                           // samples per work item; 0 = automatic (8, or 4 for small shares)
+    int num_cus = 256;
+    int opt_generations = 0;                     // 0 automatic: 1 on a single GPU, 2 when the frame is split over ranks
+    int opt_persistent = -1;                     // -1 automatic (by launch size), 0 one item per wave, 1 persistent waves
+    int opt_max_batch = 1;                       // slots a persistent wave pops from its queue at once; > 1 measured slower everywhere
+    int opt_device_build = 1;                    // scenes of >= 4096 triangles: BVH built and records packed on the GPU (bvh_device.hip)
+    bool built_on_device = false;
+    int opt_tri_thr = 6;                         // triangle arm of the walk runs when queued lanes >= tri_thr/8 x walking lanes
+    int opt_shade_thr = 0, opt_gen_thr = 16;     // scheduling lambdas in eighths, see trace_kernel; 0 = by tree depth
+    size_t opt_pass_bytes = (size_t)16 << 30;    // sample-buffer budget per pass (two such buffers at most, of the 288 GB: C4 traces its 256 spp in one launch, C5 its 1024 in two: +0.4 / +1.2 % over 4 GiB)
+
+    // multi-GPU exchange step (ptk_gather_accum): packed gather of every rank's owned tiles to the root
+    ncclComm_t comm = nullptr;                   // the context's own communicator (ptk_comm_init), or null
+    int comm_rank = 0, comm_world = 1;
+    hipStream_t xstream = nullptr;               // high priority: its kernels and the collective take wave slots ahead of queued trace waves
+    hipEvent_t ev_rendered = nullptr, ev_packed = nullptr, ev_gathered = nullptr;
+    float* d_packed = nullptr; size_t packed_floats = 0;      // non-root: this rank's packed tiles; root: every rank's, back to back
+    float* d_gathered = nullptr; size_t gathered_floats = 0;  // root: the combined image (W*H*3, rows bottom-up)
+    int gathered_w = 0, gathered_h = 0;          // the frame the last ptk_gather_accum combined (ptk_read_gathered refuses any other)
+    bool gather_pending = false;
+    // every wait of the exchange step is bounded (ptk_set_option "comm_timeout_s"): a rank that never arrives must end the run with
+    // an error that names it, not hang the node (the first real 8-GPU run is the driver's, not ours)
+    double opt_comm_timeout_s = 120.0;
+    unsigned long long gather_step = 0;          // exchanges queued so far (named in the timeout message)
+    size_t gather_bytes = 0;                     // bytes the last exchange moves on this rank (root: what it receives)
+    int gather_root = 0;
+
+    // log of every trace launch's duration (ptk_kernel_log): event pairs on the launch's own stream
+    std::vector<hipEvent_t> klog_ev;             // 2 x capacity
+    int klog_n = 0;
+    static constexpr int kMaxTimedPasses = 64;
+    hipEvent_t ev[kMaxTimedPasses][3] = {};      // per pass: before trace, after trace, after accumulate
+    int last_passes = 0;
+    int last_launches = 0;
+    bool timed = false;
+};
+
+namespace ptk {
+inline int fail(ptk_ctx* c, int code, const std::string& msg)
+{
+    if (c) { std::lock_guard<std::mutex> g(c->err_mu); c->error = msg; }
+    return code;
+}
+#define HIPCHK(c, expr)                                                                              \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess)                                                                        \
+            return ptk::fail(c, PTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
+    } while (0)
+
+template <class T>
+void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+inline float* accum_ptr(ptk_ctx* c) { return c->d_accum_bound ? c->d_accum_bound : c->d_accum; }
+
+// "Grow a context-owned buffer to the largest call so far": at least `want` elements of `bytes_per` bytes + `extra` bytes.  The stream
+// that uses it (the context's, unless named) is drained before the old buffer is freed; a refused allocation leaves null, capacity 0.
+template <class T>
+int grow(ptk_ctx* c, T*& buf, size_t& have, size_t want, size_t bytes_per, size_t extra = 0, hipStream_t user = nullptr)
+{
+    if (want <= have) return PTK_OK;
+    HIPCHK(c, hipStreamSynchronize(user ? user : c->stream));
+    dfree(buf); have = 0;
+    HIPCHK(c, hipMalloc(&buf, want * bytes_per + extra));
+    have = want;
+    return PTK_OK;
+}
+
+// timing events are made on first use: those of a fixed array that are still missing ...
+template <size_t N>
+int ensure_events(ptk_ctx* c, hipEvent_t (&ev)[N])
+{
+    for (hipEvent_t& e : ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    return PTK_OK;
+}
+// ... and the three events of timed pass `i` in a vector of such triples (none for an untimed pass, i = -1)
+inline int ensure_pass_events(ptk_ctx* c, std::vector<hipEvent_t>& ev, int i)
+{
+    while (ev.size() < (size_t)(i + 1) * 3) { hipEvent_t e = nullptr; HIPCHK(c, hipEventCreate(&e)); ev.push_back(e); }
+    return PTK_OK;
+}
+
+// ---- internals that cross the files: ptk_api.hip ...
+void fill_params(ptk_ctx* c, RenderParams& p, uint32_t first, uint32_t spp, uint64_t seed);
+int ensure_primary(ptk_ctx* c);
+// ... ptk_api_rays.hip: a ray query on the context's stream; the checks and the round loop the adaptive lightmap bake shares with
+// the adaptive ray query, and the context's adaptive buffer cut up for its capacity ...
+int trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,
+                         uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, const uint32_t* d_keys = nullptr);
+int check_adaptive_args(ptk_ctx* c, const char* who, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp);
+struct RaysAdaptiveBuffers {
+    float *origins, *dirs, *s2;
+    uint32_t *keys, *src, *list, *keep, *counts, *block_counts, *total;
+};
+RaysAdaptiveBuffers radapt_buffers(ptk_ctx* c);
+int rays_adaptive_on_stream(ptk_ctx* c, uint32_t n, const float* d_origins, const float* d_dirs, const uint32_t* d_keys, uint32_t key_base,
+                            int max_depth, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t rays_flags,
+                            float* s1, float* s2, uint32_t* counts, const uint32_t* texel, int width, int height, ptk_rays_adaptive_result* res);
+// ... ptk_api_exchange.hip: destroys the context's own communicator, if there is one
+void comm_release(ptk_ctx* c);
+
+}  // namespace ptk

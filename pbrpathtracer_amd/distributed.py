@@ -5,7 +5,7 @@ GATHER of every rank's owned tiles to the root.
 
 The reference has no distributed path at all; this is the MI355X-native addition the north star asks
 for: an RCCL gather of the accumulation buffer over xGMI.  The product path is native — `ptk_gather_accum`
-(pbrpathtracer_amd/csrc/ptk_api.hip): pack kernel -> grouped ncclSend / ncclRecv on the library's own communicator ->
+(pbrpathtracer_amd/csrc/ptk_api_exchange.hip): pack kernel -> grouped ncclSend / ncclRecv on the library's own communicator ->
 unpack kernel on the root, all on the context's high-priority exchange stream; torch is not involved.  `NativeExchange`
 is its thin Python handle.
 

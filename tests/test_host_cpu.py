@@ -42,6 +42,16 @@ def test_bvh_builder_structure(tmp_path):
     assert out.returncode == 0, out.stdout + out.stderr
 
 
+def test_stage_layout(tmp_path):
+    """The layout half of csrc/ptk_stage.h - where the parts of a host entry's staging allocation lie - compiles without HIP and
+    keeps its promises: order, no overlap, 16-byte alignment behind odd byte counts, absent parts, the total (tests/cpp)."""
+    exe = str(tmp_path / "test_stage_layout")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "pbrpathtracer_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "test_stage_layout.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+
+
 def test_trs_and_euler_match_glm_0931():
     from pbrpathtracer_amd import pathtracer as P
     z = load_golden("tier_k.npz")
