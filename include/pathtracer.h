@@ -242,6 +242,14 @@ public:
     // order) gives at (points[i], normals[i]); needs no scene
     bool SampleProbes(const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs, int num_points,
                       const float* points, const float* normals, float* out);
+    // Extensions: probe visibility (include/ptk.h ptk_bake_probe_visibility / ptk_probes_irradiance_visible, host arrays,
+    // synchronous) at the class's seed.  depth (may be null): num_probes*num_dirs distances, +inf on a miss; moments:
+    // num_probes*res*res*2 floats.  Valid after BuildBVH() with no resolution set; pending edits apply as for TraceRays.
+    bool BakeProbeVisibility(int num_probes, const float* positions, int num_dirs, const float* dirs, int res, float max_dist, float* depth,
+                             float* moments, uint32_t sample = 0, uint32_t key_base = 0);
+    // SampleProbes with every corner probe weighted by its visibility from the point pushed normal_bias along its normal
+    bool SampleProbesVisible(const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs, int res, const float* moments,
+                             float normal_bias, int num_points, const float* points, const float* normals, float* out);
     // the camera as SetCamera last received it (position, direction, up; not normalised), 3 floats each
     void GetCamera(float* pos, float* dir, float* up) const;
     // mTotalImg (float RGB, rows bottom-up), W*H*3 floats

@@ -550,8 +550,8 @@ int ptk_last_rays_adaptive_ms(ptk_ctx* ctx, float* total_ms, float* trace_ms, fl
  * c0 = lerp(c(y0,z0), c(y1,z0), fy), c1 = lerp(c(y0,z1), c(y1,z1), fy) -, then c = lerp(c0, c1, fz).  With A = 3.141593f (k = 0),
  * 2.094395f (k = 1..3), 0.785398f (k = 4..8) and Yk taken at the query normal:
  *   E = (A*c[0])*Y0;  for k = 1..8: E = E + ((A*c[k]) * Yk).
- * Points outside the grid take the boundary's value.  There is NO visibility weighting: a probe behind a wall leaks into the room
- * in front of it; leak handling is out of scope.
+ * Points outside the grid take the boundary's value.  There is NO visibility weighting in this lookup: a probe behind a wall leaks
+ * into the room in front of it.  ptk_bake_probe_visibility and ptk_probes_irradiance_visible (below) are the leak-aware pair.
  * Like ptk_trace_rays the bake entries need a scene only - no camera, no frame -, read the scene as material and geometry edits
  * left it, touch no frame, adaptive or feature state, are not cut by ptk_request_exit and ignore ptk_set_tile, "flat" and
  * "contract".  A bake is cut into blocks of whole probes of at most max(num_dirs, "pass_bytes" / 256) rays, each a ray query of its
@@ -582,6 +582,69 @@ int ptk_probes_irradiance_device(ptk_ctx* ctx, const int32_t dims[3], const floa
  * generation (the basis table and probe_rays_kernel), the trace (rays_kernel and its fold), the projection - summed over its blocks
  * of probes (the first 64 of them); waits for the call */
 int ptk_last_probes_ms(ptk_ctx* ctx, float* raygen_ms, float* trace_ms, float* project_ms);
+
+/* ---- probe visibility: per probe the moments of the distance to the nearest surface over an octahedral map, and an irradiance
+ * lookup that uses them to keep a probe behind a wall out of the room in front of it (no counterpart in the reference) --
+ * Every float below is an individual IEEE float32 operation in the order written; sqrt is the correctly rounded root, / the IEEE
+ * quotient; sgn(s) = 1.0f when s >= 0, else -1.0f (NaN: -1); `a > b ? a : b` with a NaN operand yields the second value.
+ * Depth.  Ray r = p * num_dirs + j is (positions[p], dirs[j]), the direction as given.  depth[p][j] is bit for bit the t
+ * ptk_intersect_rays returns for that ray with (sample, seed, key_base + r mod 2^32) - the same kernel, asked for t alone -, +inf on
+ * a miss (everywhere in a scene without triangles).  With depth == NULL the table lives in a buffer of the context's.
+ * Texel directions.  A probe has res x res texels, texel (a, b) with index b*res + a:
+ *   u = ((((float)a + 0.5f) * 2.0f) / (float)res) - 1.0f;  v likewise from b;  z = (1.0f - |u|) - |v|;
+ *   if (z < 0) { x = (1.0f - |v|) * sgn(u);  y = (1.0f - |u|) * sgn(v); } else { x = u;  y = v; }
+ *   len = sqrt(((x*x) + (y*y)) + (z*z));  e = (x/len, y/len, z/len).                        (len >= 1/sqrt(3))
+ * Moments.  Per probe and texel: sw = s1 = s2 = 0; for j = 0 .. num_dirs-1 ascending, with d = dirs[j]:
+ *   R = depth[p][j] < max_dist ? depth[p][j] : max_dist (NaN gives max_dist);
+ *   c = ((ex*dx) + (ey*dy)) + (ez*dz);  c = c > 0 ? c : 0;  then five times c = c*c (the weight cos^32; no pow);
+ *   sw = sw + c;  s1 = s1 + (c * R);  s2 = s2 + (c * (R * R)).
+ * moments[p][texel] = (s1 / sw, s2 / sw) if sw > 0, else (max_dist, max_dist * max_dist).
+ * Lookup.  Per query (q, n): (i0, i1, f) per axis by ptk_probes_irradiance's rule; the biased point bq_a = q_a + (n_a * normal_bias);
+ * num = (0, 0, 0), den = 0; then the eight corners, cz outer, cy, cx inner, each over (0, 1).  Per corner and axis a:
+ *   ia = c ? i1 : i0;  ta = c ? f : (1.0f - f);  tri = (tx * ty) * tz;  pp_a = origin_a + ((float)ia * spacing_a);  v = bq - pp;
+ *   dist = sqrt(((vx*vx) + (vy*vy)) + (vz*vz));  back = vis = 1.0f;
+ *   if (dist > 0) {                                                              (not for zero or NaN)
+ *     cosn = (((vx*nx) + (vy*ny)) + (vz*nz)) / dist;  h = (1.0f - cosn) * 0.5f;  back = (h*h) + 0.2f;
+ *     s = (|vx| + |vy|) + |vz|;
+ *     if (s > 0) {
+ *       px = vx / s;  py = vy / s;
+ *       if (vz < 0) (px, py) = ((1.0f - |py|) * sgn(px), (1.0f - |px|) * sgn(py)), from the old values;
+ *       per coordinate: g = ((p * 0.5f) + 0.5f) * (float)res;  g = g > 0 ? g : 0 (NaN gives 0);  top = (float)(res-1);
+ *         g = g < top ? g : top;  a = (int)g (b from py);
+ *       (mean, mean2) = moments[(iz*ny + iy)*nx + ix][b*res + a];
+ *       if (dist > mean) { var = mean2 - (mean*mean);  var = var > 0 ? var : 0;  dd = dist - mean;  dn = var + (dd*dd);
+ *                          ch = dn > 0 ? var / dn : 0;  vis = (ch*ch) * ch; } } }
+ *   w = back * vis;  w = w > 1e-6f ? w : 1e-6f (NaN gives 1e-6f);  W = w * tri;
+ *   E_p = this probe's own irradiance at n: (A*c[0])*Y0; E_p = E_p + ((A*c[k]) * Yk), as above, from the probe's coefficients;
+ *   num_ch = num_ch + (W * E_p[ch]);  den = den + W.
+ * out_ch = num_ch / den; den > 0 always (some corner has tri >= 1/8, and w >= 1e-6).  This is the Chebyshev test of DDGI without
+ * its weight crush and with the nearest moment texel instead of a bilinear filter: both are deliberately left out.
+ * Like ptk_bake_probes the bake needs a scene only, reads it as material and geometry edits left it, touches no frame, adaptive,
+ * feature or bake state, is not cut by ptk_request_exit, ignores ptk_set_tile, "flat" and "contract", and is cut into blocks of whole
+ * probes of at most max(num_dirs, "pass_bytes" / 256) rays: the same bits.  The lookup needs no scene.  Host entries: host arrays,
+ * synchronous, staged for the length of the call; _device entries: every array in this GPU's memory (dims, origin, spacing stay
+ * host arrays), asynchronous on the context's stream (the caller's after ptk_set_stream).
+ * PTK_ERR_BAD_ARG: what ptk_bake_probes refuses for the context, the scene, the counts and null arrays (moments is required, depth
+ * may be NULL), res outside 1..16, max_dist not finite, <= 0 or > 1e18; what ptk_probes_irradiance refuses, null moments with a
+ * non-zero count, normal_bias not finite.  Zero probes or zero points: PTK_OK, nothing is done - the scalar arguments (res, max_dist,
+ * normal_bias, the grid) are checked first, as ptk_bake_probes checks its weight.  PTK_ERR_LIMIT as for ptk_trace_rays.
+ * Memory, owned by the context, grown to the largest call so far: ptk_bake_probes' 24 B per ray of ONE block, and 4 B per ray for
+ * the depth table while the caller passes none. */
+int ptk_bake_probe_visibility(ptk_ctx* ctx, int32_t num_probes, const float* positions /*[P][3]*/, int32_t num_dirs, const float* dirs /*[D][3]*/,
+                              int res, float max_dist, uint32_t sample, uint64_t seed, uint32_t key_base,
+                              float* depth /*[P][D], may be NULL*/, float* moments /*[P][res*res][2]*/);
+int ptk_bake_probe_visibility_device(ptk_ctx* ctx, int32_t num_probes, const float* d_positions, int32_t num_dirs, const float* d_dirs, int res,
+                                     float max_dist, uint32_t sample, uint64_t seed, uint32_t key_base, float* d_depth, float* d_moments);
+int ptk_probes_irradiance_visible(ptk_ctx* ctx, const int32_t dims[3], const float origin[3], const float spacing[3],
+                                  const float* coefs /*[nz][ny][nx][9][3]*/, int res, const float* moments /*[nz][ny][nx][res*res][2]*/,
+                                  float normal_bias, int32_t num_points, const float* points /*[n][3]*/, const float* normals /*[n][3]*/,
+                                  float* out /*[n][3]*/);
+int ptk_probes_irradiance_visible_device(ptk_ctx* ctx, const int32_t dims[3], const float origin[3], const float spacing[3], const float* d_coefs,
+                                         int res, const float* d_moments, float normal_bias, int32_t num_points, const float* d_points,
+                                         const float* d_normals, float* d_out);
+/* measurement hook (tools/probe_visibility_timing.py), not part of the feature: HIP-event times of the last visibility bake's
+ * kernels - ray generation and hits_kernel summed over its blocks of probes (the first 64 of them), the moments; waits for the call */
+int ptk_last_probe_visibility_ms(ptk_ctx* ctx, float* raygen_ms, float* hits_ms, float* moments_ms);
 
 int ptk_samples(ptk_ctx* ctx);         /* GetSamples (pathtracer.cpp:362-365); thread-safe */
 /* Exit (pathtracer.cpp:819-822); thread-safe.  Cuts EVERY render in flight - ptk_render is asynchronous while no output

@@ -90,6 +90,12 @@ int  pth_bake_probes(pth_tracer* t, int num_probes, const float* positions, int 
                      uint32_t spp, uint32_t key_base, uint32_t flags, float weight, float* radiance, float* coefs);
 int  pth_sample_probes(pth_tracer* t, const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs,
                        int num_points, const float* points, const float* normals, float* out);
+/* BakeProbeVisibility / SampleProbesVisible (include/ptk.h ptk_bake_probe_visibility / ptk_probes_irradiance_visible with the
+ * tracer's seed): 1 on success; depth may be NULL */
+int  pth_bake_probe_visibility(pth_tracer* t, int num_probes, const float* positions, int num_dirs, const float* dirs, int res, float max_dist,
+                               uint32_t sample, uint32_t key_base, float* depth, float* moments);
+int  pth_sample_probes_visible(pth_tracer* t, const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs, int res,
+                               const float* moments, float normal_bias, int num_points, const float* points, const float* normals, float* out);
 void pth_get_camera(pth_tracer* t, float pos[3], float dir[3], float up[3]);   /* GetCamera (extension): what SetCamera last received */
 const char* pth_last_error(pth_tracer* t);
 ptk_ctx* pth_context(pth_tracer* t);

@@ -986,6 +986,28 @@ bool PathTracer::SampleProbes(const int32_t dims[3], const float origin[3], cons
     return rc == PTK_OK;
 }
 
+// Probe visibility (ptk_bake_probe_visibility, ptk_probes_irradiance_visible) of the scene as the next RenderFrame() would see it
+bool PathTracer::BakeProbeVisibility(int num_probes, const float* positions, int num_dirs, const float* dirs, int res, float max_dist, float* depth,
+                                     float* moments, uint32_t sample, uint32_t key_base)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_bake_probe_visibility(m->ctx, num_probes, positions, num_dirs, dirs, res, max_dist, sample, m->seed, key_base, depth, moments);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::SampleProbesVisible(const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs, int res,
+                                     const float* moments, float normal_bias, int num_points, const float* points, const float* normals, float* out)
+{
+    if (!m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const int rc = ptk_probes_irradiance_visible(m->ctx, dims, origin, spacing, coefs, res, moments, normal_bias, num_points, points, normals, out);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 void PathTracer::Exit() { if (m->ctx) ptk_request_exit(m->ctx); }      // :819-822
 
 // ---- extensions -----------------------------------------------------------------------------------------

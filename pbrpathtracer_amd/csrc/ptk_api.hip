@@ -586,6 +586,9 @@ void ptk_destroy(ptk_ctx* c)
     dfree(c->d_probe_basis); dfree(c->d_probe_rays); dfree(c->d_probe_table);
     for (hipEvent_t e : c->ev_probes) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_probe_blocks) (void)hipEventDestroy(e);
+    dfree(c->d_probe_depth);
+    for (hipEvent_t e : c->ev_probe_vis) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_probe_vis_blocks) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_rays) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_hits) if (e) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; b++)

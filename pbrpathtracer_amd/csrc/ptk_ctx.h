@@ -170,6 +170,15 @@ struct ptk_ctx {
     int probe_blocks_timed = 0;
     bool probes_timed = false;
 
+    // probe visibility (ptk_bake_probe_visibility): the depth table while the caller passes none (4 B per ray, grown to the largest
+    // call so far; the rays of a block are d_probe_rays); two events of the last call around the moments kernel and three per block
+    // of probes as above: before the ray generator, behind it, behind hits_kernel
+    float* d_probe_depth = nullptr; size_t probe_depth_rays = 0;
+    hipEvent_t ev_probe_vis[2] = { nullptr, nullptr };
+    std::vector<hipEvent_t> ev_probe_vis_blocks;
+    int probe_vis_blocks_timed = 0;
+    bool probe_vis_timed = false;
+
     // closest-hit and occlusion queries (ptk_intersect_rays, ptk_occluded_rays): two events around the last call's kernel, made
     // by the first call
     hipEvent_t ev_hits[2] = { nullptr, nullptr };

@@ -162,6 +162,16 @@ int pth_sample_probes(pth_tracer* t, const int32_t dims[3], const float origin[3
 {
     return t->pt.SampleProbes(dims, origin, spacing, coefs, num_points, points, normals, out) ? 1 : 0;
 }
+int pth_bake_probe_visibility(pth_tracer* t, int num_probes, const float* positions, int num_dirs, const float* dirs, int res, float max_dist,
+                              uint32_t sample, uint32_t key_base, float* depth, float* moments)
+{
+    return t->pt.BakeProbeVisibility(num_probes, positions, num_dirs, dirs, res, max_dist, depth, moments, sample, key_base) ? 1 : 0;
+}
+int pth_sample_probes_visible(pth_tracer* t, const int32_t dims[3], const float origin[3], const float spacing[3], const float* coefs, int res,
+                              const float* moments, float normal_bias, int num_points, const float* points, const float* normals, float* out)
+{
+    return t->pt.SampleProbesVisible(dims, origin, spacing, coefs, res, moments, normal_bias, num_points, points, normals, out) ? 1 : 0;
+}
 void pth_get_camera(pth_tracer* t, float* pos, float* dir, float* up) { t->pt.GetCamera(pos, dir, up); }
 const char* pth_last_error(pth_tracer* t)
 {

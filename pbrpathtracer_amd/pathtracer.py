@@ -37,6 +37,7 @@ HOST_SYMBOLS = [
     "pth_export_png", "pth_render_adaptive", "pth_read_sample_counts",
     "pth_render_features", "pth_read_feature", "pth_pick", "pth_set_object_transform", "pth_trace_rays", "pth_get_camera",
     "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
+    "pth_bake_probe_visibility", "pth_sample_probes_visible",
     "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays",
 ]
 
@@ -100,6 +101,10 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_bake_probes.restype = i32
         L.pth_bake_probes.argtypes = [vp, i32, vp, i32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32, vp, vp]
         L.pth_sample_probes.restype = i32; L.pth_sample_probes.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
+        L.pth_bake_probe_visibility.restype = i32
+        L.pth_bake_probe_visibility.argtypes = [vp, i32, vp, i32, vp, i32, f32, C.c_uint32, C.c_uint32, vp, vp]
+        L.pth_sample_probes_visible.restype = i32
+        L.pth_sample_probes_visible.argtypes = [vp, vp, vp, vp, vp, i32, vp, f32, i32, vp, vp, vp]
         u32, res = C.c_uint32, C.POINTER(_ptk.RaysAdaptiveResult)
         L.pth_trace_rays_adaptive.restype = i32
         L.pth_trace_rays_adaptive.argtypes = [vp, i32, vp, vp, f32, u32, u32, u32, u32, u32, vp, vp, vp, res]
@@ -455,6 +460,38 @@ class PathTracer:
         ptr = (lambda a: a.ctypes.data if a.size else None)
         if not self.L.pth_sample_probes(self.h, g_dims, g_origin, g_spacing, ptr(c), len(q), ptr(q), ptr(nrm), ptr(out)):
             raise _ptk.PtkError("SampleProbes failed: " + self.LastError())
+        return out
+
+    def BakeProbeVisibility(self, positions, dirs, res: int, max_dist: float, sample: int = 0, key_base: int = 0):
+        """Extension: probe visibility (include/ptk.h ptk_bake_probe_visibility) at this tracer's seed.  positions [P, 3], dirs
+        [D, 3]; returns (depth [P, D], moments [P, res * res, 2]) float32."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        depth = np.empty((len(pos), len(d)), np.float32)
+        moments = np.empty((len(pos), int(res) * int(res) if 1 <= int(res) <= 16 else 1, 2), np.float32)
+        ptr = (lambda a: a.ctypes.data if a.size else None)
+        if not self.L.pth_bake_probe_visibility(self.h, len(pos), ptr(pos), len(d), ptr(d), int(res), float(max_dist), int(sample),
+                                                int(key_base) & 0xffffffff, ptr(depth), ptr(moments)):
+            raise _ptk.PtkError("BakeProbeVisibility failed: " + self.LastError())
+        return depth, moments
+
+    def SampleProbesVisible(self, dims, origin, spacing, coefs, res: int, moments, points, normals, normal_bias: float = 0.0) -> np.ndarray:
+        """Extension: SampleProbes with the probes weighted by their visibility (ptk_probes_irradiance_visible); moments
+        [nz, ny, nx, res * res, 2] as BakeProbeVisibility gave them for probes.grid_positions(dims, origin, spacing)."""
+        g_dims = (C.c_int32 * 3)(*(int(n) for n in dims))
+        g_origin = (C.c_float * 3)(*(float(x) for x in origin))
+        g_spacing = (C.c_float * 3)(*(float(x) for x in spacing))
+        c = np.ascontiguousarray(coefs, dtype=np.float32)
+        mo = np.ascontiguousarray(moments, dtype=np.float32)
+        q = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        probes = int(g_dims[0]) * int(g_dims[1]) * int(g_dims[2])
+        assert c.size == probes * 27 and mo.size == probes * int(res) * int(res) * 2 and len(nrm) == len(q)
+        out = np.empty((len(q), 3), np.float32)
+        ptr = (lambda a: a.ctypes.data if a.size else None)
+        if not self.L.pth_sample_probes_visible(self.h, g_dims, g_origin, g_spacing, ptr(c), int(res), ptr(mo), float(normal_bias), len(q),
+                                                ptr(q), ptr(nrm), ptr(out)):
+            raise _ptk.PtkError("SampleProbesVisible failed: " + self.LastError())
         return out
 
     def ReadAccumulation(self) -> np.ndarray:

@@ -44,6 +44,13 @@ def sh_weight(num_dirs: int, samples: int) -> float:
     return float(np.float32(4.0 * math.pi / (float(num_dirs) * float(samples))))
 
 
+def default_max_dist(spacing) -> float:
+    """the max_dist of bake_probe_visibility for a grid: 1.5 x the cell diagonal sqrt((sx*sx + sy*sy) + sz*sz), every operation in
+    float32 - beyond it a surface cannot shadow a query of the probe's own cells"""
+    s = np.asarray(spacing, np.float32).reshape(3)
+    return float(np.float32(1.5) * np.sqrt(((s[0] * s[0]) + (s[1] * s[1])) + (s[2] * s[2])))
+
+
 def grid_over_bounds(lo, hi, dims):
     """(origin, spacing) float32 [3] each of a grid of dims probes that spans the box lo..hi: the outermost probes lie on the box;
     an axis of one probe puts it in the middle (spacing 1 there, as for an axis without extent)"""

@@ -97,6 +97,8 @@ SYMBOLS = [
     "ptk_trace_rays_adaptive", "ptk_trace_rays_adaptive_device", "ptk_bake_lightmap_adaptive", "ptk_bake_lightmap_adaptive_device",
     "ptk_last_rays_adaptive_ms",
     "ptk_bake_probes", "ptk_bake_probes_device", "ptk_probes_irradiance", "ptk_probes_irradiance_device", "ptk_last_probes_ms",
+    "ptk_bake_probe_visibility", "ptk_bake_probe_visibility_device", "ptk_probes_irradiance_visible",
+    "ptk_probes_irradiance_visible_device", "ptk_last_probe_visibility_ms",
 ]
 
 
@@ -186,6 +188,11 @@ def _load_locked() -> C.CDLL:
         for fn in (L.ptk_probes_irradiance, L.ptk_probes_irradiance_device):
             fn.argtypes = [vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp]
         L.ptk_last_probes_ms.argtypes = [vp, fp, fp, fp]
+        for fn in (L.ptk_bake_probe_visibility, L.ptk_bake_probe_visibility_device):
+            fn.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, i32, f32, u32, u64, u32, vp, vp]
+        for fn in (L.ptk_probes_irradiance_visible, L.ptk_probes_irradiance_visible_device):
+            fn.argtypes = [vp, vp, vp, vp, vp, i32, vp, f32, C.c_int32, vp, vp, vp]
+        L.ptk_last_probe_visibility_ms.argtypes = [vp, fp, fp, fp]
         for fn in (L.ptk_trace_rays_adaptive, L.ptk_trace_rays_adaptive_device):
             fn.argtypes = [vp, C.c_int32, vp, vp, i32, f32, u32, u32, u32, u64, u32, u32, vp, vp, vp, C.POINTER(RaysAdaptiveResult)]
         for fn in (L.ptk_bake_lightmap_adaptive, L.ptk_bake_lightmap_adaptive_device):
@@ -754,6 +761,83 @@ class Context:
         t = [C.c_float(0) for _ in range(3)]
         self._chk(self.L.ptk_last_probes_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_probes_ms")
         return dict(zip(("raygen_ms", "trace_ms", "project_ms"), (x.value for x in t)))
+
+    # ---- probe visibility ------------------------------------------------------------------
+    def bake_probe_visibility(self, positions, dirs, res: int, max_dist: float, sample: int = 0, seed: int = 0, key_base: int = 0,
+                              want_depth: bool = True):
+        """ptk_bake_probe_visibility: (depth [P, D], moments [P, res * res, 2]) float32 of the probes at positions [P, 3] over the
+        directions dirs [D, 3] (used as given): depth[p, j] = the t intersect_rays gives the ray (positions[p], dirs[j]) with
+        (sample, seed, key_base + p * D + j), inf on a miss; moments[p, b * res + a] = the cos^32-weighted mean of min(depth,
+        max_dist) and of its square about the direction of octahedral texel (a, b) (probes.default_max_dist for a grid).
+        numpy arrays go through the host entry (synchronous); torch tensors on the context's GPU through the _device entry with no
+        host copy, written on the context's stream.  want_depth=False: the table stays in the context's own buffer and None is
+        returned for it."""
+        args = (int(res), float(max_dist), int(sample), int(seed), int(key_base) & 0xffffffff)
+        texels = int(res) * int(res) if 1 <= int(res) <= 16 else 1       # (a refused res allocates no more than that)
+        if hasattr(positions, "data_ptr"):
+            import torch
+            dev = self.device_ordinal()
+            P, D = positions.numel() // 3, dirs.numel() // 3
+            depth = torch.empty((P, D), dtype=torch.float32, device=positions.device) if want_depth else None
+            moments = torch.empty((P, texels, 2), dtype=torch.float32, device=positions.device)
+            for t, n in ((positions, P * 3), (dirs, D * 3)):
+                assert t.is_cuda and t.device.index == dev, f"tensor on {t.device}, context on device {dev}"
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, "float32 contiguous tensors of [P, 3], [D, 3]"
+            ptr = (lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None)
+            self._chk(self.L.ptk_bake_probe_visibility_device(self.h, P, ptr(positions), D, ptr(dirs), *args, ptr(depth), ptr(moments)),
+                      "ptk_bake_probe_visibility_device")
+            return depth, moments
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        P, D = len(pos), len(d)
+        depth = np.empty((P, D), np.float32) if want_depth else None
+        moments = np.empty((P, texels, 2), np.float32)
+        ptr = (lambda a: a.ctypes.data if a is not None and a.size else None)
+        self._chk(self.L.ptk_bake_probe_visibility(self.h, P, ptr(pos), D, ptr(d), *args, ptr(depth), ptr(moments)), "ptk_bake_probe_visibility")
+        return depth, moments
+
+    def probes_irradiance_visible(self, dims, origin, spacing, coefs, res: int, moments, points, normals, normal_bias: float = 0.0):
+        """ptk_probes_irradiance_visible: probes_irradiance with every corner probe weighted by its trilinear factor, a back-face
+        term and the Chebyshev bound of its depth moments - moments [nz, ny, nx, res * res, 2] of bake_probe_visibility over
+        probes.grid_positions - at the point pushed normal_bias along its normal: a probe behind a wall no longer lights the room in
+        front of it.  numpy arrays: the host entry; torch tensors (coefs, moments, points, normals) on the context's GPU: the device
+        entry, on the context's stream."""
+        g_dims = (C.c_int32 * 3)(*(int(n) for n in dims))
+        g_origin = (C.c_float * 3)(*(float(x) for x in origin))
+        g_spacing = (C.c_float * 3)(*(float(x) for x in spacing))
+        probes = int(g_dims[0]) * int(g_dims[1]) * int(g_dims[2])
+        if hasattr(points, "data_ptr"):
+            import torch
+            dev = self.device_ordinal()
+            n = points.numel() // 3
+            out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+            for t, m in ((coefs, probes * 27), (moments, probes * int(res) * int(res) * 2), (points, n * 3), (normals, n * 3)):
+                assert t.is_cuda and t.device.index == dev, f"tensor on {t.device}, context on device {dev}"
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == m, \
+                    "float32 contiguous tensors of [nz, ny, nx, 9, 3], [nz, ny, nx, res * res, 2], [n, 3]"
+            ptr = (lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None)
+            self._chk(self.L.ptk_probes_irradiance_visible_device(self.h, g_dims, g_origin, g_spacing, ptr(coefs), int(res), ptr(moments),
+                                                                  float(normal_bias), n, ptr(points), ptr(normals), ptr(out)),
+                      "ptk_probes_irradiance_visible_device")
+            return out
+        c = np.ascontiguousarray(coefs, dtype=np.float32)
+        m = np.ascontiguousarray(moments, dtype=np.float32)
+        q = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        assert c.size == probes * 27, "coefs: dims[0] * dims[1] * dims[2] probes of 9 x 3 floats"
+        assert m.size == probes * int(res) * int(res) * 2, "moments: dims[0] * dims[1] * dims[2] probes of res x res x 2 floats"
+        assert len(nrm) == len(q), "as many normals as points"
+        out = np.empty((len(q), 3), np.float32)
+        ptr = (lambda a: a.ctypes.data if a.size else None)
+        self._chk(self.L.ptk_probes_irradiance_visible(self.h, g_dims, g_origin, g_spacing, ptr(c), int(res), ptr(m), float(normal_bias),
+                                                       len(q), ptr(q), ptr(nrm), ptr(out)), "ptk_probes_irradiance_visible")
+        return out
+
+    def last_probe_visibility_ms(self) -> dict:
+        """HIP-event times (ms) of the last visibility bake's kernels: ray generation, hits, moments; waits for it."""
+        t = [C.c_float(0) for _ in range(3)]
+        self._chk(self.L.ptk_last_probe_visibility_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_probe_visibility_ms")
+        return dict(zip(("raygen_ms", "hits_ms", "moments_ms"), (x.value for x in t)))
 
     def read_sample_counts(self) -> np.ndarray:
         """[H][W] uint32 samples per pixel, rows bottom-up like read_accum; 0 = not owned."""

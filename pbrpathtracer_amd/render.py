@@ -8,6 +8,7 @@
     python -m pbrpathtracer_amd.render scene.pts --bake-lightmap 1024 --spp 64 [--bake-atlas] [--bake-offset F] [--bake-back]
                                                  [--dilate K] -o map.png [--npy map.npy]
     python -m pbrpathtracer_amd.render scene.pts --bake-probes NX NY NZ [--probe-dirs D] --spp N -o probes.npz
+                                                 [--probe-visibility RES [--probe-max-dist M]]
 
 With --noise-threshold the render is adaptive (include/ptk.h ptk_render_adaptive): --spp becomes the most samples a pixel
 gets, and pixels stop once their noise meets the threshold.  --equirect and --bake-lightmap take it too (ptk_trace_rays_adaptive,
@@ -27,7 +28,10 @@ baked by PathTracer.BakeLightmap and padded by --dilate K passes of ptk_lightmap
 
 With --bake-probes NX NY NZ the output is an .npz of irradiance probes (include/ptk.h ptk_bake_probes): a grid of NX x NY x NZ probes
 that spans the scene's vertex bounds, --probe-dirs directions of probes.fibonacci_dirs each, baked by PathTracer.BakeProbes; it holds
-coefs [NZ, NY, NX, 9, 3], dims, origin and spacing - the arguments of ptk_probes_irradiance / PathTracer.SampleProbes.
+coefs [NZ, NY, NX, 9, 3], dims, origin and spacing - the arguments of ptk_probes_irradiance / PathTracer.SampleProbes.  With
+--probe-visibility RES it also holds the probes' depth moments (include/ptk.h ptk_bake_probe_visibility, sample 0, over the same
+directions): moments [NZ, NY, NX, RES * RES, 2], res and max_dist (--probe-max-dist, by default probes.default_max_dist of the
+spacing) - the further arguments of ptk_probes_irradiance_visible / PathTracer.SampleProbesVisible.
 
 The headless equivalent of the reference's Start button + Export (main.cpp:3563-3618, :760-771):
 LoadScene -> SendObjectsToPathTracer -> RenderFrame() x spp -> PNG (flipped to top-down)."""
@@ -74,6 +78,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="bake a grid of NX x NY x NZ irradiance probes over the scene's vertex bounds instead of rendering a view; "
                          "-o names an .npz with coefs [NZ, NY, NX, 9, 3], dims, origin, spacing")
     ap.add_argument("--probe-dirs", type=int, default=256, metavar="D", help="--bake-probes: directions per probe (default 256)")
+    ap.add_argument("--probe-visibility", type=int, default=None, metavar="RES",
+                    help="--bake-probes: also bake RES x RES depth moments per probe (1..16) and add moments, res, max_dist to the .npz")
+    ap.add_argument("--probe-max-dist", type=float, default=None, metavar="M",
+                    help="--probe-visibility: distance the depths are clamped to (default: 1.5 x the grid's cell diagonal)")
     return ap
 
 
@@ -156,10 +164,16 @@ def render_lightmap_adaptive(pt, a, size, uvs, offset) -> int:
 
 
 def render_probes(pt, a) -> int:
-    from .probes import fibonacci_dirs, grid_over_bounds, grid_positions, sh_weight
+    from .probes import default_max_dist, fibonacci_dirs, grid_over_bounds, grid_positions, sh_weight
     dims = tuple(a.bake_probes)
     if min(dims) < 1 or not 1 <= a.probe_dirs <= 65536 or a.spp < 1:
         print("error: --bake-probes needs dims of at least 1, --probe-dirs in 1..65536 and --spp of at least 1", file=sys.stderr)
+        return 1
+    if a.probe_visibility is not None and not 1 <= a.probe_visibility <= 16:
+        print("error: --probe-visibility needs a resolution in 1..16", file=sys.stderr)
+        return 1
+    if a.probe_max_dist is not None and (a.probe_visibility is None or not 0.0 < a.probe_max_dist <= 1e18):
+        print("error: --probe-max-dist goes with --probe-visibility and needs a distance > 0 and at most 1e18", file=sys.stderr)
         return 1
     v = np.asarray(pt.StagedScene()["verts"], np.float64).reshape(-1, 3)
     if not len(v):
@@ -168,13 +182,24 @@ def render_probes(pt, a) -> int:
     origin, spacing = grid_over_bounds(v.min(axis=0), v.max(axis=0), dims)
     pos = grid_positions(dims, origin, spacing)
     t1 = time.time()
-    _, coefs = pt.BakeProbes(pos, fibonacci_dirs(a.probe_dirs), 0, a.spp, sh_weight(a.probe_dirs, a.spp))
+    dirs = fibonacci_dirs(a.probe_dirs)
+    _, coefs = pt.BakeProbes(pos, dirs, 0, a.spp, sh_weight(a.probe_dirs, a.spp))
     t2 = time.time()
+    fields = dict(coefs=coefs.reshape(dims[2], dims[1], dims[0], 9, 3), dims=np.array(dims, np.int32), origin=origin, spacing=spacing)
+    if a.probe_visibility is not None:
+        res = a.probe_visibility
+        max_dist = a.probe_max_dist if a.probe_max_dist is not None else default_max_dist(spacing)
+        _, moments = pt.BakeProbeVisibility(pos, dirs, res, max_dist)
+        fields.update(moments=moments.reshape(dims[2], dims[1], dims[0], res * res, 2), res=np.int32(res), max_dist=np.float32(max_dist))
+    t3 = time.time()
     with open(a.out, "wb") as f:                # (np.savez would append .npz to another suffix)
-        np.savez(f, coefs=coefs.reshape(dims[2], dims[1], dims[0], 9, 3), dims=np.array(dims, np.int32), origin=origin, spacing=spacing)
+        np.savez(f, **fields)
     rays = len(pos) * a.probe_dirs
     print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {dims[0]}x{dims[1]}x{dims[2]} probes x {a.probe_dirs} directions, {a.spp} spp, "
           f"depth {pt.GetTraceDepth()}: {t2 - t1:.3f} s ({rays * a.spp / (t2 - t1) / 1e6:.0f} Msamples/s) -> {a.out}")
+    if a.probe_visibility is not None:
+        print(f"visibility: {a.probe_visibility}x{a.probe_visibility} depth moments per probe, max_dist {max_dist:g}: {t3 - t2:.3f} s "
+              f"({rays / (t3 - t2) / 1e6:.0f} Mrays/s)")
     return 0
 
 
@@ -232,6 +257,9 @@ def main(argv=None):
     if a.pinhole:
         pt.SetCameraAperture(0.0)
     pt.SetSeed(a.seed)
+    if a.bake_probes is None and (a.probe_visibility is not None or a.probe_max_dist is not None):
+        print("error: --probe-visibility and --probe-max-dist go with --bake-probes", file=sys.stderr)
+        return 1
     if a.bake_lightmap is not None:
         try:
             return render_lightmap(pt, a)
