@@ -194,6 +194,22 @@ class Oracle:
         assert rc == 0, "ray records overflowed"
         return dict(counts=counts, total=total, rays=rays)
 
+    def render_census(self, cam: CameraC, width, height, depth, first_sample, spp, seed, brute=False, threads=0, total=None) -> dict:
+        """orc_render that counts the named arms of tex2d, test_triangle, shade, sample_about and direct_illumination
+        (oracle/pt_oracle.h ORC_ARM_*): dict arm name -> count, summed over the frame.  brute: candidates in ascending index order,
+        as the FLAT and PLAIN passes meet them, instead of the tree walk's order.  total, when given, is accumulated as render does."""
+        L = self.lib
+        L.orc_arm_name.restype = C.c_char_p
+        L.orc_arm_name.argtypes = [C.c_int]
+        L.orc_render_census.argtypes = [C.c_void_p, C.POINTER(CameraC), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        arms = np.zeros(L.orc_arm_count(), np.int64)
+        if total is not None:
+            assert total.dtype == np.float32 and total.flags.c_contiguous
+        L.orc_render_census(self.h, C.byref(cam), width, height, depth, first_sample, spp, seed, int(bool(brute)),
+                            total.ctypes.data if total is not None else None, arms.ctypes.data, threads)
+        return {L.orc_arm_name(i).decode(): int(arms[i]) for i in range(len(arms))}
+
     def render_tape(self, cam: CameraC, width, height, depth, tape):
         """One RenderFrame with the reference's draws on tape (its single-thread pixel order); returns (total, draws consumed)."""
         total = np.zeros((height, width, 3), dtype=np.float32)

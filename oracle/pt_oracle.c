@@ -185,11 +185,18 @@ void orc_intersect_triangle(const float* ro, const float* rd, const float* v0, c
     else out3[0] = out3[1] = out3[2] = 0.0f;
 }
 
+/* ---- census (test infrastructure: orc_render_census) ---------------------------------------------
+ * Every function below that decides something takes `cz`, the census' counters (ORC_ARM_N of them) or NULL.  The functions
+ * orc_render, trace and the probes call are thin wrappers that pass a literal NULL into the always-inlined body, so the
+ * compiler drops every ARM() from them: their code is what it was without the census. */
+#define ORC_INLINE static inline __attribute__((always_inline))
+#define ARM(cz, id) do { if (cz) (cz)[id]++; } while (0)
+
 /* ---- Image::tex2D image.cpp:63-86 -----------------------------------------------------------*/
-static inline void tex2d(const orc_scene* s, int tex, float uvx, float uvy, float* out4)
+ORC_INLINE void tex2d_impl(const orc_scene* s, int tex, float uvx, float uvy, float* out4, int64_t* cz, int slot)
 {
     if (tex < 0 || tex >= s->ntex || s->tex[tex].width <= 0 || s->tex[tex].height <= 0)
-    { out4[0] = out4[1] = out4[2] = out4[3] = 0.0f; return; }
+    { ARM(cz, ORC_ARM_TEX + slot * ORC_TEX_ARMS + ORC_TEX_MISSING); out4[0] = out4[1] = out4[2] = out4[3] = 0.0f; return; }
     const orc_texture* T = &s->tex[tex];
     float u = fmodf(uvx, 1.0f);
     float v = fmodf(uvy, 1.0f);
@@ -197,6 +204,13 @@ static inline void tex2d(const orc_scene* s, int tex, float uvx, float uvy, floa
     if (v < 0.0f) v += 1.0f;
     int cx = (int)((float)T->width * u);
     int cy = (int)((float)T->height * v);
+    if (cz)
+    {
+        int64_t* a = cz + ORC_ARM_TEX + slot * ORC_TEX_ARMS;
+        const int hx = cx > T->width - 1, hy = cy > T->height - 1, lx = cx < 0, ly = cy < 0;
+        a[ORC_TEX_HI_X] += hx; a[ORC_TEX_HI_Y] += hy; a[ORC_TEX_LO_X] += lx; a[ORC_TEX_LO_Y] += ly;
+        a[ORC_TEX_PLAIN] += !(hx | hy | lx | ly);
+    }
     if (cx > T->width - 1) cx = T->width - 1;     /* clamp: see header (reference over-reads) */
     if (cy > T->height - 1) cy = T->height - 1;
     if (cx < 0) cx = 0;                            /* NaN uv */
@@ -207,6 +221,7 @@ static inline void tex2d(const orc_scene* s, int tex, float uvx, float uvy, floa
     out4[2] = (float)p[2] / 255.0f;
     out4[3] = (float)p[3] / 255.0f;
 }
+static inline void tex2d(const orc_scene* s, int tex, float uvx, float uvy, float* out4) { tex2d_impl(s, tex, uvx, uvy, out4, NULL, 0); }
 void orc_tex2d(const orc_scene* s, int tex, float u, float v, float* out4) { tex2d(s, tex, u, v, out4); }
 
 /* PathTracer::GetUV pathtracer.cpp:533-536 */
@@ -333,27 +348,35 @@ typedef struct { int32_t tri; float t, u, v; } hit_t;
 /* candidate test of one triangle: Hit leaf branch, pathtracer.cpp:463-489 */
 /* returns 1 when it looked up an opacity texel (the candidate hits and is nearer than the best so far), for the counting
  * render below; the others ignore it */
-static inline int test_triangle(const orc_scene* s, int tri, v3 ro, v3 rd, rng_t* rng, uint32_t ray, hit_t* best)
+ORC_INLINE int test_triangle_impl(const orc_scene* s, int tri, v3 ro, v3 rd, rng_t* rng, uint32_t ray, hit_t* best, int64_t* cz)
 {
     const float* p = s->verts + (size_t)tri * 9;
     float t, u, v;
     if (!intersect_triangle(ro, rd, ld3(p), ld3(p + 3), ld3(p + 6), &t, &u, &v)) return 0;
     /* (an infinite t - an overflowed determinant of a ray far outside every scene - is no hit: with best->t starting at
        infinity the tie rule would otherwise accept it; the kernels test the same) */
+    if (cz && t < INFINITY)
+        ARM(cz, t < best->t ? ORC_ARM_TRI_NEARER : (t == best->t ? (tri < best->tri ? ORC_ARM_TRI_TIE_ACCEPTED : ORC_ARM_TRI_TIE_REJECTED)
+                                                                 : ORC_ARM_TRI_FARTHER));
     if (!(t < INFINITY) || !(t < best->t || (t == best->t && tri < best->tri))) return 0;
     int otex = s->mats[s->material[tri]].tex[5];
     if (otex >= 0)
     {
         float ux, uy, c[4];
         get_uv(s, tri, u, v, &ux, &uy);
-        tex2d(s, otex, ux, uy, c);
-        if (!(rnd_opacity(rng, ray, (uint32_t)tri) < c[0])) return 1;
+        tex2d_impl(s, otex, ux, uy, c, cz, 5);
+        if (!(rnd_opacity(rng, ray, (uint32_t)tri) < c[0])) { ARM(cz, ORC_ARM_TRI_OPACITY_DROPPED); return 1; }
+        ARM(cz, ORC_ARM_TRI_OPACITY_KEPT);
     }
     best->tri = tri; best->t = t; best->u = u; best->v = v;
     return otex >= 0;
 }
+static inline int test_triangle(const orc_scene* s, int tri, v3 ro, v3 rd, rng_t* rng, uint32_t ray, hit_t* best)
+{
+    return test_triangle_impl(s, tri, ro, rd, rng, ray, best, NULL);
+}
 
-static int closest_hit(const orc_scene* s, v3 ro, v3 rd, rng_t* rng, uint32_t ray, hit_t* out)
+ORC_INLINE int closest_hit_impl(const orc_scene* s, v3 ro, v3 rd, rng_t* rng, uint32_t ray, hit_t* out, int64_t* cz)
 {
     hit_t best; best.tri = 0x7fffffff; best.t = INFINITY; best.u = best.v = 0.0f;
     if (s->nt == 0) return 0;
@@ -371,14 +394,29 @@ static int closest_hit(const orc_scene* s, v3 ro, v3 rd, rng_t* rng, uint32_t ra
         if (!(tn <= tf * 1.0000004f) || tf < 0.0f || tn > best.t) continue;
         if (n->left < 0)
         {
-            for (int i = 0; i < n->count; i++) test_triangle(s, s->order[n->first + i], ro, rd, rng, ray, &best);
+            for (int i = 0; i < n->count; i++) test_triangle_impl(s, s->order[n->first + i], ro, rd, rng, ray, &best, cz);
         }
         else if (sp + 2 <= 128)
         {
             stack[sp++] = n->right;
             stack[sp++] = n->left;
         }
+        else ARM(cz, ORC_ARM_WALK_STACK_FULL);
     }
+    if (best.tri == 0x7fffffff) return 0;
+    *out = best;
+    return 1;
+}
+static int closest_hit(const orc_scene* s, v3 ro, v3 rd, rng_t* rng, uint32_t ray, hit_t* out)
+{
+    return closest_hit_impl(s, ro, rd, rng, ray, out, NULL);
+}
+/* the census' closest hit: the tree walk above, or (brute) the candidates in ascending index order, the FLAT pass's */
+static int closest_hit_census(const orc_scene* s, v3 ro, v3 rd, rng_t* rng, uint32_t ray, hit_t* out, int64_t* cz, int brute)
+{
+    if (!brute) return closest_hit_impl(s, ro, rd, rng, ray, out, cz);
+    hit_t best; best.tri = 0x7fffffff; best.t = INFINITY; best.u = best.v = 0.0f;
+    for (int i = 0; i < s->nt; i++) test_triangle_impl(s, i, ro, rd, rng, ray, &best, cz);
     if (best.tri == 0x7fffffff) return 0;
     *out = best;
     return 1;
@@ -447,8 +485,13 @@ static int closest_hit_counted(const orc_scene* s, v3 ro, v3 rd, rng_t* rng, uin
 /* ---- hemisphere / lobe samplers, pathtracer.cpp:606-611 and :618-623 ------------------------------
  * pole: the axis the sample is built around (n or r); basis_from: vector crossed to make u,v
  * (n for the hemisphere form, r for the lobe form); nx_test: |n.x| against thr chooses the helper. */
-static inline v3 sample_about(v3 n_for_test, float thr, v3 basis_from, v3 pole, float w, float theta)
+ORC_INLINE v3 sample_about_impl(v3 n_for_test, float thr, v3 basis_from, v3 pole, float w, float theta, int64_t* cz, int site)
 {
+    if (cz)
+    {
+        const float ax = fabsf(n_for_test.x);
+        cz[ORC_ARM_SA + site * ORC_SA_CLASSES + (ax < 1.0f - ORC_EPS ? ORC_SA_BELOW : (ax < 1.0f - ORC_FLT_EPSILON ? ORC_SA_BAND : ORC_SA_POLE))]++;
+    }
     v3 u = fabsf(n_for_test.x) < thr ? cross(V(1.0f, 0.0f, 0.0f), basis_from) : cross(V(1.0f, 1.0f, 1.0f), basis_from);
     u = normalize(u);
     v3 v = normalize(cross(u, basis_from));
@@ -460,11 +503,12 @@ static inline v3 sample_about(v3 n_for_test, float thr, v3 basis_from, v3 pole, 
 }
 
 /* PathTracer::SampleTriangle + DirectIllumimation, pathtracer.cpp:494-531 */
-static v3 direct_illumination_c(const orc_scene* s, v3 p, v3 n, v3 diffuse, rng_t* rng, uint32_t* ray, count_t* cc)
+ORC_INLINE v3 direct_illumination_impl(const orc_scene* s, v3 p, v3 n, v3 diffuse, rng_t* rng, uint32_t* ray, count_t* cc, int64_t* cz,
+                                       int brute)
 {
-    if (s->nl == 0) return V(0.0f, 0.0f, 0.0f);
+    if (s->nl == 0) { ARM(cz, ORC_ARM_DI_NO_LIGHTS); return V(0.0f, 0.0f, 0.0f); }
     int lightId = (int)floorf(rnd(rng) * (float)s->nl);
-    if (lightId == s->nl && lightId > 0) lightId--;
+    if (lightId == s->nl && lightId > 0) { ARM(cz, ORC_ARM_DI_LIGHT_ID_CLAMPED); lightId--; }
     int ltri = s->lights[lightId];
     const float* lp = s->verts + (size_t)ltri * 9;
     float u = sqrtf(rnd(rng));
@@ -473,16 +517,23 @@ static v3 direct_illumination_c(const orc_scene* s, v3 p, v3 n, v3 diffuse, rng_
     v3 vLight = add(add(muls(ld3(lp), w0), muls(ld3(lp + 3), w1)), muls(ld3(lp + 6), w2));
     v3 l = normalize(sub(vLight, p));
     float ndl = dot(neg(n), neg(l));
-    if (ndl <= 0.0f) return V(0.0f, 0.0f, 0.0f);
+    if (ndl <= 0.0f) { ARM(cz, ORC_ARM_DI_NDL_NOT_POSITIVE); return V(0.0f, 0.0f, 0.0f); }
     hit_t h;
     uint32_t r = (*ray)++;
-    if (cc ? closest_hit_counted(s, p, l, rng, r, ORC_RAY_SHADOW, ltri, cc, &h) : closest_hit(s, p, l, rng, r, &h))
+    if (cz ? closest_hit_census(s, p, l, rng, r, &h, cz, brute)
+           : (cc ? closest_hit_counted(s, p, l, rng, r, ORC_RAY_SHADOW, ltri, cc, &h) : closest_hit(s, p, l, rng, r, &h)))
     {
-        if (h.tri != ltri) return V(0.0f, 0.0f, 0.0f);
+        if (h.tri != ltri) { ARM(cz, ORC_ARM_DI_HIT_OTHER); return V(0.0f, 0.0f, 0.0f); }
+        ARM(cz, ORC_ARM_DI_HIT_LIGHT);
     }
+    else ARM(cz, ORC_ARM_DI_SHADOW_MISSED);
     const orc_material* lm = &s->mats[s->material[ltri]];
     v3 lColor = muls(ld3(lm->emissive), lm->emissive_intensity);
     return muls(mulv(lColor, diffuse), ndl);
+}
+static v3 direct_illumination_c(const orc_scene* s, v3 p, v3 n, v3 diffuse, rng_t* rng, uint32_t* ray, count_t* cc)
+{
+    return direct_illumination_impl(s, p, n, diffuse, rng, ray, cc, NULL, 0);
 }
 static v3 direct_illumination(const orc_scene* s, v3 p, v3 n, v3 diffuse, rng_t* rng, uint32_t* ray)
 {
@@ -500,8 +551,8 @@ typedef struct {
     int diffuse_bounce;  /* 1: DirectIllumimation is added (:638, :724) */
 } bounce_t;
 
-static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* depth_io, int* iter_io,
-                 int* inside_io, rng_t* rng, bounce_t* b)
+ORC_INLINE int shade_impl(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* depth_io, int* iter_io,
+                          int* inside_io, rng_t* rng, bounce_t* b, int64_t* cz)
 {
     int depth = *depth_io, iter = *iter_io, inside = *inside_io;
     const orc_material* mat = &s->mats[s->material[h->tri]];
@@ -510,6 +561,8 @@ static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* d
     get_uv(s, h->tri, h->u, h->v, &uvx, &uvy);
     const float* tb = s->tbn + (size_t)h->tri * 9;
     v3 n = ld3(tb);
+    ARM(cz, s->smoothing[h->tri] ? ORC_ARM_SMOOTHING_ON : ORC_ARM_SMOOTHING_OFF);
+    ARM(cz, mat->tex[1] >= 0 ? ORC_ARM_NORMAL_MAP_ON : ORC_ARM_NORMAL_MAP_OFF);
     if (s->smoothing[h->tri])                                             /* :556, :538-543 */
     {
         const float* nn = s->normals + (size_t)h->tri * 9;
@@ -520,9 +573,9 @@ static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* d
     if (mat->tex[1] >= 0)                                                 /* :558-566 */
     {
         float c[4];
-        tex2d(s, mat->tex[1], uvx, uvy, c);
+        tex2d_impl(s, mat->tex[1], uvx, uvy, c, cz, 1);
         v3 nt = V(c[0] * 2.0f - 1.0f, c[1] * 2.0f - 1.0f, c[2] * 2.0f - 1.0f);
-        if (nt.z <= 0.0f) nt = V(nt.x, nt.y, ORC_EPS);
+        if (nt.z <= 0.0f) { ARM(cz, ORC_ARM_NT_Z_CLAMPED); nt = V(nt.x, nt.y, ORC_EPS); }
         nt = normalize(nt);
         v3 tg = ld3(tb + 3), bt = ld3(tb + 6);
         v3 m = V(tg.x * nt.x + bt.x * nt.y + n.x * nt.z,
@@ -530,20 +583,30 @@ static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* d
                  tg.z * nt.x + bt.z * nt.y + n.z * nt.z);                  /* glm mat3*vec3 */
         n = normalize(m);
     }
-    if (dot(n, rd) > 0.0f) n = neg(n);                                    /* :567-568 */
+    if (dot(n, rd) > 0.0f) { ARM(cz, ORC_ARM_NORMAL_FLIPPED); n = neg(n); }   /* :567-568 */
     p = add(p, muls(n, ORC_EPS));                                          /* :569 */
 
-    if (!(iter < D)) return 0;                                            /* :571 */
+    if (!(iter < D)) { ARM(cz, ORC_ARM_TERMINAL); return 0; }             /* :571 */
 
     v3 diffuse = ld3(mat->diffuse);
     float c4[4];
-    if (mat->tex[0] >= 0) { tex2d(s, mat->tex[0], uvx, uvy, c4); diffuse = V(c4[0], c4[1], c4[2]); }
+    if (mat->tex[0] >= 0) { tex2d_impl(s, mat->tex[0], uvx, uvy, c4, cz, 0); diffuse = V(c4[0], c4[1], c4[2]); }
     v3 emiss = ld3(mat->emissive);
-    if (mat->tex[2] >= 0) { tex2d(s, mat->tex[2], uvx, uvy, c4); emiss = V(c4[0], c4[1], c4[2]); }
+    if (mat->tex[2] >= 0) { tex2d_impl(s, mat->tex[2], uvx, uvy, c4, cz, 2); emiss = V(c4[0], c4[1], c4[2]); }
     float roughness = mat->roughness;
-    if (mat->tex[3] >= 0) { tex2d(s, mat->tex[3], uvx, uvy, c4); roughness = c4[0]; }
+    if (mat->tex[3] >= 0)
+    {
+        tex2d_impl(s, mat->tex[3], uvx, uvy, c4, cz, 3); roughness = c4[0];
+        if (roughness == 1.0f) ARM(cz, ORC_ARM_ROUGHNESS_TEXEL_ONE);
+        if (roughness == 0.0f) ARM(cz, ORC_ARM_ROUGHNESS_TEXEL_ZERO);
+    }
     float reflectiveness = mat->reflectiveness;
-    if (mat->tex[4] >= 0) { tex2d(s, mat->tex[4], uvx, uvy, c4); reflectiveness = c4[0]; }
+    if (mat->tex[4] >= 0)
+    {
+        tex2d_impl(s, mat->tex[4], uvx, uvy, c4, cz, 4); reflectiveness = c4[0];
+        if (reflectiveness == 1.0f) ARM(cz, ORC_ARM_REFLECTIVENESS_TEXEL_ONE);
+        if (reflectiveness == 0.0f) ARM(cz, ORC_ARM_REFLECTIVENESS_TEXEL_ZERO);
+    }
 
     depth++; iter++;                                                      /* :586-587 */
     float mx = mat->diffuse[0] < mat->diffuse[1] ? mat->diffuse[1] : mat->diffuse[0];   /* glm::max */
@@ -551,7 +614,15 @@ static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* d
     float prob = 0.95f < mx ? 0.95f : mx;                                 /* glm::min(0.95f, mx) */
     if (depth >= D)
     {
-        if (fabsf(rnd(rng)) > prob) return 0;                             /* :590-594, no 1/prob */
+        const float rr = fabsf(rnd(rng));
+        if (cz)
+        {
+            cz[ORC_ARM_RR_ENGAGED]++;
+            cz[ORC_ARM_RR_CAP_ACTIVE] += 0.95f < mx;
+            if (rr > prob) cz[0.95f < rr && rr <= mx ? ORC_ARM_RR_KILLED_UNDER_THE_CAP_ONLY : ORC_ARM_RR_KILLED_OTHERWISE]++;
+            else cz[ORC_ARM_RR_SURVIVED]++;
+        }
+        if (rr > prob) return 0;                                          /* :590-594, no 1/prob */
     }
 
     v3 r = reflect(rd, n);                                                /* :596 */
@@ -563,16 +634,17 @@ static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* d
     {
         if (rnd(rng) < reflectiveness)                                    /* :601 */
         {
-            if (roughness == 1.0f) { float w = rnd(rng), th = rnd(rng); dir = sample_about(n, 1.0f - ORC_EPS, n, n, w, th); }
-            else if (roughness == 0.0f) dir = r;
-            else { float w = rnd(rng) * roughness, th = rnd(rng); dir = sample_about(n, 1.0f - ORC_FLT_EPSILON, r, r, w, th); }
+            if (roughness == 1.0f) { ARM(cz, ORC_ARM_OPAQUE_REFLECT_ROUGH_ONE); float w = rnd(rng), th = rnd(rng); dir = sample_about_impl(n, 1.0f - ORC_EPS, n, n, w, th, cz, 0); }
+            else if (roughness == 0.0f) { ARM(cz, ORC_ARM_OPAQUE_REFLECT_MIRROR); dir = r; }
+            else { ARM(cz, ORC_ARM_OPAQUE_REFLECT_LOBE); float w = rnd(rng) * roughness, th = rnd(rng); dir = sample_about_impl(n, 1.0f - ORC_FLT_EPSILON, r, r, w, th, cz, 1); }
             iter--;
             weight = ld3(mat->specular);                                  /* :626 */
         }
         else
         {
             float w = rnd(rng), th = rnd(rng);
-            dir = sample_about(n, 1.0f - ORC_EPS, n, n, w, th);           /* :631-636 */
+            ARM(cz, ORC_ARM_OPAQUE_DIFFUSE);
+            dir = sample_about_impl(n, 1.0f - ORC_EPS, n, n, w, th, cz, 2);   /* :631-636 */
             diffuse_bounce = 1;
             weight = diffuse;                                             /* :638 */
         }
@@ -581,10 +653,12 @@ static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* d
     {
         int refract = 0;
         v3 refractN = n;
+        ARM(cz, inside ? ORC_ARM_GLASS_ENTERED_INSIDE : ORC_ARM_GLASS_ENTERED_OUTSIDE);
         if (roughness != 0.0f)                                            /* :645-654 */
         {
             float w = rnd(rng) * roughness, th = rnd(rng);
-            refractN = sample_about(n, 1.0f - ORC_FLT_EPSILON, r, n, w, th);
+            ARM(cz, ORC_ARM_GLASS_ROUGH_NORMAL);
+            refractN = sample_about_impl(n, 1.0f - ORC_FLT_EPSILON, r, n, w, th, cz, 3);
         }
         float nc = 1.0f, ng = mat->ior;
         float eta = inside ? ng / nc : nc / ng;                           /* :658 */
@@ -592,24 +666,25 @@ static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* d
         r0 = r0 * r0;
         float c = fabsf(dot(rd, refractN));
         float k = 1.0f - eta * eta * (1.0f - c * c);
-        if (k < 0.0f) refract = 0;
+        if (k < 0.0f) { ARM(cz, ORC_ARM_GLASS_TIR); refract = 0; }
         else
         {
             float re = r0 + (1.0f - r0) * (1.0f - c) * (1.0f - c);        /* :668 (squared) */
-            if (fabsf(rnd(rng)) < re) refract = 0;
-            else if (rnd(rng) < reflectiveness) refract = 0;
+            if (fabsf(rnd(rng)) < re) { ARM(cz, ORC_ARM_GLASS_FRESNEL_REFLECT); refract = 0; }
+            else if (rnd(rng) < reflectiveness) { ARM(cz, ORC_ARM_GLASS_REFLECTIVENESS_REFLECT); refract = 0; }
             else refract = 1;
         }
         if (!refract)
         {
-            if (roughness == 1.0f) { float w = rnd(rng), th = rnd(rng); dir = sample_about(n, 1.0f - ORC_EPS, n, n, w, th); }
-            else if (roughness == 0.0f) dir = r;
-            else { float w = rnd(rng) * roughness, th = rnd(rng); dir = sample_about(n, 1.0f - ORC_FLT_EPSILON, r, r, w, th); }
+            if (roughness == 1.0f) { ARM(cz, ORC_ARM_GLASS_REFLECT_ROUGH_ONE); float w = rnd(rng), th = rnd(rng); dir = sample_about_impl(n, 1.0f - ORC_EPS, n, n, w, th, cz, 4); }
+            else if (roughness == 0.0f) { ARM(cz, ORC_ARM_GLASS_REFLECT_MIRROR); dir = r; }
+            else { ARM(cz, ORC_ARM_GLASS_REFLECT_LOBE); float w = rnd(rng) * roughness, th = rnd(rng); dir = sample_about_impl(n, 1.0f - ORC_FLT_EPSILON, r, r, w, th, cz, 5); }
             iter--;
             weight = ld3(mat->specular);                                  /* :702 */
         }
         else if (rnd(rng) < mat->translucency)                            /* :706 */
         {
+            ARM(cz, ORC_ARM_GLASS_REFRACT_TRANSMIT);
             float a = eta * dot(n, rd) + sqrtf(k);
             dir = normalize(sub(muls(rd, eta), muls(refractN, a)));       /* :708 */
             p = sub(p, muls(muls(n, ORC_EPS), 2.0f));                      /* :709 */
@@ -620,7 +695,8 @@ static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* d
         else
         {
             float w = rnd(rng), th = rnd(rng);
-            dir = sample_about(n, 1.0f - ORC_EPS, n, n, w, th);           /* :717-722 */
+            ARM(cz, ORC_ARM_GLASS_REFRACT_DIFFUSE);
+            dir = sample_about_impl(n, 1.0f - ORC_EPS, n, n, w, th, cz, 6);   /* :717-722 */
             diffuse_bounce = 1;
             weight = diffuse;                                             /* :724 */
         }
@@ -630,6 +706,12 @@ static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* d
     b->weight = weight; b->diffuse = diffuse; b->diffuse_bounce = diffuse_bounce;
     *depth_io = depth; *iter_io = iter; *inside_io = inside;
     return 1;
+}
+
+static int shade(const orc_scene* s, v3 ro, v3 rd, const hit_t* h, int D, int* depth_io, int* iter_io,
+                 int* inside_io, rng_t* rng, bounce_t* b)
+{
+    return shade_impl(s, ro, rd, h, D, depth_io, iter_io, inside_io, rng, b, NULL);
 }
 
 /* PathTracer::Trace pathtracer.cpp:545-732, ITERATIVE form: L += T*emission; L += T*direct; T *= weight.
@@ -684,6 +766,29 @@ static v3 trace_counted(const orc_scene* s, v3 ro, v3 rd, int D, rng_t* rng, cou
         ro = b.p; rd = b.dir;
     }
     cc->px[ORC_CNT_RAY_NUMBERS] += ray;
+    return L;
+}
+
+/* trace() with the census: the same calls in the same order, so the same radiance bit for bit */
+static v3 trace_census(const orc_scene* s, v3 ro, v3 rd, int D, rng_t* rng, int64_t* cz, int brute)
+{
+    v3 L = V(0.0f, 0.0f, 0.0f), T = V(1.0f, 1.0f, 1.0f);
+    int depth = 0, iter = 0, inside = 0;
+    uint32_t ray = 0;
+    for (;;)
+    {
+        hit_t h; bounce_t b;
+        if (!closest_hit_census(s, ro, rd, rng, ray++, &h, cz, brute)) break;
+        if (!shade_impl(s, ro, rd, &h, D, &depth, &iter, &inside, rng, &b, cz)) break;
+        L = add(L, mulv(T, b.e));
+        if (b.diffuse_bounce)
+        {
+            v3 di = direct_illumination_impl(s, b.p, b.n, b.diffuse, rng, &ray, NULL, cz, brute);
+            L = add(L, mulv(T, di));
+        }
+        T = mulv(T, b.weight);
+        ro = b.p; rd = b.dir;
+    }
     return L;
 }
 
@@ -956,6 +1061,99 @@ int orc_render_counted(const orc_scene* s, const orc_camera* cam, int W, int H, 
     }
     free(dirs_all);
     return overflow ? -1 : 0;
+}
+
+static const char* const orc_arm_names[ORC_ARM_N] = {
+#define TEX_NAMES(slot, name) \
+    [ORC_ARM_TEX + slot * ORC_TEX_ARMS + ORC_TEX_MISSING] = "tex2d." name ".missing_texture", \
+    [ORC_ARM_TEX + slot * ORC_TEX_ARMS + ORC_TEX_HI_X] = "tex2d." name ".upper_clamp_x", \
+    [ORC_ARM_TEX + slot * ORC_TEX_ARMS + ORC_TEX_HI_Y] = "tex2d." name ".upper_clamp_y", \
+    [ORC_ARM_TEX + slot * ORC_TEX_ARMS + ORC_TEX_LO_X] = "tex2d." name ".lower_clamp_x", \
+    [ORC_ARM_TEX + slot * ORC_TEX_ARMS + ORC_TEX_LO_Y] = "tex2d." name ".lower_clamp_y", \
+    [ORC_ARM_TEX + slot * ORC_TEX_ARMS + ORC_TEX_PLAIN] = "tex2d." name ".plain_fetch"
+    TEX_NAMES(0, "diffuse"), TEX_NAMES(1, "normal"), TEX_NAMES(2, "emissive"), TEX_NAMES(3, "roughness"), TEX_NAMES(4, "metallic"),
+    TEX_NAMES(5, "opacity"),
+#undef TEX_NAMES
+    [ORC_ARM_TRI_FARTHER] = "test_triangle.rejected_farther", [ORC_ARM_TRI_NEARER] = "test_triangle.accepted_nearer",
+    [ORC_ARM_TRI_TIE_ACCEPTED] = "test_triangle.tie_accepted_smaller_index",
+    [ORC_ARM_TRI_TIE_REJECTED] = "test_triangle.tie_rejected_larger_index",
+    [ORC_ARM_TRI_OPACITY_KEPT] = "test_triangle.opacity_draw_kept", [ORC_ARM_TRI_OPACITY_DROPPED] = "test_triangle.opacity_draw_dropped",
+    [ORC_ARM_WALK_STACK_FULL] = "closest_hit.stack_guard",
+    [ORC_ARM_SMOOTHING_ON] = "shade.smoothing_on", [ORC_ARM_SMOOTHING_OFF] = "shade.smoothing_off",
+    [ORC_ARM_NORMAL_MAP_ON] = "shade.normal_map_on", [ORC_ARM_NORMAL_MAP_OFF] = "shade.normal_map_off",
+    [ORC_ARM_NT_Z_CLAMPED] = "shade.nt_z_clamped", [ORC_ARM_NORMAL_FLIPPED] = "shade.normal_flipped",
+    [ORC_ARM_TERMINAL] = "shade.terminal", [ORC_ARM_RR_ENGAGED] = "shade.rr_engaged", [ORC_ARM_RR_CAP_ACTIVE] = "shade.rr_cap_active",
+    [ORC_ARM_RR_KILLED_UNDER_THE_CAP_ONLY] = "shade.rr_killed_between_cap_and_max",
+    [ORC_ARM_RR_KILLED_OTHERWISE] = "shade.rr_killed_otherwise", [ORC_ARM_RR_SURVIVED] = "shade.rr_survived",
+    [ORC_ARM_OPAQUE_REFLECT_ROUGH_ONE] = "shade.opaque.reflect_roughness_one", [ORC_ARM_OPAQUE_REFLECT_MIRROR] = "shade.opaque.reflect_roughness_zero",
+    [ORC_ARM_OPAQUE_REFLECT_LOBE] = "shade.opaque.reflect_lobe", [ORC_ARM_OPAQUE_DIFFUSE] = "shade.opaque.diffuse",
+    [ORC_ARM_GLASS_ENTERED_OUTSIDE] = "shade.glass.inside_0", [ORC_ARM_GLASS_ENTERED_INSIDE] = "shade.glass.inside_1",
+    [ORC_ARM_GLASS_ROUGH_NORMAL] = "shade.glass.roughness_nonzero", [ORC_ARM_GLASS_TIR] = "shade.glass.tir",
+    [ORC_ARM_GLASS_FRESNEL_REFLECT] = "shade.glass.fresnel_reflect", [ORC_ARM_GLASS_REFLECTIVENESS_REFLECT] = "shade.glass.reflectiveness_reflect",
+    [ORC_ARM_GLASS_REFLECT_ROUGH_ONE] = "shade.glass.reflect_roughness_one", [ORC_ARM_GLASS_REFLECT_MIRROR] = "shade.glass.reflect_roughness_zero",
+    [ORC_ARM_GLASS_REFLECT_LOBE] = "shade.glass.reflect_lobe",
+    [ORC_ARM_GLASS_REFRACT_TRANSMIT] = "shade.glass.refract_transmit", [ORC_ARM_GLASS_REFRACT_DIFFUSE] = "shade.glass.refract_diffuse",
+    [ORC_ARM_ROUGHNESS_TEXEL_ONE] = "shade.roughness_texel_one", [ORC_ARM_ROUGHNESS_TEXEL_ZERO] = "shade.roughness_texel_zero",
+    [ORC_ARM_REFLECTIVENESS_TEXEL_ZERO] = "shade.reflectiveness_texel_zero", [ORC_ARM_REFLECTIVENESS_TEXEL_ONE] = "shade.reflectiveness_texel_one",
+#define SA_NAMES(site, name) \
+    [ORC_ARM_SA + site * ORC_SA_CLASSES + ORC_SA_BELOW] = "sample_about." name ".below_1_minus_eps", \
+    [ORC_ARM_SA + site * ORC_SA_CLASSES + ORC_SA_BAND] = "sample_about." name ".in_the_band", \
+    [ORC_ARM_SA + site * ORC_SA_CLASSES + ORC_SA_POLE] = "sample_about." name ".at_or_above_1_minus_flt_epsilon"
+    SA_NAMES(0, "opaque_rough_one"), SA_NAMES(1, "opaque_lobe"), SA_NAMES(2, "opaque_diffuse"), SA_NAMES(3, "glass_refract_normal"),
+    SA_NAMES(4, "glass_rough_one"), SA_NAMES(5, "glass_lobe"), SA_NAMES(6, "glass_diffuse"),
+#undef SA_NAMES
+    [ORC_ARM_DI_NO_LIGHTS] = "direct.no_lights", [ORC_ARM_DI_LIGHT_ID_CLAMPED] = "direct.light_id_clamped",
+    [ORC_ARM_DI_NDL_NOT_POSITIVE] = "direct.ndl_not_positive", [ORC_ARM_DI_SHADOW_MISSED] = "direct.shadow_ray_missed_everything",
+    [ORC_ARM_DI_HIT_LIGHT] = "direct.shadow_ray_hit_its_light", [ORC_ARM_DI_HIT_OTHER] = "direct.shadow_ray_hit_something_else",
+};
+int orc_arm_count(void) { return ORC_ARM_N; }
+const char* orc_arm_name(int arm) { return arm >= 0 && arm < ORC_ARM_N ? orc_arm_names[arm] : NULL; }
+
+void orc_render_census(const orc_scene* s, const orc_camera* cam, int W, int H, int D, uint32_t first_sample, uint32_t spp,
+                       uint64_t seed, int brute, float* total, int64_t* arms, int threads)
+{
+    frame_t f; frame_setup(cam, W, H, &f);
+#ifdef _OPENMP
+    if (threads <= 0) threads = omp_get_max_threads();
+#endif
+    float* dirs_all = (float*)malloc((size_t)W * H * 3 * sizeof(float));
+    for (int i = 0; i < H; i++) primary_row(&f, W, i, dirs_all + (size_t)i * W * 3);
+    memset(arms, 0, ORC_ARM_N * sizeof(int64_t));
+    /* a row's arms are counted by the one thread that traces it and added under a lock: sums, so no thread count shows */
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
+#endif
+    for (int i = 0; i < H; i++)
+    {
+        int64_t row[ORC_ARM_N];
+        memset(row, 0, sizeof row);
+        for (int j = 0; j < W; j++)
+        {
+            const size_t pix = (size_t)i * W + j;
+            uint32_t pkey = pixel_key(seed, (uint32_t)pix);
+            size_t px = ((size_t)(H - 1 - i) * W + j) * 3;
+            v3 acc = total ? ld3(total + px) : V(0.0f, 0.0f, 0.0f);
+            v3 rayDir0 = ld3(dirs_all + pix * 3);
+            for (uint32_t k = 0; k < spp; k++)
+            {
+                rng_t rng; rng_init(&rng, pkey, first_sample + k);
+                v3 camPos = f.pos;
+                v3 focalPoint = add(camPos, muls(rayDir0, cam->focal_dist));
+                float r1 = rnd(&rng), r2 = rnd(&rng), off[2];
+                orc_sample_circle(r1, r2, off);
+                off[0] = off[0] * cam->aperture; off[1] = off[1] * cam->aperture;
+                camPos = add(camPos, add(muls(f.right, off[0]), muls(f.up, off[1])));
+                v3 rayDir = normalize(sub(focalPoint, camPos));
+                acc = add(acc, trace_census(s, camPos, rayDir, D, &rng, row, brute));
+            }
+            if (total) { total[px] = acc.x; total[px + 1] = acc.y; total[px + 2] = acc.z; }
+        }
+#ifdef _OPENMP
+#pragma omp critical(orc_census)
+#endif
+        for (int a = 0; a < ORC_ARM_N; a++) arms[a] += row[a];
+    }
+    free(dirs_all);
 }
 
 /* RenderFrame (pathtracer.cpp:741-817) for ONE frame with the draws of the reference's single engine on tape, in the order its

@@ -112,6 +112,35 @@ typedef struct {
 int orc_render_counted(const orc_scene* s, const orc_camera* cam, int width, int height, int max_depth,
                        uint32_t first_sample, uint32_t spp, uint64_t seed, int rank, int world,
                        float* total, int64_t* counts, orc_ray_rec* rec, const int64_t* rec_offsets, int64_t rec_capacity, int threads);
+
+/* orc_render that takes a CENSUS of the named arms of tex2d, test_triangle, closest_hit, shade, sample_about and
+ * direct_illumination: arms[ORC_ARM_N], summed over the frame; orc_arm_name(i) names arm i.  Value classes that decide which code
+ * runs are arms too (the class of |n.x| at each sampler site, texels that are exactly 0 or 1).  brute != 0: candidates in
+ * ascending index order (the FLAT and PLAIN passes' order, which decides which tie arm a tie takes); 0: the oracle's tree walk.
+ * total (may be NULL) is accumulated as orc_render does, bit for bit.  The result does not depend on the thread count. */
+enum { ORC_TEX_MISSING = 0, ORC_TEX_HI_X, ORC_TEX_HI_Y, ORC_TEX_LO_X, ORC_TEX_LO_Y, ORC_TEX_PLAIN, ORC_TEX_ARMS };
+enum { ORC_SA_BELOW = 0, ORC_SA_BAND, ORC_SA_POLE, ORC_SA_CLASSES };
+enum {
+    ORC_ARM_TEX = 0,                                    /* + slot * ORC_TEX_ARMS + ORC_TEX_*; slots as orc_material.tex */
+    ORC_ARM_TRI_FARTHER = ORC_ARM_TEX + 6 * ORC_TEX_ARMS, ORC_ARM_TRI_NEARER, ORC_ARM_TRI_TIE_ACCEPTED, ORC_ARM_TRI_TIE_REJECTED,
+    ORC_ARM_TRI_OPACITY_KEPT, ORC_ARM_TRI_OPACITY_DROPPED, ORC_ARM_WALK_STACK_FULL,
+    ORC_ARM_SMOOTHING_ON, ORC_ARM_SMOOTHING_OFF, ORC_ARM_NORMAL_MAP_ON, ORC_ARM_NORMAL_MAP_OFF, ORC_ARM_NT_Z_CLAMPED,
+    ORC_ARM_NORMAL_FLIPPED, ORC_ARM_TERMINAL, ORC_ARM_RR_ENGAGED, ORC_ARM_RR_CAP_ACTIVE, ORC_ARM_RR_KILLED_UNDER_THE_CAP_ONLY,
+    ORC_ARM_RR_KILLED_OTHERWISE, ORC_ARM_RR_SURVIVED,
+    ORC_ARM_OPAQUE_REFLECT_ROUGH_ONE, ORC_ARM_OPAQUE_REFLECT_MIRROR, ORC_ARM_OPAQUE_REFLECT_LOBE, ORC_ARM_OPAQUE_DIFFUSE,
+    ORC_ARM_GLASS_ENTERED_OUTSIDE, ORC_ARM_GLASS_ENTERED_INSIDE, ORC_ARM_GLASS_ROUGH_NORMAL, ORC_ARM_GLASS_TIR,
+    ORC_ARM_GLASS_FRESNEL_REFLECT, ORC_ARM_GLASS_REFLECTIVENESS_REFLECT, ORC_ARM_GLASS_REFLECT_ROUGH_ONE, ORC_ARM_GLASS_REFLECT_MIRROR,
+    ORC_ARM_GLASS_REFLECT_LOBE, ORC_ARM_GLASS_REFRACT_TRANSMIT, ORC_ARM_GLASS_REFRACT_DIFFUSE,
+    ORC_ARM_ROUGHNESS_TEXEL_ONE, ORC_ARM_ROUGHNESS_TEXEL_ZERO, ORC_ARM_REFLECTIVENESS_TEXEL_ZERO, ORC_ARM_REFLECTIVENESS_TEXEL_ONE,
+    ORC_ARM_SA,                                         /* + site * ORC_SA_CLASSES + ORC_SA_*; sites in shade()'s order */
+    ORC_ARM_DI_NO_LIGHTS = ORC_ARM_SA + 7 * ORC_SA_CLASSES, ORC_ARM_DI_LIGHT_ID_CLAMPED, ORC_ARM_DI_NDL_NOT_POSITIVE,
+    ORC_ARM_DI_SHADOW_MISSED, ORC_ARM_DI_HIT_LIGHT, ORC_ARM_DI_HIT_OTHER,
+    ORC_ARM_N
+};
+int orc_arm_count(void);
+const char* orc_arm_name(int arm);
+void orc_render_census(const orc_scene* s, const orc_camera* cam, int width, int height, int max_depth,
+                       uint32_t first_sample, uint32_t spp, uint64_t seed, int brute, float* total, int64_t* arms, int threads);
 /* Moeller-Trumbore of orc_intersect_triangle on n (ray, triangle) pairs: ro, rd [n][3], tri9 [n][9] -> out3 [n][3] */
 void orc_intersect_many(int64_t n, const float* ro, const float* rd, const float* tri9, float* out3);
 
