@@ -214,6 +214,11 @@ public:
                        float* bary, int32_t* material);
     bool OccludedRays(int num_rays, const float* origins, const float* dirs, const float* tmax, uint32_t sample, uint32_t key_base,
                       uint8_t* occluded);
+    // Extension: closest-point queries (include/ptk.h ptk_closest_points, host arrays, synchronous): for each of the points the
+    // nearest point of the scene's surface strictly nearer than max_dist[i] (null: no bound).  tri, dist, point (3 per point) and
+    // bary (2 per point) may each be null, not all four.  A geometric query: seed and materials take no part.  Valid after
+    // BuildBVH() with no resolution set; pending geometry edits apply as for TraceRays; the image and the sample count are not touched.
+    bool ClosestPoints(int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point, float* bary);
     // Extensions: lightmap baking (include/ptk.h ptk_bake_lightmap / ptk_bake_coverage / ptk_lightmap_dilate, host arrays,
     // synchronous) at the class's seed and trace depth.  uvs: [triangles][6] chart corners, or null for the scene's own uvs;
     // out: width*height*3 floats, rows bottom-up; owner (may be null): width*height triangle indices, -1 uncovered;

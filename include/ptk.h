@@ -400,6 +400,62 @@ int ptk_occluded_rays_device(ptk_ctx* ctx, int32_t num_rays, const float* d_orig
  * (0 where the call launched none); waits for the call */
 int ptk_last_hits_ms(ptk_ctx* ctx, float* ms);
 
+/* ---- closest-point queries: the nearest point of the scene's surface to caller-supplied points (no counterpart in the reference) --
+ * "How far is this point from the nearest surface, and where is that surface": probe clearance and relocation, the choice of
+ * offsets, radii and biases from the scene, distance fields.  A geometric query: opacity maps, materials, seeds and keys take no
+ * part and no random draw is consumed.  For the uploaded scene and num_points points p = points[i]:
+ * THE RULE.  Every operation below is one IEEE float32 operation, in the order written (the kernel exists once, in the exact
+ * arithmetic); dot(a, b) = ((ax*bx) + (ay*by)) + (az*bz); x > y ? x : y with a NaN operand yields the second value.
+ * Triangle k is (a, e1, e2) exactly as its intersection record holds it: a = its first vertex, e1 = v2 - v1 and e2 = v3 - v1 the
+ * record packers' own float32 subtractions, kept current by ptk_update_geometry.  Nothing else of the triangle is used.
+ *   ap = p - a;   bp = ap - e1;   cp = ap - e2
+ *   d1 = dot(e1, ap); d2 = dot(e2, ap); d3 = dot(e1, bp); d4 = dot(e2, bp); d5 = dot(e1, cp); d6 = dot(e2, cp)
+ *   vc = (d1*d4) - (d3*d2);  vb = (d5*d2) - (d1*d6);  va = (d3*d6) - (d5*d4);  e43 = d4 - d3;  e56 = d5 - d6
+ *   the first that holds, in this order:
+ *     d1 <= 0 && d2 <= 0                     (v, w) = (0, 0)                                   region 0, vertex 1
+ *     d3 >= 0 && d4 <= d3                    (v, w) = (1, 0)                                   region 1, vertex 2
+ *     vc <= 0 && d1 >= 0 && d3 <= 0          (v, w) = (d1 / (d1 - d3), 0)                      region 3, edge 1-2
+ *     d6 >= 0 && d5 <= d6                    (v, w) = (0, 1)                                   region 2, vertex 3
+ *     vb <= 0 && d2 >= 0 && d6 <= 0          (v, w) = (0, d2 / (d2 - d6))                      region 4, edge 1-3
+ *     va <= 0 && e43 >= 0 && e56 >= 0        w = e43 / (e43 + e56); v = 1 - w                  region 5, edge 2-3
+ *     otherwise                              den = (va + vb) + vc; v = vb / den; w = vc / den  region 7, face
+ *   then, always:  v = v > 0 ? v : 0;  v = v < 1 ? v : 1;  w = w > 0 ? w : 0;  top = 1 - v;  w = w < top ? w : top   (NaN becomes 0)
+ *   q = (a + (e1 * v)) + (e2 * w) per component;   d = p - q;   d2k = dot(d, d)
+ * The final clamp is part of the rule: it makes q a point of the triangle, up to rounding, for every finite triangle - degenerate
+ * ones (two or three equal vertices, collinear vertices) included - so d2k never undercuts the distance to the triangle's box by
+ * more than a bounded rounding error, which is what lets the walk prune and keeps the answer independent of the tree.
+ * THE ANSWER.  Triangle k is ACCEPTED for point i when d2k < r2_i, STRICTLY, with r2_i = max_dist[i] * max_dist[i]; max_dist == NULL
+ * stands for +inf for every point; a max_dist[i] that is NaN, zero or negative accepts nothing; a d2k that is not finite is never
+ * accepted.  The answer is the accepted triangle of smallest d2k, ties going to the smaller triangle index.  Outputs, each of which
+ * may be NULL but not all four: tri[n] (-1 on a miss), dist[n] = the correctly rounded square root of d2k (+inf on a miss),
+ * point[n][3] = q (0 on a miss), bary[n][2] = v, w (0 on a miss) - the weights of vertex 2 and vertex 3, as ptk_intersect_rays' bary.
+ * The result does not depend on the builder that made the tree, on "bvh_leaf_max", on a refit, on "flat" (the call always walks
+ * the BVH), on ptk_set_tile or on "contract", nor on how a point set is cut into calls (tests/test_gpu_closest.py: array_equal
+ * with tests/closest_rule.py).  A non-finite coordinate makes THAT point's output unspecified and affects neither another point
+ * nor whether the call ends.
+ * The calls need a scene only - no camera, no frame - and read it as ptk_update_materials / ptk_update_geometry left it.  They
+ * touch no frame, adaptive, feature or bake state, stay legal after ptk_render_adaptive, and ptk_request_exit does not cut them.
+ *   ptk_closest_points: host arrays, synchronous; 12 B per point plus max_dist and the requested outputs are staged in device
+ *     memory for the length of the call.
+ *   ptk_closest_points_device: every array in memory of this context's GPU, asynchronous on the context's stream (the caller's
+ *     after ptk_set_stream).  No host wait and no allocation of device memory inside the call.  The arrays must stay allocated
+ *     until the stream has passed the call.
+ * PTK_ERR_BAD_ARG: a null context, a call before ptk_upload_scene, num_points < 0, a null points with num_points > 0, all four
+ * outputs NULL; a refused call leaves the outputs alone.  num_points == 0 is PTK_OK and does nothing.  A scene without triangles
+ * gives misses.  PTK_ERR_LIMIT as for ptk_trace_rays.  Limits: one workgroup per 64 points, in one launch. */
+int ptk_closest_points(ptk_ctx* ctx, int32_t num_points, const float* points /*[n][3]*/, const float* max_dist /*[n] or NULL*/,
+                       int32_t* tri /*[n]*/, float* dist /*[n]*/, float* point /*[n][3]*/, float* bary /*[n][2]*/);
+int ptk_closest_points_device(ptk_ctx* ctx, int32_t num_points, const float* d_points, const float* d_max_dist, int32_t* d_tri,
+                              float* d_dist, float* d_point, float* d_bary);
+/* measurement hooks (tools/closest_timing.py), not part of the feature.  The HIP-event time of the last closest-point query's
+ * kernel (0 where the call launched none); waits for the call */
+int ptk_last_closest_ms(ptk_ctx* ctx, float* ms);
+/* ... and the work of a query: the counting variant of the kernel over points and radii in this GPU's memory, no outputs written;
+ * node_visits / tri_tests = interior nodes fetched / triangle records tested, summed over the points.  Synchronous; allocates 16 B
+ * of device memory at its first call */
+int ptk_closest_stats(ptk_ctx* ctx, int32_t num_points, const float* d_points, const float* d_max_dist, uint64_t* node_visits,
+                      uint64_t* tri_tests);
+
 /* ---- lightmap baking: the radiance leaving the scene's surfaces, per texel of a uv chart layout (no counterpart in the reference) --
  * The surface half of light baking in front of and behind ptk_trace_rays' kernel: a uv rasteriser, a ray generator, a scatter and
  * a chart-padding pass, all on the GPU from what ptk_upload_scene left resident.  Inputs: the uploaded scene, a lightmap of

@@ -906,6 +906,17 @@ bool PathTracer::OccludedRays(int num_rays, const float* origins, const float* d
     return rc == PTK_OK;
 }
 
+// The nearest surface point to caller-supplied points (ptk_closest_points) in the scene as the next RenderFrame() would see it
+bool PathTracer::ClosestPoints(int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point, float* bary)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_closest_points(m->ctx, num_points, points, max_dist, tri, dist, point, bary);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 // Lightmap baking (ptk_bake_lightmap, ptk_bake_coverage, ptk_lightmap_dilate) of the scene as the next RenderFrame() would see it
 bool PathTracer::BakeLightmap(int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp, uint32_t key_base,
                               uint32_t flags, float* out, int32_t* owner)

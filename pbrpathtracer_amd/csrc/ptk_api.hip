@@ -591,6 +591,8 @@ void ptk_destroy(ptk_ctx* c)
     for (hipEvent_t e : c->ev_probe_vis_blocks) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_rays) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_hits) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_closest) if (e) (void)hipEventDestroy(e);
+    dfree(c->d_closest_stats);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
     if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);

@@ -184,6 +184,12 @@ struct ptk_ctx {
     hipEvent_t ev_hits[2] = { nullptr, nullptr };
     bool hits_timed = false;
 
+    // closest-point queries (ptk_closest_points): two events around the last call's kernel, made by the first call; the two
+    // counters of ptk_closest_stats, made by its first call
+    hipEvent_t ev_closest[2] = { nullptr, nullptr };
+    bool closest_timed = false;
+    unsigned long long* d_closest_stats = nullptr;
+
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
     // overlaps the tail of pass k's (a launch ends with the few waves that hold its longest paths - Russian roulette

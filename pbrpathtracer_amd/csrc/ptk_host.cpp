@@ -128,6 +128,10 @@ int pth_occluded_rays(pth_tracer* t, int num_rays, const float* origins, const f
 {
     return t->pt.OccludedRays(num_rays, origins, dirs, tmax, sample, key_base, occluded) ? 1 : 0;
 }
+int pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point, float* bary)
+{
+    return t->pt.ClosestPoints(num_points, points, max_dist, tri, dist, point, bary) ? 1 : 0;
+}
 int pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,
                       uint32_t key_base, uint32_t flags, float* out, int32_t* owner)
 {

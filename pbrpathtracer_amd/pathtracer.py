@@ -38,7 +38,7 @@ HOST_SYMBOLS = [
     "pth_render_features", "pth_read_feature", "pth_pick", "pth_set_object_transform", "pth_trace_rays", "pth_get_camera",
     "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
-    "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays",
+    "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points",
 ]
 
 _bound = False
@@ -112,6 +112,7 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_bake_lightmap_adaptive.argtypes = [vp, i32, i32, vp, f32, f32, u32, u32, u32, u32, u32, vp, vp, vp, res]
         L.pth_intersect_rays.restype = i32; L.pth_intersect_rays.argtypes = [vp, i32, vp, vp, u32, u32, vp, vp, vp, vp]
         L.pth_occluded_rays.restype = i32; L.pth_occluded_rays.argtypes = [vp, i32, vp, vp, vp, u32, u32, vp]
+        L.pth_closest_points.restype = i32; L.pth_closest_points.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -356,6 +357,22 @@ class PathTracer:
                                         int(key_base) & 0xffffffff, out.ctypes.data):
             raise _ptk.PtkError("OccludedRays failed: " + self.LastError())
         return out
+
+    def closest_points(self, points, max_dist=None):
+        """Extension: the nearest surface point to each of the points [n, 3] (include/ptk.h ptk_closest_points), strictly nearer
+        than max_dist[i] where max_dist is given; (tri [n] int32, dist [n] float32, point [n, 3] float32, bary [n, 2] float32),
+        misses -1 / inf / 0 / 0.  Pending geometry edits apply as for RenderFrame()."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        md = None if max_dist is None else np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
+        assert md is None or len(md) == n, "one max_dist per point"
+        out = (np.empty(n, np.int32), np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 2), np.float32))
+        if n and not self.L.pth_closest_points(self.h, n, p.ctypes.data, md.ctypes.data if md is not None else None,
+                                               *(a.ctypes.data for a in out)):
+            raise _ptk.PtkError("ClosestPoints failed: " + self.LastError())
+        return out
+
+    ClosestPoints = closest_points
 
     def _chart_uvs(self, uvs):
         if uvs is None:

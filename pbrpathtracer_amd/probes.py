@@ -63,3 +63,29 @@ def grid_over_bounds(lo, hi, dims):
         else:
             origin[a], spacing[a] = (0.5 * (lo[a] + hi[a]) if n == 1 else lo[a]), 1.0
     return origin, spacing
+
+
+def clearance(ctx, positions):
+    """(dist [n] float32, point [n, 3] float32, tri [n] int32) of Context.closest_points(positions) (include/ptk.h
+    ptk_closest_points): how far each probe lies from the nearest surface, where that surface is and which triangle it belongs to
+    (inf, 0, -1 in a scene without triangles).  numpy positions, numpy results."""
+    tri, dist, point, _ = ctx.closest_points(np.ascontiguousarray(positions, np.float32).reshape(-1, 3))
+    return dist, point, tri
+
+
+def relocate(ctx, positions, min_dist):
+    """(new positions [n, 3] float32, moved [n] bool): probes nearer to a surface than min_dist pushed away from it, straight along
+    the line from the nearest surface point through the probe, until they lie min_dist from that point.  One query with max_dist =
+    min_dist; a probe with a hit and dist > 0 moves to point + (p - point) * (min_dist / dist), in float32 in that order; a probe
+    with a miss (far enough already), or with dist == 0 (on the surface: no direction to go), stays bit for bit.  ONE step: in a
+    corner the move away from one wall may end nearer than min_dist to another, so a caller who needs the clearance iterates until
+    nothing moves."""
+    p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    md = np.float32(min_dist)
+    tri, dist, point, _ = ctx.closest_points(p, np.full(len(p), md, np.float32))
+    moved = (tri >= 0) & (dist > 0)
+    new = p.copy()
+    with np.errstate(all="ignore"):
+        scale = (md / dist[moved]).astype(np.float32)
+    new[moved] = point[moved] + (p[moved] - point[moved]) * scale[:, None]
+    return new, moved

@@ -92,6 +92,7 @@ SYMBOLS = [
     "ptk_update_geometry", "ptk_update_geometry_device", "ptk_geometry_info", "ptk_geometry_timing",
     "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
     "ptk_intersect_rays", "ptk_intersect_rays_device", "ptk_occluded_rays", "ptk_occluded_rays_device", "ptk_last_hits_ms",
+    "ptk_closest_points", "ptk_closest_points_device", "ptk_last_closest_ms", "ptk_closest_stats",
     "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
     "ptk_last_bake_ms",
     "ptk_trace_rays_adaptive", "ptk_trace_rays_adaptive_device", "ptk_bake_lightmap_adaptive", "ptk_bake_lightmap_adaptive_device",
@@ -203,6 +204,10 @@ def _load_locked() -> C.CDLL:
         for fn in (L.ptk_occluded_rays, L.ptk_occluded_rays_device):
             fn.argtypes = [vp, C.c_int32, vp, vp, vp, u32, u64, u32, vp]
         L.ptk_last_hits_ms.argtypes = [vp, fp]
+        for fn in (L.ptk_closest_points, L.ptk_closest_points_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
+        L.ptk_last_closest_ms.argtypes = [vp, fp]
+        L.ptk_closest_stats.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -533,6 +538,59 @@ class Context:
         t = C.c_float(0)
         self._chk(self.L.ptk_last_hits_ms(self.h, C.byref(t)), "ptk_last_hits_ms")
         return t.value
+
+    # ---- closest-point queries --------------------------------------------------------------
+    def closest_points(self, points, max_dist=None):
+        """ptk_closest_points: for each of the points [n, 3] float32 the nearest point of the scene's surface, under the rule of
+        include/ptk.h.  max_dist: [n] float32 of the points' kind - only surface strictly nearer counts; NaN, zero or negative finds
+        nothing - or None for no bound.  Returns (tri [n] int32, -1 on a miss; dist [n] float32, inf on a miss; point [n, 3]
+        float32, 0 on a miss; bary [n, 2] float32 = the weights of vertex 2 and vertex 3, 0 on a miss).  numpy arrays go through
+        the host entry (synchronous) and give numpy arrays; torch tensors on the context's GPU go through
+        ptk_closest_points_device with no host copy and give torch tensors written on the context's stream (see trace_rays)."""
+        if hasattr(points, "data_ptr"):
+            import torch
+            n = points.numel() // 3
+            mk = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=points.device)
+            out = (mk((n,), torch.int32), mk((n,), torch.float32), mk((n, 3), torch.float32), mk((n, 2), torch.float32))
+            self._ray_tensors((points,), n, ((torch.float32, 3),))
+            if max_dist is not None:
+                self._ray_tensors((max_dist,), n, ((torch.float32, 1),))
+            if n:
+                self._chk(self.L.ptk_closest_points_device(self.h, n, C.c_void_p(points.data_ptr()),
+                                                           C.c_void_p(max_dist.data_ptr()) if max_dist is not None else None,
+                                                           *(C.c_void_p(t.data_ptr()) for t in out)), "ptk_closest_points_device")
+            return out
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        md = None
+        if max_dist is not None:
+            md = np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
+            assert len(md) == n, "one max_dist per point"
+        out = (np.empty(n, np.int32), np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 2), np.float32))
+        if n:
+            self._chk(self.L.ptk_closest_points(self.h, n, p.ctypes.data, md.ctypes.data if md is not None else None,
+                                                *(a.ctypes.data for a in out)), "ptk_closest_points")
+        return out
+
+    def last_closest_ms(self) -> float:
+        """HIP-event time of the last closest_points call's kernel; waits for it."""
+        t = C.c_float(0)
+        self._chk(self.L.ptk_last_closest_ms(self.h, C.byref(t)), "ptk_last_closest_ms")
+        return t.value
+
+    def closest_stats(self, points, max_dist=None):
+        """ptk_closest_stats (measurement hook): (interior nodes fetched, triangle records tested) by a closest_points query of
+        these torch tensors on the context's GPU, summed over the points; synchronous, writes no outputs."""
+        import torch
+        n = points.numel() // 3
+        self._ray_tensors((points,), n, ((torch.float32, 3),))
+        if max_dist is not None:
+            self._ray_tensors((max_dist,), n, ((torch.float32, 1),))
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.L.ptk_closest_stats(self.h, n, C.c_void_p(points.data_ptr()) if n else None,
+                                           C.c_void_p(max_dist.data_ptr()) if max_dist is not None else None, C.byref(a), C.byref(b)),
+                  "ptk_closest_stats")
+        return a.value, b.value
 
     # ---- lightmap baking -------------------------------------------------------------------
     def _bake_uvs(self, uvs, torch_side: bool):
