@@ -25,6 +25,7 @@ struct ptk_ctx;
 struct ptk_scene_desc;
 struct ptk_adaptive_result;
 struct ptk_rays_adaptive_result;
+struct ptk_denoise_params;
 
 const float EPS = 0.00001f;      // mesh.h:12
 const float INF = (float)0xFFFF; // mesh.h:13
@@ -195,6 +196,16 @@ public:
     bool RenderFeatures(uint32_t mask, uint32_t sample = 0);
     // one plane of the last RenderFeatures(): W*H*channels elements of 4 bytes (ptk_feature_info), rows bottom-up
     bool ReadFeature(int feature, void* out);
+    // Extensions: the a-trous denoiser over the frame as last rendered (include/ptk.h ptk_denoise_frame; variance: the
+    // variance-guided mode, legal after RenderAdaptive()).  A convenience over the C-ABI call: the five guide planes (TRIANGLE,
+    // POSITION, NORMAL, ALBEDO, EMISSION) are rendered first - sample 0 of the class's seed, replacing the planes of an earlier
+    // RenderFeatures() - when they are missing or older than the last scene, camera, resolution or seed change a render call
+    // applied.  Pending edits are NOT applied: the accumulator does not hold them either.  The image, the sample count and the
+    // hand-off buffer are not touched.  ReadDenoised: W*H*3 floats, rows bottom-up; ResolveDenoised: W*H*3 bytes, the layout of
+    // the out image.
+    bool DenoiseFrame(const ptk_denoise_params& params, bool variance = false);
+    bool ReadDenoised(float* out);
+    bool ResolveDenoised(GLubyte* out);
     // The (object, element) under pixel (x, y), y counted from the top row: one ray (ptk_pick), pending edits applied first.
     // A pixel that sees nothing gives -1 / -1 (and triangle -1) and true; false: no scene / resolution yet, or (x, y) outside the frame.
     bool Pick(int x, int y, int* objId, int* elementId, int* triangle = nullptr);

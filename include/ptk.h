@@ -456,6 +456,94 @@ int ptk_last_closest_ms(ptk_ctx* ctx, float* ms);
 int ptk_closest_stats(ptk_ctx* ctx, int32_t num_points, const float* d_points, const float* d_max_dist, uint64_t* node_visits,
                       uint64_t* tri_tests);
 
+/* ---- a-trous denoiser for image planes and for the frame (no counterpart in the reference) ------------------------------------
+ * Turns a noisy low-sample image - a frame of a few samples per pixel, a lightmap of 16 to 64 per texel - into a usable one: an
+ * edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by normals, positions and luminance, optionally by the
+ * variance of each pixel's value (the edge-stopping idea of SVGF, Schied et al. 2017), on demodulated colour.
+ * THE RULE.  Every operation below is one IEEE float32 operation, in the order written (the kernels are compiled with
+ * -ffp-contract=off); dot(a, b) = ((ax*bx) + (ay*by)) + (az*bz); x > y ? x : y with a NaN operand yields the second value.  The rule
+ * uses + - * /, comparisons and repeated squaring only - no exp, pow or log - so a numpy restatement gives the same bits
+ * (tests/denoise_rule.py; tests/test_gpu_denoise.py: array_equal).  Edge-stopping weights are rational, 1 / (1 + x^2).
+ * PLANES, each [H][W] or [H][W][3] float32 with rows as stored - the rule never flips:
+ *   color[3]     the image                        mask      int32: a pixel is VALID iff mask >= 0 (a TRIANGLE feature plane or a
+ *   normal[3]    guide normal                               lightmap's owner plane can be passed as it is)
+ *   position[3]  guide position                   albedo[3]   optional: demodulation
+ *                                                 variance[1] optional: variance of the pixel's (demodulated) value
+ * PARAMETERS: ptk_denoise_params below.
+ * BEFORE THE FIRST ITERATION, for valid pixels with an albedo plane: A_c = albedo_c + 0.00390625f; c_c = color_c / A_c.  Without an
+ * albedo plane c = color.  inv_z = 1.0f / sigma_z.
+ * ITERATION k = 0 .. iterations-1, tap spacing s = 1 << k, reads only the output of iteration k-1.  For every valid pixel p = (x, y):
+ *   L(c) = ((0.2126f*c_r) + (0.7152f*c_g)) + (0.0722f*c_b)
+ *   den  = variance given ? ((sigma_l*sigma_l) * var_p) + 1e-10f  :  sk*sk with sk = sigma_l * (float)2^-k   (an exact scaling)
+ *   iden = 1.0f / den;   sc = (0, 0, 0); sw = 0; sv = 0;   h = (0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f)
+ *   for j = 0..4 (dy = (j-2)*s) outer, i = 0..4 (dx = (i-2)*s) inner, q = (x+dx, y+dy):
+ *     skip q when it lies outside the image or is invalid
+ *     q == p:  w = 0.140625f
+ *     else:    cn = dot(n_p, n_q);  cn = cn > 0 ? cn : 0;  then normal_squarings times cn = cn*cn
+ *              d = pos_q - pos_p;  z = dot(n_p, d) * inv_z;  a = 1.0f + (z*z)
+ *              dl = L(c_p) - L(c_q);  b = 1.0f + ((dl*dl) * iden)
+ *              w = ((h[j]*h[i]) * cn) / (a*b)
+ *     skip the tap unless w > 0   (a zero or NaN weight adds nothing)
+ *     sc_c = sc_c + (w * c_q,c);  sw = sw + w;  sv = sv + ((w*w) * var_q)   (sv only with a variance plane)
+ *   out_c = sc_c / sw;  var_out = sv / (sw*sw)
+ * One division per tap and four or five per pixel (iden, the channels, the variance); sw >= 0.140625 always, the centre tap being always taken.  INVALID pixels are copied
+ * through every iteration, colour and variance alike, and are never a tap: what they hold - NaN, 1e30 - reaches no other pixel.
+ * AFTER THE LAST ITERATION valid pixels with an albedo plane get out_c = c_c * A_c; invalid pixels get out = color, the input bits
+ * (and out_variance = variance, the input bits).
+ * Deliberately left out: exp-shaped weights (not the same bits on the GPU and in numpy), SVGF's 3x3 prefilter of the variance,
+ * temporal reprojection and accumulation, bilinear filtering of the guides.
+ *   ptk_denoise_planes: host arrays, synchronous; the planes and the requested outputs are staged in device memory for the length
+ *     of the call.  albedo, variance and out_variance may be NULL; out_variance needs variance.
+ *   ptk_denoise_planes_device: every array in memory of this context's GPU, asynchronous on the context's stream (the caller's
+ *     after ptk_set_stream), no host wait - except that the context's 64 B per pixel of packed images grow, behind a drain of the
+ *     stream, when a call is larger than every one before it.  The arrays must stay allocated until the stream has passed the call.
+ * Both need no scene, no camera and no frame; out_color may not alias an input; "contract", "flat" and ptk_set_tile do not reach
+ * them, and ptk_request_exit does not cut them.
+ *   ptk_denoise_frame: the context's frame, asynchronous on the context's stream.  Per pixel (rows bottom-up like everything of the
+ *     frame) n_p = its count after ptk_render_adaptive, else ptk_samples on the pixels this rank owns and 0 on the others;
+ *     color_c = S1_c / (float)n_p from the accumulator (the bound one after ptk_bind_accum), 0 where n_p = 0; the guides are the
+ *     context's feature planes NORMAL, POSITION and ALBEDO; a pixel is valid iff n_p > 0, TRIANGLE >= 0 and all three channels of
+ *     EMISSION equal 0 (a light seen directly carries no noise and must not be demodulated).  flags = PTK_DENOISE_VARIANCE, legal
+ *     only while the accumulator holds an adaptive render, adds the variance plane: with nf = (float)n_p, m_c = S1_c / nf,
+ *     v_c = (S2_c / nf) - (m_c*m_c), v_c = v_c < 0 ? 0 : v_c,
+ *     var = (((v_r/(A_r*A_r)) + (v_g/(A_g*A_g))) + (v_b/(A_b*A_b))) / (3.0f * (nf - 1.0f)), and pixels with n_p < 2 are invalid.
+ *     The call renders no feature planes itself - they are a caller-visible snapshot: PTK_ERR_BAD_ARG when one of the five is
+ *     missing from the last ptk_render_features, when the resolution has changed since, or when no frame is set.  The result goes
+ *     into a context-owned [H][W][3] plane (allocated by the first call, freed with the feature planes); the accumulator, counts
+ *     and moments, the sample count, the 8-bit image, a bound hand-off buffer, the feature planes and the adaptive state are not
+ *     touched: a later ptk_render continues as if the call had not been made.
+ *     Under ptk_set_tile the pixels this rank does not own have n_p = 0: they pass through as 0 and take no part, so the filter of
+ *     a split frame DIFFERS from the whole frame's along the tile borders.  To denoise a gathered image call
+ *     ptk_denoise_planes_device over ptk_gathered_device_ptr, with planes of the whole frame.
+ *   ptk_read_denoised (waits for the stream), ptk_denoised_device_ptr, ptk_resolve_denoised_rgb8 (the frame's 8-bit resolve applied
+ *     to the denoised value, in ptk_resolve_rgb8's layout, into host_out only - never into a bound buffer): PTK_ERR_BAD_ARG before
+ *     a successful ptk_denoise_frame at the current resolution.
+ * PTK_ERR_BAD_ARG: a null context or params, a null required plane with a non-zero size, width or height < 0, iterations outside
+ * 1..8, normal_squarings outside 0..7, a sigma that is not finite or is <= 0, an unknown flag bit, out_variance without variance; a
+ * refused call leaves every output alone.  A zero-sized image is PTK_OK and does nothing.  PTK_ERR_LIMIT: more than 2^28 pixels
+ * or 262140 rows. */
+typedef struct ptk_denoise_params {
+    int32_t iterations;        /* 1..8; iteration k = 0.. uses tap spacing s = 1 << k */
+    int32_t normal_squarings;  /* 0..7: the normal weight is max(0, dot)^(2^normal_squarings) */
+    float sigma_z;             /* world units, finite, > 0: the distance from p's tangent plane at which a tap's weight halves */
+    float sigma_l;             /* finite, > 0: luminance difference (in standard deviations, with a variance plane) likewise */
+} ptk_denoise_params;
+#define PTK_DENOISE_VARIANCE 1u
+int ptk_denoise_planes(ptk_ctx* ctx, int width, int height, const float* color /*[H][W][3]*/, const int32_t* mask /*[H][W]*/,
+                       const float* normal /*[H][W][3]*/, const float* position /*[H][W][3]*/, const float* albedo /*[H][W][3] or NULL*/,
+                       const float* variance /*[H][W] or NULL*/, const ptk_denoise_params* params, float* out_color /*[H][W][3]*/,
+                       float* out_variance /*[H][W] or NULL*/);
+int ptk_denoise_planes_device(ptk_ctx* ctx, int width, int height, const float* d_color, const int32_t* d_mask, const float* d_normal,
+                              const float* d_position, const float* d_albedo, const float* d_variance, const ptk_denoise_params* params,
+                              float* d_out_color, float* d_out_variance);
+int ptk_denoise_frame(ptk_ctx* ctx, const ptk_denoise_params* params, uint32_t flags);
+int ptk_read_denoised(ptk_ctx* ctx, float* host_out /*[H][W][3], rows bottom-up*/);
+int ptk_denoised_device_ptr(ptk_ctx* ctx, void** dev_ptr, size_t* bytes);
+int ptk_resolve_denoised_rgb8(ptk_ctx* ctx, uint8_t* host_out);
+/* measurement hook (tools/denoise_timing.py), not part of the feature.  HIP-event times of the last denoise call's pack kernel,
+ * its filter launches together and its unpack kernel; waits for the call */
+int ptk_last_denoise_ms(ptk_ctx* ctx, float* pack_ms, float* filter_ms, float* unpack_ms);
+
 /* ---- lightmap baking: the radiance leaving the scene's surfaces, per texel of a uv chart layout (no counterpart in the reference) --
  * The surface half of light baking in front of and behind ptk_trace_rays' kernel: a uv rasteriser, a ray generator, a scatter and
  * a chart-padding pass, all on the GPU from what ptk_upload_scene left resident.  Inputs: the uploaded scene, a lightmap of

@@ -70,6 +70,11 @@ int  pth_intersect_rays(pth_tracer* t, int num_rays, const float* origins, const
                         int32_t* tri, float* thit, float* bary, int32_t* material);
 int  pth_occluded_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, const float* tmax, uint32_t sample,
                        uint32_t key_base, uint8_t* occluded);
+/* DenoiseFrame / ReadDenoised / ResolveDenoised (the a-trous denoiser over the frame, include/ptk.h ptk_denoise_frame; the guide
+ * planes are rendered first when missing or stale): 1 on success */
+int  pth_denoise_frame(pth_tracer* t, const ptk_denoise_params* params, int variance);
+int  pth_read_denoised(pth_tracer* t, float* out);
+int  pth_resolve_denoised(pth_tracer* t, unsigned char* out);
 /* ClosestPoints (the nearest surface point to caller-supplied points, include/ptk.h ptk_closest_points): 1 on success */
 int  pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point,
                         float* bary);

@@ -440,6 +440,10 @@ struct PathTracer::Impl {
     std::vector<uint8_t> geometry_dirty;            // per object
     std::vector<int32_t> built_lights;
     bool camera_dirty = true, frame_dirty = true;
+    // DenoiseFrame's guides: view_epoch counts the scene, camera and resolution edits the device layer has received; the planes of
+    // the last RenderFeatures() / DenoiseFrame() are fresh while it, the seed and sample 0 are what they were rendered for
+    uint64_t view_epoch = 1, feat_epoch = 0, feat_seed = 0;
+    uint32_t feat_mask = 0, feat_sample = 0;
 
     uint64_t seed = 0;
     int device = 0, rank = 0, world = 1;
@@ -602,6 +606,7 @@ void PathTracer::BuildBVH()
     int rc = ptk_upload_scene(m->ctx, &d);
     m->note(rc);
     m->scene_uploaded = rc == PTK_OK;
+    m->view_epoch++;
     m->built_lights = fs.lights;
     m->built_once = m->built_once || rc == PTK_OK;
     m->materials_dirty = m->textures_dirty = false;
@@ -679,6 +684,7 @@ static bool apply_scene_edits(PathTracer::Impl* m)
     int rc;
     if (std::find(m->geometry_dirty.begin(), m->geometry_dirty.end(), (uint8_t)1) != m->geometry_dirty.end())
     {
+        m->view_epoch++;
         // SetObjectTransform after BuildBVH: one ptk_update_geometry per contiguous run of moved objects' triangles.  An update
         // the device layer refuses (a coordinate out of bounds) leaves the resident scene unmoved and its text in LastError();
         // the run's objects are then staged again under the matrices the device last accepted, so that StagedScene() and any
@@ -713,6 +719,7 @@ static bool apply_scene_edits(PathTracer::Impl* m)
     }
     if (m->materials_dirty || m->textures_dirty)
     {
+        m->view_epoch++;
         // SetMaterial / Set...TextureForElement after BuildBVH: seen by this frame, as in the reference
         FlatScene fs;
         flatten_scene(m->triangles, m->objects, fs);
@@ -741,9 +748,11 @@ static bool prepare_render(PathTracer::Impl* m, GLubyte*& out_img, unsigned& out
         rc = ptk_set_camera(m->ctx, m->cam_pos, m->cam_dir, m->cam_up, m->focal, m->fovy, m->focal_dist, m->aperture);
         m->note(rc);
         m->camera_dirty = false;
+        m->view_epoch++;
     }
     if (m->frame_dirty)
     {
+        m->view_epoch++;
         rc = ptk_set_frame(m->ctx, m->resolution.x, m->resolution.y, m->max_depth);
         m->note(rc);
         if (rc != PTK_OK) return false;
@@ -829,6 +838,42 @@ bool PathTracer::RenderFeatures(uint32_t mask, uint32_t sample)
     GLubyte* out_img; unsigned out_gl; void* out_dev;
     if (!prepare_render(m, out_img, out_gl, out_dev)) return false;
     const int rc = ptk_render_features(m->ctx, sample, m->seed, mask);
+    m->note(rc);
+    m->feat_mask = rc == PTK_OK ? mask : 0u; m->feat_sample = sample; m->feat_seed = m->seed; m->feat_epoch = m->view_epoch;
+    return rc == PTK_OK;
+}
+
+// The a-trous denoiser over the frame as it was last rendered (ptk_denoise_frame).  No pending edit is applied - the accumulator
+// does not hold it either; the five guide planes are rendered (sample 0 of the seed, at the device layer's current scene, camera
+// and resolution) unless the last RenderFeatures() / DenoiseFrame() left exactly those.
+bool PathTracer::DenoiseFrame(const ptk_denoise_params& params, bool variance)
+{
+    if (!m->scene_uploaded || !m->have_resolution || !m->ctx) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const uint32_t need = (1u << PTK_FEAT_TRIANGLE) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL) | (1u << PTK_FEAT_ALBEDO) | (1u << PTK_FEAT_EMISSION);
+    int rc = PTK_OK;
+    if ((m->feat_mask & need) != need || m->feat_sample != 0 || m->feat_seed != m->seed || m->feat_epoch != m->view_epoch)
+    {
+        rc = ptk_render_features(m->ctx, 0, m->seed, need);
+        m->note(rc);
+        m->feat_mask = rc == PTK_OK ? need : 0u; m->feat_sample = 0; m->feat_seed = m->seed; m->feat_epoch = m->view_epoch;
+    }
+    if (rc == PTK_OK) { rc = ptk_denoise_frame(m->ctx, &params, variance ? PTK_DENOISE_VARIANCE : 0u); m->note(rc); }
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ReadDenoised(float* out)
+{
+    if (!m->ctx || !out) return false;
+    const int rc = ptk_read_denoised(m->ctx, out);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ResolveDenoised(GLubyte* out)
+{
+    if (!m->ctx || !out) return false;
+    const int rc = ptk_resolve_denoised_rgb8(m->ctx, out);
     m->note(rc);
     return rc == PTK_OK;
 }
@@ -1070,6 +1115,7 @@ void PathTracer::SetTile(int rank, int world)
 {
     m->rank = rank; m->world = world;
     if (m->ctx) m->note(ptk_set_tile(m->ctx, rank, world));
+    m->view_epoch++;
 }
 void PathTracer::GetCamera(float* pos, float* dir, float* up) const
 {

@@ -148,6 +148,7 @@ void free_features(ptk_ctx* c)
 {
     for (int k = 0; k < NUM_FEATURES; k++) dfree(c->d_feat[k]);
     c->feat_w = c->feat_h = 0; c->feat_mask = 0;
+    dfree(c->d_denoised); c->den_w = c->den_h = 0;      // the denoised frame goes with the planes that guided it
 }
 
 // Brings the primary-visibility cache up to date where it is valid and hands it to p; else p keeps walking from the camera.
@@ -593,6 +594,8 @@ void ptk_destroy(ptk_ctx* c)
     for (hipEvent_t e : c->ev_hits) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_closest) if (e) (void)hipEventDestroy(e);
     dfree(c->d_closest_stats);
+    dfree(c->d_denoise);
+    for (hipEvent_t e : c->ev_denoise) if (e) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
     if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);

@@ -190,6 +190,16 @@ struct ptk_ctx {
     bool closest_timed = false;
     unsigned long long* d_closest_stats = nullptr;
 
+    // a-trous denoiser (ptk_denoise_planes, ptk_denoise_frame): the four packed float4 images of a call (64 B per pixel, grown to the
+    // largest call so far); the denoised frame [H][W][3], made by the first ptk_denoise_frame, freed with the feature planes, and
+    // the resolution it was last written at; four events of the last call: before the pack, behind it, behind the filter, behind
+    // the unpack
+    float4* d_denoise = nullptr; size_t denoise_px = 0;
+    float* d_denoised = nullptr;
+    int den_w = 0, den_h = 0;
+    hipEvent_t ev_denoise[4] = { nullptr, nullptr, nullptr, nullptr };
+    bool denoise_timed = false;
+
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
     // overlaps the tail of pass k's (a launch ends with the few waves that hold its longest paths - Russian roulette

@@ -128,6 +128,12 @@ int pth_occluded_rays(pth_tracer* t, int num_rays, const float* origins, const f
 {
     return t->pt.OccludedRays(num_rays, origins, dirs, tmax, sample, key_base, occluded) ? 1 : 0;
 }
+int pth_denoise_frame(pth_tracer* t, const ptk_denoise_params* params, int variance)
+{
+    return params && t->pt.DenoiseFrame(*params, variance != 0) ? 1 : 0;
+}
+int pth_read_denoised(pth_tracer* t, float* out) { return t->pt.ReadDenoised(out) ? 1 : 0; }
+int pth_resolve_denoised(pth_tracer* t, unsigned char* out) { return t->pt.ResolveDenoised(out) ? 1 : 0; }
 int pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point, float* bary)
 {
     return t->pt.ClosestPoints(num_points, points, max_dist, tri, dist, point, bary) ? 1 : 0;

@@ -51,3 +51,22 @@ def grid_atlas(num_tris: int, width: int, height: int, gutter: int = 1) -> np.nd
     uv[:, 0::2] /= width
     uv[:, 1::2] /= height
     return np.ascontiguousarray(uv, np.float32)
+
+
+def denoise(ctx, image, owner, pos, normals, params=None, albedo=None, variance=None, want_variance: bool = False):
+    """The a-trous denoiser (include/ptk.h ptk_denoise_planes, Context.denoise_planes) over a baked lightmap: image [H, W, 3] - the
+    mean, sums / spp -, owner [H, W] int32 as the mask (uncovered texels, -1, keep their bits and take no part), pos [H, W, 3] from
+    Context.bake_coverage as the guide position and the owner's face normal as the guide normal.  normals: [triangles, 3] face
+    normals (the scene's tbn[:, 0:3]) or a ready [H, W, 3] plane.  params None: ptk.denoise_defaults for the extent of the covered
+    positions.  Apply it before dilate_lightmap: the padding texels then copy denoised values.  numpy in, numpy out."""
+    from . import ptk
+    owner = np.ascontiguousarray(owner, np.int32)
+    h, w = owner.shape
+    normals = np.asarray(normals, np.float32)
+    if normals.shape != (h, w, 3):
+        normals = normals.reshape(-1, 3)[np.maximum(owner, 0)]
+    if params is None:
+        p = np.asarray(pos, np.float64).reshape(-1, 3)[owner.reshape(-1) >= 0]
+        params = ptk.denoise_defaults(float(np.linalg.norm(p.max(axis=0) - p.min(axis=0))) if len(p) else 1.0, variance is not None)
+    return ctx.denoise_planes(image, owner, np.ascontiguousarray(normals), pos, params, albedo=albedo, variance=variance,
+                              want_variance=want_variance)

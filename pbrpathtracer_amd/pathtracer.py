@@ -39,6 +39,7 @@ HOST_SYMBOLS = [
     "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
     "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points",
+    "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised",
 ]
 
 _bound = False
@@ -113,6 +114,9 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_intersect_rays.restype = i32; L.pth_intersect_rays.argtypes = [vp, i32, vp, vp, u32, u32, vp, vp, vp, vp]
         L.pth_occluded_rays.restype = i32; L.pth_occluded_rays.argtypes = [vp, i32, vp, vp, vp, u32, u32, vp]
         L.pth_closest_points.restype = i32; L.pth_closest_points.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+        L.pth_denoise_frame.restype = i32; L.pth_denoise_frame.argtypes = [vp, C.POINTER(_ptk.DenoiseParams), i32]
+        L.pth_read_denoised.restype = i32; L.pth_read_denoised.argtypes = [vp, vp]
+        L.pth_resolve_denoised.restype = i32; L.pth_resolve_denoised.argtypes = [vp, vp]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -299,6 +303,37 @@ class PathTracer:
         if not self.L.pth_read_feature(self.h, int(feature), out.ctypes.data):
             raise _ptk.PtkError("ReadFeature failed: " + self.LastError())
         return out
+
+    def DenoiseFrame(self, params=None, variance: bool = False):
+        """Extension: the a-trous denoiser (include/ptk.h ptk_denoise_frame) over the frame as last rendered; variance: the
+        variance-guided mode, legal after RenderAdaptive().  params: ptk.DenoiseParams or a dict of its fields; None takes
+        ptk.denoise_defaults for the staged scene's extent.  The guide planes are rendered first (sample 0 of this tracer's seed)
+        when they are missing or stale; the image and the sample count are not touched."""
+        if params is None:
+            v = np.asarray(self.StagedScene()["verts"], np.float64).reshape(-1, 3)
+            params = _ptk.denoise_defaults(float(np.linalg.norm(v.max(axis=0) - v.min(axis=0))) if len(v) else 1.0, variance)
+        prm = _ptk._denoise_params(params)
+        if not self.L.pth_denoise_frame(self.h, C.byref(prm), 1 if variance else 0):
+            raise _ptk.PtkError("DenoiseFrame failed: " + self.LastError())
+
+    def ReadDenoised(self) -> np.ndarray:
+        """[H][W][3] float32, the last DenoiseFrame()'s result, rows bottom-up like ReadAccumulation()."""
+        w, h = self.GetResolution()
+        out = np.empty((h, w, 3), np.float32)
+        if not self.L.pth_read_denoised(self.h, out.ctypes.data):
+            raise _ptk.PtkError("ReadDenoised failed: " + self.LastError())
+        return out
+
+    def ResolveDenoised(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The 8-bit resolve of the denoised frame, [H][W][3] uint8 in the out image's layout."""
+        w, h = self.GetResolution()
+        if out is None:
+            out = np.empty((h, w, 3), np.uint8)
+        if not self.L.pth_resolve_denoised(self.h, out.ctypes.data):
+            raise _ptk.PtkError("ResolveDenoised failed: " + self.LastError())
+        return out
+
+    denoise_frame, read_denoised, resolve_denoised_rgb8 = DenoiseFrame, ReadDenoised, ResolveDenoised
 
     def Pick(self, x: int, y: int):
         """(object, element, triangle) under pixel (x, y), y from the top row; (-1, -1, -1) where the pixel sees nothing."""

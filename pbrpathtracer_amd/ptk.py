@@ -69,6 +69,14 @@ class RaysAdaptiveResult(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class DenoiseParams(C.Structure):
+    """ptk_denoise_params"""
+    _fields_ = [("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("sigma_z", C.c_float), ("sigma_l", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PtkError(RuntimeError):
     pass
 
@@ -93,6 +101,8 @@ SYMBOLS = [
     "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
     "ptk_intersect_rays", "ptk_intersect_rays_device", "ptk_occluded_rays", "ptk_occluded_rays_device", "ptk_last_hits_ms",
     "ptk_closest_points", "ptk_closest_points_device", "ptk_last_closest_ms", "ptk_closest_stats",
+    "ptk_denoise_planes", "ptk_denoise_planes_device", "ptk_denoise_frame", "ptk_read_denoised", "ptk_denoised_device_ptr",
+    "ptk_resolve_denoised_rgb8", "ptk_last_denoise_ms",
     "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
     "ptk_last_bake_ms",
     "ptk_trace_rays_adaptive", "ptk_trace_rays_adaptive_device", "ptk_bake_lightmap_adaptive", "ptk_bake_lightmap_adaptive_device",
@@ -208,6 +218,13 @@ def _load_locked() -> C.CDLL:
             fn.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.ptk_last_closest_ms.argtypes = [vp, fp]
         L.ptk_closest_stats.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(u64), C.POINTER(u64)]
+        for fn in (L.ptk_denoise_planes, L.ptk_denoise_planes_device):
+            fn.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp, vp]
+        L.ptk_denoise_frame.argtypes = [vp, C.POINTER(DenoiseParams), u32]
+        L.ptk_read_denoised.argtypes = [vp, vp]
+        L.ptk_denoised_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.ptk_resolve_denoised_rgb8.argtypes = [vp, vp]
+        L.ptk_last_denoise_ms.argtypes = [vp, fp, fp, fp]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -236,6 +253,20 @@ TRACE_NONE, TRACE_BVH, TRACE_FLAT, TRACE_FLAT_PLAIN = 0, 1, 2, 3      # ptk_trac
 RAYS_ACCUMULATE, RAYS_LENS_DRAWS = 1, 2                               # ptk_trace_rays flags
 BAKE_ACCUMULATE, BAKE_BACK = 1, 2                                     # ptk_bake_lightmap flags
 PROBES_ACCUMULATE = 1                                                 # ptk_bake_probes flags
+DENOISE_VARIANCE = 1                                                  # ptk_denoise_frame flags
+
+
+def denoise_defaults(extent: float, variance: bool = False, iterations: int = 5) -> DenoiseParams:
+    """The documented default parameters of the denoiser for a scene whose bounding box has the diagonal `extent`
+    (world units): 5 iterations (a 61-pixel footprint), normal weight max(0, dot)^32, sigma_z = extent / 64, and sigma_l = 0.25 in
+    luminance of the demodulated image - or, for the variance-guided mode, 2 standard deviations of the pixel's value."""
+    return DenoiseParams(int(iterations), 5, float(extent) / 64.0, 2.0 if variance else 0.25)
+
+
+def _denoise_params(params) -> DenoiseParams:
+    if isinstance(params, DenoiseParams):
+        return params
+    return DenoiseParams(int(params["iterations"]), int(params["normal_squarings"]), float(params["sigma_z"]), float(params["sigma_l"]))
 
 
 # first-hit feature planes (ptk_render_features): ids, and their names in id order
@@ -591,6 +622,74 @@ class Context:
                                            C.c_void_p(max_dist.data_ptr()) if max_dist is not None else None, C.byref(a), C.byref(b)),
                   "ptk_closest_stats")
         return a.value, b.value
+
+    # ---- a-trous denoiser --------------------------------------------------------------------
+    def denoise_planes(self, color, mask, normal, position, params, albedo=None, variance=None, want_variance: bool = False):
+        """ptk_denoise_planes: the a-trous filter of include/ptk.h over the image color [H, W, 3] float32, guided by normal and
+        position [H, W, 3] float32 over the pixels with mask [H, W] int32 >= 0; albedo [H, W, 3] demodulates, variance [H, W]
+        switches the luminance weight to standard deviations.  params: DenoiseParams (denoise_defaults) or a dict of its fields.
+        Returns the filtered image, or (image, variance) with want_variance.  numpy arrays go through the host entry (synchronous)
+        and give numpy arrays; torch tensors on the context's GPU go through ptk_denoise_planes_device with no host copy and give
+        torch tensors written on the context's stream (see trace_rays)."""
+        prm = _denoise_params(params)
+        assert variance is not None or not want_variance, "out_variance needs a variance plane"
+        H, W = int(color.shape[0]), int(color.shape[1])
+        px = H * W
+        if hasattr(color, "data_ptr"):
+            import torch
+            planes = [(color, torch.float32, 3), (mask, torch.int32, 1), (normal, torch.float32, 3), (position, torch.float32, 3)]
+            planes += [(t, torch.float32, k) for t, k in ((albedo, 3), (variance, 1)) if t is not None]
+            self._ray_tensors([t for t, _, _ in planes], px, [(d, k) for _, d, k in planes])
+            out = torch.empty((H, W, 3), dtype=torch.float32, device=color.device)
+            out_var = torch.empty((H, W), dtype=torch.float32, device=color.device) if want_variance else None
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and px else None
+            self._chk(self.L.ptk_denoise_planes_device(self.h, W, H, ptr(color), ptr(mask), ptr(normal), ptr(position), ptr(albedo),
+                                                       ptr(variance), C.byref(prm), ptr(out), ptr(out_var)), "ptk_denoise_planes_device")
+            return (out, out_var) if want_variance else out
+        f = lambda a, shape: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
+        color, normal, position, albedo = (f(a, (H, W, 3)) for a in (color, normal, position, albedo))
+        variance = f(variance, (H, W))
+        mask = np.ascontiguousarray(mask, dtype=np.int32).reshape(H, W)
+        out = np.empty((H, W, 3), np.float32)
+        out_var = np.empty((H, W), np.float32) if want_variance else None
+        ptr = lambda a: a.ctypes.data if a is not None and px else None
+        self._chk(self.L.ptk_denoise_planes(self.h, W, H, ptr(color), ptr(mask), ptr(normal), ptr(position), ptr(albedo), ptr(variance),
+                                            C.byref(prm), ptr(out), ptr(out_var)), "ptk_denoise_planes")
+        return (out, out_var) if want_variance else out
+
+    def denoise_frame(self, params, variance: bool = False, render_features: bool = True, seed: int = 0):
+        """ptk_denoise_frame: filters the frame in the accumulator into the context's denoised plane (read_denoised); asynchronous.
+        variance: the variance-guided mode, legal after render_adaptive.  render_features: render the five guide planes first
+        (sample 0 of `seed`, which replaces the planes of an earlier render_features); False uses the caller's snapshot as it is."""
+        if render_features:
+            self.render_features((1 << FEAT_TRIANGLE) | (1 << FEAT_POSITION) | (1 << FEAT_NORMAL) | (1 << FEAT_ALBEDO) | (1 << FEAT_EMISSION),
+                                 0, seed)
+        prm = _denoise_params(params)
+        self._chk(self.L.ptk_denoise_frame(self.h, C.byref(prm), DENOISE_VARIANCE if variance else 0), "ptk_denoise_frame")
+
+    def read_denoised(self) -> np.ndarray:
+        """[H][W][3] float32, the last denoise_frame's result, rows bottom-up like read_accum; waits for the stream."""
+        out = np.empty((self.height, self.width, 3), dtype=np.float32)
+        self._chk(self.L.ptk_read_denoised(self.h, out.ctypes.data), "ptk_read_denoised")
+        return out
+
+    def denoised_device_ptr(self):
+        p = C.c_void_p(); b = C.c_size_t()
+        self._chk(self.L.ptk_denoised_device_ptr(self.h, C.byref(p), C.byref(b)), "ptk_denoised_device_ptr")
+        return p.value, b.value
+
+    def resolve_denoised_rgb8(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The 8-bit resolve of the denoised frame, in resolve_rgb8's layout."""
+        if out is None:
+            out = np.empty((self.height, self.width, 3), dtype=np.uint8)
+        self._chk(self.L.ptk_resolve_denoised_rgb8(self.h, out.ctypes.data), "ptk_resolve_denoised_rgb8")
+        return out
+
+    def last_denoise_ms(self) -> dict:
+        """HIP-event times of the last denoise call: pack kernel, filter launches, unpack kernel; waits for it."""
+        t = [C.c_float(0) for _ in range(3)]
+        self._chk(self.L.ptk_last_denoise_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_denoise_ms")
+        return dict(zip(("pack_ms", "filter_ms", "unpack_ms"), (x.value for x in t)))
 
     # ---- lightmap baking -------------------------------------------------------------------
     def _bake_uvs(self, uvs, torch_side: bool):
