@@ -26,6 +26,8 @@ struct ptk_scene_desc;
 struct ptk_adaptive_result;
 struct ptk_rays_adaptive_result;
 struct ptk_denoise_params;
+struct ptk_temporal_params;
+struct ptk_view;
 
 const float EPS = 0.00001f;      // mesh.h:12
 const float INF = (float)0xFFFF; // mesh.h:13
@@ -206,6 +208,17 @@ public:
     bool DenoiseFrame(const ptk_denoise_params& params, bool variance = false);
     bool ReadDenoised(float* out);
     bool ResolveDenoised(GLubyte* out);
+    // Extensions: temporal reprojection of the frame as last rendered (include/ptk.h ptk_temporal_frame): the result of the previous
+    // TemporalFrame() is carried into the current camera's frame and blended with it by sample counts; reset drops that history.
+    // The use: after a camera move ResetImage(), a few RenderFrame()s, TemporalFrame(), then DenoiseFrame() or the planes denoiser
+    // over the result.  The guide planes are rendered first, as DenoiseFrame() does it, when MATERIAL, POSITION or NORMAL is missing
+    // or stale (the denoiser's five come along, so that the two calls share one set).  Pending edits are NOT applied; the image,
+    // the sample count and the hand-off buffer are not touched.  ReadTemporal: W*H*3 floats and W*H floats (the samples behind
+    // each pixel), rows bottom-up, either may be NULL.  GetView: the image-plane set-up of the device layer's current camera and
+    // resolution (ptk_get_view).
+    bool TemporalFrame(const ptk_temporal_params& params, bool reset = false);
+    bool ReadTemporal(float* color, float* count);
+    bool GetView(ptk_view* out);
     // The (object, element) under pixel (x, y), y counted from the top row: one ray (ptk_pick), pending edits applied first.
     // A pixel that sees nothing gives -1 / -1 (and triangle -1) and true; false: no scene / resolution yet, or (x, y) outside the frame.
     bool Pick(int x, int y, int* objId, int* elementId, int* triangle = nullptr);

@@ -491,7 +491,7 @@ int ptk_closest_stats(ptk_ctx* ctx, int32_t num_points, const float* d_points, c
  * AFTER THE LAST ITERATION valid pixels with an albedo plane get out_c = c_c * A_c; invalid pixels get out = color, the input bits
  * (and out_variance = variance, the input bits).
  * Deliberately left out: exp-shaped weights (not the same bits on the GPU and in numpy), SVGF's 3x3 prefilter of the variance,
- * temporal reprojection and accumulation, bilinear filtering of the guides.
+ * temporal accumulation inside the filter (ptk_temporal_frame below runs in front of it), bilinear filtering of the guides.
  *   ptk_denoise_planes: host arrays, synchronous; the planes and the requested outputs are staged in device memory for the length
  *     of the call.  albedo, variance and out_variance may be NULL; out_variance needs variance.
  *   ptk_denoise_planes_device: every array in memory of this context's GPU, asynchronous on the context's stream (the caller's
@@ -543,6 +543,96 @@ int ptk_resolve_denoised_rgb8(ptk_ctx* ctx, uint8_t* host_out);
 /* measurement hook (tools/denoise_timing.py), not part of the feature.  HIP-event times of the last denoise call's pack kernel,
  * its filter launches together and its unpack kernel; waits for the call */
 int ptk_last_denoise_ms(ptk_ctx* ctx, float* pack_ms, float* filter_ms, float* unpack_ms);
+
+/* ---- temporal reprojection: a frame's samples carried across camera moves (no counterpart in the reference) -------------------
+ * ptk_set_camera + ptk_reset throws every traced sample away.  For a STATIC scene under a moving camera the previous frame can be
+ * kept instead: each pixel's first-hit world position (PTK_FEAT_POSITION) projected through the previous camera's image-plane
+ * set-up names the previous pixel exactly, no motion vectors needed.  This is the temporal half of SVGF (Schied et al. 2017); it
+ * sits between ptk_render and ptk_denoise_* and multiplies the sample count behind an interactive frame by the history length.
+ * THE VIEW.  ptk_view is what the render's frame set-up computes for a camera and a resolution: pixel (column j, top-down row i)
+ * has the image point top_left + right*(delta_x*j) - up*(delta_y*i); right is perpendicular to up, both unit vectors.
+ * ptk_get_view fills it for the context's current camera and frame, a pending ptk_set_camera included: host arithmetic only, no
+ * launch, no wait; PTK_ERR_BAD_ARG when no frame is set.  (tests/temporal_rule.py view_of restates it bit for bit.)
+ * THE RULE.  Every operation below is one IEEE float32 operation, in the order written (the kernels are compiled with
+ * -ffp-contract=off); dot(a, b) = ((ax*bx) + (ay*by)) + (az*bz); cross(a, b) = ((ay*bz) - (az*by), (az*bx) - (ax*bz), (ax*by) - (ay*bx)).
+ * Only + - * /, comparisons and floor occur, so a numpy restatement gives the same bits (tests/temporal_rule.py;
+ * tests/test_gpu_temporal.py: array_equal).
+ * PLANES, each [H][W] or [H][W][3], rows BOTTOM-UP like everything of the frame: plane row y is top-down row i = H-1-y.
+ *   for the CURRENT frame   color[3]  count[1] float, the samples behind color, >= 0   id[1] int32, < 0 means invalid
+ *                           position[3]  normal[3]
+ *   for the HISTORY         the same five planes, and the ptk_view they were rendered under
+ * PARAMETERS: ptk_temporal_params below.
+ * ONCE PER CALL:  nrm = cross(right, up);  e = top_left - pos;  num = dot(e, nrm);  zz = max_plane_dist*max_plane_dist
+ * FOR EVERY PIXEL p of the current frame:
+ *   invalid pixel    id_p < 0: out_color and out_count get the input bits of color_p and count_p - NaN and 1e30 pass through and
+ *                    reach nobody
+ *   projection       of X = position_p into the history's view:  d = X - pos;  den = dot(d, nrm);  s = num / den;  Q = (d*s) - e;
+ *                    col = dot(Q, right) / delta_x;  row = (0 - dot(Q, up)) / delta_y
+ *   history test     there is history only if s > 0 and col > -1 && col < W && row > -1 && row < H (every comparison is false for
+ *                    NaN; this also bounds the float-to-int conversions that follow)
+ *   tap origin       x0 = (int)floor(col), fx = col - (float)x0;  i0 = (int)floor(row), fy = row - (float)i0
+ *   four taps        in the order (x0, i0) (x0+1, i0) (x0, i0+1) (x0+1, i0+1), with gx = 1.0f - fx, gy = 1.0f - fy and
+ *                    b = gx*gy, fx*gy, gx*fy, fx*fy.  With n = normal_p a tap q is SKIPPED when it lies outside the image, when
+ *                    hist_id_q < 0, when match_id is set and hist_id_q != id_p, when !(hist_count_q > 0), when !(b > 0), when
+ *                    z = dot(n, hist_position_q - X); !(z*z <= zz), or when !(dot(n, hist_normal_q) >= min_normal_dot).
+ *                    A taken tap adds  sc_c = sc_c + (b*hist_color_q,c);  sn = sn + (b*hist_count_q);  sw = sw + b
+ *   blend            sw > 0:  hc_c = sc_c / sw;  hn = sn / sw;  hn = hn > max_history ? max_history : hn.  Otherwise no history.
+ *                    With nc = count_p:   no history:  out = color_p, out_count = nc
+ *                                         nc == 0 (a pixel this rank does not own, or nothing rendered yet):  out = hc, out_count = hn
+ *                                         otherwise:  tot = hn + nc;  out_c = ((hc_c*hn) + (color_p,c*nc)) / tot;  out_count = tot
+ * A history tap is read from a clamped address and dropped by its predicate, as the denoiser's taps are: nothing out of bounds is
+ * ever formed, and the only loop is the four taps.
+ * Deliberately NOT this: moving geometry (after ptk_update_geometry the history is stale where triangles moved: the caller passes
+ * PTK_TEMPORAL_RESET or accepts ghosting); view-dependent radiance (outgoing radiance is treated as view-independent, which is
+ * exact for Lambertian surfaces - glossy ones lag); a variance output; clamping of the history to the neighbourhood's colour range.
+ *   ptk_reproject_planes: host arrays, synchronous; the planes and the outputs are staged in device memory for the length of the call.
+ *   ptk_reproject_planes_device: every array in memory of this context's GPU, asynchronous on the context's stream, no host wait -
+ *     except that the context's 48 B per pixel of packed history grow, behind a drain of the stream, when a call is larger than
+ *     every one before it.  The arrays must stay allocated until the stream has passed the call.
+ * Both need no scene, no camera and no frame; the outputs may not alias an input.
+ *   ptk_temporal_frame: the context's frame, asynchronous on the context's stream.  count = n_p and color_c = S1_c / (float)n_p, 0
+ *     where n_p = 0, exactly as ptk_denoise_frame defines them (adaptive counts, the bound accumulator and the tile split apply);
+ *     id is the feature plane MATERIAL (robust on finely tessellated meshes, where TRIANGLE changes every pixel), position and
+ *     normal are POSITION and NORMAL.  The call renders no planes itself: PTK_ERR_BAD_ARG when one of the three is missing from the
+ *     last ptk_render_features, when the resolution has changed since, or when no frame is set.  The history is the previous
+ *     call's result - blended colour and count, with that call's id, position and normal - and the ptk_get_view of that call; the
+ *     feature planes must belong to the camera of the call, which is the caller's business as it is for ptk_denoise_frame.  The
+ *     first call, a call with PTK_TEMPORAL_RESET and a call after a resolution change use no history: the output equals the
+ *     current frame.  The same launch writes the next history, packed as three float4 images (color.rgb, count), (position.xyz,
+ *     id bits), (normal.xyz, 0), ping-ponging between two context-owned sets (96 B per pixel, plus 16 B for the unpacked result;
+ *     allocated by the first call, freed with the feature planes).  The accumulator, counts and moments, the sample count, the
+ *     8-bit image, a bound hand-off buffer, the feature planes, the denoised plane and the adaptive state are not touched.
+ *   ptk_read_temporal (either pointer may be NULL; waits for the stream) and ptk_temporal_device_ptr (the unpacked [H][W][3] and
+ *     [H][W] planes, which chain into ptk_denoise_planes_device with the planes of ptk_feature_device_ptr): PTK_ERR_BAD_ARG before a
+ *     successful ptk_temporal_frame at the current resolution.
+ * PTK_ERR_BAD_ARG: a null context, params, view or required array with a non-zero size, width or height < 0, max_plane_dist not
+ * finite or <= 0, min_normal_dot not finite or outside [-1, 1], max_history not finite or < 1, an unknown flag bit; a refused call
+ * leaves every output and the history alone.  A zero-sized image is PTK_OK and does nothing.  PTK_ERR_LIMIT: more than 2^28
+ * pixels or 262140 rows. */
+typedef struct ptk_view { float pos[3], right[3], up[3], top_left[3]; float delta_x, delta_y; } ptk_view;
+typedef struct ptk_temporal_params {
+    float max_plane_dist;   /* world units, finite, > 0: a tap further from p's tangent plane is not the same surface */
+    float min_normal_dot;   /* finite, in [-1, 1] */
+    float max_history;      /* finite, >= 1: cap of the history's weight in samples */
+    int32_t match_id;       /* non-zero: a tap must carry the centre's id */
+} ptk_temporal_params;
+#define PTK_TEMPORAL_RESET 1u
+int ptk_get_view(ptk_ctx* ctx, ptk_view* out);
+int ptk_reproject_planes(ptk_ctx* ctx, int width, int height, const ptk_view* hist_view, const float* color /*[H][W][3]*/,
+                         const float* count /*[H][W]*/, const int32_t* id /*[H][W]*/, const float* position /*[H][W][3]*/,
+                         const float* normal /*[H][W][3]*/, const float* hist_color, const float* hist_count, const int32_t* hist_id,
+                         const float* hist_position, const float* hist_normal, const ptk_temporal_params* params,
+                         float* out_color /*[H][W][3]*/, float* out_count /*[H][W]*/);
+int ptk_reproject_planes_device(ptk_ctx* ctx, int width, int height, const ptk_view* hist_view, const float* d_color, const float* d_count,
+                                const int32_t* d_id, const float* d_position, const float* d_normal, const float* d_hist_color,
+                                const float* d_hist_count, const int32_t* d_hist_id, const float* d_hist_position,
+                                const float* d_hist_normal, const ptk_temporal_params* params, float* d_out_color, float* d_out_count);
+int ptk_temporal_frame(ptk_ctx* ctx, const ptk_temporal_params* params, uint32_t flags);
+int ptk_read_temporal(ptk_ctx* ctx, float* color /*[H][W][3] or NULL*/, float* count /*[H][W] or NULL*/);
+int ptk_temporal_device_ptr(ptk_ctx* ctx, void** color, void** count, size_t* pixels);
+/* measurement hook (tools/temporal_timing.py), not part of the feature.  HIP-event times of the last reprojection call's pack kernel
+ * (0 for the frame entry, which has none) and its reprojection kernel; waits for the call */
+int ptk_last_temporal_ms(ptk_ctx* ctx, float* pack_ms, float* kernel_ms);
 
 /* ---- lightmap baking: the radiance leaving the scene's surfaces, per texel of a uv chart layout (no counterpart in the reference) --
  * The surface half of light baking in front of and behind ptk_trace_rays' kernel: a uv rasteriser, a ray generator, a scatter and

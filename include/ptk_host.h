@@ -75,6 +75,11 @@ int  pth_occluded_rays(pth_tracer* t, int num_rays, const float* origins, const 
 int  pth_denoise_frame(pth_tracer* t, const ptk_denoise_params* params, int variance);
 int  pth_read_denoised(pth_tracer* t, float* out);
 int  pth_resolve_denoised(pth_tracer* t, unsigned char* out);
+/* TemporalFrame / ReadTemporal / GetView (temporal reprojection of the frame, include/ptk.h ptk_temporal_frame; the guide planes are
+ * rendered first when missing or stale): 1 on success; color or count may be NULL */
+int  pth_temporal_frame(pth_tracer* t, const ptk_temporal_params* params, int reset);
+int  pth_read_temporal(pth_tracer* t, float* color, float* count);
+int  pth_get_view(pth_tracer* t, ptk_view* out);
 /* ClosestPoints (the nearest surface point to caller-supplied points, include/ptk.h ptk_closest_points): 1 on success */
 int  pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point,
                         float* bary);

@@ -878,6 +878,41 @@ bool PathTracer::ResolveDenoised(GLubyte* out)
     return rc == PTK_OK;
 }
 
+// Temporal reprojection over the frame as it was last rendered (ptk_temporal_frame).  No pending edit is applied; the guide planes
+// are rendered as DenoiseFrame() renders its own, and with them, when MATERIAL, POSITION or NORMAL is missing or stale.
+bool PathTracer::TemporalFrame(const ptk_temporal_params& params, bool reset)
+{
+    if (!m->scene_uploaded || !m->have_resolution || !m->ctx) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const uint32_t need = (1u << PTK_FEAT_MATERIAL) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL);
+    const uint32_t all = need | (1u << PTK_FEAT_TRIANGLE) | (1u << PTK_FEAT_ALBEDO) | (1u << PTK_FEAT_EMISSION);
+    int rc = PTK_OK;
+    if ((m->feat_mask & need) != need || m->feat_sample != 0 || m->feat_seed != m->seed || m->feat_epoch != m->view_epoch)
+    {
+        rc = ptk_render_features(m->ctx, 0, m->seed, all);
+        m->note(rc);
+        m->feat_mask = rc == PTK_OK ? all : 0u; m->feat_sample = 0; m->feat_seed = m->seed; m->feat_epoch = m->view_epoch;
+    }
+    if (rc == PTK_OK) { rc = ptk_temporal_frame(m->ctx, &params, reset ? PTK_TEMPORAL_RESET : 0u); m->note(rc); }
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ReadTemporal(float* color, float* count)
+{
+    if (!m->ctx) return false;
+    const int rc = ptk_read_temporal(m->ctx, color, count);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::GetView(ptk_view* out)
+{
+    if (!m->ctx || !out) return false;
+    const int rc = ptk_get_view(m->ctx, out);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 bool PathTracer::ReadFeature(int feature, void* out)
 {
     if (!m->ctx || !out) return false;

@@ -149,6 +149,7 @@ void free_features(ptk_ctx* c)
     for (int k = 0; k < NUM_FEATURES; k++) dfree(c->d_feat[k]);
     c->feat_w = c->feat_h = 0; c->feat_mask = 0;
     dfree(c->d_denoised); c->den_w = c->den_h = 0;      // the denoised frame goes with the planes that guided it
+    dfree(c->d_temporal); c->temporal_w = c->temporal_h = 0;      // ... and so does the temporal history
 }
 
 // Brings the primary-visibility cache up to date where it is valid and hands it to p; else p keeps walking from the camera.
@@ -445,6 +446,8 @@ int ptk::ensure_primary(ptk_ctx* c)
     return PTK_OK;
 }
 
+void ptk::frame_view(ptk_ctx* c, PrimaryParams& pp) { frame_setup(c, pp); }
+
 void ptk::fill_params(ptk_ctx* c, RenderParams& p, uint32_t first, uint32_t spp, uint64_t seed)
 {
     std::memset(&p, 0, sizeof(p));
@@ -596,6 +599,8 @@ void ptk_destroy(ptk_ctx* c)
     dfree(c->d_closest_stats);
     dfree(c->d_denoise);
     for (hipEvent_t e : c->ev_denoise) if (e) (void)hipEventDestroy(e);
+    dfree(c->d_temporal_pack);
+    for (hipEvent_t e : c->ev_temporal) if (e) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
     if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);

@@ -1,0 +1,223 @@
+// Host side of the ptk C-ABI: temporal reprojection for image planes and for the context's frame (ptk.h ptk_get_view,
+// ptk_reproject_planes, ptk_temporal_frame).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+
+#include "ptk_ctx.h"
+#include "ptk_stage.h"
+#include "ptk_temporal.h"
+
+using namespace ptk;
+
+static int check_temporal_params(ptk_ctx* c, const char* who, const ptk_temporal_params* p)
+{
+    if (!p) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": null params");
+    if (!std::isfinite(p->max_plane_dist) || !(p->max_plane_dist > 0.0f))
+        return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": max_plane_dist is not a finite positive number");
+    if (!std::isfinite(p->min_normal_dot) || !(p->min_normal_dot >= -1.0f && p->min_normal_dot <= 1.0f))
+        return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": min_normal_dot outside -1..1");
+    if (!std::isfinite(p->max_history) || !(p->max_history >= 1.0f)) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": max_history is not a finite number >= 1");
+    return PTK_OK;
+}
+
+// The argument checks the planes entries share; PTK_OK with *nothing = true: the call is legal and has nothing to do.
+static int check_planes_args(ptk_ctx* c, int width, int height, const ptk_view* view, const void* const (&planes)[12], const ptk_temporal_params* p,
+                             bool* nothing)
+{
+    *nothing = false;
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (width < 0 || height < 0) return fail(c, PTK_ERR_BAD_ARG, "ptk_reproject_planes: negative size");
+    if (const int rc = check_temporal_params(c, "ptk_reproject_planes", p); rc != PTK_OK) return rc;
+    if (!view) return fail(c, PTK_ERR_BAD_ARG, "ptk_reproject_planes: null view");
+    if (width == 0 || height == 0) { *nothing = true; return PTK_OK; }
+    for (const void* a : planes)
+        if (!a) return fail(c, PTK_ERR_BAD_ARG, "ptk_reproject_planes: null plane");
+    if ((int64_t)width * height > (1ll << 28) || height > 4 * 65535) return fail(c, PTK_ERR_LIMIT, "ptk_reproject_planes: more than 2^28 pixels or 262140 rows");
+    return PTK_OK;
+}
+
+// The rule's once-per-call values, in float32 and in the header's order (this file is compiled with -ffp-contract=off too).
+static void fill_view(TemporalParams& k, const ptk_view& v, const ptk_temporal_params& p)
+{
+    const float* r = v.right; const float* u = v.up;
+    k.nrm[0] = (r[1] * u[2]) - (r[2] * u[1]); k.nrm[1] = (r[2] * u[0]) - (r[0] * u[2]); k.nrm[2] = (r[0] * u[1]) - (r[1] * u[0]);
+    for (int a = 0; a < 3; a++) { k.pos[a] = v.pos[a]; k.right[a] = r[a]; k.up[a] = u[a]; k.e[a] = v.top_left[a] - v.pos[a]; }
+    k.num = ((k.e[0] * k.nrm[0]) + (k.e[1] * k.nrm[1])) + (k.e[2] * k.nrm[2]);
+    k.delta_x = v.delta_x; k.delta_y = v.delta_y;
+    k.zz = p.max_plane_dist * p.max_plane_dist;
+    k.min_normal_dot = p.min_normal_dot; k.max_history = p.max_history; k.match_id = p.match_id != 0;
+}
+
+// The planes call proper, on the context's stream, every pointer into this GPU's memory: events [0] before the pack, [1] behind
+// it, [2] behind the reprojection.
+static int planes_on_stream(ptk_ctx* c, int width, int height, const ptk_view& view, const float* d_color, const float* d_count, const int32_t* d_id,
+                            const float* d_position, const float* d_normal, const float* d_hist_color, const float* d_hist_count,
+                            const int32_t* d_hist_id, const float* d_hist_position, const float* d_hist_normal, const ptk_temporal_params& p,
+                            float* d_out_color, float* d_out_count)
+{
+    c->temporal_timed = false;
+    const size_t px = (size_t)width * height;
+    if (const int rc = grow(c, c->d_temporal_pack, c->temporal_pack_px, px, 3 * sizeof(float4)); rc != PTK_OK) return rc;
+    if (const int rc = ensure_events(c, c->ev_temporal); rc != PTK_OK) return rc;
+    TemporalImages im = { c->d_temporal_pack, c->d_temporal_pack + px, c->d_temporal_pack + 2 * px };
+    HIPCHK(c, hipEventRecord(c->ev_temporal[0], c->stream));
+    TemporalPackParams pk = {};
+    pk.color = d_hist_color; pk.count = d_hist_count; pk.id = d_hist_id; pk.position = d_hist_position; pk.normal = d_hist_normal;
+    pk.width = width; pk.height = height;
+    launch_temporal_pack(pk, im, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_temporal[1], c->stream));
+    TemporalParams k = {};
+    k.color = d_color; k.count = d_count; k.id = d_id; k.position = d_position; k.normal = d_normal;
+    k.hist = im; k.out_color = d_out_color; k.out_count = d_out_count; k.width = width; k.height = height;
+    fill_view(k, view, p);
+    launch_temporal(k, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_temporal[2], c->stream));
+    c->temporal_timed = true;
+    return PTK_OK;
+}
+
+static bool have_temporal(const ptk_ctx* c) { return c->d_temporal && c->temporal_w == c->width && c->temporal_h == c->height && c->temporal_w > 0; }
+// the frame entry's buffer cut up: history set 0 | history set 1 | colour | count
+static TemporalImages temporal_set(const ptk_ctx* c, size_t px, int set)
+{
+    float4* b = c->d_temporal + (size_t)set * 3 * px;
+    return { b, b + px, b + 2 * px };
+}
+static float* temporal_color(const ptk_ctx* c, size_t px) { return (float*)(c->d_temporal + 6 * px); }
+static float* temporal_count(const ptk_ctx* c, size_t px) { return temporal_color(c, px) + 3 * px; }
+
+extern "C" {
+
+int ptk_get_view(ptk_ctx* c, ptk_view* out)
+{
+    if (!c || !out) return PTK_ERR_BAD_ARG;
+    if (!c->d_primary || c->width <= 0 || c->height <= 0) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
+    PrimaryParams pp;
+    frame_view(c, pp);
+    for (int a = 0; a < 3; a++) { out->pos[a] = pp.cam_pos[a]; out->right[a] = pp.cam_right[a]; out->up[a] = pp.cam_up[a]; out->top_left[a] = pp.top_left[a]; }
+    out->delta_x = pp.delta_x; out->delta_y = pp.delta_y;
+    return PTK_OK;
+}
+
+int ptk_reproject_planes_device(ptk_ctx* c, int width, int height, const ptk_view* view, const float* d_color, const float* d_count,
+                                const int32_t* d_id, const float* d_position, const float* d_normal, const float* d_hist_color,
+                                const float* d_hist_count, const int32_t* d_hist_id, const float* d_hist_position,
+                                const float* d_hist_normal, const ptk_temporal_params* params, float* d_out_color, float* d_out_count)
+{
+    bool nothing;
+    const void* const planes[12] = { d_color, d_count, d_id, d_position, d_normal, d_hist_color, d_hist_count, d_hist_id, d_hist_position,
+                                     d_hist_normal, d_out_color, d_out_count };
+    const int rc = check_planes_args(c, width, height, view, planes, params, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return planes_on_stream(c, width, height, *view, d_color, d_count, d_id, d_position, d_normal, d_hist_color, d_hist_count, d_hist_id,
+                            d_hist_position, d_hist_normal, *params, d_out_color, d_out_count);
+}
+
+// The host entry: the planes and the outputs staged for the length of the call
+int ptk_reproject_planes(ptk_ctx* c, int width, int height, const ptk_view* view, const float* color, const float* count, const int32_t* id,
+                         const float* position, const float* normal, const float* hist_color, const float* hist_count, const int32_t* hist_id,
+                         const float* hist_position, const float* hist_normal, const ptk_temporal_params* params, float* out_color,
+                         float* out_count)
+{
+    bool nothing;
+    const void* const planes[12] = { color, count, id, position, normal, hist_color, hist_count, hist_id, hist_position, hist_normal, out_color, out_count };
+    const int rc = check_planes_args(c, width, height, view, planes, params, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)width * height;
+    Stage s(c);
+    const auto d_color = s.in(color, 3 * px), d_position = s.in(position, 3 * px), d_normal = s.in(normal, 3 * px), d_count = s.in(count, px);
+    const auto d_id = s.in(id, px);
+    const auto d_hist_color = s.in(hist_color, 3 * px), d_hist_position = s.in(hist_position, 3 * px), d_hist_normal = s.in(hist_normal, 3 * px);
+    const auto d_hist_count = s.in(hist_count, px);
+    const auto d_hist_id = s.in(hist_id, px);
+    const auto d_out_color = s.out(out_color, 3 * px), d_out_count = s.out(out_count, px);
+    return s.run([&] {
+        return planes_on_stream(c, width, height, *view, d_color, d_count, d_id, d_position, d_normal, d_hist_color, d_hist_count, d_hist_id,
+                                d_hist_position, d_hist_normal, *params, d_out_color, d_out_count);
+    });
+}
+
+int ptk_temporal_frame(ptk_ctx* c, const ptk_temporal_params* params, uint32_t flags)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (const int rc = check_temporal_params(c, "ptk_temporal_frame", params); rc != PTK_OK) return rc;
+    if (flags & ~PTK_TEMPORAL_RESET) return fail(c, PTK_ERR_BAD_ARG, "ptk_temporal_frame: unknown flag bit");
+    if (!c->d_primary || !accum_ptr(c)) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
+    if (c->feat_w != c->width || c->feat_h != c->height || c->feat_w == 0)
+        return fail(c, PTK_ERR_BAD_ARG, "ptk_temporal_frame: no feature planes for the current resolution: ptk_render_features first");
+    const uint32_t need = (1u << PTK_FEAT_MATERIAL) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL);
+    if ((c->feat_mask & need) != need) return fail(c, PTK_ERR_BAD_ARG, "ptk_temporal_frame: the last ptk_render_features lacks MATERIAL, POSITION or NORMAL");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)c->width * c->height;
+    // (ptk_set_frame with another resolution has freed the buffer with the feature planes: there is no history then)
+    const bool fresh = !have_temporal(c);
+    if (!c->d_temporal) HIPCHK(c, hipMalloc(&c->d_temporal, px * 7 * sizeof(float4)));
+    ptk_view now;
+    if (const int rc = ptk_get_view(c, &now); rc != PTK_OK) return rc;
+    c->temporal_timed = false;
+    if (const int rc = ensure_events(c, c->ev_temporal); rc != PTK_OK) return rc;
+    const bool adaptive = c->adaptive_accum && c->d_counts && c->d_moments;
+    const int next = fresh ? 0 : c->temporal_set ^ 1;
+    TemporalParams k = {};
+    k.accum = accum_ptr(c); k.counts = adaptive ? c->d_counts : nullptr; k.samples = c->samples.load(); k.rank = c->rank; k.world = c->world;
+    k.id = (const int32_t*)c->d_feat[PTK_FEAT_MATERIAL]; k.position = (const float*)c->d_feat[PTK_FEAT_POSITION];
+    k.normal = (const float*)c->d_feat[PTK_FEAT_NORMAL];
+    if (!fresh && !(flags & PTK_TEMPORAL_RESET)) k.hist = temporal_set(c, px, c->temporal_set);
+    k.next = temporal_set(c, px, next);
+    k.out_color = temporal_color(c, px); k.out_count = temporal_count(c, px); k.width = c->width; k.height = c->height;
+    fill_view(k, c->temporal_view, *params);
+    HIPCHK(c, hipEventRecord(c->ev_temporal[0], c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_temporal[1], c->stream));
+    launch_temporal(k, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_temporal[2], c->stream));
+    c->temporal_timed = true;
+    c->temporal_set = next; c->temporal_view = now; c->temporal_w = c->width; c->temporal_h = c->height;
+    return PTK_OK;
+}
+
+int ptk_read_temporal(ptk_ctx* c, float* color, float* count)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!have_temporal(c)) return fail(c, PTK_ERR_BAD_ARG, "no reprojected frame at the current resolution: ptk_temporal_frame first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)c->temporal_w * c->temporal_h;
+    if (color) HIPCHK(c, hipMemcpyAsync(color, temporal_color(c, px), px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (count) HIPCHK(c, hipMemcpyAsync(count, temporal_count(c, px), px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PTK_OK;
+}
+
+int ptk_temporal_device_ptr(ptk_ctx* c, void** color, void** count, size_t* pixels)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!have_temporal(c)) return fail(c, PTK_ERR_BAD_ARG, "no reprojected frame at the current resolution: ptk_temporal_frame first");
+    const size_t px = (size_t)c->temporal_w * c->temporal_h;
+    if (color) *color = temporal_color(c, px);
+    if (count) *count = temporal_count(c, px);
+    if (pixels) *pixels = px;
+    return PTK_OK;
+}
+
+int ptk_last_temporal_ms(ptk_ctx* c, float* pack_ms, float* kernel_ms)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    float t[2] = { 0.0f, 0.0f };
+    if (c->temporal_timed)
+    {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipEventSynchronize(c->ev_temporal[2]));
+        for (int k = 0; k < 2; k++) HIPCHK(c, hipEventElapsedTime(&t[k], c->ev_temporal[k], c->ev_temporal[k + 1]));
+    }
+    if (pack_ms) *pack_ms = t[0];
+    if (kernel_ms) *kernel_ms = t[1];
+    return PTK_OK;
+}
+
+}  // extern "C"

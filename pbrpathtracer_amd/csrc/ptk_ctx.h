@@ -200,6 +200,19 @@ struct ptk_ctx {
     hipEvent_t ev_denoise[4] = { nullptr, nullptr, nullptr, nullptr };
     bool denoise_timed = false;
 
+    // temporal reprojection (ptk_reproject_planes, ptk_temporal_frame).  The frame entry's buffer, 112 B per pixel, made by the first
+    // ptk_temporal_frame at a resolution and freed with the feature planes: two histories of three float4 images each, then the
+    // unpacked result, colour [H][W][3] and count [H][W].  temporal_set names the history the last call wrote, temporal_view the view
+    // stored with it; temporal_w x temporal_h is the resolution of that call (0: none yet).  The planes entries pack the caller's
+    // history into d_temporal_pack (48 B per pixel, grown to the largest call so far).  Three events of the last call: before the
+    // pack, behind it, behind the kernel
+    float4* d_temporal = nullptr;
+    int temporal_w = 0, temporal_h = 0, temporal_set = 0;
+    ptk_view temporal_view = {};
+    float4* d_temporal_pack = nullptr; size_t temporal_pack_px = 0;
+    hipEvent_t ev_temporal[3] = { nullptr, nullptr, nullptr };
+    bool temporal_timed = false;
+
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
     // overlaps the tail of pass k's (a launch ends with the few waves that hold its longest paths - Russian roulette
@@ -304,6 +317,7 @@ inline int ensure_pass_events(ptk_ctx* c, std::vector<hipEvent_t>& ev, int i)
 // ---- internals that cross the files: ptk_api.hip ...
 void fill_params(ptk_ctx* c, RenderParams& p, uint32_t first, uint32_t spp, uint64_t seed);
 int ensure_primary(ptk_ctx* c);
+void frame_view(ptk_ctx* c, PrimaryParams& pp);       // frame_setup's arithmetic for the current camera and frame: host only
 // ... ptk_api_rays.hip: a ray query on the context's stream; the checks and the round loop the adaptive lightmap bake shares with
 // the adaptive ray query, and the context's adaptive buffer cut up for its capacity ...
 int trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,

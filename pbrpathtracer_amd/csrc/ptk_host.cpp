@@ -134,6 +134,12 @@ int pth_denoise_frame(pth_tracer* t, const ptk_denoise_params* params, int varia
 }
 int pth_read_denoised(pth_tracer* t, float* out) { return t->pt.ReadDenoised(out) ? 1 : 0; }
 int pth_resolve_denoised(pth_tracer* t, unsigned char* out) { return t->pt.ResolveDenoised(out) ? 1 : 0; }
+int pth_temporal_frame(pth_tracer* t, const ptk_temporal_params* params, int reset)
+{
+    return params && t->pt.TemporalFrame(*params, reset != 0) ? 1 : 0;
+}
+int pth_read_temporal(pth_tracer* t, float* color, float* count) { return t->pt.ReadTemporal(color, count) ? 1 : 0; }
+int pth_get_view(pth_tracer* t, ptk_view* out) { return t->pt.GetView(out) ? 1 : 0; }
 int pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point, float* bary)
 {
     return t->pt.ClosestPoints(num_points, points, max_dist, tri, dist, point, bary) ? 1 : 0;

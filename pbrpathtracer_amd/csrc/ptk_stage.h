@@ -31,7 +31,8 @@ class Stage {
     struct Part { size_t at, bytes; const void* load; void* store; };
     ptk_ctx* c;
     StageLayout layout;
-    Part parts[8];                               // (the most an entry declares: the hit queries' three inputs and five outputs)
+    static constexpr int kMaxParts = 12;         // (the most an entry declares: ptk_reproject_planes' ten planes and two outputs)
+    Part parts[kMaxParts];
     int num_parts = 0;
     char* base = nullptr;
 
@@ -47,7 +48,7 @@ public:
     Slot<T> part(const T* host, size_t count, bool load, bool store)
     {
         const size_t at = layout.add(sizeof(T), count, host != nullptr);
-        if (at != StageLayout::kAbsent && num_parts++ < 8) parts[num_parts - 1] = { at, sizeof(T) * count, load ? host : nullptr, store ? (void*)host : nullptr };
+        if (at != StageLayout::kAbsent && num_parts++ < kMaxParts) parts[num_parts - 1] = { at, sizeof(T) * count, load ? host : nullptr, store ? (void*)host : nullptr };
         return { this, at };
     }
     template <class T> Slot<T> in(const T* host, size_t count) { return part(host, count, true, false); }
@@ -62,7 +63,7 @@ public:
     template <class Body>
     int run(Body&& body)
     {
-        if (num_parts > 8) return fail(c, PTK_ERR_LIMIT, "staging: more present parts than Stage::parts holds");
+        if (num_parts > kMaxParts) return fail(c, PTK_ERR_LIMIT, "staging: more present parts than Stage::parts holds");
         hipError_t e = hipMalloc(&base, layout.total ? layout.total : 1);
         if (e != hipSuccess) return fail(c, PTK_ERR_HIP, std::string("hipMalloc (staging buffer): ") + hipGetErrorString(e));
         int rc = PTK_OK;

@@ -39,7 +39,7 @@ HOST_SYMBOLS = [
     "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
     "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points",
-    "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised",
+    "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised", "pth_temporal_frame", "pth_read_temporal", "pth_get_view",
 ]
 
 _bound = False
@@ -117,6 +117,9 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_denoise_frame.restype = i32; L.pth_denoise_frame.argtypes = [vp, C.POINTER(_ptk.DenoiseParams), i32]
         L.pth_read_denoised.restype = i32; L.pth_read_denoised.argtypes = [vp, vp]
         L.pth_resolve_denoised.restype = i32; L.pth_resolve_denoised.argtypes = [vp, vp]
+        L.pth_temporal_frame.restype = i32; L.pth_temporal_frame.argtypes = [vp, C.POINTER(_ptk.TemporalParams), i32]
+        L.pth_read_temporal.restype = i32; L.pth_read_temporal.argtypes = [vp, vp, vp]
+        L.pth_get_view.restype = i32; L.pth_get_view.argtypes = [vp, C.POINTER(_ptk.View)]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -334,6 +337,36 @@ class PathTracer:
         return out
 
     denoise_frame, read_denoised, resolve_denoised_rgb8 = DenoiseFrame, ReadDenoised, ResolveDenoised
+
+    def TemporalFrame(self, params=None, reset: bool = False):
+        """Extension: temporal reprojection (include/ptk.h ptk_temporal_frame) over the frame as last rendered: the previous
+        TemporalFrame()'s result is carried into the current camera's frame and blended with it by sample counts; reset drops that
+        history.  params: ptk.TemporalParams or a dict of its fields; None takes ptk.temporal_defaults for the staged scene's
+        extent.  The guide planes are rendered first (sample 0 of this tracer's seed) when they are missing or stale; the image
+        and the sample count are not touched."""
+        if params is None:
+            v = np.asarray(self.StagedScene()["verts"], np.float64).reshape(-1, 3)
+            params = _ptk.temporal_defaults(float(np.linalg.norm(v.max(axis=0) - v.min(axis=0))) if len(v) else 1.0)
+        prm = _ptk._temporal_params(params)
+        if not self.L.pth_temporal_frame(self.h, C.byref(prm), 1 if reset else 0):
+            raise _ptk.PtkError("TemporalFrame failed: " + self.LastError())
+
+    def ReadTemporal(self):
+        """(color [H][W][3], count [H][W]) float32, the last TemporalFrame()'s result, rows bottom-up like ReadAccumulation()."""
+        w, h = self.GetResolution()
+        color = np.empty((h, w, 3), np.float32); count = np.empty((h, w), np.float32)
+        if not self.L.pth_read_temporal(self.h, color.ctypes.data, count.ctypes.data):
+            raise _ptk.PtkError("ReadTemporal failed: " + self.LastError())
+        return color, count
+
+    def GetView(self) -> "_ptk.View":
+        """ptk.View: the image-plane set-up of the device layer's current camera and resolution (include/ptk.h ptk_get_view)."""
+        v = _ptk.View()
+        if not self.L.pth_get_view(self.h, C.byref(v)):
+            raise _ptk.PtkError("GetView failed: " + self.LastError())
+        return v
+
+    temporal_frame, read_temporal, get_view = TemporalFrame, ReadTemporal, GetView
 
     def Pick(self, x: int, y: int):
         """(object, element, triangle) under pixel (x, y), y from the top row; (-1, -1, -1) where the pixel sees nothing."""

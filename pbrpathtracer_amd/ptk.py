@@ -77,6 +77,26 @@ class DenoiseParams(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class View(C.Structure):
+    """ptk_view: pixel (column j, top-down row i) has the image point top_left + right*(delta_x*j) - up*(delta_y*i)"""
+    _fields_ = [("pos", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("top_left", C.c_float * 3),
+                ("delta_x", C.c_float), ("delta_y", C.c_float)]
+
+    def as_dict(self):
+        """float32 arrays and scalars, the struct's own bits"""
+        d = {k: np.array(list(getattr(self, k)), np.float32) for k in ("pos", "right", "up", "top_left")}
+        d.update(delta_x=np.float32(self.delta_x), delta_y=np.float32(self.delta_y))
+        return d
+
+
+class TemporalParams(C.Structure):
+    """ptk_temporal_params"""
+    _fields_ = [("max_plane_dist", C.c_float), ("min_normal_dot", C.c_float), ("max_history", C.c_float), ("match_id", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PtkError(RuntimeError):
     pass
 
@@ -103,6 +123,8 @@ SYMBOLS = [
     "ptk_closest_points", "ptk_closest_points_device", "ptk_last_closest_ms", "ptk_closest_stats",
     "ptk_denoise_planes", "ptk_denoise_planes_device", "ptk_denoise_frame", "ptk_read_denoised", "ptk_denoised_device_ptr",
     "ptk_resolve_denoised_rgb8", "ptk_last_denoise_ms",
+    "ptk_get_view", "ptk_reproject_planes", "ptk_reproject_planes_device", "ptk_temporal_frame", "ptk_read_temporal",
+    "ptk_temporal_device_ptr", "ptk_last_temporal_ms",
     "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
     "ptk_last_bake_ms",
     "ptk_trace_rays_adaptive", "ptk_trace_rays_adaptive_device", "ptk_bake_lightmap_adaptive", "ptk_bake_lightmap_adaptive_device",
@@ -225,6 +247,13 @@ def _load_locked() -> C.CDLL:
         L.ptk_denoised_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
         L.ptk_resolve_denoised_rgb8.argtypes = [vp, vp]
         L.ptk_last_denoise_ms.argtypes = [vp, fp, fp, fp]
+        L.ptk_get_view.argtypes = [vp, C.POINTER(View)]
+        for fn in (L.ptk_reproject_planes, L.ptk_reproject_planes_device):
+            fn.argtypes = [vp, i32, i32, C.POINTER(View)] + [vp] * 10 + [C.POINTER(TemporalParams), vp, vp]
+        L.ptk_temporal_frame.argtypes = [vp, C.POINTER(TemporalParams), u32]
+        L.ptk_read_temporal.argtypes = [vp, vp, vp]
+        L.ptk_temporal_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.ptk_last_temporal_ms.argtypes = [vp, fp, fp]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -267,6 +296,31 @@ def _denoise_params(params) -> DenoiseParams:
     if isinstance(params, DenoiseParams):
         return params
     return DenoiseParams(int(params["iterations"]), int(params["normal_squarings"]), float(params["sigma_z"]), float(params["sigma_l"]))
+
+
+TEMPORAL_RESET = 1                                                    # ptk_temporal_frame flags
+
+
+def temporal_defaults(extent: float) -> TemporalParams:
+    """The documented default parameters of temporal reprojection for a scene whose bounding box has the diagonal
+    `extent` (world units): a history tap counts within 1 % of the extent of the pixel's tangent plane and with a normal within
+    about 26 degrees (dot >= 0.9), carrying the same id; the history weighs at most 64 samples."""
+    return TemporalParams(float(extent) / 100.0, 0.9, 64.0, 1)
+
+
+def _temporal_params(params) -> TemporalParams:
+    if isinstance(params, TemporalParams):
+        return params
+    return TemporalParams(float(params["max_plane_dist"]), float(params["min_normal_dot"]), float(params["max_history"]), int(params["match_id"]))
+
+
+def _view(view) -> View:
+    """a View, or a dict of its fields (tests/temporal_rule.py view_of)"""
+    if isinstance(view, View):
+        return view
+    f3 = C.c_float * 3
+    return View(f3(*map(float, view["pos"])), f3(*map(float, view["right"])), f3(*map(float, view["up"])), f3(*map(float, view["top_left"])),
+                float(view["delta_x"]), float(view["delta_y"]))
 
 
 # first-hit feature planes (ptk_render_features): ids, and their names in id order
@@ -690,6 +744,73 @@ class Context:
         t = [C.c_float(0) for _ in range(3)]
         self._chk(self.L.ptk_last_denoise_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_denoise_ms")
         return dict(zip(("pack_ms", "filter_ms", "unpack_ms"), (x.value for x in t)))
+
+    # ---- temporal reprojection ---------------------------------------------------------------
+    def get_view(self) -> View:
+        """ptk_get_view: the image-plane set-up of the current camera and frame (a pending set_camera included); host arithmetic."""
+        v = View()
+        self._chk(self.L.ptk_get_view(self.h, C.byref(v)), "ptk_get_view")
+        return v
+
+    def reproject_planes(self, hist_view, current, history, params):
+        """ptk_reproject_planes: the history - planes rendered under hist_view (a View or a dict of its fields) - carried into the
+        current frame and blended with it, by the rule of include/ptk.h.  current and history: sequences (color [H, W, 3] float32,
+        count [H, W] float32, id [H, W] int32, position [H, W, 3] float32, normal [H, W, 3] float32), rows bottom-up.  params:
+        TemporalParams (temporal_defaults) or a dict of its fields.  Returns (color [H, W, 3], count [H, W]).  numpy arrays go
+        through the host entry (synchronous) and give numpy arrays; torch tensors on the context's GPU go through
+        ptk_reproject_planes_device with no host copy and give torch tensors written on the context's stream (see trace_rays)."""
+        prm = _temporal_params(params)
+        view = _view(hist_view)
+        planes = list(current) + list(history)
+        assert len(planes) == 10, "five current and five history planes"
+        H, W = int(planes[0].shape[0]), int(planes[0].shape[1])
+        px = H * W
+        if hasattr(planes[0], "data_ptr"):
+            import torch
+            kinds = [(torch.float32, 3), (torch.float32, 1), (torch.int32, 1), (torch.float32, 3), (torch.float32, 3)] * 2
+            self._ray_tensors(planes, px, kinds)
+            out = torch.empty((H, W, 3), dtype=torch.float32, device=planes[0].device)
+            out_n = torch.empty((H, W), dtype=torch.float32, device=planes[0].device)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if px else None
+            self._chk(self.L.ptk_reproject_planes_device(self.h, W, H, C.byref(view), *(ptr(t) for t in planes), C.byref(prm), ptr(out),
+                                                         ptr(out_n)), "ptk_reproject_planes_device")
+            return out, out_n
+        shapes = [(np.float32, (H, W, 3)), (np.float32, (H, W)), (np.int32, (H, W)), (np.float32, (H, W, 3)), (np.float32, (H, W, 3))] * 2
+        planes = [np.ascontiguousarray(a, dtype=d).reshape(sh) for a, (d, sh) in zip(planes, shapes)]
+        out = np.empty((H, W, 3), np.float32); out_n = np.empty((H, W), np.float32)
+        ptr = lambda a: a.ctypes.data if px else None
+        self._chk(self.L.ptk_reproject_planes(self.h, W, H, C.byref(view), *(ptr(a) for a in planes), C.byref(prm), ptr(out), ptr(out_n)),
+                  "ptk_reproject_planes")
+        return out, out_n
+
+    def temporal_frame(self, params, reset: bool = False, render_features: bool = True, seed: int = 0):
+        """ptk_temporal_frame: carries the previous call's result into the frame in the accumulator and blends the two by sample
+        counts (read_temporal); asynchronous.  reset: drop the history.  render_features: render the guide planes MATERIAL,
+        POSITION and NORMAL first (sample 0 of `seed`, which replaces the planes of an earlier render_features); False uses the
+        caller's snapshot as it is."""
+        if render_features:
+            self.render_features((1 << FEAT_MATERIAL) | (1 << FEAT_POSITION) | (1 << FEAT_NORMAL), 0, seed)
+        prm = _temporal_params(params)
+        self._chk(self.L.ptk_temporal_frame(self.h, C.byref(prm), TEMPORAL_RESET if reset else 0), "ptk_temporal_frame")
+
+    def read_temporal(self):
+        """(color [H][W][3], count [H][W]) float32 of the last temporal_frame, rows bottom-up like read_accum; waits for the stream."""
+        color = np.empty((self.height, self.width, 3), dtype=np.float32)
+        count = np.empty((self.height, self.width), dtype=np.float32)
+        self._chk(self.L.ptk_read_temporal(self.h, color.ctypes.data, count.ctypes.data), "ptk_read_temporal")
+        return color, count
+
+    def temporal_device_ptr(self):
+        """(color pointer, count pointer, pixels): the unpacked planes of the last temporal_frame in device memory"""
+        a = C.c_void_p(); b = C.c_void_p(); n = C.c_size_t()
+        self._chk(self.L.ptk_temporal_device_ptr(self.h, C.byref(a), C.byref(b), C.byref(n)), "ptk_temporal_device_ptr")
+        return a.value, b.value, n.value
+
+    def last_temporal_ms(self) -> dict:
+        """HIP-event times of the last reprojection call: pack kernel (0 for the frame entry), reprojection kernel; waits for it."""
+        t = [C.c_float(0) for _ in range(2)]
+        self._chk(self.L.ptk_last_temporal_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_temporal_ms")
+        return dict(zip(("pack_ms", "kernel_ms"), (x.value for x in t)))
 
     # ---- lightmap baking -------------------------------------------------------------------
     def _bake_uvs(self, uvs, torch_side: bool):

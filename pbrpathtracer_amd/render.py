@@ -3,6 +3,7 @@
     python -m pbrpathtracer_amd.render scene.pts --spp 256 --out image.png [--seed S] [--device D]
     python -m pbrpathtracer_amd.render scene.pts --noise-threshold 0.02 [--min-spp 16] [--step 8] --spp 1024
     python -m pbrpathtracer_amd.render scene.pts --spp 8 --denoise [--denoise-iterations K] [--npy denoised.npy]
+    python -m pbrpathtracer_amd.render scene.pts --orbit FRAMES --orbit-degrees D --spp K --temporal [--denoise]
     python -m pbrpathtracer_amd.render scene.pts --features planes.npz
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz
@@ -22,6 +23,13 @@ ptk.denoise_defaults for the scene's extent; --denoise-iterations overrides the 
 position and albedo planes - after an adaptive render (--noise-threshold) also by each pixel's variance - and --npy FILE.npy holds
 the denoised float32 image [H, W, 3], rows top-down like the PNG.  With --bake-lightmap it filters the baked mean over the covered
 texels (lightmap.denoise) before --dilate pads the charts.
+
+With --orbit FRAMES the loaded camera is turned about the vertical axis through the centre of the scene's bounds, by --orbit-degrees
+in FRAMES equal steps - an interactive session's camera drag.  At each step the image is reset and --spp samples are rendered; with
+--temporal each step ends in PathTracer.TemporalFrame (include/ptk.h ptk_temporal_frame, ptk.temporal_defaults for the scene's
+extent), which carries the steps before it into the new view.  The PNG is the last view: the reprojected frame - after --denoise
+filtered by Context.denoise_planes with the guide planes TemporalFrame rendered - or, without --temporal, the plain last frame of
+--spp samples, for comparison.  --npy holds the float32 image [H, W, 3], rows top-down.
 
 With --equirect WIDTH the image is a WIDTH x WIDTH/2 latitude-longitude panorama from the scene's camera position, traced through
 PathTracer.TraceRays (include/ptk.h ptk_trace_rays; rays.equirect_rays) instead of the perspective camera.
@@ -75,6 +83,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="filter the frame (or, with --bake-lightmap, the lightmap) with the a-trous denoiser before it is written; "
                          "with --noise-threshold the frame's filter is variance-guided")
     ap.add_argument("--denoise-iterations", type=int, default=None, metavar="K", help="--denoise: a-trous iterations, 1..8 (default 5)")
+    ap.add_argument("--orbit", type=int, default=None, metavar="FRAMES",
+                    help="turn the camera about the scene's centre in FRAMES steps, --spp samples after a reset at each; the image is the last view")
+    ap.add_argument("--orbit-degrees", type=float, default=10.0, metavar="D", help="--orbit: the whole turn in degrees (default 10)")
+    ap.add_argument("--temporal", action="store_true", help="--orbit: carry each step's samples into the next by temporal reprojection")
     ap.add_argument("--features", metavar="FILE.npz", default=None,
                     help="also write the first-hit feature planes (depth, triangle, material, bary, position, normal_geom, normal, "
                          "albedo, emission, gloss; sample 0) to this .npz, rows top-down like the PNG")
@@ -333,6 +345,59 @@ def render_equirect(pt, a) -> int:
     return 0
 
 
+def orbit_cameras(pt, frames: int, degrees: float):
+    """(pos, dir, up) of the loaded camera turned about the vertical axis through the centre of the staged scene's bounds, after each
+    of `frames` equal steps of degrees / frames"""
+    v = np.asarray(pt.StagedScene()["verts"], np.float64).reshape(-1, 3)
+    centre = (v.max(axis=0) + v.min(axis=0)) / 2 if len(v) else np.zeros(3)
+    pos, dir_, up = (np.asarray(x, np.float64) for x in pt.GetCamera())
+    out = []
+    for k in range(1, frames + 1):
+        a = np.radians(degrees * k / frames)
+        R = np.array([[np.cos(a), 0.0, np.sin(a)], [0.0, 1.0, 0.0], [-np.sin(a), 0.0, np.cos(a)]])
+        out.append(tuple((x).astype(np.float32) for x in (centre + R @ (pos - centre), R @ dir_, R @ up)))
+    return out
+
+
+def render_orbit(pt, a) -> int:
+    """--orbit: a camera drag of FRAMES steps, each a reset and --spp samples, with or without temporal reprojection"""
+    from . import ptk
+    from .pathtracer import export_png
+    w, h = pt.GetResolution()
+    out = np.zeros((h, w, 3), np.uint8)
+    pt.SetOutImage(out)
+    t1 = time.time()
+    for pos, dir_, up in orbit_cameras(pt, a.orbit, a.orbit_degrees):
+        pt.SetCamera(pos, dir_, up)
+        pt.ResetImage()
+        pt.RenderFrames(a.spp)
+        if pt.LastError():
+            raise RuntimeError(pt.LastError())
+        if a.temporal:
+            pt.TemporalFrame()
+    t2 = time.time()
+    if a.temporal:
+        image, count = pt.ReadTemporal()
+        if a.denoise:
+            tri = pt.ReadFeature(ptk.FEAT_TRIANGLE)
+            mask = np.where((pt.ReadFeature(ptk.FEAT_EMISSION) != 0).any(axis=-1), -1, tri).astype(np.int32)
+            image = pt.context().denoise_planes(image, mask, pt.ReadFeature(ptk.FEAT_NORMAL), pt.ReadFeature(ptk.FEAT_POSITION),
+                                                denoise_params(pt, a), albedo=pt.ReadFeature(ptk.FEAT_ALBEDO))
+        found = count > np.float32(a.spp)
+        note = f", {float(found.mean()):.3f} of the pixels found history, {float(count[found].mean()) if found.any() else 0.0:.1f} samples behind each"
+    elif a.denoise:
+        pt.DenoiseFrame(denoise_params(pt, a))
+        image, note = pt.ReadDenoised(), ""
+    else:
+        image, note = pt.ReadAccumulation() / np.float32(a.spp), ""
+    export_png(a.out, resolve_mean(image, 1)[::-1].copy())
+    if a.npy:
+        np.save(a.npy, np.ascontiguousarray(image[::-1], np.float32))
+    print(f"{a.scene}: {w}x{h}, orbit of {a.orbit} steps over {a.orbit_degrees} degrees, {a.spp} spp each"
+          f"{' with temporal reprojection' if a.temporal else ''}{note}: {t2 - t1:.3f} s -> {a.out}")
+    return 0
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
     from .pathtracer import PathTracer, export_png
@@ -351,6 +416,19 @@ def main(argv=None):
     if a.bake_probes is None and (a.probe_visibility is not None or a.probe_max_dist is not None):
         print("error: --probe-visibility and --probe-max-dist go with --bake-probes", file=sys.stderr)
         return 1
+    if a.temporal and a.orbit is None:
+        print("error: --temporal goes with --orbit", file=sys.stderr)
+        return 1
+    if a.orbit is not None:
+        if a.orbit < 1 or a.noise_threshold is not None or a.bake_lightmap is not None or a.bake_probes is not None or \
+                a.distance_field is not None or a.equirect is not None:
+            print("error: --orbit needs FRAMES >= 1 and renders plain perspective frames", file=sys.stderr)
+            return 1
+        try:
+            return render_orbit(pt, a)
+        except RuntimeError as e:
+            print("error:", e, file=sys.stderr)
+            return 1
     if a.bake_lightmap is not None:
         try:
             return render_lightmap(pt, a)
