@@ -171,6 +171,8 @@ public:
     // (ptk_update_geometry, include/ptk.h): records are rewritten and the BVH refitted in place, no rebuild.  The image is not
     // reset (ResetImage() stays the caller's) and the light list stays BuildBVH's.  A bad id is ignored.
     void SetObjectTransform(int objId, const glm::mat4& model);
+    // The matrix object `objId` is staged under: LoadObject's, or the last SetObjectTransform's.  false for a bad id.
+    bool GetObjectTransform(int objId, glm::mat4* model);
     // EXPERIMENTAL (never executed: headless build boxes).  SetOutImage for a display path that stays on the GPU: the 8-bit image
     // (the layout of texData) is written into this OpenGL buffer object - the viewer's GL_PIXEL_UNPACK_BUFFER - instead of a host
     // buffer.  Call it on the thread whose OpenGL context is current (the viewer's GUI thread): the buffer is registered HERE
@@ -219,6 +221,17 @@ public:
     bool TemporalFrame(const ptk_temporal_params& params, bool reset = false);
     bool ReadTemporal(float* color, float* count);
     bool GetView(ptk_view* out);
+    // Extensions: temporal reprojection over objects that move (include/ptk.h ptk_temporal_frame_moving).  TrackMotion(true): the
+    // render call that applies SetObjectTransform() edits first keeps the resident geometry (ptk_geometry_snapshot) - once per
+    // TemporalFrame*() call, ahead of the first batch of edits after it, so that several batches between two temporal calls keep
+    // the geometry that matches the history.  TemporalFrameMoving() is TemporalFrame() whose history follows the moved triangles;
+    // it renders the guide planes (TemporalFrame()'s with BARY) when they are missing or stale, shares history, result and
+    // ReadTemporal with TemporalFrame(), and the two may alternate.  ReadMotion: where each pixel's surface point was in the
+    // history's geometry (W*H*3 floats), its normal there (W*H*3) and its screen-space motion vector under the history's view
+    // (W*H*2: columns, top-down rows; NaN where the pixel sees nothing or there was no history), rows bottom-up, any may be NULL.
+    void TrackMotion(bool on);
+    bool TemporalFrameMoving(const ptk_temporal_params& params, bool reset = false);
+    bool ReadMotion(float* prev_position, float* prev_normal, float* motion);
     // The (object, element) under pixel (x, y), y counted from the top row: one ray (ptk_pick), pending edits applied first.
     // A pixel that sees nothing gives -1 / -1 (and triangle -1) and true; false: no scene / resolution yet, or (x, y) outside the frame.
     bool Pick(int x, int y, int* objId, int* elementId, int* triangle = nullptr);

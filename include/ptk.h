@@ -583,7 +583,8 @@ int ptk_last_denoise_ms(ptk_ctx* ctx, float* pack_ms, float* filter_ms, float* u
  * A history tap is read from a clamped address and dropped by its predicate, as the denoiser's taps are: nothing out of bounds is
  * ever formed, and the only loop is the four taps.
  * Deliberately NOT this: moving geometry (after ptk_update_geometry the history is stale where triangles moved: the caller passes
- * PTK_TEMPORAL_RESET or accepts ghosting); view-dependent radiance (outgoing radiance is treated as view-independent, which is
+ * PTK_TEMPORAL_RESET or accepts ghosting - or calls ptk_temporal_frame_moving / ptk_reproject_planes_moving below instead, which
+ * follow the triangles); view-dependent radiance (outgoing radiance is treated as view-independent, which is
  * exact for Lambertian surfaces - glossy ones lag); a variance output; clamping of the history to the neighbourhood's colour range.
  *   ptk_reproject_planes: host arrays, synchronous; the planes and the outputs are staged in device memory for the length of the call.
  *   ptk_reproject_planes_device: every array in memory of this context's GPU, asynchronous on the context's stream, no host wait -
@@ -633,6 +634,79 @@ int ptk_temporal_device_ptr(ptk_ctx* ctx, void** color, void** count, size_t* pi
 /* measurement hook (tools/temporal_timing.py), not part of the feature.  HIP-event times of the last reprojection call's pack kernel
  * (0 for the frame entry, which has none) and its reprojection kernel; waits for the call */
 int ptk_last_temporal_ms(ptk_ctx* ctx, float* pack_ms, float* kernel_ms);
+
+/* ---- temporal reprojection over MOVING geometry, and screen-space motion vectors (no counterpart in the reference) ---------------
+ * ptk_update_geometry moves triangles between frames; the history of ptk_temporal_frame is then stale where they moved.  What
+ * closes the gap is already resident: the feature planes TRIANGLE and BARY say which surface point a pixel sees, the resident
+ * world-space vertices say where that triangle is now, and a copy of them taken before the update says where it was.  No motion
+ * vectors are stored with the scene: they fall out of the two vertex tables.
+ * PREVIOUS GEOMETRY.  ptk_geometry_snapshot copies the resident vertices [num_triangles][9] into a context-owned table (36 B per
+ * triangle, allocated by the first call, freed with the scene) on the context's stream - the stream ptk_update_geometry rewrites
+ * the vertices on - so it stands behind every update made before it and ahead of every later one, and waits for nothing on the
+ * host.  ptk_upload_scene drops the snapshot.  PTK_ERR_BAD_ARG before ptk_upload_scene; PTK_OK for a scene without triangles.
+ * THE RULE, in the terms of the temporal rule above (one IEEE float32 operation each, in the order written, dot and cross as there;
+ * only + - * /, comparisons and floor occur; the numpy restatement is tests/motion_rule.py).  PER PIXEL p with k = TRIANGLE_p,
+ * (u, v) = BARY_p, X = POSITION_p, n = NORMAL_p; v0, v1, v2 the resident vertices of triangle k and v0', v1', v2' those of the
+ * snapshot (without a snapshot: the same table):
+ *   miss       k < 0:  X' = X, n' = n (the planes' miss values), motion = (NaN, NaN)
+ *   unmoved    all nine floats of the triangle compare == to the snapshot's (a NaN therefore counts as moved):  X' = X, n' = n, bit for
+ *              bit.  So does a k >= num_triangles (planes older than an upload of a smaller scene), which names no record.
+ *   moved      w = (1.0f - u) - v;  D_c = (((v0'_c - v0_c)*w) + ((v1'_c - v1_c)*u)) + ((v2'_c - v2_c)*v);  X'_c = X_c + D_c
+ *              - a displacement of the ray-derived position, not a fresh barycentric point: the history's positions are ray-derived
+ *              too.  The normal goes through the triangle's own change of frame:
+ *                e1 = v1 - v0;  e2 = v2 - v0;  N = cross(e1, e2);  e1' = v1' - v0';  e2' = v2' - v0';  N' = cross(e1', e2')
+ *                a = dot(n, e1);  b = dot(n, e2);  c = dot(n, N);  A = cross(e2', N');  B = cross(N', e1');  nn = dot(N', N')
+ *                n'_c = (((a*A_c) + (b*B_c)) + (c*N'_c)) / nn
+ *              the expansion of n in the dual basis of the previous frame: exact for a rigid motion up to rounding, and not
+ *              renormalised (20 000 random rigid motions in float32, triangle sizes 1e-3 .. 1e2 about coordinates of order 10:
+ *              | |n'| - 1 | <= 0.018, deviation from the exactly rotated normal <= 0.020; the worst are tiny triangles whose float32
+ *              vertices are no longer a rigid image of each other).  A degenerate or overflowing previous triangle gives a non-finite
+ *              n': every comparison of the reprojection rule is then false and the pixel simply has no history.
+ *   motion     under a view V, only where k >= 0: project X' exactly as the temporal rule projects X - d, den, s, Q, col, row -;
+ *              motion = (col - (float)j, row - (float)i) for column j and top-down row i if s > 0, else (NaN, NaN).  The plane is
+ *              [H][W][2], rows bottom-up.
+ * REPROJECTION IN MOVING MODE is the temporal rule with one substitution: everything that is geometry of the history takes the
+ * primed values - the projection takes X', the plane test is z = dot(n', hist_position_q - X'), the normal test is
+ * dot(n', hist_normal_q).  The id test, the counts, the blend, invalid pixels, the clamped tap addresses and the next history are
+ * unchanged; the next history holds the unprimed X, n and id.  Where X' = X and n' = n bit for bit the result is bit for bit that of
+ * ptk_reproject_planes or ptk_temporal_frame.
+ * Deliberately NOT this: lighting that changed because something moved (shadows and bounce light lag, bounded by max_history);
+ * triangles whose count or order changes; motion of the background behind a miss.
+ *   ptk_render_motion: X', n' and motion for the context's feature planes TRIANGLE, BARY, POSITION and NORMAL of the last
+ *     ptk_render_features at the current resolution (PTK_ERR_BAD_ARG otherwise, as for ptk_temporal_frame), into three
+ *     context-owned planes of 32 B per pixel together (allocated on first use, freed with the feature planes); asynchronous on the
+ *     context's stream.  view may be NULL: motion is then NaN everywhere, X' and n' are computed all the same.  Without a snapshot
+ *     every triangle is unmoved.
+ *   ptk_read_motion (any pointer may be NULL; waits for the stream) and ptk_motion_device_ptr: PTK_ERR_BAD_ARG before a successful
+ *     ptk_render_motion or ptk_temporal_frame_moving at the current resolution.
+ *   ptk_reproject_planes_moving, ptk_reproject_planes_moving_device: ptk_reproject_planes(_device) with the planes prev_position
+ *     and prev_normal of the CURRENT frame behind its normal plane; the same checks, staging, limits and packed-history buffer.
+ *   ptk_temporal_frame_moving: ptk_temporal_frame in moving mode; flags 0 or PTK_TEMPORAL_RESET.  It runs ptk_render_motion's kernel
+ *     under the view of the context's history (NULL on a first call, after a reset or after a resolution change), then the
+ *     reprojection; it needs MATERIAL, TRIANGLE, BARY, POSITION and NORMAL.  The history, the result planes and the readers
+ *     ptk_read_temporal and ptk_temporal_device_ptr are those of ptk_temporal_frame: calls of the two may alternate.  It leaves
+ *     alone everything ptk_temporal_frame leaves alone.
+ * A refused call leaves every output, the snapshot and the history alone. */
+int ptk_geometry_snapshot(ptk_ctx* ctx);
+int ptk_render_motion(ptk_ctx* ctx, const ptk_view* view /* or NULL */);
+int ptk_read_motion(ptk_ctx* ctx, float* prev_position /*[H][W][3] or NULL*/, float* prev_normal /*[H][W][3] or NULL*/,
+                    float* motion /*[H][W][2] or NULL*/);
+int ptk_motion_device_ptr(ptk_ctx* ctx, void** prev_position, void** prev_normal, void** motion, size_t* pixels);
+int ptk_reproject_planes_moving(ptk_ctx* ctx, int width, int height, const ptk_view* hist_view, const float* color, const float* count,
+                                const int32_t* id, const float* position, const float* normal, const float* prev_position /*[H][W][3]*/,
+                                const float* prev_normal /*[H][W][3]*/, const float* hist_color, const float* hist_count,
+                                const int32_t* hist_id, const float* hist_position, const float* hist_normal,
+                                const ptk_temporal_params* params, float* out_color, float* out_count);
+int ptk_reproject_planes_moving_device(ptk_ctx* ctx, int width, int height, const ptk_view* hist_view, const float* d_color,
+                                       const float* d_count, const int32_t* d_id, const float* d_position, const float* d_normal,
+                                       const float* d_prev_position, const float* d_prev_normal, const float* d_hist_color,
+                                       const float* d_hist_count, const int32_t* d_hist_id, const float* d_hist_position,
+                                       const float* d_hist_normal, const ptk_temporal_params* params, float* d_out_color,
+                                       float* d_out_count);
+int ptk_temporal_frame_moving(ptk_ctx* ctx, const ptk_temporal_params* params, uint32_t flags);
+/* measurement hook (tools/motion_timing.py), not part of the feature.  HIP-event times of the last ptk_render_motion or
+ * ptk_temporal_frame_moving: motion_kernel, and the reprojection kernel behind it (0 for ptk_render_motion); waits for the call */
+int ptk_last_motion_ms(ptk_ctx* ctx, float* motion_ms, float* temporal_ms);
 
 /* ---- lightmap baking: the radiance leaving the scene's surfaces, per texel of a uv chart layout (no counterpart in the reference) --
  * The surface half of light baking in front of and behind ptk_trace_rays' kernel: a uv rasteriser, a ray generator, a scatter and

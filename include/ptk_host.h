@@ -24,6 +24,8 @@ void pth_destroy(pth_tracer* t);
 void pth_load_object(pth_tracer* t, const char* file, const float model_colmajor[16]);
 /* SetObjectTransform (extension): stage object `obj` again under another matrix; after BuildBVH the next render call refits */
 void pth_set_object_transform(pth_tracer* t, int obj, const float model_colmajor[16]);
+/* GetObjectTransform (extension): the matrix object `obj` is staged under; 1 on success, 0 for a bad id */
+int  pth_get_object_transform(pth_tracer* t, int obj, float model_colmajor[16]);
 void pth_set_material(pth_tracer* t, int obj, int elem, const float m15[15]);  /* type, diffuse3, specular3, emissive3, I, roughness, reflectiveness, translucency, ior */
 void pth_set_texture(pth_tracer* t, int obj, int elem, int slot, const char* file); /* slot 0..5: diffuse normal emissive roughness metallic opacity */
 void pth_build_bvh(pth_tracer* t);
@@ -80,6 +82,11 @@ int  pth_resolve_denoised(pth_tracer* t, unsigned char* out);
 int  pth_temporal_frame(pth_tracer* t, const ptk_temporal_params* params, int reset);
 int  pth_read_temporal(pth_tracer* t, float* color, float* count);
 int  pth_get_view(pth_tracer* t, ptk_view* out);
+/* TrackMotion / TemporalFrameMoving / ReadMotion (temporal reprojection over moving objects, include/ptk.h
+ * ptk_temporal_frame_moving): 1 on success; any pointer of pth_read_motion may be NULL */
+void pth_track_motion(pth_tracer* t, int on);
+int  pth_temporal_frame_moving(pth_tracer* t, const ptk_temporal_params* params, int reset);
+int  pth_read_motion(pth_tracer* t, float* prev_position, float* prev_normal, float* motion);
 /* ClosestPoints (the nearest surface point to caller-supplied points, include/ptk.h ptk_closest_points): 1 on success */
 int  pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point,
                         float* bary);

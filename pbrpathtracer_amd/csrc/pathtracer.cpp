@@ -443,6 +443,9 @@ struct PathTracer::Impl {
     // DenoiseFrame's guides: view_epoch counts the scene, camera and resolution edits the device layer has received; the planes of
     // the last RenderFeatures() / DenoiseFrame() are fresh while it, the seed and sample 0 are what they were rendered for
     uint64_t view_epoch = 1, feat_epoch = 0, feat_seed = 0;
+    // TrackMotion: a geometry snapshot goes ahead of the first ptk_update_geometry after a TemporalFrame*() call; snapshot_taken:
+    // one has been taken since that call
+    bool track_motion = false, snapshot_taken = false;
     uint32_t feat_mask = 0, feat_sample = 0;
 
     uint64_t seed = 0;
@@ -685,6 +688,14 @@ static bool apply_scene_edits(PathTracer::Impl* m)
     if (std::find(m->geometry_dirty.begin(), m->geometry_dirty.end(), (uint8_t)1) != m->geometry_dirty.end())
     {
         m->view_epoch++;
+        // TrackMotion: the history of TemporalFrameMoving() belongs to the geometry as it is resident now - kept once, however many
+        // batches of transforms arrive before the next TemporalFrame*() call
+        if (m->track_motion && !m->snapshot_taken)
+        {
+            rc = ptk_geometry_snapshot(m->ctx);
+            m->note(rc);
+            m->snapshot_taken = rc == PTK_OK;
+        }
         // SetObjectTransform after BuildBVH: one ptk_update_geometry per contiguous run of moved objects' triangles.  An update
         // the device layer refuses (a coordinate out of bounds) leaves the resident scene unmoved and its text in LastError();
         // the run's objects are then staged again under the matrices the device last accepted, so that StagedScene() and any
@@ -894,6 +905,44 @@ bool PathTracer::TemporalFrame(const ptk_temporal_params& params, bool reset)
         m->feat_mask = rc == PTK_OK ? all : 0u; m->feat_sample = 0; m->feat_seed = m->seed; m->feat_epoch = m->view_epoch;
     }
     if (rc == PTK_OK) { rc = ptk_temporal_frame(m->ctx, &params, reset ? PTK_TEMPORAL_RESET : 0u); m->note(rc); }
+    if (rc == PTK_OK) m->snapshot_taken = false;
+    return rc == PTK_OK;
+}
+
+// TemporalFrame() in moving mode (ptk_temporal_frame_moving): the history follows the triangles SetObjectTransform() moved since the
+// last TemporalFrame*() call.  Its guide planes are TemporalFrame()'s with BARY.
+bool PathTracer::TemporalFrameMoving(const ptk_temporal_params& params, bool reset)
+{
+    if (!m->scene_uploaded || !m->have_resolution || !m->ctx) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const uint32_t need = (1u << PTK_FEAT_MATERIAL) | (1u << PTK_FEAT_TRIANGLE) | (1u << PTK_FEAT_BARY) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL);
+    const uint32_t all = need | (1u << PTK_FEAT_ALBEDO) | (1u << PTK_FEAT_EMISSION);
+    int rc = PTK_OK;
+    if ((m->feat_mask & need) != need || m->feat_sample != 0 || m->feat_seed != m->seed || m->feat_epoch != m->view_epoch)
+    {
+        rc = ptk_render_features(m->ctx, 0, m->seed, all);
+        m->note(rc);
+        m->feat_mask = rc == PTK_OK ? all : 0u; m->feat_sample = 0; m->feat_seed = m->seed; m->feat_epoch = m->view_epoch;
+    }
+    // TrackMotion and nothing moved since the last TemporalFrame*() call: the snapshot of an earlier frame is not this history's
+    if (rc == PTK_OK && m->track_motion && !m->snapshot_taken) { rc = ptk_geometry_snapshot(m->ctx); m->note(rc); }
+    if (rc == PTK_OK) { rc = ptk_temporal_frame_moving(m->ctx, &params, reset ? PTK_TEMPORAL_RESET : 0u); m->note(rc); }
+    if (rc == PTK_OK) m->snapshot_taken = false;
+    return rc == PTK_OK;
+}
+
+void PathTracer::TrackMotion(bool on)
+{
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    m->track_motion = on;
+    m->snapshot_taken = false;
+}
+
+bool PathTracer::ReadMotion(float* prev_position, float* prev_normal, float* motion)
+{
+    if (!m->ctx) return false;
+    const int rc = ptk_read_motion(m->ctx, prev_position, prev_normal, motion);
+    m->note(rc);
     return rc == PTK_OK;
 }
 
@@ -1118,6 +1167,13 @@ void PathTracer::SetObjectTransform(int objId, const glm::mat4& model)
     m->sources[objId].model = model;
     if (m->scene_uploaded) m->geometry_dirty[objId] = 1;
     else m->sources[objId].resident = model;
+}
+bool PathTracer::GetObjectTransform(int objId, glm::mat4* model)
+{
+    if (!model || objId < 0 || objId >= (int)m->sources.size()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    *model = m->sources[objId].model;
+    return true;
 }
 // EXPERIMENTAL (built, its refusal tested, never executed: the GPU boxes are headless).  Registration talks to the OpenGL driver
 // through the CALLING thread's current context, so it happens here, in the setter the viewer's GUI thread calls - not inside

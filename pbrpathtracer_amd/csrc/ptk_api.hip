@@ -150,6 +150,7 @@ void free_features(ptk_ctx* c)
     c->feat_w = c->feat_h = 0; c->feat_mask = 0;
     dfree(c->d_denoised); c->den_w = c->den_h = 0;      // the denoised frame goes with the planes that guided it
     dfree(c->d_temporal); c->temporal_w = c->temporal_h = 0;      // ... and so does the temporal history
+    dfree(c->d_motion); c->motion_w = c->motion_h = 0;            // ... and the motion planes
 }
 
 // Brings the primary-visibility cache up to date where it is valid and hands it to p; else p keeps walking from the camera.
@@ -553,7 +554,7 @@ void ptk_destroy(ptk_ctx* c)
     unbind_out_image(c);
     dfree(c->d_nodes); dfree(c->d_tris); dfree(c->d_shade); dfree(c->d_mats); dfree(c->d_lights);
     dfree(c->d_flat_tris);
-    free_geometry_cache(c); dfree(c->d_verts_res); dfree(c->d_geo_stage); dfree(c->d_geo_red);
+    free_geometry_cache(c); dfree(c->d_verts_res); dfree(c->d_verts_prev); dfree(c->d_geo_stage); dfree(c->d_geo_red);
     if (c->h_geo_red) (void)hipHostFree(c->h_geo_red);
     if (c->geo_stream) { (void)hipStreamSynchronize(c->geo_stream); (void)hipStreamDestroy(c->geo_stream); }
     for (hipEvent_t e : c->ev_geo_t) if (e) (void)hipEventDestroy(e);
@@ -601,6 +602,7 @@ void ptk_destroy(ptk_ctx* c)
     for (hipEvent_t e : c->ev_denoise) if (e) (void)hipEventDestroy(e);
     dfree(c->d_temporal_pack);
     for (hipEvent_t e : c->ev_temporal) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_motion) if (e) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
     if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);
@@ -799,6 +801,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
     dfree(c->d_nodes); dfree(c->d_tris); dfree(c->d_shade); dfree(c->d_mats); dfree(c->d_lights);
     dfree(c->d_texinfo); dfree(c->d_texels);
     dfree(c->d_verts_res); free_geometry_cache(c);
+    dfree(c->d_verts_prev); c->have_snapshot = false;             // (ptk_geometry_snapshot: of the scene that goes)
     c->lights_stale = false;
     c->have_scene = false;
     auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {

@@ -1,11 +1,13 @@
 // Host side of the ptk C-ABI: temporal reprojection for image planes and for the context's frame (ptk.h ptk_get_view,
-// ptk_reproject_planes, ptk_temporal_frame).
+// ptk_reproject_planes, ptk_temporal_frame), and its moving-geometry mode with the motion planes (ptk.h
+// ptk_geometry_snapshot, ptk_render_motion, ptk_reproject_planes_moving, ptk_temporal_frame_moving).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <string>
 
 #include "ptk_ctx.h"
+#include "ptk_motion.h"
 #include "ptk_stage.h"
 #include "ptk_temporal.h"
 
@@ -23,7 +25,8 @@ static int check_temporal_params(ptk_ctx* c, const char* who, const ptk_temporal
 }
 
 // The argument checks the planes entries share; PTK_OK with *nothing = true: the call is legal and has nothing to do.
-static int check_planes_args(ptk_ctx* c, int width, int height, const ptk_view* view, const void* const (&planes)[12], const ptk_temporal_params* p,
+template <size_t N>
+static int check_planes_args(ptk_ctx* c, int width, int height, const ptk_view* view, const void* const (&planes)[N], const ptk_temporal_params* p,
                              bool* nothing)
 {
     *nothing = false;
@@ -55,9 +58,10 @@ static void fill_view(TemporalParams& k, const ptk_view& v, const ptk_temporal_p
 static int planes_on_stream(ptk_ctx* c, int width, int height, const ptk_view& view, const float* d_color, const float* d_count, const int32_t* d_id,
                             const float* d_position, const float* d_normal, const float* d_hist_color, const float* d_hist_count,
                             const int32_t* d_hist_id, const float* d_hist_position, const float* d_hist_normal, const ptk_temporal_params& p,
-                            float* d_out_color, float* d_out_count)
+                            float* d_out_color, float* d_out_count, const float* d_prev_position = nullptr, const float* d_prev_normal = nullptr)
 {
     c->temporal_timed = false;
+    if (c->motion_timed == 2) c->motion_timed = 1;      // (ev_temporal stops being the kernel behind the last motion_kernel)
     const size_t px = (size_t)width * height;
     if (const int rc = grow(c, c->d_temporal_pack, c->temporal_pack_px, px, 3 * sizeof(float4)); rc != PTK_OK) return rc;
     if (const int rc = ensure_events(c, c->ev_temporal); rc != PTK_OK) return rc;
@@ -72,6 +76,7 @@ static int planes_on_stream(ptk_ctx* c, int width, int height, const ptk_view& v
     TemporalParams k = {};
     k.color = d_color; k.count = d_count; k.id = d_id; k.position = d_position; k.normal = d_normal;
     k.hist = im; k.out_color = d_out_color; k.out_count = d_out_count; k.width = width; k.height = height;
+    k.prev_position = d_prev_position; k.prev_normal = d_prev_normal;
     fill_view(k, view, p);
     launch_temporal(k, c->stream);
     HIPCHK(c, hipGetLastError());
@@ -89,6 +94,108 @@ static TemporalImages temporal_set(const ptk_ctx* c, size_t px, int set)
 }
 static float* temporal_color(const ptk_ctx* c, size_t px) { return (float*)(c->d_temporal + 6 * px); }
 static float* temporal_count(const ptk_ctx* c, size_t px) { return temporal_color(c, px) + 3 * px; }
+
+static bool have_motion(const ptk_ctx* c) { return c->d_motion && c->motion_w == c->width && c->motion_h == c->height && c->motion_w > 0; }
+// the motion buffer cut up: previous position | previous normal | motion
+static float* motion_prev_position(const ptk_ctx* c, size_t) { return c->d_motion; }
+static float* motion_prev_normal(const ptk_ctx* c, size_t px) { return c->d_motion + 3 * px; }
+static float* motion_vectors(const ptk_ctx* c, size_t px) { return c->d_motion + 6 * px; }
+
+// What ptk_render_motion and ptk_temporal_frame_moving need of the context beyond their own arguments
+static int check_motion_state(ptk_ctx* c, const char* who, uint32_t need, const char* names)
+{
+    if (!c->have_scene || !c->d_verts_res) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (!c->d_primary || c->width <= 0 || c->height <= 0) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
+    if (c->feat_w != c->width || c->feat_h != c->height || c->feat_w == 0)
+        return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": no feature planes for the current resolution: ptk_render_features first");
+    if ((c->feat_mask & need) != need) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": the last ptk_render_features lacks " + names);
+    return PTK_OK;
+}
+
+// motion_kernel over the context's feature planes on the context's stream, between the two events of ev_motion; view null: no
+// motion vectors
+static int motion_on_stream(ptk_ctx* c, const ptk_view* view)
+{
+    c->motion_timed = 0;
+    const size_t px = (size_t)c->width * c->height;
+    if (!c->d_motion) HIPCHK(c, hipMalloc(&c->d_motion, px * 8 * sizeof(float)));
+    if (const int rc = ensure_events(c, c->ev_motion); rc != PTK_OK) return rc;
+    MotionParams m = {};
+    m.tri = (const int32_t*)c->d_feat[PTK_FEAT_TRIANGLE]; m.bary = (const float*)c->d_feat[PTK_FEAT_BARY];
+    m.position = (const float*)c->d_feat[PTK_FEAT_POSITION]; m.normal = (const float*)c->d_feat[PTK_FEAT_NORMAL];
+    m.verts = c->d_verts_res; m.prev = c->have_snapshot ? c->d_verts_prev : nullptr; m.num_tris = c->num_tris;
+    m.prev_position = motion_prev_position(c, px); m.prev_normal = motion_prev_normal(c, px); m.motion = motion_vectors(c, px);
+    m.width = c->width; m.height = c->height;
+    if (view)
+    {
+        TemporalParams k = {};
+        fill_view(k, *view, ptk_temporal_params{ 1.0f, 0.0f, 1.0f, 0 });
+        m.have_view = 1;
+        for (int a = 0; a < 3; a++) { m.pos[a] = k.pos[a]; m.right[a] = k.right[a]; m.up[a] = k.up[a]; m.e[a] = k.e[a]; m.nrm[a] = k.nrm[a]; }
+        m.num = k.num; m.delta_x = k.delta_x; m.delta_y = k.delta_y;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_motion[0], c->stream));
+    launch_motion(m, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_motion[1], c->stream));
+    c->motion_timed = 1;
+    c->motion_w = c->width; c->motion_h = c->height;
+    return PTK_OK;
+}
+
+// ptk_temporal_frame and ptk_temporal_frame_moving
+static int temporal_frame(ptk_ctx* c, const char* who, const ptk_temporal_params* params, uint32_t flags, bool moving)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (const int rc = check_temporal_params(c, who, params); rc != PTK_OK) return rc;
+    if (flags & ~PTK_TEMPORAL_RESET) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": unknown flag bit");
+    if (!c->d_primary || !accum_ptr(c)) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
+    uint32_t need = (1u << PTK_FEAT_MATERIAL) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL);
+    if (moving)
+    {
+        need |= (1u << PTK_FEAT_TRIANGLE) | (1u << PTK_FEAT_BARY);
+        if (const int rc = check_motion_state(c, who, need, "MATERIAL, TRIANGLE, BARY, POSITION or NORMAL"); rc != PTK_OK) return rc;
+    }
+    else
+    {
+        if (c->feat_w != c->width || c->feat_h != c->height || c->feat_w == 0)
+            return fail(c, PTK_ERR_BAD_ARG, "ptk_temporal_frame: no feature planes for the current resolution: ptk_render_features first");
+        if ((c->feat_mask & need) != need) return fail(c, PTK_ERR_BAD_ARG, "ptk_temporal_frame: the last ptk_render_features lacks MATERIAL, POSITION or NORMAL");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)c->width * c->height;
+    // (ptk_set_frame with another resolution has freed the buffer with the feature planes: there is no history then)
+    const bool fresh = !have_temporal(c);
+    if (!c->d_temporal) HIPCHK(c, hipMalloc(&c->d_temporal, px * 7 * sizeof(float4)));
+    ptk_view now;
+    if (const int rc = ptk_get_view(c, &now); rc != PTK_OK) return rc;
+    c->temporal_timed = false;
+    if (c->motion_timed == 2) c->motion_timed = 1;
+    if (const int rc = ensure_events(c, c->ev_temporal); rc != PTK_OK) return rc;
+    const bool with_history = !fresh && !(flags & PTK_TEMPORAL_RESET);
+    if (moving)
+        if (const int rc = motion_on_stream(c, with_history ? &c->temporal_view : nullptr); rc != PTK_OK) return rc;
+    const bool adaptive = c->adaptive_accum && c->d_counts && c->d_moments;
+    const int next = fresh ? 0 : c->temporal_set ^ 1;
+    TemporalParams k = {};
+    k.accum = accum_ptr(c); k.counts = adaptive ? c->d_counts : nullptr; k.samples = c->samples.load(); k.rank = c->rank; k.world = c->world;
+    k.id = (const int32_t*)c->d_feat[PTK_FEAT_MATERIAL]; k.position = (const float*)c->d_feat[PTK_FEAT_POSITION];
+    k.normal = (const float*)c->d_feat[PTK_FEAT_NORMAL];
+    if (with_history) k.hist = temporal_set(c, px, c->temporal_set);
+    k.next = temporal_set(c, px, next);
+    k.out_color = temporal_color(c, px); k.out_count = temporal_count(c, px); k.width = c->width; k.height = c->height;
+    if (moving) { k.prev_position = motion_prev_position(c, px); k.prev_normal = motion_prev_normal(c, px); }
+    fill_view(k, c->temporal_view, *params);
+    HIPCHK(c, hipEventRecord(c->ev_temporal[0], c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_temporal[1], c->stream));
+    launch_temporal(k, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_temporal[2], c->stream));
+    c->temporal_timed = true;
+    if (moving) c->motion_timed = 2;
+    c->temporal_set = next; c->temporal_view = now; c->temporal_w = c->width; c->temporal_h = c->height;
+    return PTK_OK;
+}
 
 extern "C" {
 
@@ -145,41 +252,7 @@ int ptk_reproject_planes(ptk_ctx* c, int width, int height, const ptk_view* view
 
 int ptk_temporal_frame(ptk_ctx* c, const ptk_temporal_params* params, uint32_t flags)
 {
-    if (!c) return PTK_ERR_BAD_ARG;
-    if (const int rc = check_temporal_params(c, "ptk_temporal_frame", params); rc != PTK_OK) return rc;
-    if (flags & ~PTK_TEMPORAL_RESET) return fail(c, PTK_ERR_BAD_ARG, "ptk_temporal_frame: unknown flag bit");
-    if (!c->d_primary || !accum_ptr(c)) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
-    if (c->feat_w != c->width || c->feat_h != c->height || c->feat_w == 0)
-        return fail(c, PTK_ERR_BAD_ARG, "ptk_temporal_frame: no feature planes for the current resolution: ptk_render_features first");
-    const uint32_t need = (1u << PTK_FEAT_MATERIAL) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL);
-    if ((c->feat_mask & need) != need) return fail(c, PTK_ERR_BAD_ARG, "ptk_temporal_frame: the last ptk_render_features lacks MATERIAL, POSITION or NORMAL");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t px = (size_t)c->width * c->height;
-    // (ptk_set_frame with another resolution has freed the buffer with the feature planes: there is no history then)
-    const bool fresh = !have_temporal(c);
-    if (!c->d_temporal) HIPCHK(c, hipMalloc(&c->d_temporal, px * 7 * sizeof(float4)));
-    ptk_view now;
-    if (const int rc = ptk_get_view(c, &now); rc != PTK_OK) return rc;
-    c->temporal_timed = false;
-    if (const int rc = ensure_events(c, c->ev_temporal); rc != PTK_OK) return rc;
-    const bool adaptive = c->adaptive_accum && c->d_counts && c->d_moments;
-    const int next = fresh ? 0 : c->temporal_set ^ 1;
-    TemporalParams k = {};
-    k.accum = accum_ptr(c); k.counts = adaptive ? c->d_counts : nullptr; k.samples = c->samples.load(); k.rank = c->rank; k.world = c->world;
-    k.id = (const int32_t*)c->d_feat[PTK_FEAT_MATERIAL]; k.position = (const float*)c->d_feat[PTK_FEAT_POSITION];
-    k.normal = (const float*)c->d_feat[PTK_FEAT_NORMAL];
-    if (!fresh && !(flags & PTK_TEMPORAL_RESET)) k.hist = temporal_set(c, px, c->temporal_set);
-    k.next = temporal_set(c, px, next);
-    k.out_color = temporal_color(c, px); k.out_count = temporal_count(c, px); k.width = c->width; k.height = c->height;
-    fill_view(k, c->temporal_view, *params);
-    HIPCHK(c, hipEventRecord(c->ev_temporal[0], c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_temporal[1], c->stream));
-    launch_temporal(k, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_temporal[2], c->stream));
-    c->temporal_timed = true;
-    c->temporal_set = next; c->temporal_view = now; c->temporal_w = c->width; c->temporal_h = c->height;
-    return PTK_OK;
+    return temporal_frame(c, "ptk_temporal_frame", params, flags, false);
 }
 
 int ptk_read_temporal(ptk_ctx* c, float* color, float* count)
@@ -217,6 +290,119 @@ int ptk_last_temporal_ms(ptk_ctx* c, float* pack_ms, float* kernel_ms)
     }
     if (pack_ms) *pack_ms = t[0];
     if (kernel_ms) *kernel_ms = t[1];
+    return PTK_OK;
+}
+
+// ---- moving geometry ------------------------------------------------------------------------------------------------------------
+int ptk_geometry_snapshot(ptk_ctx* c)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (c->num_tris <= 0 || !c->d_verts_res) return PTK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->num_tris * 9 * sizeof(float);
+    if (!c->d_verts_prev) HIPCHK(c, hipMalloc(&c->d_verts_prev, bytes));
+    // on the stream ptk_update_geometry rewrites d_verts_res on: behind every update so far, ahead of every later one
+    HIPCHK(c, hipMemcpyAsync(c->d_verts_prev, c->d_verts_res, bytes, hipMemcpyDeviceToDevice, c->stream));
+    c->have_snapshot = true;
+    return PTK_OK;
+}
+
+int ptk_render_motion(ptk_ctx* c, const ptk_view* view)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    const uint32_t need = (1u << PTK_FEAT_TRIANGLE) | (1u << PTK_FEAT_BARY) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL);
+    if (const int rc = check_motion_state(c, "ptk_render_motion", need, "TRIANGLE, BARY, POSITION or NORMAL"); rc != PTK_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return motion_on_stream(c, view);
+}
+
+int ptk_read_motion(ptk_ctx* c, float* prev_position, float* prev_normal, float* motion)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!have_motion(c)) return fail(c, PTK_ERR_BAD_ARG, "no motion planes at the current resolution: ptk_render_motion or ptk_temporal_frame_moving first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)c->motion_w * c->motion_h;
+    if (prev_position) HIPCHK(c, hipMemcpyAsync(prev_position, motion_prev_position(c, px), px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (prev_normal) HIPCHK(c, hipMemcpyAsync(prev_normal, motion_prev_normal(c, px), px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (motion) HIPCHK(c, hipMemcpyAsync(motion, motion_vectors(c, px), px * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PTK_OK;
+}
+
+int ptk_motion_device_ptr(ptk_ctx* c, void** prev_position, void** prev_normal, void** motion, size_t* pixels)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!have_motion(c)) return fail(c, PTK_ERR_BAD_ARG, "no motion planes at the current resolution: ptk_render_motion or ptk_temporal_frame_moving first");
+    const size_t px = (size_t)c->motion_w * c->motion_h;
+    if (prev_position) *prev_position = motion_prev_position(c, px);
+    if (prev_normal) *prev_normal = motion_prev_normal(c, px);
+    if (motion) *motion = motion_vectors(c, px);
+    if (pixels) *pixels = px;
+    return PTK_OK;
+}
+
+int ptk_reproject_planes_moving_device(ptk_ctx* c, int width, int height, const ptk_view* view, const float* d_color, const float* d_count,
+                                       const int32_t* d_id, const float* d_position, const float* d_normal, const float* d_prev_position,
+                                       const float* d_prev_normal, const float* d_hist_color, const float* d_hist_count, const int32_t* d_hist_id,
+                                       const float* d_hist_position, const float* d_hist_normal, const ptk_temporal_params* params,
+                                       float* d_out_color, float* d_out_count)
+{
+    bool nothing;
+    const void* const planes[14] = { d_color, d_count, d_id, d_position, d_normal, d_prev_position, d_prev_normal, d_hist_color, d_hist_count,
+                                     d_hist_id, d_hist_position, d_hist_normal, d_out_color, d_out_count };
+    const int rc = check_planes_args(c, width, height, view, planes, params, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return planes_on_stream(c, width, height, *view, d_color, d_count, d_id, d_position, d_normal, d_hist_color, d_hist_count, d_hist_id,
+                            d_hist_position, d_hist_normal, *params, d_out_color, d_out_count, d_prev_position, d_prev_normal);
+}
+
+int ptk_reproject_planes_moving(ptk_ctx* c, int width, int height, const ptk_view* view, const float* color, const float* count, const int32_t* id,
+                                const float* position, const float* normal, const float* prev_position, const float* prev_normal,
+                                const float* hist_color, const float* hist_count, const int32_t* hist_id, const float* hist_position,
+                                const float* hist_normal, const ptk_temporal_params* params, float* out_color, float* out_count)
+{
+    bool nothing;
+    const void* const planes[14] = { color, count, id, position, normal, prev_position, prev_normal, hist_color, hist_count, hist_id, hist_position,
+                                     hist_normal, out_color, out_count };
+    const int rc = check_planes_args(c, width, height, view, planes, params, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)width * height;
+    Stage s(c);
+    const auto d_color = s.in(color, 3 * px), d_position = s.in(position, 3 * px), d_normal = s.in(normal, 3 * px), d_count = s.in(count, px);
+    const auto d_id = s.in(id, px);
+    const auto d_prev_position = s.in(prev_position, 3 * px), d_prev_normal = s.in(prev_normal, 3 * px);
+    const auto d_hist_color = s.in(hist_color, 3 * px), d_hist_position = s.in(hist_position, 3 * px), d_hist_normal = s.in(hist_normal, 3 * px);
+    const auto d_hist_count = s.in(hist_count, px);
+    const auto d_hist_id = s.in(hist_id, px);
+    const auto d_out_color = s.out(out_color, 3 * px), d_out_count = s.out(out_count, px);
+    return s.run([&] {
+        return planes_on_stream(c, width, height, *view, d_color, d_count, d_id, d_position, d_normal, d_hist_color, d_hist_count, d_hist_id,
+                                d_hist_position, d_hist_normal, *params, d_out_color, d_out_count, d_prev_position, d_prev_normal);
+    });
+}
+
+int ptk_temporal_frame_moving(ptk_ctx* c, const ptk_temporal_params* params, uint32_t flags)
+{
+    return temporal_frame(c, "ptk_temporal_frame_moving", params, flags, true);
+}
+
+int ptk_last_motion_ms(ptk_ctx* c, float* motion_ms, float* temporal_ms)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    float t[2] = { 0.0f, 0.0f };
+    if (c->motion_timed)
+    {
+        // (the reprojection kernel's events are the frame entry's own, so that it is timed exactly as ptk_last_temporal_ms times it)
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipEventSynchronize(c->motion_timed == 2 ? c->ev_temporal[2] : c->ev_motion[1]));
+        HIPCHK(c, hipEventElapsedTime(&t[0], c->ev_motion[0], c->ev_motion[1]));
+        if (c->motion_timed == 2) HIPCHK(c, hipEventElapsedTime(&t[1], c->ev_temporal[1], c->ev_temporal[2]));
+    }
+    if (motion_ms) *motion_ms = t[0];
+    if (temporal_ms) *temporal_ms = t[1];
     return PTK_OK;
 }
 

@@ -213,6 +213,19 @@ struct ptk_ctx {
     hipEvent_t ev_temporal[3] = { nullptr, nullptr, nullptr };
     bool temporal_timed = false;
 
+    // moving geometry under temporal reprojection (ptk_geometry_snapshot, ptk_render_motion, ptk_temporal_frame_moving).  The snapshot
+    // of d_verts_res, 36 B per triangle, made by the first ptk_geometry_snapshot of a scene and freed with it; have_snapshot: it
+    // holds one.  The three planes of ptk_render_motion in one buffer, 32 B per pixel - previous position [H][W][3] | previous
+    // normal [H][W][3] | motion [H][W][2] -, made by the first call at a resolution and freed with the feature planes; motion_w x
+    // motion_h is the resolution of the last call (0: none yet).  Two events of the last call around motion_kernel; motion_timed 1:
+    // they are set, 2: and ev_temporal holds the reprojection kernel that followed
+    float* d_verts_prev = nullptr;
+    bool have_snapshot = false;
+    float* d_motion = nullptr;
+    int motion_w = 0, motion_h = 0;
+    hipEvent_t ev_motion[2] = { nullptr, nullptr };
+    int motion_timed = 0;
+
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
     // overlaps the tail of pass k's (a launch ends with the few waves that hold its longest paths - Russian roulette

@@ -39,6 +39,13 @@ void pth_set_object_transform(pth_tracer* t, int obj, const float* mm)
     for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) M[c][r] = mm[c * 4 + r];
     t->pt.SetObjectTransform(obj, M);
 }
+int pth_get_object_transform(pth_tracer* t, int obj, float* mm)
+{
+    glm::mat4 M(1.0f);
+    if (!mm || !t->pt.GetObjectTransform(obj, &M)) return 0;
+    for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) mm[c * 4 + r] = M[c][r];
+    return 1;
+}
 void pth_set_material(pth_tracer* t, int obj, int elem, const float* m)
 {
     Material mat;
@@ -139,6 +146,15 @@ int pth_temporal_frame(pth_tracer* t, const ptk_temporal_params* params, int res
     return params && t->pt.TemporalFrame(*params, reset != 0) ? 1 : 0;
 }
 int pth_read_temporal(pth_tracer* t, float* color, float* count) { return t->pt.ReadTemporal(color, count) ? 1 : 0; }
+void pth_track_motion(pth_tracer* t, int on) { t->pt.TrackMotion(on != 0); }
+int pth_temporal_frame_moving(pth_tracer* t, const ptk_temporal_params* params, int reset)
+{
+    return params && t->pt.TemporalFrameMoving(*params, reset != 0) ? 1 : 0;
+}
+int pth_read_motion(pth_tracer* t, float* prev_position, float* prev_normal, float* motion)
+{
+    return t->pt.ReadMotion(prev_position, prev_normal, motion) ? 1 : 0;
+}
 int pth_get_view(pth_tracer* t, ptk_view* out) { return t->pt.GetView(out) ? 1 : 0; }
 int pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point, float* bary)
 {

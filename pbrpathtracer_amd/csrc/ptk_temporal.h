@@ -46,6 +46,10 @@ struct TemporalParams {
     float pos[3], right[3], up[3], e[3], nrm[3];
     float num, delta_x, delta_y, zz, min_normal_dot, max_history;
     int match_id;
+    // moving mode (ptk_reproject_planes_moving, ptk_temporal_frame_moving; ptk_motion.h): where the current frame's points and
+    // normals were in the history's geometry.  Both null: the plain rule.  (Last, so that the fields above keep their offsets.)
+    const float* prev_position; // [H][W][3]
+    const float* prev_normal;   // [H][W][3]
 };
 
 void launch_temporal_pack(const TemporalPackParams& p, const TemporalImages& im, hipStream_t stream);

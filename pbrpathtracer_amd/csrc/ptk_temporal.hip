@@ -3,6 +3,7 @@
 //     cn = (colour, count), pi = (position, id bits), nz = (normal, 0);
 //   * temporal_kernel - one thread per pixel: projection of its first-hit position into the history's view, the four bilinear taps
 //     in the rule's order, the blend; writes the SoA outputs and - in the frame entry - the next history in the packed layout.
+//     Its MOVING instantiations project the point's previous place instead (ptk.h ptk_temporal_frame_moving).
 // Compiled once, with -ffp-contract=off: every expression below is the rule of ptk.h operation by operation, and `/` is the IEEE
 // quotient (the numpy restatement is tests/temporal_rule.py).  No atomics, no LDS, no persistent waves; the only loop is the four taps.
 #include "ptk_device_fn.h"
@@ -36,7 +37,9 @@ __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_pack_kernel(
 // FRAME: the current colour and count come from the accumulator (n_p and S1 / n_p exactly as denoise_pack_frame_kernel has them).
 // The loads of the four taps are issued together from clamped (always on-image) addresses; a tap off the image is then dropped
 // by its predicate with the others, so nothing it holds reaches a sum.
-template <bool FRAME>
+// MOVING: everything that is geometry of the history - the projected point and the two tap tests - takes X' and n' from the planes
+// motion_kernel wrote (ptk_motion.hip); the next history still holds the unprimed X and n.
+template <bool FRAME, bool MOVING>
 __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_kernel(const TemporalParams P)
 {
     int x, y;
@@ -65,7 +68,9 @@ __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_kernel(const
     float o0 = c0, o1 = c1, o2 = c2, on = nc;                  // an invalid pixel and a pixel without history: the input bits
     if (id >= 0 && P.hist.cn)
     {
-        const float d0 = X0 - P.pos[0], d1 = X1 - P.pos[1], d2 = X2 - P.pos[2];
+        const float Y0 = MOVING ? P.prev_position[3 * ip] : X0, Y1 = MOVING ? P.prev_position[3 * ip + 1] : X1, Y2 = MOVING ? P.prev_position[3 * ip + 2] : X2;
+        const float m0 = MOVING ? P.prev_normal[3 * ip] : n0, m1 = MOVING ? P.prev_normal[3 * ip + 1] : n1, m2 = MOVING ? P.prev_normal[3 * ip + 2] : n2;
+        const float d0 = Y0 - P.pos[0], d1 = Y1 - P.pos[1], d2 = Y2 - P.pos[2];
         const float den = tp_dot(d0, d1, d2, P.nrm[0], P.nrm[1], P.nrm[2]);
         const float s = P.num / den;
         const float Q0 = (d0 * s) - P.e[0], Q1 = (d1 * s) - P.e[1], Q2 = (d2 * s) - P.e[2];
@@ -94,8 +99,8 @@ __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_kernel(const
             for (int k = 0; k < 4; k++)
             {
                 const int hid = __float_as_int(hp[k].w);
-                const float z = tp_dot(n0, n1, n2, hp[k].x - X0, hp[k].y - X1, hp[k].z - X2);
-                const float cn = tp_dot(n0, n1, n2, hn[k].x, hn[k].y, hn[k].z);
+                const float z = tp_dot(m0, m1, m2, hp[k].x - Y0, hp[k].y - Y1, hp[k].z - Y2);
+                const float cn = tp_dot(m0, m1, m2, hn[k].x, hn[k].y, hn[k].z);
                 if (in[k] && hid >= 0 && (!P.match_id || hid == id) && hc[k].w > 0.0f && b[k] > 0.0f && z * z <= P.zz && cn >= P.min_normal_dot)
                 {
                     s0 = s0 + (b[k] * hc[k].x); s1 = s1 + (b[k] * hc[k].y); s2 = s2 + (b[k] * hc[k].z);
@@ -138,8 +143,14 @@ void launch_temporal_pack(const TemporalPackParams& p, const TemporalImages& im,
 
 void launch_temporal(const TemporalParams& p, hipStream_t stream)
 {
-    if (p.accum) hipLaunchKernelGGL(temporal_kernel<true>, tp_grid(p.width, p.height), tp_block, 0, stream, p);
-    else hipLaunchKernelGGL(temporal_kernel<false>, tp_grid(p.width, p.height), tp_block, 0, stream, p);
+    const dim3 grid = tp_grid(p.width, p.height);
+    if (p.prev_position)
+    {
+        if (p.accum) hipLaunchKernelGGL((temporal_kernel<true, true>), grid, tp_block, 0, stream, p);
+        else hipLaunchKernelGGL((temporal_kernel<false, true>), grid, tp_block, 0, stream, p);
+    }
+    else if (p.accum) hipLaunchKernelGGL((temporal_kernel<true, false>), grid, tp_block, 0, stream, p);
+    else hipLaunchKernelGGL((temporal_kernel<false, false>), grid, tp_block, 0, stream, p);
 }
 
 }  // namespace ptk

@@ -40,6 +40,7 @@ HOST_SYMBOLS = [
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
     "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points",
     "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised", "pth_temporal_frame", "pth_read_temporal", "pth_get_view",
+    "pth_track_motion", "pth_temporal_frame_moving", "pth_read_motion", "pth_get_object_transform",
 ]
 
 _bound = False
@@ -120,6 +121,10 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_temporal_frame.restype = i32; L.pth_temporal_frame.argtypes = [vp, C.POINTER(_ptk.TemporalParams), i32]
         L.pth_read_temporal.restype = i32; L.pth_read_temporal.argtypes = [vp, vp, vp]
         L.pth_get_view.restype = i32; L.pth_get_view.argtypes = [vp, C.POINTER(_ptk.View)]
+        L.pth_get_object_transform.restype = i32; L.pth_get_object_transform.argtypes = [vp, i32, C.POINTER(C.c_float)]
+        L.pth_track_motion.restype = None; L.pth_track_motion.argtypes = [vp, i32]
+        L.pth_temporal_frame_moving.restype = i32; L.pth_temporal_frame_moving.argtypes = [vp, C.POINTER(_ptk.TemporalParams), i32]
+        L.pth_read_motion.restype = i32; L.pth_read_motion.argtypes = [vp, vp, vp, vp]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -275,6 +280,14 @@ class PathTracer:
         the next render call moves its triangles on the device and refits the BVH (include/ptk.h ptk_update_geometry)."""
         M = np.ascontiguousarray(model, dtype=np.float32)
         self.L.pth_set_object_transform(self.h, int(objId), _fp(M.reshape(16)))
+
+    def GetObjectTransform(self, objId: int) -> np.ndarray:
+        """Extension: the 4x4 matrix ([column][row]) object `objId` is staged under - LoadObject's or the last SetObjectTransform's."""
+        M = np.zeros(16, np.float32)
+        if not self.L.pth_get_object_transform(self.h, int(objId), _fp(M)):
+            raise _ptk.PtkError(f"GetObjectTransform: no object {objId}")
+        return M.reshape(4, 4)
+
     def RenderFrames(self, count: int): self.L.pth_render_frames(self.h, count)
 
     def RenderAdaptive(self, threshold: float, min_spp: int, step: int, max_spp: int) -> dict:
@@ -344,12 +357,38 @@ class PathTracer:
         history.  params: ptk.TemporalParams or a dict of its fields; None takes ptk.temporal_defaults for the staged scene's
         extent.  The guide planes are rendered first (sample 0 of this tracer's seed) when they are missing or stale; the image
         and the sample count are not touched."""
+        prm = self._temporal_params(params)
+        if not self.L.pth_temporal_frame(self.h, C.byref(prm), 1 if reset else 0):
+            raise _ptk.PtkError("TemporalFrame failed: " + self.LastError())
+
+    def _temporal_params(self, params):
         if params is None:
             v = np.asarray(self.StagedScene()["verts"], np.float64).reshape(-1, 3)
             params = _ptk.temporal_defaults(float(np.linalg.norm(v.max(axis=0) - v.min(axis=0))) if len(v) else 1.0)
-        prm = _ptk._temporal_params(params)
-        if not self.L.pth_temporal_frame(self.h, C.byref(prm), 1 if reset else 0):
-            raise _ptk.PtkError("TemporalFrame failed: " + self.LastError())
+        return _ptk._temporal_params(params)
+
+    def TrackMotion(self, on: bool = True):
+        """Extension: with tracking on, the render call that applies SetObjectTransform() edits first keeps the resident geometry
+        (include/ptk.h ptk_geometry_snapshot) - once per TemporalFrame*() call - as the previous geometry of TemporalFrameMoving()."""
+        self.L.pth_track_motion(self.h, 1 if on else 0)
+
+    def TemporalFrameMoving(self, params=None, reset: bool = False):
+        """Extension: TemporalFrame() over objects that move (include/ptk.h ptk_temporal_frame_moving): the history follows the
+        triangles SetObjectTransform() moved since the last TemporalFrame*() call (TrackMotion).  Shares history, result and
+        ReadTemporal() with TemporalFrame(); ReadMotion() gives where the surface points were."""
+        prm = self._temporal_params(params)
+        if not self.L.pth_temporal_frame_moving(self.h, C.byref(prm), 1 if reset else 0):
+            raise _ptk.PtkError("TemporalFrameMoving failed: " + self.LastError())
+
+    def ReadMotion(self):
+        """(prev_position [H][W][3], prev_normal [H][W][3], motion [H][W][2]) float32 of the last TemporalFrameMoving(), rows
+        bottom-up: motion is (columns, top-down rows) from the pixel to where its surface point was under the history's view; NaN
+        where the pixel sees nothing or there was no history."""
+        w, h = self.GetResolution()
+        pp = np.empty((h, w, 3), np.float32); pn = np.empty((h, w, 3), np.float32); mv = np.empty((h, w, 2), np.float32)
+        if not self.L.pth_read_motion(self.h, pp.ctypes.data, pn.ctypes.data, mv.ctypes.data):
+            raise _ptk.PtkError("ReadMotion failed: " + self.LastError())
+        return pp, pn, mv
 
     def ReadTemporal(self):
         """(color [H][W][3], count [H][W]) float32, the last TemporalFrame()'s result, rows bottom-up like ReadAccumulation()."""
@@ -367,6 +406,7 @@ class PathTracer:
         return v
 
     temporal_frame, read_temporal, get_view = TemporalFrame, ReadTemporal, GetView
+    track_motion, temporal_frame_moving, read_motion = TrackMotion, TemporalFrameMoving, ReadMotion
 
     def Pick(self, x: int, y: int):
         """(object, element, triangle) under pixel (x, y), y from the top row; (-1, -1, -1) where the pixel sees nothing."""

@@ -125,6 +125,8 @@ SYMBOLS = [
     "ptk_resolve_denoised_rgb8", "ptk_last_denoise_ms",
     "ptk_get_view", "ptk_reproject_planes", "ptk_reproject_planes_device", "ptk_temporal_frame", "ptk_read_temporal",
     "ptk_temporal_device_ptr", "ptk_last_temporal_ms",
+    "ptk_geometry_snapshot", "ptk_render_motion", "ptk_read_motion", "ptk_motion_device_ptr", "ptk_reproject_planes_moving",
+    "ptk_reproject_planes_moving_device", "ptk_temporal_frame_moving", "ptk_last_motion_ms",
     "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
     "ptk_last_bake_ms",
     "ptk_trace_rays_adaptive", "ptk_trace_rays_adaptive_device", "ptk_bake_lightmap_adaptive", "ptk_bake_lightmap_adaptive_device",
@@ -254,6 +256,14 @@ def _load_locked() -> C.CDLL:
         L.ptk_read_temporal.argtypes = [vp, vp, vp]
         L.ptk_temporal_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
         L.ptk_last_temporal_ms.argtypes = [vp, fp, fp]
+        L.ptk_geometry_snapshot.argtypes = [vp]
+        L.ptk_render_motion.argtypes = [vp, C.POINTER(View)]
+        L.ptk_read_motion.argtypes = [vp, vp, vp, vp]
+        L.ptk_motion_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+        for fn in (L.ptk_reproject_planes_moving, L.ptk_reproject_planes_moving_device):
+            fn.argtypes = [vp, i32, i32, C.POINTER(View)] + [vp] * 12 + [C.POINTER(TemporalParams), vp, vp]
+        L.ptk_temporal_frame_moving.argtypes = [vp, C.POINTER(TemporalParams), u32]
+        L.ptk_last_motion_ms.argtypes = [vp, fp, fp]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -783,15 +793,24 @@ class Context:
                   "ptk_reproject_planes")
         return out, out_n
 
-    def temporal_frame(self, params, reset: bool = False, render_features: bool = True, seed: int = 0):
+    def temporal_frame(self, params, reset: bool = False, render_features: bool = True, seed: int = 0, moving: bool = False):
         """ptk_temporal_frame: carries the previous call's result into the frame in the accumulator and blends the two by sample
         counts (read_temporal); asynchronous.  reset: drop the history.  render_features: render the guide planes MATERIAL,
         POSITION and NORMAL first (sample 0 of `seed`, which replaces the planes of an earlier render_features); False uses the
-        caller's snapshot as it is."""
+        caller's snapshot as it is.  moving: ptk_temporal_frame_moving - the history follows the triangles that
+        update_geometry moved since snapshot_geometry (read_motion gives where they were); its guide planes are those three
+        with TRIANGLE and BARY."""
+        mask = (1 << FEAT_MATERIAL) | (1 << FEAT_POSITION) | (1 << FEAT_NORMAL)
+        if moving:
+            mask |= (1 << FEAT_TRIANGLE) | (1 << FEAT_BARY)
         if render_features:
-            self.render_features((1 << FEAT_MATERIAL) | (1 << FEAT_POSITION) | (1 << FEAT_NORMAL), 0, seed)
+            self.render_features(mask, 0, seed)
         prm = _temporal_params(params)
-        self._chk(self.L.ptk_temporal_frame(self.h, C.byref(prm), TEMPORAL_RESET if reset else 0), "ptk_temporal_frame")
+        flags = TEMPORAL_RESET if reset else 0
+        if moving:
+            self._chk(self.L.ptk_temporal_frame_moving(self.h, C.byref(prm), flags), "ptk_temporal_frame_moving")
+        else:
+            self._chk(self.L.ptk_temporal_frame(self.h, C.byref(prm), flags), "ptk_temporal_frame")
 
     def read_temporal(self):
         """(color [H][W][3], count [H][W]) float32 of the last temporal_frame, rows bottom-up like read_accum; waits for the stream."""
@@ -811,6 +830,71 @@ class Context:
         t = [C.c_float(0) for _ in range(2)]
         self._chk(self.L.ptk_last_temporal_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_temporal_ms")
         return dict(zip(("pack_ms", "kernel_ms"), (x.value for x in t)))
+
+    # ---- temporal reprojection over moving geometry ------------------------------------------
+    def snapshot_geometry(self):
+        """ptk_geometry_snapshot: keeps the resident vertices as they are now as the PREVIOUS geometry of render_motion and
+        temporal_frame(moving=True); on the context's stream, behind every update_geometry so far and ahead of every later one."""
+        self._chk(self.L.ptk_geometry_snapshot(self.h), "ptk_geometry_snapshot")
+
+    def render_motion(self, view=None):
+        """ptk_render_motion: for the feature planes TRIANGLE, BARY, POSITION and NORMAL of the last render_features, where each
+        pixel's surface point was at the snapshot, its normal there, and - under `view` (a View or a dict of its fields; None: NaN
+        everywhere) - its screen-space motion vector (read_motion); asynchronous."""
+        v = None if view is None else _view(view)
+        self._chk(self.L.ptk_render_motion(self.h, None if v is None else C.byref(v)), "ptk_render_motion")
+
+    def read_motion(self):
+        """(prev_position [H][W][3], prev_normal [H][W][3], motion [H][W][2]) float32 of the last render_motion or
+        temporal_frame(moving=True), rows bottom-up; motion = (columns, top-down rows) from the pixel to where its point was, NaN
+        on a miss and behind the view.  Waits for the stream."""
+        pp = np.empty((self.height, self.width, 3), dtype=np.float32)
+        pn = np.empty((self.height, self.width, 3), dtype=np.float32)
+        mv = np.empty((self.height, self.width, 2), dtype=np.float32)
+        self._chk(self.L.ptk_read_motion(self.h, pp.ctypes.data, pn.ctypes.data, mv.ctypes.data), "ptk_read_motion")
+        return pp, pn, mv
+
+    def motion_device_ptr(self):
+        """(prev_position, prev_normal, motion pointers, pixels): the planes of read_motion in device memory"""
+        a = C.c_void_p(); b = C.c_void_p(); m = C.c_void_p(); n = C.c_size_t()
+        self._chk(self.L.ptk_motion_device_ptr(self.h, C.byref(a), C.byref(b), C.byref(m), C.byref(n)), "ptk_motion_device_ptr")
+        return a.value, b.value, m.value, n.value
+
+    def reproject_planes_moving(self, hist_view, current, prev_position, prev_normal, history, params):
+        """ptk_reproject_planes_moving: reproject_planes in moving mode - prev_position and prev_normal [H, W, 3] say where the
+        current frame's points were in the history's geometry and what their normals were there (read_motion).  numpy arrays or
+        torch tensors, as reproject_planes."""
+        prm = _temporal_params(params)
+        view = _view(hist_view)
+        planes = list(current) + [prev_position, prev_normal] + list(history)
+        assert len(planes) == 12, "five current, two previous-geometry and five history planes"
+        H, W = int(planes[0].shape[0]), int(planes[0].shape[1])
+        px = H * W
+        if hasattr(planes[0], "data_ptr"):
+            import torch
+            five = [(torch.float32, 3), (torch.float32, 1), (torch.int32, 1), (torch.float32, 3), (torch.float32, 3)]
+            self._ray_tensors(planes, px, five + [(torch.float32, 3)] * 2 + five)
+            out = torch.empty((H, W, 3), dtype=torch.float32, device=planes[0].device)
+            out_n = torch.empty((H, W), dtype=torch.float32, device=planes[0].device)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if px else None
+            self._chk(self.L.ptk_reproject_planes_moving_device(self.h, W, H, C.byref(view), *(ptr(t) for t in planes), C.byref(prm),
+                                                                ptr(out), ptr(out_n)), "ptk_reproject_planes_moving_device")
+            return out, out_n
+        five = [(np.float32, (H, W, 3)), (np.float32, (H, W)), (np.int32, (H, W)), (np.float32, (H, W, 3)), (np.float32, (H, W, 3))]
+        shapes = five + [(np.float32, (H, W, 3))] * 2 + five
+        planes = [np.ascontiguousarray(a, dtype=d).reshape(sh) for a, (d, sh) in zip(planes, shapes)]
+        out = np.empty((H, W, 3), np.float32); out_n = np.empty((H, W), np.float32)
+        ptr = lambda a: a.ctypes.data if px else None
+        self._chk(self.L.ptk_reproject_planes_moving(self.h, W, H, C.byref(view), *(ptr(a) for a in planes), C.byref(prm), ptr(out),
+                                                     ptr(out_n)), "ptk_reproject_planes_moving")
+        return out, out_n
+
+    def last_motion_ms(self) -> dict:
+        """HIP-event times of the last render_motion or temporal_frame(moving=True): motion kernel, reprojection kernel (0 for
+        render_motion); waits for it."""
+        t = [C.c_float(0) for _ in range(2)]
+        self._chk(self.L.ptk_last_motion_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_motion_ms")
+        return dict(zip(("motion_ms", "temporal_ms"), (x.value for x in t)))
 
     # ---- lightmap baking -------------------------------------------------------------------
     def _bake_uvs(self, uvs, torch_side: bool):

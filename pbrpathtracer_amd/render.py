@@ -4,6 +4,8 @@
     python -m pbrpathtracer_amd.render scene.pts --noise-threshold 0.02 [--min-spp 16] [--step 8] --spp 1024
     python -m pbrpathtracer_amd.render scene.pts --spp 8 --denoise [--denoise-iterations K] [--npy denoised.npy]
     python -m pbrpathtracer_amd.render scene.pts --orbit FRAMES --orbit-degrees D --spp K --temporal [--denoise]
+    python -m pbrpathtracer_amd.render scene.pts --orbit FRAMES --spp K --temporal --move-object OBJ --move-by DX DY DZ
+                                                 [--motion-vectors FILE.npy]
     python -m pbrpathtracer_amd.render scene.pts --features planes.npz
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz
@@ -30,6 +32,13 @@ in FRAMES equal steps - an interactive session's camera drag.  At each step the 
 extent), which carries the steps before it into the new view.  The PNG is the last view: the reprojected frame - after --denoise
 filtered by Context.denoise_planes with the guide planes TemporalFrame rendered - or, without --temporal, the plain last frame of
 --spp samples, for comparison.  --npy holds the float32 image [H, W, 3], rows top-down.
+
+With --move-object OBJ --move-by DX DY DZ the orbit also drags an object: object OBJ of the scene file is translated by the total
+(DX, DY, DZ) in FRAMES equal steps through PathTracer.SetObjectTransform (a BVH refit per step, no rebuild), and with --temporal
+each step ends in PathTracer.TemporalFrameMoving (include/ptk.h ptk_temporal_frame_moving) under PathTracer.TrackMotion, so that
+the object's samples follow it instead of being thrown away or smeared.  --motion-vectors FILE.npy writes the last step's
+screen-space motion vectors, float32 [H, W, 2] = (columns, rows) from each pixel to where its surface point was in the step before,
+rows top-down, NaN where the pixel sees nothing.
 
 With --equirect WIDTH the image is a WIDTH x WIDTH/2 latitude-longitude panorama from the scene's camera position, traced through
 PathTracer.TraceRays (include/ptk.h ptk_trace_rays; rays.equirect_rays) instead of the perspective camera.
@@ -87,6 +96,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="turn the camera about the scene's centre in FRAMES steps, --spp samples after a reset at each; the image is the last view")
     ap.add_argument("--orbit-degrees", type=float, default=10.0, metavar="D", help="--orbit: the whole turn in degrees (default 10)")
     ap.add_argument("--temporal", action="store_true", help="--orbit: carry each step's samples into the next by temporal reprojection")
+    ap.add_argument("--move-object", type=int, default=None, metavar="OBJ", help="--orbit: also translate object OBJ of the scene file, by --move-by over the steps")
+    ap.add_argument("--move-by", type=float, nargs=3, default=None, metavar=("DX", "DY", "DZ"), help="--move-object: the whole translation in world units")
+    ap.add_argument("--motion-vectors", metavar="FILE.npy", default=None,
+                    help="--move-object with --temporal: write the last step's motion vectors, float32 [H, W, 2], rows top-down")
     ap.add_argument("--features", metavar="FILE.npz", default=None,
                     help="also write the first-hit feature planes (depth, triangle, material, bary, position, normal_geom, normal, "
                          "albedo, emission, gloss; sample 0) to this .npz, rows top-down like the PNG")
@@ -366,16 +379,26 @@ def render_orbit(pt, a) -> int:
     w, h = pt.GetResolution()
     out = np.zeros((h, w, 3), np.uint8)
     pt.SetOutImage(out)
+    moving = a.move_object is not None
+    if moving:
+        base = pt.GetObjectTransform(a.move_object)
+        pt.TrackMotion(True)
     t1 = time.time()
-    for pos, dir_, up in orbit_cameras(pt, a.orbit, a.orbit_degrees):
+    for k, (pos, dir_, up) in enumerate(orbit_cameras(pt, a.orbit, a.orbit_degrees)):
         pt.SetCamera(pos, dir_, up)
+        if moving:
+            M = base.copy()
+            M[3][:3] += np.asarray(a.move_by, np.float32) * np.float32((k + 1) / a.orbit)
+            pt.SetObjectTransform(a.move_object, M)
         pt.ResetImage()
         pt.RenderFrames(a.spp)
         if pt.LastError():
             raise RuntimeError(pt.LastError())
         if a.temporal:
-            pt.TemporalFrame()
+            pt.TemporalFrameMoving() if moving else pt.TemporalFrame()
     t2 = time.time()
+    if a.motion_vectors:
+        np.save(a.motion_vectors, np.ascontiguousarray(pt.ReadMotion()[2][::-1], np.float32))
     if a.temporal:
         image, count = pt.ReadTemporal()
         if a.denoise:
@@ -418,6 +441,12 @@ def main(argv=None):
         return 1
     if a.temporal and a.orbit is None:
         print("error: --temporal goes with --orbit", file=sys.stderr)
+        return 1
+    if (a.move_object is None) != (a.move_by is None) or (a.move_object is not None and a.orbit is None):
+        print("error: --move-object and --move-by go together and with --orbit", file=sys.stderr)
+        return 1
+    if a.motion_vectors and not (a.temporal and a.move_object is not None):
+        print("error: --motion-vectors goes with --temporal and --move-object", file=sys.stderr)
         return 1
     if a.orbit is not None:
         if a.orbit < 1 or a.noise_threshold is not None or a.bake_lightmap is not None or a.bake_probes is not None or \
