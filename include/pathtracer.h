@@ -27,6 +27,7 @@ struct ptk_adaptive_result;
 struct ptk_rays_adaptive_result;
 struct ptk_denoise_params;
 struct ptk_temporal_params;
+struct ptk_variance_params;
 struct ptk_view;
 
 const float EPS = 0.00001f;      // mesh.h:12
@@ -232,6 +233,19 @@ public:
     void TrackMotion(bool on);
     bool TemporalFrameMoving(const ptk_temporal_params& params, bool reset = false);
     bool ReadMotion(float* prev_position, float* prev_normal, float* motion);
+    // Extensions: the temporal half of SVGF up to the filter (include/ptk.h ptk_temporal_frame_moments, ptk_temporal_variance,
+    // ptk_denoise_temporal).  TemporalFrameMoments() is TemporalFrame() - moving: TemporalFrameMoving() - that also carries the
+    // first and second moment of demodulated luminance; it shares history, result and ReadTemporal with the two, but a moments
+    // call behind a plain one starts its history over.  It renders the guide planes (that call's with ALBEDO; TRIANGLE and
+    // EMISSION come along for DenoiseTemporal()) when they are missing or stale.  TemporalVariance(): the per-pixel variance of
+    // the accumulated value from those moments.  ReadTemporalVariance: W*H*2 floats and W*H floats, rows bottom-up, either may be
+    // NULL.  DenoiseTemporal(): the a-trous filter over the temporal result on the device - variance: guided by
+    // TemporalVariance()'s plane - into the plane ReadDenoised and ResolveDenoised serve.  Pending edits are NOT applied; the
+    // image, the sample count and the hand-off buffer are not touched.
+    bool TemporalFrameMoments(const ptk_temporal_params& params, bool reset = false, bool moving = false);
+    bool TemporalVariance(const ptk_variance_params& params);
+    bool ReadTemporalVariance(float* moments, float* variance);
+    bool DenoiseTemporal(const ptk_denoise_params& params, bool variance = true);
     // The (object, element) under pixel (x, y), y counted from the top row: one ray (ptk_pick), pending edits applied first.
     // A pixel that sees nothing gives -1 / -1 (and triangle -1) and true; false: no scene / resolution yet, or (x, y) outside the frame.
     bool Pick(int x, int y, int* objId, int* elementId, int* triangle = nullptr);

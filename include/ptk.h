@@ -490,7 +490,8 @@ int ptk_closest_stats(ptk_ctx* ctx, int32_t num_points, const float* d_points, c
  * through every iteration, colour and variance alike, and are never a tap: what they hold - NaN, 1e30 - reaches no other pixel.
  * AFTER THE LAST ITERATION valid pixels with an albedo plane get out_c = c_c * A_c; invalid pixels get out = color, the input bits
  * (and out_variance = variance, the input bits).
- * Deliberately left out: exp-shaped weights (not the same bits on the GPU and in numpy), SVGF's 3x3 prefilter of the variance,
+ * Deliberately left out: exp-shaped weights (not the same bits on the GPU and in numpy), SVGF's 3x3 prefilter of the variance
+ * (ptk_variance_planes below applies it to the plane it makes),
  * temporal accumulation inside the filter (ptk_temporal_frame below runs in front of it), bilinear filtering of the guides.
  *   ptk_denoise_planes: host arrays, synchronous; the planes and the requested outputs are staged in device memory for the length
  *     of the call.  albedo, variance and out_variance may be NULL; out_variance needs variance.
@@ -585,7 +586,8 @@ int ptk_last_denoise_ms(ptk_ctx* ctx, float* pack_ms, float* filter_ms, float* u
  * Deliberately NOT this: moving geometry (after ptk_update_geometry the history is stale where triangles moved: the caller passes
  * PTK_TEMPORAL_RESET or accepts ghosting - or calls ptk_temporal_frame_moving / ptk_reproject_planes_moving below instead, which
  * follow the triangles); view-dependent radiance (outgoing radiance is treated as view-independent, which is
- * exact for Lambertian surfaces - glossy ones lag); a variance output; clamping of the history to the neighbourhood's colour range.
+ * exact for Lambertian surfaces - glossy ones lag); a variance output (ptk_temporal_frame_moments further below has one);
+ * clamping of the history to the neighbourhood's colour range.
  *   ptk_reproject_planes: host arrays, synchronous; the planes and the outputs are staged in device memory for the length of the call.
  *   ptk_reproject_planes_device: every array in memory of this context's GPU, asynchronous on the context's stream, no host wait -
  *     except that the context's 48 B per pixel of packed history grow, behind a drain of the stream, when a call is larger than
@@ -707,6 +709,126 @@ int ptk_temporal_frame_moving(ptk_ctx* ctx, const ptk_temporal_params* params, u
 /* measurement hook (tools/motion_timing.py), not part of the feature.  HIP-event times of the last ptk_render_motion or
  * ptk_temporal_frame_moving: motion_kernel, and the reprojection kernel behind it (0 for ptk_render_motion); waits for the call */
 int ptk_last_motion_ms(ptk_ctx* ctx, float* motion_ms, float* temporal_ms);
+
+/* ---- temporal luminance moments, the variance of the accumulated value, and the denoiser behind them (no counterpart in the reference)
+ * The denoiser's luminance edge-stop is noise-aware only with a variance plane, and an interactive frame - a few samples, a history
+ * carried by reprojection - has none: ptk_denoise_frame's comes from an adaptive render.  This is the missing link of SVGF (Schied et
+ * al. 2017): the first and second moment of demodulated luminance ride through the reprojection with the colour, become a per-pixel
+ * variance of the ACCUMULATED value - with SVGF's spatial estimate where the history is short, and its 3x3 prefilter -, and the
+ * a-trous filter runs over the temporal result without leaving the device.
+ * THE RULE.  Every operation is one IEEE float32 operation in the order written (the kernels are compiled with -ffp-contract=off);
+ * only + - * /, comparisons and floor occur; dot and x > y ? x : y are as the temporal and the denoise rule define them (a NaN
+ * operand yields the second value).  L(d) = ((0.2126f*d_r) + (0.7152f*d_g)) + (0.0722f*d_b).  The numpy restatement is
+ * tests/variance_rule.py (tests/test_gpu_variance.py: array_equal).
+ * MOMENTS THROUGH THE REPROJECTION: the temporal rule - static, or MOVING with the primed geometry - with one more pair of channels.
+ *   current moments   of a valid pixel (id_p >= 0) with nc = count_p > 0:  with an albedo plane A_c = albedo_c + 0.00390625f;
+ *                     d_c = color_c / A_c, without d = color;  l = L(d);  cm1 = l;  cm2 = l*l.  Otherwise cm1 = cm2 = 0.  In the
+ *                     frame entry color_c = S1_c / (float)n_p exactly as ptk_temporal_frame takes it, and albedo is ALBEDO.
+ *   taps              every tap the temporal rule takes also adds  sm1 = sm1 + (b*hist_m1_q);  sm2 = sm2 + (b*hist_m2_q)  - the same
+ *                     taps, order and predicates; out_color and out_count are bit for bit those of the rule without moments.
+ *   blend             with history (sw > 0):  hm1 = sm1 / sw;  hm2 = sm2 / sw;  nc == 0: the output moments are (hm1, hm2); otherwise
+ *                     out_m1 = ((hm1*hn) + (cm1*nc)) / tot and likewise m2, with the capped hn and tot of the colour blend.
+ *                     Without history: (cm1, cm2).  An invalid pixel: (0, 0).
+ * VARIANCE of the accumulated demodulated luminance.  Per pixel: moments (m1, m2), the blended count n, the current frame's own
+ * count f, id, position, normal; rows as stored - the rule never flips.  Parameters: ptk_variance_params below; zz =
+ * max_plane_dist*max_plane_dist.
+ *   no variance       id_p < 0 or !(n > 0):  raw = 0
+ *   frames            fr = f > 0 ? n / f : 1.0f - the length of the history in frames like the current one
+ *   temporal          fr >= min_frames:  v = m2 - (m1*m1);  v = v > 0 ? v : 0;  raw = v / (fr - 1.0f)  - the variance of a mean of fr
+ *                     frames; the pixel reads no neighbour
+ *   spatial           otherwise (a short history; a NaN fr as well): over the window dy = -r..r outer, dx = -r..r inner, both
+ *                     ascending, with s1 = s2 = k = 0.  The centre is always taken, in its place in that order.  Another tap q is
+ *                     taken iff it lies in the image, id_q == id_p, n_q > 0, z = dot(normal_p, position_q - position_p) has
+ *                     z*z <= zz, and dot(normal_p, normal_q) >= min_normal_dot.  A taken tap adds  s1 = s1 + m1_q;  s2 = s2 + m2_q;
+ *                     k = k + 1.0f.  Then a1 = s1 / k;  a2 = s2 / k;  vs = a2 - (a1*a1);  vs = vs > 0 ? vs : 0;  raw = vs / fr
+ *   prefilter         prefilter == 0: var = raw.  Otherwise, with g = (0.25f, 0.5f, 0.25f), over j = 0..2 (dy = j-1) outer, i = 0..2
+ *                     (dx = i-1) inner and the taps q inside the image with id_q >= 0 and n_q > 0:  sv = sv + ((g[j]*g[i]) * raw_q);
+ *                     sw = sw + (g[j]*g[i]);  then var = sv / sw.  A centre that has no variance (the first line) gets var = 0.
+ * Taps are read from clamped addresses and dropped by their predicates, as in the two filters above; every loop is bounded (4, at
+ * most 49, and 9 taps); what an invalid pixel holds - NaN, 1e30 - reaches no other pixel.
+ * Deliberately NOT this: re-filtering of the variance inside each a-trous iteration, clamping of the history's colour, view-
+ * dependent radiance.
+ *   ptk_reproject_moments: host arrays, synchronous, staged like ptk_reproject_planes; ptk_reproject_moments_device: every array in
+ *     memory of this context's GPU, asynchronous on the context's stream - the packed-history buffer of ptk_reproject_planes_device
+ *     and 16 B per pixel more for the history's moments grow as there.  One descriptor instead of 25 arguments: prev_position and
+ *     prev_normal both NULL select the static rule, both set the MOVING one, one alone is PTK_ERR_BAD_ARG; albedo may be NULL;
+ *     everything else is required.  The outputs may not alias an input.
+ *   ptk_temporal_frame_moments: ptk_temporal_frame - under PTK_TEMPORAL_MOVING ptk_temporal_frame_moving - plus the moments; flags
+ *     PTK_TEMPORAL_RESET | PTK_TEMPORAL_MOVING.  It needs that entry's guide planes and ALBEDO.  It shares the colour history, the
+ *     result planes and their readers with the two, and keeps each pixel's n_p of the call for the variance.  The moment history
+ *     is valid only if the previous frame call was a moments call too; otherwise the call uses NO history, colour included, as
+ *     under PTK_TEMPORAL_RESET (a fresh moment pair behind a long colour count would claim a variance of 0).  A plain
+ *     ptk_temporal_frame or ptk_temporal_frame_moving behind a moments call continues the colour history as ever and invalidates
+ *     the moments.  Memory: 52 B per pixel beside the 112 B of ptk_temporal_frame - a fourth float4 image (m1, m2, count, n_p) in
+ *     each of the two history sets, the unpacked moments (8 B), the raw and the final variance (4 B each) and the mask of
+ *     ptk_denoise_temporal (4 B) -, allocated by the first moments call, freed with the temporal buffers.
+ *   ptk_temporal_variance: ptk_variance_planes_device over the last moments call's moments, blended count, kept n_p and that
+ *     call's MATERIAL, POSITION and NORMAL (read from the history set the call wrote: nothing is packed), into a context-owned
+ *     plane; asynchronous.  PTK_ERR_BAD_ARG unless the last frame call at the current resolution was a successful moments call.
+ *   ptk_read_temporal_variance (either pointer may be NULL; waits for the stream), ptk_temporal_variance_device_ptr: the unpacked
+ *     moments [H][W][2] and the variance [H][W].  PTK_ERR_BAD_ARG as for ptk_temporal_variance, and when the variance is asked for
+ *     before a ptk_temporal_variance behind the last moments call.
+ *   ptk_variance_planes: host arrays, synchronous; ptk_variance_planes_device: device arrays, asynchronous - except that the
+ *     context's 52 B per pixel of packed images grow, behind a drain of the stream, when a call is larger than every one before.
+ *     Both need no scene, no camera and no frame; out_variance may not alias an input.
+ *   ptk_denoise_temporal: by definition ptk_denoise_planes_device with color = the temporal colour (of any of the three frame
+ *     entries), mask_p = (count_p > 0 && TRIANGLE_p >= 0 && EMISSION_p == 0 in all three channels) ? 0 : -1 with the temporal count,
+ *     the feature planes NORMAL, POSITION and ALBEDO, and - under PTK_DENOISE_VARIANCE - variance = the plane of
+ *     ptk_temporal_variance, else none.  The result goes into the context's denoised plane, so ptk_read_denoised,
+ *     ptk_denoised_device_ptr and ptk_resolve_denoised_rgb8 serve it.  No host round trip.  PTK_ERR_BAD_ARG when one of the five
+ *     planes is missing from the last ptk_render_features or the resolution has changed since, when there is no temporal result,
+ *     and under the flag when no ptk_temporal_variance has run behind the last moments call.
+ * PTK_ERR_BAD_ARG further: a null context, descriptor, params, view or required array with a non-zero size, width or height < 0,
+ * the temporal and denoise parameters as their entries refuse them, radius outside 1..3, prefilter neither 0 nor 1, min_frames not
+ * finite or < 2, max_plane_dist not finite or <= 0, min_normal_dot not finite or outside [-1, 1], an unknown flag bit.  A refused
+ * call leaves every output, the history and the moments alone.  A zero-sized image is PTK_OK and does nothing.  PTK_ERR_LIMIT:
+ * more than 2^28 pixels or 262140 rows.  None of these entries touches the accumulator, counts and S2, the sample count, the 8-bit
+ * image, a bound hand-off buffer, the feature planes or the adaptive state. */
+typedef struct ptk_reproject_desc {
+    int32_t width, height;
+    const ptk_view* hist_view;
+    const float* color;             /* [H][W][3]   the current frame, as ptk_reproject_planes takes it */
+    const float* count;             /* [H][W] */
+    const int32_t* id;              /* [H][W] */
+    const float* position;          /* [H][W][3] */
+    const float* normal;            /* [H][W][3] */
+    const float* prev_position;     /* [H][W][3]   both NULL: the static rule; both set: MOVING */
+    const float* prev_normal;       /* [H][W][3] */
+    const float* albedo;            /* [H][W][3] or NULL: no demodulation */
+    const float* hist_color;        /* the history: the same five planes ... */
+    const float* hist_count;
+    const int32_t* hist_id;
+    const float* hist_position;
+    const float* hist_normal;
+    const float* hist_moments;      /* [H][W][2]   ... and its moments */
+    float* out_color;               /* [H][W][3] */
+    float* out_count;               /* [H][W] */
+    float* out_moments;             /* [H][W][2] */
+} ptk_reproject_desc;
+int ptk_reproject_moments(ptk_ctx* ctx, const ptk_reproject_desc* desc, const ptk_temporal_params* params);
+int ptk_reproject_moments_device(ptk_ctx* ctx, const ptk_reproject_desc* desc, const ptk_temporal_params* params);
+#define PTK_TEMPORAL_MOVING 2u   /* taken by ptk_temporal_frame_moments only */
+int ptk_temporal_frame_moments(ptk_ctx* ctx, const ptk_temporal_params* params, uint32_t flags);
+typedef struct ptk_variance_params {
+    int32_t radius;         /* 1..3: the spatial estimate's window is (2*radius+1)^2 */
+    int32_t prefilter;      /* 0 or 1: the 3x3 binomial over the raw variance */
+    float min_frames;       /* finite, >= 2: a history of fewer frames takes the spatial estimate */
+    float max_plane_dist;   /* finite, > 0, and ... */
+    float min_normal_dot;   /* ... finite, in [-1, 1]: the spatial taps' plane and normal tests, as ptk_temporal_params' */
+} ptk_variance_params;
+int ptk_variance_planes(ptk_ctx* ctx, int width, int height, const float* moments /*[H][W][2]*/, const float* count /*[H][W]*/,
+                        const float* frame_count /*[H][W]*/, const int32_t* id /*[H][W]*/, const float* position /*[H][W][3]*/,
+                        const float* normal /*[H][W][3]*/, const ptk_variance_params* params, float* out_variance /*[H][W]*/);
+int ptk_variance_planes_device(ptk_ctx* ctx, int width, int height, const float* d_moments, const float* d_count, const float* d_frame_count,
+                               const int32_t* d_id, const float* d_position, const float* d_normal, const ptk_variance_params* params,
+                               float* d_out_variance);
+int ptk_temporal_variance(ptk_ctx* ctx, const ptk_variance_params* params);
+int ptk_read_temporal_variance(ptk_ctx* ctx, float* moments /*[H][W][2] or NULL*/, float* variance /*[H][W] or NULL*/);
+int ptk_temporal_variance_device_ptr(ptk_ctx* ctx, void** moments, void** variance, size_t* pixels);
+int ptk_denoise_temporal(ptk_ctx* ctx, const ptk_denoise_params* params, uint32_t flags);
+/* measurement hook (tools/variance_timing.py), not part of the feature.  HIP-event times of the last variance call's
+ * variance_kernel and its prefilter (0 without one); waits for the call */
+int ptk_last_variance_ms(ptk_ctx* ctx, float* variance_ms, float* prefilter_ms);
 
 /* ---- lightmap baking: the radiance leaving the scene's surfaces, per texel of a uv chart layout (no counterpart in the reference) --
  * The surface half of light baking in front of and behind ptk_trace_rays' kernel: a uv rasteriser, a ray generator, a scatter and

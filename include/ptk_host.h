@@ -87,6 +87,13 @@ int  pth_get_view(pth_tracer* t, ptk_view* out);
 void pth_track_motion(pth_tracer* t, int on);
 int  pth_temporal_frame_moving(pth_tracer* t, const ptk_temporal_params* params, int reset);
 int  pth_read_motion(pth_tracer* t, float* prev_position, float* prev_normal, float* motion);
+/* TemporalFrameMoments / TemporalVariance / ReadTemporalVariance / DenoiseTemporal (the moments of demodulated luminance through
+ * the reprojection, the variance made of them and the denoiser over the temporal result; include/ptk.h ptk_temporal_frame_moments):
+ * 1 on success; either pointer of pth_read_temporal_variance may be NULL */
+int  pth_temporal_frame_moments(pth_tracer* t, const ptk_temporal_params* params, int reset, int moving);
+int  pth_temporal_variance(pth_tracer* t, const ptk_variance_params* params);
+int  pth_read_temporal_variance(pth_tracer* t, float* moments, float* variance);
+int  pth_denoise_temporal(pth_tracer* t, const ptk_denoise_params* params, int variance);
 /* ClosestPoints (the nearest surface point to caller-supplied points, include/ptk.h ptk_closest_points): 1 on success */
 int  pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point,
                         float* bary);

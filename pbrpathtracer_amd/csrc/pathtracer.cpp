@@ -931,6 +931,68 @@ bool PathTracer::TemporalFrameMoving(const ptk_temporal_params& params, bool res
     return rc == PTK_OK;
 }
 
+// TemporalFrame() - moving: TemporalFrameMoving() - with the moments of demodulated luminance (ptk_temporal_frame_moments).  Its
+// guide planes are that call's with ALBEDO; TRIANGLE and EMISSION come along for DenoiseTemporal().
+bool PathTracer::TemporalFrameMoments(const ptk_temporal_params& params, bool reset, bool moving)
+{
+    if (!m->scene_uploaded || !m->have_resolution || !m->ctx) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    uint32_t need = (1u << PTK_FEAT_MATERIAL) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL) | (1u << PTK_FEAT_ALBEDO);
+    if (moving) need |= (1u << PTK_FEAT_TRIANGLE) | (1u << PTK_FEAT_BARY);
+    const uint32_t all = need | (1u << PTK_FEAT_TRIANGLE) | (1u << PTK_FEAT_EMISSION);
+    int rc = PTK_OK;
+    if ((m->feat_mask & need) != need || m->feat_sample != 0 || m->feat_seed != m->seed || m->feat_epoch != m->view_epoch)
+    {
+        rc = ptk_render_features(m->ctx, 0, m->seed, all);
+        m->note(rc);
+        m->feat_mask = rc == PTK_OK ? all : 0u; m->feat_sample = 0; m->feat_seed = m->seed; m->feat_epoch = m->view_epoch;
+    }
+    if (rc == PTK_OK && moving && m->track_motion && !m->snapshot_taken) { rc = ptk_geometry_snapshot(m->ctx); m->note(rc); }
+    if (rc == PTK_OK)
+    {
+        rc = ptk_temporal_frame_moments(m->ctx, &params, (reset ? PTK_TEMPORAL_RESET : 0u) | (moving ? PTK_TEMPORAL_MOVING : 0u));
+        m->note(rc);
+    }
+    if (rc == PTK_OK) m->snapshot_taken = false;
+    return rc == PTK_OK;
+}
+
+bool PathTracer::TemporalVariance(const ptk_variance_params& params)
+{
+    if (!m->ctx) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const int rc = ptk_temporal_variance(m->ctx, &params);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ReadTemporalVariance(float* moments, float* variance)
+{
+    if (!m->ctx) return false;
+    const int rc = ptk_read_temporal_variance(m->ctx, moments, variance);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+// The denoiser over the last TemporalFrame*() result (ptk_denoise_temporal), on the device.  No pending edit is applied; the
+// guide planes are those the temporal call used or rendered, and they are rendered here only when one of the five is missing.
+bool PathTracer::DenoiseTemporal(const ptk_denoise_params& params, bool variance)
+{
+    if (!m->scene_uploaded || !m->have_resolution || !m->ctx) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const uint32_t need = (1u << PTK_FEAT_TRIANGLE) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL) | (1u << PTK_FEAT_ALBEDO) | (1u << PTK_FEAT_EMISSION);
+    int rc = PTK_OK;
+    if ((m->feat_mask & need) != need || m->feat_sample != 0 || m->feat_seed != m->seed || m->feat_epoch != m->view_epoch)
+    {
+        const uint32_t all = m->feat_mask | need;
+        rc = ptk_render_features(m->ctx, 0, m->seed, all);
+        m->note(rc);
+        m->feat_mask = rc == PTK_OK ? all : 0u; m->feat_sample = 0; m->feat_seed = m->seed; m->feat_epoch = m->view_epoch;
+    }
+    if (rc == PTK_OK) { rc = ptk_denoise_temporal(m->ctx, &params, variance ? PTK_DENOISE_VARIANCE : 0u); m->note(rc); }
+    return rc == PTK_OK;
+}
+
 void PathTracer::TrackMotion(bool on)
 {
     std::lock_guard<std::mutex> render_guard(m->render_mu);

@@ -11,7 +11,7 @@
 
 using namespace ptk;
 
-static int check_denoise_params(ptk_ctx* c, const char* who, const ptk_denoise_params* p)
+int ptk::check_denoise_params(ptk_ctx* c, const char* who, const ptk_denoise_params* p)
 {
     if (!p) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": null params");
     if (p->iterations < 1 || p->iterations > 8) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": iterations outside 1..8");
@@ -87,6 +87,13 @@ static int planes_on_stream(ptk_ctx* c, int width, int height, const float* d_co
     k.width = width; k.height = height;
     launch_denoise_pack(k, im, c->stream);
     return filter_on_stream(c, width, height, im, d_variance != nullptr, p, d_albedo, d_out_color, d_out_variance);
+}
+
+int ptk::denoise_planes_on_stream(ptk_ctx* c, int width, int height, const float* d_color, const int32_t* d_mask, const float* d_normal,
+                                  const float* d_position, const float* d_albedo, const float* d_variance, const ptk_denoise_params& p,
+                                  float* d_out_color, float* d_out_variance)
+{
+    return planes_on_stream(c, width, height, d_color, d_mask, d_normal, d_position, d_albedo, d_variance, p, d_out_color, d_out_variance);
 }
 
 static bool have_denoised(const ptk_ctx* c) { return c->d_denoised && c->den_w == c->width && c->den_h == c->height && c->den_w > 0; }

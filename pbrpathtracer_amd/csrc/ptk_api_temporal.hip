@@ -1,6 +1,7 @@
 // Host side of the ptk C-ABI: temporal reprojection for image planes and for the context's frame (ptk.h ptk_get_view,
 // ptk_reproject_planes, ptk_temporal_frame), and its moving-geometry mode with the motion planes (ptk.h
-// ptk_geometry_snapshot, ptk_render_motion, ptk_reproject_planes_moving, ptk_temporal_frame_moving).
+// ptk_geometry_snapshot, ptk_render_motion, ptk_reproject_planes_moving, ptk_temporal_frame_moving), and the
+// moments of demodulated luminance carried through either (ptk.h ptk_reproject_moments, ptk_temporal_frame_moments).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -58,12 +59,15 @@ static void fill_view(TemporalParams& k, const ptk_view& v, const ptk_temporal_p
 static int planes_on_stream(ptk_ctx* c, int width, int height, const ptk_view& view, const float* d_color, const float* d_count, const int32_t* d_id,
                             const float* d_position, const float* d_normal, const float* d_hist_color, const float* d_hist_count,
                             const int32_t* d_hist_id, const float* d_hist_position, const float* d_hist_normal, const ptk_temporal_params& p,
-                            float* d_out_color, float* d_out_count, const float* d_prev_position = nullptr, const float* d_prev_normal = nullptr)
+                            float* d_out_color, float* d_out_count, const float* d_prev_position = nullptr, const float* d_prev_normal = nullptr,
+                            const float* d_albedo = nullptr, const float* d_hist_moments = nullptr, float* d_out_moments = nullptr)
 {
     c->temporal_timed = false;
     if (c->motion_timed == 2) c->motion_timed = 1;      // (ev_temporal stops being the kernel behind the last motion_kernel)
     const size_t px = (size_t)width * height;
     if (const int rc = grow(c, c->d_temporal_pack, c->temporal_pack_px, px, 3 * sizeof(float4)); rc != PTK_OK) return rc;
+    if (d_out_moments)
+        if (const int rc = grow(c, c->d_temporal_pack_mm, c->temporal_pack_mm_px, px, sizeof(float4)); rc != PTK_OK) return rc;
     if (const int rc = ensure_events(c, c->ev_temporal); rc != PTK_OK) return rc;
     TemporalImages im = { c->d_temporal_pack, c->d_temporal_pack + px, c->d_temporal_pack + 2 * px };
     HIPCHK(c, hipEventRecord(c->ev_temporal[0], c->stream));
@@ -71,12 +75,14 @@ static int planes_on_stream(ptk_ctx* c, int width, int height, const ptk_view& v
     pk.color = d_hist_color; pk.count = d_hist_count; pk.id = d_hist_id; pk.position = d_hist_position; pk.normal = d_hist_normal;
     pk.width = width; pk.height = height;
     launch_temporal_pack(pk, im, c->stream);
+    if (d_out_moments) launch_temporal_pack_moments(d_hist_moments, c->d_temporal_pack_mm, width, height, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_temporal[1], c->stream));
     TemporalParams k = {};
     k.color = d_color; k.count = d_count; k.id = d_id; k.position = d_position; k.normal = d_normal;
     k.hist = im; k.out_color = d_out_color; k.out_count = d_out_count; k.width = width; k.height = height;
     k.prev_position = d_prev_position; k.prev_normal = d_prev_normal;
+    k.albedo = d_albedo; k.hist_mm = d_out_moments ? c->d_temporal_pack_mm : nullptr; k.out_moments = d_out_moments;
     fill_view(k, view, p);
     launch_temporal(k, c->stream);
     HIPCHK(c, hipGetLastError());
@@ -85,15 +91,12 @@ static int planes_on_stream(ptk_ctx* c, int width, int height, const ptk_view& v
     return PTK_OK;
 }
 
-static bool have_temporal(const ptk_ctx* c) { return c->d_temporal && c->temporal_w == c->width && c->temporal_h == c->height && c->temporal_w > 0; }
-// the frame entry's buffer cut up: history set 0 | history set 1 | colour | count
+// a history set of the frame entries' buffer (ptk_ctx.h cuts up the rest)
 static TemporalImages temporal_set(const ptk_ctx* c, size_t px, int set)
 {
     float4* b = c->d_temporal + (size_t)set * 3 * px;
     return { b, b + px, b + 2 * px };
 }
-static float* temporal_color(const ptk_ctx* c, size_t px) { return (float*)(c->d_temporal + 6 * px); }
-static float* temporal_count(const ptk_ctx* c, size_t px) { return temporal_color(c, px) + 3 * px; }
 
 static bool have_motion(const ptk_ctx* c) { return c->d_motion && c->motion_w == c->width && c->motion_h == c->height && c->motion_w > 0; }
 // the motion buffer cut up: previous position | previous normal | motion
@@ -143,18 +146,26 @@ static int motion_on_stream(ptk_ctx* c, const ptk_view* view)
     return PTK_OK;
 }
 
-// ptk_temporal_frame and ptk_temporal_frame_moving
-static int temporal_frame(ptk_ctx* c, const char* who, const ptk_temporal_params* params, uint32_t flags, bool moving)
+// ptk_temporal_frame, ptk_temporal_frame_moving and - moments - ptk_temporal_frame_moments
+static int temporal_frame(ptk_ctx* c, const char* who, const ptk_temporal_params* params, uint32_t flags, bool moving, bool moments = false)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     if (const int rc = check_temporal_params(c, who, params); rc != PTK_OK) return rc;
     if (flags & ~PTK_TEMPORAL_RESET) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": unknown flag bit");
     if (!c->d_primary || !accum_ptr(c)) return fail(c, PTK_ERR_BAD_ARG, "ptk_set_frame has not been called");
     uint32_t need = (1u << PTK_FEAT_MATERIAL) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL);
+    if (moments) need |= 1u << PTK_FEAT_ALBEDO;
     if (moving)
     {
         need |= (1u << PTK_FEAT_TRIANGLE) | (1u << PTK_FEAT_BARY);
-        if (const int rc = check_motion_state(c, who, need, "MATERIAL, TRIANGLE, BARY, POSITION or NORMAL"); rc != PTK_OK) return rc;
+        if (const int rc = check_motion_state(c, who, need, moments ? "MATERIAL, TRIANGLE, BARY, POSITION, NORMAL or ALBEDO" : "MATERIAL, TRIANGLE, BARY, POSITION or NORMAL"); rc != PTK_OK)
+            return rc;
+    }
+    else if (moments)
+    {
+        if (c->feat_w != c->width || c->feat_h != c->height || c->feat_w == 0)
+            return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": no feature planes for the current resolution: ptk_render_features first");
+        if ((c->feat_mask & need) != need) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": the last ptk_render_features lacks MATERIAL, POSITION, NORMAL or ALBEDO");
     }
     else
     {
@@ -167,12 +178,15 @@ static int temporal_frame(ptk_ctx* c, const char* who, const ptk_temporal_params
     // (ptk_set_frame with another resolution has freed the buffer with the feature planes: there is no history then)
     const bool fresh = !have_temporal(c);
     if (!c->d_temporal) HIPCHK(c, hipMalloc(&c->d_temporal, px * 7 * sizeof(float4)));
+    if (moments && !c->d_temporal_mm) HIPCHK(c, hipMalloc(&c->d_temporal_mm, px * kTemporalMomentsBytes));
     ptk_view now;
     if (const int rc = ptk_get_view(c, &now); rc != PTK_OK) return rc;
     c->temporal_timed = false;
     if (c->motion_timed == 2) c->motion_timed = 1;
     if (const int rc = ensure_events(c, c->ev_temporal); rc != PTK_OK) return rc;
-    const bool with_history = !fresh && !(flags & PTK_TEMPORAL_RESET);
+    // (a moments call behind a plain one starts over, colour included: a fresh moment pair behind a long colour count would
+    // report no variance at all)
+    const bool with_history = !fresh && !(flags & PTK_TEMPORAL_RESET) && (!moments || c->temporal_moments);
     if (moving)
         if (const int rc = motion_on_stream(c, with_history ? &c->temporal_view : nullptr); rc != PTK_OK) return rc;
     const bool adaptive = c->adaptive_accum && c->d_counts && c->d_moments;
@@ -185,6 +199,12 @@ static int temporal_frame(ptk_ctx* c, const char* who, const ptk_temporal_params
     k.next = temporal_set(c, px, next);
     k.out_color = temporal_color(c, px); k.out_count = temporal_count(c, px); k.width = c->width; k.height = c->height;
     if (moving) { k.prev_position = motion_prev_position(c, px); k.prev_normal = motion_prev_normal(c, px); }
+    if (moments)
+    {
+        k.albedo = (const float*)c->d_feat[PTK_FEAT_ALBEDO]; k.out_moments = temporal_moments_plane(c, px);
+        if (with_history) k.hist_mm = temporal_mm(c, px, c->temporal_set);
+        k.next_mm = temporal_mm(c, px, next);
+    }
     fill_view(k, c->temporal_view, *params);
     HIPCHK(c, hipEventRecord(c->ev_temporal[0], c->stream));
     HIPCHK(c, hipEventRecord(c->ev_temporal[1], c->stream));
@@ -194,6 +214,7 @@ static int temporal_frame(ptk_ctx* c, const char* who, const ptk_temporal_params
     c->temporal_timed = true;
     if (moving) c->motion_timed = 2;
     c->temporal_set = next; c->temporal_view = now; c->temporal_w = c->width; c->temporal_h = c->height;
+    c->temporal_moments = moments; c->temporal_variance = false;
     return PTK_OK;
 }
 
@@ -387,6 +408,62 @@ int ptk_reproject_planes_moving(ptk_ctx* c, int width, int height, const ptk_vie
 int ptk_temporal_frame_moving(ptk_ctx* c, const ptk_temporal_params* params, uint32_t flags)
 {
     return temporal_frame(c, "ptk_temporal_frame_moving", params, flags, true);
+}
+
+// ---- moments of demodulated luminance through the reprojection --------------------------------------------------------------------
+// The checks of the two planes entries
+static int check_moments_desc(ptk_ctx* c, const ptk_reproject_desc* d, const ptk_temporal_params* p, bool* nothing)
+{
+    *nothing = false;
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (!d) return fail(c, PTK_ERR_BAD_ARG, "ptk_reproject_moments: null descriptor");
+    if ((d->prev_position != nullptr) != (d->prev_normal != nullptr))
+        return fail(c, PTK_ERR_BAD_ARG, "ptk_reproject_moments: prev_position and prev_normal go together");
+    const void* const planes[13] = { d->color, d->count, d->id, d->position, d->normal, d->hist_color, d->hist_count, d->hist_id, d->hist_position,
+                                     d->hist_normal, d->hist_moments, d->out_color, d->out_count };
+    if (const int rc = check_planes_args(c, d->width, d->height, d->hist_view, planes, p, nothing); rc != PTK_OK || *nothing) return rc;
+    if (!d->out_moments) return fail(c, PTK_ERR_BAD_ARG, "ptk_reproject_moments: null plane");
+    return PTK_OK;
+}
+
+int ptk_reproject_moments_device(ptk_ctx* c, const ptk_reproject_desc* d, const ptk_temporal_params* params)
+{
+    bool nothing;
+    const int rc = check_moments_desc(c, d, params, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return planes_on_stream(c, d->width, d->height, *d->hist_view, d->color, d->count, d->id, d->position, d->normal, d->hist_color, d->hist_count,
+                            d->hist_id, d->hist_position, d->hist_normal, *params, d->out_color, d->out_count, d->prev_position, d->prev_normal,
+                            d->albedo, d->hist_moments, d->out_moments);
+}
+
+int ptk_reproject_moments(ptk_ctx* c, const ptk_reproject_desc* d, const ptk_temporal_params* params)
+{
+    bool nothing;
+    const int rc = check_moments_desc(c, d, params, &nothing);
+    if (rc != PTK_OK || nothing) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)d->width * d->height;
+    Stage s(c);
+    const auto d_color = s.in(d->color, 3 * px), d_position = s.in(d->position, 3 * px), d_normal = s.in(d->normal, 3 * px), d_count = s.in(d->count, px);
+    const auto d_id = s.in(d->id, px);
+    const auto d_prev_position = s.in(d->prev_position, 3 * px), d_prev_normal = s.in(d->prev_normal, 3 * px), d_albedo = s.in(d->albedo, 3 * px);
+    const auto d_hist_color = s.in(d->hist_color, 3 * px), d_hist_position = s.in(d->hist_position, 3 * px), d_hist_normal = s.in(d->hist_normal, 3 * px);
+    const auto d_hist_count = s.in(d->hist_count, px), d_hist_moments = s.in(d->hist_moments, 2 * px);
+    const auto d_hist_id = s.in(d->hist_id, px);
+    const auto d_out_color = s.out(d->out_color, 3 * px), d_out_count = s.out(d->out_count, px), d_out_moments = s.out(d->out_moments, 2 * px);
+    return s.run([&] {
+        return planes_on_stream(c, d->width, d->height, *d->hist_view, d_color, d_count, d_id, d_position, d_normal, d_hist_color, d_hist_count,
+                                d_hist_id, d_hist_position, d_hist_normal, *params, d_out_color, d_out_count, d_prev_position, d_prev_normal,
+                                d_albedo, d_hist_moments, d_out_moments);
+    });
+}
+
+int ptk_temporal_frame_moments(ptk_ctx* c, const ptk_temporal_params* params, uint32_t flags)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (flags & ~(PTK_TEMPORAL_RESET | PTK_TEMPORAL_MOVING)) return fail(c, PTK_ERR_BAD_ARG, "ptk_temporal_frame_moments: unknown flag bit");
+    return temporal_frame(c, "ptk_temporal_frame_moments", params, flags & PTK_TEMPORAL_RESET, (flags & PTK_TEMPORAL_MOVING) != 0, true);
 }
 
 int ptk_last_motion_ms(ptk_ctx* c, float* motion_ms, float* temporal_ms)

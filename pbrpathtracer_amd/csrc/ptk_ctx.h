@@ -226,6 +226,21 @@ struct ptk_ctx {
     hipEvent_t ev_motion[2] = { nullptr, nullptr };
     int motion_timed = 0;
 
+    // temporal moments and variance (ptk_temporal_frame_moments, ptk_temporal_variance, ptk_denoise_temporal).  The frame entry's
+    // buffer, 52 B per pixel, made by the first moments call at a resolution and freed with the feature planes: the fourth packed
+    // image of the two history sets (m1, m2, count, the frame's own count), then the unpacked moments [H][W][2], the raw and the
+    // final variance [H][W] each and ptk_denoise_temporal's mask [H][W].  temporal_moments: the last frame call at temporal_w x
+    // temporal_h was a moments call, so set temporal_set holds moments; temporal_variance: ptk_temporal_variance has run since.
+    // The planes entries pack into d_variance_pack (52 B per pixel with the raw plane, grown to the largest call so far);
+    // ptk_reproject_moments packs the history's moments into d_temporal_pack_mm (16 B per pixel, likewise).  Three events of the
+    // last variance call: before variance_kernel, behind it, behind the prefilter
+    float4* d_temporal_mm = nullptr;
+    bool temporal_moments = false, temporal_variance = false;
+    float4* d_variance_pack = nullptr; size_t variance_pack_px = 0;
+    float4* d_temporal_pack_mm = nullptr; size_t temporal_pack_mm_px = 0;
+    hipEvent_t ev_variance[3] = { nullptr, nullptr, nullptr };
+    bool variance_timed = false, variance_prefiltered = false;
+
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
     // overlaps the tail of pass k's (a launch ends with the few waves that hold its longest paths - Russian roulette
@@ -327,6 +342,20 @@ inline int ensure_pass_events(ptk_ctx* c, std::vector<hipEvent_t>& ev, int i)
     return PTK_OK;
 }
 
+// the frame entries' temporal buffer cut up (ptk_api_temporal.hip writes it, ptk_api_variance.hip reads it):
+// history set 0 | history set 1 | colour | count ...
+inline bool have_temporal(const ptk_ctx* c) { return c->d_temporal && c->temporal_w == c->width && c->temporal_h == c->height && c->temporal_w > 0; }
+inline float* temporal_color(const ptk_ctx* c, size_t px) { return (float*)(c->d_temporal + 6 * px); }
+inline float* temporal_count(const ptk_ctx* c, size_t px) { return temporal_color(c, px) + 3 * px; }
+// ... and the moments buffer: mm of set 0 | mm of set 1 | moments | raw variance | variance | mask
+inline bool have_temporal_moments(const ptk_ctx* c) { return have_temporal(c) && c->d_temporal_mm && c->temporal_moments; }
+inline float4* temporal_mm(const ptk_ctx* c, size_t px, int set) { return c->d_temporal_mm + (size_t)set * px; }
+inline float* temporal_moments_plane(const ptk_ctx* c, size_t px) { return (float*)(c->d_temporal_mm + 2 * px); }
+inline float* temporal_raw_variance(const ptk_ctx* c, size_t px) { return temporal_moments_plane(c, px) + 2 * px; }
+inline float* temporal_variance_plane(const ptk_ctx* c, size_t px) { return temporal_moments_plane(c, px) + 3 * px; }
+inline int32_t* temporal_mask_plane(const ptk_ctx* c, size_t px) { return (int32_t*)(temporal_moments_plane(c, px) + 4 * px); }
+constexpr size_t kTemporalMomentsBytes = 2 * sizeof(float4) + 5 * sizeof(float);      // per pixel
+
 // ---- internals that cross the files: ptk_api.hip ...
 void fill_params(ptk_ctx* c, RenderParams& p, uint32_t first, uint32_t spp, uint64_t seed);
 int ensure_primary(ptk_ctx* c);
@@ -344,6 +373,11 @@ RaysAdaptiveBuffers radapt_buffers(ptk_ctx* c);
 int rays_adaptive_on_stream(ptk_ctx* c, uint32_t n, const float* d_origins, const float* d_dirs, const uint32_t* d_keys, uint32_t key_base,
                             int max_depth, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp, uint64_t seed, uint32_t rays_flags,
                             float* s1, float* s2, uint32_t* counts, const uint32_t* texel, int width, int height, ptk_rays_adaptive_result* res);
+// ... ptk_api_denoise.hip: the parameter check and the planes call proper of ptk_denoise_planes_device, for ptk_denoise_temporal ...
+int check_denoise_params(ptk_ctx* c, const char* who, const ptk_denoise_params* p);
+int denoise_planes_on_stream(ptk_ctx* c, int width, int height, const float* d_color, const int32_t* d_mask, const float* d_normal,
+                             const float* d_position, const float* d_albedo, const float* d_variance, const ptk_denoise_params& p,
+                             float* d_out_color, float* d_out_variance);
 // ... ptk_api_exchange.hip: destroys the context's own communicator, if there is one
 void comm_release(ptk_ctx* c);
 

@@ -151,6 +151,16 @@ int pth_temporal_frame_moving(pth_tracer* t, const ptk_temporal_params* params, 
 {
     return params && t->pt.TemporalFrameMoving(*params, reset != 0) ? 1 : 0;
 }
+int pth_temporal_frame_moments(pth_tracer* t, const ptk_temporal_params* params, int reset, int moving)
+{
+    return params && t->pt.TemporalFrameMoments(*params, reset != 0, moving != 0) ? 1 : 0;
+}
+int pth_temporal_variance(pth_tracer* t, const ptk_variance_params* params) { return params && t->pt.TemporalVariance(*params) ? 1 : 0; }
+int pth_read_temporal_variance(pth_tracer* t, float* moments, float* variance) { return t->pt.ReadTemporalVariance(moments, variance) ? 1 : 0; }
+int pth_denoise_temporal(pth_tracer* t, const ptk_denoise_params* params, int variance)
+{
+    return params && t->pt.DenoiseTemporal(*params, variance != 0) ? 1 : 0;
+}
 int pth_read_motion(pth_tracer* t, float* prev_position, float* prev_normal, float* motion)
 {
     return t->pt.ReadMotion(prev_position, prev_normal, motion) ? 1 : 0;

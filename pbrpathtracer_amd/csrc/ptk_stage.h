@@ -31,7 +31,7 @@ class Stage {
     struct Part { size_t at, bytes; const void* load; void* store; };
     ptk_ctx* c;
     StageLayout layout;
-    static constexpr int kMaxParts = 14;         // (the most an entry declares: ptk_reproject_planes_moving's twelve planes and two outputs)
+    static constexpr int kMaxParts = 17;         // (the most an entry declares: ptk_reproject_moments' fourteen planes and three outputs)
     Part parts[kMaxParts];
     int num_parts = 0;
     char* base = nullptr;

@@ -50,9 +50,17 @@ struct TemporalParams {
     // normals were in the history's geometry.  Both null: the plain rule.  (Last, so that the fields above keep their offsets.)
     const float* prev_position; // [H][W][3]
     const float* prev_normal;   // [H][W][3]
+    // moments mode (ptk_reproject_moments, ptk_temporal_frame_moments; ptk_variance.h): the first and second moment of demodulated
+    // luminance ride through the same taps.  out_moments null: the plain rule.  (Last again, for the same reason.)
+    const float* albedo;        // [H][W][3], or null: no demodulation
+    const float4* hist_mm;      // the history's fourth packed image (m1, m2, count or 0, the frame's own count; ptk_variance.h); read with hist.cn
+    float4* next_mm;            // ... and the next history's, written with next.cn
+    float* out_moments;         // [H][W][2]
 };
 
 void launch_temporal_pack(const TemporalPackParams& p, const TemporalImages& im, hipStream_t stream);
+// its sibling for the moments entries: mm = (m1, m2, 0, 0) from the caller's [H][W][2] plane
+void launch_temporal_pack_moments(const float* moments, float4* mm, int width, int height, hipStream_t stream);
 void launch_temporal(const TemporalParams& p, hipStream_t stream);
 
 }  // namespace ptk

@@ -3,7 +3,9 @@
 //     cn = (colour, count), pi = (position, id bits), nz = (normal, 0);
 //   * temporal_kernel - one thread per pixel: projection of its first-hit position into the history's view, the four bilinear taps
 //     in the rule's order, the blend; writes the SoA outputs and - in the frame entry - the next history in the packed layout.
-//     Its MOVING instantiations project the point's previous place instead (ptk.h ptk_temporal_frame_moving).
+//     Its MOVING instantiations project the point's previous place instead (ptk.h ptk_temporal_frame_moving);
+//     its MOMENTS instantiations carry the two moments of demodulated luminance in a fourth image mm = (m1, m2, count, the frame's
+//     own count) beside the colour (ptk.h ptk_temporal_frame_moments).
 // Compiled once, with -ffp-contract=off: every expression below is the rule of ptk.h operation by operation, and `/` is the IEEE
 // quotient (the numpy restatement is tests/temporal_rule.py).  No atomics, no LDS, no persistent waves; the only loop is the four taps.
 #include "ptk_device_fn.h"
@@ -34,12 +36,23 @@ __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_pack_kernel(
     im.nz[i] = make_float4(P.normal[3 * i], P.normal[3 * i + 1], P.normal[3 * i + 2], 0.0f);
 }
 
+__global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_pack_moments_kernel(const float* __restrict__ moments, float4* __restrict__ mm,
+                                                                                       const int width, const int height)
+{
+    int x, y;
+    if (!tp_pixel(width, height, x, y)) return;
+    const size_t i = (size_t)y * width + x;
+    mm[i] = make_float4(moments[2 * i], moments[2 * i + 1], 0.0f, 0.0f);
+}
+
 // FRAME: the current colour and count come from the accumulator (n_p and S1 / n_p exactly as denoise_pack_frame_kernel has them).
 // The loads of the four taps are issued together from clamped (always on-image) addresses; a tap off the image is then dropped
 // by its predicate with the others, so nothing it holds reaches a sum.
 // MOVING: everything that is geometry of the history - the projected point and the two tap tests - takes X' and n' from the planes
 // motion_kernel wrote (ptk_motion.hip); the next history still holds the unprimed X and n.
-template <bool FRAME, bool MOVING>
+// MOMENTS: the two moments of demodulated luminance are one more pair of channels of every tap and of the blend (ptk.h
+// ptk_reproject_moments); the colour and the count are computed by the very expressions of the plain instantiations.
+template <bool FRAME, bool MOVING, bool MOMENTS>
 __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_kernel(const TemporalParams P)
 {
     int x, y;
@@ -66,6 +79,18 @@ __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_kernel(const
     const float X0 = P.position[3 * ip], X1 = P.position[3 * ip + 1], X2 = P.position[3 * ip + 2];
     const float n0 = P.normal[3 * ip], n1 = P.normal[3 * ip + 1], n2 = P.normal[3 * ip + 2];
     float o0 = c0, o1 = c1, o2 = c2, on = nc;                  // an invalid pixel and a pixel without history: the input bits
+    float cm1 = 0.0f, cm2 = 0.0f;                              // the current moments: 0 for an invalid pixel and for one without samples
+    if (MOMENTS && id >= 0 && nc > 0.0f)
+    {
+        float l0 = c0, l1 = c1, l2 = c2;
+        if (P.albedo)
+        {
+            l0 = c0 / (P.albedo[3 * ip] + 0.00390625f); l1 = c1 / (P.albedo[3 * ip + 1] + 0.00390625f); l2 = c2 / (P.albedo[3 * ip + 2] + 0.00390625f);
+        }
+        const float l = ((0.2126f * l0) + (0.7152f * l1)) + (0.0722f * l2);
+        cm1 = l; cm2 = l * l;
+    }
+    float om1 = cm1, om2 = cm2;
     if (id >= 0 && P.hist.cn)
     {
         const float Y0 = MOVING ? P.prev_position[3 * ip] : X0, Y1 = MOVING ? P.prev_position[3 * ip + 1] : X1, Y2 = MOVING ? P.prev_position[3 * ip + 2] : X2;
@@ -83,7 +108,7 @@ __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_kernel(const
             const float fx = col - (float)x0, fy = row - (float)i0;
             const float gx = 1.0f - fx, gy = 1.0f - fy;
             const float b[4] = { gx * gy, fx * gy, gx * fy, fx * fy };
-            float4 hc[4], hp[4], hn[4];
+            float4 hc[4], hp[4], hn[4], hm[4];
             bool in[4];
 #pragma unroll
             for (int k = 0; k < 4; k++)
@@ -93,8 +118,9 @@ __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_kernel(const
                 // top-down row qi is plane row H-1-qi
                 const size_t iq = in[k] ? (size_t)(P.height - 1 - qi) * P.width + qx : ip;
                 hc[k] = P.hist.cn[iq]; hp[k] = P.hist.pi[iq]; hn[k] = P.hist.nz[iq];
+                if (MOMENTS) hm[k] = P.hist_mm[iq];
             }
-            float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sn = 0.0f, sw = 0.0f;
+            float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sn = 0.0f, sw = 0.0f, sm1 = 0.0f, sm2 = 0.0f;
 #pragma unroll
             for (int k = 0; k < 4; k++)
             {
@@ -106,6 +132,7 @@ __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_kernel(const
                     s0 = s0 + (b[k] * hc[k].x); s1 = s1 + (b[k] * hc[k].y); s2 = s2 + (b[k] * hc[k].z);
                     sn = sn + (b[k] * hc[k].w);
                     sw = sw + b[k];
+                    if (MOMENTS) { sm1 = sm1 + (b[k] * hm[k].x); sm2 = sm2 + (b[k] * hm[k].y); }
                 }
             }
             if (sw > 0.0f)
@@ -113,12 +140,14 @@ __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_kernel(const
                 const float h0 = s0 / sw, h1 = s1 / sw, h2 = s2 / sw;
                 float hw = sn / sw;
                 hw = hw > P.max_history ? P.max_history : hw;
-                if (nc == 0.0f) { o0 = h0; o1 = h1; o2 = h2; on = hw; }
+                const float hm1 = MOMENTS ? sm1 / sw : 0.0f, hm2 = MOMENTS ? sm2 / sw : 0.0f;
+                if (nc == 0.0f) { o0 = h0; o1 = h1; o2 = h2; on = hw; om1 = hm1; om2 = hm2; }
                 else
                 {
                     const float tot = hw + nc;
                     o0 = ((h0 * hw) + (c0 * nc)) / tot; o1 = ((h1 * hw) + (c1 * nc)) / tot; o2 = ((h2 * hw) + (c2 * nc)) / tot;
                     on = tot;
+                    if (MOMENTS) { om1 = ((hm1 * hw) + (cm1 * nc)) / tot; om2 = ((hm2 * hw) + (cm2 * nc)) / tot; }
                 }
             }
         }
@@ -131,6 +160,13 @@ __global__ __launch_bounds__(TP_BLOCK_X * TP_BLOCK_Y) void temporal_kernel(const
         P.next.pi[ip] = make_float4(X0, X1, X2, __int_as_float(id));
         P.next.nz[ip] = make_float4(n0, n1, n2, 0.0f);
     }
+    if (MOMENTS)
+    {
+        P.out_moments[2 * ip] = om1; P.out_moments[2 * ip + 1] = om2;
+        // (the blended count - 0 where the pixel can have no variance - and the frame's own ride along: variance_kernel reads a
+        // pixel's four numbers in one load)
+        if (P.next_mm) P.next_mm[ip] = make_float4(om1, om2, id >= 0 && on > 0.0f ? on : 0.0f, nc);
+    }
 }
 
 static dim3 tp_grid(int width, int height) { return dim3((width + TP_BLOCK_X - 1) / TP_BLOCK_X, (height + TP_BLOCK_Y - 1) / TP_BLOCK_Y); }
@@ -141,16 +177,28 @@ void launch_temporal_pack(const TemporalPackParams& p, const TemporalImages& im,
     hipLaunchKernelGGL(temporal_pack_kernel, tp_grid(p.width, p.height), tp_block, 0, stream, p, im);
 }
 
-void launch_temporal(const TemporalParams& p, hipStream_t stream)
+void launch_temporal_pack_moments(const float* moments, float4* mm, int width, int height, hipStream_t stream)
+{
+    hipLaunchKernelGGL(temporal_pack_moments_kernel, tp_grid(width, height), tp_block, 0, stream, moments, mm, width, height);
+}
+
+template <bool MOMENTS>
+static void launch_temporal_as(const TemporalParams& p, hipStream_t stream)
 {
     const dim3 grid = tp_grid(p.width, p.height);
     if (p.prev_position)
     {
-        if (p.accum) hipLaunchKernelGGL((temporal_kernel<true, true>), grid, tp_block, 0, stream, p);
-        else hipLaunchKernelGGL((temporal_kernel<false, true>), grid, tp_block, 0, stream, p);
+        if (p.accum) hipLaunchKernelGGL((temporal_kernel<true, true, MOMENTS>), grid, tp_block, 0, stream, p);
+        else hipLaunchKernelGGL((temporal_kernel<false, true, MOMENTS>), grid, tp_block, 0, stream, p);
     }
-    else if (p.accum) hipLaunchKernelGGL((temporal_kernel<true, false>), grid, tp_block, 0, stream, p);
-    else hipLaunchKernelGGL((temporal_kernel<false, false>), grid, tp_block, 0, stream, p);
+    else if (p.accum) hipLaunchKernelGGL((temporal_kernel<true, false, MOMENTS>), grid, tp_block, 0, stream, p);
+    else hipLaunchKernelGGL((temporal_kernel<false, false, MOMENTS>), grid, tp_block, 0, stream, p);
+}
+
+void launch_temporal(const TemporalParams& p, hipStream_t stream)
+{
+    if (p.out_moments) launch_temporal_as<true>(p, stream);
+    else launch_temporal_as<false>(p, stream);
 }
 
 }  // namespace ptk

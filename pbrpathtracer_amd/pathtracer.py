@@ -40,7 +40,8 @@ HOST_SYMBOLS = [
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
     "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points",
     "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised", "pth_temporal_frame", "pth_read_temporal", "pth_get_view",
-    "pth_track_motion", "pth_temporal_frame_moving", "pth_read_motion", "pth_get_object_transform",
+    "pth_track_motion", "pth_temporal_frame_moving", "pth_read_motion", "pth_temporal_frame_moments", "pth_temporal_variance",
+    "pth_read_temporal_variance", "pth_denoise_temporal", "pth_get_object_transform",
 ]
 
 _bound = False
@@ -124,6 +125,10 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_get_object_transform.restype = i32; L.pth_get_object_transform.argtypes = [vp, i32, C.POINTER(C.c_float)]
         L.pth_track_motion.restype = None; L.pth_track_motion.argtypes = [vp, i32]
         L.pth_temporal_frame_moving.restype = i32; L.pth_temporal_frame_moving.argtypes = [vp, C.POINTER(_ptk.TemporalParams), i32]
+        L.pth_temporal_frame_moments.restype = i32; L.pth_temporal_frame_moments.argtypes = [vp, C.POINTER(_ptk.TemporalParams), i32, i32]
+        L.pth_temporal_variance.restype = i32; L.pth_temporal_variance.argtypes = [vp, C.POINTER(_ptk.VarianceParams)]
+        L.pth_read_temporal_variance.restype = i32; L.pth_read_temporal_variance.argtypes = [vp, vp, vp]
+        L.pth_denoise_temporal.restype = i32; L.pth_denoise_temporal.argtypes = [vp, C.POINTER(_ptk.DenoiseParams), i32]
         L.pth_read_motion.restype = i32; L.pth_read_motion.argtypes = [vp, vp, vp, vp]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
@@ -405,7 +410,47 @@ class PathTracer:
             raise _ptk.PtkError("GetView failed: " + self.LastError())
         return v
 
+    def _extent(self) -> float:
+        v = np.asarray(self.StagedScene()["verts"], np.float64).reshape(-1, 3)
+        return float(np.linalg.norm(v.max(axis=0) - v.min(axis=0))) if len(v) else 1.0
+
+    def TemporalFrameMoments(self, params=None, reset: bool = False, moving: bool = False):
+        """Extension: TemporalFrame() - moving: TemporalFrameMoving() - that also carries the first and second moment of
+        demodulated luminance (include/ptk.h ptk_temporal_frame_moments).  Shares history, result and ReadTemporal() with the
+        two; a moments call behind a plain one starts its history over.  TemporalVariance() and DenoiseTemporal() follow it."""
+        prm = self._temporal_params(params)
+        if not self.L.pth_temporal_frame_moments(self.h, C.byref(prm), 1 if reset else 0, 1 if moving else 0):
+            raise _ptk.PtkError("TemporalFrameMoments failed: " + self.LastError())
+
+    def TemporalVariance(self, params=None):
+        """Extension: the per-pixel variance of the accumulated demodulated luminance from the moments of the last
+        TemporalFrameMoments() (include/ptk.h ptk_temporal_variance).  params: ptk.VarianceParams or a dict of its fields; None
+        takes ptk.variance_defaults for the staged scene's extent."""
+        prm = _ptk._variance_params(_ptk.variance_defaults(self._extent()) if params is None else params)
+        if not self.L.pth_temporal_variance(self.h, C.byref(prm)):
+            raise _ptk.PtkError("TemporalVariance failed: " + self.LastError())
+
+    def ReadTemporalVariance(self, variance: bool = True):
+        """(moments [H][W][2], variance [H][W]) float32 of the last TemporalFrameMoments() and TemporalVariance(), rows bottom-up;
+        variance=False: (moments, None), legal before TemporalVariance()."""
+        w, h = self.GetResolution()
+        mom = np.empty((h, w, 2), np.float32)
+        var = np.empty((h, w), np.float32) if variance else None
+        if not self.L.pth_read_temporal_variance(self.h, mom.ctypes.data, var.ctypes.data if variance else None):
+            raise _ptk.PtkError("ReadTemporalVariance failed: " + self.LastError())
+        return mom, var
+
+    def DenoiseTemporal(self, params=None, variance: bool = True):
+        """Extension: the a-trous denoiser over the last TemporalFrame*() result, on the device (include/ptk.h
+        ptk_denoise_temporal); variance: guided by TemporalVariance()'s plane.  params: ptk.DenoiseParams or a dict of its fields;
+        None takes ptk.denoise_defaults for the staged scene's extent.  ReadDenoised() and ResolveDenoised() give the result."""
+        prm = _ptk._denoise_params(_ptk.denoise_defaults(self._extent(), variance) if params is None else params)
+        if not self.L.pth_denoise_temporal(self.h, C.byref(prm), 1 if variance else 0):
+            raise _ptk.PtkError("DenoiseTemporal failed: " + self.LastError())
+
     temporal_frame, read_temporal, get_view = TemporalFrame, ReadTemporal, GetView
+    temporal_frame_moments, temporal_variance, read_temporal_variance, denoise_temporal = (TemporalFrameMoments, TemporalVariance,
+                                                                                          ReadTemporalVariance, DenoiseTemporal)
     track_motion, temporal_frame_moving, read_motion = TrackMotion, TemporalFrameMoving, ReadMotion
 
     def Pick(self, x: int, y: int):

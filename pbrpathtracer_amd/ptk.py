@@ -97,6 +97,23 @@ class TemporalParams(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class VarianceParams(C.Structure):
+    """ptk_variance_params"""
+    _fields_ = [("radius", C.c_int32), ("prefilter", C.c_int32), ("min_frames", C.c_float), ("max_plane_dist", C.c_float),
+                ("min_normal_dot", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ReprojectDesc(C.Structure):
+    """ptk_reproject_desc"""
+    _fields_ = ([("width", C.c_int32), ("height", C.c_int32), ("hist_view", C.POINTER(View))]
+                + [(k, C.c_void_p) for k in ("color", "count", "id", "position", "normal", "prev_position", "prev_normal", "albedo",
+                                             "hist_color", "hist_count", "hist_id", "hist_position", "hist_normal", "hist_moments",
+                                             "out_color", "out_count", "out_moments")])
+
+
 class PtkError(RuntimeError):
     pass
 
@@ -127,6 +144,9 @@ SYMBOLS = [
     "ptk_temporal_device_ptr", "ptk_last_temporal_ms",
     "ptk_geometry_snapshot", "ptk_render_motion", "ptk_read_motion", "ptk_motion_device_ptr", "ptk_reproject_planes_moving",
     "ptk_reproject_planes_moving_device", "ptk_temporal_frame_moving", "ptk_last_motion_ms",
+    "ptk_reproject_moments", "ptk_reproject_moments_device", "ptk_temporal_frame_moments", "ptk_variance_planes",
+    "ptk_variance_planes_device", "ptk_temporal_variance", "ptk_read_temporal_variance", "ptk_temporal_variance_device_ptr",
+    "ptk_denoise_temporal", "ptk_last_variance_ms",
     "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
     "ptk_last_bake_ms",
     "ptk_trace_rays_adaptive", "ptk_trace_rays_adaptive_device", "ptk_bake_lightmap_adaptive", "ptk_bake_lightmap_adaptive_device",
@@ -264,6 +284,16 @@ def _load_locked() -> C.CDLL:
             fn.argtypes = [vp, i32, i32, C.POINTER(View)] + [vp] * 12 + [C.POINTER(TemporalParams), vp, vp]
         L.ptk_temporal_frame_moving.argtypes = [vp, C.POINTER(TemporalParams), u32]
         L.ptk_last_motion_ms.argtypes = [vp, fp, fp]
+        for fn in (L.ptk_reproject_moments, L.ptk_reproject_moments_device):
+            fn.argtypes = [vp, C.POINTER(ReprojectDesc), C.POINTER(TemporalParams)]
+        L.ptk_temporal_frame_moments.argtypes = [vp, C.POINTER(TemporalParams), u32]
+        for fn in (L.ptk_variance_planes, L.ptk_variance_planes_device):
+            fn.argtypes = [vp, i32, i32] + [vp] * 6 + [C.POINTER(VarianceParams), vp]
+        L.ptk_temporal_variance.argtypes = [vp, C.POINTER(VarianceParams)]
+        L.ptk_read_temporal_variance.argtypes = [vp, vp, vp]
+        L.ptk_temporal_variance_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.ptk_denoise_temporal.argtypes = [vp, C.POINTER(DenoiseParams), u32]
+        L.ptk_last_variance_ms.argtypes = [vp, fp, fp]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -309,6 +339,7 @@ def _denoise_params(params) -> DenoiseParams:
 
 
 TEMPORAL_RESET = 1                                                    # ptk_temporal_frame flags
+TEMPORAL_MOVING = 2                                                   # ... and ptk_temporal_frame_moments' own
 
 
 def temporal_defaults(extent: float) -> TemporalParams:
@@ -322,6 +353,20 @@ def _temporal_params(params) -> TemporalParams:
     if isinstance(params, TemporalParams):
         return params
     return TemporalParams(float(params["max_plane_dist"]), float(params["min_normal_dot"]), float(params["max_history"]), int(params["match_id"]))
+
+
+def variance_defaults(extent: float) -> VarianceParams:
+    """The documented default parameters of the temporal variance for a scene whose bounding box has the diagonal
+    `extent`: a 7x7 window for the spatial estimate, the 3x3 prefilter, the spatial estimate below 4 frames of history, and the
+    plane and normal thresholds of temporal_defaults."""
+    return VarianceParams(3, 1, 4.0, float(extent) / 100.0, 0.9)
+
+
+def _variance_params(params) -> VarianceParams:
+    if isinstance(params, VarianceParams):
+        return params
+    return VarianceParams(int(params["radius"]), int(params["prefilter"]), float(params["min_frames"]), float(params["max_plane_dist"]),
+                          float(params["min_normal_dot"]))
 
 
 def _view(view) -> View:
@@ -793,21 +838,29 @@ class Context:
                   "ptk_reproject_planes")
         return out, out_n
 
-    def temporal_frame(self, params, reset: bool = False, render_features: bool = True, seed: int = 0, moving: bool = False):
+    def temporal_frame(self, params, reset: bool = False, render_features: bool = True, seed: int = 0, moving: bool = False,
+                       moments: bool = False):
         """ptk_temporal_frame: carries the previous call's result into the frame in the accumulator and blends the two by sample
         counts (read_temporal); asynchronous.  reset: drop the history.  render_features: render the guide planes MATERIAL,
         POSITION and NORMAL first (sample 0 of `seed`, which replaces the planes of an earlier render_features); False uses the
         caller's snapshot as it is.  moving: ptk_temporal_frame_moving - the history follows the triangles that
         update_geometry moved since snapshot_geometry (read_motion gives where they were); its guide planes are those three
-        with TRIANGLE and BARY."""
+        with TRIANGLE and BARY.  moments: ptk_temporal_frame_moments - the moments of demodulated luminance ride along
+        (temporal_variance, read_temporal_variance, denoise_temporal); its guide planes are those of the entry with ALBEDO, and
+        the render_features of this call adds TRIANGLE and EMISSION, which denoise_temporal needs."""
         mask = (1 << FEAT_MATERIAL) | (1 << FEAT_POSITION) | (1 << FEAT_NORMAL)
         if moving:
             mask |= (1 << FEAT_TRIANGLE) | (1 << FEAT_BARY)
+        if moments:
+            mask |= (1 << FEAT_ALBEDO) | (1 << FEAT_TRIANGLE) | (1 << FEAT_EMISSION)
         if render_features:
             self.render_features(mask, 0, seed)
         prm = _temporal_params(params)
         flags = TEMPORAL_RESET if reset else 0
-        if moving:
+        if moments:
+            self._chk(self.L.ptk_temporal_frame_moments(self.h, C.byref(prm), flags | (TEMPORAL_MOVING if moving else 0)),
+                      "ptk_temporal_frame_moments")
+        elif moving:
             self._chk(self.L.ptk_temporal_frame_moving(self.h, C.byref(prm), flags), "ptk_temporal_frame_moving")
         else:
             self._chk(self.L.ptk_temporal_frame(self.h, C.byref(prm), flags), "ptk_temporal_frame")
@@ -895,6 +948,103 @@ class Context:
         t = [C.c_float(0) for _ in range(2)]
         self._chk(self.L.ptk_last_motion_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_motion_ms")
         return dict(zip(("motion_ms", "temporal_ms"), (x.value for x in t)))
+
+    # ---- temporal moments, variance and the denoiser behind them ----------------------------
+    def reproject_moments(self, hist_view, current, history, params, albedo=None, prev=None):
+        """ptk_reproject_moments: reproject_planes - with prev = (prev_position, prev_normal) reproject_planes_moving - with the
+        moments of demodulated luminance as one more pair of channels.  current: the five planes of reproject_planes; history:
+        those five and the history's moments [H, W, 2]; albedo [H, W, 3] demodulates.  Returns (color [H, W, 3], count [H, W],
+        moments [H, W, 2]).  numpy arrays or torch tensors on the context's GPU, as reproject_planes."""
+        prm = _temporal_params(params)
+        view = _view(hist_view)
+        current = list(current); history = list(history)
+        assert len(current) == 5 and len(history) == 6, "five current planes; five history planes and the history's moments"
+        assert prev is None or len(prev) == 2, "prev = (prev_position, prev_normal)"
+        extra = [None, None] if prev is None else list(prev)
+        planes = current + extra + [albedo] + history
+        H, W = int(planes[0].shape[0]), int(planes[0].shape[1])
+        px = H * W
+        torch_side = hasattr(planes[0], "data_ptr")
+        if torch_side:
+            import torch
+            five = [(torch.float32, 3), (torch.float32, 1), (torch.int32, 1), (torch.float32, 3), (torch.float32, 3)]
+            kinds = five + [(torch.float32, 3)] * 3 + five + [(torch.float32, 2)]
+            have = [(t, k) for t, k in zip(planes, kinds) if t is not None]
+            self._ray_tensors([t for t, _ in have], px, [k for _, k in have])
+            mk = lambda shape: torch.empty(shape, dtype=torch.float32, device=planes[0].device)
+            ptr = lambda t: t.data_ptr() if t is not None and px else None
+        else:
+            five = [(np.float32, (H, W, 3)), (np.float32, (H, W)), (np.int32, (H, W)), (np.float32, (H, W, 3)), (np.float32, (H, W, 3))]
+            shapes = five + [(np.float32, (H, W, 3))] * 3 + five + [(np.float32, (H, W, 2))]
+            planes = [None if a is None else np.ascontiguousarray(a, dtype=d).reshape(sh) for a, (d, sh) in zip(planes, shapes)]
+            mk = lambda shape: np.empty(shape, np.float32)
+            ptr = lambda a: a.ctypes.data if a is not None and px else None
+        outs = [mk((H, W, 3)), mk((H, W)), mk((H, W, 2))]
+        desc = ReprojectDesc(W, H, C.pointer(view), *(ptr(a) for a in planes + outs))
+        if torch_side:
+            self._chk(self.L.ptk_reproject_moments_device(self.h, C.byref(desc), C.byref(prm)), "ptk_reproject_moments_device")
+        else:
+            self._chk(self.L.ptk_reproject_moments(self.h, C.byref(desc), C.byref(prm)), "ptk_reproject_moments")
+        return tuple(outs)
+
+    def variance_planes(self, moments, count, frame_count, ident, position, normal, params):
+        """ptk_variance_planes: the variance [H, W] of the accumulated demodulated luminance from its moments [H, W, 2], the
+        blended count and the current frame's own count [H, W], by the rule of include/ptk.h; id [H, W] int32, position and normal
+        [H, W, 3] guide the spatial estimate of pixels with a short history.  params: VarianceParams (variance_defaults) or a dict
+        of its fields.  numpy arrays or torch tensors on the context's GPU, as reproject_planes."""
+        prm = _variance_params(params)
+        planes = [moments, count, frame_count, ident, position, normal]
+        H, W = int(count.shape[0]), int(count.shape[1])
+        px = H * W
+        if hasattr(moments, "data_ptr"):
+            import torch
+            kinds = [(torch.float32, 2), (torch.float32, 1), (torch.float32, 1), (torch.int32, 1), (torch.float32, 3), (torch.float32, 3)]
+            self._ray_tensors(planes, px, kinds)
+            out = torch.empty((H, W), dtype=torch.float32, device=moments.device)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if px else None
+            self._chk(self.L.ptk_variance_planes_device(self.h, W, H, *(ptr(t) for t in planes), C.byref(prm), ptr(out)),
+                      "ptk_variance_planes_device")
+            return out
+        shapes = [(np.float32, (H, W, 2)), (np.float32, (H, W)), (np.float32, (H, W)), (np.int32, (H, W)), (np.float32, (H, W, 3)),
+                  (np.float32, (H, W, 3))]
+        planes = [np.ascontiguousarray(a, dtype=d).reshape(sh) for a, (d, sh) in zip(planes, shapes)]
+        out = np.empty((H, W), np.float32)
+        ptr = lambda a: a.ctypes.data if px else None
+        self._chk(self.L.ptk_variance_planes(self.h, W, H, *(ptr(a) for a in planes), C.byref(prm), ptr(out)), "ptk_variance_planes")
+        return out
+
+    def temporal_variance(self, params):
+        """ptk_temporal_variance: the variance plane of the last temporal_frame(moments=True); asynchronous."""
+        prm = _variance_params(params)
+        self._chk(self.L.ptk_temporal_variance(self.h, C.byref(prm)), "ptk_temporal_variance")
+
+    def read_temporal_variance(self, variance: bool = True):
+        """(moments [H][W][2], variance [H][W]) float32 of the last temporal_frame(moments=True) and temporal_variance, rows
+        bottom-up; variance=False: (moments, None), legal before temporal_variance.  Waits for the stream."""
+        mom = np.empty((self.height, self.width, 2), dtype=np.float32)
+        var = np.empty((self.height, self.width), dtype=np.float32) if variance else None
+        self._chk(self.L.ptk_read_temporal_variance(self.h, mom.ctypes.data, var.ctypes.data if variance else None),
+                  "ptk_read_temporal_variance")
+        return mom, var
+
+    def temporal_variance_device_ptr(self, variance: bool = True):
+        """(moments pointer, variance pointer or None, pixels): the planes of read_temporal_variance in device memory"""
+        a = C.c_void_p(); b = C.c_void_p(); n = C.c_size_t()
+        self._chk(self.L.ptk_temporal_variance_device_ptr(self.h, C.byref(a), C.byref(b) if variance else None, C.byref(n)),
+                  "ptk_temporal_variance_device_ptr")
+        return a.value, (b.value if variance else None), n.value
+
+    def denoise_temporal(self, params, variance: bool = True):
+        """ptk_denoise_temporal: the a-trous filter over the last temporal_frame's result into the context's denoised plane
+        (read_denoised), on the device; asynchronous.  variance: guided by temporal_variance's plane."""
+        prm = _denoise_params(params)
+        self._chk(self.L.ptk_denoise_temporal(self.h, C.byref(prm), DENOISE_VARIANCE if variance else 0), "ptk_denoise_temporal")
+
+    def last_variance_ms(self) -> dict:
+        """HIP-event times of the last variance call: variance kernel, prefilter (0 without one); waits for it."""
+        t = [C.c_float(0) for _ in range(2)]
+        self._chk(self.L.ptk_last_variance_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_variance_ms")
+        return dict(zip(("variance_ms", "prefilter_ms"), (x.value for x in t)))
 
     # ---- lightmap baking -------------------------------------------------------------------
     def _bake_uvs(self, uvs, torch_side: bool):

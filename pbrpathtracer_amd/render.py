@@ -5,6 +5,7 @@
     python -m pbrpathtracer_amd.render scene.pts --spp 8 --denoise [--denoise-iterations K] [--npy denoised.npy]
     python -m pbrpathtracer_amd.render scene.pts --orbit FRAMES --orbit-degrees D --spp K --temporal [--denoise]
     python -m pbrpathtracer_amd.render scene.pts --orbit FRAMES --spp K --temporal --move-object OBJ --move-by DX DY DZ
+    python -m pbrpathtracer_amd.render scene.pts --orbit FRAMES --spp K --temporal --denoise --temporal-variance
                                                  [--motion-vectors FILE.npy]
     python -m pbrpathtracer_amd.render scene.pts --features planes.npz
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
@@ -39,6 +40,12 @@ each step ends in PathTracer.TemporalFrameMoving (include/ptk.h ptk_temporal_fra
 the object's samples follow it instead of being thrown away or smeared.  --motion-vectors FILE.npy writes the last step's
 screen-space motion vectors, float32 [H, W, 2] = (columns, rows) from each pixel to where its surface point was in the step before,
 rows top-down, NaN where the pixel sees nothing.
+
+With --temporal --denoise --temporal-variance each step ends in PathTracer.TemporalFrameMoments instead (include/ptk.h
+ptk_temporal_frame_moments; with --move-object in its moving mode), which carries the moments of demodulated luminance beside the
+colour; the last step is followed by PathTracer.TemporalVariance and PathTracer.DenoiseTemporal, so the a-trous filter weighs
+luminance differences in standard deviations of each pixel's accumulated value and the chain never leaves the device.  The PNG and
+--npy hold that result.
 
 With --equirect WIDTH the image is a WIDTH x WIDTH/2 latitude-longitude panorama from the scene's camera position, traced through
 PathTracer.TraceRays (include/ptk.h ptk_trace_rays; rays.equirect_rays) instead of the perspective camera.
@@ -96,6 +103,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="turn the camera about the scene's centre in FRAMES steps, --spp samples after a reset at each; the image is the last view")
     ap.add_argument("--orbit-degrees", type=float, default=10.0, metavar="D", help="--orbit: the whole turn in degrees (default 10)")
     ap.add_argument("--temporal", action="store_true", help="--orbit: carry each step's samples into the next by temporal reprojection")
+    ap.add_argument("--temporal-variance", action="store_true",
+                    help="--orbit --temporal --denoise: carry luminance moments through the reprojection and guide the denoiser by their variance")
     ap.add_argument("--move-object", type=int, default=None, metavar="OBJ", help="--orbit: also translate object OBJ of the scene file, by --move-by over the steps")
     ap.add_argument("--move-by", type=float, nargs=3, default=None, metavar=("DX", "DY", "DZ"), help="--move-object: the whole translation in world units")
     ap.add_argument("--motion-vectors", metavar="FILE.npy", default=None,
@@ -394,14 +403,20 @@ def render_orbit(pt, a) -> int:
         pt.RenderFrames(a.spp)
         if pt.LastError():
             raise RuntimeError(pt.LastError())
-        if a.temporal:
+        if a.temporal_variance:
+            pt.TemporalFrameMoments(moving=moving)
+        elif a.temporal:
             pt.TemporalFrameMoving() if moving else pt.TemporalFrame()
     t2 = time.time()
     if a.motion_vectors:
         np.save(a.motion_vectors, np.ascontiguousarray(pt.ReadMotion()[2][::-1], np.float32))
     if a.temporal:
         image, count = pt.ReadTemporal()
-        if a.denoise:
+        if a.temporal_variance:
+            pt.TemporalVariance()
+            pt.DenoiseTemporal(denoise_params(pt, a, True))
+            image = pt.ReadDenoised()
+        elif a.denoise:
             tri = pt.ReadFeature(ptk.FEAT_TRIANGLE)
             mask = np.where((pt.ReadFeature(ptk.FEAT_EMISSION) != 0).any(axis=-1), -1, tri).astype(np.int32)
             image = pt.context().denoise_planes(image, mask, pt.ReadFeature(ptk.FEAT_NORMAL), pt.ReadFeature(ptk.FEAT_POSITION),
@@ -447,6 +462,9 @@ def main(argv=None):
         return 1
     if a.motion_vectors and not (a.temporal and a.move_object is not None):
         print("error: --motion-vectors goes with --temporal and --move-object", file=sys.stderr)
+        return 1
+    if a.temporal_variance and not (a.temporal and a.denoise):
+        print("error: --temporal-variance goes with --temporal and --denoise", file=sys.stderr)
         return 1
     if a.orbit is not None:
         if a.orbit < 1 or a.noise_threshold is not None or a.bake_lightmap is not None or a.bake_probes is not None or \
