@@ -40,40 +40,50 @@ def per_triangle(verts, points):
     return d2k, v, w, q, region
 
 
-def mirror_full(arrays, points, max_dist=None, chunk=64):
-    """the answer of the rule with what the tests ask about it: dict of tri, dist, point, bary (the outputs of ptk_closest_points),
-    region (of the winner, -1 on a miss) and ties (accepted triangles that share the winning d2k, 0 on a miss)"""
+def _r2(max_dist, n):
+    """the squared bound of each query: +inf without one; a NaN, zero or negative max_dist gives 0 (d2k < 0 accepts nothing)"""
+    with np.errstate(all="ignore"):
+        if max_dist is None:
+            return np.full(n, np.inf, F32)
+        md = np.asarray(max_dist, F32).reshape(n)
+        return np.where(md > 0, md * md, F32(0)).astype(F32)
+
+
+def mirror_radii(arrays, points, radii, chunk=64):
+    """mirror_full for each max_dist of the list `radii` (None: no bound), with the per-triangle rule evaluated once: a list of dicts"""
     points = np.ascontiguousarray(points, F32).reshape(-1, 3)
     n = len(points)
     verts = np.asarray(arrays["verts"], F32).reshape(-1, 9)
-    out = dict(tri=np.full(n, -1, np.int32), dist=np.full(n, np.inf, F32), point=np.zeros((n, 3), F32), bary=np.zeros((n, 2), F32),
-               region=np.full(n, -1, np.int8), ties=np.zeros(n, np.int32))
+    outs = [dict(tri=np.full(n, -1, np.int32), dist=np.full(n, np.inf, F32), point=np.zeros((n, 3), F32), bary=np.zeros((n, 2), F32),
+                 region=np.full(n, -1, np.int8), ties=np.zeros(n, np.int32)) for _ in radii]
     if len(verts) == 0 or n == 0:
-        return out
-    with np.errstate(all="ignore"):
-        if max_dist is None:
-            r2 = np.full(n, np.inf, F32)
-        else:
-            md = np.asarray(max_dist, F32).reshape(n)
-            r2 = np.where(md > 0, md * md, F32(0)).astype(F32)           # (NaN, zero or negative: d2k < 0 accepts nothing)
+        return outs
+    bounds = [_r2(md, n) for md in radii]
     for s in range(0, n, chunk):
         e = min(n, s + chunk)
         d2k, v, w, q, region = per_triangle(verts, points[s:e])
-        with np.errstate(all="ignore"):
-            ok = np.isfinite(d2k) & (d2k < r2[s:e, None])
-        key = np.where(ok, d2k, F32(np.inf))
-        k = np.argmin(key, axis=1)                                      # (the first of equal minima: the smaller index)
-        rows = np.arange(e - s)
-        hit = ok[rows, k]
-        i = s + rows[hit]
-        kk = k[hit]
-        out["tri"][i] = kk
-        out["dist"][i] = np.sqrt(d2k[rows[hit], kk])
-        out["point"][i] = q[rows[hit], kk]
-        out["bary"][i, 0] = v[rows[hit], kk]; out["bary"][i, 1] = w[rows[hit], kk]
-        out["region"][i] = region[rows[hit], kk]
-        out["ties"][i] = (ok & (d2k == key[rows, k][:, None]))[rows[hit]].sum(axis=1)
-    return out
+        for out, r2 in zip(outs, bounds):
+            with np.errstate(all="ignore"):
+                ok = np.isfinite(d2k) & (d2k < r2[s:e, None])
+            key = np.where(ok, d2k, F32(np.inf))
+            k = np.argmin(key, axis=1)                                      # (the first of equal minima: the smaller index)
+            rows = np.arange(e - s)
+            hit = ok[rows, k]
+            i = s + rows[hit]
+            kk = k[hit]
+            out["tri"][i] = kk
+            out["dist"][i] = np.sqrt(d2k[rows[hit], kk])
+            out["point"][i] = q[rows[hit], kk]
+            out["bary"][i, 0] = v[rows[hit], kk]; out["bary"][i, 1] = w[rows[hit], kk]
+            out["region"][i] = region[rows[hit], kk]
+            out["ties"][i] = (ok & (d2k == key[rows, k][:, None]))[rows[hit]].sum(axis=1)
+    return outs
+
+
+def mirror_full(arrays, points, max_dist=None, chunk=64):
+    """the answer of the rule with what the tests ask about it: dict of tri, dist, point, bary (the outputs of ptk_closest_points),
+    region (of the winner, -1 on a miss) and ties (accepted triangles that share the winning d2k, 0 on a miss)"""
+    return mirror_radii(arrays, points, [max_dist], chunk)[0]
 
 
 def mirror(arrays, points, max_dist=None):

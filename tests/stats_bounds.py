@@ -27,12 +27,28 @@ a sure entry earlier than this child's earliest possible one - or has the very s
 bytes give the same t_near, bit for bit, and the slot bits break the tie).  The walk pops nothing while it goes on into interior nodes,
 so along the chain of children that are surely the nearest the pushes add up: their sum is a lower bound on the entries the
 ray's stack holds at once.
+
+Deferred entries of the closest-point walk (closest_stack_lower_bound; closest_kernel, ptk_closest.hip).  Without a radius
+(max_dist NULL) the prune bound thr2 is +inf until the first leaf has been tested, so at every interior node of the first descent
+every non-empty child (link != NODE_EXIT) survives: the walk goes on into the one with the smallest key - the bits of the squared
+box distance db2 with the two low bits replaced by the slot - and defers the other children - 1, whichever child that is.  Nothing
+is popped before the first leaf.  So the sum of children - 1 over the nodes of that descent is held at once, and the nodes of the
+descent are known as far as one child is surely the nearest.  The kernel's child box lies between the quantised box shrunk and
+inflated by MARGIN x (max |p| + 2 extent), so a child is surely the nearest when
+  - the point lies inside its shrunk box (the kernel's db2 is then exactly 0 and its key is its slot) and every other non-empty child
+    sits in a higher slot or has the point outside its inflated box (a db2 of at least the square of what is left of the margin:
+    a key above 3), or
+  - its largest possible distance (to the shrunk box) is below every other non-empty child's smallest possible one (to the inflated
+    box) by the factor 1 - 2^-20 on the distance, 2^-19 on db2: the key's two dropped bits and the few roundings of db2 are 2^-21.
+Where no child is surely the nearest the node's own children - 1 still count - they are deferred whichever child wins - and the
+chain ends there.
 """
 import numpy as np
 
 # relative to (max |ray origin| + scene extent): the kernel's own slack is 2^-21 of that per slab distance (Walk::begin)
 MARGIN = 2.0 ** -16
 PARALLEL = 1e-6          # |direction component| below which the upper bound does not let that axis cull
+NODE_EXIT = -2 ** 31     # the link of an empty slot (ptk_device.h)
 
 
 def decode(nodes: np.ndarray):
@@ -206,4 +222,41 @@ def stack_lower_bound(nodes, verts, ro, rd, t):
         nxt = link[node[has], nearest[has]]
         inner = nxt >= 0
         ray, node = ray[has][inner], nxt[inner].astype(np.int64)
+    return depth
+
+
+
+def closest_stack_lower_bound(nodes, verts, points):
+    """nodes [N,16] float32, verts [n,9] float32 (for the margin), finite points [m,3] queried WITHOUT a radius.  Returns int64 [m]:
+    entries that are surely in the point's column of closest_kernel's stack at once, on its first descent."""
+    bmin, bmax, _, link = decode(nodes)
+    child = link != NODE_EXIT                                                      # [N, 4]
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    m = len(p)
+    extent = float(np.abs(verts).max()) if len(verts) else 1.0
+    margin = (MARGIN * (np.abs(p).max(axis=1) + 2.0 * extent))[:, None]
+    early = 1.0 - 2.0 ** -20
+    depth = np.zeros(m, np.int64)
+    pt = np.arange(m)
+    node = np.zeros(m, np.int64)
+    while len(pt):
+        q, mg, c = p[pt][:, None, :], margin[pt][:, None, :], child[node]
+        lo, hi = bmin[node], bmax[node]                                            # [r, 4, 3]
+        inside = c & ((lo + mg <= q) & (q <= hi - mg)).all(axis=2)
+        late = np.sqrt((np.maximum(np.maximum((lo + mg) - q, q - (hi - mg)), 0.0) ** 2).sum(axis=2))      # to the shrunk box
+        soon = np.sqrt((np.maximum(np.maximum((lo - mg) - q, q - (hi + mg)), 0.0) ** 2).sum(axis=2))      # to the inflated box
+        depth[pt] += c.sum(axis=1) - 1
+        nearest = np.full(len(pt), -1)
+        for k in range(4):
+            by_slot = inside[:, k].copy()
+            by_dist = c[:, k].copy()
+            for j in range(4):
+                if j != k:
+                    by_slot &= ~c[:, j] | (soon[:, j] > 0.0) | (j > k)
+                    by_dist &= ~c[:, j] | ((late[:, k] < soon[:, j] * early) & (soon[:, j] > 0.0))
+            nearest = np.where(by_slot | by_dist, k, nearest)
+        has = nearest >= 0
+        nxt = link[node[has], nearest[has]]
+        inner = nxt >= 0
+        pt, node = pt[has][inner], nxt[inner].astype(np.int64)
     return depth

@@ -3,7 +3,9 @@ triangle, the reference's IntersectTriangle and its tie rule).  Closest hits do 
 §2): these tests hold the kernels to that where the suite's other trees are mild - leaves of 5 to 8 triangles (builder tuning
 "bvh_leaf_max" / "bvh_trav_cost"), a traversal stack filled to its bound, the device builder's size switch, its multi-round
 prefix sum and its fall-back to the host builder, adversarial geometry, and coordinates and ray distances near the accepted
-maximum with direction components on both sides of the 1 / d clamp."""
+maximum with direction components on both sides of the 1 / d clamp.  These tests drive probe_hits and render; the scenes, rays
+and the off-box exclusion live in tests/walker_limit_cases.py, and tests/test_gpu_walker_limits.py holds every other kernel that walks
+the tree (hit, occlusion, closest-point and radiance queries, feature planes, picking) to tree-free references on the same cases."""
 import numpy as np
 import pytest
 
@@ -11,6 +13,7 @@ import stats_bounds as SB
 from bvh_check import check_bvh, leaf_sizes
 from test_gpu_bvh_build import _scene, _soup
 from test_gpu_random_scenes import random_scene
+from walker_limit_cases import (SOAK_KINDS, TINY, _aimed_rays, _glow, _nest, _off_box, _onion, _soak_scene, far_case, nest_rays)   # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -67,16 +70,6 @@ def _upload(ctx, arrays, device_build, strict=True):
     return nodes, order
 
 
-def _glow(arrays, lights):
-    """material 1 for the triangles `lights`: an emitter, so that a render of the scene is not black"""
-    mats = np.concatenate([arrays["materials"], arrays["materials"]])
-    mats[1]["emissive"] = (1.0, 0.8, 0.6); mats[1]["emissive_intensity"] = 4.0
-    arrays["materials"] = mats
-    arrays["material"] = arrays["material"].copy(); arrays["material"][lights] = 1
-    arrays["lights"] = np.asarray(lights, np.int32)
-    return arrays
-
-
 def _render_matches(ctx, o, oracle_mod, cam, W=40, H=28, D=4, spp=2, seed=9):
     ocam = oracle_mod.make_camera(cam["pos"], cam["dir"], cam["up"], cam["focal"], cam["fovy"], cam["focal_dist"], cam["aperture"])
     ref_img, ref8 = o.render(ocam, W, H, D, 0, spp, seed)
@@ -85,19 +78,6 @@ def _render_matches(ctx, o, oracle_mod, cam, W=40, H=28, D=4, spp=2, seed=9):
     ctx.set_camera(**cam); ctx.set_frame(W, H, D); ctx.set_tile(0, 1); ctx.reset()
     ctx.render(0, spp, seed)
     assert np.array_equal(ctx.read_accum(), ref_img) and np.array_equal(ctx.resolve_rgb8(), ref8)
-
-
-def _aimed_rays(verts, m, seed, spread=1.5):
-    rng = np.random.default_rng(seed)
-    n = len(verts)
-    ext = float(np.abs(verts).max())
-    ro = (rng.uniform(-spread, spread, (m, 3)) * ext).astype(np.float32)
-    tgt = verts.reshape(n, 3, 3)[rng.integers(0, n, m)].mean(axis=1)
-    rd = tgt - ro
-    rd /= np.maximum(np.linalg.norm(rd, axis=1, keepdims=True), 1e-30)
-    rd = rd.astype(np.float32)
-    rd[::23, 2] = 0.0
-    return ro, rd
 
 
 # ---- 1. leaves of every size up to 8, both builders -----------------------------------------------------------------------
@@ -155,33 +135,11 @@ def test_leaf_size_sweep_gives_tree_independent_hits(ctx, oracle_mod, tuning, sc
 
 # ---- 2. a traversal stack filled to its bound --------------------------------------------------------------------------
 
-_YZ = np.array([[-0.9, 1.1], [1.1, 1.1], [1.1, -0.9]])
-
-
-def _nest(k=20, r=1.5, m=16384):
-    """k triangles growing by r along +x and, at the near end, m identical ones.  Every triangle's box straddles the x axis and
-    no triangle reaches it, so a ray along the axis enters every box and hits nothing: its walk defers whatever the tree lets
-    it.  The big triangles glow (material 1) so that a render through the nest is not black."""
-    s = r ** np.arange(1, k + 1)
-    v = np.zeros((k + m, 3, 3))
-    v[:k, :, 0] = 2 * s[:, None] + np.array([0.0, 0.5, 1.0]) * s[:, None]
-    v[:k, :, 1:] = _YZ[None] * s[:, None, None]
-    v[k:, :, 0] = np.array([0.0, 0.5, 1.0])
-    v[k:, :, 1:] = _YZ[None]
-    return _glow(_scene(v.astype(np.float32).reshape(-1, 9)), np.arange(k))
-
-
 def test_full_traversal_stack_is_reached_and_gives_exact_hits(ctx, oracle_mod, tuning):
     arrays = _nest()
     verts = arrays["verts"]
-    rng = np.random.default_rng(5)
-    m = 256
-    ro = np.zeros((m, 3)); ro[:, 0] = -1.0; ro[:, 1:] = rng.uniform(-0.05, 0.05, (m, 2))
-    rd = np.zeros((m, 3)); rd[:, 0] = 1.0; rd[:, 1:] = rng.uniform(-1e-7, 1e-7, (m, 2))
-    ro[m // 2:, 1:] = rng.uniform(-3.0, 3.0, (m - m // 2, 2))                  # and rays that hit the big triangles
-    rd[m // 2:, 1:] = rng.uniform(-0.05, 0.05, (m - m // 2, 2))
-    rd /= np.linalg.norm(rd, axis=1, keepdims=True)
-    ro = ro.astype(np.float32); rd = rd.astype(np.float32)
+    ro, rd = nest_rays()
+    m = len(ro)
     o = oracle_mod.Oracle(arrays)
     ref = _brute(o, ro, rd)
     assert (ref[0][:m // 2] < 0).all() and (ref[0][m // 2:] >= 0).mean() > 0.2
@@ -245,13 +203,6 @@ def test_device_build_past_one_scan_round(ctx, oracle_mod, tuning):
     o.close()
 
 
-def _onion(n=60000, seed=5):
-    """a soup scaled by 0.9995^i: boxes nest around the origin"""
-    rng = np.random.default_rng(seed)
-    v = rng.uniform(-1, 1, (n, 1, 3)) + 0.05 * rng.uniform(-1, 1, (n, 3, 3))
-    return _glow(_scene((v * (0.9995 ** np.arange(n))[:, None, None]).astype(np.float32).reshape(n, 9)), np.arange(0, 200, 7))
-
-
 @pytest.mark.parametrize("name,leaf_max", [("onion 60k", 0), ("identical 300k", 1)])
 def test_device_builder_falls_back_to_the_host_builder(ctx, oracle_mod, tuning, name, leaf_max):
     """The onion's device-built tree would defer more than the stack holds; 300 000 identical triangles at leaf_max 1 outgrow the
@@ -273,26 +224,6 @@ def test_device_builder_falls_back_to_the_host_builder(ctx, oracle_mod, tuning, 
     o.close()
 
 
-SOAK_KINDS = ["line", "plane grid", "duplicates", "big coordinates", "slivers", "huge and tiny"]
-
-
-def _soak_scene(kind, seed):
-    """tools/soak_bvh.py's adversarial kinds"""
-    rng = np.random.default_rng(seed)
-    n = int(rng.choice([4096, 5000, 12345]))
-    c = rng.uniform(-1, 1, (n, 1, 3)); size = 0.02
-    if kind == "line": c = c * np.array([1.0, 0.0, 0.0]) + np.array([0.0, 0.3, -0.2])
-    elif kind == "plane grid":
-        g = int(np.ceil(np.sqrt(n))); ij = np.stack(np.meshgrid(np.arange(g), np.arange(g)), -1).reshape(-1, 2)[:n]
-        c = np.concatenate([ij / g * 2 - 1, np.zeros((n, 1))], axis=1)[:, None, :]
-    elif kind == "big coordinates": c = c * 1e15; size = 1e13
-    v = c + size * rng.uniform(-1, 1, (n, 3, 3))
-    if kind == "huge and tiny": v[: n // 50] = c[: n // 50] + 1.5 * rng.uniform(-1, 1, (n // 50, 3, 3))
-    if kind == "duplicates": v[n // 2:] = v[: n - n // 2]
-    if kind == "slivers": v[:, 2] = v[:, 0] + (v[:, 1] - v[:, 0]) * rng.uniform(0, 1, (n, 1)) + 1e-7 * rng.normal(0, 1, (n, 3))
-    return v.astype(np.float32).reshape(n, 9)
-
-
 @pytest.mark.parametrize("kind,seed", [(k, 100 + i) for i, k in enumerate(SOAK_KINDS)])
 def test_adversarial_geometry_gives_brute_force_hits(ctx, oracle_mod, tuning, kind, seed):
     verts = _soak_scene(kind, seed)
@@ -311,9 +242,6 @@ def test_adversarial_geometry_gives_brute_force_hits(ctx, oracle_mod, tuning, ki
 
 # ---- 4. the far domain -------------------------------------------------------------------------------------------------
 
-TINY = [0.0, -0.0, 1e-40, 1e-30, 1e-19, 1e-17]           # the 1 / d clamp at +-1e18 engages below 1e-18, not above
-
-
 def test_largest_accepted_coordinate(ctx):
     from pbrpathtracer_amd import ptk
     top = np.float32(2.0 ** 61 - 2.0 ** 37)
@@ -328,54 +256,12 @@ def test_largest_accepted_coordinate(ctx):
     ctx.upload_scene(_scene(v))
 
 
-def _off_box(verts, ro, rd, ref):
-    """Rays whose brute-force hit lies off its own triangle's box by more than the walk's slack (Walk::begin: 2^-21 x (max |ro| +
-    scene bound) per axis).  Moeller-Trumbore's acceptance error grows as 1 / cos of the incidence angle: a ray from 10^6 triangle
-    sizes away that grazes a triangle's plane can be "hit" tens of triangle sizes off the triangle.  No box slack covers that, so
-    for these rays the closest hit is not tree-independent - the oracle's own tree disagrees with its brute force too."""
-    tri, tuv = ref
-    h = np.nonzero(tri >= 0)[0]
-    p = ro[h].astype(np.float64) + tuv[h, :1].astype(np.float64) * rd[h].astype(np.float64)
-    t3 = verts[tri[h]].reshape(-1, 3, 3).astype(np.float64)
-    vmax = float(np.abs(verts).max())
-    slack = (np.abs(ro[h]).max(axis=1).astype(np.float64) + 3.1 * (1.01 * vmax + 1e-3)) * 2.0 ** -21
-    off = np.maximum(t3.min(axis=1) - p, p - t3.max(axis=1)).max(axis=1)
-    out = np.zeros(len(ro), bool)
-    out[h] = off > slack
-    return out
-
-
 @pytest.mark.parametrize("e", [20, 40, 59])
 def test_far_clusters_and_far_rays_give_brute_force_hits(ctx, oracle_mod, tuning, e):
-    rng = np.random.default_rng(e)
-    off = 2.0 ** e
-    n = 4096
-    c = rng.uniform(-1, 1, (n, 1, 3)) * 2.0 ** -12 * off + off * np.array([1.0, -0.5, 0.25])
-    rot = np.linalg.qr(rng.normal(0, 1, (n, 3, 3)))[0]                          # a right isosceles triangle of legs 2^-17 x offset, turned
-    v = c + 2.0 ** -17 * off * np.einsum("kj,nij->nki", np.array([[0.0, 0, 0], [1, 0, 0], [0, 1, 0]]), rot)
-    if e == 59:
-        v[0] = np.array([[2.0 ** 61 - 2.0 ** 37, 0, 0], [2.0 ** 60, 2.0 ** 58, 0], [2.0 ** 60, 0, 2.0 ** 58]])   # the largest accepted value
-    verts = v.astype(np.float32).reshape(n, 9)
-    e1 = verts[:, 3:6].astype(np.float64) - verts[:, 0:3]
-    assert (np.linalg.norm(e1, axis=1)[1:] >= 2.0 ** -20 * off).all()
+    case = far_case(e)
+    verts, ro, rd, dist = case["verts"], case["ro"], case["rd"], case["dist"]
     arrays = _scene(verts)
-    m = 2 * 6 * 50
-    tgt = verts.reshape(n, 3, 3)[rng.integers(1, n, m)].astype(np.float64).mean(axis=1)
-    d = rng.normal(0, 1, (m, 3))
-    axis = rng.integers(0, 3, m)
-    tiny = np.tile(TINY, m // len(TINY)) * np.where((np.arange(m) // len(TINY)) % 2 == 0, 1.0, -1.0)
-    d[np.arange(m), axis] = 0.0
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    d[np.arange(m), axis] = tiny
-    leg = 2.0 ** -17 * off
-    # far: up to 2^60 away, or 2^22 triangle legs; near: close enough that Moeller-Trumbore's products (legs^2 x distance) stay
-    # finite - at 2^59 the far rays' products overflow and every one of them misses, in the reference's arithmetic as here
-    far = np.minimum(2.0 ** 60 - np.abs(tgt).max(axis=1), 2.0 ** 22 * leg)
-    dist = np.concatenate([far[: m // 2], np.minimum(far[m // 2:], 2.0 ** 118 / leg ** 2)]) * rng.uniform(0.5, 1.0, m)
-    ro = (tgt - dist[:, None] * d).astype(np.float32)
-    rd = d.astype(np.float32)
-    assert (np.abs(ro) <= 2.0 ** 60).all()
-    assert rd[np.arange(m), axis].tolist() == np.float32(tiny).tolist() and (np.signbit(rd[np.arange(m), axis]) == np.signbit(tiny)).all()
+    m = len(ro)
     o = oracle_mod.Oracle(arrays)
     ref = _brute(o, ro, rd)
     o.close()
