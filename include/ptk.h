@@ -1170,6 +1170,9 @@ int ptk_probe_unpack(ptk_ctx* ctx, int world, const float* host_packed /* all ra
  * reach compiled out; 0 launches the generic FLAT kernel for it as well.  Bit-identical either way (tests/test_gpu_plain_kernel.py).
  * A scene is plain when ptk_scene_is_plain holds for its tables AND the primary-hit cache is active (aperture 0, "primary_cache"
  * and "flat" on); decided anew for every render, so material edits, a new scene or an opened aperture take effect at once.
+ * "lambert_kernel" = 0/1 (default 1): a plain scene for which ptk_scene_is_lambert holds as well is traced by the LAMBERT level of
+ * the PLAIN kernel, which keeps the diffuse route alone; 0 launches the PLAIN kernel's generic level.  Bit-identical either way
+ * (tests/test_gpu_lambert_kernel.py); decided with "plain_kernel", per render.
  * No environment variable reaches the library. */
 int ptk_set_option(ptk_ctx* ctx, const char* name, double value);
 
@@ -1195,6 +1198,15 @@ int ptk_trace_variant(ptk_ctx* ctx, int* variant);
  * (type 0) with none of its five shading textures (tex[0..4] < 0), and no triangle is smoothed or has a material with an opacity
  * texture (tex[5] >= 0); 0 otherwise */
 int ptk_scene_is_plain(const ptk_scene_desc* scene);
+/* the scene-table half of the LAMBERT predicate, no device needed: 1 when ptk_scene_is_plain holds and NO material of the table
+ * has reflectiveness > 0.0f.  Zeros of either sign, negatives and NaN qualify: the opaque route's specular test is
+ * `draw < reflectiveness` with a draw in [0, 1), false for all of them whatever is drawn, so such a scene never takes a specular
+ * bounce and only the draw's advance of the stream is left of the test.  The smallest positive denormal does not qualify: a
+ * draw of exactly 0 is below it.  0 otherwise */
+int ptk_scene_is_lambert(const ptk_scene_desc* scene);
+/* 1 when the newest trace launch of this context ran the LAMBERT level of the PLAIN kernel (ptk_trace_variant reports
+ * PTK_TRACE_FLAT_PLAIN for both of its levels), else 0 */
+int ptk_trace_is_lambert(ptk_ctx* ctx, int* lambert);
 int ptk_kernel_log_read(ptk_ctx* ctx, float* trace_ms, int max_entries, int* num_entries);
 int ptk_collect_stats(ptk_ctx* ctx, uint32_t first_sample, uint32_t spp_count, uint64_t seed, ptk_stats* out);
 int ptk_bvh_info(ptk_ctx* ctx, int32_t* num_nodes, int32_t* depth /* wide nodes on the longest chain */, int32_t* num_leaf_tris);

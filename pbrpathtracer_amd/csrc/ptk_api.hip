@@ -114,6 +114,18 @@ bool plain_tables(int32_t n, const uint8_t* smoothing, const int32_t* material, 
     return true;
 }
 
+// "Lambert" (ptk.h ptk_scene_is_lambert): a plain scene no material of which has reflectiveness > 0.  The specular draw of the
+// opaque route, `draw < reflectiveness` with draw in [0, 1), is then false whatever is drawn - for zeros of either sign, negatives
+// and NaN alike - so the LAMBERT level of the PLAIN kernel keeps the draw's advance of the stream and the diffuse route alone.
+// Untextured by plainness: the table's value is the one the kernel compares.
+bool lambert_tables(int32_t n, const uint8_t* smoothing, const int32_t* material, int32_t num_materials, const ptk_material* mats)
+{
+    if (!plain_tables(n, smoothing, material, num_materials, mats)) return false;
+    for (int32_t i = 0; i < num_materials; i++)
+        if (mats[i].reflectiveness > 0.0f) return false;
+    return true;
+}
+
 bool primary_cacheable(const ptk_ctx* c)
 {
     return c->opt_primary_cache && c->aperture == 0.0f && !c->scene_has_opacity && c->have_scene && c->d_primary_hit;
@@ -228,6 +240,7 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
     if (const int rc = use_primary_cache(c, p); rc != PTK_OK) return rc;
     // decided per render from the staged state: a material edit, a new scene or an opened aperture since the last one is seen here
     p.plain = (c->opt_plain_kernel && c->scene_plain && p.flat_count > 0 && p.primary_hit != nullptr) ? 1 : 0;
+    p.lambert = (p.plain && c->opt_lambert_kernel && c->scene_lambert) ? 1 : 0;
     if (!c->pixel_rng_valid || c->pixel_rng_seed != seed)
     {
         launch_pixel_rng((uint32_t)seed, (uint32_t)(seed >> 32), c->width * c->height, c->d_pixel_rng, c->stream);
@@ -408,6 +421,7 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
         else launch_trace(p, tiles * 4, c->resident_waves, tstream, stats);
         HIPCHK(c, hipGetLastError());
         c->last_trace_variant = p.flat_count <= 0 ? PTK_TRACE_BVH : ((p.plain && !stats) ? PTK_TRACE_FLAT_PLAIN : PTK_TRACE_FLAT);
+        c->last_trace_lambert = p.flat_count > 0 && p.plain && p.lambert && !stats;
         if (timed && pi >= 0) HIPCHK(c, hipEventRecord(c->ev[pi][1], tstream));
         if (kl >= 0) { HIPCHK(c, hipEventRecord(c->klog_ev[2 * kl + 1], tstream)); c->klog_n = kl + 1; }
         if (overlap)
@@ -884,6 +898,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
     c->h_flat_smoothing.clear(); c->h_flat_material.clear();
     if (n > 0 && n <= 16) { c->h_flat_smoothing.assign(s->smoothing, s->smoothing + n); c->h_flat_material.assign(s->material, s->material + n); }
     c->scene_plain = plain_tables(n, s->smoothing, s->material, s->num_materials, s->materials);
+    c->scene_lambert = lambert_tables(n, s->smoothing, s->material, s->num_materials, s->materials);
     c->h_light_material.resize(s->num_lights);
     for (int32_t k = 0; k < s->num_lights; k++) c->h_light_material[k] = s->material[s->lights[k]];
     c->primary_hit_dirty = true;
@@ -927,6 +942,7 @@ int ptk_update_materials(ptk_ctx* c, int32_t num_materials, const ptk_material* 
     HIPCHK(c, hipStreamSynchronize(c->stream));          // the host vectors above go out of scope
     c->h_materials.assign(materials, materials + num_materials);
     c->scene_plain = plain_tables((int32_t)c->h_flat_material.size(), c->h_flat_smoothing.data(), c->h_flat_material.data(), num_materials, materials);
+    c->scene_lambert = lambert_tables((int32_t)c->h_flat_material.size(), c->h_flat_smoothing.data(), c->h_flat_material.data(), num_materials, materials);
     c->inputs_dirty = true;
     return PTK_OK;
 }
@@ -937,10 +953,23 @@ int ptk_scene_is_plain(const ptk_scene_desc* s)
     return plain_tables(s->num_triangles, s->smoothing, s->material, s->num_materials, s->materials) ? 1 : 0;
 }
 
+int ptk_scene_is_lambert(const ptk_scene_desc* s)
+{
+    if (!s) return 0;
+    return lambert_tables(s->num_triangles, s->smoothing, s->material, s->num_materials, s->materials) ? 1 : 0;
+}
+
 int ptk_trace_variant(ptk_ctx* c, int* variant)
 {
     if (!c || !variant) return PTK_ERR_BAD_ARG;
     *variant = c->last_trace_variant;
+    return PTK_OK;
+}
+
+int ptk_trace_is_lambert(ptk_ctx* c, int* lambert)
+{
+    if (!c || !lambert) return PTK_ERR_BAD_ARG;
+    *lambert = c->last_trace_lambert ? 1 : 0;
     return PTK_OK;
 }
 
@@ -1703,6 +1732,11 @@ int ptk_set_option(ptk_ctx* c, const char* name, double value)
     if (!std::strcmp(name, "plain_kernel"))
     {
         c->opt_plain_kernel = value != 0.0;
+        return PTK_OK;
+    }
+    if (!std::strcmp(name, "lambert_kernel"))
+    {
+        c->opt_lambert_kernel = value != 0.0;
         return PTK_OK;
     }
     if (!std::strcmp(name, "device_build"))

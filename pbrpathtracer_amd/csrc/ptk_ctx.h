@@ -59,7 +59,10 @@ struct ptk_ctx {
     float bvh_pad = 0.0f;                        // the builders' box padding for the current scene extent
     bool scene_plain = false;           // plain_tables() of the staged scene: kept current by ptk_upload_scene and ptk_update_materials
     int opt_plain_kernel = 1;           // 0: plain scenes launch the generic FLAT kernel too (tests, A/B runs)
+    bool scene_lambert = false;         // lambert_tables() of the staged scene (plain and no reflectiveness > 0): kept current with scene_plain
+    int opt_lambert_kernel = 1;         // 0: Lambert scenes launch the PLAIN kernel's generic level (tests, A/B runs)
     int last_trace_variant = PTK_TRACE_NONE;     // of the newest trace launch (ptk_trace_variant)
+    bool last_trace_lambert = false;    // ... and whether it ran the LAMBERT level of the PLAIN kernel (ptk_trace_is_lambert)
 
     // camera (host copies, already normalised / clamped like the reference setters)
     float cam_pos[3] = { 0, 0, 0 }, cam_dir[3] = { 0, 0, 1 }, cam_up[3] = { 0, 1, 0 };

@@ -110,6 +110,8 @@ struct RenderParams {
     int plain;                  // 1: launch_trace takes the PLAIN variant of the FLAT kernel - a host-side promise (ptk_api.hip plain_scene +
                                 // primary-hit cache) that every material is opaque and untextured, no triangle is smoothed or has an
                                 // opacity texture and primary_hit is set; no kernel reads it (last field: the others keep their offsets)
+    int lambert;                // 1 (only with plain): ... and no material has reflectiveness > 0 (ptk_api.hip lambert_tables), so launch_trace
+                                // takes the LAMBERT level of the PLAIN kernel; no kernel reads it either (behind plain: same offsets again)
 };
 
 struct PrimaryParams {

@@ -546,7 +546,13 @@ template <> struct FlatFrames<false> {};
 // PLAIN (trace_kernel): every material is opaque and untextured and no triangle is smoothed, so the texture lookups, the UVs,
 // the smoothed and normal-mapped normals and the glass branch are dead code; what remains is the mtype == 0 route, operation
 // for operation and draw for draw.
-template <bool STATS, bool FLAT, bool PLAIN, class PT>
+// LAMBERT (a PLAIN scene none of whose materials has reflectiveness > 0, ptk.h ptk_scene_is_lambert): the specular draw
+// `rng.next() < reflectiveness` (:601) is false for every draw - u01 is never negative, and no x >= 0 is below a zero of either
+// sign, a negative or a NaN - so only the stream's advance is left of it and the route is known at compile time: the hemisphere
+// sampler about n, weight = diffuse, a light sample.  No bounce is specular, so `iter` equals `depth` and is neither read nor
+// written; reflect(), the mirror and lobe samplers, roughness and specular are gone.  Every operation that is left is the PLAIN
+// kernel's, in its order.
+template <bool STATS, bool FLAT, bool PLAIN, bool LAMBERT, class PT>
 __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS, int* stack, Rng& rng, v3& L, v3& T, v3& Tdi, v3& nextDir,
                                                   int& depth, int& iter, bool& inside, const uint32_t ray, Counters& cnt)
 {
@@ -623,8 +629,9 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
     if (dot(n, rd) > 0.0f) n = neg(n);              // :567-568
     p = add(p, muls(n, PTK_EPS));                   // :569
 
+    static_assert(PLAIN || !LAMBERT, "LAMBERT is a level of the PLAIN kernel");
     bool ended = false;
-    if (!(iter < P.max_depth)) ended = true;        // :571 terminal bounce: no emission
+    if (!((LAMBERT ? depth : iter) < P.max_depth)) ended = true;        // :571 terminal bounce: no emission
     else
     {
         v3 diffuse = V(m0.x, m0.y, m0.z);
@@ -639,7 +646,8 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
         const v3 specular = V(m1.x, m1.y, m1.z);
         const float emissI = m1.w;
 
-        depth++; iter++;                            // :586-587
+        depth++;                                    // :586-587
+        if (!LAMBERT) iter++;
         const float prob = m3.w;                    // min(0.95, max(diffuse)) of the constant colour
         if (depth >= P.max_depth)
         {
@@ -647,7 +655,7 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
         }
         if (!ended)
         {
-            v3 r = reflect(rd, n);                  // :596
+            const v3 r = LAMBERT ? rd : reflect(rd, n);     // :596 (read by the mirror and lobe samplers only)
             v3 dir;
             v3 weight;
             bool diffuse_bounce = false;
@@ -655,7 +663,14 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
             // (:603-624, :679-700) and the hemisphere sampler twice more (:631-636, :717-722);
             // here the branch only picks the sampler's arguments and ONE call does the work
             int sampler = 0;                        // 0: mirror direction r, 1: hemisphere about n, 2: lobe about r
-            if (mtype == 0)
+            if (LAMBERT)
+            {
+                rng.state = rng.state * 747796405u + rng.inc;      // :601's draw, whose comparison is false whatever it gives
+                sampler = 1;                        // :631-636
+                diffuse_bounce = true;
+                weight = diffuse;                   // :638
+            }
+            else if (mtype == 0)
             {
                 if (rng.next() < reflectiveness)    // :601
                 {

@@ -254,7 +254,9 @@ enum : int { ST_NEED = 0, ST_GEN = 1, ST_TRAV = 2, ST_SHADE = 3, ST_DONE = 4 };
 // camera (ptk_api.hip decides, see RenderParams::plain): the same text with everything such a scene cannot reach compiled out -
 // textures, UVs, smoothed / mapped normals, stochastic opacity and its two keys per pass, the glass branch, the camera-ray block.
 // The route it does take is untouched, so its samples are bit-identical to the generic kernel's.
-template <bool STATS, bool FLAT, bool PLAIN>
+// LAMBERT = a PLAIN scene in which no material has reflectiveness > 0 (RenderParams::lambert): the specular draw can never succeed,
+// so shade_interaction keeps its advance of the stream and the diffuse route alone, and `iter`, equal to `depth`, is not carried.
+template <bool STATS, bool FLAT, bool PLAIN, bool LAMBERT = false>
 __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : FLAT ? PTK_TRACE_WAVES : PTK_TRACE_WAVES_BVH)) void trace_kernel(const RenderParams* __restrict__ Pp)
 {
     // the parameters live in the launch's queue block, in the constant address space: fields are s_load-ed where they are
@@ -262,6 +264,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
     typedef const __attribute__((address_space(4))) RenderParams ConstParams;
     ConstParams& P = *(ConstParams*)(uintptr_t)Pp;
     static_assert(FLAT || !PLAIN, "PLAIN is a variant of the FLAT kernel");
+    static_assert((PLAIN && !STATS) || !LAMBERT, "LAMBERT is a level of the PLAIN kernel; the STATS kernels count the generic route");
     __shared__ int lds_stack[FLAT ? 1 : PTK_STACK_ROWS * PTK_TRACE_BLOCK];
     if (P.exit_flag && __hip_atomic_load(P.exit_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= P.exit_gen) return;     // an Exit() named this render or a later one
 
@@ -361,7 +364,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
             W.occl_tri = -1;                                                                      \
             W.begin(W.ro, nextDir, num_nodes_u, stack, scene_bound_u);                                   \
         }                                                                                         \
-        else if (!hit_ || (FLAT && !STATS && !(iter < P.max_depth))) PTK_FINISH_PATH();     /* :550 miss -> black */  \
+        else if (!hit_ || (FLAT && !STATS && !((LAMBERT ? depth : iter) < P.max_depth))) PTK_FINISH_PATH();     /* :550 miss -> black */  \
         else st = ST_SHADE;                                                                       \
     } while (0)
 
@@ -553,7 +556,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
                     W.node = NODE_EXIT; W.top = stack; W.tri_left = 0;
                 }
                 // ---- one surface interaction of PathTracer::Trace, pathtracer.cpp:551-727 ----
-                const bool ended = shade_interaction<STATS, FLAT, PLAIN>(P, W, WS, stack, rng, L, T, Tdi, nextDir, depth, iter, inside, ray, cnt);
+                const bool ended = shade_interaction<STATS, FLAT, PLAIN, LAMBERT>(P, W, WS, stack, rng, L, T, Tdi, nextDir, depth, iter, inside, ray, cnt);
                 if (ended) PTK_FINISH_PATH();
                 else st = ST_TRAV;
             }
@@ -703,7 +706,8 @@ void launch_trace(const RenderParams& p0, int num_subtiles, int resident_waves, 
     else if (stats) hipLaunchKernelGGL((trace_kernel<true, false, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else
 #endif
-    if (flat && p.plain) hipLaunchKernelGGL((trace_kernel<false, true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    if (flat && p.plain && p.lambert) hipLaunchKernelGGL((trace_kernel<false, true, true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    else if (flat && p.plain) hipLaunchKernelGGL((trace_kernel<false, true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else if (flat) hipLaunchKernelGGL((trace_kernel<false, true, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else hipLaunchKernelGGL((trace_kernel<false, false, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
 }

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(PTK_RAYS_BLOCK, PTK_RAYS_WAVES) void PTK_RAYS_KERNE
         if (st == ST_SHADE)
         {
             // ---- one surface interaction of PathTracer::Trace, pathtracer.cpp:551-727 ----
-            const bool ended = shade_interaction<false, false, false>(P, W, W, stack, rng, L, T, Tdi, nextDir, depth, iter, inside, ray, cnt);
+            const bool ended = shade_interaction<false, false, false, false>(P, W, W, stack, rng, L, T, Tdi, nextDir, depth, iter, inside, ray, cnt);
             if (ended) PTK_FINISH_PATH();
             else st = ST_TRAV;
         }

@@ -132,7 +132,7 @@ SYMBOLS = [
     "ptk_gather_wait", "ptk_read_gathered", "ptk_gathered_device_ptr", "ptk_probe_pack", "ptk_probe_unpack",
     "ptk_bind_out_image", "ptk_bind_out_device", "ptk_bind_gl_buffer", "ptk_comm_info", "ptk_kernel_log", "ptk_kernel_log_read",
     "ptk_debug_stall_exchange", "ptk_render_adaptive", "ptk_read_sample_counts", "ptk_read_moments",
-    "ptk_trace_variant", "ptk_scene_is_plain",
+    "ptk_trace_variant", "ptk_scene_is_plain", "ptk_scene_is_lambert", "ptk_trace_is_lambert",
     "ptk_feature_info", "ptk_render_features", "ptk_read_feature", "ptk_feature_device_ptr", "ptk_pick",
     "ptk_update_geometry", "ptk_update_geometry_device", "ptk_geometry_info", "ptk_geometry_timing",
     "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
@@ -294,6 +294,8 @@ def _load_locked() -> C.CDLL:
         L.ptk_temporal_variance_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
         L.ptk_denoise_temporal.argtypes = [vp, C.POINTER(DenoiseParams), u32]
         L.ptk_last_variance_ms.argtypes = [vp, fp, fp]
+        L.ptk_scene_is_lambert.argtypes = [C.POINTER(SceneDesc)]
+        L.ptk_trace_is_lambert.argtypes = [vp, C.POINTER(C.c_int)]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -404,6 +406,13 @@ def scene_is_plain(arrays: dict) -> bool:
     a = normalise_arrays(arrays)
     d = scene_desc(a)
     return bool(load().ptk_scene_is_plain(C.byref(d)))
+
+
+def scene_is_lambert(arrays: dict) -> bool:
+    """ptk_scene_is_lambert on a scene's arrays: plain, and no material has reflectiveness > 0 (no device needed)."""
+    a = normalise_arrays(arrays)
+    d = scene_desc(a)
+    return bool(load().ptk_scene_is_lambert(C.byref(d)))
 
 
 def normalise_arrays(a: dict) -> dict:
@@ -1415,6 +1424,12 @@ class Context:
         v = C.c_int(0)
         self._chk(self.L.ptk_trace_variant(self.h, C.byref(v)), "ptk_trace_variant")
         return v.value
+
+    def trace_is_lambert(self) -> bool:
+        """Whether the newest launch ran the LAMBERT level of the PLAIN kernel (trace_variant gives TRACE_FLAT_PLAIN for both)."""
+        v = C.c_int(0)
+        self._chk(self.L.ptk_trace_is_lambert(self.h, C.byref(v)), "ptk_trace_is_lambert")
+        return bool(v.value)
 
     def set_option(self, name: str, value: float):
         self._chk(self.L.ptk_set_option(self.h, name.encode(), float(value)), "ptk_set_option")

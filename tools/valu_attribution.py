@@ -2,7 +2,7 @@
 """Dynamic VALU budget of a FLAT trace kernel on a config, block by block: static VALU counts of the kernel's basic blocks
 (tools/isa_blocks.py's parser on `hipcc -S` output) times how often the STATS kernel says each block ran.
 
-    python3 tools/valu_attribution.py kernel.s generic|plain stats.json [measured SQ_INSTS_VALU of one full launch]
+    python3 tools/valu_attribution.py kernel.s generic|plain|lambert stats.json [measured SQ_INSTS_VALU of one full launch]
 
   kernel.s    hipcc -O3 ... --offload-arch=gfx950 --offload-device-only -S ptk_kernels.hip (the Makefile's flags)
   stats.json  ptk_collect_stats of one full launch (Context.collect_stats(0, spp, seed) as JSON)
@@ -15,7 +15,9 @@ block is therefore given twice: as the static sum of its blocks that a config ca
 when a measured SQ_INSTS_VALU is passed, as what is left of the measurement once the exactly known groups are subtracted.
 
 The block labels belong to ONE build of the kernel: each group below names its labels and the VALU count they must add up to,
-and the script stops when the assembly no longer matches (re-derive the groups from tools/isa_blocks.py's table then)."""
+and the script stops when the assembly no longer matches (re-derive the groups from tools/isa_blocks.py's table then).  The label
+prefix (.LBB<n>_, n = the kernel's position in its file) is read from the assembly.  "lambert" is the LAMBERT level of the PLAIN
+kernel; its stats come from the same STATS kernel (the counters-enabled kernels have neither variant)."""
 import json
 import re
 import sys
@@ -43,7 +45,7 @@ def blocks_of(path, want):
 #   W = triangle passes (walk_wave_iters), S = shade executions (shade_wave_execs), T = W + S main-loop iterations,
 #   N = triangles per pass, I = work items taken (paths_started / 512: 64 pixels x 8 samples, an estimate)
 SPECS = {
-    "generic": dict(symbol="trace_kernelILb0ELb1ELb0E", prefix=".LBB15_", groups=[
+    "generic": dict(symbol="trace_kernelILb0ELb1ELb0ELb0E", groups=[
         ("need ballot, votes, block choice", [2, 12, 66], 14, "T"),
         ("state copies at the loop's back edges", [9], 12, "T"),          # (one of the five copy blocks 9 / 10 / 11 / 91 / 229 per iteration)
         ("dealing units to lanes", [14, 16, 18, 58, 63], 87, "D"),
@@ -56,14 +58,23 @@ SPECS = {
         ("camera-ray block", [92, 99, 100, 104], 212, "0"),
         ("shade block: texture lookups", [135, 230, 231, 232], 153, "0"),
     ], shade=(106, 227)),
-    "plain": dict(symbol="trace_kernelILb0ELb1ELb1E", prefix=".LBB14_", groups=[
-        ("need ballot, votes, block choice", [2, 10, 64], 14, "T"),
-        ("dealing units to lanes", [12, 14, 16, 56, 61], 87, "D"),
-        ("taking a work item", [7, 19, 20, 25, 26, 28, 31, 34, 37, 39, 48, 53, 55], 305, "I"),
-        ("triangle loop", [70, 72], 67, "W*N", 63),                        # (63 always + 2 + 2 hit-update moves behind execz)
+    "plain": dict(symbol="trace_kernelILb0ELb1ELb1ELb0E", groups=[
+        ("need ballot, votes, block choice", [2, 10, 12, 67], 18, "T"),
+        ("dealing units to lanes", [15, 17, 19, 59, 64], 87, "D"),
+        ("taking a work item", [7, 22, 23, 28, 29, 31, 34, 37, 40, 42, 51, 56, 58], 306, "I"),
+        ("triangle loop", [73, 75], 67, "W*N", 63),                        # (63 always + 2 + 2 hit-update moves behind execz)
         ("triangle loop: hit updates", [], 4, "W*N*U"),
-        ("pass epilogue", [75, 77], 15, "W"),
-    ], shade=(81, 128)),
+        ("pass epilogue", [78, 80, 82], 15, "W"),
+    ], shade=(86, 134)),
+    # the same blocks up to the shade block, which is shorter: no specular-draw output, no reflect(), no mirror / lobe routes
+    "lambert": dict(symbol="trace_kernelILb0ELb1ELb1ELb1E", groups=[
+        ("need ballot, votes, block choice", [2, 10, 12, 67], 18, "T"),
+        ("dealing units to lanes", [15, 17, 19, 59, 64], 87, "D"),
+        ("taking a work item", [7, 22, 23, 28, 29, 31, 34, 37, 40, 42, 51, 56, 58], 305, "I"),
+        ("triangle loop", [73, 75], 67, "W*N", 63),
+        ("triangle loop: hit updates", [], 4, "W*N*U"),
+        ("pass epilogue", [78, 80, 82], 15, "W"),
+    ], shade=(86, 116)),
 }
 
 
@@ -73,6 +84,10 @@ def main():
     spec = SPECS[which]
     st = json.load(open(stats_path))
     blk = blocks_of(path, spec["symbol"])
+    prefixes = {m.group(0) for k in blk for m in [re.match(r"\.LBB\d+_", k)] if m}
+    if len(prefixes) != 1:
+        sys.exit(f"{spec['symbol']}: expected the blocks of one kernel, found label prefixes {sorted(prefixes)}")
+    spec["prefix"] = prefixes.pop()
     num = lambda label: int(label[len(spec["prefix"]):]) if label.startswith(spec["prefix"]) and label[len(spec["prefix"]):].isdigit() else None
     W, S = st["walk_wave_iters"], st["shade_wave_execs"]
     N = st["tri_tests"] / max(1, st["rays"])                               # every ray of a pass meets every triangle
