@@ -1173,6 +1173,10 @@ int ptk_probe_unpack(ptk_ctx* ctx, int world, const float* host_packed /* all ra
  * "lambert_kernel" = 0/1 (default 1): a plain scene for which ptk_scene_is_lambert holds as well is traced by the LAMBERT level of
  * the PLAIN kernel, which keeps the diffuse route alone; 0 launches the PLAIN kernel's generic level.  Bit-identical either way
  * (tests/test_gpu_lambert_kernel.py); decided with "plain_kernel", per render.
+ * "flat_zero_classes" = 0/1 (default 1): the bit-exact PLAIN kernel sends each triangle of the flat list to a body of its triangle
+ * test from which the operations on edge words stored as zeros are deleted (ptk_flat_zero_class); 0 makes its pass treat every
+ * record as class 0, the full test.  Bit-identical either way (tests/test_gpu_flat_zero_classes.py); takes effect behind the
+ * renders already queued.  The contracted builds ("contract" 1, 2) and every other kernel run the full test regardless.
  * No environment variable reaches the library. */
 int ptk_set_option(ptk_ctx* ctx, const char* name, double value);
 
@@ -1207,6 +1211,19 @@ int ptk_scene_is_lambert(const ptk_scene_desc* scene);
 /* 1 when the newest trace launch of this context ran the LAMBERT level of the PLAIN kernel (ptk_trace_variant reports
  * PTK_TRACE_FLAT_PLAIN for both of its levels), else 0 */
 int ptk_trace_is_lambert(ptk_ctx* ctx, int* lambert);
+/* Zero classes of the flat triangle list (scenes of <= 16 triangles), no device needed: the class, 0..15, of a record whose
+ * stored edges are edges[0..2] = e1 = v2 - v1 and edges[3..5] = e2 = v3 - v1 (float32 subtractions).  A class stands for a mask
+ * over those six words, ptk_flat_zero_mask(class): bit k set = word k is known to be stored as +0 or -0, so the triangle test
+ * may delete the operations on it without changing which hits it accepts or any bit of their distance.  Class 0 (mask 0) is the
+ * full test; 1..3 are triangles in an axis plane (both edges zero on x / y / z); 4..15 such triangles one of whose stored edges is
+ * parallel to an axis as well.  A record gets the class with the most bits whose mask is a SUBSET of its words that compare
+ * equal to 0.0f, the lowest such class; a record with an all-zero edge is class 0.  ptk_flat_zero_mask: -1 outside 0..15. */
+int ptk_flat_zero_class(const float edges[6]);
+int ptk_flat_zero_mask(int zero_class);
+/* the classes the device holds for the uploaded scene's triangles, as classified there from the records (after ptk_upload_scene
+ * and after every geometry update), whatever "flat_zero_classes" says; out[k] = -1 for k >= the triangle count.  An error when
+ * the scene has no flat list (more than 16 triangles, or the "device_build" option) */
+int ptk_flat_classes(ptk_ctx* ctx, int32_t out[16]);
 int ptk_kernel_log_read(ptk_ctx* ctx, float* trace_ms, int max_entries, int* num_entries);
 int ptk_collect_stats(ptk_ctx* ctx, uint32_t first_sample, uint32_t spp_count, uint64_t seed, ptk_stats* out);
 int ptk_bvh_info(ptk_ctx* ctx, int32_t* num_nodes, int32_t* depth /* wide nodes on the longest chain */, int32_t* num_leaf_tris);

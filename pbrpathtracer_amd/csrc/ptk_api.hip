@@ -20,6 +20,7 @@
 #include "ptk_device_fn.h"
 #include "ptk_adaptive.h"
 #include "ptk_refit.h"
+#include "ptk_flat_mt.h"
 
 using namespace ptk;
 
@@ -865,7 +866,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
         dfree(c->d_flat_tris);
         if (n > 0 && n <= 16)
         {
-            std::vector<float> flat((size_t)(FLAT_FRAMES_AT + n * FLAT_FRAME_F4) * 4);     // records, room up to FLAT_MAX_TRIS, frame table
+            std::vector<float> flat((size_t)FLAT_TABLE_F4 * 4);     // records, room up to FLAT_MAX_TRIS, frame table, class table
             for (int32_t k = 0; k < n; k++)             // record of leaf position k holds triangle bvh.order[k]
                 std::memcpy(flat.data() + (size_t)bvh.order[k] * TRI_F4 * 4, tris.data() + (size_t)k * TRI_F4 * 4, TRI_F4 * 16);
             HIPCHK(c, up((void**)&c->d_flat_tris, flat.data(), flat.size() * 4));
@@ -874,6 +875,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
         if (c->d_flat_tris)                             // the frame table behind the flat records, from the normals just written
         {
             launch_flat_frames(c->d_shade, c->d_flat_tris, 0, n, c->stream);
+            launch_flat_classes(c->d_flat_tris, n, c->opt_flat_zero_classes, c->stream);     // ... and the class table, from the records
             HIPCHK(c, hipGetLastError());
         }
         HIPCHK(c, up((void**)&c->d_verts_res, s->verts, (size_t)n * 9 * sizeof(float)));
@@ -957,6 +959,29 @@ int ptk_scene_is_lambert(const ptk_scene_desc* s)
 {
     if (!s) return 0;
     return lambert_tables(s->num_triangles, s->smoothing, s->material, s->num_materials, s->materials) ? 1 : 0;
+}
+
+int ptk_flat_zero_class(const float edges[6])
+{
+    return edges ? ptk_mt::flat_zero_class(edges) : 0;          // the function classify_flat_kernel calls
+}
+
+int ptk_flat_zero_mask(int cls)
+{
+    return cls >= 0 && cls < ptk_mt::FLAT_ZERO_CLASSES ? (int)ptk_mt::flat_zero_mask(cls) : -1;
+}
+
+int ptk_flat_classes(ptk_ctx* c, int32_t out[16])
+{
+    if (!c || !out) return PTK_ERR_BAD_ARG;
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (!c->d_flat_tris) return fail(c, PTK_ERR_BAD_ARG, "the scene has no flat triangle list (more than 16 triangles, or built on the device)");
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long word = 0ull;
+    HIPCHK(c, hipMemcpyAsync(&word, (const char*)(c->d_flat_tris + FLAT_CLASSES_AT) + 8, sizeof(word), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < FLAT_MAX_TRIS; k++) out[k] = k < c->num_tris ? (int32_t)((word >> (k * 4)) & 15ull) : -1;
+    return PTK_OK;
 }
 
 int ptk_trace_variant(ptk_ctx* c, int* variant)
@@ -1737,6 +1762,20 @@ int ptk_set_option(ptk_ctx* c, const char* name, double value)
     if (!std::strcmp(name, "lambert_kernel"))
     {
         c->opt_lambert_kernel = value != 0.0;
+        return PTK_OK;
+    }
+    if (!std::strcmp(name, "flat_zero_classes"))
+    {
+        const int use = value != 0.0 ? 1 : 0;
+        if (use != c->opt_flat_zero_classes && c->have_scene && c->d_flat_tris)
+        {
+            // the word the pass reads is rewritten behind every render already queued and ahead of every later one, like a geometry update
+            HIPCHK(c, hipSetDevice(c->device));
+            launch_flat_classes(c->d_flat_tris, c->num_tris, use, c->stream);
+            HIPCHK(c, hipGetLastError());
+            c->inputs_dirty = true;
+        }
+        c->opt_flat_zero_classes = use;
         return PTK_OK;
     }
     if (!std::strcmp(name, "device_build"))

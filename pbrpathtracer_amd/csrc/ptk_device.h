@@ -33,6 +33,12 @@ constexpr int TRI_F4 = 3;
 constexpr int FLAT_MAX_TRIS = 16;
 constexpr int FLAT_FRAMES_AT = FLAT_MAX_TRIS * TRI_F4;      // in float4s from flat_tris
 constexpr int FLAT_FRAME_F4 = 4;                            // per triangle
+// ... and, behind room for FLAT_MAX_TRIS frames, the class table: one float4 holding two 64-bit words of one 4-bit class per
+// triangle (triangle k in bits 4k..4k+3; ptk_flat_mt.h flat_zero_class: which edge words of the record are stored zeros).  The
+// first word is what the exact PLAIN pass reads - all zero, "general", while the flat_zero_classes option is off - the second
+// the classification itself (ptk_flat_classes).  The allocation always reaches this far.
+constexpr int FLAT_CLASSES_AT = FLAT_FRAMES_AT + FLAT_MAX_TRIS * FLAT_FRAME_F4;
+constexpr int FLAT_TABLE_F4 = FLAT_CLASSES_AT + 1;           // the whole allocation
 
 // Shading record, 112 B, indexed by the scene's triangle index (fetched only for the accepted hit):
 //   s0 = (normal.xyz, bits (material | smoothing << 31))
@@ -163,6 +169,8 @@ void launch_pack_owned(const float* accum, float* packed, int width, int height,
 void launch_unpack_all(const float* packed, const long long* bases, float* image, int width, int height, int world, hipStream_t stream);
 // the frame table behind d_flat_tris for triangles [first, first + count), from their shading records' normals (sample_basis, the exact build's)
 void launch_flat_frames(const float4* d_shade, float4* d_flat_tris, int first, int count, hipStream_t stream);
+// the class table behind d_flat_tris, from all num_tris records as they stand on the stream; use = 0: the pass's word is all general
+void launch_flat_classes(float4* d_flat_tris, int num_tris, int use, hipStream_t stream);
 void launch_primary(const PrimaryParams& p, hipStream_t stream);
 void launch_primary_hits(const RenderParams& p, float4* out, float4* out_rd, hipStream_t stream);
 void launch_probe(const ProbeParams& p, hipStream_t stream);

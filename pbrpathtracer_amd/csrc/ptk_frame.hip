@@ -4,6 +4,7 @@
 // hand-off), the packed form of the multi-GPU exchange - and the parity probes.  Built from ptk_device_fn.h's device functions.
 #include "ptk_device_fn.h"
 #include "ptk_adaptive.h"
+#include "ptk_flat_mt.h"
 
 namespace ptk {
 
@@ -29,6 +30,33 @@ __global__ __launch_bounds__(64) void fill_flat_frames_kernel(const float4* __re
 void launch_flat_frames(const float4* d_shade, float4* d_flat_tris, int first, int count, hipStream_t stream)
 {
     if (count > 0) hipLaunchKernelGGL(fill_flat_frames_kernel, dim3((count * 2 + 63) / 64), dim3(64), 0, stream, d_shade, d_flat_tris, first, count);
+}
+
+// The class table behind the frame table (ptk_device.h FLAT_CLASSES_AT): lane k classifies record k by its six stored edge words
+// (ptk_flat_mt.h flat_zero_class, the rule ptk_flat_zero_class exports), lane 0 gathers the nibbles and writes both words.
+// One wave; classifies all records anew, whichever of them changed.
+__global__ __launch_bounds__(64) void classify_flat_kernel(float4* __restrict__ flat_tris, int num_tris, int use)
+{
+    const int k = threadIdx.x;
+    int cls = 0;
+    if (k < num_tris && k < FLAT_MAX_TRIS)
+    {
+        const float4 t0 = flat_tris[k * TRI_F4], t1 = flat_tris[k * TRI_F4 + 1], t2 = flat_tris[k * TRI_F4 + 2];
+        const float e[6] = { t0.w, t1.x, t1.y, t1.z, t1.w, t2.x };
+        cls = ptk_mt::flat_zero_class(e);
+    }
+    unsigned long long word = 0ull;
+    for (int j = 0; j < FLAT_MAX_TRIS; j++) word |= (unsigned long long)(__shfl(cls, j) & 15) << (j * 4);
+    if (k == 0)
+    {
+        unsigned long long* out = (unsigned long long*)(flat_tris + FLAT_CLASSES_AT);
+        out[0] = use ? word : 0ull;
+        out[1] = word;
+    }
+}
+void launch_flat_classes(float4* d_flat_tris, int num_tris, int use, hipStream_t stream)
+{
+    hipLaunchKernelGGL(classify_flat_kernel, dim3(1), dim3(64), 0, stream, d_flat_tris, num_tris, use);
 }
 
 // Streaming fold of the sample buffer into the float accumulator, strictly in sample order

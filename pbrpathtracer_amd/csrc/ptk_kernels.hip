@@ -54,6 +54,7 @@
 // Each build has its own probe_math_kernel (ptk_probe_math follows the option).  (The header defaults PTK_CONTRACT to 0.)
 
 #include "ptk_device_fn.h"
+#include "ptk_flat_mt.h"
 
 namespace ptk {
 #if PTK_CONTRACT >= 2
@@ -84,31 +85,27 @@ namespace fma {
 // (ox, oy, oz are not read - both rays leave W.ro, see tri_test_pair - but dropping them reorders a few moves of the kernels)
 struct RayPair { f2 ox, oy, oz, dx, dy, dz; };
 
+// The arithmetic of the test for both rays: ptk_flat_mt.h's mt_pair (shared with the host-side check of the masks) on the packed pair.
+// ZM (exact PLAIN pass only): the record's edge words that are known to be stored zeros, whose operations are deleted; ZM = 0 is
+// the full text.  u, v of a hit may then differ from the full test's in the sign of a zero, and nothing of a PLAIN scene reads them.
+template <unsigned ZM>
+__device__ __forceinline__ void tri_math_pair(const Walk& W, const RayPair& R, float4 t0, float4 t1, float4 t2, f2& a, f2& u, f2& v, f2& t)
+{
+    ptk_mt::mt_pair<ZM>(R.dx, R.dy, R.dz, W.ro.x, W.ro.y, W.ro.z, t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x,
+                        [](const f2& x) { return f2{ rcp_ieee(x.x), rcp_ieee(x.y) }; }, a, u, v, t);
+}
+
+// ... and what follows it: the reference's tests, the closest-hit rule, stochastic opacity, the hit records.
 // PLAIN (trace_kernel): no triangle of the scene has an opacity texture, so the opacity branch is dead code.
 template <bool STATS, bool PLAIN, class PT>
-__device__ __forceinline__ bool tri_test_pair(const PT& P, Walk& W, Walk& WS, const RayPair& R, const bool shadow_live, float4 t0, float4 t1,
-                                              float4 t2, const Rng& rng, uint32_t ray_bounce, uint32_t ray_shadow, Counters& cnt)
+__device__ __forceinline__ bool tri_accept_pair(const PT& P, Walk& W, Walk& WS, const bool shadow_live, const f2 a, const f2 u, const f2 v, const f2 t,
+                                                float4 t2, const Rng& rng, uint32_t ray_bounce, uint32_t ray_shadow, Counters& cnt)
 {
-    if (STATS) cnt.tris += shadow_live ? 2u : 1u;
-    const float v0x = t0.x, v0y = t0.y, v0z = t0.z, e1x = t0.w, e1y = t1.x, e1z = t1.y, e2x = t1.z, e2y = t1.w, e2z = t2.x;
-    // h = cross(rd, edge2)
-    const f2 hx = R.dy * e2z - R.dz * e2y, hy = R.dz * e2x - R.dx * e2z, hz = R.dx * e2y - R.dy * e2x;
-    const f2 a = hx * e1x + hy * e1y + hz * e1z;                 // dot(edge1, h)
-    const f2 f = { rcp_ieee(a.x), rcp_ieee(a.y) };
-    // The two rays of a lane leave the SAME point (shade_interaction starts both at p), so everything of Moeller-Trumbore that
-    // depends on the origin alone - s = ro - v0, q = cross(s, edge1), dot(edge2, q) - is the same number for both: computed once
-    // in scalar f32 (full rate) instead of twice in packed f32 (half rate), 17 of the ~60 operations per ray and triangle.  The
-    // same IEEE operations on the same inputs: bit-identical.  (No shadow ray: its half of the packed values is ignored anyway.)
-    const float sx = W.ro.x - v0x, sy = W.ro.y - v0y, sz = W.ro.z - v0z;      // s = ro - v0
-    const f2 u = f * (sx * hx + sy * hy + sz * hz);
-    const float qx = sy * e1z - sz * e1y, qy = sz * e1x - sx * e1z, qz = sx * e1y - sy * e1x;      // q = cross(s, edge1)
-    const f2 v = f * (R.dx * qx + R.dy * qy + R.dz * qz);
-    const f2 t = f * (qx * e2x + qy * e2y + qz * e2z);
     const f2 uv = u + v;
     const int tri = __float_as_int(t2.y);
     const int otex = __float_as_int(t2.z);
-    bool okb = !(fabsf(a.x) < PTK_EPS) & !(u.x < 0.0f) & !(v.x < 0.0f) & !(uv.x > 1.0f) & (t.x > PTK_EPS);     // (u > 1: implied, see tri_test)
-    bool oks = !(fabsf(a.y) < PTK_EPS) & !(u.y < 0.0f) & !(v.y < 0.0f) & !(uv.y > 1.0f) & (t.y > PTK_EPS);
+    bool okb = ptk_mt::mt_accept(a.x, u.x, v.x, uv.x, t.x, PTK_EPS);
+    bool oks = ptk_mt::mt_accept(a.y, u.y, v.y, uv.y, t.y, PTK_EPS);
     // the flat list is in ascending triangle index, so the tie rule's "equal t and smaller index" can never hold for a
     // later record: nearer-than-best is the whole rule
     okb = okb & (t.x < W.best.t);
@@ -138,6 +135,16 @@ __device__ __forceinline__ bool tri_test_pair(const PT& P, Walk& W, Walk& WS, co
     if (okb) { W.best.tri = tri; W.best.t = t.x; W.best.u = u.x; W.best.v = v.x; asm volatile("" : "+v"(W.best.t), "+v"(W.best.u), "+v"(W.best.v)); }
     if (oks) { WS.best.tri = tri; WS.best.t = t.y; WS.best.u = u.y; WS.best.v = v.y; asm volatile("" : "+v"(WS.best.t), "+v"(WS.best.u), "+v"(WS.best.v)); }
     return oks & (tri != WS.occl_tri);
+}
+
+template <bool STATS, bool PLAIN, class PT>
+__device__ __forceinline__ bool tri_test_pair(const PT& P, Walk& W, Walk& WS, const RayPair& R, const bool shadow_live, float4 t0, float4 t1,
+                                              float4 t2, const Rng& rng, uint32_t ray_bounce, uint32_t ray_shadow, Counters& cnt)
+{
+    if (STATS) cnt.tris += shadow_live ? 2u : 1u;
+    f2 a, u, v, t;
+    tri_math_pair<0u>(W, R, t0, t1, t2, a, u, v, t);
+    return tri_accept_pair<STATS, PLAIN>(P, W, WS, shadow_live, a, u, v, t, t2, rng, ray_bounce, ray_shadow, cnt);
 }
 
 // ---- work distribution shared by the persistent trace kernels -------------------------------------------------------
@@ -455,12 +462,34 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
                     RayPair R;
                     R.ox = f2{ W.ro.x, WS.ro.x }; R.oy = f2{ W.ro.y, WS.ro.y }; R.oz = f2{ W.ro.z, WS.ro.z };
                     R.dx = f2{ W.rd.x, WS.rd.x }; R.dy = f2{ W.rd.y, WS.rd.y }; R.dz = f2{ W.rd.z, WS.rd.z };
+                    // exact PLAIN pass: one 4-bit class per record (classify_flat_kernel, ptk_frame.hip) names the edge words stored
+                    // as zeros, and the record goes to the body with those operations deleted (ptk_flat_mt.h; DESIGN 4.1: same hits,
+                    // same bits of t).  The class word is one scalar load per pass, the switch is wave-uniform, the order ascending.
+                    constexpr bool ZERO_CLASSES = PLAIN && !STATS && !PTK_CONTRACT;
+                    typedef const __attribute__((address_space(4))) unsigned long long* cu64;
+                    const unsigned long long classes = ZERO_CLASSES ? *(cu64)(uintptr_t)(P.flat_tris + FLAT_CLASSES_AT) : 0ull;
                     for (int k = 0; k < P.flat_count; k++)
                     {
                         const f4v a0 = ct[k * TRI_F4], a1 = ct[k * TRI_F4 + 1], a2 = ct[k * TRI_F4 + 2];
                         const float4 t0 = make_float4(a0.x, a0.y, a0.z, a0.w), t1 = make_float4(a1.x, a1.y, a1.z, a1.w),
                                      t2 = make_float4(a2.x, a2.y, a2.z, a2.w);
-                        (void)tri_test_pair<STATS, PLAIN>(P, W, WS, R, shadow, t0, t1, t2, rng, bounce_ray, ray, cnt);
+#define PTK_ZERO_CLASS(c) case c: tri_math_pair<ZERO_CLASSES ? ptk_mt::flat_zero_mask(c) : 0u>(W, R, t0, t1, t2, ma, mu, mv, mt); break;
+                        if (ZERO_CLASSES)
+                        {
+                            // (only the arithmetic is switched: the accept chain and the hit records follow once, for all classes)
+                            f2 ma, mu, mv, mt;
+                            switch ((unsigned)(classes >> (k * 4)) & 15u)
+                            {
+                                PTK_ZERO_CLASS(1) PTK_ZERO_CLASS(2) PTK_ZERO_CLASS(3) PTK_ZERO_CLASS(4) PTK_ZERO_CLASS(5)
+                                PTK_ZERO_CLASS(6) PTK_ZERO_CLASS(7) PTK_ZERO_CLASS(8) PTK_ZERO_CLASS(9) PTK_ZERO_CLASS(10)
+                                PTK_ZERO_CLASS(11) PTK_ZERO_CLASS(12) PTK_ZERO_CLASS(13) PTK_ZERO_CLASS(14) PTK_ZERO_CLASS(15)
+                                default: tri_math_pair<0u>(W, R, t0, t1, t2, ma, mu, mv, mt); break;
+                            }
+                            (void)tri_accept_pair<STATS, PLAIN>(P, W, WS, shadow, ma, mu, mv, mt, t2, rng, bounce_ray, ray, cnt);
+                        }
+                        else
+                            (void)tri_test_pair<STATS, PLAIN>(P, W, WS, R, shadow, t0, t1, t2, rng, bounce_ray, ray, cnt);
+#undef PTK_ZERO_CLASS
                     }
                     if (shadow)
                     {

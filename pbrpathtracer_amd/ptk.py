@@ -133,6 +133,7 @@ SYMBOLS = [
     "ptk_bind_out_image", "ptk_bind_out_device", "ptk_bind_gl_buffer", "ptk_comm_info", "ptk_kernel_log", "ptk_kernel_log_read",
     "ptk_debug_stall_exchange", "ptk_render_adaptive", "ptk_read_sample_counts", "ptk_read_moments",
     "ptk_trace_variant", "ptk_scene_is_plain", "ptk_scene_is_lambert", "ptk_trace_is_lambert",
+    "ptk_flat_zero_class", "ptk_flat_zero_mask", "ptk_flat_classes",
     "ptk_feature_info", "ptk_render_features", "ptk_read_feature", "ptk_feature_device_ptr", "ptk_pick",
     "ptk_update_geometry", "ptk_update_geometry_device", "ptk_geometry_info", "ptk_geometry_timing",
     "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
@@ -296,6 +297,9 @@ def _load_locked() -> C.CDLL:
         L.ptk_last_variance_ms.argtypes = [vp, fp, fp]
         L.ptk_scene_is_lambert.argtypes = [C.POINTER(SceneDesc)]
         L.ptk_trace_is_lambert.argtypes = [vp, C.POINTER(C.c_int)]
+        L.ptk_flat_zero_class.argtypes = [C.POINTER(C.c_float)]
+        L.ptk_flat_zero_mask.argtypes = [C.c_int]
+        L.ptk_flat_classes.argtypes = [vp, C.POINTER(i32)]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -413,6 +417,18 @@ def scene_is_lambert(arrays: dict) -> bool:
     a = normalise_arrays(arrays)
     d = scene_desc(a)
     return bool(load().ptk_scene_is_lambert(C.byref(d)))
+
+
+def flat_zero_class(v1, v2, v3) -> int:
+    """ptk_flat_zero_class of the record the packers store for a triangle: edges v2 - v1, v3 - v1 in float32 (no device needed)."""
+    v1, v2, v3 = (np.asarray(v, np.float32) for v in (v1, v2, v3))
+    e = np.concatenate([v2 - v1, v3 - v1]).astype(np.float32)
+    return int(load().ptk_flat_zero_class((C.c_float * 6)(*e.tolist())))
+
+
+def flat_zero_mask(zero_class: int) -> int:
+    """The 6-bit mask over (e1.x e1.y e1.z e2.x e2.y e2.z) a class stands for; -1 outside 0..15."""
+    return int(load().ptk_flat_zero_mask(int(zero_class)))
 
 
 def normalise_arrays(a: dict) -> dict:
@@ -1430,6 +1446,12 @@ class Context:
         v = C.c_int(0)
         self._chk(self.L.ptk_trace_is_lambert(self.h, C.byref(v)), "ptk_trace_is_lambert")
         return bool(v.value)
+
+    def flat_classes(self) -> list:
+        """The device's zero class of every triangle of the flat list (scenes of <= 16 triangles), in triangle order."""
+        out = (C.c_int32 * 16)()
+        self._chk(self.L.ptk_flat_classes(self.h, out), "ptk_flat_classes")
+        return [int(v) for v in out if v >= 0]
 
     def set_option(self, name: str, value: float):
         self._chk(self.L.ptk_set_option(self.h, name.encode(), float(value)), "ptk_set_option")

@@ -16,7 +16,9 @@ when a measured SQ_INSTS_VALU is passed, as what is left of the measurement once
 
 The block labels belong to ONE build of the kernel: each group below names its labels and the VALU count they must add up to,
 and the script stops when the assembly no longer matches (re-derive the groups from tools/isa_blocks.py's table then).  The label
-prefix (.LBB<n>_, n = the kernel's position in its file) is read from the assembly.  "lambert" is the LAMBERT level of the PLAIN
+prefix (.LBB<n>_, n = the kernel's position in its file) is read from the assembly.  STALE for "plain" and "lambert" since the exact PLAIN
+pass switches per triangle to a zero-class body: their groups name the single pass block of the kernels before that, so
+the script stops on today's assembly; the per-class figures of DESIGN 5 come from tools/isa_blocks.py directly.  "lambert" is the LAMBERT level of the PLAIN
 kernel; its stats come from the same STATS kernel (the counters-enabled kernels have neither variant)."""
 import json
 import re
