@@ -28,6 +28,8 @@ struct ptk_rays_adaptive_result;
 struct ptk_denoise_params;
 struct ptk_temporal_params;
 struct ptk_variance_params;
+struct ptk_display_params;
+struct ptk_exposure_state;
 struct ptk_view;
 
 const float EPS = 0.00001f;      // mesh.h:12
@@ -246,6 +248,16 @@ public:
     bool TemporalVariance(const ptk_variance_params& params);
     bool ReadTemporalVariance(float* moments, float* variance);
     bool DenoiseTemporal(const ptk_denoise_params& params, bool variance = true);
+    // Extensions: the display transform (include/ptk.h ptk_display_frame) - exposure, given or metered from a luminance histogram
+    // and adapted from call to call on the device, a tone curve and the sRGB transfer function - over the frame as last rendered
+    // (source PTK_DISPLAY_ACCUM), the DenoiseFrame() / DenoiseTemporal() result (PTK_DISPLAY_DENOISED) or the TemporalFrame*()
+    // result (PTK_DISPLAY_TEMPORAL); false when the source does not exist at the current resolution.  ReadDisplay: W*H*3 bytes,
+    // the layout of the out image.  DisplayState: the exposure state behind the last call.  ResetDisplay forgets it.  Pending
+    // edits are NOT applied; the image, the sample count and the hand-off buffer (SetOutImage) are not touched.
+    bool DisplayFrame(int source, const ptk_display_params& params);
+    bool ReadDisplay(GLubyte* out);
+    bool DisplayState(ptk_exposure_state* out);
+    bool ResetDisplay();
     // The (object, element) under pixel (x, y), y counted from the top row: one ray (ptk_pick), pending edits applied first.
     // A pixel that sees nothing gives -1 / -1 (and triangle -1) and true; false: no scene / resolution yet, or (x, y) outside the frame.
     bool Pick(int x, int y, int* objId, int* elementId, int* triangle = nullptr);

@@ -830,6 +830,110 @@ int ptk_denoise_temporal(ptk_ctx* ctx, const ptk_denoise_params* params, uint32_
  * variance_kernel and its prefilter (0 without one); waits for the call */
 int ptk_last_variance_ms(ptk_ctx* ctx, float* variance_ms, float* prefilter_ms);
 
+/* ---- display transform: histogram exposure, tone map, transfer function, 8 bit (no counterpart in the reference) ----------------
+ * The last link of the frame pipeline (render -> temporal -> variance -> a-trous -> DISPLAY -> 8 bit).  ptk_resolve_rgb8 clamps to
+ * [0, 1] and truncates x * 255, which is the reference's resolve and stays as it is; this section adds an exposure - given, or
+ * metered from a luminance histogram and adapted over the frames on the device -, a tone curve and the sRGB transfer function.
+ * THE RULE.  Every operation below is one IEEE float32 operation, in the order written (the kernels are compiled with
+ * -ffp-contract=off); x > y ? x : y with a NaN operand yields the second value; bits(f) is the uint32 pattern of a float.  The rule
+ * uses + - * /, comparisons and integer operations on float bit patterns only - no log, exp or pow -, and the histogram is summed in
+ * integers, whose sum does not depend on the order: every byte and every bit of the state equals a numpy restatement
+ * (tests/display_rule.py; tests/test_gpu_display.py: array_equal).
+ * PARAMETERS: ptk_display_params below.  The image is color [H][W][3] float32, rows as stored - the rule never flips.
+ * METERING (mode PTK_EXPOSURE_METERED), per pixel:
+ *   L = ((0.2126f*r) + (0.7152f*g)) + (0.0722f*b)
+ *   the pixel is COUNTED iff L >= min_lum && L <= max_lum   (NaN, black, negative and infinite pixels drop out)
+ *   its bin is bits(L) >> 20: eight exponent bits and three mantissa bits, 2048 bins of uint32
+ * EXPOSURE, from the histogram, in unsigned 64-bit integers:
+ *   N = sum of the counts;  lo = N*low_permille / 1000;  hi = N*high_permille / 1000;  hi <= lo: hi = lo + 1
+ *   the pixels of rank [lo, hi) in bin order are KEPT, K = hi - lo;  S = the sum over the kept pixels of their bin
+ *   mbits = ((S << 20) + (K << 19)) / K;  Lavg = float_from_bits((uint32)mbits)
+ *     (the mean of the truncated bit patterns, re-centred by half a bin: a piecewise-linear stand-in for the log-average)
+ *   target = key / Lavg;  target = target > min_exposure ? target : min_exposure;  target = target < max_exposure ? target : max_exposure
+ *   N == 0: target = the previous exposure where there is one, else 1.0f;  Lavg = 0, K = 0
+ *   e = (no previous exposure || adapt >= 1) ? target : e_prev + ((target - e_prev) * adapt)
+ * THE STATE, ptk_exposure_state below, lives in device memory (32 B, written with ordinary stores by the one thread that
+ * finishes the exposure step) and is read by the next metered call's exposure step: an orbit adapts without the host ever seeing
+ * it.  It is the context's: the planes entries and the frame entry share it.  exposure = e, target, lavg = Lavg, counted = N,
+ * kept = K; has_prev = there was a previous exposure or N > 0 - a black frame in front of the first lit one is no anchor.  A
+ * manual call neither reads nor writes it.  ptk_display_reset forgets it (all zero), on the stream.
+ * APPLY, per channel c of every pixel, e = the state's exposure behind this call's exposure step, or params->exposure (manual):
+ *   x = c * e;  x = x > 0 ? x : 0
+ *   LINEAR:    y = x
+ *   REINHARD:  iw2 = 1.0f / (white*white) (computed on the host);  y = (x * (1.0f + (x*iw2))) / (1.0f + x)
+ *   ACES:      y = (x * ((2.51f*x) + 0.03f)) / ((x * ((2.43f*x) + 0.59f)) + 0.14f)      (Narkowicz' fit)
+ *   y = y < 1 ? y : 1      (an overflowed inf/inf becomes white)
+ * ENCODE: transfer LINEAR is (uint8)(y * 255), the resolve of ptk_resolve_rgb8.  Transfer SRGB is byte = #{ k in 1..255 : T[k] <= y }
+ * with T[k] the float32 nearest to the sRGB decoding of k/255 - k/255/12.92 below 0.04045, else ((k/255 + 0.055)/1.055)^2.4 -, a
+ * table of 256 literals (T[0] = 0, T[255] = 1, strictly increasing) generated once in double precision, which
+ * ptk_display_srgb_table returns.  THE TABLE IS THE DEFINITION: a truncating encoding, floor(255 * oetf(y)), as the resolve is.
+ * CONSEQUENCE: manual exposure 1, LINEAR, LINEAR over S1 / n gives the bytes of ptk_resolve_rgb8.
+ * Deliberately left out: dithering, luminance-preserving variants of the curves, bloom, writing into a buffer bound with
+ * ptk_bind_out_* (the display image is a buffer of its own; the accumulate kernel and the hand-off are untouched).
+ *   ptk_display_planes: host arrays, synchronous; the plane and the outputs are staged in device memory for the length of the call.
+ *     state_out, or NULL, receives the state behind the call.
+ *   ptk_display_planes_device: every array in memory of this context's GPU, asynchronous on the context's stream (the caller's
+ *     after ptk_set_stream), no host wait, no allocation after the context's first display call (8 KB + 32 B).  d_color may start
+ *     at any multiple of 4 bytes, d_rgb8_out anywhere (16- and 4-byte alignment take the wide loads and stores).
+ *   Both need no scene, no camera and no frame; "contract", "flat", ptk_set_tile and ptk_request_exit do not reach them.
+ *   ptk_display_frame: the context's frame into the context's display image ([H][W][3] bytes, rows bottom-up, allocated by the first
+ *     call at a resolution, freed with the feature planes), asynchronous.  source PTK_DISPLAY_ACCUM: color_c = S1_c / (float)n_p, 0
+ *     where n_p = 0, n_p exactly as ptk_denoise_frame defines it (adaptive counts, the bound accumulator and the tile split apply:
+ *     a pixel this rank does not own is black, is not counted and encodes to 0), read inside the meter and apply kernels with no
+ *     plane in between; PTK_DISPLAY_DENOISED: the plane of ptk_read_denoised; PTK_DISPLAY_TEMPORAL: the colour of
+ *     ptk_read_temporal.  PTK_ERR_BAD_ARG when no frame is set or the source does not exist at the current resolution.  The
+ *     accumulator, the sample count, the context's 8-bit image, a bound buffer and every other plane are not touched.
+ *   ptk_read_display (waits for the stream; W*H*3 bytes bottom-up, the layout of ptk_resolve_rgb8), ptk_display_device_ptr:
+ *     PTK_ERR_BAD_ARG before a successful ptk_display_frame at the current resolution.
+ *   ptk_display_state: waits for the stream; all zero before the context's first display call.
+ *   ptk_display_srgb_table, ptk_display_check_params (the parameter checks of the entries alone): host only, no device needed.
+ * PTK_ERR_BAD_ARG: a null context, params or required array with a non-zero size; width or height < 0; an unknown mode, op, transfer
+ * or source; a manual exposure (mode MANUAL only), key, white, min_exposure or max_exposure that is NaN or <= 0 (white = +inf is
+ * legal: plain Reinhard); min_exposure, max_exposure, min_lum or max_lum not finite; min_lum < 2^-126 or > max_lum; permilles outside
+ * 0 <= low < high <= 1000; adapt NaN or negative.  A refused call leaves the outputs and the state alone.  A zero-sized image is
+ * PTK_OK and does nothing.  PTK_ERR_LIMIT: more than 2^28 pixels. */
+#define PTK_EXPOSURE_MANUAL 0
+#define PTK_EXPOSURE_METERED 1
+#define PTK_DISPLAY_LINEAR 0
+#define PTK_DISPLAY_REINHARD 1
+#define PTK_DISPLAY_ACES 2
+#define PTK_TRANSFER_LINEAR 0
+#define PTK_TRANSFER_SRGB 1
+#define PTK_DISPLAY_ACCUM 0
+#define PTK_DISPLAY_DENOISED 1
+#define PTK_DISPLAY_TEMPORAL 2
+typedef struct ptk_display_params {
+    int32_t mode;              /* PTK_EXPOSURE_* */
+    float exposure;            /* MANUAL: the exposure, > 0 */
+    float key;                 /* > 0: the value the metered average is brought to (0.18: middle grey) */
+    float min_lum, max_lum;    /* finite, 2^-126 <= min_lum <= max_lum: the luminances the meter counts */
+    int32_t low_permille, high_permille;      /* 0 <= low < high <= 1000: the ranks of the histogram that are kept */
+    float min_exposure, max_exposure;         /* finite, > 0: the metered target is clamped to them */
+    float adapt;               /* >= 0: the step toward the target per call; >= 1 lands on it */
+    int32_t op;                /* PTK_DISPLAY_LINEAR / _REINHARD / _ACES */
+    float white;               /* REINHARD: > 0, the input that maps to 1; +inf: plain x / (1 + x) */
+    int32_t transfer;          /* PTK_TRANSFER_* */
+} ptk_display_params;
+typedef struct ptk_exposure_state {
+    float exposure, target, lavg;
+    uint32_t has_prev;
+    uint64_t counted, kept;
+} ptk_exposure_state;
+int ptk_display_planes(ptk_ctx* ctx, int width, int height, const float* color /*[H][W][3]*/, const ptk_display_params* params,
+                       uint8_t* rgb8_out /*[H][W][3]*/, ptk_exposure_state* state_out /*or NULL*/);
+int ptk_display_planes_device(ptk_ctx* ctx, int width, int height, const float* d_color, const ptk_display_params* params,
+                              uint8_t* d_rgb8_out, ptk_exposure_state* d_state_out /*or NULL*/);
+int ptk_display_frame(ptk_ctx* ctx, int source, const ptk_display_params* params);
+int ptk_read_display(ptk_ctx* ctx, uint8_t* host_out /*[H][W][3], rows bottom-up*/);
+int ptk_display_device_ptr(ptk_ctx* ctx, void** dev_ptr, size_t* bytes);
+int ptk_display_state(ptk_ctx* ctx, ptk_exposure_state* out);
+int ptk_display_reset(ptk_ctx* ctx);
+int ptk_display_srgb_table(float* out /*[256]*/);
+int ptk_display_check_params(const ptk_display_params* params);
+/* measurement hook (tools/display_timing.py), not part of the feature.  HIP-event times of the last display call's meter kernel,
+ * exposure step and apply kernel (the first two 0 for a manual call); waits for the call */
+int ptk_last_display_ms(ptk_ctx* ctx, float* meter_ms, float* exposure_ms, float* apply_ms);
+
 /* ---- lightmap baking: the radiance leaving the scene's surfaces, per texel of a uv chart layout (no counterpart in the reference) --
  * The surface half of light baking in front of and behind ptk_trace_rays' kernel: a uv rasteriser, a ray generator, a scatter and
  * a chart-padding pass, all on the GPU from what ptk_upload_scene left resident.  Inputs: the uploaded scene, a lightmap of

@@ -94,6 +94,12 @@ int  pth_temporal_frame_moments(pth_tracer* t, const ptk_temporal_params* params
 int  pth_temporal_variance(pth_tracer* t, const ptk_variance_params* params);
 int  pth_read_temporal_variance(pth_tracer* t, float* moments, float* variance);
 int  pth_denoise_temporal(pth_tracer* t, const ptk_denoise_params* params, int variance);
+/* DisplayFrame / ReadDisplay / DisplayState / ResetDisplay (the display transform over the frame, include/ptk.h ptk_display_frame;
+ * source: PTK_DISPLAY_ACCUM, _DENOISED or _TEMPORAL): 1 on success */
+int  pth_display_frame(pth_tracer* t, int source, const ptk_display_params* params);
+int  pth_read_display(pth_tracer* t, unsigned char* out);
+int  pth_display_state(pth_tracer* t, ptk_exposure_state* out);
+int  pth_display_reset(pth_tracer* t);
 /* ClosestPoints (the nearest surface point to caller-supplied points, include/ptk.h ptk_closest_points): 1 on success */
 int  pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point,
                         float* bary);

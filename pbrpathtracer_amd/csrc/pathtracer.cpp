@@ -993,6 +993,41 @@ bool PathTracer::DenoiseTemporal(const ptk_denoise_params& params, bool variance
     return rc == PTK_OK;
 }
 
+// The display transform over the frame as it was last rendered, denoised or reprojected (ptk_display_frame).  No pending edit is
+// applied; nothing is rendered.  The exposure state lives on the device and carries from call to call.
+bool PathTracer::DisplayFrame(int source, const ptk_display_params& params)
+{
+    if (!m->have_resolution || !m->ctx) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const int rc = ptk_display_frame(m->ctx, source, &params);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ReadDisplay(GLubyte* out)
+{
+    if (!m->ctx || !out) return false;
+    const int rc = ptk_read_display(m->ctx, out);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::DisplayState(ptk_exposure_state* out)
+{
+    if (!m->ctx || !out) return false;
+    const int rc = ptk_display_state(m->ctx, out);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ResetDisplay()
+{
+    if (!m->ctx) return false;
+    const int rc = ptk_display_reset(m->ctx);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 void PathTracer::TrackMotion(bool on)
 {
     std::lock_guard<std::mutex> render_guard(m->render_mu);

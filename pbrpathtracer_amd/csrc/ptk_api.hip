@@ -165,6 +165,7 @@ void free_features(ptk_ctx* c)
     dfree(c->d_temporal); c->temporal_w = c->temporal_h = 0;      // ... and so does the temporal history
     dfree(c->d_motion); c->motion_w = c->motion_h = 0;            // ... and the motion planes
     dfree(c->d_temporal_mm); c->temporal_moments = c->temporal_variance = false;      // ... and the moments and the variance
+    dfree(c->d_display); c->disp_w = c->disp_h = 0;               // ... and the display image (the exposure state stays)
 }
 
 // Brings the primary-visibility cache up to date where it is valid and hands it to p; else p keeps walking from the camera.
@@ -621,6 +622,8 @@ void ptk_destroy(ptk_ctx* c)
     for (hipEvent_t e : c->ev_motion) if (e) (void)hipEventDestroy(e);
     dfree(c->d_variance_pack); dfree(c->d_temporal_pack_mm);
     for (hipEvent_t e : c->ev_variance) if (e) (void)hipEventDestroy(e);
+    dfree(c->d_display_hist);
+    for (hipEvent_t e : c->ev_display) if (e) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
     if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);

@@ -245,6 +245,17 @@ struct ptk_ctx {
     hipEvent_t ev_variance[3] = { nullptr, nullptr, nullptr };
     bool variance_timed = false, variance_prefiltered = false;
 
+    // display transform (ptk_display_planes, ptk_display_frame).  The luminance histogram, 2048 uint32 (8 KB), with the 32 B exposure
+    // state behind it: made and zeroed by the first call, the histogram cleared by each call's exposure step behind itself.  The
+    // frame entry's 8-bit image [H][W][3], made by the first ptk_display_frame at a resolution, freed with the feature planes, and
+    // the resolution it was last written at.  Four events of the last call: before the meter, behind it, behind the exposure step,
+    // behind the apply kernel
+    uint32_t* d_display_hist = nullptr;
+    uint8_t* d_display = nullptr;
+    int disp_w = 0, disp_h = 0;
+    hipEvent_t ev_display[4] = { nullptr, nullptr, nullptr, nullptr };
+    bool display_timed = false;
+
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
     // overlaps the tail of pass k's (a launch ends with the few waves that hold its longest paths - Russian roulette

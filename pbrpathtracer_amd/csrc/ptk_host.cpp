@@ -161,6 +161,13 @@ int pth_denoise_temporal(pth_tracer* t, const ptk_denoise_params* params, int va
 {
     return params && t->pt.DenoiseTemporal(*params, variance != 0) ? 1 : 0;
 }
+int pth_display_frame(pth_tracer* t, int source, const ptk_display_params* params)
+{
+    return params && t->pt.DisplayFrame(source, *params) ? 1 : 0;
+}
+int pth_read_display(pth_tracer* t, unsigned char* out) { return t->pt.ReadDisplay(out) ? 1 : 0; }
+int pth_display_state(pth_tracer* t, ptk_exposure_state* out) { return t->pt.DisplayState(out) ? 1 : 0; }
+int pth_display_reset(pth_tracer* t) { return t->pt.ResetDisplay() ? 1 : 0; }
 int pth_read_motion(pth_tracer* t, float* prev_position, float* prev_normal, float* motion)
 {
     return t->pt.ReadMotion(prev_position, prev_normal, motion) ? 1 : 0;

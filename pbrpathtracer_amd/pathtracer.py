@@ -42,6 +42,7 @@ HOST_SYMBOLS = [
     "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised", "pth_temporal_frame", "pth_read_temporal", "pth_get_view",
     "pth_track_motion", "pth_temporal_frame_moving", "pth_read_motion", "pth_temporal_frame_moments", "pth_temporal_variance",
     "pth_read_temporal_variance", "pth_denoise_temporal", "pth_get_object_transform",
+    "pth_display_frame", "pth_read_display", "pth_display_state", "pth_display_reset",
 ]
 
 _bound = False
@@ -129,6 +130,10 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_temporal_variance.restype = i32; L.pth_temporal_variance.argtypes = [vp, C.POINTER(_ptk.VarianceParams)]
         L.pth_read_temporal_variance.restype = i32; L.pth_read_temporal_variance.argtypes = [vp, vp, vp]
         L.pth_denoise_temporal.restype = i32; L.pth_denoise_temporal.argtypes = [vp, C.POINTER(_ptk.DenoiseParams), i32]
+        L.pth_display_frame.restype = i32; L.pth_display_frame.argtypes = [vp, i32, C.POINTER(_ptk.DisplayParams)]
+        L.pth_read_display.restype = i32; L.pth_read_display.argtypes = [vp, vp]
+        L.pth_display_state.restype = i32; L.pth_display_state.argtypes = [vp, C.POINTER(_ptk.DisplayState)]
+        L.pth_display_reset.restype = i32; L.pth_display_reset.argtypes = [vp]
         L.pth_read_motion.restype = i32; L.pth_read_motion.argtypes = [vp, vp, vp, vp]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
@@ -448,6 +453,37 @@ class PathTracer:
         if not self.L.pth_denoise_temporal(self.h, C.byref(prm), 1 if variance else 0):
             raise _ptk.PtkError("DenoiseTemporal failed: " + self.LastError())
 
+    def DisplayFrame(self, source: int = _ptk.DISPLAY_ACCUM, params=None):
+        """Extension: the display transform (include/ptk.h ptk_display_frame) - exposure, given or metered and adapted on the
+        device from call to call, a tone curve and the sRGB transfer - over the frame as last rendered (ptk.DISPLAY_ACCUM), the
+        DenoiseFrame() / DenoiseTemporal() result (ptk.DISPLAY_DENOISED) or the TemporalFrame*() result (ptk.DISPLAY_TEMPORAL).
+        params: ptk.DisplayParams or a dict of its fields; None takes ptk.display_defaults.  ReadDisplay() gives the bytes."""
+        prm = _ptk._display_params(params)
+        if not self.L.pth_display_frame(self.h, int(source), C.byref(prm)):
+            raise _ptk.PtkError("DisplayFrame failed: " + self.LastError())
+
+    def ReadDisplay(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """[H][W][3] uint8, the last DisplayFrame()'s result, in the out image's layout."""
+        if out is None:
+            w, h = self.GetResolution()
+            out = np.empty((h, w, 3), np.uint8)
+        if not self.L.pth_read_display(self.h, out.ctypes.data):
+            raise _ptk.PtkError("ReadDisplay failed: " + self.LastError())
+        return out
+
+    def DisplayState(self) -> dict:
+        """The exposure state behind the last DisplayFrame() (Context.display_state)."""
+        st = _ptk.DisplayState()
+        if not self.L.pth_display_state(self.h, C.byref(st)):
+            raise _ptk.PtkError("DisplayState failed: " + self.LastError())
+        return st.as_dict()
+
+    def ResetDisplay(self):
+        """Forgets the exposure state: the next metered DisplayFrame() lands on its target."""
+        if not self.L.pth_display_reset(self.h):
+            raise _ptk.PtkError("ResetDisplay failed: " + self.LastError())
+
+    display_frame, read_display, display_state, display_reset = DisplayFrame, ReadDisplay, DisplayState, ResetDisplay
     temporal_frame, read_temporal, get_view = TemporalFrame, ReadTemporal, GetView
     temporal_frame_moments, temporal_variance, read_temporal_variance, denoise_temporal = (TemporalFrameMoments, TemporalVariance,
                                                                                           ReadTemporalVariance, DenoiseTemporal)

@@ -106,6 +106,28 @@ class VarianceParams(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DisplayParams(C.Structure):
+    """ptk_display_params"""
+    _fields_ = [("mode", C.c_int32), ("exposure", C.c_float), ("key", C.c_float), ("min_lum", C.c_float), ("max_lum", C.c_float),
+                ("low_permille", C.c_int32), ("high_permille", C.c_int32), ("min_exposure", C.c_float), ("max_exposure", C.c_float),
+                ("adapt", C.c_float), ("op", C.c_int32), ("white", C.c_float), ("transfer", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class DisplayState(C.Structure):
+    """ptk_exposure_state: the exposure state of the display transform as it lies in device memory"""
+    _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("lavg", C.c_float), ("has_prev", C.c_uint32),
+                ("counted", C.c_uint64), ("kept", C.c_uint64)]
+
+    def as_dict(self):
+        """float32 scalars and ints, the struct's own bits"""
+        d = {k: np.float32(getattr(self, k)) for k in ("exposure", "target", "lavg")}
+        d.update({k: int(getattr(self, k)) for k in ("has_prev", "counted", "kept")})
+        return d
+
+
 class ReprojectDesc(C.Structure):
     """ptk_reproject_desc"""
     _fields_ = ([("width", C.c_int32), ("height", C.c_int32), ("hist_view", C.POINTER(View))]
@@ -148,6 +170,8 @@ SYMBOLS = [
     "ptk_reproject_moments", "ptk_reproject_moments_device", "ptk_temporal_frame_moments", "ptk_variance_planes",
     "ptk_variance_planes_device", "ptk_temporal_variance", "ptk_read_temporal_variance", "ptk_temporal_variance_device_ptr",
     "ptk_denoise_temporal", "ptk_last_variance_ms",
+    "ptk_display_planes", "ptk_display_planes_device", "ptk_display_frame", "ptk_read_display", "ptk_display_device_ptr",
+    "ptk_display_state", "ptk_display_reset", "ptk_display_srgb_table", "ptk_display_check_params", "ptk_last_display_ms",
     "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
     "ptk_last_bake_ms",
     "ptk_trace_rays_adaptive", "ptk_trace_rays_adaptive_device", "ptk_bake_lightmap_adaptive", "ptk_bake_lightmap_adaptive_device",
@@ -295,6 +319,16 @@ def _load_locked() -> C.CDLL:
         L.ptk_temporal_variance_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
         L.ptk_denoise_temporal.argtypes = [vp, C.POINTER(DenoiseParams), u32]
         L.ptk_last_variance_ms.argtypes = [vp, fp, fp]
+        for fn in (L.ptk_display_planes, L.ptk_display_planes_device):
+            fn.argtypes = [vp, i32, i32, vp, C.POINTER(DisplayParams), vp, vp]
+        L.ptk_display_frame.argtypes = [vp, i32, C.POINTER(DisplayParams)]
+        L.ptk_read_display.argtypes = [vp, vp]
+        L.ptk_display_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.ptk_display_state.argtypes = [vp, C.POINTER(DisplayState)]
+        L.ptk_display_reset.argtypes = [vp]
+        L.ptk_display_srgb_table.argtypes = [vp]
+        L.ptk_display_check_params.argtypes = [C.POINTER(DisplayParams)]
+        L.ptk_last_display_ms.argtypes = [vp, fp, fp, fp]
         L.ptk_scene_is_lambert.argtypes = [C.POINTER(SceneDesc)]
         L.ptk_trace_is_lambert.argtypes = [vp, C.POINTER(C.c_int)]
         L.ptk_flat_zero_class.argtypes = [C.POINTER(C.c_float)]
@@ -342,6 +376,48 @@ def _denoise_params(params) -> DenoiseParams:
     if isinstance(params, DenoiseParams):
         return params
     return DenoiseParams(int(params["iterations"]), int(params["normal_squarings"]), float(params["sigma_z"]), float(params["sigma_l"]))
+
+
+EXPOSURE_MANUAL, EXPOSURE_METERED = 0, 1                              # ptk_display_params.mode
+DISPLAY_LINEAR, DISPLAY_REINHARD, DISPLAY_ACES = 0, 1, 2              # ... .op
+TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1                                 # ... .transfer
+DISPLAY_ACCUM, DISPLAY_DENOISED, DISPLAY_TEMPORAL = 0, 1, 2           # ptk_display_frame source
+_DISPLAY_FIELDS = tuple(k for k, _ in DisplayParams._fields_)
+
+
+def display_defaults(**overrides) -> DisplayParams:
+    """The documented default parameters of the display transform: metered exposure that brings the average of
+    the histogram's ranks 100 .. 950 permille to the key 0.18, luminances 2^-20 .. 2^20 counted, the exposure held in
+    2^-10 .. 2^10, adapt 1 (no lag), the ACES curve and the sRGB transfer; manual exposure 1 and white 4 for the modes that use
+    them.  Keyword arguments replace fields."""
+    p = DisplayParams(EXPOSURE_METERED, 1.0, 0.18, 2.0 ** -20, 2.0 ** 20, 100, 950, 2.0 ** -10, 2.0 ** 10, 1.0, DISPLAY_ACES, 4.0,
+                      TRANSFER_SRGB)
+    for k, v in overrides.items():
+        assert k in _DISPLAY_FIELDS, k
+        setattr(p, k, v)
+    return p
+
+
+def _display_params(params) -> DisplayParams:
+    if isinstance(params, DisplayParams):
+        return params
+    if params is None:
+        return display_defaults()
+    return DisplayParams(*(params[k] for k in _DISPLAY_FIELDS))
+
+
+def display_srgb_table() -> np.ndarray:
+    """ptk_display_srgb_table: the 256 float32 thresholds that define the SRGB transfer; needs no device."""
+    out = np.empty(256, np.float32)
+    rc = load().ptk_display_srgb_table(out.ctypes.data)
+    if rc != PTK_OK:
+        raise PtkError(f"ptk_display_srgb_table failed ({rc})")
+    return out
+
+
+def display_check_params(params) -> int:
+    """ptk_display_check_params: PTK_OK or the code the display entries refuse `params` with; needs no device."""
+    return int(load().ptk_display_check_params(C.byref(_display_params(params))))
 
 
 TEMPORAL_RESET = 1                                                    # ptk_temporal_frame flags
@@ -824,6 +900,70 @@ class Context:
         t = [C.c_float(0) for _ in range(3)]
         self._chk(self.L.ptk_last_denoise_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_denoise_ms")
         return dict(zip(("pack_ms", "filter_ms", "unpack_ms"), (x.value for x in t)))
+
+    # ---- display transform -------------------------------------------------------------------
+    def display_planes(self, color, params=None, want_state: bool = False):
+        """ptk_display_planes: exposure, tone curve and transfer function of include/ptk.h over the image color [H, W, 3] float32
+        into [H, W, 3] uint8, rows as given.  params: DisplayParams (display_defaults) or a dict of its fields.  A metered call
+        reads and updates the context's exposure state on the device.  Returns the bytes, or (bytes, state) with want_state: a
+        dict for numpy input, a [8] int32 tensor holding ptk_exposure_state's 32 bytes for tensors.  numpy arrays go through the
+        host entry (synchronous); torch tensors on the context's GPU go through ptk_display_planes_device with no host copy and
+        give torch tensors written on the context's stream (see trace_rays)."""
+        prm = _display_params(params)
+        H, W = int(color.shape[0]), int(color.shape[1])
+        px = H * W
+        if hasattr(color, "data_ptr"):
+            import torch
+            self._ray_tensors([color], px, [(torch.float32, 3)])
+            out = torch.empty((H, W, 3), dtype=torch.uint8, device=color.device)
+            state = torch.zeros(8, dtype=torch.int32, device=color.device) if want_state else None
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and px else None
+            self._chk(self.L.ptk_display_planes_device(self.h, W, H, ptr(color), C.byref(prm), ptr(out), ptr(state)),
+                      "ptk_display_planes_device")
+            return (out, state) if want_state else out
+        color = np.ascontiguousarray(color, dtype=np.float32).reshape(H, W, 3)
+        out = np.empty((H, W, 3), np.uint8)
+        st = DisplayState()
+        self._chk(self.L.ptk_display_planes(self.h, W, H, color.ctypes.data if px else None, C.byref(prm), out.ctypes.data if px else None,
+                                            C.byref(st) if want_state and px else None), "ptk_display_planes")
+        if want_state and not px:
+            return out, self.display_state()
+        return (out, st.as_dict()) if want_state else out
+
+    def display_frame(self, source: int = DISPLAY_ACCUM, params=None):
+        """ptk_display_frame: the display transform over the context's frame - source DISPLAY_ACCUM (S1 / n), DISPLAY_DENOISED or
+        DISPLAY_TEMPORAL - into the context's display image (read_display); asynchronous."""
+        prm = _display_params(params)
+        self._chk(self.L.ptk_display_frame(self.h, int(source), C.byref(prm)), "ptk_display_frame")
+
+    def read_display(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """[H][W][3] uint8, the last display_frame's result, in resolve_rgb8's layout; waits for the stream."""
+        if out is None:
+            out = np.empty((self.height, self.width, 3), dtype=np.uint8)
+        self._chk(self.L.ptk_read_display(self.h, out.ctypes.data), "ptk_read_display")
+        return out
+
+    def display_device_ptr(self):
+        p = C.c_void_p(); b = C.c_size_t()
+        self._chk(self.L.ptk_display_device_ptr(self.h, C.byref(p), C.byref(b)), "ptk_display_device_ptr")
+        return p.value, b.value
+
+    def display_state(self) -> dict:
+        """ptk_display_state: the exposure state behind the last display call (exposure, target, lavg as float32; has_prev,
+        counted, kept); waits for the stream."""
+        st = DisplayState()
+        self._chk(self.L.ptk_display_state(self.h, C.byref(st)), "ptk_display_state")
+        return st.as_dict()
+
+    def display_reset(self):
+        """ptk_display_reset: forgets the exposure state; asynchronous."""
+        self._chk(self.L.ptk_display_reset(self.h), "ptk_display_reset")
+
+    def last_display_ms(self) -> dict:
+        """HIP-event times of the last display call: meter kernel, exposure step, apply kernel; waits for it."""
+        t = [C.c_float(0) for _ in range(3)]
+        self._chk(self.L.ptk_last_display_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_display_ms")
+        return dict(zip(("meter_ms", "exposure_ms", "apply_ms"), (x.value for x in t)))
 
     # ---- temporal reprojection ---------------------------------------------------------------
     def get_view(self) -> View:

@@ -7,6 +7,8 @@
     python -m pbrpathtracer_amd.render scene.pts --orbit FRAMES --spp K --temporal --move-object OBJ --move-by DX DY DZ
     python -m pbrpathtracer_amd.render scene.pts --orbit FRAMES --spp K --temporal --denoise --temporal-variance
                                                  [--motion-vectors FILE.npy]
+    python -m pbrpathtracer_amd.render scene.pts ... --display {linear,reinhard,aces} [--exposure auto|EV] [--key K] [--adapt A]
+                                                 [--linear-transfer]
     python -m pbrpathtracer_amd.render scene.pts --features planes.npz
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz
@@ -15,6 +17,12 @@
                                                  [--denoise] [--dilate K] -o map.png [--npy map.npy]
     python -m pbrpathtracer_amd.render scene.pts --bake-probes NX NY NZ [--probe-dirs D] --spp N -o probes.npz
                                                  [--probe-visibility RES [--probe-max-dist M]]
+
+With --display the PNG of a perspective frame or an --orbit is the frame after the display transform (include/ptk.h
+ptk_display_frame, PathTracer.DisplayFrame): an exposure - metered from the frame's luminance histogram, or 2^EV -, the tone curve
+named, and the sRGB transfer function (--linear-transfer: none), over the --denoise or --temporal result where there is one.  With
+--orbit every step is displayed, so the exposure state on the device adapts from step to step (--adapt below 1 lets it lag).
+Without --display every output stays what it is: the plain clamp-and-truncate resolve.
 
 With --noise-threshold the render is adaptive (include/ptk.h ptk_render_adaptive): --spp becomes the most samples a pixel
 gets, and pixels stop once their noise meets the threshold.  --equirect and --bake-lightmap take it too (ptk_trace_rays_adaptive,
@@ -99,6 +107,16 @@ def build_parser() -> argparse.ArgumentParser:
                     help="filter the frame (or, with --bake-lightmap, the lightmap) with the a-trous denoiser before it is written; "
                          "with --noise-threshold the frame's filter is variance-guided")
     ap.add_argument("--denoise-iterations", type=int, default=None, metavar="K", help="--denoise: a-trous iterations, 1..8 (default 5)")
+    ap.add_argument("--display", choices=("linear", "reinhard", "aces"), default=None,
+                    help="write the frame after the display transform - exposure, this tone curve, the sRGB transfer - instead of the "
+                         "plain resolve; takes the --denoise or --temporal result where there is one; with --orbit the exposure adapts "
+                         "from step to step")
+    ap.add_argument("--exposure", default="auto", metavar="auto|EV",
+                    help="--display: metered from the frame's luminance histogram (default), or a fixed 2^EV")
+    ap.add_argument("--key", type=float, default=None, metavar="K", help="--display: the value the metered average is brought to (default 0.18)")
+    ap.add_argument("--adapt", type=float, default=None, metavar="A",
+                    help="--display --orbit: the step toward the metered exposure per frame (default 1: no lag)")
+    ap.add_argument("--linear-transfer", action="store_true", help="--display: encode linearly instead of with the sRGB transfer")
     ap.add_argument("--orbit", type=int, default=None, metavar="FRAMES",
                     help="turn the camera about the scene's centre in FRAMES steps, --spp samples after a reset at each; the image is the last view")
     ap.add_argument("--orbit-degrees", type=float, default=10.0, metavar="D", help="--orbit: the whole turn in degrees (default 10)")
@@ -174,6 +192,21 @@ def bake_offset(pt) -> float:
     """the default --bake-offset: 1e-3 of the largest side of the staged scene's bounding box"""
     v = np.asarray(pt.StagedScene()["verts"], np.float64).reshape(-1, 3)
     return float(np.float32(1e-3 * (v.max(axis=0) - v.min(axis=0)).max())) if len(v) else 1e-3
+
+
+def display_params(a):
+    """ptk.display_defaults with --display, --exposure, --key, --adapt and --linear-transfer"""
+    from . import ptk
+    p = ptk.display_defaults(op={"linear": ptk.DISPLAY_LINEAR, "reinhard": ptk.DISPLAY_REINHARD, "aces": ptk.DISPLAY_ACES}[a.display])
+    if a.exposure != "auto":
+        p.mode, p.exposure = ptk.EXPOSURE_MANUAL, float(2.0 ** float(a.exposure))
+    if a.key is not None:
+        p.key = a.key
+    if a.adapt is not None:
+        p.adapt = a.adapt
+    if a.linear_transfer:
+        p.transfer = ptk.TRANSFER_LINEAR
+    return p
 
 
 def denoise_params(pt, a, variance=False):
@@ -407,6 +440,9 @@ def render_orbit(pt, a) -> int:
             pt.TemporalFrameMoments(moving=moving)
         elif a.temporal:
             pt.TemporalFrameMoving() if moving else pt.TemporalFrame()
+        if a.display and k + 1 < a.orbit:
+            # the exposure state lives on the device and adapts step by step; the last step is displayed below, behind its filter
+            pt.DisplayFrame(ptk.DISPLAY_TEMPORAL if a.temporal else ptk.DISPLAY_ACCUM, display_params(a))
     t2 = time.time()
     if a.motion_vectors:
         np.save(a.motion_vectors, np.ascontiguousarray(pt.ReadMotion()[2][::-1], np.float32))
@@ -428,7 +464,18 @@ def render_orbit(pt, a) -> int:
         image, note = pt.ReadDenoised(), ""
     else:
         image, note = pt.ReadAccumulation() / np.float32(a.spp), ""
-    export_png(a.out, resolve_mean(image, 1)[::-1].copy())
+    if a.display:
+        if a.temporal and a.denoise and not a.temporal_variance:
+            shown = pt.context().display_planes(image, display_params(a))          # (filtered on the host side just above)
+        else:
+            pt.DisplayFrame(ptk.DISPLAY_DENOISED if a.denoise else ptk.DISPLAY_TEMPORAL if a.temporal else ptk.DISPLAY_ACCUM, display_params(a))
+            shown = pt.ReadDisplay()
+        st = pt.DisplayState()
+        if a.exposure == "auto":
+            note += f"; exposure {float(st['exposure']):.4g} (target {float(st['target']):.4g}, metered average {float(st['lavg']):.4g})"
+    else:
+        shown = resolve_mean(image, 1)
+    export_png(a.out, shown[::-1].copy())
     if a.npy:
         np.save(a.npy, np.ascontiguousarray(image[::-1], np.float32))
     print(f"{a.scene}: {w}x{h}, orbit of {a.orbit} steps over {a.orbit_degrees} degrees, {a.spp} spp each"
@@ -466,6 +513,22 @@ def main(argv=None):
     if a.temporal_variance and not (a.temporal and a.denoise):
         print("error: --temporal-variance goes with --temporal and --denoise", file=sys.stderr)
         return 1
+    if a.display is None and (a.exposure != "auto" or a.key is not None or a.adapt is not None or a.linear_transfer):
+        print("error: --exposure, --key, --adapt and --linear-transfer go with --display", file=sys.stderr)
+        return 1
+    if a.display is not None:
+        if a.bake_lightmap is not None or a.bake_probes is not None or a.distance_field is not None or a.equirect is not None:
+            print("error: --display shows a perspective frame or an --orbit", file=sys.stderr)
+            return 1
+        try:
+            if a.exposure != "auto":
+                float(a.exposure)
+            from . import ptk
+            if ptk.display_check_params(display_params(a)) != ptk.PTK_OK:
+                raise ValueError
+        except (ValueError, OverflowError):
+            print("error: --exposure takes auto or a number of stops, --key a positive number, --adapt a number >= 0", file=sys.stderr)
+            return 1
     if a.orbit is not None:
         if a.orbit < 1 or a.noise_threshold is not None or a.bake_lightmap is not None or a.bake_probes is not None or \
                 a.distance_field is not None or a.equirect is not None:
@@ -524,6 +587,14 @@ def main(argv=None):
             out = pt.ResolveDenoised()
             if a.npy:
                 np.save(a.npy, pt.ReadDenoised()[::-1].copy())
+        except RuntimeError as e:
+            print("error:", e, file=sys.stderr)
+            return 1
+    if a.display:
+        from . import ptk
+        try:
+            pt.DisplayFrame(ptk.DISPLAY_DENOISED if a.denoise else ptk.DISPLAY_ACCUM, display_params(a))
+            out = pt.ReadDisplay()
         except RuntimeError as e:
             print("error:", e, file=sys.stderr)
             return 1
