@@ -29,6 +29,7 @@ struct ptk_denoise_params;
 struct ptk_temporal_params;
 struct ptk_variance_params;
 struct ptk_display_params;
+struct ptk_upsample_params;
 struct ptk_exposure_state;
 struct ptk_view;
 
@@ -258,6 +259,19 @@ public:
     bool ReadDisplay(GLubyte* out);
     bool DisplayState(ptk_exposure_state* out);
     bool ResetDisplay();
+    // Extensions: guided upsampling (include/ptk.h ptk_render_guides, ptk_upsample_frame) - trace at a low resolution, show at a
+    // higher one.  RenderGuides: the first-hit planes MATERIAL, POSITION, NORMAL and ALBEDO of the current camera at width x height,
+    // whatever SetResolution set (sample 0 of the seed).  ReadGuide: one of them, width*height elements of the feature's type, rows
+    // bottom-up.  UpsampleFrame: the frame as last rendered (source PTK_UPSAMPLE_ACCUM), the DenoiseFrame() / DenoiseTemporal()
+    // result (PTK_UPSAMPLE_DENOISED) or the TemporalFrame*() result (PTK_UPSAMPLE_TEMPORAL) up to the guides' resolution; the
+    // frame's own guide planes are rendered first when missing or stale.  False without RenderGuides, when the two resolutions
+    // differ in aspect ratio or the source does not exist.  ReadUpsampled: width*height*3 floats and width*height classes (0
+    // bilinear, 1 wide ring, 2 a hole that holds the nearest low pixel), either may be NULL.  Pending edits are NOT applied; the
+    // image, the sample count and the hand-off buffer are not touched.
+    bool RenderGuides(int width, int height);
+    bool ReadGuide(int feature, void* out);
+    bool UpsampleFrame(int source, const ptk_upsample_params& params);
+    bool ReadUpsampled(float* color, int32_t* cls);
     // The (object, element) under pixel (x, y), y counted from the top row: one ray (ptk_pick), pending edits applied first.
     // A pixel that sees nothing gives -1 / -1 (and triangle -1) and true; false: no scene / resolution yet, or (x, y) outside the frame.
     bool Pick(int x, int y, int* objId, int* elementId, int* triangle = nullptr);

@@ -934,6 +934,105 @@ int ptk_display_check_params(const ptk_display_params* params);
  * exposure step and apply kernel (the first two 0 for a manual call); waits for the call */
 int ptk_last_display_ms(ptk_ctx* ctx, float* meter_ms, float* exposure_ms, float* apply_ms);
 
+/* ---- guided upsampling: trace at a low resolution, reconstruct at the full one (no counterpart in the reference) ----------------
+ * Trace time dominates an interactive frame and every pass above works at the resolution that was traced.  With the lens closed
+ * every sample of a pixel goes through one camera ray, so first-hit planes at the OUTPUT resolution are exact and cost one walk per
+ * pixel; ALBEDO carries the texture detail; and the id, tangent-plane and normal tests of the reprojection rule say, with
+ * comparisons only, whether a low-resolution sample lies on the surface a full-resolution pixel sees.  So: guide planes at a
+ * resolution of their own, and a bilinear upsample of the (denoised) low-resolution colour that those tests keep from bleeding
+ * across silhouettes, demodulated at the low and re-modulated at the high resolution.
+ * GUIDE PLANES.  ptk_render_guides renders the planes of ptk_render_features - the same ten features, bits, bottom-up rows and miss
+ * values - for the context's current scene and camera (a pending ptk_set_camera included) at width x height instead of the frame's
+ * size: the view is the frame set-up arithmetic at that size, the RNG pixel of the opacity draws is the top-down pixel index at
+ * width x height.  The planes are bit for bit those ptk_render_features gives a context framed at width x height with the same
+ * camera.  The call uses a primary-direction table of its own and always walks; it touches nothing of the frame - accumulator,
+ * sample count, feature planes, primary-hit cache - and needs no frame.  Buffers are the context's, grown on demand, freed with
+ * the feature planes.  ptk_read_guide (waits for the stream), ptk_guide_device_ptr, ptk_guide_view (the view of the last
+ * ptk_render_guides, as ptk_get_view returns the frame's): PTK_ERR_BAD_ARG before a ptk_render_guides of a non-empty size, and for
+ * a feature that was not in its mask.  PTK_ERR_BAD_ARG: no scene, a negative size, an unknown mask bit, a tile split with
+ * world > 1.  PTK_ERR_LIMIT: more than 2^28 pixels or 262140 rows, or a BVH deeper than the traversal stack.  A zero-sized call is
+ * PTK_OK, does nothing and keeps the previous guides.
+ * THE UPSAMPLING RULE.  Every operation is one IEEE float32 operation in the order written (the kernels are compiled with
+ * -ffp-contract=off); only + - * /, comparisons and floor occur; dot is as the temporal rule defines it.  The numpy restatement is
+ * tests/upsample_rule.py (tests/test_gpu_upsample.py: array_equal).
+ * PLANES, rows bottom-up (top-down row i of an image of R rows is plane row R-1-i).  LOW, w x h: color[3], id (int32, < 0: nothing
+ * was hit), position[3], normal[3], and albedo[3] or NULL.  HIGH, W x H: id, position, normal, and albedo or NULL - the two albedo
+ * planes are both present or both absent.  Outputs: out_color [H][W][3] and out_class [H][W] int32.
+ * PARAMETERS: ptk_upsample_params below.  ONCE PER CALL:
+ *   sx = (float)w / (float)W;  sy = (float)h / (float)H;  zz = max_plane_dist*max_plane_dist
+ * PER HIGH PIXEL p at column x and top-down row i:
+ *   position in the low image   col = (((float)x + 0.5f)*sx) - 0.5f;  row = (((float)i + 0.5f)*sy) - 0.5f
+ *                     x0 = (int)floor(col);  fx = col - (float)x0;  i0 = (int)floor(row);  fy = row - (float)i0
+ *                     gx = 1.0f - fx;  gy = 1.0f - fy
+ *   acceptance        of a low tap q at column tx and top-down row ti: q lies inside the low image, and
+ *                     id_p < 0:  id_q < 0
+ *                     otherwise: id_q == id_p,  z = dot(normal_p, position_q - position_p) has z*z <= zz,  and
+ *                     dot(normal_p, normal_q) >= min_normal_dot.  Every comparison is false for NaN.
+ *   tap value         with albedo planes and id_q >= 0:  v_c = color_q,c / (albedo_q,c + 0.00390625f)  (the denoiser's A);
+ *                     otherwise v_c = color_q,c
+ *   ring 0            the four taps (x0,i0) (x0+1,i0) (x0,i0+1) (x0+1,i0+1), in this order, with b = gx*gy, fx*gy, gx*fy, fx*fy.  A
+ *                     tap with !(b > 0) is skipped.  A taken tap adds  sc_c = sc_c + (b*v_c);  sw = sw + b.  If sw > 0: class 0,
+ *                     r_c = sc_c / sw.
+ *   ring 1            only if ring 0 took nothing and wide is set: the twelve taps of the 4x4 block tx = x0-1..x0+2, ti = i0-1..i0+2
+ *                     that are not in ring 0, rows outer, both ascending, with fresh sums.  dx = (float)tx - col;
+ *                     dy = (float)ti - row;  b = 1.0f / (1.0f + ((dx*dx) + (dy*dy))).  The same sums.  If sw > 0: class 1,
+ *                     r_c = sc_c / sw.
+ *   hole              otherwise class 2:  xn = clamp((int)floor(col + 0.5f), 0, w-1);  in = clamp((int)floor(row + 0.5f), 0, h-1);
+ *                     out = the colour of that low pixel, its bits, with no re-modulation.
+ *   classes 0 and 1   with albedo planes and id_p >= 0:  out_c = r_c * (albedo_p,c + 0.00390625f);  otherwise out_c = r_c.
+ * Taps are read from clamped addresses and dropped by their predicates: nothing out of bounds is formed.  W == w with H == h is
+ * legal (without albedo planes the output is then the input), and so is W < w: the same rule.  What an invalid low pixel holds -
+ * NaN, 1e30 - reaches no valid high pixel of class 0 or 1.
+ * Why this shape, what it costs and what is deliberately left out (jittered low-resolution views, an upsampled variance, tile
+ * splits): DESIGN.md 4.23.
+ *   ptk_upsample_planes: host arrays, synchronous, staged in device memory for the length of the call.
+ *   ptk_upsample_planes_device: every array in memory of this context's GPU, asynchronous on the context's stream - except that
+ *     the context's packed low image (48 or 64 B per low pixel) grows, behind a drain of the stream, when a call is larger than every
+ *     one before.  The outputs may not alias an input.  Both need no scene, no camera and no frame.
+ *   ptk_upsample_frame: the context's frame, w x h, up to the resolution W x H of the last ptk_render_guides.  The colour is taken
+ *     exactly as ptk_display_frame takes it for the same three sources (PTK_UPSAMPLE_ACCUM: S1 / n_p inside the pack kernel); the low
+ *     guides are the feature planes MATERIAL, POSITION, NORMAL and ALBEDO, the high guides the same four of the last
+ *     ptk_render_guides.  The result goes into a context-owned buffer (16 B per high pixel, freed with the guide planes).
+ *     PTK_ERR_BAD_ARG when no frame is set, the source does not exist at the current resolution, one of the four planes is missing
+ *     from the last ptk_render_features or ptk_render_guides, the feature planes are not of the current resolution, W*h != H*w
+ *     (the two views must share an aspect ratio, else the pixel-centre mapping is not the camera's), or a tile split with
+ *     world > 1 is set.
+ *   ptk_read_upsampled (either pointer may be NULL; waits for the stream), ptk_upsampled_device_ptr: the result of the last
+ *     ptk_upsample_frame and its size; PTK_ERR_BAD_ARG before one.  The colour pointer chains into ptk_denoise_planes_device and
+ *     ptk_display_planes_device at W x H: denoise low, upsample, display high.
+ * PTK_ERR_BAD_ARG further: a null context, params or required array with non-zero sizes, a negative size, exactly one of the two
+ * albedo planes, max_plane_dist not finite or <= 0, min_normal_dot not finite or outside [-1, 1], wide neither 0 nor 1, an unknown
+ * source.  A refused call leaves every output alone.  A call with w*h == 0 or W*H == 0 is PTK_OK and does nothing.  PTK_ERR_LIMIT:
+ * more than 2^28 pixels or 262140 rows in either image.  None of these entries touches the accumulator, the sample count, the 8-bit
+ * image, a bound hand-off buffer, the feature planes, the histories or the display image. */
+int ptk_render_guides(ptk_ctx* ctx, int width, int height, uint32_t sample, uint64_t seed, uint32_t mask);
+int ptk_read_guide(ptk_ctx* ctx, int feature, void* host_out);
+int ptk_guide_device_ptr(ptk_ctx* ctx, int feature, void** dev_ptr, size_t* bytes);
+int ptk_guide_view(ptk_ctx* ctx, ptk_view* out);   /* the view of the last ptk_render_guides */
+#define PTK_UPSAMPLE_ACCUM 0
+#define PTK_UPSAMPLE_DENOISED 1
+#define PTK_UPSAMPLE_TEMPORAL 2
+typedef struct ptk_upsample_params {
+    float max_plane_dist;   /* finite, > 0: a tap further than this from the pixel's tangent plane is another surface */
+    float min_normal_dot;   /* finite, in [-1, 1] */
+    int32_t wide;           /* 0 or 1: ring 1 */
+} ptk_upsample_params;
+int ptk_upsample_planes(ptk_ctx* ctx, int w, int h, const float* color /*[h][w][3]*/, const int32_t* id /*[h][w]*/,
+                        const float* position /*[h][w][3]*/, const float* normal /*[h][w][3]*/, const float* albedo /*[h][w][3] or NULL*/,
+                        int W, int H, const int32_t* hi_id /*[H][W]*/, const float* hi_position /*[H][W][3]*/,
+                        const float* hi_normal /*[H][W][3]*/, const float* hi_albedo /*[H][W][3] or NULL*/,
+                        const ptk_upsample_params* params, float* out_color /*[H][W][3]*/, int32_t* out_class /*[H][W]*/);
+int ptk_upsample_planes_device(ptk_ctx* ctx, int w, int h, const float* d_color, const int32_t* d_id, const float* d_position,
+                               const float* d_normal, const float* d_albedo, int W, int H, const int32_t* d_hi_id,
+                               const float* d_hi_position, const float* d_hi_normal, const float* d_hi_albedo,
+                               const ptk_upsample_params* params, float* d_out_color, int32_t* d_out_class);
+int ptk_upsample_frame(ptk_ctx* ctx, int source, const ptk_upsample_params* params);
+int ptk_read_upsampled(ptk_ctx* ctx, float* color /*[H][W][3] or NULL*/, int32_t* cls /*[H][W] or NULL*/);
+int ptk_upsampled_device_ptr(ptk_ctx* ctx, void** color, void** cls, int* width, int* height);
+/* measurement hook (tools/upsample_timing.py), not part of the feature.  HIP-event times of the last upsample call's pack kernel
+ * and upsample_kernel; waits for the call */
+int ptk_last_upsample_ms(ptk_ctx* ctx, float* pack_ms, float* kernel_ms);
+
 /* ---- lightmap baking: the radiance leaving the scene's surfaces, per texel of a uv chart layout (no counterpart in the reference) --
  * The surface half of light baking in front of and behind ptk_trace_rays' kernel: a uv rasteriser, a ray generator, a scatter and
  * a chart-padding pass, all on the GPU from what ptk_upload_scene left resident.  Inputs: the uploaded scene, a lightmap of

@@ -100,6 +100,13 @@ int  pth_display_frame(pth_tracer* t, int source, const ptk_display_params* para
 int  pth_read_display(pth_tracer* t, unsigned char* out);
 int  pth_display_state(pth_tracer* t, ptk_exposure_state* out);
 int  pth_display_reset(pth_tracer* t);
+/* RenderGuides / ReadGuide / UpsampleFrame / ReadUpsampled (guided upsampling of the frame to the resolution of guide planes of
+ * their own, include/ptk.h ptk_render_guides, ptk_upsample_frame; source: PTK_UPSAMPLE_ACCUM, _DENOISED or _TEMPORAL): 1 on success;
+ * either pointer of pth_read_upsampled may be NULL */
+int  pth_render_guides(pth_tracer* t, int width, int height);
+int  pth_read_guide(pth_tracer* t, int feature, void* out);
+int  pth_upsample_frame(pth_tracer* t, int source, const ptk_upsample_params* params);
+int  pth_read_upsampled(pth_tracer* t, float* color, int32_t* cls);
 /* ClosestPoints (the nearest surface point to caller-supplied points, include/ptk.h ptk_closest_points): 1 on success */
 int  pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point,
                         float* bary);

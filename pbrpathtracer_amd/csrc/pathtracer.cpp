@@ -1028,6 +1028,53 @@ bool PathTracer::ResetDisplay()
     return rc == PTK_OK;
 }
 
+// Guide planes at a resolution of their own (ptk_render_guides): the four planes UpsampleFrame() needs, for sample 0 of the seed,
+// like the frame's own guide planes.  No pending edit is applied.
+bool PathTracer::RenderGuides(int width, int height)
+{
+    if (!m->scene_uploaded || !m->ctx) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const uint32_t four = (1u << PTK_FEAT_MATERIAL) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL) | (1u << PTK_FEAT_ALBEDO);
+    const int rc = ptk_render_guides(m->ctx, width, height, 0, m->seed, four);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ReadGuide(int feature, void* out)
+{
+    if (!m->ctx || !out) return false;
+    const int rc = ptk_read_guide(m->ctx, feature, out);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+// Guided upsampling of the frame as it was last rendered, denoised or reprojected (ptk_upsample_frame).  No pending edit is
+// applied; the frame's guide planes are rendered as TemporalFrameMoments() renders its own when one of the four is missing or stale.
+bool PathTracer::UpsampleFrame(int source, const ptk_upsample_params& params)
+{
+    if (!m->scene_uploaded || !m->have_resolution || !m->ctx) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const uint32_t need = (1u << PTK_FEAT_MATERIAL) | (1u << PTK_FEAT_POSITION) | (1u << PTK_FEAT_NORMAL) | (1u << PTK_FEAT_ALBEDO);
+    int rc = PTK_OK;
+    if ((m->feat_mask & need) != need || m->feat_sample != 0 || m->feat_seed != m->seed || m->feat_epoch != m->view_epoch)
+    {
+        const uint32_t all = need | (1u << PTK_FEAT_TRIANGLE) | (1u << PTK_FEAT_EMISSION);
+        rc = ptk_render_features(m->ctx, 0, m->seed, all);
+        m->note(rc);
+        m->feat_mask = rc == PTK_OK ? all : 0u; m->feat_sample = 0; m->feat_seed = m->seed; m->feat_epoch = m->view_epoch;
+    }
+    if (rc == PTK_OK) { rc = ptk_upsample_frame(m->ctx, source, &params); m->note(rc); }
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ReadUpsampled(float* color, int32_t* cls)
+{
+    if (!m->ctx) return false;
+    const int rc = ptk_read_upsampled(m->ctx, color, cls);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 void PathTracer::TrackMotion(bool on)
 {
     std::lock_guard<std::mutex> render_guard(m->render_mu);

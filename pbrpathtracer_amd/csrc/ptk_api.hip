@@ -58,27 +58,36 @@ void pack_material(const ptk_material& m, const std::vector<int32_t>& texmap, fl
 }
 
 // image-plane set-up of RenderFrame, pathtracer.cpp:755-766 (host, once per camera/resolution change)
-void frame_setup(ptk_ctx* c, PrimaryParams& pp)
+// ... at any size: the context is only read, the camera's right vector goes into pp alone (the guide planes' view, ptk_render_guides)
+void frame_setup_at(const ptk_ctx* c, int width, int height, PrimaryParams& pp)
 {
     const float* pos = c->cam_pos; const float* dir = c->cam_dir; const float* up = c->cam_up;
     float center[3] = { pos[0] + dir[0] * c->focal, pos[1] + dir[1] * c->focal, pos[2] + dir[2] * c->focal };
     float img_h = (float)((double)(2.0f * c->focal) * std::tan((double)(c->fovy / 2.0f) * 3.14159265358979323846 / (double)180.0f));
-    float aspect = (float)c->width / (float)c->height;
+    float aspect = (float)width / (float)height;
     float img_w = img_h * aspect;
-    pp.delta_x = img_w / (float)c->width;
-    pp.delta_y = img_h / (float)c->height;
+    pp.delta_x = img_w / (float)width;
+    pp.delta_y = img_h / (float)height;
     // camRight = normalize(cross(up, dir))
     float cr[3] = { up[1] * dir[2] - dir[1] * up[2], up[2] * dir[0] - dir[2] * up[0], up[0] * dir[1] - dir[0] * up[1] };
-    normalize3(cr, c->cam_right);
+    float right[3];
+    normalize3(cr, right);
     float hw = img_w * 0.5f, hh = img_h * 0.5f;
     for (int a = 0; a < 3; a++)
     {
-        float tl = center[a] - c->cam_right[a] * hw;
+        float tl = center[a] - right[a] * hw;
         tl = tl + up[a] * hh;
         pp.top_left[a] = tl;
-        pp.cam_pos[a] = pos[a]; pp.cam_right[a] = c->cam_right[a]; pp.cam_up[a] = up[a];
+        pp.cam_pos[a] = pos[a]; pp.cam_right[a] = right[a]; pp.cam_up[a] = up[a];
     }
-    pp.primary = c->d_primary; pp.width = c->width; pp.height = c->height;
+    pp.primary = nullptr; pp.width = width; pp.height = height;
+}
+
+void frame_setup(ptk_ctx* c, PrimaryParams& pp)
+{
+    frame_setup_at(c, c->width, c->height, pp);
+    for (int a = 0; a < 3; a++) c->cam_right[a] = pp.cam_right[a];
+    pp.primary = c->d_primary;
 }
 
 // on-image pixels of the tiles this rank owns (same tile -> rank map as the kernels)
@@ -166,6 +175,11 @@ void free_features(ptk_ctx* c)
     dfree(c->d_motion); c->motion_w = c->motion_h = 0;            // ... and the motion planes
     dfree(c->d_temporal_mm); c->temporal_moments = c->temporal_variance = false;      // ... and the moments and the variance
     dfree(c->d_display); c->disp_w = c->disp_h = 0;               // ... and the display image (the exposure state stays)
+    // ... and the guide planes with the upsampled frame
+    for (int k = 0; k < NUM_FEATURES; k++) { dfree(c->d_guide[k]); c->guide_cap[k] = 0; }
+    dfree(c->d_guide_primary); c->guide_primary_px = 0;
+    c->guide_w = c->guide_h = 0; c->guide_mask = 0;
+    dfree(c->d_upsampled); c->upsampled_px = 0; c->ups_w = c->ups_h = 0;
 }
 
 // Brings the primary-visibility cache up to date where it is valid and hands it to p; else p keeps walking from the camera.
@@ -465,6 +479,7 @@ int ptk::ensure_primary(ptk_ctx* c)
 }
 
 void ptk::frame_view(ptk_ctx* c, PrimaryParams& pp) { frame_setup(c, pp); }
+void ptk::frame_view_at(const ptk_ctx* c, int width, int height, PrimaryParams& pp) { frame_setup_at(c, width, height, pp); }
 
 void ptk::fill_params(ptk_ctx* c, RenderParams& p, uint32_t first, uint32_t spp, uint64_t seed)
 {
@@ -624,6 +639,8 @@ void ptk_destroy(ptk_ctx* c)
     for (hipEvent_t e : c->ev_variance) if (e) (void)hipEventDestroy(e);
     dfree(c->d_display_hist);
     for (hipEvent_t e : c->ev_display) if (e) (void)hipEventDestroy(e);
+    dfree(c->d_upsample_pack);
+    for (hipEvent_t e : c->ev_upsample) if (e) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; b++)
         if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
     if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);

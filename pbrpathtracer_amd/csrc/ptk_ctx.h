@@ -256,6 +256,24 @@ struct ptk_ctx {
     hipEvent_t ev_display[4] = { nullptr, nullptr, nullptr, nullptr };
     bool display_timed = false;
 
+    // guided upsampling (ptk_render_guides, ptk_upsample_planes, ptk_upsample_frame).  The guide planes at a resolution of their
+    // own with their primary-direction table (16 B per guide pixel), each grown to the largest call so far and freed with the
+    // feature planes; guide_w x guide_h, guide_mask and guide_view describe the last ptk_render_guides (0: none yet).  The packed
+    // low image of a call, three or four float4 images (48 or 64 B per low pixel), grown likewise.  The frame entry's result, colour
+    // [H][W][3] then class [H][W] (16 B per high pixel), grown likewise and freed with the guide planes; ups_w x ups_h is the size
+    // it was last written at.  Three events of the last upsample call: before the pack, behind it, behind upsample_kernel
+    void* d_guide[ptk::NUM_FEATURES] = {};
+    size_t guide_cap[ptk::NUM_FEATURES] = {};    // pixels
+    float4* d_guide_primary = nullptr; size_t guide_primary_px = 0;
+    int guide_w = 0, guide_h = 0;
+    uint32_t guide_mask = 0;
+    ptk_view guide_view = {};
+    float4* d_upsample_pack = nullptr; size_t upsample_pack_texels = 0;
+    float* d_upsampled = nullptr; size_t upsampled_px = 0;
+    int ups_w = 0, ups_h = 0;
+    hipEvent_t ev_upsample[3] = { nullptr, nullptr, nullptr };
+    bool upsample_timed = false;
+
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
     // overlaps the tail of pass k's (a launch ends with the few waves that hold its longest paths - Russian roulette
@@ -375,6 +393,7 @@ constexpr size_t kTemporalMomentsBytes = 2 * sizeof(float4) + 5 * sizeof(float);
 void fill_params(ptk_ctx* c, RenderParams& p, uint32_t first, uint32_t spp, uint64_t seed);
 int ensure_primary(ptk_ctx* c);
 void frame_view(ptk_ctx* c, PrimaryParams& pp);       // frame_setup's arithmetic for the current camera and frame: host only
+void frame_view_at(const ptk_ctx* c, int width, int height, PrimaryParams& pp);      // ... at another size; pp.primary is left null
 // ... ptk_api_rays.hip: a ray query on the context's stream; the checks and the round loop the adaptive lightmap bake shares with
 // the adaptive ray query, and the context's adaptive buffer cut up for its capacity ...
 int trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,

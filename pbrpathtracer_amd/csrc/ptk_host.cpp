@@ -168,6 +168,13 @@ int pth_display_frame(pth_tracer* t, int source, const ptk_display_params* param
 int pth_read_display(pth_tracer* t, unsigned char* out) { return t->pt.ReadDisplay(out) ? 1 : 0; }
 int pth_display_state(pth_tracer* t, ptk_exposure_state* out) { return t->pt.DisplayState(out) ? 1 : 0; }
 int pth_display_reset(pth_tracer* t) { return t->pt.ResetDisplay() ? 1 : 0; }
+int pth_render_guides(pth_tracer* t, int width, int height) { return t->pt.RenderGuides(width, height) ? 1 : 0; }
+int pth_read_guide(pth_tracer* t, int feature, void* out) { return t->pt.ReadGuide(feature, out) ? 1 : 0; }
+int pth_upsample_frame(pth_tracer* t, int source, const ptk_upsample_params* params)
+{
+    return params && t->pt.UpsampleFrame(source, *params) ? 1 : 0;
+}
+int pth_read_upsampled(pth_tracer* t, float* color, int32_t* cls) { return t->pt.ReadUpsampled(color, cls) ? 1 : 0; }
 int pth_read_motion(pth_tracer* t, float* prev_position, float* prev_normal, float* motion)
 {
     return t->pt.ReadMotion(prev_position, prev_normal, motion) ? 1 : 0;

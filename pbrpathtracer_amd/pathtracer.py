@@ -43,6 +43,7 @@ HOST_SYMBOLS = [
     "pth_track_motion", "pth_temporal_frame_moving", "pth_read_motion", "pth_temporal_frame_moments", "pth_temporal_variance",
     "pth_read_temporal_variance", "pth_denoise_temporal", "pth_get_object_transform",
     "pth_display_frame", "pth_read_display", "pth_display_state", "pth_display_reset",
+    "pth_render_guides", "pth_read_guide", "pth_upsample_frame", "pth_read_upsampled",
 ]
 
 _bound = False
@@ -134,6 +135,10 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_read_display.restype = i32; L.pth_read_display.argtypes = [vp, vp]
         L.pth_display_state.restype = i32; L.pth_display_state.argtypes = [vp, C.POINTER(_ptk.DisplayState)]
         L.pth_display_reset.restype = i32; L.pth_display_reset.argtypes = [vp]
+        L.pth_render_guides.restype = i32; L.pth_render_guides.argtypes = [vp, i32, i32]
+        L.pth_read_guide.restype = i32; L.pth_read_guide.argtypes = [vp, i32, vp]
+        L.pth_upsample_frame.restype = i32; L.pth_upsample_frame.argtypes = [vp, i32, C.POINTER(_ptk.UpsampleParams)]
+        L.pth_read_upsampled.restype = i32; L.pth_read_upsampled.argtypes = [vp, vp, vp]
         L.pth_read_motion.restype = i32; L.pth_read_motion.argtypes = [vp, vp, vp, vp]
     except AttributeError:
         if _ptk.LIB_PATH.endswith("libptk.so"):   # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
@@ -484,6 +489,43 @@ class PathTracer:
             raise _ptk.PtkError("ResetDisplay failed: " + self.LastError())
 
     display_frame, read_display, display_state, display_reset = DisplayFrame, ReadDisplay, DisplayState, ResetDisplay
+
+    def RenderGuides(self, width: int, height: int):
+        """Extension: guide planes at a resolution of their own (include/ptk.h ptk_render_guides) - the first-hit planes MATERIAL,
+        POSITION, NORMAL and ALBEDO of the current camera at width x height, whatever SetResolution set; sample 0 of this tracer's
+        seed.  The image and the sample count are not touched.  UpsampleFrame() brings the frame up to this resolution."""
+        if not self.L.pth_render_guides(self.h, int(width), int(height)):
+            raise _ptk.PtkError("RenderGuides failed: " + self.LastError())
+        self._guide_size = (int(width), int(height))
+
+    def ReadGuide(self, feature: int) -> np.ndarray:
+        """One plane of the last RenderGuides(): [H, W] or [H, W, c] at the guides' size, rows bottom-up."""
+        w, h = getattr(self, "_guide_size", (0, 0))
+        out = _ptk.feature_array(feature, w, h)
+        if not self.L.pth_read_guide(self.h, int(feature), out.ctypes.data if out.size else None):
+            raise _ptk.PtkError("ReadGuide failed: " + self.LastError())
+        return out
+
+    def UpsampleFrame(self, source: int = _ptk.UPSAMPLE_ACCUM, params=None):
+        """Extension: guided upsampling (include/ptk.h ptk_upsample_frame) of the frame as last rendered (ptk.UPSAMPLE_ACCUM), the
+        DenoiseFrame() / DenoiseTemporal() result (ptk.UPSAMPLE_DENOISED) or the TemporalFrame*() result (ptk.UPSAMPLE_TEMPORAL)
+        up to the resolution of the last RenderGuides().  params: ptk.UpsampleParams or a dict of its fields; None takes
+        ptk.upsample_defaults for the staged scene's extent.  The frame's own guide planes are rendered first (sample 0 of this
+        tracer's seed) when they are missing or stale.  ReadUpsampled() gives the result."""
+        prm = _ptk._upsample_params(_ptk.upsample_defaults(self._extent()) if params is None else params)
+        if not self.L.pth_upsample_frame(self.h, int(source), C.byref(prm)):
+            raise _ptk.PtkError("UpsampleFrame failed: " + self.LastError())
+
+    def ReadUpsampled(self):
+        """(color [H][W][3] float32, class [H][W] int32 - 0 bilinear, 1 wide ring, 2 a hole) of the last UpsampleFrame(), at the
+        guides' size, rows bottom-up."""
+        w, h = getattr(self, "_guide_size", (0, 0))
+        color = np.empty((h, w, 3), np.float32); cls = np.empty((h, w), np.int32)
+        if not self.L.pth_read_upsampled(self.h, color.ctypes.data if color.size else None, cls.ctypes.data if cls.size else None):
+            raise _ptk.PtkError("ReadUpsampled failed: " + self.LastError())
+        return color, cls
+
+    render_guides, read_guide, upsample_frame, read_upsampled = RenderGuides, ReadGuide, UpsampleFrame, ReadUpsampled
     temporal_frame, read_temporal, get_view = TemporalFrame, ReadTemporal, GetView
     temporal_frame_moments, temporal_variance, read_temporal_variance, denoise_temporal = (TemporalFrameMoments, TemporalVariance,
                                                                                           ReadTemporalVariance, DenoiseTemporal)
@@ -723,6 +765,7 @@ class PathTracer:
         if not c.h:
             raise _ptk.PtkError("no HIP device: " + self.LastError())
         c.width, c.height = self.GetResolution()
+        c.guide_width, c.guide_height = getattr(self, "_guide_size", (0, 0))
         c._keep = self
         c.close = lambda: None
         return c

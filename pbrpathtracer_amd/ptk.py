@@ -106,6 +106,14 @@ class VarianceParams(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class UpsampleParams(C.Structure):
+    """ptk_upsample_params"""
+    _fields_ = [("max_plane_dist", C.c_float), ("min_normal_dot", C.c_float), ("wide", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DisplayParams(C.Structure):
     """ptk_display_params"""
     _fields_ = [("mode", C.c_int32), ("exposure", C.c_float), ("key", C.c_float), ("min_lum", C.c_float), ("max_lum", C.c_float),
@@ -172,6 +180,8 @@ SYMBOLS = [
     "ptk_denoise_temporal", "ptk_last_variance_ms",
     "ptk_display_planes", "ptk_display_planes_device", "ptk_display_frame", "ptk_read_display", "ptk_display_device_ptr",
     "ptk_display_state", "ptk_display_reset", "ptk_display_srgb_table", "ptk_display_check_params", "ptk_last_display_ms",
+    "ptk_render_guides", "ptk_read_guide", "ptk_guide_device_ptr", "ptk_guide_view", "ptk_upsample_planes",
+    "ptk_upsample_planes_device", "ptk_upsample_frame", "ptk_read_upsampled", "ptk_upsampled_device_ptr", "ptk_last_upsample_ms",
     "ptk_bake_coverage", "ptk_bake_lightmap", "ptk_bake_lightmap_device", "ptk_lightmap_dilate", "ptk_lightmap_dilate_device",
     "ptk_last_bake_ms",
     "ptk_trace_rays_adaptive", "ptk_trace_rays_adaptive_device", "ptk_bake_lightmap_adaptive", "ptk_bake_lightmap_adaptive_device",
@@ -329,6 +339,16 @@ def _load_locked() -> C.CDLL:
         L.ptk_display_srgb_table.argtypes = [vp]
         L.ptk_display_check_params.argtypes = [C.POINTER(DisplayParams)]
         L.ptk_last_display_ms.argtypes = [vp, fp, fp, fp]
+        L.ptk_render_guides.argtypes = [vp, i32, i32, u32, u64, u32]
+        L.ptk_read_guide.argtypes = [vp, i32, vp]
+        L.ptk_guide_device_ptr.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.ptk_guide_view.argtypes = [vp, C.POINTER(View)]
+        for fn in (L.ptk_upsample_planes, L.ptk_upsample_planes_device):
+            fn.argtypes = [vp, i32, i32] + [vp] * 5 + [i32, i32] + [vp] * 4 + [C.POINTER(UpsampleParams), vp, vp]
+        L.ptk_upsample_frame.argtypes = [vp, i32, C.POINTER(UpsampleParams)]
+        L.ptk_read_upsampled.argtypes = [vp, vp, vp]
+        L.ptk_upsampled_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.ptk_last_upsample_ms.argtypes = [vp, fp, fp]
         L.ptk_scene_is_lambert.argtypes = [C.POINTER(SceneDesc)]
         L.ptk_trace_is_lambert.argtypes = [vp, C.POINTER(C.c_int)]
         L.ptk_flat_zero_class.argtypes = [C.POINTER(C.c_float)]
@@ -418,6 +438,23 @@ def display_srgb_table() -> np.ndarray:
 def display_check_params(params) -> int:
     """ptk_display_check_params: PTK_OK or the code the display entries refuse `params` with; needs no device."""
     return int(load().ptk_display_check_params(C.byref(_display_params(params))))
+
+
+UPSAMPLE_ACCUM, UPSAMPLE_DENOISED, UPSAMPLE_TEMPORAL = 0, 1, 2        # ptk_upsample_frame source
+UPSAMPLE_GUIDES = (1 << 2) | (1 << 4) | (1 << 6) | (1 << 7)           # MATERIAL, POSITION, NORMAL, ALBEDO: what upsample_frame needs
+
+
+def upsample_defaults(extent: float) -> UpsampleParams:
+    """The documented default parameters of guided upsampling for a scene whose bounding box has the diagonal
+    `extent` (world units): a low-resolution tap counts within 1 % of the extent of the pixel's tangent plane and with a normal
+    within about 26 degrees (dot >= 0.9), as temporal_defaults has them; ring 1 is on."""
+    return UpsampleParams(float(extent) / 100.0, 0.9, 1)
+
+
+def _upsample_params(params) -> UpsampleParams:
+    if isinstance(params, UpsampleParams):
+        return params
+    return UpsampleParams(float(params["max_plane_dist"]), float(params["min_normal_dot"]), int(params["wide"]))
 
 
 TEMPORAL_RESET = 1                                                    # ptk_temporal_frame flags
@@ -964,6 +1001,98 @@ class Context:
         t = [C.c_float(0) for _ in range(3)]
         self._chk(self.L.ptk_last_display_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_display_ms")
         return dict(zip(("meter_ms", "exposure_ms", "apply_ms"), (x.value for x in t)))
+
+    # ---- guided upsampling -------------------------------------------------------------------
+    def render_guides(self, width: int, height: int, mask: int = UPSAMPLE_GUIDES, sample: int = 0, seed: int = 0):
+        """ptk_render_guides: the first-hit planes of `mask` (bit k = FEAT_*) for the current scene and camera at width x height -
+        a resolution of their own, whatever the frame's is - for sample `sample` of `seed`; asynchronous.  The frame is not
+        touched.  The default mask is what upsample_frame needs."""
+        self._chk(self.L.ptk_render_guides(self.h, int(width), int(height), int(sample), int(seed), int(mask)), "ptk_render_guides")
+        if int(width) > 0 and int(height) > 0:
+            self.guide_width, self.guide_height = int(width), int(height)
+
+    def read_guide(self, feature: int) -> np.ndarray:
+        """One plane of the last render_guides: [H, W] or [H, W, c] at the guides' size, typed and laid out like read_feature's."""
+        out = feature_array(feature, getattr(self, "guide_width", 0), getattr(self, "guide_height", 0))
+        self._chk(self.L.ptk_read_guide(self.h, int(feature), out.ctypes.data if out.size else None), "ptk_read_guide")
+        return out
+
+    def guide_device_ptr(self, feature: int):
+        p = C.c_void_p(); b = C.c_size_t()
+        self._chk(self.L.ptk_guide_device_ptr(self.h, int(feature), C.byref(p), C.byref(b)), "ptk_guide_device_ptr")
+        return p.value, b.value
+
+    def guide_view(self) -> View:
+        """ptk_guide_view: the image-plane set-up the last render_guides used (get_view's arithmetic at the guides' size)."""
+        v = View()
+        self._chk(self.L.ptk_guide_view(self.h, C.byref(v)), "ptk_guide_view")
+        return v
+
+    def upsample_planes(self, low, high, params):
+        """ptk_upsample_planes: the low image carried to the high guides' resolution by the rule of include/ptk.h.  low: (color
+        [h, w, 3] float32, id [h, w] int32, position [h, w, 3], normal [h, w, 3], albedo [h, w, 3] or None); high: (id [H, W],
+        position, normal, albedo or None); rows bottom-up; the two albedo planes go together.  params: UpsampleParams
+        (upsample_defaults) or a dict of its fields.  Returns (color [H, W, 3] float32, class [H, W] int32: 0 bilinear, 1 ring 1,
+        2 a hole).  numpy arrays go through the host entry (synchronous) and give numpy arrays; torch tensors on the context's GPU
+        go through ptk_upsample_planes_device with no host copy and give torch tensors written on the context's stream (see
+        trace_rays)."""
+        prm = _upsample_params(params)
+        low, high = list(low), list(high)
+        assert len(low) == 5 and len(high) == 4, "five low planes and four high planes (albedo may be None)"
+        h, w = int(low[0].shape[0]), int(low[0].shape[1])
+        H, W = int(high[0].shape[0]), int(high[0].shape[1])
+        px, PX = h * w, H * W
+        live = px > 0 and PX > 0
+        if hasattr(low[0], "data_ptr"):
+            import torch
+            f3, i1 = (torch.float32, 3), (torch.int32, 1)
+            have = [t for t in low + high if t is not None]
+            kinds = [k for t, k in zip(low + high, [f3, i1, f3, f3, f3, i1, f3, f3, f3]) if t is not None]
+            sizes = [n for t, n in zip(low + high, [px] * 5 + [PX] * 4) if t is not None]
+            for t, k, n in zip(have, kinds, sizes):
+                self._ray_tensors([t], n, [k])
+            out = torch.empty((H, W, 3), dtype=torch.float32, device=low[0].device)
+            cls = torch.empty((H, W), dtype=torch.int32, device=low[0].device)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and live else None
+            self._chk(self.L.ptk_upsample_planes_device(self.h, w, h, *(ptr(t) for t in low), W, H, *(ptr(t) for t in high), C.byref(prm),
+                                                        ptr(out), ptr(cls)), "ptk_upsample_planes_device")
+            return out, cls
+        lo_kinds = [(np.float32, (h, w, 3)), (np.int32, (h, w)), (np.float32, (h, w, 3)), (np.float32, (h, w, 3)), (np.float32, (h, w, 3))]
+        hi_kinds = [(np.int32, (H, W)), (np.float32, (H, W, 3)), (np.float32, (H, W, 3)), (np.float32, (H, W, 3))]
+        low = [None if a is None else np.ascontiguousarray(a, dtype=d).reshape(sh) for a, (d, sh) in zip(low, lo_kinds)]
+        high = [None if a is None else np.ascontiguousarray(a, dtype=d).reshape(sh) for a, (d, sh) in zip(high, hi_kinds)]
+        out = np.empty((H, W, 3), np.float32); cls = np.empty((H, W), np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and live else None
+        self._chk(self.L.ptk_upsample_planes(self.h, w, h, *(ptr(a) for a in low), W, H, *(ptr(a) for a in high), C.byref(prm), ptr(out),
+                                             ptr(cls)), "ptk_upsample_planes")
+        return out, cls
+
+    def upsample_frame(self, source: int = UPSAMPLE_ACCUM, params=None):
+        """ptk_upsample_frame: the context's frame - source UPSAMPLE_ACCUM (S1 / n), UPSAMPLE_DENOISED or UPSAMPLE_TEMPORAL - up to
+        the resolution of the last render_guides, guided by the feature planes and the guide planes MATERIAL, POSITION, NORMAL and
+        ALBEDO (read_upsampled); asynchronous.  params: UpsampleParams (upsample_defaults) or a dict of its fields."""
+        prm = _upsample_params(params)
+        self._chk(self.L.ptk_upsample_frame(self.h, int(source), C.byref(prm)), "ptk_upsample_frame")
+
+    def upsampled_device_ptr(self):
+        """(color pointer, class pointer, width, height): the last upsample_frame's result in device memory"""
+        a = C.c_void_p(); b = C.c_void_p(); w = C.c_int(0); h = C.c_int(0)
+        self._chk(self.L.ptk_upsampled_device_ptr(self.h, C.byref(a), C.byref(b), C.byref(w), C.byref(h)), "ptk_upsampled_device_ptr")
+        return a.value, b.value, w.value, h.value
+
+    def read_upsampled(self):
+        """(color [H][W][3] float32, class [H][W] int32) of the last upsample_frame, rows bottom-up; waits for the stream."""
+        _, _, w, h = self.upsampled_device_ptr()
+        color = np.empty((h, w, 3), dtype=np.float32)
+        cls = np.empty((h, w), dtype=np.int32)
+        self._chk(self.L.ptk_read_upsampled(self.h, color.ctypes.data, cls.ctypes.data), "ptk_read_upsampled")
+        return color, cls
+
+    def last_upsample_ms(self) -> dict:
+        """HIP-event times of the last upsample call: pack kernel, upsample kernel; waits for it."""
+        t = [C.c_float(0) for _ in range(2)]
+        self._chk(self.L.ptk_last_upsample_ms(self.h, *(C.byref(x) for x in t)), "ptk_last_upsample_ms")
+        return dict(zip(("pack_ms", "kernel_ms"), (x.value for x in t)))
 
     # ---- temporal reprojection ---------------------------------------------------------------
     def get_view(self) -> View:

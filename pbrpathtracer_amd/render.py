@@ -117,6 +117,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--adapt", type=float, default=None, metavar="A",
                     help="--display --orbit: the step toward the metered exposure per frame (default 1: no lag)")
     ap.add_argument("--linear-transfer", action="store_true", help="--display: encode linearly instead of with the sRGB transfer")
+    ap.add_argument("--upscale", type=float, default=None, metavar="S",
+                    help="trace the frame at 1/S of the scene file's resolution (adjusted to the same aspect ratio) and bring it up by "
+                         "guided upsampling; with --denoise the low frame is denoised first, with --display the full one is shown")
+    ap.add_argument("--fill-holes", type=int, default=None, metavar="SPP",
+                    help="--upscale: trace the pixels no low-resolution sample could serve with SPP samples each")
     ap.add_argument("--orbit", type=int, default=None, metavar="FRAMES",
                     help="turn the camera about the scene's centre in FRAMES steps, --spp samples after a reset at each; the image is the last view")
     ap.add_argument("--orbit-degrees", type=float, default=10.0, metavar="D", help="--orbit: the whole turn in degrees (default 10)")
@@ -400,6 +405,54 @@ def render_equirect(pt, a) -> int:
     return 0
 
 
+class _TracerRays:
+    """upscale.fill_holes' view of a PathTracer: trace_rays at the tracer's own seed and trace depth"""
+
+    def __init__(self, pt):
+        self.pt = pt
+
+    def trace_rays(self, origins, dirs, max_depth, first_sample, spp, seed, key_base=0):
+        return self.pt.TraceRays(origins, dirs, first_sample, spp, key_base=key_base)
+
+
+def render_upscaled(pt, a, export_png) -> int:
+    """--upscale: the frame traced at a low resolution, (denoised,) upsampled to the scene file's, (its holes traced,) (displayed)"""
+    from . import ptk, upscale
+    W, H = pt.GetResolution()
+    w, h = upscale.low_resolution(W, H, a.upscale)
+    pt.SetResolution((w, h))
+    low = np.zeros((h, w, 3), np.uint8)
+    pt.SetOutImage(low)
+    t1 = time.time()
+    pt.RenderFrames(a.spp)
+    if pt.LastError():
+        raise RuntimeError(pt.LastError())
+    if a.denoise:
+        pt.DenoiseFrame(denoise_params(pt, a))
+    pt.RenderGuides(W, H)
+    pt.UpsampleFrame(ptk.UPSAMPLE_DENOISED if a.denoise else ptk.UPSAMPLE_ACCUM)
+    color, cls = pt.ReadUpsampled()
+    t2 = time.time()
+    valid = pt.ReadGuide(ptk.FEAT_MATERIAL) >= 0
+    shares = upscale.class_shares(cls, valid)
+    filled = 0
+    if a.fill_holes:
+        color, info = upscale.fill_holes(_TracerRays(pt), color, cls, pt.context().guide_view(), a.fill_holes, pt.GetTraceDepth(), key_base=w * h)
+        filled = len(info["rows"])
+    if a.display:
+        out = pt.context().display_planes(color, display_params(a))
+    else:
+        out = resolve_mean(color, 1)
+    export_png(a.out, out)
+    if a.npy:
+        np.save(a.npy, color[::-1].copy())
+    print(f"{a.scene}: {pt.GetTriangleCount()} triangles, traced {w}x{h} at {a.spp} spp, shown {W}x{H} (x{W / w:.3g}): "
+          f"render + upsample {t2 - t1:.3f} s -> {a.out}")
+    print(f"upsample classes over the {int(valid.sum())} pixels that see the scene: bilinear {shares[0]:.4f}, wide ring {shares[1]:.4f}, "
+          f"holes {shares[2]:.4f}" + (f"; {filled} holes traced at {a.fill_holes} spp" if a.fill_holes else ""))
+    return 0
+
+
 def orbit_cameras(pt, frames: int, degrees: float):
     """(pos, dir, up) of the loaded camera turned about the vertical axis through the centre of the staged scene's bounds, after each
     of `frames` equal steps of degrees / frames"""
@@ -528,6 +581,19 @@ def main(argv=None):
                 raise ValueError
         except (ValueError, OverflowError):
             print("error: --exposure takes auto or a number of stops, --key a positive number, --adapt a number >= 0", file=sys.stderr)
+            return 1
+    if a.fill_holes is not None and (a.upscale is None or a.fill_holes < 1):
+        print("error: --fill-holes goes with --upscale and needs SPP >= 1", file=sys.stderr)
+        return 1
+    if a.upscale is not None:
+        if a.orbit is not None or a.noise_threshold is not None or a.bake_lightmap is not None or a.bake_probes is not None or \
+                a.distance_field is not None or a.equirect is not None or a.features:
+            print("error: --upscale renders one plain perspective frame", file=sys.stderr)
+            return 1
+        try:
+            return render_upscaled(pt, a, export_png)
+        except (RuntimeError, ValueError) as e:
+            print("error:", e, file=sys.stderr)
             return 1
     if a.orbit is not None:
         if a.orbit < 1 or a.noise_threshold is not None or a.bake_lightmap is not None or a.bake_probes is not None or \
