@@ -52,6 +52,7 @@
 // 1e-4 relative of the exact kernels' and no bias among those; the rest took another branch or texel) and to the mean image's
 // tolerance (tests/test_gpu_contract.py); and still reproducible bit for bit, whatever the work distribution, passes or tiles.
 // Each build has its own probe_math_kernel (ptk_probe_math follows the option).  (The header defaults PTK_CONTRACT to 0.)
+// A fourth time, through ptk_kernels_plain.hip, for the exact build's two PLAIN instantiations alone (PTK_PLAIN_UNIT, below the kernel).
 
 #include "ptk_device_fn.h"
 #include "ptk_flat_mt.h"
@@ -655,6 +656,24 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
     }
 }
 
+// The exact build's two PLAIN instantiations (generic level and LAMBERT) are emitted by a unit of their own, ptk_kernels_plain.hip:
+// this text once more under PTK_PLAIN_UNIT, which leaves only the kernel template and this launcher, compiled with
+// -mllvm -structurizecfg-skip-uniform-regions=1 (csrc/Makefile) so that the pass's wave-uniform class switch stays a branch tree whose
+// bodies jump straight to the accept chain (DESIGN 4.1 "The pass").  Every other kernel keeps the common command line.
+#if !PTK_CONTRACT
+void launch_trace_plain(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp);
+#endif
+#ifdef PTK_PLAIN_UNIT
+#if PTK_CONTRACT
+#error "the PLAIN unit belongs to the exact build: the contracted builds keep their PLAIN kernels in ptk_kernels.hip"
+#endif
+void launch_trace_plain(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp)
+{
+    if (lambert) hipLaunchKernelGGL((trace_kernel<false, true, true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    else hipLaunchKernelGGL((trace_kernel<false, true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+}
+#else
+
 // Probe of the arithmetic helpers as THIS build compiles them (op 0: rcp_ieee, 1: rcp_ieee_any, 2: sqrt_ieee, 3: inv_length,
 // the normalisation's factor, 4 / 5: sin / cos of sincos_2pi): the tests hold the exact build against the host's IEEE results
 // and the oracle, the contracted builds against float64 within their documented error.
@@ -733,13 +752,18 @@ void launch_trace(const RenderParams& p0, int num_subtiles, int resident_waves, 
 #if !PTK_CONTRACT
     if (stats && flat) hipLaunchKernelGGL((trace_kernel<true, true, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else if (stats) hipLaunchKernelGGL((trace_kernel<true, false, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    else if (flat && p.plain) launch_trace_plain(p.lambert != 0, blocks, stream, dp);      // (the unit built for the class switch, above)
     else
-#endif
+#else
     if (flat && p.plain && p.lambert) hipLaunchKernelGGL((trace_kernel<false, true, true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else if (flat && p.plain) hipLaunchKernelGGL((trace_kernel<false, true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
-    else if (flat) hipLaunchKernelGGL((trace_kernel<false, true, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    else
+#endif
+    if (flat) hipLaunchKernelGGL((trace_kernel<false, true, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else hipLaunchKernelGGL((trace_kernel<false, false, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
 }
+
+#endif  // !PTK_PLAIN_UNIT
 
 #if PTK_CONTRACT
 }  // namespace fma / fast
