@@ -1380,6 +1380,10 @@ int ptk_probe_unpack(ptk_ctx* ctx, int world, const float* host_packed /* all ra
  * test from which the operations on edge words stored as zeros are deleted (ptk_flat_zero_class); 0 makes its pass treat every
  * record as class 0, the full test.  Bit-identical either way (tests/test_gpu_flat_zero_classes.py); takes effect behind the
  * renders already queued.  The contracted builds ("contract" 1, 2) and every other kernel run the full test regardless.
+ * "flat_rect_pairs" = 0/1: the bit-exact PLAIN kernel is launched from a unit whose pass first tests the flat list's prefix of
+ * fan-split axis-aligned rectangles (ptk_flat_rect_pair) one pair of records at a time, sharing what their two tests have in
+ * common, and then the records behind it one by one; 0 launches the kernels without that loop.  Bit-identical either way
+ * (tests/test_gpu_flat_rect_pairs.py); takes effect behind the renders already queued.
  * No environment variable reaches the library. */
 int ptk_set_option(ptk_ctx* ctx, const char* name, double value);
 
@@ -1427,6 +1431,18 @@ int ptk_flat_zero_mask(int zero_class);
  * and after every geometry update), whatever "flat_zero_classes" says; out[k] = -1 for k >= the triangle count.  An error when
  * the scene has no flat list (more than 16 triangles, or the "device_build" option) */
 int ptk_flat_classes(ptk_ctx* ctx, int32_t out[16]);
+/* Fan-split axis-aligned rectangles of the flat list, no device needed: the kind, 1..6, of the pair of records rec_a, rec_b (each
+ * the nine stored words v0.xyz, e1.xyz, e2.xyz), or 0 when they are not such a pair.  A pair is a quad (p0, p1, p2, p3) stored as
+ * (p0, p1, p2), (p0, p2, p3) whose words are, bit for bit, A: e1 = a x_i, e2 = a x_i + b x_j; B: e1 = a x_i + b x_j, e2 = b x_j,
+ * with the same v0 and every other edge word comparing equal to 0.0f (-0 counts); kind = 1 + 2 p + s for the plane's normal
+ * axis p and i = (p + 1 + s) % 3.  One ulp of difference in any compared word, or a NaN in one, gives 0.  For such a pair the
+ * triangle test's determinant and distance are the same operations on the same bits for both records, so the exact PLAIN kernel
+ * may test them together ("flat_rect_pairs") without changing any hit or any bit of a distance. */
+int ptk_flat_rect_pair(const float rec_a[9], const float rec_b[9]);
+/* the pairs the device holds for the uploaded scene, as classified there from the records (after ptk_upload_scene and after every
+ * geometry update), whatever "flat_rect_pairs" says: *num_pairs = m, the length of the longest prefix 0 .. 2m-1 of the list in
+ * which records 2k, 2k+1 are pairs, out[k] = the kind of pair k < m, 0 for k >= m.  Errors as for ptk_flat_classes */
+int ptk_flat_rect_pairs(ptk_ctx* ctx, int32_t out[8], int32_t* num_pairs /* may be NULL */);
 int ptk_kernel_log_read(ptk_ctx* ctx, float* trace_ms, int max_entries, int* num_entries);
 int ptk_collect_stats(ptk_ctx* ctx, uint32_t first_sample, uint32_t spp_count, uint64_t seed, ptk_stats* out);
 int ptk_bvh_info(ptk_ctx* ctx, int32_t* num_nodes, int32_t* depth /* wide nodes on the longest chain */, int32_t* num_leaf_tris);

@@ -256,6 +256,7 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
     if (const int rc = use_primary_cache(c, p); rc != PTK_OK) return rc;
     // decided per render from the staged state: a material edit, a new scene or an opened aperture since the last one is seen here
     p.plain = (c->opt_plain_kernel && c->scene_plain && p.flat_count > 0 && p.primary_hit != nullptr) ? 1 : 0;
+    if (p.plain && c->opt_flat_rect_pairs) p.plain = 2;        // the exact build's pair-pass unit (launch_trace; the contracted builds have none)
     p.lambert = (p.plain && c->opt_lambert_kernel && c->scene_lambert) ? 1 : 0;
     if (!c->pixel_rng_valid || c->pixel_rng_seed != seed)
     {
@@ -895,7 +896,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
         if (c->d_flat_tris)                             // the frame table behind the flat records, from the normals just written
         {
             launch_flat_frames(c->d_shade, c->d_flat_tris, 0, n, c->stream);
-            launch_flat_classes(c->d_flat_tris, n, c->opt_flat_zero_classes, c->stream);     // ... and the class table, from the records
+            launch_flat_classes(c->d_flat_tris, n, c->opt_flat_zero_classes, c->opt_flat_rect_pairs, c->stream);     // ... and the class table and the pair word, from the records
             HIPCHK(c, hipGetLastError());
         }
         HIPCHK(c, up((void**)&c->d_verts_res, s->verts, (size_t)n * 9 * sizeof(float)));
@@ -1001,6 +1002,25 @@ int ptk_flat_classes(ptk_ctx* c, int32_t out[16])
     HIPCHK(c, hipMemcpyAsync(&word, (const char*)(c->d_flat_tris + FLAT_CLASSES_AT) + 8, sizeof(word), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < FLAT_MAX_TRIS; k++) out[k] = k < c->num_tris ? (int32_t)((word >> (k * 4)) & 15ull) : -1;
+    return PTK_OK;
+}
+
+int ptk_flat_rect_pair(const float rec_a[9], const float rec_b[9])
+{
+    return rec_a && rec_b ? ptk_mt::flat_rect_pair(rec_a, rec_b) : 0;          // the function classify_flat_kernel calls
+}
+
+int ptk_flat_rect_pairs(ptk_ctx* c, int32_t out[8], int32_t* num_pairs)
+{
+    if (!c || !out) return PTK_ERR_BAD_ARG;
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (!c->d_flat_tris) return fail(c, PTK_ERR_BAD_ARG, "the scene has no flat triangle list (more than 16 triangles, or built on the device)");
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long word = 0ull;
+    HIPCHK(c, hipMemcpyAsync(&word, (const char*)(c->d_flat_tris + FLAT_PAIRS_AT) + 8, sizeof(word), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < FLAT_MAX_TRIS / 2; k++) out[k] = (int32_t)((word >> (k * 4)) & 15ull);
+    if (num_pairs) *num_pairs = (int32_t)((word >> 32) & 15ull);
     return PTK_OK;
 }
 
@@ -1791,11 +1811,25 @@ int ptk_set_option(ptk_ctx* c, const char* name, double value)
         {
             // the word the pass reads is rewritten behind every render already queued and ahead of every later one, like a geometry update
             HIPCHK(c, hipSetDevice(c->device));
-            launch_flat_classes(c->d_flat_tris, c->num_tris, use, c->stream);
+            launch_flat_classes(c->d_flat_tris, c->num_tris, use, c->opt_flat_rect_pairs, c->stream);
             HIPCHK(c, hipGetLastError());
             c->inputs_dirty = true;
         }
         c->opt_flat_zero_classes = use;
+        return PTK_OK;
+    }
+    if (!std::strcmp(name, "flat_rect_pairs"))
+    {
+        const int use = value != 0.0 ? 1 : 0;
+        if (use != c->opt_flat_rect_pairs && c->have_scene && c->d_flat_tris)
+        {
+            // (the word the pair pass reads, rewritten stream-ordered like the class word above)
+            HIPCHK(c, hipSetDevice(c->device));
+            launch_flat_classes(c->d_flat_tris, c->num_tris, c->opt_flat_zero_classes, use, c->stream);
+            HIPCHK(c, hipGetLastError());
+            c->inputs_dirty = true;
+        }
+        c->opt_flat_rect_pairs = use;
         return PTK_OK;
     }
     if (!std::strcmp(name, "device_build"))

@@ -148,7 +148,7 @@ static int update_geometry(ptk_ctx* c, int32_t first, int32_t count, const float
     launch_repack_geometry(sv, sn, st, first, count, c->d_verts_res, c->d_tri_pos, c->d_tris, c->d_flat_tris, c->d_shade, c->stream);
     launch_repack_lights(c->d_verts_res, first, count, c->d_lights, c->num_lights, c->stream);
     if (c->d_flat_tris && sn) launch_flat_frames(c->d_shade, c->d_flat_tris, first, count, c->stream);     // (vertices only: the normals stay)
-    if (c->d_flat_tris) launch_flat_classes(c->d_flat_tris, c->num_tris, c->opt_flat_zero_classes, c->stream);   // the records' new zero words
+    if (c->d_flat_tris) launch_flat_classes(c->d_flat_tris, c->num_tris, c->opt_flat_zero_classes, c->opt_flat_rect_pairs, c->stream);   // the records' new zero words and pairs
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_geo_t[3], c->stream));
     c->bvh_pad = 1e-5f * std::max(vmax, 1.0f);

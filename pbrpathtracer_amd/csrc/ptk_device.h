@@ -38,7 +38,12 @@ constexpr int FLAT_FRAME_F4 = 4;                            // per triangle
 // first word is what the exact PLAIN pass reads - all zero, "general", while the flat_zero_classes option is off - the second
 // the classification itself (ptk_flat_classes).  The allocation always reaches this far.
 constexpr int FLAT_CLASSES_AT = FLAT_FRAMES_AT + FLAT_MAX_TRIS * FLAT_FRAME_F4;
-constexpr int FLAT_TABLE_F4 = FLAT_CLASSES_AT + 1;           // the whole allocation
+// ... and behind it the pair word (ptk_flat_mt.h flat_rect_pair): for the longest prefix 0 .. 2m-1 of the list whose records 2k, 2k+1
+// are fan-split axis-aligned rectangles, the kind (1..6) of pair k in bits 4k..4k+3 and m in bits 32..35 of a 64-bit word; nibbles
+// behind the prefix are zero.  Again two words: the first is what the pair pass reads (csrc/ptk_kernels_rect.hip) - zero, "no
+// pairs", while the flat_rect_pairs option is off - the second the classification itself (ptk_flat_rect_pairs).
+constexpr int FLAT_PAIRS_AT = FLAT_CLASSES_AT + 1;
+constexpr int FLAT_TABLE_F4 = FLAT_PAIRS_AT + 1;             // the whole allocation
 
 // Shading record, 112 B, indexed by the scene's triangle index (fetched only for the accepted hit):
 //   s0 = (normal.xyz, bits (material | smoothing << 31))
@@ -115,7 +120,8 @@ struct RenderParams {
     float resolve_samples;      // (float)(first_sample + spp) = (float)mSamples
     int plain;                  // 1: launch_trace takes the PLAIN variant of the FLAT kernel - a host-side promise (ptk_api.hip plain_scene +
                                 // primary-hit cache) that every material is opaque and untextured, no triangle is smoothed or has an
-                                // opacity texture and primary_hit is set; no kernel reads it (last field: the others keep their offsets)
+                                // opacity texture and primary_hit is set; no kernel reads it (last field: the others keep their offsets).
+                                // 2: ... and the exact build launches the pair-pass unit's kernels (the flat_rect_pairs option)
     int lambert;                // 1 (only with plain): ... and no material has reflectiveness > 0 (ptk_api.hip lambert_tables), so launch_trace
                                 // takes the LAMBERT level of the PLAIN kernel; no kernel reads it either (behind plain: same offsets again)
 };
@@ -169,8 +175,9 @@ void launch_pack_owned(const float* accum, float* packed, int width, int height,
 void launch_unpack_all(const float* packed, const long long* bases, float* image, int width, int height, int world, hipStream_t stream);
 // the frame table behind d_flat_tris for triangles [first, first + count), from their shading records' normals (sample_basis, the exact build's)
 void launch_flat_frames(const float4* d_shade, float4* d_flat_tris, int first, int count, hipStream_t stream);
-// the class table behind d_flat_tris, from all num_tris records as they stand on the stream; use = 0: the pass's word is all general
-void launch_flat_classes(float4* d_flat_tris, int num_tris, int use, hipStream_t stream);
+// the class table and the pair word behind d_flat_tris, from all num_tris records as they stand on the stream; use = 0: the pass's
+// class word is all general, use_pairs = 0: its pair word says "no pairs"
+void launch_flat_classes(float4* d_flat_tris, int num_tris, int use, int use_pairs, hipStream_t stream);
 void launch_primary(const PrimaryParams& p, hipStream_t stream);
 void launch_primary_hits(const RenderParams& p, float4* out, float4* out_rd, hipStream_t stream);
 void launch_probe(const ProbeParams& p, hipStream_t stream);

@@ -103,4 +103,62 @@ PTK_MT_HD bool mt_accept(float a, float u, float v, float uv, float t, float eps
     return !(__builtin_fabsf(a) < eps) & !(u < 0.0f) & !(v < 0.0f) & !(uv > 1.0f) & (t > eps);
 }
 
+// ---- fan-split axis-aligned rectangles: records 2k, 2k + 1 tested as one pair (exact PLAIN pass, csrc/ptk_kernels_rect.hip) ------------
+// A quad (p0, p1, p2, p3) split as the fan (p0, p1, p2), (p0, p2, p3) stores two records A, B with the same v0 and e1(B) = e2(A).
+// When it is a rectangle in an axis plane (normal axis p, in-plane axes i, j) the stored words are
+//   A: e1 = alpha x_i, e2 = alpha x_i + beta x_j        B: e1 = alpha x_i + beta x_j, e2 = beta x_j        every other word a zero
+// and when the four alphas and the four betas are the same BITS, Moeller-Trumbore's s, its determinant a (hence f = 1 / a), and t
+// are the same operations on the same operand bits for A and B (the pair lemma).  The kind of a pair names p and i:
+// kind = 1 + 2 p + s, i = (p + 1 + s) % 3, j = (p + 2 - s) % 3; 0 = no pair.
+constexpr int FLAT_RECT_KINDS = 6;
+constexpr int rect_plane(int kind) { return (kind - 1) >> 1; }
+constexpr int rect_axis_i(int kind) { return (rect_plane(kind) + 1 + ((kind - 1) & 1)) % 3; }
+constexpr int rect_axis_j(int kind) { return (rect_plane(kind) + 2 - ((kind - 1) & 1)) % 3; }
+// the zero masks of the two records of a pair (both are built classes: plane bits and one more word)
+constexpr unsigned rect_mask_a(int kind) { return (9u << rect_plane(kind)) | 1u << rect_axis_j(kind); }
+constexpr unsigned rect_mask_b(int kind) { return (9u << rect_plane(kind)) | 8u << rect_axis_i(kind); }
+
+PTK_MT_HD uint32_t mt_bits(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
+// the same bits and not a NaN
+PTK_MT_HD bool mt_same_word(float x, float y) { return mt_bits(x) == mt_bits(y) && x == y; }
+
+// The kind of the pair (recA, recB), each a record's nine stored words v0.xyz, e1.xyz, e2.xyz; 0 when they are not one.  Zeros
+// compare equal to 0.0f (-0 counts, as for the classes); everything else is compared bit by bit, so one ulp anywhere, or a NaN,
+// means no pair.  The first kind that fits (two fit only when alpha or beta is itself a zero).
+PTK_MT_HD int flat_rect_pair(const float recA[9], const float recB[9])
+{
+    for (int k = 0; k < 3; k++) if (!mt_same_word(recA[k], recB[k])) return 0;
+    const float* e1a = recA + 3; const float* e2a = recA + 6; const float* e1b = recB + 3; const float* e2b = recB + 6;
+    for (int kind = 1; kind <= FLAT_RECT_KINDS; kind++)
+    {
+        const int p = rect_plane(kind), i = rect_axis_i(kind), j = rect_axis_j(kind);
+        const bool zeros = e1a[p] == 0.0f && e1a[j] == 0.0f && e2a[p] == 0.0f && e1b[p] == 0.0f && e2b[p] == 0.0f && e2b[i] == 0.0f;
+        const bool same = mt_same_word(e1a[i], e2a[i]) && mt_same_word(e1b[i], e2a[i]) && mt_same_word(e1b[j], e2a[j]) && mt_same_word(e2b[j], e2a[j]);
+        if (zeros && same) return kind;
+    }
+    return 0;
+}
+
+// a, u, v, t of both rays against both records of a pair of kind KIND.  The existing arithmetic twice, under the two records' zero
+// masks, with every word of B - and A's alpha - NAMED as the word of e2(A) it is bitwise equal to: nothing is shared by hand, the
+// compiler's common-subexpression elimination finds s, two h products, a, f, two q products and t of B among A's values.
+template <int KIND, class F2, class Rcp>
+PTK_MT_HD void mt_rect_pair(const F2 dx, const F2 dy, const F2 dz, float rox, float roy, float roz, float v0x, float v0y, float v0z,
+                            float e2x, float e2y, float e2z, Rcp rcp, F2& aA, F2& uA, F2& vA, F2& tA, F2& aB, F2& uB, F2& vB, F2& tB)
+{
+    static_assert(KIND >= 1 && KIND <= FLAT_RECT_KINDS, "kinds are 1..6");
+    mt_pair<rect_mask_a(KIND)>(dx, dy, dz, rox, roy, roz, v0x, v0y, v0z, e2x, e2y, e2z, e2x, e2y, e2z, rcp, aA, uA, vA, tA);
+    mt_pair<rect_mask_b(KIND)>(dx, dy, dz, rox, roy, roz, v0x, v0y, v0z, e2x, e2y, e2z, e2x, e2y, e2z, rcp, aB, uB, vB, tB);
+}
+
+// The accept decisions of the pair for one ray, in the pass's sequential order (A, then B against the best A may have left), from
+// A's a and t, which are B's: X = |a| >= eps, t > eps, t < best is one value for both; an accepted A makes best.t = t, so B's
+// t < best fails, and a rejected A leaves best where it was.  NaN directions make a and t NaN and reject through X.
+PTK_MT_HD void mt_rect_accept(float a, float t, float uA, float vA, float uvA, float uB, float vB, float uvB, float best_t, float eps, bool& okA, bool& okB)
+{
+    const bool X = !(__builtin_fabsf(a) < eps) & (t > eps) & (t < best_t);
+    okA = X & !(uA < 0.0f) & !(vA < 0.0f) & !(uvA > 1.0f);
+    okB = X & !(uB < 0.0f) & !(vB < 0.0f) & !(uvB > 1.0f) & !okA;
+}
+
 }  // namespace ptk_mt

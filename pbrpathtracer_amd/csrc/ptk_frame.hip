@@ -35,28 +35,55 @@ void launch_flat_frames(const float4* d_shade, float4* d_flat_tris, int first, i
 // The class table behind the frame table (ptk_device.h FLAT_CLASSES_AT): lane k classifies record k by its six stored edge words
 // (ptk_flat_mt.h flat_zero_class, the rule ptk_flat_zero_class exports), lane 0 gathers the nibbles and writes both words.
 // One wave; classifies all records anew, whichever of them changed.
-__global__ __launch_bounds__(64) void classify_flat_kernel(float4* __restrict__ flat_tris, int num_tris, int use)
+// The pair word behind it (FLAT_PAIRS_AT): lane k < 8 takes records 2k, 2k + 1 to ptk_flat_mt.h flat_rect_pair (the rule
+// ptk_flat_rect_pair exports); lane 0 keeps the kinds of the longest prefix of pairs and its length.
+__global__ __launch_bounds__(64) void classify_flat_kernel(float4* __restrict__ flat_tris, int num_tris, int use, int use_pairs)
 {
     const int k = threadIdx.x;
-    int cls = 0;
+    int cls = 0, kind = 0;
     if (k < num_tris && k < FLAT_MAX_TRIS)
     {
         const float4 t0 = flat_tris[k * TRI_F4], t1 = flat_tris[k * TRI_F4 + 1], t2 = flat_tris[k * TRI_F4 + 2];
         const float e[6] = { t0.w, t1.x, t1.y, t1.z, t1.w, t2.x };
         cls = ptk_mt::flat_zero_class(e);
     }
-    unsigned long long word = 0ull;
+    if (2 * k + 1 < num_tris && 2 * k + 1 < FLAT_MAX_TRIS)
+    {
+        float rec[2][9];
+        int index[2];
+        for (int r = 0; r < 2; r++)
+        {
+            const float4* q = flat_tris + (2 * k + r) * TRI_F4;
+            const float4 t0 = q[0], t1 = q[1], t2 = q[2];
+            rec[r][0] = t0.x; rec[r][1] = t0.y; rec[r][2] = t0.z; rec[r][3] = t0.w; rec[r][4] = t1.x; rec[r][5] = t1.y;
+            rec[r][6] = t1.z; rec[r][7] = t1.w; rec[r][8] = t2.x;
+            index[r] = __float_as_int(t2.y);
+        }
+        // (the pair pass takes B's triangle index to be A's + 1, as the flat list's order has it)
+        kind = index[1] == index[0] + 1 ? ptk_mt::flat_rect_pair(rec[0], rec[1]) : 0;
+    }
+    unsigned long long word = 0ull, pairs = 0ull;
     for (int j = 0; j < FLAT_MAX_TRIS; j++) word |= (unsigned long long)(__shfl(cls, j) & 15) << (j * 4);
+    int m = 0;
+    for (int j = 0; j < FLAT_MAX_TRIS / 2; j++)
+    {
+        const int kj = __shfl(kind, j);
+        if (m == j && kj != 0) { pairs |= (unsigned long long)kj << (j * 4); m = j + 1; }
+    }
+    pairs |= (unsigned long long)m << 32;
     if (k == 0)
     {
         unsigned long long* out = (unsigned long long*)(flat_tris + FLAT_CLASSES_AT);
         out[0] = use ? word : 0ull;
         out[1] = word;
+        unsigned long long* outp = (unsigned long long*)(flat_tris + FLAT_PAIRS_AT);
+        outp[0] = use_pairs ? pairs : 0ull;
+        outp[1] = pairs;
     }
 }
-void launch_flat_classes(float4* d_flat_tris, int num_tris, int use, hipStream_t stream)
+void launch_flat_classes(float4* d_flat_tris, int num_tris, int use, int use_pairs, hipStream_t stream)
 {
-    hipLaunchKernelGGL(classify_flat_kernel, dim3(1), dim3(64), 0, stream, d_flat_tris, num_tris, use);
+    hipLaunchKernelGGL(classify_flat_kernel, dim3(1), dim3(64), 0, stream, d_flat_tris, num_tris, use, use_pairs);
 }
 
 // Streaming fold of the sample buffer into the float accumulator, strictly in sample order

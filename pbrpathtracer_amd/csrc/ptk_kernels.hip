@@ -52,7 +52,8 @@
 // 1e-4 relative of the exact kernels' and no bias among those; the rest took another branch or texel) and to the mean image's
 // tolerance (tests/test_gpu_contract.py); and still reproducible bit for bit, whatever the work distribution, passes or tiles.
 // Each build has its own probe_math_kernel (ptk_probe_math follows the option).  (The header defaults PTK_CONTRACT to 0.)
-// A fourth time, through ptk_kernels_plain.hip, for the exact build's two PLAIN instantiations alone (PTK_PLAIN_UNIT, below the kernel).
+// A fourth time, through ptk_kernels_plain.hip, for the exact build's two PLAIN instantiations alone (PTK_PLAIN_UNIT, below the kernel),
+// and a fifth, through ptk_kernels_rect.hip, for the same two with the pair pass in front of the record loop (PTK_RECT_UNIT).
 
 #include "ptk_device_fn.h"
 #include "ptk_flat_mt.h"
@@ -137,6 +138,32 @@ __device__ __forceinline__ bool tri_accept_pair(const PT& P, Walk& W, Walk& WS, 
     if (oks) { WS.best.tri = tri; WS.best.t = t.y; WS.best.u = u.y; WS.best.v = v.y; asm volatile("" : "+v"(WS.best.t), "+v"(WS.best.u), "+v"(WS.best.v)); }
     return oks & (tri != WS.occl_tri);
 }
+
+#ifdef PTK_RECT_UNIT
+// The pair pass of ptk_kernels_rect.hip: both records of a fan-split axis-aligned rectangle of kind KIND from v0 and e2 of the first
+// (ptk_flat_mt.h mt_rect_pair: the same arithmetic, B's words named as A's, the sharing left to the compiler) ...
+template <int KIND>
+__device__ __forceinline__ void tri_math_rect(const Walk& W, const RayPair& R, float v0x, float v0y, float v0z, float e2x, float e2y, float e2z,
+                                              f2& aA, f2& uA, f2& vA, f2& tA, f2& aB, f2& uB, f2& vB, f2& tB)
+{
+    ptk_mt::mt_rect_pair<KIND>(R.dx, R.dy, R.dz, W.ro.x, W.ro.y, W.ro.z, v0x, v0y, v0z, e2x, e2y, e2z,
+                               [](const f2& x) { return f2{ rcp_ieee(x.x), rcp_ieee(x.y) }; }, aA, uA, vA, tA, aB, uB, vB, tB);
+}
+// ... and tri_accept_pair for the two of them in turn (PLAIN: no opacity), with the tests on a and t, which the records share, taken once
+__device__ __forceinline__ void tri_accept_rect(Walk& W, Walk& WS, const bool shadow_live, const f2 a, const f2 t, const f2 uA, const f2 vA,
+                                                const f2 uB, const f2 vB, const int triA, const int triB)
+{
+    const f2 uvA = uA + vA, uvB = uB + vB;
+    bool okbA, okbB, oksA, oksB;
+    ptk_mt::mt_rect_accept(a.x, t.x, uA.x, vA.x, uvA.x, uB.x, vB.x, uvB.x, W.best.t, PTK_EPS, okbA, okbB);
+    ptk_mt::mt_rect_accept(a.y, t.y, uA.y, vA.y, uvA.y, uB.y, vB.y, uvB.y, WS.best.t, PTK_EPS, oksA, oksB);
+    oksA = oksA & shadow_live; oksB = oksB & shadow_live;
+    if (okbA) { W.best.tri = triA; W.best.t = t.x; W.best.u = uA.x; W.best.v = vA.x; asm volatile("" : "+v"(W.best.t), "+v"(W.best.u), "+v"(W.best.v)); }
+    if (okbB) { W.best.tri = triB; W.best.t = t.x; W.best.u = uB.x; W.best.v = vB.x; asm volatile("" : "+v"(W.best.t), "+v"(W.best.u), "+v"(W.best.v)); }
+    if (oksA) { WS.best.tri = triA; WS.best.t = t.y; WS.best.u = uA.y; WS.best.v = vA.y; asm volatile("" : "+v"(WS.best.t), "+v"(WS.best.u), "+v"(WS.best.v)); }
+    if (oksB) { WS.best.tri = triB; WS.best.t = t.y; WS.best.u = uB.y; WS.best.v = vB.y; asm volatile("" : "+v"(WS.best.t), "+v"(WS.best.u), "+v"(WS.best.v)); }
+}
+#endif
 
 template <bool STATS, bool PLAIN, class PT>
 __device__ __forceinline__ bool tri_test_pair(const PT& P, Walk& W, Walk& WS, const RayPair& R, const bool shadow_live, float4 t0, float4 t1,
@@ -469,7 +496,33 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
                     constexpr bool ZERO_CLASSES = PLAIN && !STATS && !PTK_CONTRACT;
                     typedef const __attribute__((address_space(4))) unsigned long long* cu64;
                     const unsigned long long classes = ZERO_CLASSES ? *(cu64)(uintptr_t)(P.flat_tris + FLAT_CLASSES_AT) : 0ull;
+#ifdef PTK_RECT_UNIT
+                    // The pair pass (this unit only): the list's prefix of fan-split axis-aligned rectangles, one pair of records per
+                    // turn of a counted loop - one wave-uniform switch over the six kinds, the arithmetic of both records with B's
+                    // words named as A's (ptk_flat_mt.h mt_rect_pair), one shared accept, the hit moves (the pair lemma).
+                    // Only a prefix is paired, so the order stays ascending; the loop below goes on from record 2m.
+                    static_assert(ZERO_CLASSES, "the pair unit holds the exact PLAIN kernels only");
+                    const unsigned long long pairs = *(cu64)(uintptr_t)(P.flat_tris + FLAT_PAIRS_AT);
+                    const int n_pairs = (int)(pairs >> 32) & 15;
+                    for (int j = 0; j < n_pairs; j++)
+                    {
+                        // of the pair's six float4s, record A's three: v0, e2 (e1(A), e1(B), e2(B) are words of e2(A) or zeros) and the index,
+                        // which B's follows (the classifier pairs no other records)
+                        const f4v a0 = ct[j * 2 * TRI_F4], a1 = ct[j * 2 * TRI_F4 + 1], a2 = ct[j * 2 * TRI_F4 + 2];
+                        f2 aA, uA, vA, tA, aB, uB, vB, tB;
+#define PTK_RECT_KIND(c) tri_math_rect<c>(W, R, a0.x, a0.y, a0.z, a1.z, a1.w, a2.x, aA, uA, vA, tA, aB, uB, vB, tB); break;
+                        switch ((unsigned)(pairs >> (j * 4)) & 15u)
+                        {
+                            case 1: PTK_RECT_KIND(1) case 2: PTK_RECT_KIND(2) case 3: PTK_RECT_KIND(3) case 4: PTK_RECT_KIND(4) case 5: PTK_RECT_KIND(5)
+                            default: PTK_RECT_KIND(6)           // (the classifier writes 1..6 inside the prefix)
+                        }
+#undef PTK_RECT_KIND
+                        tri_accept_rect(W, WS, shadow, aA, tA, uA, vA, uB, vB, __float_as_int(a2.y), __float_as_int(a2.y) + 1);
+                    }
+                    for (int k = n_pairs * 2; k < P.flat_count; k++)
+#else
                     for (int k = 0; k < P.flat_count; k++)
+#endif
                     {
                         const f4v a0 = ct[k * TRI_F4], a1 = ct[k * TRI_F4 + 1], a2 = ct[k * TRI_F4 + 2];
                         const float4 t0 = make_float4(a0.x, a0.y, a0.z, a0.w), t1 = make_float4(a1.x, a1.y, a1.z, a1.w),
@@ -662,12 +715,19 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
 // bodies jump straight to the accept chain (DESIGN 4.1 "The pass").  Every other kernel keeps the common command line.
 #if !PTK_CONTRACT
 void launch_trace_plain(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp);
+// ... and once more by ptk_kernels_rect.hip (PTK_RECT_UNIT on top of PTK_PLAIN_UNIT, the same flags): the same two instantiations under
+// the name trace_kernel_rect, whose pass tests the list's prefix of fan-split rectangles pair by pair (RenderParams::plain == 2)
+void launch_trace_rect(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp);
 #endif
 #ifdef PTK_PLAIN_UNIT
 #if PTK_CONTRACT
 #error "the PLAIN unit belongs to the exact build: the contracted builds keep their PLAIN kernels in ptk_kernels.hip"
 #endif
+#ifdef PTK_RECT_UNIT
+void launch_trace_rect(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp)
+#else
 void launch_trace_plain(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp)
+#endif
 {
     if (lambert) hipLaunchKernelGGL((trace_kernel<false, true, true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else hipLaunchKernelGGL((trace_kernel<false, true, true>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
@@ -752,6 +812,7 @@ void launch_trace(const RenderParams& p0, int num_subtiles, int resident_waves, 
 #if !PTK_CONTRACT
     if (stats && flat) hipLaunchKernelGGL((trace_kernel<true, true, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else if (stats) hipLaunchKernelGGL((trace_kernel<true, false, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    else if (flat && p.plain == 2) launch_trace_rect(p.lambert != 0, blocks, stream, dp);  // (the pair-pass unit: the flat_rect_pairs option)
     else if (flat && p.plain) launch_trace_plain(p.lambert != 0, blocks, stream, dp);      // (the unit built for the class switch, above)
     else
 #else

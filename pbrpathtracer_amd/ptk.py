@@ -163,7 +163,7 @@ SYMBOLS = [
     "ptk_bind_out_image", "ptk_bind_out_device", "ptk_bind_gl_buffer", "ptk_comm_info", "ptk_kernel_log", "ptk_kernel_log_read",
     "ptk_debug_stall_exchange", "ptk_render_adaptive", "ptk_read_sample_counts", "ptk_read_moments",
     "ptk_trace_variant", "ptk_scene_is_plain", "ptk_scene_is_lambert", "ptk_trace_is_lambert",
-    "ptk_flat_zero_class", "ptk_flat_zero_mask", "ptk_flat_classes",
+    "ptk_flat_zero_class", "ptk_flat_zero_mask", "ptk_flat_classes", "ptk_flat_rect_pair", "ptk_flat_rect_pairs",
     "ptk_feature_info", "ptk_render_features", "ptk_read_feature", "ptk_feature_device_ptr", "ptk_pick",
     "ptk_update_geometry", "ptk_update_geometry_device", "ptk_geometry_info", "ptk_geometry_timing",
     "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
@@ -354,6 +354,8 @@ def _load_locked() -> C.CDLL:
         L.ptk_flat_zero_class.argtypes = [C.POINTER(C.c_float)]
         L.ptk_flat_zero_mask.argtypes = [C.c_int]
         L.ptk_flat_classes.argtypes = [vp, C.POINTER(i32)]
+        L.ptk_flat_rect_pair.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.ptk_flat_rect_pairs.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     except AttributeError:
         if LIB_PATH.endswith("libptk.so"):      # (an older build loaded through PTK_DEV_TOOLS for an A/B may lack the newest entry points)
             raise
@@ -537,6 +539,28 @@ def flat_zero_class(v1, v2, v3) -> int:
     v1, v2, v3 = (np.asarray(v, np.float32) for v in (v1, v2, v3))
     e = np.concatenate([v2 - v1, v3 - v1]).astype(np.float32)
     return int(load().ptk_flat_zero_class((C.c_float * 6)(*e.tolist())))
+
+
+def flat_rect_pair(tri_a, tri_b) -> int:
+    """ptk_flat_rect_pair of the records the packers store for two triangles (each three vertices): 1..6, or 0 for no pair (no device needed)."""
+    recs = []
+    for t in (tri_a, tri_b):
+        v1, v2, v3 = (np.asarray(v, np.float32) for v in t)
+        recs.append(np.concatenate([v1, v2 - v1, v3 - v1]).astype(np.float32))
+    return int(load().ptk_flat_rect_pair((C.c_float * 9)(*recs[0].tolist()), (C.c_float * 9)(*recs[1].tolist())))
+
+
+def flat_rect_prefix(verts) -> list:
+    """The kinds of the pair prefix of a flat list ([n, 9] vertices in triangle order) by the rule the device applies
+    (classify_flat_kernel): pairs of records 2k, 2k + 1 from the front for as long as ptk_flat_rect_pair holds (no device needed)."""
+    v = np.asarray(verts, np.float32).reshape(-1, 3, 3)
+    kinds = []
+    for k in range(0, min(len(v), 16) - 1, 2):
+        kind = flat_rect_pair(v[k], v[k + 1])
+        if kind == 0:
+            break
+        kinds.append(kind)
+    return kinds
 
 
 def flat_zero_mask(zero_class: int) -> int:
@@ -1721,6 +1745,13 @@ class Context:
         out = (C.c_int32 * 16)()
         self._chk(self.L.ptk_flat_classes(self.h, out), "ptk_flat_classes")
         return [int(v) for v in out if v >= 0]
+
+    def flat_rect_pairs(self) -> list:
+        """The kinds (1..6) of the device's pair prefix of the flat list: entry k is the pair of records 2k, 2k + 1; [] when record 0, 1 are no pair."""
+        out = (C.c_int32 * 8)()
+        m = C.c_int32(0)
+        self._chk(self.L.ptk_flat_rect_pairs(self.h, out, C.byref(m)), "ptk_flat_rect_pairs")
+        return [int(out[k]) for k in range(m.value)]
 
     def set_option(self, name: str, value: float):
         self._chk(self.L.ptk_set_option(self.h, name.encode(), float(value)), "ptk_set_option")

@@ -11,7 +11,8 @@ starts - followed by interpreting the scalar compares, flag moves and flag tests
 conditional branches (and how many are taken), unconditional branches, flag-test hops (an s_cbranch_vcc* fed by
 s_andn2_b64 / s_and_b64 vcc, exec, <flag>) and VALU; with a class list, the sums over it (one pass of a scene with those records).
 Also checks the kernel's control flow: every s_and_saveexec_b64 is closed by an s_or_b64 exec on every route (check_exec_regions)
-and lists the natural loops with their back edges and exits (loops)."""
+and lists the natural loops with their back edges and exits (loops).  On a kernel of the pair unit (csrc/ptk_kernels_rect.hip) the
+pair loop in front of the record loop is walked the same way, per kind 1..6 (pair_header, route_table(K, pair_header(K), range(1, 7)))."""
 import re, sys
 HALF = re.compile(r"^v_(cmp|cmpx|cndmask|min|max|med3|cvt|bfe|perm|and_or|mad_u32|mul_lo|mul_hi|lshl_add|lshl_or|add_lshl|div_|pk_|bfi|alignbit|sad|mad_i32|mad_u64|add3|xad|or3|readlane|readfirstlane|writelane|ldexp|frexp|fract|trunc|floor|rndne|ceil)")
 TRANS = re.compile(r"^v_(rcp|sqrt|rsq|exp|log|sin|cos)")
@@ -97,23 +98,39 @@ def _sregs(o):
     return [o] if re.match(r"^(s\d+|vcc|vcc_lo|vcc_hi|exec)$", o) else []
 
 
-def pass_header(K):
-    """index of the pass loop's first instruction and the register that receives the class nibble"""
+def nibble_headers(K):
+    """every loop that extracts a nibble per turn (s_lshr_b64 + s_and_b32 ..., 15), in program order: (index of the loop's first
+    instruction, index of the extraction, the register that receives the nibble)"""
+    out = []
     for i, (_, op, ops) in enumerate(K.ins):
         if op == "s_and_b32" and len(ops) == 3 and ops[2] == "15" and i > 0 and K.ins[i - 1][1] == "s_lshr_b64":
-            h = max(v for v in K.label.values() if v <= i)
-            return h, i, ops[0]
-    raise AssertionError("no class extraction (s_lshr_b64 + s_and_b32 ..., 15) in " + K.name)
+            out.append((max(v for v in K.label.values() if v <= i), i, ops[0]))
+    return out
+
+
+def pass_header(K):
+    """index of the record loop's first instruction and the register that receives the class nibble (the last such loop of the
+    kernel: in the pair unit, csrc/ptk_kernels_rect.hip, the pair loop stands in front of it)"""
+    hs = nibble_headers(K)
+    if not hs: raise AssertionError("no class extraction (s_lshr_b64 + s_and_b32 ..., 15) in " + K.name)
+    return hs[-1]
+
+
+def pair_header(K):
+    """... and the pair loop's: the kind nibble of a pair of records (kernels of the pair unit only)"""
+    hs = nibble_headers(K)
+    if len(hs) != 2: raise AssertionError("%d nibble loops in %s: not a kernel of the pair unit" % (len(hs), K.name))
+    return hs[0]
 
 
 CMP = {"lt": lambda a, b: a < b, "gt": lambda a, b: a > b, "le": lambda a, b: a <= b, "ge": lambda a, b: a >= b,
        "eq": lambda a, b: a == b, "lg": lambda a, b: a != b}
 
 
-def route(K, cls):
-    """the instructions a wave executes from the pass loop's header until it is back there (or leaves the loop) for a record of class
+def route(K, cls, header=None):
+    """(header: pass_header(K), the default, or pair_header(K) with cls = the pair's kind) the instructions a wave executes from the pass loop's header until it is back there (or leaves the loop) for a record of class
     `cls`, every lane in TRAV and some lane accepting (execz branches not taken): [(index, taken or None)], and the flag-test hops"""
-    h, at, creg = pass_header(K)
+    h, at, creg = header or pass_header(K)
     val = {}           # scalar registers with a known value; 64-bit flags under the name of their first operand text
     scc = None; vcc = None; vcc_from_flag = False
     out = []; hops = []
@@ -192,14 +209,15 @@ def count(K, seq):
     return c
 
 
-def route_table(K):
-    """class -> counts of its static route from the loop header to the join (the first instruction all sixteen routes share behind
+def route_table(K, header=None, classes=range(16)):
+    """(header, classes: as for route; the pair loop's kinds are range(1, 7)) class -> counts of its static route from the loop header to the join (the first instruction all sixteen routes share behind
     the switch: the start of the accept chain), its flag-test hops on that stretch, and the unconditional branches between the end
     of the switch (the route's last s_cbranch_scc*) and the join"""
-    h, at, _ = pass_header(K)
+    classes = list(classes)
+    h, at, _ = header or pass_header(K)
     routes = {}
-    for c in range(16):
-        seq, hops, end = route(K, c)
+    for c in classes:
+        seq, hops, end = route(K, c, header)
         assert end == "latch" or seq, (c, end)
         routes[c] = (seq, hops, end)
     # the join: the routes are identical from it to the latch
@@ -207,11 +225,11 @@ def route_table(K):
         n = 0
         while n < len(a) and n < len(b) and a[-1 - n][0] == b[-1 - n][0]: n += 1
         return n
-    first = [i for i, _ in routes[0][0]]
-    n = min(suffix(routes[0][0], routes[c][0]) for c in range(1, 16))
+    first = [i for i, _ in routes[classes[0]][0]]
+    n = min(suffix(routes[classes[0]][0], routes[c][0]) for c in classes[1:])
     join = first[len(first) - n]
     table = {}
-    for c in range(16):
+    for c in classes:
         seq, hops, end = routes[c]
         k = [i for i, _ in seq].index(join)
         head = seq[:k]
@@ -340,9 +358,18 @@ def main():
         bad, n, narrowing = check_exec_regions(K)
         print("saveexec regions: %d, violations: %s; other writes of exec at lines %s" % (n, bad, narrowing))
         ph = pass_header(K)[0]
+        pp = pair_header(K)[0] if len(nibble_headers(K)) == 2 else -1
+        if pp >= 0:
+            # the pair unit: the pair loop's six kinds, header to join (both records' arithmetic) and the whole turn (with the accept)
+            ptable, pjoin = route_table(K, pair_header(K), range(1, 7))
+            print("pair loop: join (shared accept) at line %d" % pjoin)
+            print(" kind " + " ".join("%8s" % k[:8] for k in keys) + "    whole turn: valu salu smem")
+            for c in range(1, 7):
+                w = ptable[c]["whole_iteration"]
+                print("%5d " % c + " ".join("%8d" % ptable[c][k] for k in keys) + "   %22d %4d %4d" % (w["valu"], w["salu"] + w["cbranch"] + w["branch"], w["smem"]))
         for l in loops(K):
             print("loop: depth %d header line %5d%s: %d back edge(s) from %s, %d exit edge(s), %d instructions" %
-                  (l["depth"], l["header"], " (the pass)" if l["header_index"] == ph else "", len(l["back_edges"]), l["back_edges"], l["exits"], l["size"]))
+                  (l["depth"], l["header"], " (the pass)" if l["header_index"] == ph else " (the pair loop)" if l["header_index"] == pp else "", len(l["back_edges"]), l["back_edges"], l["exits"], l["size"]))
         return
     path = sys.argv[1]; want = sys.argv[2] if len(sys.argv) > 2 else None
     blocks = blocks_of(path, want)
