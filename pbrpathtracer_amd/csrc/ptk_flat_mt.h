@@ -161,4 +161,17 @@ PTK_MT_HD void mt_rect_accept(float a, float t, float uA, float vA, float uvA, f
     okB = X & !(uB < 0.0f) & !(vB < 0.0f) & !(uvB > 1.0f) & !okA;
 }
 
+// The same rule as one update per ray, the form the pair pass runs (tri_accept_rect, ptk_kernels.hip): hit = the ray's best changes,
+// first = the record it changes to is A.  With inA, inB the three barycentric tests of each record, okA = X & inA and
+// okB = X & inB & !okA, so hit = okA | okB = X & (inA | inB & !(X & inA)) = X & (inA | inB); and under hit X holds, so the accepted
+// record is A exactly when inA (okA = inA, and okB only when !inA).  Both write the same t.  (tests/cpp/flat_rect_accept_fuzz.cpp)
+PTK_MT_HD void mt_rect_accept_once(float a, float t, float uA, float vA, float uvA, float uB, float vB, float uvB, float best_t, float eps, bool& hit, bool& first)
+{
+    const bool X = !(__builtin_fabsf(a) < eps) & (t > eps) & (t < best_t);
+    const bool inA = !(uA < 0.0f) & !(vA < 0.0f) & !(uvA > 1.0f);
+    const bool inB = !(uB < 0.0f) & !(vB < 0.0f) & !(uvB > 1.0f);
+    hit = X & (inA | inB);
+    first = inA;
+}
+
 }  // namespace ptk_mt

@@ -149,19 +149,53 @@ __device__ __forceinline__ void tri_math_rect(const Walk& W, const RayPair& R, f
     ptk_mt::mt_rect_pair<KIND>(R.dx, R.dy, R.dz, W.ro.x, W.ro.y, W.ro.z, v0x, v0y, v0z, e2x, e2y, e2z,
                                [](const f2& x) { return f2{ rcp_ieee(x.x), rcp_ieee(x.y) }; }, aA, uA, vA, tA, aB, uB, vB, tB);
 }
-// ... and tri_accept_pair for the two of them in turn (PLAIN: no opacity), with the tests on a and t, which the records share, taken once
+// ... and the accept of the two of them for one ray (PLAIN: no opacity), ptk_flat_mt.h mt_rect_accept_once: the nine predicates as WAVE
+// MASKS - one compare each, straight into a scalar register pair, joined with scalar and / or.  Written as `bool & bool` on lane values the
+// compiler folds each pair of sign tests into v_max, v_max, v_min and one compare (four half-rate instructions for two), and the two
+// records' accepts into two masked regions per ray where one does.  The predicates keep their NaN behaviour: !(x < y) is the compare
+// "unordered or >=" (v_cmp_nlt_f32), !(x > y) "unordered or <=" (v_cmp_ngt_f32), t > eps and t < best the ordered ones.
+// The caller stands inside `if (st == ST_TRAV)`: a mask compare returns bits for the lanes that execute it only, so every mask here is
+// a subset of exec, the same value in every lane, and the inverse ballot - which takes a wave-uniform mask - turns it back into a lane
+// condition whose region closes as any `if` does.
+#define PTK_MASK_NLT(x, y) __builtin_amdgcn_fcmpf(x, y, 11)          // FCMP_UGE
+#define PTK_MASK_NGT(x, y) __builtin_amdgcn_fcmpf(x, y, 13)          // FCMP_ULE
+#define PTK_MASK_GT(x, y) __builtin_amdgcn_fcmpf(x, y, 2)            // FCMP_OGT
+#define PTK_MASK_LT(x, y) __builtin_amdgcn_fcmpf(x, y, 4)            // FCMP_OLT
+__device__ __forceinline__ void rect_accept_masks(float a, float t, float uA, float vA, float uvA, float uB, float vB, float uvB, float best_t,
+                                                  unsigned long long& hit, unsigned long long& first)
+{
+    const unsigned long long X = PTK_MASK_NLT(__builtin_fabsf(a), PTK_EPS) & PTK_MASK_GT(t, PTK_EPS) & PTK_MASK_LT(t, best_t);
+    const unsigned long long inA = PTK_MASK_NLT(uA, 0.0f) & PTK_MASK_NLT(vA, 0.0f) & PTK_MASK_NGT(uvA, 1.0f);
+    const unsigned long long inB = PTK_MASK_NLT(uB, 0.0f) & PTK_MASK_NLT(vB, 0.0f) & PTK_MASK_NGT(uvB, 1.0f);
+    hit = X & (inA | inB);
+    first = inA;
+}
+#undef PTK_MASK_NLT
+#undef PTK_MASK_NGT
+#undef PTK_MASK_GT
+#undef PTK_MASK_LT
+// One update per ray: A and B share t and B is accepted only when A is not, so best.t = t and the index is A's or B's by inA - B's is
+// A's + 1 (the classifier pairs no other records), so it is B's minus the lane's bit of inA: a 0 / 1 select and a subtraction, where
+// choosing between two scalar indices takes two moves first.  (u, v of the hit are not kept: nothing of a PLAIN scene reads them.)
+// The empty asm makes the update a masked move and not a select.
 __device__ __forceinline__ void tri_accept_rect(Walk& W, Walk& WS, const bool shadow_live, const f2 a, const f2 t, const f2 uA, const f2 vA,
-                                                const f2 uB, const f2 vB, const int triA, const int triB)
+                                                const f2 uB, const f2 vB, const int triA)
 {
     const f2 uvA = uA + vA, uvB = uB + vB;
-    bool okbA, okbB, oksA, oksB;
-    ptk_mt::mt_rect_accept(a.x, t.x, uA.x, vA.x, uvA.x, uB.x, vB.x, uvB.x, W.best.t, PTK_EPS, okbA, okbB);
-    ptk_mt::mt_rect_accept(a.y, t.y, uA.y, vA.y, uvA.y, uB.y, vB.y, uvB.y, WS.best.t, PTK_EPS, oksA, oksB);
-    oksA = oksA & shadow_live; oksB = oksB & shadow_live;
-    if (okbA) { W.best.tri = triA; W.best.t = t.x; W.best.u = uA.x; W.best.v = vA.x; asm volatile("" : "+v"(W.best.t), "+v"(W.best.u), "+v"(W.best.v)); }
-    if (okbB) { W.best.tri = triB; W.best.t = t.x; W.best.u = uB.x; W.best.v = vB.x; asm volatile("" : "+v"(W.best.t), "+v"(W.best.u), "+v"(W.best.v)); }
-    if (oksA) { WS.best.tri = triA; WS.best.t = t.y; WS.best.u = uA.y; WS.best.v = vA.y; asm volatile("" : "+v"(WS.best.t), "+v"(WS.best.u), "+v"(WS.best.v)); }
-    if (oksB) { WS.best.tri = triB; WS.best.t = t.y; WS.best.u = uB.y; WS.best.v = vB.y; asm volatile("" : "+v"(WS.best.t), "+v"(WS.best.u), "+v"(WS.best.v)); }
+    const int triB = triA + 1;
+    unsigned long long hb, fb, hs, fs;
+    rect_accept_masks(a.x, t.x, uA.x, vA.x, uvA.x, uB.x, vB.x, uvB.x, W.best.t, hb, fb);
+    rect_accept_masks(a.y, t.y, uA.y, vA.y, uvA.y, uB.y, vB.y, uvB.y, WS.best.t, hs, fs);
+    if (__builtin_amdgcn_inverse_ballot_w64(hb))
+    {
+        W.best.tri = triB - (int)__builtin_amdgcn_inverse_ballot_w64(fb); W.best.t = t.x;
+        asm volatile("" : "+v"(W.best.t));
+    }
+    if (__builtin_amdgcn_inverse_ballot_w64(hs) & shadow_live)
+    {
+        WS.best.tri = triB - (int)__builtin_amdgcn_inverse_ballot_w64(fs); WS.best.t = t.y;
+        asm volatile("" : "+v"(WS.best.t));
+    }
 }
 #endif
 
@@ -517,7 +551,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
                             default: PTK_RECT_KIND(6)           // (the classifier writes 1..6 inside the prefix)
                         }
 #undef PTK_RECT_KIND
-                        tri_accept_rect(W, WS, shadow, aA, tA, uA, vA, uB, vB, __float_as_int(a2.y), __float_as_int(a2.y) + 1);
+                        tri_accept_rect(W, WS, shadow, aA, tA, uA, vA, uB, vB, __float_as_int(a2.y));
                     }
                     for (int k = n_pairs * 2; k < P.flat_count; k++)
 #else
