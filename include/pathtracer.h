@@ -296,6 +296,17 @@ public:
     // bary (2 per point) may each be null, not all four.  A geometric query: seed and materials take no part.  Valid after
     // BuildBVH() with no resolution set; pending geometry edits apply as for TraceRays; the image and the sample count are not touched.
     bool ClosestPoints(int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point, float* bary);
+    // Extensions: crossing counts, point containment and a signed distance (include/ptk.h ptk_crossings_rays, ptk_contains_points,
+    // ptk_signed_distance, host arrays, synchronous).  CrossingsRays: how many triangles each ray crosses before tmax[i] (null: no
+    // bound) from their front and from their back; either output may be null, not both.  ContainsPoints: inside[i] = the majority
+    // vote of num_dirs rays from the point (dirs null: the built-in three, num_dirs 3; mode PTK_INSIDE_WINDING or _PARITY), winding
+    // (num_dirs per point) may be null.  SignedDistance: ClosestPoints with the sign bit of dist set inside.  Geometric queries:
+    // seed and materials take no part.  Valid after BuildBVH() with no resolution set; pending geometry edits apply as for
+    // TraceRays; the image and the sample count are not touched.
+    bool CrossingsRays(int num_rays, const float* origins, const float* dirs, const float* tmax, int32_t* front, int32_t* back);
+    bool ContainsPoints(int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside, int32_t* winding);
+    bool SignedDistance(int num_points, const float* points, const float* max_dist, int num_dirs, const float* dirs, int mode, int32_t* tri,
+                        float* dist, float* point, float* bary);
     // Extensions: lightmap baking (include/ptk.h ptk_bake_lightmap / ptk_bake_coverage / ptk_lightmap_dilate, host arrays,
     // synchronous) at the class's seed and trace depth.  uvs: [triangles][6] chart corners, or null for the scene's own uvs;
     // out: width*height*3 floats, rows bottom-up; owner (may be null): width*height triangle indices, -1 uncovered;

@@ -456,6 +456,87 @@ int ptk_last_closest_ms(ptk_ctx* ctx, float* ms);
 int ptk_closest_stats(ptk_ctx* ctx, int32_t num_points, const float* d_points, const float* d_max_dist, uint64_t* node_visits,
                       uint64_t* tri_tests);
 
+/* ---- crossing counts, point containment and a signed distance (no counterpart in the reference) ------------------------------------
+ * "How many surfaces does this ray pass through", "is this point inside the geometry" and "how far is it from the surface, with a
+ * sign": layer counts and walls between two points, dropping probes that sit inside a solid, signed distance fields for collision,
+ * sphere tracing and volumes.  One primitive answers all three: a walk that COUNTS every triangle a ray crosses instead of keeping
+ * the nearest.  A GEOMETRIC query - the one place where the rule departs from ptk_occluded_rays: opacity maps, materials, seeds and
+ * keys take no part and no random draw is consumed.
+ * THE RULE.  Every operation below is one IEEE float32 operation, in the order written (the kernels exist once, in the exact
+ * arithmetic); dot(a, b) = ((ax*bx) + (ay*by)) + (az*bz); cross(x, y) = (xy*yz - yy*xz, xz*yx - yz*xx, xx*yy - yx*xy).  For ray
+ * (o, d) and triangle k = (v0, e1, e2) exactly as its intersection record holds it (v0 its first vertex, e1 and e2 the second and
+ * the third vertex minus the first, the record packers' own float32 subtractions, kept current by ptk_update_geometry), Moeller-Trumbore as the
+ * product's candidate test computes it:
+ *   h = cross(d, e2);  a = dot(e1, h);  f = 1 / a;  s = o - v0;  u = f * dot(s, h);  q = cross(s, e1);  v = f * dot(d, q);
+ *   t = f * dot(e2, q)
+ * Triangle k CROSSES ray i when
+ *   !(|a| < 1e-5) & !(u < 0) & !(v < 0) & !(u + v > 1) & (t > 1e-5) & (t < tmax_i)
+ * tmax == NULL stands for +inf for every ray, and then t < inf is still required; a tmax that is NaN, zero or negative crosses
+ * nothing.  There is no closest rule and no tie rule: every crossing counts, coincident triangles each count.  A crossing is FRONT
+ * when a > 0 and BACK when a < 0 (an accepted a is finite and nonzero, so one of the two holds): front = the ray meets the side
+ * the triangle's vertices wind counter-clockwise on, i.e. it enters a solid whose faces are wound outward.
+ *   ptk_crossings_rays: front[i] / back[i] = the number of triangles that cross ray i front / back.  Either output may be NULL, not
+ *     both.  Directions are used as given and need not be unit vectors: t is in units of |dir|, so the segment from a to b is
+ *     (a, b - a) with tmax = 1.
+ *   ptk_contains_points: for each point p_i and each of the num_dirs = D directions, the ray (p_i, dirs[j]) with tmax = +inf:
+ *     winding[i][j] = back - front.  Direction j VOTES inside under mode PTK_INSIDE_WINDING (the default) when back != front, under
+ *     PTK_INSIDE_PARITY when (front + back) & 1.  inside[i] = 1 when 2 * votes > D, else 0.  D must be odd and in 1 .. 31.
+ *     dirs == NULL requires num_dirs == 3 and uses the built-in set PTK_INSIDE_DEFAULT_DIRS (ptk_inside_default_dirs returns it, so
+ *     callers and tests read it and do not copy it): the float32 normalisations of (0.5377, 0.7283, 0.4251), (-0.3119, 0.4673,
+ *     -0.8273), (0.6931, -0.6173, 0.3719) - no zero component, no two of them parallel, none along an axis or along a face or body
+ *     diagonal of a cube, because those rays run through the edges of axis-aligned meshes.  inside may be NULL if winding is not.
+ *       WINDING is the default because it does not depend on which way the mesh is wound (ingest negates x, so "outward" is not a
+ *       given): a ray leaving a closed, consistently wound solid crosses one more face of one kind than of the other, whichever
+ *       kind that is.  It also survives a ray through a shared edge that both neighbours accept: they count twice with the same
+ *       sign where one crossing was due, which leaves back - front nonzero (parity would flip).  PARITY is for closed meshes whose
+ *       faces are wound inconsistently.  Neither mode means anything for an open mesh.  A point within 1e-5 of a surface, in units
+ *       of the direction's length, is undecided (t > 1e-5).  The vote is a majority because a single ray can still graze: pass
+ *       through a vertex or an edge that neither or both neighbours accept under a rule evaluated in float32.
+ *   ptk_signed_distance: tri, dist, point, bary are bit for bit ptk_closest_points' for the same points and max_dist, except that
+ *     the sign bit of dist[i] is set where ptk_contains_points(points, num_dirs, dirs, mode) gives inside[i] = 1; a point that is
+ *     inside and beyond max_dist gives -inf.  Each output may be NULL but not all four; without dist the call is
+ *     ptk_closest_points.
+ * The results do not depend on the builder that made the tree, on "bvh_leaf_max", on a refit, on "flat" (the calls always walk the
+ * BVH), on ptk_set_tile or on "contract", nor on how a query set is cut into calls (tests/test_gpu_crossings.py: array_equal with
+ * tests/crossings_rule.py): both builders put every record into exactly one leaf, and the walk reaches every leaf whose box the ray
+ * enters before tmax.  A non-finite coordinate makes THAT query's output unspecified and affects neither another query nor whether
+ * the call ends.
+ * The calls need a scene only - no camera, no frame - and read it as ptk_update_materials / ptk_update_geometry left it.  They
+ * touch no frame, adaptive, feature or bake state, stay legal after ptk_render_adaptive, and ptk_request_exit does not cut them.
+ *   ptk_crossings_rays, ptk_contains_points, ptk_signed_distance: host arrays, synchronous; the inputs and the requested outputs
+ *     are staged in device memory for the length of the call.
+ *   the _device forms: every array in memory of this context's GPU, asynchronous on the context's stream (the caller's after
+ *     ptk_set_stream).  No host wait and no allocation of device memory inside the call (ptk_signed_distance_device runs the
+ *     closest-point kernel, then the containment kernel sets the sign bits of d_dist in place).  The arrays must stay allocated
+ *     until the stream has passed the call.
+ * PTK_ERR_BAD_ARG: a null context, a call before ptk_upload_scene, a negative count, a null origins / dirs / points with a count
+ * > 0, no output array, num_dirs even or outside 1 .. 31, dirs == NULL with num_dirs != 3, an unknown mode; a refused call leaves
+ * the outputs alone.  A count of 0 is PTK_OK and does nothing.  A scene without triangles gives zeros (and for ptk_signed_distance
+ * ptk_closest_points' misses: +inf, no point is inside).  PTK_ERR_LIMIT as for ptk_occluded_rays.  Limits: one workgroup per 64
+ * queries, in one launch. */
+#define PTK_INSIDE_WINDING 0
+#define PTK_INSIDE_PARITY 1
+#define PTK_INSIDE_DEFAULT_DIRS { 0.537632227f, 0.728208184f, 0.425046414f, -0.311888129f, 0.467282206f, -0.827268481f, 0.693184376f, -0.617375195f, 0.371945292f }
+int ptk_crossings_rays(ptk_ctx* ctx, int32_t num_rays, const float* origins /*[n][3]*/, const float* dirs /*[n][3]*/,
+                       const float* tmax /*[n] or NULL*/, int32_t* front /*[n]*/, int32_t* back /*[n]*/);
+int ptk_crossings_rays_device(ptk_ctx* ctx, int32_t num_rays, const float* d_origins, const float* d_dirs, const float* d_tmax,
+                              int32_t* d_front, int32_t* d_back);
+int ptk_contains_points(ptk_ctx* ctx, int32_t num_points, const float* points /*[n][3]*/, int32_t num_dirs, const float* dirs /*[D][3] or NULL*/,
+                        int32_t mode, uint8_t* inside /*[n]*/, int32_t* winding /*[n][D] or NULL*/);
+int ptk_contains_points_device(ptk_ctx* ctx, int32_t num_points, const float* d_points, int32_t num_dirs, const float* d_dirs, int32_t mode,
+                               uint8_t* d_inside, int32_t* d_winding);
+/* the built-in direction set, [3][3]; needs no context.  PTK_ERR_BAD_ARG for a null out */
+int ptk_inside_default_dirs(float out[3][3]);
+int ptk_signed_distance(ptk_ctx* ctx, int32_t num_points, const float* points /*[n][3]*/, const float* max_dist /*[n] or NULL*/, int32_t num_dirs,
+                        const float* dirs /*[D][3] or NULL*/, int32_t mode, int32_t* tri /*[n]*/, float* dist /*[n]*/, float* point /*[n][3]*/,
+                        float* bary /*[n][2]*/);
+int ptk_signed_distance_device(ptk_ctx* ctx, int32_t num_points, const float* d_points, const float* d_max_dist, int32_t num_dirs,
+                               const float* d_dirs, int32_t mode, int32_t* d_tri, float* d_dist, float* d_point, float* d_bary);
+/* measurement hook (tools/crossings_timing.py), not part of the feature: the HIP-event time of the last of these calls' kernels -
+ * for ptk_signed_distance the closest-point kernel and the containment kernel together (0 where the call launched none); waits for
+ * the call */
+int ptk_last_crossings_ms(ptk_ctx* ctx, float* ms);
+
 /* ---- a-trous denoiser for image planes and for the frame (no counterpart in the reference) ------------------------------------
  * Turns a noisy low-sample image - a frame of a few samples per pixel, a lightmap of 16 to 64 per texel - into a usable one: an
  * edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by normals, positions and luminance, optionally by the

@@ -110,6 +110,13 @@ int  pth_read_upsampled(pth_tracer* t, float* color, int32_t* cls);
 /* ClosestPoints (the nearest surface point to caller-supplied points, include/ptk.h ptk_closest_points): 1 on success */
 int  pth_closest_points(pth_tracer* t, int num_points, const float* points, const float* max_dist, int32_t* tri, float* dist, float* point,
                         float* bary);
+/* CrossingsRays / ContainsPoints / SignedDistance (crossing counts, point containment and the signed distance, include/ptk.h
+ * ptk_crossings_rays, ptk_contains_points, ptk_signed_distance): 1 on success; tmax, dirs (then num_dirs = 3) and winding may be NULL */
+int  pth_crossings_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, const float* tmax, int32_t* front, int32_t* back);
+int  pth_contains_points(pth_tracer* t, int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside,
+                         int32_t* winding);
+int  pth_signed_distance(pth_tracer* t, int num_points, const float* points, const float* max_dist, int num_dirs, const float* dirs, int mode,
+                         int32_t* tri, float* dist, float* point, float* bary);
 /* BakeLightmap / BakeCoverage / DilateLightmap (lightmap baking, include/ptk.h ptk_bake_lightmap with the tracer's seed and trace
  * depth): 1 on success */
 int  pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,

@@ -1190,6 +1190,39 @@ bool PathTracer::ClosestPoints(int num_points, const float* points, const float*
     return rc == PTK_OK;
 }
 
+// Crossing counts, containment and the signed distance (ptk_crossings_rays, ptk_contains_points, ptk_signed_distance) in the scene as
+// the next RenderFrame() would see it
+bool PathTracer::CrossingsRays(int num_rays, const float* origins, const float* dirs, const float* tmax, int32_t* front, int32_t* back)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_crossings_rays(m->ctx, num_rays, origins, dirs, tmax, front, back);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::ContainsPoints(int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside, int32_t* winding)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_contains_points(m->ctx, num_points, points, num_dirs, dirs, mode, inside, winding);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::SignedDistance(int num_points, const float* points, const float* max_dist, int num_dirs, const float* dirs, int mode, int32_t* tri,
+                                float* dist, float* point, float* bary)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_signed_distance(m->ctx, num_points, points, max_dist, num_dirs, dirs, mode, tri, dist, point, bary);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 // Lightmap baking (ptk_bake_lightmap, ptk_bake_coverage, ptk_lightmap_dilate) of the scene as the next RenderFrame() would see it
 bool PathTracer::BakeLightmap(int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp, uint32_t key_base,
                               uint32_t flags, float* out, int32_t* owner)

@@ -195,6 +195,11 @@ struct ptk_ctx {
     bool closest_timed = false;
     unsigned long long* d_closest_stats = nullptr;
 
+    // crossing counts, containment and signed distance (ptk_crossings_rays, ptk_contains_points, ptk_signed_distance): two events
+    // around the last call's kernels, made by the first call
+    hipEvent_t ev_crossings[2] = { nullptr, nullptr };
+    bool crossings_timed = false;
+
     // a-trous denoiser (ptk_denoise_planes, ptk_denoise_frame): the four packed float4 images of a call (64 B per pixel, grown to the
     // largest call so far); the denoised frame [H][W][3], made by the first ptk_denoise_frame, freed with the feature planes, and
     // the resolution it was last written at; four events of the last call: before the pack, behind it, behind the filter, behind

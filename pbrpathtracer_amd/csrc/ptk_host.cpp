@@ -184,6 +184,19 @@ int pth_closest_points(pth_tracer* t, int num_points, const float* points, const
 {
     return t->pt.ClosestPoints(num_points, points, max_dist, tri, dist, point, bary) ? 1 : 0;
 }
+int pth_crossings_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, const float* tmax, int32_t* front, int32_t* back)
+{
+    return t->pt.CrossingsRays(num_rays, origins, dirs, tmax, front, back) ? 1 : 0;
+}
+int pth_contains_points(pth_tracer* t, int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside, int32_t* winding)
+{
+    return t->pt.ContainsPoints(num_points, points, num_dirs, dirs, mode, inside, winding) ? 1 : 0;
+}
+int pth_signed_distance(pth_tracer* t, int num_points, const float* points, const float* max_dist, int num_dirs, const float* dirs, int mode,
+                        int32_t* tri, float* dist, float* point, float* bary)
+{
+    return t->pt.SignedDistance(num_points, points, max_dist, num_dirs, dirs, mode, tri, dist, point, bary) ? 1 : 0;
+}
 int pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,
                       uint32_t key_base, uint32_t flags, float* out, int32_t* owner)
 {

@@ -39,6 +39,7 @@ HOST_SYMBOLS = [
     "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
     "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points",
+    "pth_crossings_rays", "pth_contains_points", "pth_signed_distance",
     "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised", "pth_temporal_frame", "pth_read_temporal", "pth_get_view",
     "pth_track_motion", "pth_temporal_frame_moving", "pth_read_motion", "pth_temporal_frame_moments", "pth_temporal_variance",
     "pth_read_temporal_variance", "pth_denoise_temporal", "pth_get_object_transform",
@@ -118,6 +119,9 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_intersect_rays.restype = i32; L.pth_intersect_rays.argtypes = [vp, i32, vp, vp, u32, u32, vp, vp, vp, vp]
         L.pth_occluded_rays.restype = i32; L.pth_occluded_rays.argtypes = [vp, i32, vp, vp, vp, u32, u32, vp]
         L.pth_closest_points.restype = i32; L.pth_closest_points.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+        L.pth_crossings_rays.restype = i32; L.pth_crossings_rays.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+        L.pth_contains_points.restype = i32; L.pth_contains_points.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp]
+        L.pth_signed_distance.restype = i32; L.pth_signed_distance.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.pth_denoise_frame.restype = i32; L.pth_denoise_frame.argtypes = [vp, C.POINTER(_ptk.DenoiseParams), i32]
         L.pth_read_denoised.restype = i32; L.pth_read_denoised.argtypes = [vp, vp]
         L.pth_resolve_denoised.restype = i32; L.pth_resolve_denoised.argtypes = [vp, vp]
@@ -604,6 +608,58 @@ class PathTracer:
         return out
 
     ClosestPoints = closest_points
+
+    def crossings_rays(self, origins, dirs, tmax=None):
+        """Extension: (front [n] int32, back [n] int32), how many triangles each ray crosses before tmax[i] (None: no bound) from
+        their front and from their back (include/ptk.h ptk_crossings_rays).  Pending geometry edits apply as for RenderFrame()."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n, "as many directions as origins"
+        tm = None if tmax is None else np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+        assert tm is None or len(tm) == n, "one tmax per ray"
+        out = (np.empty(n, np.int32), np.empty(n, np.int32))
+        if n and not self.L.pth_crossings_rays(self.h, n, o.ctypes.data, d.ctypes.data, tm.ctypes.data if tm is not None else None,
+                                               *(a.ctypes.data for a in out)):
+            raise _ptk.PtkError("CrossingsRays failed: " + self.LastError())
+        return out
+
+    @staticmethod
+    def _inside_dirs(dirs):
+        d = None if dirs is None else np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        return d, (3 if d is None else len(d)), (None if d is None else d.ctypes.data)
+
+    def contains_points(self, points, dirs=None, mode=_ptk.INSIDE_WINDING, want_winding: bool = False):
+        """Extension: inside [n] uint8 - the majority vote of the rays from each point along dirs [D, 3] (None: the built-in three)
+        under mode "winding" or "parity" (include/ptk.h ptk_contains_points); with want_winding (inside, winding [n, D] int32).
+        Pending geometry edits apply as for RenderFrame()."""
+        m = _ptk.inside_mode(mode)
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        d, D, dptr = self._inside_dirs(dirs)
+        inside = np.empty(n, np.uint8)
+        winding = np.empty((n, D), np.int32) if want_winding else None
+        if n and not self.L.pth_contains_points(self.h, n, p.ctypes.data, D, dptr, m, inside.ctypes.data,
+                                                winding.ctypes.data if want_winding else None):
+            raise _ptk.PtkError("ContainsPoints failed: " + self.LastError())
+        return (inside, winding) if want_winding else inside
+
+    def signed_distance(self, points, max_dist=None, dirs=None, mode=_ptk.INSIDE_WINDING):
+        """Extension: closest_points(points, max_dist) with the sign bit of dist set where contains_points(points, dirs, mode) says
+        inside (include/ptk.h ptk_signed_distance).  Pending geometry edits apply as for RenderFrame()."""
+        m = _ptk.inside_mode(mode)
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        md = None if max_dist is None else np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
+        assert md is None or len(md) == n, "one max_dist per point"
+        d, D, dptr = self._inside_dirs(dirs)
+        out = (np.empty(n, np.int32), np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 2), np.float32))
+        if n and not self.L.pth_signed_distance(self.h, n, p.ctypes.data, md.ctypes.data if md is not None else None, D, dptr, m,
+                                                *(a.ctypes.data for a in out)):
+            raise _ptk.PtkError("SignedDistance failed: " + self.LastError())
+        return out
+
+    CrossingsRays, ContainsPoints, SignedDistance = crossings_rays, contains_points, signed_distance
 
     def _chart_uvs(self, uvs):
         if uvs is None:

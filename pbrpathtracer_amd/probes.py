@@ -73,19 +73,30 @@ def clearance(ctx, positions):
     return dist, point, tri
 
 
-def relocate(ctx, positions, min_dist):
+def inside(ctx, positions, mode="winding"):
+    """[n] bool: the probes that sit inside the scene's closed geometry (Context.contains_points with the built-in directions,
+    include/ptk.h ptk_contains_points) - probes to drop, not to relocate: no push along the line to the nearest surface point takes
+    a probe out of a solid on the right side.  Means nothing for open meshes.  numpy positions, numpy result."""
+    return ctx.contains_points(np.ascontiguousarray(positions, np.float32).reshape(-1, 3), None, mode).astype(bool)
+
+
+def relocate(ctx, positions, min_dist, drop_inside=False):
     """(new positions [n, 3] float32, moved [n] bool): probes nearer to a surface than min_dist pushed away from it, straight along
     the line from the nearest surface point through the probe, until they lie min_dist from that point.  One query with max_dist =
     min_dist; a probe with a hit and dist > 0 moves to point + (p - point) * (min_dist / dist), in float32 in that order; a probe
     with a miss (far enough already), or with dist == 0 (on the surface: no direction to go), stays bit for bit.  ONE step: in a
     corner the move away from one wall may end nearer than min_dist to another, so a caller who needs the clearance iterates until
-    nothing moves."""
+    nothing moves.  With drop_inside a third value follows, keep [n] bool = ~inside(ctx, positions): a probe inside a solid is not
+    worth relocating; it is neither moved nor removed here (new and moved keep their length), the caller drops it by the mask."""
     p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
     md = np.float32(min_dist)
     tri, dist, point, _ = ctx.closest_points(p, np.full(len(p), md, np.float32))
     moved = (tri >= 0) & (dist > 0)
+    if drop_inside:
+        keep = ~inside(ctx, p)
+        moved &= keep
     new = p.copy()
     with np.errstate(all="ignore"):
         scale = (md / dist[moved]).astype(np.float32)
     new[moved] = point[moved] + (p[moved] - point[moved]) * scale[:, None]
-    return new, moved
+    return (new, moved, keep) if drop_inside else (new, moved)

@@ -169,6 +169,8 @@ SYMBOLS = [
     "ptk_trace_rays", "ptk_trace_rays_device", "ptk_last_rays_ms",
     "ptk_intersect_rays", "ptk_intersect_rays_device", "ptk_occluded_rays", "ptk_occluded_rays_device", "ptk_last_hits_ms",
     "ptk_closest_points", "ptk_closest_points_device", "ptk_last_closest_ms", "ptk_closest_stats",
+    "ptk_crossings_rays", "ptk_crossings_rays_device", "ptk_contains_points", "ptk_contains_points_device",
+    "ptk_inside_default_dirs", "ptk_signed_distance", "ptk_signed_distance_device", "ptk_last_crossings_ms",
     "ptk_denoise_planes", "ptk_denoise_planes_device", "ptk_denoise_frame", "ptk_read_denoised", "ptk_denoised_device_ptr",
     "ptk_resolve_denoised_rgb8", "ptk_last_denoise_ms",
     "ptk_get_view", "ptk_reproject_planes", "ptk_reproject_planes_device", "ptk_temporal_frame", "ptk_read_temporal",
@@ -297,6 +299,14 @@ def _load_locked() -> C.CDLL:
             fn.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.ptk_last_closest_ms.argtypes = [vp, fp]
         L.ptk_closest_stats.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(u64), C.POINTER(u64)]
+        for fn in (L.ptk_crossings_rays, L.ptk_crossings_rays_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
+        for fn in (L.ptk_contains_points, L.ptk_contains_points_device):
+            fn.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp]
+        L.ptk_inside_default_dirs.argtypes = [vp]
+        for fn in (L.ptk_signed_distance, L.ptk_signed_distance_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
+        L.ptk_last_crossings_ms.argtypes = [vp, fp]
         for fn in (L.ptk_denoise_planes, L.ptk_denoise_planes_device):
             fn.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp, vp]
         L.ptk_denoise_frame.argtypes = [vp, C.POINTER(DenoiseParams), u32]
@@ -385,6 +395,24 @@ RAYS_ACCUMULATE, RAYS_LENS_DRAWS = 1, 2                               # ptk_trac
 BAKE_ACCUMULATE, BAKE_BACK = 1, 2                                     # ptk_bake_lightmap flags
 PROBES_ACCUMULATE = 1                                                 # ptk_bake_probes flags
 DENOISE_VARIANCE = 1                                                  # ptk_denoise_frame flags
+INSIDE_WINDING, INSIDE_PARITY = 0, 1                                  # ptk_contains_points / ptk_signed_distance modes
+INSIDE_MODES = {"winding": INSIDE_WINDING, "parity": INSIDE_PARITY}
+
+
+def inside_default_dirs() -> np.ndarray:
+    """[3, 3] float32: the built-in direction set of ptk_contains_points (ptk_inside_default_dirs; no device needed)."""
+    out = np.zeros((3, 3), np.float32)
+    if load().ptk_inside_default_dirs(out.ctypes.data) != PTK_OK:
+        raise PtkError("ptk_inside_default_dirs failed")
+    return out
+
+
+def inside_mode(mode) -> int:
+    """PTK_INSIDE_* of a mode given by name ("winding", "parity") or by value; raises PtkError for an unknown one."""
+    m = INSIDE_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if m not in (INSIDE_WINDING, INSIDE_PARITY):
+        raise PtkError(f"unknown inside mode {mode!r}")
+    return int(m)
 
 
 def denoise_defaults(extent: float, variance: bool = False, iterations: int = 5) -> DenoiseParams:
@@ -893,6 +921,129 @@ class Context:
                                            C.c_void_p(max_dist.data_ptr()) if max_dist is not None else None, C.byref(a), C.byref(b)),
                   "ptk_closest_stats")
         return a.value, b.value
+
+    # ---- crossing counts, containment, signed distance ---------------------------------------
+    def crossings_rays(self, origins, dirs, tmax=None):
+        """ptk_crossings_rays: (front [n] int32, back [n] int32), the number of triangles ray i = (origins[i], dirs[i]) crosses at
+        1e-5 < t < tmax[i] (t in units of |dir|) from the side they wind counter-clockwise on / from the other side, under the rule
+        of include/ptk.h - geometry only, every crossing counts.  tmax: [n] float32 of the rays' kind, or None for no bound.  numpy
+        in, numpy out through the host entry; torch in, torch out through ptk_crossings_rays_device with no host copy."""
+        if hasattr(origins, "data_ptr"):
+            import torch
+            n = origins.numel() // 3
+            out = (torch.empty((n,), dtype=torch.int32, device=origins.device), torch.empty((n,), dtype=torch.int32, device=origins.device))
+            self._ray_tensors((origins, dirs), n, ((torch.float32, 3),) * 2)
+            if tmax is not None:
+                self._ray_tensors((tmax,), n, ((torch.float32, 1),))
+            if n:
+                self._chk(self.L.ptk_crossings_rays_device(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(dirs.data_ptr()),
+                                                           C.c_void_p(tmax.data_ptr()) if tmax is not None else None,
+                                                           *(C.c_void_p(t.data_ptr()) for t in out)), "ptk_crossings_rays_device")
+            return out
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n, "as many directions as origins"
+        tm = None
+        if tmax is not None:
+            tm = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+            assert len(tm) == n, "one tmax per ray"
+        out = (np.empty(n, np.int32), np.empty(n, np.int32))
+        if n:
+            self._chk(self.L.ptk_crossings_rays(self.h, n, o.ctypes.data, d.ctypes.data, tm.ctypes.data if tm is not None else None,
+                                                *(a.ctypes.data for a in out)), "ptk_crossings_rays")
+        return out
+
+    def _inside_dirs(self, dirs, torch_device=None):
+        """(D, the direction array to keep alive or None for the built-in set, its pointer or None)"""
+        if dirs is None:
+            return 3, None, None
+        if torch_device is not None and hasattr(dirs, "data_ptr"):
+            import torch
+            D = dirs.numel() // 3
+            self._ray_tensors((dirs,), D, ((torch.float32, 3),))
+            return D, dirs, C.c_void_p(dirs.data_ptr())
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        if torch_device is not None:
+            import torch
+            t = torch.from_numpy(d).to(torch_device)
+            return len(d), t, C.c_void_p(t.data_ptr())
+        return len(d), d, d.ctypes.data
+
+    def contains_points(self, points, dirs=None, mode=INSIDE_WINDING, want_winding: bool = False):
+        """ptk_contains_points: inside [n] uint8, 1 where the majority of the rays from points[i] along the D directions votes
+        inside - under "winding" (the default) a ray votes when it crosses unequal numbers of back and front faces, under "parity"
+        when it crosses an odd number of faces.  dirs: [D, 3] float32, D odd and in 1 .. 31, or None for the built-in three
+        (inside_default_dirs()).  With want_winding also winding [n, D] int32 = back - front per direction: (inside, winding).
+        numpy in, numpy out through the host entry; torch in, torch out through ptk_contains_points_device (a numpy dirs is copied
+        to the points' device first)."""
+        m = inside_mode(mode)
+        if hasattr(points, "data_ptr"):
+            import torch
+            n = points.numel() // 3
+            self._ray_tensors((points,), n, ((torch.float32, 3),))
+            D, keep, dptr = self._inside_dirs(dirs, points.device)
+            inside = torch.empty((n,), dtype=torch.uint8, device=points.device)
+            winding = torch.empty((n, D), dtype=torch.int32, device=points.device) if want_winding else None
+            if n:
+                self._chk(self.L.ptk_contains_points_device(self.h, n, C.c_void_p(points.data_ptr()), D, dptr, m, C.c_void_p(inside.data_ptr()),
+                                                            C.c_void_p(winding.data_ptr()) if want_winding else None), "ptk_contains_points_device")
+                if keep is not None and keep is not dirs:
+                    self.synchronize()                      # (the copy of dirs made here must outlive the kernel)
+            return (inside, winding) if want_winding else inside
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        D, keep, dptr = self._inside_dirs(dirs)
+        inside = np.empty(n, np.uint8)
+        winding = np.empty((n, D), np.int32) if want_winding else None
+        if n:
+            self._chk(self.L.ptk_contains_points(self.h, n, p.ctypes.data, D, dptr, m, inside.ctypes.data,
+                                                 winding.ctypes.data if want_winding else None), "ptk_contains_points")
+        elif D < 1 or D > 31 or D % 2 == 0:
+            raise PtkError("ptk_contains_points: num_dirs must be odd and in 1 .. 31")
+        return (inside, winding) if want_winding else inside
+
+    def signed_distance(self, points, max_dist=None, dirs=None, mode=INSIDE_WINDING):
+        """ptk_signed_distance: closest_points(points, max_dist) - (tri, dist, point, bary), bit for bit - with the sign bit of dist
+        set where contains_points(points, dirs, mode) says inside: negative inside, -inf inside and beyond max_dist.  numpy in,
+        numpy out through the host entry; torch in, torch out through ptk_signed_distance_device."""
+        m = inside_mode(mode)
+        if hasattr(points, "data_ptr"):
+            import torch
+            n = points.numel() // 3
+            mk = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=points.device)
+            out = (mk((n,), torch.int32), mk((n,), torch.float32), mk((n, 3), torch.float32), mk((n, 2), torch.float32))
+            self._ray_tensors((points,), n, ((torch.float32, 3),))
+            if max_dist is not None:
+                self._ray_tensors((max_dist,), n, ((torch.float32, 1),))
+            D, keep, dptr = self._inside_dirs(dirs, points.device)
+            if n:
+                self._chk(self.L.ptk_signed_distance_device(self.h, n, C.c_void_p(points.data_ptr()),
+                                                            C.c_void_p(max_dist.data_ptr()) if max_dist is not None else None, D, dptr, m,
+                                                            *(C.c_void_p(t.data_ptr()) for t in out)), "ptk_signed_distance_device")
+                if keep is not None and keep is not dirs:
+                    self.synchronize()
+            return out
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        md = None
+        if max_dist is not None:
+            md = np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
+            assert len(md) == n, "one max_dist per point"
+        D, keep, dptr = self._inside_dirs(dirs)
+        out = (np.empty(n, np.int32), np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 2), np.float32))
+        if n:
+            self._chk(self.L.ptk_signed_distance(self.h, n, p.ctypes.data, md.ctypes.data if md is not None else None, D, dptr, m,
+                                                 *(a.ctypes.data for a in out)), "ptk_signed_distance")
+        elif D < 1 or D > 31 or D % 2 == 0:
+            raise PtkError("ptk_signed_distance: num_dirs must be odd and in 1 .. 31")
+        return out
+
+    def last_crossings_ms(self) -> float:
+        """HIP-event time of the last crossings_rays / contains_points / signed_distance call's kernels; waits for it."""
+        t = C.c_float(0)
+        self._chk(self.L.ptk_last_crossings_ms(self.h, C.byref(t)), "ptk_last_crossings_ms")
+        return t.value
 
     # ---- a-trous denoiser --------------------------------------------------------------------
     def denoise_planes(self, color, mask, normal, position, params, albedo=None, variance=None, want_variance: bool = False):

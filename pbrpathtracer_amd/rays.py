@@ -42,6 +42,14 @@ def segment_rays(a, b):
     return a, np.ascontiguousarray(b - a), np.ones(len(a), np.float32)
 
 
+def count_layers(ctx, a, b):
+    """[n] int32: the number of surfaces crossed strictly between the points a[i] and b[i] - one Context.crossings_rays call over
+    segment_rays(a, b), front + back (include/ptk.h ptk_crossings_rays: every triangle the segment passes through counts, whatever
+    its material; a segment through a shared edge may count both neighbours).  "How many walls between A and B"; 0 = a clear line."""
+    front, back = ctx.crossings_rays(*segment_rays(a, b))
+    return front + back
+
+
 def ambient_occlusion_rays(points, normals, dirs, offset):
     """The rays of ambient_occlusion: for point p with normal n the rays (p + n * offset, d_j) over the directions d_j with float32
     c_j = (n.x * d.x + n.y * d.y) + n.z * d.z > 0, point-major then in direction order - that order is a ray's global index.

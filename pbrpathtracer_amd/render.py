@@ -12,7 +12,7 @@
     python -m pbrpathtracer_amd.render scene.pts --features planes.npz
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz
-    python -m pbrpathtracer_amd.render scene.pts --distance-field 64 64 64 [--df-max-dist M] -o field.npz
+    python -m pbrpathtracer_amd.render scene.pts --distance-field 64 64 64 [--df-max-dist M] [--signed [--inside-mode parity]] -o field.npz
     python -m pbrpathtracer_amd.render scene.pts --bake-lightmap 1024 --spp 64 [--bake-atlas] [--bake-offset F] [--bake-back]
                                                  [--denoise] [--dilate K] -o map.png [--npy map.npy]
     python -m pbrpathtracer_amd.render scene.pts --bake-probes NX NY NZ [--probe-dirs D] --spp N -o probes.npz
@@ -78,7 +78,10 @@ scene's vertex bounds (probes.grid_over_bounds / grid_positions) to the nearest 
 ptk_closest_points): dist [NZ, NY, NX] (inf beyond --df-max-dist), tri, point [NZ, NY, NX, 3], origin, spacing and side - the sign of
 dot(p - point, face normal of tri), +1 / -1 / 0.  side is per FACE: it says which side of the nearest triangle's plane the point is
 on and is not a watertight inside / outside test (open meshes, inconsistent winding and points nearest to an edge or a vertex
-have no such thing).
+have no such thing).  With --signed the .npz also holds that test: inside [NZ, NY, NX] uint8 (PathTracer.contains_points,
+include/ptk.h ptk_contains_points, the built-in directions; --inside-mode winding, the default, or parity) and sdf = dist with its
+sign bit set where inside (ptk_signed_distance: -inf inside and beyond --df-max-dist); every other array is what it is without
+--signed, byte for byte.
 
 The headless equivalent of the reference's Start button + Export (main.cpp:3563-3618, :760-771):
 LoadScene -> SendObjectsToPathTracer -> RenderFrame() x spp -> PNG (flipped to top-down)."""
@@ -164,6 +167,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "sign of dot(p - point, face normal of tri): per face, NOT a watertight inside / outside test")
     ap.add_argument("--df-max-dist", type=float, default=None, metavar="M",
                     help="--distance-field: only surface strictly nearer than M counts (dist inf, tri -1, side 0 beyond it)")
+    ap.add_argument("--signed", action="store_true",
+                    help="--distance-field: add inside (uint8: the point lies inside the closed geometry) and sdf (dist, negative inside) "
+                         "to the .npz")
+    ap.add_argument("--inside-mode", choices=("winding", "parity"), default="winding",
+                    help="--signed: a ray votes inside when it crosses unequal numbers of back and front faces (winding: any consistently "
+                         "wound closed mesh) or an odd number of faces (parity: closed meshes wound inconsistently)")
     return ap
 
 
@@ -349,12 +358,18 @@ def render_distance_field(pt, a) -> int:
     pos = grid_positions(dims, origin, spacing)
     t1 = time.time()
     md = None if a.df_max_dist is None else np.full(len(pos), a.df_max_dist, np.float32)
-    tri, dist, point, _ = pt.closest_points(pos, md)
-    t2 = time.time()
+    extra = {}
     shape = (dims[2], dims[1], dims[0])
+    if a.signed:
+        tri, sdf, point, _ = pt.signed_distance(pos, md, None, a.inside_mode)
+        dist = np.abs(sdf)                      # (clears the sign bit: ptk_closest_points' dist, bit for bit)
+        extra = dict(inside=np.signbit(sdf).astype(np.uint8).reshape(shape), sdf=sdf.reshape(shape))
+    else:
+        tri, dist, point, _ = pt.closest_points(pos, md)
+    t2 = time.time()
     with open(a.out, "wb") as f:                # (np.savez would append .npz to another suffix)
         np.savez(f, dist=dist.reshape(shape), tri=tri.reshape(shape), point=point.reshape(shape + (3,)), origin=origin, spacing=spacing,
-                 side=face_side(verts, pos, point, tri).reshape(shape))
+                 side=face_side(verts, pos, point, tri).reshape(shape), **extra)
     print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {dims[0]}x{dims[1]}x{dims[2]} distance field, "
           f"{int((tri >= 0).sum())} points within reach: {t2 - t1:.3f} s -> {a.out}")
     return 0
