@@ -307,6 +307,13 @@ public:
     bool ContainsPoints(int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside, int32_t* winding);
     bool SignedDistance(int num_points, const float* points, const float* max_dist, int num_dirs, const float* dirs, int mode, int32_t* tri,
                         float* dist, float* point, float* bary);
+    // Extension: ordered multi-hit queries (include/ptk.h ptk_multihit_rays, host arrays, synchronous): the first max_hits (1 .. 16)
+    // triangles each ray crosses before tmax[i] (null: no bound), ascending by (t, triangle index).  count: 1 per ray; tri, t and
+    // side: max_hits per ray; bary: 2 * max_hits per ray; each may be null, not all five.  A geometric query: seed and materials
+    // take no part.  Valid after BuildBVH() with no resolution set; pending geometry edits apply as for CrossingsRays; the image and
+    // the sample count are not touched.
+    bool MultiHitRays(int num_rays, const float* origins, const float* dirs, const float* tmax, int max_hits, int32_t* count, int32_t* tri,
+                      float* t, float* bary, int8_t* side);
     // Extensions: lightmap baking (include/ptk.h ptk_bake_lightmap / ptk_bake_coverage / ptk_lightmap_dilate, host arrays,
     // synchronous) at the class's seed and trace depth.  uvs: [triangles][6] chart corners, or null for the scene's own uvs;
     // out: width*height*3 floats, rows bottom-up; owner (may be null): width*height triangle indices, -1 uncovered;

@@ -537,6 +537,53 @@ int ptk_signed_distance_device(ptk_ctx* ctx, int32_t num_points, const float* d_
  * the call */
 int ptk_last_crossings_ms(ptk_ctx* ctx, float* ms);
 
+/* ---- ordered multi-hit ray queries: the K nearest crossings of a ray (no counterpart in the reference) -----------------------------
+ * "Which surfaces does this ray pass through first, in order": thickness and inside intervals for translucency and subsurface
+ * bakes, depth peeling and x-ray views, the walls between two points, entry / exit pairs, the surface behind a picked one - in one
+ * launch, where re-shooting from each hit plus an epsilon takes K, skips coincident surfaces and depends on the epsilon.
+ * ptk_intersect_rays keeps the first crossing and ptk_crossings_rays counts them all; this call keeps the first K.  A GEOMETRIC
+ * query exactly as ptk_crossings_rays: opacity maps, materials, seeds and keys take no part and no random draw is consumed.
+ * THE RULE.  For ray i and triangle k, a, u, v, t are those of the crossings rule above - the same float32 operations in the same
+ * order on the record's own v0, e1, e2 (the kernel exists once, in the exact arithmetic) - and triangle k CROSSES ray i under the
+ * same predicate:
+ *   !(|a| < 1e-5) & !(u < 0) & !(v < 0) & !(u + v > 1) & (t > 1e-5) & (t < tmax_i)
+ * tmax == NULL stands for +inf for every ray, and then t < inf is still required; a tmax that is NaN, zero or negative crosses
+ * nothing.  The ANSWER of ray i for max_hits = K is the list of its crossings sorted ascending by (t, triangle index) - t compared
+ * as float32, equal t to the smaller index, coincident triangles each appear - cut to its first K entries:
+ *   count[i]          int32    min(K, number of crossings)
+ *   tri[i][j]         int32    the triangle index of entry j                      -1 for j >= count[i]
+ *   t[i][j]           float32  its t                                              +inf
+ *   bary[i][j][2]     float32  its u, v (as ptk_intersect_rays: weights of the second and third vertex)     0
+ *   side[i][j]        int8     +1 when a > 0 (FRONT), -1 when a < 0 (BACK)        0
+ * Each output may be NULL, but not all five.  1 <= K <= PTK_MULTIHIT_MAX.  Directions are used as given and need not be unit
+ * vectors: t is in units of |dir|.  Three consequences (tests/test_gpu_multihit.py holds them on the GPU):
+ *   - the answer for K' < K is the first K' columns of the answer for K;
+ *   - count == min(K, front + back) of ptk_crossings_rays for the same rays;
+ *   - on a scene without opacity maps, K = 1 equals ptk_intersect_rays' tri, t, bary bit for bit.
+ * The results do not depend on the builder that made the tree, on "bvh_leaf_max", on a refit, on "flat" (the call always walks the
+ * BVH), on ptk_set_tile or on "contract", nor on how the ray set is cut into calls (tests/test_gpu_multihit.py: array_equal with
+ * tests/multihit_rule.py): every record lies in exactly one leaf, every record of a leaf the walk reaches is tested once, and a
+ * node is passed over only when it lies beyond the K-th crossing found so far by more than Moeller-Trumbore's own error in t.  A
+ * non-finite component makes THAT ray's output unspecified and affects neither another ray nor whether the call ends.
+ * The call needs a scene only and reads it as ptk_update_materials / ptk_update_geometry left it; it touches no frame, adaptive,
+ * feature or bake state.
+ *   ptk_multihit_rays: host arrays, synchronous; the inputs and the requested outputs are staged in device memory for the length
+ *     of the call.
+ *   ptk_multihit_rays_device: every array in memory of this context's GPU, asynchronous on the context's stream (the caller's
+ *     after ptk_set_stream); no host wait and no allocation of device memory inside the call.
+ * Errors as for ptk_crossings_rays, and PTK_ERR_BAD_ARG for max_hits outside 1 .. PTK_MULTIHIT_MAX; a refused call leaves the
+ * outputs alone.  num_rays == 0 is PTK_OK and does nothing.  A scene without triangles gives count 0 and the unused-slot values
+ * everywhere, by fills, without a kernel.  Limits: one workgroup per 64 rays, in one launch. */
+#define PTK_MULTIHIT_MAX 16
+int ptk_multihit_rays(ptk_ctx* ctx, int32_t num_rays, const float* origins /*[n][3]*/, const float* dirs /*[n][3]*/,
+                      const float* tmax /*[n] or NULL*/, int32_t max_hits /*K*/, int32_t* count /*[n]*/, int32_t* tri /*[n][K]*/,
+                      float* t /*[n][K]*/, float* bary /*[n][K][2]*/, int8_t* side /*[n][K]*/);
+int ptk_multihit_rays_device(ptk_ctx* ctx, int32_t num_rays, const float* d_origins, const float* d_dirs, const float* d_tmax,
+                             int32_t max_hits, int32_t* d_count, int32_t* d_tri, float* d_t, float* d_bary, int8_t* d_side);
+/* measurement hook (tools/multihit_timing.py), not part of the feature: the HIP-event time of the last call's kernel (0 where the
+ * call launched none); waits for the call */
+int ptk_last_multihit_ms(ptk_ctx* ctx, float* ms);
+
 /* ---- a-trous denoiser for image planes and for the frame (no counterpart in the reference) ------------------------------------
  * Turns a noisy low-sample image - a frame of a few samples per pixel, a lightmap of 16 to 64 per texel - into a usable one: an
  * edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by normals, positions and luminance, optionally by the

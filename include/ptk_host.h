@@ -117,6 +117,10 @@ int  pth_contains_points(pth_tracer* t, int num_points, const float* points, int
                          int32_t* winding);
 int  pth_signed_distance(pth_tracer* t, int num_points, const float* points, const float* max_dist, int num_dirs, const float* dirs, int mode,
                          int32_t* tri, float* dist, float* point, float* bary);
+/* MultiHitRays (the first max_hits crossings of each ray in order, include/ptk.h ptk_multihit_rays): 1 on success; tmax and any
+ * output but one may be NULL */
+int  pth_multihit_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, const float* tmax, int max_hits, int32_t* count,
+                       int32_t* tri, float* hit_t, float* bary, int8_t* side);
 /* BakeLightmap / BakeCoverage / DilateLightmap (lightmap baking, include/ptk.h ptk_bake_lightmap with the tracer's seed and trace
  * depth): 1 on success */
 int  pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,

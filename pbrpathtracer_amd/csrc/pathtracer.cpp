@@ -1202,6 +1202,18 @@ bool PathTracer::CrossingsRays(int num_rays, const float* origins, const float* 
     return rc == PTK_OK;
 }
 
+// The first max_hits crossings of every ray in order (ptk_multihit_rays), in the scene as the next RenderFrame() would see it
+bool PathTracer::MultiHitRays(int num_rays, const float* origins, const float* dirs, const float* tmax, int max_hits, int32_t* count, int32_t* tri,
+                              float* t, float* bary, int8_t* side)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_multihit_rays(m->ctx, num_rays, origins, dirs, tmax, max_hits, count, tri, t, bary, side);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 bool PathTracer::ContainsPoints(int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside, int32_t* winding)
 {
     if (!m->scene_uploaded || !m->ensure_ctx()) return false;

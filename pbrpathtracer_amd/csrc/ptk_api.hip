@@ -632,6 +632,7 @@ void ptk_destroy(ptk_ctx* c)
     for (hipEvent_t e : c->ev_closest) if (e) (void)hipEventDestroy(e);
     dfree(c->d_closest_stats);
     for (hipEvent_t e : c->ev_crossings) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_multihit) if (e) (void)hipEventDestroy(e);
     dfree(c->d_denoise);
     for (hipEvent_t e : c->ev_denoise) if (e) (void)hipEventDestroy(e);
     dfree(c->d_temporal_pack);

@@ -200,6 +200,10 @@ struct ptk_ctx {
     hipEvent_t ev_crossings[2] = { nullptr, nullptr };
     bool crossings_timed = false;
 
+    // ordered multi-hit queries (ptk_multihit_rays): two events around the last call's kernel, made by the first call
+    hipEvent_t ev_multihit[2] = { nullptr, nullptr };
+    bool multihit_timed = false;
+
     // a-trous denoiser (ptk_denoise_planes, ptk_denoise_frame): the four packed float4 images of a call (64 B per pixel, grown to the
     // largest call so far); the denoised frame [H][W][3], made by the first ptk_denoise_frame, freed with the feature planes, and
     // the resolution it was last written at; four events of the last call: before the pack, behind it, behind the filter, behind

@@ -188,6 +188,11 @@ int pth_crossings_rays(pth_tracer* t, int num_rays, const float* origins, const 
 {
     return t->pt.CrossingsRays(num_rays, origins, dirs, tmax, front, back) ? 1 : 0;
 }
+int pth_multihit_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, const float* tmax, int max_hits, int32_t* count,
+                      int32_t* tri, float* hit_t, float* bary, int8_t* side)
+{
+    return t->pt.MultiHitRays(num_rays, origins, dirs, tmax, max_hits, count, tri, hit_t, bary, side) ? 1 : 0;
+}
 int pth_contains_points(pth_tracer* t, int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside, int32_t* winding)
 {
     return t->pt.ContainsPoints(num_points, points, num_dirs, dirs, mode, inside, winding) ? 1 : 0;

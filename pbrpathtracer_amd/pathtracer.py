@@ -39,7 +39,7 @@ HOST_SYMBOLS = [
     "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
     "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points",
-    "pth_crossings_rays", "pth_contains_points", "pth_signed_distance",
+    "pth_crossings_rays", "pth_contains_points", "pth_signed_distance", "pth_multihit_rays",
     "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised", "pth_temporal_frame", "pth_read_temporal", "pth_get_view",
     "pth_track_motion", "pth_temporal_frame_moving", "pth_read_motion", "pth_temporal_frame_moments", "pth_temporal_variance",
     "pth_read_temporal_variance", "pth_denoise_temporal", "pth_get_object_transform",
@@ -120,6 +120,7 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_occluded_rays.restype = i32; L.pth_occluded_rays.argtypes = [vp, i32, vp, vp, vp, u32, u32, vp]
         L.pth_closest_points.restype = i32; L.pth_closest_points.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
         L.pth_crossings_rays.restype = i32; L.pth_crossings_rays.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+        L.pth_multihit_rays.restype = i32; L.pth_multihit_rays.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
         L.pth_contains_points.restype = i32; L.pth_contains_points.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp]
         L.pth_signed_distance.restype = i32; L.pth_signed_distance.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.pth_denoise_frame.restype = i32; L.pth_denoise_frame.argtypes = [vp, C.POINTER(_ptk.DenoiseParams), i32]
@@ -660,6 +661,28 @@ class PathTracer:
         return out
 
     CrossingsRays, ContainsPoints, SignedDistance = crossings_rays, contains_points, signed_distance
+
+    def multihit_rays(self, origins, dirs, max_hits, tmax=None):
+        """Extension: (count [n] int32, tri [n, K] int32, t [n, K] float32, bary [n, K, 2] float32, side [n, K] int8), the first
+        K = max_hits (1 .. 16) triangles each ray crosses before tmax[i] (None: no bound), ascending by (t, triangle index)
+        (include/ptk.h ptk_multihit_rays).  Pending geometry edits apply as for RenderFrame()."""
+        K = int(max_hits)
+        if K < 1 or K > _ptk.MULTIHIT_MAX:
+            raise _ptk.PtkError(f"MultiHitRays: max_hits must be in 1 .. {_ptk.MULTIHIT_MAX}")
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n, "as many directions as origins"
+        tm = None if tmax is None else np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+        assert tm is None or len(tm) == n, "one tmax per ray"
+        out = (np.empty(n, np.int32), np.empty((n, K), np.int32), np.empty((n, K), np.float32), np.empty((n, K, 2), np.float32),
+               np.empty((n, K), np.int8))
+        if n and not self.L.pth_multihit_rays(self.h, n, o.ctypes.data, d.ctypes.data, tm.ctypes.data if tm is not None else None, K,
+                                              *(a.ctypes.data for a in out)):
+            raise _ptk.PtkError("MultiHitRays failed: " + self.LastError())
+        return out
+
+    MultiHitRays = multihit_rays
 
     def _chart_uvs(self, uvs):
         if uvs is None:

@@ -171,6 +171,7 @@ SYMBOLS = [
     "ptk_closest_points", "ptk_closest_points_device", "ptk_last_closest_ms", "ptk_closest_stats",
     "ptk_crossings_rays", "ptk_crossings_rays_device", "ptk_contains_points", "ptk_contains_points_device",
     "ptk_inside_default_dirs", "ptk_signed_distance", "ptk_signed_distance_device", "ptk_last_crossings_ms",
+    "ptk_multihit_rays", "ptk_multihit_rays_device", "ptk_last_multihit_ms",
     "ptk_denoise_planes", "ptk_denoise_planes_device", "ptk_denoise_frame", "ptk_read_denoised", "ptk_denoised_device_ptr",
     "ptk_resolve_denoised_rgb8", "ptk_last_denoise_ms",
     "ptk_get_view", "ptk_reproject_planes", "ptk_reproject_planes_device", "ptk_temporal_frame", "ptk_read_temporal",
@@ -307,6 +308,9 @@ def _load_locked() -> C.CDLL:
         for fn in (L.ptk_signed_distance, L.ptk_signed_distance_device):
             fn.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
         L.ptk_last_crossings_ms.argtypes = [vp, fp]
+        for fn in (L.ptk_multihit_rays, L.ptk_multihit_rays_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+        L.ptk_last_multihit_ms.argtypes = [vp, fp]
         for fn in (L.ptk_denoise_planes, L.ptk_denoise_planes_device):
             fn.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp, vp]
         L.ptk_denoise_frame.argtypes = [vp, C.POINTER(DenoiseParams), u32]
@@ -396,6 +400,7 @@ BAKE_ACCUMULATE, BAKE_BACK = 1, 2                                     # ptk_bake
 PROBES_ACCUMULATE = 1                                                 # ptk_bake_probes flags
 DENOISE_VARIANCE = 1                                                  # ptk_denoise_frame flags
 INSIDE_WINDING, INSIDE_PARITY = 0, 1                                  # ptk_contains_points / ptk_signed_distance modes
+MULTIHIT_MAX = 16                                                     # PTK_MULTIHIT_MAX: the most entries ptk_multihit_rays keeps per ray
 INSIDE_MODES = {"winding": INSIDE_WINDING, "parity": INSIDE_PARITY}
 
 
@@ -1043,6 +1048,51 @@ class Context:
         """HIP-event time of the last crossings_rays / contains_points / signed_distance call's kernels; waits for it."""
         t = C.c_float(0)
         self._chk(self.L.ptk_last_crossings_ms(self.h, C.byref(t)), "ptk_last_crossings_ms")
+        return t.value
+
+    # ---- ordered multi-hit queries ------------------------------------------------------------
+    def multihit_rays(self, origins, dirs, max_hits, tmax=None):
+        """ptk_multihit_rays: (count [n] int32, tri [n, K] int32, t [n, K] float32, bary [n, K, 2] float32, side [n, K] int8) for
+        K = max_hits in 1 .. MULTIHIT_MAX - the first K triangles ray i = (origins[i], dirs[i]) crosses at 1e-5 < t < tmax[i],
+        ascending by (t, triangle index) under the rule of include/ptk.h; geometry only, coincident triangles each appear.  Behind
+        count[i]: tri -1, t +inf, bary 0, side 0.  side is +1 where the ray meets the triangle's counter-clockwise side, -1 on the
+        other.  tmax: [n] float32 of the rays' kind, or None for no bound.  numpy in, numpy out through the host entry; torch in,
+        torch out through ptk_multihit_rays_device with no host copy."""
+        K = int(max_hits)
+        if K < 1 or K > MULTIHIT_MAX:
+            raise PtkError(f"ptk_multihit_rays: max_hits must be in 1 .. {MULTIHIT_MAX}")
+        if hasattr(origins, "data_ptr"):
+            import torch
+            n = origins.numel() // 3
+            mk = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=origins.device)
+            out = (mk((n,), torch.int32), mk((n, K), torch.int32), mk((n, K), torch.float32), mk((n, K, 2), torch.float32), mk((n, K), torch.int8))
+            self._ray_tensors((origins, dirs), n, ((torch.float32, 3),) * 2)
+            if tmax is not None:
+                self._ray_tensors((tmax,), n, ((torch.float32, 1),))
+            if n:
+                self._chk(self.L.ptk_multihit_rays_device(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(dirs.data_ptr()),
+                                                          C.c_void_p(tmax.data_ptr()) if tmax is not None else None, K,
+                                                          *(C.c_void_p(t.data_ptr()) for t in out)), "ptk_multihit_rays_device")
+            return out
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        assert len(d) == n, "as many directions as origins"
+        tm = None
+        if tmax is not None:
+            tm = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+            assert len(tm) == n, "one tmax per ray"
+        out = (np.empty(n, np.int32), np.empty((n, K), np.int32), np.empty((n, K), np.float32), np.empty((n, K, 2), np.float32),
+               np.empty((n, K), np.int8))
+        if n:
+            self._chk(self.L.ptk_multihit_rays(self.h, n, o.ctypes.data, d.ctypes.data, tm.ctypes.data if tm is not None else None, K,
+                                               *(a.ctypes.data for a in out)), "ptk_multihit_rays")
+        return out
+
+    def last_multihit_ms(self) -> float:
+        """HIP-event time of the last multihit_rays call's kernel (0 where it launched none); waits for it."""
+        t = C.c_float(0)
+        self._chk(self.L.ptk_last_multihit_ms(self.h, C.byref(t)), "ptk_last_multihit_ms")
         return t.value
 
     # ---- a-trous denoiser --------------------------------------------------------------------

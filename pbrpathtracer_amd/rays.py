@@ -1,7 +1,8 @@
 """Ray sets for Context.trace_rays / PathTracer.TraceRays (include/ptk.h ptk_trace_rays): camera models the library's own
 perspective camera does not cover, as plain (origins, directions) arrays - and for Context.intersect_rays / occluded_rays
-(ptk_intersect_rays, ptk_occluded_rays): segments between point pairs and ambient occlusion.  Host only but for
-ambient_occlusion, which runs its rays through the context it is given."""
+(ptk_intersect_rays, ptk_occluded_rays): segments between point pairs and ambient occlusion - and, over Context.multihit_rays
+(ptk_multihit_rays), the length of a ray inside the geometry and the surfaces between two points.  Host only but for the
+functions that take a context, which run their rays through it."""
 from __future__ import annotations
 
 import numpy as np
@@ -48,6 +49,42 @@ def count_layers(ctx, a, b):
     its material; a segment through a shared edge may count both neighbours).  "How many walls between A and B"; 0 = a clear line."""
     front, back = ctx.crossings_rays(*segment_rays(a, b))
     return front + back
+
+
+def inside_length(count, t, side, max_hits: int):
+    """(length [n] float32, complete [n] bool) from Context.multihit_rays' count [n], t [n, K] and side [n, K]: the length of each
+    ray, in units of |dir|, that lies inside the geometry.  Each list is walked with a running sum of side that starts at 0 - the
+    origin is taken to be outside - and t[j + 1] - t[j] is added, in float32 and in list order, for every j < count - 1 at which
+    the running sum after crossing j is nonzero: between the two crossings the ray has entered more often than it has left, or
+    the other way round, so the result does not depend on which way the mesh is wound, and a shared edge that both neighbours
+    accept (+1, +1, -1, -1) is one interval.  complete = count < max_hits: the list was not cut, so the length is the whole
+    ray's."""
+    count = np.asarray(count, np.int32).reshape(-1)
+    n = len(count)
+    t = np.asarray(t, np.float32).reshape(n, -1) if n else np.zeros((0, 1), np.float32)
+    side = np.asarray(side, np.int8).reshape(t.shape)
+    length = np.zeros(n, np.float32)
+    run = np.zeros(n, np.int32)
+    for j in range(t.shape[1] - 1):
+        run = run + side[:, j]
+        add = (j + 1 < count) & (run != 0)
+        with np.errstate(invalid="ignore"):                     # (inf - inf behind a list's end: not taken)
+            length = np.where(add, length + (t[:, j + 1] - t[:, j]), length)
+    return length, count < int(max_hits)
+
+
+def thickness(ctx, origins, dirs, max_hits: int = 16, tmax=None):
+    """(length [n] float32, complete [n] bool): inside_length of one Context.multihit_rays call - how much solid each ray passes
+    through among its first max_hits crossings (before tmax).  numpy arrays in and out."""
+    count, _, t, _, side = ctx.multihit_rays(origins, dirs, max_hits, tmax)
+    return inside_length(count, t, side, max_hits)
+
+
+def layers_between(ctx, a, b, max_hits: int):
+    """Context.multihit_rays over segment_rays(a, b): (count, tri, t, bary, side) of the first max_hits surfaces strictly between the
+    points a[i] and b[i], in order from a; t is the fraction of the segment.  "Which walls lie between A and B"."""
+    origins, dirs, tmax = segment_rays(a, b)
+    return ctx.multihit_rays(origins, dirs, max_hits, tmax)
 
 
 def ambient_occlusion_rays(points, normals, dirs, offset):

@@ -11,7 +11,7 @@
                                                  [--linear-transfer]
     python -m pbrpathtracer_amd.render scene.pts --features planes.npz
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
-    python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz
+    python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz [--layers K]
     python -m pbrpathtracer_amd.render scene.pts --distance-field 64 64 64 [--df-max-dist M] [--signed [--inside-mode parity]] -o field.npz
     python -m pbrpathtracer_amd.render scene.pts --bake-lightmap 1024 --spp 64 [--bake-atlas] [--bake-offset F] [--bake-back]
                                                  [--denoise] [--dilate K] -o map.png [--npy map.npy]
@@ -60,7 +60,9 @@ PathTracer.TraceRays (include/ptk.h ptk_trace_rays; rays.equirect_rays) instead 
 
 With --equirect WIDTH --hits FILE.npz nothing is traced and no image written: the .npz holds what the panorama's rays hit
 (PathTracer.IntersectRays, include/ptk.h ptk_intersect_rays, sample 0) - depth, triangle, material [H, W] and bary [H, W, 2], rows
-top-down - a depth panorama; --spp is not needed.
+top-down - a depth panorama; --spp is not needed.  With --layers K (1 .. 16) the .npz also holds the first K surfaces along each
+ray in order (PathTracer.MultiHitRays, include/ptk.h ptk_multihit_rays - geometry only, opacity maps take no part): layer_t and
+layer_tri [K, H, W] (+inf and -1 behind a ray's last surface) and layer_count [H, W]; the other arrays are what they are without it.
 
 With --bake-lightmap SIZE the image is a SIZE x SIZE lightmap (include/ptk.h ptk_bake_lightmap): per texel of the scene's own uv
 layout - or, with --bake-atlas, of lightmap.grid_atlas, one chart per triangle - the radiance leaving the surface along its normal,
@@ -145,6 +147,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--hits", metavar="FILE.npz", default=None,
                     help="--equirect: instead of tracing, write what the panorama's rays hit (depth, triangle, material, bary; rows "
                          "top-down) to this .npz")
+    ap.add_argument("--layers", type=int, metavar="K", default=None,
+                    help="--hits: also write the first K (1 .. 16) surfaces along each ray in order: layer_t, layer_tri [K, H, W] "
+                         "and layer_count [H, W]")
     ap.add_argument("--bake-lightmap", type=int, metavar="SIZE", default=None,
                     help="bake a SIZE x SIZE lightmap over the scene's uvs instead of rendering a view; the PNG holds the mean "
                          "(sum / spp) resolved like a frame, rows top-down; --npy the float32 sums [SIZE, SIZE, 3], rows bottom-up as baked")
@@ -388,9 +393,14 @@ def render_equirect(pt, a) -> int:
     t1 = time.time()
     if a.hits:
         tri, t, bary, material = pt.IntersectRays(origins, dirs)
+        planes = dict(depth=t.reshape(h, w), triangle=tri.reshape(h, w), material=material.reshape(h, w), bary=bary.reshape(h, w, 2))
+        if a.layers is not None:
+            count, ltri, lt, _, _ = pt.MultiHitRays(origins, dirs, a.layers)
+            planes.update(layer_t=np.ascontiguousarray(lt.T).reshape(a.layers, h, w),
+                          layer_tri=np.ascontiguousarray(ltri.T).reshape(a.layers, h, w), layer_count=count.reshape(h, w))
         t2 = time.time()
         with open(a.hits, "wb") as f:               # (np.savez would append .npz to another suffix)
-            np.savez(f, depth=t.reshape(h, w), triangle=tri.reshape(h, w), material=material.reshape(h, w), bary=bary.reshape(h, w, 2))
+            np.savez(f, **planes)
         print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {w}x{h} panorama, {int((tri >= 0).sum())} of {w * h} rays hit: "
               f"{t2 - t1:.3f} s -> {a.hits}")
         return 0
@@ -568,6 +578,9 @@ def main(argv=None):
         return 1
     if a.bake_probes is None and (a.probe_visibility is not None or a.probe_max_dist is not None):
         print("error: --probe-visibility and --probe-max-dist go with --bake-probes", file=sys.stderr)
+        return 1
+    if a.layers is not None and not (a.equirect is not None and a.hits and 1 <= a.layers <= 16):
+        print("error: --layers goes with --equirect --hits and needs a count in 1..16", file=sys.stderr)
         return 1
     if a.temporal and a.orbit is None:
         print("error: --temporal goes with --orbit", file=sys.stderr)
