@@ -256,6 +256,25 @@ struct Walk {
     }
 };
 
+// Moeller-Trumbore's a, u, v, t of the ray (ro, rd) for one 48-byte triangle record: the one place these float32 operations are
+// written, in this order, for every triangle arm of the BVH walk (tri_test, the crossing counts, the multi-hit list and its
+// epilogue) - so what one of them decides on is bit for bit what the others compute.
+__device__ __forceinline__ void mt_auvt(const v3 ro, const v3 rd, const float4 t0, const float4 t1, const float4 t2, float& a, float& u, float& v,
+                                        float& t)
+{
+    v3 v0 = V(t0.x, t0.y, t0.z);
+    v3 edge1 = V(t0.w, t1.x, t1.y);
+    v3 edge2 = V(t1.z, t1.w, t2.x);
+    v3 h = cross(rd, edge2);
+    a = dot(edge1, h);
+    float f = rcp_ieee(a);                      // (|a| < EPS, a NaN or infinite: rejected below whatever f is)
+    v3 s = sub(ro, v0);
+    u = f * dot(s, h);
+    v3 q = cross(s, edge1);
+    v = f * dot(rd, q);
+    t = f * dot(edge2, q);
+}
+
 // Candidate test of one triangle record: Hit's leaf branch (pathtracer.cpp:463-489) = Moeller-Trumbore
 // + order-independent closest rule + stochastic opacity.  Returns true when the walk can stop (an
 // occluder decided a shadow ray).
@@ -263,23 +282,13 @@ template <bool STATS, class PT>
 __device__ __forceinline__ bool tri_test(const PT& P, Walk& W, float4 t0, float4 t1, float4 t2, const Rng& rng,
                                          uint32_t ray, Counters& cnt)
 {
-    const v3 ro = W.ro, rd = W.rd;
     if (STATS) cnt.tris++;
     // Moeller-Trumbore, PathTracer::IntersectTriangle pathtracer.cpp:373-409.  The reference returns
     // early after each rejection test; here every quantity is computed and the SAME tests (in their
     // negated form, so NaNs fall through exactly as they do there) are AND-ed: identical results for
     // every accepted hit, no divergent branches in the hot loop.
-    v3 v0 = V(t0.x, t0.y, t0.z);
-    v3 edge1 = V(t0.w, t1.x, t1.y);
-    v3 edge2 = V(t1.z, t1.w, t2.x);
-    v3 h = cross(rd, edge2);
-    float a = dot(edge1, h);
-    float f = rcp_ieee(a);                      // (|a| < EPS, a NaN or infinite: rejected below whatever f is)
-    v3 s = sub(ro, v0);
-    float u = f * dot(s, h);
-    v3 q = cross(s, edge1);
-    float v = f * dot(rd, q);
-    float t = f * dot(edge2, q);
+    float a, u, v, t;
+    mt_auvt(W.ro, W.rd, t0, t1, t2, a, u, v, t);
     int tri = __float_as_int(t2.y);
     // (the reference also returns on u > 1, pathtracer.cpp:393: implied here - v >= 0 makes fl(u + v) >= u, rounding being
     // monotone, so u > 1 fails the u + v test, and a NaN u passes both forms alike)
@@ -357,9 +366,12 @@ __device__ __forceinline__ void request_node(const PT& P, const Walk& W, NodeRec
 // loop or at the end of the lane's previous step, and the record of the node this step ends on is requested before the step
 // returns, so its round trip also covers the loop's wave-uniform bookkeeping (ballots, debts, ~30 dependent scalar instructions)
 // instead of starting behind it.
-template <bool STATS, int STRIDE, bool PIPELINED = false, class PT>
-__device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, uint32_t ray, int* stack, Counters& cnt,
-                                          const bool run_tri_arm = true, NodeRec* rec = nullptr)
+// tri: the triangle arm, tri(t0, t1, t2, pos) for the 48-byte record at position `pos` of the triangle table; returns whether the
+// walk may stop.  Every record of a leaf is queued exactly once and arm A tests what is queued once each - unless a test stops the
+// walk - so an arm that never stops is called exactly once for every record of every leaf the walk reaches: what counting and
+// listing crossings need.  Arm B culls against W.best.t, whatever the triangle arm keeps there.
+template <bool STATS, int STRIDE, bool PIPELINED, class PT, class TRI>
+__device__ __forceinline__ void walk_step_with(const PT& P, Walk& W, int* stack, Counters& cnt, const bool run_tri_arm, NodeRec* rec, TRI tri)
 {
     // the node record of arm B is requested BEFORE arm A runs, so that its round trip overlaps arm A's loads and arithmetic
     // (one memory latency per iteration instead of two; the compiler would otherwise issue it after arm A's join)
@@ -385,8 +397,8 @@ __device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, 
         const float4* tpb = (const float4*)((const char*)P.tris + (uint32_t)iB * (uint32_t)(TRI_F4 * 16));
         float4 a0 = ldg4(tpa), a1 = ldg4(tpa + 1), a2 = ldg4(tpa + 2);
         float4 b0 = ldg4(tpb), b1 = ldg4(tpb + 1), b2 = ldg4(tpb + 2);
-        bool stop = tri_test<STATS>(P, W, a0, a1, a2, rng, ray, cnt);
-        if ((two | blocked) && !stop) stop = tri_test<STATS>(P, W, b0, b1, b2, rng, ray, cnt);
+        bool stop = tri(a0, a1, a2, (uint32_t)iA);
+        if ((two | blocked) && !stop) stop = tri(b0, b1, b2, (uint32_t)iB);
         if (blocked)
         {
             W.tri_next = (code >> 3) + 1; W.tri_left = code & 7;
@@ -467,6 +479,15 @@ __device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, 
         W.node = W.template pop<STRIDE>(stack);
     }
     if (PIPELINED) request_node(P, W, *rec);                    // for this lane's next step (a finished walk asks for the root: where its next ray starts)
+}
+// ... with the closest-hit rule in arm A: the step of the trace kernels and of every walk that keeps one hit per ray
+template <bool STATS, int STRIDE, bool PIPELINED = false, class PT>
+__device__ __forceinline__ void walk_step(const PT& P, Walk& W, const Rng& rng, uint32_t ray, int* stack, Counters& cnt,
+                                          const bool run_tri_arm = true, NodeRec* rec = nullptr)
+{
+    walk_step_with<STATS, STRIDE, PIPELINED>(P, W, stack, cnt, run_tri_arm, rec, [&](const float4 t0, const float4 t1, const float4 t2, uint32_t) {
+        return tri_test<STATS>(P, W, t0, t1, t2, rng, ray, cnt);
+    });
 }
 
 // hemisphere / lobe sampler, pathtracer.cpp:606-611 (:618-623 lobe form): see oracle sample_about()
