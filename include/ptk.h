@@ -1512,6 +1512,9 @@ int ptk_probe_unpack(ptk_ctx* ctx, int world, const float* host_packed /* all ra
  * fan-split axis-aligned rectangles (ptk_flat_rect_pair) one pair of records at a time, sharing what their two tests have in
  * common, and then the records behind it one by one; 0 launches the kernels without that loop.  Bit-identical either way
  * (tests/test_gpu_flat_rect_pairs.py); takes effect behind the renders already queued.
+ * "flat_cycle" = 0/1 (default 1; acts with "flat_rect_pairs" on): that kernel is launched from a third unit, the same pass and shade
+ * block in a fixed deal / shade / pass cycle without the block vote, its work units dealt from scalar registers; 0 launches the pair
+ * unit's kernel.  Bit-identical either way (tests/test_gpu_flat_cycle.py); decided per render.  ptk_trace_unit tells which one ran.
  * No environment variable reaches the library. */
 int ptk_set_option(ptk_ctx* ctx, const char* name, double value);
 
@@ -1546,6 +1549,13 @@ int ptk_scene_is_lambert(const ptk_scene_desc* scene);
 /* 1 when the newest trace launch of this context ran the LAMBERT level of the PLAIN kernel (ptk_trace_variant reports
  * PTK_TRACE_FLAT_PLAIN for both of its levels), else 0 */
 int ptk_trace_is_lambert(ptk_ctx* ctx, int* lambert);
+/* ... and which translation unit's kernel it was, for the bit-exact PLAIN kernels ("contract" 0, no counters): the plain unit
+ * ("flat_rect_pairs" 0), the pair unit ("flat_cycle" 0) or the cycle unit; PTK_UNIT_NONE for every other launch */
+#define PTK_UNIT_NONE 0
+#define PTK_UNIT_PLAIN 1         /* trace_kernel of ptk_kernels_plain.hip */
+#define PTK_UNIT_RECT 2          /* trace_kernel_rect of ptk_kernels_rect.hip */
+#define PTK_UNIT_CYCLE 3         /* trace_kernel_cycle of ptk_kernels_cycle.hip */
+int ptk_trace_unit(ptk_ctx* ctx, int* unit);
 /* Zero classes of the flat triangle list (scenes of <= 16 triangles), no device needed: the class, 0..15, of a record whose
  * stored edges are edges[0..2] = e1 = v2 - v1 and edges[3..5] = e2 = v3 - v1 (float32 subtractions).  A class stands for a mask
  * over those six words, ptk_flat_zero_mask(class): bit k set = word k is known to be stored as +0 or -0, so the triangle test

@@ -256,7 +256,7 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
     if (const int rc = use_primary_cache(c, p); rc != PTK_OK) return rc;
     // decided per render from the staged state: a material edit, a new scene or an opened aperture since the last one is seen here
     p.plain = (c->opt_plain_kernel && c->scene_plain && p.flat_count > 0 && p.primary_hit != nullptr) ? 1 : 0;
-    if (p.plain && c->opt_flat_rect_pairs) p.plain = 2;        // the exact build's pair-pass unit (launch_trace; the contracted builds have none)
+    if (p.plain && c->opt_flat_rect_pairs) p.plain = c->opt_flat_cycle ? 3 : 2;        // the exact build's pair-pass unit, or the cycle unit around the same pass (launch_trace; the contracted builds have neither)
     p.lambert = (p.plain && c->opt_lambert_kernel && c->scene_lambert) ? 1 : 0;
     if (!c->pixel_rng_valid || c->pixel_rng_seed != seed)
     {
@@ -439,6 +439,7 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
         HIPCHK(c, hipGetLastError());
         c->last_trace_variant = p.flat_count <= 0 ? PTK_TRACE_BVH : ((p.plain && !stats) ? PTK_TRACE_FLAT_PLAIN : PTK_TRACE_FLAT);
         c->last_trace_lambert = p.flat_count > 0 && p.plain && p.lambert && !stats;
+        c->last_trace_unit = (p.flat_count > 0 && p.plain && !stats && c->opt_contract == 0) ? (p.plain == 3 ? PTK_UNIT_CYCLE : p.plain == 2 ? PTK_UNIT_RECT : PTK_UNIT_PLAIN) : PTK_UNIT_NONE;
         if (timed && pi >= 0) HIPCHK(c, hipEventRecord(c->ev[pi][1], tstream));
         if (kl >= 0) { HIPCHK(c, hipEventRecord(c->klog_ev[2 * kl + 1], tstream)); c->klog_n = kl + 1; }
         if (overlap)
@@ -1037,6 +1038,13 @@ int ptk_trace_is_lambert(ptk_ctx* c, int* lambert)
 {
     if (!c || !lambert) return PTK_ERR_BAD_ARG;
     *lambert = c->last_trace_lambert ? 1 : 0;
+    return PTK_OK;
+}
+
+int ptk_trace_unit(ptk_ctx* c, int* unit)
+{
+    if (!c || !unit) return PTK_ERR_BAD_ARG;
+    *unit = c->last_trace_unit;
     return PTK_OK;
 }
 
@@ -1832,6 +1840,11 @@ int ptk_set_option(ptk_ctx* c, const char* name, double value)
             c->inputs_dirty = true;
         }
         c->opt_flat_rect_pairs = use;
+        return PTK_OK;
+    }
+    if (!std::strcmp(name, "flat_cycle"))
+    {
+        c->opt_flat_cycle = value != 0.0 ? 1 : 0;         // (which kernel the next render launches: nothing on the device changes)
         return PTK_OK;
     }
     if (!std::strcmp(name, "device_build"))

@@ -62,8 +62,10 @@ struct ptk_ctx {
     bool scene_lambert = false;         // lambert_tables() of the staged scene (plain and no reflectiveness > 0): kept current with scene_plain
     int opt_lambert_kernel = 1;         // 0: Lambert scenes launch the PLAIN kernel's generic level (tests, A/B runs)
     int opt_flat_rect_pairs = 1;        // 1: exact PLAIN scenes run the pair-pass unit's kernels, which test the list's prefix of fan-split rectangles pair by pair
+    int opt_flat_cycle = 1;             // 1 (with opt_flat_rect_pairs): ... from the cycle unit, the same pass and shade block in a fixed cycle with a scalar unit deal
     int opt_flat_zero_classes = 1;      // 0: the exact PLAIN pass treats every flat record as class 0 (the class table's first word is kept zero)
     int last_trace_variant = PTK_TRACE_NONE;     // of the newest trace launch (ptk_trace_variant)
+    int last_trace_unit = PTK_UNIT_NONE;         // ... which unit's kernel it was, for the exact PLAIN kernels (ptk_trace_unit)
     bool last_trace_lambert = false;    // ... and whether it ran the LAMBERT level of the PLAIN kernel (ptk_trace_is_lambert)
 
     // camera (host copies, already normalised / clamped like the reference setters)

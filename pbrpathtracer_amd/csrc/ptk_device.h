@@ -122,6 +122,7 @@ struct RenderParams {
                                 // primary-hit cache) that every material is opaque and untextured, no triangle is smoothed or has an
                                 // opacity texture and primary_hit is set; no kernel reads it (last field: the others keep their offsets).
                                 // 2: ... and the exact build launches the pair-pass unit's kernels (the flat_rect_pairs option)
+                                // 3: ... from the cycle unit, the same pass and shade block in a fixed cycle (the flat_cycle option on top of it)
     int lambert;                // 1 (only with plain): ... and no material has reflectiveness > 0 (ptk_api.hip lambert_tables), so launch_trace
                                 // takes the LAMBERT level of the PLAIN kernel; no kernel reads it either (behind plain: same offsets again)
 };

@@ -53,7 +53,8 @@
 // tolerance (tests/test_gpu_contract.py); and still reproducible bit for bit, whatever the work distribution, passes or tiles.
 // Each build has its own probe_math_kernel (ptk_probe_math follows the option).  (The header defaults PTK_CONTRACT to 0.)
 // A fourth time, through ptk_kernels_plain.hip, for the exact build's two PLAIN instantiations alone (PTK_PLAIN_UNIT, below the kernel),
-// and a fifth, through ptk_kernels_rect.hip, for the same two with the pair pass in front of the record loop (PTK_RECT_UNIT).
+// and a fifth, through ptk_kernels_rect.hip, for the same two with the pair pass in front of the record loop (PTK_RECT_UNIT),
+// and a sixth, through ptk_kernels_cycle.hip, for those two around another main loop (PTK_CYCLE_UNIT, ptk_trace_cycle.h).
 
 #include "ptk_device_fn.h"
 #include "ptk_flat_mt.h"
@@ -405,6 +406,13 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
     float4* const samples_u = uniform_ptr(P.samples);
     const int num_nodes_u = __builtin_amdgcn_readfirstlane(P.num_nodes);
     const float scene_bound_u = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(P.scene_bound)));
+    // (the cycle unit, ptk_kernels_cycle.hip, holds more of them there: see ptk_trace_cycle.h)
+#ifdef PTK_CYCLE_UNIT
+    const int max_depth_u = __builtin_amdgcn_readfirstlane(P.max_depth);
+#define PTK_U_MAX_DEPTH max_depth_u
+#else
+#define PTK_U_MAX_DEPTH P.max_depth
+#endif
     // a finished path: its radiance goes to the sample buffer, the lane moves to its next sample
 #define PTK_FINISH_PATH()                                                                         \
     do {                                                                                          \
@@ -433,10 +441,14 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
             W.occl_tri = -1;                                                                      \
             W.begin(W.ro, nextDir, num_nodes_u, stack, scene_bound_u);                                   \
         }                                                                                         \
-        else if (!hit_ || (FLAT && !STATS && !((LAMBERT ? depth : iter) < P.max_depth))) PTK_FINISH_PATH();     /* :550 miss -> black */  \
+        else if (!hit_ || (FLAT && !STATS && !((LAMBERT ? depth : iter) < PTK_U_MAX_DEPTH))) PTK_FINISH_PATH();     /* :550 miss -> black */  \
         else st = ST_SHADE;                                                                       \
     } while (0)
 
+#ifdef PTK_CYCLE_UNIT
+    // the cycle unit's main loop: a fixed shade / pass cycle around the same two blocks, units dealt from scalar registers
+#include "ptk_trace_cycle.h"
+#else
     int debt_shade = 0, debt_gen = 0;      // wave-uniform: lane-iterations wasted by parked lanes
     for (;;)
     {
@@ -514,81 +526,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
                 if (STATS && lane == 0) { cnt.walk_iters++; cnt.walk_lanes += (uint32_t)n_trav; }
                 if (st == ST_TRAV)
                 {
-                    typedef float f4v __attribute__((ext_vector_type(4)));
-                    typedef const __attribute__((address_space(4))) f4v* cf4;        // constant address space -> s_load
-                    const cf4 ct = (cf4)(uintptr_t)P.flat_tris;            // the scene's triangles in ascending index order
-                    // both rays of a diffuse bounce in one pass over the triangles: the shadow ray
-                    // (ray number `ray`) and the sampled bounce (`ray + 1`), pathtracer.cpp:638 / :724
-                    const bool shadow = WS.occl_tri >= 0;
-                    const uint32_t bounce_ray = shadow ? ray + 1u : ray;
-                    RayPair R;
-                    R.ox = f2{ W.ro.x, WS.ro.x }; R.oy = f2{ W.ro.y, WS.ro.y }; R.oz = f2{ W.ro.z, WS.ro.z };
-                    R.dx = f2{ W.rd.x, WS.rd.x }; R.dy = f2{ W.rd.y, WS.rd.y }; R.dz = f2{ W.rd.z, WS.rd.z };
-                    // exact PLAIN pass: one 4-bit class per record (classify_flat_kernel, ptk_frame.hip) names the edge words stored
-                    // as zeros, and the record goes to the body with those operations deleted (ptk_flat_mt.h; DESIGN 4.1: same hits,
-                    // same bits of t).  The class word is one scalar load per pass, the switch is wave-uniform, the order ascending.
-                    constexpr bool ZERO_CLASSES = PLAIN && !STATS && !PTK_CONTRACT;
-                    typedef const __attribute__((address_space(4))) unsigned long long* cu64;
-                    const unsigned long long classes = ZERO_CLASSES ? *(cu64)(uintptr_t)(P.flat_tris + FLAT_CLASSES_AT) : 0ull;
-#ifdef PTK_RECT_UNIT
-                    // The pair pass (this unit only): the list's prefix of fan-split axis-aligned rectangles, one pair of records per
-                    // turn of a counted loop - one wave-uniform switch over the six kinds, the arithmetic of both records with B's
-                    // words named as A's (ptk_flat_mt.h mt_rect_pair), one shared accept, the hit moves (the pair lemma).
-                    // Only a prefix is paired, so the order stays ascending; the loop below goes on from record 2m.
-                    static_assert(ZERO_CLASSES, "the pair unit holds the exact PLAIN kernels only");
-                    const unsigned long long pairs = *(cu64)(uintptr_t)(P.flat_tris + FLAT_PAIRS_AT);
-                    const int n_pairs = (int)(pairs >> 32) & 15;
-                    for (int j = 0; j < n_pairs; j++)
-                    {
-                        // of the pair's six float4s, record A's three: v0, e2 (e1(A), e1(B), e2(B) are words of e2(A) or zeros) and the index,
-                        // which B's follows (the classifier pairs no other records)
-                        const f4v a0 = ct[j * 2 * TRI_F4], a1 = ct[j * 2 * TRI_F4 + 1], a2 = ct[j * 2 * TRI_F4 + 2];
-                        f2 aA, uA, vA, tA, aB, uB, vB, tB;
-#define PTK_RECT_KIND(c) tri_math_rect<c>(W, R, a0.x, a0.y, a0.z, a1.z, a1.w, a2.x, aA, uA, vA, tA, aB, uB, vB, tB); break;
-                        switch ((unsigned)(pairs >> (j * 4)) & 15u)
-                        {
-                            case 1: PTK_RECT_KIND(1) case 2: PTK_RECT_KIND(2) case 3: PTK_RECT_KIND(3) case 4: PTK_RECT_KIND(4) case 5: PTK_RECT_KIND(5)
-                            default: PTK_RECT_KIND(6)           // (the classifier writes 1..6 inside the prefix)
-                        }
-#undef PTK_RECT_KIND
-                        tri_accept_rect(W, WS, shadow, aA, tA, uA, vA, uB, vB, __float_as_int(a2.y));
-                    }
-                    for (int k = n_pairs * 2; k < P.flat_count; k++)
-#else
-                    for (int k = 0; k < P.flat_count; k++)
-#endif
-                    {
-                        const f4v a0 = ct[k * TRI_F4], a1 = ct[k * TRI_F4 + 1], a2 = ct[k * TRI_F4 + 2];
-                        const float4 t0 = make_float4(a0.x, a0.y, a0.z, a0.w), t1 = make_float4(a1.x, a1.y, a1.z, a1.w),
-                                     t2 = make_float4(a2.x, a2.y, a2.z, a2.w);
-#define PTK_ZERO_CLASS(c) case c: tri_math_pair<ZERO_CLASSES ? ptk_mt::flat_zero_mask(c) : 0u>(W, R, t0, t1, t2, ma, mu, mv, mt); break;
-                        if (ZERO_CLASSES)
-                        {
-                            // (only the arithmetic is switched: the accept chain and the hit records follow once, for all classes)
-                            f2 ma, mu, mv, mt;
-                            switch ((unsigned)(classes >> (k * 4)) & 15u)
-                            {
-                                PTK_ZERO_CLASS(1) PTK_ZERO_CLASS(2) PTK_ZERO_CLASS(3) PTK_ZERO_CLASS(4) PTK_ZERO_CLASS(5)
-                                PTK_ZERO_CLASS(6) PTK_ZERO_CLASS(7) PTK_ZERO_CLASS(8) PTK_ZERO_CLASS(9) PTK_ZERO_CLASS(10)
-                                PTK_ZERO_CLASS(11) PTK_ZERO_CLASS(12) PTK_ZERO_CLASS(13) PTK_ZERO_CLASS(14) PTK_ZERO_CLASS(15)
-                                default: tri_math_pair<0u>(W, R, t0, t1, t2, ma, mu, mv, mt); break;
-                            }
-                            (void)tri_accept_pair<STATS, PLAIN>(P, W, WS, shadow, ma, mu, mv, mt, t2, rng, bounce_ray, ray, cnt);
-                        }
-                        else
-                            (void)tri_test_pair<STATS, PLAIN>(P, W, WS, R, shadow, t0, t1, t2, rng, bounce_ray, ray, cnt);
-#undef PTK_ZERO_CLASS
-                    }
-                    if (shadow)
-                    {
-                        // DirectIllumimation visibility (pathtracer.cpp:522-526): lit unless something else is closest
-                        if (STATS) { cnt.rays++; cnt.shadow++; }
-                        if (!(WS.best.tri != PTK_NOHIT && WS.best.tri != WS.occl_tri)) L = add(L, Tdi);
-                        WS.occl_tri = -1;
-                        ray++;
-                    }
-                    W.node = NODE_EXIT;
-                    PTK_WALK_DONE();
+#include "ptk_trace_pass.h"
                 }
                 continue;
             }
@@ -650,32 +588,7 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
             if (STATS) { const uint32_t nsx = (uint32_t)__popcll(__ballot(st == ST_SHADE)); if (lane == 0) { cnt.shade_execs++; cnt.shade_lanes += nsx; } }
             if (st == ST_SHADE)
             {
-                if (depth < 0)
-                {
-                    // a path dealt since the last shade block.  Pinhole camera, no stochastic opacity: every sample of this
-                    // pixel shoots the same camera ray, so its direction and closest hit were computed once (primary_hits_kernel)
-                    // and the path starts at its first surface interaction (pixels whose camera ray misses are never dealt).
-                    // The stream is set up as in the camera-ray block below, and the two SampleCircle draws a pinhole frame
-                    // still consumes (pathtracer.cpp:787, always two) only advance it - two LCG steps in one:
-                    //   s2 = (s * a + inc) * a + inc = s * a^2 + inc * (a + 1)      (mod 2^32: the identical state)
-                    const uint2 pr = P.pixel_rng[pix];
-                    const float4 c = P.primary_hit[pix], r = P.primary_rd[pix];
-                    rng.inc = pr.y;
-                    rng.state = hash32(P.first_sample + sample_abs + pr.x);
-                    rng.key = rng.state;
-                    rng.state = rng.state * (747796405u * 747796405u) + rng.inc * (747796405u + 1u);
-                    L = V(0.0f, 0.0f, 0.0f); T = V(1.0f, 1.0f, 1.0f);
-                    depth = 0; iter = 0; inside = false; ray = 1;
-                    W.occl_tri = -1;
-                    if (STATS) cnt.started++;
-                    W.ro = camPos0; W.rd = V(r.x, r.y, r.z);
-                    W.best.tri = __float_as_int(c.x); W.best.t = c.y; W.best.u = c.z; W.best.v = c.w;
-                    W.node = NODE_EXIT; W.top = stack; W.tri_left = 0;
-                }
-                // ---- one surface interaction of PathTracer::Trace, pathtracer.cpp:551-727 ----
-                const bool ended = shade_interaction<STATS, FLAT, PLAIN, LAMBERT>(P, W, WS, stack, rng, L, T, Tdi, nextDir, depth, iter, inside, ray, cnt);
-                if (ended) PTK_FINISH_PATH();
-                else st = ST_TRAV;
+#include "ptk_trace_shade.h"
             }
         }
         else if (!PLAIN)
@@ -717,8 +630,10 @@ __global__ __launch_bounds__(PTK_TRACE_BLOCK, (PLAIN ? PTK_TRACE_WAVES_PLAIN : F
             }
         }
     }
+#endif  // !PTK_CYCLE_UNIT
 #undef PTK_WALK_DONE
 #undef PTK_FINISH_PATH
+#undef PTK_U_MAX_DEPTH
     if (STATS)
     {
         atomicAdd(&P.stats[0], (unsigned long long)cnt.started);
@@ -752,12 +667,17 @@ void launch_trace_plain(bool lambert, int blocks, hipStream_t stream, const Rend
 // ... and once more by ptk_kernels_rect.hip (PTK_RECT_UNIT on top of PTK_PLAIN_UNIT, the same flags): the same two instantiations under
 // the name trace_kernel_rect, whose pass tests the list's prefix of fan-split rectangles pair by pair (RenderParams::plain == 2)
 void launch_trace_rect(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp);
+// ... and by ptk_kernels_cycle.hip (PTK_CYCLE_UNIT on top of both, the PLAIN unit's flags): the pair unit's pass and shade block under
+// the name trace_kernel_cycle, in a fixed shade / pass cycle with a scalar unit deal (RenderParams::plain == 3, the flat_cycle option)
+void launch_trace_cycle(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp);
 #endif
 #ifdef PTK_PLAIN_UNIT
 #if PTK_CONTRACT
 #error "the PLAIN unit belongs to the exact build: the contracted builds keep their PLAIN kernels in ptk_kernels.hip"
 #endif
-#ifdef PTK_RECT_UNIT
+#if defined(PTK_CYCLE_UNIT)
+void launch_trace_cycle(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp)
+#elif defined(PTK_RECT_UNIT)
 void launch_trace_rect(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp)
 #else
 void launch_trace_plain(bool lambert, int blocks, hipStream_t stream, const RenderParams* dp)
@@ -846,6 +766,7 @@ void launch_trace(const RenderParams& p0, int num_subtiles, int resident_waves, 
 #if !PTK_CONTRACT
     if (stats && flat) hipLaunchKernelGGL((trace_kernel<true, true, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
     else if (stats) hipLaunchKernelGGL((trace_kernel<true, false, false>), dim3(blocks), dim3(PTK_TRACE_BLOCK), 0, stream, dp);
+    else if (flat && p.plain == 3) launch_trace_cycle(p.lambert != 0, blocks, stream, dp); // (the cycle unit: the flat_cycle option on top of flat_rect_pairs)
     else if (flat && p.plain == 2) launch_trace_rect(p.lambert != 0, blocks, stream, dp);  // (the pair-pass unit: the flat_rect_pairs option)
     else if (flat && p.plain) launch_trace_plain(p.lambert != 0, blocks, stream, dp);      // (the unit built for the class switch, above)
     else

@@ -162,7 +162,7 @@ SYMBOLS = [
     "ptk_gather_wait", "ptk_read_gathered", "ptk_gathered_device_ptr", "ptk_probe_pack", "ptk_probe_unpack",
     "ptk_bind_out_image", "ptk_bind_out_device", "ptk_bind_gl_buffer", "ptk_comm_info", "ptk_kernel_log", "ptk_kernel_log_read",
     "ptk_debug_stall_exchange", "ptk_render_adaptive", "ptk_read_sample_counts", "ptk_read_moments",
-    "ptk_trace_variant", "ptk_scene_is_plain", "ptk_scene_is_lambert", "ptk_trace_is_lambert",
+    "ptk_trace_variant", "ptk_scene_is_plain", "ptk_scene_is_lambert", "ptk_trace_is_lambert", "ptk_trace_unit",
     "ptk_flat_zero_class", "ptk_flat_zero_mask", "ptk_flat_classes", "ptk_flat_rect_pair", "ptk_flat_rect_pairs",
     "ptk_feature_info", "ptk_render_features", "ptk_read_feature", "ptk_feature_device_ptr", "ptk_pick",
     "ptk_update_geometry", "ptk_update_geometry_device", "ptk_geometry_info", "ptk_geometry_timing",
@@ -365,6 +365,7 @@ def _load_locked() -> C.CDLL:
         L.ptk_last_upsample_ms.argtypes = [vp, fp, fp]
         L.ptk_scene_is_lambert.argtypes = [C.POINTER(SceneDesc)]
         L.ptk_trace_is_lambert.argtypes = [vp, C.POINTER(C.c_int)]
+        L.ptk_trace_unit.argtypes = [vp, C.POINTER(C.c_int)]
         L.ptk_flat_zero_class.argtypes = [C.POINTER(C.c_float)]
         L.ptk_flat_zero_mask.argtypes = [C.c_int]
         L.ptk_flat_classes.argtypes = [vp, C.POINTER(i32)]
@@ -395,6 +396,7 @@ def _load_locked() -> C.CDLL:
 
 
 TRACE_NONE, TRACE_BVH, TRACE_FLAT, TRACE_FLAT_PLAIN = 0, 1, 2, 3      # ptk_trace_variant
+UNIT_NONE, UNIT_PLAIN, UNIT_RECT, UNIT_CYCLE = 0, 1, 2, 3              # ptk_trace_unit
 RAYS_ACCUMULATE, RAYS_LENS_DRAWS = 1, 2                               # ptk_trace_rays flags
 BAKE_ACCUMULATE, BAKE_BACK = 1, 2                                     # ptk_bake_lightmap flags
 PROBES_ACCUMULATE = 1                                                 # ptk_bake_probes flags
@@ -1940,6 +1942,12 @@ class Context:
         v = C.c_int(0)
         self._chk(self.L.ptk_trace_is_lambert(self.h, C.byref(v)), "ptk_trace_is_lambert")
         return bool(v.value)
+
+    def trace_unit(self) -> int:
+        """Which unit's kernel the newest launch ran, for the bit-exact PLAIN kernels: UNIT_PLAIN / UNIT_RECT / UNIT_CYCLE, else UNIT_NONE."""
+        v = C.c_int(0)
+        self._chk(self.L.ptk_trace_unit(self.h, C.byref(v)), "ptk_trace_unit")
+        return v.value
 
     def flat_classes(self) -> list:
         """The device's zero class of every triangle of the flat list (scenes of <= 16 triangles), in triangle order."""

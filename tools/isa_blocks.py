@@ -12,7 +12,8 @@ conditional branches (and how many are taken), unconditional branches, flag-test
 s_andn2_b64 / s_and_b64 vcc, exec, <flag>) and VALU; with a class list, the sums over it (one pass of a scene with those records).
 Also checks the kernel's control flow: every s_and_saveexec_b64 is closed by an s_or_b64 exec on every route (check_exec_regions)
 and lists the natural loops with their back edges and exits (loops).  On a kernel of the pair unit (csrc/ptk_kernels_rect.hip) the
-pair loop in front of the record loop is walked the same way, per kind 1..6 (pair_header, route_table(K, pair_header(K), range(1, 7)))."""
+pair loop in front of the record loop is walked the same way, per kind 1..6 (pair_header, route_table(K, pair_header(K), range(1, 7))).
+--routes also prints deal_route: what lies between the pass's latch and the shade block on the route of one deal of one round."""
 import re, sys
 HALF = re.compile(r"^v_(cmp|cmpx|cndmask|min|max|med3|cvt|bfe|perm|and_or|mad_u32|mul_lo|mul_hi|lshl_add|lshl_or|add_lshl|div_|pk_|bfi|alignbit|sad|mad_i32|mad_u64|add3|xad|or3|readlane|readfirstlane|writelane|ldexp|frexp|fract|trunc|floor|rndne|ceil)")
 TRANS = re.compile(r"^v_(rcp|sqrt|rsq|exp|log|sin|cos)")
@@ -246,6 +247,71 @@ def route_table(K, header=None, classes=range(16)):
     return table, K.ins[join][0]
 
 
+# ---- the stretch between the pass and the shade block --------------------------------------------------------------------------
+def shortest_route(K, start, goal):
+    """the static route with the fewest instructions from instruction `start` to instruction `goal` (both included), every branch free
+    to go either way - a lower bound of what a wave executes between the two: a list of instruction indices, None if there is none"""
+    from collections import deque
+    prev = {start: None}; todo = deque([start])
+    while todo:
+        i = todo.popleft()
+        if i == goal: break
+        succ = K.targets(i)[0]
+        for t in succ:
+            if t < len(K.ins) and t not in prev:
+                prev[t] = i; todo.append(t)
+    if goal not in prev: return None
+    out = []; i = goal
+    while i is not None: out.append(i); i = prev[i]
+    return out[::-1]
+
+
+def pass_exit(K):
+    """index of the first instruction behind the record loop: where a wave stands when the pass's latch falls through"""
+    ph = pass_header(K)[0]
+    l = [x for x in loops(K) if x["header_index"] == ph]
+    assert len(l) == 1 and len(l[0]["back_edges"]) == 1, l
+    i = [k for k, ins in enumerate(K.ins) if ins[0] == l[0]["back_edges"][0]][0]
+    assert K.ins[i][1].startswith("s_cbranch_scc"), K.ins[i]
+    t = K.label[K.ins[i][2][0]]
+    assert ph in (t, i + 1), K.ins[i]               # the latch branches back and falls out, or branches out and falls into the header
+    return i + 1 if t == ph else t
+
+
+def shade_start(K):
+    """index of the shade block's first instruction: the path start's `depth < 0` compare, the nearest v_cmp_gt_i32 0 > v in front of the
+    instruction that carries hash32's additive constant (the stream set-up of a new path, the first thing the block does)"""
+    at = [k for k, ins in enumerate(K.ins) if "0xac564b05" in ins[2]]
+    assert len(at) == 1, at
+    for i in range(at[0], -1, -1):
+        if K.ins[i][1].startswith("v_cmp_gt_i32") and "0" in K.ins[i][2]: return i
+    raise AssertionError("no depth < 0 test in front of the path start")
+
+
+def deal_route(K):
+    """The stretch that produces nothing of the image: from the pass's latch through ONE deal of ONE round - the shortest static route
+    that passes a read of lds_pixel_of_rank (ds_read_u8: only the deal has one; the masked regions it need not enter, such as the
+    shadow ray's resolve behind the pass, are skipped in every kernel alike) - to the first instruction of the shade block.
+    Returns (instruction indices, counts): VALU, scalar ALU, LDS reads, and the s_waitcnt that wait for lgkmcnt."""
+    a, b = pass_exit(K), shade_start(K)
+    best = None
+    for w in [k for k, ins in enumerate(K.ins) if ins[1] == "ds_read_u8"]:
+        r1, r2 = shortest_route(K, a, w), shortest_route(K, w, b)
+        if r1 is None or r2 is None: continue
+        r = r1 + r2[1:-1]                    # (the shade block's first instruction is where the route ends, not part of it)
+        if best is None or len(r) < len(best): best = r
+    assert best, "no route from the pass through a deal to the shade block in " + K.name
+    c = dict(valu=0, salu=0, lds=0, smem=0, lgkm_waits=0, instructions=len(best))
+    for i in best:
+        op, ops = K.ins[i][1], K.ins[i][2]
+        if op.startswith("v_"): c["valu"] += 1
+        elif op.startswith("ds_"): c["lds"] += 1
+        elif op.startswith("s_load") or op.startswith("s_buffer_load"): c["smem"] += 1
+        elif op.startswith("s_waitcnt"): c["lgkm_waits"] += 1 if any("lgkmcnt" in o for o in ops) else 0
+        elif op.startswith("s_") and op != "s_nop": c["salu"] += 1
+    return best, c
+
+
 # ---- control-flow integrity ---------------------------------------------------------------------------------------------------
 def check_exec_regions(K):
     """Every s_and_saveexec_b64 sD, ... must be closed by s_or_b64 exec, exec, sD on every route from it to a loop latch or the kernel's
@@ -357,6 +423,8 @@ def main():
             print("whole iterations: " + str({k: sum(table[c]["whole_iteration"][k] for c in cl) for k in ("salu", "cbranch", "cbranch_taken", "branch", "taken", "valu", "smem", "wait")}))
         bad, n, narrowing = check_exec_regions(K)
         print("saveexec regions: %d, violations: %s; other writes of exec at lines %s" % (n, bad, narrowing))
+        try: print("pass latch -> one deal of one round -> shade block: %s" % deal_route(K)[1])
+        except AssertionError as e: print("no deal route: %s" % e)
         ph = pass_header(K)[0]
         pp = pair_header(K)[0] if len(nibble_headers(K)) == 2 else -1
         if pp >= 0:

@@ -8,7 +8,7 @@
 # between files still compares by name - and diffs each kernel matching the regex.  Exit status 0: every such kernel is identical.
 # A tree that has ptk_kernels_plain.hip (the exact PLAIN trace kernels' unit) gets that unit built at the exact level too, with the
 # unit's own flags as csrc/Makefile states them (PLAIN_UNIT_FLAGS), so those two kernels compare as they are built; likewise
-# ptk_kernels_rect.hip (the pair unit) with RECT_UNIT_FLAGS on top of those.
+# ptk_kernels_rect.hip (the pair unit) with RECT_UNIT_FLAGS on top of those, and ptk_kernels_cycle.hip (the cycle unit) with CYCLE_UNIT_FLAGS.
 set -euo pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 REV=${1:-HEAD}
@@ -26,6 +26,7 @@ one() {  # <csrc> <outdir> <level> <source>
     [ "$lvl" != 0 ] && extra="-DPTK_CONTRACT=$lvl -ffp-contract=fast"
     [ "$src" = ptk_kernels_plain.hip ] && extra=$(sed -n 's/^PLAIN_UNIT_FLAGS[ \t]*?=[ \t]*//p' "$csrc/Makefile")
     [ "$src" = ptk_kernels_rect.hip ] && extra="$(sed -n 's/^PLAIN_UNIT_FLAGS[ \t]*?=[ \t]*//p' "$csrc/Makefile") $(sed -n 's/^RECT_UNIT_FLAGS[ \t]*?=[ \t]*//p' "$csrc/Makefile")"
+    [ "$src" = ptk_kernels_cycle.hip ] && extra="$(sed -n 's/^PLAIN_UNIT_FLAGS[ \t]*?=[ \t]*//p' "$csrc/Makefile") $(sed -n 's/^CYCLE_UNIT_FLAGS[ \t]*?=[ \t]*//p' "$csrc/Makefile")"
     (cd "$csrc" && $HIPCC -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include -I. -Wall -Wno-unused-function -fno-slp-vectorize \
         --offload-arch=gfx950 $extra --offload-device-only -c "$src" -o "$obj.bundle")
     $LLVM/clang-offload-bundler --unbundle --type=o --input="$obj.bundle" --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output="$obj.co"
@@ -36,7 +37,7 @@ disasm() {  # <tree> <outdir>
     local csrc=$1/pbrpathtracer_amd/csrc out=$2 src
     mkdir -p "$out"
     for lvl in 0 1 2; do one "$csrc" "$out" $lvl ptk_kernels.hip; done
-    for src in ptk_frame.hip ptk_kernels_plain.hip ptk_kernels_rect.hip $EXTRA_SRCS; do
+    for src in ptk_frame.hip ptk_kernels_plain.hip ptk_kernels_rect.hip ptk_kernels_cycle.hip $EXTRA_SRCS; do
         [ -f "$csrc/$src" ] && one "$csrc" "$out" 0 "$src"
     done
     return 0
