@@ -314,6 +314,18 @@ public:
     // the sample count are not touched.
     bool MultiHitRays(int num_rays, const float* origins, const float* dirs, const float* tmax, int max_hits, int32_t* count, int32_t* tri,
                       float* t, float* bary, int8_t* side);
+    // Extension: surface sampling (include/ptk.h ptk_sample_surface / ptk_surface_weights, host arrays, synchronous) at the class's
+    // seed: num_samples points of the scene's surface, a triangle drawn in proportion to its area times its weight, the point
+    // uniform on it; sample j is a function of (seed, key_base + j, sample) and the scene alone.  tri, material: 1 per sample; bary:
+    // 2; position, normal: 3; each may be null.  SetSurfaceWeights: one weight per triangle, finite and >= 0, or null for the areas
+    // alone; BuildBVH() drops them.  Valid after BuildBVH() with no resolution set; pending SetObjectTransform edits apply first, as
+    // for the other queries; the image and the sample count are not touched.
+    bool SampleSurface(int num_samples, uint32_t key_base, uint32_t sample, int32_t* tri, float* bary, float* position, float* normal,
+                       int32_t* material);
+    bool SetSurfaceWeights(const float* weights);
+    // ... and the sampling table in force (ptk_surface_info): the sum of the quantised weights, the exponent E, the triangles that
+    // can be drawn and the largest weight; each may be null
+    bool SurfaceInfo(uint64_t* total, int32_t* exponent, int32_t* drawable, float* max_weight);
     // Extensions: lightmap baking (include/ptk.h ptk_bake_lightmap / ptk_bake_coverage / ptk_lightmap_dilate, host arrays,
     // synchronous) at the class's seed and trace depth.  uvs: [triangles][6] chart corners, or null for the scene's own uvs;
     // out: width*height*3 floats, rows bottom-up; owner (may be null): width*height triangle indices, -1 uncovered;

@@ -584,6 +584,61 @@ int ptk_multihit_rays_device(ptk_ctx* ctx, int32_t num_rays, const float* d_orig
  * call launched none); waits for the call */
 int ptk_last_multihit_ms(ptk_ctx* ctx, float* ms);
 
+/* ---- surface sampling: area-weighted points on the scene's triangles (no counterpart in the reference) ----------------------------
+ * Every other query starts from the caller's geometry and asks about the scene; this one gives points OF the scene's surface: point
+ * clouds for learning and registration, light sampling by power, scattering, probe candidates near walls, bakes that need neither
+ * vertices nor a uv layout.  A triangle is drawn with a probability proportional to its area, or to area x a caller weight, and a
+ * point on it uniformly.  No BVH is walked and no random draw of any other call is consumed.
+ * THE RULE.  Every output bit is determined by (seed, key_base + j, sample), the resident vertices and the weights; it depends neither
+ * on the launch shape, on how a range of samples is cut into calls, on "flat", on the tree nor on a refit
+ * (tests/test_gpu_surface_sample.py: array_equal with tests/surface_sample_rule.py).
+ * Weights.  For triangle i with the resident vertices v1 v2 v3 - as uploaded or as ptk_update_geometry left them -, every operation
+ * rounded to float32 and none contracted:
+ *   e1 = v2 - v1, e2 = v3 - v1, c = (e1.y e2.z - e2.y e1.z,  e1.z e2.x - e2.z e1.x,  e1.x e2.y - e2.x e1.y)
+ *   a_i = 0.5f * sqrtf((c.x c.x + c.y c.y) + c.z c.z)            and with caller weights  a_i = a_i * w_i, one float32 multiply
+ * A non-finite a_i is PTK_ERR_LIMIT.
+ * Quantised table.  m = max_i a_i; m == 0 is PTK_ERR_BAD_ARG (nothing to sample).  E = floor(log2 m).
+ *   q_i = trunc(a_i * 2^(35 - E)) as uint64 (the scaling is exact in float64), so q_i < 2^36 and the largest triangle has q >= 2^35
+ *   incl[i] = q_0 + .. + q_i in uint64, total = incl[N - 1] < 2^63
+ * TRIANGLES BELOW 2^-36 OF THE LARGEST WEIGHT GET q = 0 AND ARE NEVER DRAWN.  The sums are integers, so the order they are formed
+ * in on the GPU cannot show (the display histogram's precedent).
+ * Sample j of round `sample`.  The random stream is that of (seed, RNG pixel key_base + j mod 2^32, sample) as ptk_trace_rays sets it
+ * up: pkey = pixel_key(seed, key_base + j), inc = (hash32(pkey ^ 0x9E3779B9) << 1) | 1, state = hash32(sample + pkey); four
+ * consecutive raw outputs r0 .. r3 = pcg_out(state), with state = state * 747796405 + inc in between.
+ *   r64 = r0 << 32 | r1;  target = (r64 * total) >> 64, the high half of the 128-bit product, < total
+ *   tri = the smallest i with incl[i] > target: never a triangle with q = 0
+ *   su = sqrtf(u01(r2)), sv = u01(r3);  w0 = 1 - su, w1 = su * (1 - sv), w2 = su * sv      (u01(r) = (r >> 8) * 2^-24)
+ *   position = (v1 * w0 + v2 * w1) + v3 * w2, per component in that order
+ *   bary = (w1, w2), the (u, v) of the hit queries: weights of the second and third vertex
+ *   normal = the face normal as staged (tbn[tri][0:3], the feature plane NORMAL_GEOM's value);  material = material[tri]
+ * Progressive use: rounds `sample` = 0, 1, 2 .. of the same key range are independent sets; a range cut into calls with
+ * key_base = the global index of each call's first sample equals one call.
+ *   ptk_surface_weights / _device: sets (w: [triangles] float32, finite, >= 0) or clears (NULL) the per-triangle weights; they are
+ *     copied into the context, and the table is rebuilt by the next call that needs it.  A negative or non-finite weight is
+ *     PTK_ERR_BAD_ARG and leaves weights and table as they were: the host form checks before any device work, the _device form
+ *     with one kernel and one word read back.  ptk_upload_scene drops weights and table.
+ *   ptk_sample_surface: host arrays, synchronous; the requested outputs are staged in device memory for the length of the call.
+ *   ptk_sample_surface_device: every array in memory of this context's GPU, asynchronous on the context's stream (the caller's
+ *     after ptk_set_stream) once the table stands; d_bary must be 8-byte aligned (PTK_ERR_BAD_ARG otherwise: a sample's two
+ *     barycentrics leave as one store), the other arrays as their element type.  Where the table is missing or stale - first use, after ptk_surface_weights,
+ *     after ptk_update_geometry - the call builds it first, in stream order behind the update, and waits once for eight bytes.
+ *   Any output may be NULL.  n == 0 is PTK_OK and does nothing.  PTK_ERR_BAD_ARG without a scene, for n < 0, for a scene without
+ *     triangles and where every weight is zero.  The calls touch neither the accumulator, the sample count, the feature planes nor
+ *     any other state, and no existing entry behaves differently whether or not a table exists.
+ *   ptk_surface_info: total, E, the number of triangles with q > 0 and m of the table in force (built where needed).
+ * Memory: 8 B per triangle for incl (+ 8 KiB), 4 B per triangle of weights while some are set, and the prefix sum's workgroup sums
+ * (8 B per 4096 triangles), made by the first use for a scene and freed with it.  Limits: one thread per sample, in one launch. */
+int ptk_surface_weights(ptk_ctx* ctx, const float* w /*[triangles] or NULL*/);
+int ptk_surface_weights_device(ptk_ctx* ctx, const float* d_w);
+int ptk_sample_surface(ptk_ctx* ctx, int32_t n, uint32_t key_base, uint32_t sample, uint64_t seed, int32_t* tri /*[n]*/,
+                       float* bary /*[n][2]*/, float* position /*[n][3]*/, float* normal /*[n][3]*/, int32_t* material /*[n]*/);
+int ptk_sample_surface_device(ptk_ctx* ctx, int32_t n, uint32_t key_base, uint32_t sample, uint64_t seed, int32_t* d_tri, float* d_bary,
+                              float* d_position, float* d_normal, int32_t* d_material);
+int ptk_surface_info(ptk_ctx* ctx, uint64_t* total, int32_t* exponent /*E*/, int32_t* drawable /*triangles with q > 0*/, float* max_weight);
+/* measurement hook (tools/surface_sample_timing.py), not part of the feature: the HIP-event times of the last ptk_sample_surface call -
+ * its table build (0 where it built none) and its kernel; waits for the call */
+int ptk_last_surface_ms(ptk_ctx* ctx, float* table_ms, float* sample_ms);
+
 /* ---- a-trous denoiser for image planes and for the frame (no counterpart in the reference) ------------------------------------
  * Turns a noisy low-sample image - a frame of a few samples per pixel, a lightmap of 16 to 64 per texel - into a usable one: an
  * edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by normals, positions and luminance, optionally by the
@@ -1515,6 +1570,9 @@ int ptk_probe_unpack(ptk_ctx* ctx, int world, const float* host_packed /* all ra
  * "flat_cycle" = 0/1 (default 1; acts with "flat_rect_pairs" on): that kernel is launched from a third unit, the same pass and shade
  * block in a fixed deal / shade / pass cycle without the block vote, its work units dealt from scalar registers; 0 launches the pair
  * unit's kernel.  Bit-identical either way (tests/test_gpu_flat_cycle.py); decided per render.  ptk_trace_unit tells which one ran.
+ * "surface_variant" = 0/1 (default 1): ptk_sample_surface's kernel searches a coarse table of 1024 sums staged in LDS before the
+ * sums themselves; 0 searches the sums alone (tools/surface_sample_timing.py).  Bit-identical either way
+ * (tests/test_gpu_surface_sample.py).
  * No environment variable reaches the library. */
 int ptk_set_option(ptk_ctx* ctx, const char* name, double value);
 
@@ -1606,6 +1664,12 @@ int ptk_probe_direct(ptk_ctx* ctx, int n, const float* points, const float* norm
  * polynomial for angles in [0, 2 pi].  In the exact build ops 0-3 return the bits of the IEEE-754 operation the reference's
  * CPU code performs (1.0f / a, sqrtf(x)) and ops 4 / 5 those of the CPU oracle's polynomial. */
 int ptk_probe_math(ptk_ctx* ctx, int op, int n, const float* in, float* out);
+/* the surface sampler's table as ptk_sample_surface would use it now (built where missing or stale): incl[triangles] */
+int ptk_probe_surface_table(ptk_ctx* ctx, uint64_t* incl);
+/* the table's prefix sum on caller data: out[i] = in[0] + .. + in[i] mod 2^64, reduce-then-scan with items_per_workgroup (>= 2)
+ * items per workgroup, so few items reach every level of the recursion; 0 = the table's own, PTK_SURFACE_SCAN_ITEMS */
+#define PTK_SURFACE_SCAN_ITEMS 4096
+int ptk_probe_scan_u64(ptk_ctx* ctx, int32_t n, const uint64_t* in, uint64_t* out, int32_t items_per_workgroup);
 
 #ifdef __cplusplus
 }

@@ -121,6 +121,12 @@ int  pth_signed_distance(pth_tracer* t, int num_points, const float* points, con
  * output but one may be NULL */
 int  pth_multihit_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, const float* tmax, int max_hits, int32_t* count,
                        int32_t* tri, float* hit_t, float* bary, int8_t* side);
+/* SampleSurface / SetSurfaceWeights (area-weighted points on the scene's triangles at the tracer's seed, include/ptk.h
+ * ptk_sample_surface / ptk_surface_weights): 1 on success; any output and the weights may be NULL */
+int  pth_sample_surface(pth_tracer* t, int num_samples, uint32_t key_base, uint32_t sample, int32_t* tri, float* bary, float* position,
+                        float* normal, int32_t* material);
+int  pth_set_surface_weights(pth_tracer* t, const float* weights);
+int  pth_surface_info(pth_tracer* t, uint64_t* total, int32_t* exponent, int32_t* drawable, float* max_weight);
 /* BakeLightmap / BakeCoverage / DilateLightmap (lightmap baking, include/ptk.h ptk_bake_lightmap with the tracer's seed and trace
  * depth): 1 on success */
 int  pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,

@@ -1155,6 +1155,38 @@ bool PathTracer::TraceRays(int num_rays, const float* origins, const float* dirs
     return rc == PTK_OK;
 }
 
+// Points of the scene's surface (ptk_sample_surface) at the class's seed, on the scene as the next RenderFrame() would see it, and
+// the per-triangle weights they are drawn by (ptk_surface_weights)
+bool PathTracer::SampleSurface(int num_samples, uint32_t key_base, uint32_t sample, int32_t* tri, float* bary, float* position, float* normal,
+                               int32_t* material)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_sample_surface(m->ctx, num_samples, key_base, sample, m->seed, tri, bary, position, normal, material);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::SetSurfaceWeights(const float* weights)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    const int rc = ptk_surface_weights(m->ctx, weights);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::SurfaceInfo(uint64_t* total, int32_t* exponent, int32_t* drawable, float* max_weight)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_surface_info(m->ctx, total, exponent, drawable, max_weight);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 // Closest hits and occlusion along caller-supplied rays (ptk_intersect_rays, ptk_occluded_rays) in the scene as the next
 // RenderFrame() would see it
 bool PathTracer::IntersectRays(int num_rays, const float* origins, const float* dirs, uint32_t sample, uint32_t key_base, int32_t* tri, float* t,

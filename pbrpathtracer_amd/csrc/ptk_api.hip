@@ -634,6 +634,8 @@ void ptk_destroy(ptk_ctx* c)
     dfree(c->d_closest_stats);
     for (hipEvent_t e : c->ev_crossings) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_multihit) if (e) (void)hipEventDestroy(e);
+    surface_release(c);
+    for (hipEvent_t e : c->ev_surface) if (e) (void)hipEventDestroy(e);
     dfree(c->d_denoise);
     for (hipEvent_t e : c->ev_denoise) if (e) (void)hipEventDestroy(e);
     dfree(c->d_temporal_pack);
@@ -844,6 +846,7 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
     dfree(c->d_texinfo); dfree(c->d_texels);
     dfree(c->d_verts_res); free_geometry_cache(c);
     dfree(c->d_verts_prev); c->have_snapshot = false;             // (ptk_geometry_snapshot: of the scene that goes)
+    surface_release(c);                                            // (ptk_sample_surface: its table and weights likewise)
     c->lights_stale = false;
     c->have_scene = false;
     auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
@@ -1840,6 +1843,11 @@ int ptk_set_option(ptk_ctx* c, const char* name, double value)
             c->inputs_dirty = true;
         }
         c->opt_flat_rect_pairs = use;
+        return PTK_OK;
+    }
+    if (!std::strcmp(name, "surface_variant"))
+    {
+        c->opt_surface_variant = value != 0.0 ? 1 : 0;          // (which instantiation the next ptk_sample_surface launches: nothing on the device changes)
         return PTK_OK;
     }
     if (!std::strcmp(name, "flat_cycle"))

@@ -5,6 +5,7 @@
 
 #include "ptk_ctx.h"
 #include "ptk_stage.h"
+#include "ptk_surface.h"
 
 using namespace ptk;
 
@@ -78,6 +79,38 @@ int ptk_probe_primary_dirs(ptk_ctx* c, float* host_out)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < px; i++) { host_out[i * 3] = tmp[i].x; host_out[i * 3 + 1] = tmp[i].y; host_out[i * 3 + 2] = tmp[i].z; }
     return PTK_OK;
+}
+
+// the surface sampler's table as ptk_sample_surface would use it now (built where missing or stale): incl[num_tris]
+int ptk_probe_surface_table(ptk_ctx* c, uint64_t* incl)
+{
+    if (!c || !incl) return PTK_ERR_BAD_ARG;
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (const int rc = ensure_surface_table(c); rc != PTK_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(incl, c->d_surf_table, (size_t)c->num_tris * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PTK_OK;
+}
+
+// the table's prefix sum (launch_scan_u64) on caller data: out[i] = in[0] + .. + in[i] mod 2^64; items_per_workgroup 0: the table's own
+int ptk_probe_scan_u64(ptk_ctx* c, int32_t n, const uint64_t* in, uint64_t* out, int32_t items_per_workgroup)
+{
+    if (!c || n < 0 || (n > 0 && (!in || !out))) return PTK_ERR_BAD_ARG;
+    const int items = items_per_workgroup == 0 ? SURF_SCAN_ITEMS : items_per_workgroup;
+    if (items < 2) return fail(c, PTK_ERR_BAD_ARG, "ptk_probe_scan_u64: at least two items per workgroup");
+    if (n == 0) return PTK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    uint64_t* d_sums = nullptr;
+    HIPCHK(c, hipMalloc(&d_sums, (scan_u64_sums((size_t)n, items) + 1) * sizeof(uint64_t)));
+    Stage s(c);
+    const auto d_in = s.in(in, (size_t)n), d_out = s.out(out, (size_t)n);
+    const int rc = s.run([&] {
+        launch_scan_u64(d_in, d_out, (size_t)n, items, d_sums, c->stream);
+        return s.launched();
+    });
+    (void)hipFree(d_sums);
+    return rc;
 }
 
 }  // extern "C"

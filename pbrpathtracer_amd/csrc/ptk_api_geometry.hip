@@ -162,6 +162,7 @@ static int update_geometry(ptk_ctx* c, int32_t first, int32_t count, const float
     if (c->num_lights > 0) c->lights_stale = true;
     c->geo_updates++;
     c->sah_now_pending = true;
+    c->surf_valid = false;                       // (ptk_sample_surface rebuilds its table behind these kernels)
     c->view_generation++;
     c->primary_hit_dirty = true;
     c->out_full_next = true;

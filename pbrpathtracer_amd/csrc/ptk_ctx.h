@@ -206,6 +206,24 @@ struct ptk_ctx {
     hipEvent_t ev_multihit[2] = { nullptr, nullptr };
     bool multihit_timed = false;
 
+    // surface sampling (ptk_sample_surface, ptk_surface_weights).  The table, 8 B per triangle - the inclusive sums of the quantised
+    // weights - with the 8 KiB coarse table behind it; the caller's weights (4 B per triangle) while some are set; the workgroup
+    // sums of the scan; the reduction block of the build.  All made by the first use for a scene and freed with it.  surf_valid: the
+    // table holds the resident vertices and the weights as they are (ptk_update_geometry and ptk_surface_weights clear it).  What
+    // ptk_surface_info reports: exponent and max from the build, total and drawable read back once asked for.  Four events: around
+    // the last build, around the last call's kernel; surf_table_timed: the last call built the table
+    uint64_t* d_surf_table = nullptr;
+    float* d_surf_weights = nullptr;
+    uint64_t* d_surf_sums = nullptr;
+    uint32_t* d_surf_red = nullptr;
+    bool surf_valid = false, surf_info_pending = false;
+    uint64_t surf_total = 0;
+    int surf_exponent = 0, surf_drawable = 0;
+    float surf_max = 0.0f;
+    hipEvent_t ev_surface[4] = { nullptr, nullptr, nullptr, nullptr };
+    bool surf_table_timed = false, surf_sample_timed = false;
+    int opt_surface_variant = 1;                 // surface_sample_kernel's variant (ptk_surface.h; 1: the coarse table in LDS): speed only
+
     // a-trous denoiser (ptk_denoise_planes, ptk_denoise_frame): the four packed float4 images of a call (64 B per pixel, grown to the
     // largest call so far); the denoised frame [H][W][3], made by the first ptk_denoise_frame, freed with the feature planes, and
     // the resolution it was last written at; four events of the last call: before the pack, behind it, behind the filter, behind
@@ -424,6 +442,10 @@ int check_denoise_params(ptk_ctx* c, const char* who, const ptk_denoise_params* 
 int denoise_planes_on_stream(ptk_ctx* c, int width, int height, const float* d_color, const int32_t* d_mask, const float* d_normal,
                              const float* d_position, const float* d_albedo, const float* d_variance, const ptk_denoise_params& p,
                              float* d_out_color, float* d_out_variance);
+// ... ptk_api_surface.hip: frees the sampling table and the weights of the scene that goes; builds the table where it is missing or
+// stale, on the context's stream (one host wait, for the eight bytes of the build's reduction)
+void surface_release(ptk_ctx* c);
+int ensure_surface_table(ptk_ctx* c);
 // ... ptk_api_exchange.hip: destroys the context's own communicator, if there is one
 void comm_release(ptk_ctx* c);
 

@@ -193,6 +193,16 @@ int pth_multihit_rays(pth_tracer* t, int num_rays, const float* origins, const f
 {
     return t->pt.MultiHitRays(num_rays, origins, dirs, tmax, max_hits, count, tri, hit_t, bary, side) ? 1 : 0;
 }
+int pth_sample_surface(pth_tracer* t, int num_samples, uint32_t key_base, uint32_t sample, int32_t* tri, float* bary, float* position,
+                       float* normal, int32_t* material)
+{
+    return t->pt.SampleSurface(num_samples, key_base, sample, tri, bary, position, normal, material) ? 1 : 0;
+}
+int pth_set_surface_weights(pth_tracer* t, const float* weights) { return t->pt.SetSurfaceWeights(weights) ? 1 : 0; }
+int pth_surface_info(pth_tracer* t, uint64_t* total, int32_t* exponent, int32_t* drawable, float* max_weight)
+{
+    return t->pt.SurfaceInfo(total, exponent, drawable, max_weight) ? 1 : 0;
+}
 int pth_contains_points(pth_tracer* t, int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside, int32_t* winding)
 {
     return t->pt.ContainsPoints(num_points, points, num_dirs, dirs, mode, inside, winding) ? 1 : 0;

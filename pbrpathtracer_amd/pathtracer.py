@@ -40,6 +40,7 @@ HOST_SYMBOLS = [
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
     "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points",
     "pth_crossings_rays", "pth_contains_points", "pth_signed_distance", "pth_multihit_rays",
+    "pth_sample_surface", "pth_set_surface_weights", "pth_surface_info",
     "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised", "pth_temporal_frame", "pth_read_temporal", "pth_get_view",
     "pth_track_motion", "pth_temporal_frame_moving", "pth_read_motion", "pth_temporal_frame_moments", "pth_temporal_variance",
     "pth_read_temporal_variance", "pth_denoise_temporal", "pth_get_object_transform",
@@ -121,6 +122,9 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_closest_points.restype = i32; L.pth_closest_points.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
         L.pth_crossings_rays.restype = i32; L.pth_crossings_rays.argtypes = [vp, i32, vp, vp, vp, vp, vp]
         L.pth_multihit_rays.restype = i32; L.pth_multihit_rays.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.pth_sample_surface.restype = i32; L.pth_sample_surface.argtypes = [vp, i32, u32, u32, vp, vp, vp, vp, vp]
+        L.pth_set_surface_weights.restype = i32; L.pth_set_surface_weights.argtypes = [vp, vp]
+        L.pth_surface_info.restype = i32; L.pth_surface_info.argtypes = [vp, vp, vp, vp, vp]
         L.pth_contains_points.restype = i32; L.pth_contains_points.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp]
         L.pth_signed_distance.restype = i32; L.pth_signed_distance.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.pth_denoise_frame.restype = i32; L.pth_denoise_frame.argtypes = [vp, C.POINTER(_ptk.DenoiseParams), i32]
@@ -683,6 +687,34 @@ class PathTracer:
         return out
 
     MultiHitRays = multihit_rays
+
+    def sample_surface(self, n, key_base=0, sample=0):
+        """Extension: (tri [n] int32, bary [n, 2], position [n, 3], normal [n, 3] float32, material [n] int32) - n points of the
+        scene's surface at this tracer's seed, a triangle drawn in proportion to its area times its weight, the point uniform on it
+        (include/ptk.h ptk_sample_surface).  Pending geometry edits apply as for RenderFrame()."""
+        n = int(n)
+        out = (np.empty(n, np.int32), np.empty((n, 2), np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32),
+               np.empty(n, np.int32))
+        if not self.L.pth_sample_surface(self.h, n, int(key_base) & 0xffffffff, int(sample) & 0xffffffff, *(a.ctypes.data for a in out)):
+            raise _ptk.PtkError("SampleSurface failed: " + self.LastError())
+        return out
+
+    def set_surface_weights(self, weights=None):
+        """Extension: per-triangle weights [triangles] float32, finite and >= 0, multiplied onto the areas sample_surface draws by;
+        None: the areas alone (include/ptk.h ptk_surface_weights).  BuildBVH() drops them."""
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        assert w is None or len(w) == self.GetTriangleCount(), "one weight per triangle"
+        if not self.L.pth_set_surface_weights(self.h, w.ctypes.data if w is not None else None):
+            raise _ptk.PtkError("SetSurfaceWeights failed: " + self.LastError())
+
+    def surface_info(self):
+        """Extension: (total, exponent E, drawable triangles, largest weight) of the sampling table in force (ptk_surface_info)"""
+        total, e, dr, m = C.c_uint64(0), C.c_int32(0), C.c_int32(0), C.c_float(0)
+        if not self.L.pth_surface_info(self.h, C.byref(total), C.byref(e), C.byref(dr), C.byref(m)):
+            raise _ptk.PtkError("SurfaceInfo failed: " + self.LastError())
+        return total.value, e.value, dr.value, np.float32(m.value)
+
+    SampleSurface, SetSurfaceWeights, SurfaceInfo = sample_surface, set_surface_weights, surface_info
 
     def _chart_uvs(self, uvs):
         if uvs is None:

@@ -172,6 +172,8 @@ SYMBOLS = [
     "ptk_crossings_rays", "ptk_crossings_rays_device", "ptk_contains_points", "ptk_contains_points_device",
     "ptk_inside_default_dirs", "ptk_signed_distance", "ptk_signed_distance_device", "ptk_last_crossings_ms",
     "ptk_multihit_rays", "ptk_multihit_rays_device", "ptk_last_multihit_ms",
+    "ptk_surface_weights", "ptk_surface_weights_device", "ptk_sample_surface", "ptk_sample_surface_device", "ptk_surface_info",
+    "ptk_last_surface_ms", "ptk_probe_surface_table", "ptk_probe_scan_u64",
     "ptk_denoise_planes", "ptk_denoise_planes_device", "ptk_denoise_frame", "ptk_read_denoised", "ptk_denoised_device_ptr",
     "ptk_resolve_denoised_rgb8", "ptk_last_denoise_ms",
     "ptk_get_view", "ptk_reproject_planes", "ptk_reproject_planes_device", "ptk_temporal_frame", "ptk_read_temporal",
@@ -311,6 +313,14 @@ def _load_locked() -> C.CDLL:
         for fn in (L.ptk_multihit_rays, L.ptk_multihit_rays_device):
             fn.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.ptk_last_multihit_ms.argtypes = [vp, fp]
+        for fn in (L.ptk_surface_weights, L.ptk_surface_weights_device):
+            fn.argtypes = [vp, vp]
+        for fn in (L.ptk_sample_surface, L.ptk_sample_surface_device):
+            fn.argtypes = [vp, C.c_int32, u32, u32, u64, vp, vp, vp, vp, vp]
+        L.ptk_surface_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), fp]
+        L.ptk_last_surface_ms.argtypes = [vp, fp, fp]
+        L.ptk_probe_surface_table.argtypes = [vp, vp]
+        L.ptk_probe_scan_u64.argtypes = [vp, C.c_int32, vp, vp, C.c_int32]
         for fn in (L.ptk_denoise_planes, L.ptk_denoise_planes_device):
             fn.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp, vp]
         L.ptk_denoise_frame.argtypes = [vp, C.POINTER(DenoiseParams), u32]
@@ -403,6 +413,7 @@ PROBES_ACCUMULATE = 1                                                 # ptk_bake
 DENOISE_VARIANCE = 1                                                  # ptk_denoise_frame flags
 INSIDE_WINDING, INSIDE_PARITY = 0, 1                                  # ptk_contains_points / ptk_signed_distance modes
 MULTIHIT_MAX = 16                                                     # PTK_MULTIHIT_MAX: the most entries ptk_multihit_rays keeps per ray
+SURFACE_SCAN_ITEMS = 4096                                             # PTK_SURFACE_SCAN_ITEMS: items per workgroup of the table's prefix sum
 INSIDE_MODES = {"winding": INSIDE_WINDING, "parity": INSIDE_PARITY}
 
 
@@ -664,6 +675,10 @@ class Context:
         a = normalise_arrays(arrays)
         d = scene_desc(a)
         self._chk(self.L.ptk_upload_scene(self.h, C.byref(d)), "ptk_upload_scene")
+
+    def num_triangles(self) -> int:
+        """triangles of the uploaded scene (ptk_bvh_info: every triangle has one record in the leaf order)"""
+        return self.bvh_info()[2]
 
     def update_materials(self, materials: np.ndarray):
         m = np.ascontiguousarray(materials, dtype=MATERIAL_DTYPE)
@@ -1096,6 +1111,68 @@ class Context:
         t = C.c_float(0)
         self._chk(self.L.ptk_last_multihit_ms(self.h, C.byref(t)), "ptk_last_multihit_ms")
         return t.value
+
+    # ---- surface sampling ---------------------------------------------------------------------
+    def set_surface_weights(self, weights=None):
+        """ptk_surface_weights: per-triangle weights [triangles] float32, finite and >= 0, multiplied onto the areas - or None for
+        the areas alone.  A numpy array goes through the host entry, a torch tensor on the context's GPU through
+        ptk_surface_weights_device.  The table is rebuilt by the next call that needs it."""
+        if weights is None:
+            self._chk(self.L.ptk_surface_weights(self.h, None), "ptk_surface_weights")
+        elif hasattr(weights, "data_ptr"):
+            import torch
+            self._ray_tensors((weights,), self.num_triangles(), ((torch.float32, 1),))
+            self._chk(self.L.ptk_surface_weights_device(self.h, C.c_void_p(weights.data_ptr())), "ptk_surface_weights_device")
+        else:
+            w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+            assert len(w) == self.num_triangles(), "one weight per triangle"
+            self._chk(self.L.ptk_surface_weights(self.h, w.ctypes.data), "ptk_surface_weights")
+
+    def sample_surface(self, n, seed=0, key_base=0, sample=0, device=False, want=(True, True, True, True, True)):
+        """ptk_sample_surface: (tri [n] int32, bary [n, 2], position [n, 3], normal [n, 3] float32, material [n] int32) - n points of
+        the scene's surface, a triangle drawn in proportion to its area (times its weight, set_surface_weights), the point uniform
+        on it, under the rule of include/ptk.h; sample j is a function of (seed, key_base + j, sample) and the scene alone.
+        device=False: numpy arrays through the host entry; device=True: torch tensors on the context's GPU through
+        ptk_sample_surface_device, no host copy.  want: which of the five outputs to compute (None stands for the others)."""
+        n = int(n)
+        shapes = (((n,), "int32"), ((n, 2), "float32"), ((n, 3), "float32"), ((n, 3), "float32"), ((n,), "int32"))
+        args = (n, int(key_base) & 0xffffffff, int(sample) & 0xffffffff, int(seed) & 0xffffffffffffffff)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device_ordinal())
+            out = tuple(torch.empty(shape, dtype=getattr(torch, dt), device=dev) if w else None for (shape, dt), w in zip(shapes, want))
+            self._chk(self.L.ptk_sample_surface_device(self.h, *args, *(C.c_void_p(t.data_ptr()) if t is not None else None for t in out)),
+                      "ptk_sample_surface_device")
+            return out
+        out = tuple(np.empty(shape, dt) if w else None for (shape, dt), w in zip(shapes, want))
+        self._chk(self.L.ptk_sample_surface(self.h, *args, *(a.ctypes.data if a is not None else None for a in out)), "ptk_sample_surface")
+        return out
+
+    def surface_info(self):
+        """ptk_surface_info: (total, exponent E, drawable triangles, largest weight) of the sampling table in force, built where
+        it is missing or stale"""
+        total, e, dr, m = C.c_uint64(0), C.c_int32(0), C.c_int32(0), C.c_float(0)
+        self._chk(self.L.ptk_surface_info(self.h, C.byref(total), C.byref(e), C.byref(dr), C.byref(m)), "ptk_surface_info")
+        return total.value, e.value, dr.value, np.float32(m.value)
+
+    def last_surface_ms(self):
+        """(table_ms, sample_ms): HIP-event times of the last sample_surface call's table build (0: it built none) and kernel"""
+        a, b = C.c_float(0), C.c_float(0)
+        self._chk(self.L.ptk_last_surface_ms(self.h, C.byref(a), C.byref(b)), "ptk_last_surface_ms")
+        return a.value, b.value
+
+    def probe_surface_table(self):
+        """ptk_probe_surface_table: the inclusive sums [triangles] uint64 ptk_sample_surface would search now"""
+        incl = np.empty(self.num_triangles(), np.uint64)
+        self._chk(self.L.ptk_probe_surface_table(self.h, incl.ctypes.data), "ptk_probe_surface_table")
+        return incl
+
+    def probe_scan_u64(self, values, items_per_workgroup=0):
+        """ptk_probe_scan_u64: the table's prefix sum on these uint64 values (0 items: the table's own workgroup size)"""
+        v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
+        out = np.empty_like(v)
+        self._chk(self.L.ptk_probe_scan_u64(self.h, len(v), v.ctypes.data, out.ctypes.data, int(items_per_workgroup)), "ptk_probe_scan_u64")
+        return out
 
     # ---- a-trous denoiser --------------------------------------------------------------------
     def denoise_planes(self, color, mask, normal, position, params, albedo=None, variance=None, want_variance: bool = False):

@@ -13,6 +13,7 @@
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz [--layers K]
     python -m pbrpathtracer_amd.render scene.pts --distance-field 64 64 64 [--df-max-dist M] [--signed [--inside-mode parity]] -o field.npz
+    python -m pbrpathtracer_amd.render scene.pts --point-cloud 100000 --spp 16 [--offset O] -o cloud.npz
     python -m pbrpathtracer_amd.render scene.pts --bake-lightmap 1024 --spp 64 [--bake-atlas] [--bake-offset F] [--bake-back]
                                                  [--denoise] [--dilate K] -o map.png [--npy map.npy]
     python -m pbrpathtracer_amd.render scene.pts --bake-probes NX NY NZ [--probe-dirs D] --spp N -o probes.npz
@@ -63,6 +64,12 @@ With --equirect WIDTH --hits FILE.npz nothing is traced and no image written: th
 top-down - a depth panorama; --spp is not needed.  With --layers K (1 .. 16) the .npz also holds the first K surfaces along each
 ray in order (PathTracer.MultiHitRays, include/ptk.h ptk_multihit_rays - geometry only, opacity maps take no part): layer_t and
 layer_tri [K, H, W] (+inf and -1 behind a ray's last surface) and layer_count [H, W]; the other arrays are what they are without it.
+
+With --point-cloud N no image is written: the .npz holds N points of the scene's surface, drawn in proportion to area
+(PathTracer.SampleSurface, include/ptk.h ptk_sample_surface, sample 0 of --seed), each traced with --spp samples along the lightmap
+bake's ray - from the point lifted by --offset along its face normal (default: 1e-3 of the scene extent), against the normal -
+through surface.bake_points: position, normal [N, 3] float32, triangle, material [N] int32 and radiance [N, 3] float32, the sum over
+the samples.  A bake that needs neither vertices nor a uv layout.
 
 With --bake-lightmap SIZE the image is a SIZE x SIZE lightmap (include/ptk.h ptk_bake_lightmap): per texel of the scene's own uv
 layout - or, with --bake-atlas, of lightmap.grid_atlas, one chart per triangle - the radiance leaving the surface along its normal,
@@ -154,6 +161,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="bake a SIZE x SIZE lightmap over the scene's uvs instead of rendering a view; the PNG holds the mean "
                          "(sum / spp) resolved like a frame, rows top-down; --npy the float32 sums [SIZE, SIZE, 3], rows bottom-up as baked")
     ap.add_argument("--bake-atlas", action="store_true", help="--bake-lightmap: lay the triangles out with lightmap.grid_atlas")
+    ap.add_argument("--point-cloud", type=int, metavar="N", default=None,
+                    help="instead of rendering a view, sample N points of the scene's surface by area and bake each with --spp samples "
+                         "along its normal; -o names the .npz (position, normal, triangle, material, radiance)")
+    ap.add_argument("--offset", type=float, default=None,
+                    help="--point-cloud: distance of the ray origins from the surface (default: 1e-3 of the scene extent)")
     ap.add_argument("--bake-offset", type=float, default=None,
                     help="--bake-lightmap: distance of the ray origins from the surface (default: 1e-3 of the scene extent)")
     ap.add_argument("--bake-back", action="store_true", help="--bake-lightmap: bake the back side (PTK_BAKE_BACK)")
@@ -377,6 +389,40 @@ def render_distance_field(pt, a) -> int:
                  side=face_side(verts, pos, point, tri).reshape(shape), **extra)
     print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {dims[0]}x{dims[1]}x{dims[2]} distance field, "
           f"{int((tri >= 0).sum())} points within reach: {t2 - t1:.3f} s -> {a.out}")
+    return 0
+
+
+class _TracerSurface:
+    """surface.bake_points' view of a PathTracer: sample_surface and trace_rays at the tracer's own seed and trace depth"""
+
+    def __init__(self, pt):
+        self.pt = pt
+
+    def sample_surface(self, n, seed=0, key_base=0, sample=0):
+        return self.pt.SampleSurface(n, key_base=key_base, sample=sample)
+
+    def trace_rays(self, origins, dirs, max_depth, first_sample, spp, seed, key_base=0, out=None):
+        return self.pt.TraceRays(origins, dirs, first_sample, spp, key_base=key_base, out=out)
+
+
+def render_point_cloud(pt, a) -> int:
+    """--point-cloud: surface.bake_points over the whole surface, written as arrays"""
+    from . import surface
+    if a.point_cloud < 1 or a.spp < 1 or (a.offset is not None and not a.offset >= 0.0):
+        print("error: --point-cloud needs N >= 1, --spp >= 1 and --offset >= 0", file=sys.stderr)
+        return 1
+    if not pt.GetTriangleCount():
+        print("error: --point-cloud: the scene has no triangles", file=sys.stderr)
+        return 1
+    offset = a.offset if a.offset is not None else bake_offset(pt)
+    t1 = time.time()
+    position, normal, tri, material, radiance = surface.bake_points(_TracerSurface(pt), a.point_cloud, a.spp, offset, pt.GetTraceDepth(), seed=a.seed)
+    t2 = time.time()
+    with open(a.out, "wb") as f:                # (np.savez would append .npz to another suffix)
+        np.savez(f, position=position, normal=normal, triangle=tri, material=material, radiance=radiance, spp=np.int32(a.spp),
+                 offset=np.float32(offset))
+    print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {a.point_cloud} surface points, {a.spp} spp, depth {pt.GetTraceDepth()}: "
+          f"{t2 - t1:.3f} s -> {a.out}")
     return 0
 
 
@@ -613,6 +659,12 @@ def main(argv=None):
     if a.fill_holes is not None and (a.upscale is None or a.fill_holes < 1):
         print("error: --fill-holes goes with --upscale and needs SPP >= 1", file=sys.stderr)
         return 1
+    if a.offset is not None and a.point_cloud is None:
+        print("error: --offset goes with --point-cloud", file=sys.stderr)
+        return 1
+    if a.point_cloud is not None and (a.upscale is not None or a.orbit is not None or a.display is not None or a.features):
+        print("error: --point-cloud is a mode of its own", file=sys.stderr)
+        return 1
     if a.upscale is not None:
         if a.orbit is not None or a.noise_threshold is not None or a.bake_lightmap is not None or a.bake_probes is not None or \
                 a.distance_field is not None or a.equirect is not None or a.features:
@@ -642,6 +694,16 @@ def main(argv=None):
     if a.bake_probes is not None:
         try:
             return render_probes(pt, a)
+        except (RuntimeError, ValueError) as e:
+            print("error:", e, file=sys.stderr)
+            return 1
+    if a.point_cloud is not None:
+        if a.bake_lightmap is not None or a.bake_probes is not None or a.distance_field is not None or a.equirect is not None or \
+                a.noise_threshold is not None or a.denoise:
+            print("error: --point-cloud is a mode of its own", file=sys.stderr)
+            return 1
+        try:
+            return render_point_cloud(pt, a)
         except (RuntimeError, ValueError) as e:
             print("error:", e, file=sys.stderr)
             return 1

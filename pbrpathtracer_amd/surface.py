@@ -1,0 +1,43 @@
+"""Worked uses of surface sampling (include/ptk.h ptk_sample_surface): weight tables for
+Context.set_surface_weights, and a bake at sampled surface points that needs neither vertices nor a uv layout."""
+from __future__ import annotations
+
+import numpy as np
+
+F32 = np.float32
+
+
+def material_weights(material_ids, chosen) -> np.ndarray:
+    """[triangles] float32: 1 where the triangle's material is `chosen` (an index or several), 0 elsewhere - points on the surfaces
+    of those materials only, still in proportion to area"""
+    ids = np.asarray(material_ids, np.int32).reshape(-1)
+    return np.isin(ids, np.atleast_1d(np.asarray(chosen, np.int32))).astype(F32)
+
+
+def emissive_weights(materials, material_ids) -> np.ndarray:
+    """[triangles] float32: the luminance (Rec. 709) of emissive * emissive_intensity of each triangle's material, in float32.
+    Times the area - which the table multiplies on - this samples the lights by power; everything that does not emit gets 0 and is
+    never drawn."""
+    e = np.asarray(materials["emissive"], F32).reshape(-1, 3) * np.asarray(materials["emissive_intensity"], F32).reshape(-1, 1)
+    lum = (e[:, 0] * F32(0.2126) + e[:, 1] * F32(0.7152)) + e[:, 2] * F32(0.0722)
+    return np.maximum(lum, F32(0)).astype(F32)[np.asarray(material_ids, np.int32).reshape(-1)]
+
+
+def bake_rays(position, normal, offset):
+    """(origins, dirs) [n, 3] float32 of the lightmap bake's ray at each point: origin = P + n * offset - the product rounded to
+    float32, then the sum -, direction = -n"""
+    p = np.ascontiguousarray(position, F32).reshape(-1, 3); n = np.ascontiguousarray(normal, F32).reshape(-1, 3)
+    lift = n * F32(offset)
+    return p + lift, -n
+
+
+def bake_points(ctx, n, spp, offset, max_depth, seed=0, first_sample=0, key_base=0, out=None):
+    """A bake without a uv layout: n surface points (ctx.sample_surface at `seed`, `key_base`, sample 0), each traced with
+    ctx.trace_rays along bake_rays - the radiance leaving the surface along its normal, as a lightmap texel gathers it - over samples
+    [first_sample, first_sample + spp) with the sampling's key_base, so point j and ray j share RNG pixel key_base + j.  Returns
+    (position [n, 3], normal [n, 3] float32, tri [n], material [n] int32, radiance [n, 3] float32: the sum over the samples).  out:
+    the radiance of earlier samples of the same points, added to in place - a progressive bake equals one long bake."""
+    tri, _, position, normal, material = ctx.sample_surface(n, seed=seed, key_base=key_base, sample=0)
+    origins, dirs = bake_rays(position, normal, offset)
+    radiance = ctx.trace_rays(origins, dirs, max_depth, first_sample, spp, seed, key_base=key_base, out=out)
+    return position, normal, tri, material, radiance
