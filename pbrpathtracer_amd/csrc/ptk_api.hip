@@ -168,18 +168,18 @@ const int kFeatIsInt[NUM_FEATURES] = { 0, 1, 1, 0, 0, 0, 0, 0, 0, 0 };
 
 void free_features(ptk_ctx* c)
 {
-    for (int k = 0; k < NUM_FEATURES; k++) dfree(c->d_feat[k]);
+    for (auto& b : c->d_feat) b.release();
     c->feat_w = c->feat_h = 0; c->feat_mask = 0;
-    dfree(c->d_denoised); c->den_w = c->den_h = 0;      // the denoised frame goes with the planes that guided it
-    dfree(c->d_temporal); c->temporal_w = c->temporal_h = 0;      // ... and so does the temporal history
-    dfree(c->d_motion); c->motion_w = c->motion_h = 0;            // ... and the motion planes
-    dfree(c->d_temporal_mm); c->temporal_moments = c->temporal_variance = false;      // ... and the moments and the variance
-    dfree(c->d_display); c->disp_w = c->disp_h = 0;               // ... and the display image (the exposure state stays)
+    c->d_denoised.release(); c->den_w = c->den_h = 0;      // the denoised frame goes with the planes that guided it
+    c->d_temporal.release(); c->temporal_w = c->temporal_h = 0;      // ... and so does the temporal history
+    c->d_motion.release(); c->motion_w = c->motion_h = 0;            // ... and the motion planes
+    c->d_temporal_mm.release(); c->temporal_moments = c->temporal_variance = false;      // ... and the moments and the variance
+    c->d_display.release(); c->disp_w = c->disp_h = 0;               // ... and the display image (the exposure state stays)
     // ... and the guide planes with the upsampled frame
-    for (int k = 0; k < NUM_FEATURES; k++) { dfree(c->d_guide[k]); c->guide_cap[k] = 0; }
-    dfree(c->d_guide_primary); c->guide_primary_px = 0;
+    for (auto& b : c->d_guide) b.release();
+    c->d_guide_primary.release();
     c->guide_w = c->guide_h = 0; c->guide_mask = 0;
-    dfree(c->d_upsampled); c->upsampled_px = 0; c->ups_w = c->ups_h = 0;
+    c->d_upsampled.release(); c->ups_w = c->ups_h = 0;
 }
 
 // Brings the primary-visibility cache up to date where it is valid and hands it to p; else p keeps walking from the camera.
@@ -214,15 +214,15 @@ void* feature_plane(ptk_ctx* c, int feature, size_t* bytes)
 // what the first geometry update derives from a tree's topology; dropped with the tree
 void free_geometry_cache(ptk_ctx* c)
 {
-    dfree(c->d_tri_pos); dfree(c->d_level_nodes); dfree(c->d_refit_side); dfree(c->d_refit_partial);
+    c->d_tri_pos.release(); c->d_level_nodes.release(); c->d_refit_side.release(); c->d_refit_partial.release();
     c->level_start.clear();
     c->geo_updates = 0; c->sah_built = c->sah_now = 0.0; c->sah_now_pending = false;
 }
 
 void free_adaptive(ptk_ctx* c)
 {
-    dfree(c->d_counts); dfree(c->d_moments); dfree(c->d_adapt_active); dfree(c->d_adapt_traced); dfree(c->d_adapt_list);
-    dfree(c->d_adapt_stats);
+    c->d_counts.release(); c->d_moments.release(); c->d_adapt_active.release(); c->d_adapt_traced.release(); c->d_adapt_list.release();
+    c->d_adapt_stats.release();
     c->adapt_capacity = 0;
     c->adaptive_accum = false;
 }
@@ -296,9 +296,9 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
         if (subtiles > c->live_capacity)
         {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            dfree(c->d_live_mask); dfree(c->d_live_list); c->live_capacity = 0;
-            HIPCHK(c, hipMalloc(&c->d_live_mask, (size_t)subtiles * sizeof(unsigned long long)));
-            HIPCHK(c, hipMalloc(&c->d_live_list, ((size_t)subtiles + 1) * sizeof(unsigned)));
+            c->d_live_mask.release(); c->d_live_list.release(); c->live_capacity = 0;
+            if (const int rc = c->d_live_mask.alloc(c, (size_t)subtiles); rc != PTK_OK) return rc;
+            if (const int rc = c->d_live_list.alloc(c, (size_t)subtiles + 1); rc != PTK_OK) return rc;
             c->live_capacity = subtiles;
             c->live_key.rank = -1;
         }
@@ -342,13 +342,13 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
     // (a bound hand-off buffer means the caller waits for every frame: nothing to overlap, and one stream is two event
     // hops per frame less)
     // (nor in an adaptive render: each round depends on the one before)
-    const bool overlap = c->opt_overlap != 0 && c->trace_stream[0] != nullptr && !handoff && !ad;
+    const bool overlap = c->opt_overlap != 0 && c->trace_stream[0].s != nullptr && !handoff && !ad;
     // The pass size: what the sample-buffer budget allows - and what the device can actually give.  When an allocation of that
     // size fails (memory shared with the caller's framework, a huge scene, a 144-megapixel frame) the pass is halved and tried
     // again instead of failing the render: more passes, the same image (chunk boundaries never change a bit).
     size_t budget = c->opt_pass_bytes;
     {
-        const size_t have = overlap ? std::min(c->samples_bytes2[0], c->samples_bytes2[1]) : c->samples_bytes;
+        const size_t have = overlap ? std::min(c->d_samples2[0].cap, c->d_samples2[1].cap) : c->d_samples.cap;
         const size_t want = std::min(budget, per_sample * ((size_t)spp + (size_t)chunk_opt));      // (what this render asks for at most)
         size_t free_b = 0, total_b = 0;
         if (want > have)             // (only a render that has to allocate asks the driver: the interactive loop never does)
@@ -364,12 +364,11 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
     }
     uint32_t max_pass = (uint32_t)std::max<size_t>(1, budget / per_sample);
     if (max_pass > (uint32_t)chunk_opt) max_pass -= max_pass % (uint32_t)chunk_opt;
-    // grows *buf to `need` bytes; false (nothing allocated, *bytes = 0) when the device refuses
-    auto grow = [&](float4*& buf, size_t& bytes, size_t need) -> bool {
-        dfree(buf); bytes = 0;
-        if (hipMalloc(&buf, need) != hipSuccess) { (void)hipGetLastError(); buf = nullptr; return false; }
-        bytes = need;
-        return true;
+    // grows buf to `need` bytes; false (nothing allocated, capacity 0) when the device refuses
+    auto grow = [&](Buf<float4>& buf, size_t need) -> bool {
+        if (buf.try_alloc(need, need) == hipSuccess) return true;
+        (void)hipGetLastError();
+        return false;
     };
     uint32_t done = 0;
     while (done < spp)
@@ -387,19 +386,19 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
             {
                 // BOTH buffers are brought to size together: the second one would otherwise be allocated - a blocking call of tens of
                 // milliseconds for gigabytes - in the middle of the second render (BENCH_r03: C3's first timed steps)
-                if (need > c->samples_bytes2[0] || need > c->samples_bytes2[1])
+                if (need > c->d_samples2[0].cap || need > c->d_samples2[1].cap)
                 {
                     HIPCHK(c, hipStreamSynchronize(c->trace_stream[0]));
                     HIPCHK(c, hipStreamSynchronize(c->trace_stream[1]));
                     HIPCHK(c, hipStreamSynchronize(c->stream));
                     for (int k = 0; k < 2 && ok; k++)
-                        if (need > c->samples_bytes2[k]) ok = grow(c->d_samples2[k], c->samples_bytes2[k], need);
+                        if (need > c->d_samples2[k].cap) ok = grow(c->d_samples2[k], need);
                 }
             }
-            else if (need > c->samples_bytes)
+            else if (need > c->d_samples.cap)
             {
                 HIPCHK(c, hipStreamSynchronize(c->stream));
-                ok = grow(c->d_samples, c->samples_bytes, need);
+                ok = grow(c->d_samples, need);
             }
             if (ok) break;
             if (n <= (uint32_t)chunk && chunk <= 1) return fail(c, PTK_ERR_HIP, "hipMalloc: no memory for the sample buffer of even one sample per pixel");
@@ -429,7 +428,7 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
         if (items > (1ll << 30)) return fail(c, PTK_ERR_LIMIT, "too many work items in one pass");
         p.num_items = (int)items;
         const int pi = c->last_passes < ptk_ctx::kMaxTimedPasses ? c->last_passes : -1;
-        if (timed && pi >= 0) HIPCHK(c, hipEventRecord(c->ev[pi][0], tstream));
+        if (timed && pi >= 0) HIPCHK(c, hipEventRecord(c->ev.at(pi, 0), tstream));
         const int kl = (!stats && (size_t)(2 * c->klog_n + 1) < c->klog_ev.size()) ? c->klog_n : -1;
         if (kl >= 0) HIPCHK(c, hipEventRecord(c->klog_ev[2 * kl], tstream));
         p.queues = overlap ? c->d_queues2[b] : c->d_queues;
@@ -440,7 +439,7 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
         c->last_trace_variant = p.flat_count <= 0 ? PTK_TRACE_BVH : ((p.plain && !stats) ? PTK_TRACE_FLAT_PLAIN : PTK_TRACE_FLAT);
         c->last_trace_lambert = p.flat_count > 0 && p.plain && p.lambert && !stats;
         c->last_trace_unit = (p.flat_count > 0 && p.plain && !stats && c->opt_contract == 0) ? (p.plain == 3 ? PTK_UNIT_CYCLE : p.plain == 2 ? PTK_UNIT_RECT : PTK_UNIT_PLAIN) : PTK_UNIT_NONE;
-        if (timed && pi >= 0) HIPCHK(c, hipEventRecord(c->ev[pi][1], tstream));
+        if (timed && pi >= 0) HIPCHK(c, hipEventRecord(c->ev.at(pi, 1), tstream));
         if (kl >= 0) { HIPCHK(c, hipEventRecord(c->klog_ev[2 * kl + 1], tstream)); c->klog_n = kl + 1; }
         if (overlap)
         {
@@ -450,7 +449,7 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
         if (ad) launch_accumulate_adaptive(p, ad->a, tiles, c->stream);
         else launch_accumulate(p, tiles, c->stream);
         HIPCHK(c, hipGetLastError());
-        if (timed && pi >= 0) HIPCHK(c, hipEventRecord(c->ev[pi][2], c->stream));
+        if (timed && pi >= 0) HIPCHK(c, hipEventRecord(c->ev.at(pi, 2), c->stream));
         if (overlap)
         {
             HIPCHK(c, hipEventRecord(c->ev_acc_done[b], c->stream));
@@ -533,49 +532,34 @@ int ptk_create(ptk_ctx** out, int device_ordinal)
     ptk_ctx* c = new (std::nothrow) ptk_ctx();
     if (!c) return PTK_ERR_HIP;
     c->device = device_ordinal;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return PTK_ERR_HIP; }
-    c->own_stream = true;
+    if (c->stream_own.create(hipStreamNonBlocking) != hipSuccess) { delete c; return PTK_ERR_HIP; }
+    c->stream = c->stream_own; c->own_stream = true;
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cus > 0)
             c->resident_waves = cus * 16;        // 4 SIMDs x 4 waves of the BVH trace kernel per CU (launch_trace scales it to x 5 for the FLAT kernel)
         if (cus > 0) c->num_cus = cus;
     }
-    if (hipMalloc(&c->d_exit, sizeof(uint32_t)) != hipSuccess || hipMemset(c->d_exit, 0, sizeof(uint32_t)) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_exit, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(&c->d_stats, 16 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(&c->d_queues, PTK_QUEUE_BLOCK_BYTES) != hipSuccess)
-    {
-        ptk_destroy(c);
-        return PTK_ERR_HIP;
-    }
-    *c->h_exit = 0;
-    for (int i = 0; i < ptk_ctx::kMaxTimedPasses; i++)
-        for (int k = 0; k < 3; k++)
-            if (hipEventCreate(&c->ev[i][k]) != hipSuccess) { ptk_destroy(c); return PTK_ERR_HIP; }
+    // (ptk_destroy copes with a context of which only some members were made)
+    bool ok = c->d_exit.alloc(c, 1) == PTK_OK && hipMemset(c->d_exit, 0, sizeof(uint32_t)) == hipSuccess &&
+              c->h_exit.alloc(1) == hipSuccess && c->d_stats.alloc(c, 16) == PTK_OK &&
+              c->d_queues.alloc_bytes(c, PTK_QUEUE_BLOCK_BYTES, 0) == PTK_OK;
+    if (ok) *c->h_exit = 0;
+    ok = ok && c->ev.reserve(c, ptk_ctx::kMaxTimedPasses) == PTK_OK;
     for (int b = 0; b < 2; b++)
-        if (hipStreamCreateWithFlags(&c->trace_stream[b], hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_trace_done[b], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_acc_done[b], hipEventDisableTiming) != hipSuccess ||
-            hipMalloc(&c->d_queues2[b], PTK_QUEUE_BLOCK_BYTES) != hipSuccess)
-        { ptk_destroy(c); return PTK_ERR_HIP; }
-    if (hipEventCreateWithFlags(&c->ev_inputs, hipEventDisableTiming) != hipSuccess) { ptk_destroy(c); return PTK_ERR_HIP; }
-    if (hipStreamCreateWithFlags(&c->geo_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&c->d_geo_red, GEO_RED_WORDS * sizeof(uint32_t) + sizeof(double)) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_geo_red, GEO_RED_WORDS * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-    { ptk_destroy(c); return PTK_ERR_HIP; }
-    for (hipEvent_t& e : c->ev_geo_t)
-        if (hipEventCreate(&e) != hipSuccess) { ptk_destroy(c); return PTK_ERR_HIP; }
-    {
-        int lo = 0, hi = 0;                      // (numerically lowest = greatest priority)
-        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (hipStreamCreateWithPriority(&c->xstream, hipStreamNonBlocking, hi) != hipSuccess ||
-            hipStreamCreateWithPriority(&c->exit_stream, hipStreamNonBlocking, hi) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_rendered, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_packed, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_gathered, hipEventDisableTiming) != hipSuccess)
-        { ptk_destroy(c); return PTK_ERR_HIP; }
-    }
+        ok = ok && c->trace_stream[b].create(hipStreamNonBlocking) == hipSuccess &&
+             c->ev_trace_done[b].create(hipEventDisableTiming) == hipSuccess && c->ev_acc_done[b].create(hipEventDisableTiming) == hipSuccess &&
+             c->d_queues2[b].alloc_bytes(c, PTK_QUEUE_BLOCK_BYTES, 0) == PTK_OK;
+    ok = ok && c->ev_inputs.create(hipEventDisableTiming) == hipSuccess;
+    ok = ok && c->geo_stream.create(hipStreamNonBlocking) == hipSuccess &&
+         c->d_geo_red.alloc(c, GEO_RED_WORDS, sizeof(double)) == PTK_OK && c->h_geo_red.alloc(GEO_RED_WORDS) == hipSuccess;
+    for (Event& e : c->ev_geo_t.ev) ok = ok && e.create() == hipSuccess;
+    int lo = 0, hi = 0;                          // (numerically lowest = greatest priority)
+    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+    ok = ok && c->xstream.create(hipStreamNonBlocking, hi) == hipSuccess && c->exit_stream.create(hipStreamNonBlocking, hi) == hipSuccess &&
+         c->ev_rendered.create(hipEventDisableTiming) == hipSuccess && c->ev_packed.create(hipEventDisableTiming) == hipSuccess &&
+         c->ev_gathered.create(hipEventDisableTiming) == hipSuccess;
+    if (!ok) { ptk_destroy(c); return PTK_ERR_HIP; }
     *out = c;
     return PTK_OK;
 }
@@ -585,76 +569,9 @@ void ptk_destroy(ptk_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (const Stream* s : { &c->trace_stream[0], &c->trace_stream[1], &c->geo_stream, &c->xstream, &c->exit_stream }) s->sync();
     unbind_out_image(c);
-    dfree(c->d_nodes); dfree(c->d_tris); dfree(c->d_shade); dfree(c->d_mats); dfree(c->d_lights);
-    dfree(c->d_flat_tris);
-    free_geometry_cache(c); dfree(c->d_verts_res); dfree(c->d_verts_prev); dfree(c->d_geo_stage); dfree(c->d_geo_red);
-    if (c->h_geo_red) (void)hipHostFree(c->h_geo_red);
-    if (c->geo_stream) { (void)hipStreamSynchronize(c->geo_stream); (void)hipStreamDestroy(c->geo_stream); }
-    for (hipEvent_t e : c->ev_geo_t) if (e) (void)hipEventDestroy(e);
-    dfree(c->d_texinfo); dfree(c->d_texels); dfree(c->d_primary); dfree(c->d_primary_hit); dfree(c->d_primary_rd); dfree(c->d_accum); dfree(c->d_rgb8);
-    dfree(c->d_pixel_rng);
-    for (int b = 0; b < 2; b++)
-    {
-        if (c->trace_stream[b]) { (void)hipStreamSynchronize(c->trace_stream[b]); (void)hipStreamDestroy(c->trace_stream[b]); }
-        if (c->ev_trace_done[b]) (void)hipEventDestroy(c->ev_trace_done[b]);
-        if (c->ev_acc_done[b]) (void)hipEventDestroy(c->ev_acc_done[b]);
-        dfree(c->d_samples2[b]); dfree(c->d_queues2[b]);
-    }
-    if (c->ev_inputs) (void)hipEventDestroy(c->ev_inputs);
-    if (c->xstream) { (void)hipStreamSynchronize(c->xstream); }
-    comm_release(c);
-    if (c->xstream) (void)hipStreamDestroy(c->xstream);
-    if (c->ev_rendered) (void)hipEventDestroy(c->ev_rendered);
-    if (c->ev_packed) (void)hipEventDestroy(c->ev_packed);
-    if (c->ev_gathered) (void)hipEventDestroy(c->ev_gathered);
-    dfree(c->d_packed); dfree(c->d_gathered);
-    if (c->exit_stream) { (void)hipStreamSynchronize(c->exit_stream); (void)hipStreamDestroy(c->exit_stream); }
-    if (c->h_exit) (void)hipHostFree(c->h_exit);
-    dfree(c->d_exit); dfree(c->d_stats); dfree(c->d_queues); dfree(c->d_samples);
-    dfree(c->d_live_mask); dfree(c->d_live_list);
-    free_adaptive(c);
-    free_features(c);
-    dfree(c->d_rays_samples); dfree(c->d_rays_block);
-    dfree(c->d_bake_plane); dfree(c->d_bake_compact); dfree(c->d_bake_dilate);
-    if (c->h_bake_total) (void)hipHostFree(c->h_bake_total);
-    dfree(c->d_radapt); dfree(c->d_radapt_need);
-    if (c->h_radapt_total) (void)hipHostFree(c->h_radapt_total);
-    for (hipEvent_t e : c->ev_radapt) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_bake) if (e) (void)hipEventDestroy(e);
-    dfree(c->d_probe_basis); dfree(c->d_probe_rays); dfree(c->d_probe_table);
-    for (hipEvent_t e : c->ev_probes) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_probe_blocks) (void)hipEventDestroy(e);
-    dfree(c->d_probe_depth);
-    for (hipEvent_t e : c->ev_probe_vis) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_probe_vis_blocks) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_rays) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_hits) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_closest) if (e) (void)hipEventDestroy(e);
-    dfree(c->d_closest_stats);
-    for (hipEvent_t e : c->ev_crossings) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_multihit) if (e) (void)hipEventDestroy(e);
-    surface_release(c);
-    for (hipEvent_t e : c->ev_surface) if (e) (void)hipEventDestroy(e);
-    dfree(c->d_denoise);
-    for (hipEvent_t e : c->ev_denoise) if (e) (void)hipEventDestroy(e);
-    dfree(c->d_temporal_pack);
-    for (hipEvent_t e : c->ev_temporal) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_motion) if (e) (void)hipEventDestroy(e);
-    dfree(c->d_variance_pack); dfree(c->d_temporal_pack_mm);
-    for (hipEvent_t e : c->ev_variance) if (e) (void)hipEventDestroy(e);
-    dfree(c->d_display_hist);
-    for (hipEvent_t e : c->ev_display) if (e) (void)hipEventDestroy(e);
-    dfree(c->d_upsample_pack);
-    for (hipEvent_t e : c->ev_upsample) if (e) (void)hipEventDestroy(e);
-    for (int b = 0; b < 2; b++)
-        if (c->ev_adapt[b]) (void)hipEventDestroy(c->ev_adapt[b]);
-    if (c->h_adapt_count) (void)hipHostFree(c->h_adapt_count);
-    for (int i = 0; i < ptk_ctx::kMaxTimedPasses; i++)
-        for (int k = 0; k < 3; k++)
-            if (c->ev[i][k]) (void)hipEventDestroy(c->ev[i][k]);
-    for (hipEvent_t e : c->klog_ev) (void)hipEventDestroy(e);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
+    comm_release(c);                             // (before xstream goes)
     delete c;
 }
 
@@ -669,7 +586,7 @@ int ptk_set_stream(ptk_ctx* c, void* s)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->own_stream && c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
+    if (c->own_stream) c->stream_own.release();
     else if ((hipStream_t)s != c->stream)
     {
         // from one caller stream to another, with no host wait: the new stream goes on behind everything queued on the old one
@@ -742,18 +659,18 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
     BuiltBvh bvh;
     DeviceBvh dbvh;
     bool on_device = false;
-    float* d_verts = nullptr;
-    struct TmpFree { std::vector<void*> p; ~TmpFree() { for (void* q : p) if (q) (void)hipFree(q); } } tmp;
+    // what a device build holds until the context takes it over or the call ends: the staged vertices, the builder's two arrays
+    Buf<float> d_verts; Buf<float4> d_bvh_nodes; Buf<int32_t> d_bvh_order;
     if (c->opt_device_build && n >= 4096)
     {
-        HIPCHK(c, hipMalloc(&d_verts, (size_t)n * 9 * sizeof(float)));
-        tmp.p.push_back(d_verts);
+        if (const int rc = d_verts.alloc(c, (size_t)n * 9); rc != PTK_OK) return rc;
         HIPCHK(c, hipMemcpyAsync(d_verts, s->verts, (size_t)n * 9 * sizeof(float), hipMemcpyHostToDevice, c->stream));
         std::string derr;
         int leaf_max = 4;
         if (g_bvh_tuning.leaf_max > 0) leaf_max = g_bvh_tuning.leaf_max;                              // ptk_set_option "bvh_leaf_max"
         on_device = build_bvh_device(d_verts, n, PTK_MAX_BVH_DEPTH, leaf_max, c->stream, dbvh, &derr);
-        if (on_device && dbvh.stack_need > PTK_MAX_BVH_DEPTH) { (void)hipFree(dbvh.d_nodes); (void)hipFree(dbvh.d_order); on_device = false; }
+        if (on_device) { d_bvh_nodes.adopt(dbvh.d_nodes); d_bvh_order.adopt(dbvh.d_order); }
+        if (on_device && dbvh.stack_need > PTK_MAX_BVH_DEPTH) { d_bvh_nodes.release(); d_bvh_order.release(); on_device = false; }
     }
     if (!on_device)
     {
@@ -761,7 +678,6 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
             return fail(c, PTK_ERR_LIMIT, "BVH exceeds the kernel's depth / index limits");
         if (bvh.stack_need > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
     }
-    struct DevBvhGuard { DeviceBvh& d; bool armed; ~DevBvhGuard() { if (armed) { (void)hipFree(d.d_nodes); (void)hipFree(d.d_order); } } } dguard{ dbvh, on_device };
     if ((uint64_t)(on_device ? dbvh.num_nodes : bvh.num_nodes) * (uint64_t)(NODE_F4 * sizeof(float4)) > 0xffffffffull)
         return fail(c, PTK_ERR_LIMIT, "more BVH nodes than the kernels' 32-bit record offsets address");
 
@@ -842,10 +758,10 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
 
     c->upload_ms[1] = ms_since(t_pack);
     const auto t_copy = std::chrono::steady_clock::now();
-    dfree(c->d_nodes); dfree(c->d_tris); dfree(c->d_shade); dfree(c->d_mats); dfree(c->d_lights);
-    dfree(c->d_texinfo); dfree(c->d_texels);
-    dfree(c->d_verts_res); free_geometry_cache(c);
-    dfree(c->d_verts_prev); c->have_snapshot = false;             // (ptk_geometry_snapshot: of the scene that goes)
+    c->d_nodes.release(); c->d_tris.release(); c->d_shade.release(); c->d_mats.release(); c->d_lights.release();
+    c->d_texinfo.release(); c->d_texels.release();
+    c->d_verts_res.release(); free_geometry_cache(c);
+    c->d_verts_prev.release(); c->have_snapshot = false;             // (ptk_geometry_snapshot: of the scene that goes)
     surface_release(c);                                            // (ptk_sample_surface: its table and weights likewise)
     c->lights_stale = false;
     c->have_scene = false;
@@ -858,60 +774,58 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
     };
     if (on_device)
     {
-        dfree(c->d_flat_tris);
+        c->d_flat_tris.release();
         // the records are packed on the device from the boundary's flat arrays (one pass each; no host-side copies)
-        float *d_normals = nullptr, *d_uvs = nullptr, *d_tbn = nullptr; uint8_t* d_smooth = nullptr; int32_t *d_material = nullptr, *d_optex = nullptr;
+        Buf<float> d_normals, d_uvs, d_tbn; Buf<uint8_t> d_smooth; Buf<int32_t> d_material, d_optex;       // (freed on the way out)
         std::vector<int32_t> optex(std::max<int32_t>(s->num_materials, 1), -1);
         for (int32_t i = 0; i < s->num_materials; i++) { const int32_t ot = s->materials[i].tex[5]; optex[i] = ot >= 0 ? texmap[ot] : -1; }
         auto tup = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
             hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
             if (e != hipSuccess) return e;
-            tmp.p.push_back(*dst);
             return bytes ? hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
         };
-        HIPCHK(c, tup((void**)&d_normals, s->normals, (size_t)n * 9 * sizeof(float)));
-        HIPCHK(c, tup((void**)&d_uvs, s->uvs, (size_t)n * 6 * sizeof(float)));
-        HIPCHK(c, tup((void**)&d_tbn, s->tbn, (size_t)n * 9 * sizeof(float)));
-        HIPCHK(c, tup((void**)&d_smooth, s->smoothing, (size_t)n));
-        HIPCHK(c, tup((void**)&d_material, s->material, (size_t)n * sizeof(int32_t)));
-        HIPCHK(c, tup((void**)&d_optex, optex.data(), optex.size() * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc(&c->d_tris, (size_t)n * TRI_F4 * sizeof(float4)));
-        HIPCHK(c, hipMalloc(&c->d_shade, (size_t)n * SHADE_F4 * sizeof(float4)));
-        launch_pack_tris(d_verts, dbvh.d_order, d_material, d_optex, c->d_tris, n, c->stream);
+        HIPCHK(c, tup((void**)&d_normals.p, s->normals, (size_t)n * 9 * sizeof(float)));
+        HIPCHK(c, tup((void**)&d_uvs.p, s->uvs, (size_t)n * 6 * sizeof(float)));
+        HIPCHK(c, tup((void**)&d_tbn.p, s->tbn, (size_t)n * 9 * sizeof(float)));
+        HIPCHK(c, tup((void**)&d_smooth.p, s->smoothing, (size_t)n));
+        HIPCHK(c, tup((void**)&d_material.p, s->material, (size_t)n * sizeof(int32_t)));
+        HIPCHK(c, tup((void**)&d_optex.p, optex.data(), optex.size() * sizeof(int32_t)));
+        HIPCHK(c, hipMalloc(&c->d_tris.p, (size_t)n * TRI_F4 * sizeof(float4)));
+        HIPCHK(c, hipMalloc(&c->d_shade.p, (size_t)n * SHADE_F4 * sizeof(float4)));
+        launch_pack_tris(d_verts, d_bvh_order, d_material, d_optex, c->d_tris, n, c->stream);
         launch_pack_shade(d_normals, d_uvs, d_tbn, d_smooth, d_material, c->d_shade, n, c->stream);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->d_nodes = dbvh.d_nodes; dguard.armed = false;
-        c->d_verts_res = d_verts; tmp.p[0] = nullptr;              // the builder's input stays resident (ptk_update_geometry)
-        (void)hipFree(dbvh.d_order); dbvh.d_order = nullptr;
+        c->d_nodes.adopt(d_bvh_nodes.p); d_bvh_nodes.p = nullptr;
+        c->d_verts_res.adopt(d_verts.p); d_verts.p = nullptr;      // the builder's input stays resident (ptk_update_geometry)
         bvh.num_nodes = dbvh.num_nodes; bvh.depth = dbvh.depth; bvh.stack_need = dbvh.stack_need;
     }
     else
     {
-        HIPCHK(c, up((void**)&c->d_nodes, bvh.nodes.data(), bvh.nodes.size() * 4));
-        HIPCHK(c, up((void**)&c->d_tris, tris.data(), tris.size() * 4));
-        dfree(c->d_flat_tris);
+        HIPCHK(c, up((void**)&c->d_nodes.p, bvh.nodes.data(), bvh.nodes.size() * 4));
+        HIPCHK(c, up((void**)&c->d_tris.p, tris.data(), tris.size() * 4));
+        c->d_flat_tris.release();
         if (n > 0 && n <= 16)
         {
             std::vector<float> flat((size_t)FLAT_TABLE_F4 * 4);     // records, room up to FLAT_MAX_TRIS, frame table, class table
             for (int32_t k = 0; k < n; k++)             // record of leaf position k holds triangle bvh.order[k]
                 std::memcpy(flat.data() + (size_t)bvh.order[k] * TRI_F4 * 4, tris.data() + (size_t)k * TRI_F4 * 4, TRI_F4 * 16);
-            HIPCHK(c, up((void**)&c->d_flat_tris, flat.data(), flat.size() * 4));
+            HIPCHK(c, up((void**)&c->d_flat_tris.p, flat.data(), flat.size() * 4));
         }
-        HIPCHK(c, up((void**)&c->d_shade, shade.data(), shade.size() * 4));
+        HIPCHK(c, up((void**)&c->d_shade.p, shade.data(), shade.size() * 4));
         if (c->d_flat_tris)                             // the frame table behind the flat records, from the normals just written
         {
             launch_flat_frames(c->d_shade, c->d_flat_tris, 0, n, c->stream);
             launch_flat_classes(c->d_flat_tris, n, c->opt_flat_zero_classes, c->opt_flat_rect_pairs, c->stream);     // ... and the class table and the pair word, from the records
             HIPCHK(c, hipGetLastError());
         }
-        HIPCHK(c, up((void**)&c->d_verts_res, s->verts, (size_t)n * 9 * sizeof(float)));
+        HIPCHK(c, up((void**)&c->d_verts_res.p, s->verts, (size_t)n * 9 * sizeof(float)));
     }
     c->built_on_device = on_device;
-    HIPCHK(c, up((void**)&c->d_mats, mats.data(), mats.size() * 4));
-    HIPCHK(c, up((void**)&c->d_lights, lights.data(), lights.size() * 4));
-    HIPCHK(c, up((void**)&c->d_texinfo, texinfo.data(), texinfo.size() * sizeof(int4)));
-    HIPCHK(c, up((void**)&c->d_texels, texels.data(), texels.size() * 4));
+    HIPCHK(c, up((void**)&c->d_mats.p, mats.data(), mats.size() * 4));
+    HIPCHK(c, up((void**)&c->d_lights.p, lights.data(), lights.size() * 4));
+    HIPCHK(c, up((void**)&c->d_texinfo.p, texinfo.data(), texinfo.size() * sizeof(int4)));
+    HIPCHK(c, up((void**)&c->d_texels.p, texels.data(), texels.size() * 4));
     c->num_nodes = bvh.num_nodes; c->num_tris = n; c->num_lights = s->num_lights; c->bvh_depth = bvh.depth; c->bvh_stack = bvh.stack_need;
     c->scene_bound = scene_bound;
     c->bvh_pad = 1e-5f * std::max(vmax, 1.0f);                     // bvh_build.cpp / bvh_device.hip: 1e-5 x max(1, largest |coordinate|)
@@ -1082,15 +996,15 @@ int ptk_set_frame(ptk_ctx* c, int width, int height, int max_depth)
     if (width != c->width || height != c->height || !c->d_accum)
     {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        dfree(c->d_primary); dfree(c->d_primary_hit); dfree(c->d_primary_rd); dfree(c->d_accum); dfree(c->d_rgb8); dfree(c->d_pixel_rng);
+        c->d_primary.release(); c->d_primary_hit.release(); c->d_primary_rd.release(); c->d_accum.release(); c->d_rgb8.release(); c->d_pixel_rng.release();
         c->pixel_rng_valid = false;
         size_t px = (size_t)width * height;
-        HIPCHK(c, hipMalloc(&c->d_primary, px * sizeof(float4)));
-        HIPCHK(c, hipMalloc(&c->d_primary_hit, px * sizeof(float4)));
-        HIPCHK(c, hipMalloc(&c->d_primary_rd, px * sizeof(float4)));
-        HIPCHK(c, hipMalloc(&c->d_pixel_rng, px * sizeof(uint2)));
-        HIPCHK(c, hipMalloc(&c->d_accum, px * 3 * sizeof(float)));
-        HIPCHK(c, hipMalloc(&c->d_rgb8, px * 3));
+        HIPCHK(c, hipMalloc(&c->d_primary.p, px * sizeof(float4)));
+        HIPCHK(c, hipMalloc(&c->d_primary_hit.p, px * sizeof(float4)));
+        HIPCHK(c, hipMalloc(&c->d_primary_rd.p, px * sizeof(float4)));
+        HIPCHK(c, hipMalloc(&c->d_pixel_rng.p, px * sizeof(uint2)));
+        HIPCHK(c, hipMalloc(&c->d_accum.p, px * 3 * sizeof(float)));
+        HIPCHK(c, hipMalloc(&c->d_rgb8.p, px * 3));
         free_adaptive(c);
         free_features(c);
         c->width = width; c->height = height;
@@ -1142,7 +1056,7 @@ int ptk_render(ptk_ctx* c, uint32_t first_sample, uint32_t spp_count, uint64_t s
         return fail(c, PTK_ERR_BAD_ARG, "the accumulator holds an adaptive render (per-pixel sample counts): ptk_reset, ptk_write_accum or a new resolution first");
     HIPCHK(c, hipSetDevice(c->device));
     c->last_launches = 0;
-    c->timed = false;
+    c->ev.timed = false;
     if (spp_count == 0) return PTK_OK;
     // RenderFrame() begins with mExit = false (pathtracer.cpp:742): an Exit() only cuts the frame(s) in flight, the next
     // call renders again.
@@ -1153,7 +1067,7 @@ int ptk_render(ptk_ctx* c, uint32_t first_sample, uint32_t spp_count, uint64_t s
     if (rc != PTK_OK) return rc;
     rc = run_passes(c, first_sample, spp_count, seed, false, accum_ptr(c), c->d_rgb8, c->d_exit, true);
     if (rc != PTK_OK) return rc;
-    c->timed = true;
+    c->ev.timed = true;
     c->samples = (int)(first_sample + spp_count);
     return PTK_OK;
 }
@@ -1176,7 +1090,7 @@ int ptk_render_adaptive(ptk_ctx* c, float threshold, uint32_t min_spp, uint32_t 
     if (!std::isfinite(threshold) || threshold < 0.0f) return fail(c, PTK_ERR_BAD_ARG, "ptk_render_adaptive: threshold must be finite and >= 0");
     HIPCHK(c, hipSetDevice(c->device));
     c->last_launches = 0;
-    c->timed = false;
+    c->ev.timed = false;
     const size_t px = (size_t)c->width * c->height;
     const int tiles_x = (c->width + PTK_TILE - 1) / PTK_TILE;
     const int capacity = tiles_x * ((c->height + PTK_TILE - 1) / PTK_TILE) * 4;
@@ -1184,18 +1098,18 @@ int ptk_render_adaptive(ptk_ctx* c, float threshold, uint32_t min_spp, uint32_t 
     {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         free_adaptive(c);
-        HIPCHK(c, hipMalloc(&c->d_counts, px * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc(&c->d_moments, px * 3 * sizeof(float)));
-        HIPCHK(c, hipMalloc(&c->d_adapt_active, (size_t)capacity * sizeof(unsigned long long)));
-        HIPCHK(c, hipMalloc(&c->d_adapt_traced, (size_t)capacity * sizeof(unsigned long long)));
-        HIPCHK(c, hipMalloc(&c->d_adapt_list, ((size_t)capacity + 1) * sizeof(unsigned)));
-        HIPCHK(c, hipMalloc(&c->d_adapt_stats, 4 * sizeof(unsigned long long)));
+        HIPCHK(c, hipMalloc(&c->d_counts.p, px * sizeof(uint32_t)));
+        HIPCHK(c, hipMalloc(&c->d_moments.p, px * 3 * sizeof(float)));
+        HIPCHK(c, hipMalloc(&c->d_adapt_active.p, (size_t)capacity * sizeof(unsigned long long)));
+        HIPCHK(c, hipMalloc(&c->d_adapt_traced.p, (size_t)capacity * sizeof(unsigned long long)));
+        HIPCHK(c, hipMalloc(&c->d_adapt_list.p, ((size_t)capacity + 1) * sizeof(unsigned)));
+        HIPCHK(c, hipMalloc(&c->d_adapt_stats.p, 4 * sizeof(unsigned long long)));
         c->adapt_capacity = capacity;
     }
     if (!c->h_adapt_count)
     {
-        HIPCHK(c, hipHostMalloc((void**)&c->h_adapt_count, 2 * sizeof(unsigned), hipHostMallocDefault));
-        for (int b = 0; b < 2; b++) HIPCHK(c, hipEventCreateWithFlags(&c->ev_adapt[b], hipEventDisableTiming));
+        HIPCHK(c, c->h_adapt_count.alloc(2));
+        for (int b = 0; b < 2; b++) HIPCHK(c, c->ev_adapt[b].create(hipEventDisableTiming));
     }
     // the accumulator starts from zero: ResetImage, plus the counts, S2 and the counters of this render
     int rc = ptk_reset(c);
@@ -1255,14 +1169,14 @@ int ptk_render_adaptive(ptk_ctx* c, float threshold, uint32_t min_spp, uint32_t 
             if (q != hipSuccess) return fail(c, PTK_ERR_HIP, std::string("hipEventSynchronize: ") + hipGetErrorString(q));
             if (c->h_adapt_count[(r - 1) & 1] == 0u) { converged = true; rounds = r; break; }     // round r found nothing to do
         }
-        if (__atomic_load_n(c->h_exit, __ATOMIC_RELAXED) >= gen) break;                        // Exit(): the rest stands down anyway
+        if (__atomic_load_n(c->h_exit.p, __ATOMIC_RELAXED) >= gen) break;                        // Exit(): the rest stands down anyway
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     unsigned long long st[3] = { 0, 0, 0 };
     HIPCHK(c, hipMemcpyAsync(st, c->d_adapt_stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     uint64_t active = 0;
-    const bool cut = __atomic_load_n(c->h_exit, __ATOMIC_RELAXED) >= gen;
+    const bool cut = __atomic_load_n(c->h_exit.p, __ATOMIC_RELAXED) >= gen;
     if (cut)
     {
         // the kernels that stood down left the active set as it was: count it
@@ -1311,7 +1225,7 @@ int ptk_render_features(ptk_ctx* c, uint32_t sample, uint64_t seed, uint32_t mas
     const size_t px = (size_t)c->width * c->height;
     c->feat_mask = 0;
     for (int k = 0; k < NUM_FEATURES; k++)
-        if (((mask >> k) & 1u) && !c->d_feat[k]) HIPCHK(c, hipMalloc(&c->d_feat[k], px * kFeatChannels[k] * 4));
+        if (((mask >> k) & 1u) && !c->d_feat[k]) HIPCHK(c, hipMalloc(&c->d_feat[k].p, px * kFeatChannels[k] * 4));
     c->feat_w = c->width; c->feat_h = c->height;
     FeatureParams f = {};
     void** slot[NUM_FEATURES] = { (void**)&f.depth, (void**)&f.triangle, (void**)&f.material, (void**)&f.bary, (void**)&f.position,
@@ -1428,18 +1342,17 @@ int ptk_collect_stats(ptk_ctx* c, uint32_t first_sample, uint32_t spp_count, uin
     if (rc != PTK_OK) return rc;
     // untimed counters-enabled variant; renders into a scratch accumulator so the image is untouched
     size_t px = (size_t)c->width * c->height;
-    float* scratch = nullptr; uint8_t* scratch8 = nullptr;
-    HIPCHK(c, hipMalloc(&scratch, px * 3 * sizeof(float)));
-    if (hipMalloc(&scratch8, px * 3) != hipSuccess) { (void)hipFree(scratch); return fail(c, PTK_ERR_HIP, "hipMalloc"); }
+    Buf<float> scratch; Buf<uint8_t> scratch8;   // (freed on the way out, behind the wait for the stream)
+    if (rc = scratch.alloc(c, px * 3); rc != PTK_OK) return rc;
+    if (rc = scratch8.alloc(c, px * 3); rc != PTK_OK) return rc;
     (void)hipMemsetAsync(scratch, 0, px * 3 * sizeof(float), c->stream);
     (void)hipMemsetAsync(c->d_stats, 0, 16 * sizeof(unsigned long long), c->stream);
     c->inputs_dirty = true;                      // ... and the zeroed counters
     rc = run_passes(c, first_sample, spp_count, seed, true, scratch, scratch8, nullptr, false);
-    c->timed = false;
+    c->ev.timed = false;
     unsigned long long h[16] = { 0 };
     hipError_t e = hipMemcpyAsync(h, c->d_stats, sizeof(h), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(scratch); (void)hipFree(scratch8);
     if (rc != PTK_OK) return rc;
     if (e != hipSuccess) return fail(c, PTK_ERR_HIP, hipGetErrorString(e));
     out->samples = owned_pixels(c) * (unsigned long long)spp_count; out->rays = h[1]; out->shadow_rays = h[2]; out->node_visits = h[3];
@@ -1623,7 +1536,7 @@ int ptk_request_exit(ptk_ctx* c)
     std::lock_guard<std::mutex> lk(c->exit_mu);
     uint32_t gen = c->render_gen.load();
     c->out_full_next = true;                     // a cut render may have skipped a full write of the bound hand-off buffer
-    if (gen > __atomic_load_n(c->h_exit, __ATOMIC_RELAXED)) __atomic_store_n(c->h_exit, gen, __ATOMIC_RELAXED);
+    if (gen > __atomic_load_n(c->h_exit.p, __ATOMIC_RELAXED)) __atomic_store_n(c->h_exit.p, gen, __ATOMIC_RELAXED);
     (void)hipSetDevice(c->device);
     (void)hipMemcpyAsync(c->d_exit, c->h_exit, sizeof(uint32_t), hipMemcpyHostToDevice, c->exit_stream);
     return PTK_OK;
@@ -1678,14 +1591,8 @@ int ptk_kernel_log(ptk_ctx* c, int capacity)
     if (!c || capacity < 0 || capacity > (1 << 20)) return PTK_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    for (hipEvent_t e : c->klog_ev) (void)hipEventDestroy(e);
     c->klog_ev.clear(); c->klog_n = 0;
-    for (int i = 0; i < 2 * capacity; i++)
-    {
-        hipEvent_t e = nullptr;
-        HIPCHK(c, hipEventCreate(&e));
-        c->klog_ev.push_back(e);
-    }
+    for (int i = 0; i < 2 * capacity; i++) { Event e; HIPCHK(c, e.create()); c->klog_ev.push_back(std::move(e)); }
     return PTK_OK;
 }
 
@@ -1696,7 +1603,8 @@ int ptk_kernel_log_read(ptk_ctx* c, float* trace_ms, int max_entries, int* num_e
     for (int k = 0; k < 2; k++) if (c->trace_stream[k]) HIPCHK(c, hipStreamSynchronize(c->trace_stream[k]));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int n = std::min(c->klog_n, max_entries);
-    for (int i = 0; i < n; i++) HIPCHK(c, hipEventElapsedTime(&trace_ms[i], c->klog_ev[2 * i], c->klog_ev[2 * i + 1]));
+    for (int i = 0; i < n; i++)
+        if (const int rc = event_ms(c, c->klog_ev[2 * i], c->klog_ev[2 * i + 1], &trace_ms[i]); rc != PTK_OK) return rc;
     *num_entries = n;
     c->klog_n = 0;
     return PTK_OK;
@@ -1706,17 +1614,10 @@ int ptk_last_kernel_ms(ptk_ctx* c, float* trace_ms, float* accumulate_ms)
 {
     if (!c || !trace_ms || !accumulate_ms) return PTK_ERR_BAD_ARG;
     *trace_ms = 0.0f; *accumulate_ms = 0.0f;
-    if (!c->timed) return PTK_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    int n = std::min(c->last_passes, (int)ptk_ctx::kMaxTimedPasses);
+    if (!c->ev.timed) return PTK_OK;
+    const int n = std::min(c->last_passes, (int)ptk_ctx::kMaxTimedPasses);
     for (int i = 0; i < n; i++)
-    {
-        float a = 0.0f, b = 0.0f;
-        HIPCHK(c, hipEventSynchronize(c->ev[i][2]));
-        HIPCHK(c, hipEventElapsedTime(&a, c->ev[i][0], c->ev[i][1]));
-        HIPCHK(c, hipEventElapsedTime(&b, c->ev[i][1], c->ev[i][2]));
-        *trace_ms += a; *accumulate_ms += b;
-    }
+        if (const int rc = c->ev.add(c, i, trace_ms, accumulate_ms); rc != PTK_OK) return rc;
     return PTK_OK;
 }
 

@@ -40,17 +40,16 @@ static int bake_rays_on_stream(ptk_ctx* c, int width, int height, const float* d
                                const float* acc_out, int32_t* d_owner, float* d_bary, float* d_pos, BakeParams& b, uint32_t& covered)
 {
     const size_t texels = (size_t)width * height, blocks = (texels + 255) / 256;
-    c->bake_timed = false; c->bake_traced = false;
-    int rc = ensure_events(c, c->ev_bake);
+    c->ev_bake.begin();
     // the plane, then one count per block of 256 texels and the total
-    if (rc == PTK_OK) rc = grow(c, c->d_bake_plane, c->bake_plane_texels, texels, sizeof(int), (blocks + 1) * sizeof(int));
+    int rc = c->d_bake_plane.grow(c, texels, sizeof(int), (blocks + 1) * sizeof(int));
     if (rc != PTK_OK) return rc;
     b = BakeParams{};
     b.uvs = d_uvs; b.shade = c->d_shade; b.verts = c->d_verts_res; b.num_tris = c->d_verts_res ? c->num_tris : 0;
     b.width = width; b.height = height; b.offset = offset; b.back = (flags & PTK_BAKE_BACK) ? 1 : 0; b.key_base = key_base;
-    b.plane = c->d_bake_plane; b.block_counts = (uint32_t*)(c->d_bake_plane + c->bake_plane_texels);
+    b.plane = c->d_bake_plane; b.block_counts = (uint32_t*)(c->d_bake_plane + c->d_bake_plane.cap);
     b.owner = d_owner; b.bary = d_bary; b.pos = d_pos;
-    HIPCHK(c, hipEventRecord(c->ev_bake[0], c->stream));
+    if (const int rm = c->ev_bake.mark(c, 0, c->stream); rm != PTK_OK) return rm;
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)b.plane, PTK_BAKE_UNOWNED, texels, c->stream));
     launch_bake_cover(b, c->stream);
     HIPCHK(c, hipGetLastError());
@@ -58,29 +57,29 @@ static int bake_rays_on_stream(ptk_ctx* c, int width, int height, const float* d
     if (want_rays)
     {
         // the covered count sizes the compacted arrays and the trace: the one host wait of a bake
-        if (!c->h_bake_total) HIPCHK(c, hipHostMalloc((void**)&c->h_bake_total, sizeof(uint32_t), hipHostMallocDefault));
+        HIPCHK(c, c->h_bake_total.alloc(1));
         uint32_t* d_total = b.block_counts + blocks;
         launch_bake_count(b, d_total, c->stream);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev_bake[1], c->stream));
+        if (const int rm = c->ev_bake.mark(c, 1, c->stream); rm != PTK_OK) return rm;
         HIPCHK(c, hipMemcpyAsync(c->h_bake_total, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         covered = *c->h_bake_total;
         if (covered > texels) return fail(c, PTK_ERR_HIP, "ptk_bake_lightmap: covered count exceeds the map");
-        if (rc = grow(c, c->d_bake_compact, c->bake_compact_rays, covered, 11 * sizeof(float)); rc != PTK_OK) return rc;
+        if (rc = c->d_bake_compact.grow(c, covered, 11 * sizeof(float)); rc != PTK_OK) return rc;
         if (covered)
         {
-            const size_t cap = c->bake_compact_rays;
+            const size_t cap = c->d_bake_compact.cap;
             b.origins = c->d_bake_compact; b.dirs = b.origins + cap * 3; b.sums = b.dirs + cap * 3;
             b.keys = (uint32_t*)(b.sums + cap * 3); b.texel = b.keys + cap;
             b.out = acc_out;
         }
     }
-    else HIPCHK(c, hipEventRecord(c->ev_bake[1], c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_bake[2], c->stream));
+    else if (const int rm = c->ev_bake.mark(c, 1, c->stream); rm != PTK_OK) return rm;
+    if (const int rm = c->ev_bake.mark(c, 2, c->stream); rm != PTK_OK) return rm;
     launch_bake_rays(b, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_bake[3], c->stream));
+    if (const int rm = c->ev_bake.mark(c, 3, c->stream); rm != PTK_OK) return rm;
     return PTK_OK;
 }
 
@@ -102,15 +101,14 @@ static int bake_on_stream(ptk_ctx* c, int width, int height, const float* d_uvs,
                                                 (flags & PTK_BAKE_ACCUMULATE) ? PTK_RAYS_ACCUMULATE : 0u, b.sums, b.keys);
             if (rc != PTK_OK) return rc;
         }
-        HIPCHK(c, hipEventRecord(c->ev_bake[4], c->stream));
+        if (const int rm = c->ev_bake.mark(c, 4, c->stream); rm != PTK_OK) return rm;
         if (!(flags & PTK_BAKE_ACCUMULATE)) HIPCHK(c, hipMemsetAsync(d_out, 0, texels * 3 * sizeof(float), c->stream));     // uncovered texels
         launch_bake_scatter(b.sums, b.texel, covered, d_out, c->stream);
         HIPCHK(c, hipGetLastError());
-        c->bake_traced = true;
     }
-    else HIPCHK(c, hipEventRecord(c->ev_bake[4], c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_bake[5], c->stream));
-    c->bake_timed = true;
+    else if (const int rm = c->ev_bake.mark(c, 4, c->stream); rm != PTK_OK) return rm;
+    if (const int rm = c->ev_bake.mark(c, 5, c->stream); rm != PTK_OK) return rm;
+    c->ev_bake.done();
     return PTK_OK;
 }
 
@@ -225,7 +223,7 @@ int ptk_lightmap_dilate_device(ptk_ctx* c, int width, int height, int passes, fl
     if (rc != PTK_OK || passes == 0) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t texels = (size_t)width * height;
-    if (const int rg = grow(c, c->d_bake_dilate, c->bake_dilate_texels, texels, 4 * sizeof(float)); rg != PTK_OK) return rg;
+    if (const int rg = c->d_bake_dilate.grow(c, texels, 4 * sizeof(float)); rg != PTK_OK) return rg;
     // ping-pong between the caller's arrays and the context's; an odd number of passes ends in the latter and is copied back
     float* img[2] = { d_image, c->d_bake_dilate };
     int32_t* own[2] = { d_owner, (int32_t*)(c->d_bake_dilate + texels * 3) };
@@ -259,19 +257,13 @@ int ptk_last_bake_ms(ptk_ctx* c, float* coverage_ms, float* raygen_ms, float* tr
     if (!c) return PTK_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     float t[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    if (c->bake_timed)
-    {
-        HIPCHK(c, hipEventSynchronize(c->ev_bake[5]));
-        HIPCHK(c, hipEventElapsedTime(&t[0], c->ev_bake[0], c->ev_bake[1]));
-        HIPCHK(c, hipEventElapsedTime(&t[1], c->ev_bake[2], c->ev_bake[3]));
-        HIPCHK(c, hipEventElapsedTime(&t[2], c->ev_bake[3], c->ev_bake[4]));
-        HIPCHK(c, hipEventElapsedTime(&t[3], c->ev_bake[4], c->ev_bake[5]));
-    }
+    int rc = c->ev_bake.elapsed(c, 0, 1, &t[0]);
+    if (rc == PTK_OK) rc = c->ev_bake.spans(c, 2, 3, &t[1]);
     if (coverage_ms) *coverage_ms = t[0];
     if (raygen_ms) *raygen_ms = t[1];
     if (trace_ms) *trace_ms = t[2];
     if (scatter_ms) *scatter_ms = t[3];
-    return PTK_OK;
+    return rc;
 }
 
 }  // extern "C"

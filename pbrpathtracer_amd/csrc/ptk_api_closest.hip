@@ -9,18 +9,10 @@
 
 using namespace ptk;
 
-// The argument checks the entries share; PTK_OK with *nothing = true: the call is legal and has nothing to do.
+// The argument checks the entries share: check_query_args with the word of these entries' texts.
 static int check_closest_args(ptk_ctx* c, const char* who, int32_t num_points, const float* points, bool have_out, bool* nothing)
 {
-    *nothing = false;
-    if (!c) return PTK_ERR_BAD_ARG;
-    if (num_points < 0) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": negative point count");
-    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
-    if (!have_out) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": no output array");
-    if (num_points > 0 && !points) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": null array");
-    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
-    *nothing = num_points == 0;
-    return PTK_OK;
+    return check_query_args(c, who, "point count", num_points, points, points, have_out, nothing);
 }
 
 // The call proper, on the context's stream, every pointer into this GPU's memory: h holds the points and the outputs, the scene
@@ -28,7 +20,7 @@ static int check_closest_args(ptk_ctx* c, const char* who, int32_t num_points, c
 // from fills.
 static int closest_on_stream(ptk_ctx* c, ClosestParams& h)
 {
-    c->closest_timed = false;
+    c->ev_closest.begin();
     const size_t n = (size_t)h.num_points;
     if (c->num_nodes == 0)
     {
@@ -40,12 +32,11 @@ static int closest_on_stream(ptk_ctx* c, ClosestParams& h)
     }
     h.nodes = c->d_nodes; h.tris = c->d_tris;
     h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound;
-    if (const int rc = ensure_events(c, c->ev_closest); rc != PTK_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_closest[0], c->stream));
+    if (const int rc = c->ev_closest.mark(c, 0, c->stream); rc != PTK_OK) return rc;
     launch_closest(h, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_closest[1], c->stream));
-    c->closest_timed = true;
+    if (const int rc = c->ev_closest.mark(c, 1, c->stream); rc != PTK_OK) return rc;
+    c->ev_closest.done();
     return PTK_OK;
 }
 
@@ -77,26 +68,16 @@ int ptk_closest_points(ptk_ctx* c, int32_t num_points, const float* points, cons
     const auto d_points = s.in(points, 3 * n), d_max_dist = s.in(max_dist, n);
     const auto d_tri = s.out(tri, n);
     const auto d_dist = s.out(dist, n), d_point = s.out(point, 3 * n), d_bary = s.out(bary, 2 * n);
-    return s.run([&] {
-        ClosestParams h = {};
-        h.points = d_points; h.max_dist = d_max_dist; h.num_points = num_points;
-        h.tri = d_tri; h.dist = d_dist; h.point = d_point; h.bary = d_bary;
-        return closest_on_stream(c, h);
-    });
+    return s.run([&] { return ptk_closest_points_device(c, num_points, d_points, d_max_dist, d_tri, d_dist, d_point, d_bary); });
 }
 
 int ptk_last_closest_ms(ptk_ctx* c, float* ms)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float t = 0.0f;
-    if (c->closest_timed)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(c->ev_closest[1]));
-        HIPCHK(c, hipEventElapsedTime(&t, c->ev_closest[0], c->ev_closest[1]));
-    }
+    const int rc = c->ev_closest.elapsed(c, 0, 1, &t);
     if (ms) *ms = t;
-    return PTK_OK;
+    return rc;
 }
 
 int ptk_closest_stats(ptk_ctx* c, int32_t num_points, const float* d_points, const float* d_max_dist, uint64_t* node_visits, uint64_t* tri_tests)
@@ -108,7 +89,7 @@ int ptk_closest_stats(ptk_ctx* c, int32_t num_points, const float* d_points, con
     if (!nothing && c->num_nodes > 0)
     {
         HIPCHK(c, hipSetDevice(c->device));
-        if (!c->d_closest_stats) HIPCHK(c, hipMalloc(&c->d_closest_stats, sizeof(got)));
+        if (!c->d_closest_stats) HIPCHK(c, hipMalloc(&c->d_closest_stats.p, sizeof(got)));
         HIPCHK(c, hipMemsetAsync(c->d_closest_stats, 0, sizeof(got), c->stream));
         ClosestParams h = {};
         h.points = d_points; h.max_dist = d_max_dist; h.num_points = num_points;

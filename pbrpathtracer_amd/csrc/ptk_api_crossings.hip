@@ -14,19 +14,10 @@ using namespace ptk;
 
 static const float k_default_dirs[9] = PTK_INSIDE_DEFAULT_DIRS;
 
-// The argument checks the entries share (`a`, `b`: the arrays a count > 0 needs; b may be the same as a); PTK_OK with
-// *nothing = true: the call is legal and has nothing to do.
+// The argument checks the entries share: check_query_args with the word of these entries' texts.
 static int check_cross_args(ptk_ctx* c, const char* who, int32_t num, const void* a, const void* b, bool have_out, bool* nothing)
 {
-    *nothing = false;
-    if (!c) return PTK_ERR_BAD_ARG;
-    if (num < 0) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": negative count");
-    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
-    if (!have_out) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": no output array");
-    if (num > 0 && (!a || !b)) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": null array");
-    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
-    *nothing = num == 0;
-    return PTK_OK;
+    return check_query_args(c, who, "count", num, a, b, have_out, nothing);
 }
 
 // ... and what the containment entries add: the direction set and the mode
@@ -47,7 +38,7 @@ static void scene_half(ptk_ctx* c, CrossingsParams& h)
 // a scene without triangles has no tree to walk and gets its zeros (and the closest-point misses) from fills.
 static int crossings_on_stream(ptk_ctx* c, CrossingsParams& h)
 {
-    c->crossings_timed = false;
+    c->ev_crossings.begin();
     const size_t n = (size_t)h.num;
     if (c->num_nodes == 0)
     {
@@ -56,19 +47,18 @@ static int crossings_on_stream(ptk_ctx* c, CrossingsParams& h)
         return PTK_OK;
     }
     scene_half(c, h);
-    if (const int rc = ensure_events(c, c->ev_crossings); rc != PTK_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_crossings[0], c->stream));
+    if (const int rc = c->ev_crossings.mark(c, 0, c->stream); rc != PTK_OK) return rc;
     launch_crossings(h, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_crossings[1], c->stream));
-    c->crossings_timed = true;
+    if (const int rc = c->ev_crossings.mark(c, 1, c->stream); rc != PTK_OK) return rc;
+    c->ev_crossings.done();
     return PTK_OK;
 }
 
 // `closest`: null, or ptk_signed_distance's closest-point query, which runs first; then h.dist is its dist
 static int contains_on_stream(ptk_ctx* c, CrossingsParams& h, ClosestParams* closest)
 {
-    c->crossings_timed = false;
+    c->ev_crossings.begin();
     const size_t n = (size_t)h.num;
     if (c->num_nodes == 0)
     {
@@ -84,8 +74,7 @@ static int contains_on_stream(ptk_ctx* c, CrossingsParams& h, ClosestParams* clo
         return PTK_OK;
     }
     scene_half(c, h);
-    if (const int rc = ensure_events(c, c->ev_crossings); rc != PTK_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_crossings[0], c->stream));
+    if (const int rc = c->ev_crossings.mark(c, 0, c->stream); rc != PTK_OK) return rc;
     if (closest)
     {
         closest->nodes = c->d_nodes; closest->tris = c->d_tris; closest->num_nodes = c->num_nodes; closest->scene_bound = c->scene_bound;
@@ -97,8 +86,8 @@ static int contains_on_stream(ptk_ctx* c, CrossingsParams& h, ClosestParams* clo
         launch_contains(h, c->stream);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipEventRecord(c->ev_crossings[1], c->stream));
-    c->crossings_timed = true;
+    if (const int rc = c->ev_crossings.mark(c, 1, c->stream); rc != PTK_OK) return rc;
+    c->ev_crossings.done();
     return PTK_OK;
 }
 
@@ -133,11 +122,7 @@ int ptk_crossings_rays(ptk_ctx* c, int32_t num_rays, const float* origins, const
     Stage s(c);
     const auto d_origins = s.in(origins, 3 * n), d_dirs = s.in(dirs, 3 * n), d_tmax = s.in(tmax, n);
     const auto d_front = s.out(front, n), d_back = s.out(back, n);
-    return s.run([&] {
-        CrossingsParams h = {};
-        h.origins = d_origins; h.dirs = d_dirs; h.tmax = d_tmax; h.num = num_rays; h.front = d_front; h.back = d_back;
-        return crossings_on_stream(c, h);
-    });
+    return s.run([&] { return ptk_crossings_rays_device(c, num_rays, d_origins, d_dirs, d_tmax, d_front, d_back); });
 }
 
 int ptk_contains_points_device(ptk_ctx* c, int32_t num_points, const float* d_points, int32_t num_dirs, const float* d_dirs, int32_t mode,
@@ -166,11 +151,7 @@ int ptk_contains_points(ptk_ctx* c, int32_t num_points, const float* points, int
     const auto d_points = s.in(points, 3 * n), d_dirs = s.in(dirs, 3 * (size_t)num_dirs);
     const auto d_inside = s.out(inside, n);
     const auto d_winding = s.out(winding, n * (size_t)num_dirs);
-    return s.run([&] {
-        CrossingsParams h = {};
-        h.origins = d_points; h.dirs = d_dirs; h.num = num_points; h.num_dirs = num_dirs; h.mode = mode; h.inside = d_inside; h.winding = d_winding;
-        return contains_on_stream(c, h, nullptr);
-    });
+    return s.run([&] { return ptk_contains_points_device(c, num_points, d_points, num_dirs, d_dirs, mode, d_inside, d_winding); });
 }
 
 int ptk_signed_distance_device(ptk_ctx* c, int32_t num_points, const float* d_points, const float* d_max_dist, int32_t num_dirs, const float* d_dirs,
@@ -201,27 +182,16 @@ int ptk_signed_distance(ptk_ctx* c, int32_t num_points, const float* points, con
     const auto d_points = s.in(points, 3 * n), d_max_dist = s.in(max_dist, n), d_dirs = s.in(dirs, 3 * (size_t)num_dirs);
     const auto d_tri = s.out(tri, n);
     const auto d_dist = s.out(dist, n), d_point = s.out(point, 3 * n), d_bary = s.out(bary, 2 * n);
-    return s.run([&] {
-        ClosestParams q = {};
-        q.points = d_points; q.max_dist = d_max_dist; q.num_points = num_points; q.tri = d_tri; q.dist = d_dist; q.point = d_point; q.bary = d_bary;
-        CrossingsParams h = {};
-        h.origins = d_points; h.dirs = d_dirs; h.num = num_points; h.num_dirs = num_dirs; h.mode = mode; h.dist = d_dist;
-        return contains_on_stream(c, h, &q);
-    });
+    return s.run([&] { return ptk_signed_distance_device(c, num_points, d_points, d_max_dist, num_dirs, d_dirs, mode, d_tri, d_dist, d_point, d_bary); });
 }
 
 int ptk_last_crossings_ms(ptk_ctx* c, float* ms)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float t = 0.0f;
-    if (c->crossings_timed)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(c->ev_crossings[1]));
-        HIPCHK(c, hipEventElapsedTime(&t, c->ev_crossings[0], c->ev_crossings[1]));
-    }
+    const int rc = c->ev_crossings.elapsed(c, 0, 1, &t);
     if (ms) *ms = t;
-    return PTK_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -101,16 +101,14 @@ int ptk_probe_scan_u64(ptk_ctx* c, int32_t n, const uint64_t* in, uint64_t* out,
     if (items < 2) return fail(c, PTK_ERR_BAD_ARG, "ptk_probe_scan_u64: at least two items per workgroup");
     if (n == 0) return PTK_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    uint64_t* d_sums = nullptr;
-    HIPCHK(c, hipMalloc(&d_sums, (scan_u64_sums((size_t)n, items) + 1) * sizeof(uint64_t)));
+    Buf<uint64_t> d_sums;                        // (freed behind run()'s wait for the stream)
+    if (const int rc = d_sums.alloc(c, scan_u64_sums((size_t)n, items) + 1); rc != PTK_OK) return rc;
     Stage s(c);
     const auto d_in = s.in(in, (size_t)n), d_out = s.out(out, (size_t)n);
-    const int rc = s.run([&] {
+    return s.run([&] {
         launch_scan_u64(d_in, d_out, (size_t)n, items, d_sums, c->stream);
         return s.launched();
     });
-    (void)hipFree(d_sums);
-    return rc;
 }
 
 }  // extern "C"

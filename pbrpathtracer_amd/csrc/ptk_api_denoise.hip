@@ -39,7 +39,7 @@ static int check_planes_args(ptk_ctx* c, int width, int height, const float* col
 // the context's four packed images for `px` pixels (64 B per pixel, grown to the largest call so far)
 static int denoise_images(ptk_ctx* c, size_t px, DenoiseImages& im)
 {
-    if (const int rc = grow(c, c->d_denoise, c->denoise_px, px, 4 * sizeof(float4)); rc != PTK_OK) return rc;
+    if (const int rc = c->d_denoise.grow(c, px, 4 * sizeof(float4)); rc != PTK_OK) return rc;
     im.g0 = c->d_denoise; im.g1 = im.g0 + px; im.c[0] = im.g1 + px; im.c[1] = im.c[0] + px;
     return PTK_OK;
 }
@@ -50,7 +50,7 @@ static int filter_on_stream(ptk_ctx* c, int width, int height, const DenoiseImag
                             const float* d_albedo, float* d_out_color, float* d_out_variance)
 {
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_denoise[1], c->stream));
+    if (const int rm = c->ev_denoise.mark(c, 1, c->stream); rm != PTK_OK) return rm;
     DenoiseFilterParams f = {};
     f.g0 = im.g0; f.g1 = im.g1; f.width = width; f.height = height;
     f.iterations = p.iterations; f.normal_squarings = p.normal_squarings; f.have_variance = have_variance ? 1 : 0;
@@ -61,14 +61,14 @@ static int filter_on_stream(ptk_ctx* c, int width, int height, const DenoiseImag
         launch_denoise_filter(f, c->stream);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_denoise[2], c->stream));
+    if (const int rm = c->ev_denoise.mark(c, 2, c->stream); rm != PTK_OK) return rm;
     DenoiseUnpackParams u = {};
     u.g0 = im.g0; u.c = im.c[p.iterations & 1]; u.albedo = d_albedo; u.out_color = d_out_color; u.out_variance = d_out_variance;
     u.width = width; u.height = height;
     launch_denoise_unpack(u, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_denoise[3], c->stream));
-    c->denoise_timed = true;
+    if (const int rm = c->ev_denoise.mark(c, 3, c->stream); rm != PTK_OK) return rm;
+    c->ev_denoise.done();
     return PTK_OK;
 }
 
@@ -77,11 +77,10 @@ static int planes_on_stream(ptk_ctx* c, int width, int height, const float* d_co
                             const float* d_position, const float* d_albedo, const float* d_variance, const ptk_denoise_params& p,
                             float* d_out_color, float* d_out_variance)
 {
-    c->denoise_timed = false;
+    c->ev_denoise.begin();
     DenoiseImages im;
     if (const int rc = denoise_images(c, (size_t)width * height, im); rc != PTK_OK) return rc;
-    if (const int rc = ensure_events(c, c->ev_denoise); rc != PTK_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_denoise[0], c->stream));
+    if (const int rm = c->ev_denoise.mark(c, 0, c->stream); rm != PTK_OK) return rm;
     DenoisePackParams k = {};
     k.color = d_color; k.mask = d_mask; k.normal = d_normal; k.position = d_position; k.albedo = d_albedo; k.variance = d_variance;
     k.width = width; k.height = height;
@@ -146,17 +145,16 @@ int ptk_denoise_frame(ptk_ctx* c, const ptk_denoise_params* params, uint32_t fla
     if (variance && !adaptive) return fail(c, PTK_ERR_BAD_ARG, "ptk_denoise_frame: PTK_DENOISE_VARIANCE needs an adaptive render in the accumulator");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t px = (size_t)c->width * c->height;
-    if (!c->d_denoised) HIPCHK(c, hipMalloc(&c->d_denoised, px * 3 * sizeof(float)));
-    c->denoise_timed = false;
+    if (!c->d_denoised) HIPCHK(c, hipMalloc(&c->d_denoised.p, px * 3 * sizeof(float)));
+    c->ev_denoise.begin();
     DenoiseImages im;
     if (const int rc = denoise_images(c, px, im); rc != PTK_OK) return rc;
-    if (const int rc = ensure_events(c, c->ev_denoise); rc != PTK_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_denoise[0], c->stream));
+    if (const int rm = c->ev_denoise.mark(c, 0, c->stream); rm != PTK_OK) return rm;
     DenoiseFramePackParams k = {};
     k.accum = accum_ptr(c); k.moments = variance ? c->d_moments : nullptr; k.counts = adaptive ? c->d_counts : nullptr;
-    k.triangle = (const int32_t*)c->d_feat[PTK_FEAT_TRIANGLE]; k.emission = (const float*)c->d_feat[PTK_FEAT_EMISSION];
-    k.normal = (const float*)c->d_feat[PTK_FEAT_NORMAL]; k.position = (const float*)c->d_feat[PTK_FEAT_POSITION];
-    k.albedo = (const float*)c->d_feat[PTK_FEAT_ALBEDO];
+    k.triangle = (const int32_t*)c->d_feat[PTK_FEAT_TRIANGLE].p; k.emission = (const float*)c->d_feat[PTK_FEAT_EMISSION].p;
+    k.normal = (const float*)c->d_feat[PTK_FEAT_NORMAL].p; k.position = (const float*)c->d_feat[PTK_FEAT_POSITION].p;
+    k.albedo = (const float*)c->d_feat[PTK_FEAT_ALBEDO].p;
     k.width = c->width; k.height = c->height; k.samples = c->samples.load(); k.rank = c->rank; k.world = c->world;
     launch_denoise_pack_frame(k, im, c->stream);
     const int rc = filter_on_stream(c, c->width, c->height, im, variance, *params, k.albedo, c->d_denoised, nullptr);
@@ -201,16 +199,11 @@ int ptk_last_denoise_ms(ptk_ctx* c, float* pack_ms, float* filter_ms, float* unp
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float t[3] = { 0.0f, 0.0f, 0.0f };
-    if (c->denoise_timed)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(c->ev_denoise[3]));
-        for (int k = 0; k < 3; k++) HIPCHK(c, hipEventElapsedTime(&t[k], c->ev_denoise[k], c->ev_denoise[k + 1]));
-    }
+    const int rc = c->ev_denoise.spans(c, 0, 3, t);
     if (pack_ms) *pack_ms = t[0];
     if (filter_ms) *filter_ms = t[1];
     if (unpack_ms) *unpack_ms = t[2];
-    return PTK_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -55,7 +55,7 @@ static int ensure_state(ptk_ctx* c)
 {
     if (c->d_display_hist) return PTK_OK;
     const size_t bytes = DISPLAY_BINS * sizeof(uint32_t) + sizeof(ptk_exposure_state);
-    HIPCHK(c, hipMalloc(&c->d_display_hist, bytes));
+    HIPCHK(c, hipMalloc(&c->d_display_hist.p, bytes));
     HIPCHK(c, hipMemsetAsync(c->d_display_hist, 0, bytes, c->stream));
     return PTK_OK;
 }
@@ -64,11 +64,10 @@ static int ensure_state(ptk_ctx* c)
 // [2] behind the exposure step, [3] behind the apply kernel (a manual call launches the last alone).
 static int display_on_stream(ptk_ctx* c, const DisplaySource& src, const ptk_display_params& p, uint8_t* d_rgb8, ptk_exposure_state* d_state_out)
 {
-    c->display_timed = false;
+    c->ev_display.begin();
     if (const int rc = ensure_state(c); rc != PTK_OK) return rc;
-    if (const int rc = ensure_events(c, c->ev_display); rc != PTK_OK) return rc;
     const bool metered = p.mode == PTK_EXPOSURE_METERED;
-    HIPCHK(c, hipEventRecord(c->ev_display[0], c->stream));
+    if (const int rm = c->ev_display.mark(c, 0, c->stream); rm != PTK_OK) return rm;
     if (metered)
     {
         DisplayMeterParams m = {};
@@ -76,7 +75,7 @@ static int display_on_stream(ptk_ctx* c, const DisplaySource& src, const ptk_dis
         launch_display_meter(m, c->stream);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipEventRecord(c->ev_display[1], c->stream));
+    if (const int rm = c->ev_display.mark(c, 1, c->stream); rm != PTK_OK) return rm;
     if (metered)
     {
         DisplayExposureParams x = {};
@@ -86,14 +85,14 @@ static int display_on_stream(ptk_ctx* c, const DisplaySource& src, const ptk_dis
         launch_display_exposure(x, c->stream);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipEventRecord(c->ev_display[2], c->stream));
+    if (const int rm = c->ev_display.mark(c, 2, c->stream); rm != PTK_OK) return rm;
     DisplayApplyParams a = {};
     a.src = src; a.rgb8 = d_rgb8; a.state = metered ? state_ptr(c) : nullptr; a.exposure = p.exposure;
     a.iw2 = 1.0f / (p.white * p.white); a.op = p.op; a.transfer = p.transfer;
     launch_display_apply(a, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_display[3], c->stream));
-    c->display_timed = true;
+    if (const int rm = c->ev_display.mark(c, 3, c->stream); rm != PTK_OK) return rm;
+    c->ev_display.done();
     if (d_state_out) HIPCHK(c, hipMemcpyAsync(d_state_out, state_ptr(c), sizeof(ptk_exposure_state), hipMemcpyDeviceToDevice, c->stream));
     return PTK_OK;
 }
@@ -173,7 +172,7 @@ int ptk_display_frame(ptk_ctx* c, int source, const ptk_display_params* params)
         src.kind = adaptive ? DISPLAY_SRC_ACCUM_COUNTS : DISPLAY_SRC_ACCUM_SAMPLES;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_display) HIPCHK(c, hipMalloc(&c->d_display, px * 3));
+    if (!c->d_display) HIPCHK(c, hipMalloc(&c->d_display.p, px * 3));
     const int rc = display_on_stream(c, src, *params, c->d_display, nullptr);
     if (rc == PTK_OK) { c->disp_w = c->width; c->disp_h = c->height; }
     return rc;
@@ -222,16 +221,11 @@ int ptk_last_display_ms(ptk_ctx* c, float* meter_ms, float* exposure_ms, float* 
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float t[3] = { 0.0f, 0.0f, 0.0f };
-    if (c->display_timed)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(c->ev_display[3]));
-        for (int k = 0; k < 3; k++) HIPCHK(c, hipEventElapsedTime(&t[k], c->ev_display[k], c->ev_display[k + 1]));
-    }
+    const int rc = c->ev_display.spans(c, 0, 3, t);
     if (meter_ms) *meter_ms = t[0];
     if (exposure_ms) *exposure_ms = t[1];
     if (apply_ms) *apply_ms = t[2];
-    return PTK_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -155,8 +155,8 @@ int ptk_gather_accum(ptk_ctx* c, void* rccl_comm, int root)
     for (int r = 0; r < world; r++) { bases[r] = (long long)total; total += (size_t)packed_floats_of(W, H, r, world); }
     const size_t mine = (size_t)packed_floats_of(W, H, rank, world);
     const size_t need = rank == root ? total : mine;
-    int rg = grow(c, c->d_packed, c->packed_floats, need, sizeof(float), 0, c->xstream);
-    if (rg == PTK_OK && rank == root) rg = grow(c, c->d_gathered, c->gathered_floats, (size_t)W * H * 3, sizeof(float), 0, c->xstream);
+    int rg = c->d_packed.grow(c, need, sizeof(float), 0, c->xstream);
+    if (rg == PTK_OK && rank == root) rg = c->d_gathered.grow(c, (size_t)W * H * 3, sizeof(float), 0, c->xstream);
     if (rg != PTK_OK) return rg;
     HIPCHK(c, hipEventRecord(c->ev_rendered, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->xstream, c->ev_rendered, 0));

@@ -65,19 +65,17 @@ static int ensure_refit_topology(ptk_ctx* c)
         std::vector<int> fill(start.begin(), start.end() - 1);
         for (int id = 0; id < nn; id++) list[(size_t)fill[level[id]]++] = id;
     }
-    int32_t* d_list = nullptr; int32_t* d_pos = nullptr; float4* d_side = nullptr; double* d_partial = nullptr;
-    hipError_t e = hipMalloc(&d_list, (size_t)nn * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_partial, ((size_t)nn + 255) / 256 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&d_pos, (size_t)nt * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_side, (size_t)nn * 2 * sizeof(float4));
-    if (e == hipSuccess) e = hipMemcpy(d_list, list.data(), (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(d_pos, 0, (size_t)nt * sizeof(int32_t), c->stream);
+    hipError_t e = hipMalloc(&c->d_level_nodes.p, (size_t)nn * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&c->d_refit_partial.p, ((size_t)nn + 255) / 256 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&c->d_tri_pos.p, (size_t)nt * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&c->d_refit_side.p, (size_t)nn * 2 * sizeof(float4));
+    if (e == hipSuccess) e = hipMemcpy(c->d_level_nodes, list.data(), (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_tri_pos, 0, (size_t)nt * sizeof(int32_t), c->stream);
     if (e != hipSuccess)
     {
-        (void)hipFree(d_list); (void)hipFree(d_pos); (void)hipFree(d_side); (void)hipFree(d_partial);
+        c->d_level_nodes.release(); c->d_tri_pos.release(); c->d_refit_side.release(); c->d_refit_partial.release();
         return fail(c, PTK_ERR_HIP, std::string("refit tables: ") + hipGetErrorString(e));
     }
-    c->d_level_nodes = d_list; c->d_tri_pos = d_pos; c->d_refit_side = d_side; c->d_refit_partial = d_partial;
     c->level_start = start;
     launch_inverse_order(c->d_tris, c->d_tri_pos, nt, c->stream);
     queue_refit(c, c->bvh_pad, 0, c->stream);
@@ -112,17 +110,15 @@ static int update_geometry(ptk_ctx* c, int32_t first, int32_t count, const float
 
     // 1. stage the arrays and find the bounds the scene WOULD have, on a stream of their own: nothing resident is written yet
     const size_t floats = per * (normals ? 3 : 1);
-    if (floats > c->geo_stage_floats)
+    if (floats > c->d_geo_stage.cap)
     {
-        if (c->geo_done_recorded) HIPCHK(c, hipEventSynchronize(c->ev_geo_t[4]));       // (the previous update's repack reads the old buffer)
-        dfree(c->d_geo_stage); c->geo_stage_floats = 0;
-        HIPCHK(c, hipMalloc(&c->d_geo_stage, floats * sizeof(float)));
-        c->geo_stage_floats = floats;
+        if (c->ev_geo_t.timed) HIPCHK(c, hipEventSynchronize(c->ev_geo_t.ev[4]));    // (the previous update's repack reads the old buffer)
+        if (rc = c->d_geo_stage.alloc(c, floats); rc != PTK_OK) return rc;
     }
     float* sv = c->d_geo_stage; float* sn = normals ? sv + per : nullptr; float* st = normals ? sv + 2 * per : nullptr;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (c->geo_done_recorded) HIPCHK(c, hipStreamWaitEvent(c->geo_stream, c->ev_geo_t[4], 0));
-    HIPCHK(c, hipEventRecord(c->ev_geo_t[0], c->geo_stream));
+    if (c->ev_geo_t.timed) HIPCHK(c, hipStreamWaitEvent(c->geo_stream, c->ev_geo_t.ev[4], 0));
+    HIPCHK(c, hipEventRecord(c->ev_geo_t.ev[0], c->geo_stream));
     HIPCHK(c, hipMemcpyAsync(sv, verts, per * sizeof(float), kind, c->geo_stream));
     if (normals)
     {
@@ -133,7 +129,7 @@ static int update_geometry(ptk_ctx* c, int32_t first, int32_t count, const float
     launch_geometry_bounds(c->d_verts_res, sv, first, count, c->num_tris, c->d_geo_red, c->geo_stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->h_geo_red, c->d_geo_red, GEO_RED_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->geo_stream));
-    HIPCHK(c, hipEventRecord(c->ev_geo_t[1], c->geo_stream));
+    HIPCHK(c, hipEventRecord(c->ev_geo_t.ev[1], c->geo_stream));
     // the one host wait of an update: for the staging stream, which stands behind the PREVIOUS update only - renders queued
     // since then are not waited for; the caller's arrays are free again from here on
     HIPCHK(c, hipStreamSynchronize(c->geo_stream));
@@ -144,18 +140,18 @@ static int update_geometry(ptk_ctx* c, int32_t first, int32_t count, const float
     // 2. rewrite on the context's stream: behind every render already queued - their accumulate kernels are on this stream,
     // each behind its trace kernel on the internal streams, so no trace still reads the old records - and ahead of every
     // later one (inputs_dirty re-anchors the trace streams behind these kernels)
-    HIPCHK(c, hipEventRecord(c->ev_geo_t[2], c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_geo_t.ev[2], c->stream));
     launch_repack_geometry(sv, sn, st, first, count, c->d_verts_res, c->d_tri_pos, c->d_tris, c->d_flat_tris, c->d_shade, c->stream);
     launch_repack_lights(c->d_verts_res, first, count, c->d_lights, c->num_lights, c->stream);
     if (c->d_flat_tris && sn) launch_flat_frames(c->d_shade, c->d_flat_tris, first, count, c->stream);     // (vertices only: the normals stay)
     if (c->d_flat_tris) launch_flat_classes(c->d_flat_tris, c->num_tris, c->opt_flat_zero_classes, c->opt_flat_rect_pairs, c->stream);   // the records' new zero words and pairs
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_geo_t[3], c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_geo_t.ev[3], c->stream));
     c->bvh_pad = 1e-5f * std::max(vmax, 1.0f);
     queue_refit(c, c->bvh_pad, 1, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_geo_t[4], c->stream));
-    c->geo_done_recorded = true;
+    HIPCHK(c, hipEventRecord(c->ev_geo_t.ev[4], c->stream));
+    c->ev_geo_t.done();
 
     c->scene_bound = 3.1f * (1.01f * vmax + 1e-3f);
     for (int a = 0; a < 3; a++) { c->scene_lo[a] = geo_dec(~red[a]); c->scene_hi[a] = geo_dec(red[3 + a]); }
@@ -211,13 +207,12 @@ int ptk_geometry_info(ptk_ctx* c, uint32_t* updates, int* refitted, double* sah_
 int ptk_geometry_timing(ptk_ctx* c, float* ms3)
 {
     if (!c || !ms3) return PTK_ERR_BAD_ARG;
-    if (!c->geo_done_recorded) return fail(c, PTK_ERR_BAD_ARG, "no geometry update yet");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventSynchronize(c->ev_geo_t[4]));
-    HIPCHK(c, hipEventElapsedTime(&ms3[0], c->ev_geo_t[0], c->ev_geo_t[1]));
-    HIPCHK(c, hipEventElapsedTime(&ms3[1], c->ev_geo_t[2], c->ev_geo_t[3]));
-    HIPCHK(c, hipEventElapsedTime(&ms3[2], c->ev_geo_t[3], c->ev_geo_t[4]));
-    return PTK_OK;
+    if (!c->ev_geo_t.timed) return fail(c, PTK_ERR_BAD_ARG, "no geometry update yet");
+    // (the last interval first: its end is the newest event, behind which the others have happened)
+    int rc = c->ev_geo_t.elapsed(c, 3, 4, &ms3[2]);
+    if (rc == PTK_OK) rc = c->ev_geo_t.elapsed(c, 0, 1, &ms3[0]);
+    if (rc == PTK_OK) rc = c->ev_geo_t.elapsed(c, 2, 3, &ms3[1]);
+    return rc;
 }
 
 }  // extern "C"

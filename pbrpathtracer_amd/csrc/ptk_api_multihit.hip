@@ -9,26 +9,19 @@
 
 using namespace ptk;
 
-// ptk_crossings_rays' argument checks and max_hits; PTK_OK with *nothing = true: the call is legal and has nothing to do.
+// The shared argument checks (check_query_args) and max_hits
 static int check_multihit_args(ptk_ctx* c, int32_t num, const void* origins, const void* dirs, int32_t max_hits, bool have_out, bool* nothing)
 {
-    *nothing = false;
-    if (!c) return PTK_ERR_BAD_ARG;
-    if (num < 0) return fail(c, PTK_ERR_BAD_ARG, "ptk_multihit_rays: negative count");
-    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
-    if (!have_out) return fail(c, PTK_ERR_BAD_ARG, "ptk_multihit_rays: no output array");
-    if (max_hits < 1 || max_hits > PTK_MULTIHIT_MAX) return fail(c, PTK_ERR_BAD_ARG, "ptk_multihit_rays: max_hits must be in 1 .. " + std::to_string(PTK_MULTIHIT_MAX));
-    if (num > 0 && (!origins || !dirs)) return fail(c, PTK_ERR_BAD_ARG, "ptk_multihit_rays: null array");
-    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
-    *nothing = num == 0;
-    return PTK_OK;
+    const std::string range = "max_hits must be in 1 .. " + std::to_string(PTK_MULTIHIT_MAX);
+    return check_query_args(c, "ptk_multihit_rays", "count", num, origins, dirs, have_out, nothing,
+                            (max_hits < 1 || max_hits > PTK_MULTIHIT_MAX) ? range.c_str() : nullptr);
 }
 
 // The call proper, on the context's stream, every pointer into this GPU's memory.  The kernel between the two events; a scene
 // without triangles has no tree to walk and gets its unused-slot values from fills.
 static int multihit_on_stream(ptk_ctx* c, MultihitParams& h)
 {
-    c->multihit_timed = false;
+    c->ev_multihit.begin();
     const size_t n = (size_t)h.num, nk = n * (size_t)h.max_hits;
     if (c->num_nodes == 0)
     {
@@ -40,12 +33,11 @@ static int multihit_on_stream(ptk_ctx* c, MultihitParams& h)
         return PTK_OK;
     }
     h.nodes = c->d_nodes; h.tris = c->d_tris; h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound; h.tri_thr = c->opt_tri_thr;
-    if (const int rc = ensure_events(c, c->ev_multihit); rc != PTK_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_multihit[0], c->stream));
+    if (const int rc = c->ev_multihit.mark(c, 0, c->stream); rc != PTK_OK) return rc;
     launch_multihit(h, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_multihit[1], c->stream));
-    c->multihit_timed = true;
+    if (const int rc = c->ev_multihit.mark(c, 1, c->stream); rc != PTK_OK) return rc;
+    c->ev_multihit.done();
     return PTK_OK;
 }
 
@@ -77,26 +69,16 @@ int ptk_multihit_rays(ptk_ctx* c, int32_t num_rays, const float* origins, const 
     const auto d_count = s.out(count, n), d_tri = s.out(tri, nk);
     const auto d_t = s.out(t, nk), d_bary = s.out(bary, 2 * nk);
     const auto d_side = s.out(side, nk);
-    return s.run([&] {
-        MultihitParams h = {};
-        h.origins = d_origins; h.dirs = d_dirs; h.tmax = d_tmax; h.num = num_rays; h.max_hits = max_hits;
-        h.count = d_count; h.tri = d_tri; h.t = d_t; h.bary = d_bary; h.side = d_side;
-        return multihit_on_stream(c, h);
-    });
+    return s.run([&] { return ptk_multihit_rays_device(c, num_rays, d_origins, d_dirs, d_tmax, max_hits, d_count, d_tri, d_t, d_bary, d_side); });
 }
 
 int ptk_last_multihit_ms(ptk_ctx* c, float* ms)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float t = 0.0f;
-    if (c->multihit_timed)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(c->ev_multihit[1]));
-        HIPCHK(c, hipEventElapsedTime(&t, c->ev_multihit[0], c->ev_multihit[1]));
-    }
+    const int rc = c->ev_multihit.elapsed(c, 0, 1, &t);
     if (ms) *ms = t;
-    return PTK_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -41,41 +41,40 @@ static int probes_on_stream(ptk_ctx* c, int32_t num_probes, const float* d_posit
                             uint32_t first_sample, uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float weight, float* d_radiance,
                             float* d_coefs)
 {
-    c->probes_timed = false; c->probe_blocks_timed = 0;
+    c->ev_probes.begin(); c->ev_probe_blocks.begin();
     const size_t D = (size_t)num_dirs, rays = (size_t)num_probes * D;
     // a block holds at most max(D, pass_bytes / 256) rays, in whole probes: the rays are never all materialised
     const size_t block_probes = std::min<size_t>((size_t)num_probes, std::max<size_t>(1, c->opt_pass_bytes / 256 / D));
-    int rc = ensure_events(c, c->ev_probes);
-    if (rc == PTK_OK) rc = grow(c, c->d_probe_basis, c->probe_basis_dirs, D, PTK_PROBE_COEFS * sizeof(float));
-    if (rc == PTK_OK) rc = grow(c, c->d_probe_rays, c->probe_rays_cap, block_probes * D, 6 * sizeof(float));
-    if (rc == PTK_OK && !d_radiance) rc = grow(c, c->d_probe_table, c->probe_table_rays, rays, 3 * sizeof(float));
+    int rc = c->d_probe_basis.grow(c, D, PTK_PROBE_COEFS * sizeof(float));
+    if (rc == PTK_OK) rc = c->d_probe_rays.grow(c, block_probes * D, 6 * sizeof(float));
+    if (rc == PTK_OK && !d_radiance) rc = c->d_probe_table.grow(c, rays, 3 * sizeof(float));
     if (rc != PTK_OK) return rc;
     float* const table = d_radiance ? d_radiance : c->d_probe_table;
-    float* const origins = c->d_probe_rays, * const ray_dirs = origins + c->probe_rays_cap * 3;
-    HIPCHK(c, hipEventRecord(c->ev_probes[0], c->stream));
+    float* const origins = c->d_probe_rays, * const ray_dirs = origins + c->d_probe_rays.cap * 3;
+    if (const int rm = c->ev_probes.mark(c, 0, c->stream); rm != PTK_OK) return rm;
     launch_probe_basis(d_dirs, num_dirs, c->d_probe_basis, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_probes[1], c->stream));
+    if (const int rm = c->ev_probes.mark(c, 1, c->stream); rm != PTK_OK) return rm;
     for (size_t p0 = 0; p0 < (size_t)num_probes; p0 += block_probes)
     {
         const size_t np = std::min(block_probes, (size_t)num_probes - p0), ray0 = p0 * D;
-        const int bi = c->probe_blocks_timed < ptk_ctx::kMaxTimedPasses ? c->probe_blocks_timed : -1;
-        if (rc = ensure_pass_events(c, c->ev_probe_blocks, bi); rc != PTK_OK) return rc;
-        if (bi >= 0) HIPCHK(c, hipEventRecord(c->ev_probe_blocks[bi * 3], c->stream));
+        const int bi = c->ev_probe_blocks.passes < ptk_ctx::kMaxTimedPasses ? c->ev_probe_blocks.passes : -1;
+        if (rc = c->ev_probe_blocks.reserve(c, bi + 1); rc != PTK_OK) return rc;
+        if (bi >= 0) HIPCHK(c, hipEventRecord(c->ev_probe_blocks.at(bi, 0), c->stream));
         launch_probe_rays(d_positions + p0 * 3, d_dirs, (int)np, num_dirs, origins, ray_dirs, c->stream);
         HIPCHK(c, hipGetLastError());
-        if (bi >= 0) HIPCHK(c, hipEventRecord(c->ev_probe_blocks[bi * 3 + 1], c->stream));
+        if (bi >= 0) HIPCHK(c, hipEventRecord(c->ev_probe_blocks.at(bi, 1), c->stream));
         // (contiguous keys: plain rays_kernel)
         rc = trace_rays_on_stream(c, (int32_t)(np * D), origins, ray_dirs, max_depth, first_sample, spp, seed, key_base + (uint32_t)ray0,
                                   (flags & PTK_PROBES_ACCUMULATE) ? PTK_RAYS_ACCUMULATE : 0u, table + ray0 * 3);
         if (rc != PTK_OK) return rc;
-        if (bi >= 0) { HIPCHK(c, hipEventRecord(c->ev_probe_blocks[bi * 3 + 2], c->stream)); c->probe_blocks_timed = bi + 1; }
+        if (bi >= 0) { HIPCHK(c, hipEventRecord(c->ev_probe_blocks.at(bi, 2), c->stream)); c->ev_probe_blocks.passes = bi + 1; }
     }
-    HIPCHK(c, hipEventRecord(c->ev_probes[2], c->stream));
+    if (const int rm = c->ev_probes.mark(c, 2, c->stream); rm != PTK_OK) return rm;
     launch_probe_project(table, c->d_probe_basis, num_probes, num_dirs, weight, d_coefs, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_probes[3], c->stream));
-    c->probes_timed = true;
+    if (const int rm = c->ev_probes.mark(c, 3, c->stream); rm != PTK_OK) return rm;
+    c->ev_probes.done();
     return PTK_OK;
 }
 
@@ -162,23 +161,14 @@ int ptk_last_probes_ms(ptk_ctx* c, float* raygen_ms, float* trace_ms, float* pro
     if (!c) return PTK_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     float gen = 0.0f, trace = 0.0f, project = 0.0f;
-    if (c->probes_timed)
-    {
-        HIPCHK(c, hipEventSynchronize(c->ev_probes[3]));
-        HIPCHK(c, hipEventElapsedTime(&gen, c->ev_probes[0], c->ev_probes[1]));         // (the basis table counts as ray generation)
-        HIPCHK(c, hipEventElapsedTime(&project, c->ev_probes[2], c->ev_probes[3]));
-        for (int i = 0; i < c->probe_blocks_timed; i++)
-        {
-            float a = 0.0f, b = 0.0f;
-            HIPCHK(c, hipEventElapsedTime(&a, c->ev_probe_blocks[i * 3], c->ev_probe_blocks[i * 3 + 1]));
-            HIPCHK(c, hipEventElapsedTime(&b, c->ev_probe_blocks[i * 3 + 1], c->ev_probe_blocks[i * 3 + 2]));
-            gen += a; trace += b;
-        }
-    }
+    int rc = c->ev_probes.elapsed(c, 2, 3, &project);
+    if (rc == PTK_OK) rc = c->ev_probes.elapsed(c, 0, 1, &gen);                        // (the basis table counts as ray generation)
+    const int blocks = c->ev_probes.timed ? c->ev_probe_blocks.passes : 0;
+    for (int i = 0; i < blocks && rc == PTK_OK; i++) rc = c->ev_probe_blocks.add(c, i, &gen, &trace);
     if (raygen_ms) *raygen_ms = gen;
     if (trace_ms) *trace_ms = trace;
     if (project_ms) *project_ms = project;
-    return PTK_OK;
+    return rc;
 }
 
 // ---- probe visibility (ptk.h) ------------------------------------------------------------------------------------
@@ -209,24 +199,23 @@ static int check_visibility_args(ptk_ctx* c, int32_t num_probes, const float* po
 static int visibility_on_stream(ptk_ctx* c, int32_t num_probes, const float* d_positions, int32_t num_dirs, const float* d_dirs, int res, float max_dist,
                                 uint32_t sample, uint64_t seed, uint32_t key_base, float* d_depth, float* d_moments)
 {
-    c->probe_vis_timed = false; c->probe_vis_blocks_timed = 0;
+    c->ev_probe_vis.begin(); c->ev_probe_vis_blocks.begin();
     const size_t D = (size_t)num_dirs, rays = (size_t)num_probes * D;
     const size_t block_probes = std::min<size_t>((size_t)num_probes, std::max<size_t>(1, c->opt_pass_bytes / 256 / D));
-    int rc = ensure_events(c, c->ev_probe_vis);
-    if (rc == PTK_OK) rc = grow(c, c->d_probe_rays, c->probe_rays_cap, block_probes * D, 6 * sizeof(float));
-    if (rc == PTK_OK && !d_depth) rc = grow(c, c->d_probe_depth, c->probe_depth_rays, rays, sizeof(float));
+    int rc = c->d_probe_rays.grow(c, block_probes * D, 6 * sizeof(float));
+    if (rc == PTK_OK && !d_depth) rc = c->d_probe_depth.grow(c, rays, sizeof(float));
     if (rc != PTK_OK) return rc;
     float* const table = d_depth ? d_depth : c->d_probe_depth;
-    float* const origins = c->d_probe_rays, * const ray_dirs = origins + c->probe_rays_cap * 3;
+    float* const origins = c->d_probe_rays, * const ray_dirs = origins + c->d_probe_rays.cap * 3;
     for (size_t p0 = 0; p0 < (size_t)num_probes; p0 += block_probes)
     {
         const size_t np = std::min(block_probes, (size_t)num_probes - p0), ray0 = p0 * D;
-        const int bi = c->probe_vis_blocks_timed < ptk_ctx::kMaxTimedPasses ? c->probe_vis_blocks_timed : -1;
-        if (rc = ensure_pass_events(c, c->ev_probe_vis_blocks, bi); rc != PTK_OK) return rc;
-        if (bi >= 0) HIPCHK(c, hipEventRecord(c->ev_probe_vis_blocks[bi * 3], c->stream));
+        const int bi = c->ev_probe_vis_blocks.passes < ptk_ctx::kMaxTimedPasses ? c->ev_probe_vis_blocks.passes : -1;
+        if (rc = c->ev_probe_vis_blocks.reserve(c, bi + 1); rc != PTK_OK) return rc;
+        if (bi >= 0) HIPCHK(c, hipEventRecord(c->ev_probe_vis_blocks.at(bi, 0), c->stream));
         if (c->num_nodes > 0) launch_probe_rays(d_positions + p0 * 3, d_dirs, (int)np, num_dirs, origins, ray_dirs, c->stream);
         HIPCHK(c, hipGetLastError());
-        if (bi >= 0) HIPCHK(c, hipEventRecord(c->ev_probe_vis_blocks[bi * 3 + 1], c->stream));
+        if (bi >= 0) HIPCHK(c, hipEventRecord(c->ev_probe_vis_blocks.at(bi, 1), c->stream));
         if (c->num_nodes > 0)
         {
             HitsParams h = {};
@@ -238,13 +227,13 @@ static int visibility_on_stream(ptk_ctx* c, int32_t num_probes, const float* d_p
             HIPCHK(c, hipGetLastError());
         }
         else HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(table + ray0), 0x7f800000, np * D, c->stream));
-        if (bi >= 0) { HIPCHK(c, hipEventRecord(c->ev_probe_vis_blocks[bi * 3 + 2], c->stream)); c->probe_vis_blocks_timed = bi + 1; }
+        if (bi >= 0) { HIPCHK(c, hipEventRecord(c->ev_probe_vis_blocks.at(bi, 2), c->stream)); c->ev_probe_vis_blocks.passes = bi + 1; }
     }
-    HIPCHK(c, hipEventRecord(c->ev_probe_vis[0], c->stream));
+    if (const int rm = c->ev_probe_vis.mark(c, 0, c->stream); rm != PTK_OK) return rm;
     launch_probe_moments(table, d_dirs, num_probes, num_dirs, res, max_dist, d_moments, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_probe_vis[1], c->stream));
-    c->probe_vis_timed = true;
+    if (const int rm = c->ev_probe_vis.mark(c, 1, c->stream); rm != PTK_OK) return rm;
+    c->ev_probe_vis.done();
     return PTK_OK;
 }
 
@@ -321,22 +310,13 @@ int ptk_last_probe_visibility_ms(ptk_ctx* c, float* raygen_ms, float* hits_ms, f
     if (!c) return PTK_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     float gen = 0.0f, hits = 0.0f, moments = 0.0f;
-    if (c->probe_vis_timed)
-    {
-        HIPCHK(c, hipEventSynchronize(c->ev_probe_vis[1]));
-        HIPCHK(c, hipEventElapsedTime(&moments, c->ev_probe_vis[0], c->ev_probe_vis[1]));
-        for (int i = 0; i < c->probe_vis_blocks_timed; i++)
-        {
-            float a = 0.0f, b = 0.0f;
-            HIPCHK(c, hipEventElapsedTime(&a, c->ev_probe_vis_blocks[i * 3], c->ev_probe_vis_blocks[i * 3 + 1]));
-            HIPCHK(c, hipEventElapsedTime(&b, c->ev_probe_vis_blocks[i * 3 + 1], c->ev_probe_vis_blocks[i * 3 + 2]));
-            gen += a; hits += b;
-        }
-    }
+    int rc = c->ev_probe_vis.elapsed(c, 0, 1, &moments);
+    const int blocks = c->ev_probe_vis.timed ? c->ev_probe_vis_blocks.passes : 0;
+    for (int i = 0; i < blocks && rc == PTK_OK; i++) rc = c->ev_probe_vis_blocks.add(c, i, &gen, &hits);
     if (raygen_ms) *raygen_ms = gen;
     if (hits_ms) *hits_ms = hits;
     if (moments_ms) *moments_ms = moments;
-    return PTK_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -42,8 +42,8 @@ using RaysFold = std::function<void(size_t ray0, int rays, int chunk, int num_ch
 static int trace_rays_passes(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,
                              uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, const uint32_t* d_keys, const RaysFold& fold)
 {
-    c->rays_passes = 0;
-    if (!c->d_rays_block) HIPCHK(c, hipMalloc(&c->d_rays_block, sizeof(RaysBlock)));
+    c->ev_rays.passes = 0;
+    if (!c->d_rays_block) HIPCHK(c, hipMalloc(&c->d_rays_block.p, sizeof(RaysBlock)));
     RenderParams p;
     fill_params(c, p, first_sample, spp, seed);
     p.max_depth = max_depth;
@@ -56,9 +56,9 @@ static int trace_rays_passes(ptk_ctx* c, int32_t num_rays, const float* d_origin
     {
         const size_t want = std::min(budget, groups * group_bytes * ((size_t)spp + chunk_opt));
         size_t free_b = 0, total_b = 0;
-        if (want > c->rays_samples_bytes)        // (only a call that has to allocate asks the driver)
+        if (want > c->d_rays_samples.cap)        // (only a call that has to allocate asks the driver)
         {
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, std::max(std::max(free_b / 2, c->rays_samples_bytes), group_bytes));
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, std::max(std::max(free_b / 2, c->d_rays_samples.cap), group_bytes));
             else (void)hipGetLastError();
         }
     }
@@ -72,11 +72,10 @@ static int trace_rays_passes(ptk_ctx* c, int32_t num_rays, const float* d_origin
         // (the first pass's sample slots: its chunks, the last of which may be partly used)
         const uint32_t n0 = std::min(spp, max_pass), slots = n0 <= chunk_opt ? n0 : (n0 + chunk_opt - 1) / chunk_opt * chunk_opt;
         const size_t need = block_groups * group_bytes * slots;
-        if (need <= c->rays_samples_bytes) break;
+        if (need <= c->d_rays_samples.cap) break;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        dfree(c->d_rays_samples); c->rays_samples_bytes = 0;
-        if (hipMalloc(&c->d_rays_samples, need) == hipSuccess) { c->rays_samples_bytes = need; break; }
-        (void)hipGetLastError(); c->d_rays_samples = nullptr;
+        if (c->d_rays_samples.try_alloc(need, need) == hipSuccess) break;
+        (void)hipGetLastError();
         if (budget <= group_bytes) return fail(c, PTK_ERR_HIP, "hipMalloc: no memory for the sample buffer of even one sample of 64 rays");
         budget = std::max(group_bytes, budget / 2);
     }
@@ -95,15 +94,15 @@ static int trace_rays_passes(ptk_ctx* c, int32_t num_rays, const float* d_origin
             p.first_sample = first_sample + done; p.spp = n;
             p.chunk = (int)std::min(n, chunk_opt); p.num_chunks = (int)((n + p.chunk - 1) / p.chunk);
             p.num_items = (int)(nb * (size_t)p.num_chunks);
-            const int pi = c->rays_passes < ptk_ctx::kMaxTimedPasses ? c->rays_passes : -1;
-            if (const int rc = ensure_pass_events(c, c->ev_rays, pi); rc != PTK_OK) return rc;
-            if (pi >= 0) HIPCHK(c, hipEventRecord(c->ev_rays[pi * 3], c->stream));
+            const int pi = c->ev_rays.passes < ptk_ctx::kMaxTimedPasses ? c->ev_rays.passes : -1;
+            if (const int rc = c->ev_rays.reserve(c, pi + 1); rc != PTK_OK) return rc;
+            if (pi >= 0) HIPCHK(c, hipEventRecord(c->ev_rays.at(pi, 0), c->stream));
             launch_rays(p, r, c->d_rays_block, c->resident_waves, c->stream);
             HIPCHK(c, hipGetLastError());
-            if (pi >= 0) HIPCHK(c, hipEventRecord(c->ev_rays[pi * 3 + 1], c->stream));
+            if (pi >= 0) HIPCHK(c, hipEventRecord(c->ev_rays.at(pi, 1), c->stream));
             fold(ray0, (int)nr, p.chunk, p.num_chunks, n, done);
             HIPCHK(c, hipGetLastError());
-            if (pi >= 0) { HIPCHK(c, hipEventRecord(c->ev_rays[pi * 3 + 2], c->stream)); c->rays_passes = pi + 1; }
+            if (pi >= 0) { HIPCHK(c, hipEventRecord(c->ev_rays.at(pi, 2), c->stream)); c->ev_rays.passes = pi + 1; }
             done += n;
         }
     }
@@ -113,7 +112,7 @@ static int trace_rays_passes(ptk_ctx* c, int32_t num_rays, const float* d_origin
 int ptk::trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,
                               uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, const uint32_t* d_keys)
 {
-    c->rays_passes = 0;
+    c->ev_rays.passes = 0;
     // (a scene without triangles has no tree to walk: every path is black)
     if (spp == 0 || c->num_nodes == 0)
     {
@@ -136,9 +135,27 @@ int ptk::check_adaptive_args(ptk_ctx* c, const char* who, float threshold, uint3
     return PTK_OK;
 }
 
+// The argument checks the ray, point and surface query entries share.  `count_word` names the count in the entry's error text ("ray
+// count", "point count", "count"); `a`, `b`: the arrays a count > 0 needs (b may be the same as a); `also`: a complaint about an
+// argument of the entry's own, reported in this place.  PTK_OK with *nothing = true: the call is legal and has nothing to do.
+int ptk::check_query_args(ptk_ctx* c, const char* who, const char* count_word, int32_t num, const void* a, const void* b, bool have_out, bool* nothing,
+                          const char* also)
+{
+    *nothing = false;
+    if (!c) return PTK_ERR_BAD_ARG;
+    if (num < 0) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": negative " + count_word);
+    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
+    if (!have_out) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": no output array");
+    if (also) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": " + also);
+    if (num > 0 && (!a || !b)) return fail(c, PTK_ERR_BAD_ARG, std::string(who) + ": null array");
+    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
+    *nothing = num == 0;
+    return PTK_OK;
+}
+
 RaysAdaptiveBuffers ptk::radapt_buffers(ptk_ctx* c)
 {
-    const size_t cap = c->radapt_rays;
+    const size_t cap = c->d_radapt.cap;
     RaysAdaptiveBuffers a;
     a.origins = c->d_radapt; a.dirs = a.origins + cap * 3; a.s2 = a.dirs + cap * 3;
     a.keys = (uint32_t*)(a.s2 + cap * 3); a.src = a.keys + cap; a.list = a.src + cap; a.keep = a.list + cap; a.counts = a.keep + cap;
@@ -155,10 +172,9 @@ int ptk::rays_adaptive_on_stream(ptk_ctx* c, uint32_t n, const float* d_origins,
 {
     const auto t0 = std::chrono::steady_clock::now();
     c->radapt_ms[0] = c->radapt_ms[1] = c->radapt_ms[2] = 0.0f;
-    int rc = grow(c, c->d_radapt, c->radapt_rays, n, 14 * sizeof(float), (((size_t)n + 255) / 256 + 1) * sizeof(float));
-    if (rc == PTK_OK) rc = ensure_events(c, c->ev_radapt);
+    int rc = c->d_radapt.grow(c, n, 14 * sizeof(float), (((size_t)n + 255) / 256 + 1) * sizeof(float));
     if (rc != PTK_OK) return rc;
-    if (!c->h_radapt_total) HIPCHK(c, hipHostMalloc((void**)&c->h_radapt_total, sizeof(uint32_t), hipHostMallocDefault));
+    HIPCHK(c, c->h_radapt_total.alloc(1));
     const RaysAdaptiveBuffers a = radapt_buffers(c);
     if (!s2) s2 = a.s2;
     if (!counts) counts = a.counts;
@@ -166,7 +182,7 @@ int ptk::rays_adaptive_on_stream(ptk_ctx* c, uint32_t n, const float* d_origins,
     if (texel)
     {
         const size_t texels = (size_t)width * height;
-        if (rc = grow(c, c->d_radapt_need, c->radapt_need_texels, texels, 1); rc != PTK_OK) return rc;
+        if (rc = c->d_radapt_need.grow(c, texels, 1); rc != PTK_OK) return rc;
         need = c->d_radapt_need;
         HIPCHK(c, hipMemsetAsync(need, 0, texels, c->stream));
     }
@@ -193,7 +209,8 @@ int ptk::rays_adaptive_on_stream(ptk_ctx* c, uint32_t n, const float* d_origins,
         {
             // no test before min_spp samples: the rounds up to there are traced as one
             const uint32_t take = done == 0 ? min_spp : step;
-            HIPCHK(c, hipEventRecord(c->ev_radapt[0], c->stream));
+            c->ev_radapt.begin();
+            if (rc = c->ev_radapt.mark(c, 0, c->stream); rc != PTK_OK) return rc;
             launch_rays_gather(list, active, d_origins, d_dirs, d_keys, key_base, a.origins, a.dirs, a.keys, a.src, c->stream);
             HIPCHK(c, hipGetLastError());
             rc = trace_rays_passes(c, (int32_t)active, a.origins, a.dirs, max_depth, done, take, seed, 0u, rays_flags, a.keys,
@@ -209,18 +226,14 @@ int ptk::rays_adaptive_on_stream(ptk_ctx* c, uint32_t n, const float* d_origins,
             launch_rays_compact(a.src, a.keep, active, a.block_counts, a.total, a.list, c->stream);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipMemcpyAsync(c->h_radapt_total, a.total, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipEventRecord(c->ev_radapt[1], c->stream));
+            if (rc = c->ev_radapt.mark(c, 1, c->stream); rc != PTK_OK) return rc;
+            c->ev_radapt.done();
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (*c->h_radapt_total > active) return fail(c, PTK_ERR_HIP, "adaptive rays: the active list grew");
-            float all = 0.0f;
-            HIPCHK(c, hipEventElapsedTime(&all, c->ev_radapt[0], c->ev_radapt[1]));
-            float trace = 0.0f;
-            for (int i = 0; i < c->rays_passes; i++)
-            {
-                float t = 0.0f;
-                HIPCHK(c, hipEventElapsedTime(&t, c->ev_rays[i * 3], c->ev_rays[i * 3 + 1]));
-                trace += t;
-            }
+            float all = 0.0f, trace = 0.0f;
+            rc = c->ev_radapt.elapsed(c, 0, 1, &all);
+            for (int i = 0; i < c->ev_rays.passes && rc == PTK_OK; i++) rc = c->ev_rays.add(c, i, &trace, nullptr);
+            if (rc != PTK_OK) return rc;
             c->radapt_ms[1] += trace; c->radapt_ms[2] += all - trace;
             active = *c->h_radapt_total;
             list = a.list;
@@ -266,32 +279,18 @@ int ptk_last_rays_ms(ptk_ctx* c, float* trace_ms, float* fold_ms)
     if (!c) return PTK_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     float t = 0.0f, f = 0.0f;
-    for (int i = 0; i < c->rays_passes; i++)
-    {
-        float a = 0.0f, b = 0.0f;
-        HIPCHK(c, hipEventSynchronize(c->ev_rays[i * 3 + 2]));
-        HIPCHK(c, hipEventElapsedTime(&a, c->ev_rays[i * 3], c->ev_rays[i * 3 + 1]));
-        HIPCHK(c, hipEventElapsedTime(&b, c->ev_rays[i * 3 + 1], c->ev_rays[i * 3 + 2]));
-        t += a; f += b;
-    }
+    for (int i = 0; i < c->ev_rays.passes; i++)
+        if (const int rc = c->ev_rays.add(c, i, &t, &f); rc != PTK_OK) return rc;
     if (trace_ms) *trace_ms = t;
     if (fold_ms) *fold_ms = f;
     return PTK_OK;
 }
 
 // ---- closest-hit and occlusion queries for caller-supplied rays (ptk.h) --------------------------------------------------------
-// The argument checks the entries share; PTK_OK with *nothing = true: the call is legal and has nothing to do.
+// The argument checks the entries share: check_query_args (above) with the word of these entries' texts.
 static int check_hits_args(ptk_ctx* c, const char* who, int32_t num_rays, const float* origins, const float* dirs, bool have_out, bool* nothing)
 {
-    *nothing = false;
-    if (!c) return PTK_ERR_BAD_ARG;
-    if (num_rays < 0) return fail(c, PTK_ERR_BAD_ARG, (std::string(who) + ": negative ray count").c_str());
-    if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
-    if (!have_out) return fail(c, PTK_ERR_BAD_ARG, (std::string(who) + ": no output array").c_str());
-    if (num_rays > 0 && (!origins || !dirs)) return fail(c, PTK_ERR_BAD_ARG, (std::string(who) + ": null array").c_str());
-    if (c->bvh_stack > PTK_MAX_BVH_DEPTH) return fail(c, PTK_ERR_LIMIT, "BVH needs more entries than the LDS traversal stack holds");
-    *nothing = num_rays == 0;
-    return PTK_OK;
+    return check_query_args(c, who, "ray count", num_rays, origins, dirs, have_out, nothing);
 }
 
 // The call proper, on the context's stream, every pointer into this GPU's memory: h holds the rays and the outputs, the scene
@@ -299,7 +298,7 @@ static int check_hits_args(ptk_ctx* c, const char* who, int32_t num_rays, const 
 // from fills.
 static int hits_on_stream(ptk_ctx* c, HitsParams& h, uint32_t sample, uint64_t seed, uint32_t key_base, bool occlusion)
 {
-    c->hits_timed = false;
+    c->ev_hits.begin();
     const size_t n = (size_t)h.num_rays;
     if (c->num_nodes == 0)
     {
@@ -313,12 +312,11 @@ static int hits_on_stream(ptk_ctx* c, HitsParams& h, uint32_t sample, uint64_t s
     h.nodes = c->d_nodes; h.tris = c->d_tris; h.shade = c->d_shade; h.texinfo = c->d_texinfo; h.texels = c->d_texels;
     h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound; h.tri_thr = c->opt_tri_thr;
     h.seed_lo = (uint32_t)seed; h.seed_hi = (uint32_t)(seed >> 32); h.sample = sample; h.key_base = key_base;
-    if (const int rc = ensure_events(c, c->ev_hits); rc != PTK_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_hits[0], c->stream));
+    if (const int rc = c->ev_hits.mark(c, 0, c->stream); rc != PTK_OK) return rc;
     if (occlusion) launch_occluded(h, c->stream); else launch_hits(h, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_hits[1], c->stream));
-    c->hits_timed = true;
+    if (const int rc = c->ev_hits.mark(c, 1, c->stream); rc != PTK_OK) return rc;
+    c->ev_hits.done();
     return PTK_OK;
 }
 
@@ -348,32 +346,20 @@ int ptk_occluded_rays_device(ptk_ctx* c, int32_t num_rays, const float* d_origin
 }
 
 // The host entries: origins, dirs, tmax and the requested outputs staged for the length of the call
-static int hits_staged(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, const float* tmax, uint32_t sample, uint64_t seed,
-                       uint32_t key_base, int32_t* tri, float* t, float* bary, int32_t* material, uint8_t* occluded)
-{
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)num_rays;
-    Stage s(c);
-    const auto d_origins = s.in(origins, 3 * n), d_dirs = s.in(dirs, 3 * n), d_tmax = s.in(tmax, n);
-    const auto d_tri = s.out(tri, n);
-    const auto d_t = s.out(t, n), d_bary = s.out(bary, 2 * n);
-    const auto d_material = s.out(material, n);
-    const auto d_occluded = s.out(occluded, n);
-    return s.run([&] {
-        HitsParams h = {};
-        h.origins = d_origins; h.dirs = d_dirs; h.tmax = d_tmax; h.num_rays = num_rays;
-        h.tri = d_tri; h.t = d_t; h.bary = d_bary; h.material = d_material; h.occluded = d_occluded;
-        return hits_on_stream(c, h, sample, seed, key_base, occluded != nullptr);
-    });
-}
-
 int ptk_intersect_rays(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, uint32_t sample, uint64_t seed, uint32_t key_base,
                        int32_t* tri, float* t, float* bary, int32_t* material)
 {
     bool nothing;
     const int rc = check_hits_args(c, "ptk_intersect_rays", num_rays, origins, dirs, tri || t || bary || material, &nothing);
     if (rc != PTK_OK || nothing) return rc;
-    return hits_staged(c, num_rays, origins, dirs, nullptr, sample, seed, key_base, tri, t, bary, material, nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)num_rays;
+    Stage s(c);
+    const auto d_origins = s.in(origins, 3 * n), d_dirs = s.in(dirs, 3 * n);
+    const auto d_tri = s.out(tri, n);
+    const auto d_t = s.out(t, n), d_bary = s.out(bary, 2 * n);
+    const auto d_material = s.out(material, n);
+    return s.run([&] { return ptk_intersect_rays_device(c, num_rays, d_origins, d_dirs, sample, seed, key_base, d_tri, d_t, d_bary, d_material); });
 }
 
 int ptk_occluded_rays(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, const float* tmax, uint32_t sample, uint64_t seed,
@@ -382,21 +368,21 @@ int ptk_occluded_rays(ptk_ctx* c, int32_t num_rays, const float* origins, const 
     bool nothing;
     const int rc = check_hits_args(c, "ptk_occluded_rays", num_rays, origins, dirs, num_rays == 0 || occluded, &nothing);
     if (rc != PTK_OK || nothing) return rc;
-    return hits_staged(c, num_rays, origins, dirs, tmax, sample, seed, key_base, nullptr, nullptr, nullptr, nullptr, occluded);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)num_rays;
+    Stage s(c);
+    const auto d_origins = s.in(origins, 3 * n), d_dirs = s.in(dirs, 3 * n), d_tmax = s.in(tmax, n);
+    const auto d_occluded = s.out(occluded, n);
+    return s.run([&] { return ptk_occluded_rays_device(c, num_rays, d_origins, d_dirs, d_tmax, sample, seed, key_base, d_occluded); });
 }
 
 int ptk_last_hits_ms(ptk_ctx* c, float* ms)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float t = 0.0f;
-    if (c->hits_timed)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(c->ev_hits[1]));
-        HIPCHK(c, hipEventElapsedTime(&t, c->ev_hits[0], c->ev_hits[1]));
-    }
+    const int rc = c->ev_hits.elapsed(c, 0, 1, &t);
     if (ms) *ms = t;
-    return PTK_OK;
+    return rc;
 }
 
 static int check_rays_adaptive_args(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, float threshold, uint32_t min_spp, uint32_t step,

@@ -16,14 +16,14 @@ namespace ptk {
 
 void surface_release(ptk_ctx* c)
 {
-    dfree(c->d_surf_table); dfree(c->d_surf_weights); dfree(c->d_surf_sums); dfree(c->d_surf_red);
+    c->d_surf_table.release(); c->d_surf_weights.release(); c->d_surf_sums.release(); c->d_surf_red.release();
     c->surf_valid = false; c->surf_info_pending = false;
-    c->surf_table_timed = false; c->surf_sample_timed = false;
+    c->ev_surf_table.begin(); c->ev_surface.begin();
 }
 
 static int ensure_surface_red(ptk_ctx* c)
 {
-    if (!c->d_surf_red) HIPCHK(c, hipMalloc(&c->d_surf_red, SURF_RED_WORDS * sizeof(uint32_t)));
+    if (!c->d_surf_red) HIPCHK(c, hipMalloc(&c->d_surf_red.p, SURF_RED_WORDS * sizeof(uint32_t)));
     return PTK_OK;
 }
 
@@ -31,15 +31,14 @@ static int ensure_surface_red(ptk_ctx* c)
 // queued so far.  The one host wait is for the eight bytes that decide the exponent.
 int ensure_surface_table(ptk_ctx* c)
 {
-    c->surf_table_timed = false;
+    c->ev_surf_table.begin();
     if (c->surf_valid) return PTK_OK;
     const int n = c->num_tris;
     if (n <= 0 || !c->d_verts_res) return fail(c, PTK_ERR_BAD_ARG, "ptk_sample_surface: the uploaded scene has no triangles: nothing to sample");
-    if (!c->d_surf_table) HIPCHK(c, hipMalloc(&c->d_surf_table, ((size_t)n + SURF_COARSE_WORDS) * sizeof(uint64_t)));
-    if (!c->d_surf_sums) HIPCHK(c, hipMalloc(&c->d_surf_sums, (scan_u64_sums((size_t)n, SURF_SCAN_ITEMS) + 1) * sizeof(uint64_t)));
+    if (!c->d_surf_table) HIPCHK(c, hipMalloc(&c->d_surf_table.p, ((size_t)n + SURF_COARSE_WORDS) * sizeof(uint64_t)));
+    if (!c->d_surf_sums) HIPCHK(c, hipMalloc(&c->d_surf_sums.p, (scan_u64_sums((size_t)n, SURF_SCAN_ITEMS) + 1) * sizeof(uint64_t)));
     if (int rc = ensure_surface_red(c); rc != PTK_OK) return rc;
-    if (int rc = ensure_events(c, c->ev_surface); rc != PTK_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_surface[0], c->stream));
+    if (int rc = c->ev_surf_table.mark(c, 0, c->stream); rc != PTK_OK) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_surf_red, 0, SURF_RED_WORDS * sizeof(uint32_t), c->stream));
     launch_surface_weights(c->d_verts_res, c->d_surf_weights, n, c->d_surf_table, c->d_surf_red, c->stream);
     HIPCHK(c, hipGetLastError());
@@ -55,10 +54,10 @@ int ensure_surface_table(ptk_ctx* c)
     launch_scan_u64(c->d_surf_table, c->d_surf_table, (size_t)n, SURF_SCAN_ITEMS, c->d_surf_sums, c->stream);
     launch_surface_coarse(c->d_surf_table, n, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_surface[1], c->stream));
+    if (int rc = c->ev_surf_table.mark(c, 1, c->stream); rc != PTK_OK) return rc;
     c->surf_exponent = E; c->surf_max = m;
     c->surf_info_pending = true;
-    c->surf_valid = true; c->surf_table_timed = true;
+    c->surf_valid = true; c->ev_surf_table.done();
     return PTK_OK;
 }
 
@@ -72,17 +71,17 @@ static int check_sample_args(ptk_ctx* c, int32_t n)
     return PTK_OK;
 }
 
-// The call proper, on the context's stream, every pointer into this GPU's memory; the kernel between the last two events
+// The call proper, on the context's stream, every pointer into this GPU's memory; the kernel between ev_surface's two events
 static int sample_on_stream(ptk_ctx* c, SurfaceSampleParams& p)
 {
-    c->surf_sample_timed = false;
+    c->ev_surface.begin();
     if (int rc = ensure_surface_table(c); rc != PTK_OK) return rc;
     p.incl = c->d_surf_table; p.verts = c->d_verts_res; p.shade = c->d_shade; p.num_tris = c->num_tris;
-    HIPCHK(c, hipEventRecord(c->ev_surface[2], c->stream));
+    if (int rc = c->ev_surface.mark(c, 0, c->stream); rc != PTK_OK) return rc;
     launch_surface_sample(p, c->opt_surface_variant, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_surface[3], c->stream));
-    c->surf_sample_timed = true;
+    if (int rc = c->ev_surface.mark(c, 1, c->stream); rc != PTK_OK) return rc;
+    c->ev_surface.done();
     return PTK_OK;
 }
 
@@ -100,8 +99,8 @@ static bool bad_weight(float w) { return !(w >= 0.0f) || std::isinf(w); }
 // the validated weights (device memory, or null to clear) become the context's
 static int adopt_weights(ptk_ctx* c, const float* w, hipMemcpyKind kind)
 {
-    if (!w) { if (c->d_surf_weights) { HIPCHK(c, hipStreamSynchronize(c->stream)); dfree(c->d_surf_weights); c->surf_valid = false; } return PTK_OK; }
-    if (!c->d_surf_weights) HIPCHK(c, hipMalloc(&c->d_surf_weights, (size_t)c->num_tris * sizeof(float)));
+    if (!w) { if (c->d_surf_weights) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->d_surf_weights.release(); c->surf_valid = false; } return PTK_OK; }
+    if (!c->d_surf_weights) HIPCHK(c, hipMalloc(&c->d_surf_weights.p, (size_t)c->num_tris * sizeof(float)));
     HIPCHK(c, hipMemcpyAsync(c->d_surf_weights, w, (size_t)c->num_tris * sizeof(float), kind, c->stream));
     if (kind == hipMemcpyHostToDevice) HIPCHK(c, hipStreamSynchronize(c->stream));     // (the caller's array is free again)
     c->surf_valid = false;
@@ -165,10 +164,7 @@ int ptk_sample_surface(ptk_ctx* c, int32_t n, uint32_t key_base, uint32_t sample
     Stage s(c);
     const auto d_tri = s.out(tri, N), d_material = s.out(material, N);
     const auto d_bary = s.out(bary, 2 * N), d_position = s.out(position, 3 * N), d_normal = s.out(normal, 3 * N);
-    return s.run([&] {
-        SurfaceSampleParams p = sample_params(n, key_base, sample, seed, d_tri, d_bary, d_position, d_normal, d_material);
-        return sample_on_stream(c, p);
-    });
+    return s.run([&] { return ptk_sample_surface_device(c, n, key_base, sample, seed, d_tri, d_bary, d_position, d_normal, d_material); });
 }
 
 int ptk_surface_info(ptk_ctx* c, uint64_t* total, int32_t* exponent, int32_t* drawable, float* max_weight)
@@ -176,9 +172,9 @@ int ptk_surface_info(ptk_ctx* c, uint64_t* total, int32_t* exponent, int32_t* dr
     if (!c) return PTK_ERR_BAD_ARG;
     if (!c->have_scene) return fail(c, PTK_ERR_BAD_ARG, "ptk_upload_scene has not been called");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool was_table_timed = c->surf_table_timed;
+    const int was_table_timed = c->ev_surf_table.timed;
     if (int rc = ensure_surface_table(c); rc != PTK_OK) return rc;
-    c->surf_table_timed = c->surf_table_timed || was_table_timed;
+    if (was_table_timed) c->ev_surf_table.done();
     if (c->surf_info_pending)
     {
         uint32_t dr = 0; uint64_t tot = 0;
@@ -198,20 +194,11 @@ int ptk_last_surface_ms(ptk_ctx* c, float* table_ms, float* sample_ms)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float tt = 0.0f, ts = 0.0f;
-    if (c->surf_table_timed || c->surf_sample_timed) HIPCHK(c, hipSetDevice(c->device));
-    if (c->surf_table_timed)
-    {
-        HIPCHK(c, hipEventSynchronize(c->ev_surface[1]));
-        HIPCHK(c, hipEventElapsedTime(&tt, c->ev_surface[0], c->ev_surface[1]));
-    }
-    if (c->surf_sample_timed)
-    {
-        HIPCHK(c, hipEventSynchronize(c->ev_surface[3]));
-        HIPCHK(c, hipEventElapsedTime(&ts, c->ev_surface[2], c->ev_surface[3]));
-    }
+    int rc = c->ev_surf_table.elapsed(c, 0, 1, &tt);
+    if (rc == PTK_OK) rc = c->ev_surface.elapsed(c, 0, 1, &ts);
     if (table_ms) *table_ms = tt;
     if (sample_ms) *sample_ms = ts;
-    return PTK_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -62,22 +62,21 @@ static int planes_on_stream(ptk_ctx* c, int width, int height, const ptk_view& v
                             float* d_out_color, float* d_out_count, const float* d_prev_position = nullptr, const float* d_prev_normal = nullptr,
                             const float* d_albedo = nullptr, const float* d_hist_moments = nullptr, float* d_out_moments = nullptr)
 {
-    c->temporal_timed = false;
-    if (c->motion_timed == 2) c->motion_timed = 1;      // (ev_temporal stops being the kernel behind the last motion_kernel)
+    c->ev_temporal.begin();
+    if (c->ev_motion.timed == 2) c->ev_motion.done(1);      // (ev_temporal stops being the kernel behind the last motion_kernel)
     const size_t px = (size_t)width * height;
-    if (const int rc = grow(c, c->d_temporal_pack, c->temporal_pack_px, px, 3 * sizeof(float4)); rc != PTK_OK) return rc;
+    if (const int rc = c->d_temporal_pack.grow(c, px, 3 * sizeof(float4)); rc != PTK_OK) return rc;
     if (d_out_moments)
-        if (const int rc = grow(c, c->d_temporal_pack_mm, c->temporal_pack_mm_px, px, sizeof(float4)); rc != PTK_OK) return rc;
-    if (const int rc = ensure_events(c, c->ev_temporal); rc != PTK_OK) return rc;
+        if (const int rc = c->d_temporal_pack_mm.grow(c, px, sizeof(float4)); rc != PTK_OK) return rc;
     TemporalImages im = { c->d_temporal_pack, c->d_temporal_pack + px, c->d_temporal_pack + 2 * px };
-    HIPCHK(c, hipEventRecord(c->ev_temporal[0], c->stream));
+    if (const int rm = c->ev_temporal.mark(c, 0, c->stream); rm != PTK_OK) return rm;
     TemporalPackParams pk = {};
     pk.color = d_hist_color; pk.count = d_hist_count; pk.id = d_hist_id; pk.position = d_hist_position; pk.normal = d_hist_normal;
     pk.width = width; pk.height = height;
     launch_temporal_pack(pk, im, c->stream);
     if (d_out_moments) launch_temporal_pack_moments(d_hist_moments, c->d_temporal_pack_mm, width, height, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_temporal[1], c->stream));
+    if (const int rm = c->ev_temporal.mark(c, 1, c->stream); rm != PTK_OK) return rm;
     TemporalParams k = {};
     k.color = d_color; k.count = d_count; k.id = d_id; k.position = d_position; k.normal = d_normal;
     k.hist = im; k.out_color = d_out_color; k.out_count = d_out_count; k.width = width; k.height = height;
@@ -86,8 +85,8 @@ static int planes_on_stream(ptk_ctx* c, int width, int height, const ptk_view& v
     fill_view(k, view, p);
     launch_temporal(k, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_temporal[2], c->stream));
-    c->temporal_timed = true;
+    if (const int rm = c->ev_temporal.mark(c, 2, c->stream); rm != PTK_OK) return rm;
+    c->ev_temporal.done();
     return PTK_OK;
 }
 
@@ -119,13 +118,12 @@ static int check_motion_state(ptk_ctx* c, const char* who, uint32_t need, const 
 // motion vectors
 static int motion_on_stream(ptk_ctx* c, const ptk_view* view)
 {
-    c->motion_timed = 0;
+    c->ev_motion.begin();
     const size_t px = (size_t)c->width * c->height;
-    if (!c->d_motion) HIPCHK(c, hipMalloc(&c->d_motion, px * 8 * sizeof(float)));
-    if (const int rc = ensure_events(c, c->ev_motion); rc != PTK_OK) return rc;
+    if (!c->d_motion) HIPCHK(c, hipMalloc(&c->d_motion.p, px * 8 * sizeof(float)));
     MotionParams m = {};
-    m.tri = (const int32_t*)c->d_feat[PTK_FEAT_TRIANGLE]; m.bary = (const float*)c->d_feat[PTK_FEAT_BARY];
-    m.position = (const float*)c->d_feat[PTK_FEAT_POSITION]; m.normal = (const float*)c->d_feat[PTK_FEAT_NORMAL];
+    m.tri = (const int32_t*)c->d_feat[PTK_FEAT_TRIANGLE].p; m.bary = (const float*)c->d_feat[PTK_FEAT_BARY].p;
+    m.position = (const float*)c->d_feat[PTK_FEAT_POSITION].p; m.normal = (const float*)c->d_feat[PTK_FEAT_NORMAL].p;
     m.verts = c->d_verts_res; m.prev = c->have_snapshot ? c->d_verts_prev : nullptr; m.num_tris = c->num_tris;
     m.prev_position = motion_prev_position(c, px); m.prev_normal = motion_prev_normal(c, px); m.motion = motion_vectors(c, px);
     m.width = c->width; m.height = c->height;
@@ -137,11 +135,11 @@ static int motion_on_stream(ptk_ctx* c, const ptk_view* view)
         for (int a = 0; a < 3; a++) { m.pos[a] = k.pos[a]; m.right[a] = k.right[a]; m.up[a] = k.up[a]; m.e[a] = k.e[a]; m.nrm[a] = k.nrm[a]; }
         m.num = k.num; m.delta_x = k.delta_x; m.delta_y = k.delta_y;
     }
-    HIPCHK(c, hipEventRecord(c->ev_motion[0], c->stream));
+    if (const int rm = c->ev_motion.mark(c, 0, c->stream); rm != PTK_OK) return rm;
     launch_motion(m, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_motion[1], c->stream));
-    c->motion_timed = 1;
+    if (const int rm = c->ev_motion.mark(c, 1, c->stream); rm != PTK_OK) return rm;
+    c->ev_motion.done();
     c->motion_w = c->width; c->motion_h = c->height;
     return PTK_OK;
 }
@@ -177,13 +175,12 @@ static int temporal_frame(ptk_ctx* c, const char* who, const ptk_temporal_params
     const size_t px = (size_t)c->width * c->height;
     // (ptk_set_frame with another resolution has freed the buffer with the feature planes: there is no history then)
     const bool fresh = !have_temporal(c);
-    if (!c->d_temporal) HIPCHK(c, hipMalloc(&c->d_temporal, px * 7 * sizeof(float4)));
-    if (moments && !c->d_temporal_mm) HIPCHK(c, hipMalloc(&c->d_temporal_mm, px * kTemporalMomentsBytes));
+    if (!c->d_temporal) HIPCHK(c, hipMalloc(&c->d_temporal.p, px * 7 * sizeof(float4)));
+    if (moments && !c->d_temporal_mm) HIPCHK(c, hipMalloc(&c->d_temporal_mm.p, px * kTemporalMomentsBytes));
     ptk_view now;
     if (const int rc = ptk_get_view(c, &now); rc != PTK_OK) return rc;
-    c->temporal_timed = false;
-    if (c->motion_timed == 2) c->motion_timed = 1;
-    if (const int rc = ensure_events(c, c->ev_temporal); rc != PTK_OK) return rc;
+    c->ev_temporal.begin();
+    if (c->ev_motion.timed == 2) c->ev_motion.done(1);
     // (a moments call behind a plain one starts over, colour included: a fresh moment pair behind a long colour count would
     // report no variance at all)
     const bool with_history = !fresh && !(flags & PTK_TEMPORAL_RESET) && (!moments || c->temporal_moments);
@@ -193,26 +190,26 @@ static int temporal_frame(ptk_ctx* c, const char* who, const ptk_temporal_params
     const int next = fresh ? 0 : c->temporal_set ^ 1;
     TemporalParams k = {};
     k.accum = accum_ptr(c); k.counts = adaptive ? c->d_counts : nullptr; k.samples = c->samples.load(); k.rank = c->rank; k.world = c->world;
-    k.id = (const int32_t*)c->d_feat[PTK_FEAT_MATERIAL]; k.position = (const float*)c->d_feat[PTK_FEAT_POSITION];
-    k.normal = (const float*)c->d_feat[PTK_FEAT_NORMAL];
+    k.id = (const int32_t*)c->d_feat[PTK_FEAT_MATERIAL].p; k.position = (const float*)c->d_feat[PTK_FEAT_POSITION].p;
+    k.normal = (const float*)c->d_feat[PTK_FEAT_NORMAL].p;
     if (with_history) k.hist = temporal_set(c, px, c->temporal_set);
     k.next = temporal_set(c, px, next);
     k.out_color = temporal_color(c, px); k.out_count = temporal_count(c, px); k.width = c->width; k.height = c->height;
     if (moving) { k.prev_position = motion_prev_position(c, px); k.prev_normal = motion_prev_normal(c, px); }
     if (moments)
     {
-        k.albedo = (const float*)c->d_feat[PTK_FEAT_ALBEDO]; k.out_moments = temporal_moments_plane(c, px);
+        k.albedo = (const float*)c->d_feat[PTK_FEAT_ALBEDO].p; k.out_moments = temporal_moments_plane(c, px);
         if (with_history) k.hist_mm = temporal_mm(c, px, c->temporal_set);
         k.next_mm = temporal_mm(c, px, next);
     }
     fill_view(k, c->temporal_view, *params);
-    HIPCHK(c, hipEventRecord(c->ev_temporal[0], c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_temporal[1], c->stream));
+    if (const int rm = c->ev_temporal.mark(c, 0, c->stream); rm != PTK_OK) return rm;
+    if (const int rm = c->ev_temporal.mark(c, 1, c->stream); rm != PTK_OK) return rm;
     launch_temporal(k, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_temporal[2], c->stream));
-    c->temporal_timed = true;
-    if (moving) c->motion_timed = 2;
+    if (const int rm = c->ev_temporal.mark(c, 2, c->stream); rm != PTK_OK) return rm;
+    c->ev_temporal.done();
+    if (moving) c->ev_motion.done(2);
     c->temporal_set = next; c->temporal_view = now; c->temporal_w = c->width; c->temporal_h = c->height;
     c->temporal_moments = moments; c->temporal_variance = false;
     return PTK_OK;
@@ -303,15 +300,10 @@ int ptk_last_temporal_ms(ptk_ctx* c, float* pack_ms, float* kernel_ms)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float t[2] = { 0.0f, 0.0f };
-    if (c->temporal_timed)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(c->ev_temporal[2]));
-        for (int k = 0; k < 2; k++) HIPCHK(c, hipEventElapsedTime(&t[k], c->ev_temporal[k], c->ev_temporal[k + 1]));
-    }
+    const int rc = c->ev_temporal.spans(c, 0, 2, t);
     if (pack_ms) *pack_ms = t[0];
     if (kernel_ms) *kernel_ms = t[1];
-    return PTK_OK;
+    return rc;
 }
 
 // ---- moving geometry ------------------------------------------------------------------------------------------------------------
@@ -322,7 +314,7 @@ int ptk_geometry_snapshot(ptk_ctx* c)
     if (c->num_tris <= 0 || !c->d_verts_res) return PTK_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->num_tris * 9 * sizeof(float);
-    if (!c->d_verts_prev) HIPCHK(c, hipMalloc(&c->d_verts_prev, bytes));
+    if (!c->d_verts_prev) HIPCHK(c, hipMalloc(&c->d_verts_prev.p, bytes));
     // on the stream ptk_update_geometry rewrites d_verts_res on: behind every update so far, ahead of every later one
     HIPCHK(c, hipMemcpyAsync(c->d_verts_prev, c->d_verts_res, bytes, hipMemcpyDeviceToDevice, c->stream));
     c->have_snapshot = true;
@@ -470,17 +462,12 @@ int ptk_last_motion_ms(ptk_ctx* c, float* motion_ms, float* temporal_ms)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float t[2] = { 0.0f, 0.0f };
-    if (c->motion_timed)
-    {
-        // (the reprojection kernel's events are the frame entry's own, so that it is timed exactly as ptk_last_temporal_ms times it)
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(c->motion_timed == 2 ? c->ev_temporal[2] : c->ev_motion[1]));
-        HIPCHK(c, hipEventElapsedTime(&t[0], c->ev_motion[0], c->ev_motion[1]));
-        if (c->motion_timed == 2) HIPCHK(c, hipEventElapsedTime(&t[1], c->ev_temporal[1], c->ev_temporal[2]));
-    }
+    // (the reprojection kernel's events are the frame entry's own, so that it is timed exactly as ptk_last_temporal_ms times it)
+    int rc = c->ev_motion.elapsed(c, 0, 1, &t[0]);
+    if (rc == PTK_OK && c->ev_motion.timed == 2) rc = c->ev_temporal.elapsed(c, 1, 2, &t[1]);
     if (motion_ms) *motion_ms = t[0];
     if (temporal_ms) *temporal_ms = t[1];
-    return PTK_OK;
+    return rc;
 }
 
 }  // extern "C"

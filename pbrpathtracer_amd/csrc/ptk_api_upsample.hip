@@ -54,19 +54,18 @@ static int upsample_on_stream(ptk_ctx* c, int w, int h, const LowPlanes& lo, int
                               const float* d_hi_normal, const float* d_hi_albedo, const ptk_upsample_params& p, float* d_out_color,
                               int32_t* d_out_class)
 {
-    c->upsample_timed = false;
+    c->ev_upsample.begin();
     const size_t px = (size_t)w * h;
     const size_t images = lo.albedo ? 4 : 3;
-    if (const int rc = grow(c, c->d_upsample_pack, c->upsample_pack_texels, images * px, sizeof(float4)); rc != PTK_OK) return rc;
-    if (const int rc = ensure_events(c, c->ev_upsample); rc != PTK_OK) return rc;
+    if (const int rc = c->d_upsample_pack.grow(c, images * px, sizeof(float4)); rc != PTK_OK) return rc;
     UpsampleImages im = { c->d_upsample_pack, c->d_upsample_pack + px, c->d_upsample_pack + 2 * px, lo.albedo ? c->d_upsample_pack + 3 * px : nullptr };
-    HIPCHK(c, hipEventRecord(c->ev_upsample[0], c->stream));
+    if (const int rm = c->ev_upsample.mark(c, 0, c->stream); rm != PTK_OK) return rm;
     UpsamplePackParams pk = {};
     pk.color = lo.color; pk.counts = lo.counts; pk.samples = lo.samples; pk.kind = lo.kind;
     pk.id = lo.id; pk.position = lo.position; pk.normal = lo.normal; pk.albedo = lo.albedo; pk.width = w; pk.height = h;
     launch_upsample_pack(pk, im, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_upsample[1], c->stream));
+    if (const int rm = c->ev_upsample.mark(c, 1, c->stream); rm != PTK_OK) return rm;
     UpsampleParams k = {};
     k.lo = im; k.w = w; k.h = h;
     k.hi_id = d_hi_id; k.hi_position = d_hi_position; k.hi_normal = d_hi_normal; k.hi_albedo = d_hi_albedo;
@@ -75,8 +74,8 @@ static int upsample_on_stream(ptk_ctx* c, int w, int h, const LowPlanes& lo, int
     k.zz = p.max_plane_dist * p.max_plane_dist; k.min_normal_dot = p.min_normal_dot; k.wide = p.wide;
     launch_upsample(k, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_upsample[2], c->stream));
-    c->upsample_timed = true;
+    if (const int rm = c->ev_upsample.mark(c, 2, c->stream); rm != PTK_OK) return rm;
+    c->ev_upsample.done();
     return PTK_OK;
 }
 
@@ -135,10 +134,10 @@ int ptk_render_guides(ptk_ctx* c, int width, int height, uint32_t sample, uint64
     const size_t px = (size_t)width * height;
     // (a failure below leaves no guides rather than half of them)
     c->guide_w = c->guide_h = 0; c->guide_mask = 0;
-    if (const int rc = grow(c, c->d_guide_primary, c->guide_primary_px, px, sizeof(float4)); rc != PTK_OK) return rc;
+    if (const int rc = c->d_guide_primary.grow(c, px, sizeof(float4)); rc != PTK_OK) return rc;
     for (int k = 0; k < NUM_FEATURES; k++)
         if ((mask >> k) & 1u)
-            if (const int rc = grow(c, c->d_guide[k], c->guide_cap[k], px, (size_t)guide_channels(k) * 4); rc != PTK_OK) return rc;
+            if (const int rc = c->d_guide[k].grow(c, px, (size_t)guide_channels(k) * 4); rc != PTK_OK) return rc;
     PrimaryParams pp;
     RenderParams p;
     guide_params(c, width, height, sample, seed, pp, p);
@@ -247,8 +246,8 @@ int ptk_upsample_frame(ptk_ctx* c, int source, const ptk_upsample_params* params
     const int w = c->width, h = c->height, W = c->guide_w, H = c->guide_h;
     if ((int64_t)W * h != (int64_t)H * w) return fail(c, PTK_ERR_BAD_ARG, "ptk_upsample_frame: the frame and the guide planes differ in aspect ratio");
     const size_t px = (size_t)w * h, PX = (size_t)W * H;
-    LowPlanes lo = plane_source(nullptr, (const int32_t*)c->d_feat[PTK_FEAT_MATERIAL], (const float*)c->d_feat[PTK_FEAT_POSITION],
-                                (const float*)c->d_feat[PTK_FEAT_NORMAL], (const float*)c->d_feat[PTK_FEAT_ALBEDO]);
+    LowPlanes lo = plane_source(nullptr, (const int32_t*)c->d_feat[PTK_FEAT_MATERIAL].p, (const float*)c->d_feat[PTK_FEAT_POSITION].p,
+                                (const float*)c->d_feat[PTK_FEAT_NORMAL].p, (const float*)c->d_feat[PTK_FEAT_ALBEDO].p);
     if (source == PTK_UPSAMPLE_DENOISED)
     {
         if (!c->d_denoised || c->den_w != w || c->den_h != h || c->den_w == 0)
@@ -272,10 +271,10 @@ int ptk_upsample_frame(ptk_ctx* c, int source, const ptk_upsample_params* params
     // (a result of another size is gone once its buffer is handed to this call)
     const int was_w = c->ups_w, was_h = c->ups_h;
     c->ups_w = c->ups_h = 0;
-    if (const int rc = grow(c, c->d_upsampled, c->upsampled_px, PX, 4 * sizeof(float)); rc != PTK_OK) return rc;
+    if (const int rc = c->d_upsampled.grow(c, PX, 4 * sizeof(float)); rc != PTK_OK) return rc;
     c->ups_w = W; c->ups_h = H;
-    const int rc = upsample_on_stream(c, w, h, lo, W, H, (const int32_t*)c->d_guide[PTK_FEAT_MATERIAL], (const float*)c->d_guide[PTK_FEAT_POSITION],
-                                      (const float*)c->d_guide[PTK_FEAT_NORMAL], (const float*)c->d_guide[PTK_FEAT_ALBEDO], *params, c->d_upsampled,
+    const int rc = upsample_on_stream(c, w, h, lo, W, H, (const int32_t*)c->d_guide[PTK_FEAT_MATERIAL].p, (const float*)c->d_guide[PTK_FEAT_POSITION].p,
+                                      (const float*)c->d_guide[PTK_FEAT_NORMAL].p, (const float*)c->d_guide[PTK_FEAT_ALBEDO].p, *params, c->d_upsampled,
                                       upsampled_class(c));
     if (rc != PTK_OK && (was_w != W || was_h != H)) c->ups_w = c->ups_h = 0;
     return rc;
@@ -308,15 +307,10 @@ int ptk_last_upsample_ms(ptk_ctx* c, float* pack_ms, float* kernel_ms)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float t[2] = { 0.0f, 0.0f };
-    if (c->upsample_timed)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(c->ev_upsample[2]));
-        for (int k = 0; k < 2; k++) HIPCHK(c, hipEventElapsedTime(&t[k], c->ev_upsample[k], c->ev_upsample[k + 1]));
-    }
+    const int rc = c->ev_upsample.spans(c, 0, 2, t);
     if (pack_ms) *pack_ms = t[0];
     if (kernel_ms) *kernel_ms = t[1];
-    return PTK_OK;
+    return rc;
 }
 
 }  // extern "C"

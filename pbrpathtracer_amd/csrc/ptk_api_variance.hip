@@ -44,16 +44,15 @@ static int check_planes_args(ptk_ctx* c, int width, int height, const float* mom
 // [2] behind the prefilter.  d_raw is needed with the prefilter only; without it variance_kernel writes d_out itself.
 static int variance_on_stream(ptk_ctx* c, int width, int height, const VarianceImages& im, const ptk_variance_params& p, float* d_raw, float* d_out)
 {
-    c->variance_timed = false;
-    if (const int rc = ensure_events(c, c->ev_variance); rc != PTK_OK) return rc;
+    c->ev_variance.begin();
     VarianceParams k = {};
     k.mm = im.mm; k.pi = im.pi; k.nz = im.nz; k.raw = p.prefilter ? d_raw : d_out; k.width = width; k.height = height;
     k.radius = p.radius; k.mark = p.prefilter; k.min_frames = p.min_frames; k.zz = p.max_plane_dist * p.max_plane_dist;
     k.min_normal_dot = p.min_normal_dot;
-    HIPCHK(c, hipEventRecord(c->ev_variance[0], c->stream));
+    if (const int rm = c->ev_variance.mark(c, 0, c->stream); rm != PTK_OK) return rm;
     launch_variance(k, c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_variance[1], c->stream));
+    if (const int rm = c->ev_variance.mark(c, 1, c->stream); rm != PTK_OK) return rm;
     if (p.prefilter)
     {
         VariancePrefilterParams f = {};
@@ -61,8 +60,8 @@ static int variance_on_stream(ptk_ctx* c, int width, int height, const VarianceI
         launch_variance_prefilter(f, c->stream);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipEventRecord(c->ev_variance[2], c->stream));
-    c->variance_timed = true; c->variance_prefiltered = p.prefilter != 0;
+    if (const int rm = c->ev_variance.mark(c, 2, c->stream); rm != PTK_OK) return rm;
+    c->ev_variance.done(p.prefilter ? 2 : 1);
     return PTK_OK;
 }
 
@@ -72,7 +71,7 @@ static int planes_on_stream(ptk_ctx* c, int width, int height, const float* d_mo
 {
     const size_t px = (size_t)width * height;
     // three float4 images, and the raw plane behind them
-    if (const int rc = grow(c, c->d_variance_pack, c->variance_pack_px, px, 3 * sizeof(float4) + sizeof(float)); rc != PTK_OK) return rc;
+    if (const int rc = c->d_variance_pack.grow(c, px, 3 * sizeof(float4) + sizeof(float)); rc != PTK_OK) return rc;
     const VarianceImages im = { c->d_variance_pack, c->d_variance_pack + px, c->d_variance_pack + 2 * px };
     VariancePackParams k = {};
     k.moments = d_moments; k.count = d_count; k.frame_count = d_frame_count; k.id = d_id; k.position = d_position; k.normal = d_normal;
@@ -168,14 +167,14 @@ int ptk_denoise_temporal(ptk_ctx* c, const ptk_denoise_params* params, uint32_t 
         return fail(c, PTK_ERR_BAD_ARG, "ptk_denoise_temporal: PTK_DENOISE_VARIANCE needs ptk_temporal_variance behind the last ptk_temporal_frame_moments");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t px = (size_t)c->width * c->height;
-    if (!c->d_temporal_mm) HIPCHK(c, hipMalloc(&c->d_temporal_mm, px * kTemporalMomentsBytes));      // (the mask lives there)
-    if (!c->d_denoised) HIPCHK(c, hipMalloc(&c->d_denoised, px * 3 * sizeof(float)));
+    if (!c->d_temporal_mm) HIPCHK(c, hipMalloc(&c->d_temporal_mm.p, px * kTemporalMomentsBytes));      // (the mask lives there)
+    if (!c->d_denoised) HIPCHK(c, hipMalloc(&c->d_denoised.p, px * 3 * sizeof(float)));
     int32_t* mask = temporal_mask_plane(c, px);
-    launch_temporal_mask(temporal_count(c, px), (const int32_t*)c->d_feat[PTK_FEAT_TRIANGLE], (const float*)c->d_feat[PTK_FEAT_EMISSION], mask, c->width,
+    launch_temporal_mask(temporal_count(c, px), (const int32_t*)c->d_feat[PTK_FEAT_TRIANGLE].p, (const float*)c->d_feat[PTK_FEAT_EMISSION].p, mask, c->width,
                          c->height, c->stream);
     HIPCHK(c, hipGetLastError());
-    const int rc = denoise_planes_on_stream(c, c->width, c->height, temporal_color(c, px), mask, (const float*)c->d_feat[PTK_FEAT_NORMAL],
-                                            (const float*)c->d_feat[PTK_FEAT_POSITION], (const float*)c->d_feat[PTK_FEAT_ALBEDO],
+    const int rc = denoise_planes_on_stream(c, c->width, c->height, temporal_color(c, px), mask, (const float*)c->d_feat[PTK_FEAT_NORMAL].p,
+                                            (const float*)c->d_feat[PTK_FEAT_POSITION].p, (const float*)c->d_feat[PTK_FEAT_ALBEDO].p,
                                             variance ? temporal_variance_plane(c, px) : nullptr, *params, c->d_denoised, nullptr);
     if (rc == PTK_OK) { c->den_w = c->width; c->den_h = c->height; }
     return rc;
@@ -185,15 +184,10 @@ int ptk_last_variance_ms(ptk_ctx* c, float* variance_ms, float* prefilter_ms)
 {
     if (!c) return PTK_ERR_BAD_ARG;
     float t[2] = { 0.0f, 0.0f };
-    if (c->variance_timed)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(c->ev_variance[2]));
-        for (int k = 0; k < (c->variance_prefiltered ? 2 : 1); k++) HIPCHK(c, hipEventElapsedTime(&t[k], c->ev_variance[k], c->ev_variance[k + 1]));
-    }
+    const int rc = c->ev_variance.spans(c, 0, c->ev_variance.timed == 2 ? 2 : 1, t);
     if (variance_ms) *variance_ms = t[0];
     if (prefilter_ms) *prefilter_ms = t[1];
-    return PTK_OK;
+    return rc;
 }
 
 }  // extern "C"

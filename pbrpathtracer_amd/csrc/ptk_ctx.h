@@ -5,14 +5,19 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ptk_features.h"
+#include "ptk_own.h"
 
 typedef struct ncclComm* ncclComm_t;             // rccl.h's own declaration, repeated so that only ptk_api_exchange.hip includes that header (which checks it)
 namespace ptk { struct RaysBlock; }
 
 struct ptk_ctx {
+    // The streams come first: members go in reverse order of declaration, so every buffer and event below goes before the stream
+    // that works on it (each stream is drained as it goes).  own_stream: `stream` is stream_own, not a caller's (ptk_set_stream)
+    ptk::Stream stream_own, trace_stream[2], geo_stream, xstream, exit_stream;
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -20,10 +25,10 @@ struct ptk_ctx {
     std::mutex err_mu;
 
     // scene (device)
-    float4* d_flat_tris = nullptr;      // <= 16 triangles: records in ascending triangle index for the FLAT kernel
-    float4 *d_nodes = nullptr, *d_tris = nullptr, *d_shade = nullptr, *d_mats = nullptr, *d_lights = nullptr;
-    int4* d_texinfo = nullptr;
-    uint32_t* d_texels = nullptr;
+    ptk::Buf<float4> d_flat_tris;       // <= 16 triangles: records in ascending triangle index for the FLAT kernel
+    ptk::Buf<float4> d_nodes, d_tris, d_shade, d_mats, d_lights;
+    ptk::Buf<int4> d_texinfo;
+    ptk::Buf<uint32_t> d_texels;
     int num_nodes = 0, num_tris = 0, num_lights = 0, bvh_depth = 0, bvh_stack = 0, num_leaf_tris = 0;
     float scene_bound = 0.0f;           // 3.1 x (1.01 x the largest |vertex coordinate| + 1e-3): RenderParams::scene_bound
     float scene_lo[3] = { 0, 0, 0 }, scene_hi[3] = { 0, 0, 0 };     // the vertices' bounding box
@@ -40,20 +45,21 @@ struct ptk_ctx {
     std::vector<int32_t> h_flat_material;
     // geometry updates (ptk_update_geometry): the world-space vertices stay resident beside the records (a refit needs the exact
     // v2, v3: fl(v1 + fl(v2 - v1)) is not v2); everything else is made by the first update and lives until the next upload
-    float* d_verts_res = nullptr;                // [num_tris][9]
-    int32_t* d_tri_pos = nullptr;                // triangle -> position of its record in the leaf order
-    int32_t* d_level_nodes = nullptr;            // node indices sorted by level, the root's level first
+    ptk::Buf<float> d_verts_res;                 // [num_tris][9]
+    ptk::Buf<int32_t> d_tri_pos;                 // triangle -> position of its record in the leaf order
+    ptk::Buf<int32_t> d_level_nodes;             // node indices sorted by level, the root's level first
     std::vector<int> level_start;                // [levels + 1] offsets into d_level_nodes
-    double* d_refit_partial = nullptr;           // one partial SAH sum per 256 nodes
-    float4* d_refit_side = nullptr;              // per node: union box + summed child half-area (ptk_refit.h)
-    float* d_geo_stage = nullptr; size_t geo_stage_floats = 0;     // staged verts | normals | tbn of the update in progress
-    uint32_t* d_geo_red = nullptr;               // GEO_RED_WORDS of the bounds reduction, then one double: the SAH cost
-    uint32_t* h_geo_red = nullptr;               // page-locked target of its read-back
-    hipStream_t geo_stream = nullptr;            // staging copies and the bounds reduction: the one host wait of an update is for this stream alone
+    ptk::Buf<double> d_refit_partial;            // one partial SAH sum per 256 nodes
+    ptk::Buf<float4> d_refit_side;               // per node: union box + summed child half-area (ptk_refit.h)
+    ptk::Buf<float> d_geo_stage;                 // staged verts | normals | tbn of the update in progress
+    ptk::Buf<uint32_t> d_geo_red;                // GEO_RED_WORDS of the bounds reduction, then one double: the SAH cost
+    ptk::Pinned<uint32_t> h_geo_red;             // page-locked target of its read-back
+    // geo_stream: staging copies and the bounds reduction: the one host wait of an update is for this stream alone
     // events of the newest update: [0] [1] around staging + bounds on geo_stream; [2] before the repack, [3] behind it, [4] behind
     // the refit on the context's stream ([4] also orders the next update's staging behind this one's kernels)
-    hipEvent_t ev_geo_t[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    bool geo_done_recorded = false, lights_stale = false;          // lights_stale: h_lights lacks the vertices an update moved
+    // (all five made by ptk_create; timed: an update has recorded them)
+    ptk::Timer<5> ev_geo_t;
+    bool lights_stale = false;                   // h_lights lacks the vertices an update moved
     uint32_t geo_updates = 0;
     double sah_built = 0.0, sah_now = 0.0; bool sah_now_pending = false;
     float bvh_pad = 0.0f;                        // the builders' box padding for the current scene extent
@@ -76,18 +82,18 @@ struct ptk_ctx {
 
     // frame
     int width = 0, height = 0, max_depth = 3;                                 // pathtracer.cpp:15
-    float4* d_primary = nullptr;
-    float4* d_primary_hit = nullptr;  // primary-visibility cache (pinhole, no opacity textures)
-    float4* d_primary_rd = nullptr;   // ... and the camera ray's direction per pixel
-    uint2* d_pixel_rng = nullptr;     // per pixel: (pixel key, PCG increment) for pixel_rng_seed
+    ptk::Buf<float4> d_primary;
+    ptk::Buf<float4> d_primary_hit;   // primary-visibility cache (pinhole, no opacity textures)
+    ptk::Buf<float4> d_primary_rd;    // ... and the camera ray's direction per pixel
+    ptk::Buf<uint2> d_pixel_rng;      // per pixel: (pixel key, PCG increment) for pixel_rng_seed
     uint64_t pixel_rng_seed = 0; bool pixel_rng_valid = false;
     bool primary_hit_dirty = true, scene_has_opacity = false;
     int opt_primary_cache = 1;
     int opt_flat_shade_w = 8, opt_flat_gen_w = 64;
     int opt_flat = 1;                    // scenes of <= PTK_FLAT_MAX triangles: no BVH walk (trace_kernel<.., FLAT>)
-    float* d_accum = nullptr;        // owned accumulator
+    ptk::Buf<float> d_accum;         // owned accumulator
     float* d_accum_bound = nullptr;  // caller-owned accumulator (ptk_bind_accum) or null
-    uint8_t* d_rgb8 = nullptr;
+    ptk::Buf<uint8_t> d_rgb8;
     // hand-off buffer bound by ptk_bind_out_image: the caller's pointer, its device-visible alias, whether this context
     // page-locked it, and whether the next accumulate kernel must write every pixel (after binding, reset, a camera or
     // scene change: the set of always-black pixels may have changed)
@@ -104,135 +110,119 @@ struct ptk_ctx {
     std::atomic<int> samples{ 0 };
     std::atomic<uint32_t> render_gen{ 1 };       // generation of the newest render: Exit() names it and thereby every render still in flight (kernels stand down
                                                  // when the named generation >= their own); renders issued afterwards are not affected
-    uint32_t* d_exit = nullptr;
-    uint32_t* h_exit = nullptr;                  // page-locked source of the copy that writes d_exit (ptk_request_exit)
-    hipStream_t exit_stream = nullptr;           // high priority, nothing else on it: the copy of the Exit() word never waits behind a render
+    ptk::Buf<uint32_t> d_exit;
+    ptk::Pinned<uint32_t> h_exit;                // page-locked source of the copy that writes d_exit (ptk_request_exit)
+    // exit_stream: high priority, nothing else on it: the copy of the Exit() word never waits behind a render
     std::mutex exit_mu;                          // (Exit() may come from several threads: the source word never goes back)
-    unsigned long long* d_stats = nullptr;
-    unsigned* d_queues = nullptr;                // item queues of trace_kernel's persistent waves
+    ptk::Buf<unsigned long long> d_stats;
+    ptk::Buf<unsigned> d_queues;                 // item queues of trace_kernel's persistent waves
     // live-quadrant list (which 8x8 quadrants of the owned tiles have pixels to trace) and what it was built for
-    unsigned long long* d_live_mask = nullptr;
-    unsigned* d_live_list = nullptr;             // [capacity] entries + 1 word: the count
+    ptk::Buf<unsigned long long> d_live_mask;
+    ptk::Buf<unsigned> d_live_list;              // [capacity] entries + 1 word: the count
     int live_capacity = 0;
     unsigned long long hit_generation = 0;       // bumped whenever the primary-hit cache is recomputed
     struct LiveKey { int width, height, rank, world, cached; unsigned long long generation; } live_key = { 0, 0, -1, 0, -1, 0 };
     int resident_waves = 4096;                   // one-wave workgroups the device holds at once (CUs x 16)
 
     // adaptive render (ptk_render_adaptive): allocated by the first one, freed by ptk_set_frame with another resolution
-    uint32_t* d_counts = nullptr;                // [H][W] samples per pixel, rows bottom-up
-    float* d_moments = nullptr;                  // [H][W][3] sums of squared samples (S2)
-    unsigned long long* d_adapt_active = nullptr, * d_adapt_traced = nullptr;     // per quadrant of the frame: active set, active & live
-    unsigned* d_adapt_list = nullptr;            // [adapt_capacity] entries + 1 word: the count (the traced mask's quadrants)
-    unsigned long long* d_adapt_stats = nullptr; // [0] pixel samples, [1] largest count, [2] low word: active pixels after the last test
+    ptk::Buf<uint32_t> d_counts;                 // [H][W] samples per pixel, rows bottom-up
+    ptk::Buf<float> d_moments;                   // [H][W][3] sums of squared samples (S2)
+    ptk::Buf<unsigned long long> d_adapt_active, d_adapt_traced;                  // per quadrant of the frame: active set, active & live
+    ptk::Buf<unsigned> d_adapt_list;             // [adapt_capacity] entries + 1 word: the count (the traced mask's quadrants)
+    ptk::Buf<unsigned long long> d_adapt_stats;  // [0] pixel samples, [1] largest count, [2] low word: active pixels after the last test
     int adapt_capacity = 0;                      // quadrants the buffers hold (every quadrant of the frame: any tile split fits)
-    unsigned* h_adapt_count = nullptr;           // page-locked [2]: the active count of rounds r and r + 1, read one round behind
-    hipEvent_t ev_adapt[2] = { nullptr, nullptr };
+    ptk::Pinned<unsigned> h_adapt_count;         // page-locked [2]: the active count of rounds r and r + 1, read one round behind
+    ptk::Event ev_adapt[2];
     bool adaptive_accum = false;                 // the accumulator holds an adaptive render: per-pixel counts, no single sample count
 
     // first-hit feature planes (ptk_render_features): allocated on first use, each for the frame feat_w x feat_h
-    void* d_feat[ptk::NUM_FEATURES] = {};
+    ptk::Buf<void> d_feat[ptk::NUM_FEATURES];
     int feat_w = 0, feat_h = 0;                  // the frame the planes were allocated for and last rendered at
     uint32_t feat_mask = 0;                      // planes the last ptk_render_features wrote
 
     // radiance along caller-supplied rays (ptk_trace_rays): its own sample buffer between rays_kernel and rays_fold_kernel - renders
     // may still be in flight on the internal streams with theirs -, grown to the largest pass so far; the item counter and
     // parameter block of a launch; three events per pass of the last call: before rays_kernel, behind it, behind the fold
-    float4* d_rays_samples = nullptr; size_t rays_samples_bytes = 0;
-    ptk::RaysBlock* d_rays_block = nullptr;
-    std::vector<hipEvent_t> ev_rays;
-    int rays_passes = 0;                         // timed passes of the last call (at most kMaxTimedPasses)
+    ptk::Buf<float4> d_rays_samples;             // (capacity in bytes)
+    ptk::Buf<ptk::RaysBlock> d_rays_block;
+    ptk::PassTimer ev_rays;                      // (at most kMaxTimedPasses passes of the last call)
 
     // lightmap baking (ptk_bake_lightmap), each grown to the largest bake so far: the owner plane (4 B per texel) with the covered
     // count per block of 256 texels behind it; the compacted rays of the covered texels (origins | dirs | sums | keys | texel
     // index, 44 B each); the second image + owner plane of ptk_lightmap_dilate (16 B per texel); the covered count's page-locked
     // read-back word; six events of the last bake: start, behind coverage + count, before and behind the ray generator, behind the
     // trace, behind the scatter
-    int* d_bake_plane = nullptr; size_t bake_plane_texels = 0;
-    float* d_bake_compact = nullptr; size_t bake_compact_rays = 0;
-    float* d_bake_dilate = nullptr; size_t bake_dilate_texels = 0;
-    uint32_t* h_bake_total = nullptr;
-    hipEvent_t ev_bake[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    bool bake_timed = false, bake_traced = false;
+    ptk::Buf<int> d_bake_plane;
+    ptk::Buf<float> d_bake_compact, d_bake_dilate;
+    ptk::Pinned<uint32_t> h_bake_total;
+    ptk::Timer<6> ev_bake;
 
     // adaptive ray queries and lightmap bakes (ptk_trace_rays_adaptive, ptk_bake_lightmap_adaptive), each grown to the largest call
     // so far: per ray 56 B - the round's compacted origins | dirs (24 B), keys, source indices, the next active list and the keep
     // flags (4 B each), S2 and the counts where the caller's arrays do not hold them (12 + 4 B) - with a count per 256 rays and the
     // total behind them; a lightmap's need plane (1 B per texel); the total's page-locked read-back word; two events around the
     // GPU work of a round; the last call's times (ptk_last_rays_adaptive_ms)
-    float* d_radapt = nullptr; size_t radapt_rays = 0;
-    uint8_t* d_radapt_need = nullptr; size_t radapt_need_texels = 0;
-    uint32_t* h_radapt_total = nullptr;
-    hipEvent_t ev_radapt[2] = { nullptr, nullptr };
+    ptk::Buf<float> d_radapt;
+    ptk::Buf<uint8_t> d_radapt_need;
+    ptk::Pinned<uint32_t> h_radapt_total;
+    ptk::Timer<2> ev_radapt;
     float radapt_ms[3] = { 0.0f, 0.0f, 0.0f };   // host wall time of the round loop; rays_keyed_kernel; the other kernels of the rounds
 
     // irradiance probe baking (ptk_bake_probes), each grown to the largest call so far: the basis table (36 B per direction), one
     // block of rays (origins | dirs, 24 B each) and, while the caller passes no table, the radiance table (12 B per ray); four
     // events of the last bake - around the basis table, around the projection - and three per block of probes (the first
     // kMaxTimedPasses of them): before the ray generator, behind it, behind the trace
-    float* d_probe_basis = nullptr; size_t probe_basis_dirs = 0;
-    float* d_probe_rays = nullptr; size_t probe_rays_cap = 0;
-    float* d_probe_table = nullptr; size_t probe_table_rays = 0;
-    hipEvent_t ev_probes[4] = { nullptr, nullptr, nullptr, nullptr };
-    std::vector<hipEvent_t> ev_probe_blocks;
-    int probe_blocks_timed = 0;
-    bool probes_timed = false;
+    ptk::Buf<float> d_probe_basis, d_probe_rays, d_probe_table;
+    ptk::Timer<4> ev_probes;
+    ptk::PassTimer ev_probe_blocks;
 
     // probe visibility (ptk_bake_probe_visibility): the depth table while the caller passes none (4 B per ray, grown to the largest
     // call so far; the rays of a block are d_probe_rays); two events of the last call around the moments kernel and three per block
     // of probes as above: before the ray generator, behind it, behind hits_kernel
-    float* d_probe_depth = nullptr; size_t probe_depth_rays = 0;
-    hipEvent_t ev_probe_vis[2] = { nullptr, nullptr };
-    std::vector<hipEvent_t> ev_probe_vis_blocks;
-    int probe_vis_blocks_timed = 0;
-    bool probe_vis_timed = false;
+    ptk::Buf<float> d_probe_depth;
+    ptk::Timer<2> ev_probe_vis;
+    ptk::PassTimer ev_probe_vis_blocks;
 
     // closest-hit and occlusion queries (ptk_intersect_rays, ptk_occluded_rays): two events around the last call's kernel, made
     // by the first call
-    hipEvent_t ev_hits[2] = { nullptr, nullptr };
-    bool hits_timed = false;
+    ptk::Timer<2> ev_hits;
 
     // closest-point queries (ptk_closest_points): two events around the last call's kernel, made by the first call; the two
     // counters of ptk_closest_stats, made by its first call
-    hipEvent_t ev_closest[2] = { nullptr, nullptr };
-    bool closest_timed = false;
-    unsigned long long* d_closest_stats = nullptr;
+    ptk::Timer<2> ev_closest;
+    ptk::Buf<unsigned long long> d_closest_stats;
 
     // crossing counts, containment and signed distance (ptk_crossings_rays, ptk_contains_points, ptk_signed_distance): two events
     // around the last call's kernels, made by the first call
-    hipEvent_t ev_crossings[2] = { nullptr, nullptr };
-    bool crossings_timed = false;
+    ptk::Timer<2> ev_crossings;
 
     // ordered multi-hit queries (ptk_multihit_rays): two events around the last call's kernel, made by the first call
-    hipEvent_t ev_multihit[2] = { nullptr, nullptr };
-    bool multihit_timed = false;
+    ptk::Timer<2> ev_multihit;
 
     // surface sampling (ptk_sample_surface, ptk_surface_weights).  The table, 8 B per triangle - the inclusive sums of the quantised
     // weights - with the 8 KiB coarse table behind it; the caller's weights (4 B per triangle) while some are set; the workgroup
     // sums of the scan; the reduction block of the build.  All made by the first use for a scene and freed with it.  surf_valid: the
     // table holds the resident vertices and the weights as they are (ptk_update_geometry and ptk_surface_weights clear it).  What
-    // ptk_surface_info reports: exponent and max from the build, total and drawable read back once asked for.  Four events: around
-    // the last build, around the last call's kernel; surf_table_timed: the last call built the table
-    uint64_t* d_surf_table = nullptr;
-    float* d_surf_weights = nullptr;
-    uint64_t* d_surf_sums = nullptr;
-    uint32_t* d_surf_red = nullptr;
+    // ptk_surface_info reports: exponent and max from the build, total and drawable read back once asked for.  Two timers: around
+    // the last build (timed: the last call built the table), around the last call's kernel
+    ptk::Buf<uint64_t> d_surf_table, d_surf_sums;
+    ptk::Buf<float> d_surf_weights;
+    ptk::Buf<uint32_t> d_surf_red;
     bool surf_valid = false, surf_info_pending = false;
     uint64_t surf_total = 0;
     int surf_exponent = 0, surf_drawable = 0;
     float surf_max = 0.0f;
-    hipEvent_t ev_surface[4] = { nullptr, nullptr, nullptr, nullptr };
-    bool surf_table_timed = false, surf_sample_timed = false;
+    ptk::Timer<2> ev_surf_table, ev_surface;
     int opt_surface_variant = 1;                 // surface_sample_kernel's variant (ptk_surface.h; 1: the coarse table in LDS): speed only
 
     // a-trous denoiser (ptk_denoise_planes, ptk_denoise_frame): the four packed float4 images of a call (64 B per pixel, grown to the
     // largest call so far); the denoised frame [H][W][3], made by the first ptk_denoise_frame, freed with the feature planes, and
     // the resolution it was last written at; four events of the last call: before the pack, behind it, behind the filter, behind
     // the unpack
-    float4* d_denoise = nullptr; size_t denoise_px = 0;
-    float* d_denoised = nullptr;
+    ptk::Buf<float4> d_denoise;
+    ptk::Buf<float> d_denoised;
     int den_w = 0, den_h = 0;
-    hipEvent_t ev_denoise[4] = { nullptr, nullptr, nullptr, nullptr };
-    bool denoise_timed = false;
+    ptk::Timer<4> ev_denoise;
 
     // temporal reprojection (ptk_reproject_planes, ptk_temporal_frame).  The frame entry's buffer, 112 B per pixel, made by the first
     // ptk_temporal_frame at a resolution and freed with the feature planes: two histories of three float4 images each, then the
@@ -240,25 +230,23 @@ struct ptk_ctx {
     // stored with it; temporal_w x temporal_h is the resolution of that call (0: none yet).  The planes entries pack the caller's
     // history into d_temporal_pack (48 B per pixel, grown to the largest call so far).  Three events of the last call: before the
     // pack, behind it, behind the kernel
-    float4* d_temporal = nullptr;
+    ptk::Buf<float4> d_temporal;
     int temporal_w = 0, temporal_h = 0, temporal_set = 0;
     ptk_view temporal_view = {};
-    float4* d_temporal_pack = nullptr; size_t temporal_pack_px = 0;
-    hipEvent_t ev_temporal[3] = { nullptr, nullptr, nullptr };
-    bool temporal_timed = false;
+    ptk::Buf<float4> d_temporal_pack;
+    ptk::Timer<3> ev_temporal;
 
     // moving geometry under temporal reprojection (ptk_geometry_snapshot, ptk_render_motion, ptk_temporal_frame_moving).  The snapshot
     // of d_verts_res, 36 B per triangle, made by the first ptk_geometry_snapshot of a scene and freed with it; have_snapshot: it
     // holds one.  The three planes of ptk_render_motion in one buffer, 32 B per pixel - previous position [H][W][3] | previous
     // normal [H][W][3] | motion [H][W][2] -, made by the first call at a resolution and freed with the feature planes; motion_w x
-    // motion_h is the resolution of the last call (0: none yet).  Two events of the last call around motion_kernel; motion_timed 1:
+    // motion_h is the resolution of the last call (0: none yet).  Two events of the last call around motion_kernel; timed 1:
     // they are set, 2: and ev_temporal holds the reprojection kernel that followed
-    float* d_verts_prev = nullptr;
+    ptk::Buf<float> d_verts_prev;
     bool have_snapshot = false;
-    float* d_motion = nullptr;
+    ptk::Buf<float> d_motion;
     int motion_w = 0, motion_h = 0;
-    hipEvent_t ev_motion[2] = { nullptr, nullptr };
-    int motion_timed = 0;
+    ptk::Timer<2> ev_motion;
 
     // temporal moments and variance (ptk_temporal_frame_moments, ptk_temporal_variance, ptk_denoise_temporal).  The frame entry's
     // buffer, 52 B per pixel, made by the first moments call at a resolution and freed with the feature planes: the fourth packed
@@ -268,23 +256,20 @@ struct ptk_ctx {
     // The planes entries pack into d_variance_pack (52 B per pixel with the raw plane, grown to the largest call so far);
     // ptk_reproject_moments packs the history's moments into d_temporal_pack_mm (16 B per pixel, likewise).  Three events of the
     // last variance call: before variance_kernel, behind it, behind the prefilter
-    float4* d_temporal_mm = nullptr;
+    ptk::Buf<float4> d_temporal_mm;
     bool temporal_moments = false, temporal_variance = false;
-    float4* d_variance_pack = nullptr; size_t variance_pack_px = 0;
-    float4* d_temporal_pack_mm = nullptr; size_t temporal_pack_mm_px = 0;
-    hipEvent_t ev_variance[3] = { nullptr, nullptr, nullptr };
-    bool variance_timed = false, variance_prefiltered = false;
+    ptk::Buf<float4> d_variance_pack, d_temporal_pack_mm;
+    ptk::Timer<3> ev_variance;                   // timed 2: the last call ran the prefilter too
 
     // display transform (ptk_display_planes, ptk_display_frame).  The luminance histogram, 2048 uint32 (8 KB), with the 32 B exposure
     // state behind it: made and zeroed by the first call, the histogram cleared by each call's exposure step behind itself.  The
     // frame entry's 8-bit image [H][W][3], made by the first ptk_display_frame at a resolution, freed with the feature planes, and
     // the resolution it was last written at.  Four events of the last call: before the meter, behind it, behind the exposure step,
     // behind the apply kernel
-    uint32_t* d_display_hist = nullptr;
-    uint8_t* d_display = nullptr;
+    ptk::Buf<uint32_t> d_display_hist;
+    ptk::Buf<uint8_t> d_display;
     int disp_w = 0, disp_h = 0;
-    hipEvent_t ev_display[4] = { nullptr, nullptr, nullptr, nullptr };
-    bool display_timed = false;
+    ptk::Timer<4> ev_display;
 
     // guided upsampling (ptk_render_guides, ptk_upsample_planes, ptk_upsample_frame).  The guide planes at a resolution of their
     // own with their primary-direction table (16 B per guide pixel), each grown to the largest call so far and freed with the
@@ -292,17 +277,15 @@ struct ptk_ctx {
     // low image of a call, three or four float4 images (48 or 64 B per low pixel), grown likewise.  The frame entry's result, colour
     // [H][W][3] then class [H][W] (16 B per high pixel), grown likewise and freed with the guide planes; ups_w x ups_h is the size
     // it was last written at.  Three events of the last upsample call: before the pack, behind it, behind upsample_kernel
-    void* d_guide[ptk::NUM_FEATURES] = {};
-    size_t guide_cap[ptk::NUM_FEATURES] = {};    // pixels
-    float4* d_guide_primary = nullptr; size_t guide_primary_px = 0;
+    ptk::Buf<void> d_guide[ptk::NUM_FEATURES];   // (capacity in pixels)
+    ptk::Buf<float4> d_guide_primary;
     int guide_w = 0, guide_h = 0;
     uint32_t guide_mask = 0;
     ptk_view guide_view = {};
-    float4* d_upsample_pack = nullptr; size_t upsample_pack_texels = 0;
-    float* d_upsampled = nullptr; size_t upsampled_px = 0;
+    ptk::Buf<float4> d_upsample_pack;
+    ptk::Buf<float> d_upsampled;
     int ups_w = 0, ups_h = 0;
-    hipEvent_t ev_upsample[3] = { nullptr, nullptr, nullptr };
-    bool upsample_timed = false;
+    ptk::Timer<3> ev_upsample;
 
     // sample buffer between trace_kernel and accumulate_kernel (grown on demand, never shrunk)
     // Two sample buffers / queue blocks / trace streams: the trace kernel of pass k+1 runs on the other stream and
@@ -310,13 +293,10 @@ struct ptk_ctx {
     // lets one path in tens of millions live for 60+ bounces, ~0.4 ms with the rest of the chip idle) and pass k's
     // accumulate kernel.  The accumulate kernels stay on the context's stream, in order, each behind its trace kernel,
     // so everything the caller orders after ptk_render on that stream still sees the finished batch.
-    float4* d_samples = nullptr;                 // (non-overlapped path)
-    size_t samples_bytes = 0;
-    float4* d_samples2[2] = { nullptr, nullptr };
-    size_t samples_bytes2[2] = { 0, 0 };
-    unsigned* d_queues2[2] = { nullptr, nullptr };
-    hipStream_t trace_stream[2] = { nullptr, nullptr };
-    hipEvent_t ev_trace_done[2] = { nullptr, nullptr }, ev_acc_done[2] = { nullptr, nullptr }, ev_inputs = nullptr;
+    ptk::Buf<float4> d_samples;                  // (non-overlapped path; capacities in bytes)
+    ptk::Buf<float4> d_samples2[2];
+    ptk::Buf<unsigned> d_queues2[2];
+    ptk::Event ev_trace_done[2], ev_acc_done[2], ev_inputs;      // ordering events: no timing
     bool acc_pending[2] = { false, false }, inputs_recorded = false;
     bool inputs_dirty = true;                    // scene / camera tables were (re)written on the context's stream since ev_inputs
     unsigned pass_counter = 0;
@@ -337,10 +317,10 @@ struct ptk_ctx {
     // multi-GPU exchange step (ptk_gather_accum): packed gather of every rank's owned tiles to the root
     ncclComm_t comm = nullptr;                   // the context's own communicator (ptk_comm_init), or null
     int comm_rank = 0, comm_world = 1;
-    hipStream_t xstream = nullptr;               // high priority: its kernels and the collective take wave slots ahead of queued trace waves
-    hipEvent_t ev_rendered = nullptr, ev_packed = nullptr, ev_gathered = nullptr;
-    float* d_packed = nullptr; size_t packed_floats = 0;      // non-root: this rank's packed tiles; root: every rank's, back to back
-    float* d_gathered = nullptr; size_t gathered_floats = 0;  // root: the combined image (W*H*3, rows bottom-up)
+    // xstream: high priority: its kernels and the collective take wave slots ahead of queued trace waves
+    ptk::Event ev_rendered, ev_packed, ev_gathered;            // ordering events: no timing
+    ptk::Buf<float> d_packed;                    // non-root: this rank's packed tiles; root: every rank's, back to back
+    ptk::Buf<float> d_gathered;                  // root: the combined image (W*H*3, rows bottom-up)
     int gathered_w = 0, gathered_h = 0;          // the frame the last ptk_gather_accum combined (ptk_read_gathered refuses any other)
     bool gather_pending = false;
     // every wait of the exchange step is bounded (ptk_set_option "comm_timeout_s"): a rank that never arrives must end the run with
@@ -351,13 +331,12 @@ struct ptk_ctx {
     int gather_root = 0;
 
     // log of every trace launch's duration (ptk_kernel_log): event pairs on the launch's own stream
-    std::vector<hipEvent_t> klog_ev;             // 2 x capacity
+    std::vector<ptk::Event> klog_ev;             // 2 x capacity
     int klog_n = 0;
     static constexpr int kMaxTimedPasses = 64;
-    hipEvent_t ev[kMaxTimedPasses][3] = {};      // per pass: before trace, after trace, after accumulate
+    ptk::PassTimer ev;                           // per pass: before trace, after trace, after accumulate; all made by ptk_create
     int last_passes = 0;
     int last_launches = 0;
-    bool timed = false;
 };
 
 namespace ptk {
@@ -373,35 +352,46 @@ inline int fail(ptk_ctx* c, int code, const std::string& msg)
             return ptk::fail(c, PTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
     } while (0)
 
-template <class T>
-void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
 inline float* accum_ptr(ptk_ctx* c) { return c->d_accum_bound ? c->d_accum_bound : c->d_accum; }
 
-// "Grow a context-owned buffer to the largest call so far": at least `want` elements of `bytes_per` bytes + `extra` bytes.  The stream
-// that uses it (the context's, unless named) is drained before the old buffer is freed; a refused allocation leaves null, capacity 0.
+// ---- the owners' members that need the context (ptk_own.h)
 template <class T>
-int grow(ptk_ctx* c, T*& buf, size_t& have, size_t want, size_t bytes_per, size_t extra = 0, hipStream_t user = nullptr)
+int Buf<T>::alloc_bytes(ptk_ctx* c, size_t bytes, size_t n)
 {
-    if (want <= have) return PTK_OK;
+    HIPCHK(c, try_alloc(bytes, n));
+    return PTK_OK;
+}
+template <class T>
+int Buf<T>::grow(ptk_ctx* c, size_t want, size_t bytes_per, size_t extra, hipStream_t user)
+{
+    if (want <= cap) return PTK_OK;
     HIPCHK(c, hipStreamSynchronize(user ? user : c->stream));
-    dfree(buf); have = 0;
-    HIPCHK(c, hipMalloc(&buf, want * bytes_per + extra));
-    have = want;
+    return alloc_bytes(c, want * bytes_per + extra, want);
+}
+inline int event_ms(ptk_ctx* c, hipEvent_t a, hipEvent_t b, float* ms)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(b));
+    HIPCHK(c, hipEventElapsedTime(ms, a, b));
     return PTK_OK;
 }
-
-// timing events are made on first use: those of a fixed array that are still missing ...
-template <size_t N>
-int ensure_events(ptk_ctx* c, hipEvent_t (&ev)[N])
+template <int N>
+int Timer<N>::mark(ptk_ctx* c, int k, hipStream_t s)
 {
-    for (hipEvent_t& e : ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
+    HIPCHK(c, ev[k].create());
+    HIPCHK(c, hipEventRecord(ev[k], s));
     return PTK_OK;
 }
-// ... and the three events of timed pass `i` in a vector of such triples (none for an untimed pass, i = -1)
-inline int ensure_pass_events(ptk_ctx* c, std::vector<hipEvent_t>& ev, int i)
+inline int PassTimer::reserve(ptk_ctx* c, int n)
 {
-    while (ev.size() < (size_t)(i + 1) * 3) { hipEvent_t e = nullptr; HIPCHK(c, hipEventCreate(&e)); ev.push_back(e); }
+    while (ev.size() < (size_t)n * 3) { Event e; HIPCHK(c, e.create()); ev.push_back(std::move(e)); }
+    return PTK_OK;
+}
+inline int PassTimer::add(ptk_ctx* c, int i, float* first, float* second)
+{
+    float a = 0.0f, b = 0.0f;
+    if (second) { if (const int rc = event_ms(c, at(i, 1), at(i, 2), &b); rc != PTK_OK) return rc; *second += b; }
+    if (first) { if (const int rc = event_ms(c, at(i, 0), at(i, 1), &a); rc != PTK_OK) return rc; *first += a; }
     return PTK_OK;
 }
 
@@ -429,6 +419,9 @@ void frame_view_at(const ptk_ctx* c, int width, int height, PrimaryParams& pp); 
 int trace_rays_on_stream(ptk_ctx* c, int32_t num_rays, const float* d_origins, const float* d_dirs, int max_depth, uint32_t first_sample,
                          uint32_t spp, uint64_t seed, uint32_t key_base, uint32_t flags, float* d_out, const uint32_t* d_keys = nullptr);
 int check_adaptive_args(ptk_ctx* c, const char* who, float threshold, uint32_t min_spp, uint32_t step, uint32_t max_spp);
+// ... the argument checks of the ray, point and surface query entries (see there)
+int check_query_args(ptk_ctx* c, const char* who, const char* count_word, int32_t num, const void* a, const void* b, bool have_out, bool* nothing,
+                     const char* also = nullptr);
 struct RaysAdaptiveBuffers {
     float *origins, *dirs, *s2;
     uint32_t *keys, *src, *list, *keep, *counts, *block_counts, *total;
