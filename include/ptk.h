@@ -1570,6 +1570,8 @@ int ptk_probe_unpack(ptk_ctx* ctx, int world, const float* host_packed /* all ra
  * "flat_cycle" = 0/1 (default 1; acts with "flat_rect_pairs" on): that kernel is launched from a third unit, the same pass and shade
  * block in a fixed deal / shade / pass cycle without the block vote, its work units dealt from scalar registers; 0 launches the pair
  * unit's kernel.  Bit-identical either way (tests/test_gpu_flat_cycle.py); decided per render.  ptk_trace_unit tells which one ran.
+ * The third unit reads its tables by 32-bit byte offsets: a frame of 2^28 pixels or more (or a material table of 4 GiB) gets the pair
+ * unit's kernel whatever the option says.
  * "surface_variant" = 0/1 (default 1): ptk_sample_surface's kernel searches a coarse table of 1024 sums staged in LDS before the
  * sums themselves; 0 searches the sums alone (tools/surface_sample_timing.py).  Bit-identical either way
  * (tests/test_gpu_surface_sample.py).

@@ -21,6 +21,7 @@
 #include "ptk_adaptive.h"
 #include "ptk_refit.h"
 #include "ptk_flat_mt.h"
+#include "ptk_table_offset.h"
 
 using namespace ptk;
 
@@ -256,7 +257,9 @@ int run_passes(ptk_ctx* c, uint32_t first, uint32_t spp, uint64_t seed, bool sta
     if (const int rc = use_primary_cache(c, p); rc != PTK_OK) return rc;
     // decided per render from the staged state: a material edit, a new scene or an opened aperture since the last one is seen here
     p.plain = (c->opt_plain_kernel && c->scene_plain && p.flat_count > 0 && p.primary_hit != nullptr) ? 1 : 0;
-    if (p.plain && c->opt_flat_rect_pairs) p.plain = c->opt_flat_cycle ? 3 : 2;        // the exact build's pair-pass unit, or the cycle unit around the same pass (launch_trace; the contracted builds have neither)
+    // the exact build's pair-pass unit, or the cycle unit around the same pass (launch_trace; the contracted builds have neither) - the
+    // cycle unit only while the tables its shade block reads by 32-bit byte offsets are below 2^32 bytes (ptk_table_offset.h)
+    if (p.plain && c->opt_flat_rect_pairs) p.plain = (c->opt_flat_cycle && cycle_unit_tables_fit(c->width, c->height, (uint64_t)c->h_materials.size() * MAT_F4)) ? 3 : 2;
     p.lambert = (p.plain && c->opt_lambert_kernel && c->scene_lambert) ? 1 : 0;
     if (!c->pixel_rng_valid || c->pixel_rng_seed != seed)
     {

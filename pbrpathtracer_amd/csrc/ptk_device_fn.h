@@ -8,9 +8,18 @@
 #pragma once
 
 #include "ptk_device.h"
+#include "ptk_angle_f32.h"
 
 #ifndef PTK_CONTRACT
 #define PTK_CONTRACT 0
+#endif
+// The cycle unit (ptk_kernels_cycle.hip: the exact PLAIN kernels, nothing else) compiles its shade block's table reads and its
+// hemisphere angle in forms that hold for that block alone: ldg_at, sincos_2pi_theta_f32.  Every other unit gets 0 here and the
+// text it always had.
+#if defined(PTK_CYCLE_UNIT) && !PTK_CONTRACT
+#define PTK_SHADE32 1
+#else
+#define PTK_SHADE32 0
 #endif
 
 namespace ptk {
@@ -112,15 +121,7 @@ __device__ __forceinline__ void sincos_2pi(float a, float& s, float& c)
 {
     int k = (int)(a * 0.636619772367581343f + 0.5f);
     float r = (float)((double)a - (double)k * 1.57079632679489661923);
-    float z = r * r;
-    float sp = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
-    float cp = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z
-               - 0.5f * z + 1.0f;
-    int q = k & 3;
-    float ss = (q & 1) ? cp : sp;
-    float cc = (q & 1) ? sp : cp;
-    s = (q & 2) ? -ss : ss;
-    c = (q == 1 || q == 2) ? -cc : cc;
+    sincos_reduced(k, r, s, c);                 // (ptk_angle_f32.h: the polynomial and the quadrant selects)
 }
 
 // ---- RNG (replaces PathTracer::Rand, pathtracer.cpp:367-371) -----------------------------------
@@ -147,6 +148,12 @@ struct Rng {
 };
 
 __device__ __forceinline__ float4 ldg4(const float4* p) { return *p; }
+// The record at byte offset `off` of a table whose address is wave-uniform (a launch parameter): the load takes the base from an SGPR
+// pair and the offset from ONE 32-bit register (global_load ..., v_off, s[base:base+1] offset:imm - constant parts go into `base`
+// and land in the immediate), where table[index] costs a 64-bit multiply-add or shift and copies of the base into a VGPR pair.
+// Only for tables below 2^32 bytes: the host launches no kernel that reads through this otherwise (ptk_table_offset.h).
+template <class T>
+__device__ __forceinline__ T ldg_at(const T* base, uint32_t off) { return *(const T*)((const char*)base + off); }
 typedef float f2 __attribute__((ext_vector_type(2)));
 // (float)byte / 255.0f, exactly: the double product rounds to the same float for all 256 bytes
 // (checked exhaustively in tests/test_host_cpu.py); saves the IEEE division sequence
@@ -499,12 +506,16 @@ __device__ __forceinline__ void sample_basis(v3 n_for_test, float thr, v3 basis_
     u = normalize(u);
     v = normalize(cross(u, basis_from));
 }
-// ... and the direction drawn in that frame
+// ... and the direction drawn in that frame.  theta is a u01 draw at every call
 __device__ __forceinline__ v3 sample_in_basis(v3 u, v3 v, v3 pole, float w, float theta)
 {
-    float ang = (float)(2.0f * PTK_PI_D * theta);
     float sn, cs;
-    sincos_2pi(ang, sn, cs);
+    if (PTK_SHADE32) sincos_2pi_theta_f32(theta, sn, cs);   // the same bits for each of the 2^24 draws, without a double (ptk_angle_f32.h)
+    else
+    {
+        float ang = (float)(2.0f * PTK_PI_D * theta);
+        sincos_2pi(ang, sn, cs);
+    }
     v3 d = add(add(muls(u, w * cs), muls(v, w * sn)), muls(pole, sqrt_ieee(1.0f - w * w)));
     return normalize(d);
 }
@@ -533,8 +544,17 @@ __device__ __forceinline__ bool sample_direct_light(const PT& P, v3 p, v3 n, v3 
 {
     int lightId = (int)floorf(u_light * (float)P.num_lights);
     if (lightId == P.num_lights && lightId > 0) lightId--;
-    const float4* lp = P.lights + (size_t)lightId * LIGHT_F4;
-    float4 l0 = ldg4(lp), l1 = ldg4(lp + 1), l2 = ldg4(lp + 2), l3 = ldg4(lp + 3);
+    float4 l0, l1, l2, l3;
+    if constexpr (PTK_SHADE32)
+    {
+        const uint32_t lo = (uint32_t)lightId * (uint32_t)(LIGHT_F4 * 16);
+        l0 = ldg_at(P.lights, lo); l1 = ldg_at(P.lights + 1, lo); l2 = ldg_at(P.lights + 2, lo); l3 = ldg_at(P.lights + 3, lo);
+    }
+    else
+    {
+        const float4* lp = P.lights + (size_t)lightId * LIGHT_F4;
+        l0 = ldg4(lp); l1 = ldg4(lp + 1); l2 = ldg4(lp + 2); l3 = ldg4(lp + 3);
+    }
     float su = sqrt_ieee(u_su);
     float sv = u_sv;
     float w0 = 1.0f - su, w1 = su * (1.0f - sv), w2 = su * sv;
@@ -580,15 +600,24 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
     const Hit h = W.best;
     const v3 ro = W.ro, rd = W.rd;
     if (STATS) cnt.shaded++;
+    // (the cycle unit's PLAIN kernels read the three tables by 32-bit byte offsets: ldg_at)
+    constexpr bool OFF32 = PTK_SHADE32 && PLAIN;
     const float4* sp4 = P.shade + (size_t)h.tri * SHADE_F4;
-    float4 s0 = ldg4(sp4);
+    float4 s0;
+    if constexpr (OFF32) s0 = ldg_at(P.shade, (uint32_t)h.tri * (uint32_t)(SHADE_F4 * 16)); else s0 = ldg4(sp4);
     int mbits = __float_as_int(s0.w);
     int matid = PLAIN ? mbits : mbits & 0x7fffffff;
     bool smoothing = !PLAIN && mbits < 0;
     const float4* mp = P.mats + (size_t)matid * MAT_F4;
     // the whole 96-byte material in one batch (two of its words are only needed further down: asked for there,
     // they cost the block another memory round trip), and the vertex normals of a smoothed triangle with it
-    float4 m0 = ldg4(mp), m1 = ldg4(mp + 1), m2 = ldg4(mp + 2), m3 = ldg4(mp + 3);
+    float4 m0, m1, m2, m3;
+    if constexpr (OFF32)
+    {
+        const uint32_t mo = (uint32_t)matid * (uint32_t)(MAT_F4 * 16);
+        m0 = ldg_at(P.mats, mo); m1 = ldg_at(P.mats + 1, mo); m2 = ldg_at(P.mats + 2, mo); m3 = ldg_at(P.mats + 3, mo);
+    }
+    else { m0 = ldg4(mp); m1 = ldg4(mp + 1); m2 = ldg4(mp + 2); m3 = ldg4(mp + 3); }
     const float4 notex = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), __int_as_float(-1));
     float4 m4f = PLAIN ? notex : ldg4(mp + 4), m5f = PLAIN ? notex : ldg4(mp + 5);
     float4 sn2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), sn3 = sn2, sn4 = sn2;
@@ -599,8 +628,17 @@ __device__ __forceinline__ bool shade_interaction(const PT& P, Walk& W, Walk& WS
     FlatFrames<PLAIN && !PTK_CONTRACT> frames;
     if constexpr (PLAIN && !PTK_CONTRACT)
     {
-        const float4* fp = P.flat_tris + FLAT_FRAMES_AT + h.tri * FLAT_FRAME_F4;
-        frames.u0 = ldg4(fp); frames.v0 = ldg4(fp + 1); frames.u1 = ldg4(fp + 2); frames.v1 = ldg4(fp + 3);
+        if constexpr (OFF32)
+        {
+            const float4* ft = P.flat_tris + FLAT_FRAMES_AT;
+            const uint32_t fo = (uint32_t)h.tri * (uint32_t)(FLAT_FRAME_F4 * 16);
+            frames.u0 = ldg_at(ft, fo); frames.v0 = ldg_at(ft + 1, fo); frames.u1 = ldg_at(ft + 2, fo); frames.v1 = ldg_at(ft + 3, fo);
+        }
+        else
+        {
+            const float4* fp = P.flat_tris + FLAT_FRAMES_AT + h.tri * FLAT_FRAME_F4;
+            frames.u0 = ldg4(fp); frames.v0 = ldg4(fp + 1); frames.u1 = ldg4(fp + 2); frames.v1 = ldg4(fp + 3);
+        }
     }
     asm volatile("" ::: "memory");
     int tex_diffuse = __float_as_int(m4f.x), tex_normal = __float_as_int(m4f.y);

@@ -9,8 +9,15 @@
                     // The stream is set up as in the camera-ray block below, and the two SampleCircle draws a pinhole frame
                     // still consumes (pathtracer.cpp:787, always two) only advance it - two LCG steps in one:
                     //   s2 = (s * a + inc) * a + inc = s * a^2 + inc * (a + 1)      (mod 2^32: the identical state)
+#if PTK_SHADE32
+                    // (the cycle unit: 32-bit byte offsets from the three wave-uniform bases, ldg_at - the host launches this unit
+                    // only for frames whose tables stay below 2^32 bytes)
+                    const uint2 pr = ldg_at(P.pixel_rng, pix * 8u);
+                    const float4 c = ldg_at(P.primary_hit, pix * 16u), r = ldg_at(P.primary_rd, pix * 16u);
+#else
                     const uint2 pr = P.pixel_rng[pix];
                     const float4 c = P.primary_hit[pix], r = P.primary_rd[pix];
+#endif
                     rng.inc = pr.y;
                     rng.state = hash32(P.first_sample + sample_abs + pr.x);
                     rng.key = rng.state;

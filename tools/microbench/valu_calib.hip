@@ -81,6 +81,48 @@ typedef float f2 __attribute__((ext_vector_type(2)));
         out[1 + blockIdx.x * 64 + threadIdx.x] = (float)(a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7);                      \
     }
 
+// 64-bit chains (a VGPR pair each) with two 32-bit operands beside the 64-bit ones: the 64-bit integer forms of address arithmetic
+// (%10, %11: 32-bit; the carry of the multiply-adds goes to vcc) and the conversions to double
+#define KERNEL_64X(NAME, ASM)                                                                                         \
+    __global__ __launch_bounds__(64, 8) void k_##NAME(float* out, int iters, unsigned long long* stamp)               \
+    {                                                                                                                 \
+        double a0 = 1.0 + threadIdx.x * 1e-3, a1 = a0 + 0.1, a2 = a0 + 0.2, a3 = a0 + 0.3, a4 = a0 + 0.4,             \
+               a5 = a0 + 0.5, a6 = a0 + 0.6, a7 = a0 + 0.7;                                                           \
+        const double b = 0.99999 + out[0], c = 1e-6;                                                                  \
+        const float bf = 0.99999f + out[0], cf = 1e-6f;                                                               \
+        unsigned long long t0 = 0, r0 = 0;                                                                            \
+        if (stamp) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }                      \
+        for (int i = 0; i < iters; i++)                                                                               \
+        {                                                                                                             \
+            asm volatile(REP4(ASM)                                                                                    \
+                         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)             \
+                         : "v"(b), "v"(c), "v"(bf), "v"(cf) : "vcc");                                                 \
+        }                                                                                                             \
+        if (stamp && blockIdx.x == 0 && threadIdx.x == 0)                                                             \
+        { stamp[0] = __builtin_amdgcn_s_memtime() - t0; stamp[1] = __builtin_amdgcn_s_memrealtime() - r0; }           \
+        out[1 + blockIdx.x * 64 + threadIdx.x] = (float)(a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7);                      \
+    }
+// 32-bit chains with a 64-bit operand (%10): the conversion from double
+#define KERNEL_32X(NAME, ASM)                                                                                         \
+    __global__ __launch_bounds__(64, 8) void k_##NAME(float* out, int iters, unsigned long long* stamp)               \
+    {                                                                                                                 \
+        float a0 = 1.0f + threadIdx.x * 1e-3f, a1 = a0 + 0.1f, a2 = a0 + 0.2f, a3 = a0 + 0.3f, a4 = a0 + 0.4f,       \
+              a5 = a0 + 0.5f, a6 = a0 + 0.6f, a7 = a0 + 0.7f;                                                         \
+        const float b = 0.99999f + out[0], c = 1e-6f;                                                                 \
+        const double bd = 0.99999 + out[0];                                                                           \
+        unsigned long long t0 = 0, r0 = 0;                                                                            \
+        if (stamp) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }                      \
+        for (int i = 0; i < iters; i++)                                                                               \
+        {                                                                                                             \
+            asm volatile(REP4(ASM)                                                                                    \
+                         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)             \
+                         : "v"(b), "v"(c), "v"(bd) : "vcc");                                                          \
+        }                                                                                                             \
+        if (stamp && blockIdx.x == 0 && threadIdx.x == 0)                                                             \
+        { stamp[0] = __builtin_amdgcn_s_memtime() - t0; stamp[1] = __builtin_amdgcn_s_memrealtime() - r0; }           \
+        out[1 + blockIdx.x * 64 + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;                               \
+    }
+
 #define S8(fmt) fmt(0) fmt(1) fmt(2) fmt(3) fmt(4) fmt(5) fmt(6) fmt(7)
 #define A_FMA(k) "v_fma_f32 %" #k ", %" #k ", %8, %9\n"
 #define A_MUL(k) "v_mul_f32 %" #k ", %" #k ", %8\n"
@@ -100,6 +142,7 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 #define A_CMP(k) "v_cmp_lt_f32 vcc, %" #k ", %8\n"
 #define A_CVTUB(k) "v_cvt_f32_ubyte0 %" #k ", %" #k "\n"
 #define A_CVTI(k) "v_cvt_i32_f32 %" #k ", %" #k "\n"
+#define A_CVTFI(k) "v_cvt_f32_i32 %" #k ", %" #k "\n"
 #define A_DIVSCALE(k) "v_div_scale_f32 %" #k ", vcc, %" #k ", %8, %" #k "\n"
 #define A_DIVFMAS(k) "v_div_fmas_f32 %" #k ", %" #k ", %8, %9\n"
 #define A_DIVFIXUP(k) "v_div_fixup_f32 %" #k ", %" #k ", %8, %9\n"
@@ -130,6 +173,13 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 #define A_FMA64(k) "v_fma_f64 %" #k ", %" #k ", %8, %9\n"
 #define A_MUL64(k) "v_mul_f64 %" #k ", %" #k ", %8\n"
 #define A_ADD64(k) "v_add_f64 %" #k ", %" #k ", %9\n"
+#define A_MADI64(k) "v_mad_i64_i32 %" #k ", vcc, %10, %11, %" #k "\n"
+#define A_MADU64(k) "v_mad_u64_u32 %" #k ", vcc, %10, %11, %" #k "\n"
+#define A_LSHLADD64(k) "v_lshl_add_u64 %" #k ", %" #k ", 2, %8\n"
+#define A_LSHL64(k) "v_lshlrev_b64 %" #k ", 1, %" #k "\n"
+#define A_CVTF64F32(k) "v_cvt_f64_f32 %" #k ", %10\n"
+#define A_CVTF64I32(k) "v_cvt_f64_i32 %" #k ", %10\n"
+#define A_CVTF32F64(k) "v_cvt_f32_f64 %" #k ", %10\n"
 
 KERNEL_F32(fma, S8(A_FMA))
 KERNEL_F32(mul, S8(A_MUL))
@@ -149,6 +199,7 @@ KERNEL_F32(cndmask, S8(A_CNDMASK))
 KERNEL_F32(cmp, S8(A_CMP))
 KERNEL_F32(cvt_f32_ubyte, S8(A_CVTUB))
 KERNEL_F32(cvt_i32_f32, S8(A_CVTI))
+KERNEL_F32(cvt_f32_i32, S8(A_CVTFI))
 KERNEL_F32(div_scale, S8(A_DIVSCALE))
 KERNEL_F32(div_fmas, S8(A_DIVFMAS))
 KERNEL_F32(div_fixup, S8(A_DIVFIXUP))
@@ -179,6 +230,13 @@ KERNEL_PK(pk_fma, S8(A_PKFMA))
 KERNEL_F64(fma_f64, S8(A_FMA64))
 KERNEL_F64(mul_f64, S8(A_MUL64))
 KERNEL_F64(add_f64, S8(A_ADD64))
+KERNEL_64X(mad_i64_i32, S8(A_MADI64))
+KERNEL_64X(mad_u64_u32, S8(A_MADU64))
+KERNEL_64X(lshl_add_u64, S8(A_LSHLADD64))
+KERNEL_64X(lshlrev_b64, S8(A_LSHL64))
+KERNEL_64X(cvt_f64_f32, S8(A_CVTF64F32))
+KERNEL_64X(cvt_f64_i32, S8(A_CVTF64I32))
+KERNEL_32X(cvt_f32_f64, S8(A_CVTF32F64))
 
 // compiler-expanded sequences, as the render kernel uses them (-ffp-contract=off): 8 independent chains x 4
 __global__ __launch_bounds__(64, 8) void k_ieee_div(float* out, int iters, unsigned long long* stamp)
@@ -305,6 +363,8 @@ static const Entry entries[] = {
     E(lshl_or, 32, "v_lshl_or_b32"), E(cvt_f32_f16, 32, "v_cvt_f32_f16"), E(cmp_e64, 32, "v_cmp_lt_f32_e64 -> SGPR pair"),
     E(pk_mul, 32, "v_pk_mul_f32 (2 results per lane)"), E(pk_add, 32, "v_pk_add_f32"), E(pk_fma, 32, "v_pk_fma_f32"),
     E(fma_f64, 32, "v_fma_f64"), E(mul_f64, 32, "v_mul_f64"), E(add_f64, 32, "v_add_f64"),
+    E(mad_i64_i32, 32, "v_mad_i64_i32 (carry to vcc)"), E(mad_u64_u32, 32, "v_mad_u64_u32 (carry to vcc)"), E(lshl_add_u64, 32, "v_lshl_add_u64"), E(lshlrev_b64, 32, "v_lshlrev_b64"),
+    E(cvt_f64_f32, 32, "v_cvt_f64_f32"), E(cvt_f64_i32, 32, "v_cvt_f64_i32"), E(cvt_f32_f64, 32, "v_cvt_f32_f64"), E(cvt_f32_i32, 32, "v_cvt_f32_i32"),
     E(ieee_div, 32, "1.0f / x as hipcc expands it (per division)"), E(ieee_sqrt, 32, "sqrtf(x) + 1 as hipcc expands it (per sqrt)"),
     E(pcg_draw, 32, "one PCG-RXS-M-XS draw + u01 conversion (per draw)"),
     E(ballot, 32, "v_cmp + s_bcnt1 + dependent update (per ballot)"), E(lds_stack, 16, "ds_write_b32 + ds_read_b32 pair, [level][lane] (per pair)"),
