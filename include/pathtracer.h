@@ -314,6 +314,13 @@ public:
     // the sample count are not touched.
     bool MultiHitRays(int num_rays, const float* origins, const float* dirs, const float* tmax, int max_hits, int32_t* count, int32_t* tri,
                       float* t, float* bary, int8_t* side);
+    // Extension: overlap queries (include/ptk.h ptk_overlap_boxes, ptk_overlap_spheres, host arrays, synchronous): for each closed
+    // box [lo, hi] / each sphere the number of triangles with index >= tri_from[i] (null: 0) that meet it, and the k (0 .. 16)
+    // smallest of their indices, -1 behind the last.  count: 1 per query, may be null with k > 0; tris: k per query, may be null
+    // with k == 0.  A geometric query: seed and materials take no part.  Valid after BuildBVH() with no resolution set; pending
+    // geometry edits apply as for ClosestPoints; the image and the sample count are not touched.
+    bool OverlapBoxes(int num, const float* lo, const float* hi, const int32_t* tri_from, int k, int32_t* count, int32_t* tris);
+    bool OverlapSpheres(int num, const float* centers, const float* radius, const int32_t* tri_from, int k, int32_t* count, int32_t* tris);
     // Extension: surface sampling (include/ptk.h ptk_sample_surface / ptk_surface_weights, host arrays, synchronous) at the class's
     // seed: num_samples points of the scene's surface, a triangle drawn in proportion to its area times its weight, the point
     // uniform on it; sample j is a function of (seed, key_base + j, sample) and the scene alone.  tri, material: 1 per sample; bary:

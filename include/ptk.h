@@ -584,6 +584,79 @@ int ptk_multihit_rays_device(ptk_ctx* ctx, int32_t num_rays, const float* d_orig
  * call launched none); waits for the call */
 int ptk_last_multihit_ms(ptk_ctx* ctx, float* ms);
 
+/* ---- overlap queries: the triangles that meet caller-supplied boxes and spheres (no counterpart in the reference) -------------------
+ * "Which triangles lie in this region of space": surface voxelisation and occupancy grids, the geometry near a probe, a texel or a
+ * tool, dirty regions after ptk_update_geometry, collision candidates - the broad-phase primitive.  A ray or a point asks the
+ * other queries; a REGION asks this one.  A GEOMETRIC query as ptk_closest_points: opacity maps, materials, seeds and keys take no
+ * part and no random draw is consumed.  Triangle t is (a, e1, e2) exactly as its intersection record holds it (a = its first
+ * vertex, e1 and e2 the second and the third vertex minus the first, the record packers' own float32 subtractions, kept current by
+ * ptk_update_geometry).  Nothing else of the triangle is used.
+ * THE ANSWER, the same form for both shapes.  Triangle t is CONSIDERED by query i when t >= tri_from[i]; tri_from == NULL or a
+ * negative value stands for 0.  count[i] = the number of considered triangles query i ACCEPTS - all of them: k does not cap it.
+ * tris[i][j] = the j-th smallest accepted considered index for j < min(k, count[i]), -1 beyond.  The region is fixed and the list
+ * is ordered by index, so: the first k' columns of the answer for k are the answer for k'; count does not depend on k; a caller
+ * pages through a long list by calling again with tri_from = last listed + 1; a box that contains the scene gives count =
+ * the number of triangles and tris = 0 .. k - 1.  0 <= k <= PTK_OVERLAP_MAX_K; with k == 0 tris is not touched and may be NULL.
+ * THE SPHERE RULE.  d2k is that of ptk_closest_points' rule for p = centers[i], bit for bit.  Triangle t is accepted when d2k is
+ * finite and d2k < radius[i] * radius[i] (one float32 product), STRICTLY.  A radius that is NaN, zero or negative accepts nothing;
+ * +inf accepts every triangle with a finite d2k.  Hence count[i] > 0 exactly when ptk_closest_points with max_dist = radius finds
+ * a triangle, and that triangle is in the list.
+ * THE BOX RULE: Akenine-Moeller's 13 separating axes over the CLOSED box [lo, hi], so touching counts.  Every operation below is one
+ * IEEE float32 operation, in the order written (the kernel exists once, in the exact arithmetic).  min and max ignore a NaN operand
+ * (fminf, fmaxf) and |x| clears the sign bit; cross is that of the crossings rule above.  A box with !(lo <= hi) on any axis accepts
+ * nothing (a NaN takes this arm); lo == hi is legal: a plane, a segment or a point.
+ *   c = (lo + hi) * 0.5;  h = (hi - lo) * 0.5;  v0 = a - c;  v1 = v0 + e1;  v2 = v0 + e2                      (per component)
+ *   box axes, j in x, y, z:
+ *     separated if  min(min(v0_j, v1_j), v2_j) > h_j  or  max(max(v0_j, v1_j), v2_j) < -h_j
+ *   plane:
+ *     n = cross(e1, e2);  d_m = (n.x*v_m.x + n.y*v_m.y) + n.z*v_m.z  for m = 0, 1, 2;  r = (h.x*|n.x| + h.y*|n.y|) + h.z*|n.z|
+ *     separated if  min(min(d_0, d_1), d_2) > r  or  max(max(d_0, d_1), d_2) < -r
+ *     (all three vertices, not d_0 alone: the n of a nearly collinear triangle is rounding noise, and a test against the plane
+ *     through v0 under that n would reject boxes that hold the triangle's far end; projecting every vertex keeps the axis a
+ *     separating axis whatever n is)
+ *   edge axes, f in (e1, e2 - e1, e2), j in x, y, z, with k = j+1 mod 3, l = j+2 mod 3:
+ *     p_m = v_m.l * f.k - v_m.k * f.l  for m = 0, 1, 2;   rr = h.k * |f.l| + h.l * |f.k|
+ *     separated if  min(min(p_0, p_1), p_2) > rr  or  max(max(p_0, p_1), p_2) < -rr
+ *   ACCEPTED when none of the 13 axes separates.
+ * Every comparison is false for a NaN, so a NaN or an overflowed product does not separate: non-finite arithmetic in the ten
+ * product axes (coordinates up to 2^61 make n . v0 overflow) can only accept more.  The three box axes use additions and
+ * comparisons alone, so "accepted implies the triangle's bounds meet the box up to rounding" holds for every finite input: the
+ * one-sided property the walk's prune rests on.  Degenerate triangles need no arm of their own: a zero n or f tests 0 > 0.
+ * The result does not depend on the builder that made the tree, on "bvh_leaf_max", on a refit, on "flat" (the calls always walk
+ * the BVH), on ptk_set_tile or on "contract", nor on how a query set is cut into calls (tests/test_gpu_overlap.py: array_equal
+ * with tests/overlap_rule.py).  A non-finite query makes THAT query's output unspecified and affects neither another query nor
+ * whether the call ends.
+ * The calls need a scene only - no camera, no frame - and read it as ptk_update_materials / ptk_update_geometry left it.  They
+ * touch no frame, adaptive, feature or bake state, stay legal after ptk_render_adaptive, and ptk_request_exit does not cut them.
+ *   ptk_overlap_boxes, ptk_overlap_spheres: host arrays, synchronous; the queries and the requested outputs are staged in device
+ *     memory for the length of the call.
+ *   the _device forms: every array in memory of this context's GPU, asynchronous on the context's stream (the caller's after
+ *     ptk_set_stream).  No host wait and no allocation of device memory inside the call.  The arrays must stay allocated until
+ *     the stream has passed the call.
+ * PTK_ERR_BAD_ARG: a null context, a call before ptk_upload_scene, num < 0, a null lo / hi / centers / radius with num > 0, k
+ * outside 0 .. PTK_OVERLAP_MAX_K, k > 0 with tris == NULL, count == NULL with k == 0; a refused call leaves the outputs alone.
+ * num == 0 is PTK_OK and does nothing.  A scene without triangles gives zeros and -1s, by fills, without a kernel.  PTK_ERR_LIMIT
+ * as for ptk_trace_rays.  Limits: one workgroup per 64 queries, in one launch. */
+#define PTK_OVERLAP_MAX_K 16
+int ptk_overlap_boxes(ptk_ctx* ctx, int32_t num, const float* lo /*[n][3]*/, const float* hi /*[n][3]*/, const int32_t* tri_from /*[n] or NULL*/,
+                      int32_t k, int32_t* count /*[n]*/, int32_t* tris /*[n][k]*/);
+int ptk_overlap_boxes_device(ptk_ctx* ctx, int32_t num, const float* d_lo, const float* d_hi, const int32_t* d_tri_from, int32_t k,
+                             int32_t* d_count, int32_t* d_tris);
+int ptk_overlap_spheres(ptk_ctx* ctx, int32_t num, const float* centers /*[n][3]*/, const float* radius /*[n]*/,
+                        const int32_t* tri_from /*[n] or NULL*/, int32_t k, int32_t* count /*[n]*/, int32_t* tris /*[n][k]*/);
+int ptk_overlap_spheres_device(ptk_ctx* ctx, int32_t num, const float* d_centers, const float* d_radius, const int32_t* d_tri_from, int32_t k,
+                               int32_t* d_count, int32_t* d_tris);
+/* measurement hooks (tools/overlap_timing.py), not part of the feature.  The HIP-event time of the last overlap query's kernel (0
+ * where the call launched none); waits for the call */
+int ptk_last_overlap_ms(ptk_ctx* ctx, float* ms);
+/* ... and the work of a query: the counting variant of the kernel over queries in this GPU's memory (d_a, d_b = lo, hi under
+ * PTK_OVERLAP_BOX; centers, radius under PTK_OVERLAP_SPHERE), no outputs written.  stats = interior nodes fetched, triangle records
+ * tested, triangles accepted, and - boxes only, else 0 - records the three box axes did not separate, each summed over the
+ * queries.  Synchronous; allocates 32 B of device memory at its first call */
+#define PTK_OVERLAP_BOX 0
+#define PTK_OVERLAP_SPHERE 1
+int ptk_overlap_stats(ptk_ctx* ctx, int32_t shape, int32_t num, const float* d_a, const float* d_b, const int32_t* d_tri_from, uint64_t stats[4]);
+
 /* ---- surface sampling: area-weighted points on the scene's triangles (no counterpart in the reference) ----------------------------
  * Every other query starts from the caller's geometry and asks about the scene; this one gives points OF the scene's surface: point
  * clouds for learning and registration, light sampling by power, scattering, probe candidates near walls, bakes that need neither

@@ -121,6 +121,11 @@ int  pth_signed_distance(pth_tracer* t, int num_points, const float* points, con
  * output but one may be NULL */
 int  pth_multihit_rays(pth_tracer* t, int num_rays, const float* origins, const float* dirs, const float* tmax, int max_hits, int32_t* count,
                        int32_t* tri, float* hit_t, float* bary, int8_t* side);
+/* OverlapBoxes / OverlapSpheres (the triangles that meet each box [lo, hi] / each sphere, include/ptk.h ptk_overlap_boxes,
+ * ptk_overlap_spheres): 1 on success; tri_from may be NULL, tris with k == 0, count with k > 0 */
+int  pth_overlap_boxes(pth_tracer* t, int num, const float* lo, const float* hi, const int32_t* tri_from, int k, int32_t* count, int32_t* tris);
+int  pth_overlap_spheres(pth_tracer* t, int num, const float* centers, const float* radius, const int32_t* tri_from, int k, int32_t* count,
+                         int32_t* tris);
 /* SampleSurface / SetSurfaceWeights (area-weighted points on the scene's triangles at the tracer's seed, include/ptk.h
  * ptk_sample_surface / ptk_surface_weights): 1 on success; any output and the weights may be NULL */
 int  pth_sample_surface(pth_tracer* t, int num_samples, uint32_t key_base, uint32_t sample, int32_t* tri, float* bary, float* position,

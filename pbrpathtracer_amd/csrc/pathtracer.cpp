@@ -1246,6 +1246,28 @@ bool PathTracer::MultiHitRays(int num_rays, const float* origins, const float* d
     return rc == PTK_OK;
 }
 
+// The triangles that meet caller-supplied boxes / spheres (ptk_overlap_boxes, ptk_overlap_spheres), in the scene as the next
+// RenderFrame() would see it
+bool PathTracer::OverlapBoxes(int num, const float* lo, const float* hi, const int32_t* tri_from, int k, int32_t* count, int32_t* tris)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_overlap_boxes(m->ctx, num, lo, hi, tri_from, k, count, tris);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
+bool PathTracer::OverlapSpheres(int num, const float* centers, const float* radius, const int32_t* tri_from, int k, int32_t* count, int32_t* tris)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_overlap_spheres(m->ctx, num, centers, radius, tri_from, k, count, tris);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 bool PathTracer::ContainsPoints(int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside, int32_t* winding)
 {
     if (!m->scene_uploaded || !m->ensure_ctx()) return false;

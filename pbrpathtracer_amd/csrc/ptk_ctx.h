@@ -199,6 +199,11 @@ struct ptk_ctx {
     // ordered multi-hit queries (ptk_multihit_rays): two events around the last call's kernel, made by the first call
     ptk::Timer<2> ev_multihit;
 
+    // overlap queries (ptk_overlap_boxes, ptk_overlap_spheres): two events around the last call's kernel, made by the first call;
+    // the four counters of ptk_overlap_stats, made by its first call
+    ptk::Timer<2> ev_overlap;
+    ptk::Buf<unsigned long long> d_overlap_stats;
+
     // surface sampling (ptk_sample_surface, ptk_surface_weights).  The table, 8 B per triangle - the inclusive sums of the quantised
     // weights - with the 8 KiB coarse table behind it; the caller's weights (4 B per triangle) while some are set; the workgroup
     // sums of the scan; the reduction block of the build.  All made by the first use for a scene and freed with it.  surf_valid: the

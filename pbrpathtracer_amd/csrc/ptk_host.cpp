@@ -193,6 +193,14 @@ int pth_multihit_rays(pth_tracer* t, int num_rays, const float* origins, const f
 {
     return t->pt.MultiHitRays(num_rays, origins, dirs, tmax, max_hits, count, tri, hit_t, bary, side) ? 1 : 0;
 }
+int pth_overlap_boxes(pth_tracer* t, int num, const float* lo, const float* hi, const int32_t* tri_from, int k, int32_t* count, int32_t* tris)
+{
+    return t->pt.OverlapBoxes(num, lo, hi, tri_from, k, count, tris) ? 1 : 0;
+}
+int pth_overlap_spheres(pth_tracer* t, int num, const float* centers, const float* radius, const int32_t* tri_from, int k, int32_t* count, int32_t* tris)
+{
+    return t->pt.OverlapSpheres(num, centers, radius, tri_from, k, count, tris) ? 1 : 0;
+}
 int pth_sample_surface(pth_tracer* t, int num_samples, uint32_t key_base, uint32_t sample, int32_t* tri, float* bary, float* position,
                        float* normal, int32_t* material)
 {

@@ -38,7 +38,7 @@ HOST_SYMBOLS = [
     "pth_render_features", "pth_read_feature", "pth_pick", "pth_set_object_transform", "pth_trace_rays", "pth_get_camera",
     "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
-    "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points",
+    "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points", "pth_overlap_boxes", "pth_overlap_spheres",
     "pth_crossings_rays", "pth_contains_points", "pth_signed_distance", "pth_multihit_rays",
     "pth_sample_surface", "pth_set_surface_weights", "pth_surface_info",
     "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised", "pth_temporal_frame", "pth_read_temporal", "pth_get_view",
@@ -120,6 +120,8 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_intersect_rays.restype = i32; L.pth_intersect_rays.argtypes = [vp, i32, vp, vp, u32, u32, vp, vp, vp, vp]
         L.pth_occluded_rays.restype = i32; L.pth_occluded_rays.argtypes = [vp, i32, vp, vp, vp, u32, u32, vp]
         L.pth_closest_points.restype = i32; L.pth_closest_points.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+        for fn in (L.pth_overlap_boxes, L.pth_overlap_spheres):
+            fn.restype = i32; fn.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp]
         L.pth_crossings_rays.restype = i32; L.pth_crossings_rays.argtypes = [vp, i32, vp, vp, vp, vp, vp]
         L.pth_multihit_rays.restype = i32; L.pth_multihit_rays.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
         L.pth_sample_surface.restype = i32; L.pth_sample_surface.argtypes = [vp, i32, u32, u32, vp, vp, vp, vp, vp]
@@ -613,6 +615,37 @@ class PathTracer:
         return out
 
     ClosestPoints = closest_points
+
+    def _overlap(self, fn, who, a, b, width_b, k, tri_from):
+        """the host entry fn over queries a [n, 3], b [n, width_b]: (count [n], tris [n, k])"""
+        K = int(k)
+        if K < 0 or K > _ptk.OVERLAP_MAX_K:
+            raise _ptk.PtkError(f"{who}: k must be in 0 .. {_ptk.OVERLAP_MAX_K}")
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+        n = len(a)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        assert len(b) == n * width_b, "one box corner or radius per query"
+        tf = None if tri_from is None else np.ascontiguousarray(tri_from, dtype=np.int32).reshape(-1)
+        assert tf is None or len(tf) == n, "one tri_from per query"
+        out = (np.empty(n, np.int32), np.empty((n, K), np.int32))
+        if n and not fn(self.h, n, a.ctypes.data, b.ctypes.data, tf.ctypes.data if tf is not None else None, K, out[0].ctypes.data,
+                        out[1].ctypes.data if K else None):
+            raise _ptk.PtkError(who + " failed: " + self.LastError())
+        return out
+
+    def overlap_boxes(self, lo, hi, k: int = 0, tri_from=None):
+        """Extension: (count [n] int32, tris [n, k] int32) - how many triangles of index >= tri_from[i] (None: 0) meet the closed
+        box [lo[i], hi[i]], and the k (0 .. 16) smallest of their indices, -1 behind the last (include/ptk.h ptk_overlap_boxes).
+        Pending geometry edits apply as for RenderFrame()."""
+        return self._overlap(self.L.pth_overlap_boxes, "OverlapBoxes", lo, hi, 3, k, tri_from)
+
+    def overlap_spheres(self, centers, radius, k: int = 0, tri_from=None):
+        """Extension: overlap_boxes' answer for the spheres (centers[i], radius[i]): the triangles strictly nearer to the centre
+        than the radius under closest_points' rule (include/ptk.h ptk_overlap_spheres)."""
+        return self._overlap(self.L.pth_overlap_spheres, "OverlapSpheres", centers, radius, 1, k, tri_from)
+
+    OverlapBoxes = overlap_boxes
+    OverlapSpheres = overlap_spheres
 
     def crossings_rays(self, origins, dirs, tmax=None):
         """Extension: (front [n] int32, back [n] int32), how many triangles each ray crosses before tmax[i] (None: no bound) from

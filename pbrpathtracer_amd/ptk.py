@@ -172,6 +172,8 @@ SYMBOLS = [
     "ptk_crossings_rays", "ptk_crossings_rays_device", "ptk_contains_points", "ptk_contains_points_device",
     "ptk_inside_default_dirs", "ptk_signed_distance", "ptk_signed_distance_device", "ptk_last_crossings_ms",
     "ptk_multihit_rays", "ptk_multihit_rays_device", "ptk_last_multihit_ms",
+    "ptk_overlap_boxes", "ptk_overlap_boxes_device", "ptk_overlap_spheres", "ptk_overlap_spheres_device", "ptk_last_overlap_ms",
+    "ptk_overlap_stats",
     "ptk_surface_weights", "ptk_surface_weights_device", "ptk_sample_surface", "ptk_sample_surface_device", "ptk_surface_info",
     "ptk_last_surface_ms", "ptk_probe_surface_table", "ptk_probe_scan_u64",
     "ptk_denoise_planes", "ptk_denoise_planes_device", "ptk_denoise_frame", "ptk_read_denoised", "ptk_denoised_device_ptr",
@@ -313,6 +315,10 @@ def _load_locked() -> C.CDLL:
         for fn in (L.ptk_multihit_rays, L.ptk_multihit_rays_device):
             fn.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.ptk_last_multihit_ms.argtypes = [vp, fp]
+        for fn in (L.ptk_overlap_boxes, L.ptk_overlap_boxes_device, L.ptk_overlap_spheres, L.ptk_overlap_spheres_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp]
+        L.ptk_last_overlap_ms.argtypes = [vp, fp]
+        L.ptk_overlap_stats.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.POINTER(u64)]
         for fn in (L.ptk_surface_weights, L.ptk_surface_weights_device):
             fn.argtypes = [vp, vp]
         for fn in (L.ptk_sample_surface, L.ptk_sample_surface_device):
@@ -412,6 +418,8 @@ BAKE_ACCUMULATE, BAKE_BACK = 1, 2                                     # ptk_bake
 PROBES_ACCUMULATE = 1                                                 # ptk_bake_probes flags
 DENOISE_VARIANCE = 1                                                  # ptk_denoise_frame flags
 INSIDE_WINDING, INSIDE_PARITY = 0, 1                                  # ptk_contains_points / ptk_signed_distance modes
+OVERLAP_MAX_K = 16                                                    # PTK_OVERLAP_MAX_K: the most indices an overlap query lists per call
+OVERLAP_BOX, OVERLAP_SPHERE = 0, 1                                    # PTK_OVERLAP_BOX, PTK_OVERLAP_SPHERE (ptk_overlap_stats' shape)
 MULTIHIT_MAX = 16                                                     # PTK_MULTIHIT_MAX: the most entries ptk_multihit_rays keeps per ray
 SURFACE_SCAN_ITEMS = 4096                                             # PTK_SURFACE_SCAN_ITEMS: items per workgroup of the table's prefix sum
 INSIDE_MODES = {"winding": INSIDE_WINDING, "parity": INSIDE_PARITY}
@@ -1111,6 +1119,73 @@ class Context:
         t = C.c_float(0)
         self._chk(self.L.ptk_last_multihit_ms(self.h, C.byref(t)), "ptk_last_multihit_ms")
         return t.value
+
+    # ---- overlap queries ----------------------------------------------------------------------
+    def _overlap(self, name, a, b, width_b, k, tri_from):
+        """the entry `name` (host: numpy) or `name`_device (torch) over queries a [n, 3], b [n, width_b]: (count [n], tris [n, k])"""
+        K = int(k)
+        if K < 0 or K > OVERLAP_MAX_K:
+            raise PtkError(f"{name}: k must be in 0 .. {OVERLAP_MAX_K}")
+        if hasattr(a, "data_ptr"):
+            import torch
+            n = a.numel() // 3
+            out = (torch.empty((n,), dtype=torch.int32, device=a.device), torch.empty((n, K), dtype=torch.int32, device=a.device))
+            self._ray_tensors((a, b), n, ((torch.float32, 3), (torch.float32, width_b)))
+            if tri_from is not None:
+                self._ray_tensors((tri_from,), n, ((torch.int32, 1),))
+            if n:
+                self._chk(getattr(self.L, name + "_device")(self.h, n, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
+                                                            C.c_void_p(tri_from.data_ptr()) if tri_from is not None else None, K,
+                                                            C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()) if K else None),
+                          name + "_device")
+            return out
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+        n = len(a)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        assert len(b) == n * width_b, "one box corner or radius per query"
+        tf = None
+        if tri_from is not None:
+            tf = np.ascontiguousarray(tri_from, dtype=np.int32).reshape(-1)
+            assert len(tf) == n, "one tri_from per query"
+        out = (np.empty(n, np.int32), np.empty((n, K), np.int32))
+        if n:
+            self._chk(getattr(self.L, name)(self.h, n, a.ctypes.data, b.ctypes.data, tf.ctypes.data if tf is not None else None, K,
+                                            out[0].ctypes.data, out[1].ctypes.data if K else None), name)
+        return out
+
+    def overlap_boxes(self, lo, hi, k: int = 0, tri_from=None):
+        """ptk_overlap_boxes: (count [n] int32, tris [n, k] int32) for the closed boxes [lo[i], hi[i]] ([n, 3] float32 each) under
+        the 13-axis rule of include/ptk.h: count = how many triangles of index >= tri_from[i] (None: 0) meet the box - k does not
+        cap it -, tris = the k smallest of their indices ascending, -1 behind the last; 0 <= k <= OVERLAP_MAX_K.  A box with
+        !(lo <= hi) on some axis meets nothing.  Page through a long list with tri_from = last listed + 1 (overlap.all_in_boxes).
+        numpy in, numpy out through the host entry; torch in, torch out through ptk_overlap_boxes_device with no host copy."""
+        return self._overlap("ptk_overlap_boxes", lo, hi, 3, k, tri_from)
+
+    def overlap_spheres(self, centers, radius, k: int = 0, tri_from=None):
+        """ptk_overlap_spheres: overlap_boxes' answer for the spheres (centers[i], radius[i]) - [n, 3] and [n] float32: a triangle
+        is met when closest_points' squared distance from the centre is finite and strictly below radius^2; a NaN, zero or
+        negative radius meets nothing."""
+        return self._overlap("ptk_overlap_spheres", centers, radius, 1, k, tri_from)
+
+    def last_overlap_ms(self) -> float:
+        """HIP-event time of the last overlap_boxes / overlap_spheres call's kernel (0 where it launched none); waits for it."""
+        t = C.c_float(0)
+        self._chk(self.L.ptk_last_overlap_ms(self.h, C.byref(t)), "ptk_last_overlap_ms")
+        return t.value
+
+    def overlap_stats(self, shape, a, b, tri_from=None):
+        """ptk_overlap_stats (measurement hook): (interior nodes fetched, triangle records tested, triangles accepted, records the
+        three box axes did not separate - boxes only) by an overlap query of these torch tensors on the context's GPU (shape
+        OVERLAP_BOX: lo, hi; OVERLAP_SPHERE: centers, radius), summed over the queries; synchronous, writes no outputs."""
+        import torch
+        n = a.numel() // 3
+        self._ray_tensors((a, b), n, ((torch.float32, 3), (torch.float32, 3 if shape == OVERLAP_BOX else 1)))
+        if tri_from is not None:
+            self._ray_tensors((tri_from,), n, ((torch.int32, 1),))
+        got = (C.c_uint64 * 4)()
+        self._chk(self.L.ptk_overlap_stats(self.h, int(shape), n, C.c_void_p(a.data_ptr()) if n else None, C.c_void_p(b.data_ptr()) if n else None,
+                                           C.c_void_p(tri_from.data_ptr()) if tri_from is not None else None, got), "ptk_overlap_stats")
+        return tuple(int(v) for v in got)
 
     # ---- surface sampling ---------------------------------------------------------------------
     def set_surface_weights(self, weights=None):

@@ -13,6 +13,7 @@
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz [--layers K]
     python -m pbrpathtracer_amd.render scene.pts --distance-field 64 64 64 [--df-max-dist M] [--signed [--inside-mode parity]] -o field.npz
+    python -m pbrpathtracer_amd.render scene.pts --voxelize 64 64 64 [--solid] -o grid.npz
     python -m pbrpathtracer_amd.render scene.pts --point-cloud 100000 --spp 16 [--offset O] -o cloud.npz
     python -m pbrpathtracer_amd.render scene.pts --bake-lightmap 1024 --spp 64 [--bake-atlas] [--bake-offset F] [--bake-back]
                                                  [--denoise] [--dilate K] -o map.png [--npy map.npy]
@@ -91,6 +92,11 @@ have no such thing).  With --signed the .npz also holds that test: inside [NZ, N
 include/ptk.h ptk_contains_points, the built-in directions; --inside-mode winding, the default, or parity) and sdf = dist with its
 sign bit set where inside (ptk_signed_distance: -inf inside and beyond --df-max-dist); every other array is what it is without
 --signed, byte for byte.
+
+With --voxelize NX NY NZ the output is an .npz of a surface voxelisation over the same grid (overlap.voxel_occupancy through
+PathTracer.overlap_boxes, include/ptk.h ptk_overlap_boxes): occupancy [NZ, NY, NX] bool, True where a triangle meets the closed box
+that reaches half a spacing around the grid point, with origin and spacing; --solid also sets the voxels whose centre
+PathTracer.contains_points finds inside the closed geometry.
 
 The headless equivalent of the reference's Start button + Export (main.cpp:3563-3618, :760-771):
 LoadScene -> SendObjectsToPathTracer -> RenderFrame() x spp -> PNG (flipped to top-down)."""
@@ -190,6 +196,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--inside-mode", choices=("winding", "parity"), default="winding",
                     help="--signed: a ray votes inside when it crosses unequal numbers of back and front faces (winding: any consistently "
                          "wound closed mesh) or an odd number of faces (parity: closed meshes wound inconsistently)")
+    ap.add_argument("--voxelize", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
+                    help="instead of rendering a view, write which voxels of a grid of NX x NY x NZ voxels centred on the --distance-field "
+                         "grid's points hold surface; -o names an .npz with occupancy [NZ, NY, NX] bool, origin and spacing")
+    ap.add_argument("--solid", action="store_true", help="--voxelize: also set the voxels whose centre lies inside the closed geometry")
     return ap
 
 
@@ -389,6 +399,28 @@ def render_distance_field(pt, a) -> int:
                  side=face_side(verts, pos, point, tri).reshape(shape), **extra)
     print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {dims[0]}x{dims[1]}x{dims[2]} distance field, "
           f"{int((tri >= 0).sum())} points within reach: {t2 - t1:.3f} s -> {a.out}")
+    return 0
+
+
+def render_voxels(pt, a) -> int:
+    from .overlap import voxel_occupancy
+    from .probes import grid_over_bounds
+    dims = tuple(a.voxelize)
+    if min(dims) < 1:
+        print("error: --voxelize needs dims of at least 1", file=sys.stderr)
+        return 1
+    v = np.asarray(pt.StagedScene()["verts"], np.float64).reshape(-1, 3)
+    if not len(v):
+        print("error: --voxelize: the scene has no triangles", file=sys.stderr)
+        return 1
+    origin, spacing = grid_over_bounds(v.min(axis=0), v.max(axis=0), dims)
+    t1 = time.time()
+    occ = voxel_occupancy(pt, origin, spacing, dims, solid=a.solid)
+    t2 = time.time()
+    with open(a.out, "wb") as f:                # (np.savez would append .npz to another suffix)
+        np.savez(f, occupancy=occ, origin=origin, spacing=spacing)
+    print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {dims[0]}x{dims[1]}x{dims[2]} voxels, {int(occ.sum())} occupied: "
+          f"{t2 - t1:.3f} s -> {a.out}")
     return 0
 
 
@@ -704,6 +736,19 @@ def main(argv=None):
             return 1
         try:
             return render_point_cloud(pt, a)
+        except (RuntimeError, ValueError) as e:
+            print("error:", e, file=sys.stderr)
+            return 1
+    if a.solid and a.voxelize is None:
+        print("error: --solid goes with --voxelize", file=sys.stderr)
+        return 1
+    if a.voxelize is not None:
+        if a.bake_lightmap is not None or a.bake_probes is not None or a.distance_field is not None or a.equirect is not None or \
+                a.noise_threshold is not None or a.denoise:
+            print("error: --voxelize is a mode of its own", file=sys.stderr)
+            return 1
+        try:
+            return render_voxels(pt, a)
         except (RuntimeError, ValueError) as e:
             print("error:", e, file=sys.stderr)
             return 1
