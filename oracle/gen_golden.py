@@ -9,6 +9,10 @@ driving the reference's own code on synthetic inputs:
           SampleCircle, DirectIllumimation, Hit, glm TRS / Euler camera, LoadObject staging)
   tier T  draw-tape paths: mRng seeded, Trace run single-threaded, the float draws it consumed and
           the radiance it returned
+  tier F  whole frames on tape: RenderFrame on one worker, its draws in pixel order (tier_f: the micro scenes; tier_f2: the
+          scenes that take the arms of Trace those never do - `python -m oracle.gen_golden frames2`)
+          ... and tier_t2, paths aimed at panels (`python -m oracle.gen_golden paths2`); tests/test_reference_arms_cpu.py counts
+          which arms all the tapes together replay
   tier S  converged mean images (RenderFrame, OpenMP, as shipped)
 A fixture is data only (inputs + expected outputs); no reference text is stored.
 """
@@ -849,10 +853,202 @@ def tier_k_resize(ref: Ref, tmp: str):
     save("tier_k_resize.npz", names=np.array(RESIZE_CASES), **out)
 
 
+# --------------------------------------------------------------------------------------------
+# the second batch of tapes: the arms of Trace that the micro scenes never take (tests/test_reference_arms_cpu.py counts them).  The
+# scenes are those of tests/trace_edge_cases.py, which the GPU tests render against the oracle; here the REFERENCE traces them.
+
+
+def load_arrays(ref: Ref, arrays: dict, tmp: str, tag: str, depth: int, size, cam_pos, cam_rot, fovy: float, focal_dist: float,
+                camera_f: float) -> dict:
+    """Stage a scene given as flat arrays (the boundary's layout) in the reference, through its own loaders as far as they go: one OBJ
+    group per material that has triangles, SetMaterial, one PPM per texture (a texture of zero extent: a file that is not there).
+    What no OBJ text says exactly - vertex normals, uvs, the stored normal / tangent / bitangent, the smoothing flag - is written
+    after BuildBVH (ref_set_triangles), triangle by triangle as `arrays` holds them.  Returns the arrays as the reference now holds
+    them (its own triangle order)."""
+    n = len(arrays["verts"])
+    used = [int(m) for m in np.unique(arrays["material"])]
+    groups, mats = [], []
+    for m in used:
+        idx = np.nonzero(arrays["material"] == m)[0]
+        # (x negated: LoadObject negates it back, pathtracer.cpp:74)
+        groups.append(S.MeshGroup(f"m{m}", arrays["verts"][idx].reshape(-1, 3) * np.array([-1.0, 1.0, 1.0]), np.arange(3 * len(idx)).reshape(-1, 3),
+                                  uvs=np.nan_to_num(arrays["uvs"][idx].reshape(-1, 2).astype(np.float64), nan=0.0, posinf=0.0, neginf=0.0),
+                                  normals=np.nan_to_num(arrays["normals"][idx].reshape(-1, 3).astype(np.float64))))
+        r = arrays["materials"][m]
+        d = S.MaterialDesc(type=int(r["type"]), diffuse=tuple(float(x) for x in r["diffuse"]), specular=tuple(float(x) for x in r["specular"]),
+                           emissive=tuple(float(x) for x in r["emissive"]), emissive_intensity=float(r["emissive_intensity"]),
+                           roughness=float(r["roughness"]), reflectiveness=float(r["reflectiveness"]), translucency=float(r["translucency"]),
+                           ior=float(r["ior"]))
+        for s, slot in enumerate(S.TEX_SLOTS):
+            t = int(r["tex"][s])
+            if t < 0:
+                continue
+            w, h, off = (int(x) for x in arrays["textures"][t])
+            p = os.path.join(tmp, f"{tag}_tex{t}.ppm")
+            if w > 0 and h > 0:
+                img = arrays["texels"][off:off + 4 * w * h].reshape(h, w, 4)
+                # (a PPM has no alpha: stb_image fills in 255, whatever `arrays` held - Trace reads no alpha)
+                S.write_ppm(p, img[..., :3])
+            else:
+                p = os.path.join(tmp, f"{tag}_tex{t}_not_there.ppm")
+            d.textures[slot] = p
+        mats.append(d)
+    sc = S.SceneDesc(trace_depth=depth, width=size[0], height=size[1], focal_dist=focal_dist, camera_f=camera_f)
+    sc.cam_pos = cam_pos; sc.cam_rot = cam_rot
+    obj = os.path.join(tmp, tag + ".obj")
+    S.write_obj(obj, groups)
+    sc.objects.append(S.ObjectDesc(obj, tag, [S.ElementDesc(g.name, m) for g, m in zip(groups, mats)]))
+    ref.load_scene(sc)
+    ref.lib.ref_set_projection.argtypes = [C.c_float, C.c_float]
+    ref.lib.ref_set_projection(S.PTS_FOCAL, fovy)
+    t = ref.triangles()
+    assert len(t) == n
+    key = lambda v: tuple(float(x) + 0.0 for x in v)
+    where = {key(arrays["verts"][i]): i for i in range(n)}
+    assert len(where) == n, "coincident triangles cannot be told apart"
+    src = np.array([where[key(t[i, 0:9])] for i in range(n)])
+    t[:, 9:18] = arrays["normals"][src]; t[:, 18:24] = arrays["uvs"][src]; t[:, 24:33] = arrays["tbn"][src]
+    t[:, 33] = arrays["smoothing"][src]
+    ref.lib.ref_set_triangles(_fp(t))
+    out = arrays_from_ref(ref, sc)
+    assert np.array_equal(out["tbn"], arrays["tbn"][src], equal_nan=True) and np.array_equal(out["uvs"], arrays["uvs"][src], equal_nan=True)
+    return out, sc
+
+
+# the panel scenes' camera (trace_edge_cases.CAM: at (3, 0, 0), looking along -x, fovy 40) at an irrational pose
+PANEL_CAM = dict(cam_pos=(3.0137, 0.0071, 0.0053), cam_rot=(0.731, -90.417, 0.293), fovy=40.0, focal_dist=3.0)
+BOX_CAM = dict(cam_pos=(0.0137, 0.0071, -3.5), cam_rot=(0.731, -0.417, 0.293), fovy=40.0, focal_dist=3.5)
+
+
+def bright_scene():
+    """trace_edge_cases.rr_cap("textured"): the Cornell box with walls brighter than Russian roulette's cap - and here the walls
+    half mirrors, so that a path meets the roulette at hit after hit (a mirror bounce does not count towards the depth limit,
+    pathtracer.cpp:625) until a draw kills it; on four walls of five every kill is one that only the cap explains."""
+    import trace_edge_cases as TE
+    a, _ = TE.rr_cap("textured")
+    m = a["materials"]
+    for k, d in enumerate(((1.0, 1.0, 1.0), (1.5, 1.2, 1.0), (0.97, 0.97, 0.97), (0.2, 1.0, 0.1), (4.0, 4.0, 4.0))):
+        m["diffuse"][k] = d
+    m["reflectiveness"][:5] = 0.85; m["roughness"][:5] = 0.0; m["specular"][:5] = (0.9, 0.85, 0.8)
+    return a
+
+
+def edges_scene():
+    """Panels of ONE material that carries all five replayable maps, at texture coordinates that are not finite (the lower clamp
+    of tex2d: (int)NaN is INT_MIN, and 4 * (INT_MIN * w + INT_MIN) wraps to texel 0 of the row / the image in the reference as
+    compiled - the texel the oracle clamps to), their normal map with z <= 0 in its first column and row (nt.z clamped), and five
+    materials with one map each whose file is not there."""
+    import trace_edge_cases as TE
+    nan, inf = np.float32(np.nan), np.float32(np.inf)
+    mats = TE._materials(6)
+    mats["reflectiveness"] = 0.5; mats["roughness"] = 0.5
+    mats["tex"][0, :5] = np.arange(5)
+    for s in range(5):
+        mats["tex"][1 + s, s] = 5
+    images = [TE.edge_texture(5, 7, s) for s in range(5)] + [np.zeros((0, 0, 4), np.uint8)]
+    panels = [dict(material=0, uv=uv) for uv in ((nan, 0.3), (0.3, nan), (inf, nan), (0.3, 0.3))] + [dict(material=1 + s) for s in range(5)]
+    return TE.panel_scene(panels, mats, images, wall=False)        # (no wall: the draws go to the panels)
+
+
+def open_scene():
+    """trace_edge_cases.lost_light with a light that has an area: edges of 1e-3, so |a| <= 1e-6 < EPS in IntersectTriangle and no ray
+    ever hits it - every shadow ray leaves the scene, which counts as lit (pathtracer.cpp:522-526)"""
+    import trace_edge_cases as TE
+    a, _ = TE.lost_light()
+    c = np.array([4.0, 0.5, 0.25])
+    a["verts"][6] = np.stack([c, c + [0.0, 1e-3, 0.0], c + [0.0, 0.0, 1e-3]]).astype(np.float32).reshape(9)
+    return a
+
+
+def _band_scene(glass: bool):
+    """Two materials whose every hit samples about a normal - (glass) rough glass that never transmits, so that a refraction ends in the
+    diffuse sampler - on panels whose stored normal has |n.x| in the band between the two sampler thresholds, at the pole, and at the
+    pole with the shading normal (smoothed; mapped) in the band.  -> (arrays, number of panels)"""
+    import trace_edge_cases as TE
+    m = TE._materials(2)
+    m["type"] = 1 if glass else 0
+    m["reflectiveness"] = 0.5; m["roughness"] = (1.0, 0.5); m["translucency"] = 0.0; m["diffuse"] = (0.95, 0.9, 0.85)
+    mapped = m.copy(); mapped["tex"][:, 1] = 0
+    img = np.zeros((1, 1, 4), np.uint8); img[...] = (128, 128, 255, 255)
+    panels = []
+    for k in range(2):
+        panels += [dict(material=k, nrm=nrm) for nrm in TE._band_normals() if TE.band_class(nrm[0]) != "below"]
+        a = np.float32(1.0 - 5e-6); v = (a, np.float32(np.sqrt(1.0 - float(a) ** 2)), np.float32(0))      # as TE.shading_band_panels
+        panels.append(dict(material=k, vnormals=np.tile(np.array(v, np.float32), 3)))
+        panels.append(dict(material=k + 2, tbn_tail=(0, 0.5, 0, 0, 0, 0.5), uv=(0.5, 0.5)))
+    return TE.panel_scene(panels, np.concatenate([m, mapped]), [img]), len(panels)
+
+
+def record_frame(ref: Ref, name: str, arr: dict, sc, size, seed: int):
+    W, H = size
+    cam, proj = camera_dict(ref)
+    ref.lib.ref_seed(seed)
+    tape = ref.peek_tape(W * H * 300)
+    ref.lib.ref_mark()
+    ref.render(1, threads=4)
+    nd = ref.lib.ref_draws_since_mark(len(tape))
+    assert nd > 0
+    save(f"tier_f_{name}.npz", width=np.int32(W), height=np.int32(H), depth=np.int32(sc.trace_depth), cam=cam, proj=proj,
+         focal_dist=np.float32(sc.focal_dist), aperture=np.float32(np.float32(S.PTS_FOCAL) / np.float32(sc.camera_f)), tape=tape[: nd + 8],
+         ndraws=np.int32(nd), total=ref.total(W, H), rgb8=ref.rgb8(W, H), **scene_arrays_dict(arr))
+    print("  frame", name, (W, H), "draws", nd)
+
+
+def record_paths(ref: Ref, name: str, arr: dict, depth: int, ro, rd, seed0: int):
+    tapes, counts, rad = [], [], np.zeros((len(ro), 3), np.float32)
+    for i in range(len(ro)):
+        ref.lib.ref_seed(seed0 + i)
+        t = ref.peek_tape(4096)
+        ref.lib.ref_mark()
+        rad[i] = ref.trace(ro[i], rd[i])
+        nd = ref.lib.ref_draws_since_mark(4096)
+        assert nd >= 0
+        counts.append(nd); tapes.append(t[: nd + 4])
+    offs = np.concatenate([[0], np.cumsum([len(t) for t in tapes])]).astype(np.int64)
+    save(f"tier_t_{name}.npz", depth=np.int32(depth), ro=ro, rd=rd, radiance=rad, tape=np.concatenate(tapes), tape_off=offs,
+         ndraws=np.array(counts, np.int32), **scene_arrays_dict(arr))
+    print("  paths", name, len(ro), "draws", int(np.sum(counts)))
+
+
+def rays_at_panels(arrays_in: dict, n_panels: int, per_panel: int, seed: int):
+    """per_panel rays from the panel camera's position to random points well inside each of the first n_panels triangles"""
+    rng = np.random.default_rng(seed)
+    v = arrays_in["verts"][:n_panels].reshape(n_panels, 3, 3).astype(np.float64)
+    b = rng.dirichlet((2.0, 2.0, 2.0), (n_panels, per_panel))
+    target = np.einsum("krj,kjc->krc", b, v).reshape(-1, 3)
+    ro = np.tile(np.array(PANEL_CAM["cam_pos"], np.float32), (len(target), 1))
+    rd = target - ro
+    return ro, (rd / np.linalg.norm(rd, axis=1, keepdims=True)).astype(np.float32)
+
+
+def tier_f2(ref: Ref, tmp: str):
+    """Whole frames, as tier_f records them (one worker, the irrational pose), of the scenes that take what tier_f's four never do.
+    (Seeds: none had to be replaced - every frame replayed bit for bit with libm's sin / cos and within 1e-5 with the polynomial.
+    A second run writes the same tape and the same image; only the order of the scene's triangles follows the reference's per-run
+    random tree, as in every fixture here.)"""
+    import trace_edge_cases as TE
+    for name, arrays, cam, size, depth, camf, seed in [
+            ("bright", bright_scene(), BOX_CAM, (30, 26), 1, 1.0e9, 801),                  # the cap of Russian roulette
+            ("nolights", TE.no_lights()[0], PANEL_CAM, (16, 12), 3, 4.0, 802),             # nothing emits
+            ("open", open_scene(), PANEL_CAM, (20, 14), 3, 1.0e9, 803),                    # shadow rays that miss everything
+            ("edges", edges_scene(), PANEL_CAM, (56, 42), 1, 2.0, 804)]:                   # non-finite uvs, files that are not there
+        arr, sc = load_arrays(ref, arrays, tmp, name, depth, size, camera_f=camf, **cam)
+        record_frame(ref, name, arr, sc, size, seed)
+
+
+def tier_t2(ref: Ref, tmp: str):
+    """Draw-tape paths, as tier_t records them, aimed at panels: where a frame would spend its draws on the wall behind them."""
+    for name, (arrays, n_panels), per_panel, seed in [("band_opaque", _band_scene(False), 18, 41), ("band_glass", _band_scene(True), 18, 42)]:
+        arr, sc = load_arrays(ref, arrays, tmp, name, 1, (8, 8), camera_f=1.0e9, **PANEL_CAM)
+        ro, rd = rays_at_panels(arrays, n_panels, per_panel, seed)
+        record_paths(ref, name, arr, 1, ro, rd, 52000 + 1000 * seed)
+
+
 def main():
     ref = Ref()
     with tempfile.TemporaryDirectory() as tmp:
-        only = {"frames": tier_f, "psd_pic": tier_k_images_psd_pic, "obj_variants": tier_k_obj_variants, "jpeg_sampling": tier_k_images_jpeg_sampling}
+        only = {"frames": tier_f, "psd_pic": tier_k_images_psd_pic, "obj_variants": tier_k_obj_variants, "jpeg_sampling": tier_k_images_jpeg_sampling,
+                "frames2": tier_f2, "paths2": tier_t2}
         if len(sys.argv) > 1 and sys.argv[1] in only:          # only one of the fixtures added last (the others stay as committed)
             only[sys.argv[1]](ref, tmp)
             return
@@ -865,6 +1061,8 @@ def main():
         tier_k_scene(ref, tmp)
         tier_t(ref, tmp)
         tier_f(ref, tmp)
+        tier_f2(ref, tmp)
+        tier_t2(ref, tmp)
         tier_s(ref, tmp)
 
 

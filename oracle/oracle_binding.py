@@ -219,6 +219,38 @@ class Oracle:
         n = self.lib.orc_render_tape(self.h, C.byref(cam), width, height, depth, self._p(tape), len(tape), self._p(total))
         return total, n
 
+    def _arm_names(self):
+        L = self.lib
+        L.orc_arm_name.restype = C.c_char_p
+        L.orc_arm_name.argtypes = [C.c_int]
+        return [L.orc_arm_name(i).decode() for i in range(L.orc_arm_count())]
+
+    def render_tape_census(self, cam: CameraC, width, height, depth, tape):
+        """render_tape that also counts the arms the replay takes (as render_census does for render): (total, draws consumed,
+        dict arm name -> count)."""
+        total = np.zeros((height, width, 3), dtype=np.float32)
+        tape = np.ascontiguousarray(tape, np.float32)
+        names = self._arm_names()
+        arms = np.zeros(len(names), np.int64)
+        self.lib.orc_render_tape_census.restype = C.c_int
+        self.lib.orc_render_tape_census.argtypes = [C.c_void_p, C.POINTER(CameraC), C.c_int, C.c_int, C.c_int, _f, C.c_int, _f, C.c_void_p]
+        n = self.lib.orc_render_tape_census(self.h, C.byref(cam), width, height, depth, self._p(tape), len(tape), self._p(total),
+                                            arms.ctypes.data)
+        return total, n, {k: int(v) for k, v in zip(names, arms)}
+
+    def trace_tape_census(self, ro, rd, depth, tape, mode=2):
+        """trace_tape that also counts the arms the replay takes: (radiance, draws consumed, dict arm name -> count)."""
+        ro = np.asarray(ro, np.float32); rd = np.asarray(rd, np.float32)
+        tape = np.ascontiguousarray(tape, np.float32)
+        out = np.zeros(3, np.float32)
+        names = self._arm_names()
+        arms = np.zeros(len(names), np.int64)
+        self.lib.orc_trace_tape_census.restype = C.c_int
+        self.lib.orc_trace_tape_census.argtypes = [C.c_void_p, _f, _f, C.c_int, _f, C.c_int, C.c_int, _f, C.c_void_p]
+        n = self.lib.orc_trace_tape_census(self.h, self._p(ro), self._p(rd), depth, self._p(tape), len(tape), mode, self._p(out),
+                                           arms.ctypes.data)
+        return out, n, {k: int(v) for k, v in zip(names, arms)}
+
     def primary_dirs(self, cam: CameraC, width, height):
         out = np.zeros((height, width, 3), dtype=np.float32)
         self.lib.orc_primary_dirs(C.byref(cam), width, height, out.ctypes.data)

@@ -818,18 +818,55 @@ static v3 trace_rec(const orc_scene* s, v3 ro, v3 rd, int D, int depth, int iter
     return add(add(b.e, di), mulv(sub_, b.weight));
 }
 
+/* trace_rec() with the census: the same calls in the same order, so the same radiance bit for bit.  (A recursive function cannot
+ * be always-inlined with a literal NULL, so it is a copy, as trace_census is of trace; the walk is the tree's, as trace_rec's.) */
+static v3 trace_rec_census(const orc_scene* s, v3 ro, v3 rd, int D, int depth, int iter, int inside,
+                           rng_t* rng, uint32_t* ray, int nee_last, int64_t* cz)
+{
+    hit_t h; bounce_t b;
+    memset(&b, 0, sizeof b);
+    if (!closest_hit_census(s, ro, rd, rng, (*ray)++, &h, cz, 0)) return V(0.0f, 0.0f, 0.0f);
+    if (!shade_impl(s, ro, rd, &h, D, &depth, &iter, &inside, rng, &b, cz)) return V(0.0f, 0.0f, 0.0f);
+    if (!b.diffuse_bounce)
+        return add(b.e, mulv(trace_rec_census(s, b.p, b.dir, D, depth, iter, inside, rng, ray, nee_last, cz), b.weight));
+    v3 di, sub_;
+    if (nee_last)
+    {
+        sub_ = trace_rec_census(s, b.p, b.dir, D, depth, iter, inside, rng, ray, nee_last, cz);
+        di = direct_illumination_impl(s, b.p, b.n, b.diffuse, rng, ray, NULL, cz, 0);
+    }
+    else
+    {
+        di = direct_illumination_impl(s, b.p, b.n, b.diffuse, rng, ray, NULL, cz, 0);
+        sub_ = trace_rec_census(s, b.p, b.dir, D, depth, iter, inside, rng, ray, nee_last, cz);
+    }
+    return add(add(b.e, di), mulv(sub_, b.weight));
+}
+
 /* mode 0: iterative (NEE draws first); 1: recursive, NEE first; 2: recursive, NEE last */
-int orc_trace_tape(const orc_scene* s, const float* ro, const float* rd, int max_depth,
-                   const float* tape, int tape_len, int mode, float* out3)
+ORC_INLINE int trace_tape_impl(const orc_scene* s, const float* ro, const float* rd, int max_depth,
+                               const float* tape, int tape_len, int mode, float* out3, int64_t* cz)
 {
     rng_t r; rng_init(&r, 0, 0);
     r.tape = tape; r.tape_len = tape_len; r.tape_pos = 0;
     v3 c;
     uint32_t ray = 0;
-    if (mode == 0) c = trace(s, ld3(ro), ld3(rd), max_depth, &r);
-    else c = trace_rec(s, ld3(ro), ld3(rd), max_depth, 0, 0, 0, &r, &ray, mode == 2);
+    if (mode == 0) c = cz ? trace_census(s, ld3(ro), ld3(rd), max_depth, &r, cz, 0) : trace(s, ld3(ro), ld3(rd), max_depth, &r);
+    else c = cz ? trace_rec_census(s, ld3(ro), ld3(rd), max_depth, 0, 0, 0, &r, &ray, mode == 2, cz)
+                : trace_rec(s, ld3(ro), ld3(rd), max_depth, 0, 0, 0, &r, &ray, mode == 2);
     out3[0] = c.x; out3[1] = c.y; out3[2] = c.z;
     return r.tape_pos;
+}
+int orc_trace_tape(const orc_scene* s, const float* ro, const float* rd, int max_depth,
+                   const float* tape, int tape_len, int mode, float* out3)
+{
+    return trace_tape_impl(s, ro, rd, max_depth, tape, tape_len, mode, out3, NULL);
+}
+/* ... ADDING the arms the replay takes to arms[ORC_ARM_N] (the caller zeroes them: a tier-T fixture is many paths) */
+int orc_trace_tape_census(const orc_scene* s, const float* ro, const float* rd, int max_depth,
+                          const float* tape, int tape_len, int mode, float* out3, int64_t* arms)
+{
+    return trace_tape_impl(s, ro, rd, max_depth, tape, tape_len, mode, out3, arms);
 }
 
 /* Counter-RNG radiance of sample `sample` of `pixel` from an explicit ray, iterative (mode 0) or
@@ -1160,7 +1197,8 @@ void orc_render_census(const orc_scene* s, const orc_camera* cam, int W, int H, 
  * loop consumes them when it runs on one thread: rows top to bottom, columns left to right, per pixel the two draws of
  * SampleCircle (:736-737) and then the path's (recursive form, g++'s operand order).  Adds into `total` (rows bottom-up, :796)
  * and returns the number of draws consumed.  Test infrastructure for tools/fuzz_frame_vs_reference.py. */
-int orc_render_tape(const orc_scene* s, const orc_camera* cam, int W, int H, int D, const float* tape, int tape_len, float* total)
+ORC_INLINE int render_tape_impl(const orc_scene* s, const orc_camera* cam, int W, int H, int D, const float* tape, int tape_len, float* total,
+                                int64_t* cz)
 {
     frame_t f; frame_setup(cam, W, H, &f);
     float* dirs = (float*)malloc((size_t)W * 3 * sizeof(float));
@@ -1181,12 +1219,22 @@ int orc_render_tape(const orc_scene* s, const orc_camera* cam, int W, int H, int
             camPos = add(camPos, add(muls(f.right, off[0]), muls(f.up, off[1])));
             v3 rayDir = normalize(sub(focalPoint, camPos));
             uint32_t ray = 0;
-            v3 color = trace_rec(s, camPos, rayDir, D, 0, 0, 0, &r, &ray, 1);
+            v3 color = cz ? trace_rec_census(s, camPos, rayDir, D, 0, 0, 0, &r, &ray, 1, cz) : trace_rec(s, camPos, rayDir, D, 0, 0, 0, &r, &ray, 1);
             total[px] += color.x; total[px + 1] += color.y; total[px + 2] += color.z;
         }
     }
     free(dirs);
     return r.tape_pos;
+}
+int orc_render_tape(const orc_scene* s, const orc_camera* cam, int W, int H, int D, const float* tape, int tape_len, float* total)
+{
+    return render_tape_impl(s, cam, W, H, D, tape, tape_len, total, NULL);
+}
+/* ... ADDING the arms the replay takes to arms[ORC_ARM_N] */
+int orc_render_tape_census(const orc_scene* s, const orc_camera* cam, int W, int H, int D, const float* tape, int tape_len, float* total,
+                           int64_t* arms)
+{
+    return render_tape_impl(s, cam, W, H, D, tape, tape_len, total, arms);
 }
 
 

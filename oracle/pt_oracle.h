@@ -148,6 +148,9 @@ void orc_intersect_many(int64_t n, const float* ro, const float* rd, const float
  * `pixel += camRight*deltaX` arithmetic of pathtracer.cpp:755-766,782-785,814. */
 void orc_primary_dirs(const orc_camera* cam, int width, int height, float* out);
 int orc_render_tape(const orc_scene* s, const orc_camera* cam, int width, int height, int max_depth, const float* tape, int tape_len, float* total);
+/* orc_render_tape that also ADDS the arms the replay takes to arms[ORC_ARM_N] (not zeroed here): the same image, the same draws */
+int orc_render_tape_census(const orc_scene* s, const orc_camera* cam, int width, int height, int max_depth, const float* tape, int tape_len,
+                           float* total, int64_t* arms);
 
 /* Radiance of one path with the draws taken from `tape` (tier T).  Returns #draws consumed. */
 int orc_trace_tape(const orc_scene* s, const float* ro, const float* rd, int max_depth,
@@ -155,6 +158,9 @@ int orc_trace_tape(const orc_scene* s, const float* ro, const float* rd, int max
 /* mode 0 = iterative form (what orc_render and the HIP kernel compute), 1 = recursive form with
  * DirectIllumimation evaluated before the recursive Trace, 2 = recursive, Trace first (the order
  * g++ picked for the reference build the fixtures were recorded from). */
+/* orc_trace_tape that also ADDS the arms the replay takes to arms[ORC_ARM_N] (not zeroed here): the same radiance, the same draws */
+int orc_trace_tape_census(const orc_scene* s, const float* ro, const float* rd, int max_depth,
+                          const float* tape, int tape_len, int mode, float* out3, int64_t* arms);
 void orc_trace_counter(const orc_scene* s, const float* ro, const float* rd, int max_depth,
                        uint64_t seed, uint32_t pixel, uint32_t sample, int mode, float* out3);
 

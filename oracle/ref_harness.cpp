@@ -123,6 +123,25 @@ void ref_get_triangles(float* out)
     }
 }
 
+// The reverse, AFTER BuildBVH, for what no OBJ file can say exactly: the vertex normals, the uvs (a NaN, a value a decimal does not
+// round to), the stored normal / tangent / bitangent that Triangle::Init would compute (a normal with |n.x| between the two sampler
+// thresholds, pathtracer.cpp:606 / :618) and the smoothing flag, in ref_get_triangles' layout.  Vertices and ids stay: the tree's
+// boxes and its leaves' pointers were made from them.
+void ref_set_triangles(const float* in)
+{
+    for (size_t i = 0; i < g_pt.mTriangles.size(); i++)
+    {
+        Triangle& t = g_pt.mTriangles[i];
+        const float* o = in + i * 38;
+        glm::vec3* v3s[] = { &t.n1, &t.n2, &t.n3 };
+        for (int k = 0; k < 3; k++) *v3s[k] = glm::vec3(o[9 + k * 3], o[10 + k * 3], o[11 + k * 3]);
+        t.uv1 = glm::vec2(o[18], o[19]); t.uv2 = glm::vec2(o[20], o[21]); t.uv3 = glm::vec2(o[22], o[23]);
+        glm::vec3* w3s[] = { &t.normal, &t.tangent, &t.bitangent };
+        for (int k = 0; k < 3; k++) *w3s[k] = glm::vec3(o[24 + k * 3], o[25 + k * 3], o[26 + k * 3]);
+        t.smoothing = o[33] != 0.0f;
+    }
+}
+
 void ref_set_camera(const float* pos, const float* dir, const float* up)
 {
     g_pt.SetCamera(glm::vec3(pos[0], pos[1], pos[2]), glm::vec3(dir[0], dir[1], dir[2]),

@@ -1,4 +1,5 @@
-"""The arms of Trace that no golden, random or plain-frame scene takes (tests/trace_edge_cases.py; the census of
+"""The golden scenes of the registry (tests/trace_arms.py golden_scenes: every fixture the oracle is pinned to the reference on), and
+the arms of Trace that no golden, random or plain-frame scene takes (tests/trace_edge_cases.py; the census of
 tests/test_trace_arms_cpu.py shows that these scenes take them): Russian roulette's cap, both clamps of tex2d in all six slots,
 the band of |n.x| between the two sampler thresholds, texels of exactly 0 and 1, exact ties - each scene under every trace kernel
 it admits, asserted through ptk_trace_variant, every accumulator word == the CPU oracle's.  The texture edges also through the
@@ -81,6 +82,21 @@ def _check_scene(ctx, OB, scene):
 
 def _group(edge_scenes, prefix):
     return [s for n, s in edge_scenes.items() if n.startswith(prefix)]
+
+
+# ---- the golden scenes: every scene on which a tape pins the oracle to the reference -----------------------------------------------
+@pytest.fixture(scope="module")
+def golden_scenes():
+    return {s[0]: s + (TA.variants_admitted(s[1], s[2]),) for s in TA.golden_scenes()}
+
+
+@pytest.mark.parametrize("name", [s[0] for s in TA.golden_scenes()])
+def test_golden_scene_renders(ctx, oracle_mod, golden_scenes, name):
+    """the lens and the pinhole entry of every tier_s_* / tier_f_* fixture (tests/trace_arms.py golden_scenes), as registered: 64 x 48,
+    the fixture's depth, 8 samples - under every kernel the scene admits"""
+    scene = golden_scenes[name]
+    assert scene[3:5] + scene[6:8] == TA.GOLDEN_FRAME
+    assert _check_scene(ctx, oracle_mod, scene) == {"PLAIN": 4, "FLAT": 3, "BVH": 2}[scene[8][0]]
 
 
 # ---- renders ---------------------------------------------------------------------------------------------------------------------

@@ -53,14 +53,76 @@ def test_only_argued_arms_are_listed_unreachable():
 
 
 def test_every_scene_runs_on_the_kernel_the_registry_says():
-    for name, arrays, *_, variants in TA.registry():
-        assert variants[0] == TA.variant_of(arrays), name
+    for name, arrays, cam, *_, variants in TA.registry():
+        assert variants[0] == TA.variant_of(arrays, cam), name
         assert (len(arrays["verts"]) > 16) == (variants == ("BVH",)), name
     kinds = {name: variants for name, *_, variants in TA.edge_scenes()}
     assert kinds["rr_cap_plain_D1"][0] == "PLAIN" and kinds["rr_cap_textured_D1"][0] == "FLAT" and kinds["rr_cap_padded_D1"] == ("BVH",)
     assert kinds["render_ties_flat"][0] == "PLAIN" and kinds["render_ties_tree"] == ("BVH",)
     assert kinds["sampler_band_opaque_lobe"][0] == "PLAIN" and kinds["sampler_band_glass_lobe"][0] == "FLAT"
     assert kinds["sampler_band_all"] == ("BVH",) and kinds["tex_edges_uv_diffuse_3x2"] == ("BVH",)
+
+
+# ---- the registry is the tests ----------------------------------------------------------------------------------------------------------
+def _params(module, function):
+    """the parameter list of a parametrized test, read from its marks"""
+    import importlib
+    fn = getattr(importlib.import_module(module), function)
+    out = []
+    for m in getattr(fn, "pytestmark", []):
+        if m.name == "parametrize":
+            out += list(m.args[1])
+    return out
+
+
+def test_the_registrys_golden_entries_are_the_golden_scenes():
+    import glob
+    import os
+    gold = TA.golden_scenes()
+    reg = [s for s in TA.registry() if s[0].startswith(("tier_s_", "tier_f_"))]
+    assert [s[0] for s in reg] == [s[0] for s in gold]
+    for r, g in zip(reg, gold):
+        assert r[3:8] == g[3:8] and r[3:5] + r[6:8] == TA.GOLDEN_FRAME, r[0]
+        assert all(np.array_equal(r[2][k], g[2][k]) for k in g[2]) and set(r[2]) == set(g[2]), r[0]
+        assert all(np.array_equal(r[1][k], g[1][k], equal_nan=k in ("uvs", "tbn", "normals")) for k in g[1]), r[0]
+        assert r[8] == TA.variants_admitted(g[1], g[2]), r[0]
+    # every fixture that holds a camera is there, with and without its lens
+    with_cam = [os.path.basename(p)[:-4] for p in sorted(glob.glob(os.path.join(TA.GOLDEN, "tier_[sf]_*.npz"))) if "cam" in TA.load_golden(os.path.basename(p)).files]
+    assert sorted(s[0] for s in gold) == sorted(n + tail for n in with_cam for tail in ("_lens", "_pinhole")) and len(with_cam) >= 11
+    assert all(s[2]["aperture"] == 0.0 for s in gold if s[0].endswith("_pinhole")) and all(s[2]["aperture"] > 0.0 for s in gold if s[0].endswith("_lens"))
+    # a plain scene runs on the PLAIN kernel only without a lens
+    kinds = {r[0]: r[8] for r in reg}
+    assert kinds["tier_f_cornell_pinhole"] == ("PLAIN", "FLAT", "BVH") and kinds["tier_f_cornell_lens"] == ("FLAT", "BVH")
+    # ... and tests/test_gpu_trace_arms.py renders exactly that list
+    assert _params("test_gpu_trace_arms", "test_golden_scene_renders") == [s[0] for s in gold]
+
+
+def test_no_registry_entry_is_without_a_rendering_test():
+    import test_gpu_plain_frames as PF
+    edge = {s[0] for s in TE.scenes()}
+    seen = set()
+    for name, *_ in TA.registry():
+        prefix = max((p for p in TA.RENDERED_BY if p and name.startswith(p)), key=len, default="")
+        assert prefix or name in edge, f"{name}: no test is named for it"
+        module, function = TA.RENDERED_BY[prefix]
+        params = _params(module, function)
+        if prefix in ("tier_s_", "tier_f_"):
+            ok = name in params
+        elif prefix in ("random_", "grazing_"):
+            ok = int(name[len(prefix):]) in [p[0] for p in params]
+        elif prefix == "plain_frames_":
+            ok = name[len(prefix):] in params or name[len(prefix):] in PF.moved_scenes()       # (the moved ones: test_table_follows_a_geometry_update)
+        elif prefix == "rr_cap_":
+            ok = name.split("_")[2] in params
+        elif prefix == "tex_edges_":
+            ok = name.split("_")[3] in params
+        elif prefix == "":
+            ok = any(name.startswith(p) for p, _ in params)
+        else:
+            ok = params == []                                                               # one scene, one unparametrized test
+        assert ok, (name, module, function)
+        seen.add(prefix)
+    assert seen == set(TA.RENDERED_BY)
 
 
 # ---- tex2d: the known answers --------------------------------------------------------------------------------------------------

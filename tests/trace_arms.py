@@ -13,19 +13,20 @@ VARIANTS = ("PLAIN", "FLAT", "BVH")
 FLOOR = 32           # every reachable arm, per variant, at least this often: an arm met a handful of times in one wave proves little
 
 
-def variant_of(arrays) -> str:
+def variant_of(arrays, cam=None) -> str:
     """the trace kernel a scene gets by the product's own rule: more than 16 triangles walk the tree, otherwise
-    ptk_scene_is_plain decides between the PLAIN and the generic FLAT kernel (no device needed)"""
+    ptk_scene_is_plain decides between the PLAIN and the generic FLAT kernel (no device needed) - and the PLAIN kernel starts from
+    the cached primary hits, which only a pinhole camera has: through a lens (cam["aperture"] != 0) a plain scene runs FLAT"""
     from pbrpathtracer_amd import ptk
     if len(arrays["verts"]) > 16:
         return "BVH"
-    return "PLAIN" if ptk.scene_is_plain(arrays) else "FLAT"
+    return "PLAIN" if ptk.scene_is_plain(arrays) and (cam is None or float(cam["aperture"]) == 0.0) else "FLAT"
 
 
-def variants_admitted(arrays):
+def variants_admitted(arrays, cam=None):
     """every kernel a scene can be made to run on: "flat" 0 sends a small scene down the tree, "plain_kernel" 0 a plain one through
     the generic FLAT kernel"""
-    v = variant_of(arrays)
+    v = variant_of(arrays, cam)
     return {"BVH": ("BVH",), "FLAT": ("FLAT", "BVH"), "PLAIN": ("PLAIN", "FLAT", "BVH")}[v]
 
 
@@ -35,13 +36,16 @@ def _golden_cam(z, aperture=None):
                 aperture=float(z["aperture"]) if aperture is None else aperture)
 
 
-def existing_scenes():
-    """(name, arrays, cam, W, H, D, spp, seed, variants) of what the parity tests from before the census render, at their sizes, each
-    under the kernel it gets by default"""
-    import test_gpu_edge_cases as EC
-    import test_gpu_plain_frames as PF
-    import test_gpu_random_scenes as RS
+GOLDEN_FRAME = (64, 48, 8, 1234)                     # W, H, spp, seed of every golden entry
+
+
+def golden_scenes():
+    """(name, arrays, cam, W, H, D, spp, seed) of every tier_s_* / tier_f_* fixture that holds a camera, found by glob: once at the fixture's
+    own aperture ("_lens") and once with none ("_pinhole"), at the fixture's depth.  tests/test_gpu_trace_arms.py renders exactly this
+    list, each entry under every kernel it admits - so every scene on which a tape pins the oracle to the reference also holds the
+    kernels to the oracle."""
     out = []
+    W, H, spp, seed = GOLDEN_FRAME
     for path in sorted(glob.glob(os.path.join(GOLDEN, "tier_s_*.npz")) + glob.glob(os.path.join(GOLDEN, "tier_f_*.npz"))):
         z = load_golden(os.path.basename(path))
         if "cam" not in z.files:
@@ -49,8 +53,18 @@ def existing_scenes():
         arrays = scene_from_golden(z)
         D = int(z["depth"]) if "depth" in z.files else 5
         name = os.path.basename(path)[:-4]
-        out.append((name + "_lens", arrays, _golden_cam(z), 64, 48, D, 8, 1234))             # test_gpu_parity
-        out.append((name + "_pinhole", arrays, _golden_cam(z, 0.0), 64, 48, D, 8, 1234))
+        out.append((name + "_lens", arrays, _golden_cam(z), W, H, D, spp, seed))
+        out.append((name + "_pinhole", arrays, _golden_cam(z, 0.0), W, H, D, spp, seed))
+    return out
+
+
+def existing_scenes():
+    """(name, arrays, cam, W, H, D, spp, seed, variants) of what the parity tests from before the census render, at their sizes, each
+    under the kernel it gets by default - and the golden entries, each under every kernel it admits"""
+    import test_gpu_edge_cases as EC
+    import test_gpu_plain_frames as PF
+    import test_gpu_random_scenes as RS
+    out = []
     params = [m for m in RS.test_random_scene_matches_oracle.pytestmark if m.name == "parametrize"][0].args[1]
     for seed, n_tris, tex in params:
         if n_tris >= 6000:
@@ -68,13 +82,27 @@ def existing_scenes():
     out.append(("no_lights_degenerate", a, cam, 48, 32, 6, 3, 5))
     z = load_golden("tier_s_cornell.npz")
     out.append(("empty", EC._empty_like(scene_from_golden(z)), EC._cam(z), 33, 17, 4, 3, 5))
-    return [s + ((variant_of(s[1]),),) for s in out]
+    return [s + (variants_admitted(s[1], s[2]),) for s in golden_scenes()] + [s + ((variant_of(s[1], s[2]),),) for s in out]
+
+
+# registry entry (by the prefix of its name) -> (test module, test function) that renders it.  tests/test_trace_arms_cpu.py checks every
+# entry of the registry against that function's own parameter list, so a scene cannot stay registered after its test is gone.
+RENDERED_BY = {
+    "tier_s_": ("test_gpu_trace_arms", "test_golden_scene_renders"), "tier_f_": ("test_gpu_trace_arms", "test_golden_scene_renders"),
+    "random_": ("test_gpu_random_scenes", "test_random_scene_matches_oracle"),
+    "grazing_": ("test_gpu_random_scenes", "test_grazing_light_hits_decide_shadow_rays_like_the_reference"),
+    "plain_frames_": ("test_gpu_plain_frames", "test_plain_equals_generic_equals_oracle"),
+    "no_lights_degenerate": ("test_gpu_edge_cases", "test_no_lights_and_degenerate_triangles"),
+    "empty": ("test_gpu_edge_cases", "test_empty_scene_renders_black"),
+    "rr_cap_": ("test_gpu_trace_arms", "test_rr_cap_renders"), "tex_edges_": ("test_gpu_trace_arms", "test_tex_edges_renders"),
+    "": ("test_gpu_trace_arms", "test_other_edge_scene_renders"),                  # every other edge scene, by its prefix there
+}
 
 
 def edge_scenes():
     """the scenes of tests/trace_edge_cases.py, each under every kernel it admits (tests/test_gpu_trace_arms.py renders them so)"""
     import trace_edge_cases as TE
-    return [s + (variants_admitted(s[1]),) for s in TE.scenes()]
+    return [s + (variants_admitted(s[1], s[2]),) for s in TE.scenes()]
 
 
 def registry():
