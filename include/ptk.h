@@ -1736,7 +1736,8 @@ int ptk_probe_direct(ptk_ctx* ctx, int n, const float* points, const float* norm
 /* the kernels' arithmetic helpers on an array, as the build the "contract" option selects compiles them: op 0 = the short
  * reciprocal (valid for 2^-126 <= |a| <= 2^126), 1 = the reciprocal with IEEE special cases, 2 = the short square root,
  * 3 = the factor normalize() multiplies by (1 / sqrt(x); contract 2: the hardware's rsq), 4 / 5 = sin / cos of the fixed
- * polynomial for angles in [0, 2 pi].  In the exact build ops 0-3 return the bits of the IEEE-754 operation the reference's
+ * polynomial for angles in [0, 2 pi], 6 = the square root from v_rsq_f32 as the cycle unit's shade block compiles op 2,
+ * 7 = op 3 over it.  In the exact build ops 0-3, 6 and 7 return the bits of the IEEE-754 operation the reference's
  * CPU code performs (1.0f / a, sqrtf(x)) and ops 4 / 5 those of the CPU oracle's polynomial. */
 int ptk_probe_math(ptk_ctx* ctx, int op, int n, const float* in, float* out);
 /* the surface sampler's table as ptk_sample_surface would use it now (built where missing or stale): incl[triangles] */

@@ -52,7 +52,7 @@ int ptk_probe_direct(ptk_ctx* c, int n, const float* pts, const float* normals, 
 
 int ptk_probe_math(ptk_ctx* c, int op, int n, const float* in, float* out)
 {
-    if (!c || op < 0 || op > 5 || n < 0 || (n > 0 && (!in || !out))) return PTK_ERR_BAD_ARG;
+    if (!c || op < 0 || op > 7 || n < 0 || (n > 0 && (!in || !out))) return PTK_ERR_BAD_ARG;
     if (n == 0) return PTK_OK;
     HIPCHK(c, hipSetDevice(c->device));
     Stage s(c);

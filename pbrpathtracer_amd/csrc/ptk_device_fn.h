@@ -21,6 +21,7 @@
 #else
 #define PTK_SHADE32 0
 #endif
+// ... and its square roots: sqrt_ieee_rsq below.
 
 namespace ptk {
 #if PTK_CONTRACT >= 2
@@ -83,10 +84,13 @@ __device__ __forceinline__ float rcp_ieee_any(float a)
 // exact_math.json): identical to sqrtf for +0, +inf and every x >= 2^-104 (the largest input that differs is 0x0b6e9372,
 // where the residuals underflow); anything below - a positive length under 2^-52, which no scene produces, and negative
 // or NaN arguments - takes the compiler's expansion behind a branch that is practically never taken.
+__device__ __forceinline__ float sqrt_ieee_rsq(float x);
 __device__ __forceinline__ float sqrt_ieee(float x)
 {
 #if PTK_CONTRACT >= 2
     return __builtin_amdgcn_sqrtf(x);
+#elif PTK_SHADE32
+    return sqrt_ieee_rsq(x);                    // the cycle unit's shade block: the same bits from the shorter sequence below
 #else
     if (__builtin_expect(!(x >= 0x1p-104f), 0)) return sqrtf(x);          // (zero too: correct either way, and as rare)
     float s = __builtin_amdgcn_sqrtf(x);
@@ -96,6 +100,29 @@ __device__ __forceinline__ float sqrt_ieee(float x)
     return rp > 0.0f ? sp : s;
 #endif
 }
+// The same root from v_rsq_f32 (1 ulp): g = x * rsq(x) ~ sqrt(x), corrected once by its exact residual r = x - g * g (fma) times
+// h = rsq(x) / 2 ~ 1 / (2 sqrt(x)) - one transcendental, two multiplies and two fma, no compare and no select.  Enumerated over all
+// 2^32 bit patterns on the GPU WITH the range test in front (tools/microbench/exact_math.hip, profiles/r15/exact_math_rsq.json):
+// identical to sqrtf everywhere.  That is a fact about this hardware's v_rsq_f32, not about every 1-ulp rsq - a host model that
+// moves rsq by an ulp finds a few inputs where only the longer coupled form (g and h refined together by a Newton step first;
+// enumerated beside it, exact as well) holds - so the enumeration is the proof, and tests/test_gpu_sqrt_rsq.py holds this library's
+// code on every mantissa of eight binades.  The short form is exact for x in [2^-102, +inf) - below, the residual underflows - and
+// wrong for zero (rsq = inf) and for +inf (rsq = 0, g = NaN), so ONE test sends everything outside that interval - zeros, smaller
+// positives, +inf, negatives, NaNs - to the compiler's expansion behind the never-taken branch: as unsigned numbers the interval's
+// bit patterns are consecutive, one subtraction and one compare.  The cycle unit's sqrt_ieee is this function; every other unit
+// has it for the probe alone.
+__device__ __forceinline__ float sqrt_ieee_rsq(float x)
+{
+#if PTK_CONTRACT >= 2
+    return __builtin_amdgcn_sqrtf(x);
+#else
+    if (__builtin_expect(!(__float_as_uint(x) - 0x0c800000u < 0x7f800000u - 0x0c800000u), 0)) return sqrtf(x);
+    const float y = __builtin_amdgcn_rsqf(x);
+    const float g = x * y, h = 0.5f * y;
+    const float r = __builtin_fmaf(-g, g, x);
+    return __builtin_fmaf(r, h, g);
+#endif
+}
 // the factor normalize() multiplies by: glm's inversesqrt = 1 / sqrt(x), two IEEE roundings (level 2: v_rsq_f32)
 __device__ __forceinline__ float inv_length(float sqr)
 {
@@ -103,6 +130,15 @@ __device__ __forceinline__ float inv_length(float sqr)
     return __builtin_amdgcn_rsqf(sqr);
 #else
     return rcp_ieee_any(sqrt_ieee(sqr));
+#endif
+}
+// ... over sqrt_ieee_rsq, as the cycle unit compiles inv_length (the probe's op 7)
+__device__ __forceinline__ float inv_length_rsq(float sqr)
+{
+#if PTK_CONTRACT >= 2
+    return __builtin_amdgcn_rsqf(sqr);
+#else
+    return rcp_ieee_any(sqrt_ieee_rsq(sqr));
 #endif
 }
 __device__ __forceinline__ v3 normalize(v3 a)

@@ -689,7 +689,8 @@ void launch_trace_plain(bool lambert, int blocks, hipStream_t stream, const Rend
 #else
 
 // Probe of the arithmetic helpers as THIS build compiles them (op 0: rcp_ieee, 1: rcp_ieee_any, 2: sqrt_ieee, 3: inv_length,
-// the normalisation's factor, 4 / 5: sin / cos of sincos_2pi): the tests hold the exact build against the host's IEEE results
+// the normalisation's factor, 4 / 5: sin / cos of sincos_2pi, 6: sqrt_ieee_rsq, 7: inv_length over it - the two as the cycle
+// unit's shade block compiles sqrt_ieee and inv_length): the tests hold the exact build against the host's IEEE results
 // and the oracle, the contracted builds against float64 within their documented error.
 __global__ __launch_bounds__(PTK_BLOCK) void probe_math_kernel(int op, const float* __restrict__ in, float* __restrict__ out, int n)
 {
@@ -701,6 +702,8 @@ __global__ __launch_bounds__(PTK_BLOCK) void probe_math_kernel(int op, const flo
     else if (op == 1) r = rcp_ieee_any(x);
     else if (op == 2) r = sqrt_ieee(x);
     else if (op == 3) r = inv_length(x);
+    else if (op == 6) r = sqrt_ieee_rsq(x);
+    else if (op == 7) r = inv_length_rsq(x);
     else {
         float sn, cs;
         sincos_2pi(x, sn, cs);

@@ -2242,7 +2242,7 @@ class Context:
 
     def probe_math(self, op: int, x: np.ndarray) -> np.ndarray:
         """The kernels' arithmetic helpers on an array, from the build the "contract" option selects (op 0 rcp, 1 rcp with
-        special cases, 2 sqrt, 3 normalize()'s factor 1/sqrt, 4 sin and 5 cos of the polynomial on [0, 2 pi])."""
+        special cases, 2 sqrt, 3 normalize()'s factor 1/sqrt, 4 sin and 5 cos of the polynomial on [0, 2 pi], 6 the cycle unit's sqrt from v_rsq_f32, 7 its 1/sqrt)."""
         x = np.ascontiguousarray(x, np.float32)
         out = np.empty_like(x)
         self._chk(self.L.ptk_probe_math(self.h, op, x.size, x.ctypes.data, out.ctypes.data), "ptk_probe_math")

@@ -4,6 +4,9 @@
 //   rcp:  y = v_rcp_f32(a) (1 ulp);  two Newton steps with exact residuals (fma)            [Markstein's scheme]
 //   sqrt: y = v_rsq_f32(x); g = x*y, h = y/2; one coupled Newton step, then a residual correction of g
 // Anything the short form gets wrong shows up here with its input; the kernel's helpers take the IEEE path there.
+// Rows 4-7 (profiles/r15/exact_math_rsq.json): the rsq root BEHIND THE RANGE TEST of ptk_device_fn.h sqrt_ieee_rsq (everything
+// outside 2^-102 <= x < +inf goes to sqrtf) in the coupled form, two shorter candidates behind the same test - the first of them,
+// (ii), is what the cycle unit ships - and 1 / sqrt with the reciprocal seeded by the coupled root's own 2 h instead of v_rcp_f32.
 //   hipcc -O3 -ffp-contract=off --offload-arch=gfx950 -o exact_math exact_math.hip && ./exact_math
 #include <hip/hip_runtime.h>
 
@@ -50,7 +53,46 @@ __device__ __forceinline__ float sqrt_nb(float x)
     return rp > 0.0f ? sp : s;
 }
 
-struct Report { unsigned long long bad[4]; unsigned first[4][8]; unsigned long long lo_bad[4], hi_bad[4]; };
+// the range test of sqrt_ieee_rsq: as unsigned numbers the bit patterns of [2^-102, +inf) are consecutive
+__device__ __forceinline__ bool rsq_range(float x) { return __float_as_uint(x) - 0x0c800000u < 0x7f800000u - 0x0c800000u; }
+__device__ __forceinline__ float sqrt_rsq_guarded(float x) { return rsq_range(x) ? sqrt_short(x) : sqrtf(x); }
+// (ii) no coupled step: the residual correction of g with the unrefined h
+__device__ __forceinline__ float sqrt_rsq_ii(float x)
+{
+    if (!rsq_range(x)) return sqrtf(x);
+    const float y = __builtin_amdgcn_rsqf(x);
+    const float g = x * y, h = 0.5f * y;
+    const float r = __builtin_fmaf(-g, g, x);
+    return __builtin_fmaf(r, h, g);
+}
+// (iii) that correction twice
+__device__ __forceinline__ float sqrt_rsq_iii(float x)
+{
+    if (!rsq_range(x)) return sqrtf(x);
+    const float y = __builtin_amdgcn_rsqf(x);
+    float g = x * y; const float h = 0.5f * y;
+    float r = __builtin_fmaf(-g, g, x);
+    g = __builtin_fmaf(r, h, g);
+    r = __builtin_fmaf(-g, g, x);
+    return __builtin_fmaf(r, h, g);
+}
+// 1 / sqrt(x) in two roundings with the reciprocal's Newton step started from 2 h (the coupled step's refined h) instead of v_rcp_f32(s)
+__device__ __forceinline__ float inv_length_2h(float x)
+{
+    if (!rsq_range(x)) return 1.0f / sqrtf(x);
+    const float y = __builtin_amdgcn_rsqf(x);
+    float g = x * y, h = 0.5f * y;
+    const float r = __builtin_fmaf(-g, h, 0.5f);
+    g = __builtin_fmaf(g, r, g); h = __builtin_fmaf(h, r, h);
+    const float d = __builtin_fmaf(-g, g, x);
+    const float s = __builtin_fmaf(d, h, g);
+    const float y0 = 2.0f * h;
+    const float e = __builtin_fmaf(-s, y0, 1.0f);
+    return __builtin_fmaf(y0, e, y0);
+}
+
+#define ROWS 8
+struct Report { unsigned long long bad[ROWS]; unsigned first[ROWS][8]; unsigned long long lo_bad[ROWS], hi_bad[ROWS]; };
 
 __device__ void note(Report* r, int which, unsigned bits, bool in_domain)
 {
@@ -87,6 +129,14 @@ __global__ void sweep(Report* rep)
             const bool dom_nb = bits == 0u || (!(bits >> 31) && ex >= 1u && !is_nan);
             const float g = sqrt_nb(a);
             if (!(refnan ? (g != g) : (__float_as_uint(g) == __float_as_uint(ref)))) note(rep, 3, bits, dom_nb);
+            // the guarded forms: their domain is what passes the range test, and the whole function is held on every input
+            const bool dom_g = rsq_range(a);
+            const float f4 = sqrt_rsq_guarded(a), f5 = sqrt_rsq_ii(a), f6 = sqrt_rsq_iii(a);
+            if (!(refnan ? (f4 != f4) : (__float_as_uint(f4) == __float_as_uint(ref)))) note(rep, 4, bits, dom_g);
+            if (!(refnan ? (f5 != f5) : (__float_as_uint(f5) == __float_as_uint(ref)))) note(rep, 5, bits, dom_g);
+            if (!(refnan ? (f6 != f6) : (__float_as_uint(f6) == __float_as_uint(ref)))) note(rep, 6, bits, dom_g);
+            const float inv = 1.0f / ref, f7 = inv_length_2h(a);
+            if (!(inv != inv ? (f7 != f7) : (__float_as_uint(f7) == __float_as_uint(inv)))) note(rep, 7, bits, dom_g);
         }
     }
 }
@@ -99,15 +149,19 @@ int main()
     hipLaunchKernelGGL(sweep, dim3(256 * 16), dim3(256), 0, 0, d);
     CHECK(hipDeviceSynchronize());
     CHECK(hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost));
-    const char* names[4] = { "rcp, two Newton steps", "rcp, one Newton step", "sqrt, rsq + coupled step + residual",
-                             "sqrt, v_sqrt_f32 + residual tests of both neighbours, no range scaling" };
+    const char* names[ROWS] = { "rcp, two Newton steps", "rcp, one Newton step", "sqrt, rsq + coupled step + residual",
+                                "sqrt, v_sqrt_f32 + residual tests of both neighbours, no range scaling",
+                                "range test, rsq + coupled step + residual (Markstein), sqrtf outside",
+                                "candidate (ii), shipped as sqrt_ieee_rsq: range test, rsq + residual with the unrefined h",
+                                "candidate (iii): range test, rsq + that residual step twice",
+                                "1 / sqrt: the coupled root, then one Newton step of the reciprocal from 2 h (against 1.0f / sqrtf(x))" };
     printf("{\"inputs\": 4294967296, \"rows\": [\n");
-    for (int k = 0; k < 4; k++)
+    for (int k = 0; k < ROWS; k++)
     {
         printf(" {\"sequence\": \"%s\", \"mismatches_all_inputs\": %llu, \"mismatches_in_domain\": %llu, \"largest_mismatching_input_in_domain_hex\": \"%08llx\", \"first_inputs_hex\": [", names[k], h.bad[k], h.lo_bad[k], h.hi_bad[k]);
         for (int j = 0; j < 8 && (unsigned long long)j < h.bad[k]; j++) printf("%s\"%08x\"", j ? ", " : "", h.first[k][j]);
-        printf("]}%s\n", k < 3 ? "," : "");
+        printf("]}%s\n", k < ROWS - 1 ? "," : "");
     }
-    printf("], \"domain\": \"rcp: normal a with 2^-126 <= |a| <= 2^126 (biased exponent 1..252); sqrt: positive normal x; neighbour-test sqrt: +0, positive normal x, +inf\"}\n");
+    printf("], \"domain\": \"rcp: normal a with 2^-126 <= |a| <= 2^126 (biased exponent 1..252); sqrt: positive normal x; neighbour-test sqrt: +0, positive normal x, +inf; the four guarded rows: 2^-102 <= x < +inf, what the range test passes (outside it they are sqrtf)\"}\n");
     return 0;
 }
