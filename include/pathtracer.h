@@ -321,6 +321,13 @@ public:
     // geometry edits apply as for ClosestPoints; the image and the sample count are not touched.
     bool OverlapBoxes(int num, const float* lo, const float* hi, const int32_t* tri_from, int k, int32_t* count, int32_t* tris);
     bool OverlapSpheres(int num, const float* centers, const float* radius, const int32_t* tri_from, int k, int32_t* count, int32_t* tris);
+    // Extension: K-nearest triangle queries (include/ptk.h ptk_nearest_triangles, host arrays, synchronous): for each of the points
+    // the k (1 .. 16) nearest triangles within max_dist[i] (null: no bound), ascending by (distance, index) under ClosestPoints' rule.
+    // count: 1 per point; tri, dist: k per point; point: 3 k; bary: 2 k; behind count -1, +inf, 0, 0.  Any output but one may be
+    // null.  A geometric query: seed and materials take no part.  Valid after BuildBVH() with no resolution set; pending geometry
+    // edits apply as for ClosestPoints; the image and the sample count are not touched.
+    bool NearestTriangles(int num_points, const float* points, const float* max_dist, int k, int32_t* count, int32_t* tri, float* dist,
+                          float* point, float* bary);
     // Extension: surface sampling (include/ptk.h ptk_sample_surface / ptk_surface_weights, host arrays, synchronous) at the class's
     // seed: num_samples points of the scene's surface, a triangle drawn in proportion to its area times its weight, the point
     // uniform on it; sample j is a function of (seed, key_base + j, sample) and the scene alone.  tri, material: 1 per sample; bary:

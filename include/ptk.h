@@ -657,6 +657,66 @@ int ptk_last_overlap_ms(ptk_ctx* ctx, float* ms);
 #define PTK_OVERLAP_SPHERE 1
 int ptk_overlap_stats(ptk_ctx* ctx, int32_t shape, int32_t num, const float* d_a, const float* d_b, const int32_t* d_tri_from, uint64_t stats[4]);
 
+/* ---- K-nearest triangle queries: the K closest surfaces of a point, in order (no counterpart in the reference) ----------------------
+ * "Which surfaces lie nearest to this point, and how far": attribute transfer and inverse-distance blends between meshes, contact
+ * candidates near a tool or a probe, the second-nearest wall for medial-axis and thickness estimates, nearest-feature lookups where
+ * the single winner is a sliver.  ptk_closest_points keeps the first and ptk_overlap_spheres counts all within a radius chosen in
+ * advance and lists them by index; this call keeps the first K by distance.  A GEOMETRIC query as ptk_closest_points: opacity maps,
+ * materials, seeds and keys take no part and no random draw is consumed.
+ * THE RULE.  For point i, p = points[i], and triangle t, the values d2k, v, w, q are those of ptk_closest_points' rule above, bit for
+ * bit - the same float32 operations in the same order on the record's own a, e1, e2 (the kernel exists once, in the exact
+ * arithmetic).
+ *   ACCEPT.  r2 = max_dist[i] * max_dist[i], one float32 product.  Triangle t is ACCEPTED when d2k is finite and d2k < r2, STRICTLY:
+ *     ptk_overlap_spheres' sphere rule.  max_dist == NULL stands for +inf for every point; a max_dist[i] that is NaN, zero or negative
+ *     accepts nothing.
+ *   ORDER.  The answer of point i for k = K is the list of its accepted triangles sorted ascending by (d2k, triangle index) - d2k
+ *     compared as float32, equal d2k to the smaller index, coincident triangles each appear - cut to its first K entries.  An
+ *     accepted d2k is finite and >= +0 (a sum of squares is never -0), so this is the order of the unsigned 64-bit integers
+ *     (bits(d2k) << 32) | index, and that integer is the only thing the list ever compares.
+ *   OUTPUTS.
+ *     count[i]          int32    min(K, number of accepted triangles)
+ *     tri[i][j]         int32    the triangle index of entry j                                         -1 for j >= count[i]
+ *     dist[i][j]        float32  the correctly rounded square root of its d2k                          +inf
+ *     point[i][j][3]    float32  its q                                                                 0
+ *     bary[i][j][2]     float32  its v, w (as ptk_closest_points: weights of the second and third vertex)     0
+ * Each output may be NULL, but not all five.  1 <= K <= PTK_NEAREST_MAX_K.  Three consequences (tests/test_gpu_knearest.py holds
+ * them on the GPU):
+ *   - the answer for K' < K is the first K' columns of the answer for K;
+ *   - count == min(K, count of ptk_overlap_spheres for the same points and radii), and where that count is <= K the listed
+ *     triangles are, as a set, ptk_overlap_spheres' list;
+ *   - K = 1 equals ptk_closest_points' tri, dist, point, bary bit for bit (by this call's own kernel: nothing is forwarded).
+ * No entry is listed twice: every record lies in exactly one leaf and a leaf is reached at most once.  The results do not depend on
+ * the builder that made the tree, on "bvh_leaf_max", on a refit, on "flat" (the call always walks the BVH), on ptk_set_tile or on
+ * "contract", nor on how the point set is cut into calls (tests/test_gpu_knearest.py: array_equal with tests/knearest_rule.py): a
+ * node is passed over only when its box lies beyond the bound - r2 while the list has a free slot, the K-th smallest d2k found so
+ * far afterwards - by more than the slack of ptk_closest_points' walk, so a triangle that ties the K-th with a smaller index is
+ * still reached.  A non-finite coordinate makes THAT point's output unspecified and affects neither another point nor whether the
+ * call ends.
+ * The calls need a scene only - no camera, no frame - and read it as ptk_update_materials / ptk_update_geometry left it.  They
+ * touch no frame, adaptive, feature or bake state, stay legal after ptk_render_adaptive, and ptk_request_exit does not cut them.
+ *   ptk_nearest_triangles: host arrays, synchronous; the points, max_dist and the requested outputs are staged in device memory
+ *     for the length of the call.
+ *   ptk_nearest_triangles_device: every array in memory of this context's GPU, asynchronous on the context's stream (the caller's
+ *     after ptk_set_stream); no host wait and no allocation of device memory inside the call.  The arrays must stay allocated
+ *     until the stream has passed the call.
+ * Errors as for ptk_closest_points, and PTK_ERR_BAD_ARG for k outside 1 .. PTK_NEAREST_MAX_K; a refused call leaves the outputs
+ * alone.  num_points == 0 is PTK_OK and does nothing.  A scene without triangles gives count 0 and the unused-slot values
+ * everywhere, by fills, without a kernel.  Limits: one workgroup per 64 points, in one launch. */
+#define PTK_NEAREST_MAX_K 16
+int ptk_nearest_triangles(ptk_ctx* ctx, int32_t num_points, const float* points /*[n][3]*/, const float* max_dist /*[n] or NULL*/,
+                          int32_t k /*K*/, int32_t* count /*[n]*/, int32_t* tri /*[n][K]*/, float* dist /*[n][K]*/,
+                          float* point /*[n][K][3]*/, float* bary /*[n][K][2]*/);
+int ptk_nearest_triangles_device(ptk_ctx* ctx, int32_t num_points, const float* d_points, const float* d_max_dist, int32_t k,
+                                 int32_t* d_count, int32_t* d_tri, float* d_dist, float* d_point, float* d_bary);
+/* measurement hooks (tools/nearest_timing.py), not part of the feature.  The HIP-event time of the last call's kernel (0 where the
+ * call launched none); waits for the call */
+int ptk_last_nearest_ms(ptk_ctx* ctx, float* ms);
+/* ... and the work of a query: the counting variant of the kernel for this k over points and radii in this GPU's memory, no outputs
+ * written; node_visits / tri_tests = interior nodes fetched / triangle records tested, summed over the points.  Synchronous;
+ * allocates 16 B of device memory at its first call */
+int ptk_nearest_stats(ptk_ctx* ctx, int32_t num_points, const float* d_points, const float* d_max_dist, int32_t k, uint64_t* node_visits,
+                      uint64_t* tri_tests);
+
 /* ---- surface sampling: area-weighted points on the scene's triangles (no counterpart in the reference) ----------------------------
  * Every other query starts from the caller's geometry and asks about the scene; this one gives points OF the scene's surface: point
  * clouds for learning and registration, light sampling by power, scattering, probe candidates near walls, bakes that need neither

@@ -126,6 +126,10 @@ int  pth_multihit_rays(pth_tracer* t, int num_rays, const float* origins, const 
 int  pth_overlap_boxes(pth_tracer* t, int num, const float* lo, const float* hi, const int32_t* tri_from, int k, int32_t* count, int32_t* tris);
 int  pth_overlap_spheres(pth_tracer* t, int num, const float* centers, const float* radius, const int32_t* tri_from, int k, int32_t* count,
                          int32_t* tris);
+/* NearestTriangles (the k nearest triangles of each point in order, include/ptk.h ptk_nearest_triangles): 1 on success; max_dist
+ * and any output but one may be NULL */
+int  pth_nearest_triangles(pth_tracer* t, int num_points, const float* points, const float* max_dist, int k, int32_t* count, int32_t* tri,
+                           float* dist, float* point, float* bary);
 /* SampleSurface / SetSurfaceWeights (area-weighted points on the scene's triangles at the tracer's seed, include/ptk.h
  * ptk_sample_surface / ptk_surface_weights): 1 on success; any output and the weights may be NULL */
 int  pth_sample_surface(pth_tracer* t, int num_samples, uint32_t key_base, uint32_t sample, int32_t* tri, float* bary, float* position,

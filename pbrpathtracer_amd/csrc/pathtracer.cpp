@@ -1268,6 +1268,18 @@ bool PathTracer::OverlapSpheres(int num, const float* centers, const float* radi
     return rc == PTK_OK;
 }
 
+// The k nearest triangles of caller-supplied points (ptk_nearest_triangles), in the scene as the next RenderFrame() would see it
+bool PathTracer::NearestTriangles(int num_points, const float* points, const float* max_dist, int k, int32_t* count, int32_t* tri, float* dist,
+                                  float* point, float* bary)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const int rc = ptk_nearest_triangles(m->ctx, num_points, points, max_dist, k, count, tri, dist, point, bary);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 bool PathTracer::ContainsPoints(int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside, int32_t* winding)
 {
     if (!m->scene_uploaded || !m->ensure_ctx()) return false;

@@ -199,6 +199,11 @@ struct ptk_ctx {
     // ordered multi-hit queries (ptk_multihit_rays): two events around the last call's kernel, made by the first call
     ptk::Timer<2> ev_multihit;
 
+    // K-nearest triangle queries (ptk_nearest_triangles): two events around the last call's kernel, made by the first call; the two
+    // counters of ptk_nearest_stats, made by its first call
+    ptk::Timer<2> ev_nearest;
+    ptk::Buf<unsigned long long> d_nearest_stats;
+
     // overlap queries (ptk_overlap_boxes, ptk_overlap_spheres): two events around the last call's kernel, made by the first call;
     // the four counters of ptk_overlap_stats, made by its first call
     ptk::Timer<2> ev_overlap;

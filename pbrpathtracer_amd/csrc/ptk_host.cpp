@@ -201,6 +201,11 @@ int pth_overlap_spheres(pth_tracer* t, int num, const float* centers, const floa
 {
     return t->pt.OverlapSpheres(num, centers, radius, tri_from, k, count, tris) ? 1 : 0;
 }
+int pth_nearest_triangles(pth_tracer* t, int num_points, const float* points, const float* max_dist, int k, int32_t* count, int32_t* tri,
+                          float* dist, float* point, float* bary)
+{
+    return t->pt.NearestTriangles(num_points, points, max_dist, k, count, tri, dist, point, bary) ? 1 : 0;
+}
 int pth_sample_surface(pth_tracer* t, int num_samples, uint32_t key_base, uint32_t sample, int32_t* tri, float* bary, float* position,
                        float* normal, int32_t* material)
 {

@@ -39,7 +39,7 @@ HOST_SYMBOLS = [
     "pth_bake_lightmap", "pth_bake_coverage", "pth_lightmap_dilate", "pth_bake_probes", "pth_sample_probes",
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
     "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points", "pth_overlap_boxes", "pth_overlap_spheres",
-    "pth_crossings_rays", "pth_contains_points", "pth_signed_distance", "pth_multihit_rays",
+    "pth_crossings_rays", "pth_contains_points", "pth_signed_distance", "pth_multihit_rays", "pth_nearest_triangles",
     "pth_sample_surface", "pth_set_surface_weights", "pth_surface_info",
     "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised", "pth_temporal_frame", "pth_read_temporal", "pth_get_view",
     "pth_track_motion", "pth_temporal_frame_moving", "pth_read_motion", "pth_temporal_frame_moments", "pth_temporal_variance",
@@ -124,6 +124,7 @@ def _bind_locked(L) -> C.CDLL:
             fn.restype = i32; fn.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp]
         L.pth_crossings_rays.restype = i32; L.pth_crossings_rays.argtypes = [vp, i32, vp, vp, vp, vp, vp]
         L.pth_multihit_rays.restype = i32; L.pth_multihit_rays.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.pth_nearest_triangles.restype = i32; L.pth_nearest_triangles.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
         L.pth_sample_surface.restype = i32; L.pth_sample_surface.argtypes = [vp, i32, u32, u32, vp, vp, vp, vp, vp]
         L.pth_set_surface_weights.restype = i32; L.pth_set_surface_weights.argtypes = [vp, vp]
         L.pth_surface_info.restype = i32; L.pth_surface_info.argtypes = [vp, vp, vp, vp, vp]
@@ -720,6 +721,27 @@ class PathTracer:
         return out
 
     MultiHitRays = multihit_rays
+
+    def nearest_triangles(self, points, k, max_dist=None):
+        """Extension: (count [n] int32, tri [n, K] int32, dist [n, K] float32, point [n, K, 3] float32, bary [n, K, 2] float32), the
+        K = k (1 .. 16) triangles nearest to each point, strictly nearer than max_dist[i] where max_dist is given, ascending by
+        (distance, triangle index) (include/ptk.h ptk_nearest_triangles); behind count -1 / inf / 0 / 0.  Pending geometry edits
+        apply as for RenderFrame()."""
+        K = int(k)
+        if K < 1 or K > _ptk.NEAREST_MAX_K:
+            raise _ptk.PtkError(f"NearestTriangles: k must be in 1 .. {_ptk.NEAREST_MAX_K}")
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        md = None if max_dist is None else np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
+        assert md is None or len(md) == n, "one max_dist per point"
+        out = (np.empty(n, np.int32), np.empty((n, K), np.int32), np.empty((n, K), np.float32), np.empty((n, K, 3), np.float32),
+               np.empty((n, K, 2), np.float32))
+        if n and not self.L.pth_nearest_triangles(self.h, n, p.ctypes.data, md.ctypes.data if md is not None else None, K,
+                                                  *(a.ctypes.data for a in out)):
+            raise _ptk.PtkError("NearestTriangles failed: " + self.LastError())
+        return out
+
+    NearestTriangles = nearest_triangles
 
     def sample_surface(self, n, key_base=0, sample=0):
         """Extension: (tri [n] int32, bary [n, 2], position [n, 3], normal [n, 3] float32, material [n] int32) - n points of the

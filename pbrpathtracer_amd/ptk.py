@@ -174,6 +174,7 @@ SYMBOLS = [
     "ptk_multihit_rays", "ptk_multihit_rays_device", "ptk_last_multihit_ms",
     "ptk_overlap_boxes", "ptk_overlap_boxes_device", "ptk_overlap_spheres", "ptk_overlap_spheres_device", "ptk_last_overlap_ms",
     "ptk_overlap_stats",
+    "ptk_nearest_triangles", "ptk_nearest_triangles_device", "ptk_last_nearest_ms", "ptk_nearest_stats",
     "ptk_surface_weights", "ptk_surface_weights_device", "ptk_sample_surface", "ptk_sample_surface_device", "ptk_surface_info",
     "ptk_last_surface_ms", "ptk_probe_surface_table", "ptk_probe_scan_u64",
     "ptk_denoise_planes", "ptk_denoise_planes_device", "ptk_denoise_frame", "ptk_read_denoised", "ptk_denoised_device_ptr",
@@ -319,6 +320,10 @@ def _load_locked() -> C.CDLL:
             fn.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp]
         L.ptk_last_overlap_ms.argtypes = [vp, fp]
         L.ptk_overlap_stats.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.POINTER(u64)]
+        for fn in (L.ptk_nearest_triangles, L.ptk_nearest_triangles_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+        L.ptk_last_nearest_ms.argtypes = [vp, fp]
+        L.ptk_nearest_stats.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.POINTER(u64), C.POINTER(u64)]
         for fn in (L.ptk_surface_weights, L.ptk_surface_weights_device):
             fn.argtypes = [vp, vp]
         for fn in (L.ptk_sample_surface, L.ptk_sample_surface_device):
@@ -420,7 +425,8 @@ DENOISE_VARIANCE = 1                                                  # ptk_deno
 INSIDE_WINDING, INSIDE_PARITY = 0, 1                                  # ptk_contains_points / ptk_signed_distance modes
 OVERLAP_MAX_K = 16                                                    # PTK_OVERLAP_MAX_K: the most indices an overlap query lists per call
 OVERLAP_BOX, OVERLAP_SPHERE = 0, 1                                    # PTK_OVERLAP_BOX, PTK_OVERLAP_SPHERE (ptk_overlap_stats' shape)
-MULTIHIT_MAX = 16                                                     # PTK_MULTIHIT_MAX: the most entries ptk_multihit_rays keeps per ray
+NEAREST_MAX_K = 16                                                    # PTK_NEAREST_MAX_K: the most triangles ptk_nearest_triangles keeps per point
+MULTIHIT_MAX = 16                                                 # PTK_MULTIHIT_MAX: the most entries ptk_multihit_rays keeps per ray
 SURFACE_SCAN_ITEMS = 4096                                             # PTK_SURFACE_SCAN_ITEMS: items per workgroup of the table's prefix sum
 INSIDE_MODES = {"winding": INSIDE_WINDING, "parity": INSIDE_PARITY}
 
@@ -1119,6 +1125,64 @@ class Context:
         t = C.c_float(0)
         self._chk(self.L.ptk_last_multihit_ms(self.h, C.byref(t)), "ptk_last_multihit_ms")
         return t.value
+
+    # ---- K-nearest triangle queries -------------------------------------------------------------
+    def nearest_triangles(self, points, k, max_dist=None):
+        """ptk_nearest_triangles: (count [n] int32, tri [n, K] int32, dist [n, K] float32, point [n, K, 3] float32, bary [n, K, 2]
+        float32) for K = k in 1 .. NEAREST_MAX_K - the K triangles nearest to each of the points [n, 3] float32, ascending by
+        (distance, triangle index) under closest_points' rule (include/ptk.h); coincident triangles each appear, column 0 is
+        closest_points' answer.  max_dist: [n] float32 of the points' kind - only surface strictly nearer counts; NaN, zero or
+        negative finds nothing - or None for no bound.  Behind count[i]: tri -1, dist +inf, point 0, bary 0.  numpy in, numpy out
+        through the host entry; torch in, torch out through ptk_nearest_triangles_device with no host copy."""
+        K = int(k)
+        if K < 1 or K > NEAREST_MAX_K:
+            raise PtkError(f"ptk_nearest_triangles: k must be in 1 .. {NEAREST_MAX_K}")
+        if hasattr(points, "data_ptr"):
+            import torch
+            n = points.numel() // 3
+            mk = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=points.device)
+            out = (mk((n,), torch.int32), mk((n, K), torch.int32), mk((n, K), torch.float32), mk((n, K, 3), torch.float32),
+                   mk((n, K, 2), torch.float32))
+            self._ray_tensors((points,), n, ((torch.float32, 3),))
+            if max_dist is not None:
+                self._ray_tensors((max_dist,), n, ((torch.float32, 1),))
+            if n:
+                self._chk(self.L.ptk_nearest_triangles_device(self.h, n, C.c_void_p(points.data_ptr()),
+                                                              C.c_void_p(max_dist.data_ptr()) if max_dist is not None else None, K,
+                                                              *(C.c_void_p(t.data_ptr()) for t in out)), "ptk_nearest_triangles_device")
+            return out
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        md = None
+        if max_dist is not None:
+            md = np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
+            assert len(md) == n, "one max_dist per point"
+        out = (np.empty(n, np.int32), np.empty((n, K), np.int32), np.empty((n, K), np.float32), np.empty((n, K, 3), np.float32),
+               np.empty((n, K, 2), np.float32))
+        if n:
+            self._chk(self.L.ptk_nearest_triangles(self.h, n, p.ctypes.data, md.ctypes.data if md is not None else None, K,
+                                                   *(a.ctypes.data for a in out)), "ptk_nearest_triangles")
+        return out
+
+    def last_nearest_ms(self) -> float:
+        """HIP-event time of the last nearest_triangles call's kernel (0 where it launched none); waits for it."""
+        t = C.c_float(0)
+        self._chk(self.L.ptk_last_nearest_ms(self.h, C.byref(t)), "ptk_last_nearest_ms")
+        return t.value
+
+    def nearest_stats(self, points, k, max_dist=None):
+        """ptk_nearest_stats (measurement hook): (interior nodes fetched, triangle records tested) by a nearest_triangles query for
+        this k of these torch tensors on the context's GPU, summed over the points; synchronous, writes no outputs."""
+        import torch
+        n = points.numel() // 3
+        self._ray_tensors((points,), n, ((torch.float32, 3),))
+        if max_dist is not None:
+            self._ray_tensors((max_dist,), n, ((torch.float32, 1),))
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.L.ptk_nearest_stats(self.h, n, C.c_void_p(points.data_ptr()) if n else None,
+                                           C.c_void_p(max_dist.data_ptr()) if max_dist is not None else None, int(k), C.byref(a), C.byref(b)),
+                  "ptk_nearest_stats")
+        return a.value, b.value
 
     # ---- overlap queries ----------------------------------------------------------------------
     def _overlap(self, name, a, b, width_b, k, tri_from):

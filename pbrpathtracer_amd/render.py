@@ -13,6 +13,7 @@
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
     python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz [--layers K]
     python -m pbrpathtracer_amd.render scene.pts --distance-field 64 64 64 [--df-max-dist M] [--signed [--inside-mode parity]] -o field.npz
+    python -m pbrpathtracer_amd.render scene.pts --distance-field 64 64 64 --nearest 4 [--df-max-dist M] -o nearest.npz
     python -m pbrpathtracer_amd.render scene.pts --voxelize 64 64 64 [--solid] -o grid.npz
     python -m pbrpathtracer_amd.render scene.pts --point-cloud 100000 --spp 16 [--offset O] -o cloud.npz
     python -m pbrpathtracer_amd.render scene.pts --bake-lightmap 1024 --spp 64 [--bake-atlas] [--bake-offset F] [--bake-back]
@@ -196,6 +197,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--inside-mode", choices=("winding", "parity"), default="winding",
                     help="--signed: a ray votes inside when it crosses unequal numbers of back and front faces (winding: any consistently "
                          "wound closed mesh) or an odd number of faces (parity: closed meshes wound inconsistently)")
+    ap.add_argument("--nearest", type=int, default=None, metavar="K",
+                    help="--distance-field: the K (1..16) nearest triangles per grid point (PathTracer.nearest_triangles): the .npz holds "
+                         "count, and tri, dist, point with a trailing K axis (-1 / inf / 0 behind count), origin and spacing")
     ap.add_argument("--voxelize", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
                     help="instead of rendering a view, write which voxels of a grid of NX x NY x NZ voxels centred on the --distance-field "
                          "grid's points hold surface; -o names an .npz with occupancy [NZ, NY, NX] bool, origin and spacing")
@@ -387,6 +391,16 @@ def render_distance_field(pt, a) -> int:
     md = None if a.df_max_dist is None else np.full(len(pos), a.df_max_dist, np.float32)
     extra = {}
     shape = (dims[2], dims[1], dims[0])
+    if a.nearest is not None:                   # the K nearest triangles per grid point: a trailing K axis
+        K = a.nearest
+        count, tri, dist, point, _ = pt.nearest_triangles(pos, K, md)
+        t2 = time.time()
+        with open(a.out, "wb") as f:
+            np.savez(f, count=count.reshape(shape), dist=dist.reshape(shape + (K,)), tri=tri.reshape(shape + (K,)),
+                     point=point.reshape(shape + (K, 3)), origin=origin, spacing=spacing)
+        print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {dims[0]}x{dims[1]}x{dims[2]} distance field of the {K} nearest, "
+              f"{int((count > 0).sum())} points within reach: {t2 - t1:.3f} s -> {a.out}")
+        return 0
     if a.signed:
         tri, sdf, point, _ = pt.signed_distance(pos, md, None, a.inside_mode)
         dist = np.abs(sdf)                      # (clears the sign bit: ptk_closest_points' dist, bit for bit)
@@ -752,6 +766,9 @@ def main(argv=None):
         except (RuntimeError, ValueError) as e:
             print("error:", e, file=sys.stderr)
             return 1
+    if a.nearest is not None and (a.distance_field is None or a.signed or not 1 <= a.nearest <= 16):
+        print("error: --nearest K (1..16) goes with --distance-field, without --signed", file=sys.stderr)
+        return 1
     if a.distance_field is not None:
         try:
             return render_distance_field(pt, a)

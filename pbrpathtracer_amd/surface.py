@@ -23,6 +23,25 @@ def emissive_weights(materials, material_ids) -> np.ndarray:
     return np.maximum(lum, F32(0)).astype(F32)[np.asarray(material_ids, np.int32).reshape(-1)]
 
 
+def transfer(ctx, values_per_triangle, points, k, power=2, max_dist=None) -> np.ndarray:
+    """Attribute transfer from the scene's triangles to arbitrary points: [n, ...] float64, the inverse-distance blend of
+    values_per_triangle [triangles, ...] over the k nearest triangles of each point (ctx.nearest_triangles, include/ptk.h
+    ptk_nearest_triangles; ctx: a Context or a PathTracer) with weights (d_0 / d_j) ** power, d_0 the nearest distance, normalised to
+    sum 1.  A point on the surface (d_0 = 0) takes the mean over the triangles it lies on; k = 1 copies the nearest triangle's value;
+    a point with no triangle within max_dist gets NaN."""
+    values = np.asarray(values_per_triangle, np.float64)
+    _, tri, dist = ctx.nearest_triangles(points, k, max_dist)[:3]
+    d = dist.astype(np.float64)
+    d0 = d[:, :1]
+    with np.errstate(all="ignore"):
+        w = np.where(d0 > 0, (d0 / d) ** float(power), (d == 0).astype(np.float64))
+        w = np.where(tri >= 0, w, 0.0)
+        w = w / w.sum(axis=1, keepdims=True)                # (0 / 0 where nothing was found: NaN)
+        picked = values[np.maximum(tri, 0)]                 # [n, k, ...]
+        w = w.reshape(w.shape + (1,) * (picked.ndim - 2))
+        return (picked * w).sum(axis=1)
+
+
 def bake_rays(position, normal, offset):
     """(origins, dirs) [n, 3] float32 of the lightmap bake's ray at each point: origin = P + n * offset - the product rounded to
     float32, then the sum -, direction = -n"""

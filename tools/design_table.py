@@ -103,7 +103,7 @@ if os.path.exists(lib):
         print("| kernel | VGPRs | SGPRs | VGPR spills | SGPR spills | LDS bytes / workgroup | scratch bytes / lane | waves / SIMD by registers |")
         print("|---|---|---|---|---|---|---|---|")
         for r in sorted(rows):
-            if "trace" in r[0] or "rays" in r[0] or "accumulate" in r[0] or "level_bin" in r[0] or "collapse" in r[0] or "refit" in r[0] or "repack" in r[0] or "geometry_bounds" in r[0] or "hits_kernel" in r[0] or "occluded_kernel" in r[0] or "closest_kernel" in r[0] or "crossings_kernel" in r[0] or "contains_kernel" in r[0] or "multihit_kernel" in r[0] or "overlap_kernel" in r[0] or "surface_" in r[0] or "scan_" in r[0] or "denoise_" in r[0] or "temporal_" in r[0] or "probe_" in r[0]:
+            if "trace" in r[0] or "rays" in r[0] or "accumulate" in r[0] or "level_bin" in r[0] or "collapse" in r[0] or "refit" in r[0] or "repack" in r[0] or "geometry_bounds" in r[0] or "hits_kernel" in r[0] or "occluded_kernel" in r[0] or "closest_kernel" in r[0] or "crossings_kernel" in r[0] or "contains_kernel" in r[0] or "multihit_kernel" in r[0] or "overlap_kernel" in r[0] or "nearest_kernel" in r[0] or "surface_" in r[0] or "scan_" in r[0] or "denoise_" in r[0] or "temporal_" in r[0] or "probe_" in r[0]:
                 alloc = (r[1] + 7) // 8 * 8
                 print("| `%s` | %d | %d | %d | %d | %d | %d | %d |" % (r[0], r[1], r[2], r[3], r[4], r[5], r[6], min(8, 512 // max(8, alloc))))
     except Exception as e:          # (no llvm tools: the measurement table above still stands)
