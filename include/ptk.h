@@ -118,7 +118,21 @@ void ptk_destroy(ptk_ctx* ctx);
  * scene whose device-built tree would not fit the traversal stack or the device builder's node store, by the host builder
  * (option "device_build" = 0 forces it).
  * Limits (PTK_ERR_LIMIT): at most 89 478 485 triangles (the walk addresses its 48-byte records with 32-bit byte offsets),
- * |coordinate| < 2^61, a tree that defers at most PTK_MAX_BVH_DEPTH entries (the host builder always meets that). */
+ * |coordinate| < 2^61, a tree that defers at most PTK_MAX_BVH_DEPTH entries (the host builder always meets that).
+ * A context may be given scene after scene.  The call waits for the context's stream - every render, query and update queued
+ * so far finishes on the scene it was queued for - and then replaces everything derived from the old scene: records, tree, flat
+ * list, textures, lights, the refit tables and update count, the geometry snapshot, the surface-sampling table and weights.
+ * A successful upload also INVALIDATES what the frame entries derived from the previous scene, exactly as ptk_set_frame at
+ * another resolution does - unlike ptk_update_geometry and ptk_update_materials, after which triangle and material ids still
+ * mean what they meant: the feature planes; the guide planes and the guide view; the denoised frame; the temporal history with
+ * its moments and variance; the motion planes; the upsampled frame; the display image.  Until they are made again the read,
+ * pointer and consumer entries answer PTK_ERR_BAD_ARG with their "...: ptk_render_features first" / "no ... yet" text, and the
+ * next ptk_temporal_frame is a fresh one, with no history.
+ * Kept as they are:
+ *   - the accumulator, the sample count and the adaptive counts: ptk_reset stays the caller's (BuildBVH / ResetImage order);
+ *   - the display exposure state: it belongs to the viewer, not to the scene (ptk_display_reset);
+ *   - options, camera, frame, tile, stream and bound output buffers.
+ * A refused upload (PTK_ERR_BAD_ARG, PTK_ERR_LIMIT) leaves the resident scene and all of the above exactly as they were. */
 int ptk_upload_scene(ptk_ctx* ctx, const ptk_scene_desc* scene);
 
 /* SetMaterial after BuildBVH (pathtracer.cpp:243-258): the reference's triangles point into the loaded materials, so an

@@ -653,6 +653,17 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
             if (s->materials[i].tex[k] >= s->num_textures) return fail(c, PTK_ERR_BAD_ARG, "material texture index out of range");
 
     HIPCHK(c, hipSetDevice(c->device));
+    // The one wait before the resident scene is freed, and why the context's stream is enough.  Everything that reads scene
+    // buffers is either on this stream or tied to it before its entry returns:
+    //  - trace kernels on trace_stream[0 / 1] (run_passes): each is followed by ev_trace_done, which this stream waits for ahead
+    //    of the pass's accumulate kernel - also for a render that ptk_request_exit cuts short: its kernels still run and stand
+    //    down, and the accumulate kernels are queued all the same.  ptk_collect_stats drains both trace streams itself;
+    //  - feature, guide, pick, query, bake, probe, surface, motion, denoise, temporal, display and upsample kernels: on this stream;
+    //  - ptk_update_geometry: geo_stream only stages the caller's arrays and reduces bounds, and the update waits for it on the
+    //    host before it returns; repack and refit are on this stream;
+    //  - xstream (ptk_gather_accum) reads the accumulator and its own buffers, exit_stream writes d_exit: no scene buffer;
+    //  - a caller's stream taken by ptk_set_stream stands behind the one it replaced (ev_inputs), so "this stream" is the newest.
+    // So once this stream is idle nothing on the device still reads what is released below.
     HIPCHK(c, hipStreamSynchronize(c->stream));
 
     const auto t_begin = std::chrono::steady_clock::now();
@@ -766,6 +777,10 @@ int ptk_upload_scene(ptk_ctx* c, const ptk_scene_desc* s)
     c->d_verts_res.release(); free_geometry_cache(c);
     c->d_verts_prev.release(); c->have_snapshot = false;             // (ptk_geometry_snapshot: of the scene that goes)
     surface_release(c);                                            // (ptk_sample_surface: its table and weights likewise)
+    // ... and everything a frame entry derived from that scene - feature, guide and motion planes, the denoised, upsampled and
+    // display frames, the temporal history with its moments and variance - exactly as ptk_set_frame at another resolution drops
+    // it: triangle and material ids of the old scene mean nothing in the new one (ptk.h).  The exposure state stays
+    free_features(c);
     c->lights_stale = false;
     c->have_scene = false;
     auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
