@@ -15,29 +15,17 @@ static int check_closest_args(ptk_ctx* c, const char* who, int32_t num_points, c
     return check_query_args(c, who, "point count", num_points, points, points, have_out, nothing);
 }
 
-// The call proper, on the context's stream, every pointer into this GPU's memory: h holds the points and the outputs, the scene
-// half is filled in here.  One kernel between the two events; a scene without triangles has no tree to walk and gets its misses
-// from fills.
+// The call proper (query_on_stream): h holds the points and the outputs
 static int closest_on_stream(ptk_ctx* c, ClosestParams& h)
 {
-    c->ev_closest.begin();
-    const size_t n = (size_t)h.num_points;
-    if (c->num_nodes == 0)
-    {
+    return query_on_stream(c, c->ev_closest, h, launch_closest, [&] {
+        const size_t n = (size_t)h.num_points;
         if (h.tri) HIPCHK(c, hipMemsetAsync(h.tri, 0xff, n * sizeof(int32_t), c->stream));
         if (h.dist) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)h.dist, 0x7f800000, n, c->stream));
         if (h.point) HIPCHK(c, hipMemsetAsync(h.point, 0, n * 3 * sizeof(float), c->stream));
         if (h.bary) HIPCHK(c, hipMemsetAsync(h.bary, 0, n * 2 * sizeof(float), c->stream));
-        return PTK_OK;
-    }
-    h.nodes = c->d_nodes; h.tris = c->d_tris;
-    h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound;
-    if (const int rc = c->ev_closest.mark(c, 0, c->stream); rc != PTK_OK) return rc;
-    launch_closest(h, c->stream);
-    HIPCHK(c, hipGetLastError());
-    if (const int rc = c->ev_closest.mark(c, 1, c->stream); rc != PTK_OK) return rc;
-    c->ev_closest.done();
-    return PTK_OK;
+        return (int)PTK_OK;
+    });
 }
 
 extern "C" {
@@ -71,14 +59,7 @@ int ptk_closest_points(ptk_ctx* c, int32_t num_points, const float* points, cons
     return s.run([&] { return ptk_closest_points_device(c, num_points, d_points, d_max_dist, d_tri, d_dist, d_point, d_bary); });
 }
 
-int ptk_last_closest_ms(ptk_ctx* c, float* ms)
-{
-    if (!c) return PTK_ERR_BAD_ARG;
-    float t = 0.0f;
-    const int rc = c->ev_closest.elapsed(c, 0, 1, &t);
-    if (ms) *ms = t;
-    return rc;
-}
+int ptk_last_closest_ms(ptk_ctx* c, float* ms) { return last_ms(c, &ptk_ctx::ev_closest, ms); }
 
 int ptk_closest_stats(ptk_ctx* c, int32_t num_points, const float* d_points, const float* d_max_dist, uint64_t* node_visits, uint64_t* tri_tests)
 {
@@ -86,20 +67,9 @@ int ptk_closest_stats(ptk_ctx* c, int32_t num_points, const float* d_points, con
     const int rc = check_closest_args(c, "ptk_closest_stats", num_points, d_points, node_visits || tri_tests, &nothing);
     if (rc != PTK_OK) return rc;
     unsigned long long got[2] = { 0, 0 };
-    if (!nothing && c->num_nodes > 0)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        if (!c->d_closest_stats) HIPCHK(c, hipMalloc(&c->d_closest_stats.p, sizeof(got)));
-        HIPCHK(c, hipMemsetAsync(c->d_closest_stats, 0, sizeof(got), c->stream));
-        ClosestParams h = {};
-        h.points = d_points; h.max_dist = d_max_dist; h.num_points = num_points;
-        h.stats = c->d_closest_stats;
-        h.nodes = c->d_nodes; h.tris = c->d_tris; h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound;
-        launch_closest(h, c->stream);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(got, c->d_closest_stats, sizeof(got), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    ClosestParams h = {};
+    h.points = d_points; h.max_dist = d_max_dist; h.num_points = num_points;
+    if (const int rs = query_stats(c, nothing, c->d_closest_stats, h, launch_closest, got); rs != PTK_OK) return rs;
     if (node_visits) *node_visits = got[0];
     if (tri_tests) *tri_tests = got[1];
     return PTK_OK;

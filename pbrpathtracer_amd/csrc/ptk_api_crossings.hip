@@ -185,13 +185,6 @@ int ptk_signed_distance(ptk_ctx* c, int32_t num_points, const float* points, con
     return s.run([&] { return ptk_signed_distance_device(c, num_points, d_points, d_max_dist, num_dirs, d_dirs, mode, d_tri, d_dist, d_point, d_bary); });
 }
 
-int ptk_last_crossings_ms(ptk_ctx* c, float* ms)
-{
-    if (!c) return PTK_ERR_BAD_ARG;
-    float t = 0.0f;
-    const int rc = c->ev_crossings.elapsed(c, 0, 1, &t);
-    if (ms) *ms = t;
-    return rc;
-}
+int ptk_last_crossings_ms(ptk_ctx* c, float* ms) { return last_ms(c, &ptk_ctx::ev_crossings, ms); }
 
 }  // extern "C"

@@ -17,28 +17,18 @@ static int check_nearest_args(ptk_ctx* c, const char* who, int32_t num_points, c
                             (k < 1 || k > PTK_NEAREST_MAX_K) ? range.c_str() : nullptr);
 }
 
-// The call proper, on the context's stream, every pointer into this GPU's memory.  The kernel between the two events; a scene
-// without triangles has no tree to walk and gets its unused-slot values from fills.
+// The call proper (query_on_stream): h holds the points, k and the outputs; the fills are the unused-slot values
 static int nearest_on_stream(ptk_ctx* c, NearestParams& h)
 {
-    c->ev_nearest.begin();
-    const size_t n = (size_t)h.num_points, nk = n * (size_t)h.k;
-    if (c->num_nodes == 0)
-    {
+    return query_on_stream(c, c->ev_nearest, h, launch_nearest, [&] {
+        const size_t n = (size_t)h.num_points, nk = n * (size_t)h.k;
         if (h.count) HIPCHK(c, hipMemsetAsync(h.count, 0, n * sizeof(int32_t), c->stream));
         if (h.tri) HIPCHK(c, hipMemsetAsync(h.tri, 0xff, nk * sizeof(int32_t), c->stream));
         if (h.dist) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)h.dist, 0x7f800000, nk, c->stream));
         if (h.point) HIPCHK(c, hipMemsetAsync(h.point, 0, nk * 3 * sizeof(float), c->stream));
         if (h.bary) HIPCHK(c, hipMemsetAsync(h.bary, 0, nk * 2 * sizeof(float), c->stream));
-        return PTK_OK;
-    }
-    h.nodes = c->d_nodes; h.tris = c->d_tris; h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound;
-    if (const int rc = c->ev_nearest.mark(c, 0, c->stream); rc != PTK_OK) return rc;
-    launch_nearest(h, c->stream);
-    HIPCHK(c, hipGetLastError());
-    if (const int rc = c->ev_nearest.mark(c, 1, c->stream); rc != PTK_OK) return rc;
-    c->ev_nearest.done();
-    return PTK_OK;
+        return (int)PTK_OK;
+    });
 }
 
 extern "C" {
@@ -72,14 +62,7 @@ int ptk_nearest_triangles(ptk_ctx* c, int32_t num_points, const float* points, c
     return s.run([&] { return ptk_nearest_triangles_device(c, num_points, d_points, d_max_dist, k, d_count, d_tri, d_dist, d_point, d_bary); });
 }
 
-int ptk_last_nearest_ms(ptk_ctx* c, float* ms)
-{
-    if (!c) return PTK_ERR_BAD_ARG;
-    float t = 0.0f;
-    const int rc = c->ev_nearest.elapsed(c, 0, 1, &t);
-    if (ms) *ms = t;
-    return rc;
-}
+int ptk_last_nearest_ms(ptk_ctx* c, float* ms) { return last_ms(c, &ptk_ctx::ev_nearest, ms); }
 
 int ptk_nearest_stats(ptk_ctx* c, int32_t num_points, const float* d_points, const float* d_max_dist, int32_t k, uint64_t* node_visits,
                       uint64_t* tri_tests)
@@ -88,20 +71,9 @@ int ptk_nearest_stats(ptk_ctx* c, int32_t num_points, const float* d_points, con
     const int rc = check_nearest_args(c, "ptk_nearest_stats", num_points, d_points, k, node_visits || tri_tests, &nothing);
     if (rc != PTK_OK) return rc;
     unsigned long long got[2] = { 0, 0 };
-    if (!nothing && c->num_nodes > 0)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        if (!c->d_nearest_stats) HIPCHK(c, hipMalloc(&c->d_nearest_stats.p, sizeof(got)));
-        HIPCHK(c, hipMemsetAsync(c->d_nearest_stats, 0, sizeof(got), c->stream));
-        NearestParams h = {};
-        h.points = d_points; h.max_dist = d_max_dist; h.num_points = num_points; h.k = k;
-        h.stats = c->d_nearest_stats;
-        h.nodes = c->d_nodes; h.tris = c->d_tris; h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound;
-        launch_nearest(h, c->stream);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(got, c->d_nearest_stats, sizeof(got), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    NearestParams h = {};
+    h.points = d_points; h.max_dist = d_max_dist; h.num_points = num_points; h.k = k;
+    if (const int rs = query_stats(c, nothing, c->d_nearest_stats, h, launch_nearest, got); rs != PTK_OK) return rs;
     if (node_visits) *node_visits = got[0];
     if (tri_tests) *tri_tests = got[1];
     return PTK_OK;

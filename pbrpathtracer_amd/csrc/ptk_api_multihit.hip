@@ -72,13 +72,6 @@ int ptk_multihit_rays(ptk_ctx* c, int32_t num_rays, const float* origins, const 
     return s.run([&] { return ptk_multihit_rays_device(c, num_rays, d_origins, d_dirs, d_tmax, max_hits, d_count, d_tri, d_t, d_bary, d_side); });
 }
 
-int ptk_last_multihit_ms(ptk_ctx* c, float* ms)
-{
-    if (!c) return PTK_ERR_BAD_ARG;
-    float t = 0.0f;
-    const int rc = c->ev_multihit.elapsed(c, 0, 1, &t);
-    if (ms) *ms = t;
-    return rc;
-}
+int ptk_last_multihit_ms(ptk_ctx* c, float* ms) { return last_ms(c, &ptk_ctx::ev_multihit, ms); }
 
 }  // extern "C"

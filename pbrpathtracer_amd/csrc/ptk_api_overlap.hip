@@ -18,27 +18,15 @@ static int check_overlap_args(ptk_ctx* c, const char* who, int32_t num, const vo
     return check_query_args(c, who, "query count", num, a, b, k > 0 ? (count || list) : count != nullptr, nothing, also);
 }
 
-// The call proper, on the context's stream, every pointer into this GPU's memory: h holds the queries and the outputs, the scene
-// half is filled in here.  One kernel between the two events; a scene without triangles has no tree to walk and gets its zeros and
-// -1s from fills.
+// The call proper (query_on_stream): h holds the queries and the outputs; the fills are the zeros and -1s
 static int overlap_on_stream(ptk_ctx* c, OverlapParams& h)
 {
-    c->ev_overlap.begin();
-    const size_t n = (size_t)h.num;
-    if (c->num_nodes == 0)
-    {
+    return query_on_stream(c, c->ev_overlap, h, launch_overlap, [&] {
+        const size_t n = (size_t)h.num;
         if (h.count) HIPCHK(c, hipMemsetAsync(h.count, 0, n * sizeof(int32_t), c->stream));
         if (h.list && h.k > 0) HIPCHK(c, hipMemsetAsync(h.list, 0xff, n * (size_t)h.k * sizeof(int32_t), c->stream));
-        return PTK_OK;
-    }
-    h.nodes = c->d_nodes; h.tris = c->d_tris;
-    h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound;
-    if (const int rc = c->ev_overlap.mark(c, 0, c->stream); rc != PTK_OK) return rc;
-    launch_overlap(h, c->stream);
-    HIPCHK(c, hipGetLastError());
-    if (const int rc = c->ev_overlap.mark(c, 1, c->stream); rc != PTK_OK) return rc;
-    c->ev_overlap.done();
-    return PTK_OK;
+        return (int)PTK_OK;
+    });
 }
 
 static int overlap_device(ptk_ctx* c, const char* who, int shape, int32_t num, const float* d_a, const float* d_b, const int32_t* d_tri_from, int32_t k,
@@ -95,14 +83,7 @@ int ptk_overlap_spheres(ptk_ctx* c, int32_t num, const float* centers, const flo
     return overlap_host(c, "ptk_overlap_spheres", OVERLAP_SPHERE, num, centers, radius, tri_from, k, count, tris);
 }
 
-int ptk_last_overlap_ms(ptk_ctx* c, float* ms)
-{
-    if (!c) return PTK_ERR_BAD_ARG;
-    float t = 0.0f;
-    const int rc = c->ev_overlap.elapsed(c, 0, 1, &t);
-    if (ms) *ms = t;
-    return rc;
-}
+int ptk_last_overlap_ms(ptk_ctx* c, float* ms) { return last_ms(c, &ptk_ctx::ev_overlap, ms); }
 
 int ptk_overlap_stats(ptk_ctx* c, int32_t shape, int32_t num, const float* d_a, const float* d_b, const int32_t* d_tri_from, uint64_t stats[4])
 {
@@ -111,20 +92,9 @@ int ptk_overlap_stats(ptk_ctx* c, int32_t shape, int32_t num, const float* d_a, 
                                     (shape != PTK_OVERLAP_BOX && shape != PTK_OVERLAP_SPHERE) ? "unknown shape" : nullptr);
     if (rc != PTK_OK) return rc;
     unsigned long long got[4] = { 0, 0, 0, 0 };
-    if (!nothing && c->num_nodes > 0)
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        if (!c->d_overlap_stats) HIPCHK(c, hipMalloc(&c->d_overlap_stats.p, sizeof(got)));
-        HIPCHK(c, hipMemsetAsync(c->d_overlap_stats, 0, sizeof(got), c->stream));
-        OverlapParams h = {};
-        h.qa = d_a; h.qb = d_b; h.tri_from = d_tri_from; h.num = num; h.shape = shape == PTK_OVERLAP_BOX ? OVERLAP_BOX : OVERLAP_SPHERE;
-        h.stats = c->d_overlap_stats;
-        h.nodes = c->d_nodes; h.tris = c->d_tris; h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound;
-        launch_overlap(h, c->stream);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(got, c->d_overlap_stats, sizeof(got), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    OverlapParams h = {};
+    h.qa = d_a; h.qb = d_b; h.tri_from = d_tri_from; h.num = num; h.shape = shape == PTK_OVERLAP_BOX ? OVERLAP_BOX : OVERLAP_SPHERE;
+    if (const int rs = query_stats(c, nothing, c->d_overlap_stats, h, launch_overlap, got); rs != PTK_OK) return rs;
     for (int j = 0; j < 4; j++) stats[j] = got[j];
     return PTK_OK;
 }

@@ -376,14 +376,7 @@ int ptk_occluded_rays(ptk_ctx* c, int32_t num_rays, const float* origins, const 
     return s.run([&] { return ptk_occluded_rays_device(c, num_rays, d_origins, d_dirs, d_tmax, sample, seed, key_base, d_occluded); });
 }
 
-int ptk_last_hits_ms(ptk_ctx* c, float* ms)
-{
-    if (!c) return PTK_ERR_BAD_ARG;
-    float t = 0.0f;
-    const int rc = c->ev_hits.elapsed(c, 0, 1, &t);
-    if (ms) *ms = t;
-    return rc;
-}
+int ptk_last_hits_ms(ptk_ctx* c, float* ms) { return last_ms(c, &ptk_ctx::ev_hits, ms); }
 
 static int check_rays_adaptive_args(ptk_ctx* c, int32_t num_rays, const float* origins, const float* dirs, float threshold, uint32_t min_spp, uint32_t step,
                                     uint32_t max_spp, uint32_t flags, const float* sum, const uint32_t* counts, bool* nothing)

@@ -1,7 +1,7 @@
 // The closest-point rule of include/ptk.h (ptk_closest_points: THE RULE) for one 48-byte record, whole: d2k, the barycentrics v, w and
-// the point q.  The operations and their order are closest_tri's (ptk_closest.hip), which keeps its own copy with its own accept
-// fused in and is left as it is; nearest_kernel (ptk_knearest.hip) has the rule from here alone - in its leaf arm for the key and in
-// its epilogue for v, w and q again.  To be compiled with -ffp-contract=off only: every operation is one IEEE float32 operation.
+// the point q.  The one statement of the rule in the library: closest_kernel (ptk_closest.hip) puts its accept behind it,
+// nearest_kernel (ptk_knearest.hip) takes the key from it in its leaf arm and v, w and q again in its epilogue, overlap_kernel
+// (ptk_overlap.hip) takes a sphere's d2k.  To be compiled with -ffp-contract=off only: every operation is one IEEE float32 operation.
 #pragma once
 
 #include "ptk_device_fn.h"

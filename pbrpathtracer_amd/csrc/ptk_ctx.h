@@ -432,6 +432,54 @@ int check_adaptive_args(ptk_ctx* c, const char* who, float threshold, uint32_t m
 // ... the argument checks of the ray, point and surface query entries (see there)
 int check_query_args(ptk_ctx* c, const char* who, const char* count_word, int32_t num, const void* a, const void* b, bool have_out, bool* nothing,
                      const char* also = nullptr);
+// ... and what the one-kernel query entries share beyond them.  The body of a ptk_last_*_ms over two events around the kernel:
+inline int last_ms(ptk_ctx* c, Timer<2> ptk_ctx::*ev, float* ms)
+{
+    if (!c) return PTK_ERR_BAD_ARG;
+    float t = 0.0f;
+    const int rc = (c->*ev).elapsed(c, 0, 1, &t);
+    if (ms) *ms = t;
+    return rc;
+}
+// The scene half of a point or region query's parameter block (ClosestParams, NearestParams, OverlapParams)
+template <class P>
+void query_scene(const ptk_ctx* c, P& h)
+{
+    h.nodes = c->d_nodes; h.tris = c->d_tris; h.num_nodes = c->num_nodes; h.scene_bound = c->scene_bound;
+}
+// Such a query proper, on the context's stream, every pointer into this GPU's memory: h holds the queries and the outputs, the scene
+// half is filled in here.  One kernel between the two events; a scene without triangles has no tree to walk and gets its misses
+// from fills() instead, untimed.
+template <class P, class FILLS>
+int query_on_stream(ptk_ctx* c, Timer<2>& ev, P& h, void (*launch)(const P&, hipStream_t), FILLS fills)
+{
+    ev.begin();
+    if (c->num_nodes == 0) return fills();
+    query_scene(c, h);
+    if (const int rc = ev.mark(c, 0, c->stream); rc != PTK_OK) return rc;
+    launch(h, c->stream);
+    HIPCHK(c, hipGetLastError());
+    if (const int rc = ev.mark(c, 1, c->stream); rc != PTK_OK) return rc;
+    ev.done();
+    return PTK_OK;
+}
+// ... and its counting call (ptk_*_stats): the N counters, made by the first call, cleared, added to by the kernel's STATS variant
+// and read back - one host wait.  got stays as it is when there are no queries (nothing) or no tree.
+template <class P, int N>
+int query_stats(ptk_ctx* c, bool nothing, Buf<unsigned long long>& d_stats, P& h, void (*launch)(const P&, hipStream_t), unsigned long long (&got)[N])
+{
+    if (nothing || c->num_nodes == 0) return PTK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!d_stats) HIPCHK(c, hipMalloc(&d_stats.p, sizeof(got)));
+    HIPCHK(c, hipMemsetAsync(d_stats, 0, sizeof(got), c->stream));
+    h.stats = d_stats;
+    query_scene(c, h);
+    launch(h, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(got, d_stats, sizeof(got), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PTK_OK;
+}
 struct RaysAdaptiveBuffers {
     float *origins, *dirs, *s2;
     uint32_t *keys, *src, *list, *keep, *counts, *block_counts, *total;

@@ -1,22 +1,16 @@
 // HIP kernel for gfx950 of K-nearest triangle queries (include/ptk.h ptk_nearest_triangles): for every caller point
-// the K triangles nearest to it, in order.  closest_kernel's walk (ptk_closest.hip: one-wave workgroups, one point per lane, the
+// the K triangles nearest to it, in order.  closest_kernel's walk (ptk_point_walk.h: one-wave workgroups, one point per lane, the
 // points staged through LDS, the per-lane LDS stack of links, a distance-ordered, distance-pruned descent of the 4-wide quantised BVH
 // under walk_step's push discipline) around multihit_kernel's list (ptk_multihit.hip: a bounded sorted list per lane in registers,
 // integer keys, its worst entry the bound once it is full, the lists leaving coalesced through the stack rows).  Compiled once, with
 // -ffp-contract=off: the triangle arm is the rule of ptk.h operation by operation (ptk_closest_rule.h; the numpy restatement is
 // tests/knearest_rule.py); the box arm is acceleration only, behind the slack derived in DESIGN.md §4.17.
-#include "ptk_device_fn.h"
-#include "ptk_closest.h"
+#include "ptk_point_walk.h"
 #include "ptk_closest_rule.h"
 #include "ptk_knearest.h"
 #include "ptk.h"
-#ifdef PTK_DEBUG
-#include <cassert>
-#endif
 
 namespace ptk {
-
-#define PTK_NEAREST_BLOCK 64        // one wave per workgroup, one point per lane
 
 // An entry's key: d2k (finite and >= +0, so its bits order as the floats do) above the triangle index - one unsigned 64-bit compare
 // is the rule's (d2k, index) order, and the only comparison the list ever makes.  A free slot is all ones: above every entry's key.
@@ -53,105 +47,37 @@ struct NearList {
     }
 };
 
-// closest_kernel's prune_bound: the squared box distance a child must exceed to be dropped, (sqrt(bound) * (1 + REL) + E)^2 rounded
-// up.  +inf while nothing bounds the query; a NaN (a non-finite point) drops nothing.
-__device__ __forceinline__ float nearest_prune_bound(float bound_d2, float E)
-{
-    const float thr = __builtin_fmaf(__builtin_amdgcn_sqrtf(bound_d2), 1.0f + PTK_CLOSEST_REL, E);
-    return thr * thr * (1.0f + 0x1p-20f);
-}
-
 // The K nearest triangles of every point, K <= KT.  Column c of a point's answer is the list's slot K - 1 - c.
 template <int KT, bool STATS>
-__global__ __launch_bounds__(PTK_NEAREST_BLOCK) void nearest_kernel(const NearestParams H)
+__global__ __launch_bounds__(PTK_QUERY_BLOCK) void nearest_kernel(const NearestParams H)
 {
-    __shared__ int lds_stack[PTK_STACK_ROWS * PTK_NEAREST_BLOCK];
+    __shared__ int lds_stack[PTK_STACK_ROWS * PTK_QUERY_BLOCK];
     static_assert(KT >= 1 && KT <= PTK_NEAREST_MAX_K, "the list holds at most PTK_NEAREST_MAX_K entries");
     const uint32_t lane = threadIdx.x;
-    const uint32_t p0 = blockIdx.x * (uint32_t)PTK_NEAREST_BLOCK;                   // < num_points <= 2^31 - 1
-    const uint32_t n = min((uint32_t)PTK_NEAREST_BLOCK, (uint32_t)H.num_points - p0);
-    const bool live = lane < n;
-    const uint32_t i = p0 + lane;
     int* const stack = lds_stack + lane;
-    float* const stage = (float*)lds_stack;
-    static_assert(PTK_STACK_ROWS >= 3, "the staging area is three rows of the stack");
     const int K = min(__builtin_amdgcn_readfirstlane(H.k), KT);                     // (the launcher's choice: K <= KT)
-
-    // The group's points are 3 n consecutive floats: consecutive lanes read consecutive floats, through the rows of the stack the
-    // walk does not use yet (closest_kernel's prologue).
-    {
-        const float* const gp = H.points + (size_t)p0 * 3;
-#pragma unroll
-        for (uint32_t k = 0; k < 3; k++)
-        {
-            const uint32_t e = lane + k * PTK_NEAREST_BLOCK;
-            if (e < n * 3u) stage[e] = gp[e];
-        }
-    }
-    __syncthreads();
-    const v3 p = live ? V(stage[lane * 3], stage[lane * 3 + 1], stage[lane * 3 + 2]) : V(0.0f, 0.0f, 0.0f);
-    __syncthreads();                                                                // the rows are the stack from here on
-
-    float md = __builtin_inff();
-    if (live && H.max_dist) md = H.max_dist[i];
-    const bool walks = live & (md > 0.0f);                                          // a NaN, zero or negative radius accepts nothing
+    v3 p;
+    const QueryGroup G = query_group(lds_stack, H.num_points, H.points, p);
+    float md;
+    const bool walks = query_bound(G, H.max_dist, md);                              // a NaN, zero or negative radius accepts nothing
     const float r2 = md * md;
     NearList<KT> L;
     L.clear();
-    // what box distances and triangle distances can disagree by for this point, in position units
-    const float E = (fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fabsf(p.z)) + H.scene_bound) * (PTK_CLOSEST_K * 0x1p-21f);
+    const float E = prune_slack(p, H.scene_bound);
     // the bound: r2 while the list has a free slot, the worst kept d2k afterwards.  It never grows: key[0] only falls, and below r2
-    float thr2 = nearest_prune_bound(r2, E);
+    float thr2 = prune_bound(r2, E);
 
     const float4* const nodes = uniform_ptr(H.nodes);
     const float4* const tris = uniform_ptr(H.tris);
     int node = walks ? 0 : NODE_EXIT;
     int* top = stack;
     uint32_t n_nodes = 0, n_tris = 0;
-    // the next deferred link, NODE_EXIT when there is none
-#define PTK_NEAREST_POP(into) { if (top == stack) into = NODE_EXIT; else { top -= PTK_NEAREST_BLOCK; into = *top; } }
     while (__ballot(node != NODE_EXIT))
     {
-        if (node >= 0)                                        // ---- one 4-wide interior node: closest_kernel's arm
+        if (node >= 0)                                        // ---- one 4-wide interior node
         {
             if (STATS) n_nodes++;
-            const float4* np = (const float4*)((const char*)nodes + (uint32_t)node * (uint32_t)(NODE_F4 * 16));
-            const float4 q0 = ldg4(np), q1 = ldg4(np + 1), q2 = ldg4(np + 2), q3 = ldg4(np + 3);
-            const uint32_t lox = __float_as_uint(q2.z), loy = __float_as_uint(q2.w), loz = __float_as_uint(q3.x);
-            const uint32_t hix = __float_as_uint(q3.y), hiy = __float_as_uint(q3.z), hiz = __float_as_uint(q3.w);
-            const int link0 = __float_as_int(q1.z), link1 = __float_as_int(q1.w), link2 = __float_as_int(q2.x), link3 = __float_as_int(q2.y);
-            // per child: plane = origin + q * scale; per axis the distance to the slab, max(lo - p, p - hi, 0); the order key is the
-            // squared box distance (>= 0, so its bits order as integers) with the slot in its low bits.  An empty slot has an
-            // inverted box, which says nothing about distance: its link does.  A child is dropped only when db2 > thr2: a box at
-            // exactly the worst kept distance may hold an equal d2k with a smaller index
-            int key[4];
-            bool in[4];
-#define PTK_NEAREST_CHILD(k, link)                                                                                                              \
-            {                                                                                                                                   \
-                const float lx = __builtin_fmaf((float)((lox >> (8 * k)) & 255u), q0.w, q0.x), hx = __builtin_fmaf((float)((hix >> (8 * k)) & 255u), q0.w, q0.x); \
-                const float ly = __builtin_fmaf((float)((loy >> (8 * k)) & 255u), q1.x, q0.y), hy = __builtin_fmaf((float)((hiy >> (8 * k)) & 255u), q1.x, q0.y); \
-                const float lz = __builtin_fmaf((float)((loz >> (8 * k)) & 255u), q1.y, q0.z), hz = __builtin_fmaf((float)((hiz >> (8 * k)) & 255u), q1.y, q0.z); \
-                const float dx = fmaxf(fmaxf(lx - p.x, p.x - hx), 0.0f), dy = fmaxf(fmaxf(ly - p.y, p.y - hy), 0.0f), dz = fmaxf(fmaxf(lz - p.z, p.z - hz), 0.0f); \
-                const float db2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));                                                      \
-                in[k] = ((link) != NODE_EXIT) & !(db2 > thr2);                                                                                  \
-                key[k] = in[k] ? ((__float_as_int(db2) & ~3) | k) : 0x7fffffff;                                                                 \
-            }
-            PTK_NEAREST_CHILD(0, link0) PTK_NEAREST_CHILD(1, link1) PTK_NEAREST_CHILD(2, link2) PTK_NEAREST_CHILD(3, link3)
-#undef PTK_NEAREST_CHILD
-            const int kmin = min(min(key[0], key[1]), min(key[2], key[3]));
-            const bool o0 = key[0] != kmin, o1 = key[1] != kmin, o2 = key[2] != kmin, o3 = key[3] != kmin;
-            int next = !o0 ? link0 : (!o1 ? link1 : (!o2 ? link2 : link3));
-            // walk_step's pushes: every link is written at the running top, which moves on only behind a link that stays - at most
-            // three per node, the nearest survivor being descended into: the discipline the builders' stack_need counts
-            *top = link0; top += (in[0] & o0) ? PTK_NEAREST_BLOCK : 0;
-            *top = link1; top += (in[1] & o1) ? PTK_NEAREST_BLOCK : 0;
-            *top = link2; top += (in[2] & o2) ? PTK_NEAREST_BLOCK : 0;
-            *top = link3; top += (in[3] & o3) ? PTK_NEAREST_BLOCK : 0;
-#ifdef PTK_DEBUG                                                // (make EXTRA=-DPTK_DEBUG: DESIGN.md §4.17)
-            assert(top - stack <= (PTK_STACK_ROWS - 1) * PTK_NEAREST_BLOCK);
-#endif
-            if (kmin == 0x7fffffff) PTK_NEAREST_POP(next)
-            node = next;
+            node = ordered_node_arm(nodes, node, p, thr2, stack, top);
         }
         else if (node != NODE_EXIT)                           // ---- a leaf: its 1 .. 8 records, then the next deferred link
         {
@@ -171,11 +97,10 @@ __global__ __launch_bounds__(PTK_NEAREST_BLOCK) void nearest_kernel(const Neares
             }
             if (STATS) n_tris += count;
             // behind a leaf that changed key[0] of a full list, the bound is the d2k there (a free key[0] leaves the bound at r2)
-            if ((L.key[0] != before) & (L.key[0] != PTK_NEAREST_FREE)) thr2 = nearest_prune_bound(__uint_as_float((uint32_t)(L.key[0] >> 32)), E);
-            PTK_NEAREST_POP(node)
+            if ((L.key[0] != before) & (L.key[0] != PTK_NEAREST_FREE)) thr2 = prune_bound(__uint_as_float((uint32_t)(L.key[0] >> 32)), E);
+            node = pop_link(stack, top);
         }
     }
-#undef PTK_NEAREST_POP
 
     if (STATS)
     {
@@ -190,35 +115,35 @@ __global__ __launch_bounds__(PTK_NEAREST_BLOCK) void nearest_kernel(const Neares
     static_assert(PTK_STACK_ROWS >= 2 * PTK_NEAREST_MAX_K, "a group's bary, 2 x 64 x 16 words, passes through the stack rows");
     static_assert(2 * PTK_STACK_ROWS >= 3 * PTK_NEAREST_MAX_K, "half a group's points, 3 x 32 x 16 words, pass through the stack rows");
     uint32_t* const out = (uint32_t*)lds_stack;
-    const uint32_t nk = n * (uint32_t)K;
-    const size_t at = (size_t)p0 * (uint32_t)K;
+    const uint32_t nk = G.n * (uint32_t)K;
+    const size_t at = (size_t)G.first * (uint32_t)K;
     const uint32_t mine = lane * (uint32_t)K;
     int cnt = 0;
 #pragma unroll
     for (int j = 0; j < KT; j++) cnt += (j < K && L.key[j] != PTK_NEAREST_FREE) ? 1 : 0;
-    if (H.count && live) H.count[i] = cnt;
+    if (H.count && G.live) H.count[G.i] = cnt;
     if (H.tri)
     {
         __syncthreads();                                                            // every lane's stack is done
 #pragma unroll
         for (int j = 0; j < KT; j++)
-            if (j < K && live) out[mine + (uint32_t)(K - 1 - j)] = (uint32_t)L.key[j];      // (a free key's low word is -1)
+            if (j < K && G.live) out[mine + (uint32_t)(K - 1 - j)] = (uint32_t)L.key[j];      // (a free key's low word is -1)
         __syncthreads();
-        for (uint32_t e = lane; e < nk; e += PTK_NEAREST_BLOCK) H.tri[at + e] = (int32_t)out[e];
+        for (uint32_t e = lane; e < nk; e += PTK_QUERY_BLOCK) H.tri[at + e] = (int32_t)out[e];
     }
     if (H.dist)
     {
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < KT; j++)
-            if (j < K && live)
+            if (j < K && G.live)
             {
                 const bool kept = L.key[j] != PTK_NEAREST_FREE;
                 const float d = kept ? sqrt_ieee(__uint_as_float((uint32_t)(L.key[j] >> 32))) : __builtin_inff();
                 out[mine + (uint32_t)(K - 1 - j)] = __float_as_uint(d);
             }
         __syncthreads();
-        for (uint32_t e = lane; e < nk; e += PTK_NEAREST_BLOCK) H.dist[at + e] = __uint_as_float(out[e]);
+        for (uint32_t e = lane; e < nk; e += PTK_QUERY_BLOCK) H.dist[at + e] = __uint_as_float(out[e]);
     }
     // v, w and q once more, from the records the entries name: closest_rule again, so the bits the walk decided on
     if (H.bary)
@@ -226,7 +151,7 @@ __global__ __launch_bounds__(PTK_NEAREST_BLOCK) void nearest_kernel(const Neares
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < KT; j++)
-            if (j < K && live)
+            if (j < K && G.live)
             {
                 float v = 0.0f, w = 0.0f;
                 if (L.key[j] != PTK_NEAREST_FREE)
@@ -239,7 +164,7 @@ __global__ __launch_bounds__(PTK_NEAREST_BLOCK) void nearest_kernel(const Neares
                 out[o] = __float_as_uint(v); out[o + 1] = __float_as_uint(w);
             }
         __syncthreads();
-        for (uint32_t e = lane; e < 2u * nk; e += PTK_NEAREST_BLOCK) H.bary[2 * at + e] = __uint_as_float(out[e]);
+        for (uint32_t e = lane; e < 2u * nk; e += PTK_QUERY_BLOCK) H.bary[2 * at + e] = __uint_as_float(out[e]);
     }
     if (H.point)
     {
@@ -247,9 +172,9 @@ __global__ __launch_bounds__(PTK_NEAREST_BLOCK) void nearest_kernel(const Neares
 #pragma unroll
         for (uint32_t half = 0; half < 2; half++)
         {
-            const uint32_t base = half * (PTK_NEAREST_BLOCK / 2);
-            const bool here = live & (lane >= base) & (lane < base + PTK_NEAREST_BLOCK / 2);
-            const uint32_t nh = n > base ? min(n - base, (uint32_t)(PTK_NEAREST_BLOCK / 2)) : 0u;
+            const uint32_t base = half * (PTK_QUERY_BLOCK / 2);
+            const bool here = G.live & (lane >= base) & (lane < base + PTK_QUERY_BLOCK / 2);
+            const uint32_t nh = G.n > base ? min(G.n - base, (uint32_t)(PTK_QUERY_BLOCK / 2)) : 0u;
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < KT; j++)
@@ -266,7 +191,7 @@ __global__ __launch_bounds__(PTK_NEAREST_BLOCK) void nearest_kernel(const Neares
                 }
             __syncthreads();
             float* const gq = H.point + 3 * (at + (size_t)base * (uint32_t)K);
-            for (uint32_t e = lane; e < 3u * nh * (uint32_t)K; e += PTK_NEAREST_BLOCK) gq[e] = __uint_as_float(out[e]);
+            for (uint32_t e = lane; e < 3u * nh * (uint32_t)K; e += PTK_QUERY_BLOCK) gq[e] = __uint_as_float(out[e]);
         }
     }
 }
@@ -274,7 +199,7 @@ __global__ __launch_bounds__(PTK_NEAREST_BLOCK) void nearest_kernel(const Neares
 template <int KT>
 static void launch_list(const NearestParams& h, const dim3 grid, hipStream_t stream)
 {
-    const dim3 block(PTK_NEAREST_BLOCK);
+    const dim3 block(PTK_QUERY_BLOCK);
     if (h.stats) hipLaunchKernelGGL((nearest_kernel<KT, true>), grid, block, 0, stream, h);
     else hipLaunchKernelGGL((nearest_kernel<KT, false>), grid, block, 0, stream, h);
 }
@@ -282,7 +207,7 @@ static void launch_list(const NearestParams& h, const dim3 grid, hipStream_t str
 void launch_nearest(const NearestParams& h, hipStream_t stream)
 {
     if (h.num_points <= 0 || h.num_nodes <= 0 || h.k < 1 || h.k > PTK_NEAREST_MAX_K) return;
-    const dim3 grid((unsigned)(((size_t)h.num_points + PTK_NEAREST_BLOCK - 1) / PTK_NEAREST_BLOCK));
+    const dim3 grid((unsigned)(((size_t)h.num_points + PTK_QUERY_BLOCK - 1) / PTK_QUERY_BLOCK));
     if (h.k <= 1) launch_list<1>(h, grid, stream);
     else if (h.k <= 4) launch_list<4>(h, grid, stream);
     else launch_list<16>(h, grid, stream);

@@ -6,11 +6,9 @@
 
 namespace ptk {
 
-// The prune's slack: a child is dropped by a box query only when its decoded box lies beyond the query box by more
-// than PTK_OVERLAP_K * 2^-21 * (max |lo, hi| + scene_bound) on some axis; by a sphere query only when its box distance exceeds
-// r * (1 + PTK_OVERLAP_REL) + the same slack around the centre (ptk_closest.h's numbers: the sphere rule is the closest rule's d2k).
-#define PTK_OVERLAP_K 2.0f
-#define PTK_OVERLAP_REL 0x1p-19f
+// The prune's slack is ptk_closest.h's, PTK_CLOSEST_K and PTK_CLOSEST_REL: a child is dropped by a box query only
+// when its decoded box lies beyond the query box by more than K * 2^-21 * (max |lo, hi| + scene_bound) on some axis; by a sphere
+// query only when its box distance exceeds r * (1 + REL) + the same slack around the centre (the sphere rule is the closest rule's d2k).
 
 enum { OVERLAP_BOX = 0, OVERLAP_SPHERE = 1 };
 

@@ -2,8 +2,8 @@
 // the group's origins and directions staged through the stack rows of LDS, and each lane's walk to its end - the walk of
 // rays_kernel (ptk_rays.hip) with everything but the walk taken out: the per-lane LDS stack of links, one node record in flight
 // across iterations, the triangle arm voted by the wave.  The step is walk_step_with (ptk_device_fn.h); a query kind is its
-// triangle arm.  NOT on this header: closest_kernel (ptk_closest.hip), which stages its points the same way in text of its own -
-// through query_group its machine code changes, and its walker is another algorithm (DESIGN.md §4.24 "The walk").
+// triangle arm.  The point and region queries (ptk_closest.hip, ptk_knearest.hip, ptk_overlap.hip) have the prologue from here -
+// query_group, query_bound - and walks of another kind from ptk_point_walk.h (DESIGN.md §4.24 "The walk").
 #pragma once
 #include "ptk_device_fn.h"
 

@@ -1,6 +1,8 @@
 """The one-wave ray queries on the shared prologue and walk (csrc/ptk_query_walk.h) as the compiler lowers them: the kernels of
-csrc/ptk_crossings.hip and csrc/ptk_hits.hip (csrc/Makefile).  No device: one `hipcc -S` per unit with the Makefile's
-own command line (taken from `make -n`), as tests/test_multihit_isa_cpu.py does for the multi-hit unit.
+csrc/ptk_crossings.hip and csrc/ptk_hits.hip (csrc/Makefile), and closest_kernel's two instantiations
+(csrc/ptk_closest.hip), which have the prologue from there and their node arm from csrc/ptk_point_walk.h.  No device: one
+`hipcc -S` per unit with the Makefile's own command line (taken from `make -n`), as tests/test_multihit_isa_cpu.py does for the
+multi-hit unit.
 
 The prologue borrows rows of the traversal stack for staging and the walk's callable triangle arm must fold into the kernel: a
 lambda capture the compiler could not resolve, or staging memory of the prologue's own, would still give a correct library.  So every
@@ -16,7 +18,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pbrpathtracer_amd", "csrc")
-UNITS = {"ptk_crossings": ("crossings_kernel", "contains_kernel"), "ptk_hits": ("hits_kernel", "occluded_kernel")}
+# (closest_kernel<STATS> by its mangled names: one template's two instantiations)
+UNITS = {"ptk_crossings": ("crossings_kernel", "contains_kernel"), "ptk_hits": ("hits_kernel", "occluded_kernel"),
+         "ptk_closest": ("closest_kernelILb0EEE", "closest_kernelILb1EEE")}
 KERNELS = [(u, k) for u, ks in UNITS.items() for k in ks]
 
 
