@@ -340,6 +340,14 @@ public:
     // ... and the sampling table in force (ptk_surface_info): the sum of the quantised weights, the exponent E, the triangles that
     // can be drawn and the largest weight; each may be null
     bool SurfaceInfo(uint64_t* total, int32_t* exponent, int32_t* drawable, float* max_weight);
+    // Extension: surface attribute queries (include/ptk.h ptk_surface_attributes, host arrays, synchronous): what is AT the surface
+    // points (tri[i], bary[i] = u, v) the queries above answer with - material: 1 per query; uv, gloss: 2; position, normal_geom,
+    // normal, albedo, emission: 3; opacity: 1; each may be null, but not all.  dirs (3 per query, may be null): the direction each
+    // point is seen along; the shading normal is flipped against it.  A triangle index outside the scene - a missed ray's -1 - gives
+    // material -1 and zeros.  Valid after BuildBVH() with no resolution set; pending material and geometry edits apply as for
+    // TraceRays; the image and the sample count are not touched.
+    bool SurfaceAttributes(int num, const int32_t* tri, const float* bary, const float* dirs, int32_t* material, float* uv, float* position,
+                           float* normal_geom, float* normal, float* albedo, float* emission, float* gloss, float* opacity);
     // Extensions: lightmap baking (include/ptk.h ptk_bake_lightmap / ptk_bake_coverage / ptk_lightmap_dilate, host arrays,
     // synchronous) at the class's seed and trace depth.  uvs: [triangles][6] chart corners, or null for the scene's own uvs;
     // out: width*height*3 floats, rows bottom-up; owner (may be null): width*height triangle indices, -1 uncovered;

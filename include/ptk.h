@@ -786,6 +786,87 @@ int ptk_surface_info(ptk_ctx* ctx, uint64_t* total, int32_t* exponent /*E*/, int
  * its table build (0 where it built none) and its kernel; waits for the call */
 int ptk_last_surface_ms(ptk_ctx* ctx, float* table_ms, float* sample_ms);
 
+/* ---- surface attributes: the shading data at (triangle, bary) pairs (no counterpart in the reference) ------------------------------
+ * ptk_intersect_rays, ptk_multihit_rays, ptk_closest_points, ptk_nearest_triangles, ptk_sample_surface and ptk_bake_coverage all
+ * answer with a surface point named by (triangle, u, v).  This call tells what is AT such points: the join between the geometry
+ * queries and the material system, for guides of a denoiser where there is no camera (a panorama, a lightmap), coloured point clouds,
+ * shading in the caller's own code.  No BVH is walked, no random number drawn.
+ * THE RULE, every operation one IEEE float32 operation in the order written, none contracted.  Query i has tri[i] (int32),
+ * bary[i] = (u, v) - the weights of the triangle's second and third vertex, as every query above returns them - and, optionally,
+ * dirs[i], the direction the point is seen along.
+ * A query is a MISS when tri < 0 or tri >= the scene's triangle count - the -1 of a missed ray included, so the outputs of the other
+ * queries can be passed unfiltered.  A miss reads no scene memory and gives material -1 and 0 in every float output.
+ * u, v are used as given: no clamp and no validity test, values outside the triangle extrapolate, a NaN propagates.
+ * With w = (1 - u) - v, the records of the triangle as staged (uv1..3, n1..3, tbn = face normal | tangent | bitangent) and of its
+ * material M = materials[material[tri]] (tex[0..5] = diffuse, normal, emissive, roughness, reflectiveness, opacity map; tex2d is the
+ * product's nearest-texel fetch), one output array per attribute, n * channels elements of 4 bytes:
+ *   id name         type   value
+ *    0 MATERIAL     i32    material[tri]
+ *    1 UV           f32x2  GetUV: uv.x = (w * uv1.x + u * uv2.x) + v * uv3.x, uv.y likewise - the form of the triangle test's opacity
+ *                          lookup and of the feature planes; computed whether or not the material binds a map
+ *    2 POSITION     f32x3  (v1 * w + v2 * u) + v3 * v per component, from the RESIDENT vertices: it follows ptk_update_geometry.  A
+ *                          definition of its own: NOT bit-equal to a ray's ro + rd * t (the POSITION feature plane), nor to
+ *                          ptk_sample_surface's position, whose first weight is 1 - su and not (1 - w1) - w2
+ *    3 NORMAL_GEOM  f32x3  the staged face normal tbn[tri][0:3], not flipped
+ *    4 NORMAL       f32x3  n = the face normal; where the triangle's smoothing bit is set n = normalize((n1 * w + n2 * u) + n3 * v);
+ *                          where M binds a normal map: c = tex2d(tex[1], uv), t = c.rgb * 2 - 1, t.z = 0.00001 where t.z <= 0,
+ *                          t = normalize(t), n = normalize((tangent * t.x + bitangent * t.y) + n * t.z) (pathtracer.cpp:556-566).
+ *                          With dirs: n = -n where (n.x * d.x + n.y * d.y) + n.z * d.z > 0 - the direction is used as given, only
+ *                          the sign counts, a NaN does not flip.  Without dirs: not flipped.
+ *                          normalize(a) = a * (1 / sqrtf((a.x a.x + a.y a.y) + a.z a.z))
+ *    5 ALBEDO       f32x3  M's diffuse colour, or tex2d(tex[0], uv).rgb where a diffuse map is bound
+ *    6 EMISSION     f32x3  (M's emissive colour, or tex2d(tex[2], uv).rgb) * emissive_intensity
+ *    7 GLOSS        f32x2  roughness or tex2d(tex[3], uv).r, reflectiveness or tex2d(tex[4], uv).r
+ *    8 OPACITY      f32    tex2d(tex[5], uv).r - the value the triangle test compares its opacity draw with - or 1 where M binds
+ *                          no opacity map
+ * THE CONTRACT.  For any ray (ro, rd) whose hit (tri, u, v) comes from ptk_intersect_rays or from the TRIANGLE and BARY feature
+ * planes, MATERIAL, NORMAL_GEOM, NORMAL (given dirs = rd), ALBEDO, EMISSION and GLOSS are bit for bit what ptk_render_features
+ * writes for that pixel: both kernels call one device function (csrc/ptk_surface_attrs.h; tests/test_gpu_surface_attr.py:
+ * array_equal with the planes and with the numpy restatement tests/surface_attr_rule.py).
+ * A query's result depends on its own inputs and the resident scene only: not on how the array is cut into calls, on which outputs
+ * are requested, on "flat", the tree or ptk_set_tile, nor on whether the geometry got there by
+ * ptk_upload_scene or by ptk_update_geometry.  Edits made with ptk_update_materials are seen by the next call.
+ *   ptk_surface_attributes: host arrays, synchronous; the queries and the requested outputs are staged in device memory for the
+ *     length of the call.
+ *   ptk_surface_attributes_device: every array in memory of this context's GPU, asynchronous on the context's stream (the caller's
+ *     after ptk_set_stream); no host wait and no allocation of device memory inside the call.  d_bary, uv and gloss must be 8-byte
+ *     aligned (PTK_ERR_BAD_ARG otherwise: two floats travel as one access), the other arrays as their element type.  The arrays
+ *     must stay allocated until the stream has passed the call.
+ * `out` names the outputs: any pointer may be NULL - that attribute is not computed, and the records only it needs are not read -
+ * but not all nine (PTK_ERR_BAD_ARG "no output array").  dirs may be NULL.  n == 0 is PTK_OK and does nothing; PTK_ERR_BAD_ARG
+ * without a scene, for n < 0 and for a null tri or bary with n > 0; a refused call leaves the outputs alone.  The calls need a scene
+ * only - no camera, no frame -, touch neither the accumulator, the sample count, the feature planes nor any other state, and
+ * ptk_request_exit does not cut them.  Limits: one thread per query, in one launch. */
+#define PTK_ATTR_MATERIAL 0
+#define PTK_ATTR_UV 1
+#define PTK_ATTR_POSITION 2
+#define PTK_ATTR_NORMAL_GEOM 3
+#define PTK_ATTR_NORMAL 4
+#define PTK_ATTR_ALBEDO 5
+#define PTK_ATTR_EMISSION 6
+#define PTK_ATTR_GLOSS 7
+#define PTK_ATTR_OPACITY 8
+#define PTK_ATTR_COUNT 9
+typedef struct ptk_surface_attrs {      /* one pointer per attribute, in id order; NULL = not computed */
+    int32_t* material;      /* [n]    */
+    float* uv;              /* [n][2] */
+    float* position;        /* [n][3] */
+    float* normal_geom;     /* [n][3] */
+    float* normal;          /* [n][3] */
+    float* albedo;          /* [n][3] */
+    float* emission;        /* [n][3] */
+    float* gloss;           /* [n][2] */
+    float* opacity;         /* [n]    */
+} ptk_surface_attrs;
+int ptk_attribute_info(int attr, int* channels, int* is_int);      /* host-only, no device needed */
+int ptk_surface_attributes(ptk_ctx* ctx, int32_t n, const int32_t* tri /*[n]*/, const float* bary /*[n][2]*/,
+                           const float* dirs /*[n][3] or NULL*/, const ptk_surface_attrs* out);
+int ptk_surface_attributes_device(ptk_ctx* ctx, int32_t n, const int32_t* d_tri, const float* d_bary, const float* d_dirs,
+                                  const ptk_surface_attrs* out /* host struct of device pointers */);
+/* measurement hook (tools/attributes_timing.py), not part of the feature: the HIP-event time of the last call's kernel; waits for
+ * the call */
+int ptk_last_attributes_ms(ptk_ctx* ctx, float* ms);
+
 /* ---- a-trous denoiser for image planes and for the frame (no counterpart in the reference) ------------------------------------
  * Turns a noisy low-sample image - a frame of a few samples per pixel, a lightmap of 16 to 64 per texel - into a usable one: an
  * edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by normals, positions and luminance, optionally by the

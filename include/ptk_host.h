@@ -136,6 +136,10 @@ int  pth_sample_surface(pth_tracer* t, int num_samples, uint32_t key_base, uint3
                         float* normal, int32_t* material);
 int  pth_set_surface_weights(pth_tracer* t, const float* weights);
 int  pth_surface_info(pth_tracer* t, uint64_t* total, int32_t* exponent, int32_t* drawable, float* max_weight);
+/* SurfaceAttributes (the shading data at (triangle, bary) pairs, include/ptk.h ptk_surface_attributes): 1 on success; dirs and any
+ * output but one may be NULL */
+int  pth_surface_attributes(pth_tracer* t, int num, const int32_t* tri, const float* bary, const float* dirs, int32_t* material, float* uv,
+                            float* position, float* normal_geom, float* normal, float* albedo, float* emission, float* gloss, float* opacity);
 /* BakeLightmap / BakeCoverage / DilateLightmap (lightmap baking, include/ptk.h ptk_bake_lightmap with the tracer's seed and trace
  * depth): 1 on success */
 int  pth_bake_lightmap(pth_tracer* t, int width, int height, const float* uvs, float offset, uint32_t first_sample, uint32_t spp,

@@ -1168,6 +1168,20 @@ bool PathTracer::SampleSurface(int num_samples, uint32_t key_base, uint32_t samp
     return rc == PTK_OK;
 }
 
+// What is at (triangle, bary) pairs of the scene's surface (ptk_surface_attributes), on the scene as the next RenderFrame() would see it
+bool PathTracer::SurfaceAttributes(int num, const int32_t* tri, const float* bary, const float* dirs, int32_t* material, float* uv,
+                                   float* position, float* normal_geom, float* normal, float* albedo, float* emission, float* gloss,
+                                   float* opacity)
+{
+    if (!m->scene_uploaded || !m->ensure_ctx()) return false;
+    std::lock_guard<std::mutex> render_guard(m->render_mu);
+    if (!apply_scene_edits(m)) return false;
+    const ptk_surface_attrs out = { material, uv, position, normal_geom, normal, albedo, emission, gloss, opacity };
+    const int rc = ptk_surface_attributes(m->ctx, num, tri, bary, dirs, &out);
+    m->note(rc);
+    return rc == PTK_OK;
+}
+
 bool PathTracer::SetSurfaceWeights(const float* weights)
 {
     if (!m->scene_uploaded || !m->ensure_ctx()) return false;

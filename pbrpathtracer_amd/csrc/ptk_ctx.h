@@ -225,6 +225,9 @@ struct ptk_ctx {
     ptk::Timer<2> ev_surf_table, ev_surface;
     int opt_surface_variant = 1;                 // surface_sample_kernel's variant (ptk_surface.h; 1: the coarse table in LDS): speed only
 
+    // surface attribute queries (ptk_surface_attributes): two events around the last call's kernel, made by the first call
+    ptk::Timer<2> ev_attributes;
+
     // a-trous denoiser (ptk_denoise_planes, ptk_denoise_frame): the four packed float4 images of a call (64 B per pixel, grown to the
     // largest call so far); the denoised frame [H][W][3], made by the first ptk_denoise_frame, freed with the feature planes, and
     // the resolution it was last written at; four events of the last call: before the pack, behind it, behind the filter, behind

@@ -4,6 +4,7 @@
 // operation of the exact trace kernel.
 #include "ptk_device_fn.h"
 #include "ptk_features.h"
+#include "ptk_surface_attrs.h"
 
 namespace ptk {
 
@@ -71,78 +72,17 @@ __global__ __launch_bounds__(PTK_BLOCK) void features_kernel(const RenderParams 
         F.position[o * 3] = p.x; F.position[o * 3 + 1] = p.y; F.position[o * 3 + 2] = p.z;
     }
     if (!(F.material || F.normal_geom || F.normal || F.albedo || F.emission || F.gloss)) return;
-    int matid = -1;
-    v3 ng = V(0.0f, 0.0f, 0.0f), n = ng, albedo = ng, emission = ng;
-    float roughness = 0.0f, reflectiveness = 0.0f;
-    if (hit)
-    {
-        const float4* sp4 = P.shade + (size_t)h.tri * SHADE_F4;
-        const float4 s0 = ldg4(sp4);
-        const int mbits = __float_as_int(s0.w);
-        matid = mbits & 0x7fffffff;
-        ng = V(s0.x, s0.y, s0.z);
-        if (F.normal || F.albedo || F.emission || F.gloss)
-        {
-            const float4* mp = P.mats + (size_t)matid * MAT_F4;
-            const float4 m4f = ldg4(mp + 4), m5f = ldg4(mp + 5);
-            const int tex_diffuse = __float_as_int(m4f.x), tex_normal = __float_as_int(m4f.y);
-            const int tex_emiss = __float_as_int(m4f.z), tex_rough = __float_as_int(m4f.w);
-            const int tex_metal = __float_as_int(m5f.x);
-            float uvx = 0.0f, uvy = 0.0f;
-            if (__float_as_int(m5f.z) != 0)             // some map is bound
-            {
-                const float4 s1 = ldg4(sp4 + 1), s2 = ldg4(sp4 + 2);
-                const float w = 1.0f - h.u - h.v;       // GetUV :533-536
-                uvx = w * s1.x + h.u * s1.z + h.v * s2.x;
-                uvy = w * s1.y + h.u * s1.w + h.v * s2.y;
-            }
-            if (F.normal)
-            {
-                n = ng;
-                if (mbits < 0)                          // :556, GetSmoothNormal :538-543
-                {
-                    const float4 s2 = ldg4(sp4 + 2), s3 = ldg4(sp4 + 3), s4 = ldg4(sp4 + 4);
-                    const float w = 1.0f - h.u - h.v;
-                    const v3 n1 = V(s2.z, s2.w, s3.x), n2 = V(s3.y, s3.z, s3.w), n3 = V(s4.x, s4.y, s4.z);
-                    n = normalize(add(add(muls(n1, w), muls(n2, h.u)), muls(n3, h.v)));
-                }
-                if (tex_normal >= 0)                    // :558-566
-                {
-                    const float4 s4 = ldg4(sp4 + 4), s5 = ldg4(sp4 + 5), s6 = ldg4(sp4 + 6);
-                    const float4 c = tex2d(P, tex_normal, uvx, uvy);
-                    v3 nt = V(c.x * 2.0f - 1.0f, c.y * 2.0f - 1.0f, c.z * 2.0f - 1.0f);
-                    if (nt.z <= 0.0f) nt = V(nt.x, nt.y, PTK_EPS);
-                    nt = normalize(nt);
-                    const v3 tg = V(s4.w, s5.x, s5.y), bt = V(s5.z, s5.w, s6.x);
-                    const v3 m = V(tg.x * nt.x + bt.x * nt.y + n.x * nt.z,
-                                   tg.y * nt.x + bt.y * nt.y + n.y * nt.z,
-                                   tg.z * nt.x + bt.z * nt.y + n.z * nt.z);
-                    n = normalize(m);
-                }
-                if (dot(n, rd) > 0.0f) n = neg(n);      // :567-568
-            }
-            if (F.albedo)
-            {
-                const float4 m0 = ldg4(mp);
-                albedo = V(m0.x, m0.y, m0.z);
-                if (tex_diffuse >= 0) { const float4 c = tex2d(P, tex_diffuse, uvx, uvy); albedo = V(c.x, c.y, c.z); }
-            }
-            if (F.emission)
-            {
-                const float4 m1 = ldg4(mp + 1), m2 = ldg4(mp + 2);
-                v3 emiss = V(m2.x, m2.y, m2.z);
-                if (tex_emiss >= 0) { const float4 c = tex2d(P, tex_emiss, uvx, uvy); emiss = V(c.x, c.y, c.z); }
-                emission = muls(emiss, m1.w);
-            }
-            if (F.gloss)
-            {
-                roughness = ldg4(mp + 2).w;
-                if (tex_rough >= 0) roughness = tex2d_r(P, tex_rough, uvx, uvy);
-                reflectiveness = ldg4(mp + 3).x;
-                if (tex_metal >= 0) reflectiveness = tex2d_r(P, tex_metal, uvx, uvy);
-            }
-        }
-    }
+    // the surface quantities: the one statement of them (ptk_surface_attrs.h), shared with attributes_kernel
+    const uint32_t want = (F.material ? SA_MATERIAL : 0u) | (F.normal_geom ? SA_NORMAL_GEOM : 0u) | (F.normal ? SA_NORMAL : 0u) |
+                          (F.albedo ? SA_ALBEDO : 0u) | (F.emission ? SA_EMISSION : 0u) | (F.gloss ? SA_GLOSS : 0u);
+    SurfaceAttrs A;
+    A.material = -1;
+    A.ng = A.n = A.albedo = A.emission = V(0.0f, 0.0f, 0.0f);
+    A.roughness = A.reflectiveness = 0.0f;
+    if (hit) surface_attrs(P, h.tri, h.u, h.v, true, rd, want, A);
+    const int matid = A.material;
+    const v3 ng = A.ng, n = A.n, albedo = A.albedo, emission = A.emission;
+    const float roughness = A.roughness, reflectiveness = A.reflectiveness;
     if (F.material) F.material[o] = matid;
     if (F.normal_geom) { F.normal_geom[o * 3] = ng.x; F.normal_geom[o * 3 + 1] = ng.y; F.normal_geom[o * 3 + 2] = ng.z; }
     if (F.normal) { F.normal[o * 3] = n.x; F.normal[o * 3 + 1] = n.y; F.normal[o * 3 + 2] = n.z; }

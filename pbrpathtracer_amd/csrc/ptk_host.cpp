@@ -216,6 +216,11 @@ int pth_surface_info(pth_tracer* t, uint64_t* total, int32_t* exponent, int32_t*
 {
     return t->pt.SurfaceInfo(total, exponent, drawable, max_weight) ? 1 : 0;
 }
+int pth_surface_attributes(pth_tracer* t, int num, const int32_t* tri, const float* bary, const float* dirs, int32_t* material, float* uv,
+                           float* position, float* normal_geom, float* normal, float* albedo, float* emission, float* gloss, float* opacity)
+{
+    return t->pt.SurfaceAttributes(num, tri, bary, dirs, material, uv, position, normal_geom, normal, albedo, emission, gloss, opacity) ? 1 : 0;
+}
 int pth_contains_points(pth_tracer* t, int num_points, const float* points, int num_dirs, const float* dirs, int mode, uint8_t* inside, int32_t* winding)
 {
     return t->pt.ContainsPoints(num_points, points, num_dirs, dirs, mode, inside, winding) ? 1 : 0;

@@ -53,6 +53,19 @@ def grid_atlas(num_tris: int, width: int, height: int, gutter: int = 1) -> np.nd
     return np.ascontiguousarray(uv, np.float32)
 
 
+def guides(ctx, owner, bary):
+    """(albedo, normal) [H, W, 3] float32 each: the diffuse colour after its texture and the shading normal - smoothed, normal-mapped,
+    not flipped - at every covered texel of a coverage (Context.bake_coverage's owner [H, W] and bary [H, W, 2]), 0 where owner is
+    -1: one Context.surface_attributes call (include/ptk.h ptk_surface_attributes).  What denoise takes as `normals` and `albedo=`
+    in place of the owner's face normal and no albedo.  ctx: a Context or a PathTracer.  numpy in, numpy out."""
+    from . import ptk
+    owner = np.ascontiguousarray(owner, np.int32)
+    h, w = owner.shape
+    at = ctx.surface_attributes(owner.reshape(-1), np.ascontiguousarray(bary, np.float32).reshape(-1, 2), None,
+                                1 << ptk.ATTR_ALBEDO | 1 << ptk.ATTR_NORMAL)
+    return at["albedo"].reshape(h, w, 3), at["normal"].reshape(h, w, 3)
+
+
 def denoise(ctx, image, owner, pos, normals, params=None, albedo=None, variance=None, want_variance: bool = False):
     """The a-trous denoiser (include/ptk.h ptk_denoise_planes, Context.denoise_planes) over a baked lightmap: image [H, W, 3] - the
     mean, sums / spp -, owner [H, W] int32 as the mask (uncovered texels, -1, keep their bits and take no part), pos [H, W, 3] from

@@ -40,7 +40,7 @@ HOST_SYMBOLS = [
     "pth_bake_probe_visibility", "pth_sample_probes_visible",
     "pth_trace_rays_adaptive", "pth_bake_lightmap_adaptive", "pth_intersect_rays", "pth_occluded_rays", "pth_closest_points", "pth_overlap_boxes", "pth_overlap_spheres",
     "pth_crossings_rays", "pth_contains_points", "pth_signed_distance", "pth_multihit_rays", "pth_nearest_triangles",
-    "pth_sample_surface", "pth_set_surface_weights", "pth_surface_info",
+    "pth_sample_surface", "pth_set_surface_weights", "pth_surface_info", "pth_surface_attributes",
     "pth_denoise_frame", "pth_read_denoised", "pth_resolve_denoised", "pth_temporal_frame", "pth_read_temporal", "pth_get_view",
     "pth_track_motion", "pth_temporal_frame_moving", "pth_read_motion", "pth_temporal_frame_moments", "pth_temporal_variance",
     "pth_read_temporal_variance", "pth_denoise_temporal", "pth_get_object_transform",
@@ -126,6 +126,7 @@ def _bind_locked(L) -> C.CDLL:
         L.pth_multihit_rays.restype = i32; L.pth_multihit_rays.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
         L.pth_nearest_triangles.restype = i32; L.pth_nearest_triangles.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
         L.pth_sample_surface.restype = i32; L.pth_sample_surface.argtypes = [vp, i32, u32, u32, vp, vp, vp, vp, vp]
+        L.pth_surface_attributes.restype = i32; L.pth_surface_attributes.argtypes = [vp, i32] + [vp] * 12
         L.pth_set_surface_weights.restype = i32; L.pth_set_surface_weights.argtypes = [vp, vp]
         L.pth_surface_info.restype = i32; L.pth_surface_info.argtypes = [vp, vp, vp, vp, vp]
         L.pth_contains_points.restype = i32; L.pth_contains_points.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp]
@@ -770,6 +771,28 @@ class PathTracer:
         return total.value, e.value, dr.value, np.float32(m.value)
 
     SampleSurface, SetSurfaceWeights, SurfaceInfo = sample_surface, set_surface_weights, surface_info
+
+    def surface_attributes(self, tri, bary, dirs=None, want=_ptk.ATTR_ALL):
+        """Extension: dict name (ptk.ATTR_NAMES) -> array of what is at the surface points (tri[i], bary[i] = u, v): material, uv,
+        position, normal_geom, normal (flipped against dirs[i] where dirs is given), albedo, emission, gloss, opacity
+        (include/ptk.h ptk_surface_attributes).  want: bit k = attribute k.  A triangle index outside the scene gives material -1
+        and zeros.  Pending material and geometry edits apply as for RenderFrame()."""
+        want = int(want) & _ptk.ATTR_ALL
+        if not want:
+            raise _ptk.PtkError("SurfaceAttributes: no output array")
+        t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1)
+        n = len(t)
+        b = np.ascontiguousarray(bary, dtype=np.float32).reshape(-1, 2)
+        assert len(b) == n, "one (u, v) per triangle index"
+        d = None if dirs is None else np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        assert d is None or len(d) == n, "one direction per query"
+        out = {nm: _ptk.attribute_array(k, n) for k, nm in enumerate(_ptk.ATTR_NAMES) if want >> k & 1}
+        ptrs = [out[nm].ctypes.data if nm in out else None for nm in _ptk.ATTR_NAMES]
+        if n and not self.L.pth_surface_attributes(self.h, n, t.ctypes.data, b.ctypes.data, d.ctypes.data if d is not None else None, *ptrs):
+            raise _ptk.PtkError("SurfaceAttributes failed: " + self.LastError())
+        return out
+
+    SurfaceAttributes = surface_attributes
 
     def _chart_uvs(self, uvs):
         if uvs is None:

@@ -144,6 +144,11 @@ class ReprojectDesc(C.Structure):
                                              "out_color", "out_count", "out_moments")])
 
 
+class SurfaceAttrs(C.Structure):
+    """ptk_surface_attrs: one pointer per attribute in id order, null = not computed"""
+    _fields_ = [(k, C.c_void_p) for k in ("material", "uv", "position", "normal_geom", "normal", "albedo", "emission", "gloss", "opacity")]
+
+
 class PtkError(RuntimeError):
     pass
 
@@ -177,6 +182,7 @@ SYMBOLS = [
     "ptk_nearest_triangles", "ptk_nearest_triangles_device", "ptk_last_nearest_ms", "ptk_nearest_stats",
     "ptk_surface_weights", "ptk_surface_weights_device", "ptk_sample_surface", "ptk_sample_surface_device", "ptk_surface_info",
     "ptk_last_surface_ms", "ptk_probe_surface_table", "ptk_probe_scan_u64",
+    "ptk_attribute_info", "ptk_surface_attributes", "ptk_surface_attributes_device", "ptk_last_attributes_ms",
     "ptk_denoise_planes", "ptk_denoise_planes_device", "ptk_denoise_frame", "ptk_read_denoised", "ptk_denoised_device_ptr",
     "ptk_resolve_denoised_rgb8", "ptk_last_denoise_ms",
     "ptk_get_view", "ptk_reproject_planes", "ptk_reproject_planes_device", "ptk_temporal_frame", "ptk_read_temporal",
@@ -332,6 +338,10 @@ def _load_locked() -> C.CDLL:
         L.ptk_last_surface_ms.argtypes = [vp, fp, fp]
         L.ptk_probe_surface_table.argtypes = [vp, vp]
         L.ptk_probe_scan_u64.argtypes = [vp, C.c_int32, vp, vp, C.c_int32]
+        L.ptk_attribute_info.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
+        for fn in (L.ptk_surface_attributes, L.ptk_surface_attributes_device):
+            fn.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(SurfaceAttrs)]
+        L.ptk_last_attributes_ms.argtypes = [vp, fp]
         for fn in (L.ptk_denoise_planes, L.ptk_denoise_planes_device):
             fn.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp, vp]
         L.ptk_denoise_frame.argtypes = [vp, C.POINTER(DenoiseParams), u32]
@@ -578,6 +588,26 @@ def feature_array(feature: int, width: int, height: int) -> np.ndarray:
     """An empty host array of a feature plane's shape and type: [H, W] or [H, W, c], float32 or int32."""
     ch, isint = feature_info(feature)
     return np.empty((height, width) if ch == 1 else (height, width, ch), np.int32 if isint else np.float32)
+
+
+# surface attributes (ptk_surface_attributes): ids, and their names in id order
+(ATTR_MATERIAL, ATTR_UV, ATTR_POSITION, ATTR_NORMAL_GEOM, ATTR_NORMAL, ATTR_ALBEDO, ATTR_EMISSION, ATTR_GLOSS, ATTR_OPACITY) = range(9)
+ATTR_NAMES = ("material", "uv", "position", "normal_geom", "normal", "albedo", "emission", "gloss", "opacity")
+ATTR_ALL = (1 << len(ATTR_NAMES)) - 1
+
+
+def attribute_info(attr: int):
+    """(channels, is_int) of a surface attribute (ptk_attribute_info; no device needed); raises for an unknown id."""
+    ch = C.c_int(0); isint = C.c_int(0)
+    if load().ptk_attribute_info(int(attr), C.byref(ch), C.byref(isint)) != PTK_OK:
+        raise PtkError(f"ptk_attribute_info: unknown attribute {attr}")
+    return ch.value, bool(isint.value)
+
+
+def attribute_array(attr: int, n: int) -> np.ndarray:
+    """An empty host array of a surface attribute's shape and type for n queries: [n] or [n, c], float32 or int32."""
+    ch, isint = attribute_info(attr)
+    return np.empty((n,) if ch == 1 else (n, ch), np.int32 if isint else np.float32)
 
 
 def scene_is_plain(arrays: dict) -> bool:
@@ -1312,6 +1342,56 @@ class Context:
         out = np.empty_like(v)
         self._chk(self.L.ptk_probe_scan_u64(self.h, len(v), v.ctypes.data, out.ctypes.data, int(items_per_workgroup)), "ptk_probe_scan_u64")
         return out
+
+    # ---- surface attributes -------------------------------------------------------------------
+    def surface_attributes(self, tri, bary, dirs=None, want=ATTR_ALL):
+        """ptk_surface_attributes: dict name (ATTR_NAMES) -> array of what is AT the surface points (tri[i], bary[i] = u, v) - tri
+        [n] int32, bary [n, 2] float32, as intersect_rays, closest_points, sample_surface, bake_coverage ... return them - under the
+        rule of include/ptk.h: material [n] int32; uv, gloss [n, 2]; position, normal_geom, normal, albedo, emission [n, 3]; opacity
+        [n] float32.  A triangle index outside the scene (a missed ray's -1) gives material -1 and zeros.  dirs [n, 3] float32 or
+        None: the direction each point is seen along, against which the shading normal is flipped.  want: bit k = attribute k; only
+        those are computed and returned.  numpy in, numpy out through the host entry; torch tensors on the context's GPU in, torch
+        out through ptk_surface_attributes_device with no host copy, written on the context's stream."""
+        want = int(want) & ATTR_ALL
+        if not want:
+            raise PtkError("ptk_surface_attributes: no output array")
+        ids = [k for k in range(len(ATTR_NAMES)) if want >> k & 1]
+        if hasattr(tri, "data_ptr"):
+            import torch
+            n = tri.numel()
+            self._ray_tensors((tri, bary), n, ((torch.int32, 1), (torch.float32, 2)))
+            if dirs is not None:
+                self._ray_tensors((dirs,), n, ((torch.float32, 3),))
+            out = {}
+            for k in ids:
+                ch, isint = attribute_info(k)
+                out[ATTR_NAMES[k]] = torch.empty((n,) if ch == 1 else (n, ch), dtype=torch.int32 if isint else torch.float32, device=tri.device)
+            if n:
+                block = SurfaceAttrs(**{nm: t.data_ptr() for nm, t in out.items()})
+                self._chk(self.L.ptk_surface_attributes_device(self.h, n, C.c_void_p(tri.data_ptr()), C.c_void_p(bary.data_ptr()),
+                                                               C.c_void_p(dirs.data_ptr()) if dirs is not None else None, C.byref(block)),
+                          "ptk_surface_attributes_device")
+            return out
+        t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1)
+        n = len(t)
+        b = np.ascontiguousarray(bary, dtype=np.float32).reshape(-1, 2)
+        assert len(b) == n, "one (u, v) per triangle index"
+        d = None
+        if dirs is not None:
+            d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+            assert len(d) == n, "one direction per query"
+        out = {ATTR_NAMES[k]: attribute_array(k, n) for k in ids}
+        if n:
+            block = SurfaceAttrs(**{nm: a.ctypes.data for nm, a in out.items()})
+            self._chk(self.L.ptk_surface_attributes(self.h, n, t.ctypes.data, b.ctypes.data, d.ctypes.data if d is not None else None,
+                                                    C.byref(block)), "ptk_surface_attributes")
+        return out
+
+    def last_attributes_ms(self) -> float:
+        """HIP-event time of the last surface_attributes call's kernel; waits for it."""
+        t = C.c_float(0)
+        self._chk(self.L.ptk_last_attributes_ms(self.h, C.byref(t)), "ptk_last_attributes_ms")
+        return t.value
 
     # ---- a-trous denoiser --------------------------------------------------------------------
     def denoise_planes(self, color, mask, normal, position, params, albedo=None, variance=None, want_variance: bool = False):

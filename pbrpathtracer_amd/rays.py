@@ -1,7 +1,8 @@
 """Ray sets for Context.trace_rays / PathTracer.TraceRays (include/ptk.h ptk_trace_rays): camera models the library's own
 perspective camera does not cover, as plain (origins, directions) arrays - and for Context.intersect_rays / occluded_rays
 (ptk_intersect_rays, ptk_occluded_rays): segments between point pairs and ambient occlusion - and, over Context.multihit_rays
-(ptk_multihit_rays), the length of a ray inside the geometry and the surfaces between two points.  Host only but for the
+(ptk_multihit_rays), the length of a ray inside the geometry and the surfaces between two points - and, over
+Context.surface_attributes (ptk_surface_attributes), the guide planes of a denoiser for any ray set.  Host only but for the
 functions that take a context, which run their rays through it."""
 from __future__ import annotations
 
@@ -31,6 +32,20 @@ def equirect_rays(pos, dir, up, width: int, height: int):
     dirs = np.ascontiguousarray(d.reshape(-1, 3), np.float32)
     origins = np.ascontiguousarray(np.broadcast_to(np.asarray(pos, np.float64), dirs.shape), np.float32)
     return origins, dirs
+
+
+def hit_guides(ctx, origins, dirs, sample: int = 0, seed: int = 0):
+    """What the rays (origins[i], dirs[i]) see, as a perspective frame's first-hit feature planes give it for the one camera: dict of
+    id [n] int32 (the triangle, -1 on a miss), depth [n] float32 (t, inf on a miss), position, normal, albedo, emission [n, 3] float32
+    (0 on a miss) - one Context.intersect_rays call (the opacity draws of sample `sample` of `seed`) and one
+    Context.surface_attributes call over its tri and bary with the rays' directions, so normal is the shading normal turned towards
+    the ray's origin.  The guides of Context.denoise_planes for an image traced along these rays (mask = id): a panorama
+    (equirect_rays), a fisheye, probes' views.  numpy arrays in and out."""
+    from . import ptk
+    tri, t, bary, _ = ctx.intersect_rays(origins, dirs, sample=sample, seed=seed)
+    want = 1 << ptk.ATTR_POSITION | 1 << ptk.ATTR_NORMAL | 1 << ptk.ATTR_ALBEDO | 1 << ptk.ATTR_EMISSION
+    at = ctx.surface_attributes(tri, bary, dirs, want)
+    return dict(id=tri, depth=t, position=at["position"], normal=at["normal"], albedo=at["albedo"], emission=at["emission"])
 
 
 def segment_rays(a, b):

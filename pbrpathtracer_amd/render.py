@@ -10,8 +10,8 @@
     python -m pbrpathtracer_amd.render scene.pts ... --display {linear,reinhard,aces} [--exposure auto|EV] [--key K] [--adapt A]
                                                  [--linear-transfer]
     python -m pbrpathtracer_amd.render scene.pts --features planes.npz
-    python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 -o pano.png [--npy pano.npy]
-    python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz [--layers K]
+    python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --spp 64 [--denoise] -o pano.png [--npy pano.npy]
+    python -m pbrpathtracer_amd.render scene.pts --equirect 2048 --hits planes.npz [--layers K] [--attributes]
     python -m pbrpathtracer_amd.render scene.pts --distance-field 64 64 64 [--df-max-dist M] [--signed [--inside-mode parity]] -o field.npz
     python -m pbrpathtracer_amd.render scene.pts --distance-field 64 64 64 --nearest 4 [--df-max-dist M] -o nearest.npz
     python -m pbrpathtracer_amd.render scene.pts --voxelize 64 64 64 [--solid] -o grid.npz
@@ -36,7 +36,10 @@ With --denoise the PNG is the frame after the a-trous denoiser (include/ptk.h pt
 ptk.denoise_defaults for the scene's extent; --denoise-iterations overrides the 5 iterations), guided by the first-hit normal,
 position and albedo planes - after an adaptive render (--noise-threshold) also by each pixel's variance - and --npy FILE.npy holds
 the denoised float32 image [H, W, 3], rows top-down like the PNG.  With --bake-lightmap it filters the baked mean over the covered
-texels (lightmap.denoise) before --dilate pads the charts.
+texels (lightmap.denoise, guided by the texels' positions and shading normals and demodulated by their albedo: lightmap.guides,
+include/ptk.h ptk_surface_attributes) before --dilate pads the charts.  With --equirect it filters the panorama's sums over the
+samples (Context.denoise_planes), guided by what the panorama's rays hit (rays.hit_guides: ptk_intersect_rays, then
+ptk_surface_attributes for position, shading normal and albedo); --npy then holds the filtered sums.
 
 With --orbit FRAMES the loaded camera is turned about the vertical axis through the centre of the scene's bounds, by --orbit-degrees
 in FRAMES equal steps - an interactive session's camera drag.  At each step the image is reset and --spp samples are rendered; with
@@ -63,7 +66,9 @@ PathTracer.TraceRays (include/ptk.h ptk_trace_rays; rays.equirect_rays) instead 
 
 With --equirect WIDTH --hits FILE.npz nothing is traced and no image written: the .npz holds what the panorama's rays hit
 (PathTracer.IntersectRays, include/ptk.h ptk_intersect_rays, sample 0) - depth, triangle, material [H, W] and bary [H, W, 2], rows
-top-down - a depth panorama; --spp is not needed.  With --layers K (1 .. 16) the .npz also holds the first K surfaces along each
+top-down - a depth panorama; --spp is not needed.  With --attributes the .npz also holds what is at the hits
+(PathTracer.SurfaceAttributes, include/ptk.h ptk_surface_attributes): normal - the shading normal, towards the camera -, albedo
+and emission [H, W, 3]; the other arrays are what they are without it.  With --layers K (1 .. 16) the .npz also holds the first K surfaces along each
 ray in order (PathTracer.MultiHitRays, include/ptk.h ptk_multihit_rays - geometry only, opacity maps take no part): layer_t and
 layer_tri [K, H, W] (+inf and -1 behind a ray's last surface) and layer_count [H, W]; the other arrays are what they are without it.
 
@@ -71,7 +76,8 @@ With --point-cloud N no image is written: the .npz holds N points of the scene's
 (PathTracer.SampleSurface, include/ptk.h ptk_sample_surface, sample 0 of --seed), each traced with --spp samples along the lightmap
 bake's ray - from the point lifted by --offset along its face normal (default: 1e-3 of the scene extent), against the normal -
 through surface.bake_points: position, normal [N, 3] float32, triangle, material [N] int32 and radiance [N, 3] float32, the sum over
-the samples.  A bake that needs neither vertices nor a uv layout.
+the samples - and the points' albedo, shading_normal and emission [N, 3] float32 (ptk_surface_attributes).  A bake that needs
+neither vertices nor a uv layout.
 
 With --bake-lightmap SIZE the image is a SIZE x SIZE lightmap (include/ptk.h ptk_bake_lightmap): per texel of the scene's own uv
 layout - or, with --bake-atlas, of lightmap.grid_atlas, one chart per triangle - the radiance leaving the surface along its normal,
@@ -123,7 +129,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--min-spp", type=int, default=None, help="adaptive: samples before the first test (default: 2 x step)")
     ap.add_argument("--step", type=int, default=8, help="adaptive: samples per round (default 8)")
     ap.add_argument("--denoise", action="store_true",
-                    help="filter the frame (or, with --bake-lightmap, the lightmap) with the a-trous denoiser before it is written; "
+                    help="filter the frame (or, with --bake-lightmap, the lightmap; with --equirect, the panorama) with the a-trous denoiser before it is written; "
                          "with --noise-threshold the frame's filter is variance-guided")
     ap.add_argument("--denoise-iterations", type=int, default=None, metavar="K", help="--denoise: a-trous iterations, 1..8 (default 5)")
     ap.add_argument("--display", choices=("linear", "reinhard", "aces"), default=None,
@@ -164,6 +170,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--layers", type=int, metavar="K", default=None,
                     help="--hits: also write the first K (1 .. 16) surfaces along each ray in order: layer_t, layer_tri [K, H, W] "
                          "and layer_count [H, W]")
+    ap.add_argument("--attributes", action="store_true",
+                    help="--hits: also write what is at the hits: normal (the shading normal, towards the camera), albedo and "
+                         "emission [H, W, 3]")
     ap.add_argument("--bake-lightmap", type=int, metavar="SIZE", default=None,
                     help="bake a SIZE x SIZE lightmap over the scene's uvs instead of rendering a view; the PNG holds the mean "
                          "(sum / spp) resolved like a frame, rows top-down; --npy the float32 sums [SIZE, SIZE, 3], rows bottom-up as baked")
@@ -265,13 +274,14 @@ def denoise_params(pt, a, variance=False):
 
 
 def denoise_lightmap(pt, a, mean, owner, size, uvs):
-    """--bake-lightmap --denoise: lightmap.denoise over the covered texels, guided by their positions and face normals"""
-    from .lightmap import denoise
-    _, _, pos = pt.BakeCoverage(size, size, uvs=uvs)
-    normals = np.asarray(pt.StagedScene()["tbn"], np.float32).reshape(-1, 9)[:, 0:3]
+    """--bake-lightmap --denoise: lightmap.denoise over the covered texels, guided by their positions and shading normals and
+    demodulated by their albedo (lightmap.guides)"""
+    from .lightmap import denoise, guides
+    cover_owner, bary, pos = pt.BakeCoverage(size, size, uvs=uvs)
+    albedo, normals = guides(pt, cover_owner, bary)
     if a.bake_back:
         normals = -normals
-    return denoise(pt.context(), np.ascontiguousarray(mean, np.float32), owner, pos, normals, params=denoise_params(pt, a))
+    return denoise(pt.context(), np.ascontiguousarray(mean, np.float32), owner, pos, normals, params=denoise_params(pt, a), albedo=albedo)
 
 
 def render_lightmap(pt, a) -> int:
@@ -439,7 +449,8 @@ def render_voxels(pt, a) -> int:
 
 
 class _TracerSurface:
-    """surface.bake_points' view of a PathTracer: sample_surface and trace_rays at the tracer's own seed and trace depth"""
+    """surface.bake_points' and rays.hit_guides' view of a PathTracer: sample_surface, trace_rays, intersect_rays and
+    surface_attributes at the tracer's own seed and trace depth"""
 
     def __init__(self, pt):
         self.pt = pt
@@ -449,6 +460,12 @@ class _TracerSurface:
 
     def trace_rays(self, origins, dirs, max_depth, first_sample, spp, seed, key_base=0, out=None):
         return self.pt.TraceRays(origins, dirs, first_sample, spp, key_base=key_base, out=out)
+
+    def intersect_rays(self, origins, dirs, sample=0, seed=0, key_base=0):
+        return self.pt.IntersectRays(origins, dirs, sample, key_base=key_base)
+
+    def surface_attributes(self, tri, bary, dirs=None, want=None):
+        return self.pt.SurfaceAttributes(tri, bary, dirs) if want is None else self.pt.SurfaceAttributes(tri, bary, dirs, want)
 
 
 def render_point_cloud(pt, a) -> int:
@@ -462,11 +479,12 @@ def render_point_cloud(pt, a) -> int:
         return 1
     offset = a.offset if a.offset is not None else bake_offset(pt)
     t1 = time.time()
-    position, normal, tri, material, radiance = surface.bake_points(_TracerSurface(pt), a.point_cloud, a.spp, offset, pt.GetTraceDepth(), seed=a.seed)
+    position, normal, tri, material, radiance, at = surface.bake_points(_TracerSurface(pt), a.point_cloud, a.spp, offset, pt.GetTraceDepth(),
+                                                                        seed=a.seed, attributes=True)
     t2 = time.time()
     with open(a.out, "wb") as f:                # (np.savez would append .npz to another suffix)
         np.savez(f, position=position, normal=normal, triangle=tri, material=material, radiance=radiance, spp=np.int32(a.spp),
-                 offset=np.float32(offset))
+                 offset=np.float32(offset), albedo=at["albedo"], shading_normal=at["normal"], emission=at["emission"])
     print(f"{a.scene}: {pt.GetTriangleCount()} triangles, {a.point_cloud} surface points, {a.spp} spp, depth {pt.GetTraceDepth()}: "
           f"{t2 - t1:.3f} s -> {a.out}")
     return 0
@@ -475,8 +493,9 @@ def render_point_cloud(pt, a) -> int:
 def render_equirect(pt, a) -> int:
     """The panorama: one TraceRays call over the pixel centres' rays, mean = sum / spp resolved to 8 bits by the frame's own rule
     (pathtracer.cpp:802-812: clamped to [0, 1], NaN to 0, x * 255 truncated)."""
+    from . import ptk
     from .pathtracer import export_png
-    from .rays import equirect_rays
+    from .rays import equirect_rays, hit_guides
     w, h = a.equirect, a.equirect // 2
     if h < 1 or a.spp < 1:
         print("error: --equirect needs a width of at least 2 and --spp of at least 1", file=sys.stderr)
@@ -486,6 +505,9 @@ def render_equirect(pt, a) -> int:
     if a.hits:
         tri, t, bary, material = pt.IntersectRays(origins, dirs)
         planes = dict(depth=t.reshape(h, w), triangle=tri.reshape(h, w), material=material.reshape(h, w), bary=bary.reshape(h, w, 2))
+        if a.attributes:
+            at = pt.SurfaceAttributes(tri, bary, dirs, 1 << ptk.ATTR_NORMAL | 1 << ptk.ATTR_ALBEDO | 1 << ptk.ATTR_EMISSION)
+            planes.update(normal=at["normal"].reshape(h, w, 3), albedo=at["albedo"].reshape(h, w, 3), emission=at["emission"].reshape(h, w, 3))
         if a.layers is not None:
             count, ltri, lt, _, _ = pt.MultiHitRays(origins, dirs, a.layers)
             planes.update(layer_t=np.ascontiguousarray(lt.T).reshape(a.layers, h, w),
@@ -509,6 +531,11 @@ def render_equirect(pt, a) -> int:
               f"({res['ray_samples'] / (w * h * a.spp):.3f}), {res['rounds']} rounds, {res['active_rays']} rays still active")
         return 0
     total = pt.TraceRays(origins, dirs, 0, a.spp).reshape(h, w, 3)
+    if a.denoise:
+        # the sums over the samples through the a-trous filter, guided by what the panorama's rays hit (rays.hit_guides)
+        g = hit_guides(_TracerSurface(pt), origins, dirs)
+        total = pt.context().denoise_planes(np.ascontiguousarray(total), g["id"].reshape(h, w), g["normal"].reshape(h, w, 3),
+                                            g["position"].reshape(h, w, 3), denoise_params(pt, a), albedo=g["albedo"].reshape(h, w, 3))
     t2 = time.time()
     with np.errstate(all="ignore"):
         x = total / np.float32(a.spp)
@@ -665,14 +692,17 @@ def main(argv=None):
     if a.denoise_iterations is not None and not (a.denoise and 1 <= a.denoise_iterations <= 8):
         print("error: --denoise-iterations goes with --denoise and needs a count in 1..8", file=sys.stderr)
         return 1
-    if a.denoise and (a.bake_probes is not None or a.distance_field is not None or a.equirect is not None):
-        print("error: --denoise filters a perspective frame or a --bake-lightmap", file=sys.stderr)
+    if a.denoise and (a.bake_probes is not None or a.distance_field is not None):
+        print("error: --denoise filters a perspective frame, an --equirect panorama or a --bake-lightmap", file=sys.stderr)
         return 1
     if a.bake_probes is None and (a.probe_visibility is not None or a.probe_max_dist is not None):
         print("error: --probe-visibility and --probe-max-dist go with --bake-probes", file=sys.stderr)
         return 1
     if a.layers is not None and not (a.equirect is not None and a.hits and 1 <= a.layers <= 16):
         print("error: --layers goes with --equirect --hits and needs a count in 1..16", file=sys.stderr)
+        return 1
+    if a.attributes and not (a.equirect is not None and a.hits):
+        print("error: --attributes goes with --equirect --hits", file=sys.stderr)
         return 1
     if a.temporal and a.orbit is None:
         print("error: --temporal goes with --orbit", file=sys.stderr)

@@ -1,5 +1,6 @@
 """Worked uses of surface sampling (include/ptk.h ptk_sample_surface): weight tables for
-Context.set_surface_weights, and a bake at sampled surface points that needs neither vertices nor a uv layout."""
+Context.set_surface_weights, and a bake at sampled surface points that needs neither vertices nor a uv layout - with the
+points' colour, shading normal and emission where asked for (ptk_surface_attributes)."""
 from __future__ import annotations
 
 import numpy as np
@@ -50,13 +51,20 @@ def bake_rays(position, normal, offset):
     return p + lift, -n
 
 
-def bake_points(ctx, n, spp, offset, max_depth, seed=0, first_sample=0, key_base=0, out=None):
+def bake_points(ctx, n, spp, offset, max_depth, seed=0, first_sample=0, key_base=0, out=None, attributes=False):
     """A bake without a uv layout: n surface points (ctx.sample_surface at `seed`, `key_base`, sample 0), each traced with
     ctx.trace_rays along bake_rays - the radiance leaving the surface along its normal, as a lightmap texel gathers it - over samples
     [first_sample, first_sample + spp) with the sampling's key_base, so point j and ray j share RNG pixel key_base + j.  Returns
     (position [n, 3], normal [n, 3] float32, tri [n], material [n] int32, radiance [n, 3] float32: the sum over the samples).  out:
-    the radiance of earlier samples of the same points, added to in place - a progressive bake equals one long bake."""
-    tri, _, position, normal, material = ctx.sample_surface(n, seed=seed, key_base=key_base, sample=0)
+    the radiance of earlier samples of the same points, added to in place - a progressive bake equals one long bake.
+    attributes=True: a sixth element, the dict of ctx.surface_attributes (include/ptk.h ptk_surface_attributes) at the points with
+    albedo, normal (the shading normal, not flipped) and emission [n, 3] float32 - a coloured point cloud; the five others keep their
+    bits."""
+    tri, bary, position, normal, material = ctx.sample_surface(n, seed=seed, key_base=key_base, sample=0)
     origins, dirs = bake_rays(position, normal, offset)
     radiance = ctx.trace_rays(origins, dirs, max_depth, first_sample, spp, seed, key_base=key_base, out=out)
-    return position, normal, tri, material, radiance
+    if not attributes:
+        return position, normal, tri, material, radiance
+    from . import ptk
+    at = ctx.surface_attributes(tri, bary, None, 1 << ptk.ATTR_ALBEDO | 1 << ptk.ATTR_NORMAL | 1 << ptk.ATTR_EMISSION)
+    return position, normal, tri, material, radiance, at
